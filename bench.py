@@ -5,6 +5,7 @@ SNPs, 1 chromosome of 100 Mb, uniform recombination map (2001 rows, 5e-4/row), m
     python bench.py [--gpus N --steps K --warmup W]             (N > 1: starts its own N rank processes, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 2 --migration-rate 0.01              (BASELINE config 3: two populations exchanging 1 % per generation)
+    python bench.py ... --dump-outputs DIR                      (also writes the last timed step's A/D, sexes and seed state as DIR/*.npy)
 
 One process per GPU; each rank advances its OWN population of the full config-2 size (weak scaling: populations shard across
 GPUs); no data-path collective is needed without migration.  A step = one generation in the reference's
@@ -146,6 +147,25 @@ def cpu_baseline_reference(args):
                       f"of the SNP count); host has {os.cpu_count()} cores, 1 used (the reference is single threaded)"}
 
 
+def dump_outputs(out_dir, last, rank=None, max_bytes=64_000_000):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as float64 .npy files.  Past max_bytes in all
+    (several million individuals) the per-individual arrays are cut to a fixed, seeded sample of individuals, whose positions
+    are written as individual_index.npy.  With several ranks each writes its own population's files with a _rank<r> suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_ind = {"additive": last["ad"][0], "dominance": last["ad"][1], "sex": last.get("sex")}      # (sex: None after a host-loop migration)
+    per_ind = {k: np.asarray(v, dtype=np.float64) for k, v in per_ind.items() if v is not None}
+    n = len(per_ind["additive"])
+    row_bytes = sum(v[0].nbytes if n else 8 for v in per_ind.values()) + 8
+    if n * row_bytes > max_bytes:
+        keep = np.sort(np.random.default_rng(20240601).choice(n, size=max_bytes // row_bytes, replace=False))
+        per_ind = dict({k: v[keep] for k, v in per_ind.items()}, individual_index=keep.astype(np.float64))
+    scalars = {"seed_reproduce": last["seed_reproduce"], "glob_state": last.get("glob_state")}      # (glob_state: --mating device only)
+    arrays = dict(per_ind, **{k: np.array([v], dtype=np.float64) for k, v in scalars.items() if v is not None})
+    sfx = "" if rank is None else f"_rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
 def launch_ranks(n):
     """One worker process per GPU (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in its environment, the same contract as
     torch.distributed.run), started from a parent that has not touched the GPU.  Rank 0's stdout is this process's stdout.
@@ -208,7 +228,11 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true", help="--mating host only: mate, then gev_reproduce, strictly one after the other (default: the host forms the next couples between gev_reproduce_begin and _end)")
     ap.add_argument("--isolated-steps", type=int, default=3, help="extra untimed generations without stream overlap for roofline.isolated")
     ap.add_argument("--sustained-steps", type=int, default=300, help="generations run after the timed region for the sustained_300 block (0: none; default config and one GPU only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (A/D, sexes, seed state) as DIR/<name>.npy, "
+                    "to compare two builds output for output (the inputs are seeded: the same arguments give the same inputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` as typed: no rendezvous environment yet -> this process becomes the launcher.  It starts one
     # fresh worker process per GPU BEFORE any GPU call is made here (it never imports torch) and relays rank 0's JSON line.
@@ -320,6 +344,7 @@ def main():
         raise SystemExit("--migration-rate needs --mating device (the library mates on the sexes that travel with the migrants)")
     pipeline = presample and not migrate and not args.no_pipeline
     state = {}
+    last = {}                                                  # what the most recent step returned to its caller (--dump-outputs)
     call_ms = {}                                               # host time inside each library call of the pipelined loop, summed
 
     def step_pipelined(i):
@@ -347,7 +372,8 @@ def main():
         sim.sex[P] = sex_new
         sim.last_seed_reproduce = int(sd[0])
         t3 = time.perf_counter()
-        sim.ras_compute_AD(P, i + 1)                             # Simulation::ras_compute_AD
+        last["ad"] = sim.ras_compute_AD(P, i + 1)                # Simulation::ras_compute_AD
+        last["sex"], last["seed_reproduce"] = sex_new, int(sd[0])
         seeds[i + 2], dms = fut.result()
         seed_ms.append(dms)
         t4 = time.perf_counter()
@@ -379,6 +405,7 @@ def main():
         r = ctx.generation_end(want_couples=False, want_sex=True)
         t2 = time.perf_counter()
         sim.glob.x = int(r["glob_state"]); sim.sex[P] = r["sex"]; sim.last_seed_reproduce = int(r["seed_reproduce"])
+        last["sex"], last["seed_reproduce"], last["glob_state"] = r["sex"], int(r["seed_reproduce"]), int(r["glob_state"])
         state["begun"] = False
         if overlap_host and not migrate:
             # no selection: the next generation needs nothing the host derives from this one's A/D, so it is handed over at once and
@@ -388,7 +415,7 @@ def main():
             tb += time.perf_counter() - tb0
             state["begun"] = True
         ta = time.perf_counter()
-        sim.ras_compute_AD(P, i + 1)                             # the generation's A/D (computed inside the generation, copied out here)
+        last["ad"] = sim.ras_compute_AD(P, i + 1)                # the generation's A/D (computed inside the generation, copied out here)
         t3 = time.perf_counter()
         if migrate:
             do_migration(t3)
@@ -414,7 +441,8 @@ def main():
         if presample:                                                            # ... handed over at once: the GPU samples while the host mates
             sim.presample(P, seeds[i + 1], args.n_ind)
         t2 = time.perf_counter()
-        sim.ras_compute_AD(P, i + 1)                                             # Simulation::ras_compute_AD
+        last["ad"] = sim.ras_compute_AD(P, i + 1)                                # Simulation::ras_compute_AD
+        last["sex"], last["seed_reproduce"] = sim.sex[P], sim.last_seed_reproduce
         t3 = time.perf_counter()
         if migrate:
             do_migration(t3)
@@ -441,6 +469,8 @@ def main():
         step(i)
     barrier()                                            # torch.cuda.synchronize() waits for the last dense stitch too (and for the generation handed over ahead, if any)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:                                # outside the clock, before the untimed generations below move the state on
+        dump_outputs(args.dump_outputs, last, rank if world > 1 else None)
     rows1 = (0, 0, 0, 0) if args.plane_less else ctx.stitch_totals()
     if state.get("begun"):                               # the generation handed over in the last step: collected outside the clock (every timed step collected one)
         r = ctx.generation_end(want_couples=False, want_sex=True)
