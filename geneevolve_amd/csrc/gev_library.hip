@@ -193,12 +193,16 @@ struct PopState {
     std::vector<u32> logical;
     size_t n_phys = 0;
     bool finalized = false, gen0 = false;
+    // bumped whenever logical positions stop naming the physical rows they named (a new generation, a migration, rows removed or
+    // imported, the order materialised): couples gev_random_mate left on the device are only valid for the epoch they were made in
+    unsigned long long layout_epoch = 0;
 };
 
 struct gev_ctx {
     int device = 0, n_pop = 0, nchr = 0, nphen = 0;
     u32 rp_bits = 0;
     bool ad_effects_shared = false;         // every root population has the same CV effects bit for bit (check_multipop): A/D uses the one-population term table
+    bool multipop_ready = false;            // check_multipop has run for the current static inputs (ad_effects_shared, d_aptr / d_dptr are valid); setters clear it
     hipStream_t stream = nullptr, stream_samp = nullptr, stream_aux = nullptr, stream_list = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float last_ms[4] = {0, 0, 0, 0};
@@ -223,7 +227,7 @@ struct gev_ctx {
         bool presampled = false; int ps_pop = -1; u32 ps_seed = 0; size_t ps_n_people = 0; bool ps_has_mut = false;
         bool ps_stale = false;      // the head start was dropped by a redo of the generation in flight (record capacities changed): gev_presample_sex samples again from the retained inputs
         // gev_random_mate: father / mother of this set hold the couples of the next gev_reproduce (couples == NULL) of mate_pop
-        bool mated = false; int mate_pop = -1; size_t mate_n = 0;
+        bool mated = false; int mate_pop = -1; size_t mate_n = 0; unsigned long long mate_epoch = 0;
         // gev_set_generation_chain: seeds drawn and sampling enqueued for the NEXT gev_generation_begin (same population, size) from the predicted engine state
         bool fused_ahead = false, fa_dropped = false, fa_has_mut = false; int fa_pop = -1; size_t fa_n = 0;
         hipEvent_t ev_chain = nullptr, ev_tab = nullptr;
@@ -508,6 +512,9 @@ void gev_destroy(gev_ctx* c)
 }
 
 // ---- static inputs -----------------------------------------------------------------------
+// a setter changed what check_multipop compared or tabulated (grids, map ranges, CV positions and effects, the a / d device arrays):
+// the next A/D, eager A/D or migration runs it again instead of reading effect tables that may be stale or freed
+static void drop_multipop(gev_ctx* c) { c->multipop_ready = false; c->ad_effects_shared = false; }
 int gev_set_rmap(gev_ctx* c, int pop, int chr, const u64* bp, const double* prob, size_t R, u64 bp_dist)
 {
     GEVC(check_idx(c, pop, chr));
@@ -519,6 +526,7 @@ int gev_set_rmap(gev_ctx* c, int pop, int chr, const u64* bp, const double* prob
         if (bp[j + 1] < bp[j] + bp_dist) return fail(GEV_EUNSUPPORTED, "set_rmap: map rows %zu,%zu are closer than bp_dist_in_rmap=%llu: the reference would emit unsorted breakpoints (overlapping parts), which has no dense equivalent", j, j + 1, (unsigned long long)bp_dist);
     ChrStatic& S = c->pop[pop].cs[chr];
     S.rbp.assign(bp, bp + R); S.rprob.assign(prob, prob + R); S.bp_dist = bp_dist;
+    drop_multipop(c);
     std::vector<GevThr> thr;
     GEVC(make_thresholds(c, S.rprob, thr));
     S.r_amax = 0; for (const GevThr& t : thr) S.r_amax = std::max(S.r_amax, t.a_hi);
@@ -556,6 +564,7 @@ int gev_set_snps(gev_ctx* c, int pop, int chr, const u64* pos, size_t L)
     for (size_t i = 1; i < L; i++) if (pos[i] < pos[i - 1]) return fail(GEV_EUNSUPPORTED, "set_snps: positions must be non-decreasing (locus %zu)", i);
     ChrStatic& S = c->pop[pop].cs[chr];
     S.pos.assign(pos, pos + L); S.L = L;
+    drop_multipop(c);
     S.panel_rows = 0;                                              // a founder panel kept for another grid is void
     S.stride = std::max<size_t>(round_up(ceil_div(L, 8), 128), 128);
     S.seg_shift = c->seg_shift;                                    // 2 KiB segments (GEV_SEG_CHUNKS) unless the row would need more than 64 of them
@@ -572,7 +581,14 @@ int gev_set_cvs(gev_ctx* c, int pop, int phen, int chr, const u64* bp, const dou
     GEVC(check_idx(c, pop, chr, phen));
     if (C && (!bp || !a || !d)) return fail(GEV_EINVAL, "set_cvs: null arrays");
     if (C > 0x7fffff00u) return fail(GEV_EINVAL, "set_cvs: too many CVs");
+    if (c->pend.active) return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first");
     CvStatic& V = c->pop[pop].cv[phen][chr];
+    // the CV planes of a current generation hold its alleles at the positions they were built for (later generations inherit them
+    // from their parents' planes): new effects are allowed between generations, new positions only before gev_init_gen0
+    if (c->pop[pop].gen0 && V.set && (C != V.bp.size() || (C && memcmp(bp, V.bp.data(), C * sizeof(u64)))))
+        return fail(GEV_EUNSUPPORTED, "set_cvs: population %d phenotype %d chromosome %d has a current generation whose CV planes hold the "
+                    "alleles of the CV positions given before; new positions are only accepted before gev_init_gen0", pop, phen, chr);
+    drop_multipop(c);
     V.bp.assign(bp, bp + C); V.a.assign(a, a + C); V.d.assign(d, d + C); V.vd = vd; V.C = (u32)C; V.set = true;
     // sorted column order (stable: equal positions keep file order)
     V.icv_of_col.resize(C);
@@ -702,6 +718,7 @@ int gev_set_chr_active(gev_ctx* c, int chr, int active)
     GEVC(check_idx(c, 0, chr));
     for (auto& P : c->pop) if (P.gen0) return fail(GEV_ESTATE, "set_chr_active: must precede gev_init_gen0");
     c->chr_active[chr] = active ? 1 : 0;
+    drop_multipop(c);
     c->any_inactive = false;
     for (uint8_t a : c->chr_active) c->any_inactive |= !a;
     for (auto& P : c->pop) P.finalized = false;
@@ -921,6 +938,7 @@ static int finalize_static(gev_ctx* c, int pop)
 // with several populations the dense state needs one shared coordinate system
 static int check_multipop(gev_ctx* c)
 {
+    c->multipop_ready = false; c->ad_effects_shared = false;
     for (int pop = 1; pop < c->n_pop; pop++)
         for (int k = 0; k < c->nchr; k++) {
             if (!c->chr_active[k]) continue;
@@ -953,6 +971,7 @@ static int check_multipop(gev_ctx* c)
                 GEVC(h2d(c, c->pop[pop].cv[p][k].d_aptr, ap.data(), ap.size() * sizeof(double*)));
                 GEVC(h2d(c, c->pop[pop].cv[p][k].d_dptr, dp.data(), dp.size() * sizeof(double*)));
             }
+    c->multipop_ready = true;
     return GEV_OK;
 }
 
@@ -1003,7 +1022,7 @@ int gev_init_gen0(gev_ctx* c, int pop, size_t n_people, uint32_t seed_gen0, uint
     HIPC(hipStreamSynchronize(c->stream));
     for (int k = 0; k < c->nchr; k++) { P.st[k].mut_total[P.cur] = 0; P.st[k].parts_total[P.cur] = c->chr_active[k] ? rows : 0; P.st[k].pool_list_valid = false; P.st[k].csr_valid = true; P.st[k].lp.valid = false; }
     c->ad_cached_pop = c->ad_host_set_pop = -1;
-    P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.gen0 = true;
+    P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.gen0 = true; P.layout_epoch++;
     return GEV_OK;
 }
 
@@ -1664,7 +1683,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     // (the host enqueues slower than the device runs the first kernels of a generation: what the host waits for goes first, the
     // list kernels, which nothing of the generation reads, last)
     // the column counters are filled while the planes are written only if the A/D kernels that consume (and clear) them follow in this attempt
-    const bool ad_now = c->eager_ad && c->pop[q.pop].cv[0][0].d_aptr.p;
+    const bool ad_now = c->eager_ad && c->multipop_ready;
     const bool count_cols = ad_now && sc.cv_count_fused && sc.n_cvwork && sc.cv_used_max;
     GEVC(enqueue_cv_planes(c, sc, q.n_people, q.has_mut, count_cols, S));
     HIPC(hipEventRecord(sc.t[2], S));
@@ -1721,6 +1740,9 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     const bool dev_couples = couples == nullptr;
     if (dev_couples && !(sc.mated && sc.mate_pop == pop && sc.mate_n == n_people))
         return fail(GEV_ESTATE, "reproduce: couples is NULL but no gev_random_mate of population %d for %zu offspring precedes", pop, n_people);
+    if (dev_couples && sc.mate_epoch != P.layout_epoch)
+        return fail(GEV_ESTATE, "reproduce: couples is NULL but population %d changed (migration, rows removed or imported, order materialised) "
+                    "after the gev_random_mate that formed them: its positions no longer name the same rows", pop);
     // pinned staging: [father | mother | mut_seeds | status], written by the host, copied asynchronously
     const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
     const size_t stage_words = 2 * n_people + (has_mut ? T : 0) + n_status;
@@ -1796,7 +1818,7 @@ static int enqueue_chain_head_start(gev_ctx* c)
 // first gev_compute_ad, or here as soon as every population of the context has its static inputs
 static int prepare_eager_ad(gev_ctx* c, int pop)
 {
-    if (c->pop[pop].cv[0][0].d_aptr.p) return GEV_OK;
+    if (c->multipop_ready) return GEV_OK;
     for (const PopState& Q : c->pop)
         for (int k = 0; k < c->nchr; k++) {
             if (Q.cs[k].rbp.empty() || (c->chr_active[k] && Q.cs[k].pos.empty() && Q.cs[k].L)) return GEV_OK;
@@ -1960,7 +1982,7 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
         c->chunks_written_sum += (units - last) * seg + last * last_chunks; c->chunks_total_sum += 2ull * n_people * chunks;
         c->segments_written_sum += units; c->segments_total_sum += 2ull * n_people * S.nseg;
     }
-    const bool ad_done = c->eager_ad && c->pop[pop].cv[0][0].d_aptr.p;
+    const bool ad_done = c->eager_ad && c->multipop_ready;
     for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) P.cv[p][k].frq_valid = ad_done;
     c->ad_cached_pop = ad_done ? pop : -1;
     if (q.fused) {
@@ -1972,7 +1994,7 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
         }
         if (couples_out) { HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n_people * sizeof(gev_couple), hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     } else if (sex_out) { HIPC(hipMemcpyAsync(sex_out, sc.sex.p, n_people, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
-    P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear();
+    P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.layout_epoch++;
     c->gen_counter++;
     occ_tune_step(c, n_people);
     return GEV_OK;
@@ -2034,7 +2056,7 @@ int gev_random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_
     sc.mated = false;
     if (h[2] & FLAG_NO_MATES) return fail(GEV_ENOMATE, "Error: No one can marry, num_males_mate=%u, num_females_mate=%u", h[0], h[1]);
     if (h[2] & FLAG_RNG_SHORT) return fail(GEV_EDEVICE, "random_mate: a rejection stream ran out of candidates (internal error)");
-    sc.mated = true; sc.mate_pop = pop; sc.mate_n = pop_size;
+    sc.mated = true; sc.mate_pop = pop; sc.mate_n = pop_size; sc.mate_epoch = P.layout_epoch;
     return GEV_OK;
 }
 // Simulation::ras_glob_seed (src/Simulation.cpp:17-21) called n times, evaluated on the device: *engine_state = the state of
@@ -2298,7 +2320,7 @@ int gev_compute_ad(gev_ctx* c, int pop, double* additive, double* dominance, dou
             return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first");
     } else {
         HIPC(hipSetDevice(c->device));
-        if (!c->pop[pop].cv[0][0].d_aptr.p) GEVC(check_multipop(c));
+        if (!c->multipop_ready) GEVC(check_multipop(c));
         GEVC(materialize_order(c, pop));
         if (c->ad_cached_pop != pop) {          // not computed eagerly by the last gev_reproduce of this population
             GEVC(enqueue_ad(c, pop, P.cur, P.n_people));
@@ -2581,7 +2603,7 @@ static int materialize_order(gev_ctx* c, int pop)
     Seg all; all.src_pop = pop; all.people = P.logical;
     std::vector<Seg> segs; segs.push_back(std::move(all));
     GEVC(gather_population(c, pop, segs, P.n_people));
-    P.cur ^= 1; P.pcur = (P.pcur + 1) % 3; P.n_phys = P.n_people; P.logical.clear(); c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.cur ^= 1; P.pcur = (P.pcur + 1) % 3; P.n_phys = P.n_people; P.logical.clear(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 static int check_not_pending(gev_ctx* c)
@@ -2597,7 +2619,7 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
     HIPC(hipSetDevice(c->device));
     GEVC(gev_sync(c));
     for (int p = 0; p < c->n_pop; p++) if (c->pop[p].gen0) GEVC(materialize_order(c, p));
-    if (c->n_pop > 1 && !c->pop[0].cv[0][0].d_aptr.p) GEVC(check_multipop(c));
+    if (c->n_pop > 1 && !c->multipop_ready) GEVC(check_multipop(c));
     std::vector<std::vector<uint8_t>> gone(c->n_pop);
     for (int p = 0; p < c->n_pop; p++) {
         if (!c->pop[p].gen0) return fail(GEV_ESTATE, "migrate: population %d has no current generation", p);
@@ -2631,7 +2653,7 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
     for (int p = 0; p < c->n_pop; p++) if (n_new[p] > c->pop[p].cap_people) GEVC(ensure_capacity(c, p, n_new[p]));
     for (int p = 0; p < c->n_pop; p++) GEVC(ensure_csr(c, p));          // whole lists of every population are read (before any flag of a destination changes)
     for (int p = 0; p < c->n_pop; p++) GEVC(gather_population(c, p, plan[p], n_new[p]));
-    for (int p = 0; p < c->n_pop; p++) { c->pop[p].cur ^= 1; c->pop[p].pcur = (c->pop[p].pcur + 1) % 3; c->pop[p].n_people = n_new[p]; c->pop[p].n_phys = n_new[p]; }
+    for (int p = 0; p < c->n_pop; p++) { c->pop[p].cur ^= 1; c->pop[p].pcur = (c->pop[p].pcur + 1) % 3; c->pop[p].n_people = n_new[p]; c->pop[p].n_phys = n_new[p]; c->pop[p].layout_epoch++; }
     c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
@@ -2801,7 +2823,7 @@ int gev_remove_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n)
     // no row moves: only the logical order changes; stayers keep their order (src/Simulation.cpp:960-966)
     std::vector<u32> keep; keep.reserve(P.n_people - n);
     for (size_t i = 0; i < P.n_people; i++) if (!gone[i]) keep.push_back(P.logical.empty() ? (u32)i : P.logical[i]);
-    P.logical.swap(keep); P.n_people = P.logical.size(); c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.logical.swap(keep); P.n_people = P.logical.size(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, size_t n)
@@ -2956,7 +2978,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     if (rb_flag & 1u) return fail(GEV_EINVAL, "import_rows: Error: p.hap_index is not in range");
     if (P.logical.empty()) { P.logical.resize(P.n_people); for (size_t i = 0; i < P.n_people; i++) P.logical[i] = (u32)i; }
     for (size_t i = 0; i < n; i++) P.logical.push_back((u32)(n_old + i));
-    P.n_phys = n_new; P.n_people = P.logical.size(); c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.n_phys = n_new; P.n_people = P.logical.size(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 

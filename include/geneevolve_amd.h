@@ -127,7 +127,11 @@ int gev_set_mutmap(gev_ctx*, int pop, int chr, const uint64_t* bp, const double*
 /* Legend.pos of the founder panel (src/format_hap.h); must be non-decreasing. */
 int gev_set_snps(gev_ctx*, int pop, int chr, const uint64_t* pos, size_t L);
 /* CV_INFO of one phenotype x chromosome (src/Population.h:201-208): bp, genetic_value_a,
- * genetic_value_d in FILE order (the A/D sum runs in this order); vd = Phenotype_scheme::_vd. */
+ * genetic_value_d in FILE order (the A/D sum runs in this order); vd = Phenotype_scheme::_vd.
+ * Allowed between generations (not between gev_reproduce_begin / gev_generation_begin and their _end): the next A/D of every
+ * population uses the new a, d and vd, including the mean of two root populations' effects for admixed haplotypes.  Once the
+ * population has a generation (gev_init_gen0) its CV positions are fixed: other positions (or another count) return
+ * GEV_EUNSUPPORTED and change nothing. */
 int gev_set_cvs(gev_ctx*, int pop, int phen, int chr, const uint64_t* bp, const double* a,
                 const double* d, size_t C, double vd);
 /* Hap_SNP.hap founder panel, haplotype-major bit rows (nhap rows x L loci). */
@@ -158,7 +162,9 @@ int gev_init_gen0(gev_ctx*, int pop, size_t n_people, uint32_t seed_gen0, uint8_
  *  sex_out        : n_people bytes, Human::sex of each offspring (:2472), or NULL
  * Pedigree ids and common_sibling (:2473-2484) are pure host bookkeeping and stay with the host.
  *  couples == NULL : the couples the preceding gev_random_mate of `pop` left on the device (n_couples is ignored, n_people must be
- *                   that call's pop_size).
+ *                   that call's pop_size).  Returns GEV_ESTATE when the population changed in between (gev_migrate,
+ *                   gev_remove_rows, gev_import_rows, or a call that materialised a pending row order): the couples' positions
+ *                   would name other rows.
  * Cost note: with a mutation map every (offspring, chromosome) task restarts its rand() chain at srand(mut_seed), so all tasks are
  * sampled in parallel.  WITHOUT one (mut_seeds == NULL) the reference's chain runs through every gamete in order (the seed of a
  * gamete is the rand() output that follows the previous gamete's breakpoints): one wave walks it, about 10 us per gamete, i.e.
@@ -198,7 +204,8 @@ int gev_presample_sex(gev_ctx*, int pop, uint8_t* sex_out, size_t n_people);
  * pos_male[i_f], pos_female[i_m] with i_f / i_m the i-th values of uniform_int_distribution<unsigned long>(0, count-1) on
  * default_random_engine(seed+1) / (seed+2) (:2132-2147).  The sexes are the ones the library itself produced (gev_init_gen0,
  * gev_reproduce; they follow the individuals through gev_migrate / gev_export_rows / gev_import_rows).
- * The couples also stay on the device: the next gev_reproduce of `pop` takes them when its `couples` is NULL.
+ * The couples also stay on the device: the next gev_reproduce of `pop` takes them when its `couples` is NULL, as long as the
+ * population's rows are not changed in between.
  * Returns GEV_ENOMATE with the reference's message when no male or no female may marry (:2125-2129). */
 int gev_random_mate(gev_ctx*, int pop, uint32_t seed, const double* selection_value_func, size_t pop_size,
                     gev_couple* couples_out, size_t* num_males_mate, size_t* num_females_mate);

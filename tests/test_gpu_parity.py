@@ -608,6 +608,56 @@ def test_baseline_config2_full_size_dense_state_equals_interval_state(gpu_lib):
     g.close()
 
 
+def test_baseline_config2_full_size_benchmarked_loop_equals_oracle(gpu_lib, oracle_lib):
+    """bench.py's loop at FULL size, against the oracle: BASELINE config 2 (100k individuals x 1M SNPs, 1000 CVs, seed 12345) set up
+    as bench.py sets it up, gev_generation_begin / _end with the head start across generations (gev_set_generation_chain(0)) and
+    the next generation handed over before this one's A/D is read (bench.py step_fused).  The oracle (the reference's statements)
+    shadows every generation without a SNP panel (5-15 s a generation at this size, under 4 GB): seeds, sexes and A/D bit for bit each
+    generation, couples and mating counts of a last generation, then the interval and mutation lists -- and every word of the
+    genotype planes against those lists materialised from the founder panel, so that the planes equal the reference's state."""
+    n, L, gens = 100_000, 1_000_000, 3
+    cfg = SyntheticConfig(n, L, n_cv=1000, seed=12345)
+    g = gpu_lib.create(1, 1, 1); o = oracle_lib.create(1, 1, 1)
+    cfg.apply_static(g); cfg.apply_static(o)
+    g.synth_founders(0, 0, 2 * n, 1000)                          # the oracle never materialises genotypes here: no SNP panel
+    g.synth_cv_founders(0, 0, 0, 2 * n, 2000); o.upload_cv_founders(0, 0, 0, synth_packed(2000, 2 * n, 1000), 1000)
+    sg = Simulation(g, 12345, 1, True); so = Simulation(o, 12345, 1, True)
+    assert np.array_equal(g.init_gen0(0, n, int(sg.ras_glob_seed()[0])), o.init_gen0(0, n, int(so.ras_glob_seed()[0])))
+    g.set_generation_chain(0)
+    state = sg.glob.x
+    g.generation_begin(0, state, n)
+    for gen in range(1, gens + 2):
+        last = gen == gens + 1                                       # a last generation with its couples, nothing queued behind it
+        if last:
+            g.generation_begin(0, state, n)
+        r = g.generation_end(want_couples=last, want_sex=True)
+        state = int(r["glob_state"])
+        if gen < gens:
+            g.generation_begin(0, state, n)                          # the next generation is in flight while this one's A/D is read
+        ag = g.compute_ad(0, per_chr=False)
+        ro = so.next_generation_rm(0, n, want_couples=last)
+        ao = o.compute_ad(0, per_chr=False)
+        assert r["glob_state"] == ro["glob_state"] and r["seed_reproduce"] == ro["seed_reproduce"], f"seed stream differs at generation {gen}"
+        assert r["seed_mate"] == ro["seed_mate"], f"mating seed differs at generation {gen}"
+        assert np.array_equal(r["sex"], ro["sex"]), f"sexes differ at generation {gen}"
+        assert helpers.bits_equal(ag[0], ao[0]), f"additive values differ at generation {gen} (max abs diff {np.max(np.abs(ag[0] - ao[0]))})"
+        assert helpers.bits_equal(ag[1], ao[1]), f"dominance values differ at generation {gen}"
+        if last:
+            assert np.array_equal(r["couples"], ro["couples"]), "couples differ"
+            assert (r["num_males_mate"], r["num_females_mate"]) == (ro["num_males_mate"], ro["num_females_mate"]), "mating counts differ"
+    assert np.var(ag[0]) > 0
+    pg, og = g.download_intervals(0, 0); po, oo = o.download_intervals(0, 0)
+    assert np.array_equal(og, oo) and np.array_equal(pg, po), "interval lists differ"
+    mg, mog = g.download_mutations(0, 0); mo, moo = o.download_mutations(0, 0)
+    assert np.array_equal(mog, moo) and np.array_equal(mg, mo), "mutation lists differ"
+    assert og[-1] > 2 * n * 1.5 and mog[-1] > n                    # recombination happened, mutations accumulated
+    o.close()
+    # every one of the 200 000 x 31 250 plane words against the (reference-equal) lists materialised from the founder panel
+    assert g.dbg_verify_planes(0, 0, 1000) == (0, 0)
+    assert g.dbg_verify_planes(0, 0, 1001)[0] > 10 ** 9            # negative control: another founder panel does not match
+    g.close()
+
+
 def test_three_hundred_generations_of_shared_rows_dense_state_equals_interval_state(gpu_lib):
     """A long run at a size where the stitch overlaps the next generation's kernels (20k individuals x 256k SNPs, no synchronisation
     between generations): rows are handed down along chains of crossover-free gametes for many generations, the row pool is
@@ -1776,3 +1826,179 @@ def test_head_start_across_generations_is_only_a_schedule(gpu_lib, oracle_lib, m
     if tight:
         assert g.redo_count() >= 1, "the undersized buffers were meant to force generations to be enqueued again"
     g.close(); o.close()
+
+
+@pytest.mark.parametrize("selection", ["none", "uniform", "few"])
+@pytest.mark.parametrize("n", [100_000, 300_000])
+def test_device_random_mate_at_scale_equals_oracle(gpu_lib, oracle_lib, n, selection):
+    """gev_random_mate at the bench's population size and three times it (the mating kernels' grids run to thousands of blocks),
+    with no selection values (bench.py's case), uniform ones in [0.2, 1.4] (the rejection draw of :2113 excludes part of the
+    population) and ones that let fewer than 1 % marry: couples and mating counts equal the oracle's Simulation::random_mate on
+    the same sexes, for two seeds and two couple counts."""
+    cfg = SyntheticConfig(n, 256, chrom_bp=2_000_000, map_step=10_000, n_cv=16, seed=3)
+    g = gpu_lib.create(1, 1, 1); o = oracle_lib.create(1, 1, 1)
+    cfg.apply_static(g); cfg.apply_static(o)
+    g.synth_founders(0, 0, 2 * n, 5); g.synth_cv_founders(0, 0, 0, 2 * n, 6)      # mating reads the sexes only: no oracle panels
+    assert np.array_equal(g.init_gen0(0, n, 777), o.init_gen0(0, n, 777))
+    rng = np.random.default_rng(n)
+    svf = {"none": None, "uniform": rng.uniform(0.2, 1.4, n), "few": rng.uniform(0.0, 0.012, n)}[selection]
+    for seed, pop_size in ((4242, n), (999_983, n // 2 + 7)):
+        cg, mg, fg = g.random_mate(0, seed, svf, pop_size)
+        co, mo, fo = o.random_mate(0, seed, svf, pop_size)
+        assert (mg, fg) == (mo, fo), f"mating counts differ: device {(mg, fg)}, oracle {(mo, fo)}"
+        if selection == "none":
+            assert mg + fg == n
+        elif selection == "few":
+            assert 0 < mg + fg < n // 100
+        else:
+            assert n // 2 < mg + fg < n
+        assert np.array_equal(cg, co), f"couples differ at {np.flatnonzero(cg != co)[:5]} (seed {seed}, {pop_size} couples)"
+    g.close(); o.close()
+
+
+def _three_populations_with_shared_effects(gpu_lib, oracle_lib, n, n_cv):
+    """three populations on one grid whose CV files are the SAME (the one-population term table serves every haplotype)"""
+    rs = np.random.RandomState(23)
+    R = 41
+    bp = (100 + 5000 * np.arange(R)).astype(np.uint64)
+    prob = np.r_[0.0, np.full(R - 1, 0.04)]; rate = np.r_[0.0, np.full(R - 1, 0.05)]
+    L = 1500
+    pos = np.sort(rs.randint(0, 5000 * R + 500, L)).astype(np.uint64)
+    npop = 3
+    g = gpu_lib.create(npop, 1, 1); o = oracle_lib.create(npop, 1, 1)
+    cvbp = np.sort(rs.randint(0, 5000 * R + 400, n_cv)).astype(np.uint64)
+    a, d = rs.randn(n_cv), rs.randn(n_cv)
+    for pop in range(npop):
+        V = synth_packed(80 + pop, 2 * n, n_cv); F = synth_packed(90 + pop, 2 * n, L)
+        for ctx in (g, o):
+            ctx.set_rmap(pop, 0, bp, prob, 5000); ctx.set_mutmap(pop, 0, bp, rate); ctx.set_snps(pop, 0, pos)
+            ctx.set_cvs(pop, 0, 0, cvbp, a, d, 0.0)
+            ctx.upload_cv_founders(pop, 0, 0, V, n_cv)
+            ctx.upload_founders(pop, 0, F, L)
+    return g, o, cvbp, rs
+
+
+@pytest.mark.parametrize("change", ["new_effects", "more_cvs", "other_positions"])
+def test_set_cvs_between_generations_reaches_every_population(gpu_lib, oracle_lib, monkeypatch, change):
+    """gev_set_cvs after A/D has been computed.  Three populations start with the same CV effects (A/D takes the shared-table
+    shortcut), migrations admix their haplotypes, and after generation 2 population 1 gets new a, d and vd at the same positions:
+    from then on an admixed haplotype's effects are the mean of its two root populations' (src/Simulation.cpp:2695-2696), and
+    A/D of every population must equal the oracle's bit for bit.  New positions -- more CVs for every population, or other
+    positions for one -- cannot apply to a generation whose CV planes hold the old positions' alleles: refused with
+    GEV_EUNSUPPORTED, and nothing changes (A/D keeps matching an oracle that was given nothing)."""
+    monkeypatch.delenv("GEV_AD_SHARED", raising=False)
+    n, n_cv = 120, 300
+    g, o, cvbp, rs = _three_populations_with_shared_effects(gpu_lib, oracle_lib, n, n_cv)
+    sg, so = Simulation(g, 37, 1, True), Simulation(o, 37, 1, True)
+    for pop in range(3):
+        sg.ras_initial_human_gen0(pop, n); so.ras_initial_human_gen0(pop, n)
+    moves = [(0, 5, 1), (0, 17, 2), (0, 60, 1), (1, 3, 0), (1, 40, 2), (1, 41, 0), (2, 7, 0), (2, 8, 1)]
+    for gen in range(1, 7):
+        for pop in range(3):
+            npp = g.pop_size(pop)
+            ra = sg.next_generation_rm(pop, npp, want_couples=True); rb = so.next_generation_rm(pop, npp, want_couples=True)
+            assert np.array_equal(ra["couples"], rb["couples"]) and np.array_equal(ra["sex"], rb["sex"]), (gen, pop)
+            for x, y in zip(g.compute_ad(pop), o.compute_ad(pop)):
+                assert helpers.bits_equal(x, y), f"A/D gen {gen} pop {pop} ({change})"
+        if gen in (1, 2, 4):
+            g.migrate(moves); o.migrate(moves)
+        if gen == 2:
+            if change == "new_effects":
+                a1, d1 = rs.randn(n_cv), rs.randn(n_cv)
+                g.set_cvs(1, 0, 0, cvbp, a1, d1, 0.5); o.set_cvs(1, 0, 0, cvbp, a1, d1, 0.5)
+            else:
+                if change == "more_cvs":
+                    bp2 = np.sort(np.r_[cvbp, cvbp[:40] + 1]).astype(np.uint64); pops = range(3)
+                else:
+                    bp2 = (cvbp + 3).astype(np.uint64); pops = [1]
+                for pop in pops:
+                    with pytest.raises(capi.GevError) as e:
+                        g.set_cvs(pop, 0, 0, bp2, rs.randn(len(bp2)), rs.randn(len(bp2)), 0.0)
+                    assert e.value.code == -5, e.value                  # GEV_EUNSUPPORTED
+    parts, _ = g.download_intervals(0, 0)
+    assert len(set(int(x) for x in parts["root_population"])) == 3, "population 0 was meant to hold parts of all three root populations"
+    g.close(); o.close()
+
+
+def _device_buffer(nbytes):
+    """a plain device allocation of the HIP runtime the library is linked to (export / import records live on the device)"""
+    hip = C.CDLL("libamdhip64.so.7")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]; hip.hipFree.argtypes = [C.c_void_p]
+    p = C.c_void_p()
+    assert hip.hipMalloc(C.byref(p), max(nbytes, 16)) == 0 and p.value
+    return p.value, lambda: hip.hipFree(C.c_void_p(p.value))
+
+
+@pytest.mark.parametrize("change", ["migrate_swap", "remove_import", "materialize"])
+def test_device_couples_do_not_outlive_a_change_of_rows(gpu_lib, oracle_lib, change):
+    """Couples gev_random_mate leaves on the device name physical rows.  When the population's rows change before the
+    gev_reproduce that takes them (couples == NULL) -- a one-for-one migration swap, rows removed and imported back to the same size,
+    or a pending row order materialised by a download -- the sizes still agree, so the reproduce must be refused (GEV_ESTATE)
+    rather than breed from other rows.  Around it the legitimate order -- mate, reproduce, A/D, migrate, mate ... (an A/D between
+    mating and reproduce included) -- runs on and equals the oracle in couples, sexes, A/D and lists."""
+    n = 150
+    cfg = SyntheticConfig(n, 3000, chrom_bp=2_000_000, map_step=10_000, rec_per_row=0.01, mut_per_row=0.01, n_cv=40, seed=29)
+    g = gpu_lib.create(2, 1, 1); o = oracle_lib.create(2, 1, 1)
+    for p in range(2):
+        cfg.apply_static(g, p); cfg.apply_static(o, p)
+        g.synth_founders(p, 0, 2 * n, 60 + p); o.upload_founders(p, 0, synth_packed(60 + p, 2 * n, 3000), 3000)
+        g.synth_cv_founders(p, 0, 0, 2 * n, 70 + p); o.upload_cv_founders(p, 0, 0, synth_packed(70 + p, 2 * n, 40), 40)
+    sg, so = Simulation(g, 43, 1, True), Simulation(o, 43, 1, True)
+    for p in range(2):
+        sg.ras_initial_human_gen0(p, n); so.ras_initial_human_gen0(p, n)
+    bufs = []
+
+    def generation(gen, ad_before_reproduce=False):
+        for p in range(2):
+            npp = g.pop_size(p)
+            sg.random_mate_device(p, None, npp); so.random_mate_device(p, None, npp)
+            assert np.array_equal(sg.couples[p], so.couples[p]), f"couples gen {gen} pop {p}"
+            if ad_before_reproduce:
+                g.compute_ad(p); o.compute_ad(p)
+            assert np.array_equal(sg.reproduce(p, gen), so.reproduce(p, gen)), f"sex gen {gen} pop {p}"
+            for x, y in zip(g.compute_ad(p), o.compute_ad(p)):
+                assert helpers.bits_equal(x, y), f"A/D gen {gen} pop {p}"
+
+    def swap(gen):
+        moves = [(0, (7 * gen) % n, 1), (1, (11 * gen) % n, 0)]          # one for one: both sizes stay
+        g.migrate(moves); o.migrate(moves)
+
+    def remove_import(src, dst, who, gone):
+        nb = g.export_size(src, who)
+        dev, free = _device_buffer(nb); bufs.append(free)
+        g.export_rows(src, who, dev, nb)
+        ob = o.export_size(src, who); host = np.zeros(-(-ob // 8), dtype=np.uint64)
+        o.export_rows(src, who, host.ctypes.data, ob)
+        g.remove_rows(dst, gone); o.remove_rows(dst, gone)
+        g.import_rows(dst, dev, nb, len(who)); o.import_rows(dst, host.ctypes.data, ob, len(who))
+
+    for gen in (1, 2):
+        generation(gen, ad_before_reproduce=gen == 2)
+        swap(gen)
+    # the stale case: mate, change the rows, reproduce from the couples left on the device
+    if change == "materialize":                                  # positions are no longer rows before the mating ...
+        remove_import(1, 0, [9], [4])
+    sg.random_mate_device(0, None, n); so.random_mate_device(0, None, n)
+    if change == "migrate_swap":
+        swap(3)
+    elif change == "remove_import":
+        remove_import(1, 0, [9], [4])
+    else:                                                        # ... and a download puts the rows in order after it
+        g.download_haps(0, 0)
+    assert g.pop_size(0) == n
+    with pytest.raises(capi.GevError) as e:
+        sg.reproduce(0, 3)
+    assert e.value.code == -2 and "changed" in str(e.value), e.value       # GEV_ESTATE
+    so.glob.x = sg.glob.x                                        # (the refused call drew its seeds on the host; the oracle skips it)
+    for gen in (3, 4, 5):
+        generation(gen)
+        swap(gen)
+    for p in range(2):
+        pg, og = g.download_intervals(p, 0); po, oo = o.download_intervals(p, 0)
+        assert np.array_equal(og, oo) and np.array_equal(pg, po), f"interval lists pop {p}"
+        mg, mog = g.download_mutations(p, 0); mo, moo = o.download_mutations(p, 0)
+        assert np.array_equal(mog, moo) and np.array_equal(mg, mo), f"mutation lists pop {p}"
+        assert np.array_equal(g.download_haps(p, 0), o.download_haps(p, 0)), f"genotypes pop {p}"
+    g.close(); o.close()
+    for free in bufs:
+        free()
