@@ -38,6 +38,15 @@ class gev_gef_params(C.Structure):
                 ("s2_a_gen0", C.c_double), ("s2_d_gen0", C.c_double), ("gen_num", C.c_int32), ("reserved", C.c_int32)]
 
 
+class gev_selection_params(C.Structure):
+    _fields_ = [("gen_num", C.c_int32), ("func", C.c_int32), ("par1", C.c_double), ("par2", C.c_double),
+                ("omega", C.c_void_p), ("lambda_", C.c_void_p), ("phen_shift", C.c_void_p)]
+
+
+# GEV_SEL_* of include/geneevolve_amd.h by the reference's names of the functions (Population::_selection_func; "" = logit 0 1)
+SELECTION_FUNCS = {"none": 0, "": 1, "logit": 2, "probit": 3, "stab": 4, "thr": 5}
+
+
 class gev_generation_result(C.Structure):
     _fields_ = [("glob_state", C.c_uint32), ("seed_mate", C.c_uint32), ("seed_reproduce", C.c_uint32), ("reserved", C.c_uint32),
                 ("num_males_mate", C.c_uint64), ("num_females_mate", C.c_uint64)]
@@ -56,6 +65,7 @@ ABI_SYMBOLS = [
     "pop_size", "plane_ptr", "reserve", "set_chr_active", "set_dense_state", "materialize", "materialize_pops", "materialize_bed", "stream", "last_reproduce_ms", "set_track_intervals", "set_stitch_mode", "sync", "timing_totals", "stitch_totals", "reproduce_begin", "reproduce_end", "presample_sex", "set_overlap",
     "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
     "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
+    "compute_selection", "download_selection", "get_selection_gen0", "set_selection_gen0", "generation_begin_selected", "random_mate_selected",
     "dbg_verify_planes", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
@@ -166,6 +176,12 @@ class GevContext:
     def _call(self, name, *args):
         self.L.check(self.L._f(name)(self.h, *args))
 
+    def _call_new(self, name, *args):
+        """entry points a library may lack (the CPU oracle has no device selection values): a clear error instead of AttributeError"""
+        if not self.L.exports(name):
+            raise GevError(-5, f"{self.L.path} does not export {self.L.prefix}{name}")
+        self._call(name, *args)
+
     # ---- static inputs
     def set_rmap(self, pop, chr, bp, prob, bp_dist):
         bp = _arr(bp, np.uint64); prob = _arr(prob, np.float64)
@@ -275,6 +291,44 @@ class GevContext:
         self._call("random_mate", C.c_int(pop), C.c_uint32(int(seed)), _p(svf), C.c_size_t(pop_size), _p(couples), C.byref(nm), C.byref(nf))
         return couples, nm.value, nf.value
 
+    def random_mate_selected(self, pop, seed, pop_size, want_couples=True):
+        """random_mate() on the selection_value_func compute_selection() left in the library -> (couples or None, num_males_mate, num_females_mate)"""
+        couples = np.zeros(pop_size, dtype=COUPLE_DTYPE) if want_couples else None
+        nm, nf = C.c_size_t(), C.c_size_t()
+        self._call_new("random_mate_selected", C.c_int(pop), C.c_uint32(int(seed)), C.c_size_t(pop_size), _p(couples), C.byref(nm), C.byref(nf))
+        return couples, nm.value, nf.value
+
+    def compute_selection(self, pop, gen_num, func, par1, par2, omega, lambda_, phen_shift=None, want=("mating_value", "selection_value", "selection_value_func")):
+        """Simulation::ras_compute_mating_value_selection_value + ras_selection_func on the device, from the phenotypes the last
+        scale_ad_compute_gef() of every phenotype left there.  func: a key of SELECTION_FUNCS (the reference's name; None = "none")
+        or a GEV_SEL_* code.  -> dict of the n-vectors named in `want` (empty `want`: enqueued only, nothing waits)."""
+        code = SELECTION_FUNCS[func if func is not None else "none"] if not isinstance(func, int) else func
+        om, la = _arr(omega, np.float64), _arr(lambda_, np.float64)
+        sh = None if phen_shift is None else _arr(phen_shift, np.float64)
+        if len(om) != self.nphen or len(la) != self.nphen or (sh is not None and len(sh) != self.nphen):
+            raise ValueError("omega / lambda_ / phen_shift need one value per phenotype")
+        par = gev_selection_params(int(gen_num), code, float(par1), float(par2), om.ctypes.data, la.ctypes.data, None if sh is None else sh.ctypes.data)
+        n = self.pop_size(pop) if want else 0
+        out = {k: np.zeros(n) for k in want}
+        self._call_new("compute_selection", C.c_int(pop), C.byref(par), _p(out.get("mating_value")), _p(out.get("selection_value")), _p(out.get("selection_value_func")))
+        return out
+
+    def download_selection(self, pop):
+        """-> dict(mating_value, selection_value, selection_value_func) the library holds for the population's current generation"""
+        n = self.pop_size(pop)
+        out = {k: np.zeros(n) for k in ("mating_value", "selection_value", "selection_value_func")}
+        self._call_new("download_selection", C.c_int(pop), _p(out["mating_value"]), _p(out["selection_value"]), _p(out["selection_value_func"]))
+        return out
+
+    def get_selection_gen0(self, pop):
+        """-> (_gen0_SV_mean, _gen0_SV_var) of the population"""
+        m, v = C.c_double(), C.c_double()
+        self._call_new("get_selection_gen0", C.c_int(pop), C.byref(m), C.byref(v))
+        return m.value, v.value
+
+    def set_selection_gen0(self, pop, mean, var):
+        self._call_new("set_selection_gen0", C.c_int(pop), C.c_double(mean), C.c_double(var))
+
     def glob_seeds(self, engine_state, n, want=True):
         """n Simulation::ras_glob_seed() values from glob_generator's state -> (values or None, state after)"""
         st = C.c_uint32(int(engine_state))
@@ -286,6 +340,11 @@ class GevContext:
         """random_mate -> reproduce -> ras_compute_AD of one generation, enqueued as one unit (returns without waiting)"""
         svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
         self._call("generation_begin", C.c_int(pop), C.c_uint32(int(glob_state)), C.c_size_t(pop_size), _p(svf))
+        self._pending_people = pop_size
+
+    def generation_begin_selected(self, pop, glob_state, pop_size):
+        """generation_begin() mating on the selection_value_func compute_selection() left in the library (nothing uploaded)"""
+        self._call_new("generation_begin_selected", C.c_int(pop), C.c_uint32(int(glob_state)), C.c_size_t(pop_size))
         self._pending_people = pop_size
 
     def generation_end(self, want_couples=False, want_sex=True):

@@ -1747,7 +1747,8 @@ __global__ void __launch_bounds__(256) k_sum_final(const double* __restrict__ pa
 // :3174-3203; raw a, d strided by nphen
 __global__ void __launch_bounds__(256) k_gef_apply(const double* __restrict__ a, const double* __restrict__ d, size_t stride, const double* __restrict__ e, const double* __restrict__ par_eff,
                                                    const double* __restrict__ common, size_t n, double s_a, double s_d, double s_ev, double vf,
-                                                   double* __restrict__ o_add, double* __restrict__ o_dom, double* __restrict__ o_bv, double* __restrict__ o_e, double* __restrict__ o_par, double* __restrict__ o_phen)
+                                                   double* __restrict__ o_add, double* __restrict__ o_dom, double* __restrict__ o_bv, double* __restrict__ o_e, double* __restrict__ o_par, double* __restrict__ o_phen,
+                                                   double* __restrict__ o_keep /* the population's phenotype column, strided by stride (gev_compute_selection) */)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1757,7 +1758,8 @@ __global__ void __launch_bounds__(256) k_gef_apply(const double* __restrict__ a,
     const double pe = vf > 0 ? par_eff[i] : 0;
     const double cs = common ? common[i] : 0.0;
     o_e[i] = en; o_add[i] = ad; o_dom[i] = dm; o_bv[i] = ad + dm; o_par[i] = pe;
-    o_phen[i] = ad + dm + cs + en + pe;
+    const double ph = ad + dm + cs + en + pe;
+    o_phen[i] = ph; o_keep[i * stride] = ph;
 }
 __global__ void __launch_bounds__(256) k_par_eff(const double* __restrict__ ff, const double* __restrict__ fm, size_t n, double beta, double* __restrict__ out)
 {

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "gev_kernels.h"
+#include "gev_select.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...)
@@ -196,6 +197,14 @@ struct PopState {
     // bumped whenever logical positions stop naming the physical rows they named (a new generation, a migration, rows removed or
     // imported, the order materialised): couples gev_random_mate left on the device are only valid for the epoch they were made in
     unsigned long long layout_epoch = 0;
+    // gev_compute_selection: phenotypes of the current generation (gev_scale_ad_compute_gef writes column p; phen_ok[p] = written since the
+    // individuals last changed) and Human::mating_value / selection_value / selection_value_func, [3][n_people] (sel_ok = computed since
+    // then); [sbuf] is current, gev_migrate gathers into the other one.  d_sv0 = {_gen0_SV_mean, _gen0_SV_var} (sv0_ok: known)
+    DevBuf d_phen[2], d_sel[2], d_sv0;
+    int sbuf = 0;
+    std::vector<uint8_t> phen_ok;
+    bool sel_ok = false, sv0_ok = false;
+    void drop_selection() { std::fill(phen_ok.begin(), phen_ok.end(), 0); sel_ok = false; }
 };
 
 struct gev_ctx {
@@ -288,7 +297,7 @@ struct gev_ctx {
     // =auto measures it (a few generations per candidate, wall time between consecutive gev_reproduce returns).
     int stitch_occ = 0 /* 0 = by row length */, stitch_occ_env = 0; bool stitch_occ_auto = false;
     struct PendingRepro { bool active = false, has_mut = false, pre = false; int pop = 0, attempt = 0; size_t n_people = 0, n_status = 0; u32 seed = 0; u32* hstatus = nullptr; double th0 = 0, th1 = 0, th2 = 0;
-                          bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr; } pend;
+                          bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; const double* d_svf = nullptr; /* with has_svf: what the mating reads */ u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr; } pend;
     struct OccTune { int phase = 0 /* 0 idle, 1 measuring, 2 settled */, idx = 0, n = 0, best_occ = 8; double last = 0, cur_min = 0, best = 0; size_t people = 0; unsigned age = 0; } tune;
     DevBuf d_snpmajor, d_text;
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
@@ -460,6 +469,7 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
         P.cs.resize(nchr); P.st.resize(nchr);
         P.cv.resize(nphen); P.cvp.resize(nphen);
         for (int p = 0; p < nphen; p++) { P.cv[p].resize(nchr); P.cvp[p].resize(nchr); }
+        P.phen_ok.assign(nphen, 0);
     }
     GevRngTables T; gev_build_rng_tables(T);
     GEVC(h2d(c.get(), c->d_tables, &T, sizeof T));
@@ -1022,7 +1032,7 @@ int gev_init_gen0(gev_ctx* c, int pop, size_t n_people, uint32_t seed_gen0, uint
     HIPC(hipStreamSynchronize(c->stream));
     for (int k = 0; k < c->nchr; k++) { P.st[k].mut_total[P.cur] = 0; P.st[k].parts_total[P.cur] = c->chr_active[k] ? rows : 0; P.st[k].pool_list_valid = false; P.st[k].csr_valid = true; P.st[k].lp.valid = false; }
     c->ad_cached_pop = c->ad_host_set_pop = -1;
-    P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.gen0 = true; P.layout_epoch++;
+    P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.gen0 = true; P.layout_epoch++; P.drop_selection();
     return GEV_OK;
 }
 
@@ -1648,7 +1658,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     // overlap mode 2: only the ALU-bound sampling shares the GPU with the previous generation's stitch; everything latency-bound waits for it
     if (c->sparse_after_stitch && c->planes_pending) HIPC(hipStreamWaitEvent(X, c->ev_planes, 0));
     if (q.fused) {
-        GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? c->d_svf.as<double>() : nullptr, q.n_people, sc.father.as<u32>(), sc.mother.as<u32>(),
+        GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father.as<u32>(), sc.mother.as<u32>(),
                           c->d_couples.as<gev_couple>(), status + ST_NM_MATE, status + ST_FLAGS));
     }
     if (q.fused && c->chain_draws >= 0) {                    // where glob_generator will stand when the host comes back for the next generation
@@ -1848,7 +1858,8 @@ static int population_has_mutmap(gev_ctx* c, int pop, bool& has_mut)
 // One generation of a randomly mating population in one piece: Simulation::random_mate -> Simulation::reproduce ->
 // Simulation::ras_compute_AD (the body of sim_next_generation, src/Simulation.cpp:1907-1935) with every ras_glob_seed() value
 // the three draw -- 1 (:2092) + 1 (:2398) + n_people * nchr (:2500) -- taken from glob_generator's state ON THE DEVICE.
-int gev_generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop_size, const double* selection_value_func)
+// selection_value_func: host array (uploaded) or NULL; dev_sel: the population's own device values (gev_compute_selection) instead
+static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop_size, const double* selection_value_func, bool dev_sel)
 {
     GEVC(check_idx(c, pop, 0));
     PopState& P = c->pop[pop];
@@ -1890,14 +1901,34 @@ int gev_generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop_si
         HIPC(hipMemcpyAsync(c->d_svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
         HIPC(hipStreamSynchronize(st));                          // the caller's array is pageable memory of unknown lifetime
     }
+    const double* d_svf = selection_value_func ? c->d_svf.as<double>() : nullptr;
+    if (dev_sel) d_svf = P.d_sel[P.sbuf].as<double>() + 2 * P.n_people;     // (enqueued on this stream behind gev_compute_selection: no wait)
     gev_ctx::PendingRepro& q = c->pend;
     q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
     q.pool_rebuilt = false;
-    q.fused = true; q.has_svf = selection_value_func != nullptr; q.glob_state = glob_state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
+    q.fused = true; q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     if (c->chain_draws >= 0 && c->head_start == 0) GEVC(enqueue_chain_head_start(c));
     return GEV_OK;
+}
+int gev_generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop_size, const double* selection_value_func)
+{
+    return generation_begin(c, pop, glob_state, pop_size, selection_value_func, false);
+}
+static int check_selection(gev_ctx* c, int pop, const char* who)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (c->pend.active) return fail(GEV_ESTATE, "%s: a generation is pending: call gev_generation_end / gev_reproduce_end first", who);
+    const PopState& P = c->pop[pop];
+    if (!P.gen0 || !P.sel_ok)
+        return fail(GEV_ESTATE, "%s: population %d has no selection values of its current generation on the device (gev_compute_selection)", who, pop);
+    return GEV_OK;
+}
+int gev_generation_begin_selected(gev_ctx* c, int pop, uint32_t glob_state, size_t pop_size)
+{
+    GEVC(check_selection(c, pop, "generation_begin_selected"));
+    return generation_begin(c, pop, glob_state, pop_size, nullptr, true);
 }
 // The host announced how many ras_glob_seed() values it draws itself between two generations (gev_set_generation_chain): the state
 // glob_generator will have at the next gev_generation_begin is then known on the device as soon as this generation's seeds are
@@ -1994,7 +2025,7 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
         }
         if (couples_out) { HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n_people * sizeof(gev_couple), hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     } else if (sex_out) { HIPC(hipMemcpyAsync(sex_out, sc.sex.p, n_people, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
-    P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.layout_epoch++;
+    P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.layout_epoch++; P.drop_selection();
     c->gen_counter++;
     occ_tune_step(c, n_people);
     return GEV_OK;
@@ -2021,8 +2052,8 @@ int gev_reproduce(gev_ctx* c, int pop, const gev_couple* couples, size_t n_coupl
 }
 // Simulation::random_mate (src/Simulation.cpp:2090-2157) of the population's current generation on the device.  The couples stay
 // on the device for the next gev_reproduce of the population (couples == NULL there) and are copied out when couples_out is given.
-int gev_random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_value_func, size_t pop_size, gev_couple* couples_out,
-                    size_t* num_males_mate, size_t* num_females_mate)
+static int random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_value_func, bool dev_sel, size_t pop_size, gev_couple* couples_out,
+                       size_t* num_males_mate, size_t* num_females_mate)
 {
     GEVC(check_idx(c, pop, 0));
     PopState& P = c->pop[pop];
@@ -2045,6 +2076,7 @@ int gev_random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_
         HIPC(hipMemcpyAsync(c->d_svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
         d_svf = c->d_svf.as<double>();
     }
+    if (dev_sel) d_svf = P.d_sel[P.sbuf].as<double>() + 2 * P.n_people;
     u32* ms = c->d_mstat.as<u32>();                             // {num_males_mate, num_females_mate, flags}
     GEVC(enqueue_mate(c, st, P, (u32)seed, nullptr, d_svf, pop_size, sc.father.as<u32>(), sc.mother.as<u32>(), couples_out ? c->d_couples.as<gev_couple>() : nullptr, ms, ms + 2));
     u32 h[4] = {0, 0, 0, 0};
@@ -2058,6 +2090,16 @@ int gev_random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_
     if (h[2] & FLAG_RNG_SHORT) return fail(GEV_EDEVICE, "random_mate: a rejection stream ran out of candidates (internal error)");
     sc.mated = true; sc.mate_pop = pop; sc.mate_n = pop_size; sc.mate_epoch = P.layout_epoch;
     return GEV_OK;
+}
+int gev_random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_value_func, size_t pop_size, gev_couple* couples_out,
+                    size_t* num_males_mate, size_t* num_females_mate)
+{
+    return random_mate(c, pop, seed, selection_value_func, false, pop_size, couples_out, num_males_mate, num_females_mate);
+}
+int gev_random_mate_selected(gev_ctx* c, int pop, uint32_t seed, size_t pop_size, gev_couple* couples_out, size_t* num_males_mate, size_t* num_females_mate)
+{
+    GEVC(check_selection(c, pop, "random_mate_selected"));
+    return random_mate(c, pop, seed, nullptr, true, pop_size, couples_out, num_males_mate, num_females_mate);
 }
 // Simulation::ras_glob_seed (src/Simulation.cpp:17-21) called n times, evaluated on the device: *engine_state = the state of
 // glob_generator (std::minstd_rand0) before, and after on return; out (host, n values) may be NULL.
@@ -2451,13 +2493,16 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
         }
         s_ev = std::sqrt(var_e / par->ve);
     }
+    DevBuf& keep = P.d_phen[P.sbuf];                                                                     // the population's phenotypes, for gev_compute_selection
+    GEVC(keep.ensure(n * (size_t)c->nphen * sizeof(double), st, /*keep=*/true));
     hipLaunchKernelGGL(k_gef_apply, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, c->d_add.as<double>() + phen, c->d_dom.as<double>() + phen, (size_t)c->nphen,
                        d_e, d_par, common_sibling ? d_cs : (const double*)nullptr, n, s_a, s_d, s_ev, par->vf,
-                       d_out, d_out + n, d_out + 2 * n, d_out + 3 * n, d_out + 4 * n, d_out + 5 * n);
+                       d_out, d_out + n, d_out + 2 * n, d_out + 3 * n, d_out + 4 * n, d_out + 5 * n, keep.as<double>() + phen);
     KCHECK();
     double* outs[6] = {additive, dominance, bv, e_noise, parental_effect, phen_out};
     for (int k = 0; k < 6; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], d_out + k * n, n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
+    P.phen_ok[phen] = 1;
     return GEV_OK;
 }
 
@@ -2478,6 +2523,89 @@ int gev_set_ad(gev_ctx* c, int pop, const double* additive, const double* domina
     HIPC(hipMemcpyAsync(c->d_dom.p, dominance, nd * sizeof(double), hipMemcpyHostToDevice, st));
     HIPC(hipStreamSynchronize(st));
     c->ad_host_set_pop = pop;
+    return GEV_OK;
+}
+// ---- Simulation::ras_compute_mating_value_selection_value + ras_selection_func (src/Simulation.cpp:3300-3342, :3386-3428) ----
+// from the phenotypes gev_scale_ad_compute_gef left in the population, into its [3][n] value buffer; generation 0 also reduces the
+// mean and variance of sv on the device.  Nothing waits unless an output is asked for.
+int gev_compute_selection(gev_ctx* c, int pop, const gev_selection_params* par, double* mating_value, double* selection_value, double* selection_value_func)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (c->pend.active) return fail(GEV_ESTATE, "compute_selection: a generation is pending: call gev_generation_end / gev_reproduce_end first");
+    if (!par || !par->omega || !par->lambda) return fail(GEV_EINVAL, "compute_selection: null parameters / omega / lambda");
+    if (par->func < GEV_SEL_NONE || par->func > GEV_SEL_THR) return fail(GEV_EINVAL, "compute_selection: unknown selection function %d", par->func);
+    if (par->gen_num < 0) return fail(GEV_EINVAL, "compute_selection: gen_num %d", par->gen_num);
+    if (c->nphen > GEV_SEL_MAX_PHEN) return fail(GEV_EUNSUPPORTED, "compute_selection: more than %d phenotypes", GEV_SEL_MAX_PHEN);
+    PopState& P = c->pop[pop];
+    if (!P.gen0) return fail(GEV_ESTATE, "compute_selection: population %d has no current generation", pop);
+    for (int p = 0; p < c->nphen; p++)
+        if (!P.phen_ok[p]) return fail(GEV_ESTATE, "compute_selection: phenotype %d of population %d's current generation has not been through gev_scale_ad_compute_gef", p, pop);
+    const bool gen0 = par->gen_num == 0;
+    if (!gen0 && !P.sv0_ok) return fail(GEV_ESTATE, "compute_selection: population %d has no generation-0 selection statistics (gen_num 0 first, or gev_set_selection_gen0)", pop);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    SelArgs a{};
+    a.nphen = c->nphen; a.func = par->func; a.gen_num = par->gen_num; a.par1 = par->par1; a.par2 = par->par2;
+    for (int p = 0; p < c->nphen; p++) { a.omega[p] = par->omega[p]; a.lambda[p] = par->lambda[p]; a.shift[p] = par->phen_shift ? par->phen_shift[p] : 0.0; }
+    const size_t n = P.n_people;
+    DevBuf& V = P.d_sel[P.sbuf];
+    GEVC(V.ensure(3 * n * sizeof(double), st));
+    GEVC(P.d_sv0.ensure((2 + SEL_RED_BLOCKS) * sizeof(double), st, /*keep=*/true));     // {mean, var} + the partial sums of the reduction
+    double *mv = V.as<double>(), *sv = mv + n, *svf = mv + 2 * n, *sv0 = P.d_sv0.as<double>();
+    const unsigned nbk = (unsigned)ceil_div(n, 256);
+    hipLaunchKernelGGL(k_sel_values, dim3(nbk), dim3(256), 0, st, (const double*)P.d_phen[P.sbuf].as<double>(), n, a, (const double*)sv0, gen0 ? 0 : 1, mv, sv, svf);
+    if (gen0) {                                             // _gen0_SV_mean / _gen0_SV_var (:3326-3330), kept on the device
+        const int nb = (int)std::min<size_t>(nbk, SEL_RED_BLOCKS);
+        for (int pass = 0; pass < 2; pass++) {
+            hipLaunchKernelGGL(k_sel_sum_partial, dim3(nb), dim3(256), 0, st, (const double*)sv, n, (const double*)sv0, pass, sv0 + 2);
+            hipLaunchKernelGGL(k_sel_sum_final, dim3(1), dim3(256), 0, st, (const double*)(sv0 + 2), nb, n, pass, sv0);
+        }
+        hipLaunchKernelGGL(k_sel_finish, dim3(nbk), dim3(256), 0, st, n, a, (const double*)sv0, sv, svf);
+    }
+    KCHECK();
+    if (gen0) P.sv0_ok = true;
+    P.sel_ok = true;
+    double* outs[3] = {mating_value, selection_value, selection_value_func};
+    bool any = false;
+    for (int k = 0; k < 3; k++) if (outs[k]) { HIPC(hipMemcpyAsync(outs[k], mv + k * n, n * sizeof(double), hipMemcpyDeviceToHost, st)); any = true; }
+    if (any) HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+int gev_download_selection(gev_ctx* c, int pop, double* mating_value, double* selection_value, double* selection_value_func)
+{
+    GEVC(check_selection(c, pop, "download_selection"));
+    PopState& P = c->pop[pop];
+    HIPC(hipSetDevice(c->device));
+    const size_t n = P.n_people;
+    double* outs[3] = {mating_value, selection_value, selection_value_func};
+    for (int k = 0; k < 3; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], P.d_sel[P.sbuf].as<double>() + k * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return GEV_OK;
+}
+int gev_get_selection_gen0(gev_ctx* c, int pop, double* mean, double* var)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (c->pend.active) return fail(GEV_ESTATE, "get_selection_gen0: a generation is pending");
+    PopState& P = c->pop[pop];
+    if (!P.sv0_ok) return fail(GEV_ESTATE, "get_selection_gen0: population %d has no generation-0 selection statistics", pop);
+    HIPC(hipSetDevice(c->device));
+    double h[2] = {0, 0};
+    HIPC(hipMemcpyAsync(h, P.d_sv0.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if (mean) *mean = h[0];
+    if (var) *var = h[1];
+    return GEV_OK;
+}
+int gev_set_selection_gen0(gev_ctx* c, int pop, double mean, double var)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (c->pend.active) return fail(GEV_ESTATE, "set_selection_gen0: a generation is pending");
+    PopState& P = c->pop[pop];
+    HIPC(hipSetDevice(c->device));
+    GEVC(P.d_sv0.ensure((2 + SEL_RED_BLOCKS) * sizeof(double), c->stream));
+    hipLaunchKernelGGL(k_sel_set_gen0, dim3(1), dim3(64), 0, c->stream, P.d_sv0.as<double>(), mean, var);
+    KCHECK();
+    P.sv0_ok = true;
     return GEV_OK;
 }
 int gev_get_cv_freq(gev_ctx* c, int pop, int phen, int chr, double* frq, size_t C)
@@ -2612,6 +2740,50 @@ static int check_not_pending(gev_ctx* c)
     if (c->pend.active) return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first");
     return GEV_OK;
 }
+// The phenotypes and Human::mating_value / selection_value / selection_value_func follow the individuals (the reference computes the
+// values, src/Simulation.cpp:1988, before ras_do_migration, :1998): gathered into the other buffers of every destination, valid where
+// every population that contributes individuals had them.  Called before the populations' sizes change.
+static int migrate_selection(gev_ctx* c, const std::vector<std::vector<Seg>>& plan, const std::vector<size_t>& n_new)
+{
+    hipStream_t st = c->stream;
+    const u32 nph = (u32)c->nphen;
+    std::vector<uint8_t> phen_ok(c->n_pop), sel_ok(c->n_pop);
+    for (int d = 0; d < c->n_pop; d++) {
+        PopState& D = c->pop[d];
+        bool ph = true, sl = true;
+        for (const Seg& sg : plan[d]) if (!sg.people.empty()) {
+            const PopState& S = c->pop[sg.src_pop];
+            for (u32 k = 0; k < nph; k++) ph = ph && S.phen_ok[k];
+            sl = sl && S.sel_ok;
+        }
+        phen_ok[d] = ph; sel_ok[d] = sl;
+        if (!ph && !sl) continue;
+        const int nb = D.sbuf ^ 1;
+        if (ph) GEVC(D.d_phen[nb].ensure(n_new[d] * nph * sizeof(double), st));
+        if (sl) GEVC(D.d_sel[nb].ensure(3 * n_new[d] * sizeof(double), st));
+        size_t i0 = 0;
+        for (const Seg& sg : plan[d]) {
+            if (sg.people.empty()) continue;
+            const PopState& S = c->pop[sg.src_pop];
+            const size_t m = sg.people.size();
+            GEVC(h2d(c, c->d_map, sg.people.data(), m * sizeof(u32)));
+            if (ph)
+                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(m * nph, 256)), dim3(256), 0, st, D.d_phen[nb].as<double>() + i0 * nph,
+                                   (const double*)S.d_phen[S.sbuf].as<double>(), (const u32*)c->d_map.as<u32>(), m, nph);
+            if (sl) for (size_t v = 0; v < 3; v++)      // [3][n]: mating_value, selection_value, selection_value_func
+                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, D.d_sel[nb].as<double>() + v * n_new[d] + i0,
+                                   (const double*)S.d_sel[S.sbuf].as<double>() + v * S.n_people, (const u32*)c->d_map.as<u32>(), m, 1u);
+            KCHECK();
+            HIPC(hipStreamSynchronize(st));             // (d_map is refilled for the next segment)
+            i0 += m;
+        }
+    }
+    for (int d = 0; d < c->n_pop; d++) {
+        PopState& D = c->pop[d];
+        D.sbuf ^= 1; std::fill(D.phen_ok.begin(), D.phen_ok.end(), phen_ok[d]); D.sel_ok = sel_ok[d];
+    }
+    return GEV_OK;
+}
 int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
 {
     GEVC(check_not_pending(c));
@@ -2653,6 +2825,7 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
     for (int p = 0; p < c->n_pop; p++) if (n_new[p] > c->pop[p].cap_people) GEVC(ensure_capacity(c, p, n_new[p]));
     for (int p = 0; p < c->n_pop; p++) GEVC(ensure_csr(c, p));          // whole lists of every population are read (before any flag of a destination changes)
     for (int p = 0; p < c->n_pop; p++) GEVC(gather_population(c, p, plan[p], n_new[p]));
+    GEVC(migrate_selection(c, plan, n_new));
     for (int p = 0; p < c->n_pop; p++) { c->pop[p].cur ^= 1; c->pop[p].pcur = (c->pop[p].pcur + 1) % 3; c->pop[p].n_people = n_new[p]; c->pop[p].n_phys = n_new[p]; c->pop[p].layout_epoch++; }
     c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
@@ -2823,7 +2996,7 @@ int gev_remove_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n)
     // no row moves: only the logical order changes; stayers keep their order (src/Simulation.cpp:960-966)
     std::vector<u32> keep; keep.reserve(P.n_people - n);
     for (size_t i = 0; i < P.n_people; i++) if (!gone[i]) keep.push_back(P.logical.empty() ? (u32)i : P.logical[i]);
-    P.logical.swap(keep); P.n_people = P.logical.size(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.logical.swap(keep); P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, size_t n)
@@ -2978,7 +3151,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     if (rb_flag & 1u) return fail(GEV_EINVAL, "import_rows: Error: p.hap_index is not in range");
     if (P.logical.empty()) { P.logical.resize(P.n_people); for (size_t i = 0; i < P.n_people; i++) P.logical[i] = (u32)i; }
     for (size_t i = 0; i < n; i++) P.logical.push_back((u32)(n_old + i));
-    P.n_phys = n_new; P.n_people = P.logical.size(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.n_phys = n_new; P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 

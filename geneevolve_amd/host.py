@@ -495,6 +495,24 @@ def selection_func(kind, p1, p2, z):
     raise NotImplementedError(kind)
 
 
+def ras_selection_func(gen_num, kind, p1, p2, z):
+    """the whole of Simulation::ras_selection_func (reference src/Simulation.cpp:3386-3428): generation 0 and "none" give 1 for all,
+    "" is the reference's default (logit 0 1, :3393-3399: y = exp(b0 + b1*z), y/(1+y)); the other kinds as selection_func"""
+    import math
+    if gen_num == 0 or kind in (None, "none"):
+        return np.ones(len(z))
+    if kind == "":
+        out = []
+        for v in np.asarray(z, dtype=np.float64).tolist():
+            try:
+                y = math.exp(0.0 + 1.0 * v)
+            except OverflowError:                  # (C's exp gives inf there, and inf/(1+inf) is NaN)
+                y = math.inf
+            out.append(y / (1 + y))
+        return np.array(out)
+    return selection_func(kind, p1, p2, z)
+
+
 class SampleWithoutReplacement:
     """RasRandomNumber::ras_SampleWithoutReplacement (reference src/RasRandomNumber.cpp:90-120): Knuth's selection sampling on
     a `static` default_random_engine -- it is seeded by the seed of the FIRST call of the process and every later call
@@ -605,6 +623,9 @@ class Simulation:
         """random_mate -> reproduce -> ras_compute_AD of sim_next_generation (:1907-1935) as one library call pair; the
         ras_glob_seed() draws of the three are made by the library from glob_generator's state, which is stored back"""
         self.ctx.generation_begin(ipop, self.glob.x, pop_size, selection_value_func)
+        return self._generation_end(ipop, want_couples)
+
+    def _generation_end(self, ipop, want_couples):
         r = self.ctx.generation_end(want_couples=want_couples)
         self.glob.x = int(r["glob_state"])
         self.last_seed_reproduce = int(r["seed_reproduce"])
@@ -615,6 +636,11 @@ class Simulation:
                 c = r["couples"]
                 self.ped[ipop] = self.ped[ipop].offspring(c["pos_male"].astype(np.int64), c["pos_female"].astype(np.int64))
         return r
+
+    def next_generation_rm_selected(self, ipop, pop_size, want_couples=False):
+        """next_generation_rm() mating on the selection values gev_compute_selection left in the library: nothing is uploaded"""
+        self.ctx.generation_begin_selected(ipop, self.glob.x, pop_size)
+        return self._generation_end(ipop, want_couples)
 
     def assort_mate(self, ipop, selection_value_func, mating_value, pop_size, mat_cor, mm_percent=0.0,
                     avoid_inbreeding=False, offspring_dist="p", rank=None):   # :2167 (3 draws, +1 for Poisson offspring numbers)

@@ -267,6 +267,52 @@ int gev_scale_ad_compute_gef(gev_ctx*, int pop, int phen, const gev_gef_params* 
                              const double* common_sibling, const double* f_father, const double* f_mother,
                              double* additive, double* dominance, double* bv, double* e_noise,
                              double* parental_effect, double* phen_out);
+/* (the phen result of every (pop, phen) also stays in the library, [n_people x nphen] per population, for gev_compute_selection.) */
+
+/* ---- Simulation::ras_compute_mating_value_selection_value (src/Simulation.cpp:3300-3342) + ras_selection_func (:3386-3428) ----
+ * On the device, from the phenotypes the last gev_scale_ad_compute_gef of every phenotype left there, one thread per individual:
+ *   mv = sum_p omega[p] * (phen[p] + shift[p]),  sv = sum_p lambda[p] * (phen[p] + shift[p])   (phenotype order, FP64, no FMA)
+ *   gen_num == 0: the generation-0 mean and variance of sv (CommFunc::mean / CommFunc::var, n-1) are computed and kept for the
+ *                 population, on the device (no host wait)
+ *   z = (sv - mean) / sqrt(var) when var > 0, else sv - mean;  svf = ras_selection_func(z), 1 for all at generation 0
+ * with the reference's arithmetic: logit y = exp(b0 + b1*z), y/(1+y) -- NaN where exp overflows, and NaN never passes r < svf (the
+ * individual cannot mate); probit .5*(1+erf((z-mu)/(sqrt(2)*sigma))); stab 1/(sqrt(2*pi)*sigma)*exp(-0.5*pow((z-mu)/sigma,2)) with
+ * pi = 3.1415926 (src/CommFunc.cpp:4); thr z <= thr ? p1 : 1.  Floats agree with the reference within 1e-12 relative (device libm and
+ * parallel sums).
+ * The three vectors (Human::mating_value, selection_value = z, selection_value_func) belong to the population's current generation:
+ * they follow the individuals through gev_migrate and are dropped when the individuals change otherwise (a published generation,
+ * gev_init_gen0, gev_remove_rows, gev_import_rows).  gev_generation_begin_selected / gev_random_mate_selected mate on the device's
+ * selection_value_func and return GEV_ESTATE when the population has none. */
+#define GEV_SEL_NONE     0   /* 1 for all (a host that passes no function)                        */
+#define GEV_SEL_DEFAULT  1   /* "" : logit 0 1 (:3393-3399)                                        */
+#define GEV_SEL_LOGIT    2
+#define GEV_SEL_PROBIT   3
+#define GEV_SEL_STAB     4
+#define GEV_SEL_THR      5
+typedef struct gev_selection_params {
+    int32_t gen_num;          /* the reference's gen_num at :3300; generation 0 sets the standardisation */
+    int32_t func;             /* GEV_SEL_NONE, GEV_SEL_DEFAULT (""), GEV_SEL_LOGIT, _PROBIT, _STAB, _THR */
+    double  par1, par2;       /* _selection_func_par1/2[gen_num-1] */
+    const double* omega;      /* [nphen] Phenotype_scheme::_omega */
+    const double* lambda;     /* [nphen] Phenotype_scheme::_lambda */
+    const double* phen_shift; /* [nphen] or NULL: the --gamma constant of this population (:3291) */
+} gev_selection_params;
+/* outputs: n_people doubles each (host), each may be NULL; with all three NULL the call only enqueues and returns at once.
+ * GEV_ESTATE when a phenotype of the current generation has not been through gev_scale_ad_compute_gef, or gen_num > 0 without
+ * generation-0 statistics (computed at gen_num 0, or set by gev_set_selection_gen0). */
+int gev_compute_selection(gev_ctx*, int pop, const gev_selection_params*,
+                          double* mating_value, double* selection_value, double* selection_value_func);
+/* the population's current device values (as gev_compute_selection left them, or as gev_migrate moved them); GEV_ESTATE when there
+ * are none.  Outputs as gev_compute_selection's; waits for the device. */
+int gev_download_selection(gev_ctx*, int pop, double* mating_value, double* selection_value, double* selection_value_func);
+/* Population::_gen0_SV_mean / _gen0_SV_var of `pop` (waits for the device) / set by a host that computed generation 0 itself */
+int gev_get_selection_gen0(gev_ctx*, int pop, double* mean, double* var);
+int gev_set_selection_gen0(gev_ctx*, int pop, double mean, double var);
+/* gev_generation_begin / gev_random_mate with selection_value_func = the one gev_compute_selection left on the device: nothing is
+ * uploaded and the host does not wait.  Works with the head start of gev_set_generation_chain (only the couples read it). */
+int gev_generation_begin_selected(gev_ctx*, int pop, uint32_t glob_state, size_t pop_size);
+int gev_random_mate_selected(gev_ctx*, int pop, uint32_t seed, size_t pop_size,
+                             gev_couple* couples_out, size_t* num_males_mate, size_t* num_females_mate);
 
 /* Locus-split populations (gev_set_chr_active): every context of the population computes the A/D of its own chromosomes; after
  * the all-reduce + chromosome-ordered sum (geneevolve_amd/distributed.py:compute_ad_locus_split) each context is handed the raw
