@@ -153,7 +153,7 @@ struct AdWork {
 #define GEV_BK_CAP 8
 #define GEV_NM_CAP 8
 // status words written by the kernels of one generation, read back once at its end
-enum { ST_BK_OVF_USED = 0, ST_NM_OVF_USED = 1, ST_FLAGS = 2, ST_SLOW_MUT = 3, ST_SLOW_REC = 4 /* tasks handed to the one-task-per-wave kernels */,
+enum { ST_BK_OVF_USED = 0, ST_NM_OVF_USED = 1, ST_FLAGS = 2, /* 3, 4: unused */
        ST_GLOB_STATE = 5 /* glob_generator behind the generation's ras_glob_seed() draws (gev_generation_begin) */, ST_NM_MATE = 6, ST_NF_MATE = 7 /* num_males_mate, num_females_mate */,
        ST_NEXT_STATE = 8 /* ... and behind the draws the host announced it makes before the next generation (gev_set_generation_chain) */,
        ST_TOTALS = 16 /* then per chr: mut_total, parts_total, segments the dense stitch writes, how many of them are last (partial) segments, free list length, free list cursor */ };
@@ -329,22 +329,11 @@ __device__ __forceinline__ u32 mut_scan_write(const GevRngTables* __restrict__ T
         });
     return h;
 }
-// `list` != NULL: only the tasks list[0 .. *n_list) (the ones the batched kernel k_mut_sample8 handed over); NULL: every task
-__global__ void __launch_bounds__(256) k_mut_sample(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, int nchr,
-                                                    const u32* __restrict__ mut_seeds, size_t n_tasks, SampleDev sd,
-                                                    const u32* __restrict__ list, const u32* __restrict__ n_list)
+// one mutation task t (chromosome C, the last one of its offspring if `last`) by one wave: nmut, nm_off, the records, the sex of
+// the offspring behind its last chromosome, seed_pat[t + 1]; returns seed_pat[t + 1]
+__device__ __forceinline__ u32 mut_task(const GevRngTables* __restrict__ T, const ChrDev& C, bool last, u32 S, size_t t, const SampleDev& sd, u32 nchr)
 {
-    __shared__ __attribute__((aligned(16))) GevRngTables s_T;
-    const size_t n_iter = list ? (size_t)*n_list : n_tasks;
-    if (n_iter == 0) return;
-    const GevRngTables* T = stage_tables(Tg, &s_T);
     const u32 lane = threadIdx.x & 63;
-    for (size_t it = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < n_iter; it += (size_t)gridDim.x * 4) {
-    const size_t t = list ? (size_t)list[it] : it;
-    asm volatile("" : "+v"(T));          // keep the 62 table words of this lane out of registers across tasks (occupancy)
-    const int c = (int)(t % nchr);
-    const ChrDev& C = chrs[c];
-    const u32 S = mut_seeds[t];
     GlibcWave g; g.seed(T, S);                                   // srand(seed), :2501
     u32 off = (u32)t * GEV_NM_CAP;
     u32 n = mut_scan_write(T, C, S, g, sd.nm_pos + off, sd.nm_side + off, GEV_NM_CAP);
@@ -360,13 +349,25 @@ __global__ void __launch_bounds__(256) k_mut_sample(const GevRngTables* __restri
         } else { if (lane == 0) atomicOr(&sd.status[ST_FLAGS], (u32)FLAG_NM_OVF); n_store = 0; }     // host grows the region and redoes the generation
     }
     if (lane == 0) { sd.nmut[t] = n_store; sd.nm_off[t] = off; }
-    if (c == nchr - 1) {                                         // sex = rand()%2+1 after the last chromosome, :2472
+    if (last) {                                                  // sex = rand()%2+1 after the last chromosome, :2472
         const u32 sx = (g.out(T, n) & 1u) + 1u;
         if (lane == 0) sd.sex[t / nchr] = (uint8_t)sx;
         n++;
     }
     const u32 nxt = g.out(T, n);                                 // seed_loc of the next task, :2447
     if (lane == 0) sd.seed_pat[t + 1] = nxt;
+    return nxt;
+}
+// one task per wave (GEV_SAMPLE_BATCHED=0)
+__global__ void __launch_bounds__(256) k_mut_sample(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, int nchr,
+                                                    const u32* __restrict__ mut_seeds, size_t n_tasks, SampleDev sd)
+{
+    __shared__ __attribute__((aligned(16))) GevRngTables s_T;
+    const GevRngTables* T = stage_tables(Tg, &s_T);
+    for (size_t t = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tasks; t += (size_t)gridDim.x * 4) {
+        asm volatile("" : "+v"(T));      // keep the 62 table words of this lane out of registers across tasks (occupancy)
+        const int c = (int)(t % nchr);
+        mut_task(T, chrs[c], c == nchr - 1, mut_seeds[t], t, sd, (u32)nchr);
     }
 }
 
@@ -426,32 +427,33 @@ __device__ __forceinline__ u32 task_sample(const GevRngTables* __restrict__ T, c
     }
     return k_mat;
 }
-// task-parallel form (a mutation map is loaded: every task's chain restarts at srand(S), see
-// SURVEY.md section 7.2-1).  seed_pat[t] for t>0 was written by k_mut_sample.
+// both gametes of task t by one wave; a chromosome that another context owns (inactive) gets empty records (only the seed chain
+// is needed here, and the mutation sampling carries it)
+__device__ __forceinline__ void rec_task(const GevRngTables* __restrict__ T, const ChrDev& C, u32 seed_pat, size_t t, const SampleDev& sd)
+{
+    if (!C.active) {
+        if ((threadIdx.x & 63) == 0) {
+            sd.k[2 * t] = 0; sd.k[2 * t + 1] = 0; sd.bk_off[2 * t] = (u32)(2 * t) * GEV_BK_CAP; sd.bk_off[2 * t + 1] = (u32)(2 * t + 1) * GEV_BK_CAP;
+            sd.start[2 * t] = 0; sd.start[2 * t + 1] = 0; sd.seed_mat[t] = 0;
+        }
+        return;
+    }
+    GlibcWave g;
+    task_sample(T, C, seed_pat, t, g, sd);
+}
+// task-parallel form (a mutation map is loaded: every task's chain restarts at srand(S)), one task
+// per wave (GEV_SAMPLE_BATCHED=0).  seed_pat[t] for t>0 was written by k_mut_sample.
 __global__ void __launch_bounds__(256) k_rec_sample(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, int nchr,
-                                                    u32 seed_reproduce, const u32* __restrict__ seed_ptr /* device copy of the seed (gev_generation_begin), or null */, size_t n_tasks, SampleDev sd,
-                                                    const u32* __restrict__ list, const u32* __restrict__ n_list)
+                                                    u32 seed_reproduce, const u32* __restrict__ seed_ptr /* device copy of the seed (gev_generation_begin), or null */, size_t n_tasks, SampleDev sd)
 {
     __shared__ __attribute__((aligned(16))) GevRngTables s_T;
-    const size_t n_iter = list ? (size_t)*n_list : n_tasks;
-    if (n_iter == 0) return;
     const GevRngTables* T = stage_tables(Tg, &s_T);
-    for (size_t it = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < n_iter; it += (size_t)gridDim.x * 4) {
-        const size_t t = list ? (size_t)list[it] : it;
+    for (size_t t = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tasks; t += (size_t)gridDim.x * 4) {
         asm volatile("" : "+v"(T));      // keep the 62 table words of this lane out of registers across tasks (occupancy)
-        GlibcWave g;
         u32 seed_pat;
-        if (t == 0) { g.seed(T, seed_ptr ? *seed_ptr : seed_reproduce); seed_pat = g.out(T, 0); }     // srand(seed) :2400, first rand() :2447
+        if (t == 0) { GlibcWave g; g.seed(T, seed_ptr ? *seed_ptr : seed_reproduce); seed_pat = g.out(T, 0); }     // srand(seed) :2400, first rand() :2447
         else seed_pat = sd.seed_pat[t];
-        const ChrDev& C = chrs[t % nchr];
-        if (!C.active) {                 // another context owns this chromosome: only the seed chain (k_mut_sample) is needed here
-            if ((threadIdx.x & 63) == 0) {
-                sd.k[2 * t] = 0; sd.k[2 * t + 1] = 0; sd.bk_off[2 * t] = (u32)(2 * t) * GEV_BK_CAP; sd.bk_off[2 * t + 1] = (u32)(2 * t + 1) * GEV_BK_CAP;
-                sd.start[2 * t] = 0; sd.start[2 * t + 1] = 0; sd.seed_mat[t] = 0;
-            }
-            continue;
-        }
-        task_sample(T, C, seed_pat, t, g, sd);
+        rec_task(T, chrs[t % nchr], seed_pat, t, sd);
     }
 }
 // serial form (no mutation map): every gamete's seed depends on the previous gamete's crossover

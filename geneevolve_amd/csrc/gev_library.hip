@@ -7,7 +7,7 @@
 // Tuning / diagnosis knobs (environment, read at gev_create; defaults are what the measurements of DESIGN.md chose):
 //   GEV_OVERLAP=0|1|2|-1      stream overlap: never | everything (default) | sampling only | decide from two timed generations
 //   GEV_SERIALIZE=1           same as GEV_OVERLAP=0
-//   GEV_SAMPLE_BATCHED=0|1    sampling kernels: one task per wave | eight tasks per wave (default)
+//   GEV_SAMPLE_BATCHED=0|1    sampling kernels: one task per wave | eight tasks per wave, one kernel (default)
 //   GEV_STITCH_MODE=0|1       dense stitch kernel: k_stitch_segments (default) | k_stitch_rows (same results)
 //   GEV_SAMPLE_GRID=n         persistent workgroups of the sampling kernels (default 1792 up to 400k tasks per generation, 768 above; 1024 alone)
 //   GEV_STITCH_WG_PER_CU=n|auto stitch workgroups per CU, by dynamic LDS padding (default: unlimited; auto: measured at run time)
@@ -221,7 +221,7 @@ struct gev_ctx {
     // per-generation scratch: two sets, because the dense stitch of generation g (stream_big) still reads set g%2
     // while sampling / sparse state of generation g+1 (stream) fill the other one
     struct Scratch {
-        DevBuf father, mother, mutseeds, globvals /* [2 + T] ras_glob_seed() values drawn on the device: mate seed, reproduce seed, mutation seeds */, seed_pat, seed_mat, k, bk_off, bk, bk_idx, start, nmut, nm_off, nm_pos, nm_side, sex, status, slow_mut, slow_rec, chrwork, cvwork;
+        DevBuf father, mother, mutseeds, globvals /* [2 + T] ras_glob_seed() values drawn on the device: mate seed, reproduce seed, mutation seeds */, seed_pat, seed_mat, k, bk_off, bk, bk_idx, start, nmut, nm_off, nm_pos, nm_side, sex, status, chrwork, cvwork;
         std::vector<uint8_t> chrwork_shadow, cvwork_shadow;     // what the device copies of the tables hold (upload_table_cached)
         unsigned n_chrwork = 0, n_cvwork = 0; float sampling_ms_saved = -1;
         size_t nseg_max = 1, cv_used_max = 0, lp_entries_per_row = 0; u32 cv_max = 0;     // launch shapes of the generation (enqueue_tables)
@@ -1151,7 +1151,7 @@ static int ensure_scratch(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, boo
     GEVC(sc.nmut.ensure(T * sizeof(u32), st)); GEVC(sc.nm_off.ensure((T + 1) * sizeof(u32), st));
     GEVC(sc.nm_pos.ensure(16, st)); GEVC(sc.nm_side.ensure(16, st));
     GEVC(sc.status.ensure(n_status * sizeof(u32), st));
-    if (has_mut) { GEVC(sc.mutseeds.ensure(T * sizeof(u32), st)); GEVC(sc.slow_mut.ensure(T * sizeof(u32), st)); GEVC(sc.slow_rec.ensure(T * sizeof(u32), st)); }
+    if (has_mut) { GEVC(sc.mutseeds.ensure(T * sizeof(u32), st)); }
     return GEV_OK;
 }
 // K1-K3: crossover / mutation sampling and the rand() seed chain; depends on the seeds and n_people only, not on the couples
@@ -1181,16 +1181,12 @@ static int enqueue_sampling(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_
     const unsigned shared_grid = c->sample_grid_env ? c->sample_grid_shared : (T <= 400000 ? 1792u : c->sample_grid_shared);
     const unsigned task_blocks = (unsigned)std::min<size_t>(ceil_div(T, 4), (c->dense && !c->serialize) ? shared_grid : c->sample_grid);
     if (has_mut && c->sample_batched) {
-        // eight tasks per wave; the rare tasks that need more than 8 rand() outputs go to the one-task-per-wave kernels
+        // eight tasks per wave, mutations and gametes in one kernel; the rare slow tasks are finished in place
         const unsigned batch_blocks = (unsigned)std::min<size_t>(ceil_div(ceil_div(T, SB_TASKS), 4), task_blocks);
-        const unsigned slow_blocks = (unsigned)std::min<size_t>(ceil_div(T, 4), 64);
-        hipLaunchKernelGGL(k_mut_sample8, dim3(batch_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, seed_reproduce, seed_ptr, T, sd, sc.slow_mut.as<u32>());
-        hipLaunchKernelGGL(k_mut_sample, dim3(slow_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, T, sd, sc.slow_mut.as<u32>(), sd.status + ST_SLOW_MUT);
-        hipLaunchKernelGGL(k_rec_sample8, dim3(batch_blocks), dim3(256), 0, st, Tb, chrs, nchr, T, sd, sc.slow_rec.as<u32>());
-        hipLaunchKernelGGL(k_rec_sample, dim3(slow_blocks), dim3(256), 0, st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd, sc.slow_rec.as<u32>(), sd.status + ST_SLOW_REC);
+        hipLaunchKernelGGL(k_sample_batched, dim3(batch_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, seed_reproduce, seed_ptr, T, sd);
     } else if (has_mut) {
-        hipLaunchKernelGGL(k_mut_sample, dim3(task_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, T, sd, (const u32*)nullptr, (const u32*)nullptr);
-        hipLaunchKernelGGL(k_rec_sample, dim3(task_blocks), dim3(256), 0, st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd, (const u32*)nullptr, (const u32*)nullptr);
+        hipLaunchKernelGGL(k_mut_sample, dim3(task_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, T, sd);
+        hipLaunchKernelGGL(k_rec_sample, dim3(task_blocks), dim3(256), 0, st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd);
     } else {
         // no mutation map: the gametes of a generation form ONE serial chain (src/Simulation.cpp:2447-2455).  A workgroup per link
         // (k_rec_chain_wg); GEV_CHAIN_WG=0: the one-wave form

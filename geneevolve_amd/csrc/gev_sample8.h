@@ -14,9 +14,11 @@
 //     (breakpoint = bp[row] + rand() % dist; mutation position by uniform_int_distribution, side = rand() % 2) runs one hit per
 //     lane.
 //
-// A task that needs more than the 8 precomputed rand() outputs (k + 2 > 8 crossovers / mutations), or whose mutation
-// position draw hits the rejection branch of uniform_int_distribution, is appended to a list and redone by the one-task-
-// per-wave kernels (expected: ~1e-4 of the tasks at one event per gamete).
+// One kernel (k_sample_batched) samples a generation's mutations and gametes: wave b takes the mutations of tasks [8b, 8b+8),
+// then both gametes of tasks [8b+1, 8b+9), whose paternal seeds come out of the mutation streams it has just run.  A task
+// that needs more than the 8 precomputed rand() outputs (k + 2 > 8 crossovers / mutations), or whose mutation position draw
+// hits the rejection branch of uniform_int_distribution, is finished by the same wave with the one-task-per-wave arithmetic
+// (expected: ~1e-4 of the tasks at one event per gamete).
 #pragma once
 
 #define SB_TASKS 8          // tasks per wave batch
@@ -159,12 +161,31 @@ __device__ __forceinline__ u32 rank_hits(bool valid, u32 tg, bool hit, u32& hc)
     return h;
 }
 
+
 // ------------------------------------------------------------------------------------------
-// K2 batched: Simulation::ras_add_mutation for 8 (offspring, chromosome) tasks per wave
+// K1-K3 batched, one kernel: wave b samples the mutations of tasks [8b, 8b+8) (Simulation::ras_add_mutation), then both
+// gametes of tasks [8b+1, 8b+9) (ras_sim_loc_rec, :2447-2455).  The paternal seed of task t+1 is a rand() of task t's mutation
+// stream, so lane group g hands it to the gamete phase in a register; only task 0 takes its seed from srand(seed_reproduce)
+// (:2400, :2447), and batch 0 samples its gametes in a pass of their own before the others.  A task that needs more than
+// SB_OUT rand() outputs or hits the rejection branch of uniform_int_distribution is finished by the same wave, one task at a
+// time, with the one-task-per-wave arithmetic (mut_task / rec_task on the global tables) behind a wave-uniform branch.
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256, 4) k_mut_sample8(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, int nchr,
-                                                     const u32* __restrict__ mut_seeds, u32 seed_reproduce, const u32* __restrict__ seed_ptr, size_t n_tasks, SampleDev sd,
-                                                     u32* __restrict__ slow_list)
+// The slow tasks, out of line: their arithmetic needs far more registers than the batched loop, and called where little is live
+// they do not cost the loop its occupancy
+__device__ __noinline__ void slow_rec_task(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, u32 c, u32 seed_pat, size_t t, const SampleDev& sd)
+{
+    rec_task(Tg, chrs[c], seed_pat, t, sd);
+}
+__device__ __noinline__ void slow_mut_task(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, const u32* __restrict__ mut_seeds, u32 nchr,
+                                           size_t t, size_t n_tasks, const SampleDev& sd)
+{
+    const u32 c = (u32)(t % nchr);
+    const u32 nxt = mut_task(Tg, chrs[c], c == nchr - 1, mut_seeds[t], t, sd, nchr);
+    if (t + 1 < n_tasks) rec_task(Tg, chrs[(t + 1) % nchr], nxt, t + 1, sd);        // the gametes of the task behind it
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) k_sample_batched(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, int nchr,
+                                                        const u32* __restrict__ mut_seeds, u32 seed_reproduce, const u32* __restrict__ seed_ptr,
+                                                        size_t n_tasks, SampleDev sd)
 {
     __shared__ SmpTabs s_T;
     __shared__ SmpWave s_W[4];
@@ -174,149 +195,163 @@ __global__ void __launch_bounds__(256, 4) k_mut_sample8(const GevRngTables* __re
     const u32 lane = threadIdx.x & 63, g = lane >> 3, j = lane & 7u;
     const size_t n_batches = (n_tasks + SB_TASKS - 1) / SB_TASKS;
     for (size_t b = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < n_batches; b += (size_t)gridDim.x * 4) {
+        // ---- mutations of task t = 8b + g
         const size_t t = b * SB_TASKS + g;
         const bool valid = t < n_tasks;
         const u32 cidx = valid ? (u32)(t % (size_t)nchr) : 0u;
         const u32 S = valid ? mut_seeds[t] : 1u;
+        u32 seed0 = 0;
         if (b == 0) {                                       // first rand() after srand(seed) of reproduce (:2400, :2447) = seed_loc of task 0
             const u32 x0 = srand8(T, W->r, seed_ptr ? *seed_ptr : seed_reproduce);
-            if (lane == 0) sd.seed_pat[0] = x0 >> 1;
+            seed0 = rl_u32(x0, 0) >> 1;
+            if (lane == 0) sd.seed_pat[0] = seed0;
         }
-        const u32 xout = srand8(T, W->r, S);               // srand(seed), :2501
-        u32 hc = 0; bool rej = false;
-        u32 count = 0;
-        auto resolve = [&]() {
-            wave_fence();
-            for (u32 c0 = 0; c0 < count; c0 += 64) {
-                const u32 idx = c0 + lane; const bool cv = idx < count;
-                const u32 row = cv ? W->cand_row[idx] : 1u, x2 = cv ? W->cand_x2[idx] : 1u, tg = cv ? (u32)W->cand_tag[idx] : 0u;
-                const u32 cq = (u32)__shfl((int)cidx, (int)(tg * 8u));
-                const u32 Sq = (u32)__shfl((int)S, (int)(tg * 8u));
-                const ChrDev& C = chrs[cq];
-                bool hit = false;
-                if (cv) { const GevThr th = C.mthr[row]; hit = thr_hit(th, mulmod31(x2, T->inv16807), x2); }
-                const u32 h = rank_hits(cv, tg, hit, hc);
-                const u32 o = (u32)__shfl((int)xout, (int)(tg * 8u + (h < SB_OUT ? h : SB_OUT - 1u)));
-                bool rj = false;
-                if (hit && h < GEV_NM_CAP) {
-                    // uniform_int_distribution<unsigned long>(bp[i-1], bp[i]) on generator(seed+1), :2503, :2516-2520: hit h of a task
-                    // takes engine output h+1 as long as no earlier draw of the task was rejected
-                    const u32 x = mulmod31(T->pow_lcg[h + 2], minstd_seed(Sq + 1u));
-                    const u64 lo = C.mbp[row - 1], hi = C.mbp[row];
-                    const u32 uerange = (u32)(hi - lo) + 1u;                   // < 2147483645 (checked by gev_set_mutmap)
-                    const u32 scaling = 2147483645u / uerange, past = uerange * scaling, ret = x - 1u;
-                    rj = ret >= past;
-                    const size_t slot = (size_t)(b * SB_TASKS + tg) * GEV_NM_CAP + h;
-                    sd.nm_pos[slot] = (u64)(ret / scaling) + lo;
-                    sd.nm_side[slot] = (uint8_t)((o >> 1) & 1u);                // rand()%2, :2522
-                }
+        u32 seed_next;                                      // seed_pat[t + 1]: lane group g's paternal seed in the gamete phase
+        bool slow_mut;                                      // ... unless task t is slow: then task t + 1's gametes are late too
+        {
+            const u32 xout = srand8(T, W->r, S);           // srand(seed), :2501
+            u32 hc = 0, count = 0;
+            bool rej = false;
+            auto resolve = [&]() {
+                wave_fence();
+                for (u32 c0 = 0; c0 < count; c0 += 64) {
+                    const u32 idx = c0 + lane; const bool cv = idx < count;
+                    const u32 row = cv ? W->cand_row[idx] : 1u, x2 = cv ? W->cand_x2[idx] : 1u, tg = cv ? (u32)W->cand_tag[idx] : 0u;
+                    const u32 cq = (u32)__shfl((int)cidx, (int)(tg * 8u));
+                    const u32 Sq = (u32)__shfl((int)S, (int)(tg * 8u));
+                    const ChrDev& C = chrs[cq];
+                    bool hit = false;
+                    if (cv) { const GevThr th = C.mthr[row]; hit = thr_hit(th, mulmod31(x2, T->inv16807), x2); }
+                    const u32 h = rank_hits(cv, tg, hit, hc);
+                    const u32 o = (u32)__shfl((int)xout, (int)(tg * 8u + (h < SB_OUT ? h : SB_OUT - 1u)));
+                    bool rj = false;
+                    if (hit && h < GEV_NM_CAP) {
+                        // uniform_int_distribution<unsigned long>(bp[i-1], bp[i]) on generator(seed+1), :2503, :2516-2520: hit h of a task
+                        // takes engine output h+1 as long as no earlier draw of the task was rejected
+                        const u32 x = mulmod31(T->pow_lcg[h + 2], minstd_seed(Sq + 1u));
+                        const u64 lo = C.mbp[row - 1], hi = C.mbp[row];
+                        const u32 uerange = (u32)(hi - lo) + 1u;                   // < 2147483645 (checked by gev_set_mutmap)
+                        const u32 scaling = 2147483645u / uerange, past = uerange * scaling, ret = x - 1u;
+                        rj = ret >= past;
+                        const size_t slot = (size_t)(b * SB_TASKS + tg) * GEV_NM_CAP + h;
+                        sd.nm_pos[slot] = (u64)(ret / scaling) + lo;
+                        sd.nm_side[slot] = (uint8_t)((o >> 1) & 1u);                // rand()%2, :2522
+                    }
 #pragma unroll
-                for (u32 q = 0; q < SB_TASKS; q++) { const unsigned long long mr = __ballot(rj && tg == q); if (g == q && mr) rej = true; }
-            }
-            count = 0;
-            wave_fence();
-        };
-#pragma unroll 1
-        for (u32 q = 0; q < SB_TASKS; q++) {
-            if (b * SB_TASKS + q >= n_tasks) break;
-            const ChrDev& C = chrs[rl_u32(cidx, q * 8u)];
-            if (C.M >= 2) scan_candidates(T, W, rl_u32(S, q * 8u) + 2u, C.m_amax, 1u, C.M - 1u, q, count, resolve);   // generator_u(seed+2), i = 1..M-1
-        }
-        if (count) resolve();
-        const u32 n = hc;
-        const bool last = cidx == (u32)(nchr - 1);
-        const bool slow = valid && (n + 2u > SB_OUT || rej);
-        const u32 o_sex = (u32)__shfl((int)xout, (int)(g * 8u + (n < SB_OUT ? n : SB_OUT - 1u)));
-        const u32 n2 = n + (last ? 1u : 0u);
-        const u32 o_nxt = (u32)__shfl((int)xout, (int)(g * 8u + (n2 < SB_OUT ? n2 : SB_OUT - 1u)));
-        if (valid && j == 0) {
-            if (!slow) {
-                sd.nmut[t] = n; sd.nm_off[t] = (u32)t * GEV_NM_CAP;
-                if (last) sd.sex[t / (size_t)nchr] = (uint8_t)(((o_sex >> 1) & 1u) + 1u);      // :2472
-                sd.seed_pat[t + 1] = o_nxt >> 1;                                                // seed_loc of the next task, :2447
-            } else slow_list[atomicAdd(&sd.status[ST_SLOW_MUT], 1u)] = (u32)t;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// K1/K3 batched: both gametes of 8 (offspring, chromosome) tasks per wave
-// ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256, 4) k_rec_sample8(const GevRngTables* __restrict__ Tg, const ChrDev* __restrict__ chrs, int nchr,
-                                                     size_t n_tasks, SampleDev sd, u32* __restrict__ slow_list)
-{
-    __shared__ SmpTabs s_T;
-    __shared__ SmpWave s_W[4];
-    stage_smp_tabs(Tg, &s_T);
-    const SmpTabs* T = &s_T;
-    SmpWave* W = &s_W[threadIdx.x >> 6];
-    const u32 lane = threadIdx.x & 63, g = lane >> 3, j = lane & 7u;
-    const size_t n_batches = (n_tasks + SB_TASKS - 1) / SB_TASKS;
-    for (size_t b = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < n_batches; b += (size_t)gridDim.x * 4) {
-        const size_t t = b * SB_TASKS + g;
-        const bool valid = t < n_tasks;
-        const u32 cidx = valid ? (u32)(t % (size_t)nchr) : 0u;
-        const bool active = valid && chrs[cidx].active != 0;       // inactive: another context owns this chromosome (only the seed chain is needed)
-        const u32 seed_pat = valid ? sd.seed_pat[t] : 1u;
-        u32 seed_cur = seed_pat, xout = 0, hc = 0, count = 0, side = 0;
-        bool run = active;
-        auto resolve = [&]() {
-            wave_fence();
-            for (u32 c0 = 0; c0 < count; c0 += 64) {
-                const u32 idx = c0 + lane; const bool cv = idx < count;
-                const u32 row = cv ? W->cand_row[idx] : 0u, x2 = cv ? W->cand_x2[idx] : 1u, tg = cv ? (u32)W->cand_tag[idx] : 0u;
-                const u32 cq = (u32)__shfl((int)cidx, (int)(tg * 8u));
-                const ChrDev& C = chrs[cq];
-                bool hit = false;
-                if (cv) { const GevThr th = C.rthr[row]; hit = thr_hit(th, mulmod31(x2, T->inv16807), x2); }
-                const u32 h = rank_hits(cv, tg, hit, hc);
-                const u32 o = (u32)__shfl((int)xout, (int)(tg * 8u + (h < SB_OUT ? h : SB_OUT - 1u)));
-                if (hit && h < GEV_BK_CAP) {
-                    const u32 rv = o >> 1;                                                        // rand(), :2990
-                    const u64 dist = C.bp_dist;
-                    const u64 v = C.rbp[row] + (dist > 0x7fffffffull ? (u64)rv : (u64)(rv % (u32)dist));
-                    const size_t G = 2 * (b * SB_TASKS + tg) + side;
-                    sd.bk[G * GEV_BK_CAP + h] = v;
-                    sd.bk_idx[G * GEV_BK_CAP + h] = snp_lower_bound(C, v);     // first locus at or behind the breakpoint (what the dense stitch and the unit table work with)
+                    for (u32 q = 0; q < SB_TASKS; q++) { const unsigned long long mr = __ballot(rj && tg == q); if (g == q && mr) rej = true; }
                 }
-            }
-            count = 0;
-            wave_fence();
-        };
-        auto phase = [&]() {                               // ras_sim_loc_rec for the current gamete of every task that is still on the fast path
-            xout = srand8(T, W->r, seed_cur);              // srand(seed), :2977
-            hc = 0; count = 0;
+                count = 0;
+                wave_fence();
+            };
 #pragma unroll 1
             for (u32 q = 0; q < SB_TASKS; q++) {
-                if (!rl_u32((u32)run, q * 8u)) continue;
+                if (b * SB_TASKS + q >= n_tasks) break;
                 const ChrDev& C = chrs[rl_u32(cidx, q * 8u)];
-                scan_candidates(T, W, rl_u32(seed_cur, q * 8u) + 1u, C.r_amax, 0u, C.R, q, count, resolve);   // generator(seed+1), :2978
+                if (C.M >= 2) scan_candidates(T, W, rl_u32(S, q * 8u) + 2u, C.m_amax, 1u, C.M - 1u, q, count, resolve);   // generator_u(seed+2), i = 1..M-1
             }
             if (count) resolve();
-        };
-        // paternal gamete (:2447-2449)
-        side = 0; phase();
-        const u32 k_pat = hc;
-        bool slow = run && k_pat + 2u > SB_OUT;
-        const u32 o_sp = (u32)__shfl((int)xout, (int)(g * 8u + (k_pat < SB_OUT ? k_pat : SB_OUT - 1u)));
-        const u32 o_sm = (u32)__shfl((int)xout, (int)(g * 8u + (k_pat + 1u < SB_OUT ? k_pat + 1u : SB_OUT - 1u)));
-        const u32 start_pat = (o_sp >> 1) & 1u;            // rand()%2 after k_pat position draws, :2449
-        const u32 seed_mat = o_sm >> 1;                    // :2453
-        // maternal gamete (:2453-2455)
-        run = run && !slow; seed_cur = seed_mat;
-        side = 1; phase();
-        const u32 k_mat = hc;
-        slow = slow || (run && k_mat + 1u > SB_OUT);
-        const u32 o_st = (u32)__shfl((int)xout, (int)(g * 8u + (k_mat < SB_OUT ? k_mat : SB_OUT - 1u)));
-        const u32 start_mat = (o_st >> 1) & 1u;            // :2455
-        if (valid && j == 0) {
-            if (!active) {
-                sd.k[2 * t] = 0; sd.k[2 * t + 1] = 0; sd.bk_off[2 * t] = (u32)(2 * t) * GEV_BK_CAP; sd.bk_off[2 * t + 1] = (u32)(2 * t + 1) * GEV_BK_CAP;
-                sd.start[2 * t] = 0; sd.start[2 * t + 1] = 0; sd.seed_mat[t] = 0;
-            } else if (!slow) {
-                sd.k[2 * t] = k_pat; sd.k[2 * t + 1] = k_mat; sd.bk_off[2 * t] = (u32)(2 * t) * GEV_BK_CAP; sd.bk_off[2 * t + 1] = (u32)(2 * t + 1) * GEV_BK_CAP;
-                sd.start[2 * t] = (uint8_t)start_pat; sd.start[2 * t + 1] = (uint8_t)start_mat; sd.seed_mat[t] = seed_mat;
-            } else slow_list[atomicAdd(&sd.status[ST_SLOW_REC], 1u)] = (u32)t;
+            const u32 n = hc;
+            const bool last = cidx == (u32)(nchr - 1);
+            const bool slow = valid && (n + 2u > SB_OUT || rej);
+            const u32 o_sex = (u32)__shfl((int)xout, (int)(g * 8u + (n < SB_OUT ? n : SB_OUT - 1u)));
+            const u32 n2 = n + (last ? 1u : 0u);
+            const u32 o_nxt = (u32)__shfl((int)xout, (int)(g * 8u + (n2 < SB_OUT ? n2 : SB_OUT - 1u)));
+            seed_next = o_nxt >> 1;                                                                 // seed_loc of the next task, :2447
+            if (valid && j == 0 && !slow) {
+                sd.nmut[t] = n; sd.nm_off[t] = (u32)t * GEV_NM_CAP;
+                if (last) sd.sex[t / (size_t)nchr] = (uint8_t)(((o_sex >> 1) & 1u) + 1u);      // :2472
+                sd.seed_pat[t + 1] = seed_next;
+            }
+            slow_mut = slow;
+        }
+        // ---- both gametes of task t0 + g: t0 = 0 (task 0 alone, batch 0 only), then t0 = 8b + 1
+#pragma unroll 1
+        for (u32 pass = b == 0 ? 0u : 1u; pass < 2; pass++) {
+            const size_t t0 = pass ? b * SB_TASKS + 1 : 0, tr = t0 + g;
+            const bool rvalid = pass ? tr < n_tasks : g == 0;
+            const u32 rc = rvalid ? (u32)(tr % (size_t)nchr) : 0u;
+            const bool active = rvalid && chrs[rc].active != 0;       // inactive: another context owns this chromosome (only the seed chain is needed)
+            const u32 seed_pat = pass ? seed_next : seed0;
+            const bool late = pass && slow_mut;
+            u32 seed_cur = seed_pat, xout = 0, hc = 0, count = 0, side = 0;
+            bool run = active && !late;
+            auto resolve = [&]() {
+                wave_fence();
+                for (u32 c0 = 0; c0 < count; c0 += 64) {
+                    const u32 idx = c0 + lane; const bool cv = idx < count;
+                    const u32 row = cv ? W->cand_row[idx] : 0u, x2 = cv ? W->cand_x2[idx] : 1u, tg = cv ? (u32)W->cand_tag[idx] : 0u;
+                    const u32 cq = (u32)__shfl((int)rc, (int)(tg * 8u));
+                    const ChrDev& C = chrs[cq];
+                    bool hit = false;
+                    if (cv) { const GevThr th = C.rthr[row]; hit = thr_hit(th, mulmod31(x2, T->inv16807), x2); }
+                    const u32 h = rank_hits(cv, tg, hit, hc);
+                    const u32 o = (u32)__shfl((int)xout, (int)(tg * 8u + (h < SB_OUT ? h : SB_OUT - 1u)));
+                    if (hit && h < GEV_BK_CAP) {
+                        const u32 rv = o >> 1;                                                        // rand(), :2990
+                        const u64 dist = C.bp_dist;
+                        const u64 v = C.rbp[row] + (dist > 0x7fffffffull ? (u64)rv : (u64)(rv % (u32)dist));
+                        const size_t G = 2 * (t0 + tg) + side;
+                        sd.bk[G * GEV_BK_CAP + h] = v;
+                        sd.bk_idx[G * GEV_BK_CAP + h] = snp_lower_bound(C, v);     // first locus at or behind the breakpoint (what the dense stitch and the unit table work with)
+                    }
+                }
+                count = 0;
+                wave_fence();
+            };
+            auto phase = [&]() {                           // ras_sim_loc_rec for the current gamete of every task that is still on the fast path
+                xout = srand8(T, W->r, seed_cur);          // srand(seed), :2977
+                hc = 0; count = 0;
+#pragma unroll 1
+                for (u32 q = 0; q < SB_TASKS; q++) {
+                    if (!rl_u32((u32)run, q * 8u)) continue;
+                    const ChrDev& C = chrs[rl_u32(rc, q * 8u)];
+                    scan_candidates(T, W, rl_u32(seed_cur, q * 8u) + 1u, C.r_amax, 0u, C.R, q, count, resolve);   // generator(seed+1), :2978
+                }
+                if (count) resolve();
+            };
+            // paternal gamete (:2447-2449)
+            side = 0; phase();
+            const u32 k_pat = hc;
+            bool slow = run && k_pat + 2u > SB_OUT;
+            const u32 o_sp = (u32)__shfl((int)xout, (int)(g * 8u + (k_pat < SB_OUT ? k_pat : SB_OUT - 1u)));
+            const u32 o_sm = (u32)__shfl((int)xout, (int)(g * 8u + (k_pat + 1u < SB_OUT ? k_pat + 1u : SB_OUT - 1u)));
+            const u32 start_pat = (o_sp >> 1) & 1u;        // rand()%2 after k_pat position draws, :2449
+            const u32 seed_mat = o_sm >> 1;                // :2453
+            // maternal gamete (:2453-2455)
+            run = run && !slow; seed_cur = seed_mat;
+            side = 1; phase();
+            const u32 k_mat = hc;
+            slow = slow || (run && k_mat + 1u > SB_OUT);
+            const u32 o_st = (u32)__shfl((int)xout, (int)(g * 8u + (k_mat < SB_OUT ? k_mat : SB_OUT - 1u)));
+            const u32 start_mat = (o_st >> 1) & 1u;        // :2455
+            if (rvalid && j == 0 && !late) {
+                if (!active) {
+                    sd.k[2 * tr] = 0; sd.k[2 * tr + 1] = 0; sd.bk_off[2 * tr] = (u32)(2 * tr) * GEV_BK_CAP; sd.bk_off[2 * tr + 1] = (u32)(2 * tr + 1) * GEV_BK_CAP;
+                    sd.start[2 * tr] = 0; sd.start[2 * tr + 1] = 0; sd.seed_mat[tr] = 0;
+                } else if (!slow) {
+                    sd.k[2 * tr] = k_pat; sd.k[2 * tr + 1] = k_mat; sd.bk_off[2 * tr] = (u32)(2 * tr) * GEV_BK_CAP; sd.bk_off[2 * tr + 1] = (u32)(2 * tr + 1) * GEV_BK_CAP;
+                    sd.start[2 * tr] = (uint8_t)start_pat; sd.start[2 * tr + 1] = (uint8_t)start_mat; sd.seed_mat[tr] = seed_mat;
+                }
+            }
+            unsigned long long ms = __ballot(slow && j == 0);
+            if (ms) {                                       // rare: both gametes once more, one task per wave, in place
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");        // the records the batched pass wrote land first
+                while (ms) {
+                    const u32 q = (u32)(__ffsll((long long)ms) - 1) >> 3;
+                    ms &= ms - 1;
+                    slow_rec_task(Tg, chrs, rl_u32(rc, q * 8u), rl_u32(seed_pat, q * 8u), t0 + q, sd);
+                }
+            }
+        }
+        // rare: a slow mutation task once more, one task per wave, then the gametes of the task behind it (its seed is known now)
+        unsigned long long ms = __ballot(slow_mut && j == 0);
+        if (ms) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            while (ms) {
+                const u32 q = (u32)(__ffsll((long long)ms) - 1) >> 3;
+                ms &= ms - 1;
+                slow_mut_task(Tg, chrs, mut_seeds, (u32)nchr, b * SB_TASKS + q, n_tasks, sd);
+            }
         }
     }
 }

@@ -5,7 +5,7 @@ usage: pmc_instructions.py <out.json> <note> <pass-dir> [<pass-dir> ...]
 
 Each pass directory is what `rocprofv3 --pmc C1 C2 ... --kernel-trace --output-format csv -d <dir> -- python3 bench.py ...`
 wrote.  A dispatch's rows (one per counter instance) are summed, then averaged per kernel name over the launches; only the
-sampling kernels (k_rec_sample*, k_mut_sample*) are kept -- bench.py's `sampling_kernels` block sums their SQ_INSTS_VALU.
+sampling kernels (k_sample_batched; k_rec_sample*, k_mut_sample* of GEV_SAMPLE_BATCHED=0 and of older profiles) are kept -- bench.py's `sampling_kernels` block sums their SQ_INSTS_VALU.
 """
 import json
 import sys
@@ -14,7 +14,7 @@ import csv
 import glob
 import os
 
-KEEP = ("k_rec_sample8", "k_mut_sample8", "k_rec_sample", "k_mut_sample")
+KEEP = ("k_sample_batched", "k_rec_sample8", "k_mut_sample8", "k_rec_sample", "k_mut_sample")
 
 
 def main():
