@@ -475,41 +475,48 @@ def environmental_effects_specific_to_each_population(phens, gamma, x0=10.0, pre
     return x
 
 
+def _c_libm(f, x):
+    """the libm function f on every value of x as C calls it: Python's math raises OverflowError where C's exp / pow return +inf
+    (the only overflow of the selection formulas: exp of a large argument, pow(x, 2) of a large x); NaN and +-inf pass through"""
+    import math
+    out = []
+    for v in np.asarray(x, dtype=np.float64).tolist():
+        try:
+            out.append(f(v))
+        except OverflowError:
+            out.append(math.inf)
+    return np.array(out, dtype=np.float64)
+
+
 def selection_func(kind, p1, p2, z):
     """Simulation::ras_selection_func (reference src/Simulation.cpp:3386-3428) for generations >= 1 (generation 0: 1 for all);
-    logit and thr; z = selection value standardised to generation 0 (ras_compute_mating_value_selection_value, :3300-3342)"""
+    z = selection value standardised to generation 0 (ras_compute_mating_value_selection_value, :3300-3342).  C's semantics:
+    the literal formulas in the reference's operation order, every + - * / rounded to double by numpy (overflow gives inf,
+    division by zero +-inf or NaN, no exception), libm calls through Python's math (glibc), overflow giving inf."""
     import math
-    if kind == "logit":
-        out = []
-        for v in np.asarray(z, dtype=np.float64).tolist():
-            y = math.exp(p1 + p2 * v)
-            out.append(y / (1 + y))
-        return np.array(out)
-    if kind == "thr":
-        return np.where(np.asarray(z) <= p2, p1, 1.0)
-    if kind == "probit":                      # CommFunc::NormalCDF (src/CommFunc.cpp:257-262): .5*(1+erf((x-mu)/(sqrt(2)*sigma)))
-        return np.array([.5 * (1 + math.erf((v - p1) / (math.sqrt(2) * p2))) for v in np.asarray(z, dtype=np.float64).tolist()])
-    if kind == "stab":                        # CommFunc::NormalPDF (:266-270): 1/(sqrt(2*pi)*sigma) * exp(-0.5*pow((x-mu)/sigma,2))
-        pi = 3.1415926                         # the reference's own constant (src/CommFunc.cpp:4)
-        return np.array([1 / (math.sqrt(2.0 * pi) * p2) * math.exp(-0.5 * math.pow((v - p1) / p2, 2)) for v in np.asarray(z, dtype=np.float64).tolist()])
+    z = np.asarray(z, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        if kind == "logit":                   # y = exp(b0 + b1*z), y/(1+y): NaN where exp overflows (inf/inf)
+            y = _c_libm(math.exp, p1 + p2 * z)
+            return y / (1 + y)
+        if kind == "thr":                     # z <= thr ? p1 : 1 (NaN z: 1)
+            return np.where(z <= p2, p1, 1.0)
+        if kind == "probit":                  # CommFunc::NormalCDF (src/CommFunc.cpp:257-262): .5*(1+erf((x-mu)/(sqrt(2)*sigma)))
+            return .5 * (1 + _c_libm(math.erf, (z - p1) / (math.sqrt(2) * np.float64(p2))))
+        if kind == "stab":                    # CommFunc::NormalPDF (:266-270): 1/(sqrt(2*pi)*sigma) * exp(-0.5*pow((x-mu)/sigma,2))
+            pi = 3.1415926                     # the reference's own constant (src/CommFunc.cpp:4)
+            sq = _c_libm(lambda v: math.pow(v, 2), (z - p1) / np.float64(p2))
+            return 1 / (math.sqrt(2.0 * pi) * np.float64(p2)) * _c_libm(math.exp, -0.5 * sq)
     raise NotImplementedError(kind)
 
 
 def ras_selection_func(gen_num, kind, p1, p2, z):
     """the whole of Simulation::ras_selection_func (reference src/Simulation.cpp:3386-3428): generation 0 and "none" give 1 for all,
     "" is the reference's default (logit 0 1, :3393-3399: y = exp(b0 + b1*z), y/(1+y)); the other kinds as selection_func"""
-    import math
     if gen_num == 0 or kind in (None, "none"):
         return np.ones(len(z))
     if kind == "":
-        out = []
-        for v in np.asarray(z, dtype=np.float64).tolist():
-            try:
-                y = math.exp(0.0 + 1.0 * v)
-            except OverflowError:                  # (C's exp gives inf there, and inf/(1+inf) is NaN)
-                y = math.inf
-            out.append(y / (1 + y))
-        return np.array(out)
+        return selection_func("logit", 0.0, 1.0, z)
     return selection_func(kind, p1, p2, z)
 
 

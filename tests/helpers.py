@@ -141,6 +141,37 @@ def check_cvval_dump(ctx, fx, ip, nchr, nphen, label):
             assert np.array_equal(np.frombuffer(hashlib.sha256(txt).digest(), dtype=np.uint8), fx[k]), f"{label}: CV genotypes differ from the reference's .cvval dump (pop {ip} chr {ic})"
 
 
+GEF_OUTPUTS = ("additive", "dominance", "bv", "e_noise", "parental_effect", "phen")
+
+
+def gef_exact_outputs(gen_num, ve, vf):
+    """the outputs of ras_scale_AD_compute_GEF that a device run must give bit for bit: additive, dominance and bv are one IEEE
+    division / add of identical inputs (s_a and s_d come from the host's std::sqrt, the library is built without contraction), and
+    so is the parental effect of generation > 0 (beta * (f + m)); phen too when neither e (ve > 0) nor generation 0's parental
+    stream (vf > 0) enters it.  e_noise and the rest go through the device's log / sqrt and a parallel sum."""
+    exact = ["additive", "dominance", "bv"]
+    if gen_num > 0 or vf <= 0:
+        exact.append("parental_effect")                            # (generation 0, vf <= 0: 0 for all)
+    if ve <= 0:
+        exact.append("e_noise")                                    # 0 for all
+        if vf <= 0 or gen_num > 0:
+            exact.append("phen")
+    return exact
+
+
+def check_gef_outputs(got, want, gen_num, ve, vf, rtol, label):
+    """got: dict of the six outputs; want: [n][6] (GEF_OUTPUTS order).  rtol == 0: everything bit for bit (the oracle); else the
+    outputs of gef_exact_outputs bit for bit and the others within rtol"""
+    exact = GEF_OUTPUTS if rtol == 0.0 else gef_exact_outputs(gen_num, ve, vf)
+    for j, nm in enumerate(GEF_OUTPUTS):
+        a, b = np.asarray(got[nm]), want[:, j]
+        if nm in exact:
+            bad = np.flatnonzero(np.ascontiguousarray(a).view(np.uint64) != np.ascontiguousarray(b).view(np.uint64))
+            assert len(bad) == 0, f"{label}: scaled {nm} not bit-identical: {len(bad)} values differ, first at {bad[0]} ({a[bad[0]]!r} vs {b[bad[0]]!r})"
+        else:
+            assert np.allclose(a, b, rtol=rtol, atol=1e-12), f"{label}: scaled {nm} differs by more than {rtol} relative: max abs diff {np.max(np.abs(a - b))}"
+
+
 def replay_case(lib, fx, gen0_seeds, label, device=-1, float_exact=True, check_lists=True, max_gen=None, check_gef=False, gef_rtol=0.0):
     """Run the whole fixture through `lib` and compare every dumped quantity."""
     n_pop, nchr, nphen, ngen = int(fx["n_pop"]), int(fx["nchr"]), int(fx["nphen"]), int(fx["n_gen"])
@@ -189,11 +220,7 @@ def replay_case(lib, fx, gen0_seeds, label, device=-1, float_exact=True, check_l
                     gi, want = fx[k + "in"], fx[k + "out"]
                     got = ctx.scale_ad_compute_gef(ip, iph, g, int(fx[k + "seed"]), va, vd, ve, vf, beta, s2a, s2d,
                                                    common_sibling=gi[:, 0], f_father=gi[:, 1], f_mother=gi[:, 2])
-                    for j, nm in enumerate(("additive", "dominance", "bv", "e_noise", "parental_effect", "phen")):
-                        if gef_rtol == 0.0:
-                            assert bits_equal(got[nm], want[:, j]), f"{label}: scaled {nm} not bit-identical (gen {g} phen {iph}), max diff {np.max(np.abs(got[nm]-want[:, j]))}"
-                        else:
-                            assert np.allclose(got[nm], want[:, j], rtol=gef_rtol, atol=1e-12), f"{label}: scaled {nm} differs by more than {gef_rtol} relative (gen {g} phen {iph}): max abs diff {np.max(np.abs(got[nm]-want[:, j]))}"
+                    check_gef_outputs(got, want, g, ve, vf, gef_rtol, f"{label}: gen {g} phen {iph}")
         if f"g{g}_moves" in fx:
             ctx.migrate(derive_moves(fx, g))
             for ip in range(n_pop):
@@ -555,3 +582,66 @@ def closed_loop_migration_case(lib, fx, label, device=-1, exact=True, mate="host
         for ip in range(n_pop):
             compare_dense(ctx, fx, g, ip, nchr, label)
     ctx.close()
+
+
+# ---- the reference's selection formulas evaluated as C evaluates them ------------------------------------------------------------
+def c_libm(name, x):
+    """exp / erf / sqrt / pow(x, 2) of the double x, computed with mpmath at 50 digits and rounded once to the nearest double:
+    what a correctly rounded libm returns (glibc's are within an ulp of it).  Overflow gives +-inf, NaN and +-inf pass through."""
+    import math
+    import mpmath
+    from mpmath.libmp import to_float
+    x = float(x)
+    if math.isnan(x):
+        return math.nan
+    if math.isinf(x):
+        return {"exp": math.inf if x > 0 else 0.0, "erf": math.copysign(1.0, x), "sqrt": math.inf if x > 0 else math.nan, "pow2": math.inf}[name]
+    with mpmath.workdps(50):
+        v = mpmath.mpf(x)
+        r = {"exp": mpmath.exp, "erf": mpmath.erf, "sqrt": mpmath.sqrt, "pow2": lambda t: t * t}[name](v)
+        return to_float(r._mpf_, rnd="n")          # round to nearest (mpmath's float() truncates)
+
+
+def c_selection_formula(kind, p1, p2, z):
+    """Simulation::ras_selection_func (reference src/Simulation.cpp:3386-3428, CommFunc.cpp:257-270) at every z, evaluated the way C
+    evaluates it: the literal formula in its own operation order, every + - * / rounded to double (inf / NaN where C gives them), every
+    libm call c_libm.  Independent of geneevolve_amd.host's mirror, which calls glibc."""
+    import math
+    out = []
+    f = np.float64
+    with np.errstate(all="ignore"):
+        for v in np.asarray(z, dtype=np.float64).tolist():
+            v = f(v)
+            if kind in ("", "logit"):
+                b0, b1 = (f(0.0), f(1.0)) if kind == "" else (f(p1), f(p2))
+                y = f(c_libm("exp", b0 + b1 * v))
+                r = y / (f(1) + y)
+            elif kind == "probit":
+                r = f(.5) * (f(1) + f(c_libm("erf", (v - f(p1)) / (f(c_libm("sqrt", 2.0)) * f(p2)))))
+            elif kind == "stab":
+                pi = f(3.1415926)
+                r = f(1) / (f(c_libm("sqrt", f(2.0) * pi)) * f(p2)) * f(c_libm("exp", f(-0.5) * f(c_libm("pow2", (v - f(p1)) / f(p2)))))
+            elif kind == "thr":
+                r = f(p1) if v <= f(p2) else f(1.0)
+            elif kind in ("none", None):
+                r = f(1.0)
+            else:
+                raise NotImplementedError(kind)
+            out.append(float(r))
+    return np.array(out, dtype=np.float64)
+
+
+def ulp_distance(a, b):
+    """elementwise distance in units in the last place between float64 arrays: the number of doubles between them (0 where both are
+    NaN; 2**63 where only one is)"""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    mask = np.int64(0x7FFFFFFFFFFFFFFF)
+    ia, ib = a.view(np.int64), b.view(np.int64)
+    ia = np.where(ia < 0, -(ia & mask), ia)                        # the doubles in integer order (-0.0 and 0.0 both 0)
+    ib = np.where(ib < 0, -(ib & mask), ib)
+    same = (ia >= 0) == (ib >= 0)
+    with np.errstate(over="ignore"):
+        d = np.where(same, np.abs(ia - np.where(same, ib, 0)).astype(np.float64), np.abs(ia.astype(np.float64)) + np.abs(ib.astype(np.float64)))
+    na, nb = np.isnan(a), np.isnan(b)
+    d = np.where(na & nb, 0.0, d)
+    return np.where(na ^ nb, 2.0 ** 63, d)
