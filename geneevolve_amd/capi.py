@@ -52,6 +52,20 @@ class gev_generation_result(C.Structure):
                 ("num_males_mate", C.c_uint64), ("num_females_mate", C.c_uint64)]
 
 
+class gev_assort_params(C.Structure):
+    _fields_ = [("pop_size", C.c_uint64), ("mat_cor", C.c_double), ("mm_percent", C.c_double), ("avoid_inbreeding", C.c_int32),
+                ("offspring_dist", C.c_int32)]
+
+
+class gev_assort_result(C.Structure):
+    _fields_ = [("num_males_mate", C.c_uint64), ("num_females_mate", C.c_uint64), ("n_couples", C.c_uint64), ("n_inbreed", C.c_uint64),
+                ("n_offspring", C.c_uint64)]
+
+
+def _assort_result(r):
+    return {k: int(getattr(r, k)) for k, _ in gev_assort_result._fields_}
+
+
 COUPLE_DTYPE = np.dtype([("pos_male", "<u8"), ("pos_female", "<u8"), ("inbreed", "<i4"), ("num_offspring", "<i4")])
 PART_DTYPE = np.dtype([("st", "<u8"), ("en", "<u8"), ("hap_index", "<u8"), ("root_population", "<i4"), ("reserved", "<i4")])
 MOVE_DTYPE = np.dtype([("src_pop", "<i4"), ("dst_pop", "<i4"), ("src_pos", "<u8")])
@@ -66,6 +80,8 @@ ABI_SYMBOLS = [
     "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
     "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
     "compute_selection", "download_selection", "get_selection_gen0", "set_selection_gen0", "generation_begin_selected", "random_mate_selected",
+    "assort_mate", "assort_mate_selected", "last_assort_result", "generation_begin_assort", "generation_begin_assort_selected",
+    "dbg_assort_knobs", "dbg_assort_stats",
     "dbg_verify_planes", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
@@ -298,6 +314,74 @@ class GevContext:
         self._call_new("random_mate_selected", C.c_int(pop), C.c_uint32(int(seed)), C.c_size_t(pop_size), _p(couples), C.byref(nm), C.byref(nf))
         return couples, nm.value, nf.value
 
+    def _assort_args(self, pop, seeds, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree):
+        par = gev_assort_params(int(pop_size), float(mat_cor), float(mm_percent), int(bool(avoid_inbreeding)),
+                                ord(offspring_dist) if isinstance(offspring_dist, str) else int(offspring_dist))
+        sd = (C.c_uint32 * 4)(*[int(x) for x in (list(seeds) + [0, 0, 0, 0])[:4]])
+        ped = None if pedigree is None else _arr(pedigree, np.int64).reshape(-1, 5)
+        return par, sd, ped
+
+    def assort_mate(self, pop, seeds, mating_value, selection_value_func, pop_size, mat_cor, mm_percent=0.0, avoid_inbreeding=False,
+                    offspring_dist="p", pedigree=None, want_couples=True):
+        """Simulation::assort_mate on the library's side -> (couples or None, result dict).  seeds: the 3 (4 with 'p') ras_glob_seed()
+        values; selection_value_func None = every value 1; pedigree [n][5] (ID_Father, FF, FM, MF, MM) for avoid_inbreeding.
+        The couples stay in the library for reproduce(pop, None, ..., n_people=result["n_offspring"])."""
+        par, sd, ped = self._assort_args(pop, seeds, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree)
+        mv = _arr(mating_value, np.float64)
+        svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
+        couples = np.zeros(len(mv), dtype=COUPLE_DTYPE) if want_couples else None      # n_couples <= n_people
+        res = gev_assort_result()
+        self._call_new("assort_mate", C.c_int(pop), C.byref(par), sd, _p(mv), _p(svf), _p(ped), _p(couples), C.byref(res))
+        r = _assort_result(res)
+        return (couples[:r["n_couples"]].copy() if want_couples else None), r
+
+    def assort_mate_selected(self, pop, seeds, pop_size, mat_cor, mm_percent=0.0, avoid_inbreeding=False, offspring_dist="p",
+                             pedigree=None, want_couples=True):
+        """assort_mate() on the mating values and selection_value_func compute_selection() left in the library"""
+        par, sd, ped = self._assort_args(pop, seeds, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree)
+        couples = np.zeros(self.pop_size(pop), dtype=COUPLE_DTYPE) if want_couples else None
+        res = gev_assort_result()
+        self._call_new("assort_mate_selected", C.c_int(pop), C.byref(par), sd, _p(ped), _p(couples), C.byref(res))
+        r = _assort_result(res)
+        return (couples[:r["n_couples"]].copy() if want_couples else None), r
+
+    def last_assort_result(self, want_couples=False):
+        """-> (result dict, couples or None) of the context's last completed assort_mate()"""
+        res = gev_assort_result()
+        self._call_new("last_assort_result", C.byref(res), None)
+        r = _assort_result(res)
+        couples = None
+        if want_couples:
+            couples = np.zeros(r["n_couples"], dtype=COUPLE_DTYPE)
+            self._call_new("last_assort_result", C.byref(res), _p(couples))
+        return r, couples
+
+    def dbg_assort_knobs(self, narrow_window=False, short_poisson=False):
+        """set the test hooks of the exact fallbacks for the following assort_mate() calls (both off by default)"""
+        self._call_new("dbg_assort_knobs", C.c_int(int(bool(narrow_window))), C.c_int(int(bool(short_poisson))))
+
+    def dbg_assort_stats(self):
+        """-> {chunks, direct, pois_reruns} of the last assort_mate()"""
+        out = (C.c_ulonglong * 3)()
+        self._call_new("dbg_assort_stats", out)
+        return {"chunks": int(out[0]), "direct": int(out[1]), "pois_reruns": int(out[2])}
+
+    def generation_begin_assort(self, pop, glob_state, pop_size, mat_cor, mm_percent=0.0, avoid_inbreeding=False, offspring_dist="p",
+                                mating_value=None, selection_value_func=None, pedigree=None, selected=False):
+        """assort_mate -> reproduce -> ras_compute_AD of one generation as one call pair, every seed drawn by the library from glob_state
+        (returns once the mating counts are known, without waiting for the rest); selected=True: on the values compute_selection()
+        left in the library.  -> the assort result dict (n_couples, n_offspring, ...) of this generation"""
+        par, _, ped = self._assort_args(pop, (), pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree)
+        if selected:
+            self._call_new("generation_begin_assort_selected", C.c_int(pop), C.c_uint32(int(glob_state)), C.byref(par), _p(ped))
+        else:
+            mv = _arr(mating_value, np.float64)
+            svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
+            self._call_new("generation_begin_assort", C.c_int(pop), C.c_uint32(int(glob_state)), C.byref(par), _p(mv), _p(svf), _p(ped))
+        r, _ = self.last_assort_result()
+        self._pending_people, self._pending_couples = r["n_offspring"], r["n_couples"]
+        return r
+
     def compute_selection(self, pop, gen_num, func, par1, par2, omega, lambda_, phen_shift=None, want=("mating_value", "selection_value", "selection_value_func")):
         """Simulation::ras_compute_mating_value_selection_value + ras_selection_func on the device, from the phenotypes the last
         scale_ad_compute_gef() of every phenotype left there.  func: a key of SELECTION_FUNCS (the reference's name; None = "none")
@@ -340,17 +424,17 @@ class GevContext:
         """random_mate -> reproduce -> ras_compute_AD of one generation, enqueued as one unit (returns without waiting)"""
         svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
         self._call("generation_begin", C.c_int(pop), C.c_uint32(int(glob_state)), C.c_size_t(pop_size), _p(svf))
-        self._pending_people = pop_size
+        self._pending_people = self._pending_couples = pop_size
 
     def generation_begin_selected(self, pop, glob_state, pop_size):
         """generation_begin() mating on the selection_value_func compute_selection() left in the library (nothing uploaded)"""
         self._call_new("generation_begin_selected", C.c_int(pop), C.c_uint32(int(glob_state)), C.c_size_t(pop_size))
-        self._pending_people = pop_size
+        self._pending_people = self._pending_couples = pop_size
 
     def generation_end(self, want_couples=False, want_sex=True):
         """-> dict(glob_state, seed_mate, seed_reproduce, num_males_mate, num_females_mate, couples, sex)"""
         res = gev_generation_result()
-        couples = np.zeros(self._pending_people, dtype=COUPLE_DTYPE) if want_couples else None
+        couples = np.zeros(self._pending_couples, dtype=COUPLE_DTYPE) if want_couples else None
         sex = np.zeros(self._pending_people, dtype=np.uint8) if want_sex else None
         self._call("generation_end", C.byref(res), _p(couples), _p(sex))
         return {"glob_state": res.glob_state, "seed_mate": res.seed_mate, "seed_reproduce": res.seed_reproduce,

@@ -1970,3 +1970,4 @@ __global__ void __launch_bounds__(256) k_format_bed(const u64* __restrict__ snpm
 #define GEV_LISTS_KERNELS
 #include "gev_lists.h"
 #include "gev_mate.h"
+#include "gev_assort.h"

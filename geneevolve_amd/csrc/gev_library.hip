@@ -297,11 +297,21 @@ struct gev_ctx {
     // =auto measures it (a few generations per candidate, wall time between consecutive gev_reproduce returns).
     int stitch_occ = 0 /* 0 = by row length */, stitch_occ_env = 0; bool stitch_occ_auto = false;
     struct PendingRepro { bool active = false, has_mut = false, pre = false; int pop = 0, attempt = 0; size_t n_people = 0, n_status = 0; u32 seed = 0; u32* hstatus = nullptr; double th0 = 0, th1 = 0, th2 = 0;
-                          bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; const double* d_svf = nullptr; /* with has_svf: what the mating reads */ u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr; } pend;
+                          bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; const double* d_svf = nullptr; /* with has_svf: what the mating reads */ u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr;
+                          bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0; } pend;
     struct OccTune { int phase = 0 /* 0 idle, 1 measuring, 2 settled */, idx = 0, n = 0, best_occ = 8; double last = 0, cur_min = 0, best = 0; size_t people = 0; unsigned age = 0; } tune;
     DevBuf d_snpmajor, d_text;
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
+    // gev_assort_mate (gev_assort.h): scratch, the last call's result and couple arrays, test knobs
+    struct AssortState {
+        DevBuf stats, wlo, ww, ends, start, cm, cf, om, of, males, females, rnd, scnt, soff, sfill, stgt, ssrc, kept, sorted_m, sorted_f,
+               tblk, t1, t2, i1, i2, pm, pf, inb, num, ocnt, ooff, pois, ped, mv, svf, stat, sort_tmp;
+        gev_assort_result res = {0, 0, 0, 0, 0};
+        bool valid = false;                               // res / pm / pf / inb / num describe the last call
+        bool narrow_window = false, short_poisson = false;
+        unsigned long long n_chunks = 0, n_direct = 0, pois_reruns = 0;
+    } am;
     DevBuf d_cvdone;
     DevBuf d_cnt, d_sums, d_map, d_cvm, d_addchr, d_domchr, d_add, d_dom, d_flag, d_stage, d_thr32, d_tmp;
     // per-generation work tables (gev_kernels.h: ChrWork / CvWork / AdWork) are written into a ring of pinned host memory and
@@ -1646,18 +1656,22 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     const bool sampled = q.pre && attempt == 0;              // seeds drawn and sampling done by a head start
     if (q.fused && !sampled) {
         HIPC(hipMemsetAsync(sc.status.p, 0, q.n_status * sizeof(u32), S));
-        // glob_generator's draws in the reference's order: random_mate (:2092), reproduce (:2398), then one per (offspring, chromosome) inside ras_add_mutation (:2500)
-        GEVC(enqueue_glob(c, S, q.glob_state, nullptr, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
+        // glob_generator's draws in the reference's order: random_mate (:2092), reproduce (:2398), then one per (offspring, chromosome) inside ras_add_mutation (:2500).
+        // An assortative generation's mating seeds were drawn in front of glob_state: gv[0] = its srand seed (:2170), the rest from glob_state on.
+        if (q.assort) {
+            HIPC(hipMemsetD32Async((hipDeviceptr_t)gv, (int)q.assort_seed0, 1, S));
+            GEVC(enqueue_glob(c, S, q.glob_state, nullptr, 1 + (q.has_mut ? T : 0), gv + 1, status + ST_GLOB_STATE, status + ST_FLAGS));
+        } else GEVC(enqueue_glob(c, S, q.glob_state, nullptr, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     }
     // (the mating stream starts here: it needs the seeds, not the state behind them)
     if (X != S) { HIPC(hipEventRecord(sc.ev_fork, S)); HIPC(hipStreamWaitEvent(X, sc.ev_fork, 0)); }
     // overlap mode 2: only the ALU-bound sampling shares the GPU with the previous generation's stitch; everything latency-bound waits for it
     if (c->sparse_after_stitch && c->planes_pending) HIPC(hipStreamWaitEvent(X, c->ev_planes, 0));
-    if (q.fused) {
+    if (q.fused && !q.assort) {
         GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father.as<u32>(), sc.mother.as<u32>(),
                           c->d_couples.as<gev_couple>(), status + ST_NM_MATE, status + ST_FLAGS));
     }
-    if (q.fused && c->chain_draws >= 0) {                    // where glob_generator will stand when the host comes back for the next generation
+    if (q.fused && !q.assort && c->chain_draws >= 0) {       // where glob_generator will stand when the host comes back for the next generation
         hipLaunchKernelGGL(k_glob_skip, dim3(1), dim3(64), 0, S, (const u32*)(status + ST_GLOB_STATE), (u32)c->chain_draws, status + ST_NEXT_STATE);
         KCHECK();
         HIPC(hipEventRecord(sc.ev_chain, S));
@@ -1745,10 +1759,10 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     // couples == NULL: the couples gev_random_mate left on the device for this population
     const bool dev_couples = couples == nullptr;
     if (dev_couples && !(sc.mated && sc.mate_pop == pop && sc.mate_n == n_people))
-        return fail(GEV_ESTATE, "reproduce: couples is NULL but no gev_random_mate of population %d for %zu offspring precedes", pop, n_people);
+        return fail(GEV_ESTATE, "reproduce: couples is NULL but no gev_random_mate / gev_assort_mate of population %d for %zu offspring precedes", pop, n_people);
     if (dev_couples && sc.mate_epoch != P.layout_epoch)
         return fail(GEV_ESTATE, "reproduce: couples is NULL but population %d changed (migration, rows removed or imported, order materialised) "
-                    "after the gev_random_mate that formed them: its positions no longer name the same rows", pop);
+                    "after the gev_random_mate / gev_assort_mate that formed them: its positions no longer name the same rows", pop);
     // pinned staging: [father | mother | mut_seeds | status], written by the host, copied asynchronously
     const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
     const size_t stage_words = 2 * n_people + (has_mut ? T : 0) + n_status;
@@ -1793,7 +1807,7 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
 
     gev_ctx::PendingRepro& q = c->pend;
     q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = (u32)seed_reproduce; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
-    q.fused = false; q.has_svf = false; q.pool_rebuilt = false;
+    q.fused = false; q.assort = false; q.has_svf = false; q.pool_rebuilt = false;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     return GEV_OK;
@@ -1903,6 +1917,7 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
     q.pool_rebuilt = false;
     q.fused = true; q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
+    q.assort = false;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     if (c->chain_draws >= 0 && c->head_start == 0) GEVC(enqueue_chain_head_start(c));
@@ -2013,13 +2028,14 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
     for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) P.cv[p][k].frq_valid = ad_done;
     c->ad_cached_pop = ad_done ? pop : -1;
     if (q.fused) {
-        c->chain_valid = c->chain_draws >= 0; c->chain_state = hstatus[ST_NEXT_STATE];
+        c->chain_valid = !q.assort && c->chain_draws >= 0; c->chain_state = hstatus[ST_NEXT_STATE];     // (no head start behind an assortative generation)
         if (sex_out) memcpy(sex_out, q.hsex, n_people);
         if (res) {
             res->glob_state = hstatus[ST_GLOB_STATE]; res->seed_mate = q.hseeds2[0]; res->seed_reproduce = q.hseeds2[1]; res->reserved = 0;
-            res->num_males_mate = hstatus[ST_NM_MATE]; res->num_females_mate = hstatus[ST_NF_MATE];
+            res->num_males_mate = q.assort ? q.am_nm : hstatus[ST_NM_MATE]; res->num_females_mate = q.assort ? q.am_nf : hstatus[ST_NF_MATE];
         }
-        if (couples_out) { HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n_people * sizeof(gev_couple), hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
+        const size_t n_rec = q.assort ? q.am_couples : n_people;
+        if (couples_out) { HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n_rec * sizeof(gev_couple), hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     } else if (sex_out) { HIPC(hipMemcpyAsync(sex_out, sc.sex.p, n_people, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.layout_epoch++; P.drop_selection();
     c->gen_counter++;
@@ -2096,6 +2112,357 @@ int gev_random_mate_selected(gev_ctx* c, int pop, uint32_t seed, size_t pop_size
 {
     GEVC(check_selection(c, pop, "random_mate_selected"));
     return random_mate(c, pop, seed, nullptr, true, pop_size, couples_out, num_males_mate, num_females_mate);
+}
+// ---- Simulation::assort_mate (src/Simulation.cpp:2167-2360) on the device (gev_assort.h) -----------------------------------------
+size_t gev_sort_pairs_scratch_bytes(size_t n);
+int gev_sort_pairs_f64(const double* d_x, const uint32_t* d_gather, const uint32_t* d_vals, size_t n, uint32_t* d_vals_out, void* d_tmp, hipStream_t st);
+static int am_sort(gev_ctx* c, hipStream_t st, const double* x, const u32* gather, const u32* vals, size_t n, u32* out)
+{
+    GEVC(c->am.sort_tmp.ensure(gev_sort_pairs_scratch_bytes(n), st));
+    const int e = gev_sort_pairs_f64(x, gather, vals, n, out, c->am.sort_tmp.p, st);
+    if (e) return fail(GEV_EDEVICE, "assort_mate: device sort failed: %s", hipGetErrorString((hipError_t)e));
+    return GEV_OK;
+}
+// std::random_shuffle of m entries on the rand() values R[0 .. m-2]: src[q] = original position of the entry that ends at p0 + q
+static int am_shuffle(gev_ctx* c, hipStream_t st, const u32* R, size_t m, size_t p0, size_t p1, DevBuf& src)
+{
+    gev_ctx::AssortState& A = c->am;
+    const size_t w = (m + 1) * sizeof(u32);
+    GEVC(A.scnt.ensure(w, st)); GEVC(A.soff.ensure(w, st)); GEVC(A.sfill.ensure(w, st)); GEVC(A.stgt.ensure(w, st));
+    GEVC(src.ensure(std::max<size_t>(p1 - p0, 1) * sizeof(u32), st));
+    HIPC(hipMemsetAsync(A.scnt.p, 0, w, st)); HIPC(hipMemsetAsync(A.sfill.p, 0, w, st));
+    const unsigned nb = (unsigned)ceil_div(m, 256);
+    hipLaunchKernelGGL(k_shuf_count, dim3(nb), dim3(256), 0, st, R, m, A.scnt.as<u32>());
+    GEVC(scan_u32_on(st, c->d_sums, A.scnt.as<u32>(), m, A.soff.as<u32>()));
+    hipLaunchKernelGGL(k_shuf_fill, dim3(nb), dim3(256), 0, st, R, m, A.soff.as<u32>(), A.sfill.as<u32>(), A.stgt.as<u32>());
+    if (p1 > p0) hipLaunchKernelGGL(k_shuf_trace, dim3((unsigned)ceil_div(p1 - p0, 256)), dim3(256), 0, st, R, m, A.soff.as<u32>(), A.stgt.as<u32>(), p0, p1, src.as<u32>());
+    KCHECK();
+    return GEV_OK;
+}
+static u32 h_minstd_seed(u32 s) { const u32 x = s % GEV_M31; return x ? x : 1u; }
+static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const uint32_t* seeds, const double* mating_value, const double* selection_value_func,
+                       bool dev_sel, const int64_t* pedigree, gev_couple* couples_out, gev_assort_result* res, bool dev_records = false)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (!par || !seeds) return fail(GEV_EINVAL, "assort_mate: null params or seeds");
+    PopState& P = c->pop[pop];
+    if (!P.gen0) return fail(GEV_ESTATE, "assort_mate: population %d has no current generation", pop);
+    if (!dev_sel && !mating_value) return fail(GEV_EINVAL, "assort_mate: mating_value is NULL");
+    const int dist = par->offspring_dist;
+    const bool pois = dist == 'p' || dist == 'P', fixed = dist == 'f' || dist == 'F';
+    if (!pois && !fixed) return fail(GEV_EINVAL, "assort_mate: offspring distribution '%c' is neither 'p' nor 'f'", (char)dist);
+    const bool avoid = par->avoid_inbreeding != 0;
+    if (avoid && !pedigree) return fail(GEV_EINVAL, "assort_mate: avoid_inbreeding needs the pedigree ids");
+    if (!std::isfinite(par->mat_cor)) return fail(GEV_EINVAL, "assort_mate: mat_cor is not finite");
+    if (par->pop_size == 0 || par->pop_size >= 0x7fffffffull) return fail(GEV_EINVAL, "assort_mate: pop_size %llu out of range", (unsigned long long)par->pop_size);
+    const size_t n_h = P.n_people;
+    if (n_h == 0 || n_h >= 0x3fffffffull) return fail(GEV_EINVAL, "assort_mate: population of %zu individuals", n_h);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    gev_ctx::AssortState& A = c->am;
+    A.valid = false;
+    gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
+    sc.mated = false;
+    // father / mother of this scratch set were last read by the stitch two generations back
+    GEVC(harvest_timing(c, sc));
+    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
+    const u32* logical = nullptr;
+    if (!P.logical.empty()) {                                   // after a cross-GPU migration positions are not rows
+        GEVC(upload_table(c, c->d_logical, P.logical.data(), n_h * sizeof(u32), st));
+        logical = c->d_logical.as<u32>();
+    }
+    const double* d_mv; const double* d_svf = nullptr;
+    if (dev_sel) { d_mv = P.d_sel[P.sbuf].as<double>(); d_svf = d_mv + 2 * n_h; }
+    else {
+        GEVC(A.mv.ensure(n_h * sizeof(double), st));
+        HIPC(hipMemcpyAsync(A.mv.p, mating_value, n_h * sizeof(double), hipMemcpyHostToDevice, st));
+        d_mv = A.mv.as<double>();
+        if (selection_value_func) {
+            GEVC(A.svf.ensure(n_h * sizeof(double), st));
+            HIPC(hipMemcpyAsync(A.svf.p, selection_value_func, n_h * sizeof(double), hipMemcpyHostToDevice, st));
+            d_svf = A.svf.as<double>();
+        }
+    }
+    const int64_t* d_ped = nullptr;
+    if (avoid) {
+        GEVC(A.ped.ensure(n_h * 5 * sizeof(int64_t), st));
+        HIPC(hipMemcpyAsync(A.ped.p, pedigree, n_h * 5 * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        d_ped = A.ped.as<int64_t>();
+    }
+    const uint8_t* sex = P.d_sex[P.cur].as<uint8_t>();
+    const double mm = par->mm_percent;
+    GEVC(A.stat.ensure(AMS_WORDS * sizeof(u32), st));
+    HIPC(hipMemsetAsync(A.stat.p, 0, AMS_WORDS * sizeof(u32), st));
+    u32* stat = A.stat.as<u32>();
+
+    // :2184-2216 marriage draws: windows of start offsets per chunk, the chain over the chunks, one walk per chunk from its true start
+    const u32 nc = (u32)ceil_div(n_h, AM_B);
+    const double alpha = A.narrow_window ? 0.0 : 4.0;
+    const u32 kmin = A.narrow_window ? 0u : 16u;
+    const u32 wcap = (u32)round_up(2 * ((size_t)std::ceil(alpha * std::sqrt((double)n_h / 4.0)) + kmin + 1) + 1, 256);
+    const u32 x_sel = h_minstd_seed(seeds[1]);
+    GEVC(A.stats.ensure(nc * sizeof(double2), st)); GEVC(A.wlo.ensure(nc * sizeof(u32), st)); GEVC(A.ww.ensure(nc * sizeof(u32), st));
+    GEVC(A.ends.ensure((size_t)nc * wcap * sizeof(u32), st)); GEVC(A.start.ensure(nc * sizeof(u32), st));
+    GEVC(A.cm.ensure(n_h * sizeof(u32), st)); GEVC(A.cf.ensure(n_h * sizeof(u32), st));
+    GEVC(A.om.ensure((n_h + 1) * sizeof(u32), st)); GEVC(A.of.ensure((n_h + 1) * sizeof(u32), st));
+    GEVC(A.males.ensure(2 * n_h * sizeof(u32), st)); GEVC(A.females.ensure(2 * n_h * sizeof(u32), st));
+    hipLaunchKernelGGL(k_am_chunk_stats, dim3(nc), dim3(256), 0, st, sex, logical, d_svf, n_h, A.stats.as<double2>());
+    hipLaunchKernelGGL(k_am_windows, dim3(1), dim3(64), 0, st, (const double2*)A.stats.as<double2>(), nc, alpha, kmin, wcap, A.wlo.as<u32>(), A.ww.as<u32>());
+    hipLaunchKernelGGL(k_am_walk, dim3(nc, wcap / 256), dim3(256), 0, st, sex, logical, d_svf, n_h, x_sel, mm, (const u32*)A.wlo.as<u32>(), (const u32*)A.ww.as<u32>(), wcap, A.ends.as<u32>());
+    hipLaunchKernelGGL(k_am_chain, dim3(1), dim3(64), 0, st, sex, logical, d_svf, n_h, x_sel, mm, nc, (const u32*)A.wlo.as<u32>(), (const u32*)A.ww.as<u32>(), wcap,
+                       (const u32*)A.ends.as<u32>(), A.start.as<u32>(), stat);
+    hipLaunchKernelGGL(k_am_flags, dim3(nc), dim3(256), 0, st, sex, logical, d_svf, n_h, x_sel, mm, (const u32*)A.start.as<u32>(), A.cm.as<u32>(), A.cf.as<u32>());
+    KCHECK();
+    GEVC(scan_u32_on(st, c->d_sums, A.cm.as<u32>(), n_h, A.om.as<u32>()));
+    GEVC(scan_u32_on(st, c->d_sums, A.cf.as<u32>(), n_h, A.of.as<u32>()));
+    hipLaunchKernelGGL(k_am_compact, dim3((unsigned)ceil_div(n_h, 256)), dim3(256), 0, st, (const u32*)A.cm.as<u32>(), (const u32*)A.cf.as<u32>(), (const u32*)A.om.as<u32>(),
+                       (const u32*)A.of.as<u32>(), n_h, A.males.as<u32>(), A.females.as<u32>(), stat);
+    KCHECK();
+    u32 h[AMS_WORDS];
+    HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    const size_t nm = h[AMS_NM], nf = h[AMS_NF];
+    A.n_chunks = nc; A.n_direct = h[AMS_NDIRECT]; A.pois_reruns = 0;
+    gev_assort_result r = {nm, nf, 0, 0, 0};
+    if (res) *res = r;
+    const size_t n2 = std::min(nm, nf);
+    if (n2 == 0) return fail(GEV_ENOMATE, "Error: couples=0, num_males_mate=%zu, num_females_mate=%zu", nm, nf);
+
+    // :2232-2246 surplus removal: std::random_shuffle of the longer list on rand() after srand(seeds[0]), its first entries erased;
+    // 'f' (:2340-2352) continues the same rand() stream (its remainder is known here unless inbred couples are left out)
+    const size_t nL = std::max(nm, nf);
+    const size_t n_rand_surplus = nL > n2 ? nL - 1 : 0;
+    size_t n_rand = n_rand_surplus, remain_pre = 0;
+    if (fixed && !avoid) {
+        const size_t nfix = (size_t)std::floor((double)par->pop_size / (double)n2);
+        remain_pre = par->pop_size - nfix * n2;
+        if (remain_pre) n_rand += n2 - 1;
+    }
+    const GevRngTables* T = c->d_tables.as<GevRngTables>();
+    if (n_rand) {
+        GEVC(A.rnd.ensure(n_rand * sizeof(u32), st));
+        hipLaunchKernelGGL(k_glibc_stream, dim3(1), dim3(64), 0, st, T, (u32)seeds[0], n_rand, A.rnd.as<u32>());
+        KCHECK();
+    }
+    GEVC(A.kept.ensure(n2 * sizeof(u32), st)); GEVC(A.sorted_m.ensure(n2 * sizeof(u32), st)); GEVC(A.sorted_f.ensure(n2 * sizeof(u32), st));
+    const u32* list_m = A.males.as<u32>(); const u32* list_f = A.females.as<u32>();
+    if (nL > n2) {
+        GEVC(am_shuffle(c, st, A.rnd.as<u32>(), nL, nL - n2, nL, A.ssrc));
+        hipLaunchKernelGGL(k_gather_u32, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, st, nm > nf ? list_m : list_f, (const u32*)A.ssrc.as<u32>(), n2, A.kept.as<u32>());
+        KCHECK();
+        if (nm > nf) list_m = A.kept.as<u32>(); else list_f = A.kept.as<u32>();
+    }
+    // :2251-2252 both lists sorted by mating value (stable)
+    GEVC(am_sort(c, st, d_mv, list_m, list_m, n2, A.sorted_m.as<u32>()));
+    GEVC(am_sort(c, st, d_mv, list_f, list_f, n2, A.sorted_f.as<u32>()));
+
+    // :2257-2285 the template: ras_mvnorm(n2, 0, [[1, c], [c, 1]]) = z * U (Eigen's LLT upper factor), ranked by CommFunc::ras_rank
+    const double cc = par->mat_cor;
+    const double x11 = 1.0 - (cc / 1.0) * (cc / 1.0);          // Eigen's unblocked LLT leaves A(1,1) = 1 at a non-positive pivot
+    const double u01 = cc / 1.0, u11 = x11 > 0 ? std::sqrt(x11) : 1.0;
+    const u64 n_cand = (u64)n2 + (u64)n2 * 3 / 10 + 4096;          // acceptance pi/4: n2 pairs need 1.273 n2 candidates on average
+    const unsigned nbt = (unsigned)ceil_div((size_t)n_cand, TPL_CHUNK);
+    GEVC(A.tblk.ensure(nbt * sizeof(u32), st)); GEVC(A.t1.ensure(n2 * sizeof(double), st)); GEVC(A.t2.ensure(n2 * sizeof(double), st));
+    GEVC(A.i1.ensure(n2 * sizeof(u32), st)); GEVC(A.i2.ensure(n2 * sizeof(u32), st));
+    GEVC(A.pm.ensure(n2 * sizeof(u32), st)); GEVC(A.pf.ensure(n2 * sizeof(u32), st)); GEVC(A.inb.ensure(n2 * sizeof(u32), st));
+    GEVC(A.num.ensure(n2 * sizeof(int32_t), st));
+    const u32 x_tpl = h_minstd_seed(seeds[2]);
+    hipLaunchKernelGGL(k_tpl_count, dim3(nbt), dim3(256), 0, st, x_tpl, n_cand, A.tblk.as<u32>());
+    hipLaunchKernelGGL(k_tpl_emit, dim3(nbt), dim3(256), 0, st, x_tpl, n_cand, (u64)n2, (const u32*)A.tblk.as<u32>(), u01, u11, A.t1.as<double>(), A.t2.as<double>(), stat);
+    KCHECK();
+    GEVC(am_sort(c, st, A.t1.as<double>(), nullptr, nullptr, n2, A.i1.as<u32>()));
+    GEVC(am_sort(c, st, A.t2.as<double>(), nullptr, nullptr, n2, A.i2.as<u32>()));
+    const unsigned nb2 = (unsigned)ceil_div(n2, 256);
+    hipLaunchKernelGGL(k_am_couples, dim3(nb2), dim3(256), 0, st, (const u32*)A.i1.as<u32>(), (const u32*)A.i2.as<u32>(), (const u32*)A.sorted_m.as<u32>(), (const u32*)A.sorted_f.as<u32>(),
+                       n2, A.pm.as<u32>(), A.pf.as<u32>());
+    hipLaunchKernelGGL(k_am_inbreed, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), n2, d_ped, A.inb.as<u32>(), stat);
+    KCHECK();
+    size_t n_inb = 0;
+    if (avoid) {
+        HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        n_inb = h[AMS_NINB];
+    }
+    r.n_couples = n2; r.n_inbreed = n_inb;
+    if (res) *res = r;
+    const size_t n_ok = n2 - n_inb;
+    if (n_ok == 0) return fail(GEV_EUNSUPPORTED, "assort_mate: all %zu couples are inbred (the reference divides by zero)", n2);
+
+    // :2328-2355 offspring numbers, then the parents of every child in couple order
+    GEVC(A.ocnt.ensure(n2 * sizeof(u32), st)); GEVC(A.ooff.ensure((n2 + 1) * sizeof(u32), st));
+    size_t S = 0;
+    double thr = 0;
+    u32 L = 0;
+    if (pois) {
+        const double lam = (double)par->pop_size / (double)n_ok;
+        if (!(lam < 12)) return fail(GEV_EUNSUPPORTED, "assort_mate: poisson_distribution with mean %g >= 12 (libstdc++'s rejection branch) is not supported", lam);
+        thr = std::exp(-lam);
+        S = A.short_poisson ? n2 / 2 + 16 : (size_t)((double)n2 * (lam + 1.0) * 1.15) + 4096;
+        while ((n2 - 1) >> L) L++;                                     // levels: nxt^(2^j), j < L, cover every k < n2
+    } else {
+        const size_t nfix = (size_t)std::floor((double)par->pop_size / (double)n_ok);
+        const size_t remain = par->pop_size - nfix * n_ok;
+        if (avoid && remain) return fail(GEV_EUNSUPPORTED, "assort_mate: avoid_inbreeding with offspring_dist 'f' and %zu children left over (the reference indexes an empty list)", remain);
+        hipLaunchKernelGGL(k_am_fill_i32, dim3(nb2), dim3(256), 0, st, A.num.as<int32_t>(), n2, (int32_t)nfix);
+        if (remain) {
+            GEVC(am_shuffle(c, st, A.rnd.as<u32>() + n_rand_surplus, n2, 0, remain, A.ssrc));
+            hipLaunchKernelGGL(k_am_fixed_plus, dim3((unsigned)ceil_div(remain, 256)), dim3(256), 0, st, (const u32*)A.ssrc.as<u32>(), remain, A.num.as<int32_t>());
+        }
+        KCHECK();
+    }
+    for (;;) {
+        if (pois) {
+            if (S >= 0xfffffff0ull) return fail(GEV_EDEVICE, "assort_mate: Poisson stream of %zu draws (internal error)", S);
+            const size_t lv = std::max<u32>(L, 1);
+            GEVC(A.pois.ensure(lv * (S + 1) * sizeof(u32), st));
+            u32* tabs = A.pois.as<u32>();
+            const unsigned nbs = (unsigned)ceil_div(S + 1, 256);
+            hipLaunchKernelGGL(k_pois_next, dim3(nbs), dim3(256), 0, st, h_minstd_seed(seeds[3]), (u64)S, thr, tabs);
+            for (u32 j = 1; j < L; j++) hipLaunchKernelGGL(k_pois_double, dim3(nbs), dim3(256), 0, st, (const u32*)tabs + (size_t)(j - 1) * (S + 1), (u64)S, tabs + (size_t)j * (S + 1));
+            hipLaunchKernelGGL(k_pois_start, dim3(nb2), dim3(256), 0, st, (const u32*)tabs, (u64)S, L, (u64)n2, A.num.as<int32_t>(), stat);
+            KCHECK();
+        }
+        hipLaunchKernelGGL(k_am_offspring_count, dim3(nb2), dim3(256), 0, st, (const int32_t*)A.num.as<int32_t>(), (const u32*)A.inb.as<u32>(), n2, A.ocnt.as<u32>());
+        KCHECK();
+        GEVC(scan_u32_on(st, c->d_sums, A.ocnt.as<u32>(), n2, A.ooff.as<u32>()));
+        u32 tot = 0;
+        HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(&tot, A.ooff.as<u32>() + n2, sizeof(u32), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (h[AMS_FLAGS] & AMF_TPL_SHORT) return fail(GEV_EDEVICE, "assort_mate: the template's candidate pairs ran out (internal error)");
+        if (pois && (h[AMS_FLAGS] & AMF_POIS_SHORT)) {          // the stream ended inside a couple's draws: run it again, longer
+            HIPC(hipMemsetAsync(stat + AMS_FLAGS, 0, sizeof(u32), st));
+            S = 2 * S + 4096; A.pois_reruns++;
+            continue;
+        }
+        r.n_offspring = tot;
+        break;
+    }
+    if (res) *res = r;
+    if (r.n_offspring) {
+        GEVC(sc.father.ensure(r.n_offspring * sizeof(u32), st)); GEVC(sc.mother.ensure(r.n_offspring * sizeof(u32), st));
+    }
+    const bool records = couples_out || dev_records;           // dev_records: Couples_Info records left in d_couples (gev_generation_end copies them)
+    if (records) GEVC(c->d_couples.ensure(n2 * sizeof(gev_couple), st));
+    hipLaunchKernelGGL(k_am_expand, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), (const int32_t*)A.num.as<int32_t>(),
+                       (const u32*)A.inb.as<u32>(), (const u32*)A.ooff.as<u32>(), n2, logical, r.n_offspring ? sc.father.as<u32>() : nullptr,
+                       r.n_offspring ? sc.mother.as<u32>() : nullptr, records ? c->d_couples.as<gev_couple>() : nullptr);
+    KCHECK();
+    if (couples_out) HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n2 * sizeof(gev_couple), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    A.res = r; A.valid = true;
+    if (r.n_offspring) { sc.mated = true; sc.mate_pop = pop; sc.mate_n = r.n_offspring; sc.mate_epoch = P.layout_epoch; }
+    return GEV_OK;
+}
+int gev_assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const uint32_t seeds[4], const double* mating_value,
+                    const double* selection_value_func, const int64_t* pedigree, gev_couple* couples_out, gev_assort_result* res)
+{
+    return assort_mate(c, pop, par, seeds, mating_value, selection_value_func, false, pedigree, couples_out, res);
+}
+int gev_assort_mate_selected(gev_ctx* c, int pop, const gev_assort_params* par, const uint32_t seeds[4], const int64_t* pedigree,
+                             gev_couple* couples_out, gev_assort_result* res)
+{
+    GEVC(check_selection(c, pop, "assort_mate_selected"));
+    return assort_mate(c, pop, par, seeds, nullptr, nullptr, true, pedigree, couples_out, res);
+}
+int gev_last_assort_result(gev_ctx* c, gev_assort_result* res, gev_couple* couples_out)
+{
+    if (!c) return fail(GEV_EINVAL, "null context");
+    if (c->pend.active && (couples_out || !c->pend.assort))      // the counts of the assortative generation in flight may be read
+        return fail(GEV_ESTATE, "last_assort_result: a generation is pending: call gev_generation_end / gev_reproduce_end first");
+    gev_ctx::AssortState& A = c->am;
+    if (!A.valid) return fail(GEV_ESTATE, "last_assort_result: no gev_assort_mate has completed on this context");
+    if (res) *res = A.res;
+    if (couples_out && A.res.n_couples) {
+        HIPC(hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        const size_t n2 = A.res.n_couples;
+        GEVC(c->d_couples.ensure(n2 * sizeof(gev_couple), st));
+        hipLaunchKernelGGL(k_am_expand, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), (const int32_t*)A.num.as<int32_t>(),
+                           (const u32*)A.inb.as<u32>(), (const u32*)A.ooff.as<u32>(), n2, (const u32*)nullptr, (u32*)nullptr, (u32*)nullptr, c->d_couples.as<gev_couple>());
+        KCHECK();
+        HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n2 * sizeof(gev_couple), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    return GEV_OK;
+}
+int gev_dbg_assort_knobs(gev_ctx* c, int narrow_window, int short_poisson)
+{
+    if (!c) return fail(GEV_EINVAL, "null context");
+    c->am.narrow_window = narrow_window != 0; c->am.short_poisson = short_poisson != 0;
+    return GEV_OK;
+}
+int gev_dbg_assort_stats(gev_ctx* c, unsigned long long stats[3])
+{
+    if (!c || !stats) return fail(GEV_EINVAL, "null argument");
+    stats[0] = c->am.n_chunks; stats[1] = c->am.n_direct; stats[2] = c->am.pois_reruns;
+    return GEV_OK;
+}
+// One whole assortative generation: Simulation::assort_mate -> reproduce -> ras_compute_AD (sim_next_generation, :1907-1935, without
+// --RM).  The mating seeds (3, or 4 with 'p') are drawn on the device from glob_state; gev_assort_mate runs with them (it waits for the
+// list lengths, the inbred count with avoid_inbreeding, and the offspring count: n_offspring is random under 'p' and sizes everything
+// after); then reproduce's 1 + n_offspring * nchr draws continue from the state behind the mating seeds, and the rest is enqueued as
+// gev_generation_begin's is.  A head start queued by gev_set_generation_chain for a random-mating generation is dropped (it assumed
+// other draws); none is queued behind an assortative generation.
+static int generation_begin_assort(gev_ctx* c, int pop, uint32_t glob_state, const gev_assort_params* par, const double* mating_value,
+                                   const double* selection_value_func, bool dev_sel, const int64_t* pedigree)
+{
+    GEVC(check_idx(c, pop, 0));
+    PopState& P = c->pop[pop];
+    if (!P.gen0) return fail(GEV_ESTATE, "generation: population %d has no current generation (call gev_init_gen0)", pop);
+    if (!par) return fail(GEV_EINVAL, "generation_begin_assort: null params");
+    if (glob_state == 0 || glob_state >= GEV_M31) return fail(GEV_EINVAL, "generation: %u is not a state of std::minstd_rand0 (1 .. 2^31-2)", glob_state);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
+    // a head start for a random-mating generation must not write into the set any more, and is not used
+    if (sc.presampled || sc.fa_dropped || sc.fused_ahead) HIPC(hipStreamSynchronize(c->stream_samp));
+    if (sc.fused_ahead) c->chain_misses++;
+    sc.presampled = false; sc.ps_stale = false; sc.mated = false; sc.fused_ahead = false; sc.fa_dropped = false; c->chain_valid = false;
+    // :2170, :2173, :2265 (and :2332 for 'p'): the mating seeds
+    const bool pois = par->offspring_dist == 'p' || par->offspring_dist == 'P';
+    uint32_t seeds[4] = {0, 0, 0, 0};
+    uint32_t state = glob_state;
+    GEVC(gev_glob_seeds(c, &state, pois ? 4 : 3, seeds));
+    gev_assort_result r;
+    GEVC(assort_mate(c, pop, par, seeds, mating_value, selection_value_func, dev_sel, pedigree, nullptr, &r, /*dev_records=*/true));
+    const int nchr = c->nchr;
+    const size_t n_people = r.n_offspring, T = n_people * (size_t)nchr;
+    if (n_people == 0) return fail(GEV_EINVAL, "generation: no offspring");
+    if (2 * T * GEV_BK_CAP >= 0xf0000000ull) return fail(GEV_EINVAL, "generation: too many gametes");
+    bool has_mut = false;
+    GEVC(population_has_mutmap(c, pop, has_mut));
+    if (!has_mut) GEVC(check_chain_size(T));
+    const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
+    GEVC(ensure_stage(c, (n_status + 2) * 4 + n_people + 16));
+    u32* hstatus = (u32*)c->h_stage;
+    GEVC(finalize_static(c, pop));
+    GEVC(prepare_eager_ad(c, pop));
+    GEVC(ensure_capacity(c, pop, n_people));
+    sc.mated = false;                                          // the couples are this generation's, not a later gev_reproduce's
+    GEVC(harvest_timing(c, sc));
+    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
+    GEVC(ensure_scratch(c, sc, n_people, has_mut));             // (father / mother already hold n_people entries: kept)
+    GEVC(sc.globvals.ensure((2 + T) * sizeof(u32), st));
+    gev_ctx::PendingRepro& q = c->pend;
+    q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = false; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
+    q.pool_rebuilt = false;
+    q.fused = true; q.has_svf = false; q.d_svf = nullptr; q.glob_state = state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
+    q.assort = true; q.assort_seed0 = seeds[0]; q.am_nm = r.num_males_mate; q.am_nf = r.num_females_mate; q.am_couples = r.n_couples;
+    GEVC(enqueue_attempt(c, 0));
+    q.active = true;
+    return GEV_OK;
+}
+int gev_generation_begin_assort(gev_ctx* c, int pop, uint32_t glob_state, const gev_assort_params* par, const double* mating_value,
+                                const double* selection_value_func, const int64_t* pedigree)
+{
+    if (!mating_value) return fail(GEV_EINVAL, "generation_begin_assort: mating_value is NULL");
+    return generation_begin_assort(c, pop, glob_state, par, mating_value, selection_value_func, false, pedigree);
+}
+int gev_generation_begin_assort_selected(gev_ctx* c, int pop, uint32_t glob_state, const gev_assort_params* par, const int64_t* pedigree)
+{
+    GEVC(check_selection(c, pop, "generation_begin_assort_selected"));
+    return generation_begin_assort(c, pop, glob_state, par, nullptr, nullptr, true, pedigree);
 }
 // Simulation::ras_glob_seed (src/Simulation.cpp:17-21) called n times, evaluated on the device: *engine_state = the state of
 // glob_generator (std::minstd_rand0) before, and after on return; out (host, n values) may be NULL.

@@ -97,3 +97,47 @@ extern "C" int gev_rank_device(const double* d_x, size_t n, ull* d_rank, void* d
     }
     return (int)hipGetLastError();
 }
+
+// ---- device-to-device stable sorts of the assortative mating (gev_assort.h) -------------------------------------------------------
+// vals_out[0..n) = vals (identity when vals == NULL) ordered by a STABLE ascending sort of x[gather[q]] (gather == NULL: x[q]).
+// -0.0 and +0.0 share one key; every NaN gets the largest key, so NaNs go last in their original order (numpy's stable argsort).
+// Used for the mating-value sort of the marriageable lists (:2251-2252) and for CommFunc::ras_rank of the template (no NaNs there:
+// position in the stable sort = rank).
+__global__ void __launch_bounds__(256) k_sort_keys_gather(const double* __restrict__ x, const uint32_t* __restrict__ gather, const uint32_t* __restrict__ vals,
+                                                          size_t n, uint64_t* __restrict__ key, uint32_t* __restrict__ v)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double d = x[gather ? gather[i] : i];
+    uint64_t k;
+    if (d != d) k = ~0ull;
+    else {
+        if (d == 0.0) d = 0.0;
+        const uint64_t b = (uint64_t)__double_as_longlong(d);
+        k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    }
+    key[i] = k; v[i] = vals ? vals[i] : (uint32_t)i;
+}
+extern "C" size_t gev_sort_pairs_scratch_bytes(size_t n)
+{
+    size_t t_sort = 0;
+    (void)rocprim::radix_sort_pairs((void*)nullptr, t_sort, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n);
+    const size_t a = (n * 8 + 255) & ~(size_t)255, b = (n * 4 + 255) & ~(size_t)255;
+    return 2 * a + b + ((t_sort + 255) & ~(size_t)255) + 256;
+}
+extern "C" int gev_sort_pairs_f64(const double* d_x, const uint32_t* d_gather, const uint32_t* d_vals, size_t n, uint32_t* d_vals_out, void* d_tmp, hipStream_t st)
+{
+    if (n == 0) return 0;
+    const size_t a = (n * 8 + 255) & ~(size_t)255, b = (n * 4 + 255) & ~(size_t)255;
+    uint8_t* p = (uint8_t*)d_tmp;
+    uint64_t* key_in = (uint64_t*)p; p += a;
+    uint64_t* key_out = (uint64_t*)p; p += a;
+    uint32_t* v_in = (uint32_t*)p; p += b;
+    size_t tmp = 0;
+    (void)rocprim::radix_sort_pairs((void*)nullptr, tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n);
+    tmp = (tmp + 255) & ~(size_t)255;
+    hipLaunchKernelGGL(k_sort_keys_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, d_gather, d_vals, n, key_in, v_in);
+    hipError_t e = rocprim::radix_sort_pairs((void*)p, tmp, key_in, key_out, v_in, d_vals_out, n, 0, 64, st);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipGetLastError();
+}

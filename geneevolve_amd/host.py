@@ -649,6 +649,34 @@ class Simulation:
         self.ctx.generation_begin_selected(ipop, self.glob.x, pop_size)
         return self._generation_end(ipop, want_couples)
 
+    def next_generation_am(self, ipop, pop_size, mat_cor, mm_percent=0.0, avoid_inbreeding=False, offspring_dist="p",
+                           mating_value=None, selection_value_func=None, want_couples=False, selected=False):
+        """assort_mate -> reproduce -> ras_compute_AD of sim_next_generation (:1907-1935, without --RM) as one library call pair; all
+        ras_glob_seed() draws of the three are made by the library from glob_generator's state, which is stored back"""
+        ped = None
+        if avoid_inbreeding:
+            P = self.ped[ipop]
+            ped = np.stack([P.ID_Father, P.ID_Fathers_Father, P.ID_Fathers_Mother, P.ID_Mothers_Father, P.ID_Mothers_Mother], axis=1)
+        self.assort_result = self.ctx.generation_begin_assort(ipop, self.glob.x, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist,
+                                                              mating_value, selection_value_func, ped, selected)
+        track = self.track_pedigree and ipop in self.ped
+        r = self.ctx.generation_end(want_couples=want_couples or track)
+        self.glob.x = int(r["glob_state"])
+        self.last_seed_reproduce = int(r["seed_reproduce"])
+        self.sex[ipop] = r["sex"]
+        c = r["couples"]
+        if c is not None:
+            self.couples[ipop] = c
+        if track:                                               # enumeration order of the couple loop (:2433-2443)
+            ok = c["inbreed"] == 0
+            rep = c["num_offspring"][ok].astype(np.int64)
+            self.ped[ipop] = self.ped[ipop].offspring(np.repeat(c["pos_male"][ok].astype(np.int64), rep), np.repeat(c["pos_female"][ok].astype(np.int64), rep))
+        return r
+
+    def next_generation_am_selected(self, ipop, pop_size, mat_cor, mm_percent=0.0, avoid_inbreeding=False, offspring_dist="p", want_couples=False):
+        """next_generation_am() mating on the values compute_selection() left in the library: nothing is uploaded"""
+        return self.next_generation_am(ipop, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, want_couples=want_couples, selected=True)
+
     def assort_mate(self, ipop, selection_value_func, mating_value, pop_size, mat_cor, mm_percent=0.0,
                     avoid_inbreeding=False, offspring_dist="p", rank=None):   # :2167 (3 draws, +1 for Poisson offspring numbers)
         seeds = [int(x) for x in self.ras_glob_seed(4 if offspring_dist in ("p", "P") else 3)]
@@ -656,12 +684,33 @@ class Simulation:
                                          mm_percent, avoid_inbreeding, offspring_dist, rank=rank or self.ctx.rank_f64)
         return True
 
+    def assort_mate_device(self, ipop, selection_value_func, mating_value, pop_size, mat_cor, mm_percent=0.0,
+                           avoid_inbreeding=False, offspring_dist="p", selected=False):
+        """the same step on the library's side (gev_assort_mate): the seeds come from the host's glob stream as in assort_mate(), the
+        couples stay in the library for reproduce(); selection_value_func = None when every value is 1.  selected=True: mating on
+        the values compute_selection() left in the library (mating_value / selection_value_func are ignored)"""
+        seeds = [int(x) for x in self.ras_glob_seed(4 if offspring_dist in ("p", "P") else 3)]
+        self.last_assort_seeds = seeds
+        ped = None
+        if avoid_inbreeding:
+            P = self.ped[ipop]
+            ped = np.stack([P.ID_Father, P.ID_Fathers_Father, P.ID_Fathers_Mother, P.ID_Mothers_Father, P.ID_Mothers_Mother], axis=1)
+        if selected:
+            c, r = self.ctx.assort_mate_selected(ipop, seeds, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, ped)
+        else:
+            c, r = self.ctx.assort_mate(ipop, seeds, mating_value, selection_value_func, pop_size, mat_cor, mm_percent, avoid_inbreeding,
+                                        offspring_dist, ped)
+        self.couples[ipop] = c
+        self.num_males_mate, self.num_females_mate, self.assort_result = r["num_males_mate"], r["num_females_mate"], r
+        self._device_couples = (ipop, r["n_offspring"])
+        return True
+
     def reproduce(self, ipop, gen_num=0, seeds=None, n_people=None):   # :2394 (n_people: known offspring count, skips a host pass)
         c = self.couples[ipop]
         dev = getattr(self, "_device_couples", None)
         self._device_couples = None
         if dev is not None and dev[0] == ipop and n_people is None:
-            n_people = dev[1]                                     # one child per couple (:2149)
+            n_people = dev[1]                                     # random_mate: one child per couple (:2149); assort_mate: its n_offspring
         if n_people is None:
             n_people = int(c["num_offspring"][c["inbreed"] == 0].sum())
         if seeds is None:                                       # 1 + n_people*nchr ras_glob_seed() draws (:2398, :2500)

@@ -162,7 +162,7 @@ int gev_init_gen0(gev_ctx*, int pop, size_t n_people, uint32_t seed_gen0, uint8_
  *  sex_out        : n_people bytes, Human::sex of each offspring (:2472), or NULL
  * Pedigree ids and common_sibling (:2473-2484) are pure host bookkeeping and stay with the host.
  *  couples == NULL : the couples the preceding gev_random_mate of `pop` left on the device (n_couples is ignored, n_people must be
- *                   that call's pop_size).  Returns GEV_ESTATE when the population changed in between (gev_migrate,
+ *                   that call's pop_size), or those of the preceding gev_assort_mate (n_people must be its n_offspring).  Returns GEV_ESTATE when the population changed in between (gev_migrate,
  *                   gev_remove_rows, gev_import_rows, or a call that materialised a pending row order): the couples' positions
  *                   would name other rows.
  * Cost note: with a mutation map every (offspring, chromosome) task restarts its rand() chain at srand(mut_seed), so all tasks are
@@ -313,6 +313,63 @@ int gev_set_selection_gen0(gev_ctx*, int pop, double mean, double var);
 int gev_generation_begin_selected(gev_ctx*, int pop, uint32_t glob_state, size_t pop_size);
 int gev_random_mate_selected(gev_ctx*, int pop, uint32_t seed, size_t pop_size,
                              gev_couple* couples_out, size_t* num_males_mate, size_t* num_females_mate);
+
+/* ---- Simulation::assort_mate (src/Simulation.cpp:2167-2360), the reference's default mating mode -------------------------------
+ * Forms the couples of the population's current generation on the device, bit for bit as the reference does (stable order among
+ * equal mating values, as the host mirror geneevolve_amd/host.py:assort_mate; std::sort leaves it unspecified):
+ *  seeds[4]             : the ras_glob_seed() values drawn at :2170 (srand), :2173 (selection generator), :2265 (ras_mvnorm) and,
+ *                         with offspring_dist 'p' only, :2332 (ras_rpois)
+ *  mating_value         : Human::mating_value [n_people] (:2251)
+ *  selection_value_func : [n_people] (:2190), or NULL when every value is 1; NaN never passes
+ *  pedigree             : [n_people][5] ids (ID_Father, ID_Fathers_Father, ID_Fathers_Mother, ID_Mothers_Father, ID_Mothers_Mother)
+ *                         for the sibling / cousin test of avoid_inbreeding (:2306-2322); NULL without it
+ *  couples_out          : res->n_couples records, or NULL (size it from a call with NULL first, or from an upper bound:
+ *                         n_couples <= n_people)
+ * Second spouses (--MM, :2196-2198), surplus removal by std::random_shuffle on glibc rand() (:2232-2246), the ras_mvnorm rank
+ * template (:2257-2285), inbreeding avoidance and the offspring numbers ('p': poisson_distribution, mean < 12; 'f': pop_size /
+ * couples each, the remainder to the first couples of a shuffled list, :2328-2355) all run on the device.  Device log() may differ
+ * from glibc's in the last bit: a couple can change only where two template values lie within a few ulp of each other.
+ * The couples stay on the device: the next gev_reproduce of `pop` with couples == NULL and n_people == res->n_offspring breeds from
+ * them (same GEV_ESTATE rule as after gev_random_mate).
+ * Errors: GEV_ENOMATE "Error: couples=0, ..." (:2226-2230); GEV_EUNSUPPORTED for a Poisson mean >= 12, for no couple left after
+ * the inbred ones, and for avoid_inbreeding with 'f' and a remainder (the reference indexes an empty vector there); GEV_EINVAL for
+ * another offspring_dist, a non-finite mat_cor or a NULL pedigree with avoid_inbreeding. */
+typedef struct gev_assort_params {
+    uint64_t pop_size;          /* --pop_size of the next generation */
+    double   mat_cor;           /* mating-value correlation of spouses */
+    double   mm_percent;        /* --MM: probability of a second spouse */
+    int32_t  avoid_inbreeding;  /* --avoid_inbreeding */
+    int32_t  offspring_dist;    /* 'p' / 'P' or 'f' / 'F' */
+} gev_assort_params;
+typedef struct gev_assort_result {
+    uint64_t num_males_mate, num_females_mate;   /* list lengths before the surplus removal, second spouses included (:2222-2223) */
+    uint64_t n_couples, n_inbreed, n_offspring;  /* couples formed, inbred ones among them, children of the others */
+} gev_assort_result;
+int gev_assort_mate(gev_ctx*, int pop, const gev_assort_params*, const uint32_t seeds[4], const double* mating_value,
+                    const double* selection_value_func, const int64_t* pedigree, gev_couple* couples_out, gev_assort_result* res);
+/* gev_assort_mate on the mating values and selection_value_func gev_compute_selection left on the device (GEV_ESTATE without) */
+int gev_assort_mate_selected(gev_ctx*, int pop, const gev_assort_params*, const uint32_t seeds[4], const int64_t* pedigree,
+                             gev_couple* couples_out, gev_assort_result* res);
+/* the result of the last gev_assort_mate(_selected) of the context (also of a gev_generation_begin_assort in flight: allowed between
+ * _begin and _end); its couples as records when couples_out is not NULL (res->n_couples of them; not between _begin and _end) */
+int gev_last_assort_result(gev_ctx*, gev_assort_result* res, gev_couple* couples_out);
+/* ---- one whole assortative generation: the body of Simulation::sim_next_generation without --RM (src/Simulation.cpp:1907-1935):
+ * assort_mate -> reproduce -> ras_compute_AD as one call pair, finished by gev_generation_end.  Every ras_glob_seed() value of the
+ * generation -- 3 (:2170, :2173, :2265), a 4th with 'p' (:2332), then 1 (:2398) + n_offspring * nchr (:2500, only with a mutation
+ * map) -- is drawn on the device from glob_state; res->glob_state of gev_generation_end is the state behind the last one, res->seed_mate
+ * the srand seed (:2170), res->num_*_mate the list lengths.  Begin waits internally for the mating counts (n_offspring is random under
+ * 'p'); the rest of the generation is enqueued as gev_generation_begin's and _end waits once.  gev_last_assort_result (between _begin
+ * and _end) sizes the outputs of gev_generation_end: couples_out holds n_couples records, sex_out n_offspring bytes.
+ * The head start of gev_set_generation_chain does not apply: a head start queued by a random-mating generation is dropped here, and
+ * none is queued behind an assortative generation.  Arguments and errors as gev_assort_mate (nothing pending after an error). */
+int gev_generation_begin_assort(gev_ctx*, int pop, uint32_t glob_state, const gev_assort_params*, const double* mating_value,
+                                const double* selection_value_func, const int64_t* pedigree);
+int gev_generation_begin_assort_selected(gev_ctx*, int pop, uint32_t glob_state, const gev_assort_params*, const int64_t* pedigree);
+/* test hooks of the exact fallbacks, in force for the following calls: narrow_window != 0 shrinks the windows of the marriage-draw chain
+ * so that most chunks are walked directly; short_poisson != 0 starts the Poisson stream far too short so that it is extended and run
+ * again.  gev_dbg_assort_stats: {chunks, chunks walked directly, Poisson reruns} of the last gev_assort_mate. */
+int gev_dbg_assort_knobs(gev_ctx*, int narrow_window, int short_poisson);
+int gev_dbg_assort_stats(gev_ctx*, unsigned long long stats[3]);
 
 /* Locus-split populations (gev_set_chr_active): every context of the population computes the A/D of its own chromosomes; after
  * the all-reduce + chromosome-ordered sum (geneevolve_amd/distributed.py:compute_ad_locus_split) each context is handed the raw
