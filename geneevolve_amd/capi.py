@@ -704,8 +704,8 @@ class GevContext:
         return int(out[0]), int(out[1]), int(out[2])
 
     def set_overlap(self, on):
-        """True (default) / False / 2 (sampling-only overlap), or None: decide from two timed serialised generations"""
-        self._call("set_overlap", C.c_int(-1 if on is None else int(on)))
+        """True (default): the dense stitch overlaps later work; False: one stream, every generation waits for its stitch"""
+        self._call("set_overlap", C.c_int(1 if on else 0))
 
     def set_stitch_mode(self, mode):
         self._call("set_stitch_mode", C.c_int(mode))

@@ -4,35 +4,7 @@
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC gev_library.hip -o libgeneevolve_amd.so
 //
-// Tuning / diagnosis knobs (environment, read at gev_create; defaults are what the measurements of DESIGN.md chose):
-//   GEV_OVERLAP=0|1|2|-1      stream overlap: never | everything (default) | sampling only | decide from two timed generations
-//   GEV_SERIALIZE=1           same as GEV_OVERLAP=0
-//   GEV_SAMPLE_BATCHED=0|1    sampling kernels: one task per wave | eight tasks per wave, one kernel (default)
-//   GEV_STITCH_MODE=0|1       dense stitch kernel: k_stitch_segments (default) | k_stitch_rows (same results)
-//   GEV_SAMPLE_GRID=n         persistent workgroups of the sampling kernels (default 1792 up to 400k tasks per generation, 768 above; 1024 alone)
-//   GEV_STITCH_WG_PER_CU=n|auto stitch workgroups per CU, by dynamic LDS padding (default: unlimited; auto: measured at run time)
-//   GEV_STITCH_LDS_PAD=bytes  (experiments) that padding directly
-//   GEV_ALIAS_ROWS=0|1        write every segment of every gamete row | segments without a crossover boundary share the parental unit (default)
-//   GEV_LIST_SEGS=n           most position ranges per row the mutation / interval lists are cut into (default 32; 1 = a piece is a whole list)
-//   GEV_LIST_ARENA=n          entries per row of the list-piece arenas (default: a tenth of the device memory, at most 4096 per row)
-//   GEV_LIST_HEADROOM=0       size every list buffer exactly (tests: every generation overflows, grows and is enqueued again)
-//   GEV_STREAM_PRIO=xxxxx     h|m|l for the main, head-start, mating, list and stitch streams (default hhhhh)
-//   GEV_STITCH_PRIORITY=1|2   (older form) stitch stream high and the others low / all streams equal
-//   GEV_STITCH_START=0|1|2    the stitch starts behind the unit table | the CV planes | the generation's whole small work (default 2)
-//   GEV_STITCH_U=1|2|4        16-byte chunks per lane in flight in the segment stitch (default 1)
-//   GEV_SIDE_STREAMS=0        mating and list kernels on the main stream
-//   GEV_HEAD_START=1          the next generation's seeds + sampling are enqueued in front of this generation's work, and only the next
-//                             generation's unit table waits for the sampling (default 0: behind this generation's work, waited for as a whole)
-//   GEV_AD_WIDE=0             A/D sums with the 128-CV table pieces of k_ad_accumulate_tab instead of k_ad_accumulate_wide
-//   GEV_CHAIN_WG=0            serial-chain mode (no mutation map): one wave per link instead of a workgroup
-//   GEV_CHAIN_MAX_TASKS=n     most (offspring, chromosome) tasks accepted without a mutation map (default 4 000 000)
-//   GEV_POOL_REBUILD=1        rebuild the free list of the segment pool every generation
-//   GEV_STITCH_GRID=n         persistent workgroups of the segment stitch per chromosome (default 16384)
-//   GEV_SEG_CHUNKS=2^k        16-byte chunks per row segment (default 128 = 2 KiB)
-//   GEV_STITCH_WAVE_PRIO=0..3 s_setprio level of the stitch kernel's waves (default 0; measured: no effect next to the sampling kernels)
-//   GEV_TABLE_RING_BYTES=n    minimum size of the pinned ring the per-generation work tables are staged in (default 256 KiB)
-//   GEV_TRACE_HOST=1          stderr: host time per phase of gev_reproduce, per generation the host's and the main stream's time split by
-//                             phase (timed events), allocations, deferred frees
+// Environment knobs: the list at gev_create in include/geneevolve_amd.h is the one the library reads.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <algorithm>
@@ -221,14 +193,15 @@ struct gev_ctx {
     // per-generation scratch: two sets, because the dense stitch of generation g (stream_big) still reads set g%2
     // while sampling / sparse state of generation g+1 (stream) fill the other one
     struct Scratch {
-        DevBuf father, mother, mutseeds, globvals /* [2 + T] ras_glob_seed() values drawn on the device: mate seed, reproduce seed, mutation seeds */, seed_pat, seed_mat, k, bk_off, bk, bk_idx, start, nmut, nm_off, nm_pos, nm_side, sex, status, chrwork, cvwork;
+        DevBuf father, mother, mutseeds, globvals /* [2 + T] ras_glob_seed() values drawn on the device: mate seed, reproduce seed, mutation seeds */, seed_pat, seed_mat, k, bk_off, bk, bk_idx, start, nmut, nm_off, nm_pos, nm_side, sex, status, chrwork, cvwork,
+               globblk /* rejection counts of this set's ras_glob_seed() draws (enqueue_glob) */;
         std::vector<uint8_t> chrwork_shadow, cvwork_shadow;     // what the device copies of the tables hold (upload_table_cached)
         unsigned n_chrwork = 0, n_cvwork = 0; float sampling_ms_saved = -1;
         size_t nseg_max = 1, cv_used_max = 0, lp_entries_per_row = 0; u32 cv_max = 0;     // launch shapes of the generation (enqueue_tables)
         bool pool_rebuild = false;                                                            // this attempt rebuilds the free list of the segment pool
         bool cv_count_fused = false;                                                          // k_stitch_small also counts the alleles per CV column (every grid <= 1024 columns)
         hipEvent_t ev_fork = nullptr, ev_aux = nullptr, ev_lists = nullptr, ev_forked = nullptr;   // joins of the attempt's side streams
-        hipEvent_t ev_small_done = nullptr, ev_stitch_done = nullptr, t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_status = nullptr, ev_sampled = nullptr, ev_seeded = nullptr;   // the generation's status block (and A/D results) have arrived on the host
+        hipEvent_t ev_small_done = nullptr, ev_stitch_done = nullptr, t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_status = nullptr, ev_sampled = nullptr;   // the generation's status block (and A/D results) have arrived on the host
         bool timing_pending = false, stitch_pending = false;
         hipEvent_t tc[3] = {nullptr, nullptr, nullptr};   // GEV_TRACE_HOST: start of the attempt's main stream, A/D done, lists joined
         double th_enq = 0;
@@ -265,43 +238,20 @@ struct gev_ctx {
     int ad_cached_pop = -1;                                  // population whose current-generation A/D sits in h_ad
     int ad_host_set_pop = -1;                                // population whose raw A/D totals on the device were supplied by gev_set_ad (locus-split: all-reduced)
     bool eager_ad = true;                                    // compute A/D inside gev_reproduce (same enqueue, same sync)
-    int stitch_start = 2;          // when the dense stitch of a generation may start: 0 behind the unit table, 1 behind the CV planes, 2 behind the whole small work incl. A/D (default: with the stitch at the small kernels' priority it then runs alone for 0.16 ms, next to the host's turn-around; GEV_STITCH_START)
-    unsigned cv_threads = 512; bool cv_count_fused_ok = true;   // k_stitch_small: threads per block (GEV_CV_THREADS=256|512|1024), column counts in the same pass (GEV_CV_COUNT_FUSED=0: separate k_cv_count)
-    int stitch_u = 1;              // 16-byte chunks per lane in flight in the segment stitch: a 2 KiB segment is one step of a wave (GEV_STITCH_U=1|2|4; 8 KiB segments: 2: 722, 4: 778 generations/s)
-    int head_start = 0;            // the next generation's seeds + sampling: 0 = enqueued behind this generation's work, the whole next generation waits for them; 1 = enqueued first, the next generation's mating waits for the seeds and its unit table for the sampling (GEV_HEAD_START; same rate at config 2)
-    bool side_streams = true;      // mate + free list next to the sampling, lists next to CV planes + A/D (GEV_SIDE_STREAMS=0: one stream)
     int stitch_mode = 0;           // 0 = work-list form (production, k_stitch_segments), 1 = gamete-major (k_stitch_rows)
     bool sample_batched = true;               // K1-K3 as eight tasks per wave (gev_sample8.h); GEV_SAMPLE_BATCHED=0: one task per wave
-    unsigned sample_grid = SAMPLE_GRID_MAX;   // persistent workgroups of the sampling kernels when they have the GPU to themselves (GEV_SAMPLE_GRID)
-    bool sample_grid_env = false;             // GEV_SAMPLE_GRID fixed both
-    unsigned sample_grid_shared = 768;        // ... and next to the other streams' kernels.  Next to the 5 ms whole-row stitch of the first half of round 2, 384 was
-                                              // best (fewer of the stitch's slots taken for longer); with the 0.7 ms segment stitch and the pipelined host loop the
-                                              // sampling is what gev_presample_sex waits for: 768 finishes in 0.45 instead of 0.95 ms (config 2 +4 %, the shard unchanged)
-    bool serialize = false;        // wait for every stitch (no overlap between the two streams)
-    int overlap_mode = 1;          // 1 everything (default), 0 never, 2 sampling only, -1 decide after two serialised generations
-    bool sparse_after_stitch = false;   // mode 2: the memory-bound sparse/CV/A-D kernels wait for the running stitch, only the ALU-bound sampling shares the GPU with it
-    int auto_gens = 0; double auto_small_ms = 0, auto_stitch_ms = 0;
-    size_t stitch_grid = 16384;   // most workgroups (4 waves = 4 work-list entries each) of the segment stitch per chromosome (GEV_STITCH_GRID)
-    int stitch_wave_prio = 0;      // s_setprio level of the stitch kernel's waves (GEV_STITCH_WAVE_PRIO)
+    bool serialize = false;        // gev_set_overlap(0) / GEV_OVERLAP=0: wait for every stitch, everything on the main stream (kernel timings without interference)
     u32 seg_shift = 7;             // log2(16-byte chunks per row segment): 2 KiB.  Smaller: more table entries to manage per generation; larger: more bytes copied per
                                    // crossover.  Round 3 (free list kept across generations, one thread per table entry), config 2: 128 chunks 906, 256: 845, 512: 745
                                    // generations/s; round 2 (list rebuilt and every row's entries walked by one thread every generation): 256: 370, 512: 457, 1024: 450.
                                    // A row has at most 64 segments: longer rows get larger segments (gev_set_snps).  GEV_SEG_CHUNKS=<power of two>
     bool alias_rows = true;        // crossover-free gametes share their parent's pool row instead of copying it (GEV_ALIAS_ROWS=0: copy every row)
     unsigned long long chunks_written_sum = 0, chunks_total_sum = 0, segments_written_sum = 0, segments_total_sum = 0;   // over all generations and active chromosomes (gev_stitch_totals)
-    // Stitch workgroups per CU (8 = every wave slot).  The hardware queue priority does not let the small kernels of the next
-    // generation overtake a stitch grid that is still being dispatched: at 8 they start when the stitch is nearly over.  Slots
-    // left free (6 of 8 used) let them run next to it, at the price of a slightly slower stitch.  That pays when the small-kernel
-    // chain is the longer of the two: long rows (one 1M-SNP chromosome with shared rows: 6 -> +9 % generations/s), not when the
-    // stitch dominates anyway (11 chromosomes of 227k SNPs: 8).  Default: by row length; GEV_STITCH_WG_PER_CU=<n> fixes it,
-    // =auto measures it (a few generations per candidate, wall time between consecutive gev_reproduce returns).
-    int stitch_occ = 0 /* 0 = by row length */, stitch_occ_env = 0; bool stitch_occ_auto = false;
     struct PendingRepro { bool active = false, has_mut = false, pre = false; int pop = 0, attempt = 0; size_t n_people = 0, n_status = 0; u32 seed = 0; u32* hstatus = nullptr; double th0 = 0, th1 = 0, th2 = 0;
                           bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; const double* d_svf = nullptr; /* with has_svf: what the mating reads */ u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr;
                           bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0; } pend;
-    struct OccTune { int phase = 0 /* 0 idle, 1 measuring, 2 settled */, idx = 0, n = 0, best_occ = 8; double last = 0, cur_min = 0, best = 0; size_t people = 0; unsigned age = 0; } tune;
     DevBuf d_snpmajor, d_text;
-    DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
+    DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
     // gev_assort_mate (gev_assort.h): scratch, the last call's result and couple arrays, test knobs
     struct AssortState {
@@ -435,40 +385,29 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
     std::unique_ptr<gev_ctx> c(new gev_ctx());
     c->device = device; c->n_pop = n_pop; c->nchr = nchr; c->nphen = nphen;
     while ((1u << c->rp_bits) < (u32)n_pop) c->rp_bits++;
-    // small latency-critical kernels get the high-priority queue, the long HBM-bound stitch the low one:
-    // stitch workgroups are short-lived, so freed CU slots go to the small kernels first
+    // All five streams at the greatest priority: the stitch is short -- 0.15 ms at config 2 -- and at equal priority it is through
+    // before it is in anybody's way (at low priority it lingered for 0.35 ms next to the latency-bound chain: 1060 against 1370
+    // generations/s).  The runtime maps streams of one priority onto four hardware queues in creation order, so the order below
+    // decides which two streams share a queue.
     int prio_least = 0, prio_greatest = 0;
     HIPC(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    if (const char* e = getenv("GEV_STITCH_PRIORITY")) {      // experiment knob: 1 = stitch stream high / small streams low, 2 = all equal (default: small high, stitch low)
-        if (atoi(e) == 1) std::swap(prio_least, prio_greatest); else if (atoi(e) == 2) prio_least = prio_greatest = (prio_least + prio_greatest) / 2;
-    }
-    // GEV_STREAM_PRIO: five letters h / m / l for the main, head-start (sampling), mating, list and stitch streams (default hhhhh:
-    // the stitch is short -- 0.15 ms at config 2 -- and at equal priority it is through before it is in anybody's way; at low
-    // priority it lingered for 0.35 ms next to the latency-bound chain: 1060 against 1370 generations/s)
-    const char* pr = getenv("GEV_STREAM_PRIO");
-    auto level = [&](int i, int dflt) { if (!pr || strlen(pr) != 5) return dflt; return pr[i] == 'h' ? prio_greatest : (pr[i] == 'l' ? prio_least : (prio_least + prio_greatest) / 2); };
-    HIPC(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, level(0, prio_greatest)));
-    HIPC(hipStreamCreateWithPriority(&c->stream_samp, hipStreamNonBlocking, level(1, prio_greatest)));
-    // (the runtime maps streams of one priority onto four hardware queues: the fifth stream created shares a queue with an earlier one.
-    //  GEV_STREAM_ORDER=1 creates the list stream before the mating stream -- an experiment on which two share)
-    static const bool swap_order = getenv("GEV_STREAM_ORDER") && atoi(getenv("GEV_STREAM_ORDER")) == 1;
-    if (swap_order) HIPC(hipStreamCreateWithPriority(&c->stream_list, hipStreamNonBlocking, level(3, prio_greatest)));
-    HIPC(hipStreamCreateWithPriority(&c->stream_aux, hipStreamNonBlocking, level(2, prio_greatest)));
-    if (!swap_order) HIPC(hipStreamCreateWithPriority(&c->stream_list, hipStreamNonBlocking, level(3, prio_greatest)));
+    HIPC(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest));
+    HIPC(hipStreamCreateWithPriority(&c->stream_samp, hipStreamNonBlocking, prio_greatest));
+    HIPC(hipStreamCreateWithPriority(&c->stream_aux, hipStreamNonBlocking, prio_greatest));
+    HIPC(hipStreamCreateWithPriority(&c->stream_list, hipStreamNonBlocking, prio_greatest));
     for (auto& ev : c->ev) HIPC(hipEventCreate(&ev));
-    HIPC(hipStreamCreateWithPriority(&c->stream_big, hipStreamNonBlocking, level(4, prio_greatest)));
+    HIPC(hipStreamCreateWithPriority(&c->stream_big, hipStreamNonBlocking, prio_greatest));
     // Events that only order DEVICE work against device work carry no system-scope fence (by default recording an event makes the
     // preceding kernel write the dirty L2 lines back to memory: tens of microseconds behind a kernel that wrote 50 MB, paid by
     // whatever small kernel comes next).  Only the event the host waits on before it reads the results (ev_status) keeps it.
-    static const bool sysfence = getenv("GEV_EVENT_SYSFENCE") != nullptr;            // (A/B knob: the default flags everywhere)
-    const unsigned dev_only = hipEventDisableTiming | (sysfence ? 0u : hipEventDisableSystemFence), timed = sysfence ? hipEventDefault : hipEventDisableSystemFence;
+    const unsigned dev_only = hipEventDisableTiming | hipEventDisableSystemFence, timed = hipEventDisableSystemFence;
     HIPC(hipEventCreateWithFlags(&c->ev_planes, dev_only));
     c->chr_active.assign(nchr, 1);
     for (auto& sc : c->sc) {
         HIPC(hipEventCreateWithFlags(&sc.ev_small_done, dev_only));
         HIPC(hipEventCreateWithFlags(&sc.ev_stitch_done, dev_only));
         HIPC(hipEventCreateWithFlags(&sc.ev_status, hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&sc.ev_sampled, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_seeded, dev_only));
+        HIPC(hipEventCreateWithFlags(&sc.ev_sampled, dev_only));
         HIPC(hipEventCreateWithFlags(&sc.ev_fork, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_aux, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_lists, dev_only));
         HIPC(hipEventCreateWithFlags(&sc.ev_forked, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_chain, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_tab, dev_only));
         for (auto& e : sc.t) HIPC(hipEventCreateWithFlags(&e, timed));
@@ -483,29 +422,12 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
     }
     GevRngTables T; gev_build_rng_tables(T);
     GEVC(h2d(c.get(), c->d_tables, &T, sizeof T));
-    if (const char* e = getenv("GEV_SERIALIZE")) c->overlap_mode = atoi(e) != 0 ? 0 : 1;
-    if (const char* e = getenv("GEV_OVERLAP")) { const int v = atoi(e); c->overlap_mode = v < 0 ? -1 : std::min(v, 2); }
-    c->serialize = c->overlap_mode <= 0;                             // auto starts serialised
-    c->sparse_after_stitch = c->overlap_mode == 2;
+    if (const char* e = getenv("GEV_OVERLAP")) c->serialize = atoi(e) == 0;
     if (const char* e = getenv("GEV_SAMPLE_BATCHED")) c->sample_batched = atoi(e) != 0;
-    if (const char* e = getenv("GEV_STITCH_GRID")) c->stitch_grid = (size_t)std::max(1, atoi(e));
     if (const char* e = getenv("GEV_SEG_CHUNKS")) { const int v = atoi(e); u32 sh = 0; while ((1 << (sh + 1)) <= v) sh++; if (v >= 1 && sh <= 20) c->seg_shift = sh; }
     if (const char* e = getenv("GEV_ALIAS_ROWS")) c->alias_rows = atoi(e) != 0;
-    if (const char* e = getenv("GEV_STITCH_WAVE_PRIO")) c->stitch_wave_prio = std::max(0, std::min(atoi(e), 3));
-    if (const char* e = getenv("GEV_STITCH_START")) c->stitch_start = std::max(0, std::min(atoi(e), 2));
-    if (const char* e = getenv("GEV_SIDE_STREAMS")) c->side_streams = atoi(e) != 0;
-    if (const char* e = getenv("GEV_HEAD_START")) c->head_start = atoi(e) == 1 ? 1 : 0;
-    if (const char* e = getenv("GEV_STITCH_U")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) c->stitch_u = v; }
-    if (const char* e = getenv("GEV_CV_THREADS")) { const int v = atoi(e); if (v == 256 || v == 512 || v == 1024) c->cv_threads = (unsigned)v; }
-    if (const char* e = getenv("GEV_CV_COUNT_FUSED")) c->cv_count_fused_ok = atoi(e) != 0;
     if (const char* e = getenv("GEV_OVF_CAP")) { const long v = atol(e); if (v >= 1) c->bk_ovf_cap = c->nm_ovf_cap = (size_t)v; }
     if (const char* e = getenv("GEV_STITCH_MODE")) c->stitch_mode = std::max(0, std::min(atoi(e), 1));
-    if (const char* e = getenv("GEV_SAMPLE_GRID")) { const int g = atoi(e); if (g >= 1) { c->sample_grid = c->sample_grid_shared = (unsigned)g; c->sample_grid_env = true; } }
-    if (const char* e = getenv("GEV_STITCH_WG_PER_CU")) {       // fixed stitch workgroups per CU (default: measured, see OccTune)
-        const int occ = atoi(e);
-        if (!strcmp(e, "auto")) c->stitch_occ_auto = true;
-        else if (occ >= 1 && occ <= 8) c->stitch_occ = c->stitch_occ_env = occ;
-    }
     *out = c.release();
     return GEV_OK;
 }
@@ -521,7 +443,7 @@ void gev_destroy(gev_ctx* c)
     if (g_graveyard.bytes) g_graveyard.drain(c->device, false);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     if (c->ev_planes) (void)hipEventDestroy(c->ev_planes);
-    for (auto& sc : c->sc) { if (sc.ev_small_done) (void)hipEventDestroy(sc.ev_small_done); if (sc.ev_stitch_done) (void)hipEventDestroy(sc.ev_stitch_done); if (sc.ev_status) (void)hipEventDestroy(sc.ev_status); if (sc.ev_sampled) (void)hipEventDestroy(sc.ev_sampled); if (sc.ev_seeded) (void)hipEventDestroy(sc.ev_seeded); if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork); if (sc.ev_aux) (void)hipEventDestroy(sc.ev_aux); if (sc.ev_lists) (void)hipEventDestroy(sc.ev_lists); if (sc.ev_forked) (void)hipEventDestroy(sc.ev_forked); if (sc.ev_chain) (void)hipEventDestroy(sc.ev_chain); if (sc.ev_tab) (void)hipEventDestroy(sc.ev_tab); for (auto& e : sc.t) if (e) (void)hipEventDestroy(e); for (auto& e : sc.tc) if (e) (void)hipEventDestroy(e); }
+    for (auto& sc : c->sc) { if (sc.ev_small_done) (void)hipEventDestroy(sc.ev_small_done); if (sc.ev_stitch_done) (void)hipEventDestroy(sc.ev_stitch_done); if (sc.ev_status) (void)hipEventDestroy(sc.ev_status); if (sc.ev_sampled) (void)hipEventDestroy(sc.ev_sampled); if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork); if (sc.ev_aux) (void)hipEventDestroy(sc.ev_aux); if (sc.ev_lists) (void)hipEventDestroy(sc.ev_lists); if (sc.ev_forked) (void)hipEventDestroy(sc.ev_forked); if (sc.ev_chain) (void)hipEventDestroy(sc.ev_chain); if (sc.ev_tab) (void)hipEventDestroy(sc.ev_tab); for (auto& e : sc.t) if (e) (void)hipEventDestroy(e); for (auto& e : sc.tc) if (e) (void)hipEventDestroy(e); }
     hipStream_t s = c->stream;
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_seeds) (void)hipHostFree(c->h_seeds);
@@ -1058,7 +980,6 @@ int gev_init_gen0(gev_ctx* c, int pop, size_t n_people, uint32_t seed_gen0, uint
 // sized from the previous totals; if one was too small the buffers are grown from the exact totals
 // of the count passes and the small work is enqueued again (inputs are untouched until the flip).
 static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready = false, int hbuf = -1);
-static int enqueue_chain_head_start(gev_ctx* c);
 static int prepare_eager_ad(gev_ctx* c, int pop);
 static int check_not_pending(gev_ctx* c);
 static int check_chain_size(size_t T);
@@ -1092,12 +1013,6 @@ static int harvest_timing(gev_ctx* c, gev_ctx::Scratch& sc)
     ms[3] = ms[0] + ms[1] + ms[2];
     for (int i = 0; i < 4; i++) { c->last_ms[i] = ms[i]; c->ms_sum[i] += ms[i]; }
     c->ms_count++;
-    // overlap pays when the small kernels are a small fraction of the stitch (config 2: ~0.2); when they are
-    // comparable (many chromosomes, short rows) the starved small stream only delays everything: stay serialised
-    if (c->overlap_mode < 0 && c->serialize && c->auto_gens < 2) {
-        c->auto_small_ms += ms[0] + ms[2]; c->auto_stitch_ms += ms[1];
-        if (++c->auto_gens == 2) c->serialize = !(c->auto_small_ms < 4.0 * c->auto_stitch_ms);   // overlap unless the stitch is negligible
-    }
     sc.timing_pending = false;
     return GEV_OK;
 }
@@ -1187,9 +1102,11 @@ static int enqueue_sampling(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_
     // ---- sampling: one map scan per gamete / per mutation task
     // persistent sampling workgroups.  Next to the other streams' kernels: 1792 (7 waves per SIMD: the kernels stall on dependent
     // integer chains and LDS, and more waves hide that -- +2 % at config 2) while the generation has few tasks; 768 for many tasks
-    // (the 1.4 M tasks of the config-4 shard: its list and table kernels are the bound, and the sampling grid is in their way)
-    const unsigned shared_grid = c->sample_grid_env ? c->sample_grid_shared : (T <= 400000 ? 1792u : c->sample_grid_shared);
-    const unsigned task_blocks = (unsigned)std::min<size_t>(ceil_div(T, 4), (c->dense && !c->serialize) ? shared_grid : c->sample_grid);
+    // (the 1.4 M tasks of the config-4 shard: its list and table kernels are the bound, and the sampling grid is in their way.  Next
+    // to the 5 ms whole-row stitch of round 2, 384 was best; with the 0.7 ms segment stitch 768 finishes the sampling gev_presample_sex
+    // waits for in 0.45 instead of 0.95 ms).  With the GPU to themselves: SAMPLE_GRID_MAX
+    const unsigned shared_grid = T <= 400000 ? 1792u : 768u;
+    const unsigned task_blocks = (unsigned)std::min<size_t>(ceil_div(T, 4), (c->dense && !c->serialize) ? shared_grid : (unsigned)SAMPLE_GRID_MAX);
     if (has_mut && c->sample_batched) {
         // eight tasks per wave, mutations and gametes in one kernel; the rare slow tasks are finished in place
         const unsigned batch_blocks = (unsigned)std::min<size_t>(ceil_div(ceil_div(T, SB_TASKS), 4), task_blocks);
@@ -1364,9 +1281,8 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
     // The free list of the segment pool is kept across generations (units nobody named when it was built and that were not handed
     // out since are still unnamed) and rebuilt only when what is left of it may not cover the generation: four times what the last
     // generation took, at least a quarter of a generation's segments.  Should a generation need more than is left (k_pool_fresh
-    // raises FLAG_POOL), it is enqueued again behind a rebuild.  GEV_POOL_REBUILD=1: every generation (the round-2 behaviour).
-    static const bool always = getenv("GEV_POOL_REBUILD") && atoi(getenv("GEV_POOL_REBUILD")) != 0;
-    sc.pool_rebuild = always;
+    // raises FLAG_POOL), it is enqueued again behind a rebuild.
+    sc.pool_rebuild = false;
     if (c->dense) for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
         ChrState& cs = P.st[k];
@@ -1434,7 +1350,7 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
     sc.nseg_max = 1; sc.cv_used_max = 0; sc.cv_max = 0;
     for (const ChrWork& w : cw) sc.nseg_max = std::max<size_t>(sc.nseg_max, w.pw.nseg);
     const u32 nsub = 1 + c->rp_bits;
-    sc.cv_count_fused = c->cv_count_fused_ok;
+    sc.cv_count_fused = true;
     for (const CvWork& v : vw) { sc.cv_used_max = std::max<size_t>(sc.cv_used_max, (size_t)v.sub_w32 * nsub); sc.cv_count_fused &= v.sub_w32 <= 32; if (v.C <= SMALL_POS_LDS) sc.cv_max = std::max(sc.cv_max, v.C); }   // LDS copy of the CV grid: sized for the launch, not for the worst case (occupancy)
     if (sc.n_chrwork) {
         GEVC(upload_table_cached(c, sc.chrwork, sc.chrwork_shadow, cw.data(), cw.size() * sizeof(ChrWork), st));
@@ -1513,49 +1429,10 @@ static int enqueue_cv_planes(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, 
     SampleDev sd = make_sd(c, sc, T);
     const CvWork* Vt = sc.cvwork.as<CvWork>();
     const dim3 grid((unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK), sc.n_cvwork); const size_t lds = (size_t)sc.cv_max * sizeof(u64); const u32 nsub = 1u + c->rp_bits;
-    if (c->cv_threads == 256) hipLaunchKernelGGL((k_stitch_small<256>), grid, dim3(256), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
-    else if (c->cv_threads == 1024) hipLaunchKernelGGL((k_stitch_small<1024>), grid, dim3(1024), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
-    else hipLaunchKernelGGL((k_stitch_small<512>), grid, dim3(512), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
+    hipLaunchKernelGGL((k_stitch_small<512>), grid, dim3(512), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
     if (has_mut) hipLaunchKernelGGL(k_cv_newmut, dim3((unsigned)ceil_div(n_people, 256), sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork.as<ChrWork>(), n_people, nchr, sd, (int)count_cols);
     KCHECK();
     return GEV_OK;
-}
-// Unused dynamic LDS per stitch workgroup that limits the workgroups per CU to `occ` (160 KiB of LDS per CU; the kernels' own
-// static LDS is 3.4 KiB, allocation granularity taken as 512 B): the SMALLEST padding with which occ + 1 workgroups no longer
-// fit, so that the rest of the LDS (about 20 KiB at occ = 6) stays available to the small kernels that run next to the stitch --
-// the sampling kernels stage 17.5 KiB of tables.  The largest padding that still admits `occ` workgroups leaves 2 KiB: a small
-// kernel then has to wait for a stitch workgroup to retire and displaces it (2.5 % fewer generations/s at config 2).
-static unsigned stitch_lds_pad(int occ)
-{
-    if (const char* e = getenv("GEV_STITCH_LDS_PAD")) return (unsigned)atoi(e);       // experiments
-    if (occ >= 8) return 0;
-    const unsigned cu_lds = 160u * 1024u, own_min = 3072u, own_max = 3584u;            // the kernels' static LDS lies between these
-    const unsigned per_wg = cu_lds / (unsigned)(occ + 1) + 1u;                          // occ + 1 of these exceed the CU
-    const unsigned pad = (per_wg - own_min + 511u) / 512u * 512u;
-    return std::min(pad, 64u * 1024u - own_max);
-}
-static const int OCC_CAND[] = {8, 7, 6};
-// called at the end of every gev_reproduce: times the generations of each candidate and settles on the fastest
-static void occ_tune_step(gev_ctx* c, size_t n_people)
-{
-    gev_ctx::OccTune& t = c->tune;
-    if (!c->stitch_occ_auto || c->stitch_occ_env || !c->dense || c->serialize) return;
-    const double now = host_ms(), delta = now - t.last;
-    t.last = now;
-    const bool resized = c->n_pop == 1 && t.people && (n_people > t.people + t.people / 4 || n_people + n_people / 4 < t.people);
-    if (t.phase == 0 || resized || (t.phase == 2 && ++t.age >= 512)) {       // (re)start: first candidate, the first interval is a transition
-        t.phase = 1; t.idx = 0; t.n = 0; t.best = 0; t.people = n_people; t.age = 0; c->stitch_occ = OCC_CAND[0];
-        return;
-    }
-    if (t.phase != 1) return;
-    const int GENS = 4;                                       // intervals per candidate; the first still contains the previous candidate's stitch
-    if (t.n >= 1) t.cur_min = t.n == 1 ? delta : std::min(t.cur_min, delta);   // min: robust against a one-off host stall (a list buffer growing)
-    if (++t.n < GENS) return;
-    const bool better = t.idx == 0 || t.cur_min < t.best * 0.985;
-    if (better) { t.best = t.cur_min; t.best_occ = OCC_CAND[t.idx]; }
-    if (better && t.idx + 1 < (int)(sizeof OCC_CAND / sizeof OCC_CAND[0])) { t.idx++; t.n = 0; c->stitch_occ = OCC_CAND[t.idx]; return; }
-    t.phase = 2; c->stitch_occ = t.best_occ;
-    if (g_trace_host) fprintf(stderr, "[gev] stitch workgroups per CU: %d (best interval %.3f ms)\n", t.best_occ, t.best);
 }
 // the HBM-bound part, on stream_big, after the small work of the same generation: ONE launch over (parent, chromosome)
 static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_people)
@@ -1574,10 +1451,10 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
             size_t est = 0;
             for (int k = 0; k < nchr; k++) if (c->chr_active[k]) est = std::max<size_t>(est, c->pop[pop].st[k].pool_last_taken);
             if (!c->alias_rows || !est) est = rows * c->pop[pop].cs[0].nseg;
-            const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(ceil_div(est + est / 8, 4), 256), c->stitch_grid);
-            if (c->stitch_u == 4) hipLaunchKernelGGL((k_stitch_segments<true, 4>), dim3(nblk, sc.n_chrwork), dim3(256), stitch_lds_pad(c->stitch_occ ? c->stitch_occ : 8), sb, sc.chrwork.as<ChrWork>(), nchr, sd);
-            else if (c->stitch_u == 1) hipLaunchKernelGGL((k_stitch_segments<true, 1>), dim3(nblk, sc.n_chrwork), dim3(256), stitch_lds_pad(c->stitch_occ ? c->stitch_occ : 8), sb, sc.chrwork.as<ChrWork>(), nchr, sd);
-            else hipLaunchKernelGGL((k_stitch_segments<true, 2>), dim3(nblk, sc.n_chrwork), dim3(256), stitch_lds_pad(c->stitch_occ ? c->stitch_occ : 8), sb, sc.chrwork.as<ChrWork>(), nchr, sd);
+            // (at most 16384 workgroups of 4 waves = 4 work-list entries each per chromosome; one 16-byte chunk per lane in flight:
+            // a 2 KiB segment is one step of a wave -- with 8 KiB segments 2 chunks gave 722, 4 gave 778 generations/s)
+            const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(ceil_div(est + est / 8, 4), 256), 16384);
+            hipLaunchKernelGGL((k_stitch_segments<true, 1>), dim3(nblk, sc.n_chrwork), dim3(256), 0, sb, sc.chrwork.as<ChrWork>(), nchr, sd);
         } else
             hipLaunchKernelGGL(k_stitch_rows, dim3((unsigned)rows, sc.n_chrwork), dim3(STITCH_THREADS), 0, sb, sc.chrwork.as<ChrWork>(), nchr, sd);
         KCHECK();
@@ -1595,14 +1472,15 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
 
 // ---- Simulation::ras_glob_seed / Simulation::random_mate on the device (gev_mate.h) --------------------------------------------
 // n ras_glob_seed() values into vals[0..n) and the engine state behind them into *state_out; the engine state in front comes from
-// the host (state_val) or from a device word (state_ptr)
-static int enqueue_glob(gev_ctx* c, hipStream_t st, u32 state_val, const u32* state_ptr, size_t n, u32* vals, u32* state_out, u32* flags)
+// the host (state_val) or from a device word (state_ptr).  blk holds the rejection counts: its user orders it against every other
+// draw into it (a scratch set's own, gev_glob_seeds' own)
+static int enqueue_glob(DevBuf& blk, hipStream_t st, u32 state_val, const u32* state_ptr, size_t n, u32* vals, u32* state_out, u32* flags)
 {
     const u64 n_cand = (u64)n + n / 512 + 512;                  // expected rejections: n / 4444 (2147483646 - 2147000000 of 2147483646 outputs)
     const unsigned nb = (unsigned)ceil_div((size_t)n_cand, REJ_CHUNK);
-    GEVC(c->d_globblk.ensure(nb * sizeof(u32), st));
-    hipLaunchKernelGGL(k_glob_count, dim3(nb), dim3(256), 0, st, state_val, state_ptr, n_cand, c->d_globblk.as<u32>());
-    hipLaunchKernelGGL(k_glob_emit, dim3(nb), dim3(256), 0, st, state_val, state_ptr, (u64)n, n_cand, c->d_globblk.as<u32>(), vals, state_out, flags);
+    GEVC(blk.ensure(nb * sizeof(u32), st));
+    hipLaunchKernelGGL(k_glob_count, dim3(nb), dim3(256), 0, st, state_val, state_ptr, n_cand, blk.as<u32>());
+    hipLaunchKernelGGL(k_glob_emit, dim3(nb), dim3(256), 0, st, state_val, state_ptr, (u64)n, n_cand, blk.as<u32>(), vals, state_out, flags);
     KCHECK();
     return GEV_OK;
 }
@@ -1647,7 +1525,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     // the free list of the segment pool.  L builds the mutation / interval lists, which nothing else of the generation reads, next
     // to the CV planes and A/D.  The dense stitch has its own stream as before.  All are joined into S before the status block
     // leaves.  Serialised mode (kernel timings without interference): everything on S.
-    hipStream_t S = c->stream, X = (c->serialize || !c->side_streams) ? S : c->stream_aux, L = (c->serialize || !c->side_streams) ? S : c->stream_list;
+    hipStream_t S = c->stream, X = c->serialize ? S : c->stream_aux, L = c->serialize ? S : c->stream_list;
     const size_t T = q.n_people * (size_t)c->nchr;
     q.th0 = host_ms();
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[0], S));
@@ -1660,13 +1538,11 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
         // An assortative generation's mating seeds were drawn in front of glob_state: gv[0] = its srand seed (:2170), the rest from glob_state on.
         if (q.assort) {
             HIPC(hipMemsetD32Async((hipDeviceptr_t)gv, (int)q.assort_seed0, 1, S));
-            GEVC(enqueue_glob(c, S, q.glob_state, nullptr, 1 + (q.has_mut ? T : 0), gv + 1, status + ST_GLOB_STATE, status + ST_FLAGS));
-        } else GEVC(enqueue_glob(c, S, q.glob_state, nullptr, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
+            GEVC(enqueue_glob(sc.globblk, S, q.glob_state, nullptr, 1 + (q.has_mut ? T : 0), gv + 1, status + ST_GLOB_STATE, status + ST_FLAGS));
+        } else GEVC(enqueue_glob(sc.globblk, S, q.glob_state, nullptr, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     }
     // (the mating stream starts here: it needs the seeds, not the state behind them)
     if (X != S) { HIPC(hipEventRecord(sc.ev_fork, S)); HIPC(hipStreamWaitEvent(X, sc.ev_fork, 0)); }
-    // overlap mode 2: only the ALU-bound sampling shares the GPU with the previous generation's stitch; everything latency-bound waits for it
-    if (c->sparse_after_stitch && c->planes_pending) HIPC(hipStreamWaitEvent(X, c->ev_planes, 0));
     if (q.fused && !q.assort) {
         GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father.as<u32>(), sc.mother.as<u32>(),
                           c->d_couples.as<gev_couple>(), status + ST_NM_MATE, status + ST_FLAGS));
@@ -1675,9 +1551,6 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
         hipLaunchKernelGGL(k_glob_skip, dim3(1), dim3(64), 0, S, (const u32*)(status + ST_GLOB_STATE), (u32)c->chain_draws, status + ST_NEXT_STATE);
         KCHECK();
         HIPC(hipEventRecord(sc.ev_chain, S));
-        // the NEXT generation's seeds and sampling go to their stream right away: they take most of a generation's time next to this
-        // generation's chain, and the next generation's unit table cannot start before they are through
-        if (attempt == 0 && c->head_start == 1) GEVC(enqueue_chain_head_start(c));
     }
     GEVC(enqueue_tables(c, sc, q.pop, q.n_people, S));        // (uploaded on S while X mates)
     if (X != S) { HIPC(hipEventRecord(sc.ev_tab, S)); HIPC(hipStreamWaitEvent(X, sc.ev_tab, 0)); }
@@ -1686,20 +1559,13 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, 0u, S, gv + 1, gv + 2, /*clear_status=*/false));
     else if (!q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, q.seed, S));
     q.th1 = host_ms();
-    if (c->sparse_after_stitch && c->planes_pending && X != S) HIPC(hipStreamWaitEvent(S, c->ev_planes, 0));
     if (X != S) HIPC(hipStreamWaitEvent(S, sc.ev_aux, 0));
-    if (sampled && q.fused && c->head_start == 1) HIPC(hipStreamWaitEvent(S, sc.ev_sampled, 0));   // crossovers and new mutations of this generation (head start)
     HIPC(hipEventRecord(sc.t[5], S));
     // (the counters of the unit table concern the stitch and the host only: with the stitch behind the small work they are
     // published from the list stream, one launch less on the chain the host waits for)
-    const bool publish_aside = c->stitch_start >= 2 && L != S;
+    const bool publish_aside = L != S;
     GEVC(enqueue_pool_assign(c, sc, q.n_people, S, !publish_aside));
-    // The dense stitch needs the sampling results, the couples and the unit table only.  It saturates HBM, and every latency-bound
-    // kernel that runs next to it takes 2-5 times as long (and slows it down in turn): where it starts is a trade (stitch_start,
-    // measured at config 2: behind the CV planes 711, behind the unit table 691, behind A/D 617 generations/s); whatever the
-    // choice, the NEXT generation's ALU-bound sampling (head start) is what should share the GPU with it.
     HIPC(hipEventRecord(sc.ev_forked, S));
-    if (c->stitch_start == 0) { HIPC(hipEventRecord(sc.ev_small_done, S)); GEVC(enqueue_stitch(c, sc, q.pop, q.n_people)); }
     // (the host enqueues slower than the device runs the first kernels of a generation: what the host waits for goes first, the
     // list kernels, which nothing of the generation reads, last)
     // the column counters are filled while the planes are written only if the A/D kernels that consume (and clear) them follow in this attempt
@@ -1707,7 +1573,6 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     const bool count_cols = ad_now && sc.cv_count_fused && sc.n_cvwork && sc.cv_used_max;
     GEVC(enqueue_cv_planes(c, sc, q.n_people, q.has_mut, count_cols, S));
     HIPC(hipEventRecord(sc.t[2], S));
-    if (c->stitch_start == 1) { HIPC(hipEventRecord(sc.ev_small_done, S)); GEVC(enqueue_stitch(c, sc, q.pop, q.n_people)); }
     q.th2 = host_ms();
     if (c->ad_cached_pop != q.pop) c->ad_cached_pop = -1;    // (the device-side arrays are about to be rewritten; the published values of q.pop stay readable in their pinned buffer)
     c->ad_host_set_pop = -1;
@@ -1722,7 +1587,11 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (L != S) HIPC(hipEventRecord(sc.ev_lists, L));
     if (L != S) HIPC(hipStreamWaitEvent(S, sc.ev_lists, 0));
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[2], S));
-    if (c->stitch_start >= 2) { HIPC(hipEventRecord(sc.ev_small_done, S)); GEVC(enqueue_stitch(c, sc, q.pop, q.n_people)); }
+    // The dense stitch needs the sampling results, the couples and the unit table only, but it saturates HBM, and every
+    // latency-bound kernel that runs next to it takes 2-5 times as long (and slows it down in turn).  Behind the whole small work,
+    // at the small kernels' priority, it runs alone for 0.16 ms next to the host's turn-around; the NEXT generation's ALU-bound
+    // sampling (head start) is what shares the GPU with it (streams).
+    HIPC(hipEventRecord(sc.ev_small_done, S)); GEVC(enqueue_stitch(c, sc, q.pop, q.n_people));
     HIPC(hipMemcpyAsync(q.hstatus, sc.status.p, q.n_status * sizeof(u32), hipMemcpyDeviceToHost, S));
     HIPC(hipEventRecord(sc.ev_status, S));                  // gev_reproduce_end waits for THIS, not for whatever a head start queued behind it
     sc.th_enq = host_ms();
@@ -1827,8 +1696,7 @@ static int enqueue_chain_head_start(gev_ctx* c)
     GEVC(nx.globvals.ensure((2 + T) * sizeof(u32), SS));
     u32* gv = nx.globvals.as<u32>(); u32* status = nx.status.as<u32>();
     HIPC(hipMemsetAsync(nx.status.p, 0, q.n_status * sizeof(u32), SS));
-    GEVC(enqueue_glob(c, SS, 0u, sc.status.as<u32>() + ST_NEXT_STATE, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
-    HIPC(hipEventRecord(nx.ev_seeded, SS));               // status block cleared, seeds drawn: all that the next generation's mating needs
+    GEVC(enqueue_glob(nx.globblk, SS, 0u, sc.status.as<u32>() + ST_NEXT_STATE, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     GEVC(enqueue_sampling(c, nx, q.pop, q.n_people, q.has_mut, 0u, SS, gv + 1, gv + 2, /*clear_status=*/false));
     HIPC(hipEventRecord(nx.ev_sampled, SS));
     nx.fused_ahead = true; nx.fa_dropped = false; nx.fa_pop = q.pop; nx.fa_n = q.n_people; nx.fa_has_mut = q.has_mut;
@@ -1897,8 +1765,7 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     if (sc.presampled || sc.fa_dropped || (sc.fused_ahead && !pre)) HIPC(hipStreamSynchronize(c->stream_samp));     // a head start that does not match must not write into the set any more
     if (sc.fused_ahead) { if (pre) c->chain_hits++; else c->chain_misses++; }
     sc.presampled = false; sc.ps_stale = false; sc.mated = false; sc.fused_ahead = false; sc.fa_dropped = false; c->chain_valid = false;
-    // the head start ran on its own stream: mating needs its seeds, the unit table its crossovers (waited for in enqueue_attempt)
-    if (pre) HIPC(hipStreamWaitEvent(st, c->head_start == 1 ? sc.ev_seeded : sc.ev_sampled, 0));
+    if (pre) HIPC(hipStreamWaitEvent(st, sc.ev_sampled, 0));     // the head start ran on its own stream
     else {
         GEVC(harvest_timing(c, sc));
         if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
@@ -1920,7 +1787,7 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     q.assort = false;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
-    if (c->chain_draws >= 0 && c->head_start == 0) GEVC(enqueue_chain_head_start(c));
+    if (c->chain_draws >= 0) GEVC(enqueue_chain_head_start(c));    // behind this generation's work: the next generation waits for all of it
     return GEV_OK;
 }
 int gev_generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop_size, const double* selection_value_func)
@@ -2039,7 +1906,6 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
     } else if (sex_out) { HIPC(hipMemcpyAsync(sex_out, sc.sex.p, n_people, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.layout_epoch++; P.drop_selection();
     c->gen_counter++;
-    occ_tune_step(c, n_people);
     return GEV_OK;
 }
 int gev_reproduce_end(gev_ctx* c, uint8_t* sex_out)
@@ -2478,7 +2344,7 @@ int gev_glob_seeds(gev_ctx* c, uint32_t* engine_state, size_t n, uint32_t* out)
     GEVC(c->d_tmp.ensure((n + 4) * sizeof(u32), st));
     u32* vals = c->d_tmp.as<u32>() + 4; u32* stat = c->d_tmp.as<u32>();       // stat = {state, flags}
     HIPC(hipMemsetAsync(stat, 0, 16, st));
-    GEVC(enqueue_glob(c, st, *engine_state, nullptr, n, vals, stat, stat + 1));
+    GEVC(enqueue_glob(c->d_globblk, st, *engine_state, nullptr, n, vals, stat, stat + 1));
     u32 h[2] = {0, 0};
     HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
     if (out) HIPC(hipMemcpyAsync(out, vals, n * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -2655,8 +2521,7 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
             for (const AdWork& a : aw) direct &= a.cols_sorted != 0;
             bool chunked = direct, skip_d = true;                 // ... in whole 16-byte chunks: the term table in few large pieces (k_ad_accumulate_wide)
             for (const AdWork& a : aw) { chunked &= (a.sub_w32 & 3u) == 0 && (a.stride_w32 & 3u) == 0 && a.C > 0 && (size_t)a.sub_w32 * 32 >= (((size_t)a.C + 127) & ~(size_t)127); skip_d &= a.vd == 0; }
-            static const bool no_dir = getenv("GEV_AD_WIDE") && atoi(getenv("GEV_AD_WIDE")) == 0;
-            if (chunked && !no_dir) {
+            if (chunked) {
                 const unsigned nb = (unsigned)ceil_div(n, 256);
                 if (skip_d) hipLaunchKernelGGL((k_ad_accumulate_wide<true>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag);
                 else hipLaunchKernelGGL((k_ad_accumulate_wide<false>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag);
@@ -3403,8 +3268,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
             // units for the immigrants' segments: from the free list the generations keep (its entries behind the cursor are named by
             // no table, and nothing is in flight after gev_sync) while it lasts, else from a new one
             const size_t need_units = 2 * n * S.nseg;
-            static const bool keep_list = !(getenv("GEV_IMPORT_KEEP_LIST") && atoi(getenv("GEV_IMPORT_KEEP_LIST")) == 0);
-            const bool reuse = keep_list && cs.pool_list_valid && !cs.pool_force_rebuild && (size_t)cs.pool_cursor + need_units <= cs.pool_n_free;
+            const bool reuse = cs.pool_list_valid && !cs.pool_force_rebuild && (size_t)cs.pool_cursor + need_units <= cs.pool_n_free;
             if (!reuse) pool_new_stamp(cs);
             const PoolWork pw = pool_work(c, P, k, P.pcur);           // new slots of the CURRENT generation
             if (!reuse) GEVC(pool_free_list(pw, r_old, st));
@@ -3716,8 +3580,7 @@ int gev_download_plink_matrix(gev_ctx* c, int pop, int chr, size_t ind_begin, si
     return GEV_OK;
 }
 // CommFunc::ras_rank on the device (the O(n^2) host loop of assort_mate, src/Simulation.cpp:2278-2279): stable radix sort of
-// order-preserving keys with the reference's tie / NaN rule (gev_sort.hip); the all-pairs form (k_rank_f64) stays selectable with
-// GEV_RANK_ALLPAIRS=1 as an independent cross-check
+// order-preserving keys with the reference's tie / NaN rule (gev_sort.hip)
 extern "C" size_t gev_rank_scratch_bytes(size_t n);
 extern "C" int gev_rank_device(const double* d_x, size_t n, unsigned long long* d_rank, void* d_tmp, hipStream_t st);
 int gev_rank_f64(gev_ctx* c, const double* x, size_t n, unsigned long long* rank_out)
@@ -3731,15 +3594,9 @@ int gev_rank_f64(gev_ctx* c, const double* x, size_t n, unsigned long long* rank
     GEVC(c->d_tmp.ensure(n * 16, st));
     double* dx = c->d_tmp.as<double>(); unsigned long long* dr = (unsigned long long*)(dx + n);
     HIPC(hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, st));
-    static const bool allpairs = getenv("GEV_RANK_ALLPAIRS") != nullptr;
-    if (allpairs) {
-        hipLaunchKernelGGL(k_rank_f64, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, dx, n, dr);
-        KCHECK();
-    } else {
-        GEVC(c->d_text.ensure(gev_rank_scratch_bytes(n), st));
-        const int e = gev_rank_device(dx, n, dr, c->d_text.p, st);
-        if (e) return fail(GEV_EDEVICE, "rank_f64: HIP error %s in the sort", hipGetErrorString((hipError_t)e));
-    }
+    GEVC(c->d_text.ensure(gev_rank_scratch_bytes(n), st));
+    const int e = gev_rank_device(dx, n, dr, c->d_text.p, st);
+    if (e) return fail(GEV_EDEVICE, "rank_f64: HIP error %s in the sort", hipGetErrorString((hipError_t)e));
     HIPC(hipMemcpyAsync(rank_out, dr, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     return GEV_OK;
@@ -4020,10 +3877,9 @@ int gev_redo_count(gev_ctx* c, unsigned long long* n) { if (!c || !n) return fai
 int gev_set_overlap(gev_ctx* c, int on)
 {
     if (!c) return fail(GEV_EINVAL, "null");
+    if (on != 0 && on != 1) return fail(GEV_EINVAL, "set_overlap: %d is neither 0 (serialised) nor 1 (overlap)", on);
     GEVC(gev_sync(c));
-    c->overlap_mode = on < 0 ? -1 : std::min(on, 2);
-    c->sparse_after_stitch = c->overlap_mode == 2;
-    if (c->overlap_mode >= 0) c->serialize = c->overlap_mode == 0; else { c->serialize = true; c->auto_gens = 0; c->auto_small_ms = c->auto_stitch_ms = 0; }
+    c->serialize = on == 0;
     return GEV_OK;
 }
 int gev_set_stitch_mode(gev_ctx* c, int mode) { if (c && c->pend.active) return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first"); if (!c || mode < 0 || mode > 1) return fail(GEV_EINVAL, "stitch mode must be 0 (work list of the segments to write) or 1 (gamete-major)"); c->stitch_mode = mode; return GEV_OK; }

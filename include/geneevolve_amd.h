@@ -91,28 +91,26 @@ const char* gev_last_error(void);
 const char* gev_version(void);
 
 /* device < 0: use the current HIP device.
- * Environment read here (tuning / cross-check knobs; none changes a result):
- *   GEV_OVERLAP=0|1|2|-1        stream overlap mode (gev_set_overlap)
+ * The environment knobs the library reads, all of them (none changes a result; the first six are read here, the others where they
+ * are used).  Tests set them to force rare paths or to compare two forms of a computation; GEV_TRACE_HOST is diagnostic output:
+ *   GEV_OVERLAP=0|1             initial stream overlap mode (gev_set_overlap; default 1)
+ *   GEV_SAMPLE_BATCHED=0        one sampling task per wave (the round-1 kernels) instead of eight in one kernel
+ *   GEV_STITCH_MODE=0|1         dense stitch kernel (gev_set_stitch_mode; default 0, the segment work list)
  *   GEV_ALIAS_ROWS=0            write every segment of every gamete row (default 1: a segment without a crossover boundary shares the parental unit)
- *   GEV_STITCH_WG_PER_CU=n|auto dense-stitch workgroups per CU (default: unlimited; auto = measured at run time)
  *   GEV_SEG_CHUNKS=2^k          16-byte chunks per row segment (default 128 = 2 KiB; a row has at most 64 segments, longer rows get larger ones)
- *   GEV_STITCH_MODE=0|1         stitch kernel (gev_set_stitch_mode)
- *   GEV_STITCH_LDS_PAD=bytes    (experiments) dynamic LDS padding of the stitch workgroups, overriding the one derived from WG_PER_CU
- *   GEV_SAMPLE_BATCHED=0        one sampling task per wave (the round-1 kernels) instead of eight
- *   GEV_LIST_SEGS=n             most position ranges per row of the shared list pieces (default 32; 1 = one piece per list), GEV_LIST_ARENA=n
- *                               entries per row of their arenas (default: a tenth of the device memory) -- csrc/gev_lists.h
- *   GEV_STREAM_PRIO=xxxxx       h|m|l: priorities of the main, head-start, mating, list and stitch streams (default hhhhh);
- *                               GEV_STITCH_START=0|1|2: where in a generation the stitch is enqueued (default 2: behind the small work)
- *                               GEV_HEAD_START=1: the next generation's seeds and sampling are enqueued in front of the generation's own
- *                               work and waited for separately (seeds: mating, sampling: unit table); default 0 (same rate at config 2)
- *   GEV_CHAIN_WG=0              serial-chain mode with one wave per link; GEV_CHAIN_MAX_TASKS=n: most tasks accepted without a mutation map
- *   GEV_TABLE_RING_BYTES=n      minimum size of the pinned ring the per-generation work tables are staged through
+ *   GEV_OVF_CAP=n               initial size of the breakpoint / new-mutation overflow regions (tiny values force the grow-and-enqueue-again path)
+ *   GEV_LIST_SEGS=n             most position ranges per row of the shared list pieces (default 32; 1 = one piece per list) -- csrc/gev_lists.h
+ *   GEV_LIST_ARENA=n            entries per row of the list-piece arenas (default: a tenth of the device memory, at most 4096 per row)
+ *   GEV_LIST_HEADROOM=n         spare list entries per row when a list buffer is sized (default 48; 0: exact, every generation overflows and is enqueued again)
+ *   GEV_TABLE_RING_BYTES=n      minimum size of the pinned ring the per-generation work tables are staged through (default 256 KiB)
+ *   GEV_CHAIN_WG=0              serial-chain mode (no mutation map) with one wave per link instead of a workgroup
+ *   GEV_CHAIN_MAX_TASKS=n       most (offspring, chromosome) tasks accepted without a mutation map (default 4 000 000)
  *   GEV_AD_SHARED=0             several root populations with bit-identical CV effects: per-haplotype a/d lookup anyway (default: the one-population term table)
  *   GEV_AD_RP_FAST=0            several root populations with their own CV effects: per-haplotype a/d lookup in global memory (k_ad_accumulate) even
  *                               when the CV files are in position order (default then: k_ad_accumulate_rp, the piece's values in LDS)
- *   GEV_IMPORT_KEEP_LIST=0      gev_import_rows builds a new free list of row units instead of taking from the one the generations keep
- *   GEV_OVF_CAP=n, GEV_LIST_HEADROOM=n  (tests) initial size of the breakpoint / new-mutation overflow regions, spare list entries per row:
- *                               tiny values make generations overflow their buffers, so that the grow-and-enqueue-again path runs */
+ *   GEV_LP_LITERAL=1            list pieces built by recombine's statements one by one instead of their closed form (cross-check)
+ *   GEV_LP_LANES=1|8            lanes per new list piece (default: 1 below 20 interval entries per piece, else 8)
+ *   GEV_TRACE_HOST=1            stderr: host time per phase of a generation, the main stream's time by phase, allocations, deferred frees */
 int  gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen);
 void gev_destroy(gev_ctx* ctx);
 
@@ -509,10 +507,8 @@ int gev_stream(gev_ctx*, void** stream);
  * genotype planes keeps running on a second HIP stream and every later call is ordered after it
  * where it needs the planes.  gev_sync waits for all device work of the context. */
 int gev_sync(gev_ctx*);
-/* on == 1 (default): the stitch overlaps later work as described above; on == 0: gev_reproduce waits for it (kernel
- * timings without interference between the two streams); on == 2: only the ALU-bound sampling of the next generation
- * shares the GPU with the stitch, its memory-bound sparse/A-D kernels wait for it; on < 0: two serialised generations
- * are timed first and overlap is switched on unless the stitch is negligible (< 1/4 of the small kernels).
+/* on == 1 (default): the stitch overlaps later work as described above; on == 0: every generation runs on one stream and
+ * gev_reproduce waits for its stitch (kernel timings without interference).  Any other value: GEV_EINVAL.
  * Environment: GEV_OVERLAP=<on> sets the initial mode. */
 int gev_set_overlap(gev_ctx*, int on);
 /* kernel timing measured with HIP events on the library's own streams: ms[0] = sampling

@@ -15,7 +15,6 @@ if [ -n "$VARIANTS" ]; then
 else
 run A=1
 run A=1 --no-host-overlap
-run GEV_STITCH_START=0
 run A=1 --no-intervals
 fi
 cat $out
