@@ -38,6 +38,17 @@ class gev_gef_params(C.Structure):
                 ("s2_a_gen0", C.c_double), ("s2_d_gen0", C.c_double), ("gen_num", C.c_int32), ("reserved", C.c_int32)]
 
 
+class gev_pheno_scheme(C.Structure):
+    _fields_ = [("va", C.c_double), ("vd", C.c_double), ("vc", C.c_double), ("ve", C.c_double), ("vf", C.c_double), ("beta", C.c_double)]
+
+
+class gev_phenotypes_params(C.Structure):
+    _fields_ = [("gen_num", C.c_int32), ("vt_type", C.c_int32), ("scheme", C.c_void_p)]
+
+
+PHENOTYPE_COMPONENTS = ("additive", "dominance", "bv", "common_sibling", "e_noise", "parental_effect", "phen")
+
+
 class gev_selection_params(C.Structure):
     _fields_ = [("gen_num", C.c_int32), ("func", C.c_int32), ("par1", C.c_double), ("par2", C.c_double),
                 ("omega", C.c_void_p), ("lambda_", C.c_void_p), ("phen_shift", C.c_void_p)]
@@ -82,6 +93,8 @@ ABI_SYMBOLS = [
     "compute_selection", "download_selection", "get_selection_gen0", "set_selection_gen0", "generation_begin_selected", "random_mate_selected",
     "assort_mate", "assort_mate_selected", "last_assort_result", "generation_begin_assort", "generation_begin_assort_selected",
     "dbg_assort_knobs", "dbg_assort_stats",
+    "set_track_pedigree", "download_pedigree", "upload_pedigree",
+    "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "dbg_verify_planes", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
@@ -177,6 +190,7 @@ class GevContext:
         self.h = h
         self._nsnp = {}
         self._ncv = {}
+        self._ph_seeds = 0
 
     def close(self):
         if self.h:
@@ -381,6 +395,74 @@ class GevContext:
         r, _ = self.last_assort_result()
         self._pending_people, self._pending_couples = r["n_offspring"], r["n_couples"]
         return r
+
+    def set_track_pedigree(self, on):
+        """True (before init_gen0): the library keeps the seven pedigree ids of every individual on the device"""
+        self._call_new("set_track_pedigree", C.c_int(1 if on else 0))
+
+    def download_pedigree(self, pop):
+        """-> int64 [n_people][7]: ID, ID_Father, ID_Mother, ID_Fathers_Father, ID_Fathers_Mother, ID_Mothers_Father, ID_Mothers_Mother"""
+        ids = np.zeros((self.pop_size(pop), 7), dtype=np.int64)
+        self._call_new("download_pedigree", C.c_int(pop), _p(ids))
+        return ids
+
+    def upload_pedigree(self, pop, ids):
+        """restore the ids of the population's current individuals ([n_people][7] as download_pedigree) after remove_rows / import_rows"""
+        ids = _arr(ids, np.int64)
+        if ids.shape != (self.pop_size(pop), 7):
+            raise ValueError("upload_pedigree: one row of 7 ids per individual expected")
+        self._call_new("upload_pedigree", C.c_int(pop), _p(ids))
+
+    def generation_phenotypes(self, pop, gen_num, glob_state, schemes, vt_type=1):
+        """ras_scale_AD_compute_GEF for every phenotype from the library's own state (enqueues only).  schemes: one (va, vd, vc, ve,
+        vf, beta) per phenotype"""
+        if len(schemes) != self.nphen:
+            raise ValueError("generation_phenotypes: one scheme per phenotype expected")
+        sch = (gev_pheno_scheme * self.nphen)(*[gev_pheno_scheme(*[float(x) for x in s]) for s in schemes])
+        par = gev_phenotypes_params(int(gen_num), int(vt_type), C.cast(sch, C.c_void_p))
+        self._call_new("generation_phenotypes", C.c_int(pop), C.byref(par), C.c_uint32(int(glob_state)))
+        self._ph_seeds = (self.nphen + sum(1 for s in schemes if s[2] > 0)) if gen_num == 0 else self.nphen
+
+    def phenotypes_result(self, pop):
+        """waits -> dict(glob_state, seeds (uint32, draw order), var [nphen][7] of A D G C E F P)"""
+        st = C.c_uint32(); seeds = np.zeros(2 * self.nphen, dtype=np.uint32); var = np.zeros((self.nphen, 7))      # (at most two seeds per phenotype)
+        self._call_new("phenotypes_result", C.c_int(pop), C.byref(st), _p(seeds), _p(var))
+        return {"glob_state": st.value, "seeds": seeds[:self._ph_seeds].copy(), "var": var}
+
+    def download_phenotypes(self, pop, phen):
+        """-> dict of the seven n-vectors of PHENOTYPE_COMPONENTS"""
+        out = np.zeros((7, self.pop_size(pop)))
+        self._call_new("download_phenotypes", C.c_int(pop), C.c_int(phen), _p(out))
+        return dict(zip(PHENOTYPE_COMPONENTS, out))
+
+    def get_ad_gen0(self, pop, phen):
+        a, d = C.c_double(), C.c_double()
+        self._call_new("get_ad_gen0", C.c_int(pop), C.c_int(phen), C.byref(a), C.byref(d))
+        return a.value, d.value
+
+    def set_ad_gen0(self, pop, phen, var_a, var_d):
+        self._call_new("set_ad_gen0", C.c_int(pop), C.c_int(phen), C.c_double(var_a), C.c_double(var_d))
+
+    def save_prev_gen(self, pop, phen_shift=None):
+        sh = None if phen_shift is None else _arr(phen_shift, np.float64)
+        if sh is not None and len(sh) != self.nphen:
+            raise ValueError("save_prev_gen: one shift per phenotype expected")
+        self._call_new("save_prev_gen", C.c_int(pop), _p(sh))
+
+    def upload_prev_gen(self, pop, phen, parental_effect):
+        """the saved record from the host: [nphen][n] each (None = zeros)"""
+        ph = None if phen is None else _arr(phen, np.float64).reshape(self.nphen, -1)
+        pe = None if parental_effect is None else _arr(parental_effect, np.float64).reshape(self.nphen, -1)
+        n = (ph if ph is not None else pe).shape[1]
+        if ph is not None and pe is not None and ph.shape != pe.shape:
+            raise ValueError("upload_prev_gen: phen and parental_effect differ in shape")
+        self._call_new("upload_prev_gen", C.c_int(pop), _p(ph), _p(pe), C.c_size_t(n))
+
+    def dbg_phenotype_knobs(self, short_candidates=False):
+        """-> phenotype steps run again so far; short_candidates: start the following steps' normal streams far too short"""
+        n = C.c_ulonglong()
+        self._call_new("dbg_phenotype_knobs", C.c_int(int(bool(short_candidates))), C.byref(n))
+        return int(n.value)
 
     def compute_selection(self, pop, gen_num, func, par1, par2, omega, lambda_, phen_shift=None, want=("mating_value", "selection_value", "selection_value_func")):
         """Simulation::ras_compute_mating_value_selection_value + ras_selection_func on the device, from the phenotypes the last

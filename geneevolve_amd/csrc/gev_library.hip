@@ -21,6 +21,8 @@
 
 #include "gev_kernels.h"
 #include "gev_select.h"
+#include "gev_pedigree.h"
+#include "gev_phenotypes.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...)
@@ -176,7 +178,23 @@ struct PopState {
     int sbuf = 0;
     std::vector<uint8_t> phen_ok;
     bool sel_ok = false, sv0_ok = false;
-    void drop_selection() { std::fill(phen_ok.begin(), phen_ok.end(), 0); sel_ok = false; }
+    void drop_selection() { std::fill(phen_ok.begin(), phen_ok.end(), 0); sel_ok = false; comp_ok = false; cs_ok = false; }
+    // gev_set_track_pedigree: the seven ID fields of the current generation (gev_pedigree.h), planes of ids_stride[ibuf] rows indexed by
+    // PHYSICAL row; [ibuf] is current, a generation in flight / gev_migrate / a materialised order write the other one.  ids_ok: they
+    // describe the current individuals (dropped by gev_remove_rows / gev_import_rows, restored by gev_upload_pedigree)
+    DevBuf d_ids[2]; size_t ids_stride[2] = {0, 0};
+    int ibuf = 0;
+    bool ids_ok = false;
+    // gev_generation_phenotypes (gev_phenotypes.h).  d_cidx[ibuf]: the couple index of every child of the generation just published,
+    // cs_seed / cs_ncouples its seed_reproduce and the length of its couples list (cs_ok: until the rows change) -- what the family
+    // effect of Simulation::reproduce is drawn from.  d_comp[cbuf]: [nphen][7][n_people] A D G C E F P of the current individuals
+    // (comp_ok; they follow gev_migrate).  d_prev: the saved record [nphen][2][prev_n] (phen, parental_effect).  ad0: host copies of
+    // _var_a_gen0 / _var_d_gen0 per phenotype
+    DevBuf d_cidx[2], d_comp[2], d_prev;
+    int cbuf = 0;
+    bool cs_ok = false, comp_ok = false, prev_ok = false, ad0_ok = false;
+    u32 cs_seed = 0; size_t cs_ncouples = 0, prev_n = 0;
+    std::vector<double> ad0;
 };
 
 struct gev_ctx {
@@ -188,6 +206,7 @@ struct gev_ctx {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float last_ms[4] = {0, 0, 0, 0};
     bool track_intervals = true;
+    bool track_pedigree = false;            // gev_set_track_pedigree
     std::vector<PopState> pop;
     DevBuf d_tables;
     // per-generation scratch: two sets, because the dense stitch of generation g (stream_big) still reads set g%2
@@ -209,7 +228,8 @@ struct gev_ctx {
         bool presampled = false; int ps_pop = -1; u32 ps_seed = 0; size_t ps_n_people = 0; bool ps_has_mut = false;
         bool ps_stale = false;      // the head start was dropped by a redo of the generation in flight (record capacities changed): gev_presample_sex samples again from the retained inputs
         // gev_random_mate: father / mother of this set hold the couples of the next gev_reproduce (couples == NULL) of mate_pop
-        bool mated = false; int mate_pop = -1; size_t mate_n = 0; unsigned long long mate_epoch = 0;
+        bool mated = false, mate_assort = false; int mate_pop = -1; size_t mate_n = 0; unsigned long long mate_epoch = 0;
+        DevBuf cidx;                // gev_set_track_pedigree: the couple index of every child of a couples list the host passed
         // gev_set_generation_chain: seeds drawn and sampling enqueued for the NEXT gev_generation_begin (same population, size) from the predicted engine state
         bool fused_ahead = false, fa_dropped = false, fa_has_mut = false; int fa_pop = -1; size_t fa_n = 0;
         hipEvent_t ev_chain = nullptr, ev_tab = nullptr;
@@ -249,7 +269,8 @@ struct gev_ctx {
     unsigned long long chunks_written_sum = 0, chunks_total_sum = 0, segments_written_sum = 0, segments_total_sum = 0;   // over all generations and active chromosomes (gev_stitch_totals)
     struct PendingRepro { bool active = false, has_mut = false, pre = false; int pop = 0, attempt = 0; size_t n_people = 0, n_status = 0; u32 seed = 0; u32* hstatus = nullptr; double th0 = 0, th1 = 0, th2 = 0;
                           bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; const double* d_svf = nullptr; /* with has_svf: what the mating reads */ u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr;
-                          bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0; } pend;
+                          bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0;
+                          int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
     DevBuf d_snpmajor, d_text;
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
@@ -263,6 +284,18 @@ struct gev_ctx {
         unsigned long long n_chunks = 0, n_direct = 0, pois_reruns = 0;
     } am;
     DevBuf d_cvdone;
+    // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob
+    struct PhenoState {
+        DevBuf res /* result words, then {mean, var} pairs: e, the components, raw A and D */, starts, partial, eraw, cval, streams, tasks, blk, globblk, shift;
+        void* h_res = nullptr; size_t h_res_bytes = 0;
+        hipEvent_t ev = nullptr;
+        bool pending = false; int pop = -1; unsigned long long epoch = 0;
+        std::vector<gev_pheno_scheme> scheme; int gen_num = 0, vt_type = 1; u32 glob_state = 0;
+        size_t n = 0, words = 0, n_seeds = 0;
+        int cand_shift = 0;                                // candidate pairs per stream are doubled this many times (grown by a rerun)
+        bool short_candidates = false;                     // test hook: start far too short
+        unsigned long long reruns = 0;
+    } ph;
     DevBuf d_cnt, d_sums, d_map, d_cvm, d_addchr, d_domchr, d_add, d_dom, d_flag, d_stage, d_thr32, d_tmp;
     // per-generation work tables (gev_kernels.h: ChrWork / CvWork / AdWork) are written into a ring of pinned host memory and
     // copied to the device on the stream that uses them
@@ -449,6 +482,8 @@ void gev_destroy(gev_ctx* c)
     if (c->h_seeds) (void)hipHostFree(c->h_seeds);
     for (void* h : c->h_ad2) if (h) (void)hipHostFree(h);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
+    if (c->ph.h_res) (void)hipHostFree(c->ph.h_res);
+    if (c->ph.ev) (void)hipEventDestroy(c->ph.ev);
     delete c;
     if (s) (void)hipStreamDestroy(s);
 }
@@ -960,6 +995,14 @@ int gev_init_gen0(gev_ctx* c, int pop, size_t n_people, uint32_t seed_gen0, uint
     }
     hipLaunchKernelGGL(k_sex_sequence, dim3(1), dim3(64), 0, c->stream, c->d_tables.as<GevRngTables>(), (u32)seed_gen0, n_people, P.d_sex[P.cur].as<uint8_t>());
     KCHECK();
+    P.ids_ok = false;
+    if (c->track_pedigree) {                                 // ID = ID_Father = ... = i (:3037-3043)
+        GEVC(P.d_ids[P.ibuf].ensure(PED_FIELDS * n_people * sizeof(int64_t), c->stream));
+        P.ids_stride[P.ibuf] = n_people;
+        hipLaunchKernelGGL(k_ped_gen0, dim3((unsigned)ceil_div(n_people, 256)), dim3(256), 0, c->stream, P.d_ids[P.ibuf].as<int64_t>(), n_people, n_people);
+        KCHECK();
+        P.ids_ok = true;
+    }
     if (sex_out) HIPC(hipMemcpyAsync(sex_out, P.d_sex[P.cur].p, n_people, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     for (int k = 0; k < c->nchr; k++) { P.st[k].mut_total[P.cur] = 0; P.st[k].parts_total[P.cur] = c->chr_active[k] ? rows : 0; P.st[k].pool_list_valid = false; P.st[k].csr_valid = true; P.st[k].lp.valid = false; }
@@ -1582,6 +1625,16 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (publish_aside) GEVC(enqueue_pool_publish(c, sc, q.n_people, L));
     // Human::sex of the new generation (:2472) for the next gev_random_mate; a fused generation also sends them to the host with the status block
     HIPC(hipMemcpyAsync(P.d_sex[P.cur ^ 1].p, sc.sex.p, q.n_people, hipMemcpyDeviceToDevice, L));
+    if (P.ids_ok) {                                          // the offspring's pedigree ids (:2473-2479) from the parents' rows, into the other buffer
+        const int nb = P.ibuf ^ 1;
+        GEVC(P.d_ids[nb].ensure(PED_FIELDS * q.n_people * sizeof(int64_t), L)); GEVC(P.d_cidx[nb].ensure(q.n_people * sizeof(u32), L));
+        P.ids_stride[nb] = q.n_people;
+        hipLaunchKernelGGL(k_ped_offspring, dim3((unsigned)ceil_div(q.n_people, 256)), dim3(256), 0, L, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf],
+                           P.n_phys, (const u32*)sc.father.as<u32>(), (const u32*)sc.mother.as<u32>(), q.n_people, P.d_ids[nb].as<int64_t>(), q.n_people,
+                           q.cidx_mode == 1 ? (const u32*)sc.cidx.as<u32>() : (const u32*)nullptr, q.cidx_mode == 2 ? (const u32*)c->am.ooff.as<u32>() : (const u32*)nullptr,
+                           (u32)q.n_couples, P.d_cidx[nb].as<u32>());
+        KCHECK();
+    }
     if (q.fused) { HIPC(hipMemcpyAsync(q.hsex, sc.sex.p, q.n_people, hipMemcpyDeviceToHost, L)); HIPC(hipMemcpyAsync(q.hseeds2, gv, 2 * sizeof(u32), hipMemcpyDeviceToHost, L)); }   // (copies nothing on the device waits for: off the main stream)
     GEVC(enqueue_lists(c, sc, q.n_people, q.has_mut, L));
     if (L != S) HIPC(hipEventRecord(sc.ev_lists, L));
@@ -1634,9 +1687,10 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
                     "after the gev_random_mate / gev_assort_mate that formed them: its positions no longer name the same rows", pop);
     // pinned staging: [father | mother | mut_seeds | status], written by the host, copied asynchronously
     const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
-    const size_t stage_words = 2 * n_people + (has_mut ? T : 0) + n_status;
+    const size_t stage_words = 2 * n_people + (has_mut ? T : 0) + n_status + (c->track_pedigree ? n_people : 0);
     GEVC(ensure_stage(c, stage_words * 4));
     u32* father = (u32*)c->h_stage; u32* mother = father + n_people; u32* hseeds = mother + n_people; u32* hstatus = hseeds + (has_mut ? T : 0);
+    u32* hcidx = hstatus + n_status;                         // (tracking only) index of every child's couple in `couples`
     // offspring enumeration order of the couple loop (src/Simulation.cpp:2433-2443)
     size_t ip = 0;
     const u32* lg = P.logical.empty() ? nullptr : P.logical.data();
@@ -1648,7 +1702,9 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
         for (int ns = 0; ns < couples[it].num_offspring; ns++) {
             if (ip >= n_people) return fail(GEV_EINVAL, "reproduce: n_people=%zu but the couples list yields more offspring", n_people);
             father[ip] = lg ? lg[couples[it].pos_male] : (u32)couples[it].pos_male;
-            mother[ip] = lg ? lg[couples[it].pos_female] : (u32)couples[it].pos_female; ip++;
+            mother[ip] = lg ? lg[couples[it].pos_female] : (u32)couples[it].pos_female;
+            if (c->track_pedigree) hcidx[ip] = (u32)it;
+            ip++;
         }
     }
     if (!dev_couples && ip != n_people) return fail(GEV_EINVAL, "reproduce: n_people=%zu but the couples list yields %zu offspring", n_people, ip);
@@ -1657,6 +1713,7 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     GEVC(ensure_capacity(c, pop, n_people));
     hipStream_t st = c->stream;
     // sampling already enqueued by gev_presample for exactly these inputs?
+    const bool mate_assort = sc.mate_assort;
     const bool pre = sc.presampled && sc.ps_pop == pop && sc.ps_seed == (u32)seed_reproduce && sc.ps_n_people == n_people && sc.ps_has_mut == has_mut &&
                      (!has_mut || (c->h_seeds && memcmp(c->h_seeds, mut_seeds, T * sizeof(u32)) == 0));
     sc.presampled = false; sc.ps_stale = false; sc.mated = false; sc.fused_ahead = false; sc.fa_dropped = false; c->chain_valid = false;
@@ -1672,11 +1729,13 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     if (!dev_couples) {
         HIPC(hipMemcpyAsync(sc.father.p, father, n_people * sizeof(u32), hipMemcpyHostToDevice, st));
         HIPC(hipMemcpyAsync(sc.mother.p, mother, n_people * sizeof(u32), hipMemcpyHostToDevice, st));
+        if (P.ids_ok) { GEVC(sc.cidx.ensure(n_people * sizeof(u32), st)); HIPC(hipMemcpyAsync(sc.cidx.p, hcidx, n_people * sizeof(u32), hipMemcpyHostToDevice, st)); }
     }
 
     gev_ctx::PendingRepro& q = c->pend;
     q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = (u32)seed_reproduce; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
     q.fused = false; q.assort = false; q.has_svf = false; q.pool_rebuilt = false;
+    q.cidx_mode = !dev_couples ? 1 : (mate_assort ? 2 : 0); q.n_couples = !dev_couples ? n_couples : (mate_assort ? (size_t)c->am.res.n_couples : n_people);
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     return GEV_OK;
@@ -1784,7 +1843,7 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
     q.pool_rebuilt = false;
     q.fused = true; q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
-    q.assort = false;
+    q.assort = false; q.cidx_mode = 0; q.n_couples = n_people;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     if (c->chain_draws >= 0) GEVC(enqueue_chain_head_start(c));    // behind this generation's work: the next generation waits for all of it
@@ -1905,6 +1964,10 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
         if (couples_out) { HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n_rec * sizeof(gev_couple), hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     } else if (sex_out) { HIPC(hipMemcpyAsync(sex_out, sc.sex.p, n_people, hipMemcpyDeviceToHost, st)); HIPC(hipStreamSynchronize(st)); }
     P.cur = alt; P.pcur = (P.pcur + 1) % 3; P.n_people = n_people; P.n_phys = n_people; P.logical.clear(); P.layout_epoch++; P.drop_selection();
+    if (P.ids_ok) {                                         // (every attempt wrote the offspring's ids and couple indices into the other buffers)
+        P.ibuf ^= 1;
+        P.cs_ok = true; P.cs_seed = q.fused ? q.hseeds2[1] : q.seed; P.cs_ncouples = q.n_couples;
+    }
     c->gen_counter++;
     return GEV_OK;
 }
@@ -1966,7 +2029,7 @@ static int random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selecti
     sc.mated = false;
     if (h[2] & FLAG_NO_MATES) return fail(GEV_ENOMATE, "Error: No one can marry, num_males_mate=%u, num_females_mate=%u", h[0], h[1]);
     if (h[2] & FLAG_RNG_SHORT) return fail(GEV_EDEVICE, "random_mate: a rejection stream ran out of candidates (internal error)");
-    sc.mated = true; sc.mate_pop = pop; sc.mate_n = pop_size; sc.mate_epoch = P.layout_epoch;
+    sc.mated = true; sc.mate_assort = false; sc.mate_pop = pop; sc.mate_n = pop_size; sc.mate_epoch = P.layout_epoch;
     return GEV_OK;
 }
 int gev_random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selection_value_func, size_t pop_size, gev_couple* couples_out,
@@ -2018,7 +2081,9 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     const bool pois = dist == 'p' || dist == 'P', fixed = dist == 'f' || dist == 'F';
     if (!pois && !fixed) return fail(GEV_EINVAL, "assort_mate: offspring distribution '%c' is neither 'p' nor 'f'", (char)dist);
     const bool avoid = par->avoid_inbreeding != 0;
-    if (avoid && !pedigree) return fail(GEV_EINVAL, "assort_mate: avoid_inbreeding needs the pedigree ids");
+    const bool dev_ped = avoid && !pedigree && c->track_pedigree;      // the ids the library tracks itself (gev_set_track_pedigree)
+    if (avoid && !pedigree && !dev_ped) return fail(GEV_EINVAL, "assort_mate: avoid_inbreeding needs the pedigree ids");
+    if (dev_ped && !P.ids_ok) return fail(GEV_ESTATE, "assort_mate: population %d's pedigree ids were dropped when its rows changed (gev_upload_pedigree restores them)", pop);
     if (!std::isfinite(par->mat_cor)) return fail(GEV_EINVAL, "assort_mate: mat_cor is not finite");
     if (par->pop_size == 0 || par->pop_size >= 0x7fffffffull) return fail(GEV_EINVAL, "assort_mate: pop_size %llu out of range", (unsigned long long)par->pop_size);
     const size_t n_h = P.n_people;
@@ -2050,7 +2115,7 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
         }
     }
     const int64_t* d_ped = nullptr;
-    if (avoid) {
+    if (avoid && !dev_ped) {
         GEVC(A.ped.ensure(n_h * 5 * sizeof(int64_t), st));
         HIPC(hipMemcpyAsync(A.ped.p, pedigree, n_h * 5 * sizeof(int64_t), hipMemcpyHostToDevice, st));
         d_ped = A.ped.as<int64_t>();
@@ -2141,7 +2206,11 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     const unsigned nb2 = (unsigned)ceil_div(n2, 256);
     hipLaunchKernelGGL(k_am_couples, dim3(nb2), dim3(256), 0, st, (const u32*)A.i1.as<u32>(), (const u32*)A.i2.as<u32>(), (const u32*)A.sorted_m.as<u32>(), (const u32*)A.sorted_f.as<u32>(),
                        n2, A.pm.as<u32>(), A.pf.as<u32>());
-    hipLaunchKernelGGL(k_am_inbreed, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), n2, d_ped, A.inb.as<u32>(), stat);
+    if (dev_ped)
+        hipLaunchKernelGGL(k_am_inbreed_ids, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), n2, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(),
+                           P.ids_stride[P.ibuf], logical, A.inb.as<u32>(), stat);
+    else
+        hipLaunchKernelGGL(k_am_inbreed, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), n2, d_ped, A.inb.as<u32>(), stat);
     KCHECK();
     size_t n_inb = 0;
     if (avoid) {
@@ -2217,7 +2286,7 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     if (couples_out) HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n2 * sizeof(gev_couple), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     A.res = r; A.valid = true;
-    if (r.n_offspring) { sc.mated = true; sc.mate_pop = pop; sc.mate_n = r.n_offspring; sc.mate_epoch = P.layout_epoch; }
+    if (r.n_offspring) { sc.mated = true; sc.mate_assort = true; sc.mate_pop = pop; sc.mate_n = r.n_offspring; sc.mate_epoch = P.layout_epoch; }
     return GEV_OK;
 }
 int gev_assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const uint32_t seeds[4], const double* mating_value,
@@ -2315,6 +2384,7 @@ static int generation_begin_assort(gev_ctx* c, int pop, uint32_t glob_state, con
     q.pool_rebuilt = false;
     q.fused = true; q.has_svf = false; q.d_svf = nullptr; q.glob_state = state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
     q.assort = true; q.assort_seed0 = seeds[0]; q.am_nm = r.num_males_mate; q.am_nf = r.num_females_mate; q.am_couples = r.n_couples;
+    q.cidx_mode = 2; q.n_couples = r.n_couples;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     return GEV_OK;
@@ -2959,6 +3029,17 @@ static int materialize_order(gev_ctx* c, int pop)
     Seg all; all.src_pop = pop; all.people = P.logical;
     std::vector<Seg> segs; segs.push_back(std::move(all));
     GEVC(gather_population(c, pop, segs, P.n_people));
+    if (P.ids_ok) {                                         // the pedigree ids are kept by physical row: they move with the rows
+        const int nb = P.ibuf ^ 1;
+        GEVC(P.d_ids[nb].ensure(PED_FIELDS * P.n_people * sizeof(int64_t), c->stream));
+        GEVC(h2d(c, c->d_map, P.logical.data(), P.n_people * sizeof(u32)));
+        hipLaunchKernelGGL(k_ped_gather, dim3((unsigned)ceil_div(P.n_people, 256)), dim3(256), 0, c->stream, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf],
+                           (const u32*)c->d_map.as<u32>(), P.n_people, P.d_ids[nb].as<int64_t>(), P.n_people);
+        KCHECK();
+        HIPC(hipStreamSynchronize(c->stream));
+        P.ids_stride[nb] = P.n_people; P.ibuf = nb;
+    }
+    P.cs_ok = false; P.comp_ok = false;
     P.cur ^= 1; P.pcur = (P.pcur + 1) % 3; P.n_phys = P.n_people; P.logical.clear(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
@@ -3012,6 +3093,63 @@ static int migrate_selection(gev_ctx* c, const std::vector<std::vector<Seg>>& pl
     }
     return GEV_OK;
 }
+// The pedigree ids follow the individuals as the selection values do (gev_set_track_pedigree); kept where every population that
+// contributes individuals had them.  Called behind materialize_order: positions are physical rows.
+static int migrate_pedigree(gev_ctx* c, const std::vector<std::vector<Seg>>& plan, const std::vector<size_t>& n_new)
+{
+    if (!c->track_pedigree) return GEV_OK;
+    hipStream_t st = c->stream;
+    std::vector<uint8_t> ok(c->n_pop);
+    for (int d = 0; d < c->n_pop; d++) {
+        PopState& D = c->pop[d];
+        ok[d] = 1;
+        for (const Seg& sg : plan[d]) if (!sg.people.empty()) ok[d] = ok[d] && c->pop[sg.src_pop].ids_ok;
+        if (!ok[d]) continue;
+        const int nb = D.ibuf ^ 1;
+        GEVC(D.d_ids[nb].ensure(PED_FIELDS * n_new[d] * sizeof(int64_t), st));
+        size_t i0 = 0;
+        for (const Seg& sg : plan[d]) {
+            if (sg.people.empty()) continue;
+            const PopState& S = c->pop[sg.src_pop];
+            const size_t m = sg.people.size();
+            GEVC(h2d(c, c->d_map, sg.people.data(), m * sizeof(u32)));
+            hipLaunchKernelGGL(k_ped_gather, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, (const int64_t*)S.d_ids[S.ibuf].as<int64_t>(), S.ids_stride[S.ibuf],
+                               (const u32*)c->d_map.as<u32>(), m, D.d_ids[nb].as<int64_t>() + i0, n_new[d]);
+            KCHECK();
+            HIPC(hipStreamSynchronize(st));             // (d_map is refilled for the next segment)
+            i0 += m;
+        }
+    }
+    for (int d = 0; d < c->n_pop; d++) {
+        PopState& D = c->pop[d];
+        if (ok[d]) { D.ibuf ^= 1; D.ids_stride[D.ibuf] = n_new[d]; }
+        D.ids_ok = ok[d]; D.cs_ok = false;                  // (the children's couple indices belong to the rows as they were published)
+    }
+    // the phenotype components (gev_generation_phenotypes), plane by plane
+    const unsigned planes = (unsigned)c->nphen * PH_COMP;
+    for (int d = 0; d < c->n_pop; d++) {
+        PopState& D = c->pop[d];
+        ok[d] = 1;
+        for (const Seg& sg : plan[d]) if (!sg.people.empty()) ok[d] = ok[d] && c->pop[sg.src_pop].comp_ok;
+        if (!ok[d]) continue;
+        const int nb = D.cbuf ^ 1;
+        GEVC(D.d_comp[nb].ensure((size_t)planes * n_new[d] * sizeof(double), st));
+        size_t i0 = 0;
+        for (const Seg& sg : plan[d]) {
+            if (sg.people.empty()) continue;
+            const PopState& S = c->pop[sg.src_pop];
+            const size_t m = sg.people.size();
+            GEVC(h2d(c, c->d_map, sg.people.data(), m * sizeof(u32)));
+            hipLaunchKernelGGL(k_ph_gather, dim3((unsigned)ceil_div(m, 256), planes), dim3(256), 0, st, (const double*)S.d_comp[S.cbuf].as<double>(), S.n_people,
+                               (const u32*)c->d_map.as<u32>(), m, D.d_comp[nb].as<double>(), n_new[d], i0);
+            KCHECK();
+            HIPC(hipStreamSynchronize(st));
+            i0 += m;
+        }
+    }
+    for (int d = 0; d < c->n_pop; d++) { PopState& D = c->pop[d]; if (ok[d]) D.cbuf ^= 1; D.comp_ok = ok[d]; }
+    return GEV_OK;
+}
 int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
 {
     GEVC(check_not_pending(c));
@@ -3054,6 +3192,7 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
     for (int p = 0; p < c->n_pop; p++) GEVC(ensure_csr(c, p));          // whole lists of every population are read (before any flag of a destination changes)
     for (int p = 0; p < c->n_pop; p++) GEVC(gather_population(c, p, plan[p], n_new[p]));
     GEVC(migrate_selection(c, plan, n_new));
+    GEVC(migrate_pedigree(c, plan, n_new));
     for (int p = 0; p < c->n_pop; p++) { c->pop[p].cur ^= 1; c->pop[p].pcur = (c->pop[p].pcur + 1) % 3; c->pop[p].n_people = n_new[p]; c->pop[p].n_phys = n_new[p]; c->pop[p].layout_epoch++; }
     c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
@@ -3224,7 +3363,7 @@ int gev_remove_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n)
     // no row moves: only the logical order changes; stayers keep their order (src/Simulation.cpp:960-966)
     std::vector<u32> keep; keep.reserve(P.n_people - n);
     for (size_t i = 0; i < P.n_people; i++) if (!gone[i]) keep.push_back(P.logical.empty() ? (u32)i : P.logical[i]);
-    P.logical.swap(keep); P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.logical.swap(keep); P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); P.ids_ok = false; c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, size_t n)
@@ -3378,7 +3517,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     if (rb_flag & 1u) return fail(GEV_EINVAL, "import_rows: Error: p.hap_index is not in range");
     if (P.logical.empty()) { P.logical.resize(P.n_people); for (size_t i = 0; i < P.n_people; i++) P.logical[i] = (u32)i; }
     for (size_t i = 0; i < n; i++) P.logical.push_back((u32)(n_old + i));
-    P.n_phys = n_new; P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.n_phys = n_new; P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); P.ids_ok = false; c->ad_cached_pop = c->ad_host_set_pop = -1;
     return GEV_OK;
 }
 
@@ -3855,6 +3994,328 @@ int gev_plane_ptr(gev_ctx* c, int pop, int chr, void** dptr, size_t* unit_bytes,
 }
 int gev_stream(gev_ctx* c, void** s) { if (!c || !s) return fail(GEV_EINVAL, "null"); *s = (void*)c->stream; return GEV_OK; }
 int gev_last_reproduce_ms(gev_ctx* c, float ms[4]) { if (!c || !ms) return fail(GEV_EINVAL, "null"); GEVC(gev_sync(c)); for (int i = 0; i < 4; i++) ms[i] = c->last_ms[i]; return GEV_OK; }
+// ---- Simulation::ras_scale_AD_compute_GEF for every phenotype, fed from the device (gev_phenotypes.h) ------------------------------
+static size_t ph_candidates(const gev_ctx* c, size_t n)
+{
+    if (c->ph.short_candidates && c->ph.cand_shift == 0) return n / 4 + 16;
+    return ((size_t)((n / 2 + 1) / 0.7) + 4096) << c->ph.cand_shift;             // acceptance = pi/4
+}
+// mean / var of nvec vectors into stats (k_ph_var_partial / _final, both passes)
+static int ph_var(gev_ctx* c, const double* base, size_t vec_stride, size_t elem_stride, size_t n, unsigned nvec, double* stats)
+{
+    hipStream_t st = c->stream;
+    GEVC(c->ph.partial.ensure((size_t)nvec * 256 * sizeof(double), st));
+    const int nb = (int)std::min<size_t>(ceil_div(n, 256), 256);
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(k_ph_var_partial, dim3(nb, nvec), dim3(256), 0, st, base, vec_stride, elem_stride, n, (const double*)stats, pass, c->ph.partial.as<double>());
+        hipLaunchKernelGGL(k_ph_var_final, dim3(nvec), dim3(256), 0, st, (const double*)c->ph.partial.as<double>(), nb, n, pass, stats);
+    }
+    KCHECK();
+    return GEV_OK;
+}
+static int ph_streams(gev_ctx* c, std::vector<NrmStream>& v, const u32* seeds)
+{
+    if (v.empty()) return GEV_OK;
+    hipStream_t st = c->stream;
+    u32 off = 0, nb_max = 0;
+    for (NrmStream& s : v) { s.n_blocks = (u32)ceil_div((size_t)s.n_cand, NRM_CHUNK); s.blk_off = off; off += s.n_blocks; nb_max = std::max(nb_max, s.n_blocks); }
+    GEVC(c->ph.blk.ensure(off * sizeof(u32), st));
+    GEVC(upload_table(c, c->ph.streams, v.data(), v.size() * sizeof(NrmStream), st));
+    hipLaunchKernelGGL(k_nrm_count, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, (const u32*)c->ph.starts.as<u32>(), c->ph.blk.as<u32>());
+    hipLaunchKernelGGL(k_nrm_emit, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, c->ph.starts.as<u32>(), (const u32*)c->ph.blk.as<u32>(),
+                       c->ph.res.as<u32>() + PHR_FLAGS);
+    KCHECK();
+    return GEV_OK;
+}
+static int ph_enqueue(gev_ctx* c)
+{
+    gev_ctx::PhenoState& H = c->ph;
+    PopState& P = c->pop[H.pop];
+    hipStream_t st = c->stream;
+    const size_t n = P.n_people; const int nphen = c->nphen; const bool gen0 = H.gen_num == 0;
+    int nvc = 0;
+    for (int p = 0; p < nphen; p++) nvc += H.scheme[p].vc > 0;
+    const size_t n_seeds = (gen0 ? nvc : 0) + nphen;
+    H.n = n; H.n_seeds = n_seeds; H.words = round_up(PHR_SEEDS + n_seeds, 2);
+    const size_t n_stats = (size_t)nphen * (1 + PH_COMP + 2);                  // {mean, var}: e, 7 components, raw A, raw D per phenotype
+    const size_t res_bytes = H.words * sizeof(u32) + n_stats * 2 * sizeof(double);
+    GEVC(H.res.ensure(res_bytes, st)); GEVC(H.starts.ensure((nphen + 2) * sizeof(u32), st));
+    HIPC(hipMemsetAsync(H.res.p, 0, res_bytes, st)); HIPC(hipMemsetAsync(H.starts.p, 0, (nphen + 2) * sizeof(u32), st));
+    u32* res = H.res.as<u32>(); u32* seeds = res + PHR_SEEDS;
+    double* e_stats = (double*)(res + H.words); double* comp_stats = e_stats + 2 * nphen; double* a_stats = comp_stats + 2 * nphen * PH_COMP; double* d_stats = a_stats + 2 * nphen;
+    // the ras_glob_seed() values: generation 0 one per phenotype with vc > 0 (:3058), then one per phenotype (:3078)
+    GEVC(enqueue_glob(H.globblk, st, H.glob_state, nullptr, n_seeds, seeds, res + PHR_STATE, res + PHR_FLAGS));
+    DevBuf& comp = P.d_comp[P.cbuf];
+    GEVC(comp.ensure((size_t)nphen * PH_COMP * n * sizeof(double), st));
+    GEVC(H.eraw.ensure((size_t)nphen * n * sizeof(double), st));
+    const size_t cval_stride = gen0 ? 1 : std::max<size_t>(P.cs_ncouples, 1);
+    if (!gen0 && nvc) GEVC(H.cval.ensure((size_t)nphen * cval_stride * sizeof(double), st));
+    // _var_a_gen0 / _var_d_gen0 (:557-561) from the raw A/D; the host needs them for s_a / s_d: generation 0 waits once for them
+    if (gen0 && !P.ad0_ok) {
+        GEVC(ph_var(c, c->d_add.as<double>(), 1, (size_t)nphen, n, (unsigned)nphen, a_stats));
+        GEVC(ph_var(c, c->d_dom.as<double>(), 1, (size_t)nphen, n, (unsigned)nphen, d_stats));
+        std::vector<double> h(4 * (size_t)nphen);
+        HIPC(hipMemcpyAsync(h.data(), a_stats, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        P.ad0.assign(2 * (size_t)nphen, 0.0);
+        for (int p = 0; p < nphen; p++) { P.ad0[2 * p] = h[2 * p + 1]; P.ad0[2 * p + 1] = h[2 * nphen + 2 * p + 1]; }
+        P.ad0_ok = true;
+    }
+    // the normal streams.  Independent ones in one batch: the noise of every phenotype (:3080-3102), generation 0's family effect
+    // (an engine of its own seed per phenotype, :3053-3066) and parental effect (generator_f(seed + 1), :3095-3114)
+    std::vector<NrmStream> batch;
+    std::vector<PhTask> tasks(nphen);
+    int kvc = 0;
+    for (int p = 0; p < nphen; p++) {
+        const gev_pheno_scheme& S = H.scheme[p];
+        double* o = comp.as<double>() + (size_t)p * PH_COMP * n;
+        NrmStream e{}; e.seed_idx = (int)(gen0 ? nvc : 0) + p; e.start_idx = e.next_idx = -1; e.n = n; e.n_cand = ph_candidates(c, n); e.sd = 1.0; e.out = H.eraw.as<double>() + (size_t)p * n;
+        batch.push_back(e);
+        if (gen0 && S.vc > 0) { NrmStream s = e; s.seed_idx = kvc++; s.sd = std::sqrt(S.vc); s.out = o + PH_C * n; batch.push_back(s); }
+        if (gen0 && S.vf > 0) { NrmStream s = e; s.seed_add = 1; s.sd = std::sqrt(S.vf); s.out = o + PH_F * n; batch.push_back(s); }
+        PhTask& t = tasks[p];
+        t.s_a = 1; if (S.va > 0) t.s_a = std::sqrt(P.ad0[2 * p] / S.va);
+        t.s_d = 0; if (S.vd > 0) t.s_d = std::sqrt(P.ad0[2 * p + 1] / S.vd); else if (S.vd == -1) t.s_d = 1;
+        t.ve = S.ve; t.vf = S.vf; t.beta = S.beta;
+        t.has_c = S.vc > 0; t.c_by_couple = !gen0; t.f_gather = !gen0;
+        t.prev_plane = H.vt_type == 1 ? 0 : (H.vt_type == 2 ? 1 : -1);
+    }
+    // reproduce's family effect (:2417-2429): ONE engine (seed_reproduce + 1), a fresh distribution per phenotype with vc > 0 -- each
+    // starts at the candidate pair behind the last one its predecessor consumed, a device word.  The first one starts at pair 0 and
+    // rides with the batch; every later one is a launch pair of its own behind its predecessor
+    std::vector<std::vector<NrmStream>> chained;
+    if (!gen0) {
+        int k = 0;
+        for (int p = 0; p < nphen; p++) {
+            if (!(H.scheme[p].vc > 0)) continue;
+            NrmStream s{}; s.seed_idx = -1; s.seed_val = P.cs_seed; s.seed_add = 1; s.start_idx = k; s.next_idx = k + 1; s.n = P.cs_ncouples; s.n_cand = ph_candidates(c, P.cs_ncouples);
+            s.sd = std::sqrt(H.scheme[p].vc); s.out = H.cval.as<double>() + (size_t)p * cval_stride;
+            if (k == 0) batch.push_back(s); else chained.push_back(std::vector<NrmStream>(1, s));
+            k++;
+        }
+    }
+    GEVC(ph_streams(c, batch, seeds));
+    for (auto& one : chained) GEVC(ph_streams(c, one, seeds));
+    GEVC(ph_var(c, H.eraw.as<double>(), n, 1, n, (unsigned)nphen, e_stats));                       // CommFunc::var(e), two passes, n-1
+    GEVC(upload_table(c, H.tasks, tasks.data(), tasks.size() * sizeof(PhTask), st));
+    DevBuf& keep = P.d_phen[P.sbuf];
+    GEVC(keep.ensure(n * (size_t)nphen * sizeof(double), st));
+    hipLaunchKernelGGL(k_ph_apply, dim3((unsigned)ceil_div(n, 256), (unsigned)nphen), dim3(256), 0, st, (const PhTask*)H.tasks.as<PhTask>(), (const double*)c->d_add.as<double>(),
+                       (const double*)c->d_dom.as<double>(), n, (u32)nphen, (const double*)H.eraw.as<double>(), (const double*)e_stats, (const double*)H.cval.as<double>(), cval_stride,
+                       (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf], (const u32*)P.d_cidx[P.ibuf].as<u32>(),
+                       (const double*)P.d_prev.as<double>(), P.prev_n, comp.as<double>(), keep.as<double>(), res);
+    KCHECK();
+    GEVC(ph_var(c, comp.as<double>(), n, 1, n, (unsigned)nphen * PH_COMP, comp_stats));           // CommFunc::var of A D G C E F P (:2023-2037)
+    if (H.h_res_bytes < res_bytes) {
+        if (H.h_res) { HIPC(hipStreamSynchronize(st)); (void)hipHostFree(H.h_res); }
+        H.h_res = nullptr; H.h_res_bytes = 0;
+        HIPC(hipHostMalloc(&H.h_res, res_bytes * 2 + 256, hipHostMallocDefault));
+        H.h_res_bytes = res_bytes * 2 + 256;
+    }
+    HIPC(hipMemcpyAsync(H.h_res, H.res.p, res_bytes, hipMemcpyDeviceToHost, st));
+    if (!H.ev) HIPC(hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
+    HIPC(hipEventRecord(H.ev, st));
+    return GEV_OK;
+}
+int gev_generation_phenotypes(gev_ctx* c, int pop, const gev_phenotypes_params* par, uint32_t glob_state)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (!par || !par->scheme) return fail(GEV_EINVAL, "generation_phenotypes: null parameters");
+    if (par->gen_num < 0) return fail(GEV_EINVAL, "generation_phenotypes: gen_num %d", par->gen_num);
+    if (glob_state == 0 || glob_state >= GEV_M31) return fail(GEV_EINVAL, "generation_phenotypes: %u is not a state of std::minstd_rand0 (1 .. 2^31-2)", glob_state);
+    if (!c->track_pedigree) return fail(GEV_ESTATE, "generation_phenotypes: the context does not track pedigree ids (gev_set_track_pedigree)");
+    if (c->any_inactive && c->ad_host_set_pop != pop)
+        return fail(GEV_ESTATE, "generation_phenotypes: this context holds a subset of the chromosomes: give it the all-reduced raw A/D first (gev_set_ad / gev_ad_finish_device)");
+    PopState& P = c->pop[pop];
+    if (!P.gen0) return fail(GEV_ESTATE, "generation_phenotypes: population %d has no current generation", pop);
+    const bool gen0 = par->gen_num == 0;
+    bool any_vc = false, any_vf = false;
+    for (int p = 0; p < c->nphen; p++) { any_vc |= par->scheme[p].vc > 0; any_vf |= par->scheme[p].vf > 0; }
+    if (!P.ids_ok) return fail(GEV_ESTATE, "generation_phenotypes: population %d's pedigree ids were dropped when its rows changed (gev_upload_pedigree restores them)", pop);
+    if (!gen0 && !P.ad0_ok) return fail(GEV_ESTATE, "generation_phenotypes: population %d has no generation-0 variances of A and D (gen_num 0 first, or gev_set_ad_gen0)", pop);
+    if (!gen0 && any_vf && (par->vt_type == 1 || par->vt_type == 2) && !P.prev_ok)
+        return fail(GEV_ESTATE, "generation_phenotypes: vf > 0 at generation %d needs the saved record of the generation before (gev_save_prev_gen / gev_upload_prev_gen)", par->gen_num);
+    HIPC(hipSetDevice(c->device));
+    GEVC(materialize_order(c, pop));
+    if (!gen0 && any_vc && !P.cs_ok)
+        return fail(GEV_ESTATE, "generation_phenotypes: population %d's rows changed since its generation was published: the family effects of its couples can no longer be handed out", pop);
+    if (c->ad_cached_pop != pop && c->ad_host_set_pop != pop) GEVC(gev_compute_ad(c, pop, nullptr, nullptr, nullptr, nullptr));      // raw A/D of this generation on the device
+    gev_ctx::PhenoState& H = c->ph;
+    if (H.pending && c->pop[H.pop].layout_epoch == H.epoch)
+        return fail(GEV_ESTATE, "generation_phenotypes: the step of population %d is outstanding: call gev_phenotypes_result first", H.pop);
+    H.pop = pop; H.gen_num = par->gen_num; H.vt_type = par->vt_type; H.glob_state = glob_state; H.epoch = P.layout_epoch;
+    H.scheme.assign(par->scheme, par->scheme + c->nphen);
+    H.pending = false;
+    if (H.short_candidates) H.cand_shift = 0;                // (test hook: every step starts too short)
+    GEVC(ph_enqueue(c));
+    H.pending = true;
+    P.comp_ok = true; std::fill(P.phen_ok.begin(), P.phen_ok.end(), 1);
+    return GEV_OK;
+}
+int gev_phenotypes_result(gev_ctx* c, int pop, uint32_t* glob_state_after, uint32_t* seeds, double* var)
+{
+    GEVC(check_idx(c, pop, 0));
+    gev_ctx::PhenoState& H = c->ph;
+    if (!H.pending || H.pop != pop) return fail(GEV_ESTATE, "phenotypes_result: no gev_generation_phenotypes of population %d is outstanding", pop);
+    PopState& P = c->pop[pop];
+    if (H.epoch != P.layout_epoch) { H.pending = false; return fail(GEV_ESTATE, "phenotypes_result: population %d changed since gev_generation_phenotypes", pop); }
+    HIPC(hipSetDevice(c->device));
+    for (int attempt = 0;; attempt++) {
+        HIPC(hipEventSynchronize(H.ev));
+        const u32* w = (const u32*)H.h_res;
+        const u32 flags = w[PHR_FLAGS];
+        if (flags & FLAG_RNG_SHORT) { H.pending = false; P.comp_ok = false; P.drop_selection(); return fail(GEV_EDEVICE, "generation_phenotypes: the seed stream ran out of candidates (internal error)"); }
+        if (flags & PHF_CAND_SHORT) {                        // acceptance far below pi/4 (or the test hook): the step again with more candidate pairs
+            if (attempt == 6) { H.pending = false; P.comp_ok = false; P.drop_selection(); return fail(GEV_EDEVICE, "generation_phenotypes: normal streams still short of candidates after %d attempts", attempt + 1); }
+            H.cand_shift++; H.reruns++;
+            P.sel_ok = false;                                // (selection values computed meanwhile came from the short streams)
+            GEVC(ph_enqueue(c));
+            continue;
+        }
+        H.pending = false;
+        if (flags & PHF_ID_RANGE) {
+            P.comp_ok = false; P.drop_selection();
+            return fail(GEV_EUNSUPPORTED, "generation_phenotypes: %u individuals of population %d have a parent id at or beyond the %zu entries of the saved record "
+                        "(the reference reads past the end of its array there)", w[PHR_NBAD], pop, P.prev_n);
+        }
+        if (glob_state_after) *glob_state_after = w[PHR_STATE];
+        if (seeds) memcpy(seeds, w + PHR_SEEDS, H.n_seeds * sizeof(u32));
+        if (var) {
+            const double* cs = (const double*)(w + H.words) + 2 * c->nphen;
+            for (int k = 0; k < c->nphen * PH_COMP; k++) var[k] = cs[2 * k + 1];
+        }
+        return GEV_OK;
+    }
+}
+int gev_download_phenotypes(gev_ctx* c, int pop, int phen, double* out)
+{
+    GEVC(check_idx(c, pop, 0, phen));
+    if (!out) return fail(GEV_EINVAL, "download_phenotypes: null output");
+    PopState& P = c->pop[pop];
+    if (!P.gen0 || !P.comp_ok) return fail(GEV_ESTATE, "download_phenotypes: population %d has no phenotype components of its current individuals (gev_generation_phenotypes)", pop);
+    HIPC(hipSetDevice(c->device));
+    const size_t n = P.n_people;
+    HIPC(hipMemcpyAsync(out, P.d_comp[P.cbuf].as<double>() + (size_t)phen * PH_COMP * n, PH_COMP * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return GEV_OK;
+}
+int gev_get_ad_gen0(gev_ctx* c, int pop, int phen, double* var_a, double* var_d)
+{
+    GEVC(check_idx(c, pop, 0, phen));
+    PopState& P = c->pop[pop];
+    if (!P.ad0_ok) return fail(GEV_ESTATE, "get_ad_gen0: population %d has no generation-0 variances of A and D", pop);
+    if (var_a) *var_a = P.ad0[2 * phen];
+    if (var_d) *var_d = P.ad0[2 * phen + 1];
+    return GEV_OK;
+}
+int gev_set_ad_gen0(gev_ctx* c, int pop, int phen, double var_a, double var_d)
+{
+    GEVC(check_idx(c, pop, 0, phen));
+    PopState& P = c->pop[pop];
+    if (P.ad0.size() != 2 * (size_t)c->nphen) P.ad0.assign(2 * (size_t)c->nphen, 0.0);
+    P.ad0[2 * phen] = var_a; P.ad0[2 * phen + 1] = var_d;
+    P.ad0_ok = true;
+    return GEV_OK;
+}
+// ras_save_human_info_to_Pop_info_prev_gen (:3211-3236): called where the reference calls it, behind the migration
+int gev_save_prev_gen(gev_ctx* c, int pop, const double* phen_shift)
+{
+    GEVC(check_idx(c, pop, 0));
+    PopState& P = c->pop[pop];
+    if (!P.gen0 || !P.comp_ok) return fail(GEV_ESTATE, "save_prev_gen: population %d has no phenotype components of its current individuals (gev_generation_phenotypes)", pop);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t n = P.n_people;
+    if (phen_shift) GEVC(upload_table(c, c->ph.shift, phen_shift, c->nphen * sizeof(double), st));
+    GEVC(P.d_prev.ensure((size_t)c->nphen * 2 * n * sizeof(double), st));
+    hipLaunchKernelGGL(k_ph_save_prev, dim3((unsigned)ceil_div(n, 256), (unsigned)c->nphen), dim3(256), 0, st, (const double*)P.d_comp[P.cbuf].as<double>(), n,
+                       phen_shift ? (const double*)c->ph.shift.as<double>() : (const double*)nullptr, P.d_prev.as<double>());
+    KCHECK();
+    P.prev_n = n; P.prev_ok = true;
+    return GEV_OK;
+}
+int gev_upload_prev_gen(gev_ctx* c, int pop, const double* phen, const double* parental_effect, size_t n)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (!n) return fail(GEV_EINVAL, "upload_prev_gen: empty record");
+    PopState& P = c->pop[pop];
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIPC(hipStreamSynchronize(st));                         // (a phenotype step that reads the old record may be in flight)
+    const size_t nphen = (size_t)c->nphen;
+    GEVC(P.d_prev.ensure(nphen * 2 * n * sizeof(double), st));
+    HIPC(hipMemsetAsync(P.d_prev.p, 0, nphen * 2 * n * sizeof(double), st));
+    for (size_t p = 0; p < nphen; p++) {
+        if (phen) HIPC(hipMemcpyAsync(P.d_prev.as<double>() + (p * 2 + 0) * n, phen + p * n, n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (parental_effect) HIPC(hipMemcpyAsync(P.d_prev.as<double>() + (p * 2 + 1) * n, parental_effect + p * n, n * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIPC(hipStreamSynchronize(st));
+    P.prev_n = n; P.prev_ok = true;
+    return GEV_OK;
+}
+// test hook: the first attempt of every following gev_generation_phenotypes starts with far too few candidate pairs (on != 0);
+// *reruns = steps that were enqueued again, over the context's life
+int gev_dbg_phenotype_knobs(gev_ctx* c, int short_candidates, unsigned long long* reruns)
+{
+    if (!c) return fail(GEV_EINVAL, "null context");
+    c->ph.short_candidates = short_candidates != 0;
+    if (short_candidates) c->ph.cand_shift = 0;
+    if (reruns) *reruns = c->ph.reruns;
+    return GEV_OK;
+}
+// ---- pedigree ids on the device (gev_pedigree.h) ---------------------------------------------
+int gev_set_track_pedigree(gev_ctx* c, int on)
+{
+    GEVC(check_not_pending(c));
+    if (on != 0 && on != 1) return fail(GEV_EINVAL, "set_track_pedigree: %d is neither 0 nor 1", on);
+    for (const PopState& P : c->pop) if (P.gen0) return fail(GEV_ESTATE, "set_track_pedigree: call it before gev_init_gen0");
+    c->track_pedigree = on != 0;
+    return GEV_OK;
+}
+static int check_pedigree(gev_ctx* c, int pop, const char* who)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (!c->track_pedigree) return fail(GEV_ESTATE, "%s: the context does not track pedigree ids (gev_set_track_pedigree)", who);
+    if (!c->pop[pop].gen0) return fail(GEV_ESTATE, "%s: population %d has no current generation", who, pop);
+    return GEV_OK;
+}
+int gev_download_pedigree(gev_ctx* c, int pop, int64_t* ids)
+{
+    GEVC(check_pedigree(c, pop, "download_pedigree"));
+    if (!ids) return fail(GEV_EINVAL, "download_pedigree: null output");
+    PopState& P = c->pop[pop];
+    if (!P.ids_ok) return fail(GEV_ESTATE, "download_pedigree: population %d's pedigree ids were dropped when its rows changed (gev_upload_pedigree restores them)", pop);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t n = P.n_people;
+    const u32* logical = nullptr;
+    if (!P.logical.empty()) { GEVC(h2d(c, c->d_logical, P.logical.data(), n * sizeof(u32))); logical = c->d_logical.as<u32>(); }
+    GEVC(c->d_tmp.ensure(n * PED_FIELDS * sizeof(int64_t), st));
+    hipLaunchKernelGGL(k_ped_records, dim3((unsigned)ceil_div(n * PED_FIELDS, 256)), dim3(256), 0, st, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf],
+                       logical, n, c->d_tmp.as<int64_t>());
+    KCHECK();
+    HIPC(hipMemcpyAsync(ids, c->d_tmp.p, n * PED_FIELDS * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+int gev_upload_pedigree(gev_ctx* c, int pop, const int64_t* ids)
+{
+    GEVC(check_pedigree(c, pop, "upload_pedigree"));
+    if (!ids) return fail(GEV_EINVAL, "upload_pedigree: null ids");
+    PopState& P = c->pop[pop];
+    HIPC(hipSetDevice(c->device));
+    // planes by physical row (rows no position names any more keep -1)
+    const size_t n = P.n_people, rows = P.logical.empty() ? n : P.n_phys;
+    std::vector<int64_t> planes(PED_FIELDS * rows, -1);
+    for (size_t i = 0; i < n; i++) {
+        const size_t r = P.logical.empty() ? i : P.logical[i];
+        if (r >= rows) return fail(GEV_EDEVICE, "upload_pedigree: position %zu names row %zu of %zu (internal error)", i, r, rows);
+        for (int f = 0; f < PED_FIELDS; f++) planes[f * rows + r] = ids[i * PED_FIELDS + f];
+    }
+    GEVC(h2d(c, P.d_ids[P.ibuf], planes.data(), planes.size() * sizeof(int64_t)));
+    P.ids_stride[P.ibuf] = rows; P.ids_ok = true;
+    return GEV_OK;
+}
 int gev_set_track_intervals(gev_ctx* c, int on)
 {
     if (!c) return fail(GEV_EINVAL, "null");

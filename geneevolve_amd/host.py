@@ -284,6 +284,27 @@ class Pedigree:
         return q
 
 
+def parental_inputs(prev, ids):
+    """what ras_scale_AD_compute_GEF reads for the parental effect of generations > 0 (reference src/Simulation.cpp:3118-3131):
+    f_father[i], f_mother[i] = prev[ID_Father[i]], prev[ID_Mother[i]] with prev = the saved record's phen (vt_type 1) or
+    parental_effect (vt_type 2) of one phenotype (_Pop_info_prev_gen, saved AFTER the migration, :3211-3236).  The reference indexes
+    the saved array BY ID, not by position: after a migration the two differ and it reads whoever sits at that index.  An id at or
+    beyond the array's length is undefined behaviour there (it reads past the end of a std::vector); here it raises.
+    prev: [m] doubles; ids: [n][>= 3] (ID, ID_Father, ID_Mother, ...) or a Pedigree.  -> float64 [n][2]"""
+    prev = np.ascontiguousarray(prev, dtype=np.float64)
+    if isinstance(ids, Pedigree):
+        fa, mo = ids.ID_Father, ids.ID_Mother
+    else:
+        ids = np.asarray(ids)
+        fa, mo = ids[:, 1], ids[:, 2]
+    fa = np.asarray(fa, dtype=np.int64); mo = np.asarray(mo, dtype=np.int64)
+    bad = (fa < 0) | (fa >= len(prev)) | (mo < 0) | (mo >= len(prev))
+    if bad.any():
+        raise IndexError(f"parental_inputs: {int(bad.sum())} of {len(fa)} individuals have a parent id outside the saved record of "
+                         f"{len(prev)} entries (largest id {int(max(fa.max(), mo.max()))}): the reference reads past the end of its array there")
+    return np.stack([prev[fa], prev[mo]], axis=1)
+
+
 def assort_mate(sex, selection_value_func, mating_value, ped, pop_size, mat_cor, seeds, mm_percent=0.0,
                 avoid_inbreeding=False, offspring_dist="p", rank=None):
     """Simulation::assort_mate (reference src/Simulation.cpp:2167-2360).  `seeds` = the ras_glob_seed() values in draw order:
@@ -600,8 +621,13 @@ def ras_save_human_info(ped, sex, per_phen, mating_value, selection_value, selec
 class Simulation:
     """The seam of reference `class Simulation` (src/Simulation.h:64-144) on top of the C-ABI."""
 
-    def __init__(self, ctx, seed, nchr, has_mutation_map, track_pedigree=False):
+    def __init__(self, ctx, seed, nchr, has_mutation_map, track_pedigree=False, device_pedigree=False):
+        """track_pedigree: keep the pedigree ids on the host (self.ped); device_pedigree: the library keeps them
+        (gev_set_track_pedigree) -- avoid_inbreeding then needs no ids from the host, download_pedigree() reads them"""
         self.ctx, self.nchr, self.has_mut, self.track_pedigree = ctx, nchr, has_mutation_map, track_pedigree
+        self.device_pedigree = device_pedigree
+        if device_pedigree:
+            ctx.set_track_pedigree(True)
         self.glob = GlobSeedStream(seed)             # glob_generator.seed(par._seed), :75-76
         self.couples = {}                            # population[ipop]._couples_info
         self.sex = {}
@@ -654,7 +680,7 @@ class Simulation:
         """assort_mate -> reproduce -> ras_compute_AD of sim_next_generation (:1907-1935, without --RM) as one library call pair; all
         ras_glob_seed() draws of the three are made by the library from glob_generator's state, which is stored back"""
         ped = None
-        if avoid_inbreeding:
+        if avoid_inbreeding and not self.device_pedigree:
             P = self.ped[ipop]
             ped = np.stack([P.ID_Father, P.ID_Fathers_Father, P.ID_Fathers_Mother, P.ID_Mothers_Father, P.ID_Mothers_Mother], axis=1)
         self.assort_result = self.ctx.generation_begin_assort(ipop, self.glob.x, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist,
@@ -692,7 +718,7 @@ class Simulation:
         seeds = [int(x) for x in self.ras_glob_seed(4 if offspring_dist in ("p", "P") else 3)]
         self.last_assort_seeds = seeds
         ped = None
-        if avoid_inbreeding:
+        if avoid_inbreeding and not self.device_pedigree:
             P = self.ped[ipop]
             ped = np.stack([P.ID_Father, P.ID_Fathers_Father, P.ID_Fathers_Mother, P.ID_Mothers_Father, P.ID_Mothers_Mother], axis=1)
         if selected:
@@ -740,6 +766,21 @@ class Simulation:
             val = eng.draw(len(c), float(np.sqrt(v))) if v > 0 else np.zeros(len(c))
             out.append(np.repeat(val, rep))
         return out
+
+    def generation_phenotypes(self, ipop, gen_num, schemes, vt_type=1):
+        """ras_scale_AD_compute_GEF of every phenotype (:1938-1946) on the library's side (needs device_pedigree): its ras_glob_seed()
+        draws are made by the library from glob_generator's state; enqueues only.  schemes: (va, vd, vc, ve, vf, beta) per phenotype"""
+        self.ctx.generation_phenotypes(ipop, gen_num, self.glob.x, schemes, vt_type)
+
+    def phenotypes_result(self, ipop):
+        """waits for generation_phenotypes(): stores glob_generator's state back -> dict(glob_state, seeds, var [nphen][7])"""
+        r = self.ctx.phenotypes_result(ipop)
+        self.glob.x = int(r["glob_state"])
+        return r
+
+    def save_prev_gen(self, ipop, phen_shift=None):
+        """ras_save_human_info_to_Pop_info_prev_gen (:3211-3236) on the library's side: call it behind the migration"""
+        self.ctx.save_prev_gen(ipop, phen_shift)
 
     def ras_compute_AD(self, ipop, gen_num=0, per_chr=False):   # :2624
         return self.ctx.compute_ad(ipop, per_chr=per_chr)

@@ -158,7 +158,8 @@ int gev_init_gen0(gev_ctx*, int pop, size_t n_people, uint32_t seed_gen0, uint8_
  *                   ras_add_mutation (:2500), in call order (offspring-major, chromosome-minor)
  *  n_people       : sum of num_offspring over couples with inbreed==0 (checked)
  *  sex_out        : n_people bytes, Human::sex of each offspring (:2472), or NULL
- * Pedigree ids and common_sibling (:2473-2484) are pure host bookkeeping and stay with the host.
+ * common_sibling (:2481-2484) is host bookkeeping and stays with the host; so do the pedigree ids (:2473-2479) unless the context
+ * tracks them (gev_set_track_pedigree).
  *  couples == NULL : the couples the preceding gev_random_mate of `pop` left on the device (n_couples is ignored, n_people must be
  *                   that call's pop_size), or those of the preceding gev_assort_mate (n_people must be its n_offspring).  Returns GEV_ESTATE when the population changed in between (gev_migrate,
  *                   gev_remove_rows, gev_import_rows, or a call that materialised a pending row order): the couples' positions
@@ -312,6 +313,66 @@ int gev_generation_begin_selected(gev_ctx*, int pop, uint32_t glob_state, size_t
 int gev_random_mate_selected(gev_ctx*, int pop, uint32_t seed, size_t pop_size,
                              gev_couple* couples_out, size_t* num_males_mate, size_t* num_females_mate);
 
+/* ---- the ID fields of class Human (src/Population.h:126-137) kept by the library ------------------------------------------------
+ * gev_set_track_pedigree(ctx, 1), before any gev_init_gen0 (GEV_ESTATE after; default 0: nothing below exists and every other call
+ * behaves and costs as without it): per individual the seven ids ID, ID_Father, ID_Mother, ID_Fathers_Father, ID_Fathers_Mother,
+ * ID_Mothers_Father, ID_Mothers_Mother stay on the device.  Generation 0: all = i (:3037-3043).  Every published generation
+ * (gev_reproduce*, gev_generation_*; host couples, random and assortative mating): one kernel beside the generation's small work
+ * gathers the parents' ids through the generation's father / mother rows, ID = i_people (:2473-2479); the host waits for nothing more.
+ * The ids follow the individuals through gev_migrate as the selection values do.  gev_remove_rows / gev_import_rows drop them (the
+ * cross-GPU records do not carry them): gev_upload_pedigree restores them from the host's bookkeeping.
+ *  ids : [n_people][7] in the order above, by position.
+ * With tracking on, gev_assort_mate* / gev_generation_begin_assort* called with avoid_inbreeding and pedigree == NULL run the
+ * sibling / cousin test on these ids (GEV_ESTATE while they are dropped); with tracking off that call stays GEV_EINVAL.
+ * gev_download_pedigree / gev_upload_pedigree: GEV_ESTATE with tracking off or without a current generation; the download also while
+ * the ids are dropped.  Both wait for the device. */
+int gev_set_track_pedigree(gev_ctx*, int on);
+int gev_download_pedigree(gev_ctx*, int pop, int64_t* ids);
+int gev_upload_pedigree(gev_ctx*, int pop, const int64_t* ids);
+
+/* ---- Simulation::ras_scale_AD_compute_GEF (src/Simulation.cpp:3075-3206) for EVERY phenotype of a population's current generation, from
+ * state the library holds: nothing per individual crosses the boundary.  Needs gev_set_track_pedigree (GEV_ESTATE without).
+ * gev_generation_phenotypes enqueues on the library's stream and returns (generation 0 waits once, for _var_a_gen0 / _var_d_gen0,
+ * unless gev_set_ad_gen0 gave them); gev_phenotypes_result waits and reports.  In the reference's order:
+ *  seeds     the ras_glob_seed() values are drawn on the device from glob_state: at gen_num == 0 first one per phenotype with vc > 0
+ *            (:3058), then one per phenotype (:3078).  gev_phenotypes_result returns them in that order and the engine state behind
+ *            them; their count is what the host promises to gev_set_generation_chain.
+ *  C         gen_num > 0: default_random_engine(seed_reproduce + 1) of the generation just published, per phenotype with vc > 0 in
+ *            phenotype order one normal_distribution(0, sqrt(vc)) value per couple of its couples list (inbred couples included), a fresh
+ *            distribution per phenotype on the same engine, handed to every child of the couple (:2417-2429, :2481-2484).  GEV_ESTATE
+ *            when the population's rows changed since the generation was published.  gen_num == 0: n_people values from an engine of
+ *            its own seed per phenotype (:3053-3066).
+ *  E, F0     as gev_scale_ad_compute_gef draws them (seed, seed + 1).
+ *  F         gen_num > 0, vf > 0: beta * (prev[ID_Father] + prev[ID_Mother]), prev = the saved record's phen (vt_type 1) or parental_effect
+ *            (vt_type 2).  The saved arrays are indexed BY ID, not by position, as the reference does (:3118-3131): after a migration
+ *            the two differ.  An id at or beyond the record's length is undefined behaviour in the reference: gev_phenotypes_result
+ *            returns GEV_EUNSUPPORTED and the population's phenotypes count as not computed.  GEV_ESTATE without a saved record.
+ *  scaling   s_a, s_d from the host's sqrt of _var_a_gen0 / va, _var_d_gen0 / vd (A, D, G are one IEEE division of the same inputs as in
+ *            gev_scale_ad_compute_gef); var(e) (two passes, n-1), s_ev and P = A + D + C + E + F on the device.
+ *  var       [nphen][7]: CommFunc::var of A, D, G, C, E, F, P (:2023-2037; what "adjust beta", :648-657, needs of generation 0).
+ * The seven components stay with the population ([7][n_people] per phenotype, gev_download_phenotypes) and follow gev_migrate; phen is
+ * also left where gev_compute_selection reads it.  A normal stream that runs out of candidate pairs (acceptance far below pi/4) is
+ * answered inside gev_phenotypes_result by running the step again with more; selection values computed meanwhile are dropped.
+ * One step is outstanding per context: gev_phenotypes_result (seeds: room for 2 * nphen values) before the next gev_generation_phenotypes.
+ * Floats agree with gev_scale_ad_compute_gef's within 1e-12 relative.  Locus-split contexts: gev_set_ad / gev_ad_finish_device first. */
+typedef struct gev_pheno_scheme { double va, vd, vc, ve, vf, beta; } gev_pheno_scheme;   /* Phenotype_scheme; beta as adjusted by the host */
+typedef struct gev_phenotypes_params { int32_t gen_num, vt_type; const gev_pheno_scheme* scheme; /* [nphen] */ } gev_phenotypes_params;
+int gev_generation_phenotypes(gev_ctx*, int pop, const gev_phenotypes_params*, uint32_t glob_state);
+int gev_phenotypes_result(gev_ctx*, int pop, uint32_t* glob_state_after, uint32_t* seeds, double* var /* [nphen][7] */);   /* each may be NULL */
+int gev_download_phenotypes(gev_ctx*, int pop, int phen, double* out /* [7][n_people]: A D G C E F P */);
+/* Population::_var_a_gen0 / _var_d_gen0 of one phenotype (:557-561): computed by the gen_num == 0 call from the raw A/D (CommFunc::var),
+ * or set by a host that computed generation 0 itself */
+int gev_get_ad_gen0(gev_ctx*, int pop, int phen, double* var_a, double* var_d);
+int gev_set_ad_gen0(gev_ctx*, int pop, int phen, double var_a, double var_d);
+/* ras_save_human_info_to_Pop_info_prev_gen (:3211-3236): device copy of the current individuals' phen (+ phen_shift[p], the --gamma
+ * constant of :3292, or NULL) and parental_effect in position order; call it where the reference does, behind the migration.
+ * gev_upload_prev_gen: the same record from the host, phen / parental_effect = [nphen][n] (either may be NULL = 0). */
+int gev_save_prev_gen(gev_ctx*, int pop, const double* phen_shift);
+int gev_upload_prev_gen(gev_ctx*, int pop, const double* phen, const double* parental_effect, size_t n);
+/* test hook: short_candidates != 0 starts the normal streams of the following gev_generation_phenotypes far too short, so that the step
+ * is run again; *reruns (may be NULL) = steps run again over the context's life */
+int gev_dbg_phenotype_knobs(gev_ctx*, int short_candidates, unsigned long long* reruns);
+
 /* ---- Simulation::assort_mate (src/Simulation.cpp:2167-2360), the reference's default mating mode -------------------------------
  * Forms the couples of the population's current generation on the device, bit for bit as the reference does (stable order among
  * equal mating values, as the host mirror geneevolve_amd/host.py:assort_mate; std::sort leaves it unspecified):
@@ -320,7 +381,8 @@ int gev_random_mate_selected(gev_ctx*, int pop, uint32_t seed, size_t pop_size,
  *  mating_value         : Human::mating_value [n_people] (:2251)
  *  selection_value_func : [n_people] (:2190), or NULL when every value is 1; NaN never passes
  *  pedigree             : [n_people][5] ids (ID_Father, ID_Fathers_Father, ID_Fathers_Mother, ID_Mothers_Father, ID_Mothers_Mother)
- *                         for the sibling / cousin test of avoid_inbreeding (:2306-2322); NULL without it
+ *                         for the sibling / cousin test of avoid_inbreeding (:2306-2322); NULL without it, or to use the ids the
+ *                         library tracks (gev_set_track_pedigree)
  *  couples_out          : res->n_couples records, or NULL (size it from a call with NULL first, or from an upper bound:
  *                         n_couples <= n_people)
  * Second spouses (--MM, :2196-2198), surplus removal by std::random_shuffle on glibc rand() (:2232-2246), the ras_mvnorm rank
@@ -331,7 +393,7 @@ int gev_random_mate_selected(gev_ctx*, int pop, uint32_t seed, size_t pop_size,
  * them (same GEV_ESTATE rule as after gev_random_mate).
  * Errors: GEV_ENOMATE "Error: couples=0, ..." (:2226-2230); GEV_EUNSUPPORTED for a Poisson mean >= 12, for no couple left after
  * the inbred ones, and for avoid_inbreeding with 'f' and a remainder (the reference indexes an empty vector there); GEV_EINVAL for
- * another offspring_dist, a non-finite mat_cor or a NULL pedigree with avoid_inbreeding. */
+ * another offspring_dist, a non-finite mat_cor or a NULL pedigree with avoid_inbreeding on a context that does not track the ids. */
 typedef struct gev_assort_params {
     uint64_t pop_size;          /* --pop_size of the next generation */
     double   mat_cor;           /* mating-value correlation of spouses */
