@@ -95,6 +95,7 @@ ABI_SYMBOLS = [
     "dbg_assort_knobs", "dbg_assort_stats",
     "set_track_pedigree", "download_pedigree", "upload_pedigree",
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
+    "format_info_text", "dbg_format_g", "dbg_format_g_host",
     "dbg_verify_planes", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
@@ -108,6 +109,15 @@ def _p(a, t=None):
 def _arr(a, dtype):
     a = np.ascontiguousarray(a, dtype=dtype)
     return a
+
+
+def _format_g(f, handle, x):
+    x = _arr(x, np.float64).ravel()
+    out = np.zeros((len(x), 16), dtype=np.uint8)
+    n = C.c_ulonglong()
+    args = (_p(x), C.c_size_t(len(x)), _p(out), C.byref(n))
+    rc = f(handle, *args) if handle is not None else f(*args)
+    return rc, out, int(n.value)
 
 
 def words_for(nbits):
@@ -174,6 +184,13 @@ class GevLibrary:
 
     def create(self, n_pop, nchr, nphen, device=-1):
         return GevContext(self, n_pop, nchr, nphen, device)
+
+    def dbg_format_g_host(self, x):
+        """printf %g of every double of x by the library's own formatter compiled for the host (no device needed)
+        -> (uint8 [n][16], NUL padded; values that took the exact path)"""
+        rc, out, n = _format_g(self._f("dbg_format_g_host"), None, x)
+        self.check(rc)
+        return out, n
 
 
 class GevContext:
@@ -457,6 +474,37 @@ class GevContext:
         if ph is not None and pe is not None and ph.shape != pe.shape:
             raise ValueError("upload_prev_gen: phen and parental_effect differ in shape")
         self._call_new("upload_prev_gen", C.c_int(pop), _p(ph), _p(pe), C.c_size_t(n))
+
+    def info_row_bytes(self):
+        """the largest possible row of format_info_text"""
+        return 7 * 21 + 2 + (7 * self.nphen + 3) * 14
+
+    def format_info_text(self, pop, ind_begin=0, n_ind=None, header=True):
+        """bytes of the reference's .info file (Population::ras_save_human_info) for individuals [ind_begin, ind_begin + n_ind) of the
+        current generation, formatted on the device; header: with the header line in front"""
+        if n_ind is None:
+            n_ind = self.pop_size(pop) - ind_begin
+        cap = 128 + 56 * self.nphen + max(int(n_ind), 0) * self.info_row_bytes()
+        buf = getattr(self, "_info_buf", None)
+        if buf is None or len(buf) < cap:                   # kept: a fresh buffer of this size costs more page faults than the copy-out
+            buf = self._info_buf = np.empty(cap, dtype=np.uint8)
+        nb = C.c_size_t()
+        self._call_new("format_info_text", C.c_int(pop), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), _p(buf), C.c_size_t(len(buf)), C.byref(nb))
+        return buf[:nb.value].tobytes()
+
+    def info_text_size(self, pop, ind_begin=0, n_ind=None, header=True):
+        """the exact size format_info_text() would return (length pass only)"""
+        if n_ind is None:
+            n_ind = self.pop_size(pop) - ind_begin
+        nb = C.c_size_t()
+        self._call_new("format_info_text", C.c_int(pop), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), None, C.c_size_t(0), C.byref(nb))
+        return nb.value
+
+    def dbg_format_g(self, x):
+        """printf %g of every double of x on the device -> (uint8 [n][16], NUL padded; values that took the exact path)"""
+        rc, out, n = _format_g(self.L._f("dbg_format_g"), self.h, x)
+        self.L.check(rc)
+        return out, n
 
     def dbg_phenotype_knobs(self, short_candidates=False):
         """-> phenotype steps run again so far; short_candidates: start the following steps' normal streams far too short"""

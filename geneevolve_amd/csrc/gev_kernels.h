@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include "../../include/geneevolve_amd.h"
 #include "rng_device.h"
+#include "gev_fmt_g.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -1932,6 +1933,127 @@ __global__ void __launch_bounds__(256) k_format_bed(const u64* __restrict__ snpm
         o |= code << (2 * i);
     }
     out[q] = (uint8_t)o;
+}
+
+// ------------------------------------------------------------------------------------------
+// Population::ras_save_human_info (src/Population.cpp:510-568): one text row per individual -- the seven ids + 1, sex, per phenotype
+// A D G C E F P, then MV SV SV_f, one space between fields, '\n' at the end; doubles as %g (gev_fmt_g.h).  Rows differ in length:
+// k_info_rows<false> measures them (one thread = one individual: the component planes [7][n] and the id planes are read coalesced),
+// k_info_scan64 turns the block sums into 64-bit byte offsets, k_info_rows<true> formats again into LDS at the rows' offsets inside
+// the block and stores the block's contiguous byte range 16 bytes at a time.
+// ------------------------------------------------------------------------------------------
+#define INFO_ROWS 64                         // rows per block = one wave
+#define INFO_ID_FIELDS 7
+__host__ __device__ inline u32 info_row_cap(u32 nphen) { return INFO_ID_FIELDS * 21u + 2u + (7u * nphen + 3u) * 14u; }      // the longest possible row
+__device__ __forceinline__ u32 info_dec_len(u64 v)
+{
+    u32 n = 1;
+    if (v >> 32) { while (v >= 10) { v /= 10; n++; } return n; }
+    for (u32 w = (u32)v; w >= 10; w /= 10) n++;
+    return n;
+}
+struct InfoRow {                             // cursor of one row in the block's LDS staging area (bytes beyond `cap` are dropped, never written)
+    unsigned char* lds; u32 pos, cap;
+    __device__ __forceinline__ void put(u32 c) { if (pos < cap) lds[pos] = (unsigned char)c; pos++; }
+    __device__ __forceinline__ void dec(u64 v, u32 n)
+    {
+        u32 p = pos + n;
+        if (v >> 32) { do { --p; if (p < cap) lds[p] = (unsigned char)('0' + (u32)(v % 10)); v /= 10; } while (v); }
+        else { u32 w = (u32)v; do { --p; if (p < cap) lds[p] = (unsigned char)('0' + w % 10); w /= 10; } while (w); }
+        pos += n;
+    }
+    __device__ __forceinline__ void g(const GevG& o)
+    {
+        for (u32 k = 0; k < o.len; k++) put((u32)((k < 8 ? o.lo >> (8 * k) : o.hi >> (8 * (k - 8))) & 0xffu));
+    }
+};
+// rows [i0, i0 + cnt) of the population; ids: seven planes `ids_stride` apart, comp: [nphen][7][n], sel: [3][n].
+// WRITE = false: lens[j] = bytes of row i0 + j, bsum[block] = bytes of the block's rows.
+// WRITE = true : boff[block] = offset of the block's first byte in `out` (16-byte aligned base); dynamic LDS: 16 + INFO_ROWS * info_row_cap(nphen)
+template <bool WRITE>
+__global__ void __launch_bounds__(INFO_ROWS) k_info_rows(const GevFmtTables* __restrict__ T, const int64_t* __restrict__ ids, size_t ids_stride, const uint8_t* __restrict__ sex,
+                                                         const double* __restrict__ comp, const double* __restrict__ sel, size_t n, u32 nphen, size_t i0, size_t cnt,
+                                                         u32* __restrict__ lens, u32* __restrict__ bsum, const u64* __restrict__ boff, char* __restrict__ out)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char info_lds[];
+    const u32 lane = threadIdx.x;
+    const size_t j = (size_t)blockIdx.x * INFO_ROWS + lane, i = i0 + j;
+    const bool live = j < cnt;
+    u32 len = 0;
+    InfoRow row{info_lds, 0u, 0u};
+    u64 g0 = 0; u32 a = 0, total = 0;
+    if (WRITE) {
+        len = live ? lens[j] : 0u;
+        u32 inc = len;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const u32 o = __shfl_up(inc, d); if (lane >= (u32)d) inc += o; }
+        total = __shfl(inc, 63);
+        g0 = boff[blockIdx.x]; a = (u32)(g0 & 15u);
+        row.pos = a + inc - len; row.cap = 16u + INFO_ROWS * info_row_cap(nphen);
+    }
+    if (live) {
+        u32 L = 0;
+#pragma unroll
+        for (int f = 0; f < INFO_ID_FIELDS; f++) {
+            const u64 v = (u64)(ids[f * ids_stride + i] + 1);
+            const u32 nd = info_dec_len(v);
+            if (WRITE) { row.dec(v, nd); row.put(' '); }
+            L += nd + 1;
+        }
+        if (WRITE) { row.put('0' + (u32)sex[i]); row.put(' '); }
+        L += 2;
+        const u32 nf = 7u * nphen + 3u;
+        for (u32 f = 0; f < nf; f++) {
+            const double v = f < 7u * nphen ? comp[(size_t)f * n + i] : sel[(size_t)(f - 7u * nphen) * n + i];
+            GevG o;
+            const u32 k = gev_fmt_g(T, v, o, nullptr);
+            if (WRITE) { row.g(o); row.put(f + 1 == nf ? '\n' : ' '); }
+            L += k + 1;
+        }
+        if (!WRITE) len = L;
+    }
+    if (!WRITE) {
+        if (live) lens[j] = len;
+        u32 s = len;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+        if (lane == 0) bsum[blockIdx.x] = s;
+        return;
+    }
+    __syncthreads();
+    // the block's bytes sit at LDS [a, a + total) with a = g0 mod 16: LDS chunk k and the aligned 16 bytes of `out` at g0 - a + 16 k coincide
+    const u32 end = a + total;
+    char* base = out + (g0 - a);
+    for (u32 lo = lane * 16u; lo < end; lo += INFO_ROWS * 16u) {
+        if (lo >= a && lo + 16u <= end) *reinterpret_cast<uint4*>(base + lo) = *reinterpret_cast<const uint4*>(info_lds + lo);
+        else for (u32 b = lo < a ? a : lo; b < lo + 16u && b < end; b++) base[b] = (char)info_lds[b];       // the two ragged ends of the block's range
+    }
+}
+// exclusive scan of the block sums into 64-bit offsets: off[0 .. nb], off[nb] = the total.  One block; the carry is 64 bits wide
+// (k_scan_sums carries 32), a chunk of 256 sums stays below 2^32
+__global__ void __launch_bounds__(256) k_info_scan64(const u32* __restrict__ bsum, size_t nb, u64* __restrict__ off)
+{
+    __shared__ u32 lds[8];
+    u64 carry = 0;
+    for (size_t base = 0; base < nb; base += 256) {
+        const size_t i = base + threadIdx.x;
+        u32 v = i < nb ? bsum[i] : 0, tot;
+        const u32 ex = block_exclusive_scan_256(v, lds, tot);
+        if (i < nb) off[i] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) off[nb] = carry;
+}
+// test hook (gev_dbg_format_g): %g of x[0 .. n), 16 bytes per value
+__global__ void __launch_bounds__(256) k_dbg_format_g(const GevFmtTables* __restrict__ T, const double* __restrict__ x, size_t n, uint4* __restrict__ out,
+                                                      unsigned long long* __restrict__ n_exact)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    GevG o; u32 ex = 0;
+    gev_fmt_g(T, x[i], o, &ex);
+    out[i] = make_uint4((u32)o.lo, (u32)(o.lo >> 32), (u32)o.hi, (u32)(o.hi >> 32));
+    if (ex) atomicAdd(n_exact, 1ull);
 }
 
 #define GEV_LISTS_KERNELS

@@ -284,6 +284,8 @@ struct gev_ctx {
         unsigned long long n_chunks = 0, n_direct = 0, pois_reruns = 0;
     } am;
     DevBuf d_cvdone;
+    // gev_format_info_text / gev_dbg_format_g (gev_fmt_g.h): created by the first call, nothing before it
+    struct FmtState { DevBuf tables, lens, bsum, boff, x, cnt; bool ready = false; } fm;
     // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob
     struct PhenoState {
         DevBuf res /* result words, then {mean, var} pairs: e, the components, raw A and D */, starts, partial, eraw, cval, streams, tasks, blk, globblk, shift;
@@ -4314,6 +4316,108 @@ int gev_upload_pedigree(gev_ctx* c, int pop, const int64_t* ids)
     }
     GEVC(h2d(c, P.d_ids[P.ibuf], planes.data(), planes.size() * sizeof(int64_t)));
     P.ids_stride[P.ibuf] = rows; P.ids_ok = true;
+    return GEV_OK;
+}
+// ---- Population::ras_save_human_info on the device (gev_fmt_g.h, k_info_rows) ------------------
+static int fmt_ready(gev_ctx* c)
+{
+    if (c->fm.ready) return GEV_OK;
+    GEVC(h2d(c, c->fm.tables, &gev_fmt_host_tables(), sizeof(GevFmtTables)));
+    c->fm.ready = true;
+    return GEV_OK;
+}
+int gev_format_info_text(gev_ctx* c, int pop, size_t ind_begin, size_t n_ind, int with_header, char* out, size_t out_bytes, size_t* bytes_written)
+{
+    GEVC(check_idx(c, pop, 0));
+    if (!bytes_written) return fail(GEV_EINVAL, "format_info_text: null bytes_written");
+    *bytes_written = 0;
+    const u32 nphen = (u32)c->nphen;
+    const size_t lds_bytes = 16 + (size_t)INFO_ROWS * info_row_cap(nphen);
+    if (lds_bytes > 65536) return fail(GEV_EUNSUPPORTED, "format_info_text: %u phenotypes: a block of rows is staged in 64 KiB, which holds rows of at most 8", nphen);
+    GEVC(check_pedigree(c, pop, "format_info_text"));
+    PopState& P = c->pop[pop];
+    if (!P.ids_ok) return fail(GEV_ESTATE, "format_info_text: population %d's pedigree ids were dropped when its rows changed (gev_upload_pedigree restores them)", pop);
+    if (!P.comp_ok || !P.logical.empty())
+        return fail(GEV_ESTATE, "format_info_text: population %d has no phenotype components of its current individuals (gev_generation_phenotypes)", pop);
+    if (c->ph.pending && c->ph.pop == pop && c->ph.epoch == P.layout_epoch)
+        return fail(GEV_ESTATE, "format_info_text: the phenotype step of population %d is outstanding: call gev_phenotypes_result first", pop);
+    if (!P.sel_ok) return fail(GEV_ESTATE, "format_info_text: population %d has no selection values of its current generation on the device (gev_compute_selection)", pop);
+    const size_t n = P.n_people;
+    if (ind_begin > n || n_ind > n - ind_begin) return fail(GEV_EINVAL, "format_info_text: individuals [%zu,%zu) beyond n_people=%zu", ind_begin, ind_begin + n_ind, n);
+    std::string hdr;
+    if (with_header) {
+        hdr = "ID ID_Father ID_Mother ID_Fathers_Father ID_Fathers_Mother ID_Mothers_Father ID_Mothers_Mother sex";
+        for (u32 p = 0; p < nphen; p++) for (const char* q = "ADGCEFP"; *q; q++) { hdr += " ph" + std::to_string(p + 1) + "_"; hdr += *q; }
+        hdr += " MV SV SV_f\n";
+    }
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    u64 total = 0;
+    const size_t nb = ceil_div(n_ind, INFO_ROWS);
+    gev_ctx::FmtState& F = c->fm;
+    const int64_t* ids = P.d_ids[P.ibuf].as<int64_t>(); const size_t ids_stride = P.ids_stride[P.ibuf];
+    const uint8_t* sex = P.d_sex[P.cur].as<uint8_t>();
+    const double* comp = P.d_comp[P.cbuf].as<double>(); const double* sel = P.d_sel[P.sbuf].as<double>();
+    if (n_ind) {
+        GEVC(fmt_ready(c));
+        GEVC(F.lens.ensure(n_ind * sizeof(u32), st)); GEVC(F.bsum.ensure(nb * sizeof(u32), st)); GEVC(F.boff.ensure((nb + 1) * sizeof(u64), st));
+        hipLaunchKernelGGL(k_info_rows<false>, dim3((unsigned)nb), dim3(INFO_ROWS), 0, st, (const GevFmtTables*)F.tables.as<GevFmtTables>(), ids, ids_stride, sex, comp, sel, n, nphen,
+                           ind_begin, n_ind, F.lens.as<u32>(), F.bsum.as<u32>(), (const u64*)nullptr, (char*)nullptr);
+        hipLaunchKernelGGL(k_info_scan64, dim3(1), dim3(256), 0, st, (const u32*)F.bsum.as<u32>(), nb, F.boff.as<u64>());
+        KCHECK();
+        HIPC(hipMemcpyAsync(&total, F.boff.as<u64>() + nb, sizeof total, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    const size_t need = hdr.size() + (size_t)total;
+    *bytes_written = need;
+    if (!out) return GEV_OK;
+    if (out_bytes < need) return fail(GEV_EINVAL, "format_info_text: buffer of %zu bytes, %zu needed", out_bytes, need);
+    memcpy(out, hdr.data(), hdr.size());
+    if (!total) return GEV_OK;
+    GEVC(c->d_text.ensure((size_t)total + 16, st));
+    hipLaunchKernelGGL(k_info_rows<true>, dim3((unsigned)nb), dim3(INFO_ROWS), lds_bytes, st, (const GevFmtTables*)F.tables.as<GevFmtTables>(), ids, ids_stride, sex, comp, sel, n, nphen,
+                       ind_begin, n_ind, F.lens.as<u32>(), (u32*)nullptr, (const u64*)F.boff.as<u64>(), c->d_text.as<char>());
+    KCHECK();
+    HIPC(hipMemcpyAsync(out + hdr.size(), c->d_text.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+int gev_dbg_format_g(gev_ctx* c, const double* x, size_t n, char* out, unsigned long long* n_exact)
+{
+    GEVC(check_not_pending(c));
+    if (n && (!x || !out)) return fail(GEV_EINVAL, "dbg_format_g: null argument");
+    if (n_exact) *n_exact = 0;
+    if (!n) return GEV_OK;
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    GEVC(fmt_ready(c));
+    gev_ctx::FmtState& F = c->fm;
+    GEVC(F.x.ensure(n * sizeof(double), st)); GEVC(c->d_text.ensure(n * 16, st)); GEVC(F.cnt.ensure(sizeof(unsigned long long), st));
+    HIPC(hipMemcpyAsync(F.x.p, x, n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPC(hipMemsetAsync(F.cnt.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_dbg_format_g, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const GevFmtTables*)F.tables.as<GevFmtTables>(), (const double*)F.x.as<double>(), n,
+                       c->d_text.as<uint4>(), F.cnt.as<unsigned long long>());
+    KCHECK();
+    unsigned long long cnt = 0;
+    HIPC(hipMemcpyAsync(out, c->d_text.p, n * 16, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&cnt, F.cnt.p, sizeof cnt, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (n_exact) *n_exact = cnt;
+    return GEV_OK;
+}
+// the same header compiled for the host: no device, no context
+int gev_dbg_format_g_host(const double* x, size_t n, char* out, unsigned long long* n_exact)
+{
+    if (n && (!x || !out)) return fail(GEV_EINVAL, "dbg_format_g_host: null argument");
+    const GevFmtTables& T = gev_fmt_host_tables();
+    unsigned long long cnt = 0;
+    for (size_t i = 0; i < n; i++) {
+        GevG o; u32 ex = 0;
+        gev_fmt_g(&T, x[i], o, &ex);
+        memcpy(out + 16 * i, &o.lo, 8); memcpy(out + 16 * i + 8, &o.hi, 8);
+        cnt += ex;
+    }
+    if (n_exact) *n_exact = cnt;
     return GEV_OK;
 }
 int gev_set_track_intervals(gev_ctx* c, int on)

@@ -782,6 +782,15 @@ class Simulation:
         """ras_save_human_info_to_Pop_info_prev_gen (:3211-3236) on the library's side: call it behind the migration"""
         self.ctx.save_prev_gen(ipop, phen_shift)
 
+    def save_human_info(self, ipop, path=None):
+        """Population::ras_save_human_info (src/Population.cpp:510-568) formatted by the library on the device (needs device_pedigree,
+        the generation's phenotypes_result() and compute_selection()) -> the file's bytes, written to `path` in one piece when given"""
+        txt = self.ctx.format_info_text(ipop)
+        if path is not None:
+            with open(path, "wb") as f:
+                f.write(txt)
+        return txt
+
     def ras_compute_AD(self, ipop, gen_num=0, per_chr=False):   # :2624
         return self.ctx.compute_ad(ipop, per_chr=per_chr)
 

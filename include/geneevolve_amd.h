@@ -373,6 +373,25 @@ int gev_upload_prev_gen(gev_ctx*, int pop, const double* phen, const double* par
  * is run again; *reruns (may be NULL) = steps run again over the context's life */
 int gev_dbg_phenotype_knobs(gev_ctx*, int short_candidates, unsigned long long* reruns);
 
+/* ---- the per-generation .info text on the device ----
+ * Population::ras_save_human_info (src/Population.cpp:510-568): the file's bytes for individuals [ind_begin, ind_begin + n_ind) of the
+ * population's current generation; with_header != 0 puts the header line in front.  out == NULL: only *bytes_written = exact size.
+ * out_bytes too small: GEV_EINVAL, *bytes_written = size needed.  Waits for the device.
+ * A row holds the seven ids + 1, sex, per phenotype A D G C E F P, then MV SV SV_f, separated by one space and closed by a newline;
+ * every double as printf %g prints it (6 significant digits of the exact binary value, half to even; -nan for a NaN with the sign set).
+ * Rows are in position order (the order of the pedigree, phenotype and selection downloads).  The largest possible row has
+ * 7*21 + 2 + (7*nphen + 3)*14 bytes, so n_ind times that (plus the header: under 128 + 56*nphen bytes) always suffices.
+ * Needs pedigree tracking with the ids present, every phenotype of the current generation formed by the device's phenotype step with
+ * its result taken, and selection values on the device: GEV_ESTATE otherwise, the message names what is missing.  A range beyond
+ * n_people: GEV_EINVAL.  n_ind == 0: the header alone, or nothing.  The tables and buffers it uses are created by the first call.
+ * At most 8 phenotypes: a block of 64 rows is staged in 16 + 64 * (largest row) bytes of on-chip memory, which must fit 64 KiB
+ * (GEV_EUNSUPPORTED beyond). */
+int gev_format_info_text(gev_ctx*, int pop, size_t ind_begin, size_t n_ind, int with_header,
+                         char* out, size_t out_bytes, size_t* bytes_written);
+/* test hooks: %g of n doubles, 16 bytes per value, NUL padded; *n_exact (may be NULL) = values that took the exact path */
+int gev_dbg_format_g(gev_ctx*, const double* x, size_t n, char* out, unsigned long long* n_exact);   /* on the device */
+int gev_dbg_format_g_host(const double* x, size_t n, char* out, unsigned long long* n_exact);        /* same header, host build, no device */
+
 /* ---- Simulation::assort_mate (src/Simulation.cpp:2167-2360), the reference's default mating mode -------------------------------
  * Forms the couples of the population's current generation on the device, bit for bit as the reference does (stable order among
  * equal mating values, as the host mirror geneevolve_amd/host.py:assort_mate; std::sort leaves it unspecified):

@@ -12,12 +12,22 @@ Both mate on the device's selection values (gev_compute_selection, enqueued only
 context and the same inputs, and take turns: --warmup generations each, then --repeats windows of --steps generations per mode,
 alternating, every window closed by gev_sync.  Generation 0's variances of A and D are the host's (comm_var) in both modes, so the two
 runs differ only by the rounding of parallel sums: the couples of one further generation are hashed per mode (equal hashes = the same
-run) and the largest relative difference of the final phenotypes is reported."""
+run) and the largest relative difference of the final phenotypes is reported.
+
+--info host|device: the device mode alone, producing the generation's .info text (Population::ras_save_human_info: the one file the
+reference writes every generation) behind every phenotype step, two ways:
+  host   : the pedigree, components and selection values are downloaded and formatted by C snprintf on up to 8 threads
+           (tools/info_format_host.cpp, what the bound command-line program does)
+  device : gev_format_info_text
+Windows without and with the file's write (one write per generation, to a temporary directory) alternate; the texts of one further
+generation are hashed.  --info none (the default) is the comparison described above, unchanged."""
 import argparse
+import ctypes
 import hashlib
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,6 +109,39 @@ class Run:
         self.prev = [o["phen"] for o in outs]
         self.last = outs
 
+    # ---- --info: the generation's .info text
+    info_mode, info_path, t_info, n_info, last_text = None, None, 0.0, 0, b""
+
+    def info_text(self):
+        ctx = self.ctx
+        if self.info_mode == "device":
+            return ctx.format_info_text(0)
+        n = ctx.pop_size(0)
+        ids = ctx.download_pedigree(0)
+        comps = [ctx.download_phenotypes(0, p) for p in range(2)]
+        sel = ctx.download_selection(0)
+        cols = [np.ascontiguousarray(c[k]) for c in comps for k in ("additive", "dominance", "bv", "common_sibling", "e_noise", "parental_effect", "phen")]
+        cols += [sel["mating_value"], sel["selection_value"], sel["selection_value_func"]]
+        ptrs = (ctypes.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+        if getattr(self, "_fmt", None) is None:
+            self._fmt = ctypes.CDLL(os.path.join(ROOT, "tools", "libinfo_format_host.so")).info_format_host
+            self._buf = np.empty(n * ctx.info_row_bytes() * 2, dtype=np.uint8)
+            self._hdr = ctx.format_info_text(0, 0, 0)
+        nb = ctypes.c_size_t()
+        sex = np.ascontiguousarray(self.sim.sex[0])
+        rc = self._fmt(ctypes.c_void_p(ids.ctypes.data), ctypes.c_void_p(sex.ctypes.data), ptrs, ctypes.c_int(len(cols)), ctypes.c_size_t(n), ctypes.c_int(8),
+                       ctypes.c_void_p(self._buf.ctypes.data), ctypes.c_size_t(len(self._buf)), ctypes.byref(nb))
+        assert rc == 0
+        return self._hdr + self._buf[:nb.value].tobytes()
+
+    def info_step(self):
+        t0 = time.perf_counter()
+        self.last_text = self.info_text()
+        if self.info_path:
+            with open(self.info_path, "wb") as f:
+                f.write(self.last_text)
+        self.t_info += time.perf_counter() - t0; self.n_info += 1
+
     def generation(self, want_couples=False):
         a, sim = self.args, self.sim
         self.g += 1
@@ -110,6 +153,8 @@ class Run:
             sim.next_generation_am_selected(0, a.n_ind, 0.3, 0.1, True, "p", want_couples=want)
         self.t_generation_calls += time.perf_counter() - t0
         self.phenotypes()
+        if self.info_mode:
+            self.info_step()
 
     def window(self, steps):
         t0 = time.perf_counter()
@@ -142,7 +187,10 @@ def main():
     ap.add_argument("--n-cv", type=int, default=1000)
     ap.add_argument("--mating", choices=["rm", "am"], default="rm")
     ap.add_argument("--no-chain", action="store_true", help="no head start across generations (random mating)")
+    ap.add_argument("--info", choices=["none", "host", "device"], default="none", help="also produce every generation's .info text, on the host or on the device")
     args = ap.parse_args()
+    if args.info != "none":
+        return main_info(args)
     out = {"tool": "phenotype_loop_bench", "n_ind": args.n_ind, "n_loci": args.n_loci, "nphen": 2, "mating": args.mating,
            "avoid_inbreeding": args.mating == "am", "selection_function": "logit 1 1", "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats}
     runs = {m: Run(m, args) for m in ("host", "device")}
@@ -174,6 +222,33 @@ def main():
     out["device_over_host"] = round(float(np.mean(out["device"]["generations_per_s"]) / np.mean(out["host"]["generations_per_s"])), 3)
     for r in runs.values():
         r.ctx.close()
+    print(json.dumps(out))
+
+
+def main_info(args):
+    out = {"tool": "phenotype_loop_bench", "info": args.info, "n_ind": args.n_ind, "n_loci": args.n_loci, "nphen": 2, "mating": args.mating,
+           "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats}
+    r = Run("device", args)
+    r.info_mode = args.info
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "info.pop1.txt")
+        r.window(args.warmup)
+        secs = {"write_excluded": [], "write_included": []}
+        info_ms = {"write_excluded": [], "write_included": []}
+        for _ in range(args.repeats):
+            for key, p in (("write_excluded", None), ("write_included", path)):
+                r.info_path, r.t_info, r.n_info = p, 0.0, 0
+                secs[key].append(r.window(args.steps))
+                info_ms[key].append(round(r.t_info / r.n_info * 1e3, 3))
+        r.info_path = None
+        r.generation()
+    for key in secs:
+        out[key] = {"generations_per_s": [round(args.steps / s, 2) for s in secs[key]], "ms_per_generation": [round(s / args.steps * 1e3, 3) for s in secs[key]],
+                    "info_ms_per_generation": info_ms[key]}
+    out["text_bytes"] = len(r.last_text)
+    out["text_sha256"] = hashlib.sha256(r.last_text).hexdigest()[:16]
+    out["glob_state_after"] = int(r.sim.glob.x)
+    r.ctx.close()
     print(json.dumps(out))
 
 
