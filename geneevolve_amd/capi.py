@@ -96,7 +96,7 @@ ABI_SYMBOLS = [
     "set_track_pedigree", "download_pedigree", "upload_pedigree",
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "format_info_text", "dbg_format_g", "dbg_format_g_host",
-    "dbg_verify_planes", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
+    "dbg_verify_planes", "dbg_output_chunk", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
 
@@ -122,6 +122,14 @@ def _format_g(f, handle, x):
 
 def words_for(nbits):
     return (int(nbits) + 63) // 64
+
+
+def _rows_out(n_rows, words, stride_words=None):
+    """output matrix of `words` words per row; with a wider stride_words it starts as 0xFF bytes, so that what the library wrote shows"""
+    if stride_words is None:
+        return np.zeros((n_rows, words), dtype=np.uint64)
+    assert stride_words >= words
+    return np.full((n_rows, stride_words), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
 
 
 def pack_rows(bits01):
@@ -644,21 +652,23 @@ class GevContext:
         self._call("pop_size", C.c_int(pop), C.byref(n))
         return n.value
 
-    def download_haps(self, pop, chr, row_begin=0, n_rows=None):
+    def dbg_output_chunk(self, max_units=0):
+        """test hook: the following output calls stage at most max_units rows / individuals / SNPs (SNPs in 64s) per pass; 0 = byte budgets"""
+        self._call_new("dbg_output_chunk", C.c_size_t(max_units))
+
+    def download_haps(self, pop, chr, row_begin=0, n_rows=None, stride_words=None):
         L = self._nsnp[(pop, chr)]
         if n_rows is None:
             n_rows = 2 * self.pop_size(pop) - row_begin
-        w = words_for(L)
-        out = np.zeros((n_rows, w), dtype=np.uint64)
-        self._call("download_haps", C.c_int(pop), C.c_int(chr), C.c_size_t(row_begin), C.c_size_t(n_rows), _p(out), C.c_size_t(w))
+        out = _rows_out(n_rows, words_for(L), stride_words)
+        self._call("download_haps", C.c_int(pop), C.c_int(chr), C.c_size_t(row_begin), C.c_size_t(n_rows), _p(out), C.c_size_t(out.shape[1]))
         return out
 
-    def download_snp_major(self, pop, chr, snp_begin=0, n_snps=None):
+    def download_snp_major(self, pop, chr, snp_begin=0, n_snps=None, stride_words=None):
         L = self._nsnp[(pop, chr)]
         n_snps = L - snp_begin if n_snps is None else n_snps
-        w = words_for(2 * self.pop_size(pop))
-        out = np.zeros((n_snps, w), dtype=np.uint64)
-        self._call("download_snp_major", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(w))
+        out = _rows_out(n_snps, words_for(2 * self.pop_size(pop)), stride_words)
+        self._call("download_snp_major", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(out.shape[1]))
         return out
 
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
@@ -694,13 +704,12 @@ class GevContext:
         self._call("rank_f64", _p(x), C.c_size_t(len(x)), _p(out))
         return out
 
-    def download_plink_matrix(self, pop, chr, ind_begin=0, n_ind=None):
+    def download_plink_matrix(self, pop, chr, ind_begin=0, n_ind=None, stride_words=None):
         """matrix_plink_ped rows (bit 2*snp + hap) of ras_convert_interval_to_format_plink"""
         L = self._nsnp[(pop, chr)]
         n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
-        w = words_for(2 * L)
-        out = np.zeros((n_ind, w), dtype=np.uint64)
-        self._call("download_plink_matrix", C.c_int(pop), C.c_int(chr), C.c_size_t(ind_begin), C.c_size_t(n_ind), _p(out), C.c_size_t(w))
+        out = _rows_out(n_ind, words_for(2 * L), stride_words)
+        self._call("download_plink_matrix", C.c_int(pop), C.c_int(chr), C.c_size_t(ind_begin), C.c_size_t(n_ind), _p(out), C.c_size_t(out.shape[1]))
         return out
 
     def format_ped_text(self, pop, chr, al0=None, al1=None, ind_begin=0, n_ind=None):
@@ -779,16 +788,15 @@ class GevContext:
     def set_dense_state(self, on):
         self._call("set_dense_state", C.c_int(1 if on else 0))
 
-    def materialize(self, pop, chr, founder_tile, row_begin=0, n_rows=None, snp_begin=0, n_snps=None):
+    def materialize(self, pop, chr, founder_tile, row_begin=0, n_rows=None, snp_begin=0, n_snps=None, stride_words=None):
         """genotype tile from the interval state; founder_tile: uint64 [n_founder_haps][words] holding SNPs [snp_begin, +n_snps)"""
         L = self._nsnp[(pop, chr)]
         n_snps = L - snp_begin if n_snps is None else n_snps
         n_rows = 2 * self.pop_size(pop) - row_begin if n_rows is None else n_rows
         ft = np.ascontiguousarray(founder_tile, dtype=np.uint64)
-        w = words_for(n_snps)
-        out = np.zeros((n_rows, w), dtype=np.uint64)
+        out = _rows_out(n_rows, words_for(n_snps), stride_words)
         self._call("materialize", C.c_int(pop), C.c_int(chr), C.c_size_t(row_begin), C.c_size_t(n_rows), C.c_size_t(snp_begin), C.c_size_t(n_snps),
-                   _p(ft), C.c_size_t(ft.shape[1]), C.c_size_t(ft.shape[0]), _p(out), C.c_size_t(w))
+                   _p(ft), C.c_size_t(ft.shape[1]), C.c_size_t(ft.shape[0]), _p(out), C.c_size_t(out.shape[1]))
         return out
 
     def materialize_pops(self, pop, chr, founder_tiles, row_begin=0, n_rows=None, snp_begin=0, n_snps=None):

@@ -1476,41 +1476,6 @@ __global__ void __launch_bounds__(256) k_snp_apply_mut(
         }
     }
 }
-// K8: genotype tile from the ancestry intervals == Simulation::ras_convert_interval_to_hap_matrix (src/Simulation.cpp:1186-1230)
-// restricted to haplotype rows [row0, row0+n_rows) x loci [s0, s0+ns): out[r][ii] = founder[part.hap_index][ii] for the part
-// that contains pos[ii]; loci outside every part stay 0.  One thread per 32-bit word of the tile; the parts of a row are
-// disjoint and ascending, so the first candidate is found by bisection on `en` and usually covers the whole word.
-// `founder` holds the same loci range of every founder haplotype (bit j = locus s0 + j).  Mutations: k_tile_apply_mut.
-__global__ void __launch_bounds__(256) k_materialize_tile(const u32* __restrict__ p_off, const gev_part* __restrict__ parts, size_t row0, size_t n_rows,
-                                                          const u64* __restrict__ pos, u32 s0, u32 ns, const u32* __restrict__ founder, size_t founder_w32,
-                                                          const u64* __restrict__ founder_row0 /* [n_pop+1]: rows of root population p are [row0[p], row0[p+1]) of `founder` */,
-                                                          int n_pop, u32* __restrict__ out, size_t out_w32, u32* __restrict__ status)
-{
-    const u32 words = (ns + 31) / 32;
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_rows * words) return;
-    const size_t r = q / words; const u32 w = (u32)(q % words);
-    const u32 nb = min(32u, ns - 32u * w);
-    const u64* wp = pos + s0 + 32u * w;                       // positions of this word's loci
-    const u64 x0 = wp[0], x1 = wp[nb - 1];
-    u32 lo = p_off[row0 + r], hi = p_off[row0 + r + 1];
-    const u32 end = hi;
-    while (lo < hi) { const u32 m = (lo + hi) >> 1; if (parts[m].en <= x0) lo = m + 1; else hi = m; }    // first part with en > x0
-    u32 acc = 0;
-    for (u32 i = lo; i < end && parts[i].st <= x1; i++) {
-        const u64 st = parts[i].st, en = parts[i].en;
-        u32 a = 0, b = 0;
-        for (u32 t = 0; t < nb; t++) { a += wp[t] < st ? 1u : 0u; b += wp[t] < en ? 1u : 0u; }        // loci [a, b) lie in [st, en)
-        if (b > a) {
-            const u32 mask = (b - a == 32u) ? 0xffffffffu : (((1u << (b - a)) - 1u) << a);
-            const u64 h = parts[i].hap_index;
-            const int rp = parts[i].root_population;                                                  // founder panel of the part's ROOT population (:1204)
-            if (rp < 0 || rp >= n_pop || h >= founder_row0[rp + 1] - founder_row0[rp]) { atomicOr(status, 1u); continue; }   // :1205-1209 "hap_index is not in range"
-            acc |= founder[(founder_row0[rp] + h) * founder_w32 + w] & mask;
-        }
-    }
-    out[r * out_w32 + w] = acc;
-}
 // Diagnostic (gev_dbg_verify_planes): EVERY 32-bit word of the resident genotype plane (written by the dense stitch K5 from
 // breakpoints) against the reference's materialisation rule applied to the ancestry intervals (written by K4, k_parts) --
 // two independent paths.  The founder panel is the synthetic one (k_synth_rows), recomputed on the fly, so no founder copy
@@ -1548,22 +1513,6 @@ __global__ void __launch_bounds__(256) k_verify_plane(const u32* __restrict__ p_
         }
     }
     if (acc != rm.word32(r, w)) atomicAdd(&n_bad[0], 1ull);
-}
-// mutation overlay of a tile: out bit = !unmutated bit at every tile locus whose position is in the row's mutation list (:1212-1216)
-__global__ void __launch_bounds__(256) k_tile_apply_mut(const u32* __restrict__ plain, u32* __restrict__ out, size_t w32, size_t row0, size_t n_rows,
-                                                        const u32* __restrict__ m_off, const u64* __restrict__ m_pos, const u64* __restrict__ pos, u32 s0, u32 ns)
-{
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
-    const u32* in = plain + r * w32; u32* o = out + r * w32;
-    for (u32 j = m_off[row0 + r]; j < m_off[row0 + r + 1]; j++) {
-        const u64 x = m_pos[j];
-        u32 c = lower_bound_u64(pos + s0, ns, x);
-        for (; c < ns && pos[s0 + c] == x; c++) {
-            const u32 f = (in[c >> 5] >> (c & 31)) & 1u;
-            if (f) o[c >> 5] &= ~(1u << (c & 31)); else o[c >> 5] |= (1u << (c & 31));
-        }
-    }
 }
 // generic row gather (migration, capacity growth, download staging): dst row r <- src row map[r]
 __global__ void __launch_bounds__(256) k_gather_rows16(uint4* __restrict__ dst, size_t dst_stride16, const uint4* __restrict__ src, size_t src_stride16,
@@ -1768,171 +1717,6 @@ __global__ void __launch_bounds__(256) k_par_eff(const double* __restrict__ ff, 
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = beta * ((ff ? ff[i] : 0.0) + (fm ? fm[i] : 0.0));
-}
-
-// ------------------------------------------------------------------------------------------
-// K9: output packing.  The reference's .hap files are SNP-major text
-// (format_hap::write_hap, src/format_hap.cpp:6-30); PLINK .bed is SNP-major 2-bit.  The resident
-// plane is haplotype-major, so output = 64x64 bit-tile transposes (64 ballots per tile: lane b ends
-// up with SNP 64*sw+b across 64 haplotypes), then the sparse mutation overlay, then formatting.
-// ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_transpose_tiles(const u64* __restrict__ plane /* flat rows, or null: */, RowMap rm /* segment pool */, size_t stride_w64, size_t n_rows, u32 L,
-                                                         u32 snp_begin, u32 n_snps, u64* __restrict__ out, size_t out_stride_w64, u32 words_per_wave)
-{
-    const u32 lane = threadIdx.x & 63;
-    const size_t hb = (size_t)blockIdx.x;                                   // block of 64 haplotype rows
-    const u32 wave = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const u32 sw_first = snp_begin >> 6, sw_last = (snp_begin + n_snps - 1) >> 6;
-    const u32 sw0 = sw_first + wave * words_per_wave;
-    const size_t row = hb * 64 + lane;
-    for (u32 sw = sw0; sw < sw0 + words_per_wave && sw <= sw_last; sw++) {
-        const u64 v = row < n_rows ? (plane ? plane[row * stride_w64 + sw] : rm.word64(row, sw)) : 0ull;
-        u64 mine = 0;
-#pragma unroll 8
-        for (u32 b = 0; b < 64; b++) {
-            const u64 m = __ballot((v >> b) & 1ull);
-            if (lane == b) mine = m;
-        }
-        const u32 snp = sw * 64 + lane;
-        if (snp >= snp_begin && snp < snp_begin + n_snps && snp < L) out[(size_t)(snp - snp_begin) * out_stride_w64 + hb] = mine;
-    }
-}
-// flip (snp, hap) where the SNP position is in the haplotype's mutation set: value = !founder (idempotent)
-__global__ void __launch_bounds__(256) k_snpmajor_apply_mut(RowMap rm, size_t n_rows,
-                                                            const u32* __restrict__ m_off, const u64* __restrict__ m_pos, const u64* __restrict__ pos, u32 L,
-                                                            u32 snp_begin, u32 n_snps, unsigned long long* __restrict__ out, size_t out_stride_w64)
-{
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
-    for (u32 j = m_off[r]; j < m_off[r + 1]; j++) {
-        const u64 x = m_pos[j];
-        u32 c = lower_bound_u64(pos, L, x);
-        for (; c < L && pos[c] == x; c++) {
-            if (c < snp_begin || c >= snp_begin + n_snps) continue;
-            const u32 f = (rm.word32(r, c >> 5) >> (c & 31)) & 1u;
-            unsigned long long* w = out + (size_t)(c - snp_begin) * out_stride_w64 + (r >> 6);
-            const unsigned long long bit = 1ull << (r & 63);
-            if (f) atomicAnd(w, ~bit); else atomicOr(w, bit);
-        }
-    }
-}
-// one .hap line per SNP: "b b b ... b \n" (digit + space per haplotype, then newline)
-// The text is produced as a flat byte stream: thread t owns the aligned 16 bytes [16t, 16t+16) of the output (lines have odd
-// lengths, so line-relative ownership would make every store misaligned), one 16-byte store per thread.
-__global__ void __launch_bounds__(256) k_format_hap_text(const u64* __restrict__ snpmajor, size_t stride_w64, size_t n_rows, u32 n_snps, char* __restrict__ out)
-{
-    const size_t line_len = 2 * n_rows + 1, total = (size_t)n_snps * line_len;
-    const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (o >= total) return;
-    size_t j = o / line_len, p = o % line_len;
-    union { char ch[16]; uint4 v; } u;
-    u64 word = 0; size_t word_at = ~(size_t)0;
-#pragma unroll
-    for (int b = 0; b < 16; b++) {
-        char ch = ' ';
-        if (o + b >= total) ch = 0;
-        else if (p == 2 * n_rows) ch = '\n';
-        else if (!(p & 1)) {
-            const size_t h = p >> 1, at = j * stride_w64 + (h >> 6);
-            if (at != word_at) { word = snpmajor[at]; word_at = at; }
-            ch = (char)('0' + (int)((word >> (h & 63)) & 1ull));
-        }
-        u.ch[b] = ch;
-        if (++p == line_len) { p = 0; j++; }
-    }
-    if (o + 16 <= total) *reinterpret_cast<uint4*>(out + o) = u.v;
-    else for (int b = 0; b < 16 && o + b < total; b++) out[o + b] = u.ch[b];
-}
-// VCF genotype columns of one data line (format_vcf::write_vcf_file, src/format_vcf.cpp:55-59): per individual "\ta|b"
-// (a, b = haplotype rows 2i, 2i+1 at this SNP), then '\n'; flat-stream layout as above
-__global__ void __launch_bounds__(256) k_format_vcf_gt(const u64* __restrict__ snpmajor, size_t stride_w64, size_t n_ind, u32 n_snps, char* __restrict__ out)
-{
-    const size_t line_len = 4 * n_ind + 1, total = (size_t)n_snps * line_len;
-    const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (o >= total) return;
-    size_t j = o / line_len, p = o % line_len;
-    union { char ch[16]; uint4 v; } u;
-    u64 word = 0; size_t word_at = ~(size_t)0;
-#pragma unroll
-    for (int b = 0; b < 16; b++) {
-        char ch;
-        if (o + b >= total) ch = 0;
-        else if (p == 4 * n_ind) ch = '\n';
-        else if ((p & 3) == 0) ch = '\t';
-        else if ((p & 3) == 2) ch = '|';
-        else {
-            const size_t h = p >> 1, at = j * stride_w64 + (h >> 6);      // p = 4i+1 -> row 2i, p = 4i+3 -> row 2i+1
-            if (at != word_at) { word = snpmajor[at]; word_at = at; }
-            ch = (char)('0' + (int)((word >> (h & 63)) & 1ull));
-        }
-        u.ch[b] = ch;
-        if (++p == line_len) { p = 0; j++; }
-    }
-    if (o + 16 <= total) *reinterpret_cast<uint4*>(out + o) = u.v;
-    else for (int b = 0; b < 16 && o + b < total; b++) out[o + b] = u.ch[b];
-}
-// PLINK .ped genotype columns (format_plink::write_ped_map / write_ped01_map, src/format_plink.cpp:42-49 / :114-121):
-// per individual  L x " a b"  then '\n', a/b = allele letters of haplotype 0/1 (al1 if the bit is set else al0; "1"/"0"
-// when al0 == NULL).  `rows` = staged hap-major rows (mutations applied) of individuals [0, n_ind); same flat-stream layout.
-__global__ void __launch_bounds__(256) k_format_ped_text(const u32* __restrict__ rows, size_t stride_w32, size_t n_ind, u32 L,
-                                                         const char* __restrict__ al0, const char* __restrict__ al1, char* __restrict__ out)
-{
-    const size_t line_len = 4 * (size_t)L + 1, total = n_ind * line_len;
-    const size_t o = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (o >= total) return;
-    size_t i = o / line_len, p = o % line_len;
-    union { char ch[16]; uint4 v; } u;
-    u32 w0 = 0, w1 = 0; size_t word_at = ~(size_t)0;
-#pragma unroll
-    for (int b = 0; b < 16; b++) {
-        char ch = ' ';
-        if (o + b >= total) ch = 0;
-        else if (p == 4 * (size_t)L) ch = '\n';
-        else if (p & 1) {
-            const u32 s = (u32)(p >> 2), hap = (u32)(p >> 1) & 1u;
-            const size_t at = 2 * i * stride_w32 + (s >> 5);
-            if (at != word_at) { w0 = rows[at]; w1 = rows[at + stride_w32]; word_at = at; }
-            const u32 bit = ((hap ? w1 : w0) >> (s & 31)) & 1u;
-            ch = al0 ? (bit ? al1[s] : al0[s]) : (char)('0' + bit);
-        }
-        u.ch[b] = ch;
-        if (++p == line_len) { p = 0; i++; }
-    }
-    if (o + 16 <= total) *reinterpret_cast<uint4*>(out + o) = u.v;
-    else for (int b = 0; b < 16 && o + b < total; b++) out[o + b] = u.ch[b];
-}
-// matrix_plink_ped of ras_convert_interval_to_format_plink (src/Simulation.cpp:1308-1362): bit 2*ii+ihap of row ih
-__device__ __forceinline__ u64 spread_bits(u32 x)
-{
-    u64 v = x;
-    v = (v | (v << 16)) & 0x0000ffff0000ffffull; v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
-    v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;  v = (v | (v << 2)) & 0x3333333333333333ull;
-    v = (v | (v << 1)) & 0x5555555555555555ull;
-    return v;
-}
-__global__ void __launch_bounds__(256) k_interleave_haps(const u32* __restrict__ rows, size_t stride_w32, size_t n_ind, u32 words, u64* __restrict__ out, size_t out_stride_w64)
-{
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_ind * words) return;
-    const size_t i = q / words, w = q % words;
-    out[i * out_stride_w64 + w] = spread_bits(rows[2 * i * stride_w32 + w]) | (spread_bits(rows[(2 * i + 1) * stride_w32 + w]) << 1);
-}
-// PLINK .bed body, SNP-major: 2 bits per individual, A1 = allele 1: 00 = 1/1, 10 = heterozygous, 11 = 0/0, pad = 00
-__global__ void __launch_bounds__(256) k_format_bed(const u64* __restrict__ snpmajor, size_t stride_w64, size_t n_people, u32 n_snps, uint8_t* __restrict__ out)
-{
-    const size_t bpl = (n_people + 3) / 4;
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (size_t)n_snps * bpl) return;
-    const size_t j = q / bpl, by = q % bpl;
-    const u32 bits = (u32)((snpmajor[j * stride_w64 + (by >> 3)] >> ((by & 7) * 8)) & 0xffull);     // haplotypes 8*by .. 8*by+7
-    u32 o = 0;
-    for (u32 i = 0; i < 4; i++) {
-        if (by * 4 + i >= n_people) break;
-        const u32 b0 = (bits >> (2 * i)) & 1u, b1 = (bits >> (2 * i + 1)) & 1u;
-        const u32 code = (b0 & b1) ? 0u : ((b0 ^ b1) ? 2u : 3u);
-        o |= code << (2 * i);
-    }
-    out[q] = (uint8_t)o;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "gev_kernels.h"
+#include "gev_outputs.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -272,6 +273,7 @@ struct gev_ctx {
                           bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0;
                           int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
     DevBuf d_snpmajor, d_text;
+    size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
     // gev_assort_mate (gev_assort.h): scratch, the last call's result and couple arrays, test knobs
@@ -2054,6 +2056,28 @@ static int am_sort(gev_ctx* c, hipStream_t st, const double* x, const u32* gathe
     if (e) return fail(GEV_EDEVICE, "assort_mate: device sort failed: %s", hipGetErrorString((hipError_t)e));
     return GEV_OK;
 }
+// CommFunc::ras_rank on the device (the O(n^2) host loop of assort_mate, src/Simulation.cpp:2278-2279): stable radix sort of
+// order-preserving keys with the reference's tie / NaN rule (gev_sort.hip)
+extern "C" size_t gev_rank_scratch_bytes(size_t n);
+extern "C" int gev_rank_device(const double* d_x, size_t n, unsigned long long* d_rank, void* d_tmp, hipStream_t st);
+int gev_rank_f64(gev_ctx* c, const double* x, size_t n, unsigned long long* rank_out)
+{
+    if (!c) return fail(GEV_EINVAL, "null context");
+    if (n && (!x || !rank_out)) return fail(GEV_EINVAL, "rank_f64: null buffer");
+    if (!n) return GEV_OK;
+    if (n >= 0xffffffffull) return fail(GEV_EINVAL, "rank_f64: too many values");
+    HIPC(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    GEVC(c->d_tmp.ensure(n * 16, st));
+    double* dx = c->d_tmp.as<double>(); unsigned long long* dr = (unsigned long long*)(dx + n);
+    HIPC(hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, st));
+    GEVC(c->d_text.ensure(gev_rank_scratch_bytes(n), st));
+    const int e = gev_rank_device(dx, n, dr, c->d_text.p, st);
+    if (e) return fail(GEV_EDEVICE, "rank_f64: HIP error %s in the sort", hipGetErrorString((hipError_t)e));
+    HIPC(hipMemcpyAsync(rank_out, dr, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
 // std::random_shuffle of m entries on the rand() values R[0 .. m-2]: src[q] = original position of the entry that ends at p0 + q
 static int am_shuffle(gev_ctx* c, hipStream_t st, const u32* R, size_t m, size_t p0, size_t p1, DevBuf& src)
 {
@@ -3524,49 +3548,69 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
 }
 
 // ---- output materialisation ---------------------------------------------------------------
-// haplotype slots [slot0, slot0 + n) of the current generation, contiguous, into c->d_stage (already large enough)
-static int stage_rows(gev_ctx* c, PopState& P, int chr, size_t slot0, size_t n)
+// units (haplotype rows, individuals, SNPs) one staging pass of an output call takes: what fits the call's byte budget, at least 1;
+// SNPs in multiples of 64, at least 64.  The only place that knows the test cap of gev_dbg_output_chunk
+static size_t output_chunk(const gev_ctx* c, size_t budget_bytes, size_t bytes_per_unit, bool snps = false)
+{
+    size_t n = std::max<size_t>(budget_bytes / std::max<size_t>(bytes_per_unit, 1), 1);
+    if (c->dbg_output_chunk) n = std::min(n, c->dbg_output_chunk);
+    return snps ? std::max<size_t>(n, 64) & ~(size_t)63 : n;
+}
+// test hook: no staging pass of the following output calls takes more than max_units units (0: the byte budgets alone decide again)
+int gev_dbg_output_chunk(gev_ctx* c, size_t max_units)
+{
+    GEVC(check_not_pending(c));
+    c->dbg_output_chunk = max_units;
+    return GEV_OK;
+}
+// what every output call on (pop, chr) begins with; planes: the call reads the resident genotype planes
+static int output_begin(gev_ctx* c, int pop, int chr, const char* who, bool planes)
+{
+    GEVC(check_idx(c, pop, chr));
+    if (planes) GEVC(check_dense(c, who));
+    GEVC(check_active(c, chr, who));
+    if (!c->pop[pop].gen0) return fail(GEV_ESTATE, "%s: population %d has no current generation", who, pop);
+    HIPC(hipSetDevice(c->device));
+    GEVC(materialize_order(c, pop));
+    if (planes) GEVC(wait_planes(c));
+    return GEV_OK;
+}
+static int check_range(const char* who, const char* noun, size_t begin, size_t n, size_t bound)
+{
+    if (begin + n > bound) return fail(GEV_EINVAL, "%s: %s [%zu,%zu) beyond the %zu there are", who, noun, begin, begin + n, bound);
+    return GEV_OK;
+}
+// the caller's buffer of a request for n things: `have` of `need` (bytes, or words per row)
+static int check_out(const char* who, const void* out, size_t n, size_t have, size_t need, const char* unit)
+{
+    if (n && (!out || have < need)) return fail(GEV_EINVAL, "%s: output buffer of %zu %s, %zu needed", who, have, unit, need);
+    return GEV_OK;
+}
+// n_rows device rows of row_bytes bytes (pitch d_pitch) into the caller's rows of row_stride_words words, the pad behind each row
+// zeroed; returns when they have arrived
+static int copy_out_rows(gev_ctx* c, const void* d_rows, size_t d_pitch, size_t row_bytes, size_t n_rows, u64* bits, size_t row_stride_words)
+{
+    const size_t pitch = row_stride_words * 8;
+    if (pitch > row_bytes) for (size_t r = 0; r < n_rows; r++) memset((uint8_t*)bits + r * pitch + row_bytes, 0, pitch - row_bytes);
+    if (row_bytes) HIPC(hipMemcpy2DAsync(bits, pitch, d_rows, d_pitch, row_bytes, n_rows, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return GEV_OK;
+}
+// haplotype slots [slot0, slot0 + n) of the current generation, mutations applied, contiguous in c->d_stage (already large enough;
+// ensure_csr has run: the mutation overlay reads whole lists)
+static int stage_rows_mutated(gev_ctx* c, PopState& P, int chr, size_t slot0, size_t n)
 {
     ChrStatic& S = P.cs[chr]; ChrState& cs = P.st[chr];
     const u32 chunks = (u32)(S.stride / 16);
     if (!n) return GEV_OK;
     hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(n * chunks, 256)), dim3(256), 0, c->stream, flat_rows(c->d_stage.p, S.stride),
                        pool_rows(P, chr, cs.phys[P.pcur].as<u32>()), (const u32*)nullptr, slot0, n, chunks);
+    hipLaunchKernelGGL(k_snp_apply_mut, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, c->stream,
+                       row_map(P, chr), c->d_stage.as<u32>(), S.stride / 4, slot0, n,
+                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)S.L);
     KCHECK();
     return GEV_OK;
 }
-int gev_download_haps(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, u64* bits, size_t row_stride_words)
-{
-    if (c) GEVC(check_dense(c, "download_haps"));
-    GEVC(check_idx(c, pop, chr));
-    GEVC(check_active(c, chr, "download_haps"));
-    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr]; ChrState& cs = P.st[chr];
-    if (!P.gen0) return fail(GEV_ESTATE, "download_haps: population %d has no current generation", pop);
-    GEVC(materialize_order(c, pop));
-    GEVC(ensure_csr(c, pop));                     // (the mutation overlay reads whole lists)
-    if (row_begin + n_rows > 2 * P.n_people) return fail(GEV_EINVAL, "download_haps: rows [%zu,%zu) beyond 2*n_people=%zu", row_begin, row_begin + n_rows, 2 * P.n_people);
-    if (n_rows && (!bits || row_stride_words * 64 < S.L)) return fail(GEV_EINVAL, "download_haps: bad output buffer");
-    HIPC(hipSetDevice(c->device));
-    GEVC(wait_planes(c));
-    hipStream_t st = c->stream;
-    const size_t max_rows = std::max<size_t>((64u << 20) / S.stride, 1);
-    GEVC(c->d_stage.ensure(std::min(max_rows, std::max<size_t>(n_rows, 1)) * S.stride, st));
-    const size_t copy_bytes = std::min(row_stride_words * 8, S.stride);
-    for (size_t r0 = 0; r0 < n_rows; r0 += max_rows) {
-        const size_t nr = std::min(max_rows, n_rows - r0);
-        GEVC(stage_rows(c, P, chr, row_begin + r0, nr));
-        hipLaunchKernelGGL(k_snp_apply_mut, dim3((unsigned)ceil_div(nr, 256)), dim3(256), 0, st,
-                           row_map(P, chr), c->d_stage.as<u32>(), S.stride / 4, row_begin + r0, nr,
-                           cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)S.L);
-        KCHECK();
-        if (row_stride_words * 8 > copy_bytes)
-            for (size_t r = 0; r < nr; r++) memset((uint8_t*)(bits + (r0 + r) * row_stride_words) + copy_bytes, 0, row_stride_words * 8 - copy_bytes);
-        HIPC(hipMemcpy2DAsync(bits + r0 * row_stride_words, row_stride_words * 8, c->d_stage.p, S.stride, copy_bytes, nr, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
-    return GEV_OK;
-}
-// ---- K9: SNP-major outputs (SURVEY 8(f) row 3) ---------------------------------------------------
 // SNP-major bit matrix of SNPs [s0, s0+ns) of the current generation (mutations applied) into c->d_snpmajor
 static int snp_major_device(gev_ctx* c, int pop, int chr, size_t s0, size_t ns, size_t& stride_w64)
 {
@@ -3588,94 +3632,144 @@ static int snp_major_device(gev_ctx* c, int pop, int chr, size_t s0, size_t ns, 
     KCHECK();
     return GEV_OK;
 }
-static int snp_range_check(gev_ctx* c, int pop, int chr, size_t s0, size_t ns, const char* who)
+extern "C++" {      // (templates cannot have the C linkage of the block this file's functions sit in)
+// `bytes` of text through c->d_text: launch() enqueues the kernel that writes them there; returns when they have arrived in dst
+template <class Launch>
+static int copy_out_text(gev_ctx* c, size_t bytes, void* dst, Launch launch)
 {
-    GEVC(check_idx(c, pop, chr));
-    PopState& P = c->pop[pop];
-    if (!P.gen0) return fail(GEV_ESTATE, "%s: population %d has no current generation", who, pop);
-    if (s0 + ns > P.cs[chr].L) return fail(GEV_EINVAL, "%s: SNPs [%zu,%zu) beyond the %zu loci of chromosome %d", who, s0, s0 + ns, P.cs[chr].L, chr);
-    HIPC(hipSetDevice(c->device));
-    GEVC(materialize_order(c, pop));
-    GEVC(wait_planes(c));
+    GEVC(c->d_text.ensure(bytes, c->stream));
+    launch();
+    KCHECK();
+    HIPC(hipMemcpyAsync(dst, c->d_text.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
     return GEV_OK;
 }
-// SNPs per device chunk so that the staging buffers stay <= ~256 MB
-static size_t snp_chunk(size_t bytes_per_snp) { return std::max<size_t>((256u << 20) / std::max<size_t>(bytes_per_snp, 1), 64) & ~(size_t)63; }
-int gev_download_snp_major(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, u64* bits, size_t row_stride_words)
+// SNPs [snp_begin, +n_snps) through c->d_snpmajor in chunks that keep the staging buffers <= ~256 MB at bytes_per_snp each:
+// emit(s, ns, stride) delivers SNPs [snp_begin + s, +ns) (device rows of `stride` words) and returns when the host has them
+template <class Emit>
+static int snp_major_chunks(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t bytes_per_snp, Emit emit)
 {
-    if (c) GEVC(check_dense(c, "download_snp_major"));
-    GEVC(snp_range_check(c, pop, chr, snp_begin, n_snps, "download_snp_major"));
-    GEVC(check_active(c, chr, "download_snp_major"));
-    PopState& P = c->pop[pop];
-    const size_t rows = 2 * P.n_people, w = ceil_div(rows, 64);
-    if (n_snps && (!bits || row_stride_words < w)) return fail(GEV_EINVAL, "download_snp_major: bad output buffer");
-    const size_t chunk = snp_chunk(w * 8);
+    const size_t chunk = output_chunk(c, 256u << 20, bytes_per_snp, true);
     for (size_t s = 0; s < n_snps; s += chunk) {
         const size_t ns = std::min(chunk, n_snps - s); size_t stride;
         GEVC(snp_major_device(c, pop, chr, snp_begin + s, ns, stride));
-        if (row_stride_words > w) for (size_t j = 0; j < ns; j++) memset(bits + (s + j) * row_stride_words + w, 0, (row_stride_words - w) * 8);
-        HIPC(hipMemcpy2DAsync(bits + s * row_stride_words, row_stride_words * 8, c->d_snpmajor.p, stride * 8, w * 8, ns, hipMemcpyDeviceToHost, c->stream));
+        GEVC(emit(s, ns, stride));
+    }
+    return GEV_OK;
+}
+// the formatted ones, after output_begin: `line` bytes per SNP into out; launch(ns, stride) enqueues the kernel that formats ns SNPs
+// of c->d_snpmajor into c->d_text
+template <class Launch>
+static int format_snp_major(gev_ctx* c, int pop, int chr, const char* who, size_t snp_begin, size_t n_snps, size_t line, size_t bytes_per_snp,
+                            void* out, size_t out_bytes, Launch launch)
+{
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, c->pop[pop].cs[chr].L));
+    GEVC(check_out(who, out, n_snps, out_bytes, n_snps * line, "bytes"));
+    return snp_major_chunks(c, pop, chr, snp_begin, n_snps, bytes_per_snp, [&](size_t s, size_t ns, size_t stride) -> int {
+        return copy_out_text(c, ns * line, (char*)out + s * line, [&] { launch(ns, stride); });
+    });
+}
+// individuals [ind_begin, +n_ind) as hap-major rows (mutations applied) through c->d_stage in chunks of <= ~256 MB of output at
+// bytes_per_ind each: emit(i, n) delivers individuals [ind_begin + i, +n) from the staged rows and returns when the host has them
+template <class Emit>
+static int ind_major_chunks(gev_ctx* c, int pop, int chr, size_t ind_begin, size_t n_ind, size_t bytes_per_ind, Emit emit)
+{
+    PopState& P = c->pop[pop];
+    const size_t chunk = output_chunk(c, 256u << 20, bytes_per_ind);
+    for (size_t i = 0; i < n_ind; i += chunk) {
+        const size_t n = std::min(chunk, n_ind - i);
+        GEVC(c->d_stage.ensure(std::max<size_t>(2 * n * P.cs[chr].stride, 16), c->stream));
+        GEVC(ensure_csr(c, pop));
+        GEVC(stage_rows_mutated(c, P, chr, 2 * (ind_begin + i), 2 * n));
+        GEVC(emit(i, n));
+    }
+    return GEV_OK;
+}
+// a CSR list of the current generation to the host: *n = its length, hap_offsets[2 * n_people + 1] and the elements where asked for
+template <class T>
+static int download_list(gev_ctx* c, int pop, const char* who, const DevBuf& d_off, const DevBuf& d_val, T* out, u64* hap_offsets, size_t* n)
+{
+    if (!n) return fail(GEV_EINVAL, "%s: the list length has nowhere to go (null)", who);
+    const size_t rows = 2 * c->pop[pop].n_people;
+    std::vector<u32> off(rows + 1);
+    HIPC(hipMemcpyAsync(off.data(), d_off.p, (rows + 1) * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    *n = off[rows];
+    if (hap_offsets) for (size_t r = 0; r <= rows; r++) hap_offsets[r] = off[r];
+    if (out && off[rows]) {
+        HIPC(hipMemcpyAsync(out, d_val.p, (size_t)off[rows] * sizeof(T), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
     }
     return GEV_OK;
+}
+}
+int gev_download_haps(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, u64* bits, size_t row_stride_words)
+{
+    const char* who = "download_haps";
+    GEVC(output_begin(c, pop, chr, who, true));
+    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr];
+    GEVC(ensure_csr(c, pop));
+    GEVC(check_range(who, "rows", row_begin, n_rows, 2 * P.n_people));
+    GEVC(check_out(who, bits, n_rows, row_stride_words, ceil_div(S.L, 64), "words per row"));
+    const size_t max_rows = output_chunk(c, 64u << 20, S.stride);
+    GEVC(c->d_stage.ensure(std::min(max_rows, std::max<size_t>(n_rows, 1)) * S.stride, c->stream));
+    for (size_t r0 = 0; r0 < n_rows; r0 += max_rows) {
+        const size_t nr = std::min(max_rows, n_rows - r0);
+        GEVC(stage_rows_mutated(c, P, chr, row_begin + r0, nr));
+        GEVC(copy_out_rows(c, c->d_stage.p, S.stride, std::min(row_stride_words * 8, S.stride), nr, bits + r0 * row_stride_words, row_stride_words));
+    }
+    return GEV_OK;
+}
+// ---- K9: SNP-major outputs (SURVEY 8(f) row 3) ---------------------------------------------------
+int gev_download_snp_major(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, u64* bits, size_t row_stride_words)
+{
+    const char* who = "download_snp_major";
+    GEVC(output_begin(c, pop, chr, who, true));
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, c->pop[pop].cs[chr].L));
+    const size_t w = ceil_div(2 * c->pop[pop].n_people, 64);
+    GEVC(check_out(who, bits, n_snps, row_stride_words, w, "words per row"));
+    return snp_major_chunks(c, pop, chr, snp_begin, n_snps, w * 8, [&](size_t s, size_t ns, size_t stride) -> int {
+        return copy_out_rows(c, c->d_snpmajor.p, stride * 8, w * 8, ns, bits + s * row_stride_words, row_stride_words);
+    });
 }
 // bytes of the reference's .hap file for SNP lines [snp_begin, snp_begin+n_snps): n_snps * (4*n_people + 1)
 int gev_format_hap_text(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, char* out, size_t out_bytes)
 {
-    if (c) GEVC(check_dense(c, "format_hap_text"));
-    GEVC(snp_range_check(c, pop, chr, snp_begin, n_snps, "format_hap_text"));
-    GEVC(check_active(c, chr, "format_hap_text"));
-    PopState& P = c->pop[pop];
-    const size_t rows = 2 * P.n_people, line = 2 * rows + 1;
-    if (out_bytes < n_snps * line || (n_snps && !out)) return fail(GEV_EINVAL, "format_hap_text: buffer of %zu bytes, %zu needed", out_bytes, n_snps * line);
-    const size_t chunk = snp_chunk(line);
-    for (size_t s = 0; s < n_snps; s += chunk) {
-        const size_t ns = std::min(chunk, n_snps - s); size_t stride;
-        GEVC(snp_major_device(c, pop, chr, snp_begin + s, ns, stride));
-        GEVC(c->d_text.ensure(ns * line, c->stream));
+    GEVC(output_begin(c, pop, chr, "format_hap_text", true));
+    const size_t rows = 2 * c->pop[pop].n_people, line = 2 * rows + 1;
+    return format_snp_major(c, pop, chr, "format_hap_text", snp_begin, n_snps, line, line, out, out_bytes, [&](size_t ns, size_t stride) {
         hipLaunchKernelGGL(k_format_hap_text, dim3((unsigned)ceil_div(ceil_div(ns * line, 16), 256)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, rows, (u32)ns, c->d_text.as<char>());
-        KCHECK();
-        HIPC(hipMemcpyAsync(out + s * line, c->d_text.p, ns * line, hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    return GEV_OK;
+    });
 }
-// hap-major rows (mutations applied) of individuals [ind0, ind0+n) into c->d_stage
-static int stage_individuals(gev_ctx* c, int pop, int chr, size_t ind0, size_t n)
+// GT columns of the VCF data lines: n_snps * (4*n_people + 1) bytes; the caller writes the nine fixed columns in front
+int gev_format_vcf_gt(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, char* out, size_t out_bytes)
 {
-    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr]; ChrState& cs = P.st[chr];
-    hipStream_t st = c->stream;
-    GEVC(c->d_stage.ensure(std::max<size_t>(2 * n * S.stride, 16), st));
-    if (!n) return GEV_OK;
-    GEVC(ensure_csr(c, pop));
-    GEVC(stage_rows(c, P, chr, 2 * ind0, 2 * n));
-    hipLaunchKernelGGL(k_snp_apply_mut, dim3((unsigned)ceil_div(2 * n, 256)), dim3(256), 0, st,
-                       row_map(P, chr), c->d_stage.as<u32>(), S.stride / 4, 2 * ind0, 2 * n,
-                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)S.L);
-    KCHECK();
-    return GEV_OK;
+    GEVC(output_begin(c, pop, chr, "format_vcf_gt", true));
+    const size_t n_people = c->pop[pop].n_people, line = 4 * n_people + 1;
+    return format_snp_major(c, pop, chr, "format_vcf_gt", snp_begin, n_snps, line, line, out, out_bytes, [&](size_t ns, size_t stride) {
+        hipLaunchKernelGGL(k_format_vcf_gt, dim3((unsigned)ceil_div(ceil_div(ns * line, 16), 256)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, n_people, (u32)ns, c->d_text.as<char>());
+    });
 }
-static int ind_range_check(gev_ctx* c, int pop, int chr, size_t ind0, size_t n, const char* what)
+// PLINK .bed body (SNP-major, without the 3 magic bytes 0x6c 0x1b 0x01): n_snps * ceil(n_people/4) bytes
+int gev_format_bed(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, uint8_t* out, size_t out_bytes)
 {
-    GEVC(check_idx(c, pop, chr));
-    PopState& P = c->pop[pop];
-    if (!P.gen0) return fail(GEV_ESTATE, "%s: population %d has no current generation", what, pop);
-    GEVC(materialize_order(c, pop));
-    if (ind0 + n > P.n_people) return fail(GEV_EINVAL, "%s: individuals [%zu,%zu) beyond n_people=%zu", what, ind0, ind0 + n, P.n_people);
-    HIPC(hipSetDevice(c->device));
-    GEVC(wait_planes(c));
-    return GEV_OK;
+    GEVC(output_begin(c, pop, chr, "format_bed", true));
+    const size_t n_people = c->pop[pop].n_people, bpl = ceil_div(n_people, 4);
+    return format_snp_major(c, pop, chr, "format_bed", snp_begin, n_snps, bpl, ceil_div(2 * n_people, 64) * 8, out, out_bytes, [&](size_t ns, size_t stride) {
+        hipLaunchKernelGGL(k_format_bed, dim3((unsigned)ceil_div(ns * bpl, 256)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, n_people, (u32)ns, c->d_text.as<uint8_t>());
+    });
 }
+// ---- PLINK individual-major outputs ---------------------------------------------------------
 // genotype columns of the PLINK .ped text, one line per individual (the caller writes the six id columns in front)
 int gev_format_ped_text(gev_ctx* c, int pop, int chr, size_t ind_begin, size_t n_ind, const char* al0, const char* al1, char* out, size_t out_bytes)
 {
-    if (c) GEVC(check_dense(c, "format_ped_text"));
-    GEVC(ind_range_check(c, pop, chr, ind_begin, n_ind, "format_ped_text"));
-    GEVC(check_active(c, chr, "format_ped_text"));
+    const char* who = "format_ped_text";
+    GEVC(output_begin(c, pop, chr, who, true));
     ChrStatic& S = c->pop[pop].cs[chr];
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, c->pop[pop].n_people));
     const size_t line = 4 * S.L + 1;
     if ((al0 == nullptr) != (al1 == nullptr)) return fail(GEV_EINVAL, "format_ped_text: al0 and al1 must both be given or both be NULL");
-    if (out_bytes < n_ind * line || (n_ind && !out)) return fail(GEV_EINVAL, "format_ped_text: buffer of %zu bytes, %zu needed", out_bytes, n_ind * line);
+    GEVC(check_out(who, out, n_ind, out_bytes, n_ind * line, "bytes"));
     hipStream_t st = c->stream;
     const char *d_al0 = nullptr, *d_al1 = nullptr;
     if (al0) {
@@ -3684,80 +3778,42 @@ int gev_format_ped_text(gev_ctx* c, int pop, int chr, size_t ind_begin, size_t n
         HIPC(hipMemcpyAsync(c->d_tmp.as<char>() + S.L, al1, S.L, hipMemcpyHostToDevice, st));
         d_al0 = c->d_tmp.as<char>(); d_al1 = d_al0 + S.L;
     }
-    const size_t chunk = std::max<size_t>((256u << 20) / line, 1);
-    for (size_t i = 0; i < n_ind; i += chunk) {
-        const size_t n = std::min(chunk, n_ind - i);
-        GEVC(stage_individuals(c, pop, chr, ind_begin + i, n));
-        GEVC(c->d_text.ensure(n * line, st));
-        hipLaunchKernelGGL(k_format_ped_text, dim3((unsigned)ceil_div(ceil_div(n * line, 16), 256)), dim3(256), 0, st, c->d_stage.as<u32>(), S.stride / 4, n, (u32)S.L, d_al0, d_al1, c->d_text.as<char>());
-        KCHECK();
-        HIPC(hipMemcpyAsync(out + i * line, c->d_text.p, n * line, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
-    return GEV_OK;
+    return ind_major_chunks(c, pop, chr, ind_begin, n_ind, line, [&](size_t i, size_t n) -> int {
+        return copy_out_text(c, n * line, out + i * line, [&] {
+            hipLaunchKernelGGL(k_format_ped_text, dim3((unsigned)ceil_div(ceil_div(n * line, 16), 256)), dim3(256), 0, st, c->d_stage.as<u32>(), S.stride / 4, n, (u32)S.L, d_al0, d_al1, c->d_text.as<char>());
+        });
+    });
 }
 // matrix_plink_ped rows (bit 2*snp + hap), ceil(2L/64) words per individual
 int gev_download_plink_matrix(gev_ctx* c, int pop, int chr, size_t ind_begin, size_t n_ind, u64* bits, size_t row_stride_words)
 {
-    if (c) GEVC(check_dense(c, "download_plink_matrix"));
-    GEVC(ind_range_check(c, pop, chr, ind_begin, n_ind, "download_plink_matrix"));
-    GEVC(check_active(c, chr, "download_plink_matrix"));
+    const char* who = "download_plink_matrix";
+    GEVC(output_begin(c, pop, chr, who, true));
     ChrStatic& S = c->pop[pop].cs[chr];
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, c->pop[pop].n_people));
     const size_t w32 = ceil_div(S.L, 32);                  // one source word -> one 64-bit output word
-    if (n_ind && (!bits || row_stride_words < w32)) return fail(GEV_EINVAL, "download_plink_matrix: bad output buffer (need %zu words per row)", w32);
-    hipStream_t st = c->stream;
-    const size_t chunk = std::max<size_t>((256u << 20) / std::max<size_t>(w32 * 8, 1), 1);
-    for (size_t i = 0; i < n_ind; i += chunk) {
-        const size_t n = std::min(chunk, n_ind - i);
-        GEVC(stage_individuals(c, pop, chr, ind_begin + i, n));
-        GEVC(c->d_text.ensure(std::max<size_t>(n * w32 * 8, 16), st));
-        if (w32) hipLaunchKernelGGL(k_interleave_haps, dim3((unsigned)ceil_div(n * w32, 256)), dim3(256), 0, st, c->d_stage.as<u32>(), S.stride / 4, n, (u32)w32, c->d_text.as<u64>(), w32);
+    GEVC(check_out(who, bits, n_ind, row_stride_words, w32, "words per row"));
+    return ind_major_chunks(c, pop, chr, ind_begin, n_ind, w32 * 8, [&](size_t i, size_t n) -> int {
+        GEVC(c->d_text.ensure(std::max<size_t>(n * w32 * 8, 16), c->stream));
+        if (w32) hipLaunchKernelGGL(k_interleave_haps, dim3((unsigned)ceil_div(n * w32, 256)), dim3(256), 0, c->stream, c->d_stage.as<u32>(), S.stride / 4, n, (u32)w32, c->d_text.as<u64>(), w32);
         KCHECK();
-        if (row_stride_words > w32)
-            for (size_t r = 0; r < n; r++) memset(bits + (i + r) * row_stride_words + w32, 0, (row_stride_words - w32) * 8);
-        if (w32) HIPC(hipMemcpy2DAsync(bits + i * row_stride_words, row_stride_words * 8, c->d_text.p, w32 * 8, w32 * 8, n, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-    }
-    return GEV_OK;
+        return copy_out_rows(c, c->d_text.p, w32 * 8, w32 * 8, n, bits + i * row_stride_words, row_stride_words);
+    });
 }
-// CommFunc::ras_rank on the device (the O(n^2) host loop of assort_mate, src/Simulation.cpp:2278-2279): stable radix sort of
-// order-preserving keys with the reference's tie / NaN rule (gev_sort.hip)
-extern "C" size_t gev_rank_scratch_bytes(size_t n);
-extern "C" int gev_rank_device(const double* d_x, size_t n, unsigned long long* d_rank, void* d_tmp, hipStream_t st);
-int gev_rank_f64(gev_ctx* c, const double* x, size_t n, unsigned long long* rank_out)
+// ---- K8: tiles of the genotype matrix from the interval state and founder tiles -------------------
+// rows [row_begin, +n_rows) x loci [snp_begin, +n_snps); one founder tile per root population (after migration a part may descend
+// from another population's founders, :1204)
+static int materialize_begin(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, size_t snp_begin, size_t n_snps)
 {
-    if (!c) return fail(GEV_EINVAL, "null context");
-    if (n && (!x || !rank_out)) return fail(GEV_EINVAL, "rank_f64: null buffer");
-    if (!n) return GEV_OK;
-    if (n >= 0xffffffffull) return fail(GEV_EINVAL, "rank_f64: too many values");
-    HIPC(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    GEVC(c->d_tmp.ensure(n * 16, st));
-    double* dx = c->d_tmp.as<double>(); unsigned long long* dr = (unsigned long long*)(dx + n);
-    HIPC(hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, st));
-    GEVC(c->d_text.ensure(gev_rank_scratch_bytes(n), st));
-    const int e = gev_rank_device(dx, n, dr, c->d_text.p, st);
-    if (e) return fail(GEV_EDEVICE, "rank_f64: HIP error %s in the sort", hipGetErrorString((hipError_t)e));
-    HIPC(hipMemcpyAsync(rank_out, dr, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
-}
-// K8: rows [row_begin, +n_rows) x loci [snp_begin, +n_snps) of the genotype matrix from the interval state and founder tiles
-// (one per root population: after migration a part may descend from another population's founders, :1204)
-// checks + founder tiles to the device (c->d_snpmajor, stacked population after population; row offsets in c->d_map)
-static int materialize_prepare(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, size_t snp_begin, size_t n_snps,
-                               const u64* const* founder_bits, const size_t* founder_stride_words, const size_t* n_founder_rows)
-{
-    GEVC(check_idx(c, pop, chr));
-    GEVC(check_active(c, chr, "materialize"));
-    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr];
-    if (!P.gen0) return fail(GEV_ESTATE, "materialize: population %d has no current generation", pop);
+    GEVC(output_begin(c, pop, chr, "materialize", false));
     if (!c->track_intervals) return fail(GEV_ESTATE, "materialize: interval tracking is disabled");
-    GEVC(materialize_order(c, pop));
-    if (row_begin + n_rows > 2 * P.n_people) return fail(GEV_EINVAL, "materialize: rows [%zu,%zu) beyond 2*n_people=%zu", row_begin, row_begin + n_rows, 2 * P.n_people);
-    if (snp_begin + n_snps > S.L) return fail(GEV_EINVAL, "materialize: SNPs [%zu,%zu) beyond L=%zu", snp_begin, snp_begin + n_snps, S.L);
+    GEVC(check_range("materialize", "rows", row_begin, n_rows, 2 * c->pop[pop].n_people));
+    return check_range("materialize", "SNPs", snp_begin, n_snps, c->pop[pop].cs[chr].L);
+}
+// founder tiles to the device (c->d_snpmajor, stacked population after population; row offsets in c->d_map)
+static int upload_founder_tiles(gev_ctx* c, size_t n_snps, const u64* const* founder_bits, const size_t* founder_stride_words, const size_t* n_founder_rows)
+{
     const size_t w64 = ceil_div(n_snps, 64);
-    if (!n_rows || !n_snps) return GEV_OK;
     if (!founder_bits || !founder_stride_words || !n_founder_rows) return fail(GEV_EINVAL, "materialize: bad founder tile");
     std::vector<u64> row0(c->n_pop + 1, 0);
     for (int p = 0; p < c->n_pop; p++) {
@@ -3765,7 +3821,6 @@ static int materialize_prepare(gev_ctx* c, int pop, int chr, size_t row_begin, s
         row0[p + 1] = row0[p] + n_founder_rows[p];
     }
     if (!row0[c->n_pop]) return fail(GEV_EINVAL, "materialize: bad founder tile");
-    HIPC(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     GEVC(c->d_snpmajor.ensure(row0[c->n_pop] * w64 * 8, st));
     for (int p = 0; p < c->n_pop; p++)
@@ -3805,20 +3860,18 @@ static int materialize_status(gev_ctx* c)
 int gev_materialize_pops(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, size_t snp_begin, size_t n_snps,
                          const u64* const* founder_bits, const size_t* founder_stride_words, const size_t* n_founder_rows, u64* bits, size_t row_stride_words)
 {
-    GEVC(materialize_prepare(c, pop, chr, row_begin, n_rows, snp_begin, n_snps, founder_bits, founder_stride_words, n_founder_rows));
-    const size_t w64 = ceil_div(n_snps, 64);
+    GEVC(materialize_begin(c, pop, chr, row_begin, n_rows, snp_begin, n_snps));
     if (!n_rows || !n_snps) return GEV_OK;
-    if (!bits || row_stride_words < w64) return fail(GEV_EINVAL, "materialize: bad output buffer");
+    GEVC(upload_founder_tiles(c, n_snps, founder_bits, founder_stride_words, n_founder_rows));
+    const size_t w64 = ceil_div(n_snps, 64);
+    GEVC(check_out("materialize", bits, n_rows, row_stride_words, w64, "words per row"));
     hipStream_t st = c->stream;
-    const size_t max_rows = std::max<size_t>((128u << 20) / (w64 * 8), 1);
+    const size_t max_rows = output_chunk(c, 128u << 20, w64 * 8);
     for (size_t r0 = 0; r0 < n_rows; r0 += max_rows) {
         const size_t nr = std::min(max_rows, n_rows - r0);
         GEVC(c->d_stage.ensure(nr * w64 * 8, st)); GEVC(c->d_text.ensure(nr * w64 * 8, st));
         GEVC(materialize_rows(c, pop, chr, row_begin + r0, nr, snp_begin, n_snps, c->d_stage.as<u64>(), c->d_text.as<u64>()));
-        if (row_stride_words > w64)
-            for (size_t r = 0; r < nr; r++) memset(bits + (r0 + r) * row_stride_words + w64, 0, (row_stride_words - w64) * 8);
-        HIPC(hipMemcpy2DAsync(bits + r0 * row_stride_words, row_stride_words * 8, c->d_text.p, w64 * 8, w64 * 8, nr, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
+        GEVC(copy_out_rows(c, c->d_text.p, w64 * 8, w64 * 8, nr, bits + r0 * row_stride_words, row_stride_words));
     }
     return materialize_status(c);
 }
@@ -3827,13 +3880,12 @@ int gev_materialize_pops(gev_ctx* c, int pop, int chr, size_t row_begin, size_t 
 int gev_materialize_bed(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
                         const u64* const* founder_bits, const size_t* founder_stride_words, const size_t* n_founder_rows, uint8_t* out, size_t out_bytes)
 {
-    if (!c) return fail(GEV_EINVAL, "null context");
-    GEVC(check_idx(c, pop, chr));
+    GEVC(materialize_begin(c, pop, chr, 0, 0, snp_begin, n_snps));
     PopState& P = c->pop[pop];
     const size_t rows = 2 * P.n_people, bpl = ceil_div(P.n_people, 4), w64 = ceil_div(n_snps, 64);
-    GEVC(materialize_prepare(c, pop, chr, 0, rows, snp_begin, n_snps, founder_bits, founder_stride_words, n_founder_rows));
     if (!n_snps || !rows) return GEV_OK;
-    if (!out || out_bytes < n_snps * bpl) return fail(GEV_EINVAL, "materialize_bed: buffer of %zu bytes, %zu needed", out_bytes, n_snps * bpl);
+    GEVC(upload_founder_tiles(c, n_snps, founder_bits, founder_stride_words, n_founder_rows));
+    GEVC(check_out("materialize_bed", out, n_snps, out_bytes, n_snps * bpl, "bytes"));
     hipStream_t st = c->stream;
     GEVC(c->d_stage.ensure(rows * w64 * 8, st)); GEVC(c->d_tmp.ensure(rows * w64 * 8, st));
     GEVC(materialize_rows(c, pop, chr, 0, rows, snp_begin, n_snps, c->d_stage.as<u64>(), c->d_tmp.as<u64>()));
@@ -3857,48 +3909,6 @@ int gev_materialize(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_row
     if (!c) return fail(GEV_EINVAL, "null context");
     if (c->n_pop > 1) return fail(GEV_EINVAL, "materialize: this context has %d populations: use gev_materialize_pops (one founder tile per root population)", c->n_pop);
     return gev_materialize_pops(c, pop, chr, row_begin, n_rows, snp_begin, n_snps, &founder_bits, &founder_stride_words, &n_founder_rows, bits, row_stride_words);
-}
-// GT columns of the VCF data lines: n_snps * (4*n_people + 1) bytes; the caller writes the nine fixed columns in front
-int gev_format_vcf_gt(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, char* out, size_t out_bytes)
-{
-    if (c) GEVC(check_dense(c, "format_vcf_gt"));
-    GEVC(snp_range_check(c, pop, chr, snp_begin, n_snps, "format_vcf_gt"));
-    GEVC(check_active(c, chr, "format_vcf_gt"));
-    PopState& P = c->pop[pop];
-    const size_t line = 4 * P.n_people + 1;
-    if (out_bytes < n_snps * line || (n_snps && !out)) return fail(GEV_EINVAL, "format_vcf_gt: buffer of %zu bytes, %zu needed", out_bytes, n_snps * line);
-    const size_t chunk = snp_chunk(line);
-    for (size_t s = 0; s < n_snps; s += chunk) {
-        const size_t ns = std::min(chunk, n_snps - s); size_t stride;
-        GEVC(snp_major_device(c, pop, chr, snp_begin + s, ns, stride));
-        GEVC(c->d_text.ensure(ns * line, c->stream));
-        hipLaunchKernelGGL(k_format_vcf_gt, dim3((unsigned)ceil_div(ceil_div(ns * line, 16), 256)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, P.n_people, (u32)ns, c->d_text.as<char>());
-        KCHECK();
-        HIPC(hipMemcpyAsync(out + s * line, c->d_text.p, ns * line, hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    return GEV_OK;
-}
-// PLINK .bed body (SNP-major, without the 3 magic bytes 0x6c 0x1b 0x01): n_snps * ceil(n_people/4) bytes
-int gev_format_bed(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, uint8_t* out, size_t out_bytes)
-{
-    if (c) GEVC(check_dense(c, "format_bed"));
-    GEVC(snp_range_check(c, pop, chr, snp_begin, n_snps, "format_bed"));
-    GEVC(check_active(c, chr, "format_bed"));
-    PopState& P = c->pop[pop];
-    const size_t bpl = ceil_div(P.n_people, 4);
-    if (out_bytes < n_snps * bpl || (n_snps && !out)) return fail(GEV_EINVAL, "format_bed: buffer of %zu bytes, %zu needed", out_bytes, n_snps * bpl);
-    const size_t chunk = snp_chunk(ceil_div(2 * P.n_people, 64) * 8);
-    for (size_t s = 0; s < n_snps; s += chunk) {
-        const size_t ns = std::min(chunk, n_snps - s); size_t stride;
-        GEVC(snp_major_device(c, pop, chr, snp_begin + s, ns, stride));
-        GEVC(c->d_text.ensure(ns * bpl, c->stream));
-        hipLaunchKernelGGL(k_format_bed, dim3((unsigned)ceil_div(ns * bpl, 256)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, P.n_people, (u32)ns, c->d_text.as<uint8_t>());
-        KCHECK();
-        HIPC(hipMemcpyAsync(out + s * bpl, c->d_text.p, ns * bpl, hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    return GEV_OK;
 }
 
 int gev_download_cv(gev_ctx* c, int pop, int phen, int chr, u64* bits, size_t row_stride_words)
@@ -3927,48 +3937,18 @@ int gev_download_cv(gev_ctx* c, int pop, int phen, int chr, u64* bits, size_t ro
 }
 int gev_download_intervals(gev_ctx* c, int pop, int chr, gev_part* out, u64* hap_offsets, size_t* n_parts)
 {
-    GEVC(check_idx(c, pop, chr));
-    GEVC(check_active(c, chr, "download_intervals"));
-    PopState& P = c->pop[pop]; ChrState& cs = P.st[chr];
-    if (!P.gen0) return fail(GEV_ESTATE, "download_intervals: population %d has no current generation", pop);
-    GEVC(materialize_order(c, pop));
+    GEVC(output_begin(c, pop, chr, "download_intervals", false));
     GEVC(ensure_csr(c, pop));
     if (!c->track_intervals) return fail(GEV_ESTATE, "download_intervals: interval tracking is disabled");
-    if (!n_parts) return fail(GEV_EINVAL, "download_intervals: n_parts is null");
-    HIPC(hipSetDevice(c->device));
-    const size_t rows = 2 * P.n_people;
-    std::vector<u32> off(rows + 1);
-    HIPC(hipMemcpyAsync(off.data(), cs.poff[P.cur].p, (rows + 1) * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    *n_parts = off[rows];
-    if (hap_offsets) for (size_t r = 0; r <= rows; r++) hap_offsets[r] = off[r];
-    if (out && off[rows]) {
-        HIPC(hipMemcpyAsync(out, cs.parts[P.cur].p, (size_t)off[rows] * sizeof(gev_part), hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    return GEV_OK;
+    PopState& P = c->pop[pop]; ChrState& cs = P.st[chr];
+    return download_list(c, pop, "download_intervals", cs.poff[P.cur], cs.parts[P.cur], out, hap_offsets, n_parts);
 }
 int gev_download_mutations(gev_ctx* c, int pop, int chr, u64* out, u64* hap_offsets, size_t* n_mut)
 {
-    GEVC(check_idx(c, pop, chr));
-    GEVC(check_active(c, chr, "download_mutations"));
-    PopState& P = c->pop[pop]; ChrState& cs = P.st[chr];
-    if (!P.gen0) return fail(GEV_ESTATE, "download_mutations: population %d has no current generation", pop);
-    GEVC(materialize_order(c, pop));
+    GEVC(output_begin(c, pop, chr, "download_mutations", false));
     GEVC(ensure_csr(c, pop));
-    if (!n_mut) return fail(GEV_EINVAL, "download_mutations: n_mut is null");
-    HIPC(hipSetDevice(c->device));
-    const size_t rows = 2 * P.n_people;
-    std::vector<u32> off(rows + 1);
-    HIPC(hipMemcpyAsync(off.data(), cs.moff[P.cur].p, (rows + 1) * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    *n_mut = off[rows];
-    if (hap_offsets) for (size_t r = 0; r <= rows; r++) hap_offsets[r] = off[r];
-    if (out && off[rows]) {
-        HIPC(hipMemcpyAsync(out, cs.mpos[P.cur].p, (size_t)off[rows] * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    return GEV_OK;
+    PopState& P = c->pop[pop]; ChrState& cs = P.st[chr];
+    return download_list(c, pop, "download_mutations", cs.moff[P.cur], cs.mpos[P.cur], out, hap_offsets, n_mut);
 }
 
 // ---- introspection ------------------------------------------------------------------------

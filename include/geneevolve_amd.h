@@ -638,6 +638,9 @@ int    gev_dbg_verify_planes(gev_ctx*, int pop, int chr, const uint64_t* founder
  * for which the prefilter's 20-bit fraction deviates from the exact one by more than its proven bound (must be 0: the prefilter
  * then flags a superset of the exact candidates for every threshold), out[1] / out[2] = largest deviations seen. */
 int    gev_dbg_prefilter_sweep(gev_ctx*, uint32_t x_begin, uint32_t x_end, unsigned long long out[3]);
+/* gev_dbg_output_chunk: no staging pass of the following genotype output calls takes more than max_units haplotype rows / individuals /
+ * SNPs (SNPs: rounded down to a multiple of 64, at least 64), so that small tests run many passes; 0 = the byte budgets again.  Refused while a generation is pending. */
+int    gev_dbg_output_chunk(gev_ctx*, size_t max_units);
 int    gev_dbg_tables(void* out, size_t bytes);
 int    gev_dbg_threshold(double p, uint32_t out[4] /* a_lo, a_hi, b0, b1 */);
 double gev_dbg_canonical(uint32_t a, uint32_t b);

@@ -975,7 +975,10 @@ def test_gpu_scale_ad_compute_gef_matches_reference(gpu_lib, oracle_lib, case):
 def test_snp_major_and_bed_packing_match_their_definition(gpu_lib):
     """K9: SNP-major transpose / PLINK .bed against numpy on the downloaded haplotype-major matrix (mutations applied).
     The reference has no .bed writer: checked by definition (parity unpinned); the .hap TEXT is pinned on the
-    reference's own output files in the golden replays."""
+    reference's own output files in the golden replays.  Everything runs twice: in one staging pass per call, as the byte budgets
+    have it at this size, and with gev_dbg_output_chunk(7) in many (SNPs (70, 999): 15 passes of 64 from an unaligned start and
+    one of 39; 666 rows: 95 passes of 7 and one of 1; individuals (3, 20): 7 + 7 + 6), byte for byte the same; and every
+    row-matrix call also with a row stride three words wider than needed, whose pad words it must zero."""
     cfg = SyntheticConfig(333, 5000, chrom_bp=2_000_000, map_step=1000, rec_per_row=2e-3, mut_per_row=0.05, n_cv=10, seed=4)
     g = gpu_lib.create(1, 1, 1)
     cfg.apply_static(g)
@@ -987,35 +990,67 @@ def test_snp_major_and_bed_packing_match_their_definition(gpu_lib):
         sim.couples[0] = synthetic_random_mate(sim.sex[0], 333, rng)
         sim.reproduce(0, gen)
     L, n = 5000, 333
-    H = capi.unpack_rows(g.download_haps(0, 0), L)                       # [666][5000]
-    for (s0, ns) in ((0, L), (70, 999), (4937, 63)):
-        S = capi.unpack_rows(g.download_snp_major(0, 0, s0, ns), 2 * n)  # [ns][666]
-        assert np.array_equal(S, H[:, s0:s0 + ns].T), (s0, ns)
-        bed = g.format_bed(0, 0, s0, ns).reshape(ns, (n + 3) // 4)
-        a, b = H[0::2, s0:s0 + ns].T, H[1::2, s0:s0 + ns].T             # [ns][n]
-        code = np.where((a & b) == 1, 0, np.where((a ^ b) == 1, 2, 3)).astype(np.uint8)
-        pad = (-n) % 4
-        code = np.concatenate([code, np.zeros((ns, pad), dtype=np.uint8)], axis=1).reshape(ns, -1, 4)
-        want = code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)
-        assert np.array_equal(bed, want), (s0, ns)
-        txt = g.format_hap_text(0, 0, s0, ns).reshape(ns, 4 * n + 1)
-        assert (txt[:, -1] == ord("\n")).all() and (txt[:, 1::2][:, :2 * n] == ord(" ")).all()
-        assert np.array_equal(txt[:, 0:4 * n:2] - ord("0"), H[:, s0:s0 + ns].T)
-        gt = g.format_vcf_gt(0, 0, s0, ns).reshape(ns, 4 * n + 1)            # "\ta|b" per individual (format_vcf.cpp:55-59)
-        assert (gt[:, -1] == ord("\n")).all() and (gt[:, 0:4 * n:4] == ord("\t")).all() and (gt[:, 2:4 * n:4] == ord("|")).all()
-        assert np.array_equal(gt[:, 1:4 * n:4] - ord("0"), H[0::2, s0:s0 + ns].T) and np.array_equal(gt[:, 3:4 * n:4] - ord("0"), H[1::2, s0:s0 + ns].T)
-    # PLINK individual-major siblings (ranges that start / end inside the population; L = 5000 is not a multiple of 32 or 64)
-    full = helpers.interleave_haps(g.download_haps(0, 0), L)
     al0 = np.frombuffer(b"ACGT", dtype=np.uint8)[np.arange(L) % 4]; al1 = np.frombuffer(b"TGCA", dtype=np.uint8)[(np.arange(L) // 3) % 4]
-    for (i0, ni) in ((0, n), (1, 7), (330, 3), (5, 0)):
-        assert np.array_equal(g.download_plink_matrix(0, 0, i0, ni), full[i0:i0 + ni]), (i0, ni)
-        for letters in (False, True):
-            txt = g.format_ped_text(0, 0, al0 if letters else None, al1 if letters else None, i0, ni).reshape(ni, 4 * L + 1)
-            assert (txt[:, -1] == ord("\n")).all() and (txt[:, 0:4 * L:2] == ord(" ")).all()
-            for hp in (0, 1):
-                bits = H[2 * i0 + hp:2 * (i0 + ni):2, :]
-                want = np.where(bits == 1, al1, al0) if letters else bits + ord("0")
-                assert np.array_equal(txt[:, 1 + 2 * hp:4 * L:4], want), (i0, ni, letters, hp)
+
+    def padded(exact, wide):
+        """a call with row_stride_words = needed + 3 into 0xFF bytes: the data words of the exact-width call, three zero pad words"""
+        w = exact.shape[1]
+        assert wide.shape == (exact.shape[0], w + 3) and np.array_equal(wide[:, :w], exact) and not wide[:, w:].any()
+
+    def outputs():
+        """every output call, checked by definition against the downloaded matrix; -> all the bytes they returned"""
+        got = {}
+        words = g.download_haps(0, 0)
+        H = capi.unpack_rows(words, L)                                   # [666][5000]
+        got["haps"] = words
+        got["haps", 5, 30] = sub = g.download_haps(0, 0, 5, 30)
+        assert np.array_equal(sub, words[5:35])
+        padded(words, g.download_haps(0, 0, stride_words=words.shape[1] + 3))
+        padded(sub, g.download_haps(0, 0, 5, 30, stride_words=words.shape[1] + 3))
+        for (s0, ns) in ((0, L), (70, 999), (4937, 63)):
+            got["snp_major", s0, ns] = sm = g.download_snp_major(0, 0, s0, ns)
+            S = capi.unpack_rows(sm, 2 * n)                                  # [ns][666]
+            assert np.array_equal(S, H[:, s0:s0 + ns].T), (s0, ns)
+            padded(sm, g.download_snp_major(0, 0, s0, ns, stride_words=sm.shape[1] + 3))
+            got["bed", s0, ns] = bed = g.format_bed(0, 0, s0, ns)
+            bed = bed.reshape(ns, (n + 3) // 4)
+            a, b = H[0::2, s0:s0 + ns].T, H[1::2, s0:s0 + ns].T             # [ns][n]
+            code = np.where((a & b) == 1, 0, np.where((a ^ b) == 1, 2, 3)).astype(np.uint8)
+            pad = (-n) % 4
+            code = np.concatenate([code, np.zeros((ns, pad), dtype=np.uint8)], axis=1).reshape(ns, -1, 4)
+            want = code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)
+            assert np.array_equal(bed, want), (s0, ns)
+            got["hap_text", s0, ns] = txt = g.format_hap_text(0, 0, s0, ns)
+            txt = txt.reshape(ns, 4 * n + 1)
+            assert (txt[:, -1] == ord("\n")).all() and (txt[:, 1::2][:, :2 * n] == ord(" ")).all()
+            assert np.array_equal(txt[:, 0:4 * n:2] - ord("0"), H[:, s0:s0 + ns].T)
+            got["vcf_gt", s0, ns] = gt = g.format_vcf_gt(0, 0, s0, ns)
+            gt = gt.reshape(ns, 4 * n + 1)                                       # "\ta|b" per individual (format_vcf.cpp:55-59)
+            assert (gt[:, -1] == ord("\n")).all() and (gt[:, 0:4 * n:4] == ord("\t")).all() and (gt[:, 2:4 * n:4] == ord("|")).all()
+            assert np.array_equal(gt[:, 1:4 * n:4] - ord("0"), H[0::2, s0:s0 + ns].T) and np.array_equal(gt[:, 3:4 * n:4] - ord("0"), H[1::2, s0:s0 + ns].T)
+        # PLINK individual-major siblings (ranges that start / end inside the population; L = 5000 is not a multiple of 32 or 64)
+        full = helpers.interleave_haps(words, L)
+        for (i0, ni) in ((0, n), (1, 7), (330, 3), (3, 20), (5, 0)):
+            got["plink", i0, ni] = pm = g.download_plink_matrix(0, 0, i0, ni)
+            assert np.array_equal(pm, full[i0:i0 + ni]), (i0, ni)
+            padded(pm, g.download_plink_matrix(0, 0, i0, ni, stride_words=pm.shape[1] + 3))
+            for letters in (False, True):
+                got["ped", i0, ni, letters] = txt = g.format_ped_text(0, 0, al0 if letters else None, al1 if letters else None, i0, ni)
+                txt = txt.reshape(ni, 4 * L + 1)
+                assert (txt[:, -1] == ord("\n")).all() and (txt[:, 0:4 * L:2] == ord(" ")).all()
+                for hp in (0, 1):
+                    bits = H[2 * i0 + hp:2 * (i0 + ni):2, :]
+                    want = np.where(bits == 1, al1, al0) if letters else bits + ord("0")
+                    assert np.array_equal(txt[:, 1 + 2 * hp:4 * L:4], want), (i0, ni, letters, hp)
+        return got
+
+    whole = outputs()
+    g.dbg_output_chunk(7)                     # many staging passes per call: 64 SNPs, 7 rows, 7 individuals at a time
+    chunked = outputs()
+    g.dbg_output_chunk(0)
+    assert whole.keys() == chunked.keys()
+    for k in whole:
+        assert np.array_equal(whole[k], chunked[k]), k
     with pytest.raises(capi.GevError):
         g.format_ped_text(0, 0, None, None, n - 1, 2)
     g.close()
@@ -1312,7 +1347,8 @@ def test_materialize_tiles_from_intervals_and_the_plane_less_mode(gpu_lib, oracl
             assert np.array_equal(osx, oo) and np.array_equal(ps, po)
             ms, mos = sparse.download_mutations(0, c); mo, moo = orc.download_mutations(0, c)
             assert np.array_equal(mos, moo) and np.array_equal(ms, mo)
-            for (s0, ns, r0, nr) in ((0, L, 0, 2 * n_off), (64, 1000, 3, 57), (2990, 11, 2 * n_off - 1, 1), (31, 33, 0, 10)):
+            tiles_checked = ((0, L, 0, 2 * n_off), (64, 1000, 3, 57), (2990, 11, 2 * n_off - 1, 1), (31, 33, 0, 10))
+            for (s0, ns, r0, nr) in tiles_checked:
                 tile = slice_bits(founders[c], L, s0, ns)
                 want = slice_bits(full[r0:r0 + nr], L, s0, ns)
                 for g in (dense, sparse, orc):
@@ -1321,6 +1357,20 @@ def test_materialize_tiles_from_intervals_and_the_plane_less_mode(gpu_lib, oracl
                 tiles = [slice_bits(founders[c], L, s0, ns)]
                 want = dense.format_bed(0, c, s0, ns)
                 assert np.array_equal(sparse.materialize_bed(0, c, tiles, s0, ns), want) and np.array_equal(dense.materialize_bed(0, c, tiles, s0, ns), want), (gen, c, s0, ns)
+            if gen == 5:                                                         # the same tiles in staging passes of 7 rows ((64, 1000, 3, 57): 8 and 1)
+                for g in (dense, sparse):
+                    g.dbg_output_chunk(7)
+                for (s0, ns, r0, nr) in tiles_checked:
+                    tile = slice_bits(founders[c], L, s0, ns)
+                    want = slice_bits(full[r0:r0 + nr], L, s0, ns)
+                    for g in (dense, sparse):
+                        assert np.array_equal(g.materialize(0, c, tile, r0, nr, s0, ns), want), (gen, c, s0, ns, r0, nr)
+                        wide = g.materialize(0, c, tile, r0, nr, s0, ns, stride_words=want.shape[1] + 3)     # into 0xFF bytes: pad words zeroed
+                        assert np.array_equal(wide[:, :-3], want) and not wide[:, -3:].any(), (gen, c, s0, ns, r0, nr)
+                for g in (dense, sparse):
+                    g.dbg_output_chunk(0)
+                wide = sparse.materialize(0, c, slice_bits(founders[c], L, 64, 1000), 3, 57, 64, 1000, stride_words=16 + 3)
+                assert np.array_equal(wide[:, :16], slice_bits(full[3:60], L, 64, 1000)) and not wide[:, 16:].any()
             with pytest.raises(capi.GevError):
                 sparse.download_haps(0, c)
             with pytest.raises(capi.GevError):
