@@ -1624,6 +1624,14 @@ __global__ void k_gather_u8(uint8_t* __restrict__ dst, const uint8_t* __restrict
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[map[i << shift] >> shift];
 }
+// rows map[j] of every plane of src (sstride words apart) become rows j of the planes of dst (dstride apart), planes on grid.y.
+// 64-bit words: the [3][n] selection values, the pedigree id fields and the phenotype components follow the individuals through it
+__global__ void __launch_bounds__(256) k_gather_planes64(u64* __restrict__ dst, size_t dstride, const u64* __restrict__ src, size_t sstride,
+                                                         const u32* __restrict__ map, size_t m)
+{
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) dst[(size_t)blockIdx.y * dstride + j] = src[(size_t)blockIdx.y * sstride + map[j]];
+}
 // CSR gather: count / fill of rows selected by map (element size templated)
 __global__ void k_csr_gather_count(const u32* __restrict__ s_off, const u32* __restrict__ map, size_t n_rows, u32* __restrict__ cnt)
 {

@@ -2947,58 +2947,122 @@ int gev_get_cv_freq(gev_ctx* c, int pop, int phen, int chr, double* frq, size_t 
 
 // ---- Simulation::ras_do_migration (row movement part) -------------------------------------
 struct Seg { int src_pop; std::vector<u32> people; };     // individuals (positions in src_pop's current generation)
-// rebuild population `dst` in its alternate buffers from segments of the CURRENT buffers; caller flips
-static int gather_population(gev_ctx* c, int dst, const std::vector<Seg>& segs, size_t n_new)
+// The gather plan of one gev_migrate / materialize_order: for every destination the individuals of its non-empty segments, in segment
+// order, and the haplotype rows 2p, 2p + 1 made from them -- uploaded ONCE into c->d_map, which nothing refills before the call's last
+// gather has been enqueued ("One gather plan").  Segment g of a destination fills its individuals [g.i0, g.i0 + g.m).
+struct PlanSeg { int src_pop; size_t i0, m; const u32* people; const u32* rows; };       // device: m individuals, 2m haplotype rows
+struct GatherPlan { std::vector<std::vector<PlanSeg>> segs; std::vector<size_t> n_new; };  // [destination]
+static int upload_plan(gev_ctx* c, const std::vector<std::vector<Seg>>& plan, GatherPlan& gp)
+{
+    gp.segs.assign(plan.size(), {}); gp.n_new.assign(plan.size(), 0);
+    std::vector<u32> up;                                // [people | rows]
+    for (const auto& segs : plan) for (const Seg& sg : segs) up.insert(up.end(), sg.people.begin(), sg.people.end());
+    const size_t total = up.size();
+    up.resize(3 * total);
+    for (size_t j = 0; j < total; j++) { up[total + 2 * j] = 2 * up[j]; up[total + 2 * j + 1] = 2 * up[j] + 1; }
+    GEVC(h2d(c, c->d_map, up.data(), up.size() * sizeof(u32)));
+    const u32* d_people = c->d_map.as<u32>(); const u32* d_rows = d_people + total;
+    size_t at = 0;
+    for (size_t d = 0; d < plan.size(); d++) for (const Seg& sg : plan[d]) {
+        const size_t m = sg.people.size();
+        if (m) gp.segs[d].push_back(PlanSeg{sg.src_pop, gp.n_new[d], m, d_people + at, d_rows + 2 * at});
+        gp.n_new[d] += m; at += m;
+    }
+    return GEV_OK;
+}
+extern "C++" {      // (templates cannot have the C linkage of the block this file's functions sit in)
+// the one walk over a destination's segments: f(source population, segment)
+template <class F>
+static int for_segments(gev_ctx* c, const GatherPlan& gp, int dst, F f)
+{
+    for (const PlanSeg& g : gp.segs[dst]) GEVC(f(c->pop[g.src_pop], g));
+    return GEV_OK;
+}
+// a value that follows the individuals stays valid where every population that contributes individuals had it
+template <class Has>
+static bool every_source(gev_ctx* c, const GatherPlan& gp, int dst, Has has)
+{
+    bool ok = true;
+    for (const PlanSeg& g : gp.segs[dst]) ok = ok && has(c->pop[g.src_pop]);
+    return ok;
+}
+}   // extern "C++"
+// 8-byte planes (doubles, ids) of a segment's individuals: dst is the destination's plane 0 at the segment's i0
+static int gather_planes(gev_ctx* c, unsigned planes, void* dst, size_t dstride, const void* src, size_t sstride, const PlanSeg& g)
+{
+    hipLaunchKernelGGL(k_gather_planes64, dim3((unsigned)ceil_div(g.m, 256), planes), dim3(256), 0, c->stream, (u64*)dst, dstride, (const u64*)src, sstride, g.people, g.m);
+    KCHECK();
+    return GEV_OK;
+}
+// The lists of the rows `rows` selects from the current generation of (P, k): from the CSR form where it is there (the cheaper one to
+// read; always, behind ensure_csr), else from the pieces -- the only place that launches either pair of kernels for selected rows.
+// Lengths: mcnt[n_rows], and pcnt[n_rows] with gev_set_track_intervals
+static int selected_lists_count(gev_ctx* c, PopState& P, int k, const u32* rows, size_t n_rows, u32* mcnt, u32* pcnt)
+{
+    ChrState& cs = P.st[k];
+    const bool track = c->track_intervals, pieces = !cs.csr_valid;
+    if (pieces)
+        hipLaunchKernelGGL(k_lp_count, dim3((unsigned)ceil_div(n_rows * LP_MAXSEG, 256)), dim3(256), 0, c->stream, track ? cs.lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr,
+                           cs.lp.mtab[P.cur].as<uint2>(), cs.lp.nseg, rows, n_rows, track ? pcnt : (u32*)nullptr, mcnt);
+    else for (int pass = 0; pass < (track ? 2 : 1); pass++)
+        hipLaunchKernelGGL(k_csr_gather_count, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, c->stream, pass == 0 ? cs.moff[P.cur].as<u32>() : cs.poff[P.cur].as<u32>(),
+                           rows, n_rows, pass == 0 ? mcnt : pcnt);
+    KCHECK();
+    return GEV_OK;
+}
+// the lists themselves: row r of the selection goes behind mpos[moff[r]] / parts[poff[r]] (moff, poff: the caller's scans of the lengths)
+static int selected_lists_fill(gev_ctx* c, PopState& P, int k, const u32* rows, size_t n_rows, const u32* moff, u64* mpos, const u32* poff, gev_part* parts)
+{
+    ChrState& cs = P.st[k];
+    const bool track = c->track_intervals, pieces = !cs.csr_valid;
+    const unsigned blocks = (unsigned)ceil_div(n_rows, 256);
+    if (pieces)
+        hipLaunchKernelGGL(k_lp_fill, dim3((unsigned)ceil_div(n_rows * LP_MAXSEG, 256)), dim3(256), 0, c->stream, track ? cs.lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr,
+                           cs.lp.mtab[P.cur].as<uint2>(), cs.lp.parena.as<LpPart>(), cs.lp.marena.as<u64>(), cs.lp.nseg, rows, n_rows, (u64)P.cs[k].rbp.back(), poff, parts, moff, mpos);
+    else {
+        hipLaunchKernelGGL((k_csr_gather_fill<u64>), dim3(blocks), dim3(256), 0, c->stream, cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), rows, n_rows, moff, mpos);
+        if (track) hipLaunchKernelGGL((k_csr_gather_fill<gev_part>), dim3(blocks), dim3(256), 0, c->stream, cs.poff[P.cur].as<u32>(), cs.parts[P.cur].as<gev_part>(), rows, n_rows, poff, parts);
+    }
+    KCHECK();
+    return GEV_OK;
+}
+// the logical positions of P name other rows than they did: couples left on the device and the cached A/D are void
+static void positions_changed(gev_ctx* c, PopState& P) { P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1; }
+// P lives in the buffers a gather wrote: n individuals in dense order (gev_migrate, materialize_order)
+static void flip_to_gathered(gev_ctx* c, PopState& P, size_t n)
+{
+    P.cur ^= 1; P.pcur = (P.pcur + 1) % 3; P.n_people = P.n_phys = n; P.logical.clear();
+    positions_changed(c, P);
+}
+// individuals left or joined by position (gev_remove_rows, gev_import_rows): the per-individual values did not follow them
+static void membership_changed(gev_ctx* c, PopState& P)
+{
+    P.n_people = P.logical.size(); P.drop_selection(); P.ids_ok = false;
+    positions_changed(c, P);
+}
+// rebuild population `dst` in its alternate buffers from its segments of the CURRENT buffers (in CSR form, capacity there); caller flips
+static int gather_population(gev_ctx* c, int dst, const GatherPlan& gp)
 {
     PopState& D = c->pop[dst];
     hipStream_t st = c->stream;
     const int alt = D.cur ^ 1;
-    const size_t rows_new = 2 * n_new;
-    for (const Seg& sg : segs) if (!sg.people.empty()) GEVC(ensure_csr(c, sg.src_pop));      // whole lists of the sources are read
-    // capacity of the alternate buffers (the current ones keep their content)
-    if (n_new > D.cap_people) GEVC(ensure_capacity(c, dst, n_new));
-    GEVC(c->d_cnt.ensure((rows_new + 1) * sizeof(u32), st));
+    const size_t rows_new = 2 * gp.n_new[dst];
+    const bool track = c->track_intervals;
+    GEVC(c->d_cnt.ensure(2 * (rows_new + 1) * sizeof(u32), st));
+    u32* mcnt = c->d_cnt.as<u32>(); u32* pcnt = mcnt + rows_new + 1;
     for (int k = 0; k < c->nchr; k++) {
         if (!c->chr_active[k]) continue;                // held by another context of a locus-split population
         ChrStatic& S = D.cs[k]; ChrState& ds = D.st[k];
-        for (int pass = 0; pass < 2; pass++) {          // 0: mutation lists, 1: interval lists
-            if (pass == 1 && !c->track_intervals) continue;
-            size_t row0 = 0;
-            for (const Seg& sg : segs) {                // counts
-                if (sg.people.empty()) continue;
-                PopState& Sp = c->pop[sg.src_pop]; ChrState& ss = Sp.st[k];
-                std::vector<u32> map(2 * sg.people.size());
-                for (size_t j = 0; j < sg.people.size(); j++) { map[2 * j] = 2 * sg.people[j]; map[2 * j + 1] = 2 * sg.people[j] + 1; }
-                GEVC(h2d(c, c->d_map, map.data(), map.size() * sizeof(u32)));
-                const u32* soff = pass == 0 ? ss.moff[Sp.cur].as<u32>() : ss.poff[Sp.cur].as<u32>();
-                hipLaunchKernelGGL(k_csr_gather_count, dim3((unsigned)ceil_div(map.size(), 256)), dim3(256), 0, st, soff, c->d_map.as<u32>(), map.size(), c->d_cnt.as<u32>() + row0);
-                KCHECK();
-                HIPC(hipStreamSynchronize(st));
-                row0 += map.size();
-            }
-            u32 tot = 0;
-            u32* doff = pass == 0 ? ds.moff[alt].as<u32>() : ds.poff[alt].as<u32>();
-            GEVC(scan_u32(c, c->d_cnt.as<u32>(), rows_new, doff, &tot));
-            if (pass == 0) { GEVC(ds.mpos[alt].ensure(std::max<size_t>(tot, 2) * sizeof(u64), st, false, 1.25)); ds.mut_total[alt] = tot; }
-            else { GEVC(ds.parts[alt].ensure(std::max<size_t>(tot, 1) * sizeof(gev_part), st, false, 1.25)); ds.parts_total[alt] = tot; }
-            row0 = 0;
-            for (const Seg& sg : segs) {                // fill
-                if (sg.people.empty()) continue;
-                PopState& Sp = c->pop[sg.src_pop]; ChrState& ss = Sp.st[k];
-                std::vector<u32> map(2 * sg.people.size());
-                for (size_t j = 0; j < sg.people.size(); j++) { map[2 * j] = 2 * sg.people[j]; map[2 * j + 1] = 2 * sg.people[j] + 1; }
-                GEVC(h2d(c, c->d_map, map.data(), map.size() * sizeof(u32)));
-                if (pass == 0)
-                    hipLaunchKernelGGL((k_csr_gather_fill<u64>), dim3((unsigned)ceil_div(map.size(), 256)), dim3(256), 0, st,
-                                       ss.moff[Sp.cur].as<u32>(), ss.mpos[Sp.cur].as<u64>(), c->d_map.as<u32>(), map.size(), doff + row0, ds.mpos[alt].as<u64>());
-                else
-                    hipLaunchKernelGGL((k_csr_gather_fill<gev_part>), dim3((unsigned)ceil_div(map.size(), 256)), dim3(256), 0, st,
-                                       ss.poff[Sp.cur].as<u32>(), ss.parts[Sp.cur].as<gev_part>(), c->d_map.as<u32>(), map.size(), doff + row0, ds.parts[alt].as<gev_part>());
-                KCHECK();
-                HIPC(hipStreamSynchronize(st));
-                row0 += map.size();
-            }
-        }
+        u32* moff = ds.moff[alt].as<u32>(); u32* poff = ds.poff[alt].as<u32>();
+        GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int { return selected_lists_count(c, Sp, k, g.rows, 2 * g.m, mcnt + 2 * g.i0, pcnt + 2 * g.i0); }));
+        u32 tot_m = 0, tot_p = 0;                       // (the totals size the destination's list buffers: these syncs stay)
+        GEVC(scan_u32(c, mcnt, rows_new, moff, &tot_m));
+        if (track) GEVC(scan_u32(c, pcnt, rows_new, poff, &tot_p));
+        GEVC(ds.mpos[alt].ensure(std::max<size_t>(tot_m, 2) * sizeof(u64), st, false, 1.25)); ds.mut_total[alt] = tot_m;
+        if (track) { GEVC(ds.parts[alt].ensure(std::max<size_t>(tot_p, 1) * sizeof(gev_part), st, false, 1.25)); ds.parts_total[alt] = tot_p; }
+        GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int {
+            return selected_lists_fill(c, Sp, k, g.rows, 2 * g.m, moff + 2 * g.i0, ds.mpos[alt].as<u64>(), poff + 2 * g.i0, ds.parts[alt].as<gev_part>());
+        }));
         // genotype rows: fresh pool rows of the destination, filled from the sources' pools
         PoolWork dpw{};
         if (c->dense) {
@@ -3008,41 +3072,29 @@ static int gather_population(gev_ctx* c, int dst, const std::vector<Seg>& segs, 
             GEVC(pool_take(dpw, 0, rows_new, st));
             ds.pool_list_valid = false;                      // (the next generation builds its own list: the host's picture of this one is gone)
         }
-        size_t row0 = 0;
-        for (const Seg& sg : segs) {
-            if (sg.people.empty()) continue;
-            PopState& Sp = c->pop[sg.src_pop];
-            std::vector<u32> map(2 * sg.people.size());
-            for (size_t j = 0; j < sg.people.size(); j++) { map[2 * j] = 2 * sg.people[j]; map[2 * j + 1] = 2 * sg.people[j] + 1; }
-            GEVC(h2d(c, c->d_map, map.data(), map.size() * sizeof(u32)));
+        GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int {
             const u32 chunks = (u32)(S.stride / 16);
             if (c->dense)
-                hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(map.size() * chunks, 256)), dim3(256), 0, st,
-                                   pool_rows(D, k, dpw.phys_alt + row0 * S.nseg), pool_rows(Sp, k, Sp.st[k].phys[Sp.pcur].as<u32>()), c->d_map.as<u32>(), (size_t)0, map.size(), chunks);
+                hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * g.m * chunks, 256)), dim3(256), 0, st,
+                                   pool_rows(D, k, dpw.phys_alt + 2 * g.i0 * S.nseg), pool_rows(Sp, k, Sp.st[k].phys[Sp.pcur].as<u32>()), g.rows, (size_t)0, 2 * g.m, chunks);
             for (int p = 0; p < c->nphen; p++) {
                 CvStatic& V = D.cv[p][k];
                 const u32 cch = V.stride_w32 / 4;
-                hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)ceil_div(map.size() * cch, 256)), dim3(256), 0, st,
-                                   (uint4*)(D.cvp[p][k][alt].as<u32>() + row0 * V.stride_w32), (size_t)cch,
-                                   (const uint4*)Sp.cvp[p][k][Sp.cur].p, (size_t)Sp.cv[p][k].stride_w32 / 4, c->d_map.as<u32>(), map.size(), cch);
+                hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)ceil_div(2 * g.m * cch, 256)), dim3(256), 0, st,
+                                   (uint4*)(D.cvp[p][k][alt].as<u32>() + 2 * g.i0 * V.stride_w32), (size_t)cch,
+                                   (const uint4*)Sp.cvp[p][k][Sp.cur].p, (size_t)Sp.cv[p][k].stride_w32 / 4, g.rows, 2 * g.m, cch);
                 V.frq_valid = false;
             }
             KCHECK();
-            HIPC(hipStreamSynchronize(st));
-            row0 += map.size();
-        }
+            return GEV_OK;
+        }));
     }
     // Human::sex follows the individuals (what gev_random_mate reads)
-    size_t i0 = 0;
-    for (const Seg& sg : segs) {
-        if (sg.people.empty()) continue;
-        PopState& Sp = c->pop[sg.src_pop];
-        GEVC(h2d(c, c->d_map, sg.people.data(), sg.people.size() * sizeof(u32)));
-        hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(sg.people.size(), 256)), dim3(256), 0, st, D.d_sex[alt].as<uint8_t>() + i0, Sp.d_sex[Sp.cur].as<uint8_t>(), c->d_map.as<u32>(), 0u, sg.people.size());
+    GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int {
+        hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(g.m, 256)), dim3(256), 0, st, D.d_sex[alt].as<uint8_t>() + g.i0, Sp.d_sex[Sp.cur].as<uint8_t>(), g.people, 0u, g.m);
         KCHECK();
-        HIPC(hipStreamSynchronize(st));
-        i0 += sg.people.size();
-    }
+        return GEV_OK;
+    }));
     for (int k = 0; k < c->nchr; k++) { D.st[k].csr_valid = true; D.st[k].lp.valid = false; }     // (the caller flips to the buffers written here: CSR form, no pieces yet)
     return GEV_OK;
 }
@@ -3052,21 +3104,23 @@ static int materialize_order(gev_ctx* c, int pop)
     PopState& P = c->pop[pop];
     if (P.logical.empty()) return GEV_OK;
     GEVC(gev_sync(c));
-    Seg all; all.src_pop = pop; all.people = P.logical;
-    std::vector<Seg> segs; segs.push_back(std::move(all));
-    GEVC(gather_population(c, pop, segs, P.n_people));
+    GEVC(ensure_csr(c, pop));                               // whole lists are read
+    std::vector<std::vector<Seg>> plan(c->n_pop);
+    plan[pop].push_back(Seg{pop, P.logical});
+    GatherPlan gp;
+    GEVC(upload_plan(c, plan, gp));
+    GEVC(gather_population(c, pop, gp));
     if (P.ids_ok) {                                         // the pedigree ids are kept by physical row: they move with the rows
         const int nb = P.ibuf ^ 1;
         GEVC(P.d_ids[nb].ensure(PED_FIELDS * P.n_people * sizeof(int64_t), c->stream));
-        GEVC(h2d(c, c->d_map, P.logical.data(), P.n_people * sizeof(u32)));
-        hipLaunchKernelGGL(k_ped_gather, dim3((unsigned)ceil_div(P.n_people, 256)), dim3(256), 0, c->stream, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf],
-                           (const u32*)c->d_map.as<u32>(), P.n_people, P.d_ids[nb].as<int64_t>(), P.n_people);
-        KCHECK();
-        HIPC(hipStreamSynchronize(c->stream));
+        GEVC(for_segments(c, gp, pop, [&](PopState& S, const PlanSeg& g) -> int {
+            return gather_planes(c, PED_FIELDS, P.d_ids[nb].as<int64_t>() + g.i0, P.n_people, S.d_ids[S.ibuf].p, S.ids_stride[S.ibuf], g);
+        }));
         P.ids_stride[nb] = P.n_people; P.ibuf = nb;
     }
+    HIPC(hipStreamSynchronize(c->stream));
     P.cs_ok = false; P.comp_ok = false;
-    P.cur ^= 1; P.pcur = (P.pcur + 1) % 3; P.n_phys = P.n_people; P.logical.clear(); P.layout_epoch++; c->ad_cached_pop = c->ad_host_set_pop = -1;
+    flip_to_gathered(c, P, P.n_people);
     return GEV_OK;
 }
 static int check_not_pending(gev_ctx* c)
@@ -3078,39 +3132,29 @@ static int check_not_pending(gev_ctx* c)
 // The phenotypes and Human::mating_value / selection_value / selection_value_func follow the individuals (the reference computes the
 // values, src/Simulation.cpp:1988, before ras_do_migration, :1998): gathered into the other buffers of every destination, valid where
 // every population that contributes individuals had them.  Called before the populations' sizes change.
-static int migrate_selection(gev_ctx* c, const std::vector<std::vector<Seg>>& plan, const std::vector<size_t>& n_new)
+static int migrate_selection(gev_ctx* c, const GatherPlan& gp)
 {
     hipStream_t st = c->stream;
     const u32 nph = (u32)c->nphen;
     std::vector<uint8_t> phen_ok(c->n_pop), sel_ok(c->n_pop);
     for (int d = 0; d < c->n_pop; d++) {
         PopState& D = c->pop[d];
-        bool ph = true, sl = true;
-        for (const Seg& sg : plan[d]) if (!sg.people.empty()) {
-            const PopState& S = c->pop[sg.src_pop];
-            for (u32 k = 0; k < nph; k++) ph = ph && S.phen_ok[k];
-            sl = sl && S.sel_ok;
-        }
-        phen_ok[d] = ph; sel_ok[d] = sl;
-        if (!ph && !sl) continue;
+        const size_t n = gp.n_new[d];
         const int nb = D.sbuf ^ 1;
-        if (ph) GEVC(D.d_phen[nb].ensure(n_new[d] * nph * sizeof(double), st));
-        if (sl) GEVC(D.d_sel[nb].ensure(3 * n_new[d] * sizeof(double), st));
-        size_t i0 = 0;
-        for (const Seg& sg : plan[d]) {
-            if (sg.people.empty()) continue;
-            const PopState& S = c->pop[sg.src_pop];
-            const size_t m = sg.people.size();
-            GEVC(h2d(c, c->d_map, sg.people.data(), m * sizeof(u32)));
-            if (ph)
-                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(m * nph, 256)), dim3(256), 0, st, D.d_phen[nb].as<double>() + i0 * nph,
-                                   (const double*)S.d_phen[S.sbuf].as<double>(), (const u32*)c->d_map.as<u32>(), m, nph);
-            if (sl) for (size_t v = 0; v < 3; v++)      // [3][n]: mating_value, selection_value, selection_value_func
-                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, D.d_sel[nb].as<double>() + v * n_new[d] + i0,
-                                   (const double*)S.d_sel[S.sbuf].as<double>() + v * S.n_people, (const u32*)c->d_map.as<u32>(), m, 1u);
-            KCHECK();
-            HIPC(hipStreamSynchronize(st));             // (d_map is refilled for the next segment)
-            i0 += m;
+        phen_ok[d] = every_source(c, gp, d, [&](const PopState& S) { return std::all_of(S.phen_ok.begin(), S.phen_ok.end(), [](uint8_t v) { return v != 0; }); });
+        sel_ok[d] = every_source(c, gp, d, [](const PopState& S) { return S.sel_ok; });
+        if (phen_ok[d]) {                               // interleaved [n][nphen]
+            GEVC(D.d_phen[nb].ensure(n * nph * sizeof(double), st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int {
+                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(g.m * nph, 256)), dim3(256), 0, st, D.d_phen[nb].as<double>() + g.i0 * nph,
+                                   (const double*)S.d_phen[S.sbuf].as<double>(), g.people, g.m, nph);
+                KCHECK();
+                return GEV_OK;
+            }));
+        }
+        if (sel_ok[d]) {                                // [3][n]: mating_value, selection_value, selection_value_func
+            GEVC(D.d_sel[nb].ensure(3 * n * sizeof(double), st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, 3, D.d_sel[nb].as<double>() + g.i0, n, S.d_sel[S.sbuf].p, S.n_people, g); }));
         }
     }
     for (int d = 0; d < c->n_pop; d++) {
@@ -3121,59 +3165,35 @@ static int migrate_selection(gev_ctx* c, const std::vector<std::vector<Seg>>& pl
 }
 // The pedigree ids follow the individuals as the selection values do (gev_set_track_pedigree); kept where every population that
 // contributes individuals had them.  Called behind materialize_order: positions are physical rows.
-static int migrate_pedigree(gev_ctx* c, const std::vector<std::vector<Seg>>& plan, const std::vector<size_t>& n_new)
+static int migrate_pedigree(gev_ctx* c, const GatherPlan& gp)
 {
     if (!c->track_pedigree) return GEV_OK;
     hipStream_t st = c->stream;
-    std::vector<uint8_t> ok(c->n_pop);
+    const unsigned planes = (unsigned)c->nphen * PH_COMP;     // the phenotype components (gev_generation_phenotypes), plane by plane
+    std::vector<uint8_t> ids_ok(c->n_pop), comp_ok(c->n_pop);
     for (int d = 0; d < c->n_pop; d++) {
         PopState& D = c->pop[d];
-        ok[d] = 1;
-        for (const Seg& sg : plan[d]) if (!sg.people.empty()) ok[d] = ok[d] && c->pop[sg.src_pop].ids_ok;
-        if (!ok[d]) continue;
-        const int nb = D.ibuf ^ 1;
-        GEVC(D.d_ids[nb].ensure(PED_FIELDS * n_new[d] * sizeof(int64_t), st));
-        size_t i0 = 0;
-        for (const Seg& sg : plan[d]) {
-            if (sg.people.empty()) continue;
-            const PopState& S = c->pop[sg.src_pop];
-            const size_t m = sg.people.size();
-            GEVC(h2d(c, c->d_map, sg.people.data(), m * sizeof(u32)));
-            hipLaunchKernelGGL(k_ped_gather, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, (const int64_t*)S.d_ids[S.ibuf].as<int64_t>(), S.ids_stride[S.ibuf],
-                               (const u32*)c->d_map.as<u32>(), m, D.d_ids[nb].as<int64_t>() + i0, n_new[d]);
-            KCHECK();
-            HIPC(hipStreamSynchronize(st));             // (d_map is refilled for the next segment)
-            i0 += m;
+        const size_t n = gp.n_new[d];
+        ids_ok[d] = every_source(c, gp, d, [](const PopState& S) { return S.ids_ok; });
+        comp_ok[d] = every_source(c, gp, d, [](const PopState& S) { return S.comp_ok; });
+        if (ids_ok[d]) {
+            const int nb = D.ibuf ^ 1;
+            GEVC(D.d_ids[nb].ensure(PED_FIELDS * n * sizeof(int64_t), st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, PED_FIELDS, D.d_ids[nb].as<int64_t>() + g.i0, n, S.d_ids[S.ibuf].p, S.ids_stride[S.ibuf], g); }));
+        }
+        if (comp_ok[d]) {
+            const int nb = D.cbuf ^ 1;
+            GEVC(D.d_comp[nb].ensure((size_t)planes * n * sizeof(double), st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, planes, D.d_comp[nb].as<double>() + g.i0, n, S.d_comp[S.cbuf].p, S.n_people, g); }));
         }
     }
     for (int d = 0; d < c->n_pop; d++) {
         PopState& D = c->pop[d];
-        if (ok[d]) { D.ibuf ^= 1; D.ids_stride[D.ibuf] = n_new[d]; }
-        D.ids_ok = ok[d]; D.cs_ok = false;                  // (the children's couple indices belong to the rows as they were published)
+        if (ids_ok[d]) { D.ibuf ^= 1; D.ids_stride[D.ibuf] = gp.n_new[d]; }
+        if (comp_ok[d]) D.cbuf ^= 1;
+        D.ids_ok = ids_ok[d]; D.comp_ok = comp_ok[d];
+        D.cs_ok = false;                                    // (the children's couple indices belong to the rows as they were published)
     }
-    // the phenotype components (gev_generation_phenotypes), plane by plane
-    const unsigned planes = (unsigned)c->nphen * PH_COMP;
-    for (int d = 0; d < c->n_pop; d++) {
-        PopState& D = c->pop[d];
-        ok[d] = 1;
-        for (const Seg& sg : plan[d]) if (!sg.people.empty()) ok[d] = ok[d] && c->pop[sg.src_pop].comp_ok;
-        if (!ok[d]) continue;
-        const int nb = D.cbuf ^ 1;
-        GEVC(D.d_comp[nb].ensure((size_t)planes * n_new[d] * sizeof(double), st));
-        size_t i0 = 0;
-        for (const Seg& sg : plan[d]) {
-            if (sg.people.empty()) continue;
-            const PopState& S = c->pop[sg.src_pop];
-            const size_t m = sg.people.size();
-            GEVC(h2d(c, c->d_map, sg.people.data(), m * sizeof(u32)));
-            hipLaunchKernelGGL(k_ph_gather, dim3((unsigned)ceil_div(m, 256), planes), dim3(256), 0, st, (const double*)S.d_comp[S.cbuf].as<double>(), S.n_people,
-                               (const u32*)c->d_map.as<u32>(), m, D.d_comp[nb].as<double>(), n_new[d], i0);
-            KCHECK();
-            HIPC(hipStreamSynchronize(st));
-            i0 += m;
-        }
-    }
-    for (int d = 0; d < c->n_pop; d++) { PopState& D = c->pop[d]; if (ok[d]) D.cbuf ^= 1; D.comp_ok = ok[d]; }
     return GEV_OK;
 }
 int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
@@ -3197,7 +3217,6 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
         gone[m.src_pop][m.src_pos] = 1;
     }
     std::vector<std::vector<Seg>> plan(c->n_pop);
-    std::vector<size_t> n_new(c->n_pop);
     for (int p = 0; p < c->n_pop; p++) {
         Seg keep; keep.src_pop = p;
         for (size_t i = 0; i < c->pop[p].n_people; i++) if (!gone[p][i]) keep.people.push_back((u32)i);   // stayers keep their order (:960-966)
@@ -3208,19 +3227,21 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
         if (plan[m.dst_pop].back().src_pop != m.src_pop || plan[m.dst_pop].size() == 1) { Seg s; s.src_pop = m.src_pop; plan[m.dst_pop].push_back(std::move(s)); }
         plan[m.dst_pop].back().people.push_back((u32)m.src_pos);
     }
+    std::vector<size_t> n_new(c->n_pop, 0);
     for (int p = 0; p < c->n_pop; p++) {
-        n_new[p] = 0;
         for (auto& s : plan[p]) n_new[p] += s.people.size();
         if (n_new[p] == 0) return fail(GEV_EINVAL, "migrate: population %d would become empty", p);
     }
     // grow every destination first (capacity growth copies the current buffers), then gather
-    for (int p = 0; p < c->n_pop; p++) if (n_new[p] > c->pop[p].cap_people) GEVC(ensure_capacity(c, p, n_new[p]));
+    for (int p = 0; p < c->n_pop; p++) GEVC(ensure_capacity(c, p, n_new[p]));
     for (int p = 0; p < c->n_pop; p++) GEVC(ensure_csr(c, p));          // whole lists of every population are read (before any flag of a destination changes)
-    for (int p = 0; p < c->n_pop; p++) GEVC(gather_population(c, p, plan[p], n_new[p]));
-    GEVC(migrate_selection(c, plan, n_new));
-    GEVC(migrate_pedigree(c, plan, n_new));
-    for (int p = 0; p < c->n_pop; p++) { c->pop[p].cur ^= 1; c->pop[p].pcur = (c->pop[p].pcur + 1) % 3; c->pop[p].n_people = n_new[p]; c->pop[p].n_phys = n_new[p]; c->pop[p].layout_epoch++; }
-    c->ad_cached_pop = c->ad_host_set_pop = -1;
+    GatherPlan gp;
+    GEVC(upload_plan(c, plan, gp));                                     // the call's only upload of a gather map (gp.n_new == n_new)
+    for (int p = 0; p < c->n_pop; p++) GEVC(gather_population(c, p, gp));
+    GEVC(migrate_selection(c, gp));
+    GEVC(migrate_pedigree(c, gp));
+    HIPC(hipStreamSynchronize(c->stream));                              // every gather has read its sources before a buffer is flipped
+    for (int p = 0; p < c->n_pop; p++) flip_to_gathered(c, c->pop[p], gp.n_new[p]);
     return GEV_OK;
 }
 // ---- cross-GPU form of the migration step ---------------------------------------------------
@@ -3249,12 +3270,13 @@ static PackLayout pack_layout(gev_ctx* c, PopState& P, size_t n, const std::vect
     L.total = off;
     return L;
 }
-// per-row list lengths of the selected individuals (device count kernels, one small D2H)
-static int export_counts(gev_ctx* c, int pop, const uint64_t* positions, size_t n, std::vector<u32>& counts, std::vector<u32>& map)
+// per-row list lengths of the selected individuals (device counts, one small D2H per chromosome); c->d_map then holds their
+// haplotype rows 2*individual, 2*individual+1
+static int export_counts(gev_ctx* c, int pop, const uint64_t* positions, size_t n, std::vector<u32>& counts)
 {
     PopState& P = c->pop[pop];
     const int nchr = c->nchr;
-    map.resize(2 * n);
+    std::vector<u32> map(2 * n);
     for (size_t i = 0; i < n; i++) {
         if (positions[i] >= P.n_people) return fail(GEV_EINVAL, "export: position %llu beyond the population (%zu people)", (unsigned long long)positions[i], P.n_people);
         const u32 ph = P.logical.empty() ? (u32)positions[i] : P.logical[positions[i]];
@@ -3263,34 +3285,15 @@ static int export_counts(gev_ctx* c, int pop, const uint64_t* positions, size_t 
     counts.assign(n * nchr * 4, 0);
     if (!n) return GEV_OK;
     GEVC(h2d(c, c->d_map, map.data(), map.size() * sizeof(u32)));
-    GEVC(c->d_cnt.ensure(2 * n * sizeof(u32) * 2 + 16, c->stream));
-    std::vector<u32> tmp(2 * n);
+    GEVC(c->d_cnt.ensure(4 * n * sizeof(u32) + 16, c->stream));
+    std::vector<u32> tmp(4 * n);                          // [mutations | interval parts] of the 2n rows
     for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
-        ChrState::LpState& lp = P.st[k].lp;
-        if (lp.valid) {                                   // the lists live as pieces: lengths of the selected rows straight from the tables
-            u32* mcnt = c->d_cnt.as<u32>(); u32* pcnt = mcnt + 2 * n;
-            hipLaunchKernelGGL(k_lp_count, dim3((unsigned)ceil_div(2 * n * LP_MAXSEG, 256)), dim3(256), 0, c->stream,
-                               c->track_intervals ? lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr, lp.mtab[P.cur].as<uint2>(), lp.nseg, c->d_map.as<u32>(), 2 * n,
-                               c->track_intervals ? pcnt : (u32*)nullptr, mcnt);
-            KCHECK();
-            for (int pass = 0; pass < 2; pass++) {
-                if (pass == 1 && !c->track_intervals) continue;
-                HIPC(hipMemcpyAsync(tmp.data(), pass == 0 ? mcnt : pcnt, 2 * n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-                HIPC(hipStreamSynchronize(c->stream));
-                for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) counts[((i * nchr + k) * 2 + h) * 2 + pass] = tmp[2 * i + h];
-            }
-            continue;
-        }
-        for (int pass = 0; pass < 2; pass++) {
-            if (pass == 1 && !c->track_intervals) continue;
-            const u32* soff = pass == 0 ? P.st[k].moff[P.cur].as<u32>() : P.st[k].poff[P.cur].as<u32>();
-            hipLaunchKernelGGL(k_csr_gather_count, dim3((unsigned)ceil_div(2 * n, 256)), dim3(256), 0, c->stream, soff, c->d_map.as<u32>(), 2 * n, c->d_cnt.as<u32>());
-            KCHECK();
-            HIPC(hipMemcpyAsync(tmp.data(), c->d_cnt.p, 2 * n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-            for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) counts[((i * nchr + k) * 2 + h) * 2 + pass] = tmp[2 * i + h];
-        }
+        GEVC(selected_lists_count(c, P, k, c->d_map.as<u32>(), 2 * n, c->d_cnt.as<u32>(), c->d_cnt.as<u32>() + 2 * n));
+        HIPC(hipMemcpyAsync(tmp.data(), c->d_cnt.p, (c->track_intervals ? 4 : 2) * n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) for (int pass = 0; pass < 2; pass++)
+            counts[((i * nchr + k) * 2 + h) * 2 + pass] = tmp[pass * 2 * n + 2 * i + h];
     }
     return GEV_OK;
 }
@@ -3301,8 +3304,8 @@ int gev_export_size(gev_ctx* c, int pop, const uint64_t* positions, size_t n, si
     PopState& P = c->pop[pop];
     if (!P.gen0) return fail(GEV_ESTATE, "export_size: population %d has no current generation", pop);
     HIPC(hipSetDevice(c->device));
-    std::vector<u32> counts, map;
-    GEVC(export_counts(c, pop, positions, n, counts, map));
+    std::vector<u32> counts;
+    GEVC(export_counts(c, pop, positions, n, counts));
     *bytes = pack_layout(c, P, n, counts).total;
     return GEV_OK;
 }
@@ -3314,52 +3317,34 @@ int gev_export_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n, vo
     if (!P.gen0) return fail(GEV_ESTATE, "export_rows: population %d has no current generation", pop);
     HIPC(hipSetDevice(c->device));
     GEVC(gev_sync(c));
-    std::vector<u32> counts, map;
-    GEVC(export_counts(c, pop, positions, n, counts, map));
+    std::vector<u32> counts;
+    GEVC(export_counts(c, pop, positions, n, counts));
     const PackLayout L = pack_layout(c, P, n, counts);
     if (bytes < L.total) return fail(GEV_EINVAL, "export_rows: buffer of %zu bytes, %zu needed", bytes, L.total);
     if (!n) return GEV_OK;
     hipStream_t st = c->stream;
     uint8_t* out = (uint8_t*)device_buf;
     const int nchr = c->nchr;
+    const u32* d_rows = c->d_map.as<u32>();               // haplotype rows 2*individual, 2*individual+1 (export_counts)
     HIPC(hipMemcpyAsync(out + L.counts, counts.data(), counts.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out + L.sex, P.d_sex[P.cur].as<uint8_t>(), c->d_map.as<u32>(), 1u, n);   // d_map holds haplotype rows 2*individual, 2*individual+1
+    hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out + L.sex, P.d_sex[P.cur].as<uint8_t>(), d_rows, 1u, n);
     size_t po = L.planes, co = L.cv, mo = L.muts, pa = L.parts;
     GEVC(c->d_cnt.ensure((2 * n + 1) * sizeof(u32) * 4, st));
-    u32* d_off = c->d_cnt.as<u32>() + 2 * n + 1;
+    u32* mcnt = c->d_cnt.as<u32>(); u32* moff = mcnt + (2 * n + 1); u32* pcnt = moff + (2 * n + 1); u32* poff = pcnt + (2 * n + 1);
     for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
         ChrStatic& S = P.cs[k]; ChrState& cs = P.st[k];
         const u32 chunks = (u32)(S.stride / 16);
         if (c->dense && c->migrant_rows) {
             hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * n * chunks, 256)), dim3(256), 0, st, flat_rows(out + po, S.stride),
-                               pool_rows(P, k, cs.phys[P.pcur].as<u32>()), c->d_map.as<u32>(), (size_t)0, 2 * n, chunks);
+                               pool_rows(P, k, cs.phys[P.pcur].as<u32>()), d_rows, (size_t)0, 2 * n, chunks);
             po = al16(po + 2 * n * S.stride);
         }
-        if (cs.lp.valid) {                                // pieces -> the records' lists, for the selected rows only
-            ChrState::LpState& lp = cs.lp;
-            const bool track = c->track_intervals;
-            u32* mcnt = c->d_cnt.as<u32>(); u32* moff = mcnt + (2 * n + 1); u32* pcnt = moff + (2 * n + 1); u32* poff = pcnt + (2 * n + 1);
-            const unsigned blocks = (unsigned)ceil_div(2 * n * LP_MAXSEG, 256);
-            hipLaunchKernelGGL(k_lp_count, dim3(blocks), dim3(256), 0, st, track ? lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr, lp.mtab[P.cur].as<uint2>(), lp.nseg,
-                               c->d_map.as<u32>(), 2 * n, track ? pcnt : (u32*)nullptr, mcnt);
-            KCHECK();
-            GEVC(scan_u32(c, mcnt, 2 * n, moff, nullptr));
-            if (track) GEVC(scan_u32(c, pcnt, 2 * n, poff, nullptr));
-            hipLaunchKernelGGL(k_lp_fill, dim3(blocks), dim3(256), 0, st, track ? lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr, lp.mtab[P.cur].as<uint2>(),
-                               lp.parena.as<LpPart>(), lp.marena.as<u64>(), lp.nseg, c->d_map.as<u32>(), 2 * n, (u64)S.rbp.back(),
-                               poff, (gev_part*)(out + pa), moff, (u64*)(out + mo));
-            KCHECK();
-        } else for (int pass = 0; pass < 2; pass++) {
-            if (pass == 1 && !c->track_intervals) continue;
-            const u32* soff = pass == 0 ? cs.moff[P.cur].as<u32>() : cs.poff[P.cur].as<u32>();
-            hipLaunchKernelGGL(k_csr_gather_count, dim3((unsigned)ceil_div(2 * n, 256)), dim3(256), 0, st, soff, c->d_map.as<u32>(), 2 * n, c->d_cnt.as<u32>());
-            KCHECK();
-            GEVC(scan_u32(c, c->d_cnt.as<u32>(), 2 * n, d_off, nullptr));
-            if (pass == 0) hipLaunchKernelGGL((k_csr_gather_fill<u64>), dim3((unsigned)ceil_div(2 * n, 256)), dim3(256), 0, st, soff, cs.mpos[P.cur].as<u64>(), c->d_map.as<u32>(), 2 * n, d_off, (u64*)(out + mo));
-            else hipLaunchKernelGGL((k_csr_gather_fill<gev_part>), dim3((unsigned)ceil_div(2 * n, 256)), dim3(256), 0, st, soff, cs.parts[P.cur].as<gev_part>(), c->d_map.as<u32>(), 2 * n, d_off, (gev_part*)(out + pa));
-            KCHECK();
-        }
+        // the records' lists, for the selected rows only, from whichever form the lists live in
+        GEVC(selected_lists_count(c, P, k, d_rows, 2 * n, mcnt, pcnt));
+        GEVC(scan_u32(c, mcnt, 2 * n, moff, nullptr));
+        if (c->track_intervals) GEVC(scan_u32(c, pcnt, 2 * n, poff, nullptr));
+        GEVC(selected_lists_fill(c, P, k, d_rows, 2 * n, moff, (u64*)(out + mo), poff, (gev_part*)(out + pa)));
         mo = al16(mo + L.mut_chr[k] * sizeof(u64)); pa = al16(pa + L.parts_chr[k] * sizeof(gev_part));
     }
     for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) {
@@ -3367,7 +3352,7 @@ int gev_export_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n, vo
         CvStatic& V = P.cv[p][k];
         const u32 cch = V.stride_w32 / 4;
         hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)ceil_div(2 * n * cch, 256)), dim3(256), 0, st, (uint4*)(out + co), (size_t)cch,
-                           (const uint4*)P.cvp[p][k][P.cur].p, (size_t)cch, c->d_map.as<u32>(), 2 * n, cch);
+                           (const uint4*)P.cvp[p][k][P.cur].p, (size_t)cch, d_rows, 2 * n, cch);
         co = al16(co + 2 * n * V.stride_w32 * sizeof(u32));
     }
     KCHECK();
@@ -3389,8 +3374,17 @@ int gev_remove_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n)
     // no row moves: only the logical order changes; stayers keep their order (src/Simulation.cpp:960-966)
     std::vector<u32> keep; keep.reserve(P.n_people - n);
     for (size_t i = 0; i < P.n_people; i++) if (!gone[i]) keep.push_back(P.logical.empty() ? (u32)i : P.logical[i]);
-    P.logical.swap(keep); P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); P.ids_ok = false; c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.logical.swap(keep);
+    membership_changed(c, P);
     return GEV_OK;
+}
+// exclusive offsets (2n + 1 of them, from `base`) of the haplotype rows of chromosome k in a record's counts; pass 0: mutations, 1: interval parts
+static std::vector<u32> record_offsets(const std::vector<u32>& counts, size_t n, int nchr, int k, int pass, u32 base = 0)
+{
+    std::vector<u32> off(2 * n + 1);
+    off[0] = base;
+    for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) off[2 * i + h + 1] = off[2 * i + h] + counts[((i * nchr + k) * 2 + h) * 2 + pass];
+    return off;
 }
 int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, size_t n)
 {
@@ -3450,8 +3444,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
             } else {
                 // the migrants travelled as lists: their rows are the founder mosaic their ancestry intervals describe (:1198-1211),
                 // assembled here from the founder panels of the parts' root populations
-                std::vector<u32> offp(2 * n + 1, 0);
-                for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) offp[2 * i + h + 1] = offp[2 * i + h] + counts[((i * nchr + k) * 2 + h) * 2 + 1];
+                const std::vector<u32> offp = record_offsets(counts, n, nchr, k, 1);
                 std::vector<PanelRef> pr(c->n_pop);
                 for (int q = 0; q < c->n_pop; q++) {
                     const ChrStatic& F = c->pop[q].cs[k];
@@ -3477,11 +3470,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
             // table rows written behind the existing ones; nothing of the residents is touched
             ChrState::LpState& lp = cs.lp;
             const bool track = c->track_intervals;
-            std::vector<u32> offm(2 * n + 1, 0), offp(2 * n + 1, 0);
-            for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) {
-                offm[2 * i + h + 1] = offm[2 * i + h] + counts[((i * nchr + k) * 2 + h) * 2];
-                offp[2 * i + h + 1] = offp[2 * i + h] + counts[((i * nchr + k) * 2 + h) * 2 + 1];
-            }
+            const std::vector<u32> offm = record_offsets(counts, n, nchr, k, 0), offp = record_offsets(counts, n, nchr, k, 1);
             GEVC(c->d_cnt.ensure((2 * n + 1) * sizeof(u32) * 2, st));
             u32* d_offm = c->d_cnt.as<u32>(); u32* d_offp = d_offm + (2 * n + 1);
             HIPC(hipMemcpyAsync(d_offm, offm.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
@@ -3510,9 +3499,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
         } else for (int pass = 0; pass < 2; pass++) {
             if (pass == 1 && !c->track_intervals) continue;
             size_t& total = pass == 0 ? cs.mut_total[P.cur] : cs.parts_total[P.cur];
-            std::vector<u32> off(2 * n + 1);
-            off[0] = (u32)total;
-            for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) off[2 * i + h + 1] = off[2 * i + h] + counts[((i * nchr + k) * 2 + h) * 2 + pass];
+            const std::vector<u32> off = record_offsets(counts, n, nchr, k, pass, (u32)total);
             const size_t add = off[2 * n] - off[0];
             DevBuf& doff = pass == 0 ? cs.moff[P.cur] : cs.poff[P.cur];
             // offsets of the appended rows: entries r_old .. r_old + 2n (entry r_old already equals the old total)
@@ -3543,7 +3530,8 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     if (rb_flag & 1u) return fail(GEV_EINVAL, "import_rows: Error: p.hap_index is not in range");
     if (P.logical.empty()) { P.logical.resize(P.n_people); for (size_t i = 0; i < P.n_people; i++) P.logical[i] = (u32)i; }
     for (size_t i = 0; i < n; i++) P.logical.push_back((u32)(n_old + i));
-    P.n_phys = n_new; P.n_people = P.logical.size(); P.layout_epoch++; P.drop_selection(); P.ids_ok = false; c->ad_cached_pop = c->ad_host_set_pop = -1;
+    P.n_phys = n_new;
+    membership_changed(c, P);
     return GEV_OK;
 }
 

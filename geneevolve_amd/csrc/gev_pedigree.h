@@ -41,15 +41,6 @@ __global__ void __launch_bounds__(256) k_ped_offspring(const int64_t* __restrict
     }
     cidx_out[i] = k;
 }
-// rows map[j] of src become rows j of dst, all fields (gev_migrate, a materialised row order)
-__global__ void __launch_bounds__(256) k_ped_gather(const int64_t* __restrict__ src, size_t sstride, const u32* __restrict__ map, size_t n,
-                                                    int64_t* __restrict__ dst, size_t dstride)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const size_t r = map[j];
-    for (int f = 0; f < PED_FIELDS; f++) dst[f * dstride + j] = src[f * sstride + r];
-}
 // [n][7] records in position order for the host (gev_download_pedigree)
 __global__ void __launch_bounds__(256) k_ped_records(const int64_t* __restrict__ src, size_t sstride, const u32* __restrict__ logical, size_t n,
                                                      int64_t* __restrict__ out)

@@ -167,11 +167,3 @@ __global__ void __launch_bounds__(256) k_ph_save_prev(const double* __restrict__
     rec[((size_t)p * 2 + 0) * n + i] = shift ? o[PH_P * n + i] + shift[p] : o[PH_P * n + i];
     rec[((size_t)p * 2 + 1) * n + i] = o[PH_F * n + i];
 }
-// rows map[j] of every plane of src (n_src rows each) become rows i0 + j of dst (n_dst rows each): the components follow the migrants
-__global__ void __launch_bounds__(256) k_ph_gather(const double* __restrict__ src, size_t n_src, const u32* __restrict__ map, size_t m, double* __restrict__ dst, size_t n_dst,
-                                                   size_t i0)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= m) return;
-    dst[(size_t)blockIdx.y * n_dst + i0 + j] = src[(size_t)blockIdx.y * n_src + map[j]];
-}

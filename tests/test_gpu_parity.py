@@ -2050,3 +2050,176 @@ def test_device_couples_do_not_outlive_a_change_of_rows(gpu_lib, oracle_lib, cha
     g.close(); o.close()
     for free in bufs:
         free()
+
+
+def _record_sexes(ctx, pop, nchr, on_device):
+    """Human::sex of everyone in the population, read out of an export record of all of them (the library's record has the bytes
+    behind its counts header, the oracle's private record one word per individual in front of that individual's lists)"""
+    n = ctx.pop_size(pop)
+    who = np.arange(n, dtype=np.uint64)
+    nb = ctx.export_size(pop, who)
+    if on_device:
+        dev, free = _device_buffer(nb)
+        ctx.export_rows(pop, who, dev, nb)
+        sex = _read_device_u32(dev + ((n * nchr * 16 + 15) & ~15), -(-n // 4)).view(np.uint8)[:n].copy()
+        free()
+        return sex
+    b = np.zeros(nb // 8, dtype=np.uint64)
+    ctx.export_rows(pop, who, b.ctypes.data, nb)
+    q, sex = 1, []
+    for _ in range(int(b[0])):
+        sex.append(int(b[q])); q += 1
+        for _ in range(2 * nchr):
+            n_parts = int(b[q]); q += 1
+            for _ in range(n_parts):
+                q += 5 + int(b[q + 4])
+    return np.array(sex, dtype=np.uint8)
+
+
+@pytest.mark.parametrize("values", ["order_pending", "recomputed"])
+def test_migration_behind_an_import_moves_every_row_and_value(gpu_lib, oracle_lib, values):
+    """Three populations of 12, 9 and 7, chromosomes of 130 and 64 loci, dense state with interval and pedigree tracking, driven call
+    for call with the oracle: two generations (the lists live as pieces), two individuals of population 1 imported into population 0
+    (pieces branch, a pending row order), a migration in which population 0 receives segments of 2, 1 and 3 migrants from
+    populations 1, 2 and 1 behind its stayers, population 1 receives from 0 and population 2 nobody, another import (CSR branch) and a
+    generation on top.  Behind the migration, the second import and the generation: sizes, sexes, lists, genotype rows, CV rows and
+    A/D of every population equal the oracle's.  The pedigree ids, phenotype components, phenotypes and selection values behind the
+    migration equal the ones in front of it gathered by the move list (stayers in their order, then migrants in move order: the
+    reference's ras_do_migration), a value being there where every contributing population had it.
+
+    order_pending: population 0 goes into the migration with the import's row order pending; its ids, phenotypes and selection values
+    are restored without touching that order (gev_upload_pedigree, gev_set_ad + gev_scale_ad_compute_gef, gev_compute_selection), its
+    components cannot be (gev_generation_phenotypes puts the rows in order first), so populations 0 and 1 have none behind the
+    migration.  recomputed: gev_generation_phenotypes restores everything in population 0 (and materialises its order), so every
+    value of every population is compared."""
+    sizes, nchr, Ls, n_cv = [12, 9, 7], 2, [130, 64], [5, 3]
+    rs = np.random.RandomState(77)
+    g = gpu_lib.create(3, nchr, 1); o = oracle_lib.create(3, nchr, 1)
+    g.set_dense_state(True); g.set_track_intervals(True)
+    R, step = 61, 1000
+    bp = (500 + step * np.arange(R)).astype(np.uint64)
+    prob, rate = np.r_[0.0, np.full(R - 1, 0.02)], np.r_[0.0, np.full(R - 1, 0.1)]       # ~6 new mutations per gamete and generation
+    for c in range(nchr):
+        pos = np.sort(rs.choice(np.arange(600, 60000), Ls[c], replace=False)).astype(np.uint64)
+        cvbp = rs.choice(np.arange(600, 60000, 7), n_cv[c], replace=False).astype(np.uint64)
+        a, d = rs.randn(n_cv[c]), rs.randn(n_cv[c])
+        for p in range(3):
+            for ctx in (g, o):
+                ctx.set_rmap(p, c, bp, prob, step); ctx.set_mutmap(p, c, bp, rate); ctx.set_snps(p, c, pos)
+                ctx.set_cvs(p, 0, c, cvbp, a, d, 0.0)
+            g.synth_founders(p, c, 2 * sizes[p], 100 + 10 * p + c); o.upload_founders(p, c, synth_packed(100 + 10 * p + c, 2 * sizes[p], Ls[c]), Ls[c])
+            g.synth_cv_founders(p, 0, c, 2 * sizes[p], 200 + 10 * p + c); o.upload_cv_founders(p, 0, c, synth_packed(200 + 10 * p + c, 2 * sizes[p], n_cv[c]), n_cv[c])
+    sg, so = Simulation(g, 91, nchr, True, device_pedigree=True), Simulation(o, 91, nchr, True)
+    for p in range(3):
+        sg.ras_initial_human_gen0(p, sizes[p]); so.ras_initial_human_gen0(p, sizes[p])
+    bufs = []
+    scheme = [(0.5, 0.0, 0.0, 0.4, 0.0, 1.0)]                    # va, vd, vc, ve, vf, beta: no couple or parent enters a phenotype
+
+    def select(p, gen):
+        return g.compute_selection(p, gen, "logit", 0.2, 0.8, [0.5], [1.0])
+
+    def phenotypes(p, gen):                                      # the library's side only: the oracle's seed stream skips the draws
+        sg.generation_phenotypes(p, gen, scheme); sg.phenotypes_result(p)
+        so.glob.x = sg.glob.x
+        select(p, gen)
+
+    def generation(gen):
+        for p in range(3):
+            npp = g.pop_size(p)
+            sg.random_mate_device(p, None, npp); so.random_mate_device(p, None, npp)
+            assert np.array_equal(sg.couples[p], so.couples[p]), f"couples gen {gen} pop {p}"
+            assert np.array_equal(sg.reproduce(p, gen), so.reproduce(p, gen)), f"sex gen {gen} pop {p}"
+
+    def copy_in(src, dst, who, gone):
+        nb = g.export_size(src, who)
+        dev, free = _device_buffer(nb); bufs.append(free)
+        g.export_rows(src, who, dev, nb)
+        ob = o.export_size(src, who); host = np.zeros(-(-ob // 8), dtype=np.uint64)
+        o.export_rows(src, who, host.ctypes.data, ob)
+        g.remove_rows(dst, gone); o.remove_rows(dst, gone)
+        g.import_rows(dst, dev, nb, len(who)); o.import_rows(dst, host.ctypes.data, ob, len(who))
+
+    def compare(what):
+        for p in range(3):
+            assert g.pop_size(p) == o.pop_size(p), f"size of pop {p} {what}"
+            assert np.array_equal(_record_sexes(g, p, nchr, True), _record_sexes(o, p, nchr, False)), f"sexes of pop {p} {what}"
+            for x, y in zip(g.compute_ad(p), o.compute_ad(p)):
+                assert helpers.bits_equal(x, y), f"A/D of pop {p} {what}"
+            for k in range(nchr):
+                pg, og = g.download_intervals(p, k); po, oo = o.download_intervals(p, k)
+                assert np.array_equal(og, oo) and np.array_equal(pg, po), f"interval lists pop {p} chr {k} {what}"
+                mg, mog = g.download_mutations(p, k); mo, moo = o.download_mutations(p, k)
+                assert np.array_equal(mog, moo) and np.array_equal(mg, mo), f"mutation lists pop {p} chr {k} {what}"
+                assert np.all(np.diff(np.asarray(mog).astype(np.int64)) > 0) and np.all(np.diff(np.asarray(og).astype(np.int64)) > 0), f"an empty list in pop {p} chr {k} {what}"
+                assert np.array_equal(g.download_haps(p, k), o.download_haps(p, k)), f"genotype rows pop {p} chr {k} {what}"
+                assert np.array_equal(g.download_cv(p, 0, k), o.download_cv(p, 0, k)), f"CV rows pop {p} chr {k} {what}"
+
+    def there(call):                                             # a value the library reports as not available (GEV_ESTATE) -> None
+        try:
+            return call()
+        except capi.GevError as e:
+            assert e.code == -2, e
+            return None
+
+    def read_values(p, behind):
+        """by individual (axis 0): ids [n][7], components [n][7], phenotypes [n], selection values [n][3]"""
+        v = {"ids": there(lambda: g.download_pedigree(p))}
+        comp = there(lambda: g.download_phenotypes(p, 0))
+        v["comp"] = None if comp is None else np.stack([comp[name] for name in capi.PHENOTYPE_COMPONENTS], axis=1)
+        raw = lambda: g.compute_selection(p, 2, "none", 0, 0, [1.0], [1.0], want=("mating_value",))["mating_value"]    # 1.0 * phen: the kept phenotypes themselves
+        if behind:                                               # what the migration left, then the phenotypes under it
+            sel = there(lambda: g.download_selection(p)); v["phen"] = there(raw)
+        else:                                                    # the phenotypes, then the values the migration will find
+            v["phen"] = there(raw); sel = there(lambda: select(p, 2))
+        v["sel"] = None if sel is None else np.stack([sel[k] for k in ("mating_value", "selection_value", "selection_value_func")], axis=1)
+        return v
+
+    # 1. two generations: the lists live as pieces; every population has ids, components, phenotypes and selection values
+    for p in range(3):
+        phenotypes(p, 0)
+    for gen in (1, 2):
+        generation(gen)
+    for p in range(3):
+        phenotypes(p, 2)
+    ids = [g.download_pedigree(p) for p in range(3)]
+    # 2. two individuals of population 1 into population 0 (two of its own leave): pieces branch, a pending order, its values dropped
+    who, gone0 = [3, 7], [1, 8]
+    copy_in(1, 0, who, gone0)
+    assert there(lambda: g.download_pedigree(0)) is None and there(lambda: g.download_selection(0)) is None
+    g.upload_pedigree(0, np.concatenate([np.delete(ids[0], gone0, axis=0), ids[1][who]]))
+    if values == "order_pending":
+        g.set_ad(0, rs.randn(sizes[0], 1), rs.randn(sizes[0], 1))
+        g.scale_ad_compute_gef(0, 0, 2, 4711, 0.5, 0.0, 0.4, 0.0, 1.0, 1.0, 0.0)
+        select(0, 2)
+    else:
+        phenotypes(0, 2)
+    # 3. the migration
+    moves = [(1, 2, 0), (1, 5, 0), (2, 4, 0), (1, 0, 0), (1, 6, 0), (1, 8, 0), (0, 3, 1), (0, 9, 1)]
+    before = [read_values(p, False) for p in range(3)]
+    g.migrate(moves); o.migrate(moves)
+    after = [read_values(p, True) for p in range(3)]
+    for d in range(3):
+        stay = np.setdiff1d(np.arange(sizes[d]), [pos for sp, pos, dp in moves if sp == d])
+        src = [(d, stay)] + [(sp, np.array([pos])) for sp, pos, dp in moves if dp == d]
+        for key in ("ids", "comp", "phen", "sel"):
+            if any(before[sp][key] is None for sp, _ in src):
+                assert after[d][key] is None, f"{key} of pop {d} without a source"
+                continue
+            want = np.concatenate([before[sp][key][idx] for sp, idx in src])
+            assert after[d][key] is not None, f"{key} of pop {d} did not follow the individuals"
+            same = np.array_equal(after[d][key], want) if key == "ids" else helpers.bits_equal(after[d][key], want)
+            assert same, f"{key} of pop {d} behind the migration"
+    missing = sorted((d, key) for d in range(3) for key in after[d] if after[d][key] is None)
+    assert missing == ([(0, "comp"), (1, "comp")] if values == "order_pending" else []), missing
+    assert [g.pop_size(p) for p in range(3)] == [16, 6, 6]
+    compare("behind the migration")
+    # 4. another import straight away: the lists are in CSR form now
+    copy_in(0, 2, [13, 15], [0, 3])
+    g.upload_pedigree(2, np.tile(np.arange(6, dtype=np.int64)[:, None], (1, 7)))
+    compare("behind the second import")
+    # 5. one more generation
+    generation(3)
+    compare("a generation later")
+    g.close(); o.close()
+    for free in bufs:
+        free()
