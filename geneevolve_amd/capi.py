@@ -96,6 +96,7 @@ ABI_SYMBOLS = [
     "set_track_pedigree", "download_pedigree", "upload_pedigree",
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "format_info_text", "dbg_format_g", "dbg_format_g_host",
+    "set_founder_names", "format_interval_text", "dbg_format_interval_text_host",
     "dbg_verify_planes", "dbg_output_chunk", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
@@ -154,6 +155,14 @@ def unpack_rows(words, L):
     return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little")[:, :L]
 
 
+def pack_names(names):
+    """list of str / bytes -> (uint8 arena, uint32 offsets [n + 1]) as gev_set_founder_names takes them"""
+    b = [x if isinstance(x, bytes) else str(x).encode() for x in names]
+    offs = np.zeros(len(b) + 1, dtype=np.uint32)
+    offs[1:] = np.cumsum([len(x) for x in b], dtype=np.uint64)
+    return np.frombuffer(b"".join(b) + b"\0", dtype=np.uint8).copy(), offs
+
+
 class GevLibrary:
     def __init__(self, path=DEFAULT_LIB, prefix="gev_"):
         if not os.path.exists(path):
@@ -199,6 +208,35 @@ class GevLibrary:
         rc, out, n = _format_g(self._f("dbg_format_g_host"), None, x)
         self.check(rc)
         return out, n
+
+
+    def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
+        """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
+        parts / hap_offsets: as download_intervals returns them; ids: Human::ID of every individual; names: one list of founder
+        names per root population.  out_bytes: the buffer's size (None: sized by a size query first) -> bytes"""
+        parts = _arr(parts, PART_DTYPE); off = _arr(hap_offsets, np.uint64); ids = _arr(ids, np.int64)
+        if n_ind is None:
+            n_ind = len(ids) - ind_begin
+        packed = [pack_names(x) for x in names]
+        npop = len(packed)
+        nb_ = (C.c_void_p * max(npop, 1))(*[p[0].ctypes.data for p in packed]); no_ = (C.c_void_p * max(npop, 1))(*[p[1].ctypes.data for p in packed])
+        nn = (C.c_size_t * max(npop, 1))(*[len(p[1]) - 1 for p in packed])
+        f = self._f("dbg_format_interval_text_host")
+        nb = C.c_size_t()
+        o, i = off[2 * ind_begin:], ids[ind_begin:]
+
+        def call(buf, size):
+            return f(_p(parts), C.c_void_p(o.ctypes.data) if len(o) else None, C.c_size_t(n_ind), C.c_void_p(i.ctypes.data) if len(i) else None, C.c_int(chr_label),
+                     nb_, no_, nn, C.c_int(npop), C.c_int(1 if header else 0), buf, C.c_size_t(size), C.byref(nb))
+        if out_bytes is None:
+            self.check(call(None, 0))
+            out_bytes = nb.value
+        buf = np.empty(max(out_bytes, 1), dtype=np.uint8)
+        self.last_bytes_written = None
+        rc = call(_p(buf), out_bytes)
+        self.last_bytes_written = nb.value
+        self.check(rc)
+        return buf[:nb.value].tobytes()
 
 
 class GevContext:
@@ -506,6 +544,37 @@ class GevContext:
             n_ind = self.pop_size(pop) - ind_begin
         nb = C.c_size_t()
         self._call_new("format_info_text", C.c_int(pop), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), None, C.c_size_t(0), C.byref(nb))
+        return nb.value
+
+    def set_founder_names(self, root_pop, names):
+        """the founder individuals' names (the .indv file) of a root population, for format_interval_text"""
+        arena, offs = pack_names(names)
+        self._call_new("set_founder_names", C.c_int(root_pop), _p(arena), _p(offs), C.c_size_t(len(offs) - 1))
+
+    def format_interval_text(self, pop, chr, chr_label, ind_begin=0, n_ind=None, header=True, ids=None):
+        """bytes of the reference's .int file (Simulation::ras_write_hap_to_interval_format) for individuals [ind_begin, ind_begin +
+        n_ind) of (pop, chr), formatted on the device.  ids: Human::ID of those n_ind individuals, None = the ids the library tracks"""
+        if n_ind is None:
+            n_ind = self.pop_size(pop) - ind_begin
+        if ids is not None:
+            ids = _arr(ids, np.int64)
+            if len(ids) != n_ind:
+                raise ValueError("format_interval_text: one id per individual of the range expected")
+        size = self.interval_text_size(pop, chr, chr_label, ind_begin, n_ind, header, ids)
+        buf = np.empty(max(size, 1), dtype=np.uint8)
+        nb = C.c_size_t()
+        self._call_new("format_interval_text", C.c_int(pop), C.c_int(chr), C.c_int(chr_label), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), _p(ids),
+                       _p(buf), C.c_size_t(size), C.byref(nb))
+        return buf[:nb.value].tobytes()
+
+    def interval_text_size(self, pop, chr, chr_label, ind_begin=0, n_ind=None, header=True, ids=None):
+        """the exact size format_interval_text() would return (length pass only)"""
+        if n_ind is None:
+            n_ind = self.pop_size(pop) - ind_begin
+        ids = None if ids is None else _arr(ids, np.int64)
+        nb = C.c_size_t()
+        self._call_new("format_interval_text", C.c_int(pop), C.c_int(chr), C.c_int(chr_label), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), _p(ids),
+                       None, C.c_size_t(0), C.byref(nb))
         return nb.value
 
     def dbg_format_g(self, x):

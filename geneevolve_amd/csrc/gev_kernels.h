@@ -27,6 +27,7 @@
 #include "../../include/geneevolve_amd.h"
 #include "rng_device.h"
 #include "gev_fmt_g.h"
+#include "gev_fmt_int.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;

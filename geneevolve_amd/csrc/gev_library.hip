@@ -288,6 +288,16 @@ struct gev_ctx {
     DevBuf d_cvdone;
     // gev_format_info_text / gev_dbg_format_g (gev_fmt_g.h): created by the first call, nothing before it
     struct FmtState { DevBuf tables, lens, bsum, boff, x, cnt; bool ready = false; } fm;
+    // gev_format_interval_text (gev_fmt_int.h, k_int_rows).  host[p]: the founder names of root population p as gev_set_founder_names
+    // left them; everything on the device (the names' arenas and offset tables, d_names = IntNames[n_pop]) is created by the first
+    // formatting call, nothing before it
+    struct IntState {
+        struct Names { std::vector<unsigned char> bytes; std::vector<u32> offs; bool set = false; };
+        std::vector<Names> host;
+        std::vector<DevBuf> d_bytes, d_offs;
+        DevBuf d_names, lens, bsum, boff, flag, ids;
+        bool uploaded = false;
+    } iv;
     // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob
     struct PhenoState {
         DevBuf res /* result words, then {mean, var} pairs: e, the components, raw A and D */, starts, partial, eraw, cval, streams, tasks, blk, globblk, shift;
@@ -4386,6 +4396,151 @@ int gev_dbg_format_g_host(const double* x, size_t n, char* out, unsigned long lo
         cnt += ex;
     }
     if (n_exact) *n_exact = cnt;
+    return GEV_OK;
+}
+// ---- Simulation::ras_write_hap_to_interval_format on the device (gev_fmt_int.h, k_int_rows) ------------------
+int gev_set_founder_names(gev_ctx* c, int root_pop, const char* bytes, const uint32_t* offsets, size_t n_individuals)
+{
+    if (!c) return fail(GEV_EINVAL, "null context");
+    if (root_pop < 0 || root_pop >= c->n_pop) return fail(GEV_EINVAL, "set_founder_names: population index %d out of range", root_pop);
+    if (!offsets || (!bytes && offsets[n_individuals] != offsets[0])) return fail(GEV_EINVAL, "set_founder_names: null argument");
+    if (n_individuals >= 0xffffffffull) return fail(GEV_EINVAL, "set_founder_names: %zu names", n_individuals);
+    for (size_t i = 0; i < n_individuals; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(GEV_EINVAL, "set_founder_names: the offsets decrease at name %zu", i);
+        if (offsets[i + 1] - offsets[i] > GEV_INT_NAME_MAX)
+            return fail(GEV_EUNSUPPORTED, "set_founder_names: name %zu of population %d has %u bytes: at most %d fit a staged line", i, root_pop, offsets[i + 1] - offsets[i], GEV_INT_NAME_MAX);
+    }
+    gev_ctx::IntState& I = c->iv;
+    if (I.host.size() != (size_t)c->n_pop) I.host.resize(c->n_pop);
+    gev_ctx::IntState::Names& N = I.host[root_pop];
+    N.offs.resize(n_individuals + 1);
+    for (size_t i = 0; i <= n_individuals; i++) N.offs[i] = offsets[i] - offsets[0];
+    N.bytes.clear();
+    if (bytes) N.bytes.assign((const unsigned char*)bytes + offsets[0], (const unsigned char*)bytes + offsets[n_individuals]);
+    N.set = true; I.uploaded = false;
+    return GEV_OK;
+}
+static int int_names_ready(gev_ctx* c)
+{
+    gev_ctx::IntState& I = c->iv;
+    if (I.uploaded) return GEV_OK;
+    if (I.d_bytes.size() != (size_t)c->n_pop) { I.d_bytes.resize(c->n_pop); I.d_offs.resize(c->n_pop); }
+    std::vector<IntNames> tab(c->n_pop);
+    for (int p = 0; p < c->n_pop; p++) {
+        const gev_ctx::IntState::Names& N = I.host[p];
+        GEVC(h2d(c, I.d_bytes[p], N.bytes.data(), N.bytes.size())); GEVC(h2d(c, I.d_offs[p], N.offs.data(), N.offs.size() * sizeof(u32)));
+        tab[p] = IntNames{I.d_bytes[p].as<unsigned char>(), I.d_offs[p].as<u32>(), (u64)(N.offs.size() - 1)};
+    }
+    GEVC(h2d(c, I.d_names, tab.data(), tab.size() * sizeof(IntNames)));
+    I.uploaded = true;
+    return GEV_OK;
+}
+int gev_format_interval_text(gev_ctx* c, int pop, int chr, int chr_label, size_t ind_begin, size_t n_ind, int with_header, const int64_t* ids,
+                             char* out, size_t out_bytes, size_t* bytes_written)
+{
+    const char* who = "format_interval_text";
+    if (!bytes_written) return fail(GEV_EINVAL, "%s: null bytes_written", who);
+    *bytes_written = 0;
+    GEVC(output_begin(c, pop, chr, who, false));
+    if (!c->track_intervals) return fail(GEV_ESTATE, "%s: interval tracking is disabled (gev_set_track_intervals)", who);
+    gev_ctx::IntState& I = c->iv;
+    for (int p = 0; p < c->n_pop; p++)
+        if ((size_t)p >= I.host.size() || !I.host[p].set) return fail(GEV_ESTATE, "%s: the founder names of root population %d were never set (gev_set_founder_names)", who, p);
+    PopState& P = c->pop[pop]; ChrState& cs = P.st[chr];
+    if (!ids) {
+        if (!c->track_pedigree) return fail(GEV_ESTATE, "%s: ids == NULL and the context does not track pedigree ids (gev_set_track_pedigree)", who);
+        if (!P.ids_ok) return fail(GEV_ESTATE, "%s: ids == NULL and population %d's pedigree ids were dropped when its rows changed (gev_upload_pedigree restores them)", who, pop);
+    }
+    GEVC(ensure_csr(c, pop));
+    const size_t n = P.n_people;
+    if (ind_begin > n || n_ind > n - ind_begin) return fail(GEV_EINVAL, "%s: individuals [%zu,%zu) beyond n_people=%zu", who, ind_begin, ind_begin + n_ind, n);
+    const size_t hdr = with_header ? strlen(GEV_INT_HEADER) : 0;
+    hipStream_t st = c->stream;
+    const u32* poff = cs.poff[P.cur].as<u32>(); const gev_part* parts = cs.parts[P.cur].as<gev_part>();
+    const size_t row0 = 2 * ind_begin, row1 = 2 * (ind_begin + n_ind);
+    u32 pr[2] = {0, 0};
+    if (n_ind) {
+        HIPC(hipMemcpyAsync(&pr[0], poff + row0, sizeof(u32), hipMemcpyDeviceToHost, st)); HIPC(hipMemcpyAsync(&pr[1], poff + row1, sizeof(u32), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    const size_t np = pr[1] - pr[0], nb = ceil_div(np, INT_PARTS);
+    u64 total = 0;
+    const int64_t* d_ids = nullptr; size_t id_ind0 = 0;
+    if (np) {
+        GEVC(int_names_ready(c));
+        if (ids) { GEVC(h2d(c, I.ids, ids, n_ind * sizeof(int64_t))); d_ids = I.ids.as<int64_t>(); id_ind0 = ind_begin; }
+        else d_ids = P.d_ids[P.ibuf].as<int64_t>() + PED_ID * P.ids_stride[P.ibuf];
+        GEVC(I.lens.ensure(np, st)); GEVC(I.bsum.ensure(nb * sizeof(u32), st)); GEVC(I.boff.ensure((nb + 1) * sizeof(u64), st)); GEVC(I.flag.ensure(sizeof(u32), st));
+        HIPC(hipMemsetAsync(I.flag.p, 0, sizeof(u32), st));
+        hipLaunchKernelGGL(k_int_rows<false>, dim3((unsigned)nb), dim3(INT_PARTS), INT_SCAN_BYTES, st, poff, parts, row0, row1, pr[0], pr[1], d_ids, id_ind0, chr_label,
+                           (const IntNames*)I.d_names.as<IntNames>(), c->n_pop, 0u, I.lens.as<uint8_t>(), I.bsum.as<u32>(), (const u64*)nullptr, (u64)0, (char*)nullptr, I.flag.as<u32>());
+        hipLaunchKernelGGL(k_info_scan64, dim3(1), dim3(256), 0, st, (const u32*)I.bsum.as<u32>(), nb, I.boff.as<u64>());
+        KCHECK();
+        u32 flag = 0;
+        HIPC(hipMemcpyAsync(&total, I.boff.as<u64>() + nb, sizeof total, hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(&flag, I.flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (flag) return fail(GEV_EINVAL, "%s: a part of population %d names a founder (hap_index / 2) beyond the names of its root population", who, pop);
+    }
+    const size_t need = hdr + (size_t)total;
+    *bytes_written = need;
+    if (!out) return GEV_OK;
+    if (out_bytes < need) return fail(GEV_EINVAL, "%s: buffer of %zu bytes, %zu needed", who, out_bytes, need);
+    memcpy(out, GEV_INT_HEADER, hdr);
+    if (!total) return GEV_OK;
+    // the text leaves in runs of blocks whose largest possible lines stay within 256 MB of staging
+    const size_t chunk = output_chunk(c, 256u << 20, (size_t)INT_PARTS * GEV_INT_LINE_MAX);
+    std::vector<u64> boff;
+    if (nb > chunk) {
+        boff.resize(nb + 1);
+        HIPC(hipMemcpyAsync(boff.data(), I.boff.p, (nb + 1) * sizeof(u64), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+    }
+    for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+        const size_t b1 = std::min(nb, b0 + chunk);
+        const u64 o0 = boff.empty() ? 0 : boff[b0], o1 = boff.empty() ? total : boff[b1];
+        if (o1 == o0) continue;
+        GEVC(copy_out_text(c, (size_t)(o1 - o0), out + hdr + o0, [&] {
+            hipLaunchKernelGGL(k_int_rows<true>, dim3((unsigned)(b1 - b0)), dim3(INT_PARTS), INT_SCAN_BYTES + INT_LDS_BYTES, st, poff, parts, row0, row1, pr[0], pr[1], d_ids, id_ind0, chr_label,
+                               (const IntNames*)I.d_names.as<IntNames>(), c->n_pop, (u32)b0, I.lens.as<uint8_t>(), (u32*)nullptr, (const u64*)I.boff.as<u64>(), o0, c->d_text.as<char>(),
+                               (u32*)nullptr);
+        }));
+    }
+    return GEV_OK;
+}
+// the same header compiled for the host: no device, no context
+int gev_dbg_format_interval_text_host(const gev_part* parts, const uint64_t* hap_offsets, size_t n_ind, const int64_t* ids, int chr_label,
+                                      const char* const* name_bytes, const uint32_t* const* name_offsets, const size_t* n_names, int n_root_pop,
+                                      int with_header, char* out, size_t out_bytes, size_t* bytes_written)
+{
+    const char* who = "dbg_format_interval_text_host";
+    if (!bytes_written) return fail(GEV_EINVAL, "%s: null bytes_written", who);
+    *bytes_written = 0;
+    if (n_ind && (!hap_offsets || !ids)) return fail(GEV_EINVAL, "%s: null argument", who);
+    const size_t hdr = with_header ? strlen(GEV_INT_HEADER) : 0;
+    for (int pass = 0; pass < 2; pass++) {
+        size_t at = hdr;
+        for (size_t r = 0; r < 2 * n_ind; r++)
+            for (u64 q = hap_offsets[r]; q < hap_offsets[r + 1]; q++) {
+                if (!parts) return fail(GEV_EINVAL, "%s: null parts", who);
+                const gev_part& p = parts[q];
+                const int rp = p.root_population;
+                if (rp < 0 || rp >= n_root_pop || !name_offsets || !name_offsets[rp] || !n_names) return fail(GEV_EINVAL, "%s: root population %d has no names", who, rp);
+                const u64 k = p.hap_index >> 1;
+                if (k >= n_names[rp]) return fail(GEV_EINVAL, "%s: a part names founder %llu beyond the %zu names of root population %d", who, (unsigned long long)k, n_names[rp], rp);
+                const u32 o0 = name_offsets[rp][k], nlen = name_offsets[rp][k + 1] - o0;
+                if (nlen > GEV_INT_NAME_MAX) return fail(GEV_EUNSUPPORTED, "%s: a name of %u bytes", who, nlen);
+                const GevIntLine l{(u64)(ids[r >> 1] + 1), p.st, p.en, p.hap_index + 1, (u32)(rp + 1), (u32)(r & 1u), chr_label};
+                if (pass) { GevIntMemSink s{out + at}; gev_int_line(s, 0, l, (const unsigned char*)name_bytes[rp] + o0, nlen); }
+                at += gev_int_line_len(l, nlen);
+            }
+        if (!pass) {
+            *bytes_written = at;
+            if (!out) return GEV_OK;
+            if (out_bytes < at) return fail(GEV_EINVAL, "%s: buffer of %zu bytes, %zu needed", who, out_bytes, at);
+            memcpy(out, GEV_INT_HEADER, hdr);
+        }
+    }
     return GEV_OK;
 }
 int gev_set_track_intervals(gev_ctx* c, int on)

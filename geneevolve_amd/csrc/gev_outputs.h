@@ -218,3 +218,82 @@ __global__ void __launch_bounds__(256) k_format_bed(const u64* __restrict__ snpm
     }
     out[q] = (uint8_t)o;
 }
+
+// ------------------------------------------------------------------------------------------
+// Simulation::ras_write_hap_to_interval_format (src/Simulation.cpp:1582-1639): one text line per PART of the CSR interval lists, in
+// list order (gev_fmt_int.h has the line).  Lists lengthen with the run's age and differ from row to row, so the work is cut by part:
+// a block takes INT_PARTS consecutive parts of the request [p0, p1) = the lists of haplotype rows [row0, row1), one thread each.  The
+// rows of the block's first and last part are found by bisection in the offsets (uniform over the block), every thread then bisects
+// between the two.  k_int_rows<false> measures the lines (lens: one byte each, bsum: the block's bytes), k_info_scan64 turns the
+// block sums into 64-bit byte offsets, k_int_rows<true> formats again into LDS at the lines' offsets inside the block and stores the
+// block's contiguous byte range 16 bytes at a time, as k_info_rows does.
+// ------------------------------------------------------------------------------------------
+#define INT_PARTS 256                        // parts per block, one thread each
+#define INT_SCAN_BYTES 32u                   // the block scan's scratch sits in the dynamic region too, so that the staging area stays 16-byte aligned
+#define INT_LDS_BYTES (16u + INT_PARTS * GEV_INT_LINE_MAX)
+static_assert(INT_SCAN_BYTES + INT_LDS_BYTES <= 65536, "a block's lines are staged in 64 KiB");
+static_assert(GEV_INT_LINE_MAX <= 255, "a line's length is kept in one byte");
+struct IntNames { const unsigned char* bytes; const u32* offs; u64 n; };      // founder names of one root population: name i = bytes[offs[i], offs[i+1])
+struct IntLdsSink {                          // bytes beyond `cap` are dropped, never written
+    unsigned char* lds; u32 cap;
+    __device__ __forceinline__ void put(u32 pos, u32 c) { if (pos < cap) lds[pos] = (unsigned char)c; }
+};
+// the last row r of [lo, hi] with poff[r] <= q (rows without parts share their offset with the next one)
+__device__ __forceinline__ size_t int_row_of(const u32* __restrict__ poff, u64 q, size_t lo, size_t hi)
+{
+    while (lo < hi) { const size_t mid = (lo + hi + 1) >> 1; if ((u64)poff[mid] <= q) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+// blocks [blk0, blk0 + gridDim.x) of the request.  ids[(row >> 1) - id_ind0] = Human::ID of the row's individual.
+// WRITE = false: lens[part - p0], bsum[block]; *flag |= 1 for a part whose root population or founder has no name (length 0).
+// WRITE = true : boff[block] - out_base = offset of the block's first byte in `out` (16-byte aligned).
+// Dynamic LDS: INT_SCAN_BYTES, and with WRITE INT_LDS_BYTES behind them
+template <bool WRITE>
+__global__ void __launch_bounds__(INT_PARTS) k_int_rows(const u32* __restrict__ poff, const gev_part* __restrict__ parts, size_t row0, size_t row1, u32 p0, u32 p1,
+                                                        const int64_t* __restrict__ ids, size_t id_ind0, int chr_label, const IntNames* __restrict__ names, int n_pop, u32 blk0,
+                                                        uint8_t* __restrict__ lens, u32* __restrict__ bsum, const u64* __restrict__ boff, u64 out_base, char* __restrict__ out,
+                                                        u32* __restrict__ flag)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char int_dyn[];
+    u32* scan_lds = reinterpret_cast<u32*>(int_dyn);
+    unsigned char* int_lds = int_dyn + INT_SCAN_BYTES;
+    const u32 t = threadIdx.x;
+    const size_t blk = (size_t)blk0 + blockIdx.x;
+    const u64 qa = (u64)p0 + (u64)blk * INT_PARTS, q = qa + t;                 // (the grid never reaches beyond p1: qa < p1)
+    const u64 qb = qa + INT_PARTS - 1 < (u64)p1 - 1 ? qa + INT_PARTS - 1 : (u64)p1 - 1;
+    const bool live = q < (u64)p1;
+    u32 len = 0, nlen = 0;
+    GevIntLine l; const unsigned char* name = nullptr;
+    if (live) {
+        const size_t ra = int_row_of(poff, qa, row0, row1 - 1), rb = int_row_of(poff, qb, ra, row1 - 1);
+        const size_t r = int_row_of(poff, q, ra, rb);
+        const gev_part p = parts[q];
+        const int rp = p.root_population;
+        const u64 k = p.hap_index >> 1;
+        if (rp < 0 || rp >= n_pop || k >= names[rp].n) { if (!WRITE) atomicOr(flag, 1u); }
+        else {
+            const u32 o0 = names[rp].offs[k];
+            name = names[rp].bytes + o0; nlen = names[rp].offs[k + 1] - o0;
+            l.id1 = (u64)(ids[(r >> 1) - id_ind0] + 1); l.st = p.st; l.en = p.en; l.hap1 = p.hap_index + 1; l.root1 = (u32)(rp + 1); l.ihap = (u32)(r & 1u); l.chr_label = chr_label;
+            len = WRITE ? (u32)lens[q - p0] : gev_int_line_len(l, nlen);
+        }
+    }
+    u32 total;
+    const u32 ex = block_exclusive_scan_256(len, scan_lds, total);
+    if (!WRITE) {
+        if (live) lens[q - p0] = (uint8_t)len;
+        if (t == 0) bsum[blk] = total;
+        return;
+    }
+    const u64 g0 = boff[blk] - out_base;
+    const u32 a = (u32)(g0 & 15u);
+    if (len) { IntLdsSink s{int_lds, INT_LDS_BYTES}; gev_int_line(s, a + ex, l, name, nlen); }
+    __syncthreads();
+    // the block's bytes sit at LDS [a, a + total) with a = g0 mod 16: LDS chunk k and the aligned 16 bytes of `out` at g0 - a + 16 k coincide
+    const u32 end = a + total < INT_LDS_BYTES ? a + total : INT_LDS_BYTES;
+    char* base = out + (g0 - a);
+    for (u32 lo = t * 16u; lo < end; lo += INT_PARTS * 16u) {
+        if (lo >= a && lo + 16u <= end) *reinterpret_cast<uint4*>(base + lo) = *reinterpret_cast<const uint4*>(int_lds + lo);
+        else for (u32 b = lo < a ? a : lo; b < lo + 16u && b < end; b++) base[b] = (char)int_lds[b];       // the two ragged ends of the block's range
+    }
+}

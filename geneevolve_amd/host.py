@@ -791,6 +791,17 @@ class Simulation:
                 f.write(txt)
         return txt
 
+    def write_interval(self, ipop, ichr, chr_label, path=None):
+        """Simulation::ras_write_hap_to_interval_format (src/Simulation.cpp:1582-1639) for one population and chromosome, formatted by
+        the library on the device (needs ctx.set_founder_names of every root population).  Human::ID comes from the host's pedigree
+        (track_pedigree) or, with device_pedigree, from the library's -> the file's bytes, written to `path` when given"""
+        ids = None if self.device_pedigree else self.ped[ipop].ID
+        txt = self.ctx.format_interval_text(ipop, ichr, chr_label, ids=ids)
+        if path is not None:
+            with open(path, "wb") as f:
+                f.write(txt)
+        return txt
+
     def ras_compute_AD(self, ipop, gen_num=0, per_chr=False):   # :2624
         return self.ctx.compute_ad(ipop, per_chr=per_chr)
 

@@ -392,6 +392,37 @@ int gev_format_info_text(gev_ctx*, int pop, size_t ind_begin, size_t n_ind, int 
 int gev_dbg_format_g(gev_ctx*, const double* x, size_t n, char* out, unsigned long long* n_exact);   /* on the device */
 int gev_dbg_format_g_host(const double* x, size_t n, char* out, unsigned long long* n_exact);        /* same header, host build, no device */
 
+/* ---- the .int interval file text on the device ----
+ * Simulation::ras_write_hap_to_interval_format (src/Simulation.cpp:1582-1639): after the header line
+ * "h_ID chr hap st en hap_index gen0_indv root_pop" one line per part, individuals in position order, chromatid 0 then 1, parts in list
+ * order (the row order of gev_download_intervals):
+ *     <ID+1> <chr_label> <ihap> <st> <en> <hap_index+1> <name>.<1|2> <root_population+1>
+ * every number a plain decimal (ID + 1 in the reference's unsigned arithmetic: ID = -1 prints 0), name = the .indv id of founder
+ * individual hap_index / 2 of the part's ROOT population, .1 for an even hap_index and .2 for an odd one (:3031-3033).  A line has at
+ * most 177 bytes.
+ * gev_set_founder_names: the founder individuals' names of a ROOT population (the .indv file): name i = bytes[offsets[i] ..
+ * offsets[i+1]), offsets has n_individuals + 1 entries.  Kept on the host until the first formatting call.  GEV_EUNSUPPORTED for a name
+ * longer than 64 bytes (a block of 256 lines is staged in 16 + 256 * 177 bytes of on-chip memory). */
+int gev_set_founder_names(gev_ctx*, int root_pop, const char* bytes, const uint32_t* offsets, size_t n_individuals);
+/* the .int file's bytes for individuals [ind_begin, ind_begin + n_ind) of (pop, chr); with_header != 0 puts the header line in front.
+ * out == NULL: only *bytes_written = exact size.  out_bytes too small: GEV_EINVAL, *bytes_written = size needed.  A range beyond
+ * n_people: GEV_EINVAL.  n_ind == 0: the header alone, or nothing.  Waits for the device.  Goes the way of gev_download_intervals
+ * (a pending order is materialised, the CSR lists are derived if need be), so it works after gev_migrate, after an import and on
+ * contexts without genotype planes.  Concatenating the texts of consecutive ranges, the header on the first only, gives the file.
+ * ids: Human::ID of the n_ind individuals (host memory), or NULL = the ID plane the library tracks (gev_set_track_pedigree).
+ * GEV_ESTATE, the message naming what is missing: interval tracking off; names of some root population of the context never set;
+ * ids == NULL without pedigree tracking or with the ids dropped.  GEV_EINVAL and no text: a part whose hap_index / 2 lies beyond its
+ * root population's names.  The device tables and buffers are created by the first call.  The text leaves the device in runs of
+ * blocks of 256 lines (gev_dbg_output_chunk caps the blocks of a run). */
+int gev_format_interval_text(gev_ctx*, int pop, int chr, int chr_label, size_t ind_begin, size_t n_ind, int with_header,
+                             const int64_t* ids, char* out, size_t out_bytes, size_t* bytes_written);
+/* the same header's host build from plain arrays, no device, no context: parts / hap_offsets as gev_download_intervals returns them
+ * (hap_offsets + 2 * i and ids + i give the text from individual i on), names of root population p = name_bytes[p], name_offsets[p]
+ * (n_names[p] + 1 entries).  Same size query and short-buffer convention; GEV_EINVAL for a part without a name. */
+int gev_dbg_format_interval_text_host(const gev_part* parts, const uint64_t* hap_offsets, size_t n_ind, const int64_t* ids, int chr_label,
+                                      const char* const* name_bytes, const uint32_t* const* name_offsets, const size_t* n_names, int n_root_pop,
+                                      int with_header, char* out, size_t out_bytes, size_t* bytes_written);
+
 /* ---- Simulation::assort_mate (src/Simulation.cpp:2167-2360), the reference's default mating mode -------------------------------
  * Forms the couples of the population's current generation on the device, bit for bit as the reference does (stable order among
  * equal mating values, as the host mirror geneevolve_amd/host.py:assort_mate; std::sort leaves it unspecified):

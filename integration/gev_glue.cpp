@@ -21,6 +21,10 @@
 #include "Simulation.h"          // the EDITED copy: class Simulation has `friend struct GevGlue;`
 #include "CommFunc.h"
 #include "geneevolve_amd.h"
+// The checker variant of this program is linked to the CPU oracle, which has no .int text writer: the two entry points are weak
+// references, absent there (--out_interval then formats on the host, write_interval_host) and always present in the library.
+#pragma weak gev_set_founder_names
+#pragma weak gev_format_interval_text
 
 struct GevGlue {
     static gev_ctx*& ctx() { static gev_ctx* g = nullptr; return g; }
@@ -77,8 +81,19 @@ struct GevGlue {
                 }
             }
         }
+        // the founders' names (.indv file or VCF header, :255-302): what the .int file prints as gen0_indv (:3031-3033)
+        if (!gev_set_founder_names || !gev_format_interval_text) names_on_device() = false;
+        for (int ipop = 0; ipop < n_pop && names_on_device(); ipop++) {
+            const std::vector<std::string>& id = S.population[ipop]._indv_id;
+            std::string bytes; std::vector<uint32_t> off(id.size() + 1, 0);
+            for (size_t i = 0; i < id.size(); i++) { bytes += id[i]; off[i + 1] = (uint32_t)bytes.size(); }
+            const int rc = gev_set_founder_names(ctx(), ipop, bytes.data(), off.data(), id.size());
+            if (rc == GEV_EUNSUPPORTED) names_on_device() = false;        // a name of more than 64 bytes: --out_interval formats on the host
+            else if (rc) return fail("gev_set_founder_names");
+        }
         return true;
     }
+    static bool& names_on_device() { static bool g = true; return g; }
 
     // end of Simulation::ras_initial_human_gen0 (:3000-3072): the reference has just built its gen-0 humans from `seed`
     static bool after_gen0(Simulation& S, int ipop, unsigned seed)
@@ -468,8 +483,45 @@ struct GevGlue {
         return true;
     }
 
-    // Simulation::ras_write_hap_to_interval_format (:1582-1633): the interval state lives in the library
+    // Simulation::ras_write_hap_to_interval_format (:1582-1639): the interval state lives in the library, which also writes the lines
+    // (gev_format_interval_text).  The text is taken in slices of individuals, each sized from the size query so that it stays under
+    // 256 MB; Human::ID comes from the host's records, the library does not track the pedigree for this program.
     static bool write_interval(Simulation& S, int gen_num)
+    {
+        if (!names_on_device()) return write_interval_host(S, gen_num);
+        const std::string sep = " ";
+        const size_t bound = (size_t)256 << 20;
+        const int n_chr = (int)S.population[0].h[0].chr.size();
+        std::vector<char> buf;
+        for (int ipop = 0; ipop < S._n_pop; ipop++) {
+            Population& P = S.population[ipop];
+            const size_t nind = P.h.size();
+            std::vector<int64_t> ids(nind);
+            for (size_t ih = 0; ih < nind; ih++) ids[ih] = (int64_t)P.h[ih].ID;
+            for (int ichr = 0; ichr < n_chr; ichr++) {
+                std::ofstream file_out((S._out_prefix + ".pop" + std::to_string(ipop + 1) + ".gen" + std::to_string(gen_num) + ".chr" + std::to_string(S._all_active_chrs[ichr]) + ".int").c_str());
+                file_out << "h_ID" << sep << "chr" << sep << "hap" << sep << "st" << sep << "en" << sep << "hap_index" << sep << "gen0_indv" << sep << "root_pop" << std::endl;
+                size_t step = nind;
+                for (size_t ih = 0; ih < nind;) {
+                    size_t n = std::min(step, nind - ih), need = 0;
+                    for (;;) {
+                        if (gev_format_interval_text(ctx(), ipop, ichr, S._all_active_chrs[ichr], ih, n, 0, ids.data() + ih, NULL, 0, &need)) return fail("gev_format_interval_text");
+                        if (need <= bound || n == 1) break;
+                        n = std::max<size_t>(1, (size_t)((double)n * (double)bound / (double)need * 0.9));      // fewer individuals, in proportion
+                    }
+                    step = n;
+                    if (buf.size() < need) buf.resize(need);
+                    if (gev_format_interval_text(ctx(), ipop, ichr, S._all_active_chrs[ichr], ih, n, 0, ids.data() + ih, buf.data(), buf.size(), &need)) return fail("gev_format_interval_text");
+                    file_out.write(buf.data(), (std::streamsize)need);
+                    ih += n;
+                }
+            }
+        }
+        return true;
+    }
+    // the same file formatted on the host from the downloaded lists: for founder names longer than the library stages (64 bytes), and
+    // for the checker variant without the library
+    static bool write_interval_host(Simulation& S, int gen_num)
     {
         const std::string sep = " ";
         const int n_chr = (int)S.population[0].h[0].chr.size();
