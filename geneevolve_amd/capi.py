@@ -97,7 +97,7 @@ ABI_SYMBOLS = [
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "format_info_text", "dbg_format_g", "dbg_format_g_host",
     "set_founder_names", "format_interval_text", "dbg_format_interval_text_host",
-    "dbg_verify_planes", "dbg_output_chunk", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
+    "dbg_verify_planes", "dbg_output_chunk", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
 ]
 
 
@@ -676,6 +676,12 @@ class GevContext:
         n = C.c_ulonglong()
         self._call("redo_count", C.byref(n))
         return n.value
+
+    def dbg_pool_stats(self, pop):
+        """-> (rebuilds of the free list of the population's segment unit pool, generations enqueued again because it ran out)"""
+        out = (C.c_ulonglong * 2)()
+        self._call_new("dbg_pool_stats", C.c_int(pop), out)
+        return int(out[0]), int(out[1])
 
     def compute_ad(self, pop, per_chr=True):
         n = self.pop_size(pop)

@@ -221,6 +221,7 @@ struct gev_ctx {
         bool pool_rebuild = false;                                                            // this attempt rebuilds the free list of the segment pool
         bool cv_count_fused = false;                                                          // k_stitch_small also counts the alleles per CV column (every grid <= 1024 columns)
         hipEvent_t ev_fork = nullptr, ev_aux = nullptr, ev_lists = nullptr, ev_forked = nullptr;   // joins of the attempt's side streams
+        hipEvent_t ev_recs = nullptr, ev_pool = nullptr;                                        // sampling records complete on S (for X); unit table, work list and their counters complete on X
         hipEvent_t ev_small_done = nullptr, ev_stitch_done = nullptr, t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_status = nullptr, ev_sampled = nullptr;   // the generation's status block (and A/D results) have arrived on the host
         bool timing_pending = false, stitch_pending = false;
         hipEvent_t tc[3] = {nullptr, nullptr, nullptr};   // GEV_TRACE_HOST: start of the attempt's main stream, A/D done, lists joined
@@ -250,6 +251,7 @@ struct gev_ctx {
     bool chain_valid = false; u32 chain_state = 0;           // glob_generator state the queued head start assumed for the next gev_generation_begin
     unsigned long long chain_hits = 0, chain_misses = 0;
     unsigned long long redo_count = 0;                       // generations that were enqueued again with larger buffers (gev_redo_count)
+    unsigned long long redo_pool_count = 0;                  // ... of which because the free list of the unit pool ran out (gev_dbg_pool_stats)
     void* h_stage = nullptr; size_t h_stage_bytes = 0;       // pinned host staging
     void* h_seeds = nullptr; size_t h_seeds_bytes = 0;       // pinned copy of the mutation seeds handed to gev_presample
     // pinned A/D result cache, two buffers: [(gen_counter + 1) & 1] holds the PUBLISHED generation's values, the generation in flight
@@ -457,6 +459,7 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
         HIPC(hipEventCreateWithFlags(&sc.ev_sampled, dev_only));
         HIPC(hipEventCreateWithFlags(&sc.ev_fork, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_aux, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_lists, dev_only));
         HIPC(hipEventCreateWithFlags(&sc.ev_forked, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_chain, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_tab, dev_only));
+        HIPC(hipEventCreateWithFlags(&sc.ev_recs, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_pool, dev_only));
         for (auto& e : sc.t) HIPC(hipEventCreateWithFlags(&e, timed));
         if (g_trace_host) for (auto& e : sc.tc) HIPC(hipEventCreateWithFlags(&e, timed));
     }
@@ -490,7 +493,7 @@ void gev_destroy(gev_ctx* c)
     if (g_graveyard.bytes) g_graveyard.drain(c->device, false);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     if (c->ev_planes) (void)hipEventDestroy(c->ev_planes);
-    for (auto& sc : c->sc) { if (sc.ev_small_done) (void)hipEventDestroy(sc.ev_small_done); if (sc.ev_stitch_done) (void)hipEventDestroy(sc.ev_stitch_done); if (sc.ev_status) (void)hipEventDestroy(sc.ev_status); if (sc.ev_sampled) (void)hipEventDestroy(sc.ev_sampled); if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork); if (sc.ev_aux) (void)hipEventDestroy(sc.ev_aux); if (sc.ev_lists) (void)hipEventDestroy(sc.ev_lists); if (sc.ev_forked) (void)hipEventDestroy(sc.ev_forked); if (sc.ev_chain) (void)hipEventDestroy(sc.ev_chain); if (sc.ev_tab) (void)hipEventDestroy(sc.ev_tab); for (auto& e : sc.t) if (e) (void)hipEventDestroy(e); for (auto& e : sc.tc) if (e) (void)hipEventDestroy(e); }
+    for (auto& sc : c->sc) { if (sc.ev_small_done) (void)hipEventDestroy(sc.ev_small_done); if (sc.ev_stitch_done) (void)hipEventDestroy(sc.ev_stitch_done); if (sc.ev_status) (void)hipEventDestroy(sc.ev_status); if (sc.ev_sampled) (void)hipEventDestroy(sc.ev_sampled); if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork); if (sc.ev_aux) (void)hipEventDestroy(sc.ev_aux); if (sc.ev_lists) (void)hipEventDestroy(sc.ev_lists); if (sc.ev_forked) (void)hipEventDestroy(sc.ev_forked); if (sc.ev_chain) (void)hipEventDestroy(sc.ev_chain); if (sc.ev_tab) (void)hipEventDestroy(sc.ev_tab); if (sc.ev_recs) (void)hipEventDestroy(sc.ev_recs); if (sc.ev_pool) (void)hipEventDestroy(sc.ev_pool); for (auto& e : sc.t) if (e) (void)hipEventDestroy(e); for (auto& e : sc.tc) if (e) (void)hipEventDestroy(e); }
     hipStream_t s = c->stream;
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_seeds) (void)hipHostFree(c->h_seeds);
@@ -1428,10 +1431,7 @@ static int enqueue_pool_free(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t /
     for (int k = 0; k < c->nchr; k++) if (c->chr_active[k]) { P.st[k].pool_list_valid = true; P.st[k].pool_force_rebuild = false; P.st[k].pool_rebuilds++; }
     return GEV_OK;
 }
-// units of the offspring rows (segments with a crossover boundary take a free unit and a work-list entry, the others name the
-// parental unit) + the stitch's work-list length and the segment totals of the status block
-// publish: k_pool_publish (counters into the status block, length of the stitch's work list) right behind; otherwise the caller
-// launches it (enqueue_pool_publish) on a stream that is joined before the stitch starts and the status block leaves
+// the counters of the unit table into the status block and the length of the stitch's work list (behind k_pool_fresh)
 static int enqueue_pool_publish(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, hipStream_t st)
 {
     if (!c->dense || !sc.n_chrwork) return GEV_OK;
@@ -1440,7 +1440,10 @@ static int enqueue_pool_publish(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_peopl
     KCHECK();
     return GEV_OK;
 }
-static int enqueue_pool_assign(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, hipStream_t st, bool publish)
+// units of the offspring rows (segments with a crossover boundary take a free unit and a work-list entry, the others name the
+// parental unit) + the stitch's work-list length and the segment totals of the status block: k_pool_publish follows on the same
+// stream, which is joined before the stitch starts and the status block leaves
+static int enqueue_pool_assign(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, hipStream_t st)
 {
     if (!c->dense || !sc.n_chrwork) return GEV_OK;
     const size_t rows = 2 * n_people, T = n_people * (size_t)c->nchr;
@@ -1449,7 +1452,7 @@ static int enqueue_pool_assign(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people
     hipLaunchKernelGGL(k_pool_inherit, dim3((unsigned)ceil_div(rows, (size_t)(256u >> lg)), sc.n_chrwork), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), rows, c->nchr, sd, lg);
     hipLaunchKernelGGL(k_pool_fresh, dim3((unsigned)ceil_div(rows, 256), sc.n_chrwork), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), rows, c->nchr, sd);
     KCHECK();
-    return publish ? enqueue_pool_publish(c, sc, n_people, st) : GEV_OK;
+    return enqueue_pool_publish(c, sc, n_people, st);
 }
 // sparse state: mutation lists + ancestry intervals (count -> segmented scan -> fill).  Needs the sampling results and the couples;
 // nothing of the generation's dense / CV / A-D work reads its output.
@@ -1498,7 +1501,7 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
     const size_t T = n_people * (size_t)nchr, rows = 2 * n_people;
     hipStream_t sb = c->stream_big;
     SampleDev sd = make_sd(c, sc, T);
-    HIPC(hipStreamWaitEvent(sb, sc.ev_small_done, 0));        // recorded behind k_pool_assign: unit table, work list, sampling results and couples are complete
+    HIPC(hipStreamWaitEvent(sb, sc.ev_small_done, 0));        // recorded once the unit-table and list streams are joined: unit table, work list, sampling results and couples are complete
     HIPC(hipEventRecord(sc.t[4], sb));
     if (c->dense && sc.n_chrwork) {
         if (rows > 0x7fffffffull) return fail(GEV_EINVAL, "reproduce: stitch grid too large");
@@ -1577,11 +1580,13 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     gev_ctx::PendingRepro& q = c->pend;
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     PopState& P = c->pop[q.pop];
-    // Streams of one attempt.  S carries the chain the host waits for: seeds, sampling, unit table, CV planes, A/D, results.
+    // Streams of one attempt.  S carries the chain the host waits for: seeds, sampling, CV planes, A/D, results.
     // X runs what needs neither the sampling nor (for the free list) the couples next to the sampling: Simulation::random_mate and
-    // the free list of the segment pool.  L builds the mutation / interval lists, which nothing else of the generation reads, next
-    // to the CV planes and A/D.  The dense stitch has its own stream as before.  All are joined into S before the status block
-    // leaves.  Serialised mode (kernel timings without interference): everything on S.
+    // the free list of the segment pool; once the sampling records are complete it builds the unit table and the stitch's work list
+    // (k_pool_inherit, k_pool_fresh, k_pool_publish), which only the dense stitch and the status block read, next to the CV planes
+    // and A/D.  L builds the mutation / interval lists, which nothing else of the generation reads, there too.  The dense stitch has
+    // its own stream as before.  X and L are joined into S before ev_small_done and the status block.  Serialised mode (kernel
+    // timings without interference): everything on S, in the order CV planes, A/D, unit table, lists.
     hipStream_t S = c->stream, X = c->serialize ? S : c->stream_aux, L = c->serialize ? S : c->stream_list;
     const size_t T = q.n_people * (size_t)c->nchr;
     q.th0 = host_ms();
@@ -1615,16 +1620,22 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (X != S) HIPC(hipEventRecord(sc.ev_aux, X));
     if (q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, 0u, S, gv + 1, gv + 2, /*clear_status=*/false));
     else if (!q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, q.seed, S));
+    // (a head start's records were complete before ev_fork, which X has waited for; records sampled here are complete behind ev_recs)
+    if (X != S && !sampled) HIPC(hipEventRecord(sc.ev_recs, S));
     q.th1 = host_ms();
     if (X != S) HIPC(hipStreamWaitEvent(S, sc.ev_aux, 0));
     HIPC(hipEventRecord(sc.t[5], S));
-    // (the counters of the unit table concern the stitch and the host only: with the stitch behind the small work they are
-    // published from the list stream, one launch less on the chain the host waits for)
-    const bool publish_aside = L != S;
-    GEVC(enqueue_pool_assign(c, sc, q.n_people, S, !publish_aside));
-    HIPC(hipEventRecord(sc.ev_forked, S));
-    // (the host enqueues slower than the device runs the first kernels of a generation: what the host waits for goes first, the
-    // list kernels, which nothing of the generation reads, last)
+    if (L != S) HIPC(hipEventRecord(sc.ev_forked, S));      // couples and sampling records are complete: what the lists need
+    // The unit table, the stitch's work list and their counters: behind the free list in X's own order, next to the CV planes and
+    // A/D (nothing on S reads or writes what the pool kernels write).  A repeated attempt's rebuild of the free list is in front of
+    // them by the same stream order.  The host enqueues slower than the device runs the first kernels of a generation: the table
+    // goes in front of S's CV planes and A/D, because X is idle once it has mated and S waits for the table in the end (both orders
+    // measured: DESIGN.md, section 10); the list kernels, which nothing of the generation reads, go last.
+    if (X != S) {
+        if (!sampled) HIPC(hipStreamWaitEvent(X, sc.ev_recs, 0));
+        GEVC(enqueue_pool_assign(c, sc, q.n_people, X));
+        HIPC(hipEventRecord(sc.ev_pool, X));
+    }
     // the column counters are filled while the planes are written only if the A/D kernels that consume (and clear) them follow in this attempt
     const bool ad_now = c->eager_ad && c->multipop_ready;
     const bool count_cols = ad_now && sc.cv_count_fused && sc.n_cvwork && sc.cv_used_max;
@@ -1635,8 +1646,8 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     c->ad_host_set_pop = -1;
     if (ad_now) GEVC(enqueue_ad(c, q.pop, c->pop[q.pop].cur ^ 1, q.n_people, count_cols, (int)(c->gen_counter & 1)));   // Simulation::ras_compute_AD always follows (src/Simulation.cpp:1935)
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[1], S));
+    if (X == S) GEVC(enqueue_pool_assign(c, sc, q.n_people, S));   // serialised: behind A/D, in front of the lists
     if (L != S) HIPC(hipStreamWaitEvent(L, sc.ev_forked, 0));
-    if (publish_aside) GEVC(enqueue_pool_publish(c, sc, q.n_people, L));
     // Human::sex of the new generation (:2472) for the next gev_random_mate; a fused generation also sends them to the host with the status block
     HIPC(hipMemcpyAsync(P.d_sex[P.cur ^ 1].p, sc.sex.p, q.n_people, hipMemcpyDeviceToDevice, L));
     if (P.ids_ok) {                                          // the offspring's pedigree ids (:2473-2479) from the parents' rows, into the other buffer
@@ -1653,6 +1664,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     GEVC(enqueue_lists(c, sc, q.n_people, q.has_mut, L));
     if (L != S) HIPC(hipEventRecord(sc.ev_lists, L));
     if (L != S) HIPC(hipStreamWaitEvent(S, sc.ev_lists, 0));
+    if (X != S) HIPC(hipStreamWaitEvent(S, sc.ev_pool, 0));   // unit table, work list and the status block's segment totals
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[2], S));
     // The dense stitch needs the sampling results, the couples and the unit table only, but it saturates HBM, and every
     // latency-bound kernel that runs next to it takes 2-5 times as long (and slows it down in turn).  Behind the whole small work,
@@ -1920,7 +1932,7 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
             static double last_status = 0; const double now = host_ms();
             float a = 0, b = 0, d = 0, e = 0;
             (void)hipEventSynchronize(sc.tc[2]); (void)hipEventElapsedTime(&a, sc.tc[0], sc.t[5]); (void)hipEventElapsedTime(&b, sc.t[5], sc.t[2]); (void)hipEventElapsedTime(&d, sc.t[2], sc.tc[1]); (void)hipEventElapsedTime(&e, sc.tc[1], sc.tc[2]);
-            fprintf(stderr, "[gev] gen %u host: since last status %.3f = to first launch %.3f + enqueue %.3f + host idle %.3f + wait %.3f | device chain: to unit table %.3f, unit table + CV planes %.3f, A/D %.3f, lists after A/D %.3f\n",
+            fprintf(stderr, "[gev] gen %u host: since last status %.3f = to first launch %.3f + enqueue %.3f + host idle %.3f + wait %.3f | device chain: to CV planes %.3f, CV planes %.3f, A/D %.3f, unit table + lists after A/D %.3f\n",
                     c->gen_counter, now - last_status, q.th0 - last_status, sc.th_enq - q.th0, th_w0 - sc.th_enq, now - th_w0, a, b, d, e);
             last_status = now;
         }
@@ -1951,7 +1963,7 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
         if (flags & FLAG_NM_OVF) c->nm_ovf_cap = std::max<size_t>(2 * c->nm_ovf_cap, (size_t)hstatus[ST_NM_OVF_USED] * 5 / 4 + 1024);
         if (flags & FLAG_PARTS_CAP) for (int k = 0; k < nchr; k++) P.st[k].lp.grow_p = c->chr_active[k] && c->track_intervals;   // an arena was full: doubled before the next attempt
         if (flags & FLAG_MUT_CAP) for (int k = 0; k < nchr; k++) P.st[k].lp.grow_m = c->chr_active[k];
-        c->redo_count++;
+        c->redo_count++; if (flags & FLAG_POOL) c->redo_pool_count++;
     }
     for (int k = 0; k < nchr; k++) if (c->chr_active[k]) {      // the offspring's pieces are the state now; the CSR form is made when somebody asks for it
         ChrState::LpState& lp = P.st[k].lp;
@@ -4562,6 +4574,14 @@ int gev_list_stats(gev_ctx* c, int pop, int chr, unsigned long long out[10])
     return GEV_OK;
 }
 int gev_redo_count(gev_ctx* c, unsigned long long* n) { if (!c || !n) return fail(GEV_EINVAL, "null"); *n = c->redo_count; return GEV_OK; }
+int gev_dbg_pool_stats(gev_ctx* c, int pop, unsigned long long out[2])
+{
+    if (!c || !out) return fail(GEV_EINVAL, "null");
+    GEVC(check_idx(c, pop, 0));
+    out[0] = 0; out[1] = c->redo_pool_count;
+    for (int k = 0; k < c->nchr; k++) if (c->chr_active[k]) out[0] = std::max(out[0], c->pop[pop].st[k].pool_rebuilds);
+    return GEV_OK;
+}
 int gev_set_overlap(gev_ctx* c, int on)
 {
     if (!c) return fail(GEV_EINVAL, "null");

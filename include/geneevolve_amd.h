@@ -625,7 +625,7 @@ int gev_sync(gev_ctx*);
 int gev_set_overlap(gev_ctx*, int on);
 /* kernel timing measured with HIP events on the library's own streams: ms[0] = sampling
  * (crossover + mutation + seed chain), ms[1] = dense stitch (genotype planes), ms[2] = sparse state
- * (mutation lists, intervals, CV planes, grouping), ms[3] = sum.  _last = most recent generation
+ * (the CV planes on the main stream; the unit table and the lists run beside them on streams of their own), ms[3] = sum.  _last = most recent generation
  * (implies gev_sync); _totals = cumulative sums over all generations so far (implies gev_sync). */
 int gev_last_reproduce_ms(gev_ctx*, float ms[4]);
 int gev_timing_totals(gev_ctx*, double ms_sum[4], unsigned long long* n_generations);
@@ -672,6 +672,9 @@ int    gev_dbg_prefilter_sweep(gev_ctx*, uint32_t x_begin, uint32_t x_end, unsig
 /* gev_dbg_output_chunk: no staging pass of the following genotype output calls takes more than max_units haplotype rows / individuals /
  * SNPs (SNPs: rounded down to a multiple of 64, at least 64), so that small tests run many passes; 0 = the byte budgets again.  Refused while a generation is pending. */
 int    gev_dbg_output_chunk(gev_ctx*, size_t max_units);
+/* gev_dbg_pool_stats: out[0] = times the free list of a population's segment unit pool was rebuilt (the largest count over its active
+ * chromosomes), out[1] = generations enqueued again because the free list ran out, over the context's life.  Diagnostic. */
+int    gev_dbg_pool_stats(gev_ctx*, int pop, unsigned long long out[2]);
 int    gev_dbg_tables(void* out, size_t bytes);
 int    gev_dbg_threshold(double p, uint32_t out[4] /* a_lo, a_hi, b0, b1 */);
 double gev_dbg_canonical(uint32_t a, uint32_t b);
