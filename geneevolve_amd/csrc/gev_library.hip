@@ -102,6 +102,24 @@ struct DevBuf {
     }
     template <class T> T* as() const { return (T*)p; }
 };
+// Pinned host memory that only grows.  Asynchronous copies from or into the old buffer may be in flight when it is replaced: the
+// caller names the stream that carries them (nullptr: the whole device) and the size of the new buffer
+struct PinnedBuf {
+    void* p = nullptr; size_t bytes = 0;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
+    int ensure(size_t need, size_t want, hipStream_t drain)
+    {
+        if (need <= bytes) return GEV_OK;
+        if (drain) HIPC(hipStreamSynchronize(drain)); else HIPC(hipDeviceSynchronize());
+        if (p) (void)hipHostFree(p);
+        p = nullptr; bytes = 0;
+        HIPC(hipHostMalloc(&p, want, hipHostMallocDefault));
+        bytes = want;
+        return GEV_OK;
+    }
+};
 
 struct ChrStatic {                       // one population x one chromosome
     std::vector<u64> rbp; std::vector<double> rprob; u64 bp_dist = 0;
@@ -204,7 +222,6 @@ struct gev_ctx {
     bool ad_effects_shared = false;         // every root population has the same CV effects bit for bit (check_multipop): A/D uses the one-population term table
     bool multipop_ready = false;            // check_multipop has run for the current static inputs (ad_effects_shared, d_aptr / d_dptr are valid); setters clear it
     hipStream_t stream = nullptr, stream_samp = nullptr, stream_aux = nullptr, stream_list = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float last_ms[4] = {0, 0, 0, 0};
     bool track_intervals = true;
     bool track_pedigree = false;            // gev_set_track_pedigree
@@ -226,14 +243,14 @@ struct gev_ctx {
         bool timing_pending = false, stitch_pending = false;
         hipEvent_t tc[3] = {nullptr, nullptr, nullptr};   // GEV_TRACE_HOST: start of the attempt's main stream, A/D done, lists joined
         double th_enq = 0;
-        // gev_presample: the sampling kernels of the next gev_reproduce were already enqueued for exactly these inputs
-        bool presampled = false; int ps_pop = -1; u32 ps_seed = 0; size_t ps_n_people = 0; bool ps_has_mut = false;
-        bool ps_stale = false;      // the head start was dropped by a redo of the generation in flight (record capacities changed): gev_presample_sex samples again from the retained inputs
+        // A head start: the sampling of this set's NEXT generation, enqueued on the head-start stream before its begin call -- by
+        // gev_presample for exactly these inputs, or by gev_set_generation_chain's generation in flight (seeds drawn from the predicted
+        // engine state, c->chain_state) for the same population and size.  dropped: void (a redo of the generation in flight changed the
+        // record capacities, a setter the maps) though its kernels may still run; gev_presample_sex samples again from the retained inputs
+        struct HeadStart { enum Kind { NONE, PRESAMPLE, CHAIN } kind = NONE; bool dropped = false, has_mut = false; int pop = -1; size_t n_people = 0; u32 seed = 0 /* seed_reproduce (PRESAMPLE) */; } hs;
         // gev_random_mate: father / mother of this set hold the couples of the next gev_reproduce (couples == NULL) of mate_pop
         bool mated = false, mate_assort = false; int mate_pop = -1; size_t mate_n = 0; unsigned long long mate_epoch = 0;
         DevBuf cidx;                // gev_set_track_pedigree: the couple index of every child of a couples list the host passed
-        // gev_set_generation_chain: seeds drawn and sampling enqueued for the NEXT gev_generation_begin (same population, size) from the predicted engine state
-        bool fused_ahead = false, fa_dropped = false, fa_has_mut = false; int fa_pop = -1; size_t fa_n = 0;
         hipEvent_t ev_chain = nullptr, ev_tab = nullptr;
     } sc[2];
     unsigned gen_counter = 0;
@@ -249,15 +266,14 @@ struct gev_ctx {
     size_t bk_ovf_cap = 1 << 16, nm_ovf_cap = 1 << 16;       // overflow regions of the breakpoint / new-mutation records (GEV_OVF_CAP: initial size, tests force redos with a tiny one)
     int chain_draws = -1;                                    // gev_set_generation_chain: ras_glob_seed() draws the host makes between two generations (-1: unknown, no head start)
     bool chain_valid = false; u32 chain_state = 0;           // glob_generator state the queued head start assumed for the next gev_generation_begin
-    unsigned long long chain_hits = 0, chain_misses = 0;
     unsigned long long redo_count = 0;                       // generations that were enqueued again with larger buffers (gev_redo_count)
     unsigned long long redo_pool_count = 0;                  // ... of which because the free list of the unit pool ran out (gev_dbg_pool_stats)
-    void* h_stage = nullptr; size_t h_stage_bytes = 0;       // pinned host staging
-    void* h_seeds = nullptr; size_t h_seeds_bytes = 0;       // pinned copy of the mutation seeds handed to gev_presample
+    PinnedBuf h_stage;                                       // pinned host staging
+    PinnedBuf h_seeds;                                       // pinned copy of the mutation seeds handed to gev_presample
     // pinned A/D result cache, two buffers: [(gen_counter + 1) & 1] holds the PUBLISHED generation's values, the generation in flight
     // fills the other one -- gev_compute_ad may therefore be served between gev_generation_begin and _end (the host hands the next
     // generation over first and reads the last one's A/D while the device works)
-    void* h_ad2[2] = {nullptr, nullptr}; size_t h_ad2_bytes[2] = {0, 0}; bool ad_dom_zero2[2] = {false, false};
+    PinnedBuf h_ad2[2]; bool ad_dom_zero2[2] = {false, false};
     int ad_cached_pop = -1;                                  // population whose current-generation A/D sits in h_ad
     int ad_host_set_pop = -1;                                // population whose raw A/D totals on the device were supplied by gev_set_ad (locus-split: all-reduced)
     bool eager_ad = true;                                    // compute A/D inside gev_reproduce (same enqueue, same sync)
@@ -303,7 +319,7 @@ struct gev_ctx {
     // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob
     struct PhenoState {
         DevBuf res /* result words, then {mean, var} pairs: e, the components, raw A and D */, starts, partial, eraw, cval, streams, tasks, blk, globblk, shift;
-        void* h_res = nullptr; size_t h_res_bytes = 0;
+        PinnedBuf h_res;
         hipEvent_t ev = nullptr;
         bool pending = false; int pop = -1; unsigned long long epoch = 0;
         std::vector<gev_pheno_scheme> scheme; int gen_num = 0, vt_type = 1; u32 glob_state = 0;
@@ -315,12 +331,13 @@ struct gev_ctx {
     DevBuf d_cnt, d_sums, d_map, d_cvm, d_addchr, d_domchr, d_add, d_dom, d_flag, d_stage, d_thr32, d_tmp;
     // per-generation work tables (gev_kernels.h: ChrWork / CvWork / AdWork) are written into a ring of pinned host memory and
     // copied to the device on the stream that uses them
-    uint8_t* h_ring = nullptr; size_t h_ring_bytes = 0, h_ring_off = 0;
+    PinnedBuf h_ring; size_t h_ring_off = 0;
     DevBuf d_adwork2[2]; std::vector<uint8_t> adwork_shadow[2];
     DevBuf d_lpc_bits, d_lpc_cnt, d_lpc_wpre, d_lpc_len, d_lpc_old, d_lpc_new, d_lpc_tmp;     // scratch of an arena compaction (lp_compact)
     DevBuf d_lp_nitems;                                 // [nchr] length of each chromosome's work list of list pieces to build
     std::map<double, GevThr> thr_cache;
 };
+typedef gev_ctx::Scratch::HeadStart HeadStart;
 
 // ------------------------------------------------------------------------------------------
 static int scan_u32_on(hipStream_t st, DevBuf& sums, const u32* in, size_t n, u32* out /*n+1*/)
@@ -444,7 +461,6 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
     HIPC(hipStreamCreateWithPriority(&c->stream_samp, hipStreamNonBlocking, prio_greatest));
     HIPC(hipStreamCreateWithPriority(&c->stream_aux, hipStreamNonBlocking, prio_greatest));
     HIPC(hipStreamCreateWithPriority(&c->stream_list, hipStreamNonBlocking, prio_greatest));
-    for (auto& ev : c->ev) HIPC(hipEventCreate(&ev));
     HIPC(hipStreamCreateWithPriority(&c->stream_big, hipStreamNonBlocking, prio_greatest));
     // Events that only order DEVICE work against device work carry no system-scope fence (by default recording an event makes the
     // preceding kernel write the dirty L2 lines back to memory: tens of microseconds behind a kernel that wrote 50 MB, paid by
@@ -491,15 +507,9 @@ void gev_destroy(gev_ctx* c)
     if (c->stream_aux) { (void)hipStreamSynchronize(c->stream_aux); (void)hipStreamDestroy(c->stream_aux); }
     if (c->stream_list) { (void)hipStreamSynchronize(c->stream_list); (void)hipStreamDestroy(c->stream_list); }
     if (g_graveyard.bytes) g_graveyard.drain(c->device, false);
-    for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     if (c->ev_planes) (void)hipEventDestroy(c->ev_planes);
     for (auto& sc : c->sc) { if (sc.ev_small_done) (void)hipEventDestroy(sc.ev_small_done); if (sc.ev_stitch_done) (void)hipEventDestroy(sc.ev_stitch_done); if (sc.ev_status) (void)hipEventDestroy(sc.ev_status); if (sc.ev_sampled) (void)hipEventDestroy(sc.ev_sampled); if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork); if (sc.ev_aux) (void)hipEventDestroy(sc.ev_aux); if (sc.ev_lists) (void)hipEventDestroy(sc.ev_lists); if (sc.ev_forked) (void)hipEventDestroy(sc.ev_forked); if (sc.ev_chain) (void)hipEventDestroy(sc.ev_chain); if (sc.ev_tab) (void)hipEventDestroy(sc.ev_tab); if (sc.ev_recs) (void)hipEventDestroy(sc.ev_recs); if (sc.ev_pool) (void)hipEventDestroy(sc.ev_pool); for (auto& e : sc.t) if (e) (void)hipEventDestroy(e); for (auto& e : sc.tc) if (e) (void)hipEventDestroy(e); }
     hipStream_t s = c->stream;
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_seeds) (void)hipHostFree(c->h_seeds);
-    for (void* h : c->h_ad2) if (h) (void)hipHostFree(h);
-    if (c->h_ring) (void)hipHostFree(c->h_ring);
-    if (c->ph.h_res) (void)hipHostFree(c->ph.h_res);
     if (c->ph.ev) (void)hipEventDestroy(c->ph.ev);
     delete c;
     if (s) (void)hipStreamDestroy(s);
@@ -884,12 +894,14 @@ int gev_synth_cv_founders(gev_ctx* c, int pop, int phen, int chr, size_t nhap, u
     return cv_founders_from_tmp(c, pop, phen, chr, nhap, w64 * 2);
 }
 
+// the set's head start, if any, is void: no begin call takes it, the next one waits for its kernels (take_head_start)
+static void drop_head_start(gev_ctx::Scratch& sc) { if (sc.hs.kind != HeadStart::NONE) sc.hs.dropped = true; }
 // static tables that depend on several setters
 static int finalize_static(gev_ctx* c, int pop)
 {
     PopState& P = c->pop[pop];
     if (P.finalized) return GEV_OK;
-    for (auto& sc : c->sc) { sc.presampled = false; if (sc.fused_ahead) { sc.fused_ahead = false; sc.fa_dropped = true; } }   // maps / grids changed: a head start sampled with the old ones is void
+    for (auto& sc : c->sc) drop_head_start(sc);              // maps / grids changed: a head start sampled with the old ones is void
     std::vector<ChrDev> cd(c->nchr);
     for (int k = 0; k < c->nchr; k++) {
         ChrStatic& S = P.cs[k];
@@ -1043,6 +1055,7 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready 
 static int prepare_eager_ad(gev_ctx* c, int pop);
 static int check_not_pending(gev_ctx* c);
 static int check_chain_size(size_t T);
+static int population_has_mutmap(gev_ctx* c, int pop, bool& has_mut);
 static int materialize_order(gev_ctx* c, int pop);
 static int ensure_csr(gev_ctx* c, int pop);
 extern "C" int gev_presample(gev_ctx* c, int pop, uint32_t seed_reproduce, const uint32_t* mut_seeds, size_t n_mut_seeds, size_t n_people);
@@ -1086,27 +1099,22 @@ static int upload_table(gev_ctx* c, DevBuf& dst, const void* src, size_t bytes, 
     GEVC(dst.ensure(std::max<size_t>(bytes, 16), st));
     if (!bytes) return GEV_OK;
     const size_t need = round_up(bytes, 64);
-    if (c->h_ring_bytes < 4 * need) {
-        HIPC(hipStreamSynchronize(st));
-        if (c->h_ring) (void)hipHostFree(c->h_ring);
-        c->h_ring = nullptr; c->h_ring_bytes = 0; c->h_ring_off = 0;
+    if (c->h_ring.bytes < 4 * need) {
         static const size_t ring_min = getenv("GEV_TABLE_RING_BYTES") ? (size_t)atol(getenv("GEV_TABLE_RING_BYTES")) : (size_t)(256 << 10);   // (tests shrink it to force wrap-arounds)
-        const size_t want = std::max<size_t>(8 * need, ring_min);
-        HIPC(hipHostMalloc((void**)&c->h_ring, want, hipHostMallocDefault));
-        c->h_ring_bytes = want;
+        GEVC(c->h_ring.ensure(4 * need, std::max<size_t>(8 * need, ring_min), st));
+        c->h_ring_off = 0;
     }
-    if (c->h_ring_off + need > c->h_ring_bytes) { HIPC(hipStreamSynchronize(c->stream)); HIPC(hipStreamSynchronize(st)); c->h_ring_off = 0; }
-    memcpy(c->h_ring + c->h_ring_off, src, bytes);
-    HIPC(hipMemcpyAsync(dst.p, c->h_ring + c->h_ring_off, bytes, hipMemcpyHostToDevice, st));
+    if (c->h_ring_off + need > c->h_ring.bytes) { HIPC(hipStreamSynchronize(c->stream)); HIPC(hipStreamSynchronize(st)); c->h_ring_off = 0; }
+    uint8_t* slot = (uint8_t*)c->h_ring.p + c->h_ring_off;
+    memcpy(slot, src, bytes);
+    HIPC(hipMemcpyAsync(dst.p, slot, bytes, hipMemcpyHostToDevice, st));
     c->h_ring_off += need;
     return GEV_OK;
 }
 static int upload_table_cached(gev_ctx* c, DevBuf& dst, std::vector<uint8_t>& shadow, const void* src, size_t bytes, hipStream_t st)
 {
     if (dst.p && shadow.size() == bytes && bytes && memcmp(shadow.data(), src, bytes) == 0) return GEV_OK;
-    const void* before = dst.p;
     GEVC(upload_table(c, dst, src, bytes, st));
-    (void)before;
     shadow.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
     return GEV_OK;
 }
@@ -1137,6 +1145,34 @@ static int ensure_scratch(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, boo
     GEVC(sc.nm_pos.ensure(16, st)); GEVC(sc.nm_side.ensure(16, st));
     GEVC(sc.status.ensure(n_status * sizeof(u32), st));
     if (has_mut) { GEVC(sc.mutseeds.ensure(T * sizeof(u32), st)); }
+    return GEV_OK;
+}
+// Claim a scratch set for what `st` is about to write into it: the kernel times of the set's previous generation are collected
+// before its events are recorded again, `st` waits for the stitch that last read the set, the buffers are sized for n_people
+// offspring (0: the caller sizes what it fills).  host_may_block = false (a head start next to a generation in flight): nothing
+// waits on the host -- only the sampling time, long over, is read; the stitch's is collected, and the set's own stream made to
+// wait, when the set's generation claims it again
+static int claim_scratch(gev_ctx* c, gev_ctx::Scratch& sc, hipStream_t st, bool host_may_block, size_t n_people, bool has_mut)
+{
+    if (host_may_block) GEVC(harvest_timing(c, sc)); else GEVC(harvest_sampling_time(sc));
+    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); if (host_may_block) sc.stitch_pending = false; }
+    if (n_people) GEVC(ensure_scratch(c, sc, n_people, has_mut));
+    return GEV_OK;
+}
+// A begin call takes the head start in its scratch set if it is exactly the sampling the call would enqueue itself: alive, of the
+// kind the call can use (NONE: an assortative generation uses neither), made for the same population, size and mutation seeds'
+// presence, and for the same `key` -- seed_reproduce and the mutation seeds' values (PRESAMPLE), the engine state (CHAIN).  Taken:
+// the main stream waits for it.  A head start that is NOT taken, alive or dropped, must not write into the set any more: the host
+// waits for the head-start stream before the call refills the set.  Either way the set holds no head start and no couples after
+static int take_head_start(gev_ctx* c, gev_ctx::Scratch& sc, HeadStart::Kind kind, int pop, size_t n_people, bool has_mut, u32 key, const uint32_t* mut_seeds, bool& taken)
+{
+    const HeadStart& h = sc.hs;
+    taken = h.kind != HeadStart::NONE && h.kind == kind && !h.dropped && h.pop == pop && h.n_people == n_people && h.has_mut == has_mut;
+    if (taken && kind == HeadStart::PRESAMPLE) taken = h.seed == key && (!has_mut || (c->h_seeds.p && memcmp(c->h_seeds.p, mut_seeds, n_people * (size_t)c->nchr * sizeof(u32)) == 0));
+    if (taken && kind == HeadStart::CHAIN) taken = c->chain_valid && c->chain_state == key;
+    if (h.kind != HeadStart::NONE && !taken) HIPC(hipStreamSynchronize(c->stream_samp));
+    sc.hs = HeadStart(); sc.mated = false; c->chain_valid = false;
+    if (taken) HIPC(hipStreamWaitEvent(c->stream, sc.ev_sampled, 0));     // the head start ran on its own stream
     return GEV_OK;
 }
 // K1-K3: crossover / mutation sampling and the rand() seed chain; depends on the seeds and n_people only, not on the couples
@@ -1401,7 +1437,10 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
         for (int p = 0; p < c->nphen; p++) {
             CvStatic& V = P.cv[p][k];
             GEVC(V.d_partial.ensure(ceil_div(rows, SMALL_ROWS_PER_BLOCK) * 1024 * sizeof(uint16_t), st));
-            vw.push_back(CvWork{P.cvp[p][k][alt].as<u32>(), P.cvp[p][k][cur].as<u32>(), V.d_pos_sorted.as<u64>(), V.d_counts.as<u32>(), V.d_partial.as<uint16_t>(), S.rbp.front(), S.rbp.back(), V.stride_w32, V.sub_w32, V.C, k, (u32)(cw.size() - 1)});
+            vw.emplace_back();
+            CvWork& v = vw.back(); memset(&v, 0, sizeof v);     // (upload_table_cached compares the table byte for byte: the padding too)
+            v.cvp_alt = P.cvp[p][k][alt].as<u32>(); v.cvp_cur = P.cvp[p][k][cur].as<u32>(); v.pos_sorted = V.d_pos_sorted.as<u64>(); v.counts = V.d_counts.as<u32>(); v.partial = V.d_partial.as<uint16_t>();
+            v.bp0 = S.rbp.front(); v.bp_end = S.rbp.back(); v.stride_w32 = V.stride_w32; v.sub_w32 = V.sub_w32; v.C = V.C; v.chr = k; v.cw = (u32)(cw.size() - 1);
         }
     }
     sc.n_chrwork = (unsigned)cw.size(); sc.n_cvwork = (unsigned)vw.size();
@@ -1420,7 +1459,7 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
 }
 // free units of the pool = units no (slot, segment) of the parents names: needs the parents' table only, not this generation's
 // sampling or couples
-static int enqueue_pool_free(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t /*n_people*/, hipStream_t st)
+static int enqueue_pool_free(gev_ctx* c, gev_ctx::Scratch& sc, int pop, hipStream_t st)
 {
     PopState& P = c->pop[pop];
     if (!c->dense || !sc.n_chrwork || !sc.pool_rebuild) return GEV_OK;      // (decided by enqueue_tables)
@@ -1572,6 +1611,11 @@ static int enqueue_mate(gev_ctx* c, hipStream_t st, PopState& P, u32 seed_val, c
     return GEV_OK;
 }
 
+// Hand-overs between the streams of an attempt: `ev` is recorded on `from`, and `to` waits for it -- at once (hand_over) or at a later
+// point (hand_record, hand_wait).  Nothing to do where both are the same stream (serialised mode: stream order does it)
+static int hand_record(hipStream_t from, hipStream_t to, hipEvent_t ev) { if (from != to) HIPC(hipEventRecord(ev, from)); return GEV_OK; }
+static int hand_wait(hipStream_t from, hipStream_t to, hipEvent_t ev) { if (from != to) HIPC(hipStreamWaitEvent(to, ev, 0)); return GEV_OK; }
+static int hand_over(hipStream_t from, hipStream_t to, hipEvent_t ev) { GEVC(hand_record(from, to, ev)); return hand_wait(from, to, ev); }
 // One attempt of a generation: sampling (unless the head start covers it), lists + CV planes + unit table, the dense stitch on its
 // own stream, A/D, and the status block on its way back -- everything enqueued, nothing waited for.  A generation begun with
 // gev_generation_begin also draws its ras_glob_seed() values and forms its couples here, on the device.
@@ -1604,7 +1648,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
         } else GEVC(enqueue_glob(sc.globblk, S, q.glob_state, nullptr, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     }
     // (the mating stream starts here: it needs the seeds, not the state behind them)
-    if (X != S) { HIPC(hipEventRecord(sc.ev_fork, S)); HIPC(hipStreamWaitEvent(X, sc.ev_fork, 0)); }
+    GEVC(hand_over(S, X, sc.ev_fork));
     if (q.fused && !q.assort) {
         GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father.as<u32>(), sc.mother.as<u32>(),
                           c->d_couples.as<gev_couple>(), status + ST_NM_MATE, status + ST_FLAGS));
@@ -1615,27 +1659,25 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
         HIPC(hipEventRecord(sc.ev_chain, S));
     }
     GEVC(enqueue_tables(c, sc, q.pop, q.n_people, S));        // (uploaded on S while X mates)
-    if (X != S) { HIPC(hipEventRecord(sc.ev_tab, S)); HIPC(hipStreamWaitEvent(X, sc.ev_tab, 0)); }
-    GEVC(enqueue_pool_free(c, sc, q.pop, q.n_people, X));
-    if (X != S) HIPC(hipEventRecord(sc.ev_aux, X));
+    GEVC(hand_over(S, X, sc.ev_tab));
+    GEVC(enqueue_pool_free(c, sc, q.pop, X));
+    GEVC(hand_record(X, S, sc.ev_aux));
     if (q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, 0u, S, gv + 1, gv + 2, /*clear_status=*/false));
     else if (!q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, q.seed, S));
     // (a head start's records were complete before ev_fork, which X has waited for; records sampled here are complete behind ev_recs)
-    if (X != S && !sampled) HIPC(hipEventRecord(sc.ev_recs, S));
+    if (!sampled) GEVC(hand_record(S, X, sc.ev_recs));
     q.th1 = host_ms();
-    if (X != S) HIPC(hipStreamWaitEvent(S, sc.ev_aux, 0));
+    GEVC(hand_wait(X, S, sc.ev_aux));
     HIPC(hipEventRecord(sc.t[5], S));
-    if (L != S) HIPC(hipEventRecord(sc.ev_forked, S));      // couples and sampling records are complete: what the lists need
+    GEVC(hand_record(S, L, sc.ev_forked));                  // couples and sampling records are complete: what the lists need
     // The unit table, the stitch's work list and their counters: behind the free list in X's own order, next to the CV planes and
     // A/D (nothing on S reads or writes what the pool kernels write).  A repeated attempt's rebuild of the free list is in front of
     // them by the same stream order.  The host enqueues slower than the device runs the first kernels of a generation: the table
     // goes in front of S's CV planes and A/D, because X is idle once it has mated and S waits for the table in the end (both orders
     // measured: DESIGN.md, section 10); the list kernels, which nothing of the generation reads, go last.
-    if (X != S) {
-        if (!sampled) HIPC(hipStreamWaitEvent(X, sc.ev_recs, 0));
-        GEVC(enqueue_pool_assign(c, sc, q.n_people, X));
-        HIPC(hipEventRecord(sc.ev_pool, X));
-    }
+    if (!sampled) GEVC(hand_wait(S, X, sc.ev_recs));
+    if (X != S) GEVC(enqueue_pool_assign(c, sc, q.n_people, X));   // (the one difference of serialised mode: there it goes behind A/D, below)
+    GEVC(hand_record(X, S, sc.ev_pool));
     // the column counters are filled while the planes are written only if the A/D kernels that consume (and clear) them follow in this attempt
     const bool ad_now = c->eager_ad && c->multipop_ready;
     const bool count_cols = ad_now && sc.cv_count_fused && sc.n_cvwork && sc.cv_used_max;
@@ -1647,7 +1689,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (ad_now) GEVC(enqueue_ad(c, q.pop, c->pop[q.pop].cur ^ 1, q.n_people, count_cols, (int)(c->gen_counter & 1)));   // Simulation::ras_compute_AD always follows (src/Simulation.cpp:1935)
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[1], S));
     if (X == S) GEVC(enqueue_pool_assign(c, sc, q.n_people, S));   // serialised: behind A/D, in front of the lists
-    if (L != S) HIPC(hipStreamWaitEvent(L, sc.ev_forked, 0));
+    GEVC(hand_wait(S, L, sc.ev_forked));
     // Human::sex of the new generation (:2472) for the next gev_random_mate; a fused generation also sends them to the host with the status block
     HIPC(hipMemcpyAsync(P.d_sex[P.cur ^ 1].p, sc.sex.p, q.n_people, hipMemcpyDeviceToDevice, L));
     if (P.ids_ok) {                                          // the offspring's pedigree ids (:2473-2479) from the parents' rows, into the other buffer
@@ -1662,9 +1704,8 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     }
     if (q.fused) { HIPC(hipMemcpyAsync(q.hsex, sc.sex.p, q.n_people, hipMemcpyDeviceToHost, L)); HIPC(hipMemcpyAsync(q.hseeds2, gv, 2 * sizeof(u32), hipMemcpyDeviceToHost, L)); }   // (copies nothing on the device waits for: off the main stream)
     GEVC(enqueue_lists(c, sc, q.n_people, q.has_mut, L));
-    if (L != S) HIPC(hipEventRecord(sc.ev_lists, L));
-    if (L != S) HIPC(hipStreamWaitEvent(S, sc.ev_lists, 0));
-    if (X != S) HIPC(hipStreamWaitEvent(S, sc.ev_pool, 0));   // unit table, work list and the status block's segment totals
+    GEVC(hand_over(L, S, sc.ev_lists));
+    GEVC(hand_wait(X, S, sc.ev_pool));                        // unit table, work list and the status block's segment totals
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[2], S));
     // The dense stitch needs the sampling results, the couples and the unit table only, but it saturates HBM, and every
     // latency-bound kernel that runs next to it takes 2-5 times as long (and slows it down in turn).  Behind the whole small work,
@@ -1676,14 +1717,36 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     sc.th_enq = host_ms();
     return GEV_OK;
 }
-static int ensure_stage(gev_ctx* c, size_t bytes)
+// The size checks every call that samples a generation makes (who: the prefix of its messages)
+static int check_sizes(gev_ctx* c, const char* who, size_t n_people, const uint32_t* mut_seeds, size_t n_mut_seeds)
 {
-    if (c->h_stage_bytes >= bytes) return GEV_OK;
-    HIPC(hipDeviceSynchronize());
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr; c->h_stage_bytes = 0;
-    HIPC(hipHostMalloc(&c->h_stage, bytes * 5 / 4 + 4096, hipHostMallocDefault));
-    c->h_stage_bytes = bytes * 5 / 4 + 4096;
+    const size_t T = n_people * (size_t)c->nchr;
+    if (n_people == 0) return fail(GEV_EINVAL, "%s: no offspring", who);
+    if (2 * T * GEV_BK_CAP >= 0xf0000000ull) return fail(GEV_EINVAL, "%s: too many gametes", who);
+    if (mut_seeds && n_mut_seeds != T) return fail(GEV_EINVAL, "%s: n_mut_seeds=%zu, expected n_people*nchr=%zu", who, n_mut_seeds, T);
+    return GEV_OK;
+}
+// What the begin calls share: the size checks, the static tables, room for n_people offspring, the pinned staging buffer
+// [status | extra_bytes of the caller's] and the fields of the pending generation (c->pend) that do not depend on who begins it;
+// the caller sets what is its own.  fused: the library draws the mutation seeds itself wherever the population has a mutation map
+// (and the extra bytes start with the two seeds and the sexes that go back to the host); otherwise the caller's mut_seeds say
+static int begin_prologue(gev_ctx* c, int pop, const char* who, size_t n_people, bool fused, const uint32_t* mut_seeds, size_t n_mut_seeds, size_t extra_bytes)
+{
+    GEVC(check_sizes(c, who, n_people, mut_seeds, n_mut_seeds));
+    bool has_mut = mut_seeds != nullptr;
+    if (fused) GEVC(population_has_mutmap(c, pop, has_mut));
+    if (!has_mut) GEVC(check_chain_size(n_people * (size_t)c->nchr));
+    const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)c->nchr;
+    const size_t stage_bytes = n_status * sizeof(u32) + extra_bytes;
+    GEVC(c->h_stage.ensure(stage_bytes, stage_bytes * 5 / 4 + 4096, nullptr));
+    GEVC(finalize_static(c, pop));
+    GEVC(prepare_eager_ad(c, pop));
+    GEVC(ensure_capacity(c, pop, n_people));
+    gev_ctx::PendingRepro& q = c->pend;
+    q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = false; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = (u32*)c->h_stage.p;
+    q.pool_rebuilt = false;
+    q.fused = fused; q.has_svf = false; q.d_svf = nullptr; q.hseeds2 = q.hstatus + n_status; q.hsex = (uint8_t*)(q.hseeds2 + 2);
+    q.assort = false; q.cidx_mode = 0; q.n_couples = n_people;
     return GEV_OK;
 }
 // gev_reproduce in two halves: _begin checks and stages the inputs and enqueues the generation's device work, _end waits for it,
@@ -1696,13 +1759,13 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     PopState& P = c->pop[pop];
     if (!P.gen0) return fail(GEV_ESTATE, "reproduce: population %d has no current generation (call gev_init_gen0)", pop);
     HIPC(hipSetDevice(c->device));
-    const int nchr = c->nchr;
-    const size_t T = n_people * (size_t)nchr;
-    if (n_people == 0) return fail(GEV_EINVAL, "reproduce: no offspring");
-    if (2 * T * GEV_BK_CAP >= 0xf0000000ull) return fail(GEV_EINVAL, "reproduce: too many gametes");
+    const size_t T = n_people * (size_t)c->nchr;
     const bool has_mut = mut_seeds != nullptr;
-    if (has_mut && n_mut_seeds != T) return fail(GEV_EINVAL, "reproduce: n_mut_seeds=%zu, expected n_people*nchr=%zu", n_mut_seeds, T);
-    if (!has_mut) GEVC(check_chain_size(T));
+    // pinned staging behind the status block: [father | mother | mut_seeds | cidx], written by the host, copied asynchronously
+    // (the prologue fills c->pend and runs finalize_static / ensure_capacity although the call may still be refused below: nothing
+    // reads c->pend while pend.active is false, which only the end of this function sets)
+    GEVC(begin_prologue(c, pop, "reproduce", n_people, /*fused=*/false, mut_seeds, n_mut_seeds, (2 * n_people + (has_mut ? T : 0) + (c->track_pedigree ? n_people : 0)) * sizeof(u32)));
+    gev_ctx::PendingRepro& q = c->pend;
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     // couples == NULL: the couples gev_random_mate left on the device for this population
     const bool dev_couples = couples == nullptr;
@@ -1711,12 +1774,8 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     if (dev_couples && sc.mate_epoch != P.layout_epoch)
         return fail(GEV_ESTATE, "reproduce: couples is NULL but population %d changed (migration, rows removed or imported, order materialised) "
                     "after the gev_random_mate / gev_assort_mate that formed them: its positions no longer name the same rows", pop);
-    // pinned staging: [father | mother | mut_seeds | status], written by the host, copied asynchronously
-    const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
-    const size_t stage_words = 2 * n_people + (has_mut ? T : 0) + n_status + (c->track_pedigree ? n_people : 0);
-    GEVC(ensure_stage(c, stage_words * 4));
-    u32* father = (u32*)c->h_stage; u32* mother = father + n_people; u32* hseeds = mother + n_people; u32* hstatus = hseeds + (has_mut ? T : 0);
-    u32* hcidx = hstatus + n_status;                         // (tracking only) index of every child's couple in `couples`
+    u32* father = q.hstatus + q.n_status; u32* mother = father + n_people; u32* hseeds = mother + n_people;
+    u32* hcidx = hseeds + (has_mut ? T : 0);                 // (tracking only) index of every child's couple in `couples`
     // offspring enumeration order of the couple loop (src/Simulation.cpp:2433-2443)
     size_t ip = 0;
     const u32* lg = P.logical.empty() ? nullptr : P.logical.data();
@@ -1734,22 +1793,12 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
         }
     }
     if (!dev_couples && ip != n_people) return fail(GEV_EINVAL, "reproduce: n_people=%zu but the couples list yields %zu offspring", n_people, ip);
-    GEVC(finalize_static(c, pop));
-    GEVC(prepare_eager_ad(c, pop));
-    GEVC(ensure_capacity(c, pop, n_people));
     hipStream_t st = c->stream;
     // sampling already enqueued by gev_presample for exactly these inputs?
-    const bool mate_assort = sc.mate_assort;
-    const bool pre = sc.presampled && sc.ps_pop == pop && sc.ps_seed == (u32)seed_reproduce && sc.ps_n_people == n_people && sc.ps_has_mut == has_mut &&
-                     (!has_mut || (c->h_seeds && memcmp(c->h_seeds, mut_seeds, T * sizeof(u32)) == 0));
-    sc.presampled = false; sc.ps_stale = false; sc.mated = false; sc.fused_ahead = false; sc.fa_dropped = false; c->chain_valid = false;
-    if (pre) HIPC(hipStreamWaitEvent(st, sc.ev_sampled, 0));     // the head start ran on its own stream
-    else HIPC(hipStreamSynchronize(c->stream_samp));            // a head start that does not match must not write into the set any more
-    if (!pre) {
+    GEVC(take_head_start(c, sc, HeadStart::PRESAMPLE, pop, n_people, has_mut, (u32)seed_reproduce, mut_seeds, q.pre));
+    if (!q.pre) {
         // the stitch that last read this scratch set must be over before the set is refilled
-        GEVC(harvest_timing(c, sc));
-        if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
-        GEVC(ensure_scratch(c, sc, n_people, has_mut));
+        GEVC(claim_scratch(c, sc, st, true, n_people, has_mut));
         if (has_mut) { memcpy(hseeds, mut_seeds, T * sizeof(u32)); HIPC(hipMemcpyAsync(sc.mutseeds.p, hseeds, T * sizeof(u32), hipMemcpyHostToDevice, st)); }
     }
     if (!dev_couples) {
@@ -1757,11 +1806,9 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
         HIPC(hipMemcpyAsync(sc.mother.p, mother, n_people * sizeof(u32), hipMemcpyHostToDevice, st));
         if (P.ids_ok) { GEVC(sc.cidx.ensure(n_people * sizeof(u32), st)); HIPC(hipMemcpyAsync(sc.cidx.p, hcidx, n_people * sizeof(u32), hipMemcpyHostToDevice, st)); }
     }
-
-    gev_ctx::PendingRepro& q = c->pend;
-    q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = (u32)seed_reproduce; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
-    q.fused = false; q.assort = false; q.has_svf = false; q.pool_rebuilt = false;
-    q.cidx_mode = !dev_couples ? 1 : (mate_assort ? 2 : 0); q.n_couples = !dev_couples ? n_couples : (mate_assort ? (size_t)c->am.res.n_couples : n_people);
+    q.seed = (u32)seed_reproduce;
+    if (!dev_couples) { q.cidx_mode = 1; q.n_couples = n_couples; }
+    else if (sc.mate_assort) { q.cidx_mode = 2; q.n_couples = (size_t)c->am.res.n_couples; }
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     return GEV_OK;
@@ -1774,17 +1821,15 @@ static int enqueue_chain_head_start(gev_ctx* c)
     const size_t T = q.n_people * (size_t)c->nchr;
     // the stitch that last read the other scratch set (the previous generation's) may still be running: the sampling stream waits for
     // it, the host does not (its kernel time is collected when the set's next generation is enqueued)
-    GEVC(harvest_sampling_time(nx));
-    if (nx.stitch_pending) HIPC(hipStreamWaitEvent(SS, nx.ev_stitch_done, 0));
+    GEVC(claim_scratch(c, nx, SS, false, q.n_people, q.has_mut));   // (sizes the buffers in front of the wait below: allocations only, no stream work)
     HIPC(hipStreamWaitEvent(SS, sc.ev_chain, 0));
-    GEVC(ensure_scratch(c, nx, q.n_people, q.has_mut));
     GEVC(nx.globvals.ensure((2 + T) * sizeof(u32), SS));
     u32* gv = nx.globvals.as<u32>(); u32* status = nx.status.as<u32>();
     HIPC(hipMemsetAsync(nx.status.p, 0, q.n_status * sizeof(u32), SS));
     GEVC(enqueue_glob(nx.globblk, SS, 0u, sc.status.as<u32>() + ST_NEXT_STATE, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     GEVC(enqueue_sampling(c, nx, q.pop, q.n_people, q.has_mut, 0u, SS, gv + 1, gv + 2, /*clear_status=*/false));
     HIPC(hipEventRecord(nx.ev_sampled, SS));
-    nx.fused_ahead = true; nx.fa_dropped = false; nx.fa_pop = q.pop; nx.fa_n = q.n_people; nx.fa_has_mut = q.has_mut;
+    nx.hs.kind = HeadStart::CHAIN; nx.hs.dropped = false; nx.hs.pop = q.pop; nx.hs.n_people = q.n_people; nx.hs.has_mut = q.has_mut;
     return GEV_OK;
 }
 // A/D is computed with the generation (same enqueue, same wait) once the per-population a/d tables exist; they are set up by the
@@ -1829,33 +1874,17 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     if (!P.gen0) return fail(GEV_ESTATE, "generation: population %d has no current generation (call gev_init_gen0)", pop);
     if (glob_state == 0 || glob_state >= GEV_M31) return fail(GEV_EINVAL, "generation: %u is not a state of std::minstd_rand0 (1 .. 2^31-2)", glob_state);
     HIPC(hipSetDevice(c->device));
-    const int nchr = c->nchr;
-    const size_t n_people = pop_size, T = n_people * (size_t)nchr;
-    if (n_people == 0) return fail(GEV_EINVAL, "generation: no offspring");
-    if (2 * T * GEV_BK_CAP >= 0xf0000000ull) return fail(GEV_EINVAL, "generation: too many gametes");
-    bool has_mut = false;
-    GEVC(population_has_mutmap(c, pop, has_mut));
-    if (!has_mut) GEVC(check_chain_size(T));
-    const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
+    const size_t n_people = pop_size;
     // pinned: [status | the two seeds | sexes]
-    GEVC(ensure_stage(c, (n_status + 2) * 4 + n_people + 16));
-    u32* hstatus = (u32*)c->h_stage;
-    GEVC(finalize_static(c, pop));
-    GEVC(prepare_eager_ad(c, pop));
-    GEVC(ensure_capacity(c, pop, n_people));
+    GEVC(begin_prologue(c, pop, "generation", n_people, /*fused=*/true, nullptr, 0, 2 * sizeof(u32) + n_people + 16));
+    gev_ctx::PendingRepro& q = c->pend;
     hipStream_t st = c->stream;
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     // seeds already drawn and sampling already enqueued for exactly this call (gev_set_generation_chain)?
-    const bool pre = sc.fused_ahead && c->chain_valid && c->chain_state == (u32)glob_state && sc.fa_pop == pop && sc.fa_n == n_people && sc.fa_has_mut == has_mut;
-    if (sc.presampled || sc.fa_dropped || (sc.fused_ahead && !pre)) HIPC(hipStreamSynchronize(c->stream_samp));     // a head start that does not match must not write into the set any more
-    if (sc.fused_ahead) { if (pre) c->chain_hits++; else c->chain_misses++; }
-    sc.presampled = false; sc.ps_stale = false; sc.mated = false; sc.fused_ahead = false; sc.fa_dropped = false; c->chain_valid = false;
-    if (pre) HIPC(hipStreamWaitEvent(st, sc.ev_sampled, 0));     // the head start ran on its own stream
-    else {
-        GEVC(harvest_timing(c, sc));
-        if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
-        GEVC(ensure_scratch(c, sc, n_people, has_mut));
-        GEVC(sc.globvals.ensure((2 + T) * sizeof(u32), st));
+    GEVC(take_head_start(c, sc, HeadStart::CHAIN, pop, n_people, q.has_mut, (u32)glob_state, nullptr, q.pre));
+    if (!q.pre) {
+        GEVC(claim_scratch(c, sc, st, true, n_people, q.has_mut));
+        GEVC(sc.globvals.ensure((2 + n_people * (size_t)c->nchr) * sizeof(u32), st));
     }
     GEVC(c->d_couples.ensure(n_people * sizeof(gev_couple), st));
     if (selection_value_func) {
@@ -1865,11 +1894,7 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     }
     const double* d_svf = selection_value_func ? c->d_svf.as<double>() : nullptr;
     if (dev_sel) d_svf = P.d_sel[P.sbuf].as<double>() + 2 * P.n_people;     // (enqueued on this stream behind gev_compute_selection: no wait)
-    gev_ctx::PendingRepro& q = c->pend;
-    q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = pre; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
-    q.pool_rebuilt = false;
-    q.fused = true; q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
-    q.assort = false; q.cidx_mode = 0; q.n_couples = n_people;
+    q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
     if (c->chain_draws >= 0) GEVC(enqueue_chain_head_start(c));    // behind this generation's work: the next generation waits for all of it
@@ -1956,8 +1981,7 @@ static int generation_finish_inner(gev_ctx* c, uint8_t* sex_out, gev_generation_
         {   // a head start taken meanwhile used the old record capacities: it is sampled again (by gev_presample_sex from the retained
             // inputs, or by the next gev_reproduce_begin)
             gev_ctx::Scratch& nx = c->sc[(c->gen_counter + 1) & 1];
-            if (nx.presampled) { nx.presampled = false; nx.ps_stale = true; }
-            if (nx.fused_ahead) { nx.fused_ahead = false; nx.fa_dropped = true; }
+            drop_head_start(nx);
         }
         if (flags & FLAG_BK_OVF) c->bk_ovf_cap = std::max<size_t>(2 * c->bk_ovf_cap, (size_t)hstatus[ST_BK_OVF_USED] * 5 / 4 + 1024);
         if (flags & FLAG_NM_OVF) c->nm_ovf_cap = std::max<size_t>(2 * c->nm_ovf_cap, (size_t)hstatus[ST_NM_OVF_USED] * 5 / 4 + 1024);
@@ -2031,8 +2055,7 @@ static int random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selecti
     hipStream_t st = c->stream;
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     // father / mother of this scratch set were last read by the stitch two generations back
-    GEVC(harvest_timing(c, sc));
-    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
+    GEVC(claim_scratch(c, sc, st, true, 0, false));
     GEVC(sc.father.ensure(pop_size * sizeof(u32), st)); GEVC(sc.mother.ensure(pop_size * sizeof(u32), st));
     GEVC(c->d_couples.ensure(pop_size * sizeof(gev_couple), st));
     GEVC(c->d_mstat.ensure(4 * sizeof(u32), st));
@@ -2143,8 +2166,7 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     sc.mated = false;
     // father / mother of this scratch set were last read by the stitch two generations back
-    GEVC(harvest_timing(c, sc));
-    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
+    GEVC(claim_scratch(c, sc, st, true, 0, false));
     const u32* logical = nullptr;
     if (!P.logical.empty()) {                                   // after a cross-GPU migration positions are not rows
         GEVC(upload_table(c, c->d_logical, P.logical.data(), n_h * sizeof(u32), st));
@@ -2399,9 +2421,8 @@ static int generation_begin_assort(gev_ctx* c, int pop, uint32_t glob_state, con
     hipStream_t st = c->stream;
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     // a head start for a random-mating generation must not write into the set any more, and is not used
-    if (sc.presampled || sc.fa_dropped || sc.fused_ahead) HIPC(hipStreamSynchronize(c->stream_samp));
-    if (sc.fused_ahead) c->chain_misses++;
-    sc.presampled = false; sc.ps_stale = false; sc.mated = false; sc.fused_ahead = false; sc.fa_dropped = false; c->chain_valid = false;
+    bool taken = false;
+    GEVC(take_head_start(c, sc, HeadStart::NONE, pop, 0, false, 0u, nullptr, taken));
     // :2170, :2173, :2265 (and :2332 for 'p'): the mating seeds
     const bool pois = par->offspring_dist == 'p' || par->offspring_dist == 'P';
     uint32_t seeds[4] = {0, 0, 0, 0};
@@ -2409,28 +2430,13 @@ static int generation_begin_assort(gev_ctx* c, int pop, uint32_t glob_state, con
     GEVC(gev_glob_seeds(c, &state, pois ? 4 : 3, seeds));
     gev_assort_result r;
     GEVC(assort_mate(c, pop, par, seeds, mating_value, selection_value_func, dev_sel, pedigree, nullptr, &r, /*dev_records=*/true));
-    const int nchr = c->nchr;
-    const size_t n_people = r.n_offspring, T = n_people * (size_t)nchr;
-    if (n_people == 0) return fail(GEV_EINVAL, "generation: no offspring");
-    if (2 * T * GEV_BK_CAP >= 0xf0000000ull) return fail(GEV_EINVAL, "generation: too many gametes");
-    bool has_mut = false;
-    GEVC(population_has_mutmap(c, pop, has_mut));
-    if (!has_mut) GEVC(check_chain_size(T));
-    const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
-    GEVC(ensure_stage(c, (n_status + 2) * 4 + n_people + 16));
-    u32* hstatus = (u32*)c->h_stage;
-    GEVC(finalize_static(c, pop));
-    GEVC(prepare_eager_ad(c, pop));
-    GEVC(ensure_capacity(c, pop, n_people));
-    sc.mated = false;                                          // the couples are this generation's, not a later gev_reproduce's
-    GEVC(harvest_timing(c, sc));
-    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); sc.stitch_pending = false; }
-    GEVC(ensure_scratch(c, sc, n_people, has_mut));             // (father / mother already hold n_people entries: kept)
-    GEVC(sc.globvals.ensure((2 + T) * sizeof(u32), st));
+    const size_t n_people = r.n_offspring;
+    GEVC(begin_prologue(c, pop, "generation", n_people, /*fused=*/true, nullptr, 0, 2 * sizeof(u32) + n_people + 16));
     gev_ctx::PendingRepro& q = c->pend;
-    q.pop = pop; q.n_people = n_people; q.has_mut = has_mut; q.pre = false; q.seed = 0; q.attempt = 0; q.n_status = n_status; q.hstatus = hstatus;
-    q.pool_rebuilt = false;
-    q.fused = true; q.has_svf = false; q.d_svf = nullptr; q.glob_state = state; q.hseeds2 = hstatus + n_status; q.hsex = (uint8_t*)(hstatus + n_status + 2);
+    sc.mated = false;                                          // the couples are this generation's, not a later gev_reproduce's
+    GEVC(claim_scratch(c, sc, st, true, n_people, q.has_mut));   // (father / mother already hold n_people entries: kept)
+    GEVC(sc.globvals.ensure((2 + n_people * (size_t)c->nchr) * sizeof(u32), st));
+    q.glob_state = state;
     q.assort = true; q.assort_seed0 = seeds[0]; q.am_nm = r.num_males_mate; q.am_nf = r.num_females_mate; q.am_couples = r.n_couples;
     q.cidx_mode = 2; q.n_couples = r.n_couples;
     GEVC(enqueue_attempt(c, 0));
@@ -2479,12 +2485,11 @@ int gev_presample_sex(gev_ctx* c, int pop, uint8_t* sex_out, size_t n_people)
     GEVC(check_idx(c, pop, 0));
     if (!sex_out) return fail(GEV_EINVAL, "presample_sex: null output");
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
-    if (!sc.presampled && sc.ps_stale && sc.ps_pop == pop && sc.ps_n_people == n_people) {
-        // the head start was dropped by a redo of the previous generation (larger record regions): sample again from the retained inputs
-        sc.ps_stale = false;
-        GEVC(gev_presample(c, pop, sc.ps_seed, sc.ps_has_mut ? (const uint32_t*)c->h_seeds : nullptr, sc.ps_has_mut ? n_people * (size_t)c->nchr : 0, n_people));
-    }
-    if (!sc.presampled || sc.ps_pop != pop || sc.ps_n_people != n_people) return fail(GEV_ESTATE, "presample_sex: no matching gev_presample is pending");
+    const HeadStart& h = sc.hs;
+    const bool ours = h.kind == HeadStart::PRESAMPLE && h.pop == pop && h.n_people == n_people;
+    if (ours && h.dropped)       // by a redo of the previous generation (larger record regions): sample again from the retained inputs
+        GEVC(gev_presample(c, pop, h.seed, h.has_mut ? (const uint32_t*)c->h_seeds.p : nullptr, h.has_mut ? n_people * (size_t)c->nchr : 0, n_people));
+    if (!ours || h.dropped) return fail(GEV_ESTATE, "presample_sex: no matching gev_presample is pending");
     HIPC(hipSetDevice(c->device));
     hipStream_t st = c->serialize ? c->stream : c->stream_samp;
     HIPC(hipMemcpyAsync(sex_out, sc.sex.p, n_people, hipMemcpyDeviceToHost, st));
@@ -2502,37 +2507,24 @@ int gev_presample(gev_ctx* c, int pop, uint32_t seed_reproduce, const uint32_t* 
     if (!P.gen0) return fail(GEV_ESTATE, "presample: population %d has no current generation (call gev_init_gen0)", pop);
     HIPC(hipSetDevice(c->device));
     const size_t T = n_people * (size_t)c->nchr;
-    if (n_people == 0) return fail(GEV_EINVAL, "presample: no offspring");
-    if (2 * T * GEV_BK_CAP >= 0xf0000000ull) return fail(GEV_EINVAL, "presample: too many gametes");
     const bool has_mut = mut_seeds != nullptr;
-    if (has_mut && n_mut_seeds != T) return fail(GEV_EINVAL, "presample: n_mut_seeds=%zu, expected n_people*nchr=%zu", n_mut_seeds, T);
+    GEVC(check_sizes(c, "presample", n_people, mut_seeds, n_mut_seeds));
     GEVC(finalize_static(c, pop));
     hipStream_t st = c->serialize ? c->stream : c->stream_samp;   // the head start has a stream of its own: it runs next to the lists / A-D of the generation in flight
     // the scratch set of the generation AFTER the one in flight when called between gev_reproduce_begin and _end
     gev_ctx::Scratch& sc = c->sc[(c->gen_counter + (c->pend.active ? 1u : 0u)) & 1];
-    sc.presampled = false; sc.ps_stale = false;
-    const bool seeds_in_place = has_mut && mut_seeds == (const uint32_t*)c->h_seeds;
-    if (has_mut && !seeds_in_place) {
-        if (c->h_seeds_bytes < T * sizeof(u32)) {
-            HIPC(hipStreamSynchronize(st));              // an earlier copy out of the old buffer may be in flight
-            if (c->h_seeds) (void)hipHostFree(c->h_seeds);
-            c->h_seeds = nullptr; c->h_seeds_bytes = 0;
-            HIPC(hipHostMalloc(&c->h_seeds, T * sizeof(u32) * 5 / 4 + 4096, hipHostMallocDefault));
-            c->h_seeds_bytes = T * sizeof(u32) * 5 / 4 + 4096;
-        }
-        memcpy(c->h_seeds, mut_seeds, T * sizeof(u32));
+    drop_head_start(sc);                                 // whatever the set held is overwritten (same stream: behind it)
+    if (has_mut && mut_seeds != (const uint32_t*)c->h_seeds.p) {
+        GEVC(c->h_seeds.ensure(T * sizeof(u32), T * sizeof(u32) * 5 / 4 + 4096, st));   // an earlier copy out of the old buffer may be in flight
+        memcpy(c->h_seeds.p, mut_seeds, T * sizeof(u32));
     }
     // Called while a generation is in flight, the stitch that last used this scratch set may still be running: nothing here waits
-    // for it on the host (its kernel time is collected when the set's next generation is enqueued); the sampling stream does.
-    if (c->pend.active) GEVC(harvest_sampling_time(sc)); else GEVC(harvest_timing(c, sc));
-    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); if (!c->pend.active) sc.stitch_pending = false; }
-    GEVC(ensure_scratch(c, sc, n_people, has_mut));
-    if (has_mut) {
-        HIPC(hipMemcpyAsync(sc.mutseeds.p, c->h_seeds, T * sizeof(u32), hipMemcpyHostToDevice, st));
-    }
+    // for it on the host; the sampling stream does.
+    GEVC(claim_scratch(c, sc, st, !c->pend.active, n_people, has_mut));
+    if (has_mut) HIPC(hipMemcpyAsync(sc.mutseeds.p, c->h_seeds.p, T * sizeof(u32), hipMemcpyHostToDevice, st));
     GEVC(enqueue_sampling(c, sc, pop, n_people, has_mut, seed_reproduce, st));
     HIPC(hipEventRecord(sc.ev_sampled, st));
-    sc.presampled = true; sc.ps_pop = pop; sc.ps_seed = seed_reproduce; sc.ps_n_people = n_people; sc.ps_has_mut = has_mut;
+    sc.hs.kind = HeadStart::PRESAMPLE; sc.hs.dropped = false; sc.hs.pop = pop; sc.hs.n_people = n_people; sc.hs.has_mut = has_mut; sc.hs.seed = seed_reproduce;
     return GEV_OK;
 }
 // wait for all device work of the context (both streams) and collect pending kernel timings
@@ -2676,18 +2668,11 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
     // D-term is (+-0) * ... and the running sums stay +0.0 exactly -- nothing to copy, gev_compute_ad fills zeros.
     const size_t nd = n * nphen;
     const size_t bytes = 16 + 2 * nd * sizeof(double);
-    if (c->h_ad2_bytes[hbuf] < bytes) {
-        HIPC(hipStreamSynchronize(st));                      // (copies into the old buffer may be in flight on this stream)
-        void* old = c->h_ad2[hbuf];
-        c->h_ad2[hbuf] = nullptr; c->h_ad2_bytes[hbuf] = 0;
-        HIPC(hipHostMalloc(&c->h_ad2[hbuf], bytes * 5 / 4 + 4096, hipHostMallocDefault));
-        c->h_ad2_bytes[hbuf] = bytes * 5 / 4 + 4096;
-        if (old) (void)hipHostFree(old);
-    }
+    GEVC(c->h_ad2[hbuf].ensure(bytes, bytes * 5 / 4 + 4096, st));    // (copies into the old buffer may be in flight on this stream)
     bool dom_zero = true;
     for (const AdWork& a : aw) dom_zero &= a.vd == 0;
     c->ad_dom_zero2[hbuf] = dom_zero;
-    uint8_t* h = (uint8_t*)c->h_ad2[hbuf];
+    uint8_t* h = (uint8_t*)c->h_ad2[hbuf].p;
     HIPC(hipMemcpyAsync(h, c->d_flag.p, 4, hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(h + 16, c->d_add.p, nd * sizeof(double), hipMemcpyDeviceToHost, st));
     if (!dom_zero) HIPC(hipMemcpyAsync(h + 16 + nd * 8, c->d_dom.p, nd * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2718,7 +2703,7 @@ int gev_compute_ad(gev_ctx* c, int pop, double* additive, double* dominance, dou
         }
     }
     const size_t n = P.n_people;
-    const uint8_t* h = (const uint8_t*)c->h_ad2[hb];
+    const uint8_t* h = (const uint8_t*)c->h_ad2[hb].p;
     const size_t nd = n * nphen, ndc = n * (size_t)nchr * nphen;
     const u32 flag = *(const u32*)h;
     if (additive) memcpy(additive, h + 16, nd * sizeof(double));
@@ -4098,13 +4083,8 @@ static int ph_enqueue(gev_ctx* c)
                        (const double*)P.d_prev.as<double>(), P.prev_n, comp.as<double>(), keep.as<double>(), res);
     KCHECK();
     GEVC(ph_var(c, comp.as<double>(), n, 1, n, (unsigned)nphen * PH_COMP, comp_stats));           // CommFunc::var of A D G C E F P (:2023-2037)
-    if (H.h_res_bytes < res_bytes) {
-        if (H.h_res) { HIPC(hipStreamSynchronize(st)); (void)hipHostFree(H.h_res); }
-        H.h_res = nullptr; H.h_res_bytes = 0;
-        HIPC(hipHostMalloc(&H.h_res, res_bytes * 2 + 256, hipHostMallocDefault));
-        H.h_res_bytes = res_bytes * 2 + 256;
-    }
-    HIPC(hipMemcpyAsync(H.h_res, H.res.p, res_bytes, hipMemcpyDeviceToHost, st));
+    GEVC(H.h_res.ensure(res_bytes, res_bytes * 2 + 256, st));
+    HIPC(hipMemcpyAsync(H.h_res.p, H.res.p, res_bytes, hipMemcpyDeviceToHost, st));
     if (!H.ev) HIPC(hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
     HIPC(hipEventRecord(H.ev, st));
     return GEV_OK;
@@ -4154,7 +4134,7 @@ int gev_phenotypes_result(gev_ctx* c, int pop, uint32_t* glob_state_after, uint3
     HIPC(hipSetDevice(c->device));
     for (int attempt = 0;; attempt++) {
         HIPC(hipEventSynchronize(H.ev));
-        const u32* w = (const u32*)H.h_res;
+        const u32* w = (const u32*)H.h_res.p;
         const u32 flags = w[PHR_FLAGS];
         if (flags & FLAG_RNG_SHORT) { H.pending = false; P.comp_ok = false; P.drop_selection(); return fail(GEV_EDEVICE, "generation_phenotypes: the seed stream ran out of candidates (internal error)"); }
         if (flags & PHF_CAND_SHORT) {                        // acceptance far below pi/4 (or the test hook): the step again with more candidate pairs
