@@ -97,7 +97,7 @@ ABI_SYMBOLS = [
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "format_info_text", "dbg_format_g", "dbg_format_g_host",
     "set_founder_names", "format_interval_text", "dbg_format_interval_text_host",
-    "dbg_verify_planes", "dbg_output_chunk", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec",
+    "dbg_verify_planes", "dbg_output_chunk", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec", "dbg_sampling_path",
 ]
 
 
@@ -915,6 +915,20 @@ class GevContext:
         out = (C.c_ulonglong * 3)()
         self._call("dbg_prefilter_sweep", C.c_uint32(int(x_begin)), C.c_uint32(int(x_end)), out)
         return int(out[0]), int(out[1]), int(out[2])
+
+    def dbg_sampling_path(self):
+        """the sampling kernel the context launched last: 0 none yet, 1 k_sample_batched, 2 k_mut_sample + k_rec_sample,
+        3 k_rec_chain_wg, 4 k_rec_chain"""
+        v = C.c_int(-1)
+        self._call("dbg_sampling_path", C.byref(v))
+        return int(v.value)
+
+    def dbg_sim_loc_rec(self, pop, chr, seed, cap=4096):
+        """one Simulation::ras_sim_loc_rec call on the device: (breakpoints, the two rand() outputs that follow)"""
+        locs = np.zeros(cap, dtype=np.uint64); k = C.c_uint32(0); nx = (C.c_int * 2)()
+        self._call("dbg_sim_loc_rec", C.c_int(pop), C.c_int(chr), C.c_uint32(int(seed)), _p(locs), C.c_uint32(cap), C.byref(k), nx)
+        assert k.value <= cap
+        return locs[:k.value].copy(), (int(nx[0]), int(nx[1]))
 
     def set_overlap(self, on):
         """True (default): the dense stitch overlaps later work; False: one stream, every generation waits for its stitch"""

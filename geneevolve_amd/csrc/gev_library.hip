@@ -279,6 +279,12 @@ struct gev_ctx {
     bool eager_ad = true;                                    // compute A/D inside gev_reproduce (same enqueue, same sync)
     int stitch_mode = 0;           // 0 = work-list form (production, k_stitch_segments), 1 = gamete-major (k_stitch_rows)
     bool sample_batched = true;               // K1-K3 as eight tasks per wave (gev_sample8.h); GEV_SAMPLE_BATCHED=0: one task per wave
+    bool chain_wg = true;                     // no mutation map: a workgroup per link of the gamete chain (k_rec_chain_wg); GEV_CHAIN_WG=0: the one-wave form (k_rec_chain)
+    int sampling_path = 0;                    // the sampling kernel launched last (gev_dbg_sampling_path): 0 none yet, 1 k_sample_batched, 2 k_mut_sample + k_rec_sample, 3 k_rec_chain_wg, 4 k_rec_chain
+    size_t list_headroom = 48;                // spare list entries per haplotype row when a list buffer is (re)allocated; GEV_LIST_HEADROOM=0 (tests): just what is live, every generation overflows, grows and is enqueued again
+    bool ad_no_shared = false;                // GEV_AD_SHARED=0 (tests): force the per-haplotype effect lookup
+    bool ad_no_rp = false;                    // GEV_AD_RP_FAST=0 (tests): several root populations without the piecewise kernel
+    size_t table_ring_min = (size_t)(256 << 10);   // smallest pinned ring of the table uploads; GEV_TABLE_RING_BYTES (tests shrink it to force wrap-arounds)
     bool serialize = false;        // gev_set_overlap(0) / GEV_OVERLAP=0: wait for every stitch, everything on the main stream (kernel timings without interference)
     u32 seg_shift = 7;             // log2(16-byte chunks per row segment): 2 KiB.  Smaller: more table entries to manage per generation; larger: more bytes copied per
                                    // crossover.  Round 3 (free list kept across generations, one thread per table entry), config 2: 128 chunks 906, 256: 845, 512: 745
@@ -490,6 +496,11 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
     GEVC(h2d(c.get(), c->d_tables, &T, sizeof T));
     if (const char* e = getenv("GEV_OVERLAP")) c->serialize = atoi(e) == 0;
     if (const char* e = getenv("GEV_SAMPLE_BATCHED")) c->sample_batched = atoi(e) != 0;
+    if (const char* e = getenv("GEV_CHAIN_WG")) c->chain_wg = atoi(e) != 0;
+    if (const char* e = getenv("GEV_LIST_HEADROOM")) c->list_headroom = (size_t)atol(e);
+    if (const char* e = getenv("GEV_AD_SHARED")) c->ad_no_shared = atoi(e) == 0;
+    if (const char* e = getenv("GEV_AD_RP_FAST")) c->ad_no_rp = atoi(e) == 0;
+    if (const char* e = getenv("GEV_TABLE_RING_BYTES")) c->table_ring_min = (size_t)atol(e);
     if (const char* e = getenv("GEV_SEG_CHUNKS")) { const int v = atoi(e); u32 sh = 0; while ((1 << (sh + 1)) <= v) sh++; if (v >= 1 && sh <= 20) c->seg_shift = sh; }
     if (const char* e = getenv("GEV_ALIAS_ROWS")) c->alias_rows = atoi(e) != 0;
     if (const char* e = getenv("GEV_OVF_CAP")) { const long v = atol(e); if (v >= 1) c->bk_ovf_cap = c->nm_ovf_cap = (size_t)v; }
@@ -966,8 +977,7 @@ static int check_multipop(gev_ctx* c)
                 if (A.a.size() != B.a.size() || A.d.size() != B.d.size() || memcmp(&A.vd, &B.vd, sizeof(double)) ||
                     (A.a.size() && memcmp(A.a.data(), B.a.data(), A.a.size() * sizeof(double))) || (A.d.size() && memcmp(A.d.data(), B.d.data(), A.d.size() * sizeof(double)))) { c->ad_effects_shared = false; break; }
             }
-    static const bool no_shared = getenv("GEV_AD_SHARED") && atoi(getenv("GEV_AD_SHARED")) == 0;      // (tests: force the per-haplotype lookup)
-    if (no_shared) c->ad_effects_shared = false;
+    if (c->ad_no_shared) c->ad_effects_shared = false;      // GEV_AD_SHARED=0 (tests: force the per-haplotype lookup)
     // per (phen, chr): table of every population's a[] and d[] device arrays, stored with each population
     for (int pop = 0; pop < c->n_pop; pop++)
         for (int p = 0; p < c->nphen; p++)
@@ -1100,8 +1110,7 @@ static int upload_table(gev_ctx* c, DevBuf& dst, const void* src, size_t bytes, 
     if (!bytes) return GEV_OK;
     const size_t need = round_up(bytes, 64);
     if (c->h_ring.bytes < 4 * need) {
-        static const size_t ring_min = getenv("GEV_TABLE_RING_BYTES") ? (size_t)atol(getenv("GEV_TABLE_RING_BYTES")) : (size_t)(256 << 10);   // (tests shrink it to force wrap-arounds)
-        GEVC(c->h_ring.ensure(4 * need, std::max<size_t>(8 * need, ring_min), st));
+        GEVC(c->h_ring.ensure(4 * need, std::max<size_t>(8 * need, c->table_ring_min), st));
         c->h_ring_off = 0;
     }
     if (c->h_ring_off + need > c->h_ring.bytes) { HIPC(hipStreamSynchronize(c->stream)); HIPC(hipStreamSynchronize(st)); c->h_ring_off = 0; }
@@ -1207,19 +1216,21 @@ static int enqueue_sampling(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_
         // eight tasks per wave, mutations and gametes in one kernel; the rare slow tasks are finished in place
         const unsigned batch_blocks = (unsigned)std::min<size_t>(ceil_div(ceil_div(T, SB_TASKS), 4), task_blocks);
         hipLaunchKernelGGL(k_sample_batched, dim3(batch_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, seed_reproduce, seed_ptr, T, sd);
+        c->sampling_path = 1;
     } else if (has_mut) {
         hipLaunchKernelGGL(k_mut_sample, dim3(task_blocks), dim3(256), 0, st, Tb, chrs, nchr, mseeds, T, sd);
         hipLaunchKernelGGL(k_rec_sample, dim3(task_blocks), dim3(256), 0, st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd);
+        c->sampling_path = 2;
     } else {
         // no mutation map: the gametes of a generation form ONE serial chain (src/Simulation.cpp:2447-2455).  A workgroup per link
         // (k_rec_chain_wg); GEV_CHAIN_WG=0: the one-wave form
-        static const bool wg = !(getenv("GEV_CHAIN_WG") && atoi(getenv("GEV_CHAIN_WG")) == 0);
-        if (wg) {
+        if (c->chain_wg) {
             size_t rows_all = 0;
             for (int k = 0; k < nchr; k++) rows_all += c->pop[pop].cs[k].rbp.size();
             const u32 thr_lds = rows_all <= 2048 ? (u32)rows_all : 0u;            // thresholds of all chromosomes in LDS when they fit into 32 KiB
             hipLaunchKernelGGL(k_rec_chain_wg, dim3(1), dim3(CHAIN_THREADS), (size_t)thr_lds * sizeof(GevThr), st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd, thr_lds);
-        } else hipLaunchKernelGGL(k_rec_chain, dim3(1), dim3(64), 0, st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd);
+            c->sampling_path = 3;
+        } else { hipLaunchKernelGGL(k_rec_chain, dim3(1), dim3(64), 0, st, Tb, chrs, nchr, seed_reproduce, seed_ptr, T, sd); c->sampling_path = 4; }
     }
     KCHECK();
     HIPC(hipEventRecord(sc.t[1], st));
@@ -1235,14 +1246,13 @@ static void lp_geometry(const ChrStatic& S, u32& nseg, u32& lgw)
     while ((span >> lgw) + 1 > max_seg) lgw++;
     nseg = (u32)(span >> lgw) + 1;
 }
-static size_t lp_arena_entries(size_t rows, size_t live, int n_active_chr)
+static size_t lp_arena_entries(size_t rows, size_t live, int n_active_chr, bool tight /* GEV_LIST_HEADROOM=0 */)
 {
     // arena = room for the pieces of many generations (each appends a few entries per row): a tenth of the device memory, shared
     // out over the active chromosomes, at most 4096 entries per row (GEV_LIST_ARENA: entries per row); when it fills up, the
     // pieces are compacted (pieces -> whole lists -> pieces).  GEV_LIST_HEADROOM=0: just what is live (tests: every generation
     // then overflows, grows and is enqueued again)
     const size_t per_row_env = getenv("GEV_LIST_ARENA") ? (size_t)atol(getenv("GEV_LIST_ARENA")) : 0;      // (read at every call: tests set it per case)
-    const bool tight = getenv("GEV_LIST_HEADROOM") && atol(getenv("GEV_LIST_HEADROOM")) == 0;
     if (tight) return live + 16;
     size_t per_row = per_row_env;
     if (!per_row) {
@@ -1268,8 +1278,8 @@ static int lp_import_all(gev_ctx* c, PopState& P, int k, hipStream_t st)
         GEVC(lp.mtab[b].ensure(tab_rows * lp.nseg * sizeof(uint2), st));
     }
     int n_active = 0; for (int q = 0; q < c->nchr; q++) n_active += c->chr_active[q] ? 1 : 0;
-    if (track) GEVC(lp.parena.ensure(lp_arena_entries(rows, live_p, n_active) * sizeof(LpPart), st));
-    GEVC(lp.marena.ensure(std::max<size_t>(lp_arena_entries(rows, live_m, n_active), 16) * sizeof(u64), st));
+    if (track) GEVC(lp.parena.ensure(lp_arena_entries(rows, live_p, n_active, c->list_headroom == 0) * sizeof(LpPart), st));
+    GEVC(lp.marena.ensure(std::max<size_t>(lp_arena_entries(rows, live_m, n_active, c->list_headroom == 0), 16) * sizeof(u64), st));
     GEVC(lp.ctr.ensure(4 * sizeof(u32), st));
     HIPC(hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(u32), st));
     if (rows)
@@ -1362,7 +1372,6 @@ static void lists_changed_in_csr(gev_ctx* c, PopState& P)
 {
     for (int k = 0; k < c->nchr; k++) { P.st[k].csr_valid = true; P.st[k].lp.valid = false; }
 }
-static const size_t LIST_HEADROOM = getenv("GEV_LIST_HEADROOM") ? (size_t)atol(getenv("GEV_LIST_HEADROOM")) : 48;    // spare list entries per haplotype row when a list buffer is (re)allocated (tests force redos with 0)
 // K4/K6 + grouping: everything of the small work that needs the couples (parents) on top of the sampling results.
 // Every kernel covers ALL active chromosomes in one launch (blockIdx.y = entry of the generation's ChrWork / CvWork table).
 // work tables of the generation (one ChrWork per active chromosome, one CvWork per (phenotype, active chromosome)): list buffers
@@ -1395,7 +1404,7 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
         ChrState::LpState& lp = cs.lp;
         const size_t rows_cur = 2 * P.n_phys;
         const size_t guess_p = std::max<size_t>(4 * (size_t)lp.p_last, 8 * rows), guess_m = std::max<size_t>(4 * (size_t)lp.m_last, 4 * rows);
-        const bool tight = LIST_HEADROOM == 0;
+        const bool tight = c->list_headroom == 0;
         // room the arenas must have on top of what is used: an attempt overflowed (its status block holds what it wanted to append) ...
         size_t need_p = lp.grow_p ? (size_t)lp.p_last * 5 / 4 + 1024 : 0, need_m = lp.grow_m ? (size_t)lp.m_last * 5 / 4 + 1024 : 0;
         if (lp.valid && !tight) {
@@ -2649,7 +2658,7 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
             // several root populations with their own CV effects: the piecewise kernel when every CV file is in position order
             bool sorted_all = c->rp_bits >= 1 && c->rp_bits <= 3;
             for (const AdWork& a : aw) sorted_all &= a.cols_sorted != 0;
-            static const bool no_rp = getenv("GEV_AD_RP_FAST") && atoi(getenv("GEV_AD_RP_FAST")) == 0;
+            const bool no_rp = c->ad_no_rp;
             const dim3 grid((unsigned)ceil_div(n, 256), nw);
             const size_t lds = (size_t)ADRP_PIECE * ((size_t)c->n_pop * 2 + 5) * sizeof(double);
             if (sorted_all && !no_rp && c->rp_bits == 1) hipLaunchKernelGGL((k_ad_accumulate_rp<1>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
@@ -4695,6 +4704,12 @@ int gev_dbg_rand(gev_ctx* c, uint32_t seed, uint32_t n, int* out)
     KCHECK();
     HIPC(hipMemcpyAsync(out, c->d_tmp.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
+    return GEV_OK;
+}
+int gev_dbg_sampling_path(gev_ctx* c, int* path)
+{
+    if (!c || !path) return fail(GEV_EINVAL, "null");
+    *path = c->sampling_path;
     return GEV_OK;
 }
 int gev_dbg_sim_loc_rec(gev_ctx* c, int pop, int chr, uint32_t seed, uint64_t* locs, uint32_t cap, uint32_t* n, int next2[2])

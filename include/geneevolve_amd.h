@@ -91,8 +91,12 @@ const char* gev_last_error(void);
 const char* gev_version(void);
 
 /* device < 0: use the current HIP device.
- * The environment knobs the library reads, all of them (none changes a result; the first six are read here, the others where they
- * are used).  Tests set them to force rare paths or to compare two forms of a computation; GEV_TRACE_HOST is diagnostic output:
+ * The environment knobs the library reads, all of them (none changes a result).  Tests set them to force rare paths or to compare
+ * two forms of a computation; GEV_TRACE_HOST is diagnostic output.  PER CONTEXT, read here and kept in the context (a test may set
+ * one, create a context, and set another for the next context of the same process): GEV_OVERLAP, GEV_SAMPLE_BATCHED,
+ * GEV_STITCH_MODE, GEV_ALIAS_ROWS, GEV_SEG_CHUNKS, GEV_OVF_CAP, GEV_LIST_HEADROOM, GEV_TABLE_RING_BYTES, GEV_CHAIN_WG, GEV_AD_SHARED,
+ * GEV_AD_RP_FAST.  PER CALL, read whenever they are used: GEV_LIST_SEGS, GEV_LIST_ARENA, GEV_CHAIN_MAX_TASKS, GEV_LP_LITERAL,
+ * GEV_LP_LANES.  PER PROCESS, read once when the library is loaded: GEV_TRACE_HOST.
  *   GEV_OVERLAP=0|1             initial stream overlap mode (gev_set_overlap; default 1)
  *   GEV_SAMPLE_BATCHED=0        one sampling task per wave (the round-1 kernels) instead of eight in one kernel
  *   GEV_STITCH_MODE=0|1         dense stitch kernel (gev_set_stitch_mode; default 0, the segment work list)
@@ -681,6 +685,10 @@ double gev_dbg_canonical(uint32_t a, uint32_t b);
 int    gev_dbg_rand(gev_ctx*, uint32_t seed, uint32_t n, int* out);
 int    gev_dbg_sim_loc_rec(gev_ctx*, int pop, int chr, uint32_t seed, uint64_t* locs, uint32_t cap,
                            uint32_t* n, int next2[2]);
+/* gev_dbg_sampling_path: the sampling kernel the context launched last (which of the forms above a generation really took):
+ * 0 = none yet, 1 = k_sample_batched, 2 = k_mut_sample + k_rec_sample (GEV_SAMPLE_BATCHED=0), 3 = k_rec_chain_wg (no mutation map),
+ * 4 = k_rec_chain (no mutation map, GEV_CHAIN_WG=0).  gev_dbg_sim_loc_rec does not change it. */
+int    gev_dbg_sampling_path(gev_ctx*, int* path);
 
 #ifdef __cplusplus
 }

@@ -301,14 +301,18 @@ def test_gpu_vs_oracle_serial_chain_mode(gpu_lib, oracle_lib, monkeypatch, wg):
     and hot maps (more hits than a scanning wave's list holds: the link falls back to the one-wave walk; more than GEV_BK_CAP
     crossovers per gamete: overflow records), maps longer than one 2048-row round, thresholds in LDS and (many rows) in global memory."""
     monkeypatch.setenv("GEV_CHAIN_WG", str(wg))
+    want = 3 if wg else 4                   # gev_dbg_sampling_path: 3 = k_rec_chain_wg, 4 = k_rec_chain
+
+    def at_end(g):
+        assert g.dbg_sampling_path() == want, f"GEV_CHAIN_WG={wg}: sampling path {g.dbg_sampling_path()}, expected {want}"
     cfg = SyntheticConfig(200, 3000, nchr=3, chrom_bp=1_000_000, map_step=1000, rec_per_row=3e-3, n_cv=100, seed=5, with_mutation=False)   # 3 x 1001 rows: thresholds from global memory
-    run_pair(gpu_lib, oracle_lib, cfg, n_gen=4, seed=99)
+    run_pair(gpu_lib, oracle_lib, cfg, n_gen=4, seed=99, at_end=at_end)
     cfg = SyntheticConfig(60, 3000, nchr=1, chrom_bp=1_000_000, map_step=400, rec_per_row=3e-3, with_mutation=False, n_cv=100, seed=6)      # 2501 rows: two rounds
-    run_pair(gpu_lib, oracle_lib, cfg, n_gen=2, seed=98)
+    run_pair(gpu_lib, oracle_lib, cfg, n_gen=2, seed=98, at_end=at_end)
     cfg = SyntheticConfig(60, 3000, nchr=1, chrom_bp=1_000_000, map_step=1000, rec_per_row=2e-3, with_mutation=False, n_cv=100, seed=8)     # 1001 rows: thresholds in LDS
-    run_pair(gpu_lib, oracle_lib, cfg, n_gen=3, seed=96)
+    run_pair(gpu_lib, oracle_lib, cfg, n_gen=3, seed=96, at_end=at_end)
     cfg = SyntheticConfig(30, 3000, nchr=2, chrom_bp=400_000, map_step=1000, rec_per_row=0.4, with_mutation=False, n_cv=100, seed=7)       # ~160 crossovers per gamete
-    run_pair(gpu_lib, oracle_lib, cfg, n_gen=2, seed=97)
+    run_pair(gpu_lib, oracle_lib, cfg, n_gen=2, seed=97, at_end=at_end)
 
 
 def test_serial_chain_refuses_sizes_that_would_run_for_minutes(gpu_lib, monkeypatch):
