@@ -86,7 +86,7 @@ ABI_SYMBOLS = [
     "last_error", "version", "create", "destroy", "set_rmap", "set_mutmap", "set_snps", "set_cvs",
     "upload_founders", "upload_cv_founders", "synth_founders", "synth_cv_founders", "init_gen0",
     "reproduce", "presample", "compute_ad", "scale_ad_compute_gef", "set_ad", "get_cv_freq", "migrate", "export_size", "export_rows", "remove_rows",
-    "import_rows", "download_haps", "download_snp_major", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
+    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
     "pop_size", "plane_ptr", "reserve", "set_chr_active", "set_dense_state", "materialize", "materialize_pops", "materialize_bed", "stream", "last_reproduce_ms", "set_track_intervals", "set_stitch_mode", "sync", "timing_totals", "stitch_totals", "reproduce_begin", "reproduce_end", "presample_sex", "set_overlap",
     "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
     "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
@@ -209,6 +209,17 @@ class GevLibrary:
         self.check(rc)
         return out, n
 
+
+    def dbg_snp_counts_host(self, bits, L, snp_begin=0, n_snps=None):
+        """(n_het, n_hom_alt) of SNPs [snp_begin, +n_snps) by the library's genotype counter compiled for the host (no device needed).
+        bits: uint64 [2 * n_ind][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them"""
+        bits = _arr(bits, np.uint64)
+        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
+        n_snps = L - snp_begin if n_snps is None else n_snps
+        het = np.empty(n_snps, dtype=np.uint32); hom = np.empty(n_snps, dtype=np.uint32)
+        self.check(self._f("dbg_snp_counts_host")(_p(bits), C.c_size_t(bits.shape[1]), C.c_size_t(bits.shape[0] // 2), C.c_size_t(L),
+                                                  C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(het), _p(hom)))
+        return het, hom
 
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
@@ -745,6 +756,21 @@ class GevContext:
         out = _rows_out(n_snps, words_for(2 * self.pop_size(pop)), stride_words)
         self._call("download_snp_major", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(out.shape[1]))
         return out
+
+    def snp_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
+        """-> (n_het, n_hom_alt), uint32 [n_snps]: per SNP of the range, the individuals of [ind_begin, +n_ind) that are heterozygous /
+        carry allele 1 twice, counted on the device from the resident rows (mutations applied)"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        het = np.empty(max(n_snps, 0), dtype=np.uint32); hom = np.empty(max(n_snps, 0), dtype=np.uint32)
+        self._call_new("snp_genotype_counts", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), C.c_size_t(ind_begin), C.c_size_t(n_ind), _p(het), _p(hom))
+        return het, hom
+
+    def allele_freq(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
+        """-> float64 [n_snps]: frequency of allele 1 among the 2 * n_ind haplotypes of the individuals of the range"""
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        het, hom = self.snp_genotype_counts(pop, chr, snp_begin, n_snps, ind_begin, n_ind)
+        return (het.astype(np.float64) + 2.0 * hom) / (2.0 * n_ind)
 
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
         """bytes of the reference's .hap file (format_hap::write_hap) for the given SNP lines"""

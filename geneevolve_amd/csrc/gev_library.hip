@@ -21,6 +21,7 @@
 
 #include "gev_kernels.h"
 #include "gev_outputs.h"
+#include "gev_snpcount.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -297,6 +298,7 @@ struct gev_ctx {
                           bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0;
                           int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
     DevBuf d_snpmajor, d_text;
+    DevBuf d_snpcnt;               // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
@@ -3762,6 +3764,56 @@ int gev_format_bed(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps
     return format_snp_major(c, pop, chr, "format_bed", snp_begin, n_snps, bpl, ceil_div(2 * n_people, 64) * 8, out, out_bytes, [&](size_t ns, size_t stride) {
         hipLaunchKernelGGL(k_format_bed, dim3((unsigned)ceil_div(ns * bpl, 256)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, n_people, (u32)ns, c->d_text.as<uint8_t>());
     });
+}
+// ---- genotype counts per SNP (gev_snpcount.h) -------------------------------------------------
+// n_het / n_hom_alt of SNPs [snp_begin, +n_snps) over individuals [ind_begin, +n_ind): the plane pass reads the rows in place, the
+// mutation overlay corrects the counts, both add into c->d_snpcnt.  Nothing is staged, so gev_dbg_output_chunk has nothing to cap.
+int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, uint32_t* n_het, uint32_t* n_hom_alt)
+{
+    const char* who = "snp_genotype_counts";
+    GEVC(output_begin(c, pop, chr, who, true));
+    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr]; ChrState& cs = P.st[chr];
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, S.L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
+    if (n_snps && (!n_het || !n_hom_alt)) return fail(GEV_EINVAL, "%s: null output vector (n_het and n_hom_alt take %zu counts each)", who, n_snps);
+    if (!n_snps) return GEV_OK;
+    if (!n_ind) { memset(n_het, 0, n_snps * sizeof(u32)); memset(n_hom_alt, 0, n_snps * sizeof(u32)); return GEV_OK; }
+    GEVC(ensure_csr(c, pop));                                           // the overlay reads whole lists
+    hipStream_t st = c->stream;
+    GEVC(c->d_snpcnt.ensure(2 * n_snps * sizeof(u32), st));
+    u32* d_het = c->d_snpcnt.as<u32>(); u32* d_hom = d_het + n_snps;
+    HIPC(hipMemsetAsync(d_het, 0, 2 * n_snps * sizeof(u32), st));
+    const size_t q_first = snp_begin / SNPC_LOCI, n_q = (snp_begin + n_snps - 1) / SNPC_LOCI - q_first + 1;     // the chunks that hold a SNP of the range
+    const size_t col_blocks = (q_first + n_q - 1) / SNPC_COLS - q_first / SNPC_COLS + 1;                        // the 64-chunk pieces of a row they lie in
+    // blocks of individuals: several rounds of workgroups over the device (1024 are resident at a time) when the columns alone do
+    // not give them, but every wave keeps a run of at least two counter periods, and a workgroup's packed partial stays in range
+    const size_t min_ind = (size_t)SNPC_WAVES * 2 * (GEV_SNPC_F + 1);
+    size_t splits = std::min(ceil_div(8192, col_blocks), std::max<size_t>(n_ind / min_ind, 1));
+    size_t ind_per_block = ceil_div(n_ind, splits);
+    if (ind_per_block > SNPC_MAX_IND) ind_per_block = SNPC_MAX_IND;
+    splits = ceil_div(n_ind, ind_per_block);
+    if (splits > 65535) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals are more than one call counts", who, n_ind);
+    const auto plane_pass = S.seg_shift >= 6 ? k_snp_counts<true> : k_snp_counts<false>;                        // a wave's 1 KiB of a row in one segment unit, or not
+    hipLaunchKernelGGL(plane_pass, dim3((unsigned)col_blocks, (unsigned)splits), dim3(SNPC_WAVES * 64), 0, st, row_map(P, chr), ind_begin, n_ind, (u32)ind_per_block,
+                       (u32)q_first, (u32)n_q, (u32)snp_begin, (u32)n_snps, d_het, d_hom);
+    hipLaunchKernelGGL(k_snp_counts_apply_mut, dim3((unsigned)ceil_div(n_ind, 256)), dim3(256), 0, st, row_map(P, chr), ind_begin, n_ind,
+                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)snp_begin, (u32)n_snps, d_het, d_hom);
+    KCHECK();
+    HIPC(hipMemcpyAsync(n_het, d_het, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(n_hom_alt, d_hom, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the counter of gev_snpcount.h compiled for the host on haplotype-major rows in host memory: no device, no context
+int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L, size_t snp_begin, size_t n_snps,
+                            uint32_t* n_het, uint32_t* n_hom_alt)
+{
+    const char* who = "dbg_snp_counts_host";
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
+    if (n_snps && (!n_het || !n_hom_alt)) return fail(GEV_EINVAL, "%s: null output vector", who);
+    if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    gev_snpc_count_rows_host(bits, row_stride_words, n_ind, snp_begin, n_snps, n_het, n_hom_alt);
+    return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------
 // genotype columns of the PLINK .ped text, one line per individual (the caller writes the six id columns in front)

@@ -142,6 +142,14 @@ public:
         if (rc != GEV_OK) { printf("%s\n", gev_last_error()); return false; }                         // error convention of the reference: message + false
         return true;
     }
+    // per SNP of [snp_begin, +n_snps) over individuals [ind_begin, +n_ind) of the current generation: heterozygous individuals and
+    // individuals with allele 1 on both haplotypes (alt allele count = n_het + 2 * n_hom_alt), counted on the device
+    void snp_genotype_counts(int ipop, int ichr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                             std::vector<uint32_t>& n_het, std::vector<uint32_t>& n_hom_alt)
+    {
+        n_het.resize(n_snps); n_hom_alt.resize(n_snps);
+        check(gev_snp_genotype_counts(ctx, ipop, ichr, snp_begin, n_snps, ind_begin, n_ind, n_het.data(), n_hom_alt.data()));
+    }
     bool ras_do_migration(const std::vector<gev_move>& moves) { check(gev_migrate(ctx, moves.data(), moves.size())); return true; }   // :877
 };
 

@@ -554,6 +554,24 @@ int gev_download_snp_major(gev_ctx*, int pop, int chr, size_t snp_begin, size_t 
 int gev_format_hap_text(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, char* out, size_t out_bytes);
 int gev_format_bed(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, uint8_t* out, size_t out_bytes);
 int gev_format_vcf_gt(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, char* out, size_t out_bytes);
+/* ---- genotype counts per SNP: allele frequencies and heterozygosity without a dump -------------------------------------------
+ * per SNP of [snp_begin, +n_snps), over individuals [ind_begin, +n_ind) of the current generation, new mutations applied:
+ *   n_het[j]     = individuals whose two haplotypes differ at SNP snp_begin+j
+ *   n_hom_alt[j] = individuals with allele 1 on both
+ * (alt allele count = n_het + 2*n_hom_alt; hom-ref = n_ind - n_het - n_hom_alt).  Counted on the device from the resident rows where
+ * they lie (a positional popcount over the haplotype-major planes plus a sparse correction from the mutation lists: no transpose, no
+ * staging copy, two vectors of n_snps counts come back); rows 2i and 2i+1 are individual i's haplotypes.  Begins like the other
+ * output calls: a pending order (gev_migrate) is materialised, the planes are waited for.  GEV_ESTATE on a context without genotype
+ * planes (gev_set_dense_state 0), for an inactive chromosome and for a population without a current generation; GEV_EINVAL for a range
+ * beyond L / n_people and for a NULL vector with n_snps > 0.  n_snps == 0 touches nothing, n_ind == 0 writes zeros.  Returns when both
+ * vectors are in the caller's memory.  The device vectors are created by the first call. */
+int gev_snp_genotype_counts(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                            uint32_t* n_het, uint32_t* n_hom_alt);
+/* the same counter (csrc/gev_snpcount.h) built for the host, on haplotype-major rows in host memory as gev_download_haps returns them
+ * (rows 2i, 2i+1 = individual i, row_stride_words >= ceil(L/64)), over all n_ind individuals: no device, no context.  Words of a row
+ * that hold no SNP of the range are not read. */
+int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L,
+                            size_t snp_begin, size_t n_snps, uint32_t* n_het, uint32_t* n_hom_alt);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */

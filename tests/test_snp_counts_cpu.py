@@ -1,0 +1,73 @@
+"""The vertical (bit-sliced) genotype counter of geneevolve_amd/csrc/gev_snpcount.h compiled for the host, gev_dbg_snp_counts_host: the
+same add / overflow / expand code the device pass runs, on haplotype-major rows in host memory, against a plain numpy column count.
+No device is needed."""
+import numpy as np
+import pytest
+
+from geneevolve_amd import capi
+from tests.snp_counts_inputs import F, numpy_counts, random_rows
+
+N_IND = (0, 1, 2, F - 1, F, F + 1, 3 * F + 5)
+LOCI = (1, 31, 32, 33, 127, 128, 129, 5000)
+
+
+def padded(words, extra, rs):
+    """the rows at a wider stride, the pad words full of garbage"""
+    out = rs.randint(0, 1 << 62, size=(words.shape[0], words.shape[1] + extra)).astype(np.uint64) | np.uint64(1 << 63)
+    out[:, :words.shape[1]] = words
+    return out
+
+
+def snp_ranges(L):
+    """whole range, single SNPs at both ends, ranges that begin and end inside a word, inside a 128-bit chunk, and at L"""
+    r = {(0, L), (0, 1), (L - 1, 1), (L, 0), (0, 0)}
+    for a, b in ((5, 17), (31, 33), (63, 65), (70, 120), (100, 140), (127, 129), (64, 128), (130, 4097), (4999, 5000), (1, L), (L // 2, L)):
+        if a < b <= L:
+            r.add((a, b - a))
+    return sorted(r)
+
+
+@pytest.mark.parametrize("L", LOCI)
+@pytest.mark.parametrize("n_ind", N_IND)
+def test_host_counter_equals_numpy(gpu_lib, n_ind, L):
+    rs = np.random.RandomState(1000 * L + n_ind)
+    bits = random_rows(rs, n_ind, L)
+    words = capi.pack_rows(bits) if n_ind else np.zeros((0, capi.words_for(L)), dtype=np.uint64)
+    if n_ind > 2 and L > 2:
+        assert not bits[:, 0].any() and bits[:, -1].all()
+    wide = padded(words, 3, rs)
+    for s0, ns in snp_ranges(L):
+        want = numpy_counts(bits, s0, ns)
+        for rows, what in ((words, "tight rows"), (wide, "stride + 3 words of garbage")):
+            het, hom = gpu_lib.dbg_snp_counts_host(rows, L, s0, ns)
+            assert het.dtype == np.uint32 and len(het) == len(hom) == ns
+            assert np.array_equal(het, want[0]), f"n_het, {n_ind} individuals x {L} SNPs, SNPs [{s0},{s0 + ns}), {what}"
+            assert np.array_equal(hom, want[1]), f"n_hom_alt, {n_ind} individuals x {L} SNPs, SNPs [{s0},{s0 + ns}), {what}"
+
+
+def test_garbage_beyond_L_in_the_last_word_is_not_counted(gpu_lib):
+    """bits of the last word beyond L set in every row: inside the words the counter reads, outside every range it may report"""
+    rs = np.random.RandomState(5)
+    n_ind, L = 2 * F + 3, 70
+    bits = random_rows(rs, n_ind, L)
+    words = capi.pack_rows(bits).copy()
+    words[:, -1] |= np.uint64(0xFFFFFFFFFFFFFFFF) << np.uint64(L - 64)
+    for s0, ns in ((0, L), (64, 6), (69, 1), (3, 66)):
+        het, hom = gpu_lib.dbg_snp_counts_host(words, L, s0, ns)
+        want = numpy_counts(bits, s0, ns)
+        assert np.array_equal(het, want[0]) and np.array_equal(hom, want[1]), (s0, ns)
+
+
+def test_host_counter_refusals(gpu_lib):
+    f = gpu_lib._f("dbg_snp_counts_host")
+    words = np.zeros((4, 2), dtype=np.uint64)
+    out = np.zeros(128, dtype=np.uint32)
+    z = capi.C.c_size_t
+
+    def rc(bits, stride, n_ind, L, s0, ns, het, hom):
+        return f(capi._p(bits), z(stride), z(n_ind), z(L), z(s0), z(ns), capi._p(het), capi._p(hom))
+    assert rc(words, 2, 2, 100, 90, 11, out, out) == -1 and "beyond" in gpu_lib.last_error()
+    assert rc(words, 2, 2, 100, 0, 100, None, out) == -1 and "null" in gpu_lib.last_error()
+    assert rc(words, 1, 2, 100, 0, 100, out, out) == -1 and "words" in gpu_lib.last_error()
+    assert rc(None, 0, 0, 100, 0, 100, out, out.copy()) == 0                   # nobody to count: zeros, no row is read
+    assert rc(None, 0, 2, 100, 100, 0, None, None) == 0                        # no SNP asked for: nothing is touched
