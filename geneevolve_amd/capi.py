@@ -97,7 +97,7 @@ ABI_SYMBOLS = [
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "format_info_text", "dbg_format_g", "dbg_format_g_host",
     "set_founder_names", "format_interval_text", "dbg_format_interval_text_host",
-    "dbg_verify_planes", "dbg_output_chunk", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec", "dbg_sampling_path",
+    "dbg_verify_planes", "dbg_output_chunk", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec", "dbg_sampling_path", "dbg_ad_path",
 ]
 
 
@@ -947,6 +947,13 @@ class GevContext:
         3 k_rec_chain_wg, 4 k_rec_chain"""
         v = C.c_int(-1)
         self._call("dbg_sampling_path", C.byref(v))
+        return int(v.value)
+
+    def dbg_ad_path(self):
+        """the A/D kernel the context launched last: 0 none yet, 1 k_ad_accumulate, 2 k_ad_accumulate_rp, 3 / 4 k_ad_accumulate_tab
+        (rows staged / read directly), 5 k_ad_accumulate_wide; + 16: the wide kernel built its terms from the column counts"""
+        v = C.c_int(-1)
+        self._call("dbg_ad_path", C.byref(v))
         return int(v.value)
 
     def dbg_sim_loc_rec(self, pop, chr, seed, cap=4096):

@@ -133,7 +133,7 @@ struct ChrWork {
     int chr;
 };
 struct CvWork {
-    u32* cvp_alt; const u32* cvp_cur; const u64* pos_sorted; u32* counts;      // counts: allele count per CV column (k_cv_sum_partials / k_cv_count / k_cv_newmut add, k_cv_table / k_cv_freq consume and clear)
+    u32* cvp_alt; const u32* cvp_cur; const u64* pos_sorted; u32* counts;      // counts: allele count per CV column (k_cv_count / k_cv_newmut / k_cv_finish / k_cv_newmut_sum add; k_cv_finish or k_ad_accumulate_wide consumes and clears)
     uint16_t* partial;                                                        // [blocks of k_stitch_small][1024] allele counts of the block's rows per column
     u64 bp0, bp_end;
     u32 stride_w32, sub_w32, C;
@@ -1027,10 +1027,9 @@ __global__ void __launch_bounds__(SMALL_THREADS) k_stitch_small(const CvWork* __
 // (offspring, chromosome) task; a position that cannot be a CV position is dropped with one LDS read (64-Kbit hash bitmap of the
 // CV grid), so the lookups run for a handful of mutations per generation.  The column's allele count moves with the flip.
 __device__ __forceinline__ u32 cv_hash16(u64 x) { return (u32)((x * 0x9E3779B97F4A7C15ull) >> 48); }
-__global__ void __launch_bounds__(256) k_cv_newmut(const CvWork* __restrict__ Vt, const ChrWork* __restrict__ Wt, size_t n_people, int nchr, SampleDev sd, int count_cols)
+// (the body of one block of 256 offspring, shared by k_cv_newmut and k_cv_newmut_sum; s_bits: 2048 words of LDS)
+__device__ __forceinline__ void cv_newmut_block(const CvWork& v, const ChrWork* __restrict__ Wt, size_t n_people, int nchr, const SampleDev& sd, int count_cols, u32* s_bits)
 {
-    __shared__ u32 s_bits[2048];
-    const CvWork& v = Vt[blockIdx.y];
     for (u32 q = threadIdx.x; q < 2048; q += 256) s_bits[q] = 0;
     __syncthreads();
     for (u32 c = threadIdx.x; c < v.C; c += 256) { const u32 h = cv_hash16(v.pos_sorted[c]); atomicOr(&s_bits[h >> 5], 1u << (h & 31)); }
@@ -1070,6 +1069,39 @@ __global__ void __launch_bounds__(256) k_cv_newmut(const CvWork* __restrict__ Vt
         }
     }
 }
+__global__ void __launch_bounds__(256) k_cv_newmut(const CvWork* __restrict__ Vt, const ChrWork* __restrict__ Wt, size_t n_people, int nchr, SampleDev sd, int count_cols)
+{
+    __shared__ u32 s_bits[2048];
+    cv_newmut_block(Vt[blockIdx.y], Wt, n_people, nchr, sd, count_cols, s_bits);
+}
+// The launch behind k_stitch_small when it has counted the columns and k_ad_accumulate_wide follows (the generation chain of one
+// root population / shared effects, CV files in position order): the first `mut_blocks` blocks of a work entry are k_cv_newmut's
+// (none without a mutation map), the others add their slice of k_stitch_small's per-block partial counts to the column counters --
+// block (mut_blocks + s * ceil(C_max / 256) + x) the columns [256 x, 256 x + 256) of the partial blocks of slice s of `slices`.
+// Both only add to counts[] with commutative atomics, so neither waits for the other; the A/D kernel behind this launch finds the
+// counts complete, computes its terms from them and clears them.  One thread resets the NaN flag of the A/D kernels.
+__global__ void __launch_bounds__(256) k_cv_newmut_sum(const CvWork* __restrict__ Vt, const ChrWork* __restrict__ Wt, size_t n_people, int nchr, SampleDev sd,
+                                                       u32 mut_blocks, u32 col_blocks, u32 slices, u32 n_blocks, u32* __restrict__ nan_flag)
+{
+    __shared__ u32 s_bits[2048];
+    const CvWork& v = Vt[blockIdx.y];
+    if (blockIdx.x < mut_blocks) { cv_newmut_block(v, Wt, n_people, nchr, sd, 1, s_bits); return; }      // (block-uniform)
+    const u32 r = blockIdx.x - mut_blocks, slice = r / col_blocks, col = (r - slice * col_blocks) * 256 + threadIdx.x;
+    if (r == 0 && blockIdx.y == 0 && threadIdx.x == 0) *nan_flag = 0xffffffffu;     // (the A/D kernel reports the first NaN individual with atomicMin)
+    if (col >= v.C) return;
+    const u32 per = (n_blocks + slices - 1) / slices, b0 = slice * per, b1 = min(b0 + per, n_blocks);
+    u32 n = 0;
+    u32 b = b0;
+    for (; b + 8 <= b1; b += 8) {                           // eight independent loads in flight (next to the dense stitch a dependent load costs microseconds)
+        u32 w[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = v.partial[(size_t)(b + j) * 1024 + col];
+#pragma unroll
+        for (int j = 0; j < 8; j++) n += w[j];
+    }
+    for (; b < b1; b++) n += v.partial[(size_t)b * 1024 + col];
+    if (n) atomicAdd(&v.counts[col], n);
+}
 
 // ------------------------------------------------------------------------------------------
 // K6/K7: ras_find_cv + ras_compute_AD (src/Simulation.cpp:2624-2815)
@@ -1105,13 +1137,40 @@ __global__ void __launch_bounds__(256) k_cv_count(const AdWork* __restrict__ At,
     for (; r < r1; r++) n += (col[r * stride] >> sh) & 1u;
     if (n) atomicAdd(&counts[c], n);
 }
+// Allele frequency of a CV column from its allele count, and the three possible A- and D-terms of the CV, with EXACTLY the
+// expressions of the reference's per-individual loop (:2686-2712: same operations, same order, no contraction, so the sums stay
+// bit-identical): t = { (0-2p)alpha, (1-2p)alpha, (2-2p)alpha, -2pp*d, 2pq*d, -2qq*d }.  One root population (or shared effects):
+// both haplotypes carry the same a and d.  Shared by k_cv_finish (table in global memory) and k_ad_accumulate_wide (its piece in LDS).
+__device__ __forceinline__ double cv_frq(u32 count, size_t n_human)
+{
+    const double f = (double)count;
+    return f / (double)(2 * n_human);
+}
+__device__ __forceinline__ void cv_terms(double p, u64 x, double a_cv, double d_cv, u64 bp0, u64 bp_end, double vd, double t[6])
+{
+    const bool covered = (x >= bp0 && x < bp_end);      // a CV outside [bp0,bp_end) is covered by no part: its a, d stay 0 (Human_CV ctor, Population.h:99-108)
+    const double a0 = covered ? a_cv : 0.0, d0 = covered ? d_cv : 0.0;
+    const double a = (a0 + a0) / 2;
+    double d = (d0 + d0) / 2;
+    if (vd == 0) d = 0;
+    const double q = 1 - p;
+    const double alpha = a + d * (q - p);
+    t[0] = ((double)0u - 2 * p) * alpha;
+    t[1] = ((double)1u - 2 * p) * alpha;
+    t[2] = ((double)2u - 2 * p) * alpha;
+    t[3] = (-2 * p * p) * d;
+    t[4] = (2 * p * q) * d;
+    t[5] = (-2 * q * q) * d;
+}
 // Column counts complete -> allele frequencies and the per-CV term table, in ONE launch: every block first adds its slice of
 // k_stitch_small's per-block partial counts to the column counters (n_blocks == 0: k_cv_count has filled them); the block that
 // finishes last (a counter per work entry) then turns the counters into frq[] and the table of the three possible A- and D-terms
 // per CV, computed with EXACTLY the expressions of the reference's per-individual loop (:2686-2712: same operations, same order,
 // so the sums stay bit-identical): tab[icv] = { (0-2p)alpha, (1-2p)alpha, (2-2p)alpha, -2pp*d, 2pq*d, -2qq*d }, and clears the
 // counters for the next generation.  (As separate launches behind one another these were two to three kernels of a few
-// microseconds each -- 75 us each next to the dense stitch.)
+// microseconds each -- 75 us each next to the dense stitch.)  Not launched on a generation's chain in front of
+// k_ad_accumulate_wide: there k_cv_newmut_sum adds the partial counts up and the A/D blocks compute frequencies and terms themselves,
+// so that no block of the grid is alone on the chain.
 __global__ void __launch_bounds__(256) k_cv_finish(const AdWork* __restrict__ At, u32 n_blocks, size_t n_human, u32* __restrict__ done, u32* __restrict__ nan_flag)
 {
     __shared__ bool s_last;
@@ -1139,7 +1198,7 @@ __global__ void __launch_bounds__(256) k_cv_finish(const AdWork* __restrict__ At
     __threadfence();
     if (threadIdx.x == 0) { done[blockIdx.z] = 0; if (blockIdx.z == 0) *nan_flag = 0xffffffffu; }     // (the A/D kernels of this launch sequence report the first NaN individual with atomicMin)
     // four CVs per thread and round: the loads of a round are issued together (a dependent global access costs microseconds next
-    // to the dense stitch, and this block is alone on the generation's critical path)
+    // to the dense stitch, and this block is alone on the critical path of whoever waits for A/D)
     for (u32 icv0 = threadIdx.x; icv0 < aw.C; icv0 += 1024) {
         u32 cc[4]; u32 cnt[4]; u64 xs[4]; double as_[4], ds_[4];
 #pragma unroll
@@ -1155,25 +1214,14 @@ __global__ void __launch_bounds__(256) k_cv_finish(const AdWork* __restrict__ At
         for (int u = 0; u < 4; u++) {
             const u32 icv = icv0 + 256u * u;
             if (icv >= aw.C) continue;
-            const double f = (double)cnt[u];
-            const double p = f / (double)(2 * n_human);
+            const double p = cv_frq(cnt[u], n_human);
             aw.frq[icv] = p;
             if (!aw.tab) continue;                                      // (several root populations: k_ad_accumulate looks a and d up per haplotype)
-            const u64 x = xs[u];
-            const bool covered = (x >= aw.bp0 && x < aw.bp_end);
-            const double a0 = covered ? as_[u] : 0.0, d0 = covered ? ds_[u] : 0.0;
-            const double a = (a0 + a0) / 2;
-            double d = (d0 + d0) / 2;
-            if (aw.vd == 0) d = 0;
-            const double q = 1 - p;
-            const double alpha = a + d * (q - p);
-            double* t = aw.tab + 6 * (size_t)icv;
-            t[0] = ((double)0u - 2 * p) * alpha;
-            t[1] = ((double)1u - 2 * p) * alpha;
-            t[2] = ((double)2u - 2 * p) * alpha;
-            t[3] = (-2 * p * p) * d;
-            t[4] = (2 * p * q) * d;
-            t[5] = (-2 * q * q) * d;
+            double t[6];
+            cv_terms(p, xs[u], as_[u], ds_[u], aw.bp0, aw.bp_end, aw.vd, t);
+            double* out = aw.tab + 6 * (size_t)icv;
+#pragma unroll
+            for (int k = 0; k < 6; k++) out[k] = t[k];
         }
     }
 }
@@ -1315,17 +1363,27 @@ __global__ void __launch_bounds__(IPB) k_ad_accumulate_tab(const AdWork* __restr
     if (A_chr != A_chr || D_chr != D_chr) atomicMin(nan_flag, (u32)(ih < 0xffffffffull ? ih : 0xfffffffeull));
 }
 // The same sums when every CV file of the launch is in position order and the allele sub-row is a whole number of 16-byte
-// chunks: the term table goes through LDS in FEW large pieces (12 KiB: 512 CVs when only the A-terms are needed -- vd == 0, the
+// chunks: the terms go through LDS in FEW large pieces (16 KiB: 512 CVs when only the A-terms are needed -- vd == 0, the
 // D-sum stays +0.0 -- else 256 CVs), and a thread reads the piece's words of its two plane rows (up to 4 x 16 bytes each) in one
 // go before the barrier: two to four global round trips per individual instead of eight (next to the dense stitch every one of
 // them costs microseconds).  Same operations in the same order per individual as k_ad_accumulate_tab.
-template <bool SKIP_D>
-__global__ void __launch_bounds__(256) k_ad_accumulate_wide(const AdWork* __restrict__ At, size_t n_human, size_t out_stride, size_t tot_stride, u32* __restrict__ nan_flag)
+// FROM_COUNTS (the generation chain: k_stitch_small counted, k_cv_newmut_sum added the counts up): no table in global memory and
+// no launch that builds it -- every block computes the piece's terms itself, straight into LDS, from the complete column counts
+// (cv_frq / cv_terms: one division per CV, one or two CVs per thread and piece, their loads issued together with the row words);
+// block 0 of a work entry also writes frq[].  Every block takes a ticket (done[work entry]) when it is through, and the last one
+// clears the entry's counts[] and the ticket for whoever adds to them next -- behind the results, where nobody waits for it.
+// Else k_cv_finish has written tab[] (and consumed the counts) and the piece is copied from there.
+// LDS layout per CV: { T0, T1, T1, T2 } (then { D0, D1, D1, D2 }), indexed by the 2-bit code a_j | b_j << 1 of the two haplotypes'
+// alleles: the codes of 32 CVs are prepared with six operations per pair of words (even CVs in one word, odd CVs in another, each
+// code in two neighbouring bits), a CV costs a shift, a mask, the LDS read (the CV's place in the piece is its immediate offset)
+// and the add; the loop is unrolled over a word, so the reads of the following CVs are in flight while an add retires.
+template <bool SKIP_D, bool FROM_COUNTS>
+__global__ void __launch_bounds__(256) k_ad_accumulate_wide(const AdWork* __restrict__ At, size_t n_human, size_t out_stride, size_t tot_stride, u32* __restrict__ nan_flag, u32* __restrict__ done)
 {
-    constexpr u32 PIECE = SKIP_D ? 512u : 256u, TERMS = SKIP_D ? 3u : 6u, WORDS = PIECE / 32u;
-    __shared__ double s_tab[PIECE * TERMS];                           // 12 KiB
+    constexpr u32 PIECE = SKIP_D ? 512u : 256u, ENT = SKIP_D ? 4u : 8u, WORDS = PIECE / 32u, PER = PIECE / 256u;
+    __shared__ double s_tab[PIECE * ENT];                             // 16 KiB
+    __shared__ bool s_last;
     const AdWork& aw = At[blockIdx.y];
-    const double* __restrict__ tab = aw.tab;
     const u32 Cn = aw.C, stride = aw.stride_w32;
     const size_t ih = (size_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = ih < n_human;
@@ -1342,31 +1400,75 @@ __global__ void __launch_bounds__(256) k_ad_accumulate_wide(const AdWork* __rest
             w0[4 * q] = a.x; w0[4 * q + 1] = a.y; w0[4 * q + 2] = a.z; w0[4 * q + 3] = a.w;
             w1[4 * q] = b.x; w1[4 * q + 1] = b.y; w1[4 * q + 2] = b.z; w1[4 * q + 3] = b.w;
         }
+        u32 cnt[PER]; u64 xs[PER]; double as_[PER], ds_[PER];         // this thread's CVs of the piece (file order == column order: counts[icv])
+        if (FROM_COUNTS) {
+#pragma unroll
+            for (u32 u = 0; u < PER; u++) {
+                const u32 cv = threadIdx.x + 256u * u, icv = base + cv;
+                cnt[u] = cv < nj ? aw.counts[icv] : 0u; xs[u] = cv < nj ? aw.pos_file[icv] : 0ull;
+                as_[u] = cv < nj ? aw.a[icv] : 0.0; ds_[u] = cv < nj ? aw.d[icv] : 0.0;
+            }
+        }
         __syncthreads();                                              // the previous piece is consumed
-        for (u32 e = threadIdx.x; e < nj * TERMS; e += 256) {
-            const u32 cv = e / TERMS, k = e - cv * TERMS;
-            s_tab[e] = tab[6 * (size_t)(base + cv) + k];
+        if (FROM_COUNTS) {
+#pragma unroll
+            for (u32 u = 0; u < PER; u++) {
+                const u32 cv = threadIdx.x + 256u * u;
+                if (cv >= nj) continue;
+                const double p = cv_frq(cnt[u], n_human);
+                if (blockIdx.x == 0) aw.frq[base + cv] = p;
+                double t[6];
+                cv_terms(p, xs[u], as_[u], ds_[u], aw.bp0, aw.bp_end, aw.vd, t);
+                double* e = s_tab + ENT * cv;
+                e[0] = t[0]; e[1] = t[1]; e[2] = t[1]; e[3] = t[2];
+                if (!SKIP_D) { e[4] = t[3]; e[5] = t[4]; e[6] = t[4]; e[7] = t[5]; }
+            }
+        } else {
+            const double* __restrict__ tab = aw.tab;
+            for (u32 e = threadIdx.x; e < nj * ENT; e += 256) {
+                const u32 cv = e / ENT, k = e - cv * ENT;                // entry k holds term {0, 1, 1, 2}[k & 3] of the A (k < 4) or D half
+                s_tab[e] = tab[6 * (size_t)(base + cv) + 3u * (k >> 2) + (((k & 3u) + 1u) >> 1)];
+            }
         }
         __syncthreads();
 #pragma unroll
         for (u32 q = 0; q < WORDS; q++) {
             if (q * 32 >= nj) break;
-            u32 a = w0[q], b = w1[q];
+            const u32 a = w0[q], b = w1[q];
             const u32 m = min(32u, nj - q * 32);
-            const double* tj = s_tab + TERMS * (q * 32);
-#pragma unroll 4
-            for (u32 j = 0; j < m; j++) {
-                const u32 t = (a & 1u) + (b & 1u); a >>= 1; b >>= 1;
-                A_chr += tj[TERMS * j + t];
-                if (!SKIP_D) D_chr += tj[TERMS * j + 3 + t];
+            const double* tj = s_tab + ENT * (q * 32);
+            if (m == 32) {
+                const u32 ev = (a & 0x55555555u) | ((b & 0x55555555u) << 1), od = ((a >> 1) & 0x55555555u) | (b & 0xaaaaaaaau);
+#pragma unroll
+                for (u32 j = 0; j < 32; j += 2) {
+                    const u32 c0 = (ev >> j) & 3u, c1 = (od >> j) & 3u;
+                    A_chr += tj[ENT * j + c0];
+                    if (!SKIP_D) D_chr += tj[ENT * j + 4 + c0];
+                    A_chr += tj[ENT * (j + 1) + c1];
+                    if (!SKIP_D) D_chr += tj[ENT * (j + 1) + 4 + c1];
+                }
+            } else {
+                for (u32 j = 0; j < m; j++) {                         // (the last word of a CV file whose length is no multiple of 32)
+                    const u32 cd = ((a >> j) & 1u) | (((b >> j) & 1u) << 1);
+                    A_chr += tj[ENT * j + cd];
+                    if (!SKIP_D) D_chr += tj[ENT * j + 4 + cd];
+                }
             }
         }
     }
-    if (!live) return;
-    aw.add_out[ih * out_stride] = A_chr;
-    aw.dom_out[ih * out_stride] = D_chr;
-    if (aw.add_tot) { aw.add_tot[ih * tot_stride] = 0.0 + A_chr; aw.dom_tot[ih * tot_stride] = 0.0 + D_chr; }   // one chromosome: the sum over chromosomes (:2729-2746) is 0 + x
-    if (A_chr != A_chr || D_chr != D_chr) atomicMin(nan_flag, (u32)(ih < 0xffffffffull ? ih : 0xfffffffeull));
+    if (live) {
+        aw.add_out[ih * out_stride] = A_chr;
+        aw.dom_out[ih * out_stride] = D_chr;
+        if (aw.add_tot) { aw.add_tot[ih * tot_stride] = 0.0 + A_chr; aw.dom_tot[ih * tot_stride] = 0.0 + D_chr; }   // one chromosome: the sum over chromosomes (:2729-2746) is 0 + x
+        if (A_chr != A_chr || D_chr != D_chr) atomicMin(nan_flag, (u32)(ih < 0xffffffffull ? ih : 0xfffffffeull));
+    }
+    if (!FROM_COUNTS) return;
+    __syncthreads();                                                  // every thread of the block has its counts (their values went into the terms above)
+    if (threadIdx.x == 0) s_last = atomicAdd(&done[blockIdx.y], 1u) == gridDim.x - 1u;
+    __syncthreads();
+    if (!s_last) return;
+    for (u32 e = threadIdx.x; e < Cn; e += 256) aw.counts[e] = 0;     // every block of the entry has read them
+    if (threadIdx.x == 0) done[blockIdx.y] = 0;
 }
 // Several root populations with DIFFERENT CV effects (after migration a haplotype's a, d are its root population's, :2695-2696), CV
 // files in position order: the arithmetic of k_ad_accumulate, statement by statement, with its loads arranged as in

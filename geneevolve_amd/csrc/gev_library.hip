@@ -281,6 +281,7 @@ struct gev_ctx {
     int stitch_mode = 0;           // 0 = work-list form (production, k_stitch_segments), 1 = gamete-major (k_stitch_rows)
     bool sample_batched = true;               // K1-K3 as eight tasks per wave (gev_sample8.h); GEV_SAMPLE_BATCHED=0: one task per wave
     bool chain_wg = true;                     // no mutation map: a workgroup per link of the gamete chain (k_rec_chain_wg); GEV_CHAIN_WG=0: the one-wave form (k_rec_chain)
+    int ad_path = 0;                          // the A/D kernel launched last (gev_dbg_ad_path): AD_PATH_*, + AD_PATH_FROM_COUNTS when it built its terms from the column counts itself
     int sampling_path = 0;                    // the sampling kernel launched last (gev_dbg_sampling_path): 0 none yet, 1 k_sample_batched, 2 k_mut_sample + k_rec_sample, 3 k_rec_chain_wg, 4 k_rec_chain
     size_t list_headroom = 48;                // spare list entries per haplotype row when a list buffer is (re)allocated; GEV_LIST_HEADROOM=0 (tests): just what is live, every generation overflows, grows and is enqueued again
     bool ad_no_shared = false;                // GEV_AD_SHARED=0 (tests): force the per-haplotype effect lookup
@@ -1063,7 +1064,14 @@ int gev_init_gen0(gev_ctx* c, int pop, size_t n_people, uint32_t seed_gen0, uint
 // No host round trip inside a generation: variable-length outputs go to capacity-checked buffers
 // sized from the previous totals; if one was too small the buffers are grown from the exact totals
 // of the count passes and the small work is enqueued again (inputs are untouched until the flip).
-static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready = false, int hbuf = -1);
+// where the allele counts of the CV columns are when the A/D kernels start: nowhere yet (k_cv_count counts the planes), in
+// k_stitch_small's per-block partial counts (k_cv_finish adds them up), or complete in counts[] (k_cv_newmut_sum has added them
+// up: k_ad_accumulate_wide computes its terms from them, no k_cv_finish)
+enum { AD_COUNTS_NONE = 0, AD_COUNTS_PARTIAL = 1, AD_COUNTS_DONE = 2 };
+static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, int counts = AD_COUNTS_NONE, int hbuf = -1);
+// the A/D kernel a population's static inputs select (enqueue_ad launches it; enqueue_attempt asks before it writes the CV planes)
+enum { AD_PATH_NONE = 0, AD_PATH_GENERAL = 1, AD_PATH_RP = 2, AD_PATH_TAB = 3, AD_PATH_TAB_DIRECT = 4, AD_PATH_WIDE = 5, AD_PATH_FROM_COUNTS = 16 };
+static int choose_ad_path(const gev_ctx* c, int pop, int* ipb_out, bool* skip_d_out);
 static int prepare_eager_ad(gev_ctx* c, int pop);
 static int check_not_pending(gev_ctx* c);
 static int check_chain_size(size_t T);
@@ -1531,7 +1539,9 @@ static int enqueue_lists(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, bool
 }
 // CV planes of the offspring: every sub-row (resolved alleles, root-population bits) is inherited by the gamete's crossover
 // pattern; the generation's new mutations that fall on a CV position flip the allele there (k_cv_newmut)
-static int enqueue_cv_planes(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, bool has_mut, bool count_cols, hipStream_t st)
+// sum_counts (with count_cols, when k_ad_accumulate_wide follows): one launch applies the new mutations and adds k_stitch_small's
+// partial counts up, so that the A/D kernel finds the column counts complete (k_cv_newmut_sum)
+static int enqueue_cv_planes(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, bool has_mut, bool count_cols, bool sum_counts, hipStream_t st)
 {
     if (!sc.n_cvwork || !sc.cv_used_max) return GEV_OK;
     const int nchr = c->nchr;
@@ -1540,7 +1550,13 @@ static int enqueue_cv_planes(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, 
     const CvWork* Vt = sc.cvwork.as<CvWork>();
     const dim3 grid((unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK), sc.n_cvwork); const size_t lds = (size_t)sc.cv_max * sizeof(u64); const u32 nsub = 1u + c->rp_bits;
     hipLaunchKernelGGL((k_stitch_small<512>), grid, dim3(512), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
-    if (has_mut) hipLaunchKernelGGL(k_cv_newmut, dim3((unsigned)ceil_div(n_people, 256), sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork.as<ChrWork>(), n_people, nchr, sd, (int)count_cols);
+    if (count_cols && sum_counts) {
+        GEVC(c->d_flag.ensure(16, st));                              // (the launch resets the NaN flag of the A/D kernel behind it)
+        const unsigned nblk = (unsigned)grid.x, slices = std::min((nblk + 7u) / 8u, 128u);      // eight partial blocks per thread, as k_cv_finish
+        const unsigned mut_blocks = has_mut ? (unsigned)ceil_div(n_people, 256) : 0u, col_blocks = (unsigned)std::max<size_t>(ceil_div(sc.cv_max, 256), 1);
+        hipLaunchKernelGGL(k_cv_newmut_sum, dim3(mut_blocks + col_blocks * slices, sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork.as<ChrWork>(), n_people, nchr, sd,
+                           mut_blocks, col_blocks, slices, nblk, c->d_flag.as<u32>());
+    } else if (has_mut) hipLaunchKernelGGL(k_cv_newmut, dim3((unsigned)ceil_div(n_people, 256), sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork.as<ChrWork>(), n_people, nchr, sd, (int)count_cols);
     KCHECK();
     return GEV_OK;
 }
@@ -1692,12 +1708,16 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     // the column counters are filled while the planes are written only if the A/D kernels that consume (and clear) them follow in this attempt
     const bool ad_now = c->eager_ad && c->multipop_ready;
     const bool count_cols = ad_now && sc.cv_count_fused && sc.n_cvwork && sc.cv_used_max;
-    GEVC(enqueue_cv_planes(c, sc, q.n_people, q.has_mut, count_cols, S));
+    // ... and where k_ad_accumulate_wide follows, the launch behind the planes adds the counts up and that kernel computes its terms
+    // from them: two launches from the planes to A/D.  The A/D kernel's last block leaves the counters zero, whatever this attempt's
+    // records held, so a repeated attempt starts as a first one does.
+    const bool sum_counts = count_cols && choose_ad_path(c, q.pop, nullptr, nullptr) == AD_PATH_WIDE;
+    GEVC(enqueue_cv_planes(c, sc, q.n_people, q.has_mut, count_cols, sum_counts, S));
     HIPC(hipEventRecord(sc.t[2], S));
     q.th2 = host_ms();
     if (c->ad_cached_pop != q.pop) c->ad_cached_pop = -1;    // (the device-side arrays are about to be rewritten; the published values of q.pop stay readable in their pinned buffer)
     c->ad_host_set_pop = -1;
-    if (ad_now) GEVC(enqueue_ad(c, q.pop, c->pop[q.pop].cur ^ 1, q.n_people, count_cols, (int)(c->gen_counter & 1)));   // Simulation::ras_compute_AD always follows (src/Simulation.cpp:1935)
+    if (ad_now) GEVC(enqueue_ad(c, q.pop, c->pop[q.pop].cur ^ 1, q.n_people, sum_counts ? AD_COUNTS_DONE : count_cols ? AD_COUNTS_PARTIAL : AD_COUNTS_NONE, (int)(c->gen_counter & 1)));   // Simulation::ras_compute_AD always follows (src/Simulation.cpp:1935)
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[1], S));
     if (X == S) GEVC(enqueue_pool_assign(c, sc, q.n_people, S));   // serialised: behind A/D, in front of the lists
     GEVC(hand_wait(S, L, sc.ev_forked));
@@ -2574,9 +2594,40 @@ int gev_timing_totals(gev_ctx* c, double ms_sum[4], unsigned long long* n_genera
 
 // ---- Simulation::ras_compute_AD -----------------------------------------------------------
 // kernels of ras_compute_AD on buffer set `buf` (current generation, or the one being produced)
-// counts_ready: the allele counts of the CV columns were accumulated by k_stitch_small while it wrote the planes
+// the A/D kernel of a population: one root population (or shared effects) and the block's rows fit LDS: the term-table kernels,
+// the wide one when every CV file is in position order and the allele sub-rows are whole 16-byte chunks; else per haplotype
+static int choose_ad_path(const gev_ctx* c, int pop, int* ipb_out, bool* skip_d_out)
+{
+    const PopState& P = c->pop[pop];
+    u32 sub_max = 0; bool all_have_cv = true, any = false;
+    bool direct = true;                                      // every CV file in position order: rows are read from global memory, no row staging
+    bool chunked = true, skip_d = true;                      // ... their allele sub-rows in whole 16-byte chunks: the terms in few large pieces (k_ad_accumulate_wide)
+    for (int p = 0; p < c->nphen; p++)
+        for (int k = 0; k < c->nchr; k++) {
+            if (!c->chr_active[k]) continue;
+            const CvStatic& V = P.cv[p][k];
+            any = true; sub_max = std::max(sub_max, V.sub_w32); all_have_cv &= V.C > 0;
+            direct &= V.cols_sorted;
+            // (or the row stride pads the sub-row to whole chunks: the piece's 16-byte reads stay inside the row)
+            const bool whole = (V.stride_w32 & 3u) == 0 && ((V.sub_w32 & 3u) == 0 || V.stride_w32 == round_up((size_t)V.sub_w32, 4));
+            chunked &= whole && V.C > 0 && (size_t)V.stride_w32 * 32 >= (((size_t)V.C + 127) & ~(size_t)127);
+            skip_d &= V.vd == 0;
+        }
+    const u32 S1 = sub_max | 1u;
+    int ipb = 0;
+    const size_t ad_tab_lds = AD_CHUNK * 4 + AD_CHUNK * 6 * 8 + 8;          // column + table chunk behind the rows
+    if ((c->rp_bits == 0 || c->ad_effects_shared) && all_have_cv) { for (int cand : {256, 128, 64}) if ((size_t)2 * cand * S1 * 4 + ad_tab_lds <= 64 * 1024) { ipb = cand; break; } }
+    if (ipb_out) *ipb_out = ipb;
+    if (skip_d_out) *skip_d_out = skip_d;
+    if (!any) return AD_PATH_NONE;
+    if (ipb) return direct && chunked ? AD_PATH_WIDE : direct ? AD_PATH_TAB_DIRECT : AD_PATH_TAB;
+    // several root populations with their own CV effects: the piecewise kernel when every CV file is in position order
+    return direct && c->rp_bits >= 1 && c->rp_bits <= 3 && !c->ad_no_rp ? AD_PATH_RP : AD_PATH_GENERAL;
+}
+// counts: AD_COUNTS_PARTIAL: the allele counts of the CV columns were accumulated by k_stitch_small while it wrote the planes;
+// AD_COUNTS_DONE: k_cv_newmut_sum has also added them up and reset the NaN flag (only in front of k_ad_accumulate_wide)
 // hbuf: the pinned result buffer (default: the published generation's)
-static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready, int hbuf)
+static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, int counts, int hbuf)
 {
     if (hbuf < 0) hbuf = (int)((c->gen_counter + 1) & 1);
     PopState& P = c->pop[pop];
@@ -2586,25 +2637,25 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
     GEVC(c->d_addchr.ensure(n * nchr * nphen * sizeof(double), st)); GEVC(c->d_domchr.ensure(n * nchr * nphen * sizeof(double), st));
     GEVC(c->d_add.ensure(n * nphen * sizeof(double), st)); GEVC(c->d_dom.ensure(n * nphen * sizeof(double), st));
     GEVC(c->d_flag.ensure(16, st));
-    if (!c->d_cvdone.p) { GEVC(c->d_cvdone.ensure((size_t)nchr * nphen * sizeof(u32), st)); HIPC(hipMemsetAsync(c->d_cvdone.p, 0, (size_t)nchr * nphen * sizeof(u32), st)); }   // k_cv_finish's block counters (they re-zero themselves)
+    if (!c->d_cvdone.p) { GEVC(c->d_cvdone.ensure((size_t)nchr * nphen * sizeof(u32), st)); HIPC(hipMemsetAsync(c->d_cvdone.p, 0, (size_t)nchr * nphen * sizeof(u32), st)); }   // block tickets of k_cv_finish / k_ad_accumulate_wide (they re-zero themselves)
     c->ad_host_set_pop = -1;                                 // d_add / d_dom are rewritten below: totals handed in by gev_set_ad are gone
     if (c->any_inactive) {                                   // chromosomes held elsewhere contribute exact zeros here
         HIPC(hipMemsetAsync(c->d_addchr.p, 0, n * nchr * nphen * sizeof(double), st)); HIPC(hipMemsetAsync(c->d_domchr.p, 0, n * nchr * nphen * sizeof(double), st));
     }
     // one table entry per (phenotype, active chromosome); every kernel below covers all of them in one launch
     std::vector<AdWork> aw;
-    u32 c_max = 0, sub_max = 0; bool all_have_cv = true;
+    u32 c_max = 0, sub_max = 0;
     for (int p = 0; p < nphen; p++)
         for (int k = 0; k < nchr; k++) {
             if (!c->chr_active[k]) continue;
             CvStatic& V = P.cv[p][k];
-            c_max = std::max(c_max, V.C); sub_max = std::max(sub_max, V.sub_w32); all_have_cv &= V.C > 0;
+            c_max = std::max(c_max, V.C); sub_max = std::max(sub_max, V.sub_w32);
         }
-    // fast path: one root population and the block's rows fit LDS; else the general per-individual kernel
     const u32 S1 = sub_max | 1u;
-    int ipb = 0;
+    int ipb = 0; bool skip_d = true;
     const size_t ad_tab_lds = AD_CHUNK * 4 + AD_CHUNK * 6 * 8 + 8;          // column + table chunk behind the rows
-    if ((c->rp_bits == 0 || c->ad_effects_shared) && all_have_cv) { for (int cand : {256, 128, 64}) if ((size_t)2 * cand * S1 * 4 + ad_tab_lds <= 64 * 1024) { ipb = cand; break; } }
+    const int path = choose_ad_path(c, pop, &ipb, &skip_d);
+    if (counts == AD_COUNTS_DONE && path != AD_PATH_WIDE) return fail(GEV_ESTATE, "enqueue_ad: summed column counts in front of A/D path %d", path);
     for (int p = 0; p < nphen; p++)
         for (int k = 0; k < nchr; k++) {
             if (!c->chr_active[k]) continue;
@@ -2618,7 +2669,7 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
             a.add_out = c->d_addchr.as<double>() + (size_t)k * nphen + p; a.dom_out = c->d_domchr.as<double>() + (size_t)k * nphen + p;
             const bool one_chr = nchr == 1;                                     // the sum over chromosomes is 0 + x: written with the per-chromosome value
             a.add_tot = one_chr ? c->d_add.as<double>() + p : nullptr; a.dom_tot = one_chr ? c->d_dom.as<double>() + p : nullptr;
-            a.partial = counts_ready ? V.d_partial.as<uint16_t>() : nullptr;
+            a.partial = counts == AD_COUNTS_PARTIAL ? V.d_partial.as<uint16_t>() : nullptr;
             a.bp0 = S.rbp.front(); a.bp_end = S.rbp.back(); a.vd = V.vd;
             a.stride_w32 = V.stride_w32; a.sub_w32 = V.sub_w32; a.C = V.C; a.own_pop = pop; a.cols_sorted = V.cols_sorted ? 1u : 0u;
             aw.push_back(a);
@@ -2630,23 +2681,24 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
         const AdWork* At = adw.as<AdWork>();
         const size_t out_stride = (size_t)nchr * nphen, tot_stride = (size_t)nphen;
         u32* flag = c->d_flag.as<u32>();
-        if (c_max && !counts_ready) {
+        if (c_max && counts == AD_COUNTS_NONE) {
             const unsigned gy = (unsigned)std::min<size_t>(std::max<size_t>(rows / 512, 1), 256);
             hipLaunchKernelGGL(k_cv_count, dim3((unsigned)ceil_div(c_max, 256), gy, nw), dim3(256), 0, st, At, rows);
         }
-        // counts -> frequencies (+ the term table of the fast path), NaN flag reset: one launch
-        const unsigned nblk = counts_ready ? (unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK) : 0u;
-        hipLaunchKernelGGL(k_cv_finish, dim3((unsigned)std::max<size_t>(ceil_div(c_max, 256), 1), nblk ? std::min((nblk + 7u) / 8u, 128u) : 1u, nw), dim3(256), 0, st, At, nblk, n, c->d_cvdone.as<u32>(), flag);
+        // counts -> frequencies (+ the term table of the fast path), NaN flag reset: one launch -- none behind k_cv_newmut_sum, where
+        // the counts are complete, the flag is reset and k_ad_accumulate_wide computes frequencies and terms itself
+        const unsigned nblk = counts == AD_COUNTS_PARTIAL ? (unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK) : 0u;
+        if (counts != AD_COUNTS_DONE) hipLaunchKernelGGL(k_cv_finish, dim3((unsigned)std::max<size_t>(ceil_div(c_max, 256), 1), nblk ? std::min((nblk + 7u) / 8u, 128u) : 1u, nw), dim3(256), 0, st, At, nblk, n, c->d_cvdone.as<u32>(), flag);
         if (ipb) {
-            bool direct = true;                                  // every CV file in position order: rows are read from global memory, no row staging
-            for (const AdWork& a : aw) direct &= a.cols_sorted != 0;
-            bool chunked = direct, skip_d = true;                 // ... in whole 16-byte chunks: the term table in few large pieces (k_ad_accumulate_wide)
-            for (const AdWork& a : aw) { chunked &= (a.sub_w32 & 3u) == 0 && (a.stride_w32 & 3u) == 0 && a.C > 0 && (size_t)a.sub_w32 * 32 >= (((size_t)a.C + 127) & ~(size_t)127); skip_d &= a.vd == 0; }
-            if (chunked) {
+            if (path == AD_PATH_WIDE) {
                 const unsigned nb = (unsigned)ceil_div(n, 256);
-                if (skip_d) hipLaunchKernelGGL((k_ad_accumulate_wide<true>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag);
-                else hipLaunchKernelGGL((k_ad_accumulate_wide<false>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag);
-            } else if (direct) {
+                u32* done = c->d_cvdone.as<u32>();
+                if (counts == AD_COUNTS_DONE) {
+                    if (skip_d) hipLaunchKernelGGL((k_ad_accumulate_wide<true, true>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag, done);
+                    else hipLaunchKernelGGL((k_ad_accumulate_wide<false, true>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag, done);
+                } else if (skip_d) hipLaunchKernelGGL((k_ad_accumulate_wide<true, false>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag, done);
+                else hipLaunchKernelGGL((k_ad_accumulate_wide<false, false>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag, done);
+            } else if (path == AD_PATH_TAB_DIRECT) {
                 const unsigned nb = (unsigned)ceil_div(n, 256);
                 hipLaunchKernelGGL((k_ad_accumulate_tab<256>), dim3(nb, nw), dim3(256), ad_tab_lds, st, At, 0u, n, out_stride, tot_stride, flag, 1);
             } else {
@@ -2658,17 +2710,16 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, bool counts_ready,
             }
         } else {
             // several root populations with their own CV effects: the piecewise kernel when every CV file is in position order
-            bool sorted_all = c->rp_bits >= 1 && c->rp_bits <= 3;
-            for (const AdWork& a : aw) sorted_all &= a.cols_sorted != 0;
-            const bool no_rp = c->ad_no_rp;
+            const bool rp = path == AD_PATH_RP;
             const dim3 grid((unsigned)ceil_div(n, 256), nw);
             const size_t lds = (size_t)ADRP_PIECE * ((size_t)c->n_pop * 2 + 5) * sizeof(double);
-            if (sorted_all && !no_rp && c->rp_bits == 1) hipLaunchKernelGGL((k_ad_accumulate_rp<1>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
-            else if (sorted_all && !no_rp && c->rp_bits == 2) hipLaunchKernelGGL((k_ad_accumulate_rp<2>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
-            else if (sorted_all && !no_rp && c->rp_bits == 3) hipLaunchKernelGGL((k_ad_accumulate_rp<3>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
+            if (rp && c->rp_bits == 1) hipLaunchKernelGGL((k_ad_accumulate_rp<1>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
+            else if (rp && c->rp_bits == 2) hipLaunchKernelGGL((k_ad_accumulate_rp<2>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
+            else if (rp && c->rp_bits == 3) hipLaunchKernelGGL((k_ad_accumulate_rp<3>), grid, dim3(256), lds, st, At, (u32)c->n_pop, n, out_stride, tot_stride, flag);
             else hipLaunchKernelGGL(k_ad_accumulate, grid, dim3(256), 0, st, At, c->rp_bits, n, out_stride, tot_stride, flag);
         }
         KCHECK();
+        c->ad_path = path | (counts == AD_COUNTS_DONE ? AD_PATH_FROM_COUNTS : 0);
     } else HIPC(hipMemsetAsync(c->d_flag.p, 0xff, 4, st));
     if (nchr > 1 || !nw) {                                   // one chromosome: the A/D kernels wrote the totals themselves
         hipLaunchKernelGGL(k_ad_sum_chr, dim3((unsigned)ceil_div(n * nphen, 256)), dim3(256), 0, st, c->d_addchr.as<double>(), c->d_domchr.as<double>(), c->d_add.as<double>(), c->d_dom.as<double>(), n, nchr, nphen);
@@ -4756,6 +4807,12 @@ int gev_dbg_rand(gev_ctx* c, uint32_t seed, uint32_t n, int* out)
     KCHECK();
     HIPC(hipMemcpyAsync(out, c->d_tmp.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
+    return GEV_OK;
+}
+int gev_dbg_ad_path(gev_ctx* c, int* path)
+{
+    if (!c || !path) return fail(GEV_EINVAL, "null");
+    *path = c->ad_path;
     return GEV_OK;
 }
 int gev_dbg_sampling_path(gev_ctx* c, int* path)

@@ -707,6 +707,10 @@ int    gev_dbg_sim_loc_rec(gev_ctx*, int pop, int chr, uint32_t seed, uint64_t* 
  * 0 = none yet, 1 = k_sample_batched, 2 = k_mut_sample + k_rec_sample (GEV_SAMPLE_BATCHED=0), 3 = k_rec_chain_wg (no mutation map),
  * 4 = k_rec_chain (no mutation map, GEV_CHAIN_WG=0).  gev_dbg_sim_loc_rec does not change it. */
 int    gev_dbg_sampling_path(gev_ctx*, int* path);
+/* gev_dbg_ad_path: the A/D kernel the context launched last: 0 = none yet, 1 = k_ad_accumulate, 2 = k_ad_accumulate_rp,
+ * 3 = k_ad_accumulate_tab (rows staged), 4 = k_ad_accumulate_tab (rows read directly), 5 = k_ad_accumulate_wide; + 16 when the wide
+ * kernel built its terms from the column counts itself (a generation's chain: k_stitch_small, k_cv_newmut_sum, A/D; no k_cv_finish). */
+int    gev_dbg_ad_path(gev_ctx*, int* path);
 
 #ifdef __cplusplus
 }
