@@ -86,7 +86,7 @@ ABI_SYMBOLS = [
     "last_error", "version", "create", "destroy", "set_rmap", "set_mutmap", "set_snps", "set_cvs",
     "upload_founders", "upload_cv_founders", "synth_founders", "synth_cv_founders", "init_gen0",
     "reproduce", "presample", "compute_ad", "scale_ad_compute_gef", "set_ad", "get_cv_freq", "migrate", "export_size", "export_rows", "remove_rows",
-    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
+    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "ind_genotype_counts", "pair_genotype_counts", "dbg_pair_counts_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
     "pop_size", "plane_ptr", "reserve", "set_chr_active", "set_dense_state", "materialize", "materialize_pops", "materialize_bed", "stream", "last_reproduce_ms", "set_track_intervals", "set_stitch_mode", "sync", "timing_totals", "stitch_totals", "reproduce_begin", "reproduce_end", "presample_sex", "set_overlap",
     "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
     "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
@@ -221,6 +221,23 @@ class GevLibrary:
                                                   C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(het), _p(hom)))
         return het, hom
 
+    def dbg_pair_counts_host(self, bits, L, snp_begin=0, n_snps=None, a_begin=0, n_a=None, b_begin=0, n_b=None):
+        """(n_het, n_hom_alt, n_hethet, n_opphom, dot) by the library's pair counter compiled for the host (no device needed): the first two
+        uint32 [n_ind] over SNPs [snp_begin, +n_snps), the others uint32 [n_a][n_b] for the pairs (a_begin + i, b_begin + k).
+        bits: uint64 [2 * n_ind][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them"""
+        bits = _arr(bits, np.uint64)
+        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
+        n_ind = bits.shape[0] // 2
+        n_snps = L - snp_begin if n_snps is None else n_snps
+        n_a = n_ind - a_begin if n_a is None else n_a
+        n_b = n_ind - b_begin if n_b is None else n_b
+        het = np.empty(n_ind, dtype=np.uint32); hom = np.empty(n_ind, dtype=np.uint32)
+        mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(3)]
+        z = C.c_size_t
+        self.check(self._f("dbg_pair_counts_host")(_p(bits), z(bits.shape[1]), z(n_ind), z(L), z(snp_begin), z(n_snps), z(a_begin), z(n_a), z(b_begin), z(n_b),
+                                                   _p(het), _p(hom), _p(mats[0]), _p(mats[1]), _p(mats[2])))
+        return (het, hom, *mats)
+
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
         parts / hap_offsets: as download_intervals returns them; ids: Human::ID of every individual; names: one list of founder
@@ -264,6 +281,7 @@ class GevContext:
         self.h = h
         self._nsnp = {}
         self._ncv = {}
+        self._chr_off = set()
         self._ph_seeds = 0
 
     def close(self):
@@ -772,6 +790,33 @@ class GevContext:
         het, hom = self.snp_genotype_counts(pop, chr, snp_begin, n_snps, ind_begin, n_ind)
         return (het.astype(np.float64) + 2.0 * hom) / (2.0 * n_ind)
 
+    def ind_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, weight=None):
+        """-> (n_het, n_hom_alt) uint32 [n_ind], or with weight (n_snps uint32) (n_het, n_hom_alt, wsum), wsum uint64 [n_ind] =
+        sum_j weight[j] * g_ij: per individual of the range over the SNPs of the range, counted on the device (mutations applied)"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        het = np.empty(max(n_ind, 0), dtype=np.uint32); hom = np.empty(max(n_ind, 0), dtype=np.uint32)
+        ws = None
+        if weight is not None:
+            weight = _arr(weight, np.uint32)
+            assert weight.shape == (n_snps,), "one weight per SNP of the range"
+            ws = np.empty(max(n_ind, 0), dtype=np.uint64)
+        z = C.c_size_t
+        self._call_new("ind_genotype_counts", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(ind_begin), z(n_ind), _p(weight), _p(het), _p(hom), _p(ws))
+        return (het, hom) if weight is None else (het, hom, ws)
+
+    def pair_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, a_begin=0, n_a=None, b_begin=0, n_b=None):
+        """-> (n_hethet, n_opphom, dot), uint32 [n_a][n_b]: for every pair (a_begin + i, b_begin + k) of the population over the SNPs of the
+        range, the loci where both are heterozygous, the loci where one is 0/0 and the other 1/1, and sum_j g_ij g_kj; exact integer
+        products on the device's matrix cores from the resident rows (mutations applied)"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_a = self.pop_size(pop) - a_begin if n_a is None else n_a
+        n_b = self.pop_size(pop) - b_begin if n_b is None else n_b
+        mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(3)]
+        z = C.c_size_t
+        self._call_new("pair_genotype_counts", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(a_begin), z(n_a), z(b_begin), z(n_b), _p(mats[0]), _p(mats[1]), _p(mats[2]))
+        return tuple(mats)
+
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
         """bytes of the reference's .hap file (format_hap::write_hap) for the given SNP lines"""
         L = self._nsnp[(pop, chr)]
@@ -885,6 +930,11 @@ class GevContext:
 
     def set_chr_active(self, chr, active):
         self._call("set_chr_active", C.c_int(chr), C.c_int(1 if active else 0))
+        (self._chr_off.discard if active else self._chr_off.add)(chr)
+
+    def active_chrs(self):
+        """the chromosomes set_chr_active has not switched off"""
+        return [k for k in range(self.nchr) if k not in self._chr_off]
 
     def set_dense_state(self, on):
         self._call("set_dense_state", C.c_int(1 if on else 0))

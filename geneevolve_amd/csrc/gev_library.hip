@@ -22,6 +22,7 @@
 #include "gev_kernels.h"
 #include "gev_outputs.h"
 #include "gev_snpcount.h"
+#include "gev_paircount.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -300,6 +301,8 @@ struct gev_ctx {
                           int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
     DevBuf d_snpmajor, d_text;
     DevBuf d_snpcnt;               // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
+    int n_cu = 0;                  // compute units of the device (gev_pair_genotype_counts: the tile size), asked for by the first call
+    DevBuf d_pair_a, d_pair_b, d_pair_cnt, d_pair_w, d_pair_out;   // gev_pair_genotype_counts / gev_ind_genotype_counts: the planes of the two sides, the per-individual counts, the weights, a sub-block's results; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
@@ -3864,6 +3867,140 @@ int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_
     if (n_snps && (!n_het || !n_hom_alt)) return fail(GEV_EINVAL, "%s: null output vector", who);
     if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
     gev_snpc_count_rows_host(bits, row_stride_words, n_ind, snp_begin, n_snps, n_het, n_hom_alt);
+    return GEV_OK;
+}
+// ---- genotype counts per individual and per pair of individuals (gev_paircount.h) ---------------
+// the planes of a side: n_w4 words x n_pad individuals of x, then as many of y
+static size_t pair_words4(size_t snp_begin, size_t n_snps) { return n_snps ? (((snp_begin + n_snps - 1) >> 6) - (snp_begin >> 6) + 1 + 3) & ~(size_t)3 : 0; }
+// individuals [ind0, +n) of a side staged through c->d_stage (ensure_csr has run) in passes of <= ~256 MB of rows and prepared:
+// planes into `planes` (null: none), counts into d_het / d_hom / d_wsum (each may be null; entry i = individual ind0 + i)
+static int pair_prep_side(gev_ctx* c, PopState& P, int chr, size_t ind0, size_t n, size_t snp_begin, size_t n_snps, DevBuf* planes,
+                          const u32* d_weight, u32* d_het, u32* d_hom, u64* d_wsum)
+{
+    ChrStatic& S = P.cs[chr];
+    const size_t n_w4 = pair_words4(snp_begin, n_snps), n_pad = planes ? round_up(n, PC_TILE) : n;
+    const size_t pass = std::max<size_t>(output_chunk(c, 256u << 20, S.stride) / 2, 1);                       // (the units are rows, as in gev_download_haps)
+    GEVC(c->d_stage.ensure(std::max<size_t>(2 * std::min(pass, n) * S.stride, 16), c->stream));
+    u64 *px = nullptr, *py = nullptr;
+    if (planes) { GEVC(planes->ensure(std::max<size_t>(2 * n_w4 * n_pad * 8, 16), c->stream)); px = planes->as<u64>(); py = px + n_w4 * n_pad; }
+    for (size_t off = 0; off < n; off += pass) {
+        const size_t m = std::min(pass, n - off), cover = off + m == n ? n_pad - off : m;                     // the last pass zeroes the pad
+        GEVC(stage_rows_mutated(c, P, chr, 2 * (ind0 + off), 2 * m));
+        hipLaunchKernelGGL(k_pair_prep, dim3((unsigned)ceil_div(cover, 4)), dim3(256), 0, c->stream, c->d_stage.as<u64>(), S.stride / 8, (u32)m, (u32)cover,
+                           (u32)off, (u32)n_pad, (u32)snp_begin, (u32)n_snps, (u32)n_w4, px, py, d_weight, d_het, d_hom, d_wsum);
+        KCHECK();
+    }
+    return GEV_OK;
+}
+// what the two calls share: the opening, the three ranges, the width of a range
+static int pair_begin(gev_ctx* c, int pop, int chr, const char* who, size_t snp_begin, size_t n_snps)
+{
+    GEVC(output_begin(c, pop, chr, who, true));
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, c->pop[pop].cs[chr].L));
+    if (n_snps > GEV_PC_MAX_SNPS) return fail(GEV_EUNSUPPORTED, "%s: %zu SNPs in one call, at most %zu (a pair's dot product is a uint32)", who, n_snps, (size_t)GEV_PC_MAX_SNPS);
+    return GEV_OK;
+}
+// individuals a side of a sub-block of the pair matrix: their words of the two planes within ~1 GB, at most 4096 (3 x 64 MB of results)
+static size_t pair_block(const gev_ctx* c, size_t snp_begin, size_t n_snps)
+{
+    return std::min<size_t>(output_chunk(c, (size_t)1 << 30, 2 * pair_words4(snp_begin, n_snps) * 8), 4096);
+}
+int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                            const uint32_t* weight, uint32_t* n_het, uint32_t* n_hom_alt, uint64_t* wsum)
+{
+    const char* who = "ind_genotype_counts";
+    GEVC(pair_begin(c, pop, chr, who, snp_begin, n_snps));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
+    if (!weight != !wsum) return fail(GEV_EINVAL, "%s: weights and wsum come together or not at all", who);
+    if (!n_ind) return GEV_OK;
+    if (!n_snps) {
+        if (n_het) memset(n_het, 0, n_ind * sizeof(u32));
+        if (n_hom_alt) memset(n_hom_alt, 0, n_ind * sizeof(u32));
+        if (wsum) memset(wsum, 0, n_ind * sizeof(u64));
+        return GEV_OK;
+    }
+    GEVC(ensure_csr(c, pop));
+    hipStream_t st = c->stream;
+    const u32* d_weight = nullptr;
+    if (weight) {
+        GEVC(c->d_pair_w.ensure(n_snps * sizeof(u32), st));
+        HIPC(hipMemcpyAsync(c->d_pair_w.p, weight, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
+        d_weight = c->d_pair_w.as<u32>();
+    }
+    GEVC(c->d_pair_cnt.ensure(n_ind * 16, st));
+    u64* d_ws = c->d_pair_cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
+    GEVC(pair_prep_side(c, P, chr, ind_begin, n_ind, snp_begin, n_snps, nullptr, d_weight, d_het, d_hom, wsum ? d_ws : nullptr));
+    if (n_het) HIPC(hipMemcpyAsync(n_het, d_het, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
+    if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt, d_hom, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
+    if (wsum) HIPC(hipMemcpyAsync(wsum, d_ws, n_ind * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// The pair matrix is walked in sub-blocks of at most pair_block() individuals a side (gev_dbg_output_chunk caps them, and the rows of
+// a staging pass): side A of a block row is staged and prepared once, side B once per sub-block -- O(N L) against the product's
+// O(N^2 L) -- each through c->d_stage (the planes, not the staged rows, are what the product reads, so one staging buffer serves both
+// sides); every sub-block has its own results in c->d_pair_out and its own copy-out.  Tiles of 128 x 128 pairs, or of 64 x 64 where
+// the large ones would leave compute units without a workgroup.
+int gev_pair_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
+                             uint32_t* n_hethet, uint32_t* n_opphom, uint32_t* dot)
+{
+    const char* who = "pair_genotype_counts";
+    GEVC(pair_begin(c, pop, chr, who, snp_begin, n_snps));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "individuals (a)", a_begin, n_a, P.n_people));
+    GEVC(check_range(who, "individuals (b)", b_begin, n_b, P.n_people));
+    if (!n_a || !n_b) return GEV_OK;
+    uint32_t* const outs[3] = {n_hethet, n_opphom, dot};
+    if (!n_snps) { for (uint32_t* o : outs) if (o) memset(o, 0, n_a * n_b * sizeof(u32)); return GEV_OK; }
+    if (!n_hethet && !n_opphom && !dot) return GEV_OK;
+    GEVC(ensure_csr(c, pop));
+    hipStream_t st = c->stream;
+    if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const size_t blk = pair_block(c, snp_begin, n_snps), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
+    const size_t n_w4 = pair_words4(snp_begin, n_snps);
+    GEVC(c->d_pair_cnt.ensure((ba + bb) * sizeof(u32), st));
+    GEVC(c->d_pair_out.ensure(3 * ba * bb * sizeof(u32), st));
+    u32* d_hom_a = c->d_pair_cnt.as<u32>(); u32* d_hom_b = d_hom_a + ba;
+    for (size_t ia = 0; ia < n_a; ia += blk) {
+        const size_t na = std::min(blk, n_a - ia), pad_a = round_up(na, PC_TILE);
+        GEVC(pair_prep_side(c, P, chr, a_begin + ia, na, snp_begin, n_snps, &c->d_pair_a, nullptr, nullptr, d_hom_a, nullptr));
+        for (size_t ib = 0; ib < n_b; ib += blk) {
+            const size_t nb = std::min(blk, n_b - ib), pad_b = round_up(nb, PC_TILE);
+            GEVC(pair_prep_side(c, P, chr, b_begin + ib, nb, snp_begin, n_snps, &c->d_pair_b, nullptr, nullptr, d_hom_b, nullptr));
+            u32* d_out[3];
+            for (int o = 0; o < 3; o++) d_out[o] = outs[o] ? c->d_pair_out.as<u32>() + (size_t)o * na * nb : nullptr;
+            const u64 *xa = c->d_pair_a.as<u64>(), *xb = c->d_pair_b.as<u64>();
+            const bool large = (pad_a / PC_TILE) * (pad_b / PC_TILE) >= (size_t)c->n_cu;
+            const unsigned tile = large ? PC_TILE : PC_TILE / 2;
+            hipLaunchKernelGGL(large ? k_pair_product<4> : k_pair_product<2>, dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, st,
+                               xa, xa + n_w4 * pad_a, (u32)pad_a, xb, xb + n_w4 * pad_b, (u32)pad_b, (u32)n_w4, d_hom_a, d_hom_b, (u32)na, (u32)nb,
+                               d_out[0], d_out[1], d_out[2]);
+            KCHECK();
+            for (int o = 0; o < 3; o++) {
+                if (!outs[o]) continue;
+                if (nb == n_b) HIPC(hipMemcpyAsync(outs[o] + ia * n_b, d_out[o], na * nb * sizeof(u32), hipMemcpyDeviceToHost, st));     // whole rows of the caller's matrix
+                else HIPC(hipMemcpy2DAsync(outs[o] + ia * n_b + ib, n_b * sizeof(u32), d_out[o], nb * sizeof(u32), nb * sizeof(u32), na, hipMemcpyDeviceToHost, st));
+            }
+            HIPC(hipStreamSynchronize(st));
+        }
+    }
+    return GEV_OK;
+}
+// the arithmetic of gev_paircount.h compiled for the host on haplotype-major rows in host memory: no device, no context
+int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L, size_t snp_begin, size_t n_snps,
+                             size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
+                             uint32_t* n_het, uint32_t* n_hom_alt, uint32_t* n_hethet, uint32_t* n_opphom, uint32_t* dot)
+{
+    const char* who = "dbg_pair_counts_host";
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
+    if (n_snps > GEV_PC_MAX_SNPS) return fail(GEV_EUNSUPPORTED, "%s: %zu SNPs in one call, at most %zu (a pair's dot product is a uint32)", who, n_snps, (size_t)GEV_PC_MAX_SNPS);
+    GEVC(check_range(who, "individuals (a)", a_begin, n_a, n_ind));
+    GEVC(check_range(who, "individuals (b)", b_begin, n_b, n_ind));
+    if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    const bool pairs = n_a && n_b;
+    gev_pc_counts_host(bits, row_stride_words, n_ind, snp_begin, n_snps, a_begin, pairs ? n_a : 0, b_begin, pairs ? n_b : 0, n_het, n_hom_alt,
+                       pairs ? n_hethet : nullptr, pairs ? n_opphom : nullptr, pairs ? dot : nullptr);
     return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------

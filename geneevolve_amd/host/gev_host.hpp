@@ -150,6 +150,21 @@ public:
         n_het.resize(n_snps); n_hom_alt.resize(n_snps);
         check(gev_snp_genotype_counts(ctx, ipop, ichr, snp_begin, n_snps, ind_begin, n_ind, n_het.data(), n_hom_alt.data()));
     }
+    // per pair (i of [a_begin, +n_a), k of [b_begin, +n_b)) of the current generation over SNPs [snp_begin, +n_snps), row-major [n_a][n_b]:
+    // loci where both are heterozygous, loci where one is 0/0 and the other 1/1, and sum_j g_ij g_kj, counted on the device
+    void pair_genotype_counts(int ipop, int ichr, size_t snp_begin, size_t n_snps, size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
+                              std::vector<uint32_t>& n_hethet, std::vector<uint32_t>& n_opphom, std::vector<uint32_t>& dot)
+    {
+        n_hethet.resize(n_a * n_b); n_opphom.resize(n_a * n_b); dot.resize(n_a * n_b);
+        check(gev_pair_genotype_counts(ctx, ipop, ichr, snp_begin, n_snps, a_begin, n_a, b_begin, n_b, n_hethet.data(), n_opphom.data(), dot.data()));
+    }
+    // per individual of [ind_begin, +n_ind): heterozygous loci and loci with allele 1 twice among SNPs [snp_begin, +n_snps)
+    void ind_genotype_counts(int ipop, int ichr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                             std::vector<uint32_t>& n_het, std::vector<uint32_t>& n_hom_alt)
+    {
+        n_het.resize(n_ind); n_hom_alt.resize(n_ind);
+        check(gev_ind_genotype_counts(ctx, ipop, ichr, snp_begin, n_snps, ind_begin, n_ind, nullptr, n_het.data(), n_hom_alt.data(), nullptr));
+    }
     bool ras_do_migration(const std::vector<gev_move>& moves) { check(gev_migrate(ctx, moves.data(), moves.size())); return true; }   // :877
 };
 

@@ -572,6 +572,38 @@ int gev_snp_genotype_counts(gev_ctx*, int pop, int chr, size_t snp_begin, size_t
  * that hold no SNP of the range are not read. */
 int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L,
                             size_t snp_begin, size_t n_snps, uint32_t* n_het, uint32_t* n_hom_alt);
+/* ---- genotype counts per individual and per pair of individuals: kinship, IBS and GRM without a dump -----------------------------
+ * Counted on the device from the resident rows of the current generation, new mutations applied (csrc/gev_paircount.h): each side's
+ * rows are staged once, one pass makes the range-masked planes x = a ^ b and y = a & b and the per-individual counts, and the pair
+ * counts are two exact integer matrix products on the matrix cores (v_mfma_i32_16x16x64_i8) finished in the same kernel.  Counts are
+ * additive over SNP ranges and over chromosomes: one call serves one (pop, chr).  Both calls begin like the other output calls (a
+ * pending order is materialised, the planes are waited for) and return when the results are in the caller's memory.  GEV_ESTATE on a
+ * context without genotype planes, for an inactive chromosome and for a population without a current generation; GEV_EINVAL for a
+ * range beyond L / n_people; GEV_EUNSUPPORTED for n_snps > 2^30 (dot can reach 4 * n_snps).  The device buffers are created by the
+ * first call; gev_dbg_output_chunk caps the individuals of one staging pass (and so the side of a sub-block of the pair matrix).
+ *
+ * per individual of [ind_begin,+n_ind), over SNPs [snp_begin,+n_snps) of (pop, chr):
+ *   n_het[i], n_hom_alt[i]   uint32;
+ *   wsum[i] = sum_j weight[j] * g_ij (uint64; g = 0/1/2 copies of allele 1; weight: n_snps uint32 in host memory)
+ *   weight == NULL <=> wsum == NULL (GEV_EINVAL otherwise); each output may be NULL.  n_snps == 0 writes zeros, n_ind == 0 touches nothing */
+int gev_ind_genotype_counts(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                            const uint32_t* weight, uint32_t* n_het, uint32_t* n_hom_alt, uint64_t* wsum);
+/* for every pair (i of [a_begin,+n_a), k of [b_begin,+n_b)) of one population, row-major [n_a][n_b] uint32, each may be NULL:
+ *   n_hethet  loci where both are heterozygous
+ *   n_opphom  loci where one is 0/0 and the other 1/1 (IBS0)
+ *   dot       sum_j g_ij * g_kj
+ * n_snps == 0 writes zeros; n_a == 0 or n_b == 0 touches nothing */
+int gev_pair_genotype_counts(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps,
+                             size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
+                             uint32_t* n_hethet, uint32_t* n_opphom, uint32_t* dot);
+/* the same arithmetic (masking, expansion of bits to operand bytes, finishing formulas) compiled for the host on rows in host memory
+ * as gev_download_haps returns them (rows 2i, 2i+1 = individual i, row_stride_words >= ceil(L/64)), a plain integer loop in place of
+ * the matrix instruction: no device, no context.  n_het / n_hom_alt: all n_ind individuals; the pair ranges lie in [0, n_ind).  Words
+ * of a row that hold no SNP of the range are not read. */
+int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L, size_t snp_begin, size_t n_snps,
+                             size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
+                             uint32_t* n_het /*[n_ind]*/, uint32_t* n_hom_alt /*[n_ind]*/,
+                             uint32_t* n_hethet, uint32_t* n_opphom, uint32_t* dot);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */
