@@ -86,7 +86,7 @@ ABI_SYMBOLS = [
     "last_error", "version", "create", "destroy", "set_rmap", "set_mutmap", "set_snps", "set_cvs",
     "upload_founders", "upload_cv_founders", "synth_founders", "synth_cv_founders", "init_gen0",
     "reproduce", "presample", "compute_ad", "scale_ad_compute_gef", "set_ad", "get_cv_freq", "migrate", "export_size", "export_rows", "remove_rows",
-    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "ind_genotype_counts", "pair_genotype_counts", "dbg_pair_counts_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
+    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "ind_genotype_counts", "pair_genotype_counts", "dbg_pair_counts_host", "ld_counts", "ld_scores", "dbg_ld_host", "dbg_ld_r2_q40_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
     "pop_size", "plane_ptr", "reserve", "set_chr_active", "set_dense_state", "materialize", "materialize_pops", "materialize_bed", "stream", "last_reproduce_ms", "set_track_intervals", "set_stitch_mode", "sync", "timing_totals", "stitch_totals", "reproduce_begin", "reproduce_end", "presample_sex", "set_overlap",
     "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
     "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
@@ -237,6 +237,45 @@ class GevLibrary:
         self.check(self._f("dbg_pair_counts_host")(_p(bits), z(bits.shape[1]), z(n_ind), z(L), z(snp_begin), z(n_snps), z(a_begin), z(n_a), z(b_begin), z(n_b),
                                                    _p(het), _p(hom), _p(mats[0]), _p(mats[1]), _p(mats[2])))
         return (het, hom, *mats)
+
+    def dbg_ld_host(self, bits_a, L_a, a_begin=0, n_a=None, bits_b=None, L_b=None, b_begin=0, n_b=None, ind_begin=0, n_ind=None,
+                    win_lo=None, win_hi=None, genotype=False):
+        """the library's LD counter compiled for the host (no device needed).  bits_*: uint64 [2 * n_people][stride_words >= ceil(L / 64)]
+        haplotype-major rows as download_haps returns them (bits_b None: side B lies on side A's rows).  Without windows the block form
+        -> (n11, gg, c_a, het_a, hom_a, c_b, het_b, hom_b) as GevContext.ld_counts; with win_lo / win_hi (uint32 [n_a]) the score form
+        over SNPs [a_begin, +n_a) -> (score_q40 uint64 [n_a], n_terms uint32 [n_a]) as GevContext.ld_scores"""
+        bits_a = _arr(bits_a, np.uint64)
+        assert bits_a.ndim == 2 and bits_a.shape[0] % 2 == 0
+        n_people = bits_a.shape[0] // 2
+        n_a = L_a - a_begin if n_a is None else n_a
+        n_ind = n_people - ind_begin if n_ind is None else n_ind
+        z = C.c_size_t
+        if win_lo is not None or win_hi is not None:
+            lo = None if win_lo is None else _arr(win_lo, np.uint32); hi = None if win_hi is None else _arr(win_hi, np.uint32)
+            assert all(w is None or w.shape == (n_a,) for w in (lo, hi)), "one window per SNP of the range"
+            score = np.empty(max(n_a, 0), dtype=np.uint64); terms = np.empty(max(n_a, 0), dtype=np.uint32)
+            self.check(self._f("dbg_ld_host")(_p(bits_a), z(bits_a.shape[1]), z(L_a), None, z(0), z(0), z(n_people), z(a_begin), z(n_a), z(0), z(0), z(ind_begin), z(n_ind),
+                                              None, None, None, None, None, None, None, None, _p(lo), _p(hi), C.c_int(1 if genotype else 0), _p(score), _p(terms)))
+            return score, terms
+        if bits_b is None:
+            bits_b, L_b = bits_a, L_a
+        bits_b = _arr(bits_b, np.uint64)
+        assert bits_b.ndim == 2 and bits_b.shape[0] == bits_a.shape[0], "both sides hold the same people"
+        n_b = L_b - b_begin if n_b is None else n_b
+        mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(2)]
+        va = [np.empty(max(n_a, 0), dtype=np.uint32) for _ in range(3)]; vb = [np.empty(max(n_b, 0), dtype=np.uint32) for _ in range(3)]
+        self.check(self._f("dbg_ld_host")(_p(bits_a), z(bits_a.shape[1]), z(L_a), _p(bits_b), z(bits_b.shape[1]), z(L_b), z(n_people), z(a_begin), z(n_a), z(b_begin), z(n_b),
+                                          z(ind_begin), z(n_ind), _p(mats[0]), _p(mats[1]), *[_p(v) for v in va + vb], None, None, C.c_int(0), None, None))
+        return (*mats, *va, *vb)
+
+    def dbg_ld_r2_q40_host(self, num, den_j, den_k):
+        """the r^2 quantum of every triple (int64 num, uint64 den_j, den_k with num^2 <= den_j * den_k) by the library's function compiled
+        for the host -> uint64"""
+        num = _arr(num, np.int64).ravel(); den_j = _arr(den_j, np.uint64).ravel(); den_k = _arr(den_k, np.uint64).ravel()
+        assert len(num) == len(den_j) == len(den_k)
+        out = np.empty(len(num), dtype=np.uint64)
+        self.check(self._f("dbg_ld_r2_q40_host")(_p(num), _p(den_j), _p(den_k), C.c_size_t(len(num)), _p(out)))
+        return out
 
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
@@ -816,6 +855,35 @@ class GevContext:
         z = C.c_size_t
         self._call_new("pair_genotype_counts", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(a_begin), z(n_a), z(b_begin), z(n_b), _p(mats[0]), _p(mats[1]), _p(mats[2]))
         return tuple(mats)
+
+    def ld_counts(self, pop, chr_a, a_begin=0, n_a=None, chr_b=None, b_begin=0, n_b=None, ind_begin=0, n_ind=None):
+        """-> (n11, gg, c_a, het_a, hom_a, c_b, het_b, hom_b): for SNP j of [a_begin, +n_a) of chr_a and SNP k of [b_begin, +n_b) of chr_b
+        (None: chr_a) over individuals [ind_begin, +n_ind), uint32 [n_a][n_b]: n11 = haplotypes with allele 1 at both, gg = sum_i g_ij g_ik;
+        per SNP of each side, uint32: allele-1 count, heterozygous and homozygous-alt individuals.  Exact integer products on the device's
+        matrix cores from the current generation (mutations applied)"""
+        chr_b = chr_a if chr_b is None else chr_b
+        n_a = self._nsnp[(pop, chr_a)] - a_begin if n_a is None else n_a
+        n_b = self._nsnp[(pop, chr_b)] - b_begin if n_b is None else n_b
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(2)]
+        vecs = [np.empty(max(n, 0), dtype=np.uint32) for n in (n_a, n_a, n_a, n_b, n_b, n_b)]
+        z = C.c_size_t
+        self._call_new("ld_counts", C.c_int(pop), C.c_int(chr_a), z(a_begin), z(n_a), C.c_int(chr_b), z(b_begin), z(n_b), z(ind_begin), z(n_ind),
+                       _p(mats[0]), _p(mats[1]), *[_p(v) for v in vecs])
+        return (*mats, *vecs)
+
+    def ld_scores(self, pop, chr, win_lo, win_hi, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, genotype=False):
+        """-> (score_q40 uint64 [n_snps], n_terms uint32 [n_snps]): for SNP snp_begin + t the sum over SNPs [win_lo[t], win_hi[t]) of the
+        chromosome of the r^2 quantum llrint(r^2 * 2^40) (haplotype r^2, or genotype r^2) over individuals [ind_begin, +n_ind), and the
+        window's SNPs that are polymorphic among them; the band is walked and reduced on the device"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        lo = _arr(win_lo, np.uint32); hi = _arr(win_hi, np.uint32)
+        assert lo.shape == hi.shape == (max(n_snps, 0),), "one window per SNP of the range"
+        score = np.empty(max(n_snps, 0), dtype=np.uint64); terms = np.empty(max(n_snps, 0), dtype=np.uint32)
+        z = C.c_size_t
+        self._call_new("ld_scores", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), _p(lo), _p(hi), z(ind_begin), z(n_ind), C.c_int(1 if genotype else 0), _p(score), _p(terms))
+        return score, terms
 
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
         """bytes of the reference's .hap file (format_hap::write_hap) for the given SNP lines"""

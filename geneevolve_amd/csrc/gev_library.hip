@@ -23,6 +23,7 @@
 #include "gev_outputs.h"
 #include "gev_snpcount.h"
 #include "gev_paircount.h"
+#include "gev_ldcount.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -303,6 +304,7 @@ struct gev_ctx {
     DevBuf d_snpcnt;               // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
     int n_cu = 0;                  // compute units of the device (gev_pair_genotype_counts: the tile size), asked for by the first call
     DevBuf d_pair_a, d_pair_b, d_pair_cnt, d_pair_w, d_pair_out;   // gev_pair_genotype_counts / gev_ind_genotype_counts: the planes of the two sides, the per-individual counts, the weights, a sub-block's results; created by the first call
+    DevBuf d_ld_a, d_ld_b, d_ld_cnt, d_ld_out, d_ld_win, d_ld_score;   // gev_ld_counts / gev_ld_scores: the planes of the two sides, the per-SNP counts, a sub-block's matrices, the windows, the scores; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
@@ -4001,6 +4003,202 @@ int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size
     const bool pairs = n_a && n_b;
     gev_pc_counts_host(bits, row_stride_words, n_ind, snp_begin, n_snps, a_begin, pairs ? n_a : 0, b_begin, pairs ? n_b : 0, n_het, n_hom_alt,
                        pairs ? n_hethet : nullptr, pairs ? n_opphom : nullptr, pairs ? dot : nullptr);
+    return GEV_OK;
+}
+// ---- linkage disequilibrium per pair of SNPs (gev_ldcount.h) ------------------------------------
+// SNPs a side of a sub-block of the SNP-pair matrix: their words of the plane within ~1 GB, their SNP-major rows within the ~256 MB of
+// one snp_major_device pass (so a side is one pass), at most 4096 (2 x 64 MB of results)
+static size_t ld_block(const gev_ctx* c, size_t n_people, size_t ind_begin, size_t n_ind)
+{
+    const size_t plane = output_chunk(c, (size_t)1 << 30, gev_ld_words4(2 * ind_begin, 2 * n_ind) * 8);
+    return std::min(std::min(plane, output_chunk(c, 256u << 20, ceil_div(2 * n_people, 64) * 8)), (size_t)4096);
+}
+struct LdSide { const u64* plane; u32 *c, *het, *hom; size_t n_pad; };
+// SNPs [s0, +n) of (pop, chr) through c->d_snpmajor into `planes` over individuals [ind_begin, +n_ind), their counts into the three
+// vectors of cnt_stride entries at d_cnt
+static int ld_prep_side(gev_ctx* c, int pop, int chr, size_t s0, size_t n, size_t ind_begin, size_t n_ind, DevBuf& planes, u32* d_cnt, size_t cnt_stride, LdSide& side)
+{
+    const size_t n_w4 = gev_ld_words4(2 * ind_begin, 2 * n_ind), n_pad = round_up(n, LD_TILE);
+    size_t stride;
+    GEVC(planes.ensure(std::max<size_t>(n_w4 * n_pad * 8, 16), c->stream));
+    GEVC(snp_major_device(c, pop, chr, s0, n, stride));
+    side = LdSide{planes.as<u64>(), d_cnt, d_cnt + cnt_stride, d_cnt + 2 * cnt_stride, n_pad};
+    hipLaunchKernelGGL(k_ld_prep, dim3((unsigned)ceil_div(n_pad, 4)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, (u32)n, (u32)n_pad, 0u, (u32)n_pad,
+                       (u64)(2 * ind_begin), (u64)(2 * n_ind), (u32)n_w4, planes.as<u64>(), side.c, side.het, side.hom);
+    KCHECK();
+    return GEV_OK;
+}
+typedef void (*ld_kernel_t)(const u64*, u32, const u64*, u32, u32, u32, u32, u32*, LdScoreArgs);
+static ld_kernel_t ld_kernel(bool large, bool gen, bool score)
+{
+    if (score) {
+        if (gen) return large ? k_ld_product<4, true, true> : k_ld_product<2, true, true>;
+        return large ? k_ld_product<4, false, true> : k_ld_product<2, false, true>;
+    }
+    if (gen) return large ? k_ld_product<4, true, false> : k_ld_product<2, true, false>;
+    return large ? k_ld_product<4, false, false> : k_ld_product<2, false, false>;
+}
+// one product of one sub-block: tiles of 128 x 128 SNP pairs, or of 64 x 64 where fewer than `tiles` large ones have work and would
+// leave compute units without a workgroup
+static int ld_launch(gev_ctx* c, const LdSide& A, size_t na, const LdSide& B, size_t nb, size_t n_w4, size_t tiles, bool gen, bool score, u32* d_out, const LdScoreArgs& sa)
+{
+    if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const bool large = tiles >= (size_t)c->n_cu;
+    const unsigned tile = large ? LD_TILE : LD_TILE / 2;
+    hipLaunchKernelGGL(ld_kernel(large, gen, score), dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, c->stream,
+                       A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, d_out, sa);
+    KCHECK();
+    return GEV_OK;
+}
+// The SNP-pair matrix is walked in sub-blocks of at most ld_block() SNPs a side (gev_dbg_output_chunk caps them, and with them the SNPs
+// of a snp_major_device pass): side A of a block row is prepared once, side B once per sub-block -- O(L n) against the product's
+// O(L^2 n) -- each through c->d_snpmajor (the planes, not the SNP-major rows, are what the product reads, so one staging buffer serves
+// both sides and both chromosomes); every sub-block has its own results in c->d_ld_out and its own copy-out.
+int gev_ld_counts(gev_ctx* c, int pop, int chr_a, size_t a_begin, size_t n_a, int chr_b, size_t b_begin, size_t n_b, size_t ind_begin, size_t n_ind,
+                  uint32_t* n11, uint32_t* gg, uint32_t* c_a, uint32_t* het_a, uint32_t* hom_a, uint32_t* c_b, uint32_t* het_b, uint32_t* hom_b)
+{
+    const char* who = "ld_counts";
+    GEVC(output_begin(c, pop, chr_a, who, true));
+    if (chr_b != chr_a) GEVC(output_begin(c, pop, chr_b, who, true));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "SNPs (a)", a_begin, n_a, P.cs[chr_a].L));
+    GEVC(check_range(who, "SNPs (b)", b_begin, n_b, P.cs[chr_b].L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
+    if (n_ind > GEV_LD_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a pair's genotype product is a uint32)", who, n_ind, (size_t)GEV_LD_MAX_IND);
+    if (!n_a || !n_b) return GEV_OK;
+    uint32_t* const vec_a[3] = {c_a, het_a, hom_a}; uint32_t* const vec_b[3] = {c_b, het_b, hom_b}; uint32_t* const mats[2] = {n11, gg};
+    if (!n_ind) {
+        for (uint32_t* o : mats) if (o) memset(o, 0, n_a * n_b * sizeof(u32));
+        for (uint32_t* o : vec_a) if (o) memset(o, 0, n_a * sizeof(u32));
+        for (uint32_t* o : vec_b) if (o) memset(o, 0, n_b * sizeof(u32));
+        return GEV_OK;
+    }
+    const bool want_mat = n11 || gg, want_b = c_b || het_b || hom_b;
+    if (!want_mat && !want_b && !c_a && !het_a && !hom_a) return GEV_OK;
+    hipStream_t st = c->stream;
+    const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
+    const size_t n_w4 = gev_ld_words4(2 * ind_begin, 2 * n_ind);
+    GEVC(c->d_ld_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
+    GEVC(c->d_ld_out.ensure(2 * ba * bb * sizeof(u32), st));
+    u32* d_cnt_a = c->d_ld_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
+    for (size_t ia = 0; ia < n_a; ia += blk) {
+        const size_t na = std::min(blk, n_a - ia);
+        LdSide A, B;
+        GEVC(ld_prep_side(c, pop, chr_a, a_begin + ia, na, ind_begin, n_ind, c->d_ld_a, d_cnt_a, ba, A));
+        u32* const d_vec_a[3] = {A.c, A.het, A.hom};
+        for (int o = 0; o < 3; o++) if (vec_a[o]) HIPC(hipMemcpyAsync(vec_a[o] + ia, d_vec_a[o], na * sizeof(u32), hipMemcpyDeviceToHost, st));
+        for (size_t ib = 0; ib < n_b; ib += blk) {
+            if (!want_mat && (ia || !want_b)) break;                                          // only side B's vectors are left to make, once
+            const size_t nb = std::min(blk, n_b - ib);
+            GEVC(ld_prep_side(c, pop, chr_b, b_begin + ib, nb, ind_begin, n_ind, c->d_ld_b, d_cnt_b, bb, B));
+            u32* const d_vec_b[3] = {B.c, B.het, B.hom};
+            if (!ia) for (int o = 0; o < 3; o++) if (vec_b[o]) HIPC(hipMemcpyAsync(vec_b[o] + ib, d_vec_b[o], nb * sizeof(u32), hipMemcpyDeviceToHost, st));
+            if (want_mat) {
+                u32* d_out[2];
+                for (int o = 0; o < 2; o++) d_out[o] = mats[o] ? c->d_ld_out.as<u32>() + (size_t)o * na * nb : nullptr;
+                for (int o = 0; o < 2; o++) if (mats[o]) GEVC(ld_launch(c, A, na, B, nb, n_w4, (A.n_pad / LD_TILE) * (B.n_pad / LD_TILE), o == 1, false, d_out[o], LdScoreArgs{}));
+                for (int o = 0; o < 2; o++) {
+                    if (!mats[o]) continue;
+                    if (nb == n_b) HIPC(hipMemcpyAsync(mats[o] + ia * n_b, d_out[o], na * nb * sizeof(u32), hipMemcpyDeviceToHost, st));     // whole rows of the caller's matrix
+                    else HIPC(hipMemcpy2DAsync(mats[o] + ia * n_b + ib, n_b * sizeof(u32), d_out[o], nb * sizeof(u32), nb * sizeof(u32), na, hipMemcpyDeviceToHost, st));
+                }
+            }
+            HIPC(hipStreamSynchronize(st));
+        }
+    }
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the windows of SNPs [snp_begin, +n_snps) of a chromosome of L SNPs: both arrays non-decreasing, win_lo[t] <= snp_begin + t < win_hi[t] <= L
+static int ld_check_windows(const char* who, size_t snp_begin, size_t n_snps, const uint32_t* win_lo, const uint32_t* win_hi, size_t L)
+{
+    if (n_snps && (!win_lo || !win_hi)) return fail(GEV_EINVAL, "%s: null window array (win_lo and win_hi take %zu entries each)", who, n_snps);
+    for (size_t t = 0; t < n_snps; t++) {
+        const size_t j = snp_begin + t;
+        if (win_lo[t] > j || win_hi[t] <= j || win_hi[t] > L) return fail(GEV_EINVAL, "%s: window [%u,%u) of SNP %zu does not hold it or ends beyond the %zu SNPs there are", who, win_lo[t], win_hi[t], j, L);
+        if (t && (win_lo[t] < win_lo[t - 1] || win_hi[t] < win_hi[t - 1])) return fail(GEV_EINVAL, "%s: window [%u,%u) of SNP %zu begins or ends before the one in front of it", who, win_lo[t], win_hi[t], j);
+    }
+    return GEV_OK;
+}
+// The band is walked in the same sub-blocks: for a block row of SNPs, side B runs over the union of their windows (the windows are
+// non-decreasing: from the first one's begin to the last one's end) and no further; within a sub-block a wave whose pairs lie outside
+// the band leaves at once.  The quanta are added on the device; what comes back are the two vectors.
+int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, const uint32_t* win_lo, const uint32_t* win_hi,
+                  size_t ind_begin, size_t n_ind, int genotype, uint64_t* score_q40, uint32_t* n_terms)
+{
+    const char* who = "ld_scores";
+    GEVC(output_begin(c, pop, chr, who, true));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, P.cs[chr].L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
+    if (n_ind > GEV_LD_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a pair's genotype product is a uint32)", who, n_ind, (size_t)GEV_LD_MAX_IND);
+    GEVC(ld_check_windows(who, snp_begin, n_snps, win_lo, win_hi, P.cs[chr].L));
+    if (!n_snps || (!score_q40 && !n_terms)) return GEV_OK;
+    if (!n_ind) {
+        if (score_q40) memset(score_q40, 0, n_snps * sizeof(u64));
+        if (n_terms) memset(n_terms, 0, n_snps * sizeof(u32));
+        return GEV_OK;
+    }
+    hipStream_t st = c->stream;
+    const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_snps), bb = std::min<size_t>(blk, P.cs[chr].L);
+    const size_t n_w4 = gev_ld_words4(2 * ind_begin, 2 * n_ind);
+    GEVC(c->d_ld_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
+    GEVC(c->d_ld_win.ensure(2 * n_snps * sizeof(u32), st));
+    GEVC(c->d_ld_score.ensure(n_snps * (sizeof(u64) + sizeof(u32)), st));
+    u32* d_cnt_a = c->d_ld_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
+    u32* d_lo = c->d_ld_win.as<u32>(); u32* d_hi = d_lo + n_snps;
+    u64* d_score = c->d_ld_score.as<u64>(); u32* d_terms = (u32*)(d_score + n_snps);
+    HIPC(hipMemcpyAsync(d_lo, win_lo, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_hi, win_hi, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIPC(hipMemsetAsync(d_score, 0, n_snps * (sizeof(u64) + sizeof(u32)), st));
+    for (size_t ia = 0; ia < n_snps; ia += blk) {
+        const size_t na = std::min(blk, n_snps - ia);
+        LdSide A, B;
+        GEVC(ld_prep_side(c, pop, chr, snp_begin + ia, na, ind_begin, n_ind, c->d_ld_a, d_cnt_a, ba, A));
+        const size_t u0 = win_lo[ia], u1 = win_hi[ia + na - 1];
+        for (size_t ib = u0; ib < u1; ib += blk) {
+            const size_t nb = std::min(blk, u1 - ib);
+            GEVC(ld_prep_side(c, pop, chr, ib, nb, ind_begin, n_ind, c->d_ld_b, d_cnt_b, bb, B));
+            const LdScoreArgs sa{A.c, A.het, A.hom, B.c, B.het, B.hom, d_lo + ia, d_hi + ia, d_score + ia, d_terms + ia, (u64)n_ind, (u32)ib};
+            size_t band_tiles = 0;                                                             // the large tiles of the sub-block that the band touches
+            for (size_t r0 = 0; r0 < na; r0 += LD_TILE) {
+                const size_t k0 = std::max<size_t>(win_lo[ia + r0], ib), k1 = std::min<size_t>(win_hi[ia + std::min<size_t>(r0 + LD_TILE, na) - 1], ib + nb);
+                if (k1 > k0) band_tiles += (k1 - 1 - ib) / LD_TILE - (k0 - ib) / LD_TILE + 1;
+            }
+            if (!band_tiles) continue;
+            GEVC(ld_launch(c, A, na, B, nb, n_w4, band_tiles / LD_SCORE_TILES_PER_CU, genotype != 0, true, nullptr, sa));
+        }
+    }
+    if (score_q40) HIPC(hipMemcpyAsync(score_q40, d_score, n_snps * sizeof(u64), hipMemcpyDeviceToHost, st));
+    if (n_terms) HIPC(hipMemcpyAsync(n_terms, d_terms, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the arithmetic of gev_ldcount.h compiled for the host on haplotype-major rows in host memory: no device, no context.  The block form
+// (SNPs [a_begin, +n_a) of rows_a against [b_begin, +n_b) of rows_b) and, with windows, the score form over side A's rows
+int gev_dbg_ld_host(const uint64_t* bits_a, size_t stride_a, size_t L_a, const uint64_t* bits_b, size_t stride_b, size_t L_b, size_t n_people,
+                    size_t a_begin, size_t n_a, size_t b_begin, size_t n_b, size_t ind_begin, size_t n_ind,
+                    uint32_t* n11, uint32_t* gg, uint32_t* c_a, uint32_t* het_a, uint32_t* hom_a, uint32_t* c_b, uint32_t* het_b, uint32_t* hom_b,
+                    const uint32_t* win_lo, const uint32_t* win_hi, int genotype, uint64_t* score_q40, uint32_t* n_terms)
+{
+    const char* who = "dbg_ld_host";
+    GEVC(check_range(who, "SNPs (a)", a_begin, n_a, L_a));
+    GEVC(check_range(who, "SNPs (b)", b_begin, n_b, L_b));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
+    if (n_ind > GEV_LD_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a pair's genotype product is a uint32)", who, n_ind, (size_t)GEV_LD_MAX_IND);
+    const bool scores = win_lo || win_hi || score_q40 || n_terms;
+    if (scores) GEVC(ld_check_windows(who, a_begin, n_a, win_lo, win_hi, L_a));
+    if (n_ind && n_a && (!bits_a || stride_a < ceil_div(L_a, 64))) return fail(GEV_EINVAL, "%s: rows (a) of %zu words, %zu needed", who, stride_a, ceil_div(L_a, 64));
+    if (n_ind && n_a && n_b && (!bits_b || stride_b < ceil_div(L_b, 64))) return fail(GEV_EINVAL, "%s: rows (b) of %zu words, %zu needed", who, stride_b, ceil_div(L_b, 64));
+    if (n_a && n_b) gev_ld_counts_host(bits_a, stride_a, a_begin, n_a, bits_b, stride_b, b_begin, n_b, ind_begin, n_ind, n11, gg, c_a, het_a, hom_a, c_b, het_b, hom_b);
+    if (scores) gev_ld_scores_host(bits_a, stride_a, a_begin, n_a, win_lo, win_hi, ind_begin, n_ind, genotype != 0, score_q40, n_terms);
+    return GEV_OK;
+}
+// gev_ld_r2_q40 alone, compiled for the host, on n triples
+int gev_dbg_ld_r2_q40_host(const int64_t* num, const uint64_t* den_j, const uint64_t* den_k, size_t n, uint64_t* q40)
+{
+    if (n && (!num || !den_j || !den_k || !q40)) return fail(GEV_EINVAL, "dbg_ld_r2_q40_host: null array");
+    for (size_t i = 0; i < n; i++) q40[i] = gev_ld_r2_q40(num[i], den_j[i], den_k[i]);
     return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------

@@ -604,6 +604,50 @@ int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size
                              size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
                              uint32_t* n_het /*[n_ind]*/, uint32_t* n_hom_alt /*[n_ind]*/,
                              uint32_t* n_hethet, uint32_t* n_opphom, uint32_t* dot);
+/* ---- linkage disequilibrium per pair of SNPs: r^2 blocks and LD scores without a dump ----------------------------------------------
+ * Counted on the device from the current generation, new mutations applied (csrc/gev_ldcount.h): a side's SNPs are turned SNP-major
+ * (row = SNP, bit h = haplotype row h, bits 2i and 2i+1 = individual i), one pass cuts the rows to the haplotypes of individuals
+ * [ind_begin, +n_ind), writes the side's plane and counts per SNP, and the pair counts are exact integer matrix products on the matrix
+ * cores (v_mfma_i32_16x16x64_i8) over n = 2 n_ind haplotypes (n11) and N = n_ind individuals (gg).  Both calls begin like the other
+ * output calls (a pending order is materialised, the planes are waited for) and return when the results are in the caller's memory.
+ * GEV_ESTATE on a context without genotype planes, for an inactive chromosome and for a population without a current generation;
+ * GEV_EINVAL for a range beyond L / n_people; GEV_EUNSUPPORTED for n_ind > 2^30.  The device buffers are created by the first call;
+ * gev_dbg_output_chunk caps the SNPs of one SNP-major pass and the side of a sub-block of the SNP-pair matrix.
+ *
+ * gev_ld_counts: for SNP j of [a_begin,+n_a) of chr_a and SNP k of [b_begin,+n_b) of chr_b (chr_a != chr_b is allowed: the
+ * disequilibrium between chromosomes), row-major [n_a][n_b] uint32, each may be NULL:
+ *   n11   haplotypes of the range that carry allele 1 at both SNPs
+ *   gg    sum over the individuals of the range of g_ij * g_ik (g = 0/1/2 copies of allele 1)
+ * and per SNP of each side over the same individuals, uint32 [n_a] / [n_b], each may be NULL:
+ *   c (allele-1 count = sum g), n_het, n_hom_alt (sum g^2 = n_het + 4 n_hom_alt)
+ * n_ind == 0 writes zeros; n_a == 0 or n_b == 0 touches nothing.
+ * Haplotype r^2 = (n n11 - c_j c_k)^2 / (c_j (n - c_j) c_k (n - c_k)); genotype r^2 = (N gg - s_j s_k)^2 / ((N sum g_j^2 - s_j^2)(..k..)). */
+int gev_ld_counts(gev_ctx*, int pop, int chr_a, size_t a_begin, size_t n_a, int chr_b, size_t b_begin, size_t n_b, size_t ind_begin, size_t n_ind,
+                  uint32_t* n11, uint32_t* gg, uint32_t* c_a, uint32_t* het_a, uint32_t* hom_a, uint32_t* c_b, uint32_t* het_b, uint32_t* hom_b);
+/* gev_ld_scores: for SNP j = snp_begin + t of [snp_begin,+n_snps) the window is SNPs [win_lo[t], win_hi[t]) of the same chromosome
+ * (host arrays of n_snps uint32, both non-decreasing, win_lo[t] <= j < win_hi[t] <= L; GEV_EINVAL otherwise; windows may reach outside
+ * the range of the call).  genotype: 0 haplotype r^2, otherwise genotype r^2.  Each output may be NULL:
+ *   score_q40[t] (uint64) = sum over the window, j itself included, of the r^2 quantum llrint(r^2 * 2^40), r^2 formed in separately
+ *                rounded IEEE double operations from the exact integers (num^2 / (den_j den_k)); 0 where either SNP is monomorphic
+ *                among the individuals (den = 0).  The sum is an integer sum: the same on every run and in every order.
+ *   n_terms[t]   (uint32) = the window's SNPs with den > 0
+ * The band is walked on the device and reduced there; no pair matrix is written or copied out.  n_snps == 0 touches nothing,
+ * n_ind == 0 writes zeros. */
+int gev_ld_scores(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, const uint32_t* win_lo, const uint32_t* win_hi,
+                  size_t ind_begin, size_t n_ind, int genotype, uint64_t* score_q40, uint32_t* n_terms);
+/* the same arithmetic (masking, expansion of bits to operand bytes, counts, quantum) compiled for the host on rows in host memory as
+ * gev_download_haps returns them (2 n_people rows, rows 2i, 2i+1 = individual i, stride >= ceil(L/64) words), a plain integer loop in
+ * place of the matrix instruction: no device, no context.  The block form as gev_ld_counts (bits_b may be bits_a, or another
+ * chromosome's rows of the same people); with win_lo / win_hi the score form as gev_ld_scores over SNPs [a_begin,+n_a) of bits_a.
+ * Only the rows of the individuals of the range are read, and of those the words that hold a SNP of a side or a window. */
+int gev_dbg_ld_host(const uint64_t* bits_a, size_t stride_a, size_t L_a, const uint64_t* bits_b, size_t stride_b, size_t L_b, size_t n_people,
+                    size_t a_begin, size_t n_a, size_t b_begin, size_t n_b, size_t ind_begin, size_t n_ind,
+                    uint32_t* n11, uint32_t* gg, uint32_t* c_a, uint32_t* het_a, uint32_t* hom_a, uint32_t* c_b, uint32_t* het_b, uint32_t* hom_b,
+                    const uint32_t* win_lo, const uint32_t* win_hi, int genotype, uint64_t* score_q40, uint32_t* n_terms);
+/* the r^2 quantum alone (gev_ld_r2_q40 of csrc/gev_ldcount.h compiled for the host) on n triples with num^2 <= den_j * den_k, as the
+ * counts of real data always have it (Cauchy-Schwarz): q40[i] = llrint(((double)num * (double)num) / ((double)den_j * (double)den_k) * 2^40),
+ * 0 where a denominator is 0 */
+int gev_dbg_ld_r2_q40_host(const int64_t* num, const uint64_t* den_j, const uint64_t* den_k, size_t n, uint64_t* q40);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */
