@@ -17,8 +17,7 @@
 //     genotype bytes    v = w - ((w >> 1) & 0x55555555)               every bit pair becomes its popcount
 //                       g[j] = (v >> 2 j) & 0x03030303, j = 0..3     byte b of g[j] = individual 4 b + j: 16 bytes, one matrix step
 // 16 operations for the 32 haplotype bytes (j = 0 needs no shift: 15), 3 + 7 for the 16 genotype bytes: 25 per half word, 50 per
-// 64-bit operand word for both kinds, against 6 matrix steps.  The order inside a step is free as long as both operands share it: a
-// permutation of the summation index cancels in the sum.
+// 64-bit operand word for both kinds, against 6 matrix steps (the order inside a step is free: gev_bitprod.h).
 //
 // r^2 is formed in integers as far as it goes and then in four separately rounded IEEE double operations (gev_ld_r2_q40): the
 // quantum llrint(r^2 * 2^40).  An LD score is an integer sum of quanta, so the order of the sum is free.
@@ -30,8 +29,9 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 #include <vector>
-#include "gev_paircount.h"                         // gev_pc_range_mask, gev_pc_popcount64
+#include "gev_bitprod.h"                           // GEV_PC_HD, gev_pc_range_mask, gev_pc_popcount64, the product and the preparation walk
 
 #define GEV_LD_MAX_IND ((size_t)1 << 30)          // gg can reach 4 n_ind, n11 2 n_ind
 #define GEV_LD_Q40 1099511627776.0                // 2^40
@@ -83,9 +83,6 @@ GEV_PC_HD inline uint64_t gev_ld_r2_q40(int64_t num, uint64_t den_j, uint64_t de
     return (uint64_t)llrint(r2 * GEV_LD_Q40);
 #endif
 }
-// words of a SNP-major row that hold a haplotype of [hap_begin, +n_hap), padded to the 4 words one product step takes
-inline size_t gev_ld_words4(size_t hap_begin, size_t n_hap) { return n_hap ? (((hap_begin + n_hap - 1) >> 6) - (hap_begin >> 6) + 1 + 3) & ~(size_t)3 : 0; }
-
 // One side on the host: SNPs [s0, +ns) of haplotype-major rows (row r = bits + r * stride words, SNP j = bit j & 63 of word j >> 6)
 // turned SNP-major over haplotypes [2 ind_begin, +2 n_ind), masked, counted and expanded to the operand bytes of the device's order.
 // Only the rows of the range and, of each, the words that hold a SNP of the side are read.
@@ -97,7 +94,7 @@ struct gev_ld_side_host {
     {
         ns = n_snps;
         const size_t h0 = 2 * ind_begin, nh = 2 * n_ind, w_first = h0 >> 6;
-        n_w4 = gev_ld_words4(h0, nh);
+        n_w4 = gev_bp_words4(h0, nh);
         c.assign(ns, 0); het.assign(ns, 0); hom.assign(ns, 0);
         if (want_hap) hb.assign(ns * n_w4 * 64, 0);
         if (want_gen) gb.assign(ns * n_w4 * 32, 0);
@@ -113,14 +110,8 @@ struct gev_ld_side_host {
                     const uint32_t w32 = (uint32_t)(v >> (32 * half));
                     uint32_t e[4];
                     if (want_hap)
-                        for (int st = 0; st < 2; st++) {
-                            gev_ld_expand_hap(w32, st, e);
-                            for (int q = 0; q < 4; q++) for (int b = 0; b < 4; b++) hb[(s * n_w4 + w) * 64 + 32 * half + 16 * st + 4 * q + b] = (int8_t)(e[q] >> (8 * b));
-                        }
-                    if (want_gen) {
-                        gev_ld_expand_gen(w32, e);
-                        for (int q = 0; q < 4; q++) for (int b = 0; b < 4; b++) gb[(s * n_w4 + w) * 32 + 16 * half + 4 * q + b] = (int8_t)(e[q] >> (8 * b));
-                    }
+                        for (int st = 0; st < 2; st++) { gev_ld_expand_hap(w32, st, e); gev_bp_store16(e, &hb[(s * n_w4 + w) * 64 + 32 * half + 16 * st]); }
+                    if (want_gen) { gev_ld_expand_gen(w32, e); gev_bp_store16(e, &gb[(s * n_w4 + w) * 32 + 16 * half]); }
                 }
             }
         }
@@ -129,10 +120,8 @@ struct gev_ld_side_host {
     uint32_t product(bool genotype, size_t i, const gev_ld_side_host& o, size_t k) const
     {
         const size_t nb = n_w4 * (genotype ? 32 : 64);
-        const int8_t* a = (genotype ? gb.data() : hb.data()) + i * nb; const int8_t* b = (genotype ? o.gb.data() : o.hb.data()) + k * nb;
-        int32_t acc = 0;
-        for (size_t j = 0; j < nb; j++) acc += (int32_t)a[j] * b[j];
-        return (uint32_t)acc;
+        const std::vector<int8_t> &a = genotype ? gb : hb, &b = genotype ? o.gb : o.hb;
+        return gev_bp_dot_i8(a.data() + i * nb, b.data() + k * nb, nb);
     }
     void copy_counts(uint32_t* oc, uint32_t* ohet, uint32_t* ohom) const
     {
@@ -179,27 +168,25 @@ inline void gev_ld_scores_host(const uint64_t* bits, size_t stride, size_t snp_b
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------
-// The device.  Both kernels work on SNP-major rows (snp_major_device: transposed from the resident planes, mutation overlay applied).
+// The device (the walk and the product: gev_bitprod.h).  Both kernels work on SNP-major rows (snp_major_device: transposed from the
+// resident planes, mutation overlay applied).
 //
-// 1. k_ld_prep: one wave per SNP walks the words of the haplotype range (lane = word, coalesced), writes the masked words into the
-// side's plane and reduces c, n_het, n_hom_alt over the wave.  The plane is WORD-major: plane[w * n_pad + snp], so that the product's
-// 16 lanes of a fragment row read 16 consecutive words.  It is padded to LD_TILE SNPs and to 4 words with zeros (a zero operand adds
-// nothing to any sum), so the product needs no bounds on its loads.  One plane serves both products.
-//
-// 2. k_ld_product: v_mfma_i32_16x16x64_i8, exact i32 accumulators.  A workgroup of four waves owns a tile of SNP pairs and the whole
-// haplotype range: no split over the summation index.  A wave owns 16 FR x 16 FR pairs; per step of 256 haplotypes lane (r = lane &
-// 15, q = lane >> 4) loads ONE word per fragment -- word 4 W + q of SNP r -- which feeds four haplotype or two genotype matrix steps.
-// A row = lane & 15, B column = lane & 15, C/D column = lane & 15 and row = 4 (lane >> 4) + register; the order of the summation index
-// inside a step is the same function of (lane, step) for both operands and cancels.  GEN: which of the two products is formed.
+// k_ld_prep: a row of the side is a SNP; its masked words go into the side's one plane, which serves both products.
+// k_ld_product: one plane a side, one accumulator set; a word feeds four haplotype or two genotype matrix steps (GEN: which).
 //   block form (SCORE false): the accumulators are stored, [n_a][n_b].
 //   score form (SCORE true): per element the window test, the quantum from the accumulator and the per-SNP
 //   counts, a sum along the tile's row over the fragments and the 16 lanes of a row, one 64-bit atomic add per row and wave.  A wave
 //   whose pairs lie wholly outside the band leaves at once.  No pair matrix is written.
 // Every store and atomic is a vector one.
 // ------------------------------------------------------------------------------------------
-#define LD_TILE 128u                              // SNPs the planes are padded to = the larger tile side
 #define LD_SCORE_TILES_PER_CU 2u                  // score form: large tiles where the band touches at least this many of them per compute unit (measured)
 
+struct LdRow {
+    static constexpr int NPLANES = 1;
+    typedef BpSums<3, false> Sums;                // c, n_het, n_hom_alt
+    const u64* rows; size_t row_w64;
+    __device__ void word(u32 s, size_t w, u64 mask, u64 (&v)[1], Sums& sums) const { v[0] = rows[(size_t)s * row_w64 + w] & mask; gev_ld_word_counts(v[0], sums.s[0], sums.s[1], sums.s[2]); }
+};
 // rows: SNP-major rows of n_snps SNPs (row_w64 words apart), which are SNPs [snp_off, +n_snps) of the side; the block writes SNPs
 // [snp_off, +n_cover) of the plane, zeros beyond n_snps (the pad of the side).  plane: n_w4 words x n_pad SNPs; the three count vectors
 // are indexed like the plane
@@ -207,24 +194,7 @@ __global__ void __launch_bounds__(256) k_ld_prep(const u64* __restrict__ rows, s
                                                  u64 hap_begin, u64 n_hap, u32 n_w4, u64* __restrict__ plane,
                                                  u32* __restrict__ cnt_c, u32* __restrict__ cnt_het, u32* __restrict__ cnt_hom)
 {
-    const u32 lane = threadIdx.x & 63u;
-    const u32 s = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (s >= n_cover) return;
-    const size_t w_first = (size_t)(hap_begin >> 6);
-    const u32 n_w = n_hap ? (u32)(((hap_begin + n_hap - 1u) >> 6) - w_first + 1u) : 0u;
-    u32 c = 0, het = 0, hom = 0;
-    for (u32 w = lane; w < n_w4; w += 64u) {
-        u64 v = 0;
-        if (s < n_snps && w < n_w) {
-            v = rows[(size_t)s * row_w64 + w_first + w] & gev_pc_range_mask(w_first + w, (size_t)hap_begin, (size_t)(hap_begin + n_hap));
-            gev_ld_word_counts(v, c, het, hom);
-        }
-        plane[(size_t)w * n_pad + snp_off + s] = v;
-    }
-    if (s >= n_snps) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { c += __shfl_xor(c, d); het += __shfl_xor(het, d); hom += __shfl_xor(hom, d); }
-    if (lane == 0) { cnt_c[snp_off + s] = c; cnt_het[snp_off + s] = het; cnt_hom[snp_off + s] = hom; }
+    bp_prep(LdRow{rows, row_w64}, LdRow::Sums{{0, 0, 0}, 0, {cnt_c, cnt_het, cnt_hom}, nullptr}, n_snps, n_cover, snp_off, n_pad, hap_begin, n_hap, n_w4, {plane});
 }
 
 // what the score form needs beside the planes
@@ -236,79 +206,37 @@ struct LdScoreArgs {
     u32 b_first;                                              // SNP index (within the chromosome) of side B's SNP 0
 };
 
-// planes of side A (n_pad_a SNPs) and side B (n_pad_b), n_w4 words each (a multiple of 4); block form: out row-major [n_a][n_b].  GEN: the
-// genotype product (gg), otherwise the haplotype product (n11) -- one product per launch: a kernel that forms both holds 128 accumulators
-// beside both operand sets, runs one wave per SIMD and was measured slower than the two launches.  FR: 16 x 16 fragments per
-// wave and side (4: tiles of 128 x 128, 2: tiles of 64 x 64 for blocks too small to fill the device with the large ones).
-// blockIdx.y = tile of A, blockIdx.x = tile of B
+struct LdHapProduct {                             // n11: 0/1 bytes, one per haplotype
+    static constexpr int NPLANES = 1, NACC = 1, STEPS = 4;
+    __device__ static void expand(const u64 (&w)[1], int s, pc_v4i (&f)[1]) { u32 e[4]; gev_ld_expand_hap((u32)(w[0] >> (32 * (s >> 1))), s & 1, e); f[0] = bp_v4(e); }
+};
+struct LdGenProduct {                             // gg: 0/1/2 bytes, one per individual
+    static constexpr int NPLANES = 1, NACC = 1, STEPS = 2;
+    __device__ static void expand(const u64 (&w)[1], int s, pc_v4i (&f)[1]) { u32 e[4]; gev_ld_expand_gen((u32)(w[0] >> (32 * s)), e); f[0] = bp_v4(e); }
+};
+
+// planes of side A (n_pad_a SNPs) and side B (n_pad_b), n_w4 words each; block form: out row-major [n_a][n_b].  GEN: the genotype
+// product (gg), otherwise the haplotype product (n11) -- one product per launch: a kernel that forms both holds 128 accumulators
+// beside both operand sets, runs one wave per SIMD and was measured slower than the two launches
 template <int FR, bool GEN, bool SCORE>
 __global__ void __launch_bounds__(256) k_ld_product(const u64* __restrict__ pa_p, u32 n_pad_a, const u64* __restrict__ pb_p, u32 n_pad_b, u32 n_w4,
                                                     u32 n_a, u32 n_b, u32* __restrict__ out, LdScoreArgs sa)
 {
-    constexpr u32 WAVE = 16u * FR, TILE = 2u * WAVE;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u32 r = lane & 15u, q = lane >> 4;
-    const u32 a0 = blockIdx.y * TILE + (wave >> 1) * WAVE, b0 = blockIdx.x * TILE + (wave & 1u) * WAVE;         // the wave's pairs
-    if (a0 >= n_a || b0 >= n_b) return;                                                                        // (nothing of the wave's is stored)
-    if (SCORE) {                                  // the windows are non-decreasing: the first row's begin and the last row's end bound the band
+    using P = typename std::conditional<GEN, LdGenProduct, LdHapProduct>::type;
+    constexpr u32 WAVE = 16u * FR;
+    const u64* const pa[1] = {pa_p}; const u64* const pb[1] = {pb_p};
+    const auto outside_band = [&](u32 a0, u32 b0) -> bool {   // the windows are non-decreasing: the first row's begin and the last row's end bound the band
+        if (!SCORE) return false;
         const u32 i_last = (a0 + WAVE < n_a ? a0 + WAVE : n_a) - 1u;
         const u32 k_first = sa.b_first + b0, k_end = sa.b_first + (b0 + WAVE < n_b ? b0 + WAVE : n_b);
-        if (k_end <= sa.win_lo[a0] || k_first >= sa.win_hi[i_last]) return;
-    }
-    pc_v4i acc[FR][FR];
-#pragma unroll
-    for (int m = 0; m < FR; m++)
-#pragma unroll
-        for (int n = 0; n < FR; n++) acc[m][n] = pc_v4i{0, 0, 0, 0};
-    const u64* pa = pa_p + (size_t)q * n_pad_a + a0 + r;
-    const u64* pb = pb_p + (size_t)q * n_pad_b + b0 + r;
-    u64 wa[FR], wb[FR];                           // the step in hand
-    u64 na[FR], nb[FR];                           // the next one, loaded while this one is multiplied
-#pragma unroll
-    for (int m = 0; m < FR; m++) { na[m] = pa[16 * m]; nb[m] = pb[16 * m]; }
-    for (u32 W = 0; W < n_w4; W += 4u) {
-#pragma unroll
-        for (int m = 0; m < FR; m++) { wa[m] = na[m]; wb[m] = nb[m]; }
-        if (W + 4u < n_w4) {
-            pa += (size_t)4 * n_pad_a; pb += (size_t)4 * n_pad_b;
-#pragma unroll
-            for (int m = 0; m < FR; m++) { na[m] = pa[16 * m]; nb[m] = pb[16 * m]; }
-        }
-#pragma unroll
-        for (int half = 0; half < 2; half++)
-#pragma unroll
-            for (int s = 0; s < (GEN ? 1 : 2); s++) {
-                pc_v4i ea[FR], eb[FR];
-#pragma unroll
-                for (int m = 0; m < FR; m++) {
-                    u32 e[4];
-                    if (GEN) gev_ld_expand_gen((u32)(wa[m] >> (32 * half)), e); else gev_ld_expand_hap((u32)(wa[m] >> (32 * half)), s, e);
-                    ea[m] = pc_v4i{(int)e[0], (int)e[1], (int)e[2], (int)e[3]};
-                    if (GEN) gev_ld_expand_gen((u32)(wb[m] >> (32 * half)), e); else gev_ld_expand_hap((u32)(wb[m] >> (32 * half)), s, e);
-                    eb[m] = pc_v4i{(int)e[0], (int)e[1], (int)e[2], (int)e[3]};
-                }
-#pragma unroll
-                for (int m = 0; m < FR; m++)
-#pragma unroll
-                    for (int n = 0; n < FR; n++) acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ea[m], eb[n], acc[m][n], 0, 0, 0);
-            }
-    }
-    // C/D: column = lane & 15, row = 4 (lane >> 4) + register
+        return k_end <= sa.win_lo[a0] || k_first >= sa.win_hi[i_last];
+    };
+    u32 a0, b0; pc_v4i acc[1][FR][FR] = {};
+    if (!bp_product<FR, P>(pa, n_pad_a, pb, n_pad_b, n_w4, n_a, n_b, outside_band, a0, b0, acc)) return;
     if (!SCORE) {
-#pragma unroll
-        for (int n = 0; n < FR; n++) {
-            const u32 k = b0 + 16u * n + r;
-            if (k >= n_b) continue;
-#pragma unroll
-            for (int m = 0; m < FR; m++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) {
-                    const u32 i = a0 + 16u * m + 4u * q + v;
-                    if (i >= n_a) continue;
-                    out[(size_t)i * n_b + k] = (u32)acc[m][n][v];
-                }
-        }
+        bp_for_each<FR>(acc, a0, b0, n_a, n_b, [&](u32 i, u32 k, const u32 (&p)[1]) { out[(size_t)i * n_b + k] = p[0]; });
     } else {
+        const u32 lane = threadIdx.x & 63u, r = lane & 15u, q = lane >> 4;
         u32 ck[FR], kk[FR]; u64 den_k[FR];        // the wave's columns of this lane: count, SNP index within the chromosome (none: ~0), denominator
 #pragma unroll
         for (int n = 0; n < FR; n++) {
@@ -332,7 +260,7 @@ __global__ void __launch_bounds__(256) k_ld_product(const u64* __restrict__ pa_p
                 for (int n = 0; n < FR; n++) {
                     if (kk[n] < lo || kk[n] >= hi) continue;
                     terms += den_k[n] != 0;
-                    sum += gev_ld_r2_q40(gev_ld_num(GEN, sa.n_ind, (u32)acc[m][n][v], cj, ck[n]), den_j, den_k[n]);
+                    sum += gev_ld_r2_q40(gev_ld_num(GEN, sa.n_ind, (u32)acc[0][m][n][v], cj, ck[n]), den_j, den_k[n]);
                 }
 #pragma unroll
                 for (int d = 8; d >= 1; d >>= 1) { sum += __shfl_xor((unsigned long long)sum, d); terms += __shfl_xor(terms, d); }   // the 16 lanes of the row

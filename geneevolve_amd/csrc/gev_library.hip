@@ -302,9 +302,9 @@ struct gev_ctx {
                           int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
     DevBuf d_snpmajor, d_text;
     DevBuf d_snpcnt;               // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
-    int n_cu = 0;                  // compute units of the device (gev_pair_genotype_counts: the tile size), asked for by the first call
-    DevBuf d_pair_a, d_pair_b, d_pair_cnt, d_pair_w, d_pair_out;   // gev_pair_genotype_counts / gev_ind_genotype_counts: the planes of the two sides, the per-individual counts, the weights, a sub-block's results; created by the first call
-    DevBuf d_ld_a, d_ld_b, d_ld_cnt, d_ld_out, d_ld_win, d_ld_score;   // gev_ld_counts / gev_ld_scores: the planes of the two sides, the per-SNP counts, a sub-block's matrices, the windows, the scores; created by the first call
+    int n_cu = 0;                  // compute units of the device (bitprod_launch: the tile size), asked for by the first call
+    DevBuf d_bp_a, d_bp_b, d_bp_cnt, d_bp_out;   // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
+    DevBuf d_pair_w, d_ld_win, d_ld_score;       // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
@@ -3871,16 +3871,71 @@ int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_
     gev_snpc_count_rows_host(bits, row_stride_words, n_ind, snp_begin, n_snps, n_het, n_hom_alt);
     return GEV_OK;
 }
+// ---- the matrix-core products over bit planes (gev_bitprod.h): what the pair counts and LD share on the host --------
+extern "C++" {      // (templates cannot have the C linkage of the block this file's functions sit in)
+// One product of one sub-block of na x nb pairs with kernel k[large]: tiles of 128 x 128 pairs, or of 64 x 64 where fewer than `tiles`
+// large ones have work and would leave compute units without a workgroup.  k[0]: the instantiation with FR = 2, k[1]: FR = 4
+template <class K, class... Args>
+static int bitprod_launch(gev_ctx* c, K* const (&k)[2], size_t na, size_t nb, size_t tiles, Args... args)
+{
+    if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const bool large = tiles >= (size_t)c->n_cu;
+    const unsigned tile = large ? BP_TILE : BP_TILE / 2;
+    hipLaunchKernelGGL(k[large], dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, c->stream, args...);
+    KCHECK();
+    return GEV_OK;
+}
+// the ten instantiations: [large]; [score][genotype][large]
+static constexpr decltype(&k_pair_product<2>) pair_kernels[2] = {k_pair_product<2>, k_pair_product<4>};
+static constexpr decltype(&k_ld_product<2, false, false>) ld_kernels[2][2][2] = {
+    {{k_ld_product<2, false, false>, k_ld_product<4, false, false>}, {k_ld_product<2, true, false>, k_ld_product<4, true, false>}},
+    {{k_ld_product<2, false, true>, k_ld_product<4, false, true>}, {k_ld_product<2, true, true>, k_ld_product<4, true, true>}}};
+// A matrix of n_a x n_b pairs is walked in sub-blocks of at most blk rows a side (gev_dbg_output_chunk caps blk): side A of a block row
+// is prepared once, side B once per sub-block -- O(rows) against the product's O(rows^2); the planes, not the staged rows, are what
+// the product reads, so one staging buffer serves both sides.  prep(side_b, off, n, first) prepares rows [off, +n) of a side into its
+// planes (first: these rows have not been prepared before in this call); products(na, nb, d_out) launches what fills the sub-block's
+// results d_out[o] ([na][nb] in c->d_bp_out, null where outs[o] is).  They are copied into the caller's matrices outs[o] ([n_a][n_b],
+// each may be null) and the stream is waited for, sub-block by sub-block.  With no matrix wanted only the sides are prepared: every
+// block row of A and, where b_alone says that something of side B is wanted for itself, every block of B once
+template <int NOUT, class Prep, class Products>
+static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, uint32_t* const (&outs)[NOUT], bool b_alone, Prep prep, Products products)
+{
+    hipStream_t st = c->stream;
+    bool want_mat = false;
+    for (uint32_t* o : outs) want_mat = want_mat || o;
+    GEVC(c->d_bp_out.ensure(NOUT * std::min(blk, n_a) * std::min(blk, n_b) * sizeof(u32), st));
+    for (size_t ia = 0; ia < n_a; ia += blk) {
+        const size_t na = std::min(blk, n_a - ia);
+        GEVC(prep(false, ia, na, true));
+        for (size_t ib = 0; ib < n_b; ib += blk) {
+            if (!want_mat && (ia || !b_alone)) break;                                         // only side B's vectors are left to make, once
+            const size_t nb = std::min(blk, n_b - ib);
+            GEVC(prep(true, ib, nb, ia == 0));
+            if (want_mat) {
+                u32* d_out[NOUT];
+                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o] ? c->d_bp_out.as<u32>() + (size_t)o * na * nb : nullptr;
+                GEVC(products(na, nb, d_out));
+                for (int o = 0; o < NOUT; o++) {
+                    if (!outs[o]) continue;
+                    if (nb == n_b) HIPC(hipMemcpyAsync(outs[o] + ia * n_b, d_out[o], na * nb * sizeof(u32), hipMemcpyDeviceToHost, st));     // whole rows of the caller's matrix
+                    else HIPC(hipMemcpy2DAsync(outs[o] + ia * n_b + ib, n_b * sizeof(u32), d_out[o], nb * sizeof(u32), nb * sizeof(u32), na, hipMemcpyDeviceToHost, st));
+                }
+            }
+            HIPC(hipStreamSynchronize(st));
+        }
+    }
+    if (!want_mat) HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+}   // extern "C++"
 // ---- genotype counts per individual and per pair of individuals (gev_paircount.h) ---------------
-// the planes of a side: n_w4 words x n_pad individuals of x, then as many of y
-static size_t pair_words4(size_t snp_begin, size_t n_snps) { return n_snps ? (((snp_begin + n_snps - 1) >> 6) - (snp_begin >> 6) + 1 + 3) & ~(size_t)3 : 0; }
 // individuals [ind0, +n) of a side staged through c->d_stage (ensure_csr has run) in passes of <= ~256 MB of rows and prepared:
-// planes into `planes` (null: none), counts into d_het / d_hom / d_wsum (each may be null; entry i = individual ind0 + i)
+// planes into `planes` (null: none; n_w4 words x n_pad individuals of x, then as many of y), counts into d_het / d_hom / d_wsum (each may be null; entry i = individual ind0 + i)
 static int pair_prep_side(gev_ctx* c, PopState& P, int chr, size_t ind0, size_t n, size_t snp_begin, size_t n_snps, DevBuf* planes,
                           const u32* d_weight, u32* d_het, u32* d_hom, u64* d_wsum)
 {
     ChrStatic& S = P.cs[chr];
-    const size_t n_w4 = pair_words4(snp_begin, n_snps), n_pad = planes ? round_up(n, PC_TILE) : n;
+    const size_t n_w4 = gev_bp_words4(snp_begin, n_snps), n_pad = planes ? round_up(n, BP_TILE) : n;
     const size_t pass = std::max<size_t>(output_chunk(c, 256u << 20, S.stride) / 2, 1);                       // (the units are rows, as in gev_download_haps)
     GEVC(c->d_stage.ensure(std::max<size_t>(2 * std::min(pass, n) * S.stride, 16), c->stream));
     u64 *px = nullptr, *py = nullptr;
@@ -3905,7 +3960,7 @@ static int pair_begin(gev_ctx* c, int pop, int chr, const char* who, size_t snp_
 // individuals a side of a sub-block of the pair matrix: their words of the two planes within ~1 GB, at most 4096 (3 x 64 MB of results)
 static size_t pair_block(const gev_ctx* c, size_t snp_begin, size_t n_snps)
 {
-    return std::min<size_t>(output_chunk(c, (size_t)1 << 30, 2 * pair_words4(snp_begin, n_snps) * 8), 4096);
+    return std::min<size_t>(output_chunk(c, (size_t)1 << 30, 2 * gev_bp_words4(snp_begin, n_snps) * 8), 4096);
 }
 int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
                             const uint32_t* weight, uint32_t* n_het, uint32_t* n_hom_alt, uint64_t* wsum)
@@ -3930,8 +3985,8 @@ int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
         HIPC(hipMemcpyAsync(c->d_pair_w.p, weight, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
         d_weight = c->d_pair_w.as<u32>();
     }
-    GEVC(c->d_pair_cnt.ensure(n_ind * 16, st));
-    u64* d_ws = c->d_pair_cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
+    GEVC(c->d_bp_cnt.ensure(n_ind * 16, st));
+    u64* d_ws = c->d_bp_cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
     GEVC(pair_prep_side(c, P, chr, ind_begin, n_ind, snp_begin, n_snps, nullptr, d_weight, d_het, d_hom, wsum ? d_ws : nullptr));
     if (n_het) HIPC(hipMemcpyAsync(n_het, d_het, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
     if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt, d_hom, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -3939,11 +3994,8 @@ int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     HIPC(hipStreamSynchronize(st));
     return GEV_OK;
 }
-// The pair matrix is walked in sub-blocks of at most pair_block() individuals a side (gev_dbg_output_chunk caps them, and the rows of
-// a staging pass): side A of a block row is staged and prepared once, side B once per sub-block -- O(N L) against the product's
-// O(N^2 L) -- each through c->d_stage (the planes, not the staged rows, are what the product reads, so one staging buffer serves both
-// sides); every sub-block has its own results in c->d_pair_out and its own copy-out.  Tiles of 128 x 128 pairs, or of 64 x 64 where
-// the large ones would leave compute units without a workgroup.
+// The pair matrix is walked in sub-blocks of at most pair_block() individuals a side (bitprod_walk; gev_dbg_output_chunk caps them, and the
+// rows of a staging pass), each side staged and prepared through c->d_stage.
 int gev_pair_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t a_begin, size_t n_a, size_t b_begin, size_t n_b,
                              uint32_t* n_hethet, uint32_t* n_opphom, uint32_t* dot)
 {
@@ -3958,36 +4010,19 @@ int gev_pair_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, siz
     if (!n_hethet && !n_opphom && !dot) return GEV_OK;
     GEVC(ensure_csr(c, pop));
     hipStream_t st = c->stream;
-    if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const size_t blk = pair_block(c, snp_begin, n_snps), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
-    const size_t n_w4 = pair_words4(snp_begin, n_snps);
-    GEVC(c->d_pair_cnt.ensure((ba + bb) * sizeof(u32), st));
-    GEVC(c->d_pair_out.ensure(3 * ba * bb * sizeof(u32), st));
-    u32* d_hom_a = c->d_pair_cnt.as<u32>(); u32* d_hom_b = d_hom_a + ba;
-    for (size_t ia = 0; ia < n_a; ia += blk) {
-        const size_t na = std::min(blk, n_a - ia), pad_a = round_up(na, PC_TILE);
-        GEVC(pair_prep_side(c, P, chr, a_begin + ia, na, snp_begin, n_snps, &c->d_pair_a, nullptr, nullptr, d_hom_a, nullptr));
-        for (size_t ib = 0; ib < n_b; ib += blk) {
-            const size_t nb = std::min(blk, n_b - ib), pad_b = round_up(nb, PC_TILE);
-            GEVC(pair_prep_side(c, P, chr, b_begin + ib, nb, snp_begin, n_snps, &c->d_pair_b, nullptr, nullptr, d_hom_b, nullptr));
-            u32* d_out[3];
-            for (int o = 0; o < 3; o++) d_out[o] = outs[o] ? c->d_pair_out.as<u32>() + (size_t)o * na * nb : nullptr;
-            const u64 *xa = c->d_pair_a.as<u64>(), *xb = c->d_pair_b.as<u64>();
-            const bool large = (pad_a / PC_TILE) * (pad_b / PC_TILE) >= (size_t)c->n_cu;
-            const unsigned tile = large ? PC_TILE : PC_TILE / 2;
-            hipLaunchKernelGGL(large ? k_pair_product<4> : k_pair_product<2>, dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, st,
-                               xa, xa + n_w4 * pad_a, (u32)pad_a, xb, xb + n_w4 * pad_b, (u32)pad_b, (u32)n_w4, d_hom_a, d_hom_b, (u32)na, (u32)nb,
-                               d_out[0], d_out[1], d_out[2]);
-            KCHECK();
-            for (int o = 0; o < 3; o++) {
-                if (!outs[o]) continue;
-                if (nb == n_b) HIPC(hipMemcpyAsync(outs[o] + ia * n_b, d_out[o], na * nb * sizeof(u32), hipMemcpyDeviceToHost, st));     // whole rows of the caller's matrix
-                else HIPC(hipMemcpy2DAsync(outs[o] + ia * n_b + ib, n_b * sizeof(u32), d_out[o], nb * sizeof(u32), nb * sizeof(u32), na, hipMemcpyDeviceToHost, st));
-            }
-            HIPC(hipStreamSynchronize(st));
-        }
-    }
-    return GEV_OK;
+    const size_t blk = pair_block(c, snp_begin, n_snps), ba = std::min(blk, n_a), n_w4 = gev_bp_words4(snp_begin, n_snps);
+    GEVC(c->d_bp_cnt.ensure((ba + std::min(blk, n_b)) * sizeof(u32), st));
+    u32* d_hom_a = c->d_bp_cnt.as<u32>(); u32* d_hom_b = d_hom_a + ba;
+    return bitprod_walk(c, n_a, n_b, blk, outs, false,
+        [&](bool side_b, size_t off, size_t n, bool) -> int {
+            return pair_prep_side(c, P, chr, (side_b ? b_begin : a_begin) + off, n, snp_begin, n_snps, side_b ? &c->d_bp_b : &c->d_bp_a, nullptr, nullptr, side_b ? d_hom_b : d_hom_a, nullptr);
+        },
+        [&](size_t na, size_t nb, u32* const* d_out) -> int {
+            const size_t pad_a = round_up(na, BP_TILE), pad_b = round_up(nb, BP_TILE);
+            const u64 *xa = c->d_bp_a.as<u64>(), *xb = c->d_bp_b.as<u64>();
+            return bitprod_launch(c, pair_kernels, na, nb, (pad_a / BP_TILE) * (pad_b / BP_TILE), xa, xa + n_w4 * pad_a, (u32)pad_a, xb, xb + n_w4 * pad_b, (u32)pad_b, (u32)n_w4,
+                                  (const u32*)d_hom_a, (const u32*)d_hom_b, (u32)na, (u32)nb, d_out[0], d_out[1], d_out[2]);
+        });
 }
 // the arithmetic of gev_paircount.h compiled for the host on haplotype-major rows in host memory: no device, no context
 int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L, size_t snp_begin, size_t n_snps,
@@ -4010,7 +4045,7 @@ int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size
 // one snp_major_device pass (so a side is one pass), at most 4096 (2 x 64 MB of results)
 static size_t ld_block(const gev_ctx* c, size_t n_people, size_t ind_begin, size_t n_ind)
 {
-    const size_t plane = output_chunk(c, (size_t)1 << 30, gev_ld_words4(2 * ind_begin, 2 * n_ind) * 8);
+    const size_t plane = output_chunk(c, (size_t)1 << 30, gev_bp_words4(2 * ind_begin, 2 * n_ind) * 8);
     return std::min(std::min(plane, output_chunk(c, 256u << 20, ceil_div(2 * n_people, 64) * 8)), (size_t)4096);
 }
 struct LdSide { const u64* plane; u32 *c, *het, *hom; size_t n_pad; };
@@ -4018,7 +4053,7 @@ struct LdSide { const u64* plane; u32 *c, *het, *hom; size_t n_pad; };
 // vectors of cnt_stride entries at d_cnt
 static int ld_prep_side(gev_ctx* c, int pop, int chr, size_t s0, size_t n, size_t ind_begin, size_t n_ind, DevBuf& planes, u32* d_cnt, size_t cnt_stride, LdSide& side)
 {
-    const size_t n_w4 = gev_ld_words4(2 * ind_begin, 2 * n_ind), n_pad = round_up(n, LD_TILE);
+    const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind), n_pad = round_up(n, BP_TILE);
     size_t stride;
     GEVC(planes.ensure(std::max<size_t>(n_w4 * n_pad * 8, 16), c->stream));
     GEVC(snp_major_device(c, pop, chr, s0, n, stride));
@@ -4028,32 +4063,8 @@ static int ld_prep_side(gev_ctx* c, int pop, int chr, size_t s0, size_t n, size_
     KCHECK();
     return GEV_OK;
 }
-typedef void (*ld_kernel_t)(const u64*, u32, const u64*, u32, u32, u32, u32, u32*, LdScoreArgs);
-static ld_kernel_t ld_kernel(bool large, bool gen, bool score)
-{
-    if (score) {
-        if (gen) return large ? k_ld_product<4, true, true> : k_ld_product<2, true, true>;
-        return large ? k_ld_product<4, false, true> : k_ld_product<2, false, true>;
-    }
-    if (gen) return large ? k_ld_product<4, true, false> : k_ld_product<2, true, false>;
-    return large ? k_ld_product<4, false, false> : k_ld_product<2, false, false>;
-}
-// one product of one sub-block: tiles of 128 x 128 SNP pairs, or of 64 x 64 where fewer than `tiles` large ones have work and would
-// leave compute units without a workgroup
-static int ld_launch(gev_ctx* c, const LdSide& A, size_t na, const LdSide& B, size_t nb, size_t n_w4, size_t tiles, bool gen, bool score, u32* d_out, const LdScoreArgs& sa)
-{
-    if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const bool large = tiles >= (size_t)c->n_cu;
-    const unsigned tile = large ? LD_TILE : LD_TILE / 2;
-    hipLaunchKernelGGL(ld_kernel(large, gen, score), dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, c->stream,
-                       A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, d_out, sa);
-    KCHECK();
-    return GEV_OK;
-}
-// The SNP-pair matrix is walked in sub-blocks of at most ld_block() SNPs a side (gev_dbg_output_chunk caps them, and with them the SNPs
-// of a snp_major_device pass): side A of a block row is prepared once, side B once per sub-block -- O(L n) against the product's
-// O(L^2 n) -- each through c->d_snpmajor (the planes, not the SNP-major rows, are what the product reads, so one staging buffer serves
-// both sides and both chromosomes); every sub-block has its own results in c->d_ld_out and its own copy-out.
+// The SNP-pair matrix is walked in sub-blocks of at most ld_block() SNPs a side (bitprod_walk; gev_dbg_output_chunk caps them, and with them
+// the SNPs of a snp_major_device pass), each side prepared through c->d_snpmajor, which so serves both sides and both chromosomes.
 int gev_ld_counts(gev_ctx* c, int pop, int chr_a, size_t a_begin, size_t n_a, int chr_b, size_t b_begin, size_t n_b, size_t ind_begin, size_t n_ind,
                   uint32_t* n11, uint32_t* gg, uint32_t* c_a, uint32_t* het_a, uint32_t* hom_a, uint32_t* c_b, uint32_t* het_b, uint32_t* hom_b)
 {
@@ -4077,37 +4088,23 @@ int gev_ld_counts(gev_ctx* c, int pop, int chr_a, size_t a_begin, size_t n_a, in
     if (!want_mat && !want_b && !c_a && !het_a && !hom_a) return GEV_OK;
     hipStream_t st = c->stream;
     const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
-    const size_t n_w4 = gev_ld_words4(2 * ind_begin, 2 * n_ind);
-    GEVC(c->d_ld_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
-    GEVC(c->d_ld_out.ensure(2 * ba * bb * sizeof(u32), st));
-    u32* d_cnt_a = c->d_ld_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
-    for (size_t ia = 0; ia < n_a; ia += blk) {
-        const size_t na = std::min(blk, n_a - ia);
-        LdSide A, B;
-        GEVC(ld_prep_side(c, pop, chr_a, a_begin + ia, na, ind_begin, n_ind, c->d_ld_a, d_cnt_a, ba, A));
-        u32* const d_vec_a[3] = {A.c, A.het, A.hom};
-        for (int o = 0; o < 3; o++) if (vec_a[o]) HIPC(hipMemcpyAsync(vec_a[o] + ia, d_vec_a[o], na * sizeof(u32), hipMemcpyDeviceToHost, st));
-        for (size_t ib = 0; ib < n_b; ib += blk) {
-            if (!want_mat && (ia || !want_b)) break;                                          // only side B's vectors are left to make, once
-            const size_t nb = std::min(blk, n_b - ib);
-            GEVC(ld_prep_side(c, pop, chr_b, b_begin + ib, nb, ind_begin, n_ind, c->d_ld_b, d_cnt_b, bb, B));
-            u32* const d_vec_b[3] = {B.c, B.het, B.hom};
-            if (!ia) for (int o = 0; o < 3; o++) if (vec_b[o]) HIPC(hipMemcpyAsync(vec_b[o] + ib, d_vec_b[o], nb * sizeof(u32), hipMemcpyDeviceToHost, st));
-            if (want_mat) {
-                u32* d_out[2];
-                for (int o = 0; o < 2; o++) d_out[o] = mats[o] ? c->d_ld_out.as<u32>() + (size_t)o * na * nb : nullptr;
-                for (int o = 0; o < 2; o++) if (mats[o]) GEVC(ld_launch(c, A, na, B, nb, n_w4, (A.n_pad / LD_TILE) * (B.n_pad / LD_TILE), o == 1, false, d_out[o], LdScoreArgs{}));
-                for (int o = 0; o < 2; o++) {
-                    if (!mats[o]) continue;
-                    if (nb == n_b) HIPC(hipMemcpyAsync(mats[o] + ia * n_b, d_out[o], na * nb * sizeof(u32), hipMemcpyDeviceToHost, st));     // whole rows of the caller's matrix
-                    else HIPC(hipMemcpy2DAsync(mats[o] + ia * n_b + ib, n_b * sizeof(u32), d_out[o], nb * sizeof(u32), nb * sizeof(u32), na, hipMemcpyDeviceToHost, st));
-                }
-            }
-            HIPC(hipStreamSynchronize(st));
-        }
-    }
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind);
+    GEVC(c->d_bp_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
+    u32* d_cnt_a = c->d_bp_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
+    LdSide A, B;
+    return bitprod_walk(c, n_a, n_b, blk, mats, want_b,
+        [&](bool side_b, size_t off, size_t n, bool first) -> int {                           // a side's vectors come back the first time its SNPs are prepared
+            LdSide& S = side_b ? B : A; uint32_t* const* vec = side_b ? vec_b : vec_a;
+            if (side_b) GEVC(ld_prep_side(c, pop, chr_b, b_begin + off, n, ind_begin, n_ind, c->d_bp_b, d_cnt_b, bb, S));
+            else GEVC(ld_prep_side(c, pop, chr_a, a_begin + off, n, ind_begin, n_ind, c->d_bp_a, d_cnt_a, ba, S));
+            u32* const d_vec[3] = {S.c, S.het, S.hom};
+            for (int o = 0; o < 3 && first; o++) if (vec[o]) HIPC(hipMemcpyAsync(vec[o] + off, d_vec[o], n * sizeof(u32), hipMemcpyDeviceToHost, st));
+            return GEV_OK;
+        },
+        [&](size_t na, size_t nb, u32* const* d_out) -> int {
+            for (int o = 0; o < 2; o++) if (mats[o]) GEVC(bitprod_launch(c, ld_kernels[0][o], na, nb, (A.n_pad / BP_TILE) * (B.n_pad / BP_TILE), A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, d_out[o], LdScoreArgs{}));
+            return GEV_OK;
+        });
 }
 // the windows of SNPs [snp_begin, +n_snps) of a chromosome of L SNPs: both arrays non-decreasing, win_lo[t] <= snp_begin + t < win_hi[t] <= L
 static int ld_check_windows(const char* who, size_t snp_begin, size_t n_snps, const uint32_t* win_lo, const uint32_t* win_hi, size_t L)
@@ -4141,11 +4138,11 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     }
     hipStream_t st = c->stream;
     const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_snps), bb = std::min<size_t>(blk, P.cs[chr].L);
-    const size_t n_w4 = gev_ld_words4(2 * ind_begin, 2 * n_ind);
-    GEVC(c->d_ld_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
+    const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind);
+    GEVC(c->d_bp_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
     GEVC(c->d_ld_win.ensure(2 * n_snps * sizeof(u32), st));
     GEVC(c->d_ld_score.ensure(n_snps * (sizeof(u64) + sizeof(u32)), st));
-    u32* d_cnt_a = c->d_ld_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
+    u32* d_cnt_a = c->d_bp_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
     u32* d_lo = c->d_ld_win.as<u32>(); u32* d_hi = d_lo + n_snps;
     u64* d_score = c->d_ld_score.as<u64>(); u32* d_terms = (u32*)(d_score + n_snps);
     HIPC(hipMemcpyAsync(d_lo, win_lo, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
@@ -4154,19 +4151,19 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     for (size_t ia = 0; ia < n_snps; ia += blk) {
         const size_t na = std::min(blk, n_snps - ia);
         LdSide A, B;
-        GEVC(ld_prep_side(c, pop, chr, snp_begin + ia, na, ind_begin, n_ind, c->d_ld_a, d_cnt_a, ba, A));
+        GEVC(ld_prep_side(c, pop, chr, snp_begin + ia, na, ind_begin, n_ind, c->d_bp_a, d_cnt_a, ba, A));
         const size_t u0 = win_lo[ia], u1 = win_hi[ia + na - 1];
         for (size_t ib = u0; ib < u1; ib += blk) {
             const size_t nb = std::min(blk, u1 - ib);
-            GEVC(ld_prep_side(c, pop, chr, ib, nb, ind_begin, n_ind, c->d_ld_b, d_cnt_b, bb, B));
+            GEVC(ld_prep_side(c, pop, chr, ib, nb, ind_begin, n_ind, c->d_bp_b, d_cnt_b, bb, B));
             const LdScoreArgs sa{A.c, A.het, A.hom, B.c, B.het, B.hom, d_lo + ia, d_hi + ia, d_score + ia, d_terms + ia, (u64)n_ind, (u32)ib};
             size_t band_tiles = 0;                                                             // the large tiles of the sub-block that the band touches
-            for (size_t r0 = 0; r0 < na; r0 += LD_TILE) {
-                const size_t k0 = std::max<size_t>(win_lo[ia + r0], ib), k1 = std::min<size_t>(win_hi[ia + std::min<size_t>(r0 + LD_TILE, na) - 1], ib + nb);
-                if (k1 > k0) band_tiles += (k1 - 1 - ib) / LD_TILE - (k0 - ib) / LD_TILE + 1;
+            for (size_t r0 = 0; r0 < na; r0 += BP_TILE) {
+                const size_t k0 = std::max<size_t>(win_lo[ia + r0], ib), k1 = std::min<size_t>(win_hi[ia + std::min<size_t>(r0 + BP_TILE, na) - 1], ib + nb);
+                if (k1 > k0) band_tiles += (k1 - 1 - ib) / BP_TILE - (k0 - ib) / BP_TILE + 1;
             }
             if (!band_tiles) continue;
-            GEVC(ld_launch(c, A, na, B, nb, n_w4, band_tiles / LD_SCORE_TILES_PER_CU, genotype != 0, true, nullptr, sa));
+            GEVC(bitprod_launch(c, ld_kernels[1][genotype != 0], na, nb, band_tiles / LD_SCORE_TILES_PER_CU, A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, (u32*)nullptr, sa));
         }
     }
     if (score_q40) HIPC(hipMemcpyAsync(score_q40, d_score, n_snps * sizeof(u64), hipMemcpyDeviceToHost, st));

@@ -17,9 +17,8 @@
 // because its bytes cost less to make from bits (below), with no third plane and no range mask inside the product.
 //
 // The products run on bytes: one locus = one int8 of the operand.  Bits become bytes in registers, 16 loci (one matrix step of a lane)
-// at a time.  The order of the loci inside a step is free as long as both operands of a product use the same one -- a permutation of
-// the summation index cancels in the sum -- so the loci are taken where masks alone find them.  Of a 32-locus half word the loci of one
-// parity are packed as 2-bit fields (gev_pc_pack2)
+// at a time, in the order in which masks alone find them (the order inside a step is free: gev_bitprod.h).  Of a 32-locus half word
+// the loci of one parity are packed as 2-bit fields (gev_pc_pack2)
 //     c = ((x >> parity) & 0x55555555) | (((y >> parity) & 0x55555555) << 1)          field f = g of locus 2 f + parity
 // (x and y are disjoint, so the field is x + 2y), and four shifted masks turn c into the step's 16 bytes (gev_pc_expand)
 //     g bytes[j] = (c >> 2j) & 0x03030303        byte b = g of field j + 4 b
@@ -32,25 +31,10 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
-
-#if defined(__HIPCC__)
-#define GEV_PC_HD __host__ __device__
-#else
-#define GEV_PC_HD
-#endif
+#include "gev_bitprod.h"                           // GEV_PC_HD, gev_pc_range_mask, gev_pc_popcount64, the product and the preparation walk
 
 #define GEV_PC_MAX_SNPS ((size_t)1 << 30)         // dot can reach 4 * n_snps
 
-// the loci of word w (64 w .. 64 w + 63) that lie in [s0, s1)
-GEV_PC_HD inline uint64_t gev_pc_range_mask(size_t w, size_t s0, size_t s1)
-{
-    const size_t lo = w * 64, hi = lo + 64;
-    if (s1 <= lo || s0 >= hi || s0 >= s1) return 0;
-    uint64_t m = ~(uint64_t)0;
-    if (s0 > lo) m &= ~(uint64_t)0 << (s0 - lo);
-    if (s1 < hi) m &= ~(uint64_t)0 >> (hi - s1);
-    return m;
-}
 // one individual's word of the two planes from its two haplotype words
 GEV_PC_HD inline void gev_pc_planes(uint64_t a, uint64_t b, uint64_t mask, uint64_t& x, uint64_t& y) { x = (a ^ b) & mask; y = (a & b) & mask; }
 // the loci of one parity of a 32-locus half word as sixteen 2-bit fields: field f = g of locus 2 f + parity
@@ -77,14 +61,6 @@ GEV_PC_HD inline void gev_pc_finish(uint32_t xx, uint32_t gg, uint32_t hom_i, ui
     n_hethet = xx;
     dot = gg;
     n_opphom = hom_i + hom_k - ((gg - xx) >> 1);
-}
-GEV_PC_HD inline uint32_t gev_pc_popcount64(uint64_t v)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__popcll(v);
-#else
-    return (uint32_t)__builtin_popcountll(v);
-#endif
 }
 // sum over the loci of a word of weight * g: weight[first + b] is the weight of the word's locus b (only loci with a bit in x | y are
 // read, so first may be negative for a word the range begins in)
@@ -124,11 +100,7 @@ inline void gev_pc_counts_host(const uint64_t* bits, size_t row_stride_words, si
             for (int s = 0; s < 4; s++) {
                 uint32_t xe[4], ge[4];
                 gev_pc_expand_step(x, y, s, ge, xe);
-                for (int q = 0; q < 4; q++)
-                    for (int b = 0; b < 4; b++) {
-                        xb[i * n_bytes + w * 64 + 16 * s + 4 * q + b] = (int8_t)(xe[q] >> (8 * b));
-                        gb[i * n_bytes + w * 64 + 16 * s + 4 * q + b] = (int8_t)(ge[q] >> (8 * b));
-                    }
+                gev_bp_store16(xe, &xb[i * n_bytes + w * 64 + 16 * s]); gev_bp_store16(ge, &gb[i * n_bytes + w * 64 + 16 * s]);
             }
         }
         if (n_het) n_het[i] = het[i];
@@ -137,12 +109,10 @@ inline void gev_pc_counts_host(const uint64_t* bits, size_t row_stride_words, si
     if (!n_hethet && !n_opphom && !dot) return;
     for (size_t i = 0; i < n_a; i++)
         for (size_t k = 0; k < n_b; k++) {
-            const int8_t* xi = xb.data() + (a_begin + i) * n_bytes; const int8_t* xk = xb.data() + (b_begin + k) * n_bytes;
-            const int8_t* gi = gb.data() + (a_begin + i) * n_bytes; const int8_t* gk = gb.data() + (b_begin + k) * n_bytes;
-            int32_t xx = 0, gg = 0;                                  // the accumulators of the matrix instruction
-            for (size_t j = 0; j < n_bytes; j++) { xx += (int32_t)xi[j] * xk[j]; gg += (int32_t)gi[j] * gk[j]; }
+            const size_t ri = (a_begin + i) * n_bytes, rk = (b_begin + k) * n_bytes;
+            const uint32_t xx = gev_bp_dot_i8(xb.data() + ri, xb.data() + rk, n_bytes), gg = gev_bp_dot_i8(gb.data() + ri, gb.data() + rk, n_bytes);
             uint32_t o_hethet, o_opphom, o_dot;
-            gev_pc_finish((uint32_t)xx, (uint32_t)gg, hom[a_begin + i], hom[b_begin + k], o_hethet, o_opphom, o_dot);
+            gev_pc_finish(xx, gg, hom[a_begin + i], hom[b_begin + k], o_hethet, o_opphom, o_dot);
             if (n_hethet) n_hethet[i * n_b + k] = o_hethet;
             if (n_opphom) n_opphom[i * n_b + k] = o_opphom;
             if (dot) dot[i * n_b + k] = o_dot;
@@ -151,28 +121,27 @@ inline void gev_pc_counts_host(const uint64_t* bits, size_t row_stride_words, si
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------
-// The device.  Both kernels read STAGED rows (stage_rows_mutated: pool units resolved, mutation overlay applied, once per row).
+// The device (the walk and the product: gev_bitprod.h).  Both kernels read STAGED rows (stage_rows_mutated: pool units resolved,
+// mutation overlay applied, once per row).
 //
-// 1. k_pair_prep: one wave per individual walks the words of the SNP range (lane = word, coalesced), writes the individual's x and y
-// words into the two planes and reduces n_het, n_hom_alt and, with weights, wsum over the wave.  The planes are WORD-major:
-// plane[w * n_pad + i], so that the product's 16 lanes of a fragment row read 16 consecutive words.  They are padded to PC_TILE
-// individuals and to 4 words with zeros (a zero operand adds nothing to any sum), so the product needs no bounds on its loads.
-// gev_ind_genotype_counts is this kernel alone, without planes.
+// 1. k_pair_prep: a row of the side is an individual; its x and y words go into the two planes, n_het, n_hom_alt and, with weights,
+// wsum are its counts.  gev_ind_genotype_counts is this kernel alone, without planes.
 //
-// 2. k_pair_product: v_mfma_i32_16x16x64_i8, exact i32 accumulators.  A workgroup of four waves owns a PC_TILE x PC_TILE tile of pairs
-// and the whole SNP range: no split over the loci, no atomics.  A wave owns 64 x 64 pairs = 4 x 4 fragments of 16 x 16, two accumulator
-// sets (xx, gg) of 16 x 4 registers each.  Per step of 256 loci lane (r = lane & 15, q = lane >> 4) loads ONE word per plane per
-// fragment -- word 4 W + q of individual r -- straight from the planes (L2; the bit rows are 8x smaller than the operand bytes, and a
-// tile's 2 x 128 x 2 words of a step are shared by the two waves beside it through the cache); the word then feeds four matrix steps
-// (gev_pc_expand_step).  Inside a matrix step lane group q thus carries 16 loci of word 4 W + q in the order the masks give them: a
-// permutation of the k index that is the SAME for the A and the B operand, because both come from the same function of (lane, step),
-// so it cancels in the sum over k.  What has to be right is only the row / column map: A row = lane & 15, B column = lane & 15,
-// C/D column = lane & 15 and row = 4 (lane >> 4) + register.  The expansion (14 operations per fragment and step for both operands) is
-// amortised over the 4 fragments of the other side.  The finishing formulas run in the epilogue; every store is a vector store.
+// 2. k_pair_product: two planes a side, two accumulator sets (xx, gg), four matrix steps per word (gev_pc_expand_step: 14 operations
+// per fragment and step for both operands).  The finishing formulas run in the epilogue; every store is a vector store.
 // ------------------------------------------------------------------------------------------
-#define PC_TILE 128u                              // individuals the planes are padded to = the larger tile side
-typedef int pc_v4i __attribute__((ext_vector_type(4)));
-
+struct PairRow {
+    static constexpr int NPLANES = 2;
+    typedef BpSums<2, true> Sums;                 // n_het, n_hom_alt; wsum
+    const u64* rows; size_t row_w64; const u32* weight; u32 snp_begin;
+    __device__ void word(u32 i, size_t w, u64 mask, u64 (&v)[2], Sums& sums) const
+    {
+        const u64* ra = rows + 2 * (size_t)i * row_w64 + w;
+        gev_pc_planes(ra[0], ra[row_w64], mask, v[0], v[1]);
+        sums.s[0] += gev_pc_popcount64(v[0]); sums.s[1] += gev_pc_popcount64(v[1]);
+        if (weight) sums.w += gev_pc_weighted(v[0], v[1], weight, (ptrdiff_t)(64 * w) - (ptrdiff_t)snp_begin);
+    }
+};
 // rows: staged haplotype rows of n_ind individuals (2 per individual, row_w64 words apart), which are individuals [ind_off, +n_ind) of
 // the side; the block writes individuals [ind_off, +n_cover) of the planes, zeros beyond n_ind (the pad of the side's last pass).
 // planes: n_w4 words x n_pad individuals each or null; weight: n_snps weights (entry j = SNP snp_begin + j) or null; wsum null <=>
@@ -182,104 +151,31 @@ __global__ void __launch_bounds__(256) k_pair_prep(const u64* __restrict__ rows,
                                                    u64* __restrict__ plane_x, u64* __restrict__ plane_y, const u32* __restrict__ weight,
                                                    u32* __restrict__ n_het, u32* __restrict__ n_hom, u64* __restrict__ wsum)
 {
-    const u32 lane = threadIdx.x & 63u;
-    const u32 i = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (i >= n_cover) return;
-    const u32 snp_end = snp_begin + n_snps, w_first = snp_begin >> 6;
-    const u32 n_w = n_snps ? ((snp_end - 1u) >> 6) - w_first + 1u : 0u;
-    u32 het = 0, hom = 0; u64 ws = 0;
-    for (u32 w = lane; w < n_w4; w += 64u) {
-        u64 x = 0, y = 0;
-        if (i < n_ind && w < n_w) {
-            const u64* ra = rows + 2 * (size_t)i * row_w64 + w_first + w;
-            gev_pc_planes(ra[0], ra[row_w64], gev_pc_range_mask(w_first + w, snp_begin, snp_end), x, y);
-            het += gev_pc_popcount64(x); hom += gev_pc_popcount64(y);
-            if (weight) ws += gev_pc_weighted(x, y, weight, (ptrdiff_t)64 * (w_first + w) - (ptrdiff_t)snp_begin);
-        }
-        if (plane_x) { plane_x[(size_t)w * n_pad + ind_off + i] = x; plane_y[(size_t)w * n_pad + ind_off + i] = y; }
-    }
-    if (i >= n_ind) return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { het += __shfl_xor(het, d); hom += __shfl_xor(hom, d); ws += __shfl_xor((unsigned long long)ws, d); }
-    if (lane == 0) {
-        if (n_het) n_het[ind_off + i] = het;
-        if (n_hom) n_hom[ind_off + i] = hom;
-        if (wsum) wsum[ind_off + i] = ws;
-    }
+    bp_prep(PairRow{rows, row_w64, weight, snp_begin}, PairRow::Sums{{0, 0}, 0, {n_het, n_hom}, wsum}, n_ind, n_cover, ind_off, n_pad, snp_begin, n_snps, n_w4, {plane_x, plane_y});
 }
 
-// planes of side A (n_pad_a individuals) and side B (n_pad_b), n_w4 words each (a multiple of 4); hom_a / hom_b: n_hom_alt of the n_a / n_b
-// individuals; outputs row-major [n_a][n_b], each may be null.  FR: 16 x 16 fragments per wave and side (4: tiles of 128 x 128, 2: tiles of
-// 64 x 64 for blocks too small to fill the device with the large ones).  blockIdx.y = tile of A, blockIdx.x = tile of B
+struct PairProduct {
+    static constexpr int NPLANES = 2, NACC = 2, STEPS = 4;
+    __device__ static void expand(const u64 (&w)[2], int s, pc_v4i (&f)[2]) { u32 e[4], g[4]; gev_pc_expand_step(w[0], w[1], s, g, e); f[0] = bp_v4(e); f[1] = bp_v4(g); }   // x, g
+};
+// planes of side A (n_pad_a individuals) and side B (n_pad_b), n_w4 words each; hom_a / hom_b: n_hom_alt of the n_a / n_b individuals;
+// outputs row-major [n_a][n_b], each may be null
 template <int FR>
 __global__ void __launch_bounds__(256) k_pair_product(const u64* __restrict__ xa_p, const u64* __restrict__ ya_p, u32 n_pad_a,
                                                       const u64* __restrict__ xb_p, const u64* __restrict__ yb_p, u32 n_pad_b, u32 n_w4,
                                                       const u32* __restrict__ hom_a, const u32* __restrict__ hom_b, u32 n_a, u32 n_b,
                                                       u32* __restrict__ n_hethet, u32* __restrict__ n_opphom, u32* __restrict__ dot)
 {
-    constexpr u32 WAVE = 16u * FR, TILE = 2u * WAVE;
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u32 r = lane & 15u, q = lane >> 4;
-    const u32 a0 = blockIdx.y * TILE + (wave >> 1) * WAVE, b0 = blockIdx.x * TILE + (wave & 1u) * WAVE;         // the wave's pairs
-    if (a0 >= n_a || b0 >= n_b) return;                                                                        // (nothing of the wave's is stored)
-    pc_v4i acc_x[FR][FR], acc_g[FR][FR];
-#pragma unroll
-    for (int m = 0; m < FR; m++)
-#pragma unroll
-        for (int n = 0; n < FR; n++) { acc_x[m][n] = pc_v4i{0, 0, 0, 0}; acc_g[m][n] = pc_v4i{0, 0, 0, 0}; }
-    const u64* pxa = xa_p + (size_t)q * n_pad_a + a0 + r; const u64* pya = ya_p + (size_t)q * n_pad_a + a0 + r;
-    const u64* pxb = xb_p + (size_t)q * n_pad_b + b0 + r; const u64* pyb = yb_p + (size_t)q * n_pad_b + b0 + r;
-    u64 xa[FR], ya[FR], xb[FR], yb[FR];                       // the step in hand
-    u64 nxa[FR], nya[FR], nxb[FR], nyb[FR];                   // the next one, loaded while this one is multiplied
-#pragma unroll
-    for (int m = 0; m < FR; m++) { nxa[m] = pxa[16 * m]; nya[m] = pya[16 * m]; nxb[m] = pxb[16 * m]; nyb[m] = pyb[16 * m]; }
-    for (u32 W = 0; W < n_w4; W += 4u) {
-#pragma unroll
-        for (int m = 0; m < FR; m++) { xa[m] = nxa[m]; ya[m] = nya[m]; xb[m] = nxb[m]; yb[m] = nyb[m]; }
-        if (W + 4u < n_w4) {
-            pxa += (size_t)4 * n_pad_a; pya += (size_t)4 * n_pad_a; pxb += (size_t)4 * n_pad_b; pyb += (size_t)4 * n_pad_b;
-#pragma unroll
-            for (int m = 0; m < FR; m++) { nxa[m] = pxa[16 * m]; nya[m] = pya[16 * m]; nxb[m] = pxb[16 * m]; nyb[m] = pyb[16 * m]; }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            pc_v4i ax[FR], ag[FR], bx[FR], bg[FR];
-#pragma unroll
-            for (int m = 0; m < FR; m++) {
-                u32 e[4], g[4];
-                gev_pc_expand_step(xa[m], ya[m], s, g, e);
-                ax[m] = pc_v4i{(int)e[0], (int)e[1], (int)e[2], (int)e[3]}; ag[m] = pc_v4i{(int)g[0], (int)g[1], (int)g[2], (int)g[3]};
-                gev_pc_expand_step(xb[m], yb[m], s, g, e);
-                bx[m] = pc_v4i{(int)e[0], (int)e[1], (int)e[2], (int)e[3]}; bg[m] = pc_v4i{(int)g[0], (int)g[1], (int)g[2], (int)g[3]};
-            }
-#pragma unroll
-            for (int m = 0; m < FR; m++)
-#pragma unroll
-                for (int n = 0; n < FR; n++) {
-                    acc_x[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ax[m], bx[n], acc_x[m][n], 0, 0, 0);
-                    acc_g[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ag[m], bg[n], acc_g[m][n], 0, 0, 0);
-                }
-        }
-    }
-    // C/D: column = lane & 15, row = 4 (lane >> 4) + register
-#pragma unroll
-    for (int n = 0; n < FR; n++) {
-        const u32 k = b0 + 16u * n + r;
-        if (k >= n_b) continue;
-        const u32 hk = hom_b[k];
-#pragma unroll
-        for (int m = 0; m < FR; m++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const u32 i = a0 + 16u * m + 4u * q + v;
-                if (i >= n_a) continue;
-                u32 o_hethet, o_opphom, o_dot;
-                gev_pc_finish((u32)acc_x[m][n][v], (u32)acc_g[m][n][v], hom_a[i], hk, o_hethet, o_opphom, o_dot);
-                const size_t at = (size_t)i * n_b + k;
-                if (n_hethet) n_hethet[at] = o_hethet;
-                if (n_opphom) n_opphom[at] = o_opphom;
-                if (dot) dot[at] = o_dot;
-            }
-    }
+    const u64* const pa[2] = {xa_p, ya_p}; const u64* const pb[2] = {xb_p, yb_p};
+    u32 a0, b0; pc_v4i acc[2][FR][FR] = {};
+    if (!bp_product<FR, PairProduct>(pa, n_pad_a, pb, n_pad_b, n_w4, n_a, n_b, [](u32, u32) { return false; }, a0, b0, acc)) return;
+    bp_for_each<FR>(acc, a0, b0, n_a, n_b, [&](u32 i, u32 k, const u32 (&p)[2]) {
+        u32 o_hethet, o_opphom, o_dot;
+        gev_pc_finish(p[0], p[1], hom_a[i], hom_b[k], o_hethet, o_opphom, o_dot);
+        const size_t at = (size_t)i * n_b + k;
+        if (n_hethet) n_hethet[at] = o_hethet;
+        if (n_opphom) n_opphom[at] = o_opphom;
+        if (dot) dot[at] = o_dot;
+    });
 }
 #endif

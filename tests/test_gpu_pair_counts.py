@@ -12,6 +12,7 @@ from geneevolve_amd import capi, relatedness
 from geneevolve_amd.host import Simulation, SyntheticConfig
 from tests import helpers
 from tests.pair_counts_inputs import PairTruth
+from tests.snp_counts_inputs import random_rows
 from tests.test_gpu_snp_counts import overlay_situations, unpacked
 
 pytestmark = pytest.mark.gpu
@@ -150,6 +151,27 @@ def test_weighted_sums_need_64_bits(awkward):
         assert [int(v) for v in ws] == [int(v) * 0xFFFFFFFF for v in g.sum(axis=1)]
     finally:
         ctx.dbg_output_chunk(0)
+
+
+def test_blocks_wide_enough_for_the_large_tiles(gpu_lib):
+    """The product takes tiles of 128 x 128 pairs where they give every compute unit work, of 64 x 64 otherwise; with the 256 compute
+    units of an MI355X a block of 2100 x 2100 individuals (17 x 17 large tiles, the last one partly filled on both sides) and one of
+    2200 x 2049 (18 x 17) take the large ones; the blocks before this took the small ones.  2300 individuals x 200 SNPs, founders with
+    every allele frequency from 0 to 1; every sum is at most 800, so the truth's products are exact in float64"""
+    n, L = 2300, 200
+    cfg = SyntheticConfig(n, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.05, n_cv=10, seed=6, with_mutation=False)
+    ctx = gpu_lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    ctx.upload_founders(0, 0, capi.pack_rows(random_rows(np.random.RandomState(23), n, L)), L)
+    ctx.synth_cv_founders(0, 0, 0, 2 * n, 9)
+    sim = Simulation(ctx, 79, 1, True)
+    sim.ras_initial_human_gen0(0, n)
+    sim.next_generation_rm(0, n)
+    bits = unpacked(ctx, 0, 0)
+    hethet, opphom, dot = check_block(ctx, 0, 0, PairTruth(bits, products=np.float64), 0, L, 0, 2100, 150, 2100, "2100 x 2100 individuals")
+    assert hethet.any() and opphom.any() and int(dot.max()) > 255
+    check_block(ctx, 0, 0, PairTruth(bits, 1, 130, products=np.float64), 1, 130, 3, 2200, 1, 2049, "2200 x 2049 individuals")
+    ctx.close()
 
 
 # ---- fixture replays -------------------------------------------------------------------------------------------------------------------
