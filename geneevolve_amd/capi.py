@@ -97,7 +97,7 @@ ABI_SYMBOLS = [
     "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
     "format_info_text", "dbg_format_g", "dbg_format_g_host",
     "set_founder_names", "format_interval_text", "dbg_format_interval_text_host",
-    "dbg_verify_planes", "dbg_output_chunk", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec", "dbg_sampling_path", "dbg_ad_path",
+    "dbg_verify_planes", "dbg_output_chunk", "dbg_bitprod_tiles", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec", "dbg_sampling_path", "dbg_ad_path",
 ]
 
 
@@ -798,6 +798,13 @@ class GevContext:
     def dbg_output_chunk(self, max_units=0):
         """test hook: the following output calls stage at most max_units rows / individuals / SNPs (SNPs in 64s) per pass; 0 = byte budgets"""
         self._call_new("dbg_output_chunk", C.c_size_t(max_units))
+
+    def dbg_bitprod_tiles(self, mode=-1):
+        """test hook: the tile size of the following pair-count / LD products (0 = by compute units, 1 = always 64 x 64, 2 = always
+        128 x 128, -1 = unchanged) -> (small, large): the product launches on either size since the context was created"""
+        n = (C.c_ulonglong * 2)()
+        self._call_new("dbg_bitprod_tiles", C.c_int(mode), n)
+        return int(n[0]), int(n[1])
 
     def download_haps(self, pop, chr, row_begin=0, n_rows=None, stride_words=None):
         L = self._nsnp[(pop, chr)]

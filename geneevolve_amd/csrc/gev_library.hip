@@ -303,6 +303,8 @@ struct gev_ctx {
     DevBuf d_snpmajor, d_text;
     DevBuf d_snpcnt;               // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
     int n_cu = 0;                  // compute units of the device (bitprod_launch: the tile size), asked for by the first call
+    int dbg_bp_tiles = 0;          // gev_dbg_bitprod_tiles: 0 = the tile size by compute units, 1 = always 64 x 64, 2 = always 128 x 128
+    unsigned long long bp_launches[2] = {0, 0};   // product launches on small / large tiles over the context's life (bitprod_launch)
     DevBuf d_bp_a, d_bp_b, d_bp_cnt, d_bp_out;   // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
     DevBuf d_pair_w, d_ld_win, d_ld_score;       // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
@@ -3874,15 +3876,17 @@ int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_
 // ---- the matrix-core products over bit planes (gev_bitprod.h): what the pair counts and LD share on the host --------
 extern "C++" {      // (templates cannot have the C linkage of the block this file's functions sit in)
 // One product of one sub-block of na x nb pairs with kernel k[large]: tiles of 128 x 128 pairs, or of 64 x 64 where fewer than `tiles`
-// large ones have work and would leave compute units without a workgroup.  k[0]: the instantiation with FR = 2, k[1]: FR = 4
+// large ones have work and would leave compute units without a workgroup.  k[0]: the instantiation with FR = 2, k[1]: FR = 4.  The only
+// place that knows the test mode of gev_dbg_bitprod_tiles and counts the launches
 template <class K, class... Args>
 static int bitprod_launch(gev_ctx* c, K* const (&k)[2], size_t na, size_t nb, size_t tiles, Args... args)
 {
     if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const bool large = tiles >= (size_t)c->n_cu;
+    const bool large = c->dbg_bp_tiles ? c->dbg_bp_tiles == 2 : tiles >= (size_t)c->n_cu;
     const unsigned tile = large ? BP_TILE : BP_TILE / 2;
     hipLaunchKernelGGL(k[large], dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, c->stream, args...);
     KCHECK();
+    c->bp_launches[large]++;
     return GEV_OK;
 }
 // the ten instantiations: [large]; [score][genotype][large]
@@ -3928,6 +3932,15 @@ static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, uint32_t
     return GEV_OK;
 }
 }   // extern "C++"
+// test hook: the tile size of the following products (0: by compute units, 1: 64 x 64, 2: 128 x 128, -1: as it is) and the launches so far
+int gev_dbg_bitprod_tiles(gev_ctx* c, int mode, unsigned long long launches[2])
+{
+    GEVC(check_not_pending(c));
+    if (mode < -1 || mode > 2) return fail(GEV_EINVAL, "dbg_bitprod_tiles: mode %d (0: by compute units, 1: tiles of 64 x 64, 2: tiles of 128 x 128, -1: unchanged)", mode);
+    if (mode >= 0) c->dbg_bp_tiles = mode;
+    if (launches) { launches[0] = c->bp_launches[0]; launches[1] = c->bp_launches[1]; }
+    return GEV_OK;
+}
 // ---- genotype counts per individual and per pair of individuals (gev_paircount.h) ---------------
 // individuals [ind0, +n) of a side staged through c->d_stage (ensure_csr has run) in passes of <= ~256 MB of rows and prepared:
 // planes into `planes` (null: none; n_w4 words x n_pad individuals of x, then as many of y), counts into d_het / d_hom / d_wsum (each may be null; entry i = individual ind0 + i)

@@ -770,6 +770,12 @@ int    gev_dbg_prefilter_sweep(gev_ctx*, uint32_t x_begin, uint32_t x_end, unsig
 /* gev_dbg_output_chunk: no staging pass of the following genotype output calls takes more than max_units haplotype rows / individuals /
  * SNPs (SNPs: rounded down to a multiple of 64, at least 64), so that small tests run many passes; 0 = the byte budgets again.  Refused while a generation is pending. */
 int    gev_dbg_output_chunk(gev_ctx*, size_t max_units);
+/* gev_dbg_bitprod_tiles: the tile size of the matrix-core products of the following gev_pair_genotype_counts / gev_ld_counts /
+ * gev_ld_scores calls.  mode 0 = by the device's compute units (the default: tiles of 128 x 128 where a sub-block has at least as many
+ * of them as the device has compute units, of 64 x 64 otherwise), 1 = always 64 x 64, 2 = always 128 x 128, -1 = leave the mode as it
+ * is; anything else GEV_EINVAL.  launches (may be NULL): [0] / [1] = product launches on small / large tiles since the context was
+ * created, so that a test can assert which instantiation it ran.  Results never depend on the mode.  Refused while a generation is pending. */
+int    gev_dbg_bitprod_tiles(gev_ctx*, int mode, unsigned long long launches[2]);
 /* gev_dbg_pool_stats: out[0] = times the free list of a population's segment unit pool was rebuilt (the largest count over its active
  * chromosomes), out[1] = generations enqueued again because the free list ran out, over the context's life.  Diagnostic. */
 int    gev_dbg_pool_stats(gev_ctx*, int pop, unsigned long long out[2]);

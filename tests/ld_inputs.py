@@ -33,6 +33,16 @@ def numpy_q40(num, den_j, den_k):
     return np.where(ok, np.rint(r2 * Q40), 0.0).astype(np.uint64)
 
 
+def numpy_q40_reassociated(num, den_j, den_k):
+    """what the quantum is NOT: (x / den_j) * (x / den_k), the same r^2 in another order of the double operations.  It differs from
+    numpy_q40 in about one term in 10^5 once num^2 and den_j den_k round, and in none while they are exact and small; the tests that
+    mean to tell the two apart assert that their input does"""
+    num, den_j, den_k = np.broadcast_arrays(np.asarray(num, dtype=np.int64), np.asarray(den_j, dtype=np.uint64), np.asarray(den_k, dtype=np.uint64))
+    ok = (den_j != 0) & (den_k != 0)
+    x, dj, dk = num.astype(np.float64), np.where(ok, den_j, 1).astype(np.float64), np.where(ok, den_k, 1).astype(np.float64)
+    return np.where(ok, np.rint((x / dj) * (x / dk) * Q40), 0.0).astype(np.uint64)
+
+
 def numpy_num_den(counts, ni, genotype):
     """(num [na][nb], den_a [na], den_b [nb]) of numpy_ld_counts' result, int64"""
     n11, gg, ca, hea, hoa, cb, heb, hob = counts
@@ -40,6 +50,41 @@ def numpy_num_den(counts, ni, genotype):
         return ni * gg - ca[:, None] * cb[None, :], ni * (hea + 4 * hoa) - ca * ca, ni * (heb + 4 * hob) - cb * cb
     n = 2 * ni
     return n * n11 - ca[:, None] * cb[None, :], ca * (n - ca), cb * (n - cb)
+
+
+def structured_rows(rs, n_ind, L):
+    """uint8 [2 * n_ind][L] of 0/1 in strong LD: 12 ancestral haplotypes of fair coin bits; an individual's first haplotype copies a
+    random ancestor, its second the same one with probability 0.7 and another random one otherwise; every bit is then flipped with
+    probability 0.02.  Column 0 is all 0 and column L // 2 all 1.  With tens of thousands of individuals the numerators and
+    denominators of r^2 are far beyond 2^26.5, so their products are no doubles and every operation of the quantum rounds"""
+    anc = rs.randint(0, 2, size=(12, L)).astype(np.uint8)
+    first = rs.randint(0, 12, size=n_ind)
+    second = np.where(rs.random_sample(n_ind) < 0.7, first, rs.randint(0, 12, size=n_ind))
+    rows = np.empty((2 * n_ind, L), dtype=np.uint8)
+    rows[0::2] = anc[first]; rows[1::2] = anc[second]
+    rows ^= (rs.random_sample((2 * n_ind, L)) < 0.02).astype(np.uint8)
+    rows[:, 0] = 0; rows[:, L // 2] = 1
+    return rows
+
+
+def rounding_shares(truth, snp_begin, win_lo, win_hi, genotype):
+    """of the in-window terms of SNPs snp_begin + t whose quantum lies strictly between 0 and 2^40: (the share whose num^2 is not a
+    double, the share whose den_j den_k is not a double), decided in Python integers.  (double)num and (double)den are exact here."""
+    num, den_a, den_b = numpy_num_den(truth.counts, truth.ni, genotype)
+    q = truth.q[genotype]
+    terms = nn = dd = 0
+    for t, (lo, hi) in enumerate(zip(win_lo, win_hi)):
+        j = snp_begin + t - truth.s0
+        for k in range(int(lo) - truth.s0, int(hi) - truth.s0):
+            if not 0 < int(q[j, k]) < 1 << 40:
+                continue
+            x, dj, dk = int(num[j, k]), int(den_a[j]), int(den_b[k])
+            assert abs(x) < 1 << 53 and dj < 1 << 53 and dk < 1 << 53
+            terms += 1
+            nn += int(float(x) * float(x)) != x * x
+            dd += int(float(dj) * float(dk)) != dj * dk
+    assert terms, "a quantum strictly between 0 and 2^40"
+    return nn / terms, dd / terms
 
 
 class _Lazy:
@@ -64,18 +109,23 @@ class LDTruth:
     def kind(self, genotype):
         """(quanta uint64 [ns][ns], polymorphic bool [ns]) of one kind of r^2, computed when first asked for"""
         if genotype not in self._kinds:
-            num, den_a, den_b = numpy_num_den(self.counts, self.ni, genotype)
-            self._kinds[genotype] = (numpy_q40(num, den_a[:, None], den_b[None, :]), den_a > 0)
+            self._kinds[genotype] = (self.quanta(genotype), numpy_num_den(self.counts, self.ni, genotype)[1] > 0)
         return self._kinds[genotype]
+
+    def quanta(self, genotype, quantum=numpy_q40):
+        """uint64 [ns][ns]: quantum(num, den_j, den_k) of every pair"""
+        num, den_a, den_b = numpy_num_den(self.counts, self.ni, genotype)
+        return quantum(num, den_a[:, None], den_b[None, :])
 
     def block(self, a0, na, b0, nb):
         n11, gg, c, het, hom = self.counts[:5]
         ra, rb = slice(a0 - self.s0, a0 - self.s0 + na), slice(b0 - self.s0, b0 - self.s0 + nb)
         return n11[ra, rb], gg[ra, rb], c[ra], het[ra], hom[ra], c[rb], het[rb], hom[rb]
 
-    def scores(self, snp_begin, win_lo, win_hi, genotype):
-        """-> (score_q40 uint64, n_terms uint32) of SNPs snp_begin + t with windows [win_lo[t], win_hi[t]), all inside [s0, s0 + ns)"""
-        q, poly = self.q[genotype], self.poly[genotype]
+    def scores(self, snp_begin, win_lo, win_hi, genotype, q=None):
+        """-> (score_q40 uint64, n_terms uint32) of SNPs snp_begin + t with windows [win_lo[t], win_hi[t]), all inside [s0, s0 + ns).
+        q: other quanta than the truth's (self.quanta(genotype, another_form))"""
+        q, poly = self.q[genotype] if q is None else q, self.poly[genotype]
         score = np.zeros(len(win_lo), dtype=np.uint64); terms = np.zeros(len(win_lo), dtype=np.uint32)
         for t, (lo, hi) in enumerate(zip(win_lo, win_hi)):
             assert self.s0 <= lo and hi <= self.s0 + self.ns

@@ -11,7 +11,8 @@ import pytest
 from geneevolve_amd import capi, ld
 from geneevolve_amd.host import Simulation, SyntheticConfig
 from tests import helpers
-from tests.ld_inputs import LDTruth, numpy_ld_counts
+from tests.ld_inputs import LDTruth, numpy_ld_counts, numpy_q40_reassociated, rounding_shares, structured_rows
+from tests.pair_counts_inputs import tile_mode
 from tests.snp_counts_inputs import random_rows
 from tests.test_gpu_snp_counts import overlay_situations, unpacked
 
@@ -88,8 +89,7 @@ def awkward(request, gpu_lib):
     ctx.close()
 
 
-@pytest.mark.parametrize("chunk", [0, 7], ids=["byte budgets", "output chunk 7"])
-def test_rectangular_blocks(awkward, chunk):
+def rectangular_blocks(awkward, chunk):
     ctx, n, L, bits, pos = awkward
     ctx.dbg_output_chunk(chunk)
     try:
@@ -100,8 +100,22 @@ def test_rectangular_blocks(awkward, chunk):
         ctx.dbg_output_chunk(0)
 
 
-def test_blocks_of_333_snps_and_the_identities(awkward):
-    """333 x 333 SNPs: three tiles a side, the last one partly filled.  Of a self block: symmetric, n11[j][j] = c_j, gg[j][j] = het + 4 hom"""
+@pytest.mark.parametrize("chunk", [0, 7], ids=["byte budgets", "output chunk 7"])
+def test_rectangular_blocks(awkward, chunk):
+    rectangular_blocks(awkward, chunk)
+
+
+@pytest.mark.parametrize("chunk", [0, 7], ids=["byte budgets", "output chunk 7"])
+def test_rectangular_blocks_on_the_large_tiles(awkward, chunk):
+    """the same blocks and individual ranges with the 128 x 128 instantiations forced (gev_dbg_bitprod_tiles(2)), which the compute-unit
+    rule gives no block below about 2000 SNPs a side: one partly filled tile, down to one pair in it"""
+    with tile_mode(awkward[0], 2) as t:
+        rectangular_blocks(awkward, chunk)
+        small, large = t.launched()
+        assert small == 0 and (large == 2 * len(IND) * len(BLOCKS) if chunk == 0 else large > 0)
+
+
+def blocks_of_333_snps_and_the_identities(awkward):
     ctx, n, L, bits, pos = awkward
     for i0, ni in IND:
         n11, gg, c, het, hom = check_block(ctx, 0, 0, bits, 100, 333, 0, bits, 100, 333, i0, ni, "self block")[:5]
@@ -114,6 +128,18 @@ def test_blocks_of_333_snps_and_the_identities(awkward):
             check_block(ctx, 0, 0, bits, 50, 333, 0, bits, 4600, 333, i0, ni, "output chunk 7")
     finally:
         ctx.dbg_output_chunk(0)
+
+
+def test_blocks_of_333_snps_and_the_identities(awkward):
+    """333 x 333 SNPs: three tiles a side, the last one partly filled.  Of a self block: symmetric, n11[j][j] = c_j, gg[j][j] = het + 4 hom"""
+    blocks_of_333_snps_and_the_identities(awkward)
+
+
+def test_blocks_of_333_snps_and_the_identities_on_the_large_tiles(awkward):
+    """333 x 333 SNPs on tiles of 128 x 128: three tiles a side, the last one filled to 77"""
+    with tile_mode(awkward[0], 2) as t:
+        blocks_of_333_snps_and_the_identities(awkward)
+        assert t.large_only()
 
 
 def test_per_snp_vectors_equal_the_snp_counter(awkward):
@@ -156,10 +182,7 @@ def test_each_output_may_be_null_and_empty_requests(awkward):
     assert fs(ctx.h, i(0), i(0), z(70), z(0), None, None, z(5), z(200), i(1), p(score), None) == 0 and (score == 7).all()
 
 
-@pytest.mark.parametrize("genotype", [False, True], ids=["haplotype r2", "genotype r2"])
-def test_ld_scores_by_count(awkward, genotype):
-    """w = 0, 1, 50, 300 on a sub-range of 90 SNPs whose windows reach outside it; among individuals (32, 32) the range lies around a
-    monomorphic SNP, so the windows hold both kinds and the zero rule is at work"""
+def ld_scores_by_count(awkward, genotype):
     ctx, n, L, bits, pos = awkward
     for i0, ni in IND:
         s0, truth = around_a_monomorphic_snp(bits, 32, 32, 90, 300)
@@ -189,7 +212,22 @@ def test_ld_scores_by_count(awkward, genotype):
 
 
 @pytest.mark.parametrize("genotype", [False, True], ids=["haplotype r2", "genotype r2"])
-def test_ld_scores_by_distance(awkward, genotype):
+def test_ld_scores_by_count(awkward, genotype):
+    """w = 0, 1, 50, 300 on a sub-range of 90 SNPs whose windows reach outside it; among individuals (32, 32) the range lies around a
+    monomorphic SNP, so the windows hold both kinds and the zero rule is at work"""
+    ld_scores_by_count(awkward, genotype)
+
+
+@pytest.mark.parametrize("genotype", [False, True], ids=["haplotype r2", "genotype r2"])
+def test_ld_scores_by_count_on_the_large_tiles(awkward, genotype):
+    """the score epilogue of the 128 x 128 instantiations (its own fragment loops, row reduction and atomics) on the same windows: of
+    one SNP (w = 0), with an empty band on one side of the tile, around a monomorphic SNP, cut at the chromosome's ends"""
+    with tile_mode(awkward[0], 2) as t:
+        ld_scores_by_count(awkward, genotype)
+        assert t.large_only()
+
+
+def ld_scores_by_distance(awkward, genotype):
     ctx, n, L, bits, pos = awkward
     s0, truth = around_a_monomorphic_snp(bits, 32, 32, 150, 200)
     step = int(pos[1] - pos[0])
@@ -207,6 +245,19 @@ def test_ld_scores_by_distance(awkward, genotype):
     assert len(set((hi - lo).tolist())) > 10
     check_scores(ctx, 0, 0, truth, s0, 150, lo, hi, 32, 32, genotype, "uneven map")
     assert truth.meaningful(s0, lo, hi, genotype)
+
+
+@pytest.mark.parametrize("genotype", [False, True], ids=["haplotype r2", "genotype r2"])
+def test_ld_scores_by_distance(awkward, genotype):
+    ld_scores_by_distance(awkward, genotype)
+
+
+@pytest.mark.parametrize("genotype", [False, True], ids=["haplotype r2", "genotype r2"])
+def test_ld_scores_by_distance_on_the_large_tiles(awkward, genotype):
+    """... and on windows by distance, the uneven map included"""
+    with tile_mode(awkward[0], 2) as t:
+        ld_scores_by_distance(awkward, genotype)
+        assert t.large_only()
 
 
 # ---- more haplotype words than one pass of the loop, and not a multiple of its step -----------------------------------------------------
@@ -239,9 +290,13 @@ def test_many_haplotype_words(gpu_lib):
 # ---- the tiles of 128 x 128 ----------------------------------------------------------------------------------------------------------------
 def test_blocks_and_bands_wide_enough_for_the_large_tiles(gpu_lib):
     """The product takes tiles of 128 x 128 where they give every compute unit work, of 64 x 64 otherwise; with the 256 compute units of an
-    MI355X a block of 2100 x 2100 SNPs (17 x 17 large tiles) and a band of 1500 SNPs to either side of 4096 SNPs (644 large tiles in the
-    first sub-block of 4096 SNPs, 68 in the second: one call, both tile sizes) take the large ones; the blocks before this took the
-    small ones.  40 individuals x 5000 SNPs, founders with every allele frequency from 0 to 1"""
+    MI355X a block of 2100 x 2100 SNPs (17 x 17 large tiles) launches on the large ones alone and a band of 1500 SNPs to either side of
+    4096 SNPs (644 large tiles in the first sub-block of 4096 SNPs, 68 in the second: one call, both tile sizes) on both, which the
+    launch counters of gev_dbg_bitprod_tiles assert; the 2100 x 2100 block once more with the small tiles forced is a grid of 33 x 33 of
+    them.  Then the walk at its real side, byte budgets alone: SNPs (0, 4200) x (700, 4300) are one sub-block of 4096 x 4096 on large
+    tiles and the ragged remainders 4096 x 204, 104 x 4096 and 104 x 204 on small ones, copied out at a pitch of 4300 with side B's
+    vectors at offset 4096; scores of all 5000 SNPs at w = 1500 are block rows of 4096 and 904 SNPs, the second with windows, scores
+    and a band of its own.  40 individuals x 5000 SNPs, founders with every allele frequency from 0 to 1"""
     n, L = 40, 5000
     cfg = SyntheticConfig(n, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.05, n_cv=10, seed=6, with_mutation=False)
     ctx = gpu_lib.create(1, 1, 1)
@@ -252,14 +307,104 @@ def test_blocks_and_bands_wide_enough_for_the_large_tiles(gpu_lib):
     sim.ras_initial_human_gen0(0, n)
     sim.next_generation_rm(0, n)
     bits = unpacked(ctx, 0, 0)
-    for i0, ni in ((0, n), (3, 33)):
-        check_block(ctx, 0, 0, bits, 0, 2100, 0, bits, 2500, 2100, i0, ni, "2100 x 2100 SNPs")
-    check_block(ctx, 0, 0, bits, 2800, 2200, 0, bits, 1, 2049, 3, 33, "2200 x 2049 SNPs")
+    with tile_mode(ctx, 0) as t:
+        for i0, ni in ((0, n), (3, 33)):
+            check_block(ctx, 0, 0, bits, 0, 2100, 0, bits, 2500, 2100, i0, ni, "2100 x 2100 SNPs")
+            assert t.launched() == (0, 2), "17 x 17 large tiles are more than the compute units: n11 and gg on the large tiles, and nothing else"
+        check_block(ctx, 0, 0, bits, 2800, 2200, 0, bits, 1, 2049, 3, 33, "2200 x 2049 SNPs")
+        assert t.launched() == (0, 2)
+    with tile_mode(ctx, 1) as t:
+        check_block(ctx, 0, 0, bits, 0, 2100, 0, bits, 2500, 2100, 3, 33, "2100 x 2100 SNPs, small tiles")
+        assert t.launched() == (2, 0)
     truth = LDTruth(bits, 0, L, 3, 33)
-    lo, hi = ld.windows_by_count(L, 0, 4096, 1500)
+    with tile_mode(ctx, 0) as t:
+        # sub-blocks of 4096 SNPs a side, each matrix and vector against its slice of the truth
+        got = list(ctx.ld_counts(0, 0, 0, 4200, 0, 700, 4300, 3, 33))
+        assert t.launched() == (6, 2), "n11 and gg: one sub-block of 32 x 32 large tiles, three remainders on small ones"
+        for k, (name, w) in enumerate(zip(NAMES, truth.block(0, 4200, 700, 4300))):
+            assert got[k].dtype == np.uint32 and got[k].shape == w.shape, name
+            assert np.array_equal(got[k], w), f"4200 x 4300 SNPs: {name} differs at {np.argwhere(got[k] != w)[:5].tolist()}"
+            got[k] = None
+        lo, hi = ld.windows_by_count(L, 0, 4096, 1500)
+        for genotype in (False, True):
+            check_scores(ctx, 0, 0, truth, 0, 4096, lo, hi, 3, 33, genotype, "w = 1500")
+            small, large = t.launched()
+            assert small == 1 and large == 1, "the band of the first sub-block on large tiles, of the second on small ones"
+            assert truth.meaningful(0, lo, hi, genotype)
+        # two block rows of SNPs
+        lo, hi = ld.windows_by_count(L, 0, L, 1500)
+        for genotype in (False, True):
+            check_scores(ctx, 0, 0, truth, 0, L, lo, hi, 3, 33, genotype, "w = 1500, all 5000 SNPs")
+            small, large = t.launched()
+            assert small + large == 3 and small >= 1 and large >= 1, (small, large)
+    ctx.close()
+
+
+# ---- counts so large that every operation of the quantum rounds -----------------------------------------------------------------------------
+def test_quanta_whose_products_round(gpu_lib):
+    """32 000 individuals x 96 SNPs in strong LD (structured_rows), generation 0, individuals (0, 32000) and (3, 31965), both kinds of
+    r^2, w = 20 and the whole chromosome, tiles by compute units (64 x 64 here) and 128 x 128 forced, so that both score epilogues
+    round.  In every other device test n_ind <= 4100, so |num| and the denominators stay below 2^24.1, num^2 and den_j den_k are exact
+    doubles and only the quotient rounds; here the largest num^2 is near 2^60.  Asserted on the downloaded rows: of the in-window terms
+    with a quantum strictly between 0 and 2^40, num^2 is no double in at least 0.10 and den_j den_k in at least 0.10.  Measured:
+    num^2 0.32 - 0.44, den_j den_k 0.78 - 0.85 (generation 0 keeps the founders' rows, so these are the shares of test_ld_cpu.py's
+    host test).  Products or a quotient formed in less than a double, or a score summed in another type, differ here; another order
+    of the same double operations shows in about one term in 10^5 and takes the million terms of the test below.  (double)num and
+    (double)den stay exact below 2^27 haplotypes: those conversions are pinned on the host alone (test_ld_cpu.test_quantum_alone)"""
+    n, L = 32000, 96
+    cfg = SyntheticConfig(n, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.05, n_cv=10, seed=6, with_mutation=False)
+    ctx = gpu_lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    ctx.upload_founders(0, 0, capi.pack_rows(structured_rows(np.random.RandomState(31), n, L)), L)
+    ctx.synth_cv_founders(0, 0, 0, 2 * n, 9)
+    ctx.init_gen0(0, n, 81)
+    bits = unpacked(ctx, 0, 0)
+    for i0, ni in ((0, n), (3, 31965)):
+        truth = LDTruth(bits, 0, L, i0, ni)
+        windows = [ld.windows_by_count(L, 0, L, w) for w in (20, L)]
+        for genotype in (False, True):
+            for lo, hi in windows:
+                nn, dd = rounding_shares(truth, 0, lo, hi, genotype)
+                print(f"individuals [{i0},+{ni}) genotype {genotype} windows of {int((hi - lo).max())}: num^2 rounds in {nn:.3f} of the terms, den_j den_k in {dd:.3f}")
+                assert truth.meaningful(0, lo, hi, genotype)
+                assert nn >= 0.10 and dd >= 0.10, (i0, ni, genotype, nn, dd)
+        for mode in (0, 2):
+            with tile_mode(ctx, mode) as t:
+                got = ctx.ld_counts(0, 0, 0, L, 0, 0, L, i0, ni)
+                for name, g, w in zip(NAMES, got, truth.counts):
+                    assert np.array_equal(g, w), f"individuals [{i0},+{ni}) tile mode {mode}: {name} differs at {np.argwhere(g != w)[:5].tolist()}"
+                for genotype in (False, True):
+                    for lo, hi in windows:
+                        check_scores(ctx, 0, 0, truth, 0, L, lo, hi, i0, ni, genotype, f"tile mode {mode}")
+                assert t.launched() == ((0, 6) if mode == 2 else (6, 0))
+    ctx.close()
+
+
+def test_quanta_that_tell_the_order_of_the_operations(gpu_lib):
+    """The same founders with 1024 SNPs, individuals (3, 31965), the whole chromosome as every SNP's window: a million terms a kind.
+    A quantum keeps 40 bits behind the point of an r^2 of 53, so r^2 formed as (x / dj) * (x / dk) shows in about one term in 10^5
+    once the products round, and in none of the 36 864 terms of the test above (counted in numpy).  Here it does: asserted of the
+    input, the reassociated form moves at least 3 scores of either kind (measured: 12 of haplotype r^2, 6 of genotype r^2), so equal
+    scores say that the device forms the quotient of the two rounded products.  Tiles by compute units and 128 x 128 forced"""
+    n, L, i0, ni = 32000, 1024, 3, 31965
+    cfg = SyntheticConfig(n, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.05, n_cv=10, seed=6, with_mutation=False)
+    ctx = gpu_lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    ctx.upload_founders(0, 0, capi.pack_rows(structured_rows(np.random.RandomState(31), n, L)), L)
+    ctx.synth_cv_founders(0, 0, 0, 2 * n, 9)
+    ctx.init_gen0(0, n, 81)
+    truth = LDTruth(unpacked(ctx, 0, 0), 0, L, i0, ni)
+    lo, hi = ld.windows_by_count(L, 0, L, L)
     for genotype in (False, True):
-        check_scores(ctx, 0, 0, truth, 0, 4096, lo, hi, 3, 33, genotype, "w = 1500")
-        assert truth.meaningful(0, lo, hi, genotype)
+        want = truth.scores(0, lo, hi, genotype)
+        other = truth.scores(0, lo, hi, genotype, q=truth.quanta(genotype, numpy_q40_reassociated))
+        moved = int((other[0] != want[0]).sum())
+        print(f"genotype {genotype}: (x / dj) * (x / dk) moves {moved} of {L} scores")
+        assert moved >= 3 and np.array_equal(other[1], want[1])
+        for mode in (0, 2):
+            with tile_mode(ctx, mode) as t:
+                check_scores(ctx, 0, 0, truth, 0, L, lo, hi, i0, ni, genotype, f"tile mode {mode}")
+                assert t.launched() == ((0, 1) if mode == 2 else (1, 0))
     ctx.close()
 
 

@@ -11,7 +11,7 @@ import pytest
 from geneevolve_amd import capi, relatedness
 from geneevolve_amd.host import Simulation, SyntheticConfig
 from tests import helpers
-from tests.pair_counts_inputs import PairTruth
+from tests.pair_counts_inputs import PairTruth, numpy_pair_counts, tile_mode
 from tests.snp_counts_inputs import random_rows
 from tests.test_gpu_snp_counts import overlay_situations, unpacked
 
@@ -73,16 +73,26 @@ def awkward(request, gpu_lib):
     ctx.close()
 
 
-def test_rectangular_blocks(awkward):
+def rectangular_blocks(awkward, what):
     ctx, n, L, snps, truths = awkward
     for s0, ns in snps:
         for na, nb, a0, b0 in BLOCKS:
-            check_block(ctx, 0, 0, truths[(s0, ns)], s0, ns, a0, na, b0, nb, "awkward shapes")
+            check_block(ctx, 0, 0, truths[(s0, ns)], s0, ns, a0, na, b0, nb, what)
 
 
-def test_whole_matrix_and_its_diagonal(awkward):
-    """333 x 333: three tiles a side, the last one partly filled.  The diagonal of a self block is the per-individual counts:
-    n_hethet = n_het, n_opphom = 0, dot = n_het + 4 n_hom_alt"""
+def test_rectangular_blocks(awkward):
+    rectangular_blocks(awkward, "awkward shapes")
+
+
+def test_rectangular_blocks_on_the_large_tiles(awkward):
+    """the same blocks and SNP ranges with the 128 x 128 instantiation forced (gev_dbg_bitprod_tiles(2)), which the compute-unit rule
+    gives no block below about 2000 a side: one partly filled tile, down to one pair in it"""
+    with tile_mode(awkward[0], 2) as t:
+        rectangular_blocks(awkward, "awkward shapes, large tiles")
+        assert t.launched() == (0, len(awkward[3]) * len(BLOCKS))
+
+
+def whole_matrix_and_its_diagonal(awkward):
     ctx, n, L, snps, truths = awkward
     for s0, ns in ((0, L), (63, 4097 - 63)):
         t = truths[(s0, ns)]
@@ -93,8 +103,20 @@ def test_whole_matrix_and_its_diagonal(awkward):
     check_ind(ctx, 0, 0, truths[(31, 2)], 31, 2, 17, 300, "a range of individuals")
 
 
-def test_output_chunk_makes_no_difference(awkward):
-    """gev_dbg_output_chunk(7): sub-blocks of 7 x 7 pairs, each staged, multiplied and copied out on its own"""
+def test_whole_matrix_and_its_diagonal(awkward):
+    """333 x 333: three tiles a side, the last one partly filled.  The diagonal of a self block is the per-individual counts:
+    n_hethet = n_het, n_opphom = 0, dot = n_het + 4 n_hom_alt"""
+    whole_matrix_and_its_diagonal(awkward)
+
+
+def test_whole_matrix_and_its_diagonal_on_the_large_tiles(awkward):
+    """333 x 333 on tiles of 128 x 128: three tiles a side, the last one filled to 77"""
+    with tile_mode(awkward[0], 2) as t:
+        whole_matrix_and_its_diagonal(awkward)
+        assert t.launched() == (0, 2)
+
+
+def output_chunk_makes_no_difference(awkward):
     ctx, n, L, snps, truths = awkward
     ctx.dbg_output_chunk(7)
     try:
@@ -105,6 +127,18 @@ def test_output_chunk_makes_no_difference(awkward):
         check_block(ctx, 0, 0, truths[(0, L)], 0, L, 0, n, 0, n, "output chunk 7, whole matrix")
     finally:
         ctx.dbg_output_chunk(0)
+
+
+def test_output_chunk_makes_no_difference(awkward):
+    """gev_dbg_output_chunk(7): sub-blocks of 7 x 7 pairs, each staged, multiplied and copied out on its own"""
+    output_chunk_makes_no_difference(awkward)
+
+
+def test_output_chunk_makes_no_difference_on_the_large_tiles(awkward):
+    """... each of them 7 x 7 pairs in the corner of one tile of 128 x 128"""
+    with tile_mode(awkward[0], 2) as t:
+        output_chunk_makes_no_difference(awkward)
+        assert t.large_only()
 
 
 def test_each_output_may_be_null_and_empty_requests(awkward):
@@ -153,12 +187,31 @@ def test_weighted_sums_need_64_bits(awkward):
         ctx.dbg_output_chunk(0)
 
 
+def check_block_by_matrix(ctx, bits, s0, ns, a0, na, b0, nb, what):
+    """a block of thousands a side: one matrix of the truth at a time (products in float64: exact while 4 n_snps < 2^53), each dropped
+    with its result once compared -> the largest entry of each matrix"""
+    got = list(ctx.pair_genotype_counts(0, 0, s0, ns, a0, na, b0, nb))
+    label = f"{what}: SNPs [{s0},{s0 + ns}) a [{a0},+{na}) b [{b0},+{nb})"
+    largest = []
+    for o, name in enumerate(("n_hethet", "n_opphom", "dot")):
+        want = numpy_pair_counts(bits, s0, ns, a0, na, b0, nb, products=np.float64, only=o)
+        assert got[o].dtype == np.uint32 and got[o].shape == (na, nb), label
+        assert np.array_equal(got[o], want), f"{label}: {name} differs at {np.argwhere(got[o] != want)[:5].tolist()}"
+        largest.append(int(got[o].max()))
+        got[o] = want = None
+    return largest
+
+
 def test_blocks_wide_enough_for_the_large_tiles(gpu_lib):
     """The product takes tiles of 128 x 128 pairs where they give every compute unit work, of 64 x 64 otherwise; with the 256 compute
     units of an MI355X a block of 2100 x 2100 individuals (17 x 17 large tiles, the last one partly filled on both sides) and one of
-    2200 x 2049 (18 x 17) take the large ones; the blocks before this took the small ones.  2300 individuals x 200 SNPs, founders with
-    every allele frequency from 0 to 1; every sum is at most 800, so the truth's products are exact in float64"""
-    n, L = 2300, 200
+    2200 x 2049 (18 x 17) launch on the large ones alone, which the launch counters of gev_dbg_bitprod_tiles assert; the 2100 x 2100
+    block once more with the small tiles forced is a grid of 33 x 33 of them.  Then the walk at its real side, byte budgets alone:
+    individuals (3, 4197) x (0, 4200) are one sub-block of 4096 x 4096 (32 x 32 large tiles) and, in the same call, the ragged
+    remainders 4096 x 104, 101 x 4096 and 101 x 104 on 32, 32 and 1 small tiles, copied out at a pitch of 4200 with the count vectors
+    of side B at offset 4096.  4200 individuals x 200 SNPs, founders with every allele frequency from 0 to 1; every sum is at most
+    800, so the truth's products are exact in float64"""
+    n, L = 4200, 200
     cfg = SyntheticConfig(n, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.05, n_cv=10, seed=6, with_mutation=False)
     ctx = gpu_lib.create(1, 1, 1)
     cfg.apply_static(ctx)
@@ -168,9 +221,82 @@ def test_blocks_wide_enough_for_the_large_tiles(gpu_lib):
     sim.ras_initial_human_gen0(0, n)
     sim.next_generation_rm(0, n)
     bits = unpacked(ctx, 0, 0)
-    hethet, opphom, dot = check_block(ctx, 0, 0, PairTruth(bits, products=np.float64), 0, L, 0, 2100, 150, 2100, "2100 x 2100 individuals")
-    assert hethet.any() and opphom.any() and int(dot.max()) > 255
-    check_block(ctx, 0, 0, PairTruth(bits, 1, 130, products=np.float64), 1, 130, 3, 2200, 1, 2049, "2200 x 2049 individuals")
+    with tile_mode(ctx, 0) as t:
+        hethet, opphom, dot = check_block_by_matrix(ctx, bits, 0, L, 0, 2100, 150, 2100, "2100 x 2100 individuals")
+        assert hethet > 0 and opphom > 0 and dot > 255
+        assert t.launched() == (0, 1), "17 x 17 large tiles are more than the compute units: the large tiles, and nothing else"
+        check_block_by_matrix(ctx, bits, 1, 130, 3, 2200, 1, 2049, "2200 x 2049 individuals")
+        assert t.launched() == (0, 1)
+        check_block_by_matrix(ctx, bits, 1, 130, 3, 4197, 0, 4200, "4197 x 4200 individuals, sub-blocks of 4096")
+        assert t.launched() == (3, 1), "one sub-block of 32 x 32 large tiles, three remainders on small ones"
+    with tile_mode(ctx, 1) as t:
+        check_block_by_matrix(ctx, bits, 0, L, 0, 2100, 150, 2100, "2100 x 2100 individuals, small tiles")
+        assert t.launched() == (1, 0)
+    ctx.close()
+
+
+def test_sums_beyond_16_bits(gpu_lib):
+    """64 individuals x 300 000 SNPs of allele frequency 0.5 at distinct positions, generation 0: the counts of a pair are near 75 000
+    (both heterozygous) and 300 000 (dot), where no other pair test has a sum above 20 000 -- an accumulator or an output narrower than
+    32 bits, or a count added in 16-bit halves, cannot pass.  Counts add over SNP ranges: the truth is summed over chunks of 50 000
+    (products in float64: a chunk's sums are at most 200 000, exact)"""
+    n, L = 64, 300_000
+    cfg = SyntheticConfig(n, L, chrom_bp=3_000_000, map_step=20_000, rec_per_row=0.05, n_cv=10, seed=6, with_mutation=False)
+    assert len(set(cfg.snp_pos.tolist())) == L
+    ctx = gpu_lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    ctx.upload_founders(0, 0, capi.pack_rows(np.random.RandomState(24).randint(0, 2, size=(2 * n, L)).astype(np.uint8)), L)
+    ctx.synth_cv_founders(0, 0, 0, 2 * n, 9)
+    ctx.init_gen0(0, n, 80)
+    bits = unpacked(ctx, 0, 0)
+    want = [sum(m) for m in zip(*(numpy_pair_counts(bits, s0, min(50_000, L - s0), products=np.float64) for s0 in range(0, L, 50_000)))]
+    got = ctx.pair_genotype_counts(0, 0)
+    for name, g, w in zip(("n_hethet", "n_opphom", "dot"), got, want):
+        assert g.dtype == np.uint32 and np.array_equal(g, w), f"{name} differs at {np.argwhere(g != w)[:5].tolist()}"
+    assert int(got[0].max()) > 65535 and int(got[2].max()) > 65535 and int(np.min(got[2])) > 65535
+    het, hom = ctx.ind_genotype_counts(0, 0)
+    assert np.array_equal(het, np.diag(got[0])) and np.array_equal(het + 4 * hom, np.diag(got[2])) and int(het.min()) > 65535
+    # a range that begins and ends inside a word
+    s0, ns = 33, L - 70
+    want = [sum(m) for m in zip(*(numpy_pair_counts(bits, a, min(50_000, s0 + ns - a), 1, 33, 0, n, products=np.float64) for a in range(s0, s0 + ns, 50_000)))]
+    for name, g, w in zip(("n_hethet", "n_opphom", "dot"), ctx.pair_genotype_counts(0, 0, s0, ns, 1, 33, 0, n), want):
+        assert np.array_equal(g, w), f"SNPs [{s0},+{ns}): {name} differs at {np.argwhere(g != w)[:5].tolist()}"
+    ctx.close()
+
+
+def test_the_tile_mode_hook(gpu_lib):
+    """gev_dbg_bitprod_tiles: modes 0, 1, 2 and -1 (unchanged), GEV_EINVAL for any other, counters from the context's creation on,
+    refused while a generation is pending"""
+    n, L = 50, 300
+    cfg = SyntheticConfig(n, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=1e-3, n_cv=10, seed=2, with_mutation=False)
+    ctx = gpu_lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    ctx.synth_founders(0, 0, 2 * n, 50); ctx.synth_cv_founders(0, 0, 0, 2 * n, 60)
+    sim = Simulation(ctx, 5, 1, True)
+    sim.ras_initial_human_gen0(0, n)
+    t = PairTruth(unpacked(ctx, 0, 0))
+    assert ctx.dbg_bitprod_tiles() == (0, 0)
+    ctx.L._f("dbg_bitprod_tiles")(ctx.h, capi.C.c_int(-1), None)                # the counters may be left out
+    check_block(ctx, 0, 0, t, 0, L, 0, n, 0, n, "tiles by compute units")
+    assert ctx.dbg_bitprod_tiles() == (1, 0), "one tile: fewer than the compute units"
+    assert ctx.dbg_bitprod_tiles(2) == (1, 0)
+    check_block(ctx, 0, 0, t, 0, L, 0, n, 0, n, "large tiles")
+    assert ctx.dbg_bitprod_tiles(-1) == (1, 1)
+    check_block(ctx, 0, 0, t, 0, L, 0, n, 0, n, "large tiles still")
+    for mode in (3, -2, 128):
+        with pytest.raises(capi.GevError) as e:
+            ctx.dbg_bitprod_tiles(mode)
+        assert e.value.code == -1 and "mode" in str(e.value)
+    check_block(ctx, 0, 0, t, 0, L, 0, n, 0, n, "large tiles after a refusal")
+    assert ctx.dbg_bitprod_tiles(1) == (1, 3)
+    check_block(ctx, 0, 0, t, 0, L, 0, n, 0, n, "small tiles")
+    assert ctx.dbg_bitprod_tiles(0) == (2, 3)
+    ctx.generation_begin(0, sim.glob.x, n)
+    with pytest.raises(capi.GevError) as e:
+        ctx.dbg_bitprod_tiles(2)
+    assert e.value.code == -2 and "pending" in str(e.value)
+    ctx.generation_end()
+    assert ctx.dbg_bitprod_tiles() == (2, 3)
     ctx.close()
 
 

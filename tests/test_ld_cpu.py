@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from geneevolve_amd import capi, ld
-from tests.ld_inputs import LDTruth, numpy_ld_counts, numpy_q40
+from tests.ld_inputs import LDTruth, numpy_ld_counts, numpy_q40, numpy_q40_reassociated, rounding_shares, structured_rows
 from tests.snp_counts_inputs import random_rows
 from tests.test_snp_counts_cpu import padded
 
@@ -124,6 +124,23 @@ def test_quantum_alone(gpu_lib):
             assert abs(int(got[i]) - exact) <= 0.5 + exact * 2.0 ** -50
 
 
+def test_quantum_on_millions_of_triples_that_round(gpu_lib):
+    """4 000 000 random triples with both denominators in [2^26, 2^31) and num^2 <= den_j den_k: the counts of tens of thousands of
+    individuals, where num^2 and den_j den_k are no doubles.  A quantum keeps 40 bits behind the point of an r^2 of 53, so another
+    order of the same operations shows in about one triple in 10^5 only: the few thousand triples above (and the 10^4 terms of a
+    small score test) cannot tell r^2 = (x / dj) * (x / dk) from (x * x) / (dj * dk); these can, which is asserted of the input (the
+    reassociated form differs in 122 of them)"""
+    rs = np.random.RandomState(8)
+    m = 4_000_000
+    den_j = rs.randint(1 << 26, 1 << 31, size=m, dtype=np.int64).astype(np.uint64); den_k = rs.randint(1 << 26, 1 << 31, size=m, dtype=np.int64).astype(np.uint64)
+    lim = np.floor(np.sqrt(den_j.astype(np.float64)) * np.sqrt(den_k.astype(np.float64)) * (1 - 2.0 ** -40)).astype(np.int64)
+    num = (lim * rs.uniform(-1, 1, size=m)).astype(np.int64)
+    want = numpy_q40(num, den_j, den_k)
+    assert int(want.max()) <= 1 << 40 and int((numpy_q40_reassociated(num, den_j, den_k) != want).sum()) >= 10, "triples that tell the order of the operations"
+    got = gpu_lib.dbg_ld_r2_q40_host(num, den_j, den_k)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:5]
+
+
 @pytest.mark.parametrize("genotype", [False, True], ids=["haplotype r2", "genotype r2"])
 def test_host_ld_scores_equal_numpy(gpu_lib, population, genotype):
     bits, tight, wide, bits_b, wide_b = population
@@ -145,6 +162,28 @@ def test_host_ld_scores_equal_numpy(gpu_lib, population, genotype):
                     assert truth.meaningful(s0, lo, hi, genotype)
                 if k == 3:      # the whole chromosome
                     assert (lo == 0).all() and (hi == L).all() and (terms == poly.sum()).all()
+
+
+def test_host_ld_scores_where_the_products_round(gpu_lib):
+    """32 000 individuals x 96 SNPs in strong LD (structured_rows), individuals (3, 31965), w = 20: the input of
+    test_gpu_ld.test_quanta_whose_products_round.  With the 70 people above |num| and the denominators stay below 2^13, so num^2 and
+    den_j den_k are exact and only the quotient rounds; here the largest num^2 is near 2^60 and both products round in a large share of
+    the terms, so that the host mirror and numpy have to agree on four roundings.  Shares of the in-window terms with a quantum strictly
+    between 0 and 2^40, measured: num^2 no double 0.39 (haplotype r^2) and 0.44 (genotype r^2), den_j den_k no double 0.79 and 0.84"""
+    n, Ls, i0, ni = 32000, 96, 3, 31965
+    bits = structured_rows(np.random.RandomState(31), n, Ls)
+    rows = capi.pack_rows(bits)
+    truth = LDTruth(bits, 0, Ls, i0, ni)
+    lo, hi = ld.windows_by_count(Ls, 0, Ls, 20)
+    for genotype in (False, True):
+        nn, dd = rounding_shares(truth, 0, lo, hi, genotype)
+        print(f"genotype {genotype}: num^2 rounds in {nn:.3f} of the terms, den_j den_k in {dd:.3f}")
+        assert truth.meaningful(0, lo, hi, genotype)
+        assert nn >= 0.10 and dd >= 0.10, (genotype, nn, dd)
+        score, terms = gpu_lib.dbg_ld_host(rows, Ls, 0, Ls, ind_begin=i0, n_ind=ni, win_lo=lo, win_hi=hi, genotype=genotype)
+        want = truth.scores(0, lo, hi, genotype)
+        assert np.array_equal(terms, want[1]), np.flatnonzero(terms != want[1])[:5]
+        assert np.array_equal(score, want[0]), np.flatnonzero(score != want[0])[:5]
 
 
 def test_windows(population):
