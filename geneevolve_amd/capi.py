@@ -652,7 +652,7 @@ class GevContext:
         return out, n
 
     def dbg_phenotype_knobs(self, short_candidates=False):
-        """-> phenotype steps run again so far; short_candidates: start the following steps' normal streams far too short"""
+        """-> phenotype steps and scale_ad_compute_gef() calls run again so far; short_candidates: start their normal streams far too short"""
         n = C.c_ulonglong()
         self._call_new("dbg_phenotype_knobs", C.c_int(int(bool(short_candidates))), C.byref(n))
         return int(n.value)

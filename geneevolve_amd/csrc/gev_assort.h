@@ -1,6 +1,6 @@
 // gev_assort.h -- Simulation::assort_mate (reference src/Simulation.cpp:2167-2360) on the device (gfx950, wave64).  Included by
-// gev_kernels.h after gev_mate.h.  The host mirror geneevolve_amd/host.py:assort_mate is the specification; every stream below is
-// reproduced bit for bit (DESIGN.md "Assortative mating on the device" has the exactness arguments).
+// gev_kernels.h after gev_mate.h and gev_normal.h.  The host mirror geneevolve_amd/host.py:assort_mate is the specification; every
+// stream below is reproduced bit for bit (DESIGN.md "Assortative mating on the device" has the exactness arguments).
 //
 //   :2184-2216  marriage draws      k_am_chunk_stats / k_am_windows / k_am_walk / k_am_chain / k_am_flags / k_am_compact
 //   :2232-2246  surplus removal     k_glibc_stream + k_shuf_count / k_shuf_fill / k_shuf_trace (std::random_shuffle on rand())
@@ -196,63 +196,23 @@ __global__ void __launch_bounds__(256) k_gather_u32(const u32* __restrict__ in, 
     if (i < n) out[i] = in[idx[i]];
 }
 
-// ---- ras_mvnorm (:2268, RasRandomNumber.cpp:15-51): Marsaglia polar pairs on default_random_engine(seed2); candidate pair m uses
-// draws 2m, 2m+1 (engine outputs 4m+1..4m+4); row i of z = the i-th accepted pair (y*mult, x*mult); t1 / t2 = z * chol without FMA
-#define TPL_PER_THREAD 8
-#define TPL_CHUNK (256 * TPL_PER_THREAD)
-__device__ __forceinline__ bool tpl_candidate(u32& x, double& xx, double& yy, double& r2)
-{
-    const u32 x1 = mulmod31(x, 16807u), x2 = mulmod31(x1, 16807u), x3 = mulmod31(x2, 16807u), x4 = mulmod31(x3, 16807u);
-    x = x4;
-    xx = __dadd_rn(__dmul_rn(2.0, canonical_f64(x1, x2)), -1.0);
-    yy = __dadd_rn(__dmul_rn(2.0, canonical_f64(x3, x4)), -1.0);
-    r2 = __dadd_rn(__dmul_rn(xx, xx), __dmul_rn(yy, yy));
-    return !(r2 > 1.0 || r2 == 0.0);
-}
+// ---- ras_mvnorm (:2268, RasRandomNumber.cpp:15-51): Marsaglia polar pairs on default_random_engine(seed2), drawn by the skeleton
+// of gev_normal.h; row i of z = the i-th accepted pair (y*mult, x*mult); t1 / t2 = z * chol without FMA
 __global__ void __launch_bounds__(256) k_tpl_count(u32 x0, u64 n_cand, u32* __restrict__ blk)
 {
     __shared__ u32 lds[8];
-    const u64 m0 = (u64)blockIdx.x * TPL_CHUNK + (u64)threadIdx.x * TPL_PER_THREAD;
-    u32 cnt = 0;
-    if (m0 < n_cand) {
-        u32 x = mulmod31(powmod31(16807u, 4 * m0), x0);
-        for (int q = 0; q < TPL_PER_THREAD && m0 + q < n_cand; q++) { double a, b, r; cnt += tpl_candidate(x, a, b, r) ? 1u : 0u; }
-    }
-    const u32 tot = block_sum_256(cnt, lds);
-    if (threadIdx.x == 0) blk[blockIdx.x] = tot;
+    polar_count_block(x0, n_cand, blk, lds);
 }
 __global__ void __launch_bounds__(256) k_tpl_emit(u32 x0, u64 n_cand, u64 n2, const u32* __restrict__ blk, double u01, double u11,
                                                   double* __restrict__ t1, double* __restrict__ t2, u32* __restrict__ stat)
 {
     __shared__ u32 lds[8];
-    u32 part = 0;
-    for (u32 b = threadIdx.x; b < blockIdx.x; b += 256) part += blk[b];
-    const u32 before_blocks = block_sum_256(part, lds);
-    const u64 m0 = (u64)blockIdx.x * TPL_CHUNK + (u64)threadIdx.x * TPL_PER_THREAD;
-    u32 acc = 0;
-    u32 x = 0;
-    if (m0 < n_cand) {
-        x = mulmod31(powmod31(16807u, 4 * m0), x0);
-        u32 y = x;
-        for (int q = 0; q < TPL_PER_THREAD && m0 + q < n_cand; q++) { double a, b, r; acc |= (tpl_candidate(y, a, b, r) ? 1u : 0u) << q; }
-    }
-    u32 tot;
-    const u32 before = before_blocks + block_exclusive_scan_256((u32)__popc(acc), lds, tot);
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255 && (u64)before + __popc(acc) < n2) atomicOr(stat + AMS_FLAGS, (u32)AMF_TPL_SHORT);
-    if (m0 >= n_cand) return;
-    u32 k = before;
-    for (int q = 0; q < TPL_PER_THREAD && m0 + q < n_cand; q++) {
-        double xx, yy, r2;
-        const bool ok = tpl_candidate(x, xx, yy, r2);
-        if (!ok) continue;
-        if (k < n2) {
-            const double mult = sqrt(-2 * log(r2) / r2);
-            const double z0 = __dmul_rn(yy, mult), z1 = __dmul_rn(xx, mult);
-            t1[k] = __dadd_rn(__dadd_rn(0.0, __dmul_rn(z0, 1.0)), __dmul_rn(z1, 0.0));
-            t2[k] = __dadd_rn(__dadd_rn(0.0, __dmul_rn(z0, u01)), __dmul_rn(z1, u11));
-        }
-        k++;
-    }
+    polar_emit_block(x0, n_cand, n2, gridDim.x, blk, lds, stat + AMS_FLAGS, (u32)AMF_TPL_SHORT, [&](u64 k, double xx, double yy, double r2, u32) {
+        const double mult = polar_mult(r2);
+        const double z0 = __dmul_rn(yy, mult), z1 = __dmul_rn(xx, mult);
+        t1[k] = __dadd_rn(__dadd_rn(0.0, __dmul_rn(z0, 1.0)), __dmul_rn(z1, 0.0));
+        t2[k] = __dadd_rn(__dadd_rn(0.0, __dmul_rn(z0, u01)), __dmul_rn(z1, u11));
+    });
 }
 
 // ---- couples (:2286-2326): couple i = (males sorted by mv at rank_t1[i], females sorted at rank_t2[i]); position p of the stable sort

@@ -1753,11 +1753,8 @@ __global__ void k_csr_gather_fill(const u32* __restrict__ s_off, const E* __rest
 
 // ------------------------------------------------------------------------------------------
 // Simulation::ras_scale_AD_compute_GEF (src/Simulation.cpp:3075-3206)
-// std::normal_distribution<double> on minstd_rand0 = Marsaglia polar method with rejection
-// (libstdc++ bits/random.tcc:1802-1835): candidate pair j consumes engine outputs 4j+1..4j+4, the
-// k-th ACCEPTED pair yields normals 2k (= y*mult) and 2k+1 (= x*mult).  Candidates are evaluated in
-// parallel (LCG jump-ahead) and compacted with a scan.  u = generate_canonical is computed in FP64
-// exactly as libstdc++ does (no contraction); log() is the device libm (<= 1 ulp from glibc's).
+// The normal streams are drawn by k_nrm_count / k_nrm_emit and var(e) is formed by k_ph_var_* (gev_normal.h).
+// u = generate_canonical is computed in FP64 exactly as libstdc++ does (no contraction).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double canonical_f64(u32 x1, u32 x2)
 {
@@ -1768,61 +1765,33 @@ __device__ __forceinline__ double canonical_f64(u32 x1, u32 x2)
     if (ret >= 1.0) ret = 0x1.fffffffffffffp-1;       // nextafter(1, 0)
     return ret;
 }
-__global__ void __launch_bounds__(256) k_polar_candidates(u32 engine_seed, size_t n_cand, u32* __restrict__ flag, double* __restrict__ first, double* __restrict__ second)
+// :3174-3203 for one individual of one phenotype: raw a / d over s_a / s_d, raw e over s_ev = sqrt(var(e) / ve), and their sum with
+// the family effect cs and the parental effect pe.  The one place this arithmetic is written: k_gef_apply and k_ph_apply call it
+struct GefValues { double a, d, g, e, p; };
+__device__ __forceinline__ GefValues gef_scale(double a_raw, double d_raw, double s_a, double s_d, double e_raw, double var_e, double ve, double cs, double pe)
 {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_cand) return;
-    u32 x = mulmod31(powmod31(16807u, 4 * j + 1), minstd_seed(engine_seed));
-    const u32 x1 = x; x = mulmod31(x, 16807u); const u32 x2 = x; x = mulmod31(x, 16807u); const u32 x3 = x; x = mulmod31(x, 16807u); const u32 x4 = x;
-    const double xx = 2.0 * canonical_f64(x1, x2) - 1.0;
-    const double yy = 2.0 * canonical_f64(x3, x4) - 1.0;
-    const double r2 = xx * xx + yy * yy;
-    const bool ok = !(r2 > 1.0 || r2 == 0.0);
-    flag[j] = ok ? 1u : 0u;
-    if (ok) { const double mult = sqrt(-2 * log(r2) / r2); first[j] = yy * mult; second[j] = xx * mult; }
+    const double s_ev = ve > 0 ? sqrt(var_e / ve) : 0;
+    GefValues o;
+    o.e = s_ev > 0 ? e_raw / s_ev : 0;
+    o.a = a_raw / s_a;
+    o.d = s_d > 0 ? d_raw / s_d : 0;
+    o.g = o.a + o.d;
+    o.p = o.a + o.d + cs + o.e + pe;
+    return o;
 }
-__global__ void __launch_bounds__(256) k_polar_emit(const u32* __restrict__ flag, const u32* __restrict__ off, const double* __restrict__ first, const double* __restrict__ second,
-                                                    size_t n_cand, size_t n, double sd, double* __restrict__ out)
-{
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_cand || !flag[j]) return;
-    const size_t k = off[j];
-    if (2 * k < n) out[2 * k] = first[j] * sd + 0.0;          // ret * stddev + mean
-    if (2 * k + 1 < n) out[2 * k + 1] = second[j] * sd + 0.0;
-}
-// deterministic two-level sum of (x[i]-shift)^pw, pw in {1,2}
-__global__ void __launch_bounds__(256) k_sum_partial(const double* __restrict__ x, size_t n, double shift, int pw, double* __restrict__ partial)
-{
-    __shared__ double s[256];
-    double acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const double v = x[i] - shift; acc += pw == 2 ? v * v : v; }
-    s[threadIdx.x] = acc; __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
-}
-__global__ void __launch_bounds__(256) k_sum_final(const double* __restrict__ partial, int nb, double* __restrict__ out)
-{
-    __shared__ double s[256];
-    s[threadIdx.x] = (int)threadIdx.x < nb ? partial[threadIdx.x] : 0.0; __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) *out = s[0];
-}
-// :3174-3203; raw a, d strided by nphen
-__global__ void __launch_bounds__(256) k_gef_apply(const double* __restrict__ a, const double* __restrict__ d, size_t stride, const double* __restrict__ e, const double* __restrict__ par_eff,
-                                                   const double* __restrict__ common, size_t n, double s_a, double s_d, double s_ev, double vf,
+// raw a, d strided by nphen; e_stats = {mean, var} of e (k_ph_var_*)
+__global__ void __launch_bounds__(256) k_gef_apply(const double* __restrict__ a, const double* __restrict__ d, size_t stride, const double* __restrict__ e, const double* __restrict__ e_stats,
+                                                   const double* __restrict__ par_eff, const double* __restrict__ common, size_t n, double s_a, double s_d, double ve, double vf,
                                                    double* __restrict__ o_add, double* __restrict__ o_dom, double* __restrict__ o_bv, double* __restrict__ o_e, double* __restrict__ o_par, double* __restrict__ o_phen,
                                                    double* __restrict__ o_keep /* the population's phenotype column, strided by stride (gev_compute_selection) */)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double en = s_ev > 0 ? e[i] / s_ev : 0;
-    const double ad = a[i * stride] / s_a;
-    const double dm = s_d > 0 ? d[i * stride] / s_d : 0;
     const double pe = vf > 0 ? par_eff[i] : 0;
     const double cs = common ? common[i] : 0.0;
-    o_e[i] = en; o_add[i] = ad; o_dom[i] = dm; o_bv[i] = ad + dm; o_par[i] = pe;
-    const double ph = ad + dm + cs + en + pe;
-    o_phen[i] = ph; o_keep[i * stride] = ph;
+    const GefValues v = gef_scale(a[i * stride], d[i * stride], s_a, s_d, e[i], e_stats[1], ve, cs, pe);
+    o_e[i] = v.e; o_add[i] = v.a; o_dom[i] = v.d; o_bv[i] = v.g; o_par[i] = pe;
+    o_phen[i] = v.p; o_keep[i * stride] = v.p;
 }
 __global__ void __launch_bounds__(256) k_par_eff(const double* __restrict__ ff, const double* __restrict__ fm, size_t n, double beta, double* __restrict__ out)
 {
@@ -1954,4 +1923,5 @@ __global__ void __launch_bounds__(256) k_dbg_format_g(const GevFmtTables* __rest
 #define GEV_LISTS_KERNELS
 #include "gev_lists.h"
 #include "gev_mate.h"
+#include "gev_normal.h"
 #include "gev_assort.h"

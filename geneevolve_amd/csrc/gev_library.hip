@@ -309,7 +309,7 @@ struct gev_ctx {
     DevBuf d_pair_w, d_ld_win, d_ld_score;       // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
-    DevBuf d_gef_flag, d_gef_first, d_gef_red, d_gef_io;
+    DevBuf d_gef_io, d_gef_stat;                 // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
     // gev_assort_mate (gev_assort.h): scratch, the last call's result and couple arrays, test knobs
     struct AssortState {
         DevBuf stats, wlo, ww, ends, start, cm, cf, om, of, males, females, rnd, scnt, soff, sfill, stgt, ssrc, kept, sorted_m, sorted_f,
@@ -332,7 +332,8 @@ struct gev_ctx {
         DevBuf d_names, lens, bsum, boff, flag, ids;
         bool uploaded = false;
     } iv;
-    // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob
+    // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob.  streams / blk /
+    // partial are also the scratch of ph_streams / ph_var under gev_scale_ad_compute_gef and gev_compute_selection (one stream)
     struct PhenoState {
         DevBuf res /* result words, then {mean, var} pairs: e, the components, raw A and D */, starts, partial, eraw, cval, streams, tasks, blk, globblk, shift;
         PinnedBuf h_res;
@@ -2300,7 +2301,7 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     const double x11 = 1.0 - (cc / 1.0) * (cc / 1.0);          // Eigen's unblocked LLT leaves A(1,1) = 1 at a non-positive pivot
     const double u01 = cc / 1.0, u11 = x11 > 0 ? std::sqrt(x11) : 1.0;
     const u64 n_cand = (u64)n2 + (u64)n2 * 3 / 10 + 4096;          // acceptance pi/4: n2 pairs need 1.273 n2 candidates on average
-    const unsigned nbt = (unsigned)ceil_div((size_t)n_cand, TPL_CHUNK);
+    const unsigned nbt = (unsigned)ceil_div((size_t)n_cand, POLAR_CHUNK);
     GEVC(A.tblk.ensure(nbt * sizeof(u32), st)); GEVC(A.t1.ensure(n2 * sizeof(double), st)); GEVC(A.t2.ensure(n2 * sizeof(double), st));
     GEVC(A.i1.ensure(n2 * sizeof(u32), st)); GEVC(A.i2.ensure(n2 * sizeof(u32), st));
     GEVC(A.pm.ensure(n2 * sizeof(u32), st)); GEVC(A.pf.ensure(n2 * sizeof(u32), st)); GEVC(A.inb.ensure(n2 * sizeof(u32), st));
@@ -2818,37 +2819,42 @@ int gev_ad_finish_device(gev_ctx* c, int pop, double* additive, double* dominanc
     return GEV_OK;
 }
 // ---- Simulation::ras_scale_AD_compute_GEF ---------------------------------
-static int normal_stream(gev_ctx* c, u32 engine_seed, size_t n, double sd, double* d_out)
+// The normal streams and the mean / variance sums of this call, of gev_compute_selection and of gev_generation_phenotypes
+// (gev_normal.h).  Their scratch (c->ph.streams / blk / partial) is shared: every caller enqueues on c->stream.  The status words
+// (stream offsets, short flag) and the statistics belong to the caller.
+static size_t ph_candidates(const gev_ctx* c, size_t n, int shift)
 {
-    hipStream_t st = c->stream;
-    size_t n_cand = (size_t)((n / 2 + 1) / 0.7) + 4096;           // acceptance = pi/4
-    for (int attempt = 0; attempt < 4; attempt++, n_cand *= 2) {
-        GEVC(c->d_gef_flag.ensure((n_cand + 1) * sizeof(u32) * 2, st)); GEVC(c->d_gef_first.ensure(n_cand * sizeof(double) * 2, st));
-        u32* flag = c->d_gef_flag.as<u32>(); u32* off = flag + n_cand + 1;
-        double* first = c->d_gef_first.as<double>(); double* second = first + n_cand;
-        hipLaunchKernelGGL(k_polar_candidates, dim3((unsigned)ceil_div(n_cand, 256)), dim3(256), 0, st, engine_seed, n_cand, flag, first, second);
-        KCHECK();
-        u32 accepted = 0;
-        GEVC(scan_u32(c, flag, n_cand, off, &accepted));
-        if ((size_t)accepted * 2 < n) continue;                     // (practically never) not enough accepted pairs: more candidates
-        hipLaunchKernelGGL(k_polar_emit, dim3((unsigned)ceil_div(n_cand, 256)), dim3(256), 0, st, flag, off, first, second, n_cand, n, sd, d_out);
-        KCHECK();
-        return GEV_OK;
-    }
-    return fail(GEV_EDEVICE, "normal_stream: acceptance far below pi/4");
+    if (c->ph.short_candidates && shift == 0) return n / 4 + 16;
+    return ((size_t)((n / 2 + 1) / 0.7) + 4096) << shift;                        // acceptance = pi/4
 }
-static int device_sum(gev_ctx* c, const double* x, size_t n, double shift, int pw, double* host_out)
+// mean / var of nvec vectors into stats (k_ph_var_partial / _final, both passes)
+static int ph_var(gev_ctx* c, const double* base, size_t vec_stride, size_t elem_stride, size_t n, unsigned nvec, double* stats)
 {
     hipStream_t st = c->stream;
-    GEVC(c->d_gef_red.ensure(512 * sizeof(double), st));
+    GEVC(c->ph.partial.ensure((size_t)nvec * 256 * sizeof(double), st));
     const int nb = (int)std::min<size_t>(ceil_div(n, 256), 256);
-    hipLaunchKernelGGL(k_sum_partial, dim3(nb), dim3(256), 0, st, x, n, shift, pw, c->d_gef_red.as<double>());
-    hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(256), 0, st, c->d_gef_red.as<double>(), nb, c->d_gef_red.as<double>() + 256);
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(k_ph_var_partial, dim3(nb, nvec), dim3(256), 0, st, base, vec_stride, elem_stride, n, (const double*)stats, pass, c->ph.partial.as<double>());
+        hipLaunchKernelGGL(k_ph_var_final, dim3(nvec), dim3(256), 0, st, (const double*)c->ph.partial.as<double>(), nb, n, pass, stats);
+    }
     KCHECK();
-    HIPC(hipMemcpyAsync(host_out, c->d_gef_red.as<double>() + 256, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
     return GEV_OK;
 }
+// one batch of streams: *flag |= NRM_CAND_SHORT when one of them ran out of candidate pairs
+static int ph_streams(gev_ctx* c, std::vector<NrmStream>& v, const u32* seeds, u32* starts, u32* flag)
+{
+    if (v.empty()) return GEV_OK;
+    hipStream_t st = c->stream;
+    u32 off = 0, nb_max = 0;
+    for (NrmStream& s : v) { s.n_blocks = (u32)ceil_div((size_t)s.n_cand, POLAR_CHUNK); s.blk_off = off; off += s.n_blocks; nb_max = std::max(nb_max, s.n_blocks); }
+    GEVC(c->ph.blk.ensure(off * sizeof(u32), st));
+    GEVC(upload_table(c, c->ph.streams, v.data(), v.size() * sizeof(NrmStream), st));
+    hipLaunchKernelGGL(k_nrm_count, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, (const u32*)starts, c->ph.blk.as<u32>());
+    hipLaunchKernelGGL(k_nrm_emit, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, starts, (const u32*)c->ph.blk.as<u32>(), flag);
+    KCHECK();
+    return GEV_OK;
+}
+enum { GEF_FLAG = 0, GEF_STARTS = 1, GEF_WORDS = 4 };       // d_gef_stat: the short flag, the stream offsets (unused: no stream continues another), then {mean, var} of e
 int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params* par, uint32_t seed,
                              const double* common_sibling, const double* f_father, const double* f_mother,
                              double* additive, double* dominance, double* bv, double* e_noise, double* parental_effect, double* phen_out)
@@ -2866,10 +2872,10 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
     GEVC(c->d_gef_io.ensure(10 * n * sizeof(double), st));
     double* io = c->d_gef_io.as<double>();
     double *d_e = io, *d_par = io + n, *d_cs = io + 2 * n, *d_ff = io + 3 * n, *d_out = io + 4 * n;     // d_out: 6 vectors
-    GEVC(normal_stream(c, seed, n, 1.0, d_e));                                                           // generator_e(seed), N(0,1), :3080-3102
+    GEVC(c->d_gef_stat.ensure(GEF_WORDS * sizeof(u32) + 2 * sizeof(double), st));
+    u32* stat = c->d_gef_stat.as<u32>(); double* e_stats = (double*)(stat + GEF_WORDS);
     const bool need_par = par->vf > 0;
-    if (par->gen_num == 0) { if (need_par) GEVC(normal_stream(c, seed + 1u, n, std::sqrt(par->vf), d_par)); }   // generator_f(seed+1), :3095-3114
-    else if (need_par) {
+    if (par->gen_num != 0 && need_par) {
         double* d_fm = d_out;                                                                             // staging before d_out is written
         if (f_father) HIPC(hipMemcpyAsync(d_ff, f_father, n * sizeof(double), hipMemcpyHostToDevice, st));
         if (f_mother) HIPC(hipMemcpyAsync(d_fm, f_mother, n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2882,28 +2888,32 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
     if (par->va > 0) s_a = std::sqrt(par->s2_a_gen0 / par->va);
     double s_d = 0;
     if (par->vd > 0) s_d = std::sqrt(par->s2_d_gen0 / par->vd); else if (par->vd == -1) s_d = 1;
-    double s_ev = 0;
-    if (par->ve > 0) {                                                                                    // CommFunc::var(e): two passes, n-1
-        double sum = 0, ss = 0, var_e = 0;
-        if (n > 1) {
-            GEVC(device_sum(c, d_e, n, 0.0, 1, &sum));
-            const double mu = sum / (double)n;
-            GEVC(device_sum(c, d_e, n, mu, 2, &ss));
-            var_e = ss / (double)(n - 1);
-        }
-        s_ev = std::sqrt(var_e / par->ve);
-    }
     DevBuf& keep = P.d_phen[P.sbuf];                                                                     // the population's phenotypes, for gev_compute_selection
     GEVC(keep.ensure(n * (size_t)c->nphen * sizeof(double), st, /*keep=*/true));
-    hipLaunchKernelGGL(k_gef_apply, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, c->d_add.as<double>() + phen, c->d_dom.as<double>() + phen, (size_t)c->nphen,
-                       d_e, d_par, common_sibling ? d_cs : (const double*)nullptr, n, s_a, s_d, s_ev, par->vf,
-                       d_out, d_out + n, d_out + 2 * n, d_out + 3 * n, d_out + 4 * n, d_out + 5 * n, keep.as<double>() + phen);
-    KCHECK();
     double* outs[6] = {additive, dominance, bv, e_noise, parental_effect, phen_out};
-    for (int k = 0; k < 6; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], d_out + k * n, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    P.phen_ok[phen] = 1;
-    return GEV_OK;
+    // the streams, var(e), the scaling and the copies out, with twice the candidate pairs while a stream runs short of them
+    // (practically never: acceptance far below pi/4)
+    for (int attempt = 0; attempt < 4; attempt++) {
+        if (attempt) c->ph.reruns++;
+        HIPC(hipMemsetAsync(stat, 0, GEF_WORDS * sizeof(u32), st));
+        std::vector<NrmStream> batch;
+        NrmStream e{}; e.seed_idx = -1; e.seed_val = seed; e.start_idx = e.next_idx = -1; e.n = n; e.n_cand = ph_candidates(c, n, attempt); e.sd = 1.0; e.out = d_e;
+        batch.push_back(e);                                                                               // generator_e(seed), N(0,1), :3080-3102
+        if (par->gen_num == 0 && need_par) { NrmStream f = e; f.seed_add = 1; f.sd = std::sqrt(par->vf); f.out = d_par; batch.push_back(f); }   // generator_f(seed+1), :3095-3114
+        GEVC(ph_streams(c, batch, nullptr, stat + GEF_STARTS, stat + GEF_FLAG));
+        GEVC(ph_var(c, d_e, n, 1, n, 1, e_stats));                                                        // CommFunc::var(e): two passes, n-1
+        hipLaunchKernelGGL(k_gef_apply, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, c->d_add.as<double>() + phen, c->d_dom.as<double>() + phen, (size_t)c->nphen,
+                           d_e, (const double*)e_stats, d_par, common_sibling ? d_cs : (const double*)nullptr, n, s_a, s_d, par->ve, par->vf,
+                           d_out, d_out + n, d_out + 2 * n, d_out + 3 * n, d_out + 4 * n, d_out + 5 * n, keep.as<double>() + phen);
+        KCHECK();
+        for (int k = 0; k < 6; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], d_out + k * n, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        u32 flag = 0;
+        HIPC(hipMemcpyAsync(&flag, stat + GEF_FLAG, sizeof flag, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (!(flag & NRM_CAND_SHORT)) { P.phen_ok[phen] = 1; return GEV_OK; }
+    }
+    P.phen_ok[phen] = 0;       // the short attempts have written the kept phenotype column: gev_compute_selection must not read it
+    return fail(GEV_EDEVICE, "normal_stream: acceptance far below pi/4");
 }
 
 // Raw A/D totals of the current generation from the host: a locus-split population's contexts each hold partial sums; after the
@@ -2950,16 +2960,12 @@ int gev_compute_selection(gev_ctx* c, int pop, const gev_selection_params* par, 
     const size_t n = P.n_people;
     DevBuf& V = P.d_sel[P.sbuf];
     GEVC(V.ensure(3 * n * sizeof(double), st));
-    GEVC(P.d_sv0.ensure((2 + SEL_RED_BLOCKS) * sizeof(double), st, /*keep=*/true));     // {mean, var} + the partial sums of the reduction
+    GEVC(P.d_sv0.ensure(2 * sizeof(double), st, /*keep=*/true));
     double *mv = V.as<double>(), *sv = mv + n, *svf = mv + 2 * n, *sv0 = P.d_sv0.as<double>();
     const unsigned nbk = (unsigned)ceil_div(n, 256);
     hipLaunchKernelGGL(k_sel_values, dim3(nbk), dim3(256), 0, st, (const double*)P.d_phen[P.sbuf].as<double>(), n, a, (const double*)sv0, gen0 ? 0 : 1, mv, sv, svf);
     if (gen0) {                                             // _gen0_SV_mean / _gen0_SV_var (:3326-3330), kept on the device
-        const int nb = (int)std::min<size_t>(nbk, SEL_RED_BLOCKS);
-        for (int pass = 0; pass < 2; pass++) {
-            hipLaunchKernelGGL(k_sel_sum_partial, dim3(nb), dim3(256), 0, st, (const double*)sv, n, (const double*)sv0, pass, sv0 + 2);
-            hipLaunchKernelGGL(k_sel_sum_final, dim3(1), dim3(256), 0, st, (const double*)(sv0 + 2), nb, n, pass, sv0);
-        }
+        GEVC(ph_var(c, sv, 1, 1, n, 1, sv0));
         hipLaunchKernelGGL(k_sel_finish, dim3(nbk), dim3(256), 0, st, n, a, (const double*)sv0, sv, svf);
     }
     KCHECK();
@@ -3002,7 +3008,7 @@ int gev_set_selection_gen0(gev_ctx* c, int pop, double mean, double var)
     if (c->pend.active) return fail(GEV_ESTATE, "set_selection_gen0: a generation is pending");
     PopState& P = c->pop[pop];
     HIPC(hipSetDevice(c->device));
-    GEVC(P.d_sv0.ensure((2 + SEL_RED_BLOCKS) * sizeof(double), c->stream));
+    GEVC(P.d_sv0.ensure(2 * sizeof(double), c->stream));
     hipLaunchKernelGGL(k_sel_set_gen0, dim3(1), dim3(64), 0, c->stream, P.d_sv0.as<double>(), mean, var);
     KCHECK();
     P.sv0_ok = true;
@@ -4429,38 +4435,6 @@ int gev_plane_ptr(gev_ctx* c, int pop, int chr, void** dptr, size_t* unit_bytes,
 int gev_stream(gev_ctx* c, void** s) { if (!c || !s) return fail(GEV_EINVAL, "null"); *s = (void*)c->stream; return GEV_OK; }
 int gev_last_reproduce_ms(gev_ctx* c, float ms[4]) { if (!c || !ms) return fail(GEV_EINVAL, "null"); GEVC(gev_sync(c)); for (int i = 0; i < 4; i++) ms[i] = c->last_ms[i]; return GEV_OK; }
 // ---- Simulation::ras_scale_AD_compute_GEF for every phenotype, fed from the device (gev_phenotypes.h) ------------------------------
-static size_t ph_candidates(const gev_ctx* c, size_t n)
-{
-    if (c->ph.short_candidates && c->ph.cand_shift == 0) return n / 4 + 16;
-    return ((size_t)((n / 2 + 1) / 0.7) + 4096) << c->ph.cand_shift;             // acceptance = pi/4
-}
-// mean / var of nvec vectors into stats (k_ph_var_partial / _final, both passes)
-static int ph_var(gev_ctx* c, const double* base, size_t vec_stride, size_t elem_stride, size_t n, unsigned nvec, double* stats)
-{
-    hipStream_t st = c->stream;
-    GEVC(c->ph.partial.ensure((size_t)nvec * 256 * sizeof(double), st));
-    const int nb = (int)std::min<size_t>(ceil_div(n, 256), 256);
-    for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(k_ph_var_partial, dim3(nb, nvec), dim3(256), 0, st, base, vec_stride, elem_stride, n, (const double*)stats, pass, c->ph.partial.as<double>());
-        hipLaunchKernelGGL(k_ph_var_final, dim3(nvec), dim3(256), 0, st, (const double*)c->ph.partial.as<double>(), nb, n, pass, stats);
-    }
-    KCHECK();
-    return GEV_OK;
-}
-static int ph_streams(gev_ctx* c, std::vector<NrmStream>& v, const u32* seeds)
-{
-    if (v.empty()) return GEV_OK;
-    hipStream_t st = c->stream;
-    u32 off = 0, nb_max = 0;
-    for (NrmStream& s : v) { s.n_blocks = (u32)ceil_div((size_t)s.n_cand, NRM_CHUNK); s.blk_off = off; off += s.n_blocks; nb_max = std::max(nb_max, s.n_blocks); }
-    GEVC(c->ph.blk.ensure(off * sizeof(u32), st));
-    GEVC(upload_table(c, c->ph.streams, v.data(), v.size() * sizeof(NrmStream), st));
-    hipLaunchKernelGGL(k_nrm_count, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, (const u32*)c->ph.starts.as<u32>(), c->ph.blk.as<u32>());
-    hipLaunchKernelGGL(k_nrm_emit, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, c->ph.starts.as<u32>(), (const u32*)c->ph.blk.as<u32>(),
-                       c->ph.res.as<u32>() + PHR_FLAGS);
-    KCHECK();
-    return GEV_OK;
-}
 static int ph_enqueue(gev_ctx* c)
 {
     gev_ctx::PhenoState& H = c->ph;
@@ -4503,7 +4477,7 @@ static int ph_enqueue(gev_ctx* c)
     for (int p = 0; p < nphen; p++) {
         const gev_pheno_scheme& S = H.scheme[p];
         double* o = comp.as<double>() + (size_t)p * PH_COMP * n;
-        NrmStream e{}; e.seed_idx = (int)(gen0 ? nvc : 0) + p; e.start_idx = e.next_idx = -1; e.n = n; e.n_cand = ph_candidates(c, n); e.sd = 1.0; e.out = H.eraw.as<double>() + (size_t)p * n;
+        NrmStream e{}; e.seed_idx = (int)(gen0 ? nvc : 0) + p; e.start_idx = e.next_idx = -1; e.n = n; e.n_cand = ph_candidates(c, n, H.cand_shift); e.sd = 1.0; e.out = H.eraw.as<double>() + (size_t)p * n;
         batch.push_back(e);
         if (gen0 && S.vc > 0) { NrmStream s = e; s.seed_idx = kvc++; s.sd = std::sqrt(S.vc); s.out = o + PH_C * n; batch.push_back(s); }
         if (gen0 && S.vf > 0) { NrmStream s = e; s.seed_add = 1; s.sd = std::sqrt(S.vf); s.out = o + PH_F * n; batch.push_back(s); }
@@ -4522,14 +4496,14 @@ static int ph_enqueue(gev_ctx* c)
         int k = 0;
         for (int p = 0; p < nphen; p++) {
             if (!(H.scheme[p].vc > 0)) continue;
-            NrmStream s{}; s.seed_idx = -1; s.seed_val = P.cs_seed; s.seed_add = 1; s.start_idx = k; s.next_idx = k + 1; s.n = P.cs_ncouples; s.n_cand = ph_candidates(c, P.cs_ncouples);
+            NrmStream s{}; s.seed_idx = -1; s.seed_val = P.cs_seed; s.seed_add = 1; s.start_idx = k; s.next_idx = k + 1; s.n = P.cs_ncouples; s.n_cand = ph_candidates(c, P.cs_ncouples, H.cand_shift);
             s.sd = std::sqrt(H.scheme[p].vc); s.out = H.cval.as<double>() + (size_t)p * cval_stride;
             if (k == 0) batch.push_back(s); else chained.push_back(std::vector<NrmStream>(1, s));
             k++;
         }
     }
-    GEVC(ph_streams(c, batch, seeds));
-    for (auto& one : chained) GEVC(ph_streams(c, one, seeds));
+    GEVC(ph_streams(c, batch, seeds, H.starts.as<u32>(), res + PHR_FLAGS));
+    for (auto& one : chained) GEVC(ph_streams(c, one, seeds, H.starts.as<u32>(), res + PHR_FLAGS));
     GEVC(ph_var(c, H.eraw.as<double>(), n, 1, n, (unsigned)nphen, e_stats));                       // CommFunc::var(e), two passes, n-1
     GEVC(upload_table(c, H.tasks, tasks.data(), tasks.size() * sizeof(PhTask), st));
     DevBuf& keep = P.d_phen[P.sbuf];
@@ -4682,8 +4656,8 @@ int gev_upload_prev_gen(gev_ctx* c, int pop, const double* phen, const double* p
     P.prev_n = n; P.prev_ok = true;
     return GEV_OK;
 }
-// test hook: the first attempt of every following gev_generation_phenotypes starts with far too few candidate pairs (on != 0);
-// *reruns = steps that were enqueued again, over the context's life
+// test hook: the first attempt of every following gev_generation_phenotypes / gev_scale_ad_compute_gef starts with far too few
+// candidate pairs (on != 0); *reruns = steps and calls that were enqueued again, over the context's life
 int gev_dbg_phenotype_knobs(gev_ctx* c, int short_candidates, unsigned long long* reruns)
 {
     if (!c) return fail(GEV_EINVAL, "null context");

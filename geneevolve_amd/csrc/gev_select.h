@@ -5,7 +5,6 @@
 #pragma once
 
 #define GEV_SEL_MAX_PHEN 64
-#define SEL_RED_BLOCKS 256
 
 // per-call constants, passed by value (no upload, no host wait)
 struct SelArgs {
@@ -39,7 +38,7 @@ __device__ __forceinline__ double sel_standardise(double sv, const double* sv0)
 
 // mv = sum omega[p] * phen[p], sv = sum lambda[p] * phen[p] in phenotype order (:3310-3318); phen[p] includes the --gamma constant
 // of the population (:3291), added first as the reference adds it to Human::phen.  finish != 0 (generation > 0, or generation-0
-// statistics already known): standardise and apply the function here; else sv is left raw for the generation-0 reduction.
+// statistics already known): standardise and apply the function here; else sv is left raw for the generation-0 reduction (k_ph_var_*).
 __global__ void __launch_bounds__(256) k_sel_values(const double* __restrict__ phen, size_t n, SelArgs a, const double* __restrict__ sv0, int finish,
                                                     double* __restrict__ mv_out, double* __restrict__ sv_out, double* __restrict__ svf_out)
 {
@@ -61,31 +60,6 @@ __global__ void __launch_bounds__(256) k_sel_finish(size_t n, SelArgs a, const d
     if (i >= n) return;
     const double z = sel_standardise(sv[i], sv0);
     sv[i] = z; svf_out[i] = sel_func(a, z);
-}
-// CommFunc::mean / CommFunc::var (src/CommFunc.cpp:38-68) of x on the device, two passes: pass 0 sums x, pass 1 sums (x - mean)^2
-// with the mean of pass 0 (read from out[0]).  Grid-stride partial sums of SEL_RED_BLOCKS x 256 threads, then one block.
-__global__ void __launch_bounds__(256) k_sel_sum_partial(const double* __restrict__ x, size_t n, const double* __restrict__ out, int pass, double* __restrict__ partial)
-{
-    __shared__ double s[256];
-    const double mu = pass ? out[0] : 0.0;
-    double acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        if (pass) { const double v = x[i] - mu; acc += v * v; } else acc += x[i];
-    }
-    s[threadIdx.x] = acc; __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
-}
-// out[0] = mean (pass 0), out[1] = var with n-1, 0 for n <= 1 (pass 1)
-__global__ void __launch_bounds__(256) k_sel_sum_final(const double* __restrict__ partial, int nb, size_t n, int pass, double* __restrict__ out)
-{
-    __shared__ double s[256];
-    s[threadIdx.x] = (int)threadIdx.x < nb ? partial[threadIdx.x] : 0.0; __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w]; __syncthreads(); }
-    if (threadIdx.x == 0) {
-        if (pass == 0) out[0] = s[0] / (double)n;
-        else out[1] = n <= 1 ? 0.0 : s[0] / (double)(n - 1);
-    }
 }
 __global__ void k_sel_set_gen0(double* __restrict__ out, double mean, double var)
 {

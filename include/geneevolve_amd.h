@@ -373,8 +373,8 @@ int gev_set_ad_gen0(gev_ctx*, int pop, int phen, double var_a, double var_d);
  * gev_upload_prev_gen: the same record from the host, phen / parental_effect = [nphen][n] (either may be NULL = 0). */
 int gev_save_prev_gen(gev_ctx*, int pop, const double* phen_shift);
 int gev_upload_prev_gen(gev_ctx*, int pop, const double* phen, const double* parental_effect, size_t n);
-/* test hook: short_candidates != 0 starts the normal streams of the following gev_generation_phenotypes far too short, so that the step
- * is run again; *reruns (may be NULL) = steps run again over the context's life */
+/* test hook: short_candidates != 0 starts the normal streams of the following gev_generation_phenotypes and gev_scale_ad_compute_gef
+ * calls far too short, so that the step / the call is run again; *reruns (may be NULL) = such reruns over the context's life */
 int gev_dbg_phenotype_knobs(gev_ctx*, int short_candidates, unsigned long long* reruns);
 
 /* ---- the per-generation .info text on the device ----

@@ -106,8 +106,8 @@ SEEDS = [1, 999_999, 2_147_483_646, 2_147_483_647, 4_294_967_295]
 @pytest.mark.parametrize("n", SIZES)
 def test_generation0_parental_stream_is_libstdcxx_normal_distribution(gpu_lib, oracle_lib, n):
     """generation 0, vf > 0: parental_effect is the raw N(0, sqrt(vf)) stream of generator_f(seed + 1) (:3095-3114), unscaled.
-    n = 65 536 is where k_sum_partial starts to stride; 1 000 001 is odd (the last pair half used) and its ~718k candidates make
-    k_scan_sums loop over more than 256 partials.  Seeds: seed + 1 = 2**31 - 1 (engine state 1), seed = 2**31 - 1, and seed + 1
+    n = 65 536 is where k_ph_var_partial starts to stride; 1 000 001 is odd (the last pair half used) and its ~718k candidates are
+    351 blocks: k_nrm_emit's threads sum more than one block count each.  Seeds: seed + 1 = 2**31 - 1 (engine state 1), seed = 2**31 - 1, and seed + 1
     wrapping to 0 in unsigned arithmetic, as in the reference.  A misaligned pair after a rejection moves values by O(1)."""
     g, o = twins(gpu_lib, oracle_lib, n)
     vf = 0.3
