@@ -86,7 +86,7 @@ ABI_SYMBOLS = [
     "last_error", "version", "create", "destroy", "set_rmap", "set_mutmap", "set_snps", "set_cvs",
     "upload_founders", "upload_cv_founders", "synth_founders", "synth_cv_founders", "init_gen0",
     "reproduce", "presample", "compute_ad", "scale_ad_compute_gef", "set_ad", "get_cv_freq", "migrate", "export_size", "export_rows", "remove_rows",
-    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "ind_genotype_counts", "pair_genotype_counts", "dbg_pair_counts_host", "ld_counts", "ld_scores", "dbg_ld_host", "dbg_ld_r2_q40_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
+    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "ind_genotype_counts", "pair_genotype_counts", "dbg_pair_counts_host", "ld_counts", "ld_scores", "dbg_ld_host", "dbg_ld_r2_q40_host", "snp_trait_sums", "dbg_trait_sums_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
     "pop_size", "plane_ptr", "reserve", "set_chr_active", "set_dense_state", "materialize", "materialize_pops", "materialize_bed", "stream", "last_reproduce_ms", "set_track_intervals", "set_stitch_mode", "sync", "timing_totals", "stitch_totals", "reproduce_begin", "reproduce_end", "presample_sex", "set_overlap",
     "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
     "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
@@ -153,6 +153,21 @@ def bytes_to_words(packed_u8, L):
 
 def unpack_rows(words, L):
     return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little")[:, :L]
+
+
+def _traits(trait, n_ind):
+    """quanta as the trait-sum calls take them: int32 [n_traits][n_ind], a single vector as one trait"""
+    trait = _arr(trait, np.int32)
+    if trait.ndim == 1:
+        trait = trait.reshape(1, -1)
+    assert trait.ndim == 2 and trait.shape[1] == max(n_ind, 0), "one quantum per trait and individual of the range"
+    return trait
+
+
+def _trait_sum_outs(n_traits, n_snps):
+    n_snps = max(n_snps, 0)
+    return (np.empty((n_traits, n_snps), dtype=np.int64), np.empty((n_traits, n_snps), dtype=np.int64),
+            np.empty(n_snps, dtype=np.uint32), np.empty(n_snps, dtype=np.uint32))
 
 
 def pack_names(names):
@@ -276,6 +291,22 @@ class GevLibrary:
         out = np.empty(len(num), dtype=np.uint64)
         self.check(self._f("dbg_ld_r2_q40_host")(_p(num), _p(den_j), _p(den_k), C.c_size_t(len(num)), _p(out)))
         return out
+
+    def dbg_trait_sums_host(self, bits, L, trait, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
+        """the library's trait-sum arithmetic compiled for the host (no device needed) -> (gsum, hetsum, n_het, n_hom_alt) as
+        GevContext.snp_trait_sums.  bits: uint64 [2 * n_people][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns
+        them; trait: int32 [n_traits][n_ind] quanta (or [n_ind] for one trait), entry i = individual ind_begin + i"""
+        bits = _arr(bits, np.uint64)
+        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
+        n_people = bits.shape[0] // 2
+        n_snps = L - snp_begin if n_snps is None else n_snps
+        n_ind = n_people - ind_begin if n_ind is None else n_ind
+        trait = _traits(trait, n_ind)
+        outs = _trait_sum_outs(trait.shape[0], n_snps)
+        z = C.c_size_t
+        self.check(self._f("dbg_trait_sums_host")(_p(bits), z(bits.shape[1]), z(n_people), z(L), z(snp_begin), z(n_snps), z(ind_begin), z(n_ind),
+                                                  _p(trait), z(trait.shape[0]), *[_p(o) for o in outs]))
+        return outs
 
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
@@ -891,6 +922,19 @@ class GevContext:
         z = C.c_size_t
         self._call_new("ld_scores", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), _p(lo), _p(hi), z(ind_begin), z(n_ind), C.c_int(1 if genotype else 0), _p(score), _p(terms))
         return score, terms
+
+    def snp_trait_sums(self, pop, chr, trait, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
+        """-> (gsum, hetsum, n_het, n_hom_alt): for SNP j of [snp_begin, +n_snps) and trait t over individuals [ind_begin, +n_ind), int64
+        [n_traits][n_snps]: gsum = sum_i g_ij q[t][i], hetsum = the sum of q[t][i] over the heterozygous individuals; uint32 [n_snps]: the
+        heterozygous and homozygous-alt individuals.  trait: int32 [n_traits][n_ind] quanta, |q| <= 2^30 (or [n_ind] for one trait), entry
+        i = individual ind_begin + i.  Exact integer products on the device's matrix cores from the current generation (mutations applied)"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        trait = _traits(trait, n_ind)
+        outs = _trait_sum_outs(trait.shape[0], n_snps)
+        z = C.c_size_t
+        self._call_new("snp_trait_sums", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(ind_begin), z(n_ind), _p(trait), z(trait.shape[0]), *[_p(o) for o in outs])
+        return outs
 
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
         """bytes of the reference's .hap file (format_hap::write_hap) for the given SNP lines"""

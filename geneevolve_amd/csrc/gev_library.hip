@@ -24,6 +24,7 @@
 #include "gev_snpcount.h"
 #include "gev_paircount.h"
 #include "gev_ldcount.h"
+#include "gev_traitsum.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -307,6 +308,7 @@ struct gev_ctx {
     unsigned long long bp_launches[2] = {0, 0};   // product launches on small / large tiles over the context's life (bitprod_launch)
     DevBuf d_bp_a, d_bp_b, d_bp_cnt, d_bp_out;   // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
     DevBuf d_pair_w, d_ld_win, d_ld_score;       // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
+    DevBuf d_ts_trait, d_ts_b, d_ts_acc, d_ts_out;   // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
     DevBuf d_gef_io, d_gef_stat;                 // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
@@ -4215,6 +4217,90 @@ int gev_dbg_ld_r2_q40_host(const int64_t* num, const uint64_t* den_j, const uint
 {
     if (n && (!num || !den_j || !den_k || !q40)) return fail(GEV_EINVAL, "dbg_ld_r2_q40_host: null array");
     for (size_t i = 0; i < n; i++) q40[i] = gev_ld_r2_q40(num[i], den_j[i], den_k[i]);
+    return GEV_OK;
+}
+// ---- trait sums per SNP (gev_traitsum.h) -------------------------------------------------------
+static int ts_check_traits(const char* who, const int32_t* trait, size_t n_traits, size_t n_ind)
+{
+    if (n_ind > GEV_TS_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a digit's sum is an int32)", who, n_ind, (size_t)GEV_TS_MAX_IND);
+    if (!n_traits || !n_ind) return GEV_OK;
+    if (!trait) return fail(GEV_EINVAL, "%s: null trait array (%zu traits of %zu quanta each)", who, n_traits, n_ind);
+    for (size_t i = 0; i < n_traits * n_ind; i++)
+        if (trait[i] > GEV_TS_MAX_Q || trait[i] < -GEV_TS_MAX_Q) return fail(GEV_EINVAL, "%s: quantum %d of trait %zu, individual %zu beyond +-2^30", who, trait[i], i / n_ind, i % n_ind);
+    return GEV_OK;
+}
+static void ts_zero(size_t n_snps, size_t n_traits, int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
+{
+    if (gsum) memset(gsum, 0, n_traits * n_snps * sizeof(int64_t));
+    if (hetsum) memset(hetsum, 0, n_traits * n_snps * sizeof(int64_t));
+    if (n_het) memset(n_het, 0, n_snps * sizeof(u32));
+    if (n_hom_alt) memset(n_hom_alt, 0, n_snps * sizeof(u32));
+}
+// The SNPs are walked in blocks of at most ld_block() (gev_dbg_output_chunk caps them): a block is one snp_major_device pass and one
+// k_ld_prep into c->d_bp_a; the traits' operand bytes are made once per call and serve every block; a block's sums are copied out before the
+// next block's kernels run (stream order), and the call returns when the last ones have arrived.
+int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                       const int32_t* trait, size_t n_traits, int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
+{
+    const char* who = "snp_trait_sums";
+    GEVC(output_begin(c, pop, chr, who, true));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, P.cs[chr].L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
+    GEVC(ts_check_traits(who, trait, n_traits, n_ind));
+    if (!n_snps) return GEV_OK;
+    if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
+    const bool want_sums = (gsum || hetsum) && n_traits;
+    if (!want_sums && !n_het && !n_hom_alt) return GEV_OK;
+    hipStream_t st = c->stream;
+    const size_t blk = std::min(ld_block(c, P.n_people, ind_begin, n_ind), n_snps), pad = round_up(blk, BP_TILE);
+    const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind), n_cg = ceil_div(n_traits, 4), slices = ceil_div(n_w4, GEV_TS_SLICE_W);
+    GEVC(c->d_bp_cnt.ensure(3 * blk * sizeof(u32), st));
+    if (want_sums) {
+        GEVC(c->d_ts_trait.ensure(n_traits * n_ind * sizeof(int32_t), st));
+        GEVC(c->d_ts_b.ensure(n_cg * n_w4 * 512, st));                                       // 32 individuals x 16 columns a word
+        GEVC(c->d_ts_acc.ensure(2 * n_cg * pad * 16 * sizeof(int), st));
+        GEVC(c->d_ts_out.ensure(2 * n_traits * blk * sizeof(int64_t), st));
+        HIPC(hipMemcpyAsync(c->d_ts_trait.p, trait, n_traits * n_ind * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)ceil_div(n_cg * (n_w4 / 4) * 128, 256)), dim3(256), 0, st, c->d_ts_trait.as<int32_t>(), (u32)n_traits,
+                           (u64)ind_begin, (u64)n_ind, (u32)n_w4, (u32)n_cg, c->d_ts_b.as<uint4>());
+        KCHECK();
+    }
+    for (size_t off = 0; off < n_snps; off += blk) {
+        const size_t n = std::min(blk, n_snps - off);
+        LdSide A;
+        GEVC(ld_prep_side(c, pop, chr, snp_begin + off, n, ind_begin, n_ind, c->d_bp_a, c->d_bp_cnt.as<u32>(), blk, A));
+        if (n_het) HIPC(hipMemcpyAsync(n_het + off, A.het, n * sizeof(u32), hipMemcpyDeviceToHost, st));
+        if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt + off, A.hom, n * sizeof(u32), hipMemcpyDeviceToHost, st));
+        if (!want_sums) continue;
+        HIPC(hipMemsetAsync(c->d_ts_acc.p, 0, 2 * n_cg * A.n_pad * 16 * sizeof(int), st));
+        for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535)                                        // (a grid's z)
+            hipLaunchKernelGGL(k_ts_product, dim3((unsigned)(A.n_pad / BP_TILE), (unsigned)slices, (unsigned)std::min<size_t>(n_cg - cg0, 65535)), dim3(256), 0, st,
+                               A.plane, (u32)A.n_pad, (u32)n_w4, (const uint4*)c->d_ts_b.p, (u32)n_cg, (u32)cg0, c->d_ts_acc.as<int>());
+        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_traits * n, 256)), dim3(256), 0, st, (const int*)c->d_ts_acc.p, (u32)A.n_pad, (u32)n_cg,
+                           (u32)n_traits, (u32)n, (u32)blk, c->d_ts_out.as<long long>());
+        KCHECK();
+        int64_t* const outs[2] = {gsum, hetsum};
+        for (int o = 0; o < 2; o++)
+            if (outs[o]) HIPC(hipMemcpy2DAsync(outs[o] + off, n_snps * sizeof(int64_t), c->d_ts_out.as<int64_t>() + (size_t)o * n_traits * blk, blk * sizeof(int64_t),
+                                               n * sizeof(int64_t), n_traits, hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the arithmetic of gev_traitsum.h compiled for the host on haplotype-major rows in host memory: no device, no context
+int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
+                            size_t ind_begin, size_t n_ind, const int32_t* trait, size_t n_traits,
+                            int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
+{
+    const char* who = "dbg_trait_sums_host";
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
+    GEVC(ts_check_traits(who, trait, n_traits, n_ind));
+    if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    if (!n_snps) return GEV_OK;
+    if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
+    gev_trait_sums_host(bits, row_stride_words, snp_begin, n_snps, ind_begin, n_ind, trait, n_traits, gsum, hetsum, n_het, n_hom_alt);
     return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------

@@ -648,6 +648,33 @@ int gev_dbg_ld_host(const uint64_t* bits_a, size_t stride_a, size_t L_a, const u
  * counts of real data always have it (Cauchy-Schwarz): q40[i] = llrint(((double)num * (double)num) / ((double)den_j * (double)den_k) * 2^40),
  * 0 where a denominator is 0 */
 int gev_dbg_ld_r2_q40_host(const int64_t* num, const uint64_t* den_j, const uint64_t* den_k, size_t n, uint64_t* q40);
+/* ---- trait sums per SNP: an association scan without a dump -------------------------------------------------------------------------
+ * Counted on the device from the current generation, new mutations applied (csrc/gev_traitsum.h).  A trait is a host vector of int32
+ * quanta q[t][i], |q| <= 2^30, entry i = individual ind_begin + i (floating-point phenotypes are quantised by the caller:
+ * geneevolve_amd/assoc.py), so every sum is an exact integer sum, the same on every run and in every order.  For SNP j of
+ * [snp_begin,+n_snps) and trait t over individuals [ind_begin,+n_ind), each output may be NULL:
+ *   gsum[t][j]   (int64, [n_traits][n_snps]) = sum_i g_ij q[t][i], g = 0/1/2 copies of allele 1
+ *   hetsum[t][j] (int64, [n_traits][n_snps]) = sum of q[t][i] over the individuals heterozygous at j
+ *   n_het[j], n_hom_alt[j] (uint32 [n_snps]) = the heterozygous / homozygous-alt individuals, as gev_ld_counts gives them
+ * The genotype-class sums are S1 = hetsum and S2 = (gsum - hetsum) / 2; S0 follows from sum q, which the caller owns.  The SNPs go
+ * through the SNP-major pass and the plane of gev_ld_counts; the quanta are split into four balanced base-256 digits, and the sums
+ * are integer matrix products on the matrix cores (v_mfma_i32_16x16x64_i8) with the individuals split over workgroups.  The call
+ * begins like the other output calls and returns when the results are in the caller's memory.  GEV_ESTATE on a context without
+ * genotype planes, for an inactive chromosome and for a population without a current generation; GEV_EINVAL for a range beyond L /
+ * n_people, for a NULL trait with n_traits > 0 and n_ind > 0 and for a quantum beyond +-2^30 (checked before anything is enqueued);
+ * GEV_EUNSUPPORTED for n_ind > 2^22 (a digit's sum is an int32).  n_snps == 0 touches nothing, n_ind == 0 writes zeros, n_traits == 0
+ * gives the two count vectors only.  The device buffers are created by the first call; gev_dbg_output_chunk caps the SNPs of one pass. */
+int gev_snp_trait_sums(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                       const int32_t* trait /*[n_traits][n_ind], host*/, size_t n_traits,
+                       int64_t* gsum /*[n_traits][n_snps]*/, int64_t* hetsum /*[n_traits][n_snps]*/,
+                       uint32_t* n_het /*[n_snps]*/, uint32_t* n_hom_alt /*[n_snps]*/);
+/* the same arithmetic (masking, digit split, byte order of both operands, recombination) compiled for the host on rows in host memory
+ * as gev_download_haps returns them (2 n_people rows, stride >= ceil(L/64) words), a plain integer loop in place of the matrix
+ * instruction: no device, no context.  Only the rows of the individuals of the range are read, and of those the words that hold a SNP
+ * of the range. */
+int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
+                            size_t ind_begin, size_t n_ind, const int32_t* trait, size_t n_traits,
+                            int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */
