@@ -7,8 +7,9 @@
 //   * srand(): the glibc TYPE_3 generator is linear, output j = sum_i W[i][j] * r_i (mod 2^32).  The old form evaluates all 64
 //     outputs of one generator per wave (31 multiply steps) and uses ~3 of them.  Here lane (g, j) = (lane >> 3, lane & 7) holds
 //     output j of generator g: ONE pass of 31 multiply steps yields the first 8 outputs of 8 generators.
-//   * map scan: unchanged inner loop (lane l owns draws l, l+64, ...; only the high digit of generate_canonical is produced per
-//     draw and compared with the map's largest a_hi), but a candidate is only RECORDED (row, high digit, task) in an LDS list.
+//   * map scan: the same lane grid.  Lane (g, j) owns draws j, j + 8, ... of task g, so ONE loop scans the maps of all eight
+//     tasks (see scan_candidates); only the high digit of generate_canonical is produced per draw and compared with the map's
+//     largest a_hi, and a candidate is only RECORDED (row, high digit, task) in an LDS list.
 //   * resolve: the candidates of all 8 scans are tested against their threshold rows lane-parallel (one 16-byte load per
 //     candidate instead of a divergent load inside the scan loop), hits are ranked per task with ballots, and the per-hit work
 //     (breakpoint = bp[row] + rand() % dist; mutation position by uniform_int_distribution, side = rand() % 2) runs one hit per
@@ -25,14 +26,16 @@
 #define SB_OUT 8            // rand() outputs per generator held in the lane grid
 #define SB_CAND 320         // candidate slots per wave: a flush is forced at >= 64, one scan step adds <= 256
 
-#define SB_J 32             // draws per lane that are prefiltered from ONE exact engine state (64 * SB_J = 2048 draws per block)
+#define SB_M 256            // draws per lane that are prefiltered from ONE exact engine state
+#define SB_BLK (8 * SB_M)   // draws of one task per block: 8 lanes x SB_M
 struct __attribute__((aligned(32))) SmpTabs {   // constant tables, one copy per workgroup (LDS)
-    double kd[SB_J];        // c_j / M with c_j = 16807^(128 j) mod M: draw (lane + 64 j)'s high digit = x_lane * c_j mod M
-    u32 ci[SB_J];           // c_j
-    u32 pow_even[64];       // 16807^(2l+2): lane l's first high-digit engine output
+    double kd[SB_M + 4];    // c_m / M with c_m = 16807^(16 m) mod M: draw (j + 8 m)'s high digit = x_j * c_m mod M; 4 spare entries
+                            // (0) behind the last one, so that the scan may always load the next step's four
+    u32 ci[SB_M];           // c_m
+    u32 pow_even[64];       // 16807^(2l+2): draw l's high-digit engine output
     u32 w8[31 * SB_OUT];    // w_init[i][j], j < 8
     u32 pow_lcg[32];        // 16807^(i-1), i = 1..30
-    u32 pow128, pow_blk /* 16807^(128 SB_J): next block of draws */, inv16807, pad;
+    u32 pow_blk /* 16807^(2 SB_BLK): next block of draws */, inv16807, pad[2];
 };
 struct SmpWave {            // scratch of one wave (LDS)
     u32 r[SB_TASKS * 33];   // seed words r_0..r_30 of the 8 generators, odd stride
@@ -44,16 +47,22 @@ struct SmpWave {            // scratch of one wave (LDS)
 __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 __device__ __forceinline__ u32 mbcnt64(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
 
+// Multiplier m < SB_M of the scan, c_m = 16807^(16 m) mod M (8 draws = 16 engine steps; 16807^16 is pow_even[7]), and the FP64
+// constant fl(c_m / M) the prefilter multiplies with.  The one definition for the kernel's tables and for the exhaustive check.
+__device__ __forceinline__ void smp_scan_multiplier(const GevRngTables* __restrict__ g, u32 m, u32& c, double& k)
+{
+    c = powmod31(g->pow_even[7], m);
+    k = (double)c / 2147483647.0;
+}
+
 __device__ __forceinline__ void stage_smp_tabs(const GevRngTables* __restrict__ g, SmpTabs* s)
 {
     for (u32 i = threadIdx.x; i < 64; i += blockDim.x) s->pow_even[i] = g->pow_even[i];
     for (u32 i = threadIdx.x; i < 31 * SB_OUT; i += blockDim.x) s->w8[i] = g->w_init[(i / SB_OUT) * 64 + (i % SB_OUT)];
     for (u32 i = threadIdx.x; i < 31; i += blockDim.x) s->pow_lcg[i] = g->pow_lcg[i];
-    if (threadIdx.x < SB_J) {
-        const u32 c = powmod31(g->pow128, threadIdx.x);              // (16807^128)^j
-        s->ci[threadIdx.x] = c; s->kd[threadIdx.x] = (double)c / 2147483647.0;
-    }
-    if (threadIdx.x == 0) { s->pow_lcg[31] = 0; s->pow128 = g->pow128; s->pow_blk = powmod31(g->pow128, SB_J); s->inv16807 = g->inv16807; s->pad = 0; }
+    for (u32 i = threadIdx.x; i < SB_M; i += blockDim.x) smp_scan_multiplier(g, i, s->ci[i], s->kd[i]);
+    if (threadIdx.x < 4) s->kd[SB_M + threadIdx.x] = 0.0;
+    if (threadIdx.x == 0) { s->pow_lcg[31] = 0; s->pow_blk = powmod31(g->pow_even[7], SB_M); s->inv16807 = g->inv16807; s->pad[0] = s->pad[1] = 0; }
     __syncthreads();
 }
 
@@ -84,64 +93,89 @@ __device__ __forceinline__ u32 srand8(const SmpTabs* __restrict__ T, volatile u3
     return acc;
 }
 
-// One Bernoulli scan (engine = minstd_rand0(engine_seed), draw d tests map row first_row + d) that only RECORDS candidates:
-// draws whose high digit x2 - 1 is below `amax` (the largest a_hi of the map) go to the wave's candidate list tagged `tag`.
-// `count` (wave-uniform) is the list length; `flush()` must consume the list and reset count when it reaches 64.
+// The Bernoulli scans of the wave's EIGHT tasks in one loop, on the lane grid of srand8.  All arguments but T, W, count and flush
+// are per-lane values, equal within a lane group: task g = lane >> 3 draws from engine = minstd_rand0(engine_seed), its draw d
+// tests map row first_row + d, d < n_draws (0: the task has no scan), and a draw whose high digit x2 - 1 is below `amax` (the
+// largest a_hi of the task's map) is only RECORDED: it goes to the wave's candidate list, tagged g.  `count` (wave-uniform) is
+// the list length; `flush()` must consume the list and reset count when it reaches 64.
 //
-// FP64 prefilter.  Lane l holds ONE exact engine state x (the high digit of draw l of the current block of 64 * SB_J draws); the
-// high digit of its draw l + 64 j is x2 = x * c_j mod M, i.e. M * frac(T) with T = x * c_j / M < 2^31.  One FMA evaluates
-//     s = x * fl(c_j / M) + (1.5 * 2^32 + 4 u),   u = 2^-20 = ulp(s),
+// Layout.  Lane (g, j) owns draws j, j + 8, j + 16, ... of task g.  It holds ONE exact engine state x per block of SB_BLK = 2048
+// draws of its task, the high digit of draw j of the block (engine output 2 j + 2: pow_even[j]); the high digit of its draw
+// j + 8 m is x * c_m mod M with c_m = 16807^(16 m), m < SB_M = 256, and the next block starts from x * 16807^4096.  One step of
+// the loop tests four m, that is 32 draws of each of the eight tasks, with wave-uniform constants c_m / M (one broadcast 32-byte
+// LDS read per step, issued one step ahead of its use; two steps ahead measured the same, and broadcasting the constants from
+// lanes with v_readlane measured 33 % slower in the earlier layout).  The tasks' ranges may differ (chromosomes with different maps, tasks
+// off the fast path): the loop runs without bounds tests while every lane that has draws left in the block is inside its
+// range, then with a per-lane bound up to the longest range; a lane without draws in the block carries the threshold 0, which
+// no draw passes.
+//
+// Order.  rank_hits needs the candidates of one task in ascending draw order.  Candidates are pushed step by step, within a
+// step m by m, and within one m in lane order; for one task, (m, j) ascending is draw 8 m + j ascending.
+//
+// FP64 prefilter.  The high digit of draw j + 8 m is x2 = x * c_m mod M, i.e. M * frac(T) with T = x * c_m / M < 2^31.  One FMA
+// evaluates
+//     s = x * fl(c_m / M) + (1.5 * 2^32 + 4 u),   u = 2^-20 = ulp(s),
 // whose 20 low mantissa bits are  L = (frac(T) * 2^20 + e + 4) mod 2^20  with |e| < 1 (2^-22 from the rounded constant, 2^-21 from
-// the rounding of the FMA, in units of u = 2^-20 less than one unit together).  A draw with x2 <= amax has frac(T) * 2^20 in
-// (0, A], A = amax * 2^20 / M, hence L in [4, A + 5): it passes  L < ceil(A) + 6.  The test is a SUPERSET of the exact one
-// (a few thousand x2 values wide: ~0.4 % extra candidates at 5e-4 per row); every candidate's exact x2 is then computed with
-// the integer multiply and the exact threshold test runs in the resolve step, so the result is bit-identical.  Cost per 64 draws:
-// one v_fma_f64, one v_and, one v_cmp (the exact form needs a 10-instruction modular multiply per 64 draws), plus one uniform
-// 32-byte LDS read of the constants per 256 draws (broadcasting them from lanes with v_readlane measured 33 % slower).
-// gev_dbg_prefilter_sweep checks the bound exhaustively over all 2^31 - 2 engine states x 32 multipliers.
+// the rounding of the FMA, in units of u = 2^-20 less than one unit together; the bound holds for any multiplier below M).  A
+// draw with x2 <= amax has frac(T) * 2^20 in (0, A], A = amax * 2^20 / M, hence L in [4, A + 5): it passes  L < ceil(A) + 6.
+// The test is a SUPERSET of the exact one (a few thousand x2 values wide: ~0.4 % extra candidates at 5e-4 per row); every
+// candidate's exact x2 is then computed with the integer multiply and the exact threshold test runs in the resolve step, so the
+// result is bit-identical.  Cost per 64 draws: one v_fma_f64, one v_and, one v_cmp (the exact form needs a 10-instruction
+// modular multiply per 64 draws).  gev_dbg_prefilter_sweep checks the bound exhaustively over all 2^31 - 2 engine states x 256
+// multipliers.
 template <class Flush>
 __device__ __forceinline__ void scan_candidates(const SmpTabs* __restrict__ T, SmpWave* __restrict__ W, u32 engine_seed, u32 amax,
-                                                u32 first_row, u32 n_draws, u32 tag, u32& count, Flush&& flush)
+                                                u32 first_row, u32 n_draws, u32& count, Flush&& flush)
 {
-    const u32 lane = threadIdx.x & 63;
-    if (amax == 0) return;                                 // every row has probability 0: no draw can hit
-    const u32 s0 = minstd_seed(engine_seed);
-    u32 x = mulmod31(T->pow_even[lane], s0);               // exact high digit (engine output 2 lane + 2) of draw `lane`
+    const u32 lane = threadIdx.x & 63, g = lane >> 3, j = lane & 7u;
+    if (amax == 0) n_draws = 0;                            // every row has probability 0: no draw can hit
+    u32 n_max = 0;                                         // the longest scan of the eight
+#pragma unroll
+    for (u32 q = 0; q < SB_TASKS; q++) n_max = max(n_max, rl_u32(n_draws, q * 8u));
+    if (n_max == 0) return;
+    u32 x = mulmod31(T->pow_even[j], minstd_seed(engine_seed));   // exact high digit (engine output 2 j + 2) of draw j
     const double A = (double)amax * (1048576.0 / 2147483647.0);
     const bool all_cand = A + 8.0 >= 1048576.0;            // thresholds near 1: every draw is a candidate
     const u32 thr20 = all_cand ? 0xffffffffu : (u32)A + 7u;   // >= ceil(A) + 6
     const double C = 6442450944.0 + 4.0 / 1048576.0;       // 1.5 * 2^32 + 4 u
-    for (u32 base = 0; base < n_draws; base += 64 * SB_J) {
-        const u32 n_here = min(64u * SB_J, n_draws - base);
-        const u32 jfull = n_here >> 6, jn = (n_here + 63u) >> 6;   // full groups of 64 draws / groups incl. a partial last one
+    for (u32 base = 0; base < n_max; base += SB_BLK) {
+        const u32 n_here = n_draws > base ? min((u32)SB_BLK, n_draws - base) : 0u;   // draws of the lane's task in this block
+        const u32 cnt = n_here > j ? (n_here - j + 7u) >> 3 : 0u;                    // ... of which the lane owns m < cnt
+        const u32 thr = cnt ? thr20 : 0u;
+        u32 n_lo = SB_BLK, n_hi = 0;                       // shortest non-empty and longest range of the eight tasks
+#pragma unroll
+        for (u32 q = 0; q < SB_TASKS; q++) { const u32 nq = rl_u32(n_here, q * 8u); n_hi = max(n_hi, nq); if (nq) n_lo = min(n_lo, nq); }
+        const u32 m_all = n_lo >= 8u ? n_lo >> 3 : 1u;     // every lane with cnt != 0 has cnt >= m_all (its smallest: lane min(7, n_lo - 1))
+        const u32 m_end = (n_hi + 7u) >> 3;                // the largest cnt (lane 0 of the longest task)
         const double xd = (double)x;
-        auto testk = [&](double k) -> bool { return ((u32)__double2loint(__fma_rn(xd, k, C)) & 0xfffffu) < thr20; };
-        auto push = [&](unsigned long long m, bool c, u32 j) {
+        const u32 row0 = first_row + base + j;
+        auto testk = [&](double k) -> bool { return ((u32)__double2loint(__fma_rn(xd, k, C)) & 0xfffffu) < thr; };
+        auto push = [&](unsigned long long mk, bool c, u32 m) {
             if (c) {
-                const u32 idx = count + mbcnt64(m);
-                W->cand_row[idx] = first_row + base + 64u * j + lane;
-                W->cand_x2[idx] = mulmod31(x, T->ci[j]);  // the exact high digit of this draw
-                W->cand_tag[idx] = (uint8_t)tag;
+                const u32 idx = count + mbcnt64(mk);
+                W->cand_row[idx] = row0 + 8u * m;
+                W->cand_x2[idx] = mulmod31(x, T->ci[m]);  // the exact high digit of this draw
+                W->cand_tag[idx] = (uint8_t)g;
             }
-            count += (u32)__popcll(m);
+            count += (u32)__popcll(mk);
         };
-        // four groups (256 draws) per step; the constants c_j / M of a step are one uniform 32-byte LDS read
-        u32 j = 0;
-        for (; j + 4 <= jfull; j += 4) {                   // full groups: no bounds to check
-            const double4 kk = *reinterpret_cast<const double4*>(&T->kd[j]);
-            const bool c0 = testk(kk.x), c1 = testk(kk.y), c2 = testk(kk.z), c3 = testk(kk.w);
+        // four m (32 draws of every task) per step; a step tests with the constants c_m / M in `k` and loads the next step's
+        // into `kn` first (two register sets that take turns, so that nothing is copied)
+        auto step = [&](u32 m, const double4& k, double4& kn, const bool bounded) {
+            kn = *reinterpret_cast<const double4*>(&T->kd[m + 4]);
+            const bool c0 = (!bounded || m < cnt) && testk(k.x), c1 = (!bounded || m + 1 < cnt) && testk(k.y),
+                       c2 = (!bounded || m + 2 < cnt) && testk(k.z), c3 = (!bounded || m + 3 < cnt) && testk(k.w);
             const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1), m2 = __ballot(c2), m3 = __ballot(c3);
             if (m0 | m1 | m2 | m3) {
-                push(m0, c0, j); push(m1, c1, j + 1); push(m2, c2, j + 2); push(m3, c3, j + 3);
+                push(m0, c0, m); push(m1, c1, m + 1); push(m2, c2, m + 2); push(m3, c3, m + 3);
                 if (count >= 64) flush();
             }
-        }
-        for (; j < jn; j++) {                              // the last (up to three full + one partial) groups of the block
-            const bool c0 = 64u * j + lane < n_here && testk(T->kd[j]);
-            const unsigned long long m0 = __ballot(c0);
-            if (m0) { push(m0, c0, j); if (count >= 64) flush(); }
-        }
-        if (base + 64 * SB_J < n_draws) x = mulmod31(x, T->pow_blk);
+        };
+        double4 ka = *reinterpret_cast<const double4*>(&T->kd[0]), kb;
+        u32 m = 0;
+        for (; m + 8 <= m_all; m += 8) { step(m, ka, kb, false); step(m + 4, kb, ka, false); }   // every lane in range (or empty): no bounds to check
+        for (; m < m_end; m += 4) { step(m, ka, kb, true); ka = kb; }                            // the ends of the ranges
+        if (base + SB_BLK < n_max) x = mulmod31(x, T->pow_blk);
     }
 }
 
@@ -243,11 +277,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) k
                 count = 0;
                 wave_fence();
             };
-#pragma unroll 1
-            for (u32 q = 0; q < SB_TASKS; q++) {
-                if (b * SB_TASKS + q >= n_tasks) break;
-                const ChrDev& C = chrs[rl_u32(cidx, q * 8u)];
-                if (C.M >= 2) scan_candidates(T, W, rl_u32(S, q * 8u) + 2u, C.m_amax, 1u, C.M - 1u, q, count, resolve);   // generator_u(seed+2), i = 1..M-1
+            {
+                const ChrDev& C = chrs[cidx];
+                const u32 M = valid ? C.M : 0u;
+                scan_candidates(T, W, S + 2u, C.m_amax, 1u, M >= 2 ? M - 1u : 0u, count, resolve);   // generator_u(seed+2), i = 1..M-1
             }
             if (count) resolve();
             const u32 n = hc;
@@ -271,6 +304,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) k
             const bool rvalid = pass ? tr < n_tasks : g == 0;
             const u32 rc = rvalid ? (u32)(tr % (size_t)nchr) : 0u;
             const bool active = rvalid && chrs[rc].active != 0;       // inactive: another context owns this chromosome (only the seed chain is needed)
+            const u32 R = chrs[rc].R, r_amax = chrs[rc].r_amax;       // the map of both gametes' scans
             const u32 seed_pat = pass ? seed_next : seed0;
             const bool late = pass && slow_mut;
             u32 seed_cur = seed_pat, xout = 0, hc = 0, count = 0, side = 0;
@@ -301,12 +335,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) k
             auto phase = [&]() {                           // ras_sim_loc_rec for the current gamete of every task that is still on the fast path
                 xout = srand8(T, W->r, seed_cur);          // srand(seed), :2977
                 hc = 0; count = 0;
-#pragma unroll 1
-                for (u32 q = 0; q < SB_TASKS; q++) {
-                    if (!rl_u32((u32)run, q * 8u)) continue;
-                    const ChrDev& C = chrs[rl_u32(rc, q * 8u)];
-                    scan_candidates(T, W, rl_u32(seed_cur, q * 8u) + 1u, C.r_amax, 0u, C.R, q, count, resolve);   // generator(seed+1), :2978
-                }
+                scan_candidates(T, W, seed_cur + 1u, r_amax, 0u, run ? R : 0u, count, resolve);   // generator(seed+1), :2978
                 if (count) resolve();
             };
             // paternal gamete (:2447-2449)
