@@ -17,6 +17,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gev_kernels.h"
@@ -75,37 +76,66 @@ static Graveyard g_graveyard;                 // one host thread calls the seam 
 
 static const size_t GRAVEYARD_LIMIT = (size_t)16 << 30;
 
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept { p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
-    int ensure(size_t need, hipStream_t st, bool keep = false, double slack = 1.0)
+// the one allocator under Dev<T>::ensure: p / bytes = the buffer and its size, need = the bytes asked for
+static int dev_grow(void*& p, size_t& bytes, size_t need, hipStream_t st, bool keep, double slack)
+{
+    size_t want = std::max<size_t>((size_t)(need * slack), 256);
+    void* q = nullptr;
+    const double tm0 = host_ms();
+    hipError_t e = hipMalloc(&q, want);
+    g_malloc_ms += host_ms() - tm0; g_malloc_n++; g_malloc_bytes += want;
+    if (e != hipSuccess && g_graveyard.bytes) {                      // out of memory with parked buffers: release them and retry
+        (void)hipGetLastError();
+        int d = 0; (void)hipGetDevice(&d); g_graveyard.drain(d, false);
+        e = hipMalloc(&q, want);
+    }
+    if (e != hipSuccess && want > need) { (void)hipGetLastError(); want = std::max<size_t>(need, 256); e = hipMalloc(&q, want); }
+    if (e != hipSuccess) return fail(GEV_EDEVICE, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
+    if (p) {
+        if (keep && bytes) { HIPC(hipMemcpyAsync(q, p, bytes, hipMemcpyDeviceToDevice, st)); }
+        g_graveyard.park(p, bytes);        // the old buffer may still be in use on either stream
+        if (g_graveyard.bytes > GRAVEYARD_LIMIT) { int d = 0; (void)hipGetDevice(&d); g_graveyard.drain(d, false); }
+    }
+    p = q; bytes = want;
+    return GEV_OK;
+}
+// A device allocation of elements of type T that only grows.  ensure() takes ELEMENTS; a launch or a work-table entry takes the buffer
+// itself (it converts to T*, and buf + n is pointer arithmetic on T); bytes() is for the hipMemset / hipMemcpy calls that need the size.
+// DevBytes (= Dev<uint8_t>) is sized in bytes and alone has as<U>().  It is for the buffers whose content has no one element type:
+//   pool, panel       genotype rows of unit_bytes() / stride bytes: kernels read them as bytes, u32 or u64 words
+//   d_snpmajor        SNP-major bit rows: u64 words, unsigned long long for the transpose's atomics, u32 halves in k_materialize_tile
+//   d_stage, d_tmp, d_text, d_map   scratch of whichever call uses them (rows, ranks, text, maps with their offsets)
+//   d_flag            flag words of several calls: u32 flags, or one 64-bit counter
+//   d_bp_cnt          per-row counts of a bit-plane product: u64[n] then u32[n] twice (pair counts), u32 triples (LD, trait sums)
+//   d_ld_score        u64[n] sums, then u32[n] counts
+//   d_gef_stat        GEF_WORDS u32 status words, then {mean, var} as doubles
+//   ph.res            u32 result words, then {mean, var} pairs as doubles
+//   d_lpc_tmp         an arena compaction's copy of the entries in use: LpPart or u64 (lp_compact_arena)
+//   am.sort_tmp       scratch of gev_sort_pairs, which gives its size in bytes
+// A buffer of several arrays of one type is typed and its parts are buf + offset (d_snpcnt, d_ld_win, d_sel, d_cnt).
+template <class T> struct Dev {
+    T* p = nullptr;
+    ~Dev() { if (p) (void)hipFree(p); }
+    Dev() = default;
+    Dev(const Dev&) = delete; Dev& operator=(const Dev&) = delete;
+    Dev(Dev&& o) noexcept { p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    operator T*() const { return p; }
+    size_t bytes() const { return cap; }                     // of the allocation
+    size_t capacity() const { return cap / sizeof(T); }      // elements that fit
+    int ensure(size_t count, hipStream_t st, bool keep = false, double slack = 1.0)
     {
-        if (need <= bytes && p) return GEV_OK;
-        size_t want = std::max<size_t>((size_t)(need * slack), 256);
-        void* q = nullptr;
-        const double tm0 = host_ms();
-        hipError_t e = hipMalloc(&q, want);
-        g_malloc_ms += host_ms() - tm0; g_malloc_n++; g_malloc_bytes += want;
-        if (e != hipSuccess && g_graveyard.bytes) {                      // out of memory with parked buffers: release them and retry
-            (void)hipGetLastError();
-            int d = 0; (void)hipGetDevice(&d); g_graveyard.drain(d, false);
-            e = hipMalloc(&q, want);
-        }
-        if (e != hipSuccess && want > need) { (void)hipGetLastError(); want = std::max<size_t>(need, 256); e = hipMalloc(&q, want); }
-        if (e != hipSuccess) return fail(GEV_EDEVICE, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-        if (p) {
-            if (keep && bytes) { HIPC(hipMemcpyAsync(q, p, bytes, hipMemcpyDeviceToDevice, st)); }
-            g_graveyard.park(p, bytes);        // the old buffer may still be in use on either stream
-            if (g_graveyard.bytes > GRAVEYARD_LIMIT) { int d = 0; (void)hipGetDevice(&d); g_graveyard.drain(d, false); }
-        }
-        p = q; bytes = want;
+        if (count > SIZE_MAX / sizeof(T)) return fail(GEV_EINVAL, "device buffer of %zu elements of %zu bytes: the size overflows", count, sizeof(T));
+        if (count * sizeof(T) <= cap && p) return GEV_OK;
+        void* q = p;
+        GEVC(dev_grow(q, cap, count * sizeof(T), st, keep, slack));
+        p = (T*)q;
         return GEV_OK;
     }
-    template <class T> T* as() const { return (T*)p; }
+    template <class U, class B = T> typename std::enable_if<std::is_same<B, uint8_t>::value, U*>::type as() const { return (U*)p; }
+private:
+    size_t cap = 0;                                          // bytes
 };
+typedef Dev<uint8_t> DevBytes;
 // Pinned host memory that only grows.  Asynchronous copies from or into the old buffer may be in flight when it is replaced: the
 // caller names the stream that carries them (nullptr: the whole device) and the size of the new buffer
 struct PinnedBuf {
@@ -129,7 +159,7 @@ struct ChrStatic {                       // one population x one chromosome
     std::vector<u64> rbp; std::vector<double> rprob; u64 bp_dist = 0;
     std::vector<u64> mbp; std::vector<double> mrate; bool mut_set = false;
     std::vector<u64> pos;                // Legend.pos
-    DevBuf d_rthr, d_rbp, d_mthr, d_mbp, d_pos, d_coarse;
+    Dev<GevThr> d_rthr, d_mthr; Dev<u64> d_rbp, d_mbp, d_pos; Dev<u32> d_coarse;
     size_t L = 0, stride = 0;            // bytes of a whole genotype row in flat (host-side / staging) layouts, multiple of 128
     u32 nseg = 1, seg_shift = 9;         // the device keeps a row as nseg segments of 2^seg_shift 16-byte chunks (gev_kernels.h, PoolWork)
     size_t unit_bytes() const { return (size_t)16 << seg_shift; }
@@ -137,13 +167,13 @@ struct ChrStatic {                       // one population x one chromosome
     u32 idx_lo = 0, idx_hi = 0;          // loci inside [bp0, bp_end)
     u32 r_amax = 0, m_amax = 0;
     size_t founder_rows = 0;
-    DevBuf panel; size_t panel_rows = 0; // read-only founder panel of this ROOT population, flat rows of `stride` bytes (gev_*_founder_panel): immigrants' rows are rebuilt from it
+    DevBytes panel; size_t panel_rows = 0; // read-only founder panel of this ROOT population, flat rows of `stride` bytes (gev_*_founder_panel): immigrants' rows are rebuilt from it
 };
 struct CvStatic {                        // one population x phenotype x chromosome
     std::vector<u64> bp; std::vector<double> a, d; double vd = 0; bool set = false;
     std::vector<u32> col_of_icv;         // file index -> column in the sorted CV plane
     std::vector<u32> icv_of_col;
-    DevBuf d_pos_sorted, d_pos_file, d_col_of_icv, d_icv_of_col, d_a, d_d, d_frq, d_counts, d_partial, d_aptr, d_dptr, d_tab;
+    Dev<u64> d_pos_sorted, d_pos_file; Dev<u32> d_col_of_icv, d_icv_of_col, d_counts; Dev<double> d_a, d_d, d_frq, d_tab; Dev<uint16_t> d_partial; Dev<const double*> d_aptr, d_dptr;
     u32 C = 0, sub_w32 = 0, stride_w32 = 0;
     u32 idx_lo = 0, idx_hi = 0;
     size_t founder_rows = 0;
@@ -154,7 +184,7 @@ struct ChrState {
     // genotype rows: one pool of 4 * cap_people rows (two generations' worth); slot s of the current generation is pool row
     // phys[pcur][s] (gev_kernels.h, PoolWork).  phys has THREE buffers: the stitch of generation g (stream_big) still reads
     // phys of g-1 and g while the small work of g+1 writes the next one.
-    DevBuf pool, phys[3], live, freel, pctr, items[2]; u32 pool_stamp = 0;
+    DevBytes pool; Dev<u32> phys[3], live, freel, pctr; Dev<StitchItem> items[2]; u32 pool_stamp = 0;
     // the free list of the pool is rebuilt (mark + collect) only when it runs low: valid = built for the current table lineage,
     // n_free / cursor = its length and how much of it has been handed out (from the last generation's status block)
     bool pool_list_valid = false, pool_force_rebuild = false; u32 pool_n_free = 0, pool_cursor = 0, pool_last_taken = 0;
@@ -163,11 +193,11 @@ struct ChrState {
     //   pieces (gev_lists.h): what Simulation::reproduce reads and writes -- per-range pieces shared between parent and offspring
     //   CSR (moff/mpos, poff/parts of buffer P.cur): what everything else reads (downloads, output, migration, plane-less assembly)
     // csr_valid / lp.valid say which of them describe the current generation (at least one does).
-    DevBuf moff[2], mpos[2], poff[2], parts[2];
+    Dev<u32> moff[2], poff[2]; Dev<u64> mpos[2]; Dev<gev_part> parts[2];
     size_t mut_total[2] = {0, 0}, parts_total[2] = {0, 0};   // list sizes of the two CSR buffers
     bool csr_valid = true;
     struct LpState {
-        DevBuf ptab[2], mtab[2], parena, marena, ctr, items;        // tables [P.cur] = current generation; ctr: {interval entries, mutation entries appended by an import, overflow flags}
+        Dev<uint2> ptab[2], mtab[2]; Dev<LpPart> parena; Dev<u64> marena; Dev<u32> ctr, items;      // tables [P.cur] = current generation; ctr: {interval entries, mutation entries appended by an import, overflow flags}
         u32 p_used = 0, m_used = 0;                          // arena cursors (entries)
         u32 p_last = 0, m_last = 0;                          // what the last generation appended
         u32 nseg = 0, lgw = 0;
@@ -179,9 +209,9 @@ struct PopState {
     std::vector<ChrStatic> cs;                         // [chr]
     std::vector<std::vector<CvStatic>> cv;             // [phen][chr]
     std::vector<ChrState> st;                          // [chr]
-    std::vector<std::vector<std::array<DevBuf, 2>>> cvp; // [phen][chr][2]
-    DevBuf d_chrdev;
-    DevBuf d_sex[2];                                   // Human::sex of the individuals (1 male, 2 female), physical row order, [cur]: what Simulation::random_mate reads (gev_random_mate)
+    std::vector<std::vector<std::array<Dev<u32>, 2>>> cvp; // [phen][chr][2]
+    Dev<ChrDev> d_chrdev;
+    Dev<uint8_t> d_sex[2];                                 // Human::sex of the individuals (1 male, 2 female), physical row order, [cur]: what Simulation::random_mate reads (gev_random_mate)
     int cur = 0, pcur = 0;                             // current buffer of the double-buffered lists / of phys[3]
     size_t n_people = 0, cap_people = 0;
     // After a cross-GPU migration the individuals of the current generation are not moved physically:
@@ -197,7 +227,7 @@ struct PopState {
     // gev_compute_selection: phenotypes of the current generation (gev_scale_ad_compute_gef writes column p; phen_ok[p] = written since the
     // individuals last changed) and Human::mating_value / selection_value / selection_value_func, [3][n_people] (sel_ok = computed since
     // then); [sbuf] is current, gev_migrate gathers into the other one.  d_sv0 = {_gen0_SV_mean, _gen0_SV_var} (sv0_ok: known)
-    DevBuf d_phen[2], d_sel[2], d_sv0;
+    Dev<double> d_phen[2], d_sel[2], d_sv0;
     int sbuf = 0;
     std::vector<uint8_t> phen_ok;
     bool sel_ok = false, sv0_ok = false;
@@ -205,7 +235,7 @@ struct PopState {
     // gev_set_track_pedigree: the seven ID fields of the current generation (gev_pedigree.h), planes of ids_stride[ibuf] rows indexed by
     // PHYSICAL row; [ibuf] is current, a generation in flight / gev_migrate / a materialised order write the other one.  ids_ok: they
     // describe the current individuals (dropped by gev_remove_rows / gev_import_rows, restored by gev_upload_pedigree)
-    DevBuf d_ids[2]; size_t ids_stride[2] = {0, 0};
+    Dev<int64_t> d_ids[2]; size_t ids_stride[2] = {0, 0};
     int ibuf = 0;
     bool ids_ok = false;
     // gev_generation_phenotypes (gev_phenotypes.h).  d_cidx[ibuf]: the couple index of every child of the generation just published,
@@ -213,7 +243,7 @@ struct PopState {
     // effect of Simulation::reproduce is drawn from.  d_comp[cbuf]: [nphen][7][n_people] A D G C E F P of the current individuals
     // (comp_ok; they follow gev_migrate).  d_prev: the saved record [nphen][2][prev_n] (phen, parental_effect).  ad0: host copies of
     // _var_a_gen0 / _var_d_gen0 per phenotype
-    DevBuf d_cidx[2], d_comp[2], d_prev;
+    Dev<u32> d_cidx[2]; Dev<double> d_comp[2], d_prev;
     int cbuf = 0;
     bool cs_ok = false, comp_ok = false, prev_ok = false, ad0_ok = false;
     u32 cs_seed = 0; size_t cs_ncouples = 0, prev_n = 0;
@@ -230,12 +260,13 @@ struct gev_ctx {
     bool track_intervals = true;
     bool track_pedigree = false;            // gev_set_track_pedigree
     std::vector<PopState> pop;
-    DevBuf d_tables;
+    Dev<GevRngTables> d_tables;
     // per-generation scratch: two sets, because the dense stitch of generation g (stream_big) still reads set g%2
     // while sampling / sparse state of generation g+1 (stream) fill the other one
     struct Scratch {
-        DevBuf father, mother, mutseeds, globvals /* [2 + T] ras_glob_seed() values drawn on the device: mate seed, reproduce seed, mutation seeds */, seed_pat, seed_mat, k, bk_off, bk, bk_idx, start, nmut, nm_off, nm_pos, nm_side, sex, status, chrwork, cvwork,
-               globblk /* rejection counts of this set's ras_glob_seed() draws (enqueue_glob) */;
+        Dev<u32> father, mother, mutseeds, globvals /* [2 + T] ras_glob_seed() values drawn on the device: mate seed, reproduce seed, mutation seeds */, seed_pat, seed_mat, k, bk_off, bk_idx, nmut, nm_off, status,
+                 globblk /* rejection counts of this set's ras_glob_seed() draws (enqueue_glob) */;
+        Dev<u64> bk, nm_pos; Dev<uint8_t> start, nm_side, sex; Dev<ChrWork> chrwork; Dev<CvWork> cvwork;
         std::vector<uint8_t> chrwork_shadow, cvwork_shadow;     // what the device copies of the tables hold (upload_table_cached)
         unsigned n_chrwork = 0, n_cvwork = 0; float sampling_ms_saved = -1;
         size_t nseg_max = 1, cv_used_max = 0, lp_entries_per_row = 0; u32 cv_max = 0;     // launch shapes of the generation (enqueue_tables)
@@ -254,14 +285,14 @@ struct gev_ctx {
         struct HeadStart { enum Kind { NONE, PRESAMPLE, CHAIN } kind = NONE; bool dropped = false, has_mut = false; int pop = -1; size_t n_people = 0; u32 seed = 0 /* seed_reproduce (PRESAMPLE) */; } hs;
         // gev_random_mate: father / mother of this set hold the couples of the next gev_reproduce (couples == NULL) of mate_pop
         bool mated = false, mate_assort = false; int mate_pop = -1; size_t mate_n = 0; unsigned long long mate_epoch = 0;
-        DevBuf cidx;                // gev_set_track_pedigree: the couple index of every child of a couples list the host passed
+        Dev<u32> cidx;              // gev_set_track_pedigree: the couple index of every child of a couples list the host passed
         hipEvent_t ev_chain = nullptr, ev_tab = nullptr;
     } sc[2];
     unsigned gen_counter = 0;
     std::vector<uint8_t> chr_active;        // 0: chromosome held by another context (gev_set_chr_active); sampling chain only
     bool any_inactive = false;
     bool migrant_rows = true;               // false (gev_set_migrant_rows): gev_export_rows packs no genotype rows, gev_import_rows rebuilds them from the founder panels
-    DevBuf d_poff, d_prange;                      // rebuild of immigrants' rows: PanelRef per root population, offsets of the rows' parts in the payload
+    Dev<u32> d_poff; Dev<uint2> d_prange;                  // rebuild of immigrants' rows: PanelRef per root population, offsets of the rows' parts in the payload
     bool dense = true;                      // false: no resident genotype planes (gev_set_dense_state); lists + CV planes only, output by gev_materialize
     hipStream_t stream_big = nullptr;
     bool planes_pending = false;            // a stitch may still be writing the current planes (stream_big)
@@ -301,43 +332,44 @@ struct gev_ctx {
                           bool fused = false /* gev_generation_begin: seeds and couples are made on the device */, has_svf = false, pool_rebuilt = false; const double* d_svf = nullptr; /* with has_svf: what the mating reads */ u32 glob_state = 0; u32* hseeds2 = nullptr; uint8_t* hsex = nullptr;
                           bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0;
                           int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
-    DevBuf d_snpmajor, d_text;
-    DevBuf d_snpcnt;               // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
+    DevBytes d_snpmajor, d_text;
+    Dev<u32> d_snpcnt;             // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
     int n_cu = 0;                  // compute units of the device (bitprod_launch: the tile size), asked for by the first call
     int dbg_bp_tiles = 0;          // gev_dbg_bitprod_tiles: 0 = the tile size by compute units, 1 = always 64 x 64, 2 = always 128 x 128
     unsigned long long bp_launches[2] = {0, 0};   // product launches on small / large tiles over the context's life (bitprod_launch)
-    DevBuf d_bp_a, d_bp_b, d_bp_cnt, d_bp_out;   // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
-    DevBuf d_pair_w, d_ld_win, d_ld_score;       // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
-    DevBuf d_ts_trait, d_ts_b, d_ts_acc, d_ts_out;   // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
+    Dev<u64> d_bp_a, d_bp_b; DevBytes d_bp_cnt; Dev<u32> d_bp_out; // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
+    Dev<u32> d_pair_w, d_ld_win; DevBytes d_ld_score; // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
+    Dev<int32_t> d_ts_trait, d_ts_acc; Dev<uint4> d_ts_b; Dev<long long> d_ts_out; // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
-    DevBuf d_mflag, d_mblk, d_posm, d_posf, d_pickblk, d_couples, d_svf, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat;   // gev_random_mate / gev_glob_seeds scratch
-    DevBuf d_gef_io, d_gef_stat;                 // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
+    Dev<uint8_t> d_mflag; Dev<u32> d_mblk, d_posm, d_posf, d_pickblk, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat; Dev<gev_couple> d_couples; Dev<double> d_svf; // gev_random_mate / gev_glob_seeds scratch
+    Dev<double> d_gef_io; DevBytes d_gef_stat; // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
     // gev_assort_mate (gev_assort.h): scratch, the last call's result and couple arrays, test knobs
     struct AssortState {
-        DevBuf stats, wlo, ww, ends, start, cm, cf, om, of, males, females, rnd, scnt, soff, sfill, stgt, ssrc, kept, sorted_m, sorted_f,
-               tblk, t1, t2, i1, i2, pm, pf, inb, num, ocnt, ooff, pois, ped, mv, svf, stat, sort_tmp;
+        Dev<u32> wlo, ww, ends, start, cm, cf, om, of, males, females, rnd, scnt, soff, sfill, stgt, ssrc, kept, sorted_m, sorted_f,
+                 tblk, i1, i2, pm, pf, inb, ocnt, ooff, pois, stat;
+        Dev<double2> stats; Dev<double> t1, t2, mv, svf; Dev<int32_t> num; Dev<int64_t> ped; DevBytes sort_tmp;
         gev_assort_result res = {0, 0, 0, 0, 0};
         bool valid = false;                               // res / pm / pf / inb / num describe the last call
         bool narrow_window = false, short_poisson = false;
         unsigned long long n_chunks = 0, n_direct = 0, pois_reruns = 0;
     } am;
-    DevBuf d_cvdone;
+    Dev<u32> d_cvdone;
     // gev_format_info_text / gev_dbg_format_g (gev_fmt_g.h): created by the first call, nothing before it
-    struct FmtState { DevBuf tables, lens, bsum, boff, x, cnt; bool ready = false; } fm;
+    struct FmtState { Dev<GevFmtTables> tables; Dev<u32> lens, bsum; Dev<u64> boff; Dev<double> x; Dev<unsigned long long> cnt; bool ready = false; } fm;
     // gev_format_interval_text (gev_fmt_int.h, k_int_rows).  host[p]: the founder names of root population p as gev_set_founder_names
     // left them; everything on the device (the names' arenas and offset tables, d_names = IntNames[n_pop]) is created by the first
     // formatting call, nothing before it
     struct IntState {
         struct Names { std::vector<unsigned char> bytes; std::vector<u32> offs; bool set = false; };
         std::vector<Names> host;
-        std::vector<DevBuf> d_bytes, d_offs;
-        DevBuf d_names, lens, bsum, boff, flag, ids;
+        std::vector<Dev<unsigned char>> d_bytes; std::vector<Dev<u32>> d_offs;
+        Dev<IntNames> d_names; Dev<uint8_t> lens; Dev<u32> bsum, flag; Dev<u64> boff; Dev<int64_t> ids;
         bool uploaded = false;
     } iv;
     // gev_generation_phenotypes (gev_phenotypes.h): scratch, the call whose result block is on its way, test knob.  streams / blk /
     // partial are also the scratch of ph_streams / ph_var under gev_scale_ad_compute_gef and gev_compute_selection (one stream)
     struct PhenoState {
-        DevBuf res /* result words, then {mean, var} pairs: e, the components, raw A and D */, starts, partial, eraw, cval, streams, tasks, blk, globblk, shift;
+        DevBytes res /* result words, then {mean, var} pairs: e, the components, raw A and D */; Dev<u32> starts, blk, globblk; Dev<double> partial, eraw, cval, shift; Dev<NrmStream> streams; Dev<PhTask> tasks;
         PinnedBuf h_res;
         hipEvent_t ev = nullptr;
         bool pending = false; int pop = -1; unsigned long long epoch = 0;
@@ -347,25 +379,25 @@ struct gev_ctx {
         bool short_candidates = false;                     // test hook: start far too short
         unsigned long long reruns = 0;
     } ph;
-    DevBuf d_cnt, d_sums, d_map, d_cvm, d_addchr, d_domchr, d_add, d_dom, d_flag, d_stage, d_thr32, d_tmp;
+    DevBytes d_map, d_flag, d_stage, d_tmp; Dev<u32> d_cnt, d_sums, d_cvm, d_thr32; Dev<double> d_addchr, d_domchr, d_add, d_dom;
     // per-generation work tables (gev_kernels.h: ChrWork / CvWork / AdWork) are written into a ring of pinned host memory and
     // copied to the device on the stream that uses them
     PinnedBuf h_ring; size_t h_ring_off = 0;
-    DevBuf d_adwork2[2]; std::vector<uint8_t> adwork_shadow[2];
-    DevBuf d_lpc_bits, d_lpc_cnt, d_lpc_wpre, d_lpc_len, d_lpc_old, d_lpc_new, d_lpc_tmp;     // scratch of an arena compaction (lp_compact)
-    DevBuf d_lp_nitems;                                 // [nchr] length of each chromosome's work list of list pieces to build
+    Dev<AdWork> d_adwork2[2]; std::vector<uint8_t> adwork_shadow[2];
+    Dev<u32> d_lpc_bits, d_lpc_cnt, d_lpc_wpre, d_lpc_len, d_lpc_old, d_lpc_new; DevBytes d_lpc_tmp;   // scratch of an arena compaction (lp_compact)
+    Dev<u32> d_lp_nitems;                            // [nchr] length of each chromosome's work list of list pieces to build
     std::map<double, GevThr> thr_cache;
 };
 typedef gev_ctx::Scratch::HeadStart HeadStart;
 
 // ------------------------------------------------------------------------------------------
-static int scan_u32_on(hipStream_t st, DevBuf& sums, const u32* in, size_t n, u32* out /*n+1*/)
+static int scan_u32_on(hipStream_t st, Dev<u32>& sums, const u32* in, size_t n, u32* out /*n+1*/)
 {
     const size_t nb = ceil_div(n + 1, SCAN_ITEMS);
-    GEVC(sums.ensure(nb * sizeof(u32), st));
-    hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(256), 0, st, in, n, sums.as<u32>());
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, sums.as<u32>(), nb);
-    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(256), 0, st, in, n, sums.as<u32>(), out);
+    GEVC(sums.ensure(nb, st));
+    hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(256), 0, st, in, n, sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, sums, nb);
+    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(256), 0, st, in, n, sums, out);
     KCHECK();
     return GEV_OK;
 }
@@ -378,10 +410,10 @@ static int scan_u32(gev_ctx* c, const u32* in, size_t n, u32* out /*n+1*/, u32* 
     }
     return GEV_OK;
 }
-static int h2d(gev_ctx* c, DevBuf& b, const void* src, size_t bytes)
+template <class T> static int h2d(gev_ctx* c, Dev<T>& b, const void* src, size_t count)
 {
-    GEVC(b.ensure(std::max<size_t>(bytes, 16), c->stream));
-    if (bytes) HIPC(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+    GEVC(b.ensure(std::max<size_t>(count, 1), c->stream));
+    if (count) HIPC(hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
     HIPC(hipStreamSynchronize(c->stream));          // src may be a caller-owned temporary
     return GEV_OK;
 }
@@ -506,7 +538,7 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
         P.phen_ok.assign(nphen, 0);
     }
     GevRngTables T; gev_build_rng_tables(T);
-    GEVC(h2d(c.get(), c->d_tables, &T, sizeof T));
+    GEVC(h2d(c.get(), c->d_tables, &T, 1));
     if (const char* e = getenv("GEV_OVERLAP")) c->serialize = atoi(e) == 0;
     if (const char* e = getenv("GEV_SAMPLE_BATCHED")) c->sample_batched = atoi(e) != 0;
     if (const char* e = getenv("GEV_CHAIN_WG")) c->chain_wg = atoi(e) != 0;
@@ -559,8 +591,8 @@ int gev_set_rmap(gev_ctx* c, int pop, int chr, const u64* bp, const double* prob
     GEVC(make_thresholds(c, S.rprob, thr));
     S.r_amax = 0; for (const GevThr& t : thr) S.r_amax = std::max(S.r_amax, t.a_hi);
     HIPC(hipSetDevice(c->device));
-    GEVC(h2d(c, S.d_rthr, thr.data(), R * sizeof(GevThr)));
-    GEVC(h2d(c, S.d_rbp, bp, R * sizeof(u64)));
+    GEVC(h2d(c, S.d_rthr, thr.data(), R));
+    GEVC(h2d(c, S.d_rbp, bp, R));
     c->pop[pop].finalized = false;
     return GEV_OK;
 }
@@ -579,8 +611,8 @@ int gev_set_mutmap(gev_ctx* c, int pop, int chr, const u64* bp, const double* ra
     GEVC(make_thresholds(c, S.mrate, thr));
     S.m_amax = 0; for (size_t i = 1; i < M; i++) S.m_amax = std::max(S.m_amax, thr[i].a_hi);
     HIPC(hipSetDevice(c->device));
-    GEVC(h2d(c, S.d_mthr, thr.data(), M * sizeof(GevThr)));
-    GEVC(h2d(c, S.d_mbp, bp, M * sizeof(u64)));
+    GEVC(h2d(c, S.d_mthr, thr.data(), M));
+    GEVC(h2d(c, S.d_mbp, bp, M));
     c->pop[pop].finalized = false;
     return GEV_OK;
 }
@@ -600,7 +632,7 @@ int gev_set_snps(gev_ctx* c, int pop, int chr, const u64* pos, size_t L)
     while (S.seg_shift > 0 && ((size_t)1 << (S.seg_shift - 1)) >= S.stride / 16) S.seg_shift--;     // a row shorter than a segment: the smallest power-of-two unit that holds it
     S.nseg = (u32)ceil_div(S.stride / 16, (size_t)1 << S.seg_shift);
     HIPC(hipSetDevice(c->device));
-    GEVC(h2d(c, S.d_pos, pos, L * sizeof(u64)));
+    GEVC(h2d(c, S.d_pos, pos, L));
     c->pop[pop].finalized = false;
     return GEV_OK;
 }
@@ -631,14 +663,14 @@ int gev_set_cvs(gev_ctx* c, int pop, int phen, int chr, const u64* bp, const dou
     V.sub_w32 = (u32)std::max<size_t>(ceil_div(C, 32), 1);
     V.stride_w32 = (u32)round_up((size_t)V.sub_w32 * (1 + c->rp_bits), 4);      // sub-rows: resolved alleles, root-population bits
     HIPC(hipSetDevice(c->device));
-    GEVC(h2d(c, V.d_pos_sorted, sorted.data(), C * sizeof(u64)));
-    GEVC(h2d(c, V.d_pos_file, V.bp.data(), C * sizeof(u64)));
-    GEVC(h2d(c, V.d_col_of_icv, V.col_of_icv.data(), C * sizeof(u32)));
-    GEVC(h2d(c, V.d_icv_of_col, V.icv_of_col.data(), C * sizeof(u32)));
-    GEVC(h2d(c, V.d_a, a, C * sizeof(double)));
-    GEVC(h2d(c, V.d_d, d, C * sizeof(double)));
-    GEVC(V.d_frq.ensure(std::max<size_t>(C, 1) * sizeof(double), c->stream));
-    GEVC(V.d_counts.ensure(std::max<size_t>(C, 1) * sizeof(u32), c->stream));
+    GEVC(h2d(c, V.d_pos_sorted, sorted.data(), C));
+    GEVC(h2d(c, V.d_pos_file, V.bp.data(), C));
+    GEVC(h2d(c, V.d_col_of_icv, V.col_of_icv.data(), C));
+    GEVC(h2d(c, V.d_icv_of_col, V.icv_of_col.data(), C));
+    GEVC(h2d(c, V.d_a, a, C));
+    GEVC(h2d(c, V.d_d, d, C));
+    GEVC(V.d_frq.ensure(std::max<size_t>(C, 1), c->stream));
+    GEVC(V.d_counts.ensure(std::max<size_t>(C, 1), c->stream));
     HIPC(hipMemsetAsync(V.d_counts.p, 0, std::max<size_t>(C, 1) * sizeof(u32), c->stream));     // k_cv_count adds into them, k_cv_table / k_cv_freq consume and clear them
     V.frq_valid = false;
     c->ad_cached_pop = c->ad_host_set_pop = -1;
@@ -653,11 +685,11 @@ static PoolWork pool_work(const gev_ctx* c, PopState& P, int chr, int alt)
     ChrState& cs = P.st[chr];
     PoolWork pw{};
     const ChrStatic& S = P.cs[chr];
-    pw.pool = cs.pool.as<uint8_t>(); pw.phys_cur = cs.phys[P.pcur].as<u32>(); pw.phys_alt = cs.phys[alt].as<u32>();
-    pw.live = cs.live.as<u32>(); pw.freel = cs.freel.as<u32>(); pw.pctr = cs.pctr.as<u32>();
+    pw.pool = cs.pool.as<uint8_t>(); pw.phys_cur = cs.phys[P.pcur]; pw.phys_alt = cs.phys[alt];
+    pw.live = cs.live; pw.freel = cs.freel; pw.pctr = cs.pctr;
     pw.nseg = S.nseg; pw.seg_shift = S.seg_shift;
     pw.pool_units = (u32)(4 * P.cap_people * S.nseg); pw.alias = c->alias_rows ? 1u : 0u;
-    pw.items = cs.items[P.cur ^ 1].as<StitchItem>(); pw.items_cap = (u32)(2 * P.cap_people * S.nseg);
+    pw.items = cs.items[P.cur ^ 1]; pw.items_cap = (u32)(2 * P.cap_people * S.nseg);
     pw.stamp = cs.pool_stamp;                             // (pool_new_stamp before a rebuild of the free list)
     return pw;
 }
@@ -666,7 +698,7 @@ static void pool_new_stamp(ChrState& cs) { if (++cs.pool_stamp == 0) cs.pool_sta
 static RowMap row_map(const PopState& P, int chr)
 {
     const ChrStatic& S = P.cs[chr]; const ChrState& cs = P.st[chr];
-    return RowMap{cs.pool.as<uint8_t>(), cs.phys[P.pcur].as<u32>(), S.nseg, S.seg_shift};
+    return RowMap{cs.pool.as<uint8_t>(), cs.phys[P.pcur], S.nseg, S.seg_shift};
 }
 static RowRef pool_rows(const PopState& P, int chr, const u32* table)
 {
@@ -714,21 +746,21 @@ static int ensure_capacity(gev_ctx* c, int pop, size_t people)
             ChrState& cs = P.st[k];
             const size_t units = rows * P.cs[k].nseg;                                          // per generation
             GEVC(cs.pool.ensure(2 * units * P.cs[k].unit_bytes(), c->stream, /*keep=*/true));   // unit numbers stay valid: the pool grows at its end
-            for (int b = 0; b < 3; b++) GEVC(cs.phys[b].ensure(units * sizeof(u32), c->stream, b == P.pcur));
-            for (int b = 0; b < 2; b++) GEVC(cs.items[b].ensure((units + 1) * sizeof(StitchItem), c->stream));
-            GEVC(cs.live.ensure(2 * units * sizeof(u32), c->stream)); GEVC(cs.freel.ensure(2 * units * sizeof(u32), c->stream));
-            HIPC(hipMemsetAsync(cs.live.p, 0, cs.live.bytes, c->stream)); cs.pool_stamp = 0;   // marks are generation stamps: start from a clean buffer
-            GEVC(cs.pctr.ensure(8 * sizeof(u32), c->stream));
+            for (int b = 0; b < 3; b++) GEVC(cs.phys[b].ensure(units, c->stream, b == P.pcur));
+            for (int b = 0; b < 2; b++) GEVC(cs.items[b].ensure((units + 1), c->stream));
+            GEVC(cs.live.ensure(2 * units, c->stream)); GEVC(cs.freel.ensure(2 * units, c->stream));
+            HIPC(hipMemsetAsync(cs.live.p, 0, cs.live.bytes(), c->stream)); cs.pool_stamp = 0;   // marks are generation stamps: start from a clean buffer
+            GEVC(cs.pctr.ensure(8, c->stream));
             cs.pool_list_valid = false;                                                         // the pool grew: its new units are in no free list yet
         }
         for (int b = 0; b < 2; b++) {
-            GEVC(P.st[k].moff[b].ensure((rows + 1) * sizeof(u32), c->stream, b == P.cur));
-            GEVC(P.st[k].poff[b].ensure((rows + 1) * sizeof(u32), c->stream, b == P.cur));
+            GEVC(P.st[k].moff[b].ensure((rows + 1), c->stream, b == P.cur));
+            GEVC(P.st[k].poff[b].ensure((rows + 1), c->stream, b == P.cur));
         }
         for (int p = 0; p < c->nphen; p++) {
             if (!P.cv[p][k].set) return fail(GEV_ESTATE, "set_cvs must precede allocation (pop %d phen %d chr %d)", pop, p, k);
             for (int b = 0; b < 2; b++)
-                GEVC(P.cvp[p][k][b].ensure(rows * P.cv[p][k].stride_w32 * sizeof(u32), c->stream, b == P.cur));
+                GEVC(P.cvp[p][k][b].ensure(rows * P.cv[p][k].stride_w32, c->stream, b == P.cur));
         }
     }
     for (int b = 0; b < 2; b++) GEVC(P.d_sex[b].ensure(people, c->stream, b == P.cur));
@@ -804,11 +836,11 @@ int gev_synth_founders(gev_ctx* c, int pop, int chr, size_t nhap, u64 seed)
     GEVC(gev_sync(c));
     GEVC(P.st[chr].pool.ensure(nhap * S.pitch(), c->stream));
     HIPC(hipMemsetAsync(P.st[chr].pool.p, 0, nhap * S.pitch(), c->stream));
-    GEVC(c->d_thr32.ensure(S.L * sizeof(u32), c->stream));
-    hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(S.L, 256)), dim3(256), 0, c->stream, c->d_thr32.as<u32>(), S.L, seed);
+    GEVC(c->d_thr32.ensure(S.L, c->stream));
+    hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(S.L, 256)), dim3(256), 0, c->stream, c->d_thr32, S.L, seed);
     const size_t words = ceil_div(S.L, 64);
     hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)ceil_div(nhap * words, 256)), dim3(256), 0, c->stream,
-                       P.st[chr].pool.as<u64>(), S.pitch() / 8, nhap, S.L, c->d_thr32.as<u32>(), seed);
+                       P.st[chr].pool.as<u64>(), S.pitch() / 8, nhap, S.L, c->d_thr32, seed);
     KCHECK();
     HIPC(hipStreamSynchronize(c->stream));
     S.founder_rows = nhap; P.gen0 = false;
@@ -852,10 +884,10 @@ int gev_synth_founder_panel(gev_ctx* c, int pop, int chr, size_t nhap, u64 seed)
 {
     GEVC(panel_prepare(c, pop, chr, nhap, "synth_founder_panel"));
     ChrStatic& S = c->pop[pop].cs[chr];
-    GEVC(c->d_thr32.ensure(S.L * sizeof(u32), c->stream));
-    hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(S.L, 256)), dim3(256), 0, c->stream, c->d_thr32.as<u32>(), S.L, seed);
+    GEVC(c->d_thr32.ensure(S.L, c->stream));
+    hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(S.L, 256)), dim3(256), 0, c->stream, c->d_thr32, S.L, seed);
     hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)ceil_div(nhap * ceil_div(S.L, 64), 256)), dim3(256), 0, c->stream,
-                       S.panel.as<u64>(), S.stride / 8, nhap, S.L, c->d_thr32.as<u32>(), seed);      // the same generator as gev_synth_founders
+                       S.panel.as<u64>(), S.stride / 8, nhap, S.L, c->d_thr32, seed);      // the same generator as gev_synth_founders
     KCHECK();
     HIPC(hipStreamSynchronize(c->stream));
     S.panel_rows = nhap;
@@ -874,12 +906,12 @@ int gev_set_migrant_rows(gev_ctx* c, int on)
 static int cv_founders_from_tmp(gev_ctx* c, int pop, int phen, int chr, size_t nhap, size_t tmp_w32)
 {
     PopState& P = c->pop[pop]; CvStatic& V = P.cv[phen][chr];
-    GEVC(P.cvp[phen][chr][P.cur].ensure(nhap * V.stride_w32 * sizeof(u32), c->stream));
+    GEVC(P.cvp[phen][chr][P.cur].ensure(nhap * V.stride_w32, c->stream));
     HIPC(hipMemsetAsync(P.cvp[phen][chr][P.cur].p, 0, nhap * V.stride_w32 * sizeof(u32), c->stream));
     if (V.C) {
         hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)ceil_div(nhap * V.sub_w32, 256)), dim3(256), 0, c->stream,
-                           c->d_tmp.as<u32>(), tmp_w32, P.cvp[phen][chr][P.cur].as<u32>(), (size_t)V.stride_w32, V.sub_w32,
-                           V.d_icv_of_col.as<u32>(), V.C, nhap);
+                           c->d_tmp.as<u32>(), tmp_w32, P.cvp[phen][chr][P.cur], (size_t)V.stride_w32, V.sub_w32,
+                           V.d_icv_of_col, V.C, nhap);
         KCHECK();
     }
     HIPC(hipStreamSynchronize(c->stream));
@@ -907,12 +939,12 @@ int gev_synth_cv_founders(gev_ctx* c, int pop, int phen, int chr, size_t nhap, u
     HIPC(hipSetDevice(c->device));
     const size_t w64 = std::max<size_t>(ceil_div(V.C, 64), 1);
     GEVC(c->d_tmp.ensure(nhap * w64 * 8, c->stream));
-    GEVC(c->d_thr32.ensure(std::max<size_t>(V.C, 1) * sizeof(u32), c->stream));
+    GEVC(c->d_thr32.ensure(std::max<size_t>(V.C, 1), c->stream));
     HIPC(hipMemsetAsync(c->d_tmp.p, 0, nhap * w64 * 8, c->stream));
     if (V.C) {
-        hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(V.C, 256)), dim3(256), 0, c->stream, c->d_thr32.as<u32>(), (size_t)V.C, seed);
+        hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(V.C, 256)), dim3(256), 0, c->stream, c->d_thr32, (size_t)V.C, seed);
         hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)ceil_div(nhap * w64, 256)), dim3(256), 0, c->stream,
-                           c->d_tmp.as<u64>(), w64, nhap, (size_t)V.C, c->d_thr32.as<u32>(), seed);
+                           c->d_tmp.as<u64>(), w64, nhap, (size_t)V.C, c->d_thr32, seed);
         KCHECK();
     }
     return cv_founders_from_tmp(c, pop, phen, chr, nhap, w64 * 2);
@@ -947,11 +979,11 @@ static int finalize_static(gev_ctx* c, int pop)
                 while (at < S.L && S.pos[at] < x) at++;
                 coarse[j] = (u32)at;
             }
-            GEVC(h2d(c, S.d_coarse, coarse.data(), coarse.size() * sizeof(u32)));
+            GEVC(h2d(c, S.d_coarse, coarse.data(), coarse.size()));
         }
-        cd[k] = ChrDev{S.d_rthr.as<GevThr>(), S.d_rbp.as<u64>(), S.d_mthr.as<GevThr>(), S.d_mbp.as<u64>(), S.bp_dist, bp0, bpe,
-                       (u32)S.rbp.size(), (u32)S.mbp.size(), S.r_amax, S.m_amax, S.d_pos.as<u64>(), (u32)S.L, (u32)c->chr_active[k],
-                       S.d_coarse.as<u32>(), cbase, cshift, cn};
+        cd[k] = ChrDev{S.d_rthr, S.d_rbp, S.d_mthr, S.d_mbp, S.bp_dist, bp0, bpe,
+                       (u32)S.rbp.size(), (u32)S.mbp.size(), S.r_amax, S.m_amax, S.d_pos, (u32)S.L, (u32)c->chr_active[k],
+                       S.d_coarse, cbase, cshift, cn};
         for (int p = 0; p < c->nphen; p++) {
             CvStatic& V = P.cv[p][k];
             if (!V.set) continue;
@@ -961,7 +993,7 @@ static int finalize_static(gev_ctx* c, int pop)
             V.idx_hi = (u32)(std::lower_bound(sorted.begin(), sorted.end(), bpe) - sorted.begin());
         }
     }
-    GEVC(h2d(c, P.d_chrdev, cd.data(), cd.size() * sizeof(ChrDev)));
+    GEVC(h2d(c, P.d_chrdev, cd.data(), cd.size()));
     P.finalized = true;
     return GEV_OK;
 }
@@ -996,9 +1028,9 @@ static int check_multipop(gev_ctx* c)
         for (int p = 0; p < c->nphen; p++)
             for (int k = 0; k < c->nchr; k++) {
                 std::vector<const double*> ap(c->n_pop), dp(c->n_pop);
-                for (int r = 0; r < c->n_pop; r++) { ap[r] = c->pop[r].cv[p][k].d_a.as<double>(); dp[r] = c->pop[r].cv[p][k].d_d.as<double>(); }
-                GEVC(h2d(c, c->pop[pop].cv[p][k].d_aptr, ap.data(), ap.size() * sizeof(double*)));
-                GEVC(h2d(c, c->pop[pop].cv[p][k].d_dptr, dp.data(), dp.size() * sizeof(double*)));
+                for (int r = 0; r < c->n_pop; r++) { ap[r] = c->pop[r].cv[p][k].d_a; dp[r] = c->pop[r].cv[p][k].d_d; }
+                GEVC(h2d(c, c->pop[pop].cv[p][k].d_aptr, ap.data(), ap.size()));
+                GEVC(h2d(c, c->pop[pop].cv[p][k].d_dptr, dp.data(), dp.size()));
             }
     c->multipop_ready = true;
     return GEV_OK;
@@ -1028,30 +1060,30 @@ int gev_init_gen0(gev_ctx* c, int pop, size_t n_people, uint32_t seed_gen0, uint
         if (c->dense) {                                  // founder haplotype r is pool row r
             hipLaunchKernelGGL(k_mask_rows, dim3((unsigned)ceil_div(rows * (S.pitch() / 4), 256)), dim3(256), 0, c->stream,
                                st.pool.as<u32>(), S.pitch() / 4, rows, S.idx_lo, S.idx_hi);
-            hipLaunchKernelGGL(k_iota_u32, dim3((unsigned)ceil_div(rows * S.nseg, 256)), dim3(256), 0, c->stream, st.phys[P.pcur].as<u32>(), rows * S.nseg);
+            hipLaunchKernelGGL(k_iota_u32, dim3((unsigned)ceil_div(rows * S.nseg, 256)), dim3(256), 0, c->stream, st.phys[P.pcur], rows * S.nseg);
         }
         HIPC(hipMemsetAsync(st.moff[P.cur].p, 0, (rows + 1) * sizeof(u32), c->stream));
-        GEVC(st.parts[P.cur].ensure(rows * sizeof(gev_part), c->stream));
+        GEVC(st.parts[P.cur].ensure(rows, c->stream));
         hipLaunchKernelGGL(k_init_parts, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, c->stream,
-                           st.parts[P.cur].as<gev_part>(), st.poff[P.cur].as<u32>(), rows, S.rbp.front(), S.rbp.back(), pop);
+                           st.parts[P.cur], st.poff[P.cur], rows, S.rbp.front(), S.rbp.back(), pop);
         for (int p = 0; p < c->nphen; p++) {
             CvStatic& V = P.cv[p][k];
             hipLaunchKernelGGL(k_mask_rows, dim3((unsigned)ceil_div(rows * V.stride_w32, 256)), dim3(256), 0, c->stream,
-                               P.cvp[p][k][P.cur].as<u32>(), (size_t)V.stride_w32, rows, V.idx_lo, V.idx_hi);
+                               P.cvp[p][k][P.cur], (size_t)V.stride_w32, rows, V.idx_lo, V.idx_hi);
             // k_mask_rows zeroed the (still empty) root-population sub-rows too; write them now
             if (c->rp_bits)
                 hipLaunchKernelGGL(k_fill_rp, dim3((unsigned)ceil_div(rows * V.sub_w32 * c->rp_bits, 256)), dim3(256), 0, c->stream,
-                                   P.cvp[p][k][P.cur].as<u32>(), (size_t)V.stride_w32, V.sub_w32, c->rp_bits, (u32)pop, rows);
+                                   P.cvp[p][k][P.cur], (size_t)V.stride_w32, V.sub_w32, c->rp_bits, (u32)pop, rows);
             V.frq_valid = false;
         }
     }
-    hipLaunchKernelGGL(k_sex_sequence, dim3(1), dim3(64), 0, c->stream, c->d_tables.as<GevRngTables>(), (u32)seed_gen0, n_people, P.d_sex[P.cur].as<uint8_t>());
+    hipLaunchKernelGGL(k_sex_sequence, dim3(1), dim3(64), 0, c->stream, c->d_tables, (u32)seed_gen0, n_people, P.d_sex[P.cur]);
     KCHECK();
     P.ids_ok = false;
     if (c->track_pedigree) {                                 // ID = ID_Father = ... = i (:3037-3043)
-        GEVC(P.d_ids[P.ibuf].ensure(PED_FIELDS * n_people * sizeof(int64_t), c->stream));
+        GEVC(P.d_ids[P.ibuf].ensure(PED_FIELDS * n_people, c->stream));
         P.ids_stride[P.ibuf] = n_people;
-        hipLaunchKernelGGL(k_ped_gen0, dim3((unsigned)ceil_div(n_people, 256)), dim3(256), 0, c->stream, P.d_ids[P.ibuf].as<int64_t>(), n_people, n_people);
+        hipLaunchKernelGGL(k_ped_gen0, dim3((unsigned)ceil_div(n_people, 256)), dim3(256), 0, c->stream, P.d_ids[P.ibuf], n_people, n_people);
         KCHECK();
         P.ids_ok = true;
     }
@@ -1123,11 +1155,12 @@ static int harvest_timing(gev_ctx* c, gev_ctx::Scratch& sc)
 // asynchronous copy has run: a slot is reused only after a wrap, which waits for the stream)
 // ... unless the device copy already holds exactly these bytes (the tables of a scratch set repeat from generation to generation
 // as long as no buffer moved): `shadow` = host copy of what was uploaded last
-static int upload_table_cached(gev_ctx* c, DevBuf& dst, std::vector<uint8_t>& shadow, const void* src, size_t bytes, hipStream_t st);
-static int upload_table(gev_ctx* c, DevBuf& dst, const void* src, size_t bytes, hipStream_t st)
+extern "C++" {      // (templates cannot have the C linkage of the block this file's functions sit in)
+template <class T> static int upload_table(gev_ctx* c, Dev<T>& dst, const void* src, size_t count, hipStream_t st)
 {
-    GEVC(dst.ensure(std::max<size_t>(bytes, 16), st));
-    if (!bytes) return GEV_OK;
+    GEVC(dst.ensure(std::max<size_t>(count, 1), st));
+    if (!count) return GEV_OK;
+    const size_t bytes = count * sizeof(T);
     const size_t need = round_up(bytes, 64);
     if (c->h_ring.bytes < 4 * need) {
         GEVC(c->h_ring.ensure(4 * need, std::max<size_t>(8 * need, c->table_ring_min), st));
@@ -1140,24 +1173,26 @@ static int upload_table(gev_ctx* c, DevBuf& dst, const void* src, size_t bytes, 
     c->h_ring_off += need;
     return GEV_OK;
 }
-static int upload_table_cached(gev_ctx* c, DevBuf& dst, std::vector<uint8_t>& shadow, const void* src, size_t bytes, hipStream_t st)
+template <class T> static int upload_table_cached(gev_ctx* c, Dev<T>& dst, std::vector<uint8_t>& shadow, const void* src, size_t count, hipStream_t st)
 {
+    const size_t bytes = count * sizeof(T);
     if (dst.p && shadow.size() == bytes && bytes && memcmp(shadow.data(), src, bytes) == 0) return GEV_OK;
-    GEVC(upload_table(c, dst, src, bytes, st));
+    GEVC(upload_table(c, dst, src, count, st));
     shadow.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
     return GEV_OK;
 }
+}   // extern "C++"
 static SampleDev make_sd(gev_ctx* c, gev_ctx::Scratch& sc, size_t T)
 {
     SampleDev sd;
-    sd.seed_pat = sc.seed_pat.as<u32>(); sd.seed_mat = sc.seed_mat.as<u32>(); sd.k = sc.k.as<u32>();
-    sd.bk_off = sc.bk_off.as<u32>(); sd.bk = sc.bk.as<u64>(); sd.bk_idx = sc.bk_idx.as<u32>(); sd.start = sc.start.as<uint8_t>();
-    sd.nmut = sc.nmut.as<u32>(); sd.nm_off = sc.nm_off.as<u32>(); sd.nm_pos = sc.nm_pos.as<u64>();
-    sd.nm_side = sc.nm_side.as<uint8_t>(); sd.sex = sc.sex.as<uint8_t>();
-    sd.father = sc.father.as<u32>(); sd.mother = sc.mother.as<u32>();
+    sd.seed_pat = sc.seed_pat; sd.seed_mat = sc.seed_mat; sd.k = sc.k;
+    sd.bk_off = sc.bk_off; sd.bk = sc.bk; sd.bk_idx = sc.bk_idx; sd.start = sc.start;
+    sd.nmut = sc.nmut; sd.nm_off = sc.nm_off; sd.nm_pos = sc.nm_pos;
+    sd.nm_side = sc.nm_side; sd.sex = sc.sex;
+    sd.father = sc.father; sd.mother = sc.mother;
     sd.bk_ovf_base = (u32)(2 * T * GEV_BK_CAP); sd.bk_ovf_cap = (u32)c->bk_ovf_cap;
     sd.nm_ovf_base = (u32)(T * GEV_NM_CAP); sd.nm_ovf_cap = (u32)c->nm_ovf_cap;
-    sd.status = sc.status.as<u32>();
+    sd.status = sc.status;
     return sd;
 }
 // per-generation scratch every phase needs (sizes depend on n_people only)
@@ -1166,14 +1201,14 @@ static int ensure_scratch(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, boo
     hipStream_t st = c->stream;
     const size_t T = n_people * (size_t)c->nchr;
     const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)c->nchr;
-    GEVC(sc.father.ensure(n_people * sizeof(u32), st)); GEVC(sc.mother.ensure(n_people * sizeof(u32), st));
-    GEVC(sc.seed_pat.ensure((T + 1) * sizeof(u32), st)); GEVC(sc.seed_mat.ensure(T * sizeof(u32), st));
-    GEVC(sc.k.ensure(2 * T * sizeof(u32), st)); GEVC(sc.bk_off.ensure((2 * T + 1) * sizeof(u32), st));
+    GEVC(sc.father.ensure(n_people, st)); GEVC(sc.mother.ensure(n_people, st));
+    GEVC(sc.seed_pat.ensure((T + 1), st)); GEVC(sc.seed_mat.ensure(T, st));
+    GEVC(sc.k.ensure(2 * T, st)); GEVC(sc.bk_off.ensure((2 * T + 1), st));
     GEVC(sc.start.ensure(2 * T, st)); GEVC(sc.sex.ensure(n_people, st));
-    GEVC(sc.nmut.ensure(T * sizeof(u32), st)); GEVC(sc.nm_off.ensure((T + 1) * sizeof(u32), st));
-    GEVC(sc.nm_pos.ensure(16, st)); GEVC(sc.nm_side.ensure(16, st));
-    GEVC(sc.status.ensure(n_status * sizeof(u32), st));
-    if (has_mut) { GEVC(sc.mutseeds.ensure(T * sizeof(u32), st)); }
+    GEVC(sc.nmut.ensure(T, st)); GEVC(sc.nm_off.ensure((T + 1), st));
+    GEVC(sc.nm_pos.ensure(2, st)); GEVC(sc.nm_side.ensure(16, st));
+    GEVC(sc.status.ensure(n_status, st));
+    if (has_mut) { GEVC(sc.mutseeds.ensure(T, st)); }
     return GEV_OK;
 }
 // Claim a scratch set for what `st` is about to write into it: the kernel times of the set's previous generation are collected
@@ -1211,17 +1246,17 @@ static int enqueue_sampling(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_
     PopState& P = c->pop[pop];
     const int nchr = c->nchr;
     const size_t T = n_people * (size_t)nchr;
-    const GevRngTables* Tb = c->d_tables.as<GevRngTables>();
-    const ChrDev* chrs = P.d_chrdev.as<ChrDev>();
+    const GevRngTables* Tb = c->d_tables;
+    const ChrDev* chrs = P.d_chrdev;
     const size_t bk_fixed = 2 * T * GEV_BK_CAP, nm_fixed = T * GEV_NM_CAP;
     if (bk_fixed + c->bk_ovf_cap >= 0xffffffffull || nm_fixed + c->nm_ovf_cap >= 0xffffffffull) return fail(GEV_EINVAL, "reproduce: breakpoint/mutation record space exceeds 32-bit offsets");
-    GEVC(sc.bk.ensure((bk_fixed + c->bk_ovf_cap) * sizeof(u64), st));
-    GEVC(sc.bk_idx.ensure((bk_fixed + c->bk_ovf_cap) * sizeof(u32), st));
-    if (has_mut) { GEVC(sc.nm_pos.ensure((nm_fixed + c->nm_ovf_cap) * sizeof(u64), st)); GEVC(sc.nm_side.ensure(nm_fixed + c->nm_ovf_cap, st)); }
+    GEVC(sc.bk.ensure((bk_fixed + c->bk_ovf_cap), st));
+    GEVC(sc.bk_idx.ensure((bk_fixed + c->bk_ovf_cap), st));
+    if (has_mut) { GEVC(sc.nm_pos.ensure((nm_fixed + c->nm_ovf_cap), st)); GEVC(sc.nm_side.ensure(nm_fixed + c->nm_ovf_cap, st)); }
     const size_t n_status = ST_TOTALS + ST_PER_CHR * (size_t)nchr;
     if (clear_status) HIPC(hipMemsetAsync(sc.status.p, 0, n_status * sizeof(u32), st));
     SampleDev sd = make_sd(c, sc, T);
-    const u32* mseeds = mut_seeds_dev ? mut_seeds_dev : sc.mutseeds.as<u32>();
+    const u32* mseeds = mut_seeds_dev ? mut_seeds_dev : sc.mutseeds;
 
     HIPC(hipEventRecord(sc.t[0], st));
     // ---- sampling: one map scan per gamete / per mutation task
@@ -1294,52 +1329,53 @@ static int lp_import_all(gev_ctx* c, PopState& P, int k, hipStream_t st)
     if (live_p >= 0xfffffff0u || live_m >= 0xfffffff0u) return fail(GEV_EDEVICE, "list pieces: more than 2^32 list entries on one chromosome");
     const size_t tab_rows = std::max<size_t>(rows, 2 * P.cap_people);
     for (int b = 0; b < 2; b++) {
-        if (track) GEVC(lp.ptab[b].ensure(tab_rows * lp.nseg * sizeof(uint2), st));
-        GEVC(lp.mtab[b].ensure(tab_rows * lp.nseg * sizeof(uint2), st));
+        if (track) GEVC(lp.ptab[b].ensure(tab_rows * lp.nseg, st));
+        GEVC(lp.mtab[b].ensure(tab_rows * lp.nseg, st));
     }
     int n_active = 0; for (int q = 0; q < c->nchr; q++) n_active += c->chr_active[q] ? 1 : 0;
-    if (track) GEVC(lp.parena.ensure(lp_arena_entries(rows, live_p, n_active, c->list_headroom == 0) * sizeof(LpPart), st));
-    GEVC(lp.marena.ensure(std::max<size_t>(lp_arena_entries(rows, live_m, n_active, c->list_headroom == 0), 16) * sizeof(u64), st));
-    GEVC(lp.ctr.ensure(4 * sizeof(u32), st));
+    if (track) GEVC(lp.parena.ensure(lp_arena_entries(rows, live_p, n_active, c->list_headroom == 0), st));
+    GEVC(lp.marena.ensure(std::max<size_t>(lp_arena_entries(rows, live_m, n_active, c->list_headroom == 0), 16), st));
+    GEVC(lp.ctr.ensure(4, st));
     HIPC(hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(u32), st));
     if (rows)
         hipLaunchKernelGGL(k_lp_import, dim3((unsigned)ceil_div(rows * LP_MAXSEG, 256)), dim3(256), 0, st,
-                           track ? cs.poff[P.cur].as<u32>() : (const u32*)nullptr, track ? cs.parts[P.cur].as<gev_part>() : (const gev_part*)nullptr,
-                           cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), (size_t)0, rows,
-                           track ? lp.ptab[P.cur].as<uint2>() : (uint2*)nullptr, lp.mtab[P.cur].as<uint2>(), lp.parena.as<LpPart>(), lp.marena.as<u64>(),
-                           0u, 0u, (u32)(lp.parena.bytes / sizeof(LpPart)), (u32)(lp.marena.bytes / sizeof(u64)), lp.nseg, lp.lgw, (u64)S.rbp.front(),
-                           lp.ctr.as<u32>(), lp.ctr.as<u32>() + 2);
+                           track ? cs.poff[P.cur] : (const u32*)nullptr, track ? cs.parts[P.cur] : (const gev_part*)nullptr,
+                           cs.moff[P.cur], cs.mpos[P.cur], (size_t)0, rows,
+                           track ? lp.ptab[P.cur] : (uint2*)nullptr, lp.mtab[P.cur], lp.parena, lp.marena,
+                           0u, 0u, (u32)(lp.parena.capacity()), (u32)(lp.marena.capacity()), lp.nseg, lp.lgw, (u64)S.rbp.front(),
+                           lp.ctr, lp.ctr + 2);
     KCHECK();
     u32 h[4] = {0, 0, 0, 0};
     HIPC(hipMemcpyAsync(h, lp.ctr.p, sizeof h, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
-    if (h[2]) return fail(GEV_EDEVICE, "list pieces: import overflowed its arena (internal error: %u of %zu interval, %u of %zu mutation entries)", h[0], lp.parena.bytes / sizeof(LpPart), h[1], lp.marena.bytes / sizeof(u64));
+    if (h[2]) return fail(GEV_EDEVICE, "list pieces: import overflowed its arena (internal error: %u of %zu interval, %u of %zu mutation entries)", h[0], lp.parena.capacity(), h[1], lp.marena.capacity());
     lp.p_used = h[0]; lp.m_used = h[1]; lp.p_last = 0; lp.m_last = 0; lp.valid = true; lp.grow_p = lp.grow_m = false; lp.imports++;
     return GEV_OK;
 }
 // one arena of the current generation's pieces compacted in place, sharing kept (gev_lists.h); *used = entries in use afterwards
-static int lp_compact_arena(gev_ctx* c, uint2* tab, size_t n_entries, u32 extra, DevBuf& arena, size_t elem_bytes, u32* used, hipStream_t st)
+extern "C++" template <class E> static int lp_compact_arena(gev_ctx* c, uint2* tab, size_t n_entries, u32 extra, Dev<E>& arena, u32* used, hipStream_t st)
 {
+    const size_t elem_bytes = sizeof(E);            // k_lpc_copy moves entries of either kind as 64-bit words
     const size_t n_words = ceil_div(std::max<size_t>(*used, 1), 32);
-    GEVC(c->d_lpc_bits.ensure(n_words * sizeof(u32), st)); GEVC(c->d_lpc_cnt.ensure((n_words + 1) * sizeof(u32), st)); GEVC(c->d_lpc_wpre.ensure((n_words + 1) * sizeof(u32), st));
+    GEVC(c->d_lpc_bits.ensure(n_words, st)); GEVC(c->d_lpc_cnt.ensure((n_words + 1), st)); GEVC(c->d_lpc_wpre.ensure((n_words + 1), st));
     HIPC(hipMemsetAsync(c->d_lpc_bits.p, 0, n_words * sizeof(u32), st));
     const unsigned eb = (unsigned)ceil_div(std::max<size_t>(n_entries, 1), 256);
-    hipLaunchKernelGGL(k_lpc_mark, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->d_lpc_bits.as<u32>());
-    hipLaunchKernelGGL(k_lpc_popc, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, st, c->d_lpc_bits.as<u32>(), n_words, c->d_lpc_cnt.as<u32>());
+    hipLaunchKernelGGL(k_lpc_mark, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->d_lpc_bits);
+    hipLaunchKernelGGL(k_lpc_popc, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, st, c->d_lpc_bits, n_words, c->d_lpc_cnt);
     KCHECK();
     u32 n_pieces = 0, total = 0;
-    GEVC(scan_u32(c, c->d_lpc_cnt.as<u32>(), n_words, c->d_lpc_wpre.as<u32>(), &n_pieces));
-    GEVC(c->d_lpc_len.ensure(((size_t)n_pieces + 1) * sizeof(u32), st)); GEVC(c->d_lpc_old.ensure(((size_t)n_pieces + 1) * sizeof(u32), st)); GEVC(c->d_lpc_new.ensure(((size_t)n_pieces + 2) * sizeof(u32), st));
-    hipLaunchKernelGGL(k_lpc_collect, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->d_lpc_bits.as<u32>(), c->d_lpc_wpre.as<u32>(), c->d_lpc_len.as<u32>(), c->d_lpc_old.as<u32>());
+    GEVC(scan_u32(c, c->d_lpc_cnt, n_words, c->d_lpc_wpre, &n_pieces));
+    GEVC(c->d_lpc_len.ensure(((size_t)n_pieces + 1), st)); GEVC(c->d_lpc_old.ensure(((size_t)n_pieces + 1), st)); GEVC(c->d_lpc_new.ensure(((size_t)n_pieces + 2), st));
+    hipLaunchKernelGGL(k_lpc_collect, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->d_lpc_bits, c->d_lpc_wpre, c->d_lpc_len, c->d_lpc_old);
     KCHECK();
-    GEVC(scan_u32(c, c->d_lpc_len.as<u32>(), n_pieces, c->d_lpc_new.as<u32>(), &total));
+    GEVC(scan_u32(c, c->d_lpc_len, n_pieces, c->d_lpc_new, &total));
     if (n_pieces) {
         GEVC(c->d_lpc_tmp.ensure(std::max<size_t>(total, 1) * elem_bytes, st));
-        hipLaunchKernelGGL(k_lpc_copy, dim3((unsigned)ceil_div(n_pieces, 256)), dim3(256), 0, st, (const u64*)arena.p, c->d_lpc_tmp.as<u64>(), c->d_lpc_len.as<u32>(), c->d_lpc_old.as<u32>(), c->d_lpc_new.as<u32>(), (size_t)n_pieces, (u32)(elem_bytes / 8));
+        hipLaunchKernelGGL(k_lpc_copy, dim3((unsigned)ceil_div(n_pieces, 256)), dim3(256), 0, st, (const u64*)arena.p, c->d_lpc_tmp.as<u64>(), c->d_lpc_len, c->d_lpc_old, c->d_lpc_new, (size_t)n_pieces, (u32)(elem_bytes / 8));
         KCHECK();
         HIPC(hipMemcpyAsync(arena.p, c->d_lpc_tmp.p, (size_t)total * elem_bytes, hipMemcpyDeviceToDevice, st));
     }
-    hipLaunchKernelGGL(k_lpc_rewrite, dim3(eb), dim3(256), 0, st, tab, n_entries, extra, c->d_lpc_bits.as<u32>(), c->d_lpc_wpre.as<u32>(), c->d_lpc_new.as<u32>());
+    hipLaunchKernelGGL(k_lpc_rewrite, dim3(eb), dim3(256), 0, st, tab, n_entries, extra, c->d_lpc_bits, c->d_lpc_wpre, c->d_lpc_new);
     KCHECK();
     *used = total;
     return GEV_OK;
@@ -1349,8 +1385,8 @@ static int lp_compact(gev_ctx* c, PopState& P, int k, hipStream_t st)
     ChrState::LpState& lp = P.st[k].lp;
     const size_t n_entries = 2 * P.n_phys * (size_t)lp.nseg;
     if (st != c->stream) HIPC(hipStreamSynchronize(st));
-    if (c->track_intervals) GEVC(lp_compact_arena(c, lp.ptab[P.cur].as<uint2>(), n_entries, 1u, lp.parena, sizeof(LpPart), &lp.p_used, c->stream));
-    GEVC(lp_compact_arena(c, lp.mtab[P.cur].as<uint2>(), n_entries, 0u, lp.marena, sizeof(u64), &lp.m_used, c->stream));
+    if (c->track_intervals) GEVC(lp_compact_arena(c, lp.ptab[P.cur], n_entries, 1u, lp.parena, &lp.p_used, c->stream));
+    GEVC(lp_compact_arena(c, lp.mtab[P.cur], n_entries, 0u, lp.marena, &lp.m_used, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     lp.compactions++;
     return GEV_OK;
@@ -1366,21 +1402,21 @@ static int ensure_csr(gev_ctx* c, int pop)
         if (!c->chr_active[k] || cs.csr_valid) continue;
         if (!lp.valid) return fail(GEV_ESTATE, "internal error: neither form of the sparse state is valid (pop %d chr %d)", pop, k);
         const bool track = c->track_intervals;
-        GEVC(cs.moff[P.cur].ensure((rows + 1) * sizeof(u32), st)); GEVC(cs.poff[P.cur].ensure((rows + 1) * sizeof(u32), st));
-        GEVC(c->d_cnt.ensure(2 * (rows + 1) * sizeof(u32), st));
-        u32* pcnt = c->d_cnt.as<u32>(); u32* mcnt = pcnt + rows + 1;
+        GEVC(cs.moff[P.cur].ensure((rows + 1), st)); GEVC(cs.poff[P.cur].ensure((rows + 1), st));
+        GEVC(c->d_cnt.ensure(2 * (rows + 1), st));
+        u32* pcnt = c->d_cnt; u32* mcnt = pcnt + rows + 1;
         const unsigned blocks = (unsigned)ceil_div(std::max<size_t>(rows, 1) * LP_MAXSEG, 256);
-        hipLaunchKernelGGL(k_lp_count, dim3(blocks), dim3(256), 0, st, track ? lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr, lp.mtab[P.cur].as<uint2>(), lp.nseg,
+        hipLaunchKernelGGL(k_lp_count, dim3(blocks), dim3(256), 0, st, track ? lp.ptab[P.cur] : (const uint2*)nullptr, lp.mtab[P.cur], lp.nseg,
                            (const u32*)nullptr, rows, track ? pcnt : (u32*)nullptr, mcnt);
         KCHECK();
         u32 tot_m = 0, tot_p = 0;
-        GEVC(scan_u32(c, mcnt, rows, cs.moff[P.cur].as<u32>(), &tot_m));
-        if (track) GEVC(scan_u32(c, pcnt, rows, cs.poff[P.cur].as<u32>(), &tot_p));
-        GEVC(cs.mpos[P.cur].ensure(std::max<size_t>(tot_m, 2) * sizeof(u64), st, false, 1.25));
-        if (track) GEVC(cs.parts[P.cur].ensure(std::max<size_t>(tot_p, 1) * sizeof(gev_part), st, false, 1.25));
-        hipLaunchKernelGGL(k_lp_fill, dim3(blocks), dim3(256), 0, st, track ? lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr, lp.mtab[P.cur].as<uint2>(),
-                           lp.parena.as<LpPart>(), lp.marena.as<u64>(), lp.nseg, (const u32*)nullptr, rows, (u64)P.cs[k].rbp.back(),
-                           cs.poff[P.cur].as<u32>(), cs.parts[P.cur].as<gev_part>(), cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>());
+        GEVC(scan_u32(c, mcnt, rows, cs.moff[P.cur], &tot_m));
+        if (track) GEVC(scan_u32(c, pcnt, rows, cs.poff[P.cur], &tot_p));
+        GEVC(cs.mpos[P.cur].ensure(std::max<size_t>(tot_m, 2), st, false, 1.25));
+        if (track) GEVC(cs.parts[P.cur].ensure(std::max<size_t>(tot_p, 1), st, false, 1.25));
+        hipLaunchKernelGGL(k_lp_fill, dim3(blocks), dim3(256), 0, st, track ? lp.ptab[P.cur] : (const uint2*)nullptr, lp.mtab[P.cur],
+                           lp.parena, lp.marena, lp.nseg, (const u32*)nullptr, rows, (u64)P.cs[k].rbp.back(),
+                           cs.poff[P.cur], cs.parts[P.cur], cs.moff[P.cur], cs.mpos[P.cur]);
         KCHECK();
         HIPC(hipStreamSynchronize(st));
         cs.mut_total[P.cur] = tot_m; cs.parts_total[P.cur] = track ? tot_p : 0; cs.csr_valid = true;
@@ -1429,8 +1465,8 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
         size_t need_p = lp.grow_p ? (size_t)lp.p_last * 5 / 4 + 1024 : 0, need_m = lp.grow_m ? (size_t)lp.m_last * 5 / 4 + 1024 : 0;
         if (lp.valid && !tight) {
             const size_t want_p = c->track_intervals ? std::max(need_p, guess_p) : 0, want_m = std::max(need_m, guess_m);
-            const bool full_p = c->track_intervals && lp.p_used + want_p > lp.parena.bytes / sizeof(LpPart);
-            const bool full_m = lp.m_used + want_m > lp.marena.bytes / sizeof(u64);
+            const bool full_p = c->track_intervals && lp.p_used + want_p > lp.parena.capacity();
+            const bool full_m = lp.m_used + want_m > lp.marena.capacity();
             if (full_p || full_m) {                           // drop the pieces nobody names any more; should that not make room, the arena grows below
                 GEVC(lp_compact(c, P, k, st));
                 need_p = want_p; need_m = want_m;
@@ -1440,35 +1476,35 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
             GEVC(lp_import_all(c, P, k, st));
             if (!tight) { need_p = c->track_intervals ? guess_p : 0; need_m = guess_m; }     // ... or a fresh import has to leave room for this generation
         }
-        if (need_p && lp.p_used + need_p > lp.parena.bytes / sizeof(LpPart))
-            GEVC(lp.parena.ensure(std::min<size_t>(lp.p_used + need_p, 0xfffffff0u) * sizeof(LpPart), st, /*keep=*/true, tight ? 1.0 : 1.5));
-        if (need_m && lp.m_used + need_m > lp.marena.bytes / sizeof(u64))
-            GEVC(lp.marena.ensure(std::min<size_t>(lp.m_used + need_m, 0xfffffff0u) * sizeof(u64), st, /*keep=*/true, tight ? 1.0 : 1.5));
+        if (need_p && lp.p_used + need_p > lp.parena.capacity())
+            GEVC(lp.parena.ensure(std::min<size_t>(lp.p_used + need_p, 0xfffffff0u), st, /*keep=*/true, tight ? 1.0 : 1.5));
+        if (need_m && lp.m_used + need_m > lp.marena.capacity())
+            GEVC(lp.marena.ensure(std::min<size_t>(lp.m_used + need_m, 0xfffffff0u), st, /*keep=*/true, tight ? 1.0 : 1.5));
         lp.grow_p = lp.grow_m = false;
-        const size_t tab_bytes = std::max<size_t>(rows, rows_cur) * lp.nseg * sizeof(uint2);
-        if (c->track_intervals) { GEVC(lp.ptab[alt].ensure(tab_bytes, st)); }
-        GEVC(lp.mtab[alt].ensure(tab_bytes, st));
+        const size_t tab_entries = std::max<size_t>(rows, rows_cur) * lp.nseg;
+        if (c->track_intervals) { GEVC(lp.ptab[alt].ensure(tab_entries, st)); }
+        GEVC(lp.mtab[alt].ensure(tab_entries, st));
         ChrWork w{};
-        w.lp.ptab_cur = lp.ptab[cur].as<uint2>(); w.lp.ptab_alt = lp.ptab[alt].as<uint2>(); w.lp.mtab_cur = lp.mtab[cur].as<uint2>(); w.lp.mtab_alt = lp.mtab[alt].as<uint2>();
-        w.lp.parena = lp.parena.as<LpPart>(); w.lp.marena = lp.marena.as<u64>();
+        w.lp.ptab_cur = lp.ptab[cur]; w.lp.ptab_alt = lp.ptab[alt]; w.lp.mtab_cur = lp.mtab[cur]; w.lp.mtab_alt = lp.mtab[alt];
+        w.lp.parena = lp.parena; w.lp.marena = lp.marena;
         w.lp.pbase = lp.p_used; w.lp.mbase = lp.m_used;
-        w.lp.pcap = (u32)std::min<size_t>(lp.parena.bytes / sizeof(LpPart), 0xfffffff0u); w.lp.mcap = (u32)std::min<size_t>(lp.marena.bytes / sizeof(u64), 0xfffffff0u);
+        w.lp.pcap = (u32)std::min<size_t>(lp.parena.capacity(), 0xfffffff0u); w.lp.mcap = (u32)std::min<size_t>(lp.marena.capacity(), 0xfffffff0u);
         w.lp.nseg = lp.nseg; w.lp.lgw = lp.lgw; w.lp.track = c->track_intervals ? 1u : 0u;
-        GEVC(lp.items.ensure(rows * LP_MAXSEG * sizeof(u32), st));
-        GEVC(c->d_lp_nitems.ensure((size_t)nchr * sizeof(u32), st));
-        w.lp.items = lp.items.as<u32>(); w.lp.n_items = c->d_lp_nitems.as<u32>() + k;
+        GEVC(lp.items.ensure(rows * LP_MAXSEG, st));
+        GEVC(c->d_lp_nitems.ensure((size_t)nchr, st));
+        w.lp.items = lp.items; w.lp.n_items = c->d_lp_nitems + k;
         w.bp0 = S.rbp.front(); w.bp_end = S.rbp.back(); w.chr = k;
         if (c->dense) {
-            w.pw = pool_work(c, P, k, (P.pcur + 1) % 3); w.snp_pos = S.d_pos.as<u64>();
+            w.pw = pool_work(c, P, k, (P.pcur + 1) % 3); w.snp_pos = S.d_pos;
             w.stride = S.stride; w.chunks = (u32)(S.stride / 16); w.L = (u32)S.L;
         }
         cw.push_back(w);
         for (int p = 0; p < c->nphen; p++) {
             CvStatic& V = P.cv[p][k];
-            GEVC(V.d_partial.ensure(ceil_div(rows, SMALL_ROWS_PER_BLOCK) * 1024 * sizeof(uint16_t), st));
+            GEVC(V.d_partial.ensure(ceil_div(rows, SMALL_ROWS_PER_BLOCK) * 1024, st));
             vw.emplace_back();
             CvWork& v = vw.back(); memset(&v, 0, sizeof v);     // (upload_table_cached compares the table byte for byte: the padding too)
-            v.cvp_alt = P.cvp[p][k][alt].as<u32>(); v.cvp_cur = P.cvp[p][k][cur].as<u32>(); v.pos_sorted = V.d_pos_sorted.as<u64>(); v.counts = V.d_counts.as<u32>(); v.partial = V.d_partial.as<uint16_t>();
+            v.cvp_alt = P.cvp[p][k][alt]; v.cvp_cur = P.cvp[p][k][cur]; v.pos_sorted = V.d_pos_sorted; v.counts = V.d_counts; v.partial = V.d_partial;
             v.bp0 = S.rbp.front(); v.bp_end = S.rbp.back(); v.stride_w32 = V.stride_w32; v.sub_w32 = V.sub_w32; v.C = V.C; v.chr = k; v.cw = (u32)(cw.size() - 1);
         }
     }
@@ -1481,8 +1517,8 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
     sc.cv_count_fused = true;
     for (const CvWork& v : vw) { sc.cv_used_max = std::max<size_t>(sc.cv_used_max, (size_t)v.sub_w32 * nsub); sc.cv_count_fused &= v.sub_w32 <= 32; if (v.C <= SMALL_POS_LDS) sc.cv_max = std::max(sc.cv_max, v.C); }   // LDS copy of the CV grid: sized for the launch, not for the worst case (occupancy)
     if (sc.n_chrwork) {
-        GEVC(upload_table_cached(c, sc.chrwork, sc.chrwork_shadow, cw.data(), cw.size() * sizeof(ChrWork), st));
-        GEVC(upload_table_cached(c, sc.cvwork, sc.cvwork_shadow, vw.data(), vw.size() * sizeof(CvWork), st));
+        GEVC(upload_table_cached(c, sc.chrwork, sc.chrwork_shadow, cw.data(), cw.size(), st));
+        GEVC(upload_table_cached(c, sc.cvwork, sc.cvwork_shadow, vw.data(), vw.size(), st));
     }
     return GEV_OK;
 }
@@ -1493,8 +1529,8 @@ static int enqueue_pool_free(gev_ctx* c, gev_ctx::Scratch& sc, int pop, hipStrea
     PopState& P = c->pop[pop];
     if (!c->dense || !sc.n_chrwork || !sc.pool_rebuild) return GEV_OK;      // (decided by enqueue_tables)
     const unsigned pool_blocks = (unsigned)std::min<size_t>(ceil_div(4 * P.cap_people * sc.nseg_max, 256), 1024);
-    hipLaunchKernelGGL(k_pool_mark_tab, dim3(pool_blocks, sc.n_chrwork), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), 2 * P.n_phys);
-    hipLaunchKernelGGL(k_pool_collect_tab, dim3(pool_blocks, sc.n_chrwork), dim3(256), 0, st, sc.chrwork.as<ChrWork>());
+    hipLaunchKernelGGL(k_pool_mark_tab, dim3(pool_blocks, sc.n_chrwork), dim3(256), 0, st, sc.chrwork, 2 * P.n_phys);
+    hipLaunchKernelGGL(k_pool_collect_tab, dim3(pool_blocks, sc.n_chrwork), dim3(256), 0, st, sc.chrwork);
     KCHECK();
     for (int k = 0; k < c->nchr; k++) if (c->chr_active[k]) { P.st[k].pool_list_valid = true; P.st[k].pool_force_rebuild = false; P.st[k].pool_rebuilds++; }
     return GEV_OK;
@@ -1504,7 +1540,7 @@ static int enqueue_pool_publish(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_peopl
 {
     if (!c->dense || !sc.n_chrwork) return GEV_OK;
     SampleDev sd = make_sd(c, sc, n_people * (size_t)c->nchr);
-    hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(64), 0, st, sc.chrwork.as<ChrWork>(), sc.n_chrwork, sd.status);
+    hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(64), 0, st, sc.chrwork, sc.n_chrwork, sd.status);
     KCHECK();
     return GEV_OK;
 }
@@ -1517,8 +1553,8 @@ static int enqueue_pool_assign(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people
     const size_t rows = 2 * n_people, T = n_people * (size_t)c->nchr;
     SampleDev sd = make_sd(c, sc, T);
     u32 lg = 0; while ((1u << lg) * POOL_INH < sc.nseg_max) lg++;    // threads per row of k_pool_inherit: 2^lg, rows per block: 256 >> lg
-    hipLaunchKernelGGL(k_pool_inherit, dim3((unsigned)ceil_div(rows, (size_t)(256u >> lg)), sc.n_chrwork), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), rows, c->nchr, sd, lg);
-    hipLaunchKernelGGL(k_pool_fresh, dim3((unsigned)ceil_div(rows, 256), sc.n_chrwork), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), rows, c->nchr, sd);
+    hipLaunchKernelGGL(k_pool_inherit, dim3((unsigned)ceil_div(rows, (size_t)(256u >> lg)), sc.n_chrwork), dim3(256), 0, st, sc.chrwork, rows, c->nchr, sd, lg);
+    hipLaunchKernelGGL(k_pool_fresh, dim3((unsigned)ceil_div(rows, 256), sc.n_chrwork), dim3(256), 0, st, sc.chrwork, rows, c->nchr, sd);
     KCHECK();
     return enqueue_pool_publish(c, sc, n_people, st);
 }
@@ -1532,8 +1568,8 @@ static int enqueue_lists(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, bool
     const size_t T = n_people * (size_t)nchr, rows = 2 * n_people;
     SampleDev sd = make_sd(c, sc, T);
     // one launch: every (offspring row, position range) either names the parent's pieces or builds its own (gev_lists.h)
-    HIPC(hipMemsetAsync(c->d_lp_nitems.p, 0, c->d_lp_nitems.bytes, st));
-    hipLaunchKernelGGL(k_lp_inherit, dim3((unsigned)ceil_div(rows, 256), na), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), rows, nchr, (int)has_mut, sd);
+    HIPC(hipMemsetAsync(c->d_lp_nitems.p, 0, c->d_lp_nitems.bytes(), st));
+    hipLaunchKernelGGL(k_lp_inherit, dim3((unsigned)ceil_div(rows, 256), na), dim3(256), 0, st, sc.chrwork, rows, nchr, (int)has_mut, sd);
     const bool literal = getenv("GEV_LP_LITERAL") && atoi(getenv("GEV_LP_LITERAL")) != 0;      // recombine's statements one by one instead of their closed form (cross-check)
     const dim3 bgrid((unsigned)std::min<size_t>(ceil_div(rows * 4, 256), 2048), na);
     // one lane per piece while pieces are short, a group of eight once they are long (the one-lane kernel is faster up to about 20
@@ -1541,9 +1577,9 @@ static int enqueue_lists(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, bool
     // kernel's hardly does: 0.77 -> 0.89 ms per generation over 700 generations against 0.67 -> 0.97).  GEV_LP_LANES=1|8 fixes it.
     int lanes = getenv("GEV_LP_LANES") ? atoi(getenv("GEV_LP_LANES")) : 0;
     if (lanes != 1 && lanes != 8) lanes = sc.lp_entries_per_row >= 20 ? 8 : 1;
-    if (literal) hipLaunchKernelGGL((k_lp_build<true>), bgrid, dim3(256), 0, st, sc.chrwork.as<ChrWork>(), nchr, (int)has_mut, sd);
-    else if (lanes == 1) hipLaunchKernelGGL((k_lp_build<false>), bgrid, dim3(256), 0, st, sc.chrwork.as<ChrWork>(), nchr, (int)has_mut, sd);
-    else hipLaunchKernelGGL(k_lp_build8, dim3((unsigned)std::min<size_t>(ceil_div(rows * 4, 32), 8192), na), dim3(256), 0, st, sc.chrwork.as<ChrWork>(), nchr, (int)has_mut, sd);
+    if (literal) hipLaunchKernelGGL((k_lp_build<true>), bgrid, dim3(256), 0, st, sc.chrwork, nchr, (int)has_mut, sd);
+    else if (lanes == 1) hipLaunchKernelGGL((k_lp_build<false>), bgrid, dim3(256), 0, st, sc.chrwork, nchr, (int)has_mut, sd);
+    else hipLaunchKernelGGL(k_lp_build8, dim3((unsigned)std::min<size_t>(ceil_div(rows * 4, 32), 8192), na), dim3(256), 0, st, sc.chrwork, nchr, (int)has_mut, sd);
     KCHECK();
     return GEV_OK;
 }
@@ -1557,16 +1593,16 @@ static int enqueue_cv_planes(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, 
     const int nchr = c->nchr;
     const size_t T = n_people * (size_t)nchr, rows = 2 * n_people;
     SampleDev sd = make_sd(c, sc, T);
-    const CvWork* Vt = sc.cvwork.as<CvWork>();
+    const CvWork* Vt = sc.cvwork;
     const dim3 grid((unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK), sc.n_cvwork); const size_t lds = (size_t)sc.cv_max * sizeof(u64); const u32 nsub = 1u + c->rp_bits;
     hipLaunchKernelGGL((k_stitch_small<512>), grid, dim3(512), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
     if (count_cols && sum_counts) {
         GEVC(c->d_flag.ensure(16, st));                              // (the launch resets the NaN flag of the A/D kernel behind it)
         const unsigned nblk = (unsigned)grid.x, slices = std::min((nblk + 7u) / 8u, 128u);      // eight partial blocks per thread, as k_cv_finish
         const unsigned mut_blocks = has_mut ? (unsigned)ceil_div(n_people, 256) : 0u, col_blocks = (unsigned)std::max<size_t>(ceil_div(sc.cv_max, 256), 1);
-        hipLaunchKernelGGL(k_cv_newmut_sum, dim3(mut_blocks + col_blocks * slices, sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork.as<ChrWork>(), n_people, nchr, sd,
+        hipLaunchKernelGGL(k_cv_newmut_sum, dim3(mut_blocks + col_blocks * slices, sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork, n_people, nchr, sd,
                            mut_blocks, col_blocks, slices, nblk, c->d_flag.as<u32>());
-    } else if (has_mut) hipLaunchKernelGGL(k_cv_newmut, dim3((unsigned)ceil_div(n_people, 256), sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork.as<ChrWork>(), n_people, nchr, sd, (int)count_cols);
+    } else if (has_mut) hipLaunchKernelGGL(k_cv_newmut, dim3((unsigned)ceil_div(n_people, 256), sc.n_cvwork), dim3(256), 0, st, Vt, sc.chrwork, n_people, nchr, sd, (int)count_cols);
     KCHECK();
     return GEV_OK;
 }
@@ -1590,9 +1626,9 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
             // (at most 16384 workgroups of 4 waves = 4 work-list entries each per chromosome; one 16-byte chunk per lane in flight:
             // a 2 KiB segment is one step of a wave -- with 8 KiB segments 2 chunks gave 722, 4 gave 778 generations/s)
             const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(ceil_div(est + est / 8, 4), 256), 16384);
-            hipLaunchKernelGGL((k_stitch_segments<true, 1>), dim3(nblk, sc.n_chrwork), dim3(256), 0, sb, sc.chrwork.as<ChrWork>(), nchr, sd);
+            hipLaunchKernelGGL((k_stitch_segments<true, 1>), dim3(nblk, sc.n_chrwork), dim3(256), 0, sb, sc.chrwork, nchr, sd);
         } else
-            hipLaunchKernelGGL(k_stitch_rows, dim3((unsigned)rows, sc.n_chrwork), dim3(STITCH_THREADS), 0, sb, sc.chrwork.as<ChrWork>(), nchr, sd);
+            hipLaunchKernelGGL(k_stitch_rows, dim3((unsigned)rows, sc.n_chrwork), dim3(STITCH_THREADS), 0, sb, sc.chrwork, nchr, sd);
         KCHECK();
     }
     HIPC(hipEventRecord(sc.t[3], sb));
@@ -1610,13 +1646,13 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
 // n ras_glob_seed() values into vals[0..n) and the engine state behind them into *state_out; the engine state in front comes from
 // the host (state_val) or from a device word (state_ptr).  blk holds the rejection counts: its user orders it against every other
 // draw into it (a scratch set's own, gev_glob_seeds' own)
-static int enqueue_glob(DevBuf& blk, hipStream_t st, u32 state_val, const u32* state_ptr, size_t n, u32* vals, u32* state_out, u32* flags)
+static int enqueue_glob(Dev<u32>& blk, hipStream_t st, u32 state_val, const u32* state_ptr, size_t n, u32* vals, u32* state_out, u32* flags)
 {
     const u64 n_cand = (u64)n + n / 512 + 512;                  // expected rejections: n / 4444 (2147483646 - 2147000000 of 2147483646 outputs)
     const unsigned nb = (unsigned)ceil_div((size_t)n_cand, REJ_CHUNK);
-    GEVC(blk.ensure(nb * sizeof(u32), st));
-    hipLaunchKernelGGL(k_glob_count, dim3(nb), dim3(256), 0, st, state_val, state_ptr, n_cand, blk.as<u32>());
-    hipLaunchKernelGGL(k_glob_emit, dim3(nb), dim3(256), 0, st, state_val, state_ptr, (u64)n, n_cand, blk.as<u32>(), vals, state_out, flags);
+    GEVC(blk.ensure(nb, st));
+    hipLaunchKernelGGL(k_glob_count, dim3(nb), dim3(256), 0, st, state_val, state_ptr, n_cand, blk);
+    hipLaunchKernelGGL(k_glob_emit, dim3(nb), dim3(256), 0, st, state_val, state_ptr, (u64)n, n_cand, blk, vals, state_out, flags);
     KCHECK();
     return GEV_OK;
 }
@@ -1629,21 +1665,21 @@ static int enqueue_mate(gev_ctx* c, hipStream_t st, PopState& P, u32 seed_val, c
     const size_t n_h = P.n_people;
     const u32* logical = nullptr;
     if (!P.logical.empty()) {                                   // after a cross-GPU migration positions are not rows
-        GEVC(upload_table(c, c->d_logical, P.logical.data(), n_h * sizeof(u32), st));
-        logical = c->d_logical.as<u32>();
+        GEVC(upload_table(c, c->d_logical, P.logical.data(), n_h, st));
+        logical = c->d_logical;
     }
     const unsigned nb = (unsigned)ceil_div(n_h, MATE_CHUNK);
-    GEVC(c->d_mflag.ensure(n_h, st)); GEVC(c->d_mblk.ensure(nb * sizeof(u32), st));
-    GEVC(c->d_posm.ensure(n_h * sizeof(u32), st)); GEVC(c->d_posf.ensure(n_h * sizeof(u32), st));
-    hipLaunchKernelGGL(k_mate_flags, dim3(nb), dim3(256), 0, st, P.d_sex[P.cur].as<uint8_t>(), logical, d_svf, n_h, seed_val, seed_ptr, c->d_mflag.as<uint8_t>(), c->d_mblk.as<u32>());
-    hipLaunchKernelGGL(k_mate_compact, dim3(nb), dim3(256), 0, st, c->d_mflag.as<uint8_t>(), n_h, c->d_mblk.as<u32>(), nb, c->d_posm.as<u32>(), c->d_posf.as<u32>(), meta, flags);
+    GEVC(c->d_mflag.ensure(n_h, st)); GEVC(c->d_mblk.ensure(nb, st));
+    GEVC(c->d_posm.ensure(n_h, st)); GEVC(c->d_posf.ensure(n_h, st));
+    hipLaunchKernelGGL(k_mate_flags, dim3(nb), dim3(256), 0, st, P.d_sex[P.cur], logical, d_svf, n_h, seed_val, seed_ptr, c->d_mflag, c->d_mblk);
+    hipLaunchKernelGGL(k_mate_compact, dim3(nb), dim3(256), 0, st, c->d_mflag, n_h, c->d_mblk, nb, c->d_posm, c->d_posf, meta, flags);
     // candidates of the two pick streams: a draw is rejected with probability < n_h / 2^31
     const u64 n_cand = (u64)pop_size + (u64)(2.0 * (double)pop_size * (double)n_h / 2147483648.0) + 1024;
     const unsigned nbp = (unsigned)ceil_div((size_t)n_cand, REJ_CHUNK);
-    GEVC(c->d_pickblk.ensure(2 * (size_t)nbp * sizeof(u32), st));
-    hipLaunchKernelGGL(k_pick_count, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, n_cand, c->d_pickblk.as<u32>());
-    hipLaunchKernelGGL(k_pick_emit, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, (u64)pop_size, n_cand, c->d_pickblk.as<u32>(),
-                       c->d_posm.as<u32>(), c->d_posf.as<u32>(), logical, father, mother, d_couples, flags);
+    GEVC(c->d_pickblk.ensure(2 * (size_t)nbp, st));
+    hipLaunchKernelGGL(k_pick_count, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, n_cand, c->d_pickblk);
+    hipLaunchKernelGGL(k_pick_emit, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, (u64)pop_size, n_cand, c->d_pickblk,
+                       c->d_posm, c->d_posf, logical, father, mother, d_couples, flags);
     KCHECK();
     return GEV_OK;
 }
@@ -1673,7 +1709,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     q.th0 = host_ms();
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[0], S));
     if (attempt == 0) GEVC(harvest_timing(c, sc));          // kernel times of the set's previous generation, before its events are recorded again
-    u32* gv = sc.globvals.as<u32>(); u32* status = sc.status.as<u32>();
+    u32* gv = sc.globvals; u32* status = sc.status;
     const bool sampled = q.pre && attempt == 0;              // seeds drawn and sampling done by a head start
     if (q.fused && !sampled) {
         HIPC(hipMemsetAsync(sc.status.p, 0, q.n_status * sizeof(u32), S));
@@ -1687,8 +1723,8 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     // (the mating stream starts here: it needs the seeds, not the state behind them)
     GEVC(hand_over(S, X, sc.ev_fork));
     if (q.fused && !q.assort) {
-        GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father.as<u32>(), sc.mother.as<u32>(),
-                          c->d_couples.as<gev_couple>(), status + ST_NM_MATE, status + ST_FLAGS));
+        GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father, sc.mother,
+                          c->d_couples, status + ST_NM_MATE, status + ST_FLAGS));
     }
     if (q.fused && !q.assort && c->chain_draws >= 0) {       // where glob_generator will stand when the host comes back for the next generation
         hipLaunchKernelGGL(k_glob_skip, dim3(1), dim3(64), 0, S, (const u32*)(status + ST_GLOB_STATE), (u32)c->chain_draws, status + ST_NEXT_STATE);
@@ -1735,12 +1771,12 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     HIPC(hipMemcpyAsync(P.d_sex[P.cur ^ 1].p, sc.sex.p, q.n_people, hipMemcpyDeviceToDevice, L));
     if (P.ids_ok) {                                          // the offspring's pedigree ids (:2473-2479) from the parents' rows, into the other buffer
         const int nb = P.ibuf ^ 1;
-        GEVC(P.d_ids[nb].ensure(PED_FIELDS * q.n_people * sizeof(int64_t), L)); GEVC(P.d_cidx[nb].ensure(q.n_people * sizeof(u32), L));
+        GEVC(P.d_ids[nb].ensure(PED_FIELDS * q.n_people, L)); GEVC(P.d_cidx[nb].ensure(q.n_people, L));
         P.ids_stride[nb] = q.n_people;
-        hipLaunchKernelGGL(k_ped_offspring, dim3((unsigned)ceil_div(q.n_people, 256)), dim3(256), 0, L, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf],
-                           P.n_phys, (const u32*)sc.father.as<u32>(), (const u32*)sc.mother.as<u32>(), q.n_people, P.d_ids[nb].as<int64_t>(), q.n_people,
-                           q.cidx_mode == 1 ? (const u32*)sc.cidx.as<u32>() : (const u32*)nullptr, q.cidx_mode == 2 ? (const u32*)c->am.ooff.as<u32>() : (const u32*)nullptr,
-                           (u32)q.n_couples, P.d_cidx[nb].as<u32>());
+        hipLaunchKernelGGL(k_ped_offspring, dim3((unsigned)ceil_div(q.n_people, 256)), dim3(256), 0, L, P.d_ids[P.ibuf], P.ids_stride[P.ibuf],
+                           P.n_phys, sc.father, sc.mother, q.n_people, P.d_ids[nb], q.n_people,
+                           q.cidx_mode == 1 ? sc.cidx : (const u32*)nullptr, q.cidx_mode == 2 ? c->am.ooff : (const u32*)nullptr,
+                           (u32)q.n_couples, P.d_cidx[nb]);
         KCHECK();
     }
     if (q.fused) { HIPC(hipMemcpyAsync(q.hsex, sc.sex.p, q.n_people, hipMemcpyDeviceToHost, L)); HIPC(hipMemcpyAsync(q.hseeds2, gv, 2 * sizeof(u32), hipMemcpyDeviceToHost, L)); }   // (copies nothing on the device waits for: off the main stream)
@@ -1845,7 +1881,7 @@ int gev_reproduce_begin(gev_ctx* c, int pop, const gev_couple* couples, size_t n
     if (!dev_couples) {
         HIPC(hipMemcpyAsync(sc.father.p, father, n_people * sizeof(u32), hipMemcpyHostToDevice, st));
         HIPC(hipMemcpyAsync(sc.mother.p, mother, n_people * sizeof(u32), hipMemcpyHostToDevice, st));
-        if (P.ids_ok) { GEVC(sc.cidx.ensure(n_people * sizeof(u32), st)); HIPC(hipMemcpyAsync(sc.cidx.p, hcidx, n_people * sizeof(u32), hipMemcpyHostToDevice, st)); }
+        if (P.ids_ok) { GEVC(sc.cidx.ensure(n_people, st)); HIPC(hipMemcpyAsync(sc.cidx.p, hcidx, n_people * sizeof(u32), hipMemcpyHostToDevice, st)); }
     }
     q.seed = (u32)seed_reproduce;
     if (!dev_couples) { q.cidx_mode = 1; q.n_couples = n_couples; }
@@ -1864,10 +1900,10 @@ static int enqueue_chain_head_start(gev_ctx* c)
     // it, the host does not (its kernel time is collected when the set's next generation is enqueued)
     GEVC(claim_scratch(c, nx, SS, false, q.n_people, q.has_mut));   // (sizes the buffers in front of the wait below: allocations only, no stream work)
     HIPC(hipStreamWaitEvent(SS, sc.ev_chain, 0));
-    GEVC(nx.globvals.ensure((2 + T) * sizeof(u32), SS));
-    u32* gv = nx.globvals.as<u32>(); u32* status = nx.status.as<u32>();
+    GEVC(nx.globvals.ensure((2 + T), SS));
+    u32* gv = nx.globvals; u32* status = nx.status;
     HIPC(hipMemsetAsync(nx.status.p, 0, q.n_status * sizeof(u32), SS));
-    GEVC(enqueue_glob(nx.globblk, SS, 0u, sc.status.as<u32>() + ST_NEXT_STATE, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
+    GEVC(enqueue_glob(nx.globblk, SS, 0u, sc.status + ST_NEXT_STATE, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     GEVC(enqueue_sampling(c, nx, q.pop, q.n_people, q.has_mut, 0u, SS, gv + 1, gv + 2, /*clear_status=*/false));
     HIPC(hipEventRecord(nx.ev_sampled, SS));
     nx.hs.kind = HeadStart::CHAIN; nx.hs.dropped = false; nx.hs.pop = q.pop; nx.hs.n_people = q.n_people; nx.hs.has_mut = q.has_mut;
@@ -1925,16 +1961,16 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     GEVC(take_head_start(c, sc, HeadStart::CHAIN, pop, n_people, q.has_mut, (u32)glob_state, nullptr, q.pre));
     if (!q.pre) {
         GEVC(claim_scratch(c, sc, st, true, n_people, q.has_mut));
-        GEVC(sc.globvals.ensure((2 + n_people * (size_t)c->nchr) * sizeof(u32), st));
+        GEVC(sc.globvals.ensure((2 + n_people * (size_t)c->nchr), st));
     }
-    GEVC(c->d_couples.ensure(n_people * sizeof(gev_couple), st));
+    GEVC(c->d_couples.ensure(n_people, st));
     if (selection_value_func) {
-        GEVC(c->d_svf.ensure(P.n_people * sizeof(double), st));
+        GEVC(c->d_svf.ensure(P.n_people, st));
         HIPC(hipMemcpyAsync(c->d_svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
         HIPC(hipStreamSynchronize(st));                          // the caller's array is pageable memory of unknown lifetime
     }
-    const double* d_svf = selection_value_func ? c->d_svf.as<double>() : nullptr;
-    if (dev_sel) d_svf = P.d_sel[P.sbuf].as<double>() + 2 * P.n_people;     // (enqueued on this stream behind gev_compute_selection: no wait)
+    const double* d_svf = selection_value_func ? c->d_svf : nullptr;
+    if (dev_sel) d_svf = P.d_sel[P.sbuf] + 2 * P.n_people;     // (enqueued on this stream behind gev_compute_selection: no wait)
     q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state;
     GEVC(enqueue_attempt(c, 0));
     q.active = true;
@@ -2097,19 +2133,19 @@ static int random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selecti
     gev_ctx::Scratch& sc = c->sc[c->gen_counter & 1];
     // father / mother of this scratch set were last read by the stitch two generations back
     GEVC(claim_scratch(c, sc, st, true, 0, false));
-    GEVC(sc.father.ensure(pop_size * sizeof(u32), st)); GEVC(sc.mother.ensure(pop_size * sizeof(u32), st));
-    GEVC(c->d_couples.ensure(pop_size * sizeof(gev_couple), st));
-    GEVC(c->d_mstat.ensure(4 * sizeof(u32), st));
+    GEVC(sc.father.ensure(pop_size, st)); GEVC(sc.mother.ensure(pop_size, st));
+    GEVC(c->d_couples.ensure(pop_size, st));
+    GEVC(c->d_mstat.ensure(4, st));
     HIPC(hipMemsetAsync(c->d_mstat.p, 0, 4 * sizeof(u32), st));
     const double* d_svf = nullptr;
     if (selection_value_func) {
-        GEVC(c->d_svf.ensure(P.n_people * sizeof(double), st));
+        GEVC(c->d_svf.ensure(P.n_people, st));
         HIPC(hipMemcpyAsync(c->d_svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
-        d_svf = c->d_svf.as<double>();
+        d_svf = c->d_svf;
     }
-    if (dev_sel) d_svf = P.d_sel[P.sbuf].as<double>() + 2 * P.n_people;
-    u32* ms = c->d_mstat.as<u32>();                             // {num_males_mate, num_females_mate, flags}
-    GEVC(enqueue_mate(c, st, P, (u32)seed, nullptr, d_svf, pop_size, sc.father.as<u32>(), sc.mother.as<u32>(), couples_out ? c->d_couples.as<gev_couple>() : nullptr, ms, ms + 2));
+    if (dev_sel) d_svf = P.d_sel[P.sbuf] + 2 * P.n_people;
+    u32* ms = c->d_mstat;                             // {num_males_mate, num_females_mate, flags}
+    GEVC(enqueue_mate(c, st, P, (u32)seed, nullptr, d_svf, pop_size, sc.father, sc.mother, couples_out ? c->d_couples : nullptr, ms, ms + 2));
     u32 h[4] = {0, 0, 0, 0};
     HIPC(hipMemcpyAsync(h, ms, sizeof h, hipMemcpyDeviceToHost, st));
     if (couples_out) HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, pop_size * sizeof(gev_couple), hipMemcpyDeviceToHost, st));
@@ -2165,18 +2201,18 @@ int gev_rank_f64(gev_ctx* c, const double* x, size_t n, unsigned long long* rank
     return GEV_OK;
 }
 // std::random_shuffle of m entries on the rand() values R[0 .. m-2]: src[q] = original position of the entry that ends at p0 + q
-static int am_shuffle(gev_ctx* c, hipStream_t st, const u32* R, size_t m, size_t p0, size_t p1, DevBuf& src)
+static int am_shuffle(gev_ctx* c, hipStream_t st, const u32* R, size_t m, size_t p0, size_t p1, Dev<u32>& src)
 {
     gev_ctx::AssortState& A = c->am;
     const size_t w = (m + 1) * sizeof(u32);
-    GEVC(A.scnt.ensure(w, st)); GEVC(A.soff.ensure(w, st)); GEVC(A.sfill.ensure(w, st)); GEVC(A.stgt.ensure(w, st));
-    GEVC(src.ensure(std::max<size_t>(p1 - p0, 1) * sizeof(u32), st));
+    GEVC(A.scnt.ensure(m + 1, st)); GEVC(A.soff.ensure(m + 1, st)); GEVC(A.sfill.ensure(m + 1, st)); GEVC(A.stgt.ensure(m + 1, st));
+    GEVC(src.ensure(std::max<size_t>(p1 - p0, 1), st));
     HIPC(hipMemsetAsync(A.scnt.p, 0, w, st)); HIPC(hipMemsetAsync(A.sfill.p, 0, w, st));
     const unsigned nb = (unsigned)ceil_div(m, 256);
-    hipLaunchKernelGGL(k_shuf_count, dim3(nb), dim3(256), 0, st, R, m, A.scnt.as<u32>());
-    GEVC(scan_u32_on(st, c->d_sums, A.scnt.as<u32>(), m, A.soff.as<u32>()));
-    hipLaunchKernelGGL(k_shuf_fill, dim3(nb), dim3(256), 0, st, R, m, A.soff.as<u32>(), A.sfill.as<u32>(), A.stgt.as<u32>());
-    if (p1 > p0) hipLaunchKernelGGL(k_shuf_trace, dim3((unsigned)ceil_div(p1 - p0, 256)), dim3(256), 0, st, R, m, A.soff.as<u32>(), A.stgt.as<u32>(), p0, p1, src.as<u32>());
+    hipLaunchKernelGGL(k_shuf_count, dim3(nb), dim3(256), 0, st, R, m, A.scnt);
+    GEVC(scan_u32_on(st, c->d_sums, A.scnt, m, A.soff));
+    hipLaunchKernelGGL(k_shuf_fill, dim3(nb), dim3(256), 0, st, R, m, A.soff, A.sfill, A.stgt);
+    if (p1 > p0) hipLaunchKernelGGL(k_shuf_trace, dim3((unsigned)ceil_div(p1 - p0, 256)), dim3(256), 0, st, R, m, A.soff, A.stgt, p0, p1, src);
     KCHECK();
     return GEV_OK;
 }
@@ -2210,32 +2246,32 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     GEVC(claim_scratch(c, sc, st, true, 0, false));
     const u32* logical = nullptr;
     if (!P.logical.empty()) {                                   // after a cross-GPU migration positions are not rows
-        GEVC(upload_table(c, c->d_logical, P.logical.data(), n_h * sizeof(u32), st));
-        logical = c->d_logical.as<u32>();
+        GEVC(upload_table(c, c->d_logical, P.logical.data(), n_h, st));
+        logical = c->d_logical;
     }
     const double* d_mv; const double* d_svf = nullptr;
-    if (dev_sel) { d_mv = P.d_sel[P.sbuf].as<double>(); d_svf = d_mv + 2 * n_h; }
+    if (dev_sel) { d_mv = P.d_sel[P.sbuf]; d_svf = d_mv + 2 * n_h; }
     else {
-        GEVC(A.mv.ensure(n_h * sizeof(double), st));
+        GEVC(A.mv.ensure(n_h, st));
         HIPC(hipMemcpyAsync(A.mv.p, mating_value, n_h * sizeof(double), hipMemcpyHostToDevice, st));
-        d_mv = A.mv.as<double>();
+        d_mv = A.mv;
         if (selection_value_func) {
-            GEVC(A.svf.ensure(n_h * sizeof(double), st));
+            GEVC(A.svf.ensure(n_h, st));
             HIPC(hipMemcpyAsync(A.svf.p, selection_value_func, n_h * sizeof(double), hipMemcpyHostToDevice, st));
-            d_svf = A.svf.as<double>();
+            d_svf = A.svf;
         }
     }
     const int64_t* d_ped = nullptr;
     if (avoid && !dev_ped) {
-        GEVC(A.ped.ensure(n_h * 5 * sizeof(int64_t), st));
+        GEVC(A.ped.ensure(n_h * 5, st));
         HIPC(hipMemcpyAsync(A.ped.p, pedigree, n_h * 5 * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        d_ped = A.ped.as<int64_t>();
+        d_ped = A.ped;
     }
-    const uint8_t* sex = P.d_sex[P.cur].as<uint8_t>();
+    const uint8_t* sex = P.d_sex[P.cur];
     const double mm = par->mm_percent;
-    GEVC(A.stat.ensure(AMS_WORDS * sizeof(u32), st));
+    GEVC(A.stat.ensure(AMS_WORDS, st));
     HIPC(hipMemsetAsync(A.stat.p, 0, AMS_WORDS * sizeof(u32), st));
-    u32* stat = A.stat.as<u32>();
+    u32* stat = A.stat;
 
     // :2184-2216 marriage draws: windows of start offsets per chunk, the chain over the chunks, one walk per chunk from its true start
     const u32 nc = (u32)ceil_div(n_h, AM_B);
@@ -2243,22 +2279,22 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     const u32 kmin = A.narrow_window ? 0u : 16u;
     const u32 wcap = (u32)round_up(2 * ((size_t)std::ceil(alpha * std::sqrt((double)n_h / 4.0)) + kmin + 1) + 1, 256);
     const u32 x_sel = h_minstd_seed(seeds[1]);
-    GEVC(A.stats.ensure(nc * sizeof(double2), st)); GEVC(A.wlo.ensure(nc * sizeof(u32), st)); GEVC(A.ww.ensure(nc * sizeof(u32), st));
-    GEVC(A.ends.ensure((size_t)nc * wcap * sizeof(u32), st)); GEVC(A.start.ensure(nc * sizeof(u32), st));
-    GEVC(A.cm.ensure(n_h * sizeof(u32), st)); GEVC(A.cf.ensure(n_h * sizeof(u32), st));
-    GEVC(A.om.ensure((n_h + 1) * sizeof(u32), st)); GEVC(A.of.ensure((n_h + 1) * sizeof(u32), st));
-    GEVC(A.males.ensure(2 * n_h * sizeof(u32), st)); GEVC(A.females.ensure(2 * n_h * sizeof(u32), st));
-    hipLaunchKernelGGL(k_am_chunk_stats, dim3(nc), dim3(256), 0, st, sex, logical, d_svf, n_h, A.stats.as<double2>());
-    hipLaunchKernelGGL(k_am_windows, dim3(1), dim3(64), 0, st, (const double2*)A.stats.as<double2>(), nc, alpha, kmin, wcap, A.wlo.as<u32>(), A.ww.as<u32>());
-    hipLaunchKernelGGL(k_am_walk, dim3(nc, wcap / 256), dim3(256), 0, st, sex, logical, d_svf, n_h, x_sel, mm, (const u32*)A.wlo.as<u32>(), (const u32*)A.ww.as<u32>(), wcap, A.ends.as<u32>());
-    hipLaunchKernelGGL(k_am_chain, dim3(1), dim3(64), 0, st, sex, logical, d_svf, n_h, x_sel, mm, nc, (const u32*)A.wlo.as<u32>(), (const u32*)A.ww.as<u32>(), wcap,
-                       (const u32*)A.ends.as<u32>(), A.start.as<u32>(), stat);
-    hipLaunchKernelGGL(k_am_flags, dim3(nc), dim3(256), 0, st, sex, logical, d_svf, n_h, x_sel, mm, (const u32*)A.start.as<u32>(), A.cm.as<u32>(), A.cf.as<u32>());
+    GEVC(A.stats.ensure(nc, st)); GEVC(A.wlo.ensure(nc, st)); GEVC(A.ww.ensure(nc, st));
+    GEVC(A.ends.ensure((size_t)nc * wcap, st)); GEVC(A.start.ensure(nc, st));
+    GEVC(A.cm.ensure(n_h, st)); GEVC(A.cf.ensure(n_h, st));
+    GEVC(A.om.ensure((n_h + 1), st)); GEVC(A.of.ensure((n_h + 1), st));
+    GEVC(A.males.ensure(2 * n_h, st)); GEVC(A.females.ensure(2 * n_h, st));
+    hipLaunchKernelGGL(k_am_chunk_stats, dim3(nc), dim3(256), 0, st, sex, logical, d_svf, n_h, A.stats);
+    hipLaunchKernelGGL(k_am_windows, dim3(1), dim3(64), 0, st, A.stats, nc, alpha, kmin, wcap, A.wlo, A.ww);
+    hipLaunchKernelGGL(k_am_walk, dim3(nc, wcap / 256), dim3(256), 0, st, sex, logical, d_svf, n_h, x_sel, mm, A.wlo, A.ww, wcap, A.ends);
+    hipLaunchKernelGGL(k_am_chain, dim3(1), dim3(64), 0, st, sex, logical, d_svf, n_h, x_sel, mm, nc, A.wlo, A.ww, wcap,
+                       A.ends, A.start, stat);
+    hipLaunchKernelGGL(k_am_flags, dim3(nc), dim3(256), 0, st, sex, logical, d_svf, n_h, x_sel, mm, A.start, A.cm, A.cf);
     KCHECK();
-    GEVC(scan_u32_on(st, c->d_sums, A.cm.as<u32>(), n_h, A.om.as<u32>()));
-    GEVC(scan_u32_on(st, c->d_sums, A.cf.as<u32>(), n_h, A.of.as<u32>()));
-    hipLaunchKernelGGL(k_am_compact, dim3((unsigned)ceil_div(n_h, 256)), dim3(256), 0, st, (const u32*)A.cm.as<u32>(), (const u32*)A.cf.as<u32>(), (const u32*)A.om.as<u32>(),
-                       (const u32*)A.of.as<u32>(), n_h, A.males.as<u32>(), A.females.as<u32>(), stat);
+    GEVC(scan_u32_on(st, c->d_sums, A.cm, n_h, A.om));
+    GEVC(scan_u32_on(st, c->d_sums, A.cf, n_h, A.of));
+    hipLaunchKernelGGL(k_am_compact, dim3((unsigned)ceil_div(n_h, 256)), dim3(256), 0, st, A.cm, A.cf, A.om,
+                       A.of, n_h, A.males, A.females, stat);
     KCHECK();
     u32 h[AMS_WORDS];
     HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
@@ -2280,23 +2316,23 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
         remain_pre = par->pop_size - nfix * n2;
         if (remain_pre) n_rand += n2 - 1;
     }
-    const GevRngTables* T = c->d_tables.as<GevRngTables>();
+    const GevRngTables* T = c->d_tables;
     if (n_rand) {
-        GEVC(A.rnd.ensure(n_rand * sizeof(u32), st));
-        hipLaunchKernelGGL(k_glibc_stream, dim3(1), dim3(64), 0, st, T, (u32)seeds[0], n_rand, A.rnd.as<u32>());
+        GEVC(A.rnd.ensure(n_rand, st));
+        hipLaunchKernelGGL(k_glibc_stream, dim3(1), dim3(64), 0, st, T, (u32)seeds[0], n_rand, A.rnd);
         KCHECK();
     }
-    GEVC(A.kept.ensure(n2 * sizeof(u32), st)); GEVC(A.sorted_m.ensure(n2 * sizeof(u32), st)); GEVC(A.sorted_f.ensure(n2 * sizeof(u32), st));
-    const u32* list_m = A.males.as<u32>(); const u32* list_f = A.females.as<u32>();
+    GEVC(A.kept.ensure(n2, st)); GEVC(A.sorted_m.ensure(n2, st)); GEVC(A.sorted_f.ensure(n2, st));
+    const u32* list_m = A.males; const u32* list_f = A.females;
     if (nL > n2) {
-        GEVC(am_shuffle(c, st, A.rnd.as<u32>(), nL, nL - n2, nL, A.ssrc));
-        hipLaunchKernelGGL(k_gather_u32, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, st, nm > nf ? list_m : list_f, (const u32*)A.ssrc.as<u32>(), n2, A.kept.as<u32>());
+        GEVC(am_shuffle(c, st, A.rnd, nL, nL - n2, nL, A.ssrc));
+        hipLaunchKernelGGL(k_gather_u32, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, st, nm > nf ? list_m : list_f, A.ssrc, n2, A.kept);
         KCHECK();
-        if (nm > nf) list_m = A.kept.as<u32>(); else list_f = A.kept.as<u32>();
+        if (nm > nf) list_m = A.kept; else list_f = A.kept;
     }
     // :2251-2252 both lists sorted by mating value (stable)
-    GEVC(am_sort(c, st, d_mv, list_m, list_m, n2, A.sorted_m.as<u32>()));
-    GEVC(am_sort(c, st, d_mv, list_f, list_f, n2, A.sorted_f.as<u32>()));
+    GEVC(am_sort(c, st, d_mv, list_m, list_m, n2, A.sorted_m));
+    GEVC(am_sort(c, st, d_mv, list_f, list_f, n2, A.sorted_f));
 
     // :2257-2285 the template: ras_mvnorm(n2, 0, [[1, c], [c, 1]]) = z * U (Eigen's LLT upper factor), ranked by CommFunc::ras_rank
     const double cc = par->mat_cor;
@@ -2304,24 +2340,24 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     const double u01 = cc / 1.0, u11 = x11 > 0 ? std::sqrt(x11) : 1.0;
     const u64 n_cand = (u64)n2 + (u64)n2 * 3 / 10 + 4096;          // acceptance pi/4: n2 pairs need 1.273 n2 candidates on average
     const unsigned nbt = (unsigned)ceil_div((size_t)n_cand, POLAR_CHUNK);
-    GEVC(A.tblk.ensure(nbt * sizeof(u32), st)); GEVC(A.t1.ensure(n2 * sizeof(double), st)); GEVC(A.t2.ensure(n2 * sizeof(double), st));
-    GEVC(A.i1.ensure(n2 * sizeof(u32), st)); GEVC(A.i2.ensure(n2 * sizeof(u32), st));
-    GEVC(A.pm.ensure(n2 * sizeof(u32), st)); GEVC(A.pf.ensure(n2 * sizeof(u32), st)); GEVC(A.inb.ensure(n2 * sizeof(u32), st));
-    GEVC(A.num.ensure(n2 * sizeof(int32_t), st));
+    GEVC(A.tblk.ensure(nbt, st)); GEVC(A.t1.ensure(n2, st)); GEVC(A.t2.ensure(n2, st));
+    GEVC(A.i1.ensure(n2, st)); GEVC(A.i2.ensure(n2, st));
+    GEVC(A.pm.ensure(n2, st)); GEVC(A.pf.ensure(n2, st)); GEVC(A.inb.ensure(n2, st));
+    GEVC(A.num.ensure(n2, st));
     const u32 x_tpl = h_minstd_seed(seeds[2]);
-    hipLaunchKernelGGL(k_tpl_count, dim3(nbt), dim3(256), 0, st, x_tpl, n_cand, A.tblk.as<u32>());
-    hipLaunchKernelGGL(k_tpl_emit, dim3(nbt), dim3(256), 0, st, x_tpl, n_cand, (u64)n2, (const u32*)A.tblk.as<u32>(), u01, u11, A.t1.as<double>(), A.t2.as<double>(), stat);
+    hipLaunchKernelGGL(k_tpl_count, dim3(nbt), dim3(256), 0, st, x_tpl, n_cand, A.tblk);
+    hipLaunchKernelGGL(k_tpl_emit, dim3(nbt), dim3(256), 0, st, x_tpl, n_cand, (u64)n2, A.tblk, u01, u11, A.t1, A.t2, stat);
     KCHECK();
-    GEVC(am_sort(c, st, A.t1.as<double>(), nullptr, nullptr, n2, A.i1.as<u32>()));
-    GEVC(am_sort(c, st, A.t2.as<double>(), nullptr, nullptr, n2, A.i2.as<u32>()));
+    GEVC(am_sort(c, st, A.t1, nullptr, nullptr, n2, A.i1));
+    GEVC(am_sort(c, st, A.t2, nullptr, nullptr, n2, A.i2));
     const unsigned nb2 = (unsigned)ceil_div(n2, 256);
-    hipLaunchKernelGGL(k_am_couples, dim3(nb2), dim3(256), 0, st, (const u32*)A.i1.as<u32>(), (const u32*)A.i2.as<u32>(), (const u32*)A.sorted_m.as<u32>(), (const u32*)A.sorted_f.as<u32>(),
-                       n2, A.pm.as<u32>(), A.pf.as<u32>());
+    hipLaunchKernelGGL(k_am_couples, dim3(nb2), dim3(256), 0, st, A.i1, A.i2, A.sorted_m, A.sorted_f,
+                       n2, A.pm, A.pf);
     if (dev_ped)
-        hipLaunchKernelGGL(k_am_inbreed_ids, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), n2, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(),
-                           P.ids_stride[P.ibuf], logical, A.inb.as<u32>(), stat);
+        hipLaunchKernelGGL(k_am_inbreed_ids, dim3(nb2), dim3(256), 0, st, A.pm, A.pf, n2, P.d_ids[P.ibuf],
+                           P.ids_stride[P.ibuf], logical, A.inb, stat);
     else
-        hipLaunchKernelGGL(k_am_inbreed, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), n2, d_ped, A.inb.as<u32>(), stat);
+        hipLaunchKernelGGL(k_am_inbreed, dim3(nb2), dim3(256), 0, st, A.pm, A.pf, n2, d_ped, A.inb, stat);
     KCHECK();
     size_t n_inb = 0;
     if (avoid) {
@@ -2335,7 +2371,7 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     if (n_ok == 0) return fail(GEV_EUNSUPPORTED, "assort_mate: all %zu couples are inbred (the reference divides by zero)", n2);
 
     // :2328-2355 offspring numbers, then the parents of every child in couple order
-    GEVC(A.ocnt.ensure(n2 * sizeof(u32), st)); GEVC(A.ooff.ensure((n2 + 1) * sizeof(u32), st));
+    GEVC(A.ocnt.ensure(n2, st)); GEVC(A.ooff.ensure((n2 + 1), st));
     size_t S = 0;
     double thr = 0;
     u32 L = 0;
@@ -2349,10 +2385,10 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
         const size_t nfix = (size_t)std::floor((double)par->pop_size / (double)n_ok);
         const size_t remain = par->pop_size - nfix * n_ok;
         if (avoid && remain) return fail(GEV_EUNSUPPORTED, "assort_mate: avoid_inbreeding with offspring_dist 'f' and %zu children left over (the reference indexes an empty list)", remain);
-        hipLaunchKernelGGL(k_am_fill_i32, dim3(nb2), dim3(256), 0, st, A.num.as<int32_t>(), n2, (int32_t)nfix);
+        hipLaunchKernelGGL(k_am_fill_i32, dim3(nb2), dim3(256), 0, st, A.num, n2, (int32_t)nfix);
         if (remain) {
-            GEVC(am_shuffle(c, st, A.rnd.as<u32>() + n_rand_surplus, n2, 0, remain, A.ssrc));
-            hipLaunchKernelGGL(k_am_fixed_plus, dim3((unsigned)ceil_div(remain, 256)), dim3(256), 0, st, (const u32*)A.ssrc.as<u32>(), remain, A.num.as<int32_t>());
+            GEVC(am_shuffle(c, st, A.rnd + n_rand_surplus, n2, 0, remain, A.ssrc));
+            hipLaunchKernelGGL(k_am_fixed_plus, dim3((unsigned)ceil_div(remain, 256)), dim3(256), 0, st, A.ssrc, remain, A.num);
         }
         KCHECK();
     }
@@ -2360,20 +2396,20 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
         if (pois) {
             if (S >= 0xfffffff0ull) return fail(GEV_EDEVICE, "assort_mate: Poisson stream of %zu draws (internal error)", S);
             const size_t lv = std::max<u32>(L, 1);
-            GEVC(A.pois.ensure(lv * (S + 1) * sizeof(u32), st));
-            u32* tabs = A.pois.as<u32>();
+            GEVC(A.pois.ensure(lv * (S + 1), st));
+            u32* tabs = A.pois;
             const unsigned nbs = (unsigned)ceil_div(S + 1, 256);
             hipLaunchKernelGGL(k_pois_next, dim3(nbs), dim3(256), 0, st, h_minstd_seed(seeds[3]), (u64)S, thr, tabs);
             for (u32 j = 1; j < L; j++) hipLaunchKernelGGL(k_pois_double, dim3(nbs), dim3(256), 0, st, (const u32*)tabs + (size_t)(j - 1) * (S + 1), (u64)S, tabs + (size_t)j * (S + 1));
-            hipLaunchKernelGGL(k_pois_start, dim3(nb2), dim3(256), 0, st, (const u32*)tabs, (u64)S, L, (u64)n2, A.num.as<int32_t>(), stat);
+            hipLaunchKernelGGL(k_pois_start, dim3(nb2), dim3(256), 0, st, (const u32*)tabs, (u64)S, L, (u64)n2, A.num, stat);
             KCHECK();
         }
-        hipLaunchKernelGGL(k_am_offspring_count, dim3(nb2), dim3(256), 0, st, (const int32_t*)A.num.as<int32_t>(), (const u32*)A.inb.as<u32>(), n2, A.ocnt.as<u32>());
+        hipLaunchKernelGGL(k_am_offspring_count, dim3(nb2), dim3(256), 0, st, A.num, A.inb, n2, A.ocnt);
         KCHECK();
-        GEVC(scan_u32_on(st, c->d_sums, A.ocnt.as<u32>(), n2, A.ooff.as<u32>()));
+        GEVC(scan_u32_on(st, c->d_sums, A.ocnt, n2, A.ooff));
         u32 tot = 0;
         HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
-        HIPC(hipMemcpyAsync(&tot, A.ooff.as<u32>() + n2, sizeof(u32), hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(&tot, A.ooff + n2, sizeof(u32), hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
         if (h[AMS_FLAGS] & AMF_TPL_SHORT) return fail(GEV_EDEVICE, "assort_mate: the template's candidate pairs ran out (internal error)");
         if (pois && (h[AMS_FLAGS] & AMF_POIS_SHORT)) {          // the stream ended inside a couple's draws: run it again, longer
@@ -2386,13 +2422,13 @@ static int assort_mate(gev_ctx* c, int pop, const gev_assort_params* par, const 
     }
     if (res) *res = r;
     if (r.n_offspring) {
-        GEVC(sc.father.ensure(r.n_offspring * sizeof(u32), st)); GEVC(sc.mother.ensure(r.n_offspring * sizeof(u32), st));
+        GEVC(sc.father.ensure(r.n_offspring, st)); GEVC(sc.mother.ensure(r.n_offspring, st));
     }
     const bool records = couples_out || dev_records;           // dev_records: Couples_Info records left in d_couples (gev_generation_end copies them)
-    if (records) GEVC(c->d_couples.ensure(n2 * sizeof(gev_couple), st));
-    hipLaunchKernelGGL(k_am_expand, dim3(nb2), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), (const int32_t*)A.num.as<int32_t>(),
-                       (const u32*)A.inb.as<u32>(), (const u32*)A.ooff.as<u32>(), n2, logical, r.n_offspring ? sc.father.as<u32>() : nullptr,
-                       r.n_offspring ? sc.mother.as<u32>() : nullptr, records ? c->d_couples.as<gev_couple>() : nullptr);
+    if (records) GEVC(c->d_couples.ensure(n2, st));
+    hipLaunchKernelGGL(k_am_expand, dim3(nb2), dim3(256), 0, st, A.pm, A.pf, A.num,
+                       A.inb, A.ooff, n2, logical, r.n_offspring ? sc.father : nullptr,
+                       r.n_offspring ? sc.mother : nullptr, records ? c->d_couples : nullptr);
     KCHECK();
     if (couples_out) HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n2 * sizeof(gev_couple), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -2423,9 +2459,9 @@ int gev_last_assort_result(gev_ctx* c, gev_assort_result* res, gev_couple* coupl
         HIPC(hipSetDevice(c->device));
         hipStream_t st = c->stream;
         const size_t n2 = A.res.n_couples;
-        GEVC(c->d_couples.ensure(n2 * sizeof(gev_couple), st));
-        hipLaunchKernelGGL(k_am_expand, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, st, (const u32*)A.pm.as<u32>(), (const u32*)A.pf.as<u32>(), (const int32_t*)A.num.as<int32_t>(),
-                           (const u32*)A.inb.as<u32>(), (const u32*)A.ooff.as<u32>(), n2, (const u32*)nullptr, (u32*)nullptr, (u32*)nullptr, c->d_couples.as<gev_couple>());
+        GEVC(c->d_couples.ensure(n2, st));
+        hipLaunchKernelGGL(k_am_expand, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, st, A.pm, A.pf, A.num,
+                           A.inb, A.ooff, n2, (const u32*)nullptr, (u32*)nullptr, (u32*)nullptr, c->d_couples);
         KCHECK();
         HIPC(hipMemcpyAsync(couples_out, c->d_couples.p, n2 * sizeof(gev_couple), hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
@@ -2476,7 +2512,7 @@ static int generation_begin_assort(gev_ctx* c, int pop, uint32_t glob_state, con
     gev_ctx::PendingRepro& q = c->pend;
     sc.mated = false;                                          // the couples are this generation's, not a later gev_reproduce's
     GEVC(claim_scratch(c, sc, st, true, n_people, q.has_mut));   // (father / mother already hold n_people entries: kept)
-    GEVC(sc.globvals.ensure((2 + n_people * (size_t)c->nchr) * sizeof(u32), st));
+    GEVC(sc.globvals.ensure((2 + n_people * (size_t)c->nchr), st));
     q.glob_state = state;
     q.assort = true; q.assort_seed0 = seeds[0]; q.am_nm = r.num_males_mate; q.am_nf = r.num_females_mate; q.am_couples = r.n_couples;
     q.cidx_mode = 2; q.n_couples = r.n_couples;
@@ -2644,10 +2680,10 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, int counts, int hb
     hipStream_t st = c->stream;
     const size_t rows = 2 * n;
     const int nchr = c->nchr, nphen = c->nphen;
-    GEVC(c->d_addchr.ensure(n * nchr * nphen * sizeof(double), st)); GEVC(c->d_domchr.ensure(n * nchr * nphen * sizeof(double), st));
-    GEVC(c->d_add.ensure(n * nphen * sizeof(double), st)); GEVC(c->d_dom.ensure(n * nphen * sizeof(double), st));
+    GEVC(c->d_addchr.ensure(n * nchr * nphen, st)); GEVC(c->d_domchr.ensure(n * nchr * nphen, st));
+    GEVC(c->d_add.ensure(n * nphen, st)); GEVC(c->d_dom.ensure(n * nphen, st));
     GEVC(c->d_flag.ensure(16, st));
-    if (!c->d_cvdone.p) { GEVC(c->d_cvdone.ensure((size_t)nchr * nphen * sizeof(u32), st)); HIPC(hipMemsetAsync(c->d_cvdone.p, 0, (size_t)nchr * nphen * sizeof(u32), st)); }   // block tickets of k_cv_finish / k_ad_accumulate_wide (they re-zero themselves)
+    if (!c->d_cvdone.p) { GEVC(c->d_cvdone.ensure((size_t)nchr * nphen, st)); HIPC(hipMemsetAsync(c->d_cvdone.p, 0, (size_t)nchr * nphen * sizeof(u32), st)); }   // block tickets of k_cv_finish / k_ad_accumulate_wide (they re-zero themselves)
     c->ad_host_set_pop = -1;                                 // d_add / d_dom are rewritten below: totals handed in by gev_set_ad are gone
     if (c->any_inactive) {                                   // chromosomes held elsewhere contribute exact zeros here
         HIPC(hipMemsetAsync(c->d_addchr.p, 0, n * nchr * nphen * sizeof(double), st)); HIPC(hipMemsetAsync(c->d_domchr.p, 0, n * nchr * nphen * sizeof(double), st));
@@ -2670,25 +2706,25 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, int counts, int hb
         for (int k = 0; k < nchr; k++) {
             if (!c->chr_active[k]) continue;
             CvStatic& V = P.cv[p][k]; ChrStatic& S = P.cs[k];
-            if (ipb) GEVC(V.d_tab.ensure((size_t)V.C * 6 * sizeof(double), st));
+            if (ipb) GEVC(V.d_tab.ensure((size_t)V.C * 6, st));
             AdWork a{};
-            a.cvp = P.cvp[p][k][buf].as<u32>();
-            a.pos_sorted = V.d_pos_sorted.as<u64>(); a.pos_file = V.d_pos_file.as<u64>(); a.col_of_icv = V.d_col_of_icv.as<u32>();
-            a.a = V.d_a.as<double>(); a.d = V.d_d.as<double>(); a.aptr = V.d_aptr.as<const double*>(); a.dptr = V.d_dptr.as<const double*>();
-            a.counts = V.d_counts.as<u32>(); a.frq = V.d_frq.as<double>(); a.tab = ipb ? V.d_tab.as<double>() : nullptr;
-            a.add_out = c->d_addchr.as<double>() + (size_t)k * nphen + p; a.dom_out = c->d_domchr.as<double>() + (size_t)k * nphen + p;
+            a.cvp = P.cvp[p][k][buf];
+            a.pos_sorted = V.d_pos_sorted; a.pos_file = V.d_pos_file; a.col_of_icv = V.d_col_of_icv;
+            a.a = V.d_a; a.d = V.d_d; a.aptr = V.d_aptr; a.dptr = V.d_dptr;
+            a.counts = V.d_counts; a.frq = V.d_frq; a.tab = ipb ? V.d_tab : nullptr;
+            a.add_out = c->d_addchr + (size_t)k * nphen + p; a.dom_out = c->d_domchr + (size_t)k * nphen + p;
             const bool one_chr = nchr == 1;                                     // the sum over chromosomes is 0 + x: written with the per-chromosome value
-            a.add_tot = one_chr ? c->d_add.as<double>() + p : nullptr; a.dom_tot = one_chr ? c->d_dom.as<double>() + p : nullptr;
-            a.partial = counts == AD_COUNTS_PARTIAL ? V.d_partial.as<uint16_t>() : nullptr;
+            a.add_tot = one_chr ? c->d_add + p : nullptr; a.dom_tot = one_chr ? c->d_dom + p : nullptr;
+            a.partial = counts == AD_COUNTS_PARTIAL ? V.d_partial : nullptr;
             a.bp0 = S.rbp.front(); a.bp_end = S.rbp.back(); a.vd = V.vd;
             a.stride_w32 = V.stride_w32; a.sub_w32 = V.sub_w32; a.C = V.C; a.own_pop = pop; a.cols_sorted = V.cols_sorted ? 1u : 0u;
             aw.push_back(a);
         }
     const unsigned nw = (unsigned)aw.size();
     if (nw) {
-        DevBuf& adw = c->d_adwork2[hbuf]; std::vector<uint8_t>& adw_shadow = c->adwork_shadow[hbuf];      // (one table per result buffer: they alternate with the generations)
-        GEVC(upload_table_cached(c, adw, adw_shadow, aw.data(), aw.size() * sizeof(AdWork), st));
-        const AdWork* At = adw.as<AdWork>();
+        Dev<AdWork>& adw = c->d_adwork2[hbuf]; std::vector<uint8_t>& adw_shadow = c->adwork_shadow[hbuf];      // (one table per result buffer: they alternate with the generations)
+        GEVC(upload_table_cached(c, adw, adw_shadow, aw.data(), aw.size(), st));
+        const AdWork* At = adw;
         const size_t out_stride = (size_t)nchr * nphen, tot_stride = (size_t)nphen;
         u32* flag = c->d_flag.as<u32>();
         if (c_max && counts == AD_COUNTS_NONE) {
@@ -2698,11 +2734,11 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, int counts, int hb
         // counts -> frequencies (+ the term table of the fast path), NaN flag reset: one launch -- none behind k_cv_newmut_sum, where
         // the counts are complete, the flag is reset and k_ad_accumulate_wide computes frequencies and terms itself
         const unsigned nblk = counts == AD_COUNTS_PARTIAL ? (unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK) : 0u;
-        if (counts != AD_COUNTS_DONE) hipLaunchKernelGGL(k_cv_finish, dim3((unsigned)std::max<size_t>(ceil_div(c_max, 256), 1), nblk ? std::min((nblk + 7u) / 8u, 128u) : 1u, nw), dim3(256), 0, st, At, nblk, n, c->d_cvdone.as<u32>(), flag);
+        if (counts != AD_COUNTS_DONE) hipLaunchKernelGGL(k_cv_finish, dim3((unsigned)std::max<size_t>(ceil_div(c_max, 256), 1), nblk ? std::min((nblk + 7u) / 8u, 128u) : 1u, nw), dim3(256), 0, st, At, nblk, n, c->d_cvdone, flag);
         if (ipb) {
             if (path == AD_PATH_WIDE) {
                 const unsigned nb = (unsigned)ceil_div(n, 256);
-                u32* done = c->d_cvdone.as<u32>();
+                u32* done = c->d_cvdone;
                 if (counts == AD_COUNTS_DONE) {
                     if (skip_d) hipLaunchKernelGGL((k_ad_accumulate_wide<true, true>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag, done);
                     else hipLaunchKernelGGL((k_ad_accumulate_wide<false, true>), dim3(nb, nw), dim3(256), 0, st, At, n, out_stride, tot_stride, flag, done);
@@ -2732,7 +2768,7 @@ static int enqueue_ad(gev_ctx* c, int pop, int buf, size_t n, int counts, int hb
         c->ad_path = path | (counts == AD_COUNTS_DONE ? AD_PATH_FROM_COUNTS : 0);
     } else HIPC(hipMemsetAsync(c->d_flag.p, 0xff, 4, st));
     if (nchr > 1 || !nw) {                                   // one chromosome: the A/D kernels wrote the totals themselves
-        hipLaunchKernelGGL(k_ad_sum_chr, dim3((unsigned)ceil_div(n * nphen, 256)), dim3(256), 0, st, c->d_addchr.as<double>(), c->d_domchr.as<double>(), c->d_add.as<double>(), c->d_dom.as<double>(), n, nchr, nphen);
+        hipLaunchKernelGGL(k_ad_sum_chr, dim3((unsigned)ceil_div(n * nphen, 256)), dim3(256), 0, st, c->d_addchr, c->d_domchr, c->d_add, c->d_dom, n, nchr, nphen);
         KCHECK();
     }
     // results to the pinned host cache: [flag | additive | dominance].  The per-chromosome arrays stay on the device and are
@@ -2795,7 +2831,7 @@ int gev_compute_ad_device(gev_ctx* c, int pop, double** add_chr, double** dom_ch
     if (!add_chr || !dom_chr || !n_doubles) return fail(GEV_EINVAL, "compute_ad_device: null argument");
     GEVC(gev_compute_ad(c, pop, nullptr, nullptr, nullptr, nullptr));          // (computes unless the last generation already did; checks the NaN flag)
     PopState& P = c->pop[pop];
-    *add_chr = c->d_addchr.as<double>(); *dom_chr = c->d_domchr.as<double>(); *n_doubles = P.n_people * (size_t)c->nchr * c->nphen;
+    *add_chr = c->d_addchr; *dom_chr = c->d_domchr; *n_doubles = P.n_people * (size_t)c->nchr * c->nphen;
     return GEV_OK;
 }
 int gev_ad_finish_device(gev_ctx* c, int pop, double* additive, double* dominance, double* add_chr_out, double* dom_chr_out)
@@ -2808,8 +2844,8 @@ int gev_ad_finish_device(gev_ctx* c, int pop, double* additive, double* dominanc
     hipStream_t st = c->stream;
     const size_t n = P.n_people; const int nchr = c->nchr, nphen = c->nphen;
     const size_t nd = n * nphen, ndc = nd * nchr;
-    GEVC(c->d_add.ensure(nd * sizeof(double), st)); GEVC(c->d_dom.ensure(nd * sizeof(double), st));
-    hipLaunchKernelGGL(k_ad_sum_chr, dim3((unsigned)ceil_div(n * nphen, 256)), dim3(256), 0, st, c->d_addchr.as<double>(), c->d_domchr.as<double>(), c->d_add.as<double>(), c->d_dom.as<double>(), n, nchr, nphen);
+    GEVC(c->d_add.ensure(nd, st)); GEVC(c->d_dom.ensure(nd, st));
+    hipLaunchKernelGGL(k_ad_sum_chr, dim3((unsigned)ceil_div(n * nphen, 256)), dim3(256), 0, st, c->d_addchr, c->d_domchr, c->d_add, c->d_dom, n, nchr, nphen);
     KCHECK();
     if (additive) HIPC(hipMemcpyAsync(additive, c->d_add.p, nd * sizeof(double), hipMemcpyDeviceToHost, st));
     if (dominance) HIPC(hipMemcpyAsync(dominance, c->d_dom.p, nd * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2833,11 +2869,11 @@ static size_t ph_candidates(const gev_ctx* c, size_t n, int shift)
 static int ph_var(gev_ctx* c, const double* base, size_t vec_stride, size_t elem_stride, size_t n, unsigned nvec, double* stats)
 {
     hipStream_t st = c->stream;
-    GEVC(c->ph.partial.ensure((size_t)nvec * 256 * sizeof(double), st));
+    GEVC(c->ph.partial.ensure((size_t)nvec * 256, st));
     const int nb = (int)std::min<size_t>(ceil_div(n, 256), 256);
     for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(k_ph_var_partial, dim3(nb, nvec), dim3(256), 0, st, base, vec_stride, elem_stride, n, (const double*)stats, pass, c->ph.partial.as<double>());
-        hipLaunchKernelGGL(k_ph_var_final, dim3(nvec), dim3(256), 0, st, (const double*)c->ph.partial.as<double>(), nb, n, pass, stats);
+        hipLaunchKernelGGL(k_ph_var_partial, dim3(nb, nvec), dim3(256), 0, st, base, vec_stride, elem_stride, n, (const double*)stats, pass, c->ph.partial);
+        hipLaunchKernelGGL(k_ph_var_final, dim3(nvec), dim3(256), 0, st, c->ph.partial, nb, n, pass, stats);
     }
     KCHECK();
     return GEV_OK;
@@ -2849,10 +2885,10 @@ static int ph_streams(gev_ctx* c, std::vector<NrmStream>& v, const u32* seeds, u
     hipStream_t st = c->stream;
     u32 off = 0, nb_max = 0;
     for (NrmStream& s : v) { s.n_blocks = (u32)ceil_div((size_t)s.n_cand, POLAR_CHUNK); s.blk_off = off; off += s.n_blocks; nb_max = std::max(nb_max, s.n_blocks); }
-    GEVC(c->ph.blk.ensure(off * sizeof(u32), st));
-    GEVC(upload_table(c, c->ph.streams, v.data(), v.size() * sizeof(NrmStream), st));
-    hipLaunchKernelGGL(k_nrm_count, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, (const u32*)starts, c->ph.blk.as<u32>());
-    hipLaunchKernelGGL(k_nrm_emit, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, (const NrmStream*)c->ph.streams.as<NrmStream>(), seeds, starts, (const u32*)c->ph.blk.as<u32>(), flag);
+    GEVC(c->ph.blk.ensure(off, st));
+    GEVC(upload_table(c, c->ph.streams, v.data(), v.size(), st));
+    hipLaunchKernelGGL(k_nrm_count, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, c->ph.streams, seeds, (const u32*)starts, c->ph.blk);
+    hipLaunchKernelGGL(k_nrm_emit, dim3(nb_max, (unsigned)v.size()), dim3(256), 0, st, c->ph.streams, seeds, starts, c->ph.blk, flag);
     KCHECK();
     return GEV_OK;
 }
@@ -2871,8 +2907,8 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
     if (c->ad_cached_pop != pop && c->ad_host_set_pop != pop) GEVC(gev_compute_ad(c, pop, nullptr, nullptr, nullptr, nullptr));      // raw A/D of this generation on the device
     hipStream_t st = c->stream;
     const size_t n = P.n_people;
-    GEVC(c->d_gef_io.ensure(10 * n * sizeof(double), st));
-    double* io = c->d_gef_io.as<double>();
+    GEVC(c->d_gef_io.ensure(10 * n, st));
+    double* io = c->d_gef_io;
     double *d_e = io, *d_par = io + n, *d_cs = io + 2 * n, *d_ff = io + 3 * n, *d_out = io + 4 * n;     // d_out: 6 vectors
     GEVC(c->d_gef_stat.ensure(GEF_WORDS * sizeof(u32) + 2 * sizeof(double), st));
     u32* stat = c->d_gef_stat.as<u32>(); double* e_stats = (double*)(stat + GEF_WORDS);
@@ -2890,8 +2926,8 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
     if (par->va > 0) s_a = std::sqrt(par->s2_a_gen0 / par->va);
     double s_d = 0;
     if (par->vd > 0) s_d = std::sqrt(par->s2_d_gen0 / par->vd); else if (par->vd == -1) s_d = 1;
-    DevBuf& keep = P.d_phen[P.sbuf];                                                                     // the population's phenotypes, for gev_compute_selection
-    GEVC(keep.ensure(n * (size_t)c->nphen * sizeof(double), st, /*keep=*/true));
+    Dev<double>& keep = P.d_phen[P.sbuf];                                                                     // the population's phenotypes, for gev_compute_selection
+    GEVC(keep.ensure(n * (size_t)c->nphen, st, /*keep=*/true));
     double* outs[6] = {additive, dominance, bv, e_noise, parental_effect, phen_out};
     // the streams, var(e), the scaling and the copies out, with twice the candidate pairs while a stream runs short of them
     // (practically never: acceptance far below pi/4)
@@ -2904,9 +2940,9 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
         if (par->gen_num == 0 && need_par) { NrmStream f = e; f.seed_add = 1; f.sd = std::sqrt(par->vf); f.out = d_par; batch.push_back(f); }   // generator_f(seed+1), :3095-3114
         GEVC(ph_streams(c, batch, nullptr, stat + GEF_STARTS, stat + GEF_FLAG));
         GEVC(ph_var(c, d_e, n, 1, n, 1, e_stats));                                                        // CommFunc::var(e): two passes, n-1
-        hipLaunchKernelGGL(k_gef_apply, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, c->d_add.as<double>() + phen, c->d_dom.as<double>() + phen, (size_t)c->nphen,
+        hipLaunchKernelGGL(k_gef_apply, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, c->d_add + phen, c->d_dom + phen, (size_t)c->nphen,
                            d_e, (const double*)e_stats, d_par, common_sibling ? d_cs : (const double*)nullptr, n, s_a, s_d, par->ve, par->vf,
-                           d_out, d_out + n, d_out + 2 * n, d_out + 3 * n, d_out + 4 * n, d_out + 5 * n, keep.as<double>() + phen);
+                           d_out, d_out + n, d_out + 2 * n, d_out + 3 * n, d_out + 4 * n, d_out + 5 * n, keep + phen);
         KCHECK();
         for (int k = 0; k < 6; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], d_out + k * n, n * sizeof(double), hipMemcpyDeviceToHost, st));
         u32 flag = 0;
@@ -2930,7 +2966,7 @@ int gev_set_ad(gev_ctx* c, int pop, const double* additive, const double* domina
     HIPC(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t nd = P.n_people * (size_t)c->nphen;
-    GEVC(c->d_add.ensure(nd * sizeof(double), st)); GEVC(c->d_dom.ensure(nd * sizeof(double), st));
+    GEVC(c->d_add.ensure(nd, st)); GEVC(c->d_dom.ensure(nd, st));
     HIPC(hipMemcpyAsync(c->d_add.p, additive, nd * sizeof(double), hipMemcpyHostToDevice, st));
     HIPC(hipMemcpyAsync(c->d_dom.p, dominance, nd * sizeof(double), hipMemcpyHostToDevice, st));
     HIPC(hipStreamSynchronize(st));
@@ -2960,12 +2996,12 @@ int gev_compute_selection(gev_ctx* c, int pop, const gev_selection_params* par, 
     a.nphen = c->nphen; a.func = par->func; a.gen_num = par->gen_num; a.par1 = par->par1; a.par2 = par->par2;
     for (int p = 0; p < c->nphen; p++) { a.omega[p] = par->omega[p]; a.lambda[p] = par->lambda[p]; a.shift[p] = par->phen_shift ? par->phen_shift[p] : 0.0; }
     const size_t n = P.n_people;
-    DevBuf& V = P.d_sel[P.sbuf];
-    GEVC(V.ensure(3 * n * sizeof(double), st));
-    GEVC(P.d_sv0.ensure(2 * sizeof(double), st, /*keep=*/true));
-    double *mv = V.as<double>(), *sv = mv + n, *svf = mv + 2 * n, *sv0 = P.d_sv0.as<double>();
+    Dev<double>& V = P.d_sel[P.sbuf];
+    GEVC(V.ensure(3 * n, st));
+    GEVC(P.d_sv0.ensure(2, st, /*keep=*/true));
+    double *mv = V, *sv = mv + n, *svf = mv + 2 * n, *sv0 = P.d_sv0;
     const unsigned nbk = (unsigned)ceil_div(n, 256);
-    hipLaunchKernelGGL(k_sel_values, dim3(nbk), dim3(256), 0, st, (const double*)P.d_phen[P.sbuf].as<double>(), n, a, (const double*)sv0, gen0 ? 0 : 1, mv, sv, svf);
+    hipLaunchKernelGGL(k_sel_values, dim3(nbk), dim3(256), 0, st, P.d_phen[P.sbuf], n, a, (const double*)sv0, gen0 ? 0 : 1, mv, sv, svf);
     if (gen0) {                                             // _gen0_SV_mean / _gen0_SV_var (:3326-3330), kept on the device
         GEVC(ph_var(c, sv, 1, 1, n, 1, sv0));
         hipLaunchKernelGGL(k_sel_finish, dim3(nbk), dim3(256), 0, st, n, a, (const double*)sv0, sv, svf);
@@ -2986,7 +3022,7 @@ int gev_download_selection(gev_ctx* c, int pop, double* mating_value, double* se
     HIPC(hipSetDevice(c->device));
     const size_t n = P.n_people;
     double* outs[3] = {mating_value, selection_value, selection_value_func};
-    for (int k = 0; k < 3; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], P.d_sel[P.sbuf].as<double>() + k * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < 3; k++) if (outs[k]) HIPC(hipMemcpyAsync(outs[k], P.d_sel[P.sbuf] + k * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     return GEV_OK;
 }
@@ -3010,8 +3046,8 @@ int gev_set_selection_gen0(gev_ctx* c, int pop, double mean, double var)
     if (c->pend.active) return fail(GEV_ESTATE, "set_selection_gen0: a generation is pending");
     PopState& P = c->pop[pop];
     HIPC(hipSetDevice(c->device));
-    GEVC(P.d_sv0.ensure(2 * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_sel_set_gen0, dim3(1), dim3(64), 0, c->stream, P.d_sv0.as<double>(), mean, var);
+    GEVC(P.d_sv0.ensure(2, c->stream));
+    hipLaunchKernelGGL(k_sel_set_gen0, dim3(1), dim3(64), 0, c->stream, P.d_sv0, mean, var);
     KCHECK();
     P.sv0_ok = true;
     return GEV_OK;
@@ -3086,10 +3122,10 @@ static int selected_lists_count(gev_ctx* c, PopState& P, int k, const u32* rows,
     ChrState& cs = P.st[k];
     const bool track = c->track_intervals, pieces = !cs.csr_valid;
     if (pieces)
-        hipLaunchKernelGGL(k_lp_count, dim3((unsigned)ceil_div(n_rows * LP_MAXSEG, 256)), dim3(256), 0, c->stream, track ? cs.lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr,
-                           cs.lp.mtab[P.cur].as<uint2>(), cs.lp.nseg, rows, n_rows, track ? pcnt : (u32*)nullptr, mcnt);
+        hipLaunchKernelGGL(k_lp_count, dim3((unsigned)ceil_div(n_rows * LP_MAXSEG, 256)), dim3(256), 0, c->stream, track ? cs.lp.ptab[P.cur] : (const uint2*)nullptr,
+                           cs.lp.mtab[P.cur], cs.lp.nseg, rows, n_rows, track ? pcnt : (u32*)nullptr, mcnt);
     else for (int pass = 0; pass < (track ? 2 : 1); pass++)
-        hipLaunchKernelGGL(k_csr_gather_count, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, c->stream, pass == 0 ? cs.moff[P.cur].as<u32>() : cs.poff[P.cur].as<u32>(),
+        hipLaunchKernelGGL(k_csr_gather_count, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, c->stream, pass == 0 ? cs.moff[P.cur] : cs.poff[P.cur],
                            rows, n_rows, pass == 0 ? mcnt : pcnt);
     KCHECK();
     return GEV_OK;
@@ -3101,11 +3137,11 @@ static int selected_lists_fill(gev_ctx* c, PopState& P, int k, const u32* rows, 
     const bool track = c->track_intervals, pieces = !cs.csr_valid;
     const unsigned blocks = (unsigned)ceil_div(n_rows, 256);
     if (pieces)
-        hipLaunchKernelGGL(k_lp_fill, dim3((unsigned)ceil_div(n_rows * LP_MAXSEG, 256)), dim3(256), 0, c->stream, track ? cs.lp.ptab[P.cur].as<uint2>() : (const uint2*)nullptr,
-                           cs.lp.mtab[P.cur].as<uint2>(), cs.lp.parena.as<LpPart>(), cs.lp.marena.as<u64>(), cs.lp.nseg, rows, n_rows, (u64)P.cs[k].rbp.back(), poff, parts, moff, mpos);
+        hipLaunchKernelGGL(k_lp_fill, dim3((unsigned)ceil_div(n_rows * LP_MAXSEG, 256)), dim3(256), 0, c->stream, track ? cs.lp.ptab[P.cur] : (const uint2*)nullptr,
+                           cs.lp.mtab[P.cur], cs.lp.parena, cs.lp.marena, cs.lp.nseg, rows, n_rows, (u64)P.cs[k].rbp.back(), poff, parts, moff, mpos);
     else {
-        hipLaunchKernelGGL((k_csr_gather_fill<u64>), dim3(blocks), dim3(256), 0, c->stream, cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), rows, n_rows, moff, mpos);
-        if (track) hipLaunchKernelGGL((k_csr_gather_fill<gev_part>), dim3(blocks), dim3(256), 0, c->stream, cs.poff[P.cur].as<u32>(), cs.parts[P.cur].as<gev_part>(), rows, n_rows, poff, parts);
+        hipLaunchKernelGGL((k_csr_gather_fill<u64>), dim3(blocks), dim3(256), 0, c->stream, cs.moff[P.cur], cs.mpos[P.cur], rows, n_rows, moff, mpos);
+        if (track) hipLaunchKernelGGL((k_csr_gather_fill<gev_part>), dim3(blocks), dim3(256), 0, c->stream, cs.poff[P.cur], cs.parts[P.cur], rows, n_rows, poff, parts);
     }
     KCHECK();
     return GEV_OK;
@@ -3132,20 +3168,20 @@ static int gather_population(gev_ctx* c, int dst, const GatherPlan& gp)
     const int alt = D.cur ^ 1;
     const size_t rows_new = 2 * gp.n_new[dst];
     const bool track = c->track_intervals;
-    GEVC(c->d_cnt.ensure(2 * (rows_new + 1) * sizeof(u32), st));
-    u32* mcnt = c->d_cnt.as<u32>(); u32* pcnt = mcnt + rows_new + 1;
+    GEVC(c->d_cnt.ensure(2 * (rows_new + 1), st));
+    u32* mcnt = c->d_cnt; u32* pcnt = mcnt + rows_new + 1;
     for (int k = 0; k < c->nchr; k++) {
         if (!c->chr_active[k]) continue;                // held by another context of a locus-split population
         ChrStatic& S = D.cs[k]; ChrState& ds = D.st[k];
-        u32* moff = ds.moff[alt].as<u32>(); u32* poff = ds.poff[alt].as<u32>();
+        u32* moff = ds.moff[alt]; u32* poff = ds.poff[alt];
         GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int { return selected_lists_count(c, Sp, k, g.rows, 2 * g.m, mcnt + 2 * g.i0, pcnt + 2 * g.i0); }));
         u32 tot_m = 0, tot_p = 0;                       // (the totals size the destination's list buffers: these syncs stay)
         GEVC(scan_u32(c, mcnt, rows_new, moff, &tot_m));
         if (track) GEVC(scan_u32(c, pcnt, rows_new, poff, &tot_p));
-        GEVC(ds.mpos[alt].ensure(std::max<size_t>(tot_m, 2) * sizeof(u64), st, false, 1.25)); ds.mut_total[alt] = tot_m;
-        if (track) { GEVC(ds.parts[alt].ensure(std::max<size_t>(tot_p, 1) * sizeof(gev_part), st, false, 1.25)); ds.parts_total[alt] = tot_p; }
+        GEVC(ds.mpos[alt].ensure(std::max<size_t>(tot_m, 2), st, false, 1.25)); ds.mut_total[alt] = tot_m;
+        if (track) { GEVC(ds.parts[alt].ensure(std::max<size_t>(tot_p, 1), st, false, 1.25)); ds.parts_total[alt] = tot_p; }
         GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int {
-            return selected_lists_fill(c, Sp, k, g.rows, 2 * g.m, moff + 2 * g.i0, ds.mpos[alt].as<u64>(), poff + 2 * g.i0, ds.parts[alt].as<gev_part>());
+            return selected_lists_fill(c, Sp, k, g.rows, 2 * g.m, moff + 2 * g.i0, ds.mpos[alt], poff + 2 * g.i0, ds.parts[alt]);
         }));
         // genotype rows: fresh pool rows of the destination, filled from the sources' pools
         PoolWork dpw{};
@@ -3160,12 +3196,12 @@ static int gather_population(gev_ctx* c, int dst, const GatherPlan& gp)
             const u32 chunks = (u32)(S.stride / 16);
             if (c->dense)
                 hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * g.m * chunks, 256)), dim3(256), 0, st,
-                                   pool_rows(D, k, dpw.phys_alt + 2 * g.i0 * S.nseg), pool_rows(Sp, k, Sp.st[k].phys[Sp.pcur].as<u32>()), g.rows, (size_t)0, 2 * g.m, chunks);
+                                   pool_rows(D, k, dpw.phys_alt + 2 * g.i0 * S.nseg), pool_rows(Sp, k, Sp.st[k].phys[Sp.pcur]), g.rows, (size_t)0, 2 * g.m, chunks);
             for (int p = 0; p < c->nphen; p++) {
                 CvStatic& V = D.cv[p][k];
                 const u32 cch = V.stride_w32 / 4;
                 hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)ceil_div(2 * g.m * cch, 256)), dim3(256), 0, st,
-                                   (uint4*)(D.cvp[p][k][alt].as<u32>() + 2 * g.i0 * V.stride_w32), (size_t)cch,
+                                   (uint4*)(D.cvp[p][k][alt] + 2 * g.i0 * V.stride_w32), (size_t)cch,
                                    (const uint4*)Sp.cvp[p][k][Sp.cur].p, (size_t)Sp.cv[p][k].stride_w32 / 4, g.rows, 2 * g.m, cch);
                 V.frq_valid = false;
             }
@@ -3175,7 +3211,7 @@ static int gather_population(gev_ctx* c, int dst, const GatherPlan& gp)
     }
     // Human::sex follows the individuals (what gev_random_mate reads)
     GEVC(for_segments(c, gp, dst, [&](PopState& Sp, const PlanSeg& g) -> int {
-        hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(g.m, 256)), dim3(256), 0, st, D.d_sex[alt].as<uint8_t>() + g.i0, Sp.d_sex[Sp.cur].as<uint8_t>(), g.people, 0u, g.m);
+        hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(g.m, 256)), dim3(256), 0, st, D.d_sex[alt] + g.i0, Sp.d_sex[Sp.cur], g.people, 0u, g.m);
         KCHECK();
         return GEV_OK;
     }));
@@ -3196,9 +3232,9 @@ static int materialize_order(gev_ctx* c, int pop)
     GEVC(gather_population(c, pop, gp));
     if (P.ids_ok) {                                         // the pedigree ids are kept by physical row: they move with the rows
         const int nb = P.ibuf ^ 1;
-        GEVC(P.d_ids[nb].ensure(PED_FIELDS * P.n_people * sizeof(int64_t), c->stream));
+        GEVC(P.d_ids[nb].ensure(PED_FIELDS * P.n_people, c->stream));
         GEVC(for_segments(c, gp, pop, [&](PopState& S, const PlanSeg& g) -> int {
-            return gather_planes(c, PED_FIELDS, P.d_ids[nb].as<int64_t>() + g.i0, P.n_people, S.d_ids[S.ibuf].p, S.ids_stride[S.ibuf], g);
+            return gather_planes(c, PED_FIELDS, P.d_ids[nb] + g.i0, P.n_people, S.d_ids[S.ibuf].p, S.ids_stride[S.ibuf], g);
         }));
         P.ids_stride[nb] = P.n_people; P.ibuf = nb;
     }
@@ -3228,17 +3264,17 @@ static int migrate_selection(gev_ctx* c, const GatherPlan& gp)
         phen_ok[d] = every_source(c, gp, d, [&](const PopState& S) { return std::all_of(S.phen_ok.begin(), S.phen_ok.end(), [](uint8_t v) { return v != 0; }); });
         sel_ok[d] = every_source(c, gp, d, [](const PopState& S) { return S.sel_ok; });
         if (phen_ok[d]) {                               // interleaved [n][nphen]
-            GEVC(D.d_phen[nb].ensure(n * nph * sizeof(double), st));
+            GEVC(D.d_phen[nb].ensure(n * nph, st));
             GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int {
-                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(g.m * nph, 256)), dim3(256), 0, st, D.d_phen[nb].as<double>() + g.i0 * nph,
-                                   (const double*)S.d_phen[S.sbuf].as<double>(), g.people, g.m, nph);
+                hipLaunchKernelGGL(k_gather_f64, dim3((unsigned)ceil_div(g.m * nph, 256)), dim3(256), 0, st, D.d_phen[nb] + g.i0 * nph,
+                                   S.d_phen[S.sbuf], g.people, g.m, nph);
                 KCHECK();
                 return GEV_OK;
             }));
         }
         if (sel_ok[d]) {                                // [3][n]: mating_value, selection_value, selection_value_func
-            GEVC(D.d_sel[nb].ensure(3 * n * sizeof(double), st));
-            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, 3, D.d_sel[nb].as<double>() + g.i0, n, S.d_sel[S.sbuf].p, S.n_people, g); }));
+            GEVC(D.d_sel[nb].ensure(3 * n, st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, 3, D.d_sel[nb] + g.i0, n, S.d_sel[S.sbuf].p, S.n_people, g); }));
         }
     }
     for (int d = 0; d < c->n_pop; d++) {
@@ -3262,13 +3298,13 @@ static int migrate_pedigree(gev_ctx* c, const GatherPlan& gp)
         comp_ok[d] = every_source(c, gp, d, [](const PopState& S) { return S.comp_ok; });
         if (ids_ok[d]) {
             const int nb = D.ibuf ^ 1;
-            GEVC(D.d_ids[nb].ensure(PED_FIELDS * n * sizeof(int64_t), st));
-            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, PED_FIELDS, D.d_ids[nb].as<int64_t>() + g.i0, n, S.d_ids[S.ibuf].p, S.ids_stride[S.ibuf], g); }));
+            GEVC(D.d_ids[nb].ensure(PED_FIELDS * n, st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, PED_FIELDS, D.d_ids[nb] + g.i0, n, S.d_ids[S.ibuf].p, S.ids_stride[S.ibuf], g); }));
         }
         if (comp_ok[d]) {
             const int nb = D.cbuf ^ 1;
-            GEVC(D.d_comp[nb].ensure((size_t)planes * n * sizeof(double), st));
-            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, planes, D.d_comp[nb].as<double>() + g.i0, n, S.d_comp[S.cbuf].p, S.n_people, g); }));
+            GEVC(D.d_comp[nb].ensure((size_t)planes * n, st));
+            GEVC(for_segments(c, gp, d, [&](PopState& S, const PlanSeg& g) -> int { return gather_planes(c, planes, D.d_comp[nb] + g.i0, n, S.d_comp[S.cbuf].p, S.n_people, g); }));
         }
     }
     for (int d = 0; d < c->n_pop; d++) {
@@ -3369,11 +3405,11 @@ static int export_counts(gev_ctx* c, int pop, const uint64_t* positions, size_t 
     counts.assign(n * nchr * 4, 0);
     if (!n) return GEV_OK;
     GEVC(h2d(c, c->d_map, map.data(), map.size() * sizeof(u32)));
-    GEVC(c->d_cnt.ensure(4 * n * sizeof(u32) + 16, c->stream));
+    GEVC(c->d_cnt.ensure(4 * n + 4, c->stream));
     std::vector<u32> tmp(4 * n);                          // [mutations | interval parts] of the 2n rows
     for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
-        GEVC(selected_lists_count(c, P, k, c->d_map.as<u32>(), 2 * n, c->d_cnt.as<u32>(), c->d_cnt.as<u32>() + 2 * n));
+        GEVC(selected_lists_count(c, P, k, c->d_map.as<u32>(), 2 * n, c->d_cnt, c->d_cnt + 2 * n));
         HIPC(hipMemcpyAsync(tmp.data(), c->d_cnt.p, (c->track_intervals ? 4 : 2) * n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) for (int pass = 0; pass < 2; pass++)
@@ -3411,17 +3447,17 @@ int gev_export_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n, vo
     const int nchr = c->nchr;
     const u32* d_rows = c->d_map.as<u32>();               // haplotype rows 2*individual, 2*individual+1 (export_counts)
     HIPC(hipMemcpyAsync(out + L.counts, counts.data(), counts.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out + L.sex, P.d_sex[P.cur].as<uint8_t>(), d_rows, 1u, n);
+    hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out + L.sex, P.d_sex[P.cur], d_rows, 1u, n);
     size_t po = L.planes, co = L.cv, mo = L.muts, pa = L.parts;
-    GEVC(c->d_cnt.ensure((2 * n + 1) * sizeof(u32) * 4, st));
-    u32* mcnt = c->d_cnt.as<u32>(); u32* moff = mcnt + (2 * n + 1); u32* pcnt = moff + (2 * n + 1); u32* poff = pcnt + (2 * n + 1);
+    GEVC(c->d_cnt.ensure((2 * n + 1) * 4, st));
+    u32* mcnt = c->d_cnt; u32* moff = mcnt + (2 * n + 1); u32* pcnt = moff + (2 * n + 1); u32* poff = pcnt + (2 * n + 1);
     for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
         ChrStatic& S = P.cs[k]; ChrState& cs = P.st[k];
         const u32 chunks = (u32)(S.stride / 16);
         if (c->dense && c->migrant_rows) {
             hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * n * chunks, 256)), dim3(256), 0, st, flat_rows(out + po, S.stride),
-                               pool_rows(P, k, cs.phys[P.pcur].as<u32>()), d_rows, (size_t)0, 2 * n, chunks);
+                               pool_rows(P, k, cs.phys[P.pcur]), d_rows, (size_t)0, 2 * n, chunks);
             po = al16(po + 2 * n * S.stride);
         }
         // the records' lists, for the selected rows only, from whichever form the lists live in
@@ -3502,7 +3538,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     mark("header");
     GEVC(ensure_capacity(c, pop, n_new));                              // keeps the current buffers' content
     mark("capacity");
-    HIPC(hipMemcpyAsync(P.d_sex[P.cur].as<uint8_t>() + n_old, in + L.sex, n, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(P.d_sex[P.cur] + n_old, in + L.sex, n, hipMemcpyDeviceToDevice, st));
     size_t po = L.planes, co = L.cv, mo = L.muts, pa = L.parts;
     for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
@@ -3538,13 +3574,13 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
                 const size_t off_words = (offp.size() + 1) & ~(size_t)1;
                 std::vector<u32> up(off_words + pr.size() * sizeof(PanelRef) / sizeof(u32), 0);
                 memcpy(up.data(), offp.data(), offp.size() * sizeof(u32)); memcpy(up.data() + off_words, pr.data(), pr.size() * sizeof(PanelRef));
-                GEVC(h2d(c, c->d_poff, up.data(), up.size() * sizeof(u32)));
-                const PanelRef* d_panels = (const PanelRef*)(c->d_poff.as<u32>() + off_words);
-                GEVC(c->d_prange.ensure(std::max<size_t>(offp[2 * n], 1) * sizeof(uint2), st));
+                GEVC(h2d(c, c->d_poff, up.data(), up.size()));
+                const PanelRef* d_panels = (const PanelRef*)(c->d_poff + off_words);
+                GEVC(c->d_prange.ensure(std::max<size_t>(offp[2 * n], 1), st));
                 if (offp[2 * n]) hipLaunchKernelGGL(k_parts_locus_range, dim3((unsigned)ceil_div((size_t)offp[2 * n], 256)), dim3(256), 0, st, (const gev_part*)(in + pa), (size_t)offp[2 * n],
-                                                    P.d_chrdev.as<ChrDev>(), k, c->d_prange.as<uint2>());
-                hipLaunchKernelGGL(k_rebuild_rows, dim3((unsigned)(2 * n), (unsigned)ceil_div(chunks, 4 * REBUILD_CPW)), dim3(256), 0, st, c->d_poff.as<u32>(), (const gev_part*)(in + pa),
-                                   c->d_prange.as<uint2>(), (u32)S.L, d_panels, c->n_pop, pool_rows(P, k, pw.phys_alt + r_old * S.nseg), chunks, c->d_flag.as<u32>());
+                                                    P.d_chrdev, k, c->d_prange);
+                hipLaunchKernelGGL(k_rebuild_rows, dim3((unsigned)(2 * n), (unsigned)ceil_div(chunks, 4 * REBUILD_CPW)), dim3(256), 0, st, c->d_poff, (const gev_part*)(in + pa),
+                                   c->d_prange, (u32)S.L, d_panels, c->n_pop, pool_rows(P, k, pw.phys_alt + r_old * S.nseg), chunks, c->d_flag.as<u32>());
                 KCHECK();
             }
             mark("rows");
@@ -3555,23 +3591,23 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
             ChrState::LpState& lp = cs.lp;
             const bool track = c->track_intervals;
             const std::vector<u32> offm = record_offsets(counts, n, nchr, k, 0), offp = record_offsets(counts, n, nchr, k, 1);
-            GEVC(c->d_cnt.ensure((2 * n + 1) * sizeof(u32) * 2, st));
-            u32* d_offm = c->d_cnt.as<u32>(); u32* d_offp = d_offm + (2 * n + 1);
+            GEVC(c->d_cnt.ensure((2 * n + 1) * 2, st));
+            u32* d_offm = c->d_cnt; u32* d_offp = d_offm + (2 * n + 1);
             HIPC(hipMemcpyAsync(d_offm, offm.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
             HIPC(hipMemcpyAsync(d_offp, offp.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-            const size_t tab_bytes = (r_old + 2 * n) * lp.nseg * sizeof(uint2);
-            if (track) GEVC(lp.ptab[P.cur].ensure(tab_bytes, st, /*keep=*/true, 1.25));
-            GEVC(lp.mtab[P.cur].ensure(tab_bytes, st, /*keep=*/true, 1.25));
+            const size_t tab_entries = (r_old + 2 * n) * lp.nseg;
+            if (track) GEVC(lp.ptab[P.cur].ensure(tab_entries, st, /*keep=*/true, 1.25));
+            GEVC(lp.mtab[P.cur].ensure(tab_entries, st, /*keep=*/true, 1.25));
             const size_t need_p = track ? (size_t)lp.p_used + offp[2 * n] + 2 * n * lp.nseg : 0, need_m = (size_t)lp.m_used + offm[2 * n];
             if (need_p >= 0xfffffff0u || need_m >= 0xfffffff0u) return fail(GEV_EDEVICE, "import_rows: list arenas beyond 2^32 entries");
-            if (track && need_p > lp.parena.bytes / sizeof(LpPart)) GEVC(lp.parena.ensure(need_p * sizeof(LpPart), st, true, 1.5));
-            if (need_m > lp.marena.bytes / sizeof(u64)) GEVC(lp.marena.ensure(std::max<size_t>(need_m, 16) * sizeof(u64), st, true, 1.5));
+            if (track && need_p > lp.parena.capacity()) GEVC(lp.parena.ensure(need_p, st, true, 1.5));
+            if (need_m > lp.marena.capacity()) GEVC(lp.marena.ensure(std::max<size_t>(need_m, 16), st, true, 1.5));
             HIPC(hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(u32), st));
             hipLaunchKernelGGL(k_lp_import, dim3((unsigned)ceil_div(2 * n * LP_MAXSEG, 256)), dim3(256), 0, st,
                                track ? d_offp : (const u32*)nullptr, track ? (const gev_part*)(in + pa) : (const gev_part*)nullptr, d_offm, (const u64*)(in + mo),
-                               r_old, 2 * n, track ? lp.ptab[P.cur].as<uint2>() : (uint2*)nullptr, lp.mtab[P.cur].as<uint2>(), lp.parena.as<LpPart>(), lp.marena.as<u64>(),
-                               lp.p_used, lp.m_used, (u32)(lp.parena.bytes / sizeof(LpPart)), (u32)(lp.marena.bytes / sizeof(u64)), lp.nseg, lp.lgw, (u64)S.rbp.front(),
-                               lp.ctr.as<u32>(), lp.ctr.as<u32>() + 2);
+                               r_old, 2 * n, track ? lp.ptab[P.cur] : (uint2*)nullptr, lp.mtab[P.cur], lp.parena, lp.marena,
+                               lp.p_used, lp.m_used, (u32)(lp.parena.capacity()), (u32)(lp.marena.capacity()), lp.nseg, lp.lgw, (u64)S.rbp.front(),
+                               lp.ctr, lp.ctr + 2);
             KCHECK();
             u32 h[4] = {0, 0, 0, 0};
             HIPC(hipMemcpyAsync(h, lp.ctr.p, sizeof h, hipMemcpyDeviceToHost, st));
@@ -3585,16 +3621,16 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
             size_t& total = pass == 0 ? cs.mut_total[P.cur] : cs.parts_total[P.cur];
             const std::vector<u32> off = record_offsets(counts, n, nchr, k, pass, (u32)total);
             const size_t add = off[2 * n] - off[0];
-            DevBuf& doff = pass == 0 ? cs.moff[P.cur] : cs.poff[P.cur];
+            Dev<u32>& doff = pass == 0 ? cs.moff[P.cur] : cs.poff[P.cur];
             // offsets of the appended rows: entries r_old .. r_old + 2n (entry r_old already equals the old total)
-            HIPC(hipMemcpyAsync(doff.as<u32>() + r_old, off.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
+            HIPC(hipMemcpyAsync(doff + r_old, off.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
             HIPC(hipStreamSynchronize(st));
             if (pass == 0) {
-                GEVC(cs.mpos[P.cur].ensure(std::max<size_t>(total + add, 2) * sizeof(u64), st, /*keep=*/true, 1.25));
-                if (add) HIPC(hipMemcpyAsync(cs.mpos[P.cur].as<u64>() + total, in + mo, add * sizeof(u64), hipMemcpyDeviceToDevice, st));
+                GEVC(cs.mpos[P.cur].ensure(std::max<size_t>(total + add, 2), st, /*keep=*/true, 1.25));
+                if (add) HIPC(hipMemcpyAsync(cs.mpos[P.cur] + total, in + mo, add * sizeof(u64), hipMemcpyDeviceToDevice, st));
             } else {
-                GEVC(cs.parts[P.cur].ensure(std::max<size_t>(total + add, 1) * sizeof(gev_part), st, true, 1.25));
-                if (add) HIPC(hipMemcpyAsync(cs.parts[P.cur].as<gev_part>() + total, in + pa, add * sizeof(gev_part), hipMemcpyDeviceToDevice, st));
+                GEVC(cs.parts[P.cur].ensure(std::max<size_t>(total + add, 1), st, true, 1.25));
+                if (add) HIPC(hipMemcpyAsync(cs.parts[P.cur] + total, in + pa, add * sizeof(gev_part), hipMemcpyDeviceToDevice, st));
             }
             total += add;
         }
@@ -3603,7 +3639,7 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
         CvStatic& V = P.cv[p][k];
-        HIPC(hipMemcpyAsync(P.cvp[p][k][P.cur].as<u32>() + r_old * V.stride_w32, in + co, 2 * n * V.stride_w32 * sizeof(u32), hipMemcpyDeviceToDevice, st));
+        HIPC(hipMemcpyAsync(P.cvp[p][k][P.cur] + r_old * V.stride_w32, in + co, 2 * n * V.stride_w32 * sizeof(u32), hipMemcpyDeviceToDevice, st));
         co = al16(co + 2 * n * V.stride_w32 * sizeof(u32));
         V.frq_valid = false;
     }
@@ -3676,10 +3712,10 @@ static int stage_rows_mutated(gev_ctx* c, PopState& P, int chr, size_t slot0, si
     const u32 chunks = (u32)(S.stride / 16);
     if (!n) return GEV_OK;
     hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(n * chunks, 256)), dim3(256), 0, c->stream, flat_rows(c->d_stage.p, S.stride),
-                       pool_rows(P, chr, cs.phys[P.pcur].as<u32>()), (const u32*)nullptr, slot0, n, chunks);
+                       pool_rows(P, chr, cs.phys[P.pcur]), (const u32*)nullptr, slot0, n, chunks);
     hipLaunchKernelGGL(k_snp_apply_mut, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, c->stream,
                        row_map(P, chr), c->d_stage.as<u32>(), S.stride / 4, slot0, n,
-                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)S.L);
+                       cs.moff[P.cur], cs.mpos[P.cur], S.d_pos, (u32)S.L);
     KCHECK();
     return GEV_OK;
 }
@@ -3699,8 +3735,8 @@ static int snp_major_device(gev_ctx* c, int pop, int chr, size_t s0, size_t ns, 
     hipLaunchKernelGGL(k_transpose_tiles, dim3((unsigned)stride_w64, gy), dim3(256), 0, st, (const u64*)nullptr, row_map(P, chr), S.stride / 8, rows, (u32)S.L,
                        (u32)s0, (u32)ns, c->d_snpmajor.as<u64>(), stride_w64, wpw);
     hipLaunchKernelGGL(k_snpmajor_apply_mut, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, row_map(P, chr), rows,
-                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)S.L, (u32)s0, (u32)ns,
-                       (unsigned long long*)c->d_snpmajor.p, stride_w64);
+                       cs.moff[P.cur], cs.mpos[P.cur], S.d_pos, (u32)S.L, (u32)s0, (u32)ns,
+                       c->d_snpmajor.as<unsigned long long>(), stride_w64);
     KCHECK();
     return GEV_OK;
 }
@@ -3759,7 +3795,7 @@ static int ind_major_chunks(gev_ctx* c, int pop, int chr, size_t ind_begin, size
 }
 // a CSR list of the current generation to the host: *n = its length, hap_offsets[2 * n_people + 1] and the elements where asked for
 template <class T>
-static int download_list(gev_ctx* c, int pop, const char* who, const DevBuf& d_off, const DevBuf& d_val, T* out, u64* hap_offsets, size_t* n)
+static int download_list(gev_ctx* c, int pop, const char* who, const Dev<u32>& d_off, const Dev<T>& d_val, T* out, u64* hap_offsets, size_t* n)
 {
     if (!n) return fail(GEV_EINVAL, "%s: the list length has nowhere to go (null)", who);
     const size_t rows = 2 * c->pop[pop].n_people;
@@ -3846,8 +3882,8 @@ int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     if (!n_ind) { memset(n_het, 0, n_snps * sizeof(u32)); memset(n_hom_alt, 0, n_snps * sizeof(u32)); return GEV_OK; }
     GEVC(ensure_csr(c, pop));                                           // the overlay reads whole lists
     hipStream_t st = c->stream;
-    GEVC(c->d_snpcnt.ensure(2 * n_snps * sizeof(u32), st));
-    u32* d_het = c->d_snpcnt.as<u32>(); u32* d_hom = d_het + n_snps;
+    GEVC(c->d_snpcnt.ensure(2 * n_snps, st));
+    u32* d_het = c->d_snpcnt; u32* d_hom = d_het + n_snps;
     HIPC(hipMemsetAsync(d_het, 0, 2 * n_snps * sizeof(u32), st));
     const size_t q_first = snp_begin / SNPC_LOCI, n_q = (snp_begin + n_snps - 1) / SNPC_LOCI - q_first + 1;     // the chunks that hold a SNP of the range
     const size_t col_blocks = (q_first + n_q - 1) / SNPC_COLS - q_first / SNPC_COLS + 1;                        // the 64-chunk pieces of a row they lie in
@@ -3863,7 +3899,7 @@ int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     hipLaunchKernelGGL(plane_pass, dim3((unsigned)col_blocks, (unsigned)splits), dim3(SNPC_WAVES * 64), 0, st, row_map(P, chr), ind_begin, n_ind, (u32)ind_per_block,
                        (u32)q_first, (u32)n_q, (u32)snp_begin, (u32)n_snps, d_het, d_hom);
     hipLaunchKernelGGL(k_snp_counts_apply_mut, dim3((unsigned)ceil_div(n_ind, 256)), dim3(256), 0, st, row_map(P, chr), ind_begin, n_ind,
-                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)snp_begin, (u32)n_snps, d_het, d_hom);
+                       cs.moff[P.cur], cs.mpos[P.cur], S.d_pos, (u32)snp_begin, (u32)n_snps, d_het, d_hom);
     KCHECK();
     HIPC(hipMemcpyAsync(n_het, d_het, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
     HIPC(hipMemcpyAsync(n_hom_alt, d_hom, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -3915,7 +3951,7 @@ static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, uint32_t
     hipStream_t st = c->stream;
     bool want_mat = false;
     for (uint32_t* o : outs) want_mat = want_mat || o;
-    GEVC(c->d_bp_out.ensure(NOUT * std::min(blk, n_a) * std::min(blk, n_b) * sizeof(u32), st));
+    GEVC(c->d_bp_out.ensure(NOUT * std::min(blk, n_a) * std::min(blk, n_b), st));
     for (size_t ia = 0; ia < n_a; ia += blk) {
         const size_t na = std::min(blk, n_a - ia);
         GEVC(prep(false, ia, na, true));
@@ -3925,7 +3961,7 @@ static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, uint32_t
             GEVC(prep(true, ib, nb, ia == 0));
             if (want_mat) {
                 u32* d_out[NOUT];
-                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o] ? c->d_bp_out.as<u32>() + (size_t)o * na * nb : nullptr;
+                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o] ? c->d_bp_out + (size_t)o * na * nb : nullptr;
                 GEVC(products(na, nb, d_out));
                 for (int o = 0; o < NOUT; o++) {
                     if (!outs[o]) continue;
@@ -3952,7 +3988,7 @@ int gev_dbg_bitprod_tiles(gev_ctx* c, int mode, unsigned long long launches[2])
 // ---- genotype counts per individual and per pair of individuals (gev_paircount.h) ---------------
 // individuals [ind0, +n) of a side staged through c->d_stage (ensure_csr has run) in passes of <= ~256 MB of rows and prepared:
 // planes into `planes` (null: none; n_w4 words x n_pad individuals of x, then as many of y), counts into d_het / d_hom / d_wsum (each may be null; entry i = individual ind0 + i)
-static int pair_prep_side(gev_ctx* c, PopState& P, int chr, size_t ind0, size_t n, size_t snp_begin, size_t n_snps, DevBuf* planes,
+static int pair_prep_side(gev_ctx* c, PopState& P, int chr, size_t ind0, size_t n, size_t snp_begin, size_t n_snps, Dev<u64>* planes,
                           const u32* d_weight, u32* d_het, u32* d_hom, u64* d_wsum)
 {
     ChrStatic& S = P.cs[chr];
@@ -3960,7 +3996,7 @@ static int pair_prep_side(gev_ctx* c, PopState& P, int chr, size_t ind0, size_t 
     const size_t pass = std::max<size_t>(output_chunk(c, 256u << 20, S.stride) / 2, 1);                       // (the units are rows, as in gev_download_haps)
     GEVC(c->d_stage.ensure(std::max<size_t>(2 * std::min(pass, n) * S.stride, 16), c->stream));
     u64 *px = nullptr, *py = nullptr;
-    if (planes) { GEVC(planes->ensure(std::max<size_t>(2 * n_w4 * n_pad * 8, 16), c->stream)); px = planes->as<u64>(); py = px + n_w4 * n_pad; }
+    if (planes) { GEVC(planes->ensure(std::max<size_t>(2 * n_w4 * n_pad, 2), c->stream)); px = *planes; py = px + n_w4 * n_pad; }
     for (size_t off = 0; off < n; off += pass) {
         const size_t m = std::min(pass, n - off), cover = off + m == n ? n_pad - off : m;                     // the last pass zeroes the pad
         GEVC(stage_rows_mutated(c, P, chr, 2 * (ind0 + off), 2 * m));
@@ -4002,9 +4038,9 @@ int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     hipStream_t st = c->stream;
     const u32* d_weight = nullptr;
     if (weight) {
-        GEVC(c->d_pair_w.ensure(n_snps * sizeof(u32), st));
+        GEVC(c->d_pair_w.ensure(n_snps, st));
         HIPC(hipMemcpyAsync(c->d_pair_w.p, weight, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
-        d_weight = c->d_pair_w.as<u32>();
+        d_weight = c->d_pair_w;
     }
     GEVC(c->d_bp_cnt.ensure(n_ind * 16, st));
     u64* d_ws = c->d_bp_cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
@@ -4040,7 +4076,7 @@ int gev_pair_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, siz
         },
         [&](size_t na, size_t nb, u32* const* d_out) -> int {
             const size_t pad_a = round_up(na, BP_TILE), pad_b = round_up(nb, BP_TILE);
-            const u64 *xa = c->d_bp_a.as<u64>(), *xb = c->d_bp_b.as<u64>();
+            const u64 *xa = c->d_bp_a, *xb = c->d_bp_b;
             return bitprod_launch(c, pair_kernels, na, nb, (pad_a / BP_TILE) * (pad_b / BP_TILE), xa, xa + n_w4 * pad_a, (u32)pad_a, xb, xb + n_w4 * pad_b, (u32)pad_b, (u32)n_w4,
                                   (const u32*)d_hom_a, (const u32*)d_hom_b, (u32)na, (u32)nb, d_out[0], d_out[1], d_out[2]);
         });
@@ -4072,15 +4108,15 @@ static size_t ld_block(const gev_ctx* c, size_t n_people, size_t ind_begin, size
 struct LdSide { const u64* plane; u32 *c, *het, *hom; size_t n_pad; };
 // SNPs [s0, +n) of (pop, chr) through c->d_snpmajor into `planes` over individuals [ind_begin, +n_ind), their counts into the three
 // vectors of cnt_stride entries at d_cnt
-static int ld_prep_side(gev_ctx* c, int pop, int chr, size_t s0, size_t n, size_t ind_begin, size_t n_ind, DevBuf& planes, u32* d_cnt, size_t cnt_stride, LdSide& side)
+static int ld_prep_side(gev_ctx* c, int pop, int chr, size_t s0, size_t n, size_t ind_begin, size_t n_ind, Dev<u64>& planes, u32* d_cnt, size_t cnt_stride, LdSide& side)
 {
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind), n_pad = round_up(n, BP_TILE);
     size_t stride;
-    GEVC(planes.ensure(std::max<size_t>(n_w4 * n_pad * 8, 16), c->stream));
+    GEVC(planes.ensure(std::max<size_t>(n_w4 * n_pad, 2), c->stream));
     GEVC(snp_major_device(c, pop, chr, s0, n, stride));
-    side = LdSide{planes.as<u64>(), d_cnt, d_cnt + cnt_stride, d_cnt + 2 * cnt_stride, n_pad};
+    side = LdSide{planes, d_cnt, d_cnt + cnt_stride, d_cnt + 2 * cnt_stride, n_pad};
     hipLaunchKernelGGL(k_ld_prep, dim3((unsigned)ceil_div(n_pad, 4)), dim3(256), 0, c->stream, c->d_snpmajor.as<u64>(), stride, (u32)n, (u32)n_pad, 0u, (u32)n_pad,
-                       (u64)(2 * ind_begin), (u64)(2 * n_ind), (u32)n_w4, planes.as<u64>(), side.c, side.het, side.hom);
+                       (u64)(2 * ind_begin), (u64)(2 * n_ind), (u32)n_w4, planes, side.c, side.het, side.hom);
     KCHECK();
     return GEV_OK;
 }
@@ -4161,10 +4197,10 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_snps), bb = std::min<size_t>(blk, P.cs[chr].L);
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind);
     GEVC(c->d_bp_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
-    GEVC(c->d_ld_win.ensure(2 * n_snps * sizeof(u32), st));
+    GEVC(c->d_ld_win.ensure(2 * n_snps, st));
     GEVC(c->d_ld_score.ensure(n_snps * (sizeof(u64) + sizeof(u32)), st));
     u32* d_cnt_a = c->d_bp_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
-    u32* d_lo = c->d_ld_win.as<u32>(); u32* d_hi = d_lo + n_snps;
+    u32* d_lo = c->d_ld_win; u32* d_hi = d_lo + n_snps;
     u64* d_score = c->d_ld_score.as<u64>(); u32* d_terms = (u32*)(d_score + n_snps);
     HIPC(hipMemcpyAsync(d_lo, win_lo, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
     HIPC(hipMemcpyAsync(d_hi, win_hi, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
@@ -4257,13 +4293,13 @@ int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind), n_cg = ceil_div(n_traits, 4), slices = ceil_div(n_w4, GEV_TS_SLICE_W);
     GEVC(c->d_bp_cnt.ensure(3 * blk * sizeof(u32), st));
     if (want_sums) {
-        GEVC(c->d_ts_trait.ensure(n_traits * n_ind * sizeof(int32_t), st));
-        GEVC(c->d_ts_b.ensure(n_cg * n_w4 * 512, st));                                       // 32 individuals x 16 columns a word
-        GEVC(c->d_ts_acc.ensure(2 * n_cg * pad * 16 * sizeof(int), st));
-        GEVC(c->d_ts_out.ensure(2 * n_traits * blk * sizeof(int64_t), st));
+        GEVC(c->d_ts_trait.ensure(n_traits * n_ind, st));
+        GEVC(c->d_ts_b.ensure(n_cg * n_w4 * 32, st));                                        // 32 individuals x 16 columns a word: 512 bytes
+        GEVC(c->d_ts_acc.ensure(2 * n_cg * pad * 16, st));
+        GEVC(c->d_ts_out.ensure(2 * n_traits * blk, st));
         HIPC(hipMemcpyAsync(c->d_ts_trait.p, trait, n_traits * n_ind * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)ceil_div(n_cg * (n_w4 / 4) * 128, 256)), dim3(256), 0, st, c->d_ts_trait.as<int32_t>(), (u32)n_traits,
-                           (u64)ind_begin, (u64)n_ind, (u32)n_w4, (u32)n_cg, c->d_ts_b.as<uint4>());
+        hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)ceil_div(n_cg * (n_w4 / 4) * 128, 256)), dim3(256), 0, st, c->d_ts_trait, (u32)n_traits,
+                           (u64)ind_begin, (u64)n_ind, (u32)n_w4, (u32)n_cg, c->d_ts_b);
         KCHECK();
     }
     for (size_t off = 0; off < n_snps; off += blk) {
@@ -4276,13 +4312,13 @@ int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_
         HIPC(hipMemsetAsync(c->d_ts_acc.p, 0, 2 * n_cg * A.n_pad * 16 * sizeof(int), st));
         for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535)                                        // (a grid's z)
             hipLaunchKernelGGL(k_ts_product, dim3((unsigned)(A.n_pad / BP_TILE), (unsigned)slices, (unsigned)std::min<size_t>(n_cg - cg0, 65535)), dim3(256), 0, st,
-                               A.plane, (u32)A.n_pad, (u32)n_w4, (const uint4*)c->d_ts_b.p, (u32)n_cg, (u32)cg0, c->d_ts_acc.as<int>());
-        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_traits * n, 256)), dim3(256), 0, st, (const int*)c->d_ts_acc.p, (u32)A.n_pad, (u32)n_cg,
-                           (u32)n_traits, (u32)n, (u32)blk, c->d_ts_out.as<long long>());
+                               A.plane, (u32)A.n_pad, (u32)n_w4, c->d_ts_b, (u32)n_cg, (u32)cg0, c->d_ts_acc);
+        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_traits * n, 256)), dim3(256), 0, st, c->d_ts_acc, (u32)A.n_pad, (u32)n_cg,
+                           (u32)n_traits, (u32)n, (u32)blk, c->d_ts_out);
         KCHECK();
         int64_t* const outs[2] = {gsum, hetsum};
         for (int o = 0; o < 2; o++)
-            if (outs[o]) HIPC(hipMemcpy2DAsync(outs[o] + off, n_snps * sizeof(int64_t), c->d_ts_out.as<int64_t>() + (size_t)o * n_traits * blk, blk * sizeof(int64_t),
+            if (outs[o]) HIPC(hipMemcpy2DAsync(outs[o] + off, n_snps * sizeof(int64_t), c->d_ts_out + (size_t)o * n_traits * blk, blk * sizeof(int64_t),
                                                n * sizeof(int64_t), n_traits, hipMemcpyDeviceToHost, st));
     }
     HIPC(hipStreamSynchronize(st));
@@ -4386,11 +4422,11 @@ static int materialize_rows(gev_ctx* c, int pop, int chr, size_t row0, size_t nr
     GEVC(ensure_csr(c, pop));
     HIPC(hipMemsetAsync(plain, 0, nr * w64 * 8, st));                                     // pad bits of the last word stay 0
     hipLaunchKernelGGL(k_materialize_tile, dim3((unsigned)ceil_div(nr * ceil_div(n_snps, 32), 256)), dim3(256), 0, st,
-                       cs.poff[P.cur].as<u32>(), cs.parts[P.cur].as<gev_part>(), row0, nr, S.d_pos.as<u64>(), (u32)snp_begin, (u32)n_snps,
+                       cs.poff[P.cur], cs.parts[P.cur], row0, nr, S.d_pos, (u32)snp_begin, (u32)n_snps,
                        c->d_snpmajor.as<u32>(), w32, c->d_map.as<u64>(), c->n_pop, (u32*)plain, w32, c->d_flag.as<u32>());
     HIPC(hipMemcpyAsync(out, plain, nr * w64 * 8, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_tile_apply_mut, dim3((unsigned)ceil_div(nr, 256)), dim3(256), 0, st, (const u32*)plain, (u32*)out, w32, row0, nr,
-                       cs.moff[P.cur].as<u32>(), cs.mpos[P.cur].as<u64>(), S.d_pos.as<u64>(), (u32)snp_begin, (u32)n_snps);
+                       cs.moff[P.cur], cs.mpos[P.cur], S.d_pos, (u32)snp_begin, (u32)n_snps);
     KCHECK();
     return GEV_OK;
 }
@@ -4466,14 +4502,14 @@ int gev_download_cv(gev_ctx* c, int pop, int phen, int chr, u64* bits, size_t ro
     HIPC(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t rows = 2 * P.n_people;
-    GEVC(c->d_cvm.ensure(std::max<size_t>(rows * V.sub_w32 * sizeof(u32), 16), st));
+    GEVC(c->d_cvm.ensure(std::max<size_t>(rows * V.sub_w32, 4), st));
     GEVC(c->d_tmp.ensure(rows * row_stride_words * 8, st));
     hipLaunchKernelGGL(k_cv_resolve, dim3((unsigned)ceil_div(rows * V.sub_w32, 256)), dim3(256), 0, st,
-                       P.cvp[phen][chr][P.cur].as<u32>(), V.stride_w32, V.sub_w32, c->d_cvm.as<u32>(), rows);
+                       P.cvp[phen][chr][P.cur], V.stride_w32, V.sub_w32, c->d_cvm, rows);
     HIPC(hipMemsetAsync(c->d_tmp.p, 0, rows * row_stride_words * 8, st));
     if (V.C)
         hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)ceil_div(rows * V.sub_w32, 256)), dim3(256), 0, st,
-                           c->d_cvm.as<u32>(), (size_t)V.sub_w32, c->d_tmp.as<u32>(), row_stride_words * 2, V.sub_w32, V.d_col_of_icv.as<u32>(), V.C, rows);
+                           c->d_cvm, (size_t)V.sub_w32, c->d_tmp.as<u32>(), row_stride_words * 2, V.sub_w32, V.d_col_of_icv, V.C, rows);
     KCHECK();
     HIPC(hipMemcpyAsync(bits, c->d_tmp.p, rows * row_stride_words * 8, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -4512,7 +4548,7 @@ int gev_plane_ptr(gev_ctx* c, int pop, int chr, void** dptr, size_t* unit_bytes,
     if (c->pop[pop].gen0) GEVC(materialize_order(c, pop));
     PopState& P = c->pop[pop];
     if (dptr) *dptr = P.st[chr].pool.p;
-    if (unit_of) *unit_of = P.st[chr].phys[P.pcur].as<u32>();
+    if (unit_of) *unit_of = P.st[chr].phys[P.pcur];
     if (unit_bytes) *unit_bytes = P.cs[chr].unit_bytes();
     if (segments_per_row) *segments_per_row = P.cs[chr].nseg;
     if (n_slots) *n_slots = 2 * P.n_people;
@@ -4533,21 +4569,21 @@ static int ph_enqueue(gev_ctx* c)
     H.n = n; H.n_seeds = n_seeds; H.words = round_up(PHR_SEEDS + n_seeds, 2);
     const size_t n_stats = (size_t)nphen * (1 + PH_COMP + 2);                  // {mean, var}: e, 7 components, raw A, raw D per phenotype
     const size_t res_bytes = H.words * sizeof(u32) + n_stats * 2 * sizeof(double);
-    GEVC(H.res.ensure(res_bytes, st)); GEVC(H.starts.ensure((nphen + 2) * sizeof(u32), st));
+    GEVC(H.res.ensure(res_bytes, st)); GEVC(H.starts.ensure((nphen + 2), st));
     HIPC(hipMemsetAsync(H.res.p, 0, res_bytes, st)); HIPC(hipMemsetAsync(H.starts.p, 0, (nphen + 2) * sizeof(u32), st));
     u32* res = H.res.as<u32>(); u32* seeds = res + PHR_SEEDS;
     double* e_stats = (double*)(res + H.words); double* comp_stats = e_stats + 2 * nphen; double* a_stats = comp_stats + 2 * nphen * PH_COMP; double* d_stats = a_stats + 2 * nphen;
     // the ras_glob_seed() values: generation 0 one per phenotype with vc > 0 (:3058), then one per phenotype (:3078)
     GEVC(enqueue_glob(H.globblk, st, H.glob_state, nullptr, n_seeds, seeds, res + PHR_STATE, res + PHR_FLAGS));
-    DevBuf& comp = P.d_comp[P.cbuf];
-    GEVC(comp.ensure((size_t)nphen * PH_COMP * n * sizeof(double), st));
-    GEVC(H.eraw.ensure((size_t)nphen * n * sizeof(double), st));
+    Dev<double>& comp = P.d_comp[P.cbuf];
+    GEVC(comp.ensure((size_t)nphen * PH_COMP * n, st));
+    GEVC(H.eraw.ensure((size_t)nphen * n, st));
     const size_t cval_stride = gen0 ? 1 : std::max<size_t>(P.cs_ncouples, 1);
-    if (!gen0 && nvc) GEVC(H.cval.ensure((size_t)nphen * cval_stride * sizeof(double), st));
+    if (!gen0 && nvc) GEVC(H.cval.ensure((size_t)nphen * cval_stride, st));
     // _var_a_gen0 / _var_d_gen0 (:557-561) from the raw A/D; the host needs them for s_a / s_d: generation 0 waits once for them
     if (gen0 && !P.ad0_ok) {
-        GEVC(ph_var(c, c->d_add.as<double>(), 1, (size_t)nphen, n, (unsigned)nphen, a_stats));
-        GEVC(ph_var(c, c->d_dom.as<double>(), 1, (size_t)nphen, n, (unsigned)nphen, d_stats));
+        GEVC(ph_var(c, c->d_add, 1, (size_t)nphen, n, (unsigned)nphen, a_stats));
+        GEVC(ph_var(c, c->d_dom, 1, (size_t)nphen, n, (unsigned)nphen, d_stats));
         std::vector<double> h(4 * (size_t)nphen);
         HIPC(hipMemcpyAsync(h.data(), a_stats, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
@@ -4562,8 +4598,8 @@ static int ph_enqueue(gev_ctx* c)
     int kvc = 0;
     for (int p = 0; p < nphen; p++) {
         const gev_pheno_scheme& S = H.scheme[p];
-        double* o = comp.as<double>() + (size_t)p * PH_COMP * n;
-        NrmStream e{}; e.seed_idx = (int)(gen0 ? nvc : 0) + p; e.start_idx = e.next_idx = -1; e.n = n; e.n_cand = ph_candidates(c, n, H.cand_shift); e.sd = 1.0; e.out = H.eraw.as<double>() + (size_t)p * n;
+        double* o = comp + (size_t)p * PH_COMP * n;
+        NrmStream e{}; e.seed_idx = (int)(gen0 ? nvc : 0) + p; e.start_idx = e.next_idx = -1; e.n = n; e.n_cand = ph_candidates(c, n, H.cand_shift); e.sd = 1.0; e.out = H.eraw + (size_t)p * n;
         batch.push_back(e);
         if (gen0 && S.vc > 0) { NrmStream s = e; s.seed_idx = kvc++; s.sd = std::sqrt(S.vc); s.out = o + PH_C * n; batch.push_back(s); }
         if (gen0 && S.vf > 0) { NrmStream s = e; s.seed_add = 1; s.sd = std::sqrt(S.vf); s.out = o + PH_F * n; batch.push_back(s); }
@@ -4583,23 +4619,23 @@ static int ph_enqueue(gev_ctx* c)
         for (int p = 0; p < nphen; p++) {
             if (!(H.scheme[p].vc > 0)) continue;
             NrmStream s{}; s.seed_idx = -1; s.seed_val = P.cs_seed; s.seed_add = 1; s.start_idx = k; s.next_idx = k + 1; s.n = P.cs_ncouples; s.n_cand = ph_candidates(c, P.cs_ncouples, H.cand_shift);
-            s.sd = std::sqrt(H.scheme[p].vc); s.out = H.cval.as<double>() + (size_t)p * cval_stride;
+            s.sd = std::sqrt(H.scheme[p].vc); s.out = H.cval + (size_t)p * cval_stride;
             if (k == 0) batch.push_back(s); else chained.push_back(std::vector<NrmStream>(1, s));
             k++;
         }
     }
-    GEVC(ph_streams(c, batch, seeds, H.starts.as<u32>(), res + PHR_FLAGS));
-    for (auto& one : chained) GEVC(ph_streams(c, one, seeds, H.starts.as<u32>(), res + PHR_FLAGS));
-    GEVC(ph_var(c, H.eraw.as<double>(), n, 1, n, (unsigned)nphen, e_stats));                       // CommFunc::var(e), two passes, n-1
-    GEVC(upload_table(c, H.tasks, tasks.data(), tasks.size() * sizeof(PhTask), st));
-    DevBuf& keep = P.d_phen[P.sbuf];
-    GEVC(keep.ensure(n * (size_t)nphen * sizeof(double), st));
-    hipLaunchKernelGGL(k_ph_apply, dim3((unsigned)ceil_div(n, 256), (unsigned)nphen), dim3(256), 0, st, (const PhTask*)H.tasks.as<PhTask>(), (const double*)c->d_add.as<double>(),
-                       (const double*)c->d_dom.as<double>(), n, (u32)nphen, (const double*)H.eraw.as<double>(), (const double*)e_stats, (const double*)H.cval.as<double>(), cval_stride,
-                       (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf], (const u32*)P.d_cidx[P.ibuf].as<u32>(),
-                       (const double*)P.d_prev.as<double>(), P.prev_n, comp.as<double>(), keep.as<double>(), res);
+    GEVC(ph_streams(c, batch, seeds, H.starts, res + PHR_FLAGS));
+    for (auto& one : chained) GEVC(ph_streams(c, one, seeds, H.starts, res + PHR_FLAGS));
+    GEVC(ph_var(c, H.eraw, n, 1, n, (unsigned)nphen, e_stats));                       // CommFunc::var(e), two passes, n-1
+    GEVC(upload_table(c, H.tasks, tasks.data(), tasks.size(), st));
+    Dev<double>& keep = P.d_phen[P.sbuf];
+    GEVC(keep.ensure(n * (size_t)nphen, st));
+    hipLaunchKernelGGL(k_ph_apply, dim3((unsigned)ceil_div(n, 256), (unsigned)nphen), dim3(256), 0, st, H.tasks, c->d_add,
+                       c->d_dom, n, (u32)nphen, H.eraw, (const double*)e_stats, H.cval, cval_stride,
+                       P.d_ids[P.ibuf], P.ids_stride[P.ibuf], P.d_cidx[P.ibuf],
+                       P.d_prev, P.prev_n, comp, keep, res);
     KCHECK();
-    GEVC(ph_var(c, comp.as<double>(), n, 1, n, (unsigned)nphen * PH_COMP, comp_stats));           // CommFunc::var of A D G C E F P (:2023-2037)
+    GEVC(ph_var(c, comp, n, 1, n, (unsigned)nphen * PH_COMP, comp_stats));           // CommFunc::var of A D G C E F P (:2023-2037)
     GEVC(H.h_res.ensure(res_bytes, res_bytes * 2 + 256, st));
     HIPC(hipMemcpyAsync(H.h_res.p, H.res.p, res_bytes, hipMemcpyDeviceToHost, st));
     if (!H.ev) HIPC(hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
@@ -4684,7 +4720,7 @@ int gev_download_phenotypes(gev_ctx* c, int pop, int phen, double* out)
     if (!P.gen0 || !P.comp_ok) return fail(GEV_ESTATE, "download_phenotypes: population %d has no phenotype components of its current individuals (gev_generation_phenotypes)", pop);
     HIPC(hipSetDevice(c->device));
     const size_t n = P.n_people;
-    HIPC(hipMemcpyAsync(out, P.d_comp[P.cbuf].as<double>() + (size_t)phen * PH_COMP * n, PH_COMP * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(out, P.d_comp[P.cbuf] + (size_t)phen * PH_COMP * n, PH_COMP * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     return GEV_OK;
 }
@@ -4715,10 +4751,10 @@ int gev_save_prev_gen(gev_ctx* c, int pop, const double* phen_shift)
     HIPC(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t n = P.n_people;
-    if (phen_shift) GEVC(upload_table(c, c->ph.shift, phen_shift, c->nphen * sizeof(double), st));
-    GEVC(P.d_prev.ensure((size_t)c->nphen * 2 * n * sizeof(double), st));
-    hipLaunchKernelGGL(k_ph_save_prev, dim3((unsigned)ceil_div(n, 256), (unsigned)c->nphen), dim3(256), 0, st, (const double*)P.d_comp[P.cbuf].as<double>(), n,
-                       phen_shift ? (const double*)c->ph.shift.as<double>() : (const double*)nullptr, P.d_prev.as<double>());
+    if (phen_shift) GEVC(upload_table(c, c->ph.shift, phen_shift, c->nphen, st));
+    GEVC(P.d_prev.ensure((size_t)c->nphen * 2 * n, st));
+    hipLaunchKernelGGL(k_ph_save_prev, dim3((unsigned)ceil_div(n, 256), (unsigned)c->nphen), dim3(256), 0, st, P.d_comp[P.cbuf], n,
+                       phen_shift ? c->ph.shift : (const double*)nullptr, P.d_prev);
     KCHECK();
     P.prev_n = n; P.prev_ok = true;
     return GEV_OK;
@@ -4732,11 +4768,11 @@ int gev_upload_prev_gen(gev_ctx* c, int pop, const double* phen, const double* p
     hipStream_t st = c->stream;
     HIPC(hipStreamSynchronize(st));                         // (a phenotype step that reads the old record may be in flight)
     const size_t nphen = (size_t)c->nphen;
-    GEVC(P.d_prev.ensure(nphen * 2 * n * sizeof(double), st));
+    GEVC(P.d_prev.ensure(nphen * 2 * n, st));
     HIPC(hipMemsetAsync(P.d_prev.p, 0, nphen * 2 * n * sizeof(double), st));
     for (size_t p = 0; p < nphen; p++) {
-        if (phen) HIPC(hipMemcpyAsync(P.d_prev.as<double>() + (p * 2 + 0) * n, phen + p * n, n * sizeof(double), hipMemcpyHostToDevice, st));
-        if (parental_effect) HIPC(hipMemcpyAsync(P.d_prev.as<double>() + (p * 2 + 1) * n, parental_effect + p * n, n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (phen) HIPC(hipMemcpyAsync(P.d_prev + (p * 2 + 0) * n, phen + p * n, n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (parental_effect) HIPC(hipMemcpyAsync(P.d_prev + (p * 2 + 1) * n, parental_effect + p * n, n * sizeof(double), hipMemcpyHostToDevice, st));
     }
     HIPC(hipStreamSynchronize(st));
     P.prev_n = n; P.prev_ok = true;
@@ -4778,9 +4814,9 @@ int gev_download_pedigree(gev_ctx* c, int pop, int64_t* ids)
     hipStream_t st = c->stream;
     const size_t n = P.n_people;
     const u32* logical = nullptr;
-    if (!P.logical.empty()) { GEVC(h2d(c, c->d_logical, P.logical.data(), n * sizeof(u32))); logical = c->d_logical.as<u32>(); }
+    if (!P.logical.empty()) { GEVC(h2d(c, c->d_logical, P.logical.data(), n)); logical = c->d_logical; }
     GEVC(c->d_tmp.ensure(n * PED_FIELDS * sizeof(int64_t), st));
-    hipLaunchKernelGGL(k_ped_records, dim3((unsigned)ceil_div(n * PED_FIELDS, 256)), dim3(256), 0, st, (const int64_t*)P.d_ids[P.ibuf].as<int64_t>(), P.ids_stride[P.ibuf],
+    hipLaunchKernelGGL(k_ped_records, dim3((unsigned)ceil_div(n * PED_FIELDS, 256)), dim3(256), 0, st, P.d_ids[P.ibuf], P.ids_stride[P.ibuf],
                        logical, n, c->d_tmp.as<int64_t>());
     KCHECK();
     HIPC(hipMemcpyAsync(ids, c->d_tmp.p, n * PED_FIELDS * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -4801,7 +4837,7 @@ int gev_upload_pedigree(gev_ctx* c, int pop, const int64_t* ids)
         if (r >= rows) return fail(GEV_EDEVICE, "upload_pedigree: position %zu names row %zu of %zu (internal error)", i, r, rows);
         for (int f = 0; f < PED_FIELDS; f++) planes[f * rows + r] = ids[i * PED_FIELDS + f];
     }
-    GEVC(h2d(c, P.d_ids[P.ibuf], planes.data(), planes.size() * sizeof(int64_t)));
+    GEVC(h2d(c, P.d_ids[P.ibuf], planes.data(), planes.size()));
     P.ids_stride[P.ibuf] = rows; P.ids_ok = true;
     return GEV_OK;
 }
@@ -4809,7 +4845,7 @@ int gev_upload_pedigree(gev_ctx* c, int pop, const int64_t* ids)
 static int fmt_ready(gev_ctx* c)
 {
     if (c->fm.ready) return GEV_OK;
-    GEVC(h2d(c, c->fm.tables, &gev_fmt_host_tables(), sizeof(GevFmtTables)));
+    GEVC(h2d(c, c->fm.tables, &gev_fmt_host_tables(), 1));
     c->fm.ready = true;
     return GEV_OK;
 }
@@ -4842,17 +4878,17 @@ int gev_format_info_text(gev_ctx* c, int pop, size_t ind_begin, size_t n_ind, in
     u64 total = 0;
     const size_t nb = ceil_div(n_ind, INFO_ROWS);
     gev_ctx::FmtState& F = c->fm;
-    const int64_t* ids = P.d_ids[P.ibuf].as<int64_t>(); const size_t ids_stride = P.ids_stride[P.ibuf];
-    const uint8_t* sex = P.d_sex[P.cur].as<uint8_t>();
-    const double* comp = P.d_comp[P.cbuf].as<double>(); const double* sel = P.d_sel[P.sbuf].as<double>();
+    const int64_t* ids = P.d_ids[P.ibuf]; const size_t ids_stride = P.ids_stride[P.ibuf];
+    const uint8_t* sex = P.d_sex[P.cur];
+    const double* comp = P.d_comp[P.cbuf]; const double* sel = P.d_sel[P.sbuf];
     if (n_ind) {
         GEVC(fmt_ready(c));
-        GEVC(F.lens.ensure(n_ind * sizeof(u32), st)); GEVC(F.bsum.ensure(nb * sizeof(u32), st)); GEVC(F.boff.ensure((nb + 1) * sizeof(u64), st));
-        hipLaunchKernelGGL(k_info_rows<false>, dim3((unsigned)nb), dim3(INFO_ROWS), 0, st, (const GevFmtTables*)F.tables.as<GevFmtTables>(), ids, ids_stride, sex, comp, sel, n, nphen,
-                           ind_begin, n_ind, F.lens.as<u32>(), F.bsum.as<u32>(), (const u64*)nullptr, (char*)nullptr);
-        hipLaunchKernelGGL(k_info_scan64, dim3(1), dim3(256), 0, st, (const u32*)F.bsum.as<u32>(), nb, F.boff.as<u64>());
+        GEVC(F.lens.ensure(n_ind, st)); GEVC(F.bsum.ensure(nb, st)); GEVC(F.boff.ensure((nb + 1), st));
+        hipLaunchKernelGGL(k_info_rows<false>, dim3((unsigned)nb), dim3(INFO_ROWS), 0, st, F.tables, ids, ids_stride, sex, comp, sel, n, nphen,
+                           ind_begin, n_ind, F.lens, F.bsum, (const u64*)nullptr, (char*)nullptr);
+        hipLaunchKernelGGL(k_info_scan64, dim3(1), dim3(256), 0, st, F.bsum, nb, F.boff);
         KCHECK();
-        HIPC(hipMemcpyAsync(&total, F.boff.as<u64>() + nb, sizeof total, hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(&total, F.boff + nb, sizeof total, hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
     }
     const size_t need = hdr.size() + (size_t)total;
@@ -4862,8 +4898,8 @@ int gev_format_info_text(gev_ctx* c, int pop, size_t ind_begin, size_t n_ind, in
     memcpy(out, hdr.data(), hdr.size());
     if (!total) return GEV_OK;
     GEVC(c->d_text.ensure((size_t)total + 16, st));
-    hipLaunchKernelGGL(k_info_rows<true>, dim3((unsigned)nb), dim3(INFO_ROWS), lds_bytes, st, (const GevFmtTables*)F.tables.as<GevFmtTables>(), ids, ids_stride, sex, comp, sel, n, nphen,
-                       ind_begin, n_ind, F.lens.as<u32>(), (u32*)nullptr, (const u64*)F.boff.as<u64>(), c->d_text.as<char>());
+    hipLaunchKernelGGL(k_info_rows<true>, dim3((unsigned)nb), dim3(INFO_ROWS), lds_bytes, st, F.tables, ids, ids_stride, sex, comp, sel, n, nphen,
+                       ind_begin, n_ind, F.lens, (u32*)nullptr, F.boff, c->d_text.as<char>());
     KCHECK();
     HIPC(hipMemcpyAsync(out + hdr.size(), c->d_text.p, (size_t)total, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -4879,11 +4915,11 @@ int gev_dbg_format_g(gev_ctx* c, const double* x, size_t n, char* out, unsigned 
     hipStream_t st = c->stream;
     GEVC(fmt_ready(c));
     gev_ctx::FmtState& F = c->fm;
-    GEVC(F.x.ensure(n * sizeof(double), st)); GEVC(c->d_text.ensure(n * 16, st)); GEVC(F.cnt.ensure(sizeof(unsigned long long), st));
+    GEVC(F.x.ensure(n, st)); GEVC(c->d_text.ensure(n * 16, st)); GEVC(F.cnt.ensure(1, st));
     HIPC(hipMemcpyAsync(F.x.p, x, n * sizeof(double), hipMemcpyHostToDevice, st));
     HIPC(hipMemsetAsync(F.cnt.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_dbg_format_g, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, (const GevFmtTables*)F.tables.as<GevFmtTables>(), (const double*)F.x.as<double>(), n,
-                       c->d_text.as<uint4>(), F.cnt.as<unsigned long long>());
+    hipLaunchKernelGGL(k_dbg_format_g, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, F.tables, F.x, n,
+                       c->d_text.as<uint4>(), F.cnt);
     KCHECK();
     unsigned long long cnt = 0;
     HIPC(hipMemcpyAsync(out, c->d_text.p, n * 16, hipMemcpyDeviceToHost, st));
@@ -4937,10 +4973,10 @@ static int int_names_ready(gev_ctx* c)
     std::vector<IntNames> tab(c->n_pop);
     for (int p = 0; p < c->n_pop; p++) {
         const gev_ctx::IntState::Names& N = I.host[p];
-        GEVC(h2d(c, I.d_bytes[p], N.bytes.data(), N.bytes.size())); GEVC(h2d(c, I.d_offs[p], N.offs.data(), N.offs.size() * sizeof(u32)));
-        tab[p] = IntNames{I.d_bytes[p].as<unsigned char>(), I.d_offs[p].as<u32>(), (u64)(N.offs.size() - 1)};
+        GEVC(h2d(c, I.d_bytes[p], N.bytes.data(), N.bytes.size())); GEVC(h2d(c, I.d_offs[p], N.offs.data(), N.offs.size()));
+        tab[p] = IntNames{I.d_bytes[p], I.d_offs[p], (u64)(N.offs.size() - 1)};
     }
-    GEVC(h2d(c, I.d_names, tab.data(), tab.size() * sizeof(IntNames)));
+    GEVC(h2d(c, I.d_names, tab.data(), tab.size()));
     I.uploaded = true;
     return GEV_OK;
 }
@@ -4965,7 +5001,7 @@ int gev_format_interval_text(gev_ctx* c, int pop, int chr, int chr_label, size_t
     if (ind_begin > n || n_ind > n - ind_begin) return fail(GEV_EINVAL, "%s: individuals [%zu,%zu) beyond n_people=%zu", who, ind_begin, ind_begin + n_ind, n);
     const size_t hdr = with_header ? strlen(GEV_INT_HEADER) : 0;
     hipStream_t st = c->stream;
-    const u32* poff = cs.poff[P.cur].as<u32>(); const gev_part* parts = cs.parts[P.cur].as<gev_part>();
+    const u32* poff = cs.poff[P.cur]; const gev_part* parts = cs.parts[P.cur];
     const size_t row0 = 2 * ind_begin, row1 = 2 * (ind_begin + n_ind);
     u32 pr[2] = {0, 0};
     if (n_ind) {
@@ -4977,16 +5013,16 @@ int gev_format_interval_text(gev_ctx* c, int pop, int chr, int chr_label, size_t
     const int64_t* d_ids = nullptr; size_t id_ind0 = 0;
     if (np) {
         GEVC(int_names_ready(c));
-        if (ids) { GEVC(h2d(c, I.ids, ids, n_ind * sizeof(int64_t))); d_ids = I.ids.as<int64_t>(); id_ind0 = ind_begin; }
-        else d_ids = P.d_ids[P.ibuf].as<int64_t>() + PED_ID * P.ids_stride[P.ibuf];
-        GEVC(I.lens.ensure(np, st)); GEVC(I.bsum.ensure(nb * sizeof(u32), st)); GEVC(I.boff.ensure((nb + 1) * sizeof(u64), st)); GEVC(I.flag.ensure(sizeof(u32), st));
+        if (ids) { GEVC(h2d(c, I.ids, ids, n_ind)); d_ids = I.ids; id_ind0 = ind_begin; }
+        else d_ids = P.d_ids[P.ibuf] + PED_ID * P.ids_stride[P.ibuf];
+        GEVC(I.lens.ensure(np, st)); GEVC(I.bsum.ensure(nb, st)); GEVC(I.boff.ensure((nb + 1), st)); GEVC(I.flag.ensure(1, st));
         HIPC(hipMemsetAsync(I.flag.p, 0, sizeof(u32), st));
         hipLaunchKernelGGL(k_int_rows<false>, dim3((unsigned)nb), dim3(INT_PARTS), INT_SCAN_BYTES, st, poff, parts, row0, row1, pr[0], pr[1], d_ids, id_ind0, chr_label,
-                           (const IntNames*)I.d_names.as<IntNames>(), c->n_pop, 0u, I.lens.as<uint8_t>(), I.bsum.as<u32>(), (const u64*)nullptr, (u64)0, (char*)nullptr, I.flag.as<u32>());
-        hipLaunchKernelGGL(k_info_scan64, dim3(1), dim3(256), 0, st, (const u32*)I.bsum.as<u32>(), nb, I.boff.as<u64>());
+                           I.d_names, c->n_pop, 0u, I.lens, I.bsum, (const u64*)nullptr, (u64)0, (char*)nullptr, I.flag);
+        hipLaunchKernelGGL(k_info_scan64, dim3(1), dim3(256), 0, st, I.bsum, nb, I.boff);
         KCHECK();
         u32 flag = 0;
-        HIPC(hipMemcpyAsync(&total, I.boff.as<u64>() + nb, sizeof total, hipMemcpyDeviceToHost, st));
+        HIPC(hipMemcpyAsync(&total, I.boff + nb, sizeof total, hipMemcpyDeviceToHost, st));
         HIPC(hipMemcpyAsync(&flag, I.flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
         HIPC(hipStreamSynchronize(st));
         if (flag) return fail(GEV_EINVAL, "%s: a part of population %d names a founder (hap_index / 2) beyond the names of its root population", who, pop);
@@ -5011,7 +5047,7 @@ int gev_format_interval_text(gev_ctx* c, int pop, int chr, int chr_label, size_t
         if (o1 == o0) continue;
         GEVC(copy_out_text(c, (size_t)(o1 - o0), out + hdr + o0, [&] {
             hipLaunchKernelGGL(k_int_rows<true>, dim3((unsigned)(b1 - b0)), dim3(INT_PARTS), INT_SCAN_BYTES + INT_LDS_BYTES, st, poff, parts, row0, row1, pr[0], pr[1], d_ids, id_ind0, chr_label,
-                               (const IntNames*)I.d_names.as<IntNames>(), c->n_pop, (u32)b0, I.lens.as<uint8_t>(), (u32*)nullptr, (const u64*)I.boff.as<u64>(), o0, c->d_text.as<char>(),
+                               I.d_names, c->n_pop, (u32)b0, I.lens, (u32*)nullptr, I.boff, o0, c->d_text.as<char>(),
                                (u32*)nullptr);
         }));
     }
@@ -5066,7 +5102,7 @@ int gev_list_stats(gev_ctx* c, int pop, int chr, unsigned long long out[10])
     GEVC(check_idx(c, pop, chr));
     if (!out) return fail(GEV_EINVAL, "list_stats: null argument");
     const ChrState::LpState& lp = c->pop[pop].st[chr].lp;
-    out[0] = lp.imports; out[1] = lp.p_used; out[2] = lp.m_used; out[3] = lp.parena.bytes / sizeof(LpPart); out[4] = lp.marena.bytes / sizeof(u64);
+    out[0] = lp.imports; out[1] = lp.p_used; out[2] = lp.m_used; out[3] = lp.parena.capacity(); out[4] = lp.marena.capacity();
     out[5] = lp.nseg; out[6] = lp.p_last; out[7] = lp.m_last; out[8] = lp.compactions; out[9] = 0;
     return GEV_OK;
 }
@@ -5131,19 +5167,19 @@ int gev_dbg_verify_planes(gev_ctx* c, int pop, int chr, const uint64_t* founder_
     // per ROOT population: allele-frequency thresholds of its synthetic panel, its seed, its number of founder haplotypes
     // (a population this context never generated founders for is taken to have as many as this one: same panel shape on every GPU)
     const int np = c->n_pop;
-    GEVC(c->d_thr32.ensure((size_t)np * S.L * sizeof(u32), st));
+    GEVC(c->d_thr32.ensure((size_t)np * S.L, st));
     std::vector<u64> meta(2 * (size_t)np);
     for (int r = 0; r < np; r++) {
         meta[r] = founder_seeds[r];
         meta[np + r] = c->pop[r].cs[chr].founder_rows ? c->pop[r].cs[chr].founder_rows : S.founder_rows;
-        hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(S.L, 256)), dim3(256), 0, st, c->d_thr32.as<u32>() + (size_t)r * S.L, S.L, founder_seeds[r]);
+        hipLaunchKernelGGL(k_synth_thresholds, dim3((unsigned)ceil_div(S.L, 256)), dim3(256), 0, st, c->d_thr32 + (size_t)r * S.L, S.L, founder_seeds[r]);
     }
     GEVC(h2d(c, c->d_map, meta.data(), meta.size() * sizeof(u64)));
     GEVC(c->d_flag.ensure(16, st));
     HIPC(hipMemsetAsync(c->d_flag.p, 0, 16, st));
-    hipLaunchKernelGGL(k_verify_plane, dim3((unsigned)ceil_div(rows * words, 256)), dim3(256), 0, st, cs.poff[P.cur].as<u32>(), cs.parts[P.cur].as<gev_part>(), rows,
-                       S.d_pos.as<u64>(), (u32)S.L, row_map(P, chr), c->d_thr32.as<u32>(), c->d_map.as<u64>(), np, c->d_map.as<u64>() + np,
-                       (unsigned long long*)c->d_flag.p);
+    hipLaunchKernelGGL(k_verify_plane, dim3((unsigned)ceil_div(rows * words, 256)), dim3(256), 0, st, cs.poff[P.cur], cs.parts[P.cur], rows,
+                       S.d_pos, (u32)S.L, row_map(P, chr), c->d_thr32, c->d_map.as<u64>(), np, c->d_map.as<u64>() + np,
+                       c->d_flag.as<unsigned long long>());
     KCHECK();
     unsigned long long h[2] = {0, 0};
     HIPC(hipMemcpyAsync(h, c->d_flag.p, 16, hipMemcpyDeviceToHost, st));
@@ -5186,7 +5222,7 @@ int gev_dbg_prefilter_sweep(gev_ctx* c, uint32_t x_begin, uint32_t x_end, unsign
     HIPC(hipSetDevice(c->device));
     GEVC(c->d_flag.ensure(32, c->stream));
     HIPC(hipMemsetAsync(c->d_flag.p, 0, 24, c->stream));
-    hipLaunchKernelGGL(k_dbg_prefilter_sweep, dim3(8192), dim3(256), 0, c->stream, c->d_tables.as<GevRngTables>(), x_begin, x_end, (unsigned long long*)c->d_flag.p);
+    hipLaunchKernelGGL(k_dbg_prefilter_sweep, dim3(8192), dim3(256), 0, c->stream, c->d_tables, x_begin, x_end, c->d_flag.as<unsigned long long>());
     KCHECK();
     HIPC(hipMemcpyAsync(out, c->d_flag.p, 24, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
@@ -5209,7 +5245,7 @@ int gev_dbg_rand(gev_ctx* c, uint32_t seed, uint32_t n, int* out)
     if (!c || !out) return fail(GEV_EINVAL, "null");
     HIPC(hipSetDevice(c->device));
     GEVC(c->d_tmp.ensure(std::max<size_t>(n, 4) * sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_dbg_rand, dim3(1), dim3(64), 0, c->stream, c->d_tables.as<GevRngTables>(), seed, n, c->d_tmp.as<int>());
+    hipLaunchKernelGGL(k_dbg_rand, dim3(1), dim3(64), 0, c->stream, c->d_tables, seed, n, c->d_tmp.as<int>());
     KCHECK();
     HIPC(hipMemcpyAsync(out, c->d_tmp.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
@@ -5234,7 +5270,7 @@ int gev_dbg_sim_loc_rec(gev_ctx* c, int pop, int chr, uint32_t seed, uint64_t* l
     GEVC(finalize_static(c, pop));
     GEVC(c->d_tmp.ensure((size_t)cap * 8 + 64, c->stream));
     u64* dl = c->d_tmp.as<u64>(); u32* dn = (u32*)(dl + cap); int* dx = (int*)(dn + 2);
-    hipLaunchKernelGGL(k_dbg_sim_loc_rec, dim3(1), dim3(64), 0, c->stream, c->d_tables.as<GevRngTables>(), c->pop[pop].d_chrdev.as<ChrDev>(), chr, seed, dl, cap, dn, dx);
+    hipLaunchKernelGGL(k_dbg_sim_loc_rec, dim3(1), dim3(64), 0, c->stream, c->d_tables, c->pop[pop].d_chrdev, chr, seed, dl, cap, dn, dx);
     KCHECK();
     HIPC(hipMemcpyAsync(n, dn, 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(next2, dx, 8, hipMemcpyDeviceToHost, c->stream));
