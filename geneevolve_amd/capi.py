@@ -3,7 +3,8 @@
 This is the stub a Python host would add; the C++ host binding is shown in INTEGRATION.md.
 `GevLibrary(path, prefix)` binds any shared library that exports the ABI under `prefix`
 (the product library exports `gev_*`).  No compute happens in Python: every method is one
-C call on caller-owned numpy buffers.
+C call on caller-owned numpy buffers.  Every function is typed from one table, `ABI`, which
+tests/test_abi_cpu.py holds equal to the header: a new entry point adds a line there and a method.
 """
 import ctypes as C
 import os
@@ -77,34 +78,179 @@ def _assort_result(r):
     return {k: int(getattr(r, k)) for k, _ in gev_assort_result._fields_}
 
 
-COUPLE_DTYPE = np.dtype([("pos_male", "<u8"), ("pos_female", "<u8"), ("inbreed", "<i4"), ("num_offspring", "<i4")])
-PART_DTYPE = np.dtype([("st", "<u8"), ("en", "<u8"), ("hap_index", "<u8"), ("root_population", "<i4"), ("reserved", "<i4")])
-MOVE_DTYPE = np.dtype([("src_pop", "<i4"), ("dst_pop", "<i4"), ("src_pos", "<u8")])
+COUPLE_DTYPE = np.dtype(gev_couple)
+PART_DTYPE = np.dtype(gev_part)
+MOVE_DTYPE = np.dtype(gev_move)
 
-# every symbol include/geneevolve_amd.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = [
-    "last_error", "version", "create", "destroy", "set_rmap", "set_mutmap", "set_snps", "set_cvs",
-    "upload_founders", "upload_cv_founders", "synth_founders", "synth_cv_founders", "init_gen0",
-    "reproduce", "presample", "compute_ad", "scale_ad_compute_gef", "set_ad", "get_cv_freq", "migrate", "export_size", "export_rows", "remove_rows",
-    "import_rows", "download_haps", "download_snp_major", "snp_genotype_counts", "dbg_snp_counts_host", "ind_genotype_counts", "pair_genotype_counts", "dbg_pair_counts_host", "ld_counts", "ld_scores", "dbg_ld_host", "dbg_ld_r2_q40_host", "snp_trait_sums", "dbg_trait_sums_host", "format_hap_text", "format_bed", "format_vcf_gt", "rank_f64", "download_plink_matrix", "format_ped_text", "download_cv", "download_intervals", "download_mutations",
-    "pop_size", "plane_ptr", "reserve", "set_chr_active", "set_dense_state", "materialize", "materialize_pops", "materialize_bed", "stream", "last_reproduce_ms", "set_track_intervals", "set_stitch_mode", "sync", "timing_totals", "stitch_totals", "reproduce_begin", "reproduce_end", "presample_sex", "set_overlap",
-    "random_mate", "glob_seeds", "generation_begin", "generation_end", "set_generation_chain", "redo_count", "list_stats", "compute_ad_device", "ad_finish_device",
-    "upload_founder_panel", "synth_founder_panel", "set_migrant_rows",
-    "compute_selection", "download_selection", "get_selection_gen0", "set_selection_gen0", "generation_begin_selected", "random_mate_selected",
-    "assort_mate", "assort_mate_selected", "last_assort_result", "generation_begin_assort", "generation_begin_assort_selected",
-    "dbg_assort_knobs", "dbg_assort_stats",
-    "set_track_pedigree", "download_pedigree", "upload_pedigree",
-    "generation_phenotypes", "phenotypes_result", "download_phenotypes", "get_ad_gen0", "set_ad_gen0", "save_prev_gen", "upload_prev_gen", "dbg_phenotype_knobs",
-    "format_info_text", "dbg_format_g", "dbg_format_g_host",
-    "set_founder_names", "format_interval_text", "dbg_format_interval_text_host",
-    "dbg_verify_planes", "dbg_output_chunk", "dbg_bitprod_tiles", "dbg_pool_stats", "dbg_prefilter_sweep", "dbg_tables", "dbg_threshold", "dbg_canonical", "dbg_rand", "dbg_sim_loc_rec", "dbg_sampling_path", "dbg_ad_path",
-]
+# Every function include/geneevolve_amd.h declares, in its order, as "return: parameters" (tests hold the table equal to the header
+# and check that the library exports every name).  By value: int, size (size_t), u32, u64, f64.  `ctx*` is the context handle.  A
+# pointer is its element and a star: int i32 u32 i64 u64 ull (unsigned long long) size f32 f64, u8 (char and uint8_t alike), void, or a
+# gev_* struct by its name without the prefix; two stars: a pointer to pointers.  Returns: int, void, f64, str (const char*).
+ABI = {
+    "last_error": "str:",
+    "version": "str:",
+    "create": "int: ctx** int int int int",
+    "destroy": "void: ctx*",
+    "set_rmap": "int: ctx* int int u64* f64* size u64",
+    "set_mutmap": "int: ctx* int int u64* f64* size",
+    "set_snps": "int: ctx* int int u64* size",
+    "set_cvs": "int: ctx* int int int u64* f64* f64* size f64",
+    "upload_founders": "int: ctx* int int u64* size size size",
+    "upload_cv_founders": "int: ctx* int int int u64* size size size",
+    "synth_founders": "int: ctx* int int size u64",
+    "synth_cv_founders": "int: ctx* int int int size u64",
+    "init_gen0": "int: ctx* int size u32 u8*",
+    "reproduce": "int: ctx* int couple* size u32 u32* size size u8*",
+    "presample": "int: ctx* int u32 u32* size size",
+    "reproduce_begin": "int: ctx* int couple* size u32 u32* size size",
+    "reproduce_end": "int: ctx* u8*",
+    "presample_sex": "int: ctx* int u8* size",
+    "random_mate": "int: ctx* int u32 f64* size couple* size* size*",
+    "glob_seeds": "int: ctx* u32* size u32*",
+    "generation_begin": "int: ctx* int u32 size f64*",
+    "generation_end": "int: ctx* generation_result* couple* u8*",
+    "set_generation_chain": "int: ctx* int",
+    "compute_ad": "int: ctx* int f64* f64* f64* f64*",
+    "scale_ad_compute_gef": "int: ctx* int int gef_params* u32 f64* f64* f64* f64* f64* f64* f64* f64* f64*",
+    "compute_selection": "int: ctx* int selection_params* f64* f64* f64*",
+    "download_selection": "int: ctx* int f64* f64* f64*",
+    "get_selection_gen0": "int: ctx* int f64* f64*",
+    "set_selection_gen0": "int: ctx* int f64 f64",
+    "generation_begin_selected": "int: ctx* int u32 size",
+    "random_mate_selected": "int: ctx* int u32 size couple* size* size*",
+    "set_track_pedigree": "int: ctx* int",
+    "download_pedigree": "int: ctx* int i64*",
+    "upload_pedigree": "int: ctx* int i64*",
+    "generation_phenotypes": "int: ctx* int phenotypes_params* u32",
+    "phenotypes_result": "int: ctx* int u32* u32* f64*",
+    "download_phenotypes": "int: ctx* int int f64*",
+    "get_ad_gen0": "int: ctx* int int f64* f64*",
+    "set_ad_gen0": "int: ctx* int int f64 f64",
+    "save_prev_gen": "int: ctx* int f64*",
+    "upload_prev_gen": "int: ctx* int f64* f64* size",
+    "dbg_phenotype_knobs": "int: ctx* int ull*",
+    "format_info_text": "int: ctx* int size size int u8* size size*",
+    "dbg_format_g": "int: ctx* f64* size u8* ull*",
+    "dbg_format_g_host": "int: f64* size u8* ull*",
+    "set_founder_names": "int: ctx* int u8* u32* size",
+    "format_interval_text": "int: ctx* int int int size size int i64* u8* size size*",
+    "dbg_format_interval_text_host": "int: part* u64* size i64* int u8** u32** size* int int u8* size size*",
+    "assort_mate": "int: ctx* int assort_params* u32* f64* f64* i64* couple* assort_result*",
+    "assort_mate_selected": "int: ctx* int assort_params* u32* i64* couple* assort_result*",
+    "last_assort_result": "int: ctx* assort_result* couple*",
+    "generation_begin_assort": "int: ctx* int u32 assort_params* f64* f64* i64*",
+    "generation_begin_assort_selected": "int: ctx* int u32 assort_params* i64*",
+    "dbg_assort_knobs": "int: ctx* int int",
+    "dbg_assort_stats": "int: ctx* ull*",
+    "set_ad": "int: ctx* int f64* f64*",
+    "get_cv_freq": "int: ctx* int int int f64* size",
+    "migrate": "int: ctx* move* size",
+    "export_size": "int: ctx* int u64* size size*",
+    "export_rows": "int: ctx* int u64* size void* size",
+    "remove_rows": "int: ctx* int u64* size",
+    "import_rows": "int: ctx* int void* size size",
+    "upload_founder_panel": "int: ctx* int int u64* size size size",
+    "synth_founder_panel": "int: ctx* int int size u64",
+    "set_migrant_rows": "int: ctx* int",
+    "download_haps": "int: ctx* int int size size u64* size",
+    "materialize_pops": "int: ctx* int int size size size size u64** size* size* u64* size",
+    "materialize_bed": "int: ctx* int int size size u64** size* size* u8* size",
+    "download_snp_major": "int: ctx* int int size size u64* size",
+    "format_hap_text": "int: ctx* int int size size u8* size",
+    "format_bed": "int: ctx* int int size size u8* size",
+    "format_vcf_gt": "int: ctx* int int size size u8* size",
+    "snp_genotype_counts": "int: ctx* int int size size size size u32* u32*",
+    "dbg_snp_counts_host": "int: u64* size size size size size u32* u32*",
+    "ind_genotype_counts": "int: ctx* int int size size size size u32* u32* u32* u64*",
+    "pair_genotype_counts": "int: ctx* int int size size size size size size u32* u32* u32*",
+    "dbg_pair_counts_host": "int: u64* size size size size size size size size size u32* u32* u32* u32* u32*",
+    "ld_counts": "int: ctx* int int size size int size size size size u32* u32* u32* u32* u32* u32* u32* u32*",
+    "ld_scores": "int: ctx* int int size size u32* u32* size size int u64* u32*",
+    "dbg_ld_host": "int: u64* size size u64* size size size size size size size size size"
+                   " u32* u32* u32* u32* u32* u32* u32* u32* u32* u32* int u64* u32*",
+    "dbg_ld_r2_q40_host": "int: i64* u64* u64* size u64*",
+    "snp_trait_sums": "int: ctx* int int size size size size i32* size i64* i64* u32* u32*",
+    "dbg_trait_sums_host": "int: u64* size size size size size size size i32* size i64* i64* u32* u32*",
+    "rank_f64": "int: ctx* f64* size ull*",
+    "download_plink_matrix": "int: ctx* int int size size u64* size",
+    "format_ped_text": "int: ctx* int int size size u8* u8* u8* size",
+    "set_dense_state": "int: ctx* int",
+    "materialize": "int: ctx* int int size size size size u64* size size u64* size",
+    "download_cv": "int: ctx* int int int u64* size",
+    "download_intervals": "int: ctx* int int part* u64* size*",
+    "download_mutations": "int: ctx* int int u64* u64* size*",
+    "pop_size": "int: ctx* int size*",
+    "plane_ptr": "int: ctx* int int void** size* size* u32** u32*",
+    "stitch_totals": "int: ctx* ull* ull* ull* ull*",
+    "set_chr_active": "int: ctx* int int",
+    "reserve": "int: ctx* int size",
+    "stream": "int: ctx* void**",
+    "sync": "int: ctx*",
+    "set_overlap": "int: ctx* int",
+    "last_reproduce_ms": "int: ctx* f32*",
+    "timing_totals": "int: ctx* f64* ull*",
+    "redo_count": "int: ctx* ull*",
+    "compute_ad_device": "int: ctx* int f64** f64** size*",
+    "ad_finish_device": "int: ctx* int f64* f64* f64* f64*",
+    "list_stats": "int: ctx* int int ull*",
+    "set_track_intervals": "int: ctx* int",
+    "set_stitch_mode": "int: ctx* int",
+    "dbg_verify_planes": "int: ctx* int int u64* ull* ull*",
+    "dbg_prefilter_sweep": "int: ctx* u32 u32 ull*",
+    "dbg_output_chunk": "int: ctx* size",
+    "dbg_bitprod_tiles": "int: ctx* int ull*",
+    "dbg_pool_stats": "int: ctx* int ull*",
+    "dbg_tables": "int: void* size",
+    "dbg_threshold": "int: f64 u32*",
+    "dbg_canonical": "f64: u32 u32",
+    "dbg_rand": "int: ctx* u32 u32 int*",
+    "dbg_sim_loc_rec": "int: ctx* int int u32 u64* u32 u32* int*",
+    "dbg_sampling_path": "int: ctx* int*",
+    "dbg_ad_path": "int: ctx* int*",
+}
+ABI_SYMBOLS = list(ABI)
+
+_RETURNS = {"int": C.c_int, "void": None, "f64": C.c_double, "str": C.c_char_p}
+_BY_VALUE = {"int": C.c_int, "size": C.c_size_t, "u32": C.c_uint32, "u64": C.c_uint64, "f64": C.c_double, "ctx*": C.c_void_p}
+# numpy kinds and item size of a pointer's elements (char* takes bytes and either signedness)
+_ELEMENTS = {"int": ("i", C.sizeof(C.c_int)), "i32": ("i", 4), "u32": ("u", 4), "i64": ("i", 8), "u64": ("u", 8),
+             "ull": ("u", C.sizeof(C.c_ulonglong)), "size": ("u", C.sizeof(C.c_size_t)), "f32": ("f", 4), "f64": ("f", 8), "u8": ("uiS", 1)}
+_void_p = C.c_void_p.from_param
+
+
+class _Ptr:
+    """argtypes entry of a pointer parameter: None, an address, a ctypes instance, array or byref() as c_void_p takes them, or a
+    C-contiguous numpy array whose elements fit the parameter (structs by their size, void* anything, pointer-to-pointer none)"""
+
+    def __init__(self, kind):
+        self.kind, elem = kind, kind[:-1]
+        if elem.endswith("*"):
+            self.fits = None
+        elif elem == "void":
+            self.fits = lambda dt: True
+        elif elem in _ELEMENTS:
+            kinds, size = _ELEMENTS[elem]
+            self.fits = lambda dt: dt.itemsize == size and dt.kind in kinds
+        else:
+            size = C.sizeof(globals()["gev_" + elem])
+            self.fits = lambda dt: dt.itemsize == size
+
+    def from_param(self, a):
+        if a is None:
+            return None
+        if not isinstance(a, np.ndarray):
+            return _void_p(a)
+        if self.fits is None:
+            raise TypeError(f"{self.kind} takes a ctypes array of pointers, not a numpy array")
+        if not (a.flags.c_contiguous and self.fits(a.dtype)):
+            raise TypeError(f"{self.kind} does not take a{'' if a.flags.c_contiguous else ' non-contiguous'} {a.dtype} array")
+        return C.c_void_p(a.ctypes.data)
 
 
 def _p(a, t=None):
-    if a is None:
-        return None
-    return a.ctypes.data_as(C.c_void_p)
+    """address of a numpy array (or None) as a void*, which every pointer parameter takes unchecked.  Nothing in this module needs
+    it; raw calls written before the binding was typed wrap their arrays in it and stay valid"""
+    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 def _arr(a, dtype):
@@ -116,7 +262,7 @@ def _format_g(f, handle, x):
     x = _arr(x, np.float64).ravel()
     out = np.zeros((len(x), 16), dtype=np.uint8)
     n = C.c_ulonglong()
-    args = (_p(x), C.c_size_t(len(x)), _p(out), C.byref(n))
+    args = (x, len(x), out, C.byref(n))
     rc = f(handle, *args) if handle is not None else f(*args)
     return rc, out, int(n.value)
 
@@ -179,7 +325,8 @@ def pack_names(names):
 
 
 class GevLibrary:
-    def __init__(self, path=DEFAULT_LIB, prefix="gev_"):
+    def __init__(self, path=DEFAULT_LIB, prefix="gev_", extra_abi=None):
+        """extra_abi: lines of ABI's form for functions the library exports beside the header's (the oracle's known-answer helpers)"""
         if not os.path.exists(path):
             raise GevError(-3, f"native library not found: {path} (build it: python -c 'import __graft_entry__ as g; g.build()')")
         self.path, self.prefix = path, prefix
@@ -194,17 +341,38 @@ class GevLibrary:
                 pass
         self.lib = C.CDLL(path)
         self.has_device_arg = prefix == "gev_"
-        f = self._f("last_error"); f.restype = C.c_char_p; f.argtypes = []
+        self.abi = {**ABI, **extra_abi} if extra_abi else ABI
+        self._bound = {}
 
     def _f(self, name):
-        return getattr(self.lib, self.prefix + name)
+        """the library's function `name`, typed from the table when it is first looked up"""
+        return self._bound.get(name) or self._bind(name)
+
+    def _bind(self, name):
+        ret, kinds = self.abi[name].split(":")
+        kinds = kinds.split()
+        if name == "create" and not self.has_device_arg:
+            del kinds[1]
+        sym = self.prefix + name
+        try:
+            cf = getattr(self.lib, sym)
+        except AttributeError:
+            raise GevError(-5, f"{self.path} does not export {sym}") from None
+        cf.restype = _RETURNS[ret]
+        cf.argtypes = [_BY_VALUE.get(k) or _Ptr(k) for k in kinds]
+
+        def f(*args):
+            if len(args) != len(kinds):         # (ctypes lets surplus arguments through)
+                raise TypeError(f"{sym} takes {len(kinds)} arguments ({len(args)} given)")
+            try:
+                return cf(*args)
+            except C.ArgumentError as e:        # "argument <n>: ..." of a by-value conversion or of _Ptr
+                raise TypeError(f"{sym}: {e}") from None
+        self._bound[name] = f
+        return f
 
     def exports(self, name):
-        try:
-            self._f(name)
-            return True
-        except AttributeError:
-            return False
+        return hasattr(self.lib, self.prefix + name)
 
     def last_error(self):
         s = self._f("last_error")()
@@ -232,8 +400,7 @@ class GevLibrary:
         assert bits.ndim == 2 and bits.shape[0] % 2 == 0
         n_snps = L - snp_begin if n_snps is None else n_snps
         het = np.empty(n_snps, dtype=np.uint32); hom = np.empty(n_snps, dtype=np.uint32)
-        self.check(self._f("dbg_snp_counts_host")(_p(bits), C.c_size_t(bits.shape[1]), C.c_size_t(bits.shape[0] // 2), C.c_size_t(L),
-                                                  C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(het), _p(hom)))
+        self.check(self._f("dbg_snp_counts_host")(bits, bits.shape[1], bits.shape[0] // 2, L, snp_begin, n_snps, het, hom))
         return het, hom
 
     def dbg_pair_counts_host(self, bits, L, snp_begin=0, n_snps=None, a_begin=0, n_a=None, b_begin=0, n_b=None):
@@ -248,9 +415,7 @@ class GevLibrary:
         n_b = n_ind - b_begin if n_b is None else n_b
         het = np.empty(n_ind, dtype=np.uint32); hom = np.empty(n_ind, dtype=np.uint32)
         mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(3)]
-        z = C.c_size_t
-        self.check(self._f("dbg_pair_counts_host")(_p(bits), z(bits.shape[1]), z(n_ind), z(L), z(snp_begin), z(n_snps), z(a_begin), z(n_a), z(b_begin), z(n_b),
-                                                   _p(het), _p(hom), _p(mats[0]), _p(mats[1]), _p(mats[2])))
+        self.check(self._f("dbg_pair_counts_host")(bits, bits.shape[1], n_ind, L, snp_begin, n_snps, a_begin, n_a, b_begin, n_b, het, hom, *mats))
         return (het, hom, *mats)
 
     def dbg_ld_host(self, bits_a, L_a, a_begin=0, n_a=None, bits_b=None, L_b=None, b_begin=0, n_b=None, ind_begin=0, n_ind=None,
@@ -264,13 +429,12 @@ class GevLibrary:
         n_people = bits_a.shape[0] // 2
         n_a = L_a - a_begin if n_a is None else n_a
         n_ind = n_people - ind_begin if n_ind is None else n_ind
-        z = C.c_size_t
         if win_lo is not None or win_hi is not None:
             lo = None if win_lo is None else _arr(win_lo, np.uint32); hi = None if win_hi is None else _arr(win_hi, np.uint32)
             assert all(w is None or w.shape == (n_a,) for w in (lo, hi)), "one window per SNP of the range"
             score = np.empty(max(n_a, 0), dtype=np.uint64); terms = np.empty(max(n_a, 0), dtype=np.uint32)
-            self.check(self._f("dbg_ld_host")(_p(bits_a), z(bits_a.shape[1]), z(L_a), None, z(0), z(0), z(n_people), z(a_begin), z(n_a), z(0), z(0), z(ind_begin), z(n_ind),
-                                              None, None, None, None, None, None, None, None, _p(lo), _p(hi), C.c_int(1 if genotype else 0), _p(score), _p(terms)))
+            self.check(self._f("dbg_ld_host")(bits_a, bits_a.shape[1], L_a, None, 0, 0, n_people, a_begin, n_a, 0, 0, ind_begin, n_ind,
+                                              None, None, None, None, None, None, None, None, lo, hi, 1 if genotype else 0, score, terms))
             return score, terms
         if bits_b is None:
             bits_b, L_b = bits_a, L_a
@@ -279,8 +443,8 @@ class GevLibrary:
         n_b = L_b - b_begin if n_b is None else n_b
         mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(2)]
         va = [np.empty(max(n_a, 0), dtype=np.uint32) for _ in range(3)]; vb = [np.empty(max(n_b, 0), dtype=np.uint32) for _ in range(3)]
-        self.check(self._f("dbg_ld_host")(_p(bits_a), z(bits_a.shape[1]), z(L_a), _p(bits_b), z(bits_b.shape[1]), z(L_b), z(n_people), z(a_begin), z(n_a), z(b_begin), z(n_b),
-                                          z(ind_begin), z(n_ind), _p(mats[0]), _p(mats[1]), *[_p(v) for v in va + vb], None, None, C.c_int(0), None, None))
+        self.check(self._f("dbg_ld_host")(bits_a, bits_a.shape[1], L_a, bits_b, bits_b.shape[1], L_b, n_people, a_begin, n_a, b_begin, n_b,
+                                          ind_begin, n_ind, *mats, *va, *vb, None, None, 0, None, None))
         return (*mats, *va, *vb)
 
     def dbg_ld_r2_q40_host(self, num, den_j, den_k):
@@ -289,7 +453,7 @@ class GevLibrary:
         num = _arr(num, np.int64).ravel(); den_j = _arr(den_j, np.uint64).ravel(); den_k = _arr(den_k, np.uint64).ravel()
         assert len(num) == len(den_j) == len(den_k)
         out = np.empty(len(num), dtype=np.uint64)
-        self.check(self._f("dbg_ld_r2_q40_host")(_p(num), _p(den_j), _p(den_k), C.c_size_t(len(num)), _p(out)))
+        self.check(self._f("dbg_ld_r2_q40_host")(num, den_j, den_k, len(num), out))
         return out
 
     def dbg_trait_sums_host(self, bits, L, trait, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
@@ -303,9 +467,7 @@ class GevLibrary:
         n_ind = n_people - ind_begin if n_ind is None else n_ind
         trait = _traits(trait, n_ind)
         outs = _trait_sum_outs(trait.shape[0], n_snps)
-        z = C.c_size_t
-        self.check(self._f("dbg_trait_sums_host")(_p(bits), z(bits.shape[1]), z(n_people), z(L), z(snp_begin), z(n_snps), z(ind_begin), z(n_ind),
-                                                  _p(trait), z(trait.shape[0]), *[_p(o) for o in outs]))
+        self.check(self._f("dbg_trait_sums_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs))
         return outs
 
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
@@ -324,14 +486,13 @@ class GevLibrary:
         o, i = off[2 * ind_begin:], ids[ind_begin:]
 
         def call(buf, size):
-            return f(_p(parts), C.c_void_p(o.ctypes.data) if len(o) else None, C.c_size_t(n_ind), C.c_void_p(i.ctypes.data) if len(i) else None, C.c_int(chr_label),
-                     nb_, no_, nn, C.c_int(npop), C.c_int(1 if header else 0), buf, C.c_size_t(size), C.byref(nb))
+            return f(parts, o if len(o) else None, n_ind, i if len(i) else None, chr_label, nb_, no_, nn, npop, 1 if header else 0, buf, size, C.byref(nb))
         if out_bytes is None:
             self.check(call(None, 0))
             out_bytes = nb.value
         buf = np.empty(max(out_bytes, 1), dtype=np.uint8)
         self.last_bytes_written = None
-        rc = call(_p(buf), out_bytes)
+        rc = call(buf, out_bytes)
         self.last_bytes_written = nb.value
         self.check(rc)
         return buf[:nb.value].tobytes()
@@ -343,11 +504,7 @@ class GevContext:
     def __init__(self, lib, n_pop, nchr, nphen, device=-1):
         self.L, self.n_pop, self.nchr, self.nphen = lib, n_pop, nchr, nphen
         h = C.c_void_p()
-        if lib.has_device_arg:
-            rc = lib._f("create")(C.byref(h), C.c_int(device), C.c_int(n_pop), C.c_int(nchr), C.c_int(nphen))
-        else:
-            rc = lib._f("create")(C.byref(h), C.c_int(n_pop), C.c_int(nchr), C.c_int(nphen))
-        lib.check(rc)
+        lib.check(lib._f("create")(C.byref(h), *([device] if lib.has_device_arg else []), n_pop, nchr, nphen))
         self.h = h
         self._nsnp = {}
         self._ncv = {}
@@ -356,8 +513,7 @@ class GevContext:
 
     def close(self):
         if self.h:
-            f = self.L._f("destroy"); f.restype = None
-            f(self.h); self.h = None
+            self.L._f("destroy")(self.h); self.h = None
 
     def __del__(self):
         try:
@@ -368,61 +524,55 @@ class GevContext:
     def _call(self, name, *args):
         self.L.check(self.L._f(name)(self.h, *args))
 
-    def _call_new(self, name, *args):
-        """entry points a library may lack (the CPU oracle has no device selection values): a clear error instead of AttributeError"""
-        if not self.L.exports(name):
-            raise GevError(-5, f"{self.L.path} does not export {self.L.prefix}{name}")
-        self._call(name, *args)
-
     # ---- static inputs
     def set_rmap(self, pop, chr, bp, prob, bp_dist):
         bp = _arr(bp, np.uint64); prob = _arr(prob, np.float64)
-        self._call("set_rmap", C.c_int(pop), C.c_int(chr), _p(bp), _p(prob), C.c_size_t(len(bp)), C.c_uint64(int(bp_dist)))
+        self._call("set_rmap", pop, chr, bp, prob, len(bp), int(bp_dist))
 
     def set_mutmap(self, pop, chr, bp, rate):
         bp = _arr(bp, np.uint64); rate = _arr(rate, np.float64)
-        self._call("set_mutmap", C.c_int(pop), C.c_int(chr), _p(bp), _p(rate), C.c_size_t(len(bp)))
+        self._call("set_mutmap", pop, chr, bp, rate, len(bp))
 
     def set_snps(self, pop, chr, pos):
         pos = _arr(pos, np.uint64)
         self._nsnp[(pop, chr)] = len(pos)
-        self._call("set_snps", C.c_int(pop), C.c_int(chr), _p(pos), C.c_size_t(len(pos)))
+        self._call("set_snps", pop, chr, pos, len(pos))
 
     def set_cvs(self, pop, phen, chr, bp, a, d, vd):
         bp = _arr(bp, np.uint64); a = _arr(a, np.float64); d = _arr(d, np.float64)
         self._ncv[(pop, phen, chr)] = len(bp)
-        self._call("set_cvs", C.c_int(pop), C.c_int(phen), C.c_int(chr), _p(bp), _p(a), _p(d), C.c_size_t(len(bp)), C.c_double(vd))
+        self._call("set_cvs", pop, phen, chr, bp, a, d, len(bp), vd)
 
     def upload_founders(self, pop, chr, words, L):
         words = _arr(words, np.uint64)
-        self._call("upload_founders", C.c_int(pop), C.c_int(chr), _p(words), C.c_size_t(words.shape[1]), C.c_size_t(words.shape[0]), C.c_size_t(L))
+        self._call("upload_founders", pop, chr, words, words.shape[1], words.shape[0], L)
 
     def upload_cv_founders(self, pop, phen, chr, words, ncv):
         words = _arr(words, np.uint64)
-        self._call("upload_cv_founders", C.c_int(pop), C.c_int(phen), C.c_int(chr), _p(words), C.c_size_t(words.shape[1]), C.c_size_t(words.shape[0]), C.c_size_t(ncv))
+        self._call("upload_cv_founders", pop, phen, chr, words, words.shape[1], words.shape[0], ncv)
 
     def synth_founders(self, pop, chr, nhap, seed):
-        self._call("synth_founders", C.c_int(pop), C.c_int(chr), C.c_size_t(nhap), C.c_uint64(seed))
+        self._call("synth_founders", pop, chr, nhap, seed)
 
     def upload_founder_panel(self, pop, chr, words, L):
         words = _arr(words, np.uint64)
-        self._call("upload_founder_panel", C.c_int(pop), C.c_int(chr), _p(words), C.c_size_t(words.shape[1]), C.c_size_t(words.shape[0]), C.c_size_t(L))
+        self._call("upload_founder_panel", pop, chr, words, words.shape[1], words.shape[0], L)
 
     def synth_founder_panel(self, pop, chr, nhap, seed):
         """read-only founder panel of ROOT population `pop` (immigrants' rows are rebuilt from it, set_migrant_rows(False))"""
-        self._call("synth_founder_panel", C.c_int(pop), C.c_int(chr), C.c_size_t(nhap), C.c_uint64(seed))
+        self._call("synth_founder_panel", pop, chr, nhap, seed)
 
     def set_migrant_rows(self, on):
         """False: export_rows packs no genotype rows, import_rows rebuilds them from the founder panels"""
-        self._call("set_migrant_rows", C.c_int(1 if on else 0))
+        self._call("set_migrant_rows", 1 if on else 0)
 
     def synth_cv_founders(self, pop, phen, chr, nhap, seed):
-        self._call("synth_cv_founders", C.c_int(pop), C.c_int(phen), C.c_int(chr), C.c_size_t(nhap), C.c_uint64(seed))
+        self._call("synth_cv_founders", pop, phen, chr, nhap, seed)
 
     # ---- generation steps
     def init_gen0(self, pop, n_people, seed_gen0, want_sex=True):
         sex = np.zeros(n_people, dtype=np.uint8) if want_sex else None
-        self._call("init_gen0", C.c_int(pop), C.c_size_t(n_people), C.c_uint32(int(seed_gen0)), _p(sex))
+        self._call("init_gen0", pop, n_people, int(seed_gen0), sex)
         return sex
 
     def reproduce(self, pop, couples, seed_reproduce, mut_seeds=None, want_sex=True, n_people=None):
@@ -431,8 +581,7 @@ class GevContext:
         if couples is None:
             ms = None if mut_seeds is None else _arr(mut_seeds, np.uint32)
             sex = np.zeros(n_people, dtype=np.uint8) if want_sex else None
-            self._call("reproduce", C.c_int(pop), None, C.c_size_t(0), C.c_uint32(int(seed_reproduce)),
-                       _p(ms), C.c_size_t(0 if ms is None else len(ms)), C.c_size_t(n_people), _p(sex))
+            self._call("reproduce", pop, None, 0, int(seed_reproduce), ms, 0 if ms is None else len(ms), n_people, sex)
             return sex
         if couples.dtype != COUPLE_DTYPE:
             c = np.zeros(len(couples), dtype=COUPLE_DTYPE)
@@ -443,8 +592,7 @@ class GevContext:
             n_people = int(couples["num_offspring"][couples["inbreed"] == 0].sum())
         ms = None if mut_seeds is None else _arr(mut_seeds, np.uint32)
         sex = np.zeros(n_people, dtype=np.uint8) if want_sex else None
-        self._call("reproduce", C.c_int(pop), _p(couples), C.c_size_t(len(couples)), C.c_uint32(int(seed_reproduce)),
-                   _p(ms), C.c_size_t(0 if ms is None else len(ms)), C.c_size_t(n_people), _p(sex))
+        self._call("reproduce", pop, couples, len(couples), int(seed_reproduce), ms, 0 if ms is None else len(ms), n_people, sex)
         return sex
 
     def reproduce_begin(self, pop, couples, seed_reproduce, mut_seeds=None, n_people=None):
@@ -454,40 +602,39 @@ class GevContext:
         if n_people is None:
             n_people = int(couples["num_offspring"][couples["inbreed"] == 0].sum())
         ms = None if mut_seeds is None else _arr(mut_seeds, np.uint32)
-        self._call("reproduce_begin", C.c_int(pop), _p(couples), C.c_size_t(len(couples)), C.c_uint32(int(seed_reproduce)),
-                   _p(ms), C.c_size_t(0 if ms is None else len(ms)), C.c_size_t(n_people))
+        self._call("reproduce_begin", pop, couples, len(couples), int(seed_reproduce), ms, 0 if ms is None else len(ms), n_people)
         self._pending_people = n_people
 
     def reproduce_end(self, want_sex=True):
         """second half: wait, redo with larger buffers if needed, publish the generation; returns the sexes"""
         sex = np.zeros(self._pending_people, dtype=np.uint8) if want_sex else None
-        self._call("reproduce_end", _p(sex))
+        self._call("reproduce_end", sex)
         return sex
 
     def presample_sex(self, pop, n_people):
         """sexes of the generation whose sampling presample() has enqueued (waits for the sampling kernels only)"""
         sex = np.zeros(n_people, dtype=np.uint8)
-        self._call("presample_sex", C.c_int(pop), _p(sex), C.c_size_t(n_people))
+        self._call("presample_sex", pop, sex, n_people)
         return sex
 
     def presample(self, pop, seed_reproduce, mut_seeds, n_people):
         """head start for the next reproduce() with the same seeds / n_people (returns without waiting)"""
         ms = None if mut_seeds is None else _arr(mut_seeds, np.uint32)
-        self._call("presample", C.c_int(pop), C.c_uint32(int(seed_reproduce)), _p(ms), C.c_size_t(0 if ms is None else len(ms)), C.c_size_t(n_people))
+        self._call("presample", pop, int(seed_reproduce), ms, 0 if ms is None else len(ms), n_people)
 
     def random_mate(self, pop, seed, selection_value_func, pop_size, want_couples=True):
         """Simulation::random_mate on the library's side -> (couples or None, num_males_mate, num_females_mate)"""
         svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
         couples = np.zeros(pop_size, dtype=COUPLE_DTYPE) if want_couples else None
         nm, nf = C.c_size_t(), C.c_size_t()
-        self._call("random_mate", C.c_int(pop), C.c_uint32(int(seed)), _p(svf), C.c_size_t(pop_size), _p(couples), C.byref(nm), C.byref(nf))
+        self._call("random_mate", pop, int(seed), svf, pop_size, couples, C.byref(nm), C.byref(nf))
         return couples, nm.value, nf.value
 
     def random_mate_selected(self, pop, seed, pop_size, want_couples=True):
         """random_mate() on the selection_value_func compute_selection() left in the library -> (couples or None, num_males_mate, num_females_mate)"""
         couples = np.zeros(pop_size, dtype=COUPLE_DTYPE) if want_couples else None
         nm, nf = C.c_size_t(), C.c_size_t()
-        self._call_new("random_mate_selected", C.c_int(pop), C.c_uint32(int(seed)), C.c_size_t(pop_size), _p(couples), C.byref(nm), C.byref(nf))
+        self._call("random_mate_selected", pop, int(seed), pop_size, couples, C.byref(nm), C.byref(nf))
         return couples, nm.value, nf.value
 
     def _assort_args(self, pop, seeds, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree):
@@ -507,7 +654,7 @@ class GevContext:
         svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
         couples = np.zeros(len(mv), dtype=COUPLE_DTYPE) if want_couples else None      # n_couples <= n_people
         res = gev_assort_result()
-        self._call_new("assort_mate", C.c_int(pop), C.byref(par), sd, _p(mv), _p(svf), _p(ped), _p(couples), C.byref(res))
+        self._call("assort_mate", pop, C.byref(par), sd, mv, svf, ped, couples, C.byref(res))
         r = _assort_result(res)
         return (couples[:r["n_couples"]].copy() if want_couples else None), r
 
@@ -517,29 +664,29 @@ class GevContext:
         par, sd, ped = self._assort_args(pop, seeds, pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree)
         couples = np.zeros(self.pop_size(pop), dtype=COUPLE_DTYPE) if want_couples else None
         res = gev_assort_result()
-        self._call_new("assort_mate_selected", C.c_int(pop), C.byref(par), sd, _p(ped), _p(couples), C.byref(res))
+        self._call("assort_mate_selected", pop, C.byref(par), sd, ped, couples, C.byref(res))
         r = _assort_result(res)
         return (couples[:r["n_couples"]].copy() if want_couples else None), r
 
     def last_assort_result(self, want_couples=False):
         """-> (result dict, couples or None) of the context's last completed assort_mate()"""
         res = gev_assort_result()
-        self._call_new("last_assort_result", C.byref(res), None)
+        self._call("last_assort_result", C.byref(res), None)
         r = _assort_result(res)
         couples = None
         if want_couples:
             couples = np.zeros(r["n_couples"], dtype=COUPLE_DTYPE)
-            self._call_new("last_assort_result", C.byref(res), _p(couples))
+            self._call("last_assort_result", C.byref(res), couples)
         return r, couples
 
     def dbg_assort_knobs(self, narrow_window=False, short_poisson=False):
         """set the test hooks of the exact fallbacks for the following assort_mate() calls (both off by default)"""
-        self._call_new("dbg_assort_knobs", C.c_int(int(bool(narrow_window))), C.c_int(int(bool(short_poisson))))
+        self._call("dbg_assort_knobs", int(bool(narrow_window)), int(bool(short_poisson)))
 
     def dbg_assort_stats(self):
         """-> {chunks, direct, pois_reruns} of the last assort_mate()"""
         out = (C.c_ulonglong * 3)()
-        self._call_new("dbg_assort_stats", out)
+        self._call("dbg_assort_stats", out)
         return {"chunks": int(out[0]), "direct": int(out[1]), "pois_reruns": int(out[2])}
 
     def generation_begin_assort(self, pop, glob_state, pop_size, mat_cor, mm_percent=0.0, avoid_inbreeding=False, offspring_dist="p",
@@ -549,23 +696,23 @@ class GevContext:
         left in the library.  -> the assort result dict (n_couples, n_offspring, ...) of this generation"""
         par, _, ped = self._assort_args(pop, (), pop_size, mat_cor, mm_percent, avoid_inbreeding, offspring_dist, pedigree)
         if selected:
-            self._call_new("generation_begin_assort_selected", C.c_int(pop), C.c_uint32(int(glob_state)), C.byref(par), _p(ped))
+            self._call("generation_begin_assort_selected", pop, int(glob_state), C.byref(par), ped)
         else:
             mv = _arr(mating_value, np.float64)
             svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
-            self._call_new("generation_begin_assort", C.c_int(pop), C.c_uint32(int(glob_state)), C.byref(par), _p(mv), _p(svf), _p(ped))
+            self._call("generation_begin_assort", pop, int(glob_state), C.byref(par), mv, svf, ped)
         r, _ = self.last_assort_result()
         self._pending_people, self._pending_couples = r["n_offspring"], r["n_couples"]
         return r
 
     def set_track_pedigree(self, on):
         """True (before init_gen0): the library keeps the seven pedigree ids of every individual on the device"""
-        self._call_new("set_track_pedigree", C.c_int(1 if on else 0))
+        self._call("set_track_pedigree", 1 if on else 0)
 
     def download_pedigree(self, pop):
         """-> int64 [n_people][7]: ID, ID_Father, ID_Mother, ID_Fathers_Father, ID_Fathers_Mother, ID_Mothers_Father, ID_Mothers_Mother"""
         ids = np.zeros((self.pop_size(pop), 7), dtype=np.int64)
-        self._call_new("download_pedigree", C.c_int(pop), _p(ids))
+        self._call("download_pedigree", pop, ids)
         return ids
 
     def upload_pedigree(self, pop, ids):
@@ -573,7 +720,7 @@ class GevContext:
         ids = _arr(ids, np.int64)
         if ids.shape != (self.pop_size(pop), 7):
             raise ValueError("upload_pedigree: one row of 7 ids per individual expected")
-        self._call_new("upload_pedigree", C.c_int(pop), _p(ids))
+        self._call("upload_pedigree", pop, ids)
 
     def generation_phenotypes(self, pop, gen_num, glob_state, schemes, vt_type=1):
         """ras_scale_AD_compute_GEF for every phenotype from the library's own state (enqueues only).  schemes: one (va, vd, vc, ve,
@@ -582,34 +729,34 @@ class GevContext:
             raise ValueError("generation_phenotypes: one scheme per phenotype expected")
         sch = (gev_pheno_scheme * self.nphen)(*[gev_pheno_scheme(*[float(x) for x in s]) for s in schemes])
         par = gev_phenotypes_params(int(gen_num), int(vt_type), C.cast(sch, C.c_void_p))
-        self._call_new("generation_phenotypes", C.c_int(pop), C.byref(par), C.c_uint32(int(glob_state)))
+        self._call("generation_phenotypes", pop, C.byref(par), int(glob_state))
         self._ph_seeds = (self.nphen + sum(1 for s in schemes if s[2] > 0)) if gen_num == 0 else self.nphen
 
     def phenotypes_result(self, pop):
         """waits -> dict(glob_state, seeds (uint32, draw order), var [nphen][7] of A D G C E F P)"""
         st = C.c_uint32(); seeds = np.zeros(2 * self.nphen, dtype=np.uint32); var = np.zeros((self.nphen, 7))      # (at most two seeds per phenotype)
-        self._call_new("phenotypes_result", C.c_int(pop), C.byref(st), _p(seeds), _p(var))
+        self._call("phenotypes_result", pop, C.byref(st), seeds, var)
         return {"glob_state": st.value, "seeds": seeds[:self._ph_seeds].copy(), "var": var}
 
     def download_phenotypes(self, pop, phen):
         """-> dict of the seven n-vectors of PHENOTYPE_COMPONENTS"""
         out = np.zeros((7, self.pop_size(pop)))
-        self._call_new("download_phenotypes", C.c_int(pop), C.c_int(phen), _p(out))
+        self._call("download_phenotypes", pop, phen, out)
         return dict(zip(PHENOTYPE_COMPONENTS, out))
 
     def get_ad_gen0(self, pop, phen):
         a, d = C.c_double(), C.c_double()
-        self._call_new("get_ad_gen0", C.c_int(pop), C.c_int(phen), C.byref(a), C.byref(d))
+        self._call("get_ad_gen0", pop, phen, C.byref(a), C.byref(d))
         return a.value, d.value
 
     def set_ad_gen0(self, pop, phen, var_a, var_d):
-        self._call_new("set_ad_gen0", C.c_int(pop), C.c_int(phen), C.c_double(var_a), C.c_double(var_d))
+        self._call("set_ad_gen0", pop, phen, var_a, var_d)
 
     def save_prev_gen(self, pop, phen_shift=None):
         sh = None if phen_shift is None else _arr(phen_shift, np.float64)
         if sh is not None and len(sh) != self.nphen:
             raise ValueError("save_prev_gen: one shift per phenotype expected")
-        self._call_new("save_prev_gen", C.c_int(pop), _p(sh))
+        self._call("save_prev_gen", pop, sh)
 
     def upload_prev_gen(self, pop, phen, parental_effect):
         """the saved record from the host: [nphen][n] each (None = zeros)"""
@@ -618,7 +765,7 @@ class GevContext:
         n = (ph if ph is not None else pe).shape[1]
         if ph is not None and pe is not None and ph.shape != pe.shape:
             raise ValueError("upload_prev_gen: phen and parental_effect differ in shape")
-        self._call_new("upload_prev_gen", C.c_int(pop), _p(ph), _p(pe), C.c_size_t(n))
+        self._call("upload_prev_gen", pop, ph, pe, n)
 
     def info_row_bytes(self):
         """the largest possible row of format_info_text"""
@@ -634,7 +781,7 @@ class GevContext:
         if buf is None or len(buf) < cap:                   # kept: a fresh buffer of this size costs more page faults than the copy-out
             buf = self._info_buf = np.empty(cap, dtype=np.uint8)
         nb = C.c_size_t()
-        self._call_new("format_info_text", C.c_int(pop), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), _p(buf), C.c_size_t(len(buf)), C.byref(nb))
+        self._call("format_info_text", pop, ind_begin, n_ind, 1 if header else 0, buf, len(buf), C.byref(nb))
         return buf[:nb.value].tobytes()
 
     def info_text_size(self, pop, ind_begin=0, n_ind=None, header=True):
@@ -642,13 +789,13 @@ class GevContext:
         if n_ind is None:
             n_ind = self.pop_size(pop) - ind_begin
         nb = C.c_size_t()
-        self._call_new("format_info_text", C.c_int(pop), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), None, C.c_size_t(0), C.byref(nb))
+        self._call("format_info_text", pop, ind_begin, n_ind, 1 if header else 0, None, 0, C.byref(nb))
         return nb.value
 
     def set_founder_names(self, root_pop, names):
         """the founder individuals' names (the .indv file) of a root population, for format_interval_text"""
         arena, offs = pack_names(names)
-        self._call_new("set_founder_names", C.c_int(root_pop), _p(arena), _p(offs), C.c_size_t(len(offs) - 1))
+        self._call("set_founder_names", root_pop, arena, offs, len(offs) - 1)
 
     def format_interval_text(self, pop, chr, chr_label, ind_begin=0, n_ind=None, header=True, ids=None):
         """bytes of the reference's .int file (Simulation::ras_write_hap_to_interval_format) for individuals [ind_begin, ind_begin +
@@ -662,8 +809,7 @@ class GevContext:
         size = self.interval_text_size(pop, chr, chr_label, ind_begin, n_ind, header, ids)
         buf = np.empty(max(size, 1), dtype=np.uint8)
         nb = C.c_size_t()
-        self._call_new("format_interval_text", C.c_int(pop), C.c_int(chr), C.c_int(chr_label), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), _p(ids),
-                       _p(buf), C.c_size_t(size), C.byref(nb))
+        self._call("format_interval_text", pop, chr, chr_label, ind_begin, n_ind, 1 if header else 0, ids, buf, size, C.byref(nb))
         return buf[:nb.value].tobytes()
 
     def interval_text_size(self, pop, chr, chr_label, ind_begin=0, n_ind=None, header=True, ids=None):
@@ -672,8 +818,7 @@ class GevContext:
             n_ind = self.pop_size(pop) - ind_begin
         ids = None if ids is None else _arr(ids, np.int64)
         nb = C.c_size_t()
-        self._call_new("format_interval_text", C.c_int(pop), C.c_int(chr), C.c_int(chr_label), C.c_size_t(ind_begin), C.c_size_t(n_ind), C.c_int(1 if header else 0), _p(ids),
-                       None, C.c_size_t(0), C.byref(nb))
+        self._call("format_interval_text", pop, chr, chr_label, ind_begin, n_ind, 1 if header else 0, ids, None, 0, C.byref(nb))
         return nb.value
 
     def dbg_format_g(self, x):
@@ -685,7 +830,7 @@ class GevContext:
     def dbg_phenotype_knobs(self, short_candidates=False):
         """-> phenotype steps and scale_ad_compute_gef() calls run again so far; short_candidates: start their normal streams far too short"""
         n = C.c_ulonglong()
-        self._call_new("dbg_phenotype_knobs", C.c_int(int(bool(short_candidates))), C.byref(n))
+        self._call("dbg_phenotype_knobs", int(bool(short_candidates)), C.byref(n))
         return int(n.value)
 
     def compute_selection(self, pop, gen_num, func, par1, par2, omega, lambda_, phen_shift=None, want=("mating_value", "selection_value", "selection_value_func")):
@@ -700,41 +845,41 @@ class GevContext:
         par = gev_selection_params(int(gen_num), code, float(par1), float(par2), om.ctypes.data, la.ctypes.data, None if sh is None else sh.ctypes.data)
         n = self.pop_size(pop) if want else 0
         out = {k: np.zeros(n) for k in want}
-        self._call_new("compute_selection", C.c_int(pop), C.byref(par), _p(out.get("mating_value")), _p(out.get("selection_value")), _p(out.get("selection_value_func")))
+        self._call("compute_selection", pop, C.byref(par), out.get("mating_value"), out.get("selection_value"), out.get("selection_value_func"))
         return out
 
     def download_selection(self, pop):
         """-> dict(mating_value, selection_value, selection_value_func) the library holds for the population's current generation"""
         n = self.pop_size(pop)
         out = {k: np.zeros(n) for k in ("mating_value", "selection_value", "selection_value_func")}
-        self._call_new("download_selection", C.c_int(pop), _p(out["mating_value"]), _p(out["selection_value"]), _p(out["selection_value_func"]))
+        self._call("download_selection", pop, out["mating_value"], out["selection_value"], out["selection_value_func"])
         return out
 
     def get_selection_gen0(self, pop):
         """-> (_gen0_SV_mean, _gen0_SV_var) of the population"""
         m, v = C.c_double(), C.c_double()
-        self._call_new("get_selection_gen0", C.c_int(pop), C.byref(m), C.byref(v))
+        self._call("get_selection_gen0", pop, C.byref(m), C.byref(v))
         return m.value, v.value
 
     def set_selection_gen0(self, pop, mean, var):
-        self._call_new("set_selection_gen0", C.c_int(pop), C.c_double(mean), C.c_double(var))
+        self._call("set_selection_gen0", pop, mean, var)
 
     def glob_seeds(self, engine_state, n, want=True):
         """n Simulation::ras_glob_seed() values from glob_generator's state -> (values or None, state after)"""
         st = C.c_uint32(int(engine_state))
         out = np.zeros(n, dtype=np.uint32) if want else None
-        self._call("glob_seeds", C.byref(st), C.c_size_t(n), _p(out))
+        self._call("glob_seeds", C.byref(st), n, out)
         return out, st.value
 
     def generation_begin(self, pop, glob_state, pop_size, selection_value_func=None):
         """random_mate -> reproduce -> ras_compute_AD of one generation, enqueued as one unit (returns without waiting)"""
         svf = None if selection_value_func is None else _arr(selection_value_func, np.float64)
-        self._call("generation_begin", C.c_int(pop), C.c_uint32(int(glob_state)), C.c_size_t(pop_size), _p(svf))
+        self._call("generation_begin", pop, int(glob_state), pop_size, svf)
         self._pending_people = self._pending_couples = pop_size
 
     def generation_begin_selected(self, pop, glob_state, pop_size):
         """generation_begin() mating on the selection_value_func compute_selection() left in the library (nothing uploaded)"""
-        self._call_new("generation_begin_selected", C.c_int(pop), C.c_uint32(int(glob_state)), C.c_size_t(pop_size))
+        self._call("generation_begin_selected", pop, int(glob_state), pop_size)
         self._pending_people = self._pending_couples = pop_size
 
     def generation_end(self, want_couples=False, want_sex=True):
@@ -742,18 +887,18 @@ class GevContext:
         res = gev_generation_result()
         couples = np.zeros(self._pending_couples, dtype=COUPLE_DTYPE) if want_couples else None
         sex = np.zeros(self._pending_people, dtype=np.uint8) if want_sex else None
-        self._call("generation_end", C.byref(res), _p(couples), _p(sex))
+        self._call("generation_end", C.byref(res), couples, sex)
         return {"glob_state": res.glob_state, "seed_mate": res.seed_mate, "seed_reproduce": res.seed_reproduce,
                 "num_males_mate": res.num_males_mate, "num_females_mate": res.num_females_mate, "couples": couples, "sex": sex}
 
     def set_generation_chain(self, draws_between):
         """ras_glob_seed() draws the host makes itself between two generation_begin() calls (None: unknown, no head start)"""
-        self._call("set_generation_chain", C.c_int(-1 if draws_between is None else int(draws_between)))
+        self._call("set_generation_chain", -1 if draws_between is None else int(draws_between))
 
     def compute_ad_device(self, pop):
         """gev_compute_ad_device: (device pointer of the per-chromosome additive array, ... of the dominance array, length in doubles)"""
         a, d, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
-        self._call("compute_ad_device", C.c_int(pop), C.byref(a), C.byref(d), C.byref(n))
+        self._call("compute_ad_device", pop, C.byref(a), C.byref(d), C.byref(n))
         return int(a.value), int(d.value), int(n.value)
 
     def ad_finish_device(self, pop, per_chr=True):
@@ -761,13 +906,13 @@ class GevContext:
         n = self.pop_size(pop)
         add = np.zeros((n, self.nphen)); dom = np.zeros((n, self.nphen))
         addc = np.zeros((n, self.nchr, self.nphen)) if per_chr else None; domc = np.zeros((n, self.nchr, self.nphen)) if per_chr else None
-        self._call("ad_finish_device", C.c_int(pop), _p(add), _p(dom), _p(addc) if per_chr else None, _p(domc) if per_chr else None)
+        self._call("ad_finish_device", pop, add, dom, addc, domc)
         return add, dom, addc, domc
 
     def list_stats(self, pop=0, chrom=0):
         """gev_list_stats as a dict"""
         out = (C.c_ulonglong * 10)()
-        self._call("list_stats", C.c_int(pop), C.c_int(chrom), out)
+        self._call("list_stats", pop, chrom, out)
         keys = ("rebuilds", "interval_entries_used", "mutation_entries_used", "interval_capacity", "mutation_capacity", "ranges_per_row", "interval_entries_last_generation", "mutation_entries_last_generation", "compactions", "reserved")
         return dict(zip(keys, (int(v) for v in out)))
 
@@ -779,7 +924,7 @@ class GevContext:
     def dbg_pool_stats(self, pop):
         """-> (rebuilds of the free list of the population's segment unit pool, generations enqueued again because it ran out)"""
         out = (C.c_ulonglong * 2)()
-        self._call_new("dbg_pool_stats", C.c_int(pop), out)
+        self._call("dbg_pool_stats", pop, out)
         return int(out[0]), int(out[1])
 
     def compute_ad(self, pop, per_chr=True):
@@ -787,7 +932,7 @@ class GevContext:
         add = np.zeros((n, self.nphen)); dom = np.zeros((n, self.nphen))
         addc = np.zeros((n, self.nchr, self.nphen)) if per_chr else None
         domc = np.zeros((n, self.nchr, self.nphen)) if per_chr else None
-        self._call("compute_ad", C.c_int(pop), _p(add), _p(dom), _p(addc), _p(domc))
+        self._call("compute_ad", pop, add, dom, addc, domc)
         return add, dom, addc, domc
 
     def scale_ad_compute_gef(self, pop, phen, gen_num, seed, va, vd, ve, vf, beta, s2_a_gen0, s2_d_gen0,
@@ -798,19 +943,19 @@ class GevContext:
         arr = lambda x: None if x is None else _arr(x, np.float64)
         cs, ff, fm = arr(common_sibling), arr(f_father), arr(f_mother)
         out = {k: np.zeros(n) for k in ("additive", "dominance", "bv", "e_noise", "parental_effect", "phen")}
-        self._call("scale_ad_compute_gef", C.c_int(pop), C.c_int(phen), C.byref(par), C.c_uint32(int(seed)), _p(cs), _p(ff), _p(fm),
-                   _p(out["additive"]), _p(out["dominance"]), _p(out["bv"]), _p(out["e_noise"]), _p(out["parental_effect"]), _p(out["phen"]))
+        self._call("scale_ad_compute_gef", pop, phen, C.byref(par), int(seed), cs, ff, fm,
+                   out["additive"], out["dominance"], out["bv"], out["e_noise"], out["parental_effect"], out["phen"])
         return out
 
     def set_ad(self, pop, additive, dominance):
         """raw A/D totals of the current generation from the host (locus-split populations: the all-reduced sums)"""
         a = _arr(additive, np.float64); d = _arr(dominance, np.float64)
-        self._call("set_ad", C.c_int(pop), _p(a), _p(d))
+        self._call("set_ad", pop, a, d)
 
     def get_cv_freq(self, pop, phen, chr):
         ncv = self._ncv[(pop, phen, chr)]
         f = np.zeros(ncv)
-        self._call("get_cv_freq", C.c_int(pop), C.c_int(phen), C.c_int(chr), _p(f), C.c_size_t(ncv))
+        self._call("get_cv_freq", pop, phen, chr, f, ncv)
         return f
 
     def migrate(self, moves):
@@ -818,23 +963,23 @@ class GevContext:
         m = np.zeros(len(moves), dtype=MOVE_DTYPE)
         for i, (sp, pos, dp) in enumerate(moves):
             m[i] = (sp, dp, pos)
-        self._call("migrate", _p(m), C.c_size_t(len(m)))
+        self._call("migrate", m, len(m))
 
     # ---- downloads
     def pop_size(self, pop):
         n = C.c_size_t()
-        self._call("pop_size", C.c_int(pop), C.byref(n))
+        self._call("pop_size", pop, C.byref(n))
         return n.value
 
     def dbg_output_chunk(self, max_units=0):
         """test hook: the following output calls stage at most max_units rows / individuals / SNPs (SNPs in 64s) per pass; 0 = byte budgets"""
-        self._call_new("dbg_output_chunk", C.c_size_t(max_units))
+        self._call("dbg_output_chunk", max_units)
 
     def dbg_bitprod_tiles(self, mode=-1):
         """test hook: the tile size of the following pair-count / LD products (0 = by compute units, 1 = always 64 x 64, 2 = always
         128 x 128, -1 = unchanged) -> (small, large): the product launches on either size since the context was created"""
         n = (C.c_ulonglong * 2)()
-        self._call_new("dbg_bitprod_tiles", C.c_int(mode), n)
+        self._call("dbg_bitprod_tiles", mode, n)
         return int(n[0]), int(n[1])
 
     def download_haps(self, pop, chr, row_begin=0, n_rows=None, stride_words=None):
@@ -842,14 +987,14 @@ class GevContext:
         if n_rows is None:
             n_rows = 2 * self.pop_size(pop) - row_begin
         out = _rows_out(n_rows, words_for(L), stride_words)
-        self._call("download_haps", C.c_int(pop), C.c_int(chr), C.c_size_t(row_begin), C.c_size_t(n_rows), _p(out), C.c_size_t(out.shape[1]))
+        self._call("download_haps", pop, chr, row_begin, n_rows, out, out.shape[1])
         return out
 
     def download_snp_major(self, pop, chr, snp_begin=0, n_snps=None, stride_words=None):
         L = self._nsnp[(pop, chr)]
         n_snps = L - snp_begin if n_snps is None else n_snps
         out = _rows_out(n_snps, words_for(2 * self.pop_size(pop)), stride_words)
-        self._call("download_snp_major", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(out.shape[1]))
+        self._call("download_snp_major", pop, chr, snp_begin, n_snps, out, out.shape[1])
         return out
 
     def snp_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
@@ -858,7 +1003,7 @@ class GevContext:
         n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
         n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
         het = np.empty(max(n_snps, 0), dtype=np.uint32); hom = np.empty(max(n_snps, 0), dtype=np.uint32)
-        self._call_new("snp_genotype_counts", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), C.c_size_t(ind_begin), C.c_size_t(n_ind), _p(het), _p(hom))
+        self._call("snp_genotype_counts", pop, chr, snp_begin, n_snps, ind_begin, n_ind, het, hom)
         return het, hom
 
     def allele_freq(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
@@ -878,8 +1023,7 @@ class GevContext:
             weight = _arr(weight, np.uint32)
             assert weight.shape == (n_snps,), "one weight per SNP of the range"
             ws = np.empty(max(n_ind, 0), dtype=np.uint64)
-        z = C.c_size_t
-        self._call_new("ind_genotype_counts", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(ind_begin), z(n_ind), _p(weight), _p(het), _p(hom), _p(ws))
+        self._call("ind_genotype_counts", pop, chr, snp_begin, n_snps, ind_begin, n_ind, weight, het, hom, ws)
         return (het, hom) if weight is None else (het, hom, ws)
 
     def pair_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, a_begin=0, n_a=None, b_begin=0, n_b=None):
@@ -890,8 +1034,7 @@ class GevContext:
         n_a = self.pop_size(pop) - a_begin if n_a is None else n_a
         n_b = self.pop_size(pop) - b_begin if n_b is None else n_b
         mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(3)]
-        z = C.c_size_t
-        self._call_new("pair_genotype_counts", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(a_begin), z(n_a), z(b_begin), z(n_b), _p(mats[0]), _p(mats[1]), _p(mats[2]))
+        self._call("pair_genotype_counts", pop, chr, snp_begin, n_snps, a_begin, n_a, b_begin, n_b, *mats)
         return tuple(mats)
 
     def ld_counts(self, pop, chr_a, a_begin=0, n_a=None, chr_b=None, b_begin=0, n_b=None, ind_begin=0, n_ind=None):
@@ -905,9 +1048,7 @@ class GevContext:
         n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
         mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(2)]
         vecs = [np.empty(max(n, 0), dtype=np.uint32) for n in (n_a, n_a, n_a, n_b, n_b, n_b)]
-        z = C.c_size_t
-        self._call_new("ld_counts", C.c_int(pop), C.c_int(chr_a), z(a_begin), z(n_a), C.c_int(chr_b), z(b_begin), z(n_b), z(ind_begin), z(n_ind),
-                       _p(mats[0]), _p(mats[1]), *[_p(v) for v in vecs])
+        self._call("ld_counts", pop, chr_a, a_begin, n_a, chr_b, b_begin, n_b, ind_begin, n_ind, *mats, *vecs)
         return (*mats, *vecs)
 
     def ld_scores(self, pop, chr, win_lo, win_hi, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, genotype=False):
@@ -919,8 +1060,7 @@ class GevContext:
         lo = _arr(win_lo, np.uint32); hi = _arr(win_hi, np.uint32)
         assert lo.shape == hi.shape == (max(n_snps, 0),), "one window per SNP of the range"
         score = np.empty(max(n_snps, 0), dtype=np.uint64); terms = np.empty(max(n_snps, 0), dtype=np.uint32)
-        z = C.c_size_t
-        self._call_new("ld_scores", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), _p(lo), _p(hi), z(ind_begin), z(n_ind), C.c_int(1 if genotype else 0), _p(score), _p(terms))
+        self._call("ld_scores", pop, chr, snp_begin, n_snps, lo, hi, ind_begin, n_ind, 1 if genotype else 0, score, terms)
         return score, terms
 
     def snp_trait_sums(self, pop, chr, trait, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
@@ -932,8 +1072,7 @@ class GevContext:
         n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
         trait = _traits(trait, n_ind)
         outs = _trait_sum_outs(trait.shape[0], n_snps)
-        z = C.c_size_t
-        self._call_new("snp_trait_sums", C.c_int(pop), C.c_int(chr), z(snp_begin), z(n_snps), z(ind_begin), z(n_ind), _p(trait), z(trait.shape[0]), *[_p(o) for o in outs])
+        self._call("snp_trait_sums", pop, chr, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs)
         return outs
 
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
@@ -942,7 +1081,7 @@ class GevContext:
         n_snps = L - snp_begin if n_snps is None else n_snps
         nb = n_snps * (4 * self.pop_size(pop) + 1)
         out = np.zeros(nb, dtype=np.uint8)
-        self._call("format_hap_text", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(nb))
+        self._call("format_hap_text", pop, chr, snp_begin, n_snps, out, nb)
         return out
 
     def format_bed(self, pop, chr, snp_begin=0, n_snps=None):
@@ -950,7 +1089,7 @@ class GevContext:
         n_snps = L - snp_begin if n_snps is None else n_snps
         nb = n_snps * ((self.pop_size(pop) + 3) // 4)
         out = np.zeros(nb, dtype=np.uint8)
-        self._call("format_bed", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(nb))
+        self._call("format_bed", pop, chr, snp_begin, n_snps, out, nb)
         return out
 
     def format_vcf_gt(self, pop, chr, snp_begin=0, n_snps=None):
@@ -959,14 +1098,14 @@ class GevContext:
         n_snps = L - snp_begin if n_snps is None else n_snps
         nb = n_snps * (4 * self.pop_size(pop) + 1)
         out = np.zeros(nb, dtype=np.uint8)
-        self._call("format_vcf_gt", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), _p(out), C.c_size_t(nb))
+        self._call("format_vcf_gt", pop, chr, snp_begin, n_snps, out, nb)
         return out
 
     def rank_f64(self, x):
         """CommFunc::ras_rank (zero-based, ties by index)"""
         x = _arr(x, np.float64)
         out = np.zeros(len(x), dtype=np.uint64)
-        self._call("rank_f64", _p(x), C.c_size_t(len(x)), _p(out))
+        self._call("rank_f64", x, len(x), out)
         return out
 
     def download_plink_matrix(self, pop, chr, ind_begin=0, n_ind=None, stride_words=None):
@@ -974,7 +1113,7 @@ class GevContext:
         L = self._nsnp[(pop, chr)]
         n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
         out = _rows_out(n_ind, words_for(2 * L), stride_words)
-        self._call("download_plink_matrix", C.c_int(pop), C.c_int(chr), C.c_size_t(ind_begin), C.c_size_t(n_ind), _p(out), C.c_size_t(out.shape[1]))
+        self._call("download_plink_matrix", pop, chr, ind_begin, n_ind, out, out.shape[1])
         return out
 
     def format_ped_text(self, pop, chr, al0=None, al1=None, ind_begin=0, n_ind=None):
@@ -987,40 +1126,40 @@ class GevContext:
                 raise ValueError("format_ped_text: one allele letter per SNP expected")
         nb = n_ind * (4 * L + 1)
         out = np.zeros(nb, dtype=np.uint8)
-        self._call("format_ped_text", C.c_int(pop), C.c_int(chr), C.c_size_t(ind_begin), C.c_size_t(n_ind), _p(al0), _p(al1), _p(out), C.c_size_t(nb))
+        self._call("format_ped_text", pop, chr, ind_begin, n_ind, al0, al1, out, nb)
         return out
 
     def download_cv(self, pop, phen, chr):
         ncv = self._ncv[(pop, phen, chr)]
         w = words_for(ncv)
         out = np.zeros((2 * self.pop_size(pop), w), dtype=np.uint64)
-        self._call("download_cv", C.c_int(pop), C.c_int(phen), C.c_int(chr), _p(out), C.c_size_t(w))
+        self._call("download_cv", pop, phen, chr, out, w)
         return out
 
     def download_intervals(self, pop, chr):
         n = C.c_size_t()
-        self._call("download_intervals", C.c_int(pop), C.c_int(chr), None, None, C.byref(n))
+        self._call("download_intervals", pop, chr, None, None, C.byref(n))
         parts = np.zeros(n.value, dtype=PART_DTYPE)
         off = np.zeros(2 * self.pop_size(pop) + 1, dtype=np.uint64)
-        self._call("download_intervals", C.c_int(pop), C.c_int(chr), _p(parts), _p(off), C.byref(n))
+        self._call("download_intervals", pop, chr, parts, off, C.byref(n))
         return parts, off
 
     def download_mutations(self, pop, chr):
         n = C.c_size_t()
-        self._call("download_mutations", C.c_int(pop), C.c_int(chr), None, None, C.byref(n))
+        self._call("download_mutations", pop, chr, None, None, C.byref(n))
         muts = np.zeros(n.value, dtype=np.uint64)
         off = np.zeros(2 * self.pop_size(pop) + 1, dtype=np.uint64)
-        self._call("download_mutations", C.c_int(pop), C.c_int(chr), _p(muts), _p(off), C.byref(n))
+        self._call("download_mutations", pop, chr, muts, off, C.byref(n))
         return muts, off
 
     # ---- product-only entry points
     def reserve(self, pop, max_people):
-        self._call("reserve", C.c_int(pop), C.c_size_t(max_people))
+        self._call("reserve", pop, max_people)
 
     def plane_ptr(self, pop, chr):
         """(pool pointer, unit bytes, number of haplotype slots, device pointer of the (slot, segment) -> unit table, segments per row)"""
         p = C.c_void_p(); s = C.c_size_t(); n = C.c_size_t(); t = C.c_void_p(); g = C.c_uint32()
-        self._call("plane_ptr", C.c_int(pop), C.c_int(chr), C.byref(p), C.byref(s), C.byref(n), C.byref(t), C.byref(g))
+        self._call("plane_ptr", pop, chr, C.byref(p), C.byref(s), C.byref(n), C.byref(t), C.byref(g))
         return p.value, s.value, n.value, t.value, g.value
 
     def stitch_totals(self):
@@ -1048,7 +1187,7 @@ class GevContext:
         return [float(x) for x in ms], n.value
 
     def set_chr_active(self, chr, active):
-        self._call("set_chr_active", C.c_int(chr), C.c_int(1 if active else 0))
+        self._call("set_chr_active", chr, 1 if active else 0)
         (self._chr_off.discard if active else self._chr_off.add)(chr)
 
     def active_chrs(self):
@@ -1056,7 +1195,7 @@ class GevContext:
         return [k for k in range(self.nchr) if k not in self._chr_off]
 
     def set_dense_state(self, on):
-        self._call("set_dense_state", C.c_int(1 if on else 0))
+        self._call("set_dense_state", 1 if on else 0)
 
     def materialize(self, pop, chr, founder_tile, row_begin=0, n_rows=None, snp_begin=0, n_snps=None, stride_words=None):
         """genotype tile from the interval state; founder_tile: uint64 [n_founder_haps][words] holding SNPs [snp_begin, +n_snps)"""
@@ -1065,8 +1204,7 @@ class GevContext:
         n_rows = 2 * self.pop_size(pop) - row_begin if n_rows is None else n_rows
         ft = np.ascontiguousarray(founder_tile, dtype=np.uint64)
         out = _rows_out(n_rows, words_for(n_snps), stride_words)
-        self._call("materialize", C.c_int(pop), C.c_int(chr), C.c_size_t(row_begin), C.c_size_t(n_rows), C.c_size_t(snp_begin), C.c_size_t(n_snps),
-                   _p(ft), C.c_size_t(ft.shape[1]), C.c_size_t(ft.shape[0]), _p(out), C.c_size_t(out.shape[1]))
+        self._call("materialize", pop, chr, row_begin, n_rows, snp_begin, n_snps, ft, ft.shape[1], ft.shape[0], out, out.shape[1])
         return out
 
     def materialize_pops(self, pop, chr, founder_tiles, row_begin=0, n_rows=None, snp_begin=0, n_snps=None):
@@ -1080,8 +1218,7 @@ class GevContext:
         strides = (C.c_size_t * len(tiles))(*[t.shape[1] for t in tiles])
         rows = (C.c_size_t * len(tiles))(*[t.shape[0] for t in tiles])
         out = np.zeros((n_rows, w), dtype=np.uint64)
-        self._call("materialize_pops", C.c_int(pop), C.c_int(chr), C.c_size_t(row_begin), C.c_size_t(n_rows), C.c_size_t(snp_begin), C.c_size_t(n_snps),
-                   ptrs, strides, rows, _p(out), C.c_size_t(w))
+        self._call("materialize_pops", pop, chr, row_begin, n_rows, snp_begin, n_snps, ptrs, strides, rows, out, w)
         return out
 
     def materialize_bed(self, pop, chr, founder_tiles, snp_begin=0, n_snps=None):
@@ -1094,7 +1231,7 @@ class GevContext:
         rows = (C.c_size_t * len(tiles))(*[t.shape[0] for t in tiles])
         nb = n_snps * ((self.pop_size(pop) + 3) // 4)
         out = np.zeros(nb, dtype=np.uint8)
-        self._call("materialize_bed", C.c_int(pop), C.c_int(chr), C.c_size_t(snp_begin), C.c_size_t(n_snps), ptrs, strides, rows, _p(out), C.c_size_t(nb))
+        self._call("materialize_bed", pop, chr, snp_begin, n_snps, ptrs, strides, rows, out, nb)
         return out
 
     def dbg_verify_planes(self, pop, chr, founder_seeds):
@@ -1103,12 +1240,12 @@ class GevContext:
         seeds = np.atleast_1d(np.asarray(founder_seeds, dtype=np.uint64))
         assert len(seeds) == self.n_pop
         a, b = C.c_ulonglong(0), C.c_ulonglong(0)
-        self._call("dbg_verify_planes", C.c_int(pop), C.c_int(chr), _p(seeds), C.byref(a), C.byref(b))
+        self._call("dbg_verify_planes", pop, chr, seeds, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def dbg_prefilter_sweep(self, x_begin, x_end):
         out = (C.c_ulonglong * 3)()
-        self._call("dbg_prefilter_sweep", C.c_uint32(int(x_begin)), C.c_uint32(int(x_end)), out)
+        self._call("dbg_prefilter_sweep", int(x_begin), int(x_end), out)
         return int(out[0]), int(out[1]), int(out[2])
 
     def dbg_sampling_path(self):
@@ -1128,32 +1265,32 @@ class GevContext:
     def dbg_sim_loc_rec(self, pop, chr, seed, cap=4096):
         """one Simulation::ras_sim_loc_rec call on the device: (breakpoints, the two rand() outputs that follow)"""
         locs = np.zeros(cap, dtype=np.uint64); k = C.c_uint32(0); nx = (C.c_int * 2)()
-        self._call("dbg_sim_loc_rec", C.c_int(pop), C.c_int(chr), C.c_uint32(int(seed)), _p(locs), C.c_uint32(cap), C.byref(k), nx)
+        self._call("dbg_sim_loc_rec", pop, chr, int(seed), locs, cap, C.byref(k), nx)
         assert k.value <= cap
         return locs[:k.value].copy(), (int(nx[0]), int(nx[1]))
 
     def set_overlap(self, on):
         """True (default): the dense stitch overlaps later work; False: one stream, every generation waits for its stitch"""
-        self._call("set_overlap", C.c_int(1 if on else 0))
+        self._call("set_overlap", 1 if on else 0)
 
     def set_stitch_mode(self, mode):
-        self._call("set_stitch_mode", C.c_int(mode))
+        self._call("set_stitch_mode", mode)
 
     def set_track_intervals(self, on):
-        self._call("set_track_intervals", C.c_int(1 if on else 0))
+        self._call("set_track_intervals", 1 if on else 0)
 
     def export_size(self, pop, positions):
         pos = _arr(positions, np.uint64); b = C.c_size_t()
-        self._call("export_size", C.c_int(pop), _p(pos), C.c_size_t(len(pos)), C.byref(b))
+        self._call("export_size", pop, pos, len(pos), C.byref(b))
         return b.value
 
     def export_rows(self, pop, positions, device_ptr, nbytes):
         pos = _arr(positions, np.uint64)
-        self._call("export_rows", C.c_int(pop), _p(pos), C.c_size_t(len(pos)), C.c_void_p(device_ptr), C.c_size_t(nbytes))
+        self._call("export_rows", pop, pos, len(pos), device_ptr, nbytes)
 
     def remove_rows(self, pop, positions):
         pos = _arr(positions, np.uint64)
-        self._call("remove_rows", C.c_int(pop), _p(pos), C.c_size_t(len(pos)))
+        self._call("remove_rows", pop, pos, len(pos))
 
     def import_rows(self, pop, device_ptr, nbytes, n):
-        self._call("import_rows", C.c_int(pop), C.c_void_p(device_ptr), C.c_size_t(nbytes), C.c_size_t(n))
+        self._call("import_rows", pop, device_ptr, nbytes, n)

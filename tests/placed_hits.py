@@ -122,7 +122,7 @@ def fit_map_to_stream(ol, E, first_row, n_rows_total, n_draws, k):
 def threshold(gl, p):
     """(a_lo, a_hi, b0, b1) of the library's integer threshold of probability p (host code)"""
     out = (C.c_uint32 * 4)()
-    assert gl.lib.gev_dbg_threshold(C.c_double(p), out) == 0
+    assert gl._f("dbg_threshold")(p, out) == 0
     return tuple(int(x) for x in out)
 
 

@@ -84,9 +84,9 @@ def check_text(ctx, ipop, sex, nphen, what, slices=True):
         assert hdr + b"".join(parts) == want, f"{what}: slices"
         nb = capi.C.c_size_t()
         buf = np.zeros(len(want), dtype=np.uint8)
-        rc = ctx.L._f("format_info_text")(ctx.h, ipop, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, capi._p(buf), capi.C.c_size_t(len(want) - 1), capi.C.byref(nb))
+        rc = ctx.L._f("format_info_text")(ctx.h, ipop, 0, n, 1, buf, len(want) - 1, capi.C.byref(nb))
         assert rc == -1 and nb.value == len(want), f"{what}: one byte too few"
-        rc = ctx.L._f("format_info_text")(ctx.h, ipop, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, capi._p(buf), capi.C.c_size_t(len(want)), capi.C.byref(nb))
+        rc = ctx.L._f("format_info_text")(ctx.h, ipop, 0, n, 1, buf, len(want), capi.C.byref(nb))
         assert rc == 0 and buf.tobytes() == want, f"{what}: a buffer of exactly the size"
     return got
 
@@ -289,7 +289,7 @@ def test_info_text_refusals(gpu_lib):
     assert len(ctx.format_info_text(0)) > n * 30
     assert refused(lambda: ctx.format_info_text(0, n - 1, 2), "beyond") == -1
     assert refused(lambda: ctx.format_info_text(0, n + 1, 0), "beyond") == -1
-    rc = ctx.L._f("format_info_text")(ctx.h, 0, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, None, capi.C.c_size_t(0), None)
+    rc = ctx.L._f("format_info_text")(ctx.h, 0, 0, n, 1, None, 0, None)
     assert rc == -1 and "bytes_written" in ctx.L.last_error()
     ctx.remove_rows(0, np.array([1, 2], dtype=np.uint64))
     assert refused(lambda: ctx.format_info_text(0), "ids were dropped") == -2

@@ -171,7 +171,7 @@ def test_interval_text_refusals(gpu_lib):
     assert refused(lambda: ctx.format_interval_text(0, 0, 1), "beyond the names") == -1
     nb = capi.C.c_size_t(77)
     buf = np.zeros(1 << 16, dtype=np.uint8)
-    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, None, capi._p(buf), capi.C.c_size_t(len(buf)), capi.C.byref(nb))
+    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, 0, n, 1, None, buf, len(buf), capi.C.byref(nb))
     assert rc == -1 and nb.value == 0 and not buf.any(), "no text is returned"
     assert ctx.format_interval_text(0, 0, 1, 0, n - 1).count(b"\n") == 2 * (n - 1) + 1       # the named ones alone are fine
     ctx.set_founder_names(0, synth_names(0, n))
@@ -181,12 +181,12 @@ def test_interval_text_refusals(gpu_lib):
     assert ctx.format_interval_text(0, 0, 1, n, 0, header=False) == b""
     assert refused(lambda: ctx.format_interval_text(0, 0, 1, n - 1, 2), "beyond") == -1
     assert refused(lambda: ctx.format_interval_text(0, 0, 1, n + 1, 0), "beyond") == -1
-    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, None, None, capi.C.c_size_t(0), None)
+    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, 0, n, 1, None, None, 0, None)
     assert rc == -1 and "bytes_written" in ctx.L.last_error()
     buf = np.zeros(len(want), dtype=np.uint8)
-    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, None, capi._p(buf), capi.C.c_size_t(len(want) - 1), capi.C.byref(nb))
+    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, 0, n, 1, None, buf, len(want) - 1, capi.C.byref(nb))
     assert rc == -1 and nb.value == len(want), "one byte too few"
-    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, capi.C.c_size_t(0), capi.C.c_size_t(n), 1, None, capi._p(buf), capi.C.c_size_t(len(want)), capi.C.byref(nb))
+    rc = ctx.L._f("format_interval_text")(ctx.h, 0, 0, 1, 0, n, 1, None, buf, len(want), capi.C.byref(nb))
     assert rc == 0 and buf.tobytes() == want, "a buffer of exactly the size"
     ctx.remove_rows(0, np.array([1, 2], dtype=np.uint64))
     assert refused(lambda: ctx.format_interval_text(0, 0, 1), "dropped") == -2

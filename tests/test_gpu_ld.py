@@ -155,31 +155,31 @@ def test_per_snp_vectors_equal_the_snp_counter(awkward):
 
 def test_each_output_may_be_null_and_empty_requests(awkward):
     ctx, n, L, bits, pos = awkward
-    f, z, i, p = ctx.L._f("ld_counts"), capi.C.c_size_t, capi.C.c_int, capi._p
+    f = ctx.L._f("ld_counts")
     want = numpy_ld_counts(bits, 70, 20, bits, 500, 30, 5, 200)
     for k in range(8):
         out = [None] * 8
         out[k] = np.full(want[k].shape, 7, dtype=np.uint32)
-        assert f(ctx.h, i(0), i(0), z(70), z(20), i(0), z(500), z(30), z(5), z(200), *[p(o) for o in out]) == 0
+        assert f(ctx.h, 0, 0, 70, 20, 0, 500, 30, 5, 200, *out) == 0
         assert np.array_equal(out[k], want[k]), NAMES[k]
     # n_ind == 0 writes zeros; n_a == 0 or n_b == 0 touches nothing
     m = np.full((20, 30), 7, dtype=np.uint32); v = np.full(30, 7, dtype=np.uint32)
-    assert f(ctx.h, i(0), i(0), z(70), z(20), i(0), z(500), z(30), z(5), z(0), p(m), None, None, None, None, p(v), None, None) == 0
+    assert f(ctx.h, 0, 0, 70, 20, 0, 500, 30, 5, 0, m, None, None, None, None, v, None, None) == 0
     assert not m.any() and not v.any()
     m[:] = 7; v[:] = 7
-    assert f(ctx.h, i(0), i(0), z(70), z(0), i(0), z(500), z(30), z(5), z(200), p(m), None, None, None, None, p(v), None, None) == 0
-    assert f(ctx.h, i(0), i(0), z(70), z(20), i(0), z(L), z(0), z(5), z(200), p(m), None, p(v), None, None, None, None, None) == 0
+    assert f(ctx.h, 0, 0, 70, 0, 0, 500, 30, 5, 200, m, None, None, None, None, v, None, None) == 0
+    assert f(ctx.h, 0, 0, 70, 20, 0, L, 0, 5, 200, m, None, v, None, None, None, None, None) == 0
     assert (m == 7).all() and (v == 7).all()
     lo, hi = ld.windows_by_count(L, 70, 20, 3)
     truth = LDTruth(bits, 60, 40, 5, 200).scores(70, lo, hi, True)
     fs = ctx.L._f("ld_scores")
     score = np.zeros(20, dtype=np.uint64); terms = np.zeros(20, dtype=np.uint32)
-    assert fs(ctx.h, i(0), i(0), z(70), z(20), p(lo), p(hi), z(5), z(200), i(1), p(score), None) == 0 and np.array_equal(score, truth[0])
-    assert fs(ctx.h, i(0), i(0), z(70), z(20), p(lo), p(hi), z(5), z(200), i(1), None, p(terms)) == 0 and np.array_equal(terms, truth[1])
+    assert fs(ctx.h, 0, 0, 70, 20, lo, hi, 5, 200, 1, score, None) == 0 and np.array_equal(score, truth[0])
+    assert fs(ctx.h, 0, 0, 70, 20, lo, hi, 5, 200, 1, None, terms) == 0 and np.array_equal(terms, truth[1])
     score[:] = 7
-    assert fs(ctx.h, i(0), i(0), z(70), z(20), p(lo), p(hi), z(5), z(0), i(1), p(score), p(terms)) == 0 and not score.any() and not terms.any()
+    assert fs(ctx.h, 0, 0, 70, 20, lo, hi, 5, 0, 1, score, terms) == 0 and not score.any() and not terms.any()
     score[:] = 7
-    assert fs(ctx.h, i(0), i(0), z(70), z(0), None, None, z(5), z(200), i(1), p(score), None) == 0 and (score == 7).all()
+    assert fs(ctx.h, 0, 0, 70, 0, None, None, 5, 200, 1, score, None) == 0 and (score == 7).all()
 
 
 def ld_scores_by_count(awkward, genotype):
@@ -554,8 +554,8 @@ def test_ld_refusals(gpu_lib):
     still_usable()
     for a, b in ((lo + 6, hi), (lo, hi - 6), (lo, hi + L), (lo[::-1].copy(), hi), (lo, np.where(np.arange(L) == 100, hi - 2, hi))):
         assert refused(lambda: ctx.ld_scores(0, 0, a, b), "window") == -1
-    f, z, i, p = ctx.L._f("ld_scores"), capi.C.c_size_t, capi.C.c_int, capi._p
+    f = ctx.L._f("ld_scores")
     score = np.zeros(L, dtype=np.uint64)
-    assert f(ctx.h, i(0), i(0), z(0), z(L), p(lo), None, z(0), z(n), i(0), p(score), None) == -1 and "null window" in ctx.L.last_error()
+    assert f(ctx.h, 0, 0, 0, L, lo, None, 0, n, 0, score, None) == -1 and "null window" in ctx.L.last_error()
     still_usable()
     ctx.close()

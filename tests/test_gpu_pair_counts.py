@@ -143,20 +143,20 @@ def test_output_chunk_makes_no_difference_on_the_large_tiles(awkward):
 
 def test_each_output_may_be_null_and_empty_requests(awkward):
     ctx, n, L, snps, truths = awkward
-    f, z, i, p = ctx.L._f("pair_genotype_counts"), capi.C.c_size_t, capi.C.c_int, capi._p
+    f = ctx.L._f("pair_genotype_counts")
     want = truths[(0, L)].block(2, 20, 50, 30)
     for k in range(3):
         out = [None, None, None]
         out[k] = np.full((20, 30), 7, dtype=np.uint32)
-        assert f(ctx.h, i(0), i(0), z(0), z(L), z(2), z(20), z(50), z(30), p(out[0]), p(out[1]), p(out[2])) == 0
+        assert f(ctx.h, 0, 0, 0, L, 2, 20, 50, 30, out[0], out[1], out[2]) == 0
         assert np.array_equal(out[k], want[k])
     # n_snps == 0 writes zeros; n_a == 0 or n_b == 0 touches nothing
     m = [np.full((20, 30), 7, dtype=np.uint32) for _ in range(3)]
-    assert f(ctx.h, i(0), i(0), z(100), z(0), z(2), z(20), z(50), z(30), p(m[0]), p(m[1]), p(m[2])) == 0
+    assert f(ctx.h, 0, 0, 100, 0, 2, 20, 50, 30, m[0], m[1], m[2]) == 0
     assert not any(a.any() for a in m)
     m[0][:] = 7
-    assert f(ctx.h, i(0), i(0), z(0), z(L), z(2), z(0), z(50), z(30), p(m[0]), None, None) == 0
-    assert f(ctx.h, i(0), i(0), z(0), z(L), z(2), z(20), z(n), z(0), p(m[0]), None, None) == 0
+    assert f(ctx.h, 0, 0, 0, L, 2, 0, 50, 30, m[0], None, None) == 0
+    assert f(ctx.h, 0, 0, 0, L, 2, 20, n, 0, m[0], None, None) == 0
     assert (m[0] == 7).all()
     het, hom = ctx.ind_genotype_counts(0, 0, 100, 0, 5, 9)
     assert len(het) == 9 and not het.any() and not hom.any()
@@ -276,7 +276,7 @@ def test_the_tile_mode_hook(gpu_lib):
     sim.ras_initial_human_gen0(0, n)
     t = PairTruth(unpacked(ctx, 0, 0))
     assert ctx.dbg_bitprod_tiles() == (0, 0)
-    ctx.L._f("dbg_bitprod_tiles")(ctx.h, capi.C.c_int(-1), None)                # the counters may be left out
+    ctx.L._f("dbg_bitprod_tiles")(ctx.h, -1, None)               # the counters may be left out
     check_block(ctx, 0, 0, t, 0, L, 0, n, 0, n, "tiles by compute units")
     assert ctx.dbg_bitprod_tiles() == (1, 0), "one tile: fewer than the compute units"
     assert ctx.dbg_bitprod_tiles(2) == (1, 0)
@@ -453,11 +453,11 @@ def test_pair_counts_refusals(gpu_lib):
     assert refused(lambda: ctx.ind_genotype_counts(0, 0, 0, L, n - 1, 2), "individuals") == -1
     still_usable()
     # weights and wsum come together
-    f, z, i, p = ctx.L._f("ind_genotype_counts"), capi.C.c_size_t, capi.C.c_int, capi._p
+    f = ctx.L._f("ind_genotype_counts")
     w = np.ones(L, dtype=np.uint32); ws = np.zeros(n, dtype=np.uint64)
-    assert f(ctx.h, i(0), i(0), z(0), z(L), z(0), z(n), p(w), None, None, None) == -1 and "wsum" in ctx.L.last_error()
-    assert f(ctx.h, i(0), i(0), z(0), z(L), z(0), z(n), None, None, None, p(ws)) == -1 and "wsum" in ctx.L.last_error()
-    assert f(ctx.h, i(0), i(0), z(0), z(L), z(0), z(n), p(w), None, None, p(ws)) == 0
+    assert f(ctx.h, 0, 0, 0, L, 0, n, w, None, None, None) == -1 and "wsum" in ctx.L.last_error()
+    assert f(ctx.h, 0, 0, 0, L, 0, n, None, None, None, ws) == -1 and "wsum" in ctx.L.last_error()
+    assert f(ctx.h, 0, 0, 0, L, 0, n, w, None, None, ws) == 0
     assert np.array_equal(ws, t.het.astype(np.uint64) + 2 * t.hom.astype(np.uint64))
     still_usable()
     t1 = PairTruth(unpacked(ctx, 0, 1), 299, 1)

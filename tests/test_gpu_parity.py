@@ -25,8 +25,7 @@ def kat_lines(tag):
 
 def test_native_library_is_the_hip_build(gpu_lib):
     assert gpu_lib.path.endswith("geneevolve_amd/csrc/libgeneevolve_amd.so")
-    v = gpu_lib.lib.gev_version; v.restype = C.c_char_p
-    assert b"gfx950" in v()
+    assert b"gfx950" in gpu_lib._f("version")()
 
 
 def test_device_glibc_rand_matches_oracle(gpu_lib, oracle_lib):
@@ -34,7 +33,7 @@ def test_device_glibc_rand_matches_oracle(gpu_lib, oracle_lib):
     rs = np.random.RandomState(3)
     for seed in [0, 1, 2, 12345, 2147483646, 2147483647, 2147483648, 4294967295] + [int(x) for x in rs.randint(0, 2**32, 20, dtype=np.uint64)]:
         out = np.zeros(200, dtype=np.int32)
-        gpu_lib.check(gpu_lib.lib.gev_dbg_rand(ctx.h, C.c_uint32(seed), C.c_uint32(200), out.ctypes.data_as(C.c_void_p)))
+        gpu_lib.check(gpu_lib._f("dbg_rand")(ctx.h, seed, 200, out))
         assert np.array_equal(out, oracle_api.kat_rand(oracle_lib, seed, 200)), f"srand({seed})"
     ctx.close()
 
@@ -50,7 +49,7 @@ def test_device_sim_loc_rec_matches_reference_vectors(gpu_lib):
         seed = int(t[1]); nxt = [int(t[2]), int(t[3])]; n = int(t[4])
         want = np.array([int(x) for x in t[5:5 + n]], dtype=np.uint64)
         locs = np.zeros(512, dtype=np.uint64); k = C.c_uint32(); nx = (C.c_int * 2)()
-        gpu_lib.check(gpu_lib.lib.gev_dbg_sim_loc_rec(ctx.h, 0, 0, C.c_uint32(seed), locs.ctypes.data_as(C.c_void_p), C.c_uint32(512), C.byref(k), nx))
+        gpu_lib.check(gpu_lib._f("dbg_sim_loc_rec")(ctx.h, 0, 0, seed, locs, 512, C.byref(k), nx))
         assert k.value == n - 2, f"seed {seed}: crossover count"
         assert np.array_equal(locs[:k.value], want[1:-1]), f"seed {seed}: breakpoints"
         assert [nx[0], nx[1]] == nxt, f"seed {seed}: rand() state after the call"

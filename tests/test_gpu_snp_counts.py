@@ -230,15 +230,15 @@ def test_snp_counts_refusals(gpu_lib):
     assert refused(lambda: ctx.snp_genotype_counts(0, 0, 0, L, n - 1, 2), "individuals") == -1
     assert refused(lambda: ctx.snp_genotype_counts(0, 0, 0, L, n + 1, 0), "individuals") == -1
     still_usable()
-    f, z, i = ctx.L._f("snp_genotype_counts"), capi.C.c_size_t, capi.C.c_int
+    f = ctx.L._f("snp_genotype_counts")
     out = np.full(L, 7, dtype=np.uint32)
     for het, hom in ((None, out), (out, None), (None, None)):
-        assert f(ctx.h, i(0), i(0), z(0), z(L), z(0), z(n), capi._p(het), capi._p(hom)) == -1 and "null" in ctx.L.last_error()
+        assert f(ctx.h, 0, 0, 0, L, 0, n, het, hom) == -1 and "null" in ctx.L.last_error()
     assert (out == 7).all()
     still_usable()
     # n_snps == 0 touches nothing (null vectors are fine); n_ind == 0 writes zeros
-    assert f(ctx.h, i(0), i(0), z(5), z(0), z(0), z(n), None, None) == 0
-    assert f(ctx.h, i(0), i(0), z(L), z(0), z(n), z(0), None, None) == 0
+    assert f(ctx.h, 0, 0, 5, 0, 0, n, None, None) == 0
+    assert f(ctx.h, 0, 0, L, 0, n, 0, None, None) == 0
     het, hom = ctx.snp_genotype_counts(0, 0, 3, 100, 10, 0)
     assert len(het) == 100 and not het.any() and not hom.any()
     het, hom = ctx.snp_genotype_counts(0, 0, 0, None, n, 0)

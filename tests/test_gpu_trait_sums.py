@@ -128,19 +128,19 @@ def test_no_trait_gives_the_snp_counter(awkward):
 
 def test_each_output_may_be_null_and_empty_requests(awkward):
     ctx, n, L, bits, rows = awkward
-    f, z, i, p = ctx.L._f("snp_trait_sums"), capi.C.c_size_t, capi.C.c_int, capi._p
+    f = ctx.L._f("snp_trait_sums")
     q = random_quanta(np.random.RandomState(2), 3, 200)
     want = numpy_trait_sums(bits, 70, 20, 5, 200, q)
     for k in range(4):
         out = [None] * 4
         out[k] = np.full(want[k].shape, 7, dtype=np.int64 if k < 2 else np.uint32)
-        assert f(ctx.h, i(0), i(0), z(70), z(20), z(5), z(200), p(q), z(3), *[p(o) for o in out]) == 0
+        assert f(ctx.h, 0, 0, 70, 20, 5, 200, q, 3, *out) == 0
         assert np.array_equal(out[k], want[k]), NAMES[k]
     m = [np.full((3, 20), 7, dtype=np.int64) for _ in range(2)]; v = [np.full(20, 7, dtype=np.uint32) for _ in range(2)]
-    outs = [p(a) for a in m + v]
-    assert f(ctx.h, i(0), i(0), z(70), z(0), z(5), z(200), p(q), z(3), *outs) == 0 and all((a == 7).all() for a in m + v), "no SNP: nothing is touched"
-    assert f(ctx.h, i(0), i(0), z(70), z(20), z(5), z(0), None, z(3), *outs) == 0 and not any(a.any() for a in m + v), "no individual: zeros"
-    assert f(ctx.h, i(0), i(0), z(70), z(20), z(5), z(200), p(q), z(3), None, None, None, None) == 0
+    outs = m + v
+    assert f(ctx.h, 0, 0, 70, 0, 5, 200, q, 3, *outs) == 0 and all((a == 7).all() for a in m + v), "no SNP: nothing is touched"
+    assert f(ctx.h, 0, 0, 70, 20, 5, 0, None, 3, *outs) == 0 and not any(a.any() for a in m + v), "no individual: zeros"
+    assert f(ctx.h, 0, 0, 70, 20, 5, 200, q, 3, None, None, None, None) == 0
 
 
 # ---- more individuals than one slice of the split --------------------------------------------------------------------------------------
@@ -363,13 +363,13 @@ def test_trait_sums_refusals(gpu_lib):
     for bad in (Q_MAX + 1, -Q_MAX - 1):
         q1 = q.copy(); q1[1, n - 1] = bad
         assert refused(lambda: ctx.snp_trait_sums(0, 0, q1, 0, L, 0, n), "quantum") == -1
-    f, z, i, p = ctx.L._f("snp_trait_sums"), capi.C.c_size_t, capi.C.c_int, capi._p
+    f = ctx.L._f("snp_trait_sums")
     out = np.zeros((2, L), dtype=np.int64)
-    assert f(ctx.h, i(0), i(0), z(0), z(L), z(0), z(n), None, z(2), p(out), None, None, None) == -1 and "null trait" in gpu_lib.last_error()
+    assert f(ctx.h, 0, 0, 0, L, 0, n, None, 2, out, None, None, None) == -1 and "null trait" in gpu_lib.last_error()
     still_usable()
     ctx.close()
     # more than 2^22 individuals: refused before anything is touched (the population itself is smaller, so the range is refused first
     # there; the bound is pinned on the host build, which takes the count of individuals as an argument)
     big = (1 << 22) + 1
     fh = gpu_lib._f("dbg_trait_sums_host")
-    assert fh(None, z(0), z(big), z(10), z(0), z(1), z(0), z(big), None, z(1), None, None, None, None) == -5 and "at most" in gpu_lib.last_error()
+    assert fh(None, 0, big, 10, 0, 1, 0, big, None, 1, None, None, None, None) == -5 and "at most" in gpu_lib.last_error()

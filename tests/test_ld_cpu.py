@@ -198,29 +198,29 @@ def test_windows(population):
 
 def test_nothing_asked_for_and_nulls(gpu_lib, population):
     bits, tight, wide, bits_b, wide_b = population
-    f, z, p = gpu_lib._f("dbg_ld_host"), capi.C.c_size_t, capi._p
+    f = gpu_lib._f("dbg_ld_host")
     mat = np.full((4, 5), 7, dtype=np.uint32); vec = np.full(5, 7, dtype=np.uint32)
     none8 = [None] * 8
 
-    def call(na, nb, ni, outs, tail=(None, None, capi.C.c_int(0), None, None)):
-        return f(p(wide), z(wide.shape[1]), z(L), p(wide), z(wide.shape[1]), z(L), z(N_PEOPLE), z(10), z(na), z(20), z(nb), z(3), z(ni), *outs, *tail)
+    def call(na, nb, ni, outs, tail=(None, None, 0, None, None)):
+        return f(wide, wide.shape[1], L, wide, wide.shape[1], L, N_PEOPLE, 10, na, 20, nb, 3, ni, *outs, *tail)
     # no individual: zeros; no SNP on a side: nothing is touched
-    assert call(4, 5, 0, [p(mat), None, None, None, None, p(vec), None, None]) == 0 and not mat.any() and not vec.any()
+    assert call(4, 5, 0, [mat, None, None, None, None, vec, None, None]) == 0 and not mat.any() and not vec.any()
     mat[:] = 7; vec[:] = 7
-    assert call(0, 5, 9, [p(mat), p(mat), None, None, None, p(vec), p(vec), p(vec)]) == 0 and (mat == 7).all() and (vec == 7).all()
-    assert call(4, 0, 9, [p(mat), p(mat), p(vec), p(vec), p(vec), None, None, None]) == 0 and (mat == 7).all() and (vec == 7).all()
+    assert call(0, 5, 9, [mat, mat, None, None, None, vec, vec, vec]) == 0 and (mat == 7).all() and (vec == 7).all()
+    assert call(4, 0, 9, [mat, mat, vec, vec, vec, None, None, None]) == 0 and (mat == 7).all() and (vec == 7).all()
     # each output on its own
     want = numpy_ld_counts(bits, 10, 4, bits, 20, 5, 3, 9)
     for k in range(8):
         out = np.full(want[k].shape, 7, dtype=np.uint32)
-        outs = list(none8); outs[k] = p(out)
+        outs = list(none8); outs[k] = out
         assert call(4, 5, 9, outs) == 0 and np.array_equal(out, want[k]), NAMES[k]
     # the score form: either output may be null
     lo, hi = ld.windows_by_count(L, 10, 4, 2)
     score = np.zeros(4, dtype=np.uint64); terms = np.zeros(4, dtype=np.uint32)
     truth = LDTruth(bits, 0, L, 3, 9).scores(10, lo, hi, False)
-    assert call(4, 0, 9, none8, (p(lo), p(hi), capi.C.c_int(0), p(score), None)) == 0 and np.array_equal(score, truth[0])
-    assert call(4, 0, 9, none8, (p(lo), p(hi), capi.C.c_int(0), None, p(terms))) == 0 and np.array_equal(terms, truth[1])
+    assert call(4, 0, 9, none8, (lo, hi, 0, score, None)) == 0 and np.array_equal(score, truth[0])
+    assert call(4, 0, 9, none8, (lo, hi, 0, None, terms)) == 0 and np.array_equal(terms, truth[1])
 
 
 def test_host_ld_refusals(gpu_lib, population):
@@ -236,9 +236,9 @@ def test_host_ld_refusals(gpu_lib, population):
     refused(lambda: gpu_lib.dbg_ld_host(wide, L, 0, 5, ind_begin=N_PEOPLE - 1, n_ind=2), "individuals")
     refused(lambda: gpu_lib.dbg_ld_host(tight[:, :3], L, 0, 5), "words")
     refused(lambda: gpu_lib.dbg_ld_host(wide, L, 0, 5, tight[:, :1], L_B, 0, 5), "words")
-    f, z = gpu_lib._f("dbg_ld_host"), capi.C.c_size_t
+    f = gpu_lib._f("dbg_ld_host")
     big = (1 << 30) + 1
-    assert f(None, z(0), z(10), None, z(0), z(10), z(big), z(0), z(1), z(0), z(1), z(0), z(big), *[None] * 8, None, None, capi.C.c_int(0), None, None) == -5
+    assert f(None, 0, 10, None, 0, 10, big, 0, 1, 0, 1, 0, big, *[None] * 8, None, None, 0, None, None) == -5
     assert "at most" in gpu_lib.last_error()
     # windows: every SNP inside its own, both arrays non-decreasing, none beyond L, none missing
     lo, hi = ld.windows_by_count(L, 50, 10, 3)

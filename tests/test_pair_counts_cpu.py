@@ -80,31 +80,27 @@ def test_extreme_rows(gpu_lib):
 
 def test_nothing_asked_for(gpu_lib):
     f = gpu_lib._f("dbg_pair_counts_host")
-    z = capi.C.c_size_t
     words = capi.pack_rows(np.ones((4, 100), dtype=np.uint8))
     vec = np.full(2, 7, dtype=np.uint32); mat = np.full((2, 2), 7, dtype=np.uint32)
-    p = capi._p
     # no SNP: zeros everywhere
-    assert f(p(words), z(2), z(2), z(100), z(40), z(0), z(0), z(2), z(0), z(2), p(vec), p(vec), p(mat), p(mat), p(mat)) == 0
+    assert f(words, 2, 2, 100, 40, 0, 0, 2, 0, 2, vec, vec, mat, mat, mat) == 0
     assert not vec.any() and not mat.any()
     # no pair: the matrices are not touched (null is fine), the vectors are written
     mat[:] = 7
-    assert f(p(words), z(2), z(2), z(100), z(0), z(100), z(1), z(0), z(0), z(2), p(vec), None, None, None, None) == 0
+    assert f(words, 2, 2, 100, 0, 100, 1, 0, 0, 2, vec, None, None, None, None) == 0
     assert list(vec) == [0, 0] and (mat == 7).all()
     # each output may be null
-    assert f(p(words), z(2), z(2), z(100), z(0), z(100), z(0), z(2), z(0), z(2), None, None, None, None, p(mat)) == 0
+    assert f(words, 2, 2, 100, 0, 100, 0, 2, 0, 2, None, None, None, None, mat) == 0
     assert (mat == 400).all()
 
 
 def test_host_pair_counts_refusals(gpu_lib):
     f = gpu_lib._f("dbg_pair_counts_host")
-    z = capi.C.c_size_t
     words = np.zeros((4, 2), dtype=np.uint64)
     vec = np.zeros(2, dtype=np.uint32); mat = np.zeros((2, 2), dtype=np.uint32)
-    p = capi._p
 
     def rc(bits, stride, n_ind, L, s0, ns, a0, na, b0, nb):
-        return f(p(bits), z(stride), z(n_ind), z(L), z(s0), z(ns), z(a0), z(na), z(b0), z(nb), p(vec), p(vec), p(mat), p(mat), p(mat))
+        return f(bits, stride, n_ind, L, s0, ns, a0, na, b0, nb, vec, vec, mat, mat, mat)
     assert rc(words, 2, 2, 100, 90, 11, 0, 2, 0, 2) == -1 and "SNPs" in gpu_lib.last_error() and "beyond" in gpu_lib.last_error()
     assert rc(words, 2, 2, 100, 0, 100, 1, 2, 0, 2) == -1 and "(a)" in gpu_lib.last_error()
     assert rc(words, 2, 2, 100, 0, 100, 0, 2, 2, 1) == -1 and "(b)" in gpu_lib.last_error()

@@ -59,13 +59,9 @@ def test_garbage_beyond_L_in_the_last_word_is_not_counted(gpu_lib):
 
 
 def test_host_counter_refusals(gpu_lib):
-    f = gpu_lib._f("dbg_snp_counts_host")
+    rc = gpu_lib._f("dbg_snp_counts_host")                                     # (bits, stride, n_ind, L, s0, ns, het, hom)
     words = np.zeros((4, 2), dtype=np.uint64)
     out = np.zeros(128, dtype=np.uint32)
-    z = capi.C.c_size_t
-
-    def rc(bits, stride, n_ind, L, s0, ns, het, hom):
-        return f(capi._p(bits), z(stride), z(n_ind), z(L), z(s0), z(ns), capi._p(het), capi._p(hom))
     assert rc(words, 2, 2, 100, 90, 11, out, out) == -1 and "beyond" in gpu_lib.last_error()
     assert rc(words, 2, 2, 100, 0, 100, None, out) == -1 and "null" in gpu_lib.last_error()
     assert rc(words, 1, 2, 100, 0, 100, out, out) == -1 and "words" in gpu_lib.last_error()

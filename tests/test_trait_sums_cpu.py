@@ -98,23 +98,23 @@ def test_digit_carry_edges(gpu_lib, population):
 
 def test_nothing_asked_for_and_nulls(gpu_lib, population):
     bits, tight, wide = population
-    f, z, p = gpu_lib._f("dbg_trait_sums_host"), capi.C.c_size_t, capi._p
+    f = gpu_lib._f("dbg_trait_sums_host")
     q = random_quanta(np.random.RandomState(3), 3, 9)
     want = numpy_trait_sums(bits, 10, 4, 20, 9, q)
 
     def call(ns, ni, nt, outs, trait=q):
-        return f(p(wide), z(wide.shape[1]), z(N_PEOPLE), z(L), z(10), z(ns), z(20), z(ni), p(trait), z(nt), *outs)
+        return f(wide, wide.shape[1], N_PEOPLE, L, 10, ns, 20, ni, trait, nt, *outs)
     mats = [np.full((3, 4), 7, dtype=np.int64) for _ in range(2)]; vecs = [np.full(4, 7, dtype=np.uint32) for _ in range(2)]
-    all4 = [p(a) for a in mats + vecs]
+    all4 = mats + vecs
     assert call(0, 9, 3, all4) == 0 and all((a == 7).all() for a in mats + vecs), "no SNP: nothing is touched"
     assert call(4, 0, 3, all4, None) == 0 and not any(a.any() for a in mats + vecs), "no individual: zeros"
     for k in range(4):                                       # each output on its own
         out = np.full(want[k].shape, 7, dtype=np.int64 if k < 2 else np.uint32)
-        outs = [None] * 4; outs[k] = p(out)
+        outs = [None] * 4; outs[k] = out
         assert call(4, 9, 3, outs) == 0 and np.array_equal(out, want[k]), NAMES[k]
     for a in vecs:
         a[:] = 7
-    assert call(4, 9, 0, [None, None] + [p(a) for a in vecs], None) == 0, "no trait: the two count vectors only"
+    assert call(4, 9, 0, [None, None] + vecs, None) == 0, "no trait: the two count vectors only"
     assert np.array_equal(vecs[0], want[2]) and np.array_equal(vecs[1], want[3])
 
 
@@ -135,12 +135,12 @@ def test_host_trait_sums_refusals(gpu_lib, population):
         refused(lambda: gpu_lib.dbg_trait_sums_host(wide, L, q1, 0, 5, 0, 5), "quantum")
     q1 = q.copy(); q1[0, 0] = Q_MAX; q1[1, 4] = -Q_MAX
     gpu_lib.dbg_trait_sums_host(wide, L, q1, 0, 5, 0, 5)
-    f, z, p = gpu_lib._f("dbg_trait_sums_host"), capi.C.c_size_t, capi._p
+    f = gpu_lib._f("dbg_trait_sums_host")
     out = np.zeros((2, 5), dtype=np.int64)
-    assert f(p(wide), z(wide.shape[1]), z(N_PEOPLE), z(L), z(0), z(5), z(0), z(5), None, z(2), p(out), None, None, None) == -1
+    assert f(wide, wide.shape[1], N_PEOPLE, L, 0, 5, 0, 5, None, 2, out, None, None, None) == -1
     assert "null trait" in gpu_lib.last_error()
     big = (1 << 22) + 1
-    assert f(None, z(0), z(big), z(10), z(0), z(1), z(0), z(big), None, z(1), None, None, None, None) == -5
+    assert f(None, 0, big, 10, 0, 1, 0, big, None, 1, None, None, None, None) == -5
     assert "at most" in gpu_lib.last_error()
 
 

@@ -63,13 +63,13 @@ def step_scan(args):
     n, L, T = args.n_ind, args.n_loci, args.n_traits
     ctx = population(n, L)
     q = quanta(T, n)
-    f, z = ctx.L._f("snp_trait_sums"), C.c_size_t
+    f = ctx.L._f("snp_trait_sums")
     gsum = np.empty((T, L), dtype=np.int64); hetsum = np.empty((T, L), dtype=np.int64)
     het = np.empty(L, dtype=np.uint32); hom = np.empty(L, dtype=np.uint32)
 
     def call(ns, ni, trait):                                          # (into the same host pages every time)
         t0 = time.perf_counter()
-        ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), z(0), z(ns), z(0), z(ni), capi._p(trait), z(T), capi._p(gsum), capi._p(hetsum), capi._p(het), capi._p(hom)))
+        ctx.L.check(f(ctx.h, 0, 0, 0, ns, 0, ni, trait, T, gsum, hetsum, het, hom))
         return time.perf_counter() - t0
     one = np.ascontiguousarray(q[:, :1])
     call(min(L, 4096), n, q); call(L, n, q)                           # warm-up: the CSR lists, the buffers, the code objects, the host pages

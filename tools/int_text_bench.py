@@ -56,16 +56,17 @@ def main():
         ctx.sync()
         size = ctx.interval_text_size(0, 0, args.chr_label, header=False)
         n_parts = C.c_size_t()
-        ctx._call("download_intervals", C.c_int(0), C.c_int(0), None, None, C.byref(n_parts))
+        ctx._call("download_intervals", 0, 0, None, None, C.byref(n_parts))
         parts = np.zeros(n_parts.value, dtype=capi.PART_DTYPE); off = np.zeros(2 * n + 1, dtype=np.uint64)
         buf_h, buf_d = np.empty(size, dtype=np.uint8), np.empty(size, dtype=np.uint8)
         nb = C.c_size_t()
 
         def host(write):
             t0 = time.perf_counter()
-            ctx._call("download_intervals", C.c_int(0), C.c_int(0), capi._p(parts), capi._p(off), C.byref(n_parts))
+            ctx._call("download_intervals", 0, 0, parts, off, C.byref(n_parts))
             t1 = time.perf_counter()
-            rc = hostlib.int_format_host(capi._p(parts), capi._p(off), capi._p(ids), C.c_size_t(n), C.c_int(args.chr_label), nb_, no_, C.c_int(args.threads), capi._p(buf_h), C.c_size_t(size), C.byref(nb))
+            p = lambda a: a.ctypes.data_as(C.c_void_p)               # (the host formatter is a library of its own, bound without types)
+            rc = hostlib.int_format_host(p(parts), p(off), p(ids), C.c_size_t(n), C.c_int(args.chr_label), nb_, no_, C.c_int(args.threads), p(buf_h), C.c_size_t(size), C.byref(nb))
             assert rc == 0 and nb.value == size
             t2 = time.perf_counter()
             if write:
@@ -75,7 +76,7 @@ def main():
 
         def device(write):
             t0 = time.perf_counter()
-            lib.check(fmt(ctx.h, 0, 0, C.c_int(args.chr_label), C.c_size_t(0), C.c_size_t(n), 0, None, capi._p(buf_d), C.c_size_t(size), C.byref(nb)))
+            lib.check(fmt(ctx.h, 0, 0, args.chr_label, 0, n, 0, None, buf_d, size, C.byref(nb)))
             assert nb.value == size
             if write:
                 with open(os.path.join(tmp, "d.int"), "wb") as f:

@@ -68,12 +68,12 @@ def step_counts(args):
     import ctypes as C
     import numpy as np
     from geneevolve_amd import capi
-    f, z, mat, vec = ctx.L._f("ld_counts"), C.c_size_t, np.empty((B, B), dtype=np.uint32), np.empty(B, dtype=np.uint32)
+    f, mat, vec = ctx.L._f("ld_counts"), np.empty((B, B), dtype=np.uint32), np.empty(B, dtype=np.uint32)
     mats = [mat, np.empty((B, B), dtype=np.uint32)]
 
     def call(b, ni):                                                  # (into the same host pages every time)
         t0 = time.perf_counter()
-        ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), z(0), z(b), C.c_int(0), z(B), z(b), z(0), z(ni), capi._p(mats[0]), capi._p(mats[1]), *[None] * 6))
+        ctx.L.check(f(ctx.h, 0, 0, 0, b, 0, B, b, 0, ni, mats[0], mats[1], *[None] * 6))
         return time.perf_counter() - t0
     call(min(B, 256), n); call(B, n)                                  # warm-up: the CSR lists, the buffers, the code objects, the host pages
     times = [call(B, n) for _ in range(args.repeats)]
@@ -85,8 +85,7 @@ def step_counts(args):
     def part(n11, gg):
         def once():
             t0 = time.perf_counter()
-            ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), z(0), z(B), C.c_int(0), z(B), z(B), z(0), z(n), capi._p(mat) if n11 else None, capi._p(mat) if gg else None,
-                          capi._p(vec), None, None, capi._p(vec), None, None))
+            ctx.L.check(f(ctx.h, 0, 0, 0, B, 0, B, B, 0, n, mat if n11 else None, mat if gg else None, vec, None, None, vec, None, None))
             return time.perf_counter() - t0
         once()
         return median([once() for _ in range(args.repeats)])

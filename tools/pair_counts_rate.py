@@ -60,18 +60,17 @@ def step_device(args):
     ctx = population(n, L)
     mats = [np.empty((B, B), dtype=np.uint32) for _ in range(3)]
     f = ctx.L._f("pair_genotype_counts")
-    z = C.c_size_t
 
     def call(ns, b):
         t0 = time.perf_counter()
-        ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), z(0), z(ns), z(0), z(b), z(0), z(b), *(capi._p(m) for m in mats)))
+        ctx.L.check(f(ctx.h, 0, 0, 0, ns, 0, b, 0, b, *mats))
         return time.perf_counter() - t0
     call(L, min(B, 256)); call(L, B)                                  # warm-up: the CSR lists, the buffers, the code objects, the host pages
     times = sorted(call(L, B) for _ in range(args.repeats))
     med = times[len(times) // 2]
     small = [np.empty((B, B), dtype=np.uint32) for _ in range(3)]
     hl = host_loci(args)
-    ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), z(0), z(hl), z(0), z(B), z(0), z(B), *(capi._p(m) for m in small)))
+    ctx.L.check(f(ctx.h, 0, 0, 0, hl, 0, B, 0, B, *small))
     rec = {"step": "device", "n_ind": n, "n_loci": L, "block": B, "repeats": args.repeats, "call_s": times, "call_median_s": med,
            "pair_loci": B * B * L, "pair_loci_per_s": B * B * L / med, "fraction_of_i8_rate": B * B * L / med / I8_PAIR_LOCI_PER_S,
            "result_bytes": 3 * B * B * 4, "dot_trace": int(np.trace(mats[2]).astype(np.int64)), "sha256_host_loci": digest(small)}

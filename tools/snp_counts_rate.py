@@ -56,7 +56,7 @@ def step_counts(args):
 
     def call(n_ind):
         t0 = time.perf_counter()
-        ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(L), C.c_size_t(0), C.c_size_t(n_ind), capi._p(het), capi._p(hom)))
+        ctx.L.check(f(ctx.h, 0, 0, 0, L, 0, n_ind, het, hom))
         return time.perf_counter() - t0
     call(1); call(n)                                                  # warm-up: the CSR lists, the count vectors, the code objects
     fixed = sorted(call(1) for _ in range(args.repeats))
@@ -87,7 +87,7 @@ def step_snp_major(args):
 
     def run(s0, ns):
         t0 = time.perf_counter()
-        ctx.L.check(f(ctx.h, C.c_int(0), C.c_int(0), C.c_size_t(s0), C.c_size_t(ns), capi._p(buf), C.c_size_t(w)))
+        ctx.L.check(f(ctx.h, 0, 0, s0, ns, buf, w))
         t1 = time.perf_counter()
         b = buf[:ns]
         sh = b >> np.uint64(1)                                         # haplotypes 2i and 2i+1 are bits 2i and 2i+1 of a SNP's row
