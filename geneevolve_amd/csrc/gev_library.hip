@@ -5189,26 +5189,27 @@ int gev_dbg_verify_planes(gev_ctx* c, int pop, int chr, const uint64_t* founder_
 }
 // Exhaustive check of the FP64 prefilter of the batched sampling kernels (gev_sample8.h:scan_candidates) over engine states
 // [x_begin, x_end) and all SB_M multipliers of a block (smp_scan_multiplier, the same definition the kernel's tables are built
-// from): with the exact high digit x2 = x * c_m mod M and F = floor(x2 * 2^20 / M), the 20 low
-// mantissa bits L of fma(x, fl(c_m / M), 1.5 * 2^32 + 4 u) must satisfy L - 4 - F in {-1, 0, 1, 2} (mod 2^20): then every draw
-// whose x2 is <= amax passes L < floor(amax * 2^20 / M) + 7, for every amax.  out[0] = violations, out[1] = largest (L - 4 - F),
-// out[2] = largest (F + 4 - L).
+// from): with the exact high digit x2 = x * c_m mod M and F = floor(x2 * 2^16 / M), the SB_PF_BITS = 16 low mantissa bits L of
+// fma(x, fl(c_m / M), SB_PF_BIAS) must satisfy d = L - SB_PF_OFF - F in [-SB_PF_DNEG, SB_PF_DPOS] = {0, 1} (mod 2^16): then every
+// draw whose x2 is <= amax passes L < floor(amax * 2^16 / M) + SB_PF_MARGIN, for every amax, and no L wraps below 0.  The scan
+// takes its offset and margin from the same constants, so a violation of the band is a violation of the kernel's test.
+// out[0] = violations, out[1] = largest d, out[2] = largest -d.
 __global__ void __launch_bounds__(256) k_dbg_prefilter_sweep(const GevRngTables* __restrict__ Tg, u32 x_begin, u32 x_end, unsigned long long* __restrict__ out)
 {
     __shared__ double s_kd[SB_M]; __shared__ u32 s_ci[SB_M];
     for (u32 i = threadIdx.x; i < SB_M; i += blockDim.x) smp_scan_multiplier(Tg, i, s_ci[i], s_kd[i]);
     __syncthreads();
-    const double C = 6442450944.0 + 4.0 / 1048576.0;
+    const double C = SB_PF_BIAS;
     unsigned long long bad = 0; int dpos = 0, dneg = 0;
     for (u64 x = (u64)x_begin + (u64)blockIdx.x * 256 + threadIdx.x; x < x_end; x += (u64)gridDim.x * 256) {
         const double xd = (double)(u32)x;
         for (u32 j = 0; j < SB_M; j++) {
             const u32 x2 = mulmod31((u32)x, s_ci[j]);
-            const u32 F = (u32)(((u64)x2 << 20) / 2147483647ull);
-            const u32 L = (u32)__double2loint(__fma_rn(xd, s_kd[j], C)) & 0xfffffu;
-            int d = (int)((L - 4u - F) & 0xfffffu);
-            if (d >= (1 << 19)) d -= (1 << 20);
-            if (d < -1 || d > 2) bad++;
+            const u32 F = (u32)(((u64)x2 << SB_PF_BITS) / 2147483647ull);
+            const u32 L = (u32)__double2loint(__fma_rn(xd, s_kd[j], C)) & SB_PF_MASK;
+            int d = (int)((L - (u32)SB_PF_OFF - F) & SB_PF_MASK);
+            if (d >= (1 << (SB_PF_BITS - 1))) d -= (1 << SB_PF_BITS);
+            if (d < -SB_PF_DNEG || d > SB_PF_DPOS) bad++;
             dpos = max(dpos, d); dneg = max(dneg, -d);
         }
     }

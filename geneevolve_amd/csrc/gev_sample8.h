@@ -28,17 +28,31 @@
 
 #define SB_M 256            // draws per lane that are prefiltered from ONE exact engine state
 #define SB_BLK (8 * SB_M)   // draws of one task per block: 8 lanes x SB_M
+#define SB_RSTRIDE 36       // words per row of the srand8 operands (31 used, the 32nd is padding): rows start on 16 bytes and, at 144
+                            // bytes apart, the eight rows of a 16-byte read fall on eight different bank quads (0, 36, 8, 44, 16, 52, 24, 60)
+// FP64 prefilter of the scan (derivation: scan_candidates).  The fraction field is the SB_PF_BITS low mantissa bits of the FMA; with
+// F = floor(x2 * 2^16 / M) the field is L = F + SB_PF_OFF + d (mod 2^16) with -SB_PF_DNEG <= d <= SB_PF_DPOS, which
+// gev_dbg_prefilter_sweep checks exhaustively with these very constants.  The offset keeps L from wrapping below 0, the margin is
+// what a draw with F = floor(A) can reach, plus one for the strict compare.
+#define SB_PF_BITS 16
+#define SB_PF_DNEG 0
+#define SB_PF_DPOS 1
+#define SB_PF_OFF SB_PF_DNEG
+#define SB_PF_MARGIN (SB_PF_OFF + SB_PF_DPOS + 1u)
+#define SB_PF_ONE 65536.0                                              // 2^SB_PF_BITS
+#define SB_PF_MASK 0xffffu
+#define SB_PF_BIAS (103079215104.0 + (double)SB_PF_OFF / SB_PF_ONE)    // 1.5 * 2^36 + offset: ulp = 2^-16 = one unit of the field
 struct __attribute__((aligned(32))) SmpTabs {   // constant tables, one copy per workgroup (LDS)
     double kd[SB_M + 4];    // c_m / M with c_m = 16807^(16 m) mod M: draw (j + 8 m)'s high digit = x_j * c_m mod M; 4 spare entries
                             // (0) behind the last one, so that the scan may always load the next step's four
     u32 ci[SB_M];           // c_m
     u32 pow_even[64];       // 16807^(2l+2): draw l's high-digit engine output
-    u32 w8[31 * SB_OUT];    // w_init[i][j], j < 8
+    u32 w8[SB_OUT * SB_RSTRIDE];   // row j < 8: w_init[i][j], i < 31, then 0
     u32 pow_lcg[32];        // 16807^(i-1), i = 1..30
     u32 pow_blk /* 16807^(2 SB_BLK): next block of draws */, inv16807, pad[2];
 };
-struct SmpWave {            // scratch of one wave (LDS)
-    u32 r[SB_TASKS * 33];   // seed words r_0..r_30 of the 8 generators, odd stride
+struct __attribute__((aligned(16))) SmpWave {   // scratch of one wave (LDS)
+    u32 r[SB_TASKS * SB_RSTRIDE];   // row g: seed words r_0..r_30 of generator g, then one padding word
     u32 cand_row[SB_CAND];
     u32 cand_x2[SB_CAND];
     uint8_t cand_tag[SB_CAND];
@@ -58,7 +72,7 @@ __device__ __forceinline__ void smp_scan_multiplier(const GevRngTables* __restri
 __device__ __forceinline__ void stage_smp_tabs(const GevRngTables* __restrict__ g, SmpTabs* s)
 {
     for (u32 i = threadIdx.x; i < 64; i += blockDim.x) s->pow_even[i] = g->pow_even[i];
-    for (u32 i = threadIdx.x; i < 31 * SB_OUT; i += blockDim.x) s->w8[i] = g->w_init[(i / SB_OUT) * 64 + (i % SB_OUT)];
+    for (u32 i = threadIdx.x; i < SB_OUT * 32; i += blockDim.x) s->w8[(i >> 5) * SB_RSTRIDE + (i & 31u)] = (i & 31u) < 31u ? g->w_init[(i & 31u) * 64 + (i >> 5)] : 0u;
     for (u32 i = threadIdx.x; i < 31; i += blockDim.x) s->pow_lcg[i] = g->pow_lcg[i];
     for (u32 i = threadIdx.x; i < SB_M; i += blockDim.x) smp_scan_multiplier(g, i, s->ci[i], s->kd[i]);
     if (threadIdx.x < 4) s->kd[SB_M + threadIdx.x] = 0.0;
@@ -67,28 +81,36 @@ __device__ __forceinline__ void stage_smp_tabs(const GevRngTables* __restrict__ 
 }
 
 // srand(seed) for eight generators at once: every lane of group g passes generator g's seed; returns raw output word j = lane & 7
-// of generator g = lane >> 3 (rand() = word >> 1).  Same seeding arithmetic as GlibcWave::seed.
-__device__ __forceinline__ u32 srand8(const SmpTabs* __restrict__ T, volatile u32* __restrict__ Wr, u32 seed)
+// of generator g = lane >> 3 (rand() = word >> 1).  Same seeding arithmetic as GlibcWave::seed: r_0 = seed (0 -> 1), r_1 by the
+// signed Schrage step of random_r.c (a seed >= 2^31 enters as a negative int32; every intermediate fits 32 bits: |lo| < 127773
+// and |hi| <= 16807 give |16807 lo - 2836 hi| < 2^31), r_i = 16807^(i-1) r_1 mod M.  Each lane takes the step for its own group's
+// seed once and writes the words i = j, j + 8, j + 16, j + 24 of its group's generator (i = 31, lane 7's last: pow_lcg[31] = 0, the
+// row's padding word); then lane (g, j) sums row j of w8 against row g of Wr, both read 16 bytes at a time.  Wr is plain LDS
+// between two wave fences, like the candidate lists.
+__device__ __forceinline__ u32 srand8(const SmpTabs* __restrict__ T, u32* __restrict__ Wr, u32 seed)
 {
-    const u32 lane = threadIdx.x & 63;
-#pragma unroll 1
-    for (int p = 0; p < 4; p++) {
-        const u32 e = p * 64 + lane;                       // word e % 31 of generator e / 31
-        const u32 ge = e / 31u, ie = e - ge * 31u;
-        u32 sv = (u32)__shfl((int)seed, (int)((ge & 7u) * 8u));
-        if (sv == 0) sv = 1;
-        const int32_t w0 = (int32_t)sv;                    // r[1] by the signed Schrage step of random_r.c
-        const long hi = w0 / 127773, lo = w0 % 127773;
-        long w = 16807 * lo - 2836 * hi;
-        if (w < 0) w += 2147483647;
-        const u32 val = ie == 0 ? sv : mulmod31(T->pow_lcg[ie], (u32)w);
-        if (e < 31u * SB_TASKS) Wr[ge * 33u + ie] = val;
+    const u32 lane = threadIdx.x & 63, g = lane >> 3, j = lane & 7u;
+    const u32 sv = seed == 0 ? 1u : seed;
+    const int32_t w0 = (int32_t)sv;
+    const int32_t hi = w0 / 127773, lo = w0 % 127773;
+    int32_t w = 16807 * lo - 2836 * hi;
+    if (w < 0) w += 2147483647;
+    u32* row = Wr + g * SB_RSTRIDE;
+#pragma unroll
+    for (u32 p = 0; p < 4; p++) {
+        const u32 i = j + 8u * p;
+        const u32 val = mulmod31(T->pow_lcg[i], (u32)w);
+        row[i] = i == 0 ? sv : val;
     }
     wave_fence();
-    const u32 g = lane >> 3, j = lane & 7u;
+    const uint4* wq = reinterpret_cast<const uint4*>(T->w8 + j * SB_RSTRIDE);
+    const uint4* rq = reinterpret_cast<const uint4*>(row);
     u32 acc = 0;
-#pragma unroll 8
-    for (int i = 0; i < 31; i++) acc += T->w8[i * SB_OUT + j] * Wr[g * 33u + i];
+#pragma unroll
+    for (u32 q = 0; q < 8; q++) {
+        const uint4 a = wq[q], b = rq[q];
+        acc += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+    }
     wave_fence();
     return acc;
 }
@@ -114,15 +136,20 @@ __device__ __forceinline__ u32 srand8(const SmpTabs* __restrict__ T, volatile u3
 //
 // FP64 prefilter.  The high digit of draw j + 8 m is x2 = x * c_m mod M, i.e. M * frac(T) with T = x * c_m / M < 2^31.  One FMA
 // evaluates
-//     s = x * fl(c_m / M) + (1.5 * 2^32 + 4 u),   u = 2^-20 = ulp(s),
-// whose 20 low mantissa bits are  L = (frac(T) * 2^20 + e + 4) mod 2^20  with |e| < 1 (2^-22 from the rounded constant, 2^-21 from
-// the rounding of the FMA, in units of u = 2^-20 less than one unit together; the bound holds for any multiplier below M).  A
-// draw with x2 <= amax has frac(T) * 2^20 in (0, A], A = amax * 2^20 / M, hence L in [4, A + 5): it passes  L < ceil(A) + 6.
-// The test is a SUPERSET of the exact one (a few thousand x2 values wide: ~0.4 % extra candidates at 5e-4 per row); every
-// candidate's exact x2 is then computed with the integer multiply and the exact threshold test runs in the resolve step, so the
-// result is bit-identical.  Cost per 64 draws: one v_fma_f64, one v_and, one v_cmp (the exact form needs a 10-instruction
-// modular multiply per 64 draws).  gev_dbg_prefilter_sweep checks the bound exhaustively over all 2^31 - 2 engine states x 256
-// multipliers.
+//     s = x * fl(c_m / M) + 1.5 * 2^36,   u = 2^-16 = ulp(s),
+// whose 16 low mantissa bits are  L = round(y + e) mod 2^16,  y = frac(T) * 2^16 = x2 * 2^16 / M,  where e is the error of the
+// rounded constant alone, |e| <= 2^-22 absolute = 2^-6 u (the bound holds for any multiplier below M), and round() is the one
+// rounding of the FMA to a multiple of u.  With F = floor(y): y is no integer (M is prime) and lies at least 2^-31 from one, so
+// y + e stays inside (F - 1/2, F + 3/2) and  L = F + d,  d in {0, 1}.  A draw with x2 <= amax has F <= floor(A), A = amax * 2^16 / M,
+// hence L <= floor(A) + 1: it passes  L < floor(A) + 2  (SB_PF_MARGIN; no offset is needed, because d is never negative; the 20-bit
+// field this replaces carried an offset of 4 and a margin of 7, which the same argument and the sweep's extremes show to be more
+// than needed).  floor(A) is exact in FP64: A is no integer either, at least 2^-31 from one, and the two roundings of its
+// evaluation move it by less than 2^-35.  Where floor(A) + 2 >= 2^16 every draw is a candidate.  The field is 16 bits wide so that
+// the mask folds into the compare (v_cmp_lt_u32_sdwa on WORD_0): the test is ONE v_fma_f64 and ONE compare per 64 draws, against
+// a 10-instruction modular multiply for the exact form.  It is a SUPERSET of the exact test, 1 to 2 units of 2^-16 wide beyond A
+// (~2.3e-5 of the draws: 5 % extra candidates at 5e-4 per row); every candidate's exact x2 is then computed with the integer
+// multiply and the exact threshold test runs in the resolve step, so the result is bit-identical.  gev_dbg_prefilter_sweep checks
+// d in [-SB_PF_DNEG, SB_PF_DPOS] exhaustively over all 2^31 - 2 engine states x 256 multipliers, with the kernel's own constants.
 template <class Flush>
 __device__ __forceinline__ void scan_candidates(const SmpTabs* __restrict__ T, SmpWave* __restrict__ W, u32 engine_seed, u32 amax,
                                                 u32 first_row, u32 n_draws, u32& count, Flush&& flush)
@@ -134,14 +161,16 @@ __device__ __forceinline__ void scan_candidates(const SmpTabs* __restrict__ T, S
     for (u32 q = 0; q < SB_TASKS; q++) n_max = max(n_max, rl_u32(n_draws, q * 8u));
     if (n_max == 0) return;
     u32 x = mulmod31(T->pow_even[j], minstd_seed(engine_seed));   // exact high digit (engine output 2 j + 2) of draw j
-    const double A = (double)amax * (1048576.0 / 2147483647.0);
-    const bool all_cand = A + 8.0 >= 1048576.0;            // thresholds near 1: every draw is a candidate
-    const u32 thr20 = all_cand ? 0xffffffffu : (u32)A + 7u;   // >= ceil(A) + 6
-    const double C = 6442450944.0 + 4.0 / 1048576.0;       // 1.5 * 2^32 + 4 u
+    const double A = (double)amax * (SB_PF_ONE / 2147483647.0);      // floor(A) is exact: see the header comment
+    const bool all_cand = A + (double)SB_PF_MARGIN >= SB_PF_ONE;     // thresholds near 1: every draw is a candidate
+    const u32 thr_pf = all_cand ? 0xffffffffu : (u32)A + SB_PF_MARGIN;
+    double C = SB_PF_BIAS;
+    asm volatile("" : "+s"(C));                            // wave-uniform: lives in a scalar register pair, which the FMA reads directly (left to
+                                                           // itself the compiler rebuilds it in vector registers with two moves per half-step)
     for (u32 base = 0; base < n_max; base += SB_BLK) {
         const u32 n_here = n_draws > base ? min((u32)SB_BLK, n_draws - base) : 0u;   // draws of the lane's task in this block
         const u32 cnt = n_here > j ? (n_here - j + 7u) >> 3 : 0u;                    // ... of which the lane owns m < cnt
-        const u32 thr = cnt ? thr20 : 0u;
+        const u32 thr = cnt ? thr_pf : 0u;
         u32 n_lo = SB_BLK, n_hi = 0;                       // shortest non-empty and longest range of the eight tasks
 #pragma unroll
         for (u32 q = 0; q < SB_TASKS; q++) { const u32 nq = rl_u32(n_here, q * 8u); n_hi = max(n_hi, nq); if (nq) n_lo = min(n_lo, nq); }
@@ -149,7 +178,7 @@ __device__ __forceinline__ void scan_candidates(const SmpTabs* __restrict__ T, S
         const u32 m_end = (n_hi + 7u) >> 3;                // the largest cnt (lane 0 of the longest task)
         const double xd = (double)x;
         const u32 row0 = first_row + base + j;
-        auto testk = [&](double k) -> bool { return ((u32)__double2loint(__fma_rn(xd, k, C)) & 0xfffffu) < thr; };
+        auto testk = [&](double k) -> bool { return ((u32)__double2loint(__fma_rn(xd, k, C)) & SB_PF_MASK) < thr; };
         auto push = [&](unsigned long long mk, bool c, u32 m) {
             if (c) {
                 const u32 idx = count + mbcnt64(mk);

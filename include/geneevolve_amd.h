@@ -791,8 +791,9 @@ int gev_set_stitch_mode(gev_ctx*, int mode);
 int    gev_dbg_verify_planes(gev_ctx*, int pop, int chr, const uint64_t* founder_seeds, unsigned long long* n_bad_words, unsigned long long* n_bad_parts);
 /* gev_dbg_prefilter_sweep: exhaustive check of the FP64 candidate prefilter of the batched sampling kernels over the engine states
  * [x_begin, x_end) (the whole state space of minstd_rand0 is 1 .. 2^31-2) and all 256 per-lane multipliers of a scan block: out[0] = states x multipliers
- * for which the prefilter's 20-bit fraction deviates from the exact one by more than its proven bound (must be 0: the prefilter
- * then flags a superset of the exact candidates for every threshold), out[1] / out[2] = largest deviations seen. */
+ * for which the prefilter's 16-bit fraction field L deviates from the exact one, F = floor(x2 * 2^16 / M), by anything but d = L - F
+ * in {0, 1} (mod 2^16), the band the scan takes its margin from (must be 0: the prefilter then flags a superset of the exact
+ * candidates for every threshold), out[1] / out[2] = largest d / largest -d seen (1 and 0). */
 int    gev_dbg_prefilter_sweep(gev_ctx*, uint32_t x_begin, uint32_t x_end, unsigned long long out[3]);
 /* gev_dbg_output_chunk: no staging pass of the following genotype output calls takes more than max_units haplotype rows / individuals /
  * SNPs (SNPs: rounded down to a multiple of 64, at least 64), so that small tests run many passes; 0 = the byte budgets again.  Refused while a generation is pending. */
