@@ -24,6 +24,7 @@
 #include "gev_outputs.h"
 #include "gev_snpcount.h"
 #include "gev_paircount.h"
+#include "gev_migrant_record.h"
 #include "gev_ldcount.h"
 #include "gev_traitsum.h"
 #include "gev_select.h"
@@ -3365,30 +3366,16 @@ int gev_migrate(gev_ctx* c, const gev_move* moves, size_t n_moves)
     return GEV_OK;
 }
 // ---- cross-GPU form of the migration step ---------------------------------------------------
-// Packed record buffer (all offsets 16-byte aligned), for n individuals:
-//   [counts]  u32[n][nchr][2 haps][2] = (n_mut, n_parts) per haplotype row
-//   [sex]     u8[n]  Human::sex
-//   [planes]  per chr: 2n rows x stride bytes          [cv] per (phen, chr): 2n rows x stride_w32*4 bytes
-//   [muts]    per chr: u64 lists concatenated in row order   [parts] per chr: gev_part lists likewise
-struct PackLayout { size_t counts, sex, planes, cv, muts, parts, total; std::vector<size_t> mut_chr, parts_chr; };
-static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-static PackLayout pack_layout(gev_ctx* c, PopState& P, size_t n, const std::vector<u32>& counts)
+// The packed record's format and layout: gev_migrant_record.h.  Export and import fill and read its sections by index.
+static_assert(MigrantRecord::MUT_BYTES == sizeof(u64) && MigrantRecord::PART_BYTES == sizeof(gev_part), "list entries of the migrant record");
+// the record of n individuals of P whose header is `counts` (borrowed: it outlives the record)
+static MigrantRecord migrant_record(gev_ctx* c, PopState& P, size_t n, const std::vector<u32>& counts)
 {
-    PackLayout L; const int nchr = c->nchr;
-    size_t off = 0;
-    // chromosomes this context does not hold (locus-split population) take no space: both ends of an exchange hold the same set
-    L.counts = off; off = al16(off + n * nchr * 4 * sizeof(u32));
-    L.sex = off; off = al16(off + n);
-    L.planes = off; for (int k = 0; k < nchr; k++) if (c->chr_active[k] && c->dense && c->migrant_rows) off = al16(off + 2 * n * P.cs[k].stride);
-    L.cv = off; for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) if (c->chr_active[k]) off = al16(off + 2 * n * P.cv[p][k].stride_w32 * sizeof(u32));
-    L.mut_chr.assign(nchr, 0); L.parts_chr.assign(nchr, 0);
-    for (size_t i = 0; i < n; i++) for (int k = 0; k < nchr; k++) for (int h = 0; h < 2; h++) {
-        L.mut_chr[k] += counts[((i * nchr + k) * 2 + h) * 2]; L.parts_chr[k] += counts[((i * nchr + k) * 2 + h) * 2 + 1];
-    }
-    L.muts = off; for (int k = 0; k < nchr; k++) off = al16(off + L.mut_chr[k] * sizeof(u64));
-    L.parts = off; for (int k = 0; k < nchr; k++) off = al16(off + L.parts_chr[k] * sizeof(gev_part));
-    L.total = off;
-    return L;
+    const int nchr = c->nchr;
+    std::vector<size_t> stride(nchr), cv_row_bytes((size_t)c->nphen * nchr);
+    for (int k = 0; k < nchr; k++) stride[k] = P.cs[k].stride;
+    for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) cv_row_bytes[(size_t)p * nchr + k] = P.cv[p][k].stride_w32 * sizeof(u32);
+    return migrant_record_layout(n, nchr, c->nphen, c->chr_active.data(), c->dense && c->migrant_rows, stride.data(), cv_row_bytes.data(), counts.data());
 }
 // per-row list lengths of the selected individuals (device counts, one small D2H per chromosome); c->d_map then holds their
 // haplotype rows 2*individual, 2*individual+1
@@ -3402,7 +3389,7 @@ static int export_counts(gev_ctx* c, int pop, const uint64_t* positions, size_t 
         const u32 ph = P.logical.empty() ? (u32)positions[i] : P.logical[positions[i]];
         map[2 * i] = 2 * ph; map[2 * i + 1] = 2 * ph + 1;
     }
-    counts.assign(n * nchr * 4, 0);
+    counts.assign(MigrantRecord::n_counts(n, nchr), 0);
     if (!n) return GEV_OK;
     GEVC(h2d(c, c->d_map, map.data(), map.size() * sizeof(u32)));
     GEVC(c->d_cnt.ensure(4 * n + 4, c->stream));
@@ -3413,7 +3400,7 @@ static int export_counts(gev_ctx* c, int pop, const uint64_t* positions, size_t 
         HIPC(hipMemcpyAsync(tmp.data(), c->d_cnt.p, (c->track_intervals ? 4 : 2) * n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) for (int pass = 0; pass < 2; pass++)
-            counts[((i * nchr + k) * 2 + h) * 2 + pass] = tmp[pass * 2 * n + 2 * i + h];
+            counts[MigrantRecord::count_index(i, nchr, k, h, pass)] = tmp[pass * 2 * n + 2 * i + h];
     }
     return GEV_OK;
 }
@@ -3426,7 +3413,7 @@ int gev_export_size(gev_ctx* c, int pop, const uint64_t* positions, size_t n, si
     HIPC(hipSetDevice(c->device));
     std::vector<u32> counts;
     GEVC(export_counts(c, pop, positions, n, counts));
-    *bytes = pack_layout(c, P, n, counts).total;
+    *bytes = migrant_record(c, P, n, counts).total;
     return GEV_OK;
 }
 int gev_export_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n, void* device_buf, size_t bytes)
@@ -3439,41 +3426,35 @@ int gev_export_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n, vo
     GEVC(gev_sync(c));
     std::vector<u32> counts;
     GEVC(export_counts(c, pop, positions, n, counts));
-    const PackLayout L = pack_layout(c, P, n, counts);
-    if (bytes < L.total) return fail(GEV_EINVAL, "export_rows: buffer of %zu bytes, %zu needed", bytes, L.total);
+    const MigrantRecord rec = migrant_record(c, P, n, counts);
+    if (bytes < rec.total) return fail(GEV_EINVAL, "export_rows: buffer of %zu bytes, %zu needed", bytes, rec.total);
     if (!n) return GEV_OK;
     hipStream_t st = c->stream;
     uint8_t* out = (uint8_t*)device_buf;
     const int nchr = c->nchr;
     const u32* d_rows = c->d_map.as<u32>();               // haplotype rows 2*individual, 2*individual+1 (export_counts)
-    HIPC(hipMemcpyAsync(out + L.counts, counts.data(), counts.size() * sizeof(u32), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out + L.sex, P.d_sex[P.cur], d_rows, 1u, n);
-    size_t po = L.planes, co = L.cv, mo = L.muts, pa = L.parts;
+    HIPC(hipMemcpyAsync(out + rec.counts_at, counts.data(), counts.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gather_u8, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, out + rec.sex_at, P.d_sex[P.cur], d_rows, 1u, n);
     GEVC(c->d_cnt.ensure((2 * n + 1) * 4, st));
     u32* mcnt = c->d_cnt; u32* moff = mcnt + (2 * n + 1); u32* pcnt = moff + (2 * n + 1); u32* poff = pcnt + (2 * n + 1);
     for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
         ChrStatic& S = P.cs[k]; ChrState& cs = P.st[k];
         const u32 chunks = (u32)(S.stride / 16);
-        if (c->dense && c->migrant_rows) {
-            hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * n * chunks, 256)), dim3(256), 0, st, flat_rows(out + po, S.stride),
+        if (c->dense && c->migrant_rows)
+            hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * n * chunks, 256)), dim3(256), 0, st, flat_rows(out + rec.planes_at(k), S.stride),
                                pool_rows(P, k, cs.phys[P.pcur]), d_rows, (size_t)0, 2 * n, chunks);
-            po = al16(po + 2 * n * S.stride);
-        }
         // the records' lists, for the selected rows only, from whichever form the lists live in
         GEVC(selected_lists_count(c, P, k, d_rows, 2 * n, mcnt, pcnt));
         GEVC(scan_u32(c, mcnt, 2 * n, moff, nullptr));
         if (c->track_intervals) GEVC(scan_u32(c, pcnt, 2 * n, poff, nullptr));
-        GEVC(selected_lists_fill(c, P, k, d_rows, 2 * n, moff, (u64*)(out + mo), poff, (gev_part*)(out + pa)));
-        mo = al16(mo + L.mut_chr[k] * sizeof(u64)); pa = al16(pa + L.parts_chr[k] * sizeof(gev_part));
+        GEVC(selected_lists_fill(c, P, k, d_rows, 2 * n, moff, (u64*)(out + rec.muts_at(k)), poff, (gev_part*)(out + rec.parts_at(k))));
     }
     for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) {
         if (!c->chr_active[k]) continue;
-        CvStatic& V = P.cv[p][k];
-        const u32 cch = V.stride_w32 / 4;
-        hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)ceil_div(2 * n * cch, 256)), dim3(256), 0, st, (uint4*)(out + co), (size_t)cch,
+        const u32 cch = P.cv[p][k].stride_w32 / 4;
+        hipLaunchKernelGGL(k_gather_rows16, dim3((unsigned)ceil_div(2 * n * cch, 256)), dim3(256), 0, st, (uint4*)(out + rec.cv_at(p, k)), (size_t)cch,
                            (const uint4*)P.cvp[p][k][P.cur].p, (size_t)cch, d_rows, 2 * n, cch);
-        co = al16(co + 2 * n * V.stride_w32 * sizeof(u32));
     }
     KCHECK();
     HIPC(hipStreamSynchronize(st));
@@ -3498,13 +3479,155 @@ int gev_remove_rows(gev_ctx* c, int pop, const uint64_t* positions, size_t n)
     membership_changed(c, P);
     return GEV_OK;
 }
-// exclusive offsets (2n + 1 of them, from `base`) of the haplotype rows of chromosome k in a record's counts; pass 0: mutations, 1: interval parts
-static std::vector<u32> record_offsets(const std::vector<u32>& counts, size_t n, int nchr, int k, int pass, u32 base = 0)
+// ---- gev_import_rows: its steps, in the order the driver below issues them.  n immigrants become the physical rows r_old .. r_old + 2n
+struct ImportTrace {                                                  // GEV_TRACE_HOST: where an import's time goes (serialises the steps)
+    hipStream_t st; double t;
+    void mark(const char* what)
+    {
+        if (g_trace_host) { (void)hipStreamSynchronize(st); const double now = host_ms(); fprintf(stderr, "[gev] import_rows %s %.3f ms\n", what, now - t); t = now; }
+    }
+};
+// leaves: the record's header in `counts`, its layout in `rec`, size and state checked, the rebuild flag zeroed where rows are rebuilt
+static int import_header(gev_ctx* c, PopState& P, const uint8_t* in, size_t bytes, size_t n, std::vector<u32>& counts, MigrantRecord& rec)
 {
-    std::vector<u32> off(2 * n + 1);
-    off[0] = base;
-    for (size_t i = 0; i < n; i++) for (int h = 0; h < 2; h++) off[2 * i + h + 1] = off[2 * i + h] + counts[((i * nchr + k) * 2 + h) * 2 + pass];
-    return off;
+    hipStream_t st = c->stream;
+    if (bytes < MigrantRecord::n_counts(n, c->nchr) * sizeof(u32)) return fail(GEV_EINVAL, "import_rows: buffer too small for its own header");
+    counts.resize(MigrantRecord::n_counts(n, c->nchr));
+    HIPC(hipMemcpyAsync(counts.data(), in, counts.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    rec = migrant_record(c, P, n, counts);
+    if (bytes < rec.total) return fail(GEV_EINVAL, "import_rows: buffer of %zu bytes, %zu expected from its header", bytes, rec.total);
+    const bool rebuild = c->dense && !c->migrant_rows;
+    if (rebuild && !c->track_intervals) return fail(GEV_ESTATE, "import_rows: migrants without genotype rows need the interval state (gev_set_track_intervals)");
+    if (rebuild) { GEVC(c->d_flag.ensure(16, st)); HIPC(hipMemsetAsync(c->d_flag.p, 0, 4, st)); }
+    if ((P.n_phys + n) * 2 >= 0xffffffffull) return fail(GEV_EINVAL, "import_rows: too many rows");
+    return GEV_OK;
+}
+// leaves: pool units for the new rows of chromosome k in the current generation's table, `dst` naming those rows: from the free list the generations
+// keep (its entries behind the cursor are named by no table, and nothing is in flight after gev_sync) while it lasts, else from a new one
+static int import_units(gev_ctx* c, PopState& P, int k, size_t r_old, size_t n, ImportTrace& tr, RowRef& dst)
+{
+    ChrState& cs = P.st[k];
+    const size_t need_units = 2 * n * P.cs[k].nseg;
+    const bool reuse = cs.pool_list_valid && !cs.pool_force_rebuild && (size_t)cs.pool_cursor + need_units <= cs.pool_n_free;
+    if (!reuse) pool_new_stamp(cs);
+    const PoolWork pw = pool_work(c, P, k, P.pcur);                 // new slots of the CURRENT generation
+    if (!reuse) GEVC(pool_free_list(pw, r_old, c->stream));
+    tr.mark("free list");
+    GEVC(pool_take(pw, r_old, 2 * n, c->stream));
+    if (reuse) cs.pool_cursor += (u32)need_units; else cs.pool_list_valid = false;
+    tr.mark("units");
+    dst = pool_rows(P, k, pw.phys_alt + r_old * P.cs[k].nseg);
+    return GEV_OK;
+}
+// leaves: the new rows of chromosome k copied from the record's [planes] section (enqueued)
+static int import_rows_copied(gev_ctx* c, PopState& P, int k, const MigrantRecord& rec, const uint8_t* in, const RowRef& dst, size_t n)
+{
+    const u32 chunks = (u32)(P.cs[k].stride / 16);
+    hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * n * chunks, 256)), dim3(256), 0, c->stream, dst,
+                       flat_rows((void*)(in + rec.planes_at(k)), P.cs[k].stride), (const u32*)nullptr, (size_t)0, 2 * n, chunks);
+    KCHECK();
+    return GEV_OK;
+}
+// leaves: the new rows of chromosome k rebuilt (enqueued; c->d_flag tells of a missing panel or hap_index): the migrants travelled as lists, their
+// rows are the founder mosaic their ancestry intervals describe (:1198-1211), assembled from the founder panels of the parts' root populations
+static int import_rows_rebuilt(gev_ctx* c, PopState& P, int k, const MigrantRecord& rec, const uint8_t* in, const RowRef& dst, size_t n)
+{
+    hipStream_t st = c->stream;
+    const ChrStatic& S = P.cs[k];
+    const u32 chunks = (u32)(S.stride / 16);
+    const gev_part* parts = (const gev_part*)(in + rec.parts_at(k));
+    const std::vector<u32> offp = rec.row_offsets(k, 1);
+    std::vector<PanelRef> pr(c->n_pop);
+    for (int q = 0; q < c->n_pop; q++) {
+        const ChrStatic& F = c->pop[q].cs[k];
+        pr[q] = PanelRef{F.panel.as<u32>(), (u64)(F.stride / 4), (F.panel_rows && F.L == S.L) ? (u64)F.panel_rows : 0ull};
+    }
+    // one upload: the rows' part offsets, then the panel table (8-byte aligned behind them)
+    const size_t off_words = (offp.size() + 1) & ~(size_t)1;
+    std::vector<u32> up(off_words + pr.size() * sizeof(PanelRef) / sizeof(u32), 0);
+    memcpy(up.data(), offp.data(), offp.size() * sizeof(u32)); memcpy(up.data() + off_words, pr.data(), pr.size() * sizeof(PanelRef));
+    GEVC(h2d(c, c->d_poff, up.data(), up.size()));
+    const PanelRef* d_panels = (const PanelRef*)(c->d_poff + off_words);
+    GEVC(c->d_prange.ensure(std::max<size_t>(offp[2 * n], 1), st));
+    if (offp[2 * n]) hipLaunchKernelGGL(k_parts_locus_range, dim3((unsigned)ceil_div((size_t)offp[2 * n], 256)), dim3(256), 0, st, parts, (size_t)offp[2 * n],
+                                        P.d_chrdev, k, c->d_prange);
+    hipLaunchKernelGGL(k_rebuild_rows, dim3((unsigned)(2 * n), (unsigned)ceil_div(chunks, 4 * REBUILD_CPW)), dim3(256), 0, st, c->d_poff, parts,
+                       c->d_prange, (u32)S.L, d_panels, c->n_pop, dst, chunks, c->d_flag.as<u32>());
+    KCHECK();
+    return GEV_OK;
+}
+// leaves: the new rows' lists of chromosome k appended as pieces of their own behind the arenas, their table rows written behind the
+// existing ones, the arena fill counts taken (one host wait); nothing of the residents is touched
+static int import_list_pieces(gev_ctx* c, PopState& P, int k, const MigrantRecord& rec, const uint8_t* in, size_t r_old, size_t n)
+{
+    hipStream_t st = c->stream;
+    ChrState::LpState& lp = P.st[k].lp;
+    const bool track = c->track_intervals;
+    const std::vector<u32> offm = rec.row_offsets(k, 0), offp = rec.row_offsets(k, 1);
+    GEVC(c->d_cnt.ensure((2 * n + 1) * 2, st));
+    u32* d_offm = c->d_cnt; u32* d_offp = d_offm + (2 * n + 1);
+    HIPC(hipMemcpyAsync(d_offm, offm.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_offp, offp.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
+    const size_t tab_entries = (r_old + 2 * n) * lp.nseg;
+    if (track) GEVC(lp.ptab[P.cur].ensure(tab_entries, st, /*keep=*/true, 1.25));
+    GEVC(lp.mtab[P.cur].ensure(tab_entries, st, /*keep=*/true, 1.25));
+    const size_t need_p = track ? (size_t)lp.p_used + offp[2 * n] + 2 * n * lp.nseg : 0, need_m = (size_t)lp.m_used + offm[2 * n];
+    if (need_p >= 0xfffffff0u || need_m >= 0xfffffff0u) return fail(GEV_EDEVICE, "import_rows: list arenas beyond 2^32 entries");
+    if (track && need_p > lp.parena.capacity()) GEVC(lp.parena.ensure(need_p, st, true, 1.5));
+    if (need_m > lp.marena.capacity()) GEVC(lp.marena.ensure(std::max<size_t>(need_m, 16), st, true, 1.5));
+    HIPC(hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(u32), st));
+    hipLaunchKernelGGL(k_lp_import, dim3((unsigned)ceil_div(2 * n * LP_MAXSEG, 256)), dim3(256), 0, st,
+                       track ? d_offp : (const u32*)nullptr, track ? (const gev_part*)(in + rec.parts_at(k)) : (const gev_part*)nullptr, d_offm, (const u64*)(in + rec.muts_at(k)),
+                       r_old, 2 * n, track ? lp.ptab[P.cur] : (uint2*)nullptr, lp.mtab[P.cur], lp.parena, lp.marena,
+                       lp.p_used, lp.m_used, (u32)(lp.parena.capacity()), (u32)(lp.marena.capacity()), lp.nseg, lp.lgw, (u64)P.cs[k].rbp.front(),
+                       lp.ctr, lp.ctr + 2);
+    KCHECK();
+    u32 h[4] = {0, 0, 0, 0};
+    HIPC(hipMemcpyAsync(h, lp.ctr.p, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (h[2]) return fail(GEV_EDEVICE, "import_rows: list arena overflow (internal error)");
+    lp.p_used += h[0]; lp.m_used += h[1];
+    P.st[k].csr_valid = false;
+    return GEV_OK;
+}
+// leaves: one kind of list (T: u64 mutations, gev_part intervals) of the new rows appended in CSR form: `off`, the rows' offsets from the old
+// total on, at entries r_old .. r_old + 2n of doff (entry r_old already equals the old total), the elements behind `data`
+extern "C++" template <class T> static int import_csr_list(gev_ctx* c, const std::vector<u32>& off, const T* src, size_t r_old, Dev<u32>& doff, Dev<T>& data, size_t& total, size_t min_elems)
+{
+    hipStream_t st = c->stream;
+    const size_t add = off.back() - off[0];
+    HIPC(hipMemcpyAsync(doff + r_old, off.data(), off.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIPC(hipStreamSynchronize(st));
+    GEVC(data.ensure(std::max<size_t>(total + add, min_elems), st, /*keep=*/true, 1.25));
+    if (add) HIPC(hipMemcpyAsync(data + total, src, add * sizeof(T), hipMemcpyDeviceToDevice, st));
+    total += add;
+    return GEV_OK;
+}
+// leaves: the new rows' CV rows of every (phenotype, chromosome) behind the existing ones (enqueued), the allele frequencies stale
+static int import_cv_rows(gev_ctx* c, PopState& P, const MigrantRecord& rec, const uint8_t* in, size_t r_old, size_t n)
+{
+    for (int p = 0; p < c->nphen; p++) for (int k = 0; k < c->nchr; k++) {
+        if (!c->chr_active[k]) continue;
+        CvStatic& V = P.cv[p][k];
+        HIPC(hipMemcpyAsync(P.cvp[p][k][P.cur] + r_old * V.stride_w32, in + rec.cv_at(p, k), 2 * n * V.stride_w32 * sizeof(u32), hipMemcpyDeviceToDevice, c->stream));
+        V.frq_valid = false;
+    }
+    return GEV_OK;
+}
+// leaves: everything enqueued done and the rebuild flag checked; the n new individuals behind the others in the logical order
+static int import_finish(gev_ctx* c, PopState& P, size_t n_old, size_t n)
+{
+    u32 rb_flag = 0;
+    if (c->dense && !c->migrant_rows) HIPC(hipMemcpyAsync(&rb_flag, c->d_flag.p, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if (rb_flag & 2u) return fail(GEV_ESTATE, "import_rows: an immigrant descends from a root population whose founder panel is not held here (gev_upload_founder_panel / gev_synth_founder_panel)");
+    if (rb_flag & 1u) return fail(GEV_EINVAL, "import_rows: Error: p.hap_index is not in range");
+    if (P.logical.empty()) { P.logical.resize(P.n_people); for (size_t i = 0; i < P.n_people; i++) P.logical[i] = (u32)i; }
+    for (size_t i = 0; i < n; i++) P.logical.push_back((u32)(n_old + i));
+    P.n_phys = n_old + n;
+    membership_changed(c, P);
+    return GEV_OK;
 }
 int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, size_t n)
 {
@@ -3515,144 +3638,35 @@ int gev_import_rows(gev_ctx* c, int pop, const void* device_buf, size_t bytes, s
     if (!device_buf) return fail(GEV_EINVAL, "import_rows: null buffer");
     HIPC(hipSetDevice(c->device));
     GEVC(gev_sync(c));
-    hipStream_t st = c->stream;
-    const int nchr = c->nchr;
     const uint8_t* in = (const uint8_t*)device_buf;
-    double tr_t = host_ms();
-    auto mark = [&](const char* what) {                   // GEV_TRACE_HOST: where an import's time goes (serialises the steps)
-        if (!g_trace_host) return;
-        (void)hipStreamSynchronize(st);
-        const double now = host_ms(); fprintf(stderr, "[gev] import_rows %s %.3f ms\n", what, now - tr_t); tr_t = now;
-    };
-    if (bytes < n * nchr * 4 * sizeof(u32)) return fail(GEV_EINVAL, "import_rows: buffer too small for its own header");
-    std::vector<u32> counts(n * nchr * 4);
-    HIPC(hipMemcpyAsync(counts.data(), in, counts.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    const PackLayout L = pack_layout(c, P, n, counts);
-    if (bytes < L.total) return fail(GEV_EINVAL, "import_rows: buffer of %zu bytes, %zu expected from its header", bytes, L.total);
-    const bool rebuild = c->dense && !c->migrant_rows;
-    if (rebuild && !c->track_intervals) return fail(GEV_ESTATE, "import_rows: migrants without genotype rows need the interval state (gev_set_track_intervals)");
-    if (rebuild) { GEVC(c->d_flag.ensure(16, st)); HIPC(hipMemsetAsync(c->d_flag.p, 0, 4, st)); }
-    const size_t n_old = P.n_phys, n_new = n_old + n, r_old = 2 * n_old;     // physical append behind every existing row
-    if (n_new * 2 >= 0xffffffffull) return fail(GEV_EINVAL, "import_rows: too many rows");
-    mark("header");
-    GEVC(ensure_capacity(c, pop, n_new));                              // keeps the current buffers' content
-    mark("capacity");
-    HIPC(hipMemcpyAsync(P.d_sex[P.cur] + n_old, in + L.sex, n, hipMemcpyDeviceToDevice, st));
-    size_t po = L.planes, co = L.cv, mo = L.muts, pa = L.parts;
-    for (int k = 0; k < nchr; k++) {
+    ImportTrace tr{c->stream, host_ms()};
+    std::vector<u32> counts; MigrantRecord rec;
+    GEVC(import_header(c, P, in, bytes, n, counts, rec));
+    const size_t n_old = P.n_phys, r_old = 2 * n_old;                  // physical append behind every existing row
+    tr.mark("header");
+    GEVC(ensure_capacity(c, pop, n_old + n));                           // keeps the current buffers' content
+    tr.mark("capacity");
+    HIPC(hipMemcpyAsync(P.d_sex[P.cur] + n_old, in + rec.sex_at, n, hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < c->nchr; k++) {
         if (!c->chr_active[k]) continue;
-        ChrStatic& S = P.cs[k]; ChrState& cs = P.st[k];
+        ChrState& cs = P.st[k];
         if (c->dense) {
-            // units for the immigrants' segments: from the free list the generations keep (its entries behind the cursor are named by
-            // no table, and nothing is in flight after gev_sync) while it lasts, else from a new one
-            const size_t need_units = 2 * n * S.nseg;
-            const bool reuse = cs.pool_list_valid && !cs.pool_force_rebuild && (size_t)cs.pool_cursor + need_units <= cs.pool_n_free;
-            if (!reuse) pool_new_stamp(cs);
-            const PoolWork pw = pool_work(c, P, k, P.pcur);           // new slots of the CURRENT generation
-            if (!reuse) GEVC(pool_free_list(pw, r_old, st));
-            mark("free list");
-            GEVC(pool_take(pw, r_old, 2 * n, st));
-            if (reuse) cs.pool_cursor += (u32)need_units; else cs.pool_list_valid = false;
-            mark("units");
-            const u32 chunks = (u32)(S.stride / 16);
-            if (c->migrant_rows) {
-                hipLaunchKernelGGL(k_copy_rows16, dim3((unsigned)ceil_div(2 * n * chunks, 256)), dim3(256), 0, st, pool_rows(P, k, pw.phys_alt + r_old * S.nseg),
-                                   flat_rows((void*)(in + po), S.stride), (const u32*)nullptr, (size_t)0, 2 * n, chunks);
-                KCHECK();
-                po = al16(po + 2 * n * S.stride);
-            } else {
-                // the migrants travelled as lists: their rows are the founder mosaic their ancestry intervals describe (:1198-1211),
-                // assembled here from the founder panels of the parts' root populations
-                const std::vector<u32> offp = record_offsets(counts, n, nchr, k, 1);
-                std::vector<PanelRef> pr(c->n_pop);
-                for (int q = 0; q < c->n_pop; q++) {
-                    const ChrStatic& F = c->pop[q].cs[k];
-                    pr[q] = PanelRef{F.panel.as<u32>(), (u64)(F.stride / 4), (F.panel_rows && F.L == S.L) ? (u64)F.panel_rows : 0ull};
-                }
-                // one upload: the rows' part offsets, then the panel table (8-byte aligned behind them)
-                const size_t off_words = (offp.size() + 1) & ~(size_t)1;
-                std::vector<u32> up(off_words + pr.size() * sizeof(PanelRef) / sizeof(u32), 0);
-                memcpy(up.data(), offp.data(), offp.size() * sizeof(u32)); memcpy(up.data() + off_words, pr.data(), pr.size() * sizeof(PanelRef));
-                GEVC(h2d(c, c->d_poff, up.data(), up.size()));
-                const PanelRef* d_panels = (const PanelRef*)(c->d_poff + off_words);
-                GEVC(c->d_prange.ensure(std::max<size_t>(offp[2 * n], 1), st));
-                if (offp[2 * n]) hipLaunchKernelGGL(k_parts_locus_range, dim3((unsigned)ceil_div((size_t)offp[2 * n], 256)), dim3(256), 0, st, (const gev_part*)(in + pa), (size_t)offp[2 * n],
-                                                    P.d_chrdev, k, c->d_prange);
-                hipLaunchKernelGGL(k_rebuild_rows, dim3((unsigned)(2 * n), (unsigned)ceil_div(chunks, 4 * REBUILD_CPW)), dim3(256), 0, st, c->d_poff, (const gev_part*)(in + pa),
-                                   c->d_prange, (u32)S.L, d_panels, c->n_pop, pool_rows(P, k, pw.phys_alt + r_old * S.nseg), chunks, c->d_flag.as<u32>());
-                KCHECK();
-            }
-            mark("rows");
+            RowRef dst{};
+            GEVC(import_units(c, P, k, r_old, n, tr, dst));
+            GEVC(c->migrant_rows ? import_rows_copied(c, P, k, rec, in, dst, n) : import_rows_rebuilt(c, P, k, rec, in, dst, n));
+            tr.mark("rows");
         }
         if (cs.lp.valid) {
-            // the lists live as pieces: the immigrants' lists are cut into pieces of their own, appended to the arenas, and their
-            // table rows written behind the existing ones; nothing of the residents is touched
-            ChrState::LpState& lp = cs.lp;
-            const bool track = c->track_intervals;
-            const std::vector<u32> offm = record_offsets(counts, n, nchr, k, 0), offp = record_offsets(counts, n, nchr, k, 1);
-            GEVC(c->d_cnt.ensure((2 * n + 1) * 2, st));
-            u32* d_offm = c->d_cnt; u32* d_offp = d_offm + (2 * n + 1);
-            HIPC(hipMemcpyAsync(d_offm, offm.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-            HIPC(hipMemcpyAsync(d_offp, offp.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-            const size_t tab_entries = (r_old + 2 * n) * lp.nseg;
-            if (track) GEVC(lp.ptab[P.cur].ensure(tab_entries, st, /*keep=*/true, 1.25));
-            GEVC(lp.mtab[P.cur].ensure(tab_entries, st, /*keep=*/true, 1.25));
-            const size_t need_p = track ? (size_t)lp.p_used + offp[2 * n] + 2 * n * lp.nseg : 0, need_m = (size_t)lp.m_used + offm[2 * n];
-            if (need_p >= 0xfffffff0u || need_m >= 0xfffffff0u) return fail(GEV_EDEVICE, "import_rows: list arenas beyond 2^32 entries");
-            if (track && need_p > lp.parena.capacity()) GEVC(lp.parena.ensure(need_p, st, true, 1.5));
-            if (need_m > lp.marena.capacity()) GEVC(lp.marena.ensure(std::max<size_t>(need_m, 16), st, true, 1.5));
-            HIPC(hipMemsetAsync(lp.ctr.p, 0, 4 * sizeof(u32), st));
-            hipLaunchKernelGGL(k_lp_import, dim3((unsigned)ceil_div(2 * n * LP_MAXSEG, 256)), dim3(256), 0, st,
-                               track ? d_offp : (const u32*)nullptr, track ? (const gev_part*)(in + pa) : (const gev_part*)nullptr, d_offm, (const u64*)(in + mo),
-                               r_old, 2 * n, track ? lp.ptab[P.cur] : (uint2*)nullptr, lp.mtab[P.cur], lp.parena, lp.marena,
-                               lp.p_used, lp.m_used, (u32)(lp.parena.capacity()), (u32)(lp.marena.capacity()), lp.nseg, lp.lgw, (u64)S.rbp.front(),
-                               lp.ctr, lp.ctr + 2);
-            KCHECK();
-            u32 h[4] = {0, 0, 0, 0};
-            HIPC(hipMemcpyAsync(h, lp.ctr.p, sizeof h, hipMemcpyDeviceToHost, st));
-            HIPC(hipStreamSynchronize(st));
-            if (h[2]) return fail(GEV_EDEVICE, "import_rows: list arena overflow (internal error)");
-            lp.p_used += h[0]; lp.m_used += h[1];
-            cs.csr_valid = false;
-            mark("list pieces");
-        } else for (int pass = 0; pass < 2; pass++) {
-            if (pass == 1 && !c->track_intervals) continue;
-            size_t& total = pass == 0 ? cs.mut_total[P.cur] : cs.parts_total[P.cur];
-            const std::vector<u32> off = record_offsets(counts, n, nchr, k, pass, (u32)total);
-            const size_t add = off[2 * n] - off[0];
-            Dev<u32>& doff = pass == 0 ? cs.moff[P.cur] : cs.poff[P.cur];
-            // offsets of the appended rows: entries r_old .. r_old + 2n (entry r_old already equals the old total)
-            HIPC(hipMemcpyAsync(doff + r_old, off.data(), (2 * n + 1) * sizeof(u32), hipMemcpyHostToDevice, st));
-            HIPC(hipStreamSynchronize(st));
-            if (pass == 0) {
-                GEVC(cs.mpos[P.cur].ensure(std::max<size_t>(total + add, 2), st, /*keep=*/true, 1.25));
-                if (add) HIPC(hipMemcpyAsync(cs.mpos[P.cur] + total, in + mo, add * sizeof(u64), hipMemcpyDeviceToDevice, st));
-            } else {
-                GEVC(cs.parts[P.cur].ensure(std::max<size_t>(total + add, 1), st, true, 1.25));
-                if (add) HIPC(hipMemcpyAsync(cs.parts[P.cur] + total, in + pa, add * sizeof(gev_part), hipMemcpyDeviceToDevice, st));
-            }
-            total += add;
+            GEVC(import_list_pieces(c, P, k, rec, in, r_old, n));
+            tr.mark("list pieces");
+        } else {
+            GEVC(import_csr_list(c, rec.row_offsets(k, 0, (u32)cs.mut_total[P.cur]), (const u64*)(in + rec.muts_at(k)), r_old, cs.moff[P.cur], cs.mpos[P.cur], cs.mut_total[P.cur], 2));
+            if (c->track_intervals)
+                GEVC(import_csr_list(c, rec.row_offsets(k, 1, (u32)cs.parts_total[P.cur]), (const gev_part*)(in + rec.parts_at(k)), r_old, cs.poff[P.cur], cs.parts[P.cur], cs.parts_total[P.cur], 1));
         }
-        mo = al16(mo + L.mut_chr[k] * sizeof(u64)); pa = al16(pa + L.parts_chr[k] * sizeof(gev_part));
     }
-    for (int p = 0; p < c->nphen; p++) for (int k = 0; k < nchr; k++) {
-        if (!c->chr_active[k]) continue;
-        CvStatic& V = P.cv[p][k];
-        HIPC(hipMemcpyAsync(P.cvp[p][k][P.cur] + r_old * V.stride_w32, in + co, 2 * n * V.stride_w32 * sizeof(u32), hipMemcpyDeviceToDevice, st));
-        co = al16(co + 2 * n * V.stride_w32 * sizeof(u32));
-        V.frq_valid = false;
-    }
-    u32 rb_flag = 0;
-    if (rebuild) HIPC(hipMemcpyAsync(&rb_flag, c->d_flag.p, sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    if (rb_flag & 2u) return fail(GEV_ESTATE, "import_rows: an immigrant descends from a root population whose founder panel is not held here (gev_upload_founder_panel / gev_synth_founder_panel)");
-    if (rb_flag & 1u) return fail(GEV_EINVAL, "import_rows: Error: p.hap_index is not in range");
-    if (P.logical.empty()) { P.logical.resize(P.n_people); for (size_t i = 0; i < P.n_people; i++) P.logical[i] = (u32)i; }
-    for (size_t i = 0; i < n; i++) P.logical.push_back((u32)(n_old + i));
-    P.n_phys = n_new;
-    membership_changed(c, P);
-    return GEV_OK;
+    GEVC(import_cv_rows(c, P, rec, in, r_old, n));
+    return import_finish(c, P, n_old, n);
 }
 
 // ---- output materialisation ---------------------------------------------------------------

@@ -120,6 +120,85 @@ def compare_dense(ctx, fx, g, ip, nchr, label, chrs=None):
     return checked
 
 
+def _hip():
+    """the HIP runtime the library itself is linked to (already loaded with it), so that pointers and allocations are the same runtime's"""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so.7")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]; hip.hipFree.argtypes = [C.c_void_p]
+    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return hip
+
+
+def device_buffer(nbytes, zero=False):
+    """a plain device allocation (export / import records live on the device), zero-filled on request -> (pointer, free())"""
+    import ctypes as C
+    hip = _hip()
+    p = C.c_void_p()
+    assert hip.hipMalloc(C.byref(p), max(nbytes, 16)) == 0 and p.value
+    if zero:
+        assert hip.hipMemset(p, 0, max(nbytes, 16)) == 0
+    return p.value, lambda: hip.hipFree(p.value)
+
+
+def read_device_u32(ptr, n):
+    """copy n uint32 from a device pointer"""
+    out = np.empty(n, dtype=np.uint32)
+    rc = _hip().hipMemcpy(out.ctypes.data, ptr, 4 * n, 2)      # hipMemcpyDeviceToHost
+    assert rc == 0, f"hipMemcpy failed ({rc})"
+    return out
+
+
+# ---- the packed migrant record of gev_export_rows / gev_import_rows, decoded from the format comment of csrc/gev_migrant_record.h
+def _up(x, m):
+    return -(-x // m) * m
+
+
+def record_sex_offset(n, nchr):
+    """byte offset of the sexes: behind the counts header u32[n][nchr][2][2], at the next multiple of 16"""
+    return _up(n * nchr * 2 * 2 * 4, 16)
+
+
+def decode_record(rec, n, Ls, cv_pos, n_pop, rows_travel, active=None):
+    """rec: the record's bytes (uint8).  Ls[k]: loci of chromosome k; cv_pos[p][k]: CV positions in file order -> dict: total, counts
+    [n][nchr][2][2], sex [n], rows[k] (bits [2n][L], None where no rows travel), cv[p][k] (bits [2n][C], file order), muts[k], parts[k]"""
+    from geneevolve_amd.capi import PART_DTYPE, unpack_rows
+    nchr, cur = len(Ls), 0
+    active = [True] * nchr if active is None else active
+
+    def take(nbytes):                                            # one section: its bytes; the next one begins at a multiple of 16
+        nonlocal cur
+        at = cur; cur = _up(cur + nbytes, 16)
+        assert at + nbytes <= len(rec), "the record is shorter than its header says"
+        return rec[at:at + nbytes]
+
+    d = {"counts": take(n * nchr * 16).view(np.uint32).reshape(n, nchr, 2, 2)}
+    assert cur == record_sex_offset(n, nchr)
+    d["sex"] = take(n)
+    d["rows"] = []
+    for k in range(nchr):
+        stride = _up(-(-Ls[k] // 8), 128)
+        on = active[k] and rows_travel
+        d["rows"].append(np.unpackbits(take(2 * n * stride).reshape(2 * n, stride), axis=1, bitorder="little")[:, :Ls[k]] if on else None)
+    rp_bits = (n_pop - 1).bit_length()
+    d["cv"] = []
+    for pos_p in cv_pos:
+        d["cv"].append([])
+        for k in range(nchr):
+            if not active[k]:
+                d["cv"][-1].append(None); continue
+            C = len(pos_p[k]); sub = max(-(-C // 32), 1); words = _up(sub * (1 + rp_bits), 4)
+            raw = take(2 * n * words * 4).view(np.uint32).reshape(2 * n, words)
+            by_position = unpack_rows(raw[:, :sub], C)
+            in_file_order = np.empty_like(by_position)
+            in_file_order[:, np.argsort(np.asarray(pos_p[k]), kind="stable")] = by_position
+            d["cv"][-1].append(in_file_order)
+    d["muts"] = [take(int(d["counts"][:, k, :, 0].sum()) * 8).view(np.uint64) for k in range(nchr)]
+    d["parts"] = [take(int(d["counts"][:, k, :, 1].sum()) * 32).view(PART_DTYPE) for k in range(nchr)]
+    d["total"] = cur
+    return d
+
+
 def bits_equal(a, b):
     """bit-exact comparison of float64 arrays (NaN-safe, distinguishes -0.0)"""
     return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))

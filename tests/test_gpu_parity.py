@@ -154,15 +154,6 @@ def test_alternative_stitch_kernels_give_the_same_state(gpu_lib, oracle_lib, mod
     run_pair(gpu_lib, oracle_lib, cfg, n_gen=2, seed=7, stitch_mode=mode)
 
 
-def _read_device_u32(ptr, n):
-    """copy n uint32 from a device pointer (the library's slot -> row table)"""
-    hip = C.CDLL("libamdhip64.so")
-    out = np.empty(n, dtype=np.uint32)
-    rc = hip.hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(ptr), C.c_size_t(4 * n), C.c_int(2))      # hipMemcpyDeviceToHost
-    assert rc == 0, f"hipMemcpy failed ({rc})"
-    return out
-
-
 @pytest.mark.parametrize("max_ranges,arena,literal,lanes", [(32, 0, 0, 8), (32, 0, 1, 1), (32, 0, 0, 1), (1, 0, 0, 8), (5, 0, 1, 1), (32, 6, 0, 8), (7, 3, 0, 8)])
 def test_lists_as_shared_pieces_per_position_range(gpu_lib, oracle_lib, monkeypatch, max_ranges, arena, literal, lanes):
     """the mutation / interval lists live as pieces per position range, shared between parent and offspring where a gamete has
@@ -227,7 +218,7 @@ def test_segments_without_a_crossover_share_the_parental_unit(gpu_lib, oracle_li
         before = []
         for c in range(cfg.nchr):
             _, _, n_slots, tab, nseg = g.plane_ptr(0, c)
-            before.append(_read_device_u32(tab, n_slots * nseg))
+            before.append(helpers.read_device_u32(tab, n_slots * nseg))
         _, _, sw0, st0 = g.stitch_totals()
         assert np.array_equal(sg.reproduce(0, gen, n_people=n), so.reproduce(0, gen, n_people=n)), f"sex differs at generation {gen}"
         bw1, bt1, sw1, st1 = g.stitch_totals()
@@ -238,7 +229,7 @@ def test_segments_without_a_crossover_share_the_parental_unit(gpu_lib, oracle_li
         for c in range(cfg.nchr):
             _, unit_bytes, n_slots, tab, nseg = g.plane_ptr(0, c)
             assert n_slots == 2 * n and unit_bytes == 16 * min(seg_chunks, 256) and nseg == -(-3840 // unit_bytes)      # rows of 30000 bits = 3840 bytes = 240 chunks (a longer segment shrinks to 256 chunks)
-            after = _read_device_u32(tab, n_slots * nseg)
+            after = helpers.read_device_u32(tab, n_slots * nseg)
             inherited = np.isin(after, before[c])
             fresh = after[~inherited]
             assert len(np.unique(fresh)) == len(fresh), "two written segments were given the same pool unit"
@@ -1971,15 +1962,6 @@ def test_set_cvs_between_generations_reaches_every_population(gpu_lib, oracle_li
     g.close(); o.close()
 
 
-def _device_buffer(nbytes):
-    """a plain device allocation of the HIP runtime the library is linked to (export / import records live on the device)"""
-    hip = C.CDLL("libamdhip64.so.7")
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]; hip.hipFree.argtypes = [C.c_void_p]
-    p = C.c_void_p()
-    assert hip.hipMalloc(C.byref(p), max(nbytes, 16)) == 0 and p.value
-    return p.value, lambda: hip.hipFree(C.c_void_p(p.value))
-
-
 @pytest.mark.parametrize("change", ["migrate_swap", "remove_import", "materialize"])
 def test_device_couples_do_not_outlive_a_change_of_rows(gpu_lib, oracle_lib, change):
     """Couples gev_random_mate leaves on the device name physical rows.  When the population's rows change before the
@@ -2016,7 +1998,7 @@ def test_device_couples_do_not_outlive_a_change_of_rows(gpu_lib, oracle_lib, cha
 
     def remove_import(src, dst, who, gone):
         nb = g.export_size(src, who)
-        dev, free = _device_buffer(nb); bufs.append(free)
+        dev, free = helpers.device_buffer(nb); bufs.append(free)
         g.export_rows(src, who, dev, nb)
         ob = o.export_size(src, who); host = np.zeros(-(-ob // 8), dtype=np.uint64)
         o.export_rows(src, who, host.ctypes.data, ob)
@@ -2062,9 +2044,9 @@ def _record_sexes(ctx, pop, nchr, on_device):
     who = np.arange(n, dtype=np.uint64)
     nb = ctx.export_size(pop, who)
     if on_device:
-        dev, free = _device_buffer(nb)
+        dev, free = helpers.device_buffer(nb)
         ctx.export_rows(pop, who, dev, nb)
-        sex = _read_device_u32(dev + ((n * nchr * 16 + 15) & ~15), -(-n // 4)).view(np.uint8)[:n].copy()
+        sex = helpers.read_device_u32(dev + helpers.record_sex_offset(n, nchr), -(-n // 4)).view(np.uint8)[:n].copy()
         free()
         return sex
     b = np.zeros(nb // 8, dtype=np.uint64)
@@ -2135,7 +2117,7 @@ def test_migration_behind_an_import_moves_every_row_and_value(gpu_lib, oracle_li
 
     def copy_in(src, dst, who, gone):
         nb = g.export_size(src, who)
-        dev, free = _device_buffer(nb); bufs.append(free)
+        dev, free = helpers.device_buffer(nb); bufs.append(free)
         g.export_rows(src, who, dev, nb)
         ob = o.export_size(src, who); host = np.zeros(-(-ob // 8), dtype=np.uint64)
         o.export_rows(src, who, host.ctypes.data, ob)
