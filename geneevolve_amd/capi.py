@@ -171,6 +171,9 @@ ABI = {
     "dbg_ld_r2_q40_host": "int: i64* u64* u64* size u64*",
     "snp_trait_sums": "int: ctx* int int size size size size i32* size i64* i64* u32* u32*",
     "dbg_trait_sums_host": "int: u64* size size size size size size size i32* size i64* i64* u32* u32*",
+    "ibd_sharing": "int: ctx* int int size size int size size u64 u64* u32* u64*",
+    "ancestry_bp": "int: ctx* int int size size u64* u32*",
+    "dbg_ibd_host": "int: part* u64* size part* u64* size u64 u64* u32* u64*",
     "rank_f64": "int: ctx* f64* size ull*",
     "download_plink_matrix": "int: ctx* int int size size u64* size",
     "format_ped_text": "int: ctx* int int size size u8* u8* u8* size",
@@ -314,6 +317,12 @@ def _trait_sum_outs(n_traits, n_snps):
     n_snps = max(n_snps, 0)
     return (np.empty((n_traits, n_snps), dtype=np.int64), np.empty((n_traits, n_snps), dtype=np.int64),
             np.empty(n_snps, dtype=np.uint32), np.empty(n_snps, dtype=np.uint32))
+
+
+def _ibd_outs(n_a, n_b, want=(True, True, True)):
+    """the three matrices of the IBD calls (None where not wanted)"""
+    shape = (max(n_a, 0), max(n_b, 0))
+    return tuple(np.empty(shape, dtype=dt) if w else None for dt, w in zip((np.uint64, np.uint32, np.uint64), want))
 
 
 def pack_names(names):
@@ -470,6 +479,17 @@ class GevLibrary:
         self.check(self._f("dbg_trait_sums_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs))
         return outs
 
+    def dbg_ibd_host(self, parts_a, off_a, parts_b=None, off_b=None, min_bp=0, want=(True, True, True)):
+        """(shared_bp, n_seg, max_seg) of every pair of rows of two sets of interval lists by the library's walk compiled for the host (no
+        device needed): uint64 / uint32 / uint64 [n_a][n_b].  parts_* / off_*: as download_intervals returns them (off: rows + 1 entries;
+        side b None: side a again); want: an output that is not wanted goes in as NULL and comes back as None"""
+        parts_a = _arr(parts_a, PART_DTYPE); off_a = _arr(off_a, np.uint64)
+        parts_b = parts_a if parts_b is None else _arr(parts_b, PART_DTYPE); off_b = off_a if off_b is None else _arr(off_b, np.uint64)
+        n_a, n_b = len(off_a) - 1, len(off_b) - 1
+        outs = _ibd_outs(n_a, n_b, want)
+        self.check(self._f("dbg_ibd_host")(parts_a, off_a, n_a, parts_b, off_b, n_b, int(min_bp), *outs))
+        return outs
+
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
         parts / hap_offsets: as download_intervals returns them; ids: Human::ID of every individual; names: one list of founder
@@ -507,6 +527,7 @@ class GevContext:
         lib.check(lib._f("create")(C.byref(h), *([device] if lib.has_device_arg else []), n_pop, nchr, nphen))
         self.h = h
         self._nsnp = {}
+        self._span_bp = {}
         self._ncv = {}
         self._chr_off = set()
         self._ph_seeds = 0
@@ -528,6 +549,7 @@ class GevContext:
     def set_rmap(self, pop, chr, bp, prob, bp_dist):
         bp = _arr(bp, np.uint64); prob = _arr(prob, np.float64)
         self._call("set_rmap", pop, chr, bp, prob, len(bp), int(bp_dist))
+        self._span_bp[(pop, chr)] = int(bp[-1]) - int(bp[0]) if len(bp) else 0     # (the length of a whole-chromosome part: ibd.py)
 
     def set_mutmap(self, pop, chr, bp, rate):
         bp = _arr(bp, np.uint64); rate = _arr(rate, np.float64)
@@ -1074,6 +1096,26 @@ class GevContext:
         outs = _trait_sum_outs(trait.shape[0], n_snps)
         self._call("snp_trait_sums", pop, chr, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs)
         return outs
+
+    def ibd_sharing(self, chr, pop_a, a_begin=0, n_a=None, pop_b=None, b_begin=0, n_b=None, min_bp=0, want=(True, True, True)):
+        """-> (shared_bp, n_seg, max_seg), uint64 / uint32 / uint64 [n_a][n_b]: for haplotype row a_begin + i of pop_a against row b_begin + k
+        of pop_b (None: pop_a), over the segments of at least min_bp base pairs along which both descend from the same founder haplotype:
+        their summed length, their number and the longest.  Walked on the device from the ancestry interval lists (works without genotype
+        planes).  want: an output that is not wanted goes in as NULL and comes back as None"""
+        pop_b = pop_a if pop_b is None else pop_b
+        n_a = 2 * self.pop_size(pop_a) - a_begin if n_a is None else n_a
+        n_b = 2 * self.pop_size(pop_b) - b_begin if n_b is None else n_b
+        outs = _ibd_outs(n_a, n_b, want)
+        self._call("ibd_sharing", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), *outs)
+        return outs
+
+    def ancestry_bp(self, pop, chr, row_begin=0, n_rows=None):
+        """-> (bp uint64 [n_rows][n_pop], n_parts uint32 [n_rows]): the base pairs of every haplotype row covered by parts of each root
+        population, and the length of the row's interval list"""
+        n_rows = 2 * self.pop_size(pop) - row_begin if n_rows is None else n_rows
+        bp = np.empty((max(n_rows, 0), self.n_pop), dtype=np.uint64); n_parts = np.empty(max(n_rows, 0), dtype=np.uint32)
+        self._call("ancestry_bp", pop, chr, row_begin, n_rows, bp, n_parts)
+        return bp, n_parts
 
     def format_hap_text(self, pop, chr, snp_begin=0, n_snps=None):
         """bytes of the reference's .hap file (format_hap::write_hap) for the given SNP lines"""

@@ -27,6 +27,7 @@
 #include "gev_migrant_record.h"
 #include "gev_ldcount.h"
 #include "gev_traitsum.h"
+#include "gev_ibd.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -341,6 +342,7 @@ struct gev_ctx {
     Dev<u64> d_bp_a, d_bp_b; DevBytes d_bp_cnt; Dev<u32> d_bp_out; // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
     Dev<u32> d_pair_w, d_ld_win; DevBytes d_ld_score; // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
     Dev<int32_t> d_ts_trait, d_ts_acc; Dev<uint4> d_ts_b; Dev<long long> d_ts_out; // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
+    DevBytes d_ibd_out; Dev<u32> d_ibd_flag; // gev_ibd_sharing / gev_ancestry_bp (gev_ibd.h): a sub-block's results, the flag of a bad root population; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     Dev<uint8_t> d_mflag; Dev<u32> d_mblk, d_posm, d_posf, d_pickblk, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat; Dev<gev_couple> d_couples; Dev<double> d_svf; // gev_random_mate / gev_glob_seeds scratch
     Dev<double> d_gef_io; DevBytes d_gef_stat; // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
@@ -4351,6 +4353,96 @@ int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_
     if (!n_snps) return GEV_OK;
     if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
     gev_trait_sums_host(bits, row_stride_words, snp_begin, n_snps, ind_begin, n_ind, trait, n_traits, gsum, hetsum, n_het, n_hom_alt);
+    return GEV_OK;
+}
+// ---- identity by descent per pair of haplotype rows, base pairs by root population (gev_ibd.h) ----------------
+// what the two calls begin with, for one population: the opening of gev_format_interval_text
+static int ibd_begin(gev_ctx* c, int pop, int chr, const char* who)
+{
+    GEVC(output_begin(c, pop, chr, who, false));
+    if (!c->track_intervals) return fail(GEV_ESTATE, "%s: interval tracking is disabled (gev_set_track_intervals)", who);
+    return ensure_csr(c, pop);
+}
+// The pair matrix is walked in sub-blocks of at most 4096 rows a side (gev_dbg_output_chunk caps them): a sub-block is one launch of
+// k_ibd_tiles into c->d_ibd_out, copied into the caller's matrices before the next one's kernel runs.
+int gev_ibd_sharing(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b,
+                    uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg)
+{
+    const char* who = "ibd_sharing";
+    GEVC(ibd_begin(c, pop_a, chr, who));
+    if (pop_b != pop_a) GEVC(ibd_begin(c, pop_b, chr, who));
+    PopState &PA = c->pop[pop_a], &PB = c->pop[pop_b];
+    GEVC(check_range(who, "rows (a)", a_begin, n_a, 2 * PA.n_people));
+    GEVC(check_range(who, "rows (b)", b_begin, n_b, 2 * PB.n_people));
+    if (!n_a || !n_b || (!shared_bp && !n_seg && !max_seg)) return GEV_OK;
+    hipStream_t st = c->stream;
+    const u32* poff_a = PA.st[chr].poff[PA.cur]; const gev_part* parts_a = PA.st[chr].parts[PA.cur];
+    const u32* poff_b = PB.st[chr].poff[PB.cur]; const gev_part* parts_b = PB.st[chr].parts[PB.cur];
+    const size_t blk = std::min<size_t>(output_chunk(c, (size_t)1 << 30, 1), 4096), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
+    const size_t per_pair = (shared_bp ? 8 : 0) + (max_seg ? 8 : 0) + (n_seg ? 4 : 0);
+    GEVC(c->d_ibd_out.ensure(ba * bb * per_pair, st));
+    // the 8-byte matrices first: every part of the buffer begins on a multiple of its element
+    u64* d_sh = shared_bp ? c->d_ibd_out.as<u64>() : nullptr;
+    u64* d_mx = max_seg ? c->d_ibd_out.as<u64>() + (shared_bp ? ba * bb : 0) : nullptr;
+    u32* d_ns = n_seg ? (u32*)(c->d_ibd_out.as<u64>() + ((shared_bp ? 1 : 0) + (max_seg ? 1 : 0)) * ba * bb) : nullptr;
+    for (size_t ia = 0; ia < n_a; ia += blk)
+        for (size_t ib = 0; ib < n_b; ib += blk) {
+            const size_t na = std::min(blk, n_a - ia), nb = std::min(blk, n_b - ib);
+            hipLaunchKernelGGL(k_ibd_tiles, dim3((unsigned)ceil_div(nb, GEV_IBD_TILE), (unsigned)ceil_div(na, GEV_IBD_TILE)), dim3(256), 0, st,
+                               poff_a, parts_a, (u64)(a_begin + ia), (u32)na, poff_b, parts_b, (u64)(b_begin + ib), (u32)nb, (u64)min_bp, d_sh, d_ns, d_mx);
+            KCHECK();
+            const struct { void* host; const void* dev; size_t el; } outs[3] = {{shared_bp, d_sh, 8}, {max_seg, d_mx, 8}, {n_seg, d_ns, 4}};
+            for (const auto& o : outs) {
+                if (!o.host) continue;
+                char* dst = (char*)o.host + (ia * n_b + ib) * o.el;
+                if (nb == n_b) HIPC(hipMemcpyAsync(dst, o.dev, na * nb * o.el, hipMemcpyDeviceToHost, st));                       // whole rows of the caller's matrix
+                else HIPC(hipMemcpy2DAsync(dst, n_b * o.el, o.dev, nb * o.el, nb * o.el, na, hipMemcpyDeviceToHost, st));
+            }
+            HIPC(hipStreamSynchronize(st));
+        }
+    return GEV_OK;
+}
+int gev_ancestry_bp(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, uint64_t* bp, uint32_t* n_parts)
+{
+    const char* who = "ancestry_bp";
+    GEVC(ibd_begin(c, pop, chr, who));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "rows", row_begin, n_rows, 2 * P.n_people));
+    if (!n_rows || (!bp && !n_parts)) return GEV_OK;
+    if (n_rows > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: %zu rows in one call", who, n_rows);
+    hipStream_t st = c->stream;
+    const size_t npop = (size_t)c->n_pop;
+    GEVC(c->d_ibd_out.ensure(n_rows * (8 * npop + 4), st));
+    GEVC(c->d_ibd_flag.ensure(1, st));
+    HIPC(hipMemsetAsync(c->d_ibd_flag.p, 0, sizeof(u32), st));
+    u64* d_bp = c->d_ibd_out.as<u64>(); u32* d_np = (u32*)(d_bp + n_rows * npop);
+    hipLaunchKernelGGL(k_ancestry_bp, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, st, (const u32*)P.st[chr].poff[P.cur], (const gev_part*)P.st[chr].parts[P.cur],
+                       (u64)row_begin, (u32)n_rows, c->n_pop, d_bp, d_np, c->d_ibd_flag.p);
+    KCHECK();
+    u32 flag = 0;
+    HIPC(hipMemcpyAsync(&flag, c->d_ibd_flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (flag) return fail(GEV_EINVAL, "%s: a part of population %d names a root population outside [0, %d)", who, pop, c->n_pop);
+    if (bp) HIPC(hipMemcpyAsync(bp, d_bp, n_rows * npop * sizeof(u64), hipMemcpyDeviceToHost, st));
+    if (n_parts) HIPC(hipMemcpyAsync(n_parts, d_np, n_rows * sizeof(u32), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the walk of gev_ibd.h compiled for the host on lists in host memory: no device, no context
+int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                     uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg)
+{
+    const char* who = "dbg_ibd_host";
+    if ((n_a && !off_a) || (n_b && !off_b)) return fail(GEV_EINVAL, "%s: null offsets", who);
+    for (int side = 0; side < 2; side++) {
+        const uint64_t* off = side ? off_b : off_a; const size_t n = side ? n_b : n_a;
+        for (size_t r = 0; r < n; r++) {
+            if (off[r + 1] < off[r]) return fail(GEV_EINVAL, "%s: the offsets of side %c decrease at row %zu", who, "ab"[side], r);
+            if (off[r + 1] - off[r] > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: a row of %llu parts", who, (unsigned long long)(off[r + 1] - off[r]));
+        }
+        if (n && off[n] > off[0] && !(side ? parts_b : parts_a)) return fail(GEV_EINVAL, "%s: null parts", who);
+    }
+    gev_ibd_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, shared_bp, n_seg, max_seg);
     return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------

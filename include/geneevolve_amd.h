@@ -675,6 +675,39 @@ int gev_snp_trait_sums(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_sn
 int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
                             size_t ind_begin, size_t n_ind, const int32_t* trait, size_t n_traits,
                             int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt);
+/* ---- identity by descent per pair of haplotypes, from the ancestry intervals: realised coancestry and inbreeding without a dump ------
+ * The one analysis call on the interval lists (csrc/gev_ibd.h).  For haplotype row r (row = 2 * individual + chromatid) of (pop, chr)
+ * let f_r(x) = (root_population, hap_index) of the part of r's list with st <= x < en (half-open, as part::check_interval, reference
+ * src/Population.h), undefined where no part covers x.  The IBD set of rows r, s is {x : f_r(x) and f_s(x) defined and equal}; its
+ * segments are its maximal intervals (a segment runs on where both rows change founder together and still agree, and across adjacent
+ * parts of one row with the same label).  New mutations play no part: this is identity by founder origin.  Over the segments of length
+ * >= min_bp (0: all of them), for row a_begin + i of pop_a against row b_begin + k of pop_b (the same population or another one; the
+ * ranges may overlap, coincide or be disjoint), row-major [n_a][n_b], each may be NULL:
+ *   shared_bp (uint64)  the summed length of the segments
+ *   n_seg     (uint32)  their number
+ *   max_seg   (uint64)  the longest, 0 without one
+ * Plain 64-bit integers: exact and the same on every run.  One workgroup takes a tile of 16 x 16 pairs, one pair per lane, each lane
+ * walking its two lists with two cursors where they lie.  Nothing bounds a row's length; rows without parts share nothing.  The call begins like gev_format_interval_text, for both
+ * populations (a pending order is materialised, the CSR lists are derived if need be), so it works after gev_migrate, after an import
+ * and on contexts without genotype planes (gev_set_dense_state 0), and returns when the results are in the caller's memory.
+ * GEV_ESTATE, the message naming what is missing: interval tracking off, an inactive chromosome, a population without a current
+ * generation, a generation pending; GEV_EINVAL for a range beyond 2 * n_people.  n_a == 0 or n_b == 0 touches nothing.  The device
+ * buffers are created by the first call; the results leave in sub-blocks of at most 4096 rows a side (gev_dbg_output_chunk caps them). */
+int gev_ibd_sharing(gev_ctx*, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b,
+                    uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg);
+/* per haplotype row of [row_begin, +n_rows) of (pop, chr), one thread per row, each may be NULL:
+ *   bp[r][p]   (uint64 [n_rows][n_pop]) the base pairs of the row covered by parts whose root_population is p: local-ancestry totals,
+ *              admixture proportions after migration
+ *   n_parts[r] (uint32 [n_rows]) the length of the row's list
+ * Begins as gev_ibd_sharing and returns the same errors; a root_population outside [0, n_pop): GEV_EINVAL, nothing is written.
+ * n_rows == 0 touches nothing. */
+int gev_ancestry_bp(gev_ctx*, int pop, int chr, size_t row_begin, size_t n_rows,
+                    uint64_t* bp /* [n_rows][n_pop] */, uint32_t* n_parts /* [n_rows] */);
+/* the same walk (csrc/gev_ibd.h) compiled for the host on lists in host memory as gev_download_intervals returns them (parts of row r of
+ * side a = parts_a[off_a[r] .. off_a[r+1]), off_* has n_* + 1 entries; parts of a row in position order, not overlapping): no device, no
+ * context.  Outputs as gev_ibd_sharing's. */
+int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                     uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */
