@@ -12,7 +12,7 @@ import pytest
 from geneevolve_amd import capi
 from geneevolve_amd.host import GlobSeedStream, Simulation, SyntheticConfig, synthetic_random_mate
 from oracle import oracle_api
-from tests import helpers
+from tests import helpers, output_inputs
 from tests.synth import synth_packed
 
 pytestmark = pytest.mark.gpu
@@ -973,18 +973,9 @@ def test_snp_major_and_bed_packing_match_their_definition(gpu_lib):
     have it at this size, and with gev_dbg_output_chunk(7) in many (SNPs (70, 999): 15 passes of 64 from an unaligned start and
     one of 39; 666 rows: 95 passes of 7 and one of 1; individuals (3, 20): 7 + 7 + 6), byte for byte the same; and every
     row-matrix call also with a row stride three words wider than needed, whose pad words it must zero."""
-    cfg = SyntheticConfig(333, 5000, chrom_bp=2_000_000, map_step=1000, rec_per_row=2e-3, mut_per_row=0.05, n_cv=10, seed=4)
-    g = gpu_lib.create(1, 1, 1)
-    cfg.apply_static(g)
-    g.synth_founders(0, 0, 666, 9); g.synth_cv_founders(0, 0, 0, 666, 10)
-    sim = Simulation(g, 77, 1, True)
-    sim.ras_initial_human_gen0(0, 333)
-    rng = np.random.default_rng(0)
-    for gen in (1, 2, 3):
-        sim.couples[0] = synthetic_random_mate(sim.sex[0], 333, rng)
-        sim.reproduce(0, gen)
-    L, n = 5000, 333
-    al0 = np.frombuffer(b"ACGT", dtype=np.uint8)[np.arange(L) % 4]; al1 = np.frombuffer(b"TGCA", dtype=np.uint8)[(np.arange(L) // 3) % 4]
+    g = output_inputs.build_p1(gpu_lib).ctx                   # 333 x 5000, three generations (tests/output_inputs.py, with the definitions)
+    L, n = output_inputs.P1_L, output_inputs.P1_N
+    al0, al1 = output_inputs.allele_letters(L)
 
     def padded(exact, wide):
         """a call with row_stride_words = needed + 3 into 0xFF bytes: the data words of the exact-width call, three zero pad words"""
@@ -1005,31 +996,31 @@ def test_snp_major_and_bed_packing_match_their_definition(gpu_lib):
             got["snp_major", s0, ns] = sm = g.download_snp_major(0, 0, s0, ns)
             S = capi.unpack_rows(sm, 2 * n)                                  # [ns][666]
             assert np.array_equal(S, H[:, s0:s0 + ns].T), (s0, ns)
+            assert np.array_equal(sm, output_inputs.snp_major_words(H, s0, ns)), (s0, ns)
             padded(sm, g.download_snp_major(0, 0, s0, ns, stride_words=sm.shape[1] + 3))
             got["bed", s0, ns] = bed = g.format_bed(0, 0, s0, ns)
             bed = bed.reshape(ns, (n + 3) // 4)
-            a, b = H[0::2, s0:s0 + ns].T, H[1::2, s0:s0 + ns].T             # [ns][n]
-            code = np.where((a & b) == 1, 0, np.where((a ^ b) == 1, 2, 3)).astype(np.uint8)
-            pad = (-n) % 4
-            code = np.concatenate([code, np.zeros((ns, pad), dtype=np.uint8)], axis=1).reshape(ns, -1, 4)
-            want = code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)
+            want = output_inputs.bed_bytes(H, s0, ns).reshape(ns, (n + 3) // 4)
             assert np.array_equal(bed, want), (s0, ns)
             got["hap_text", s0, ns] = txt = g.format_hap_text(0, 0, s0, ns)
+            assert np.array_equal(txt, output_inputs.hap_text(H, s0, ns)), (s0, ns)
             txt = txt.reshape(ns, 4 * n + 1)
             assert (txt[:, -1] == ord("\n")).all() and (txt[:, 1::2][:, :2 * n] == ord(" ")).all()
             assert np.array_equal(txt[:, 0:4 * n:2] - ord("0"), H[:, s0:s0 + ns].T)
             got["vcf_gt", s0, ns] = gt = g.format_vcf_gt(0, 0, s0, ns)
+            assert np.array_equal(gt, output_inputs.vcf_gt(H, s0, ns)), (s0, ns)
             gt = gt.reshape(ns, 4 * n + 1)                                       # "\ta|b" per individual (format_vcf.cpp:55-59)
             assert (gt[:, -1] == ord("\n")).all() and (gt[:, 0:4 * n:4] == ord("\t")).all() and (gt[:, 2:4 * n:4] == ord("|")).all()
             assert np.array_equal(gt[:, 1:4 * n:4] - ord("0"), H[0::2, s0:s0 + ns].T) and np.array_equal(gt[:, 3:4 * n:4] - ord("0"), H[1::2, s0:s0 + ns].T)
         # PLINK individual-major siblings (ranges that start / end inside the population; L = 5000 is not a multiple of 32 or 64)
-        full = helpers.interleave_haps(words, L)
+        full = output_inputs.plink_words(H, 0, n)
         for (i0, ni) in ((0, n), (1, 7), (330, 3), (3, 20), (5, 0)):
             got["plink", i0, ni] = pm = g.download_plink_matrix(0, 0, i0, ni)
             assert np.array_equal(pm, full[i0:i0 + ni]), (i0, ni)
             padded(pm, g.download_plink_matrix(0, 0, i0, ni, stride_words=pm.shape[1] + 3))
             for letters in (False, True):
                 got["ped", i0, ni, letters] = txt = g.format_ped_text(0, 0, al0 if letters else None, al1 if letters else None, i0, ni)
+                assert np.array_equal(txt, output_inputs.ped_text(H, i0, ni, al0 if letters else None, al1 if letters else None)), (i0, ni, letters)
                 txt = txt.reshape(ni, 4 * L + 1)
                 assert (txt[:, -1] == ord("\n")).all() and (txt[:, 0:4 * L:2] == ord(" ")).all()
                 for hp in (0, 1):
