@@ -30,6 +30,10 @@ class gev_part(C.Structure):
     _fields_ = [("st", C.c_uint64), ("en", C.c_uint64), ("hap_index", C.c_uint64), ("root_population", C.c_int32), ("reserved", C.c_int32)]
 
 
+class gev_ibd_segment(C.Structure):
+    _fields_ = [("st", C.c_uint64), ("en", C.c_uint64), ("row_a", C.c_uint32), ("row_b", C.c_uint32)]
+
+
 class gev_move(C.Structure):
     _fields_ = [("src_pop", C.c_int32), ("dst_pop", C.c_int32), ("src_pos", C.c_uint64)]
 
@@ -81,6 +85,8 @@ def _assort_result(r):
 COUPLE_DTYPE = np.dtype(gev_couple)
 PART_DTYPE = np.dtype(gev_part)
 MOVE_DTYPE = np.dtype(gev_move)
+SEGMENT_DTYPE = np.dtype(gev_ibd_segment)       # 24 bytes: st, en (uint64, [st, en)), row_a, row_b (uint32)
+IBD_ALL_PAIRS, IBD_UPPER = 0, 1
 
 # Every function include/geneevolve_amd.h declares, in its order, as "return: parameters" (tests hold the table equal to the header
 # and check that the library exports every name).  By value: int, size (size_t), u32, u64, f64.  `ctx*` is the context handle.  A
@@ -174,6 +180,8 @@ ABI = {
     "ibd_sharing": "int: ctx* int int size size int size size u64 u64* u32* u64*",
     "ancestry_bp": "int: ctx* int int size size u64* u32*",
     "dbg_ibd_host": "int: part* u64* size part* u64* size u64 u64* u32* u64*",
+    "ibd_segments": "int: ctx* int int size size int size size u64 int ibd_segment* size u64*",
+    "dbg_ibd_segments_host": "int: part* u64* size part* u64* size u64 int ibd_segment* size u64*",
     "rank_f64": "int: ctx* f64* size ull*",
     "download_plink_matrix": "int: ctx* int int size size u64* size",
     "format_ped_text": "int: ctx* int int size size u8* u8* u8* size",
@@ -323,6 +331,18 @@ def _ibd_outs(n_a, n_b, want=(True, True, True)):
     """the three matrices of the IBD calls (None where not wanted)"""
     shape = (max(n_a, 0), max(n_b, 0))
     return tuple(np.empty(shape, dtype=dt) if w else None for dt, w in zip((np.uint64, np.uint32, np.uint64), want))
+
+
+def _ibd_segment_list(call, upper):
+    """the two calls of the segment lists: call(pairs, out, capacity, n_total) counts with (None, 0), then fills an exactly sized array"""
+    pairs = IBD_UPPER if upper else IBD_ALL_PAIRS
+    n = C.c_uint64()
+    call(pairs, None, 0, C.byref(n))
+    out = np.zeros(n.value, dtype=SEGMENT_DTYPE)
+    if n.value:
+        call(pairs, out, n.value, C.byref(n))
+        assert n.value == len(out), "the list changed between the count and the fill"
+    return out
 
 
 def pack_names(names):
@@ -489,6 +509,15 @@ class GevLibrary:
         outs = _ibd_outs(n_a, n_b, want)
         self.check(self._f("dbg_ibd_host")(parts_a, off_a, n_a, parts_b, off_b, n_b, int(min_bp), *outs))
         return outs
+
+    def dbg_ibd_segments_host(self, parts_a, off_a, parts_b=None, off_b=None, min_bp=0, upper=False):
+        """SEGMENT_DTYPE records of every pair of rows of two sets of interval lists by the library's walk compiled for the host (no device
+        needed), sorted by (row_a, row_b, st); row_a / row_b index off_a / off_b.  Side b None: side a again, which upper (only pairs
+        with row_a < row_b) needs"""
+        parts_a = _arr(parts_a, PART_DTYPE); off_a = _arr(off_a, np.uint64)
+        parts_b = parts_a if parts_b is None else _arr(parts_b, PART_DTYPE); off_b = off_a if off_b is None else _arr(off_b, np.uint64)
+        f = self._f("dbg_ibd_segments_host")
+        return _ibd_segment_list(lambda pairs, out, cap, n: self.check(f(parts_a, off_a, len(off_a) - 1, parts_b, off_b, len(off_b) - 1, int(min_bp), pairs, out, cap, n)), upper)
 
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
@@ -1108,6 +1137,15 @@ class GevContext:
         outs = _ibd_outs(n_a, n_b, want)
         self._call("ibd_sharing", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), *outs)
         return outs
+
+    def ibd_segments(self, chr, pop_a, a_begin=0, n_a=None, pop_b=None, b_begin=0, n_b=None, min_bp=0, upper=False):
+        """-> SEGMENT_DTYPE records (st, en, row_a, row_b), sorted by (row_a, row_b, st): the segments of at least min_bp base pairs along
+        which row a_begin + i of pop_a and row b_begin + k of pop_b (None: pop_a) descend from the same founder haplotype, [st, en), the
+        rows absolute in their populations.  upper: only pairs with row_a < row_b (one population).  A count call, then a fill call"""
+        pop_b = pop_a if pop_b is None else pop_b
+        n_a = 2 * self.pop_size(pop_a) - a_begin if n_a is None else n_a
+        n_b = 2 * self.pop_size(pop_b) - b_begin if n_b is None else n_b
+        return _ibd_segment_list(lambda pairs, out, cap, n: self._call("ibd_segments", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), pairs, out, cap, n), upper)
 
     def ancestry_bp(self, pop, chr, row_begin=0, n_rows=None):
         """-> (bp uint64 [n_rows][n_pop], n_parts uint32 [n_rows]): the base pairs of every haplotype row covered by parts of each root

@@ -1,6 +1,7 @@
-// gev_ibd.h -- identity by descent per pair of haplotype rows from the ancestry interval lists (gev_ibd_sharing), and the base pairs
-// of a row by root population (gev_ancestry_bp).  The reference has no such output; the truth it is held to is a per-position raster
-// of the lists gev_download_intervals returns (tests/ibd_inputs.py, tools/ibd_check.cpp).
+// gev_ibd.h -- identity by descent per pair of haplotype rows from the ancestry interval lists: three summaries per pair
+// (gev_ibd_sharing) and the segments themselves as one ordered list (gev_ibd_segments); and the base pairs of a row by root
+// population (gev_ancestry_bp).  The reference has no such output; the truth it is held to is a per-position raster of the lists
+// gev_download_intervals returns (tests/ibd_inputs.py, tests/ibd_segments_inputs.py, tools/ibd_check.cpp, tools/ibd_segments_check.cpp).
 //
 // A row's list is what the library keeps for it: gev_part records in position order, half-open [st, en), no two overlapping (gaps,
 // rows without parts and parts with st >= en, which cover nothing, are allowed).  f_r(x) = (root_population, hap_index) of the part
@@ -75,6 +76,68 @@ inline void gev_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t 
             if (max_seg) max_seg[a * n_b + b] = r.longest;
         }
 }
+// ---- the segments themselves (gev_ibd_segments) ----
+// The same walk with an emit point in place of the three sums: emit(st, en) is called for every closed run of length >= min_bp, in
+// position order.  It stands beside gev_ibd_walk, which k_ibd_tiles keeps as it was measured; a count, a fill
+// and the host form are this one function under three functors.
+template <class F>
+GEV_IBD_HD inline void gev_ibd_walk_emit(const gev_part* pa, uint32_t na, const gev_part* pb, uint32_t nb, uint64_t min_bp, F& emit)
+{
+    if (!na || !nb) return;
+    uint32_t i = 0, j = 0;
+    gev_part A = pa[0], B = pb[0];
+    uint64_t run_st = 0, run_en = 0;
+    bool open = false;
+    for (;;) {
+        const uint64_t lo = A.st > B.st ? A.st : B.st, hi = A.en < B.en ? A.en : B.en;
+        if (lo < hi && A.hap_index == B.hap_index && A.root_population == B.root_population) {
+            if (open && lo == run_en) run_en = hi;
+            else {
+                if (open && run_en - run_st >= min_bp) emit(run_st, run_en);
+                run_st = lo; run_en = hi; open = true;
+            }
+        }
+        const bool adv_a = A.en <= B.en, adv_b = B.en <= A.en;
+        if (adv_a) { if (++i == na) break; A = pa[i]; }
+        if (adv_b) { if (++j == nb) break; B = pb[j]; }
+    }
+    if (open && run_en - run_st >= min_bp) emit(run_st, run_en);
+}
+struct GevIbdCount { uint32_t n; GEV_IBD_HD void operator()(uint64_t, uint64_t) { n++; } };
+// writes the records of one pair one behind the other: a plain assignment of the 8-byte-aligned record (vector stores on the device)
+struct GevIbdFill {
+    gev_ibd_segment* out; uint32_t row_a, row_b;
+    GEV_IBD_HD void operator()(uint64_t st, uint64_t en) { gev_ibd_segment s; s.st = st; s.en = en; s.row_a = row_a; s.row_b = row_b; *out++ = s; }
+};
+// the host form: the records of all pairs in (row_a, row_b, st) order, rows numbered by their index in off_*; upper: only pairs with
+// a < b.  out null: nothing is written.  Returns the number of records; a caller fills a buffer it has sized by a first, counting call
+inline uint64_t gev_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                                      uint64_t min_bp, bool upper, gev_ibd_segment* out)
+{
+    uint64_t total = 0;
+    for (size_t a = 0; a < n_a; a++)
+        for (size_t b = upper ? a + 1 : 0; b < n_b; b++) {
+            const uint32_t la = (uint32_t)(off_a[a + 1] - off_a[a]), lb = (uint32_t)(off_b[b + 1] - off_b[b]);
+            const gev_part* pa = la ? parts_a + off_a[a] : nullptr; const gev_part* pb = lb ? parts_b + off_b[b] : nullptr;
+            if (out) {
+                GevIbdFill f = {out + total, (uint32_t)a, (uint32_t)b};
+                gev_ibd_walk_emit(pa, la, pb, lb, min_bp, f);
+                total += (uint64_t)(f.out - (out + total));
+            } else {
+                GevIbdCount k = {0};
+                gev_ibd_walk_emit(pa, la, pb, lb, min_bp, k);
+                total += k.n;
+            }
+        }
+    return total;
+}
+// the capacity rule of gev_ibd_segments on the host: *n_total always; out filled if and only if *n_total <= capacity
+inline void gev_ibd_segments_fit_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                                      uint64_t min_bp, bool upper, gev_ibd_segment* out, size_t capacity, uint64_t* n_total)
+{
+    *n_total = gev_ibd_segments_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, upper, nullptr);
+    if (*n_total && *n_total <= capacity) gev_ibd_segments_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, upper, out);
+}
 // base pairs of one row by root population into bp[n_pop] (zeroed here); false, with bp left as it is, when a part's root population lies
 // outside [0, n_pop).  A part with st >= en covers nothing
 GEV_IBD_HD inline bool gev_ancestry_row(const gev_part* p, uint32_t n, int n_pop, uint64_t* bp)
@@ -109,6 +172,59 @@ __global__ void __launch_bounds__(256) k_ibd_tiles(const u32* __restrict__ poff_
     if (shared_bp) shared_bp[o] = r.shared;
     if (n_seg) n_seg[o] = r.n;
     if (max_seg) max_seg[o] = r.longest;
+}
+// ------------------------------------------------------------------------------------------
+// k_ibd_segments: the count and the fill of gev_ibd_segments over one strip of n_a whole A rows against n_b B rows (row_a, row_b: the
+// absolute rows of the strip's first pair, which are also what the records name).  The geometry is k_ibd_tiles': 256 pairs a workgroup,
+// one per lane, 64 a wave in a block of rows so that a wave's loads touch few lists; no on-chip memory.  A tile is 2^ta_log2 A rows x
+// 2^(8 - ta_log2) B rows, a wave's block min(2^ta_log2, 8) A rows x the B rows that make 64: ta_log2 = 4 is the 16 x 16 tile with 8 x 8
+// wave blocks, and a strip of fewer than 16 rows takes the smallest power of two that holds it (8 x 32, 4 x 64, 2 x 128, 1 x 256), so
+// that at least half of a tile's A rows exist.  Tiles are numbered B-fastest in blockIdx.x (tiles_b a tile row).
+//   FILL = false: cnt[ia][ib] = the pair's records (u32 [n_a][n_b]).  upper: lanes with row_a >= row_b store nothing and tiles wholly
+//                 on or below the diagonal return at once, so the host zeroes cnt first.
+//   FILL = true:  cnt is the exclusive scan of those counts (n_a n_b + 1 entries); a pair with records walks again and writes them from
+//                 out[cnt[pair]] on, a pair without returns.  The walk is the count's, so it writes exactly its count.
+// ------------------------------------------------------------------------------------------
+template <bool FILL>
+__global__ void __launch_bounds__(256) k_ibd_segments(const u32* __restrict__ poff_a, const gev_part* __restrict__ parts_a, u64 row_a, u32 n_a,
+                                                      const u32* __restrict__ poff_b, const gev_part* __restrict__ parts_b, u64 row_b, u32 n_b,
+                                                      u64 min_bp, u32 upper, u32 ta_log2, u32 tiles_b, u32* __restrict__ cnt, gev_ibd_segment* __restrict__ out)
+{
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const u32 tb_log2 = 8u - ta_log2, wa_log2 = ta_log2 < 3u ? ta_log2 : 3u, wb_log2 = 6u - wa_log2, waves_a_log2 = ta_log2 - wa_log2;    // (waves_a_log2: 1 for the 16-row tile, else 0)
+    const u32 tile_a = blockIdx.x / tiles_b, tile_b = blockIdx.x - tile_a * tiles_b;
+    const u64 a0 = (u64)tile_a << ta_log2, b0 = (u64)tile_b << tb_log2;
+    if (upper && row_b + b0 + (1u << tb_log2) - 1u <= row_a + a0) return;                     // the tile's last B row is no later than its first A row
+    const u64 ia = a0 + ((wave >> (2u - waves_a_log2)) << wa_log2) + (lane >> wb_log2);
+    const u64 ib = b0 + ((wave & ((4u >> waves_a_log2) - 1u)) << wb_log2) + (lane & ((1u << wb_log2) - 1u));
+    if (ia >= n_a || ib >= n_b) return;
+    const u64 ra = row_a + ia, rb = row_b + ib;
+    if (upper && ra >= rb) return;
+    const size_t o = (size_t)ia * n_b + ib;
+    const u32* oa = poff_a + ra; const u32* ob = poff_b + rb;
+    const u32 pa0 = oa[0], na = oa[1] - pa0, pb0 = ob[0], nb = ob[1] - pb0;
+    if (FILL) {
+        const u32 at = cnt[o];
+        if (cnt[o + 1] == at) return;
+        GevIbdFill f = {out + at, (u32)ra, (u32)rb};
+        gev_ibd_walk_emit(parts_a + pa0, na, parts_b + pb0, nb, min_bp, f);
+    } else {
+        GevIbdCount k = {0};
+        gev_ibd_walk_emit(parts_a + pa0, na, parts_b + pb0, nb, min_bp, k);
+        cnt[o] = k.n;
+    }
+}
+// *total += the sum of cnt[0 .. n) in 64 bits (the host zeroes it): a strip's record count, which a 32-bit scan's last entry would wrap
+__global__ void __launch_bounds__(256) k_ibd_total(const u32* __restrict__ cnt, size_t n, unsigned long long* __restrict__ total)
+{
+    __shared__ unsigned long long lds[4];
+    unsigned long long s = 0;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) s += cnt[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
+    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(total, lds[0] + lds[1] + lds[2] + lds[3]);
 }
 // one thread per row of [row0, +n_rows): bp[r][n_pop] and n_parts[r]; a root population outside [0, n_pop) raises *flag (the host then
 // hands nothing out)

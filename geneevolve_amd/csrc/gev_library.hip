@@ -343,6 +343,7 @@ struct gev_ctx {
     Dev<u32> d_pair_w, d_ld_win; DevBytes d_ld_score; // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
     Dev<int32_t> d_ts_trait, d_ts_acc; Dev<uint4> d_ts_b; Dev<long long> d_ts_out; // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
     DevBytes d_ibd_out; Dev<u32> d_ibd_flag; // gev_ibd_sharing / gev_ancestry_bp (gev_ibd.h): a sub-block's results, the flag of a bad root population; created by the first call
+    Dev<u32> d_ibd_cnt, d_ibd_off; Dev<gev_ibd_segment> d_ibd_seg; Dev<unsigned long long> d_ibd_tot; // gev_ibd_segments: a strip's counts per pair, their exclusive scan, its records, its 64-bit record count; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     Dev<uint8_t> d_mflag; Dev<u32> d_mblk, d_posm, d_posf, d_pickblk, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat; Dev<gev_couple> d_couples; Dev<double> d_svf; // gev_random_mate / gev_glob_seeds scratch
     Dev<double> d_gef_io; DevBytes d_gef_stat; // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
@@ -4428,11 +4429,9 @@ int gev_ancestry_bp(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_row
     HIPC(hipStreamSynchronize(st));
     return GEV_OK;
 }
-// the walk of gev_ibd.h compiled for the host on lists in host memory: no device, no context
-int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
-                     uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg)
+// what the host forms refuse of two sets of lists in host memory
+static int ibd_host_lists(const char* who, const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b)
 {
-    const char* who = "dbg_ibd_host";
     if ((n_a && !off_a) || (n_b && !off_b)) return fail(GEV_EINVAL, "%s: null offsets", who);
     for (int side = 0; side < 2; side++) {
         const uint64_t* off = side ? off_b : off_a; const size_t n = side ? n_b : n_a;
@@ -4442,7 +4441,121 @@ int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a,
         }
         if (n && off[n] > off[0] && !(side ? parts_b : parts_a)) return fail(GEV_EINVAL, "%s: null parts", who);
     }
+    return GEV_OK;
+}
+// the walk of gev_ibd.h compiled for the host on lists in host memory: no device, no context
+int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                     uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg)
+{
+    GEVC(ibd_host_lists("dbg_ibd_host", parts_a, off_a, n_a, parts_b, off_b, n_b));
     gev_ibd_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, shared_bp, n_seg, max_seg);
+    return GEV_OK;
+}
+// ---- the IBD segments themselves (gev_ibd.h: k_ibd_segments) ----
+// what the device and the host form refuse of the list's own arguments
+static int ibd_seg_args(const char* who, int pairs, const gev_ibd_segment* out, size_t capacity, const uint64_t* n_total)
+{
+    if (!n_total) return fail(GEV_EINVAL, "%s: n_total is null", who);
+    if (pairs != GEV_IBD_ALL_PAIRS && pairs != GEV_IBD_UPPER) return fail(GEV_EINVAL, "%s: pairs is %d (GEV_IBD_ALL_PAIRS or GEV_IBD_UPPER)", who, pairs);
+    if (!out && capacity) return fail(GEV_EINVAL, "%s: a null output of capacity %zu", who, capacity);
+    return GEV_OK;
+}
+// one request's constants, and a strip of whole A rows [row0, +rows) of it against all its B rows
+struct IbdSegCall { const u32 *poff_a, *poff_b; const gev_part *parts_a, *parts_b; size_t a_begin, b_begin, n_b; u64 min_bp; u32 upper; };
+struct IbdStrip { size_t row0, rows; u64 total; };
+static int ibd_seg_launch(gev_ctx* c, const IbdSegCall& q, size_t row0, size_t rows, bool fill)
+{
+    u32 ta_log2 = 0;
+    while (ta_log2 < 4 && ((size_t)1 << ta_log2) < rows) ta_log2++;                          // the smallest tile height that holds the strip, 16 at the most
+    const size_t tiles_b = ceil_div(q.n_b, (size_t)256 >> ta_log2), tiles = ceil_div(rows, (size_t)1 << ta_log2) * tiles_b;
+    const auto kernel = fill ? k_ibd_segments<true> : k_ibd_segments<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, q.poff_a, q.parts_a, (u64)(q.a_begin + row0), (u32)rows,
+                       q.poff_b, q.parts_b, (u64)q.b_begin, (u32)q.n_b, q.min_bp, q.upper, ta_log2, (u32)tiles_b,
+                       fill ? c->d_ibd_off.p : c->d_ibd_cnt.p, c->d_ibd_seg.p);
+    KCHECK();
+    return GEV_OK;
+}
+// the strip's counts per pair into c->d_ibd_cnt; total: their sum in 64 bits, in host memory when this returns (null: not wanted)
+static int ibd_seg_count(gev_ctx* c, const IbdSegCall& q, size_t row0, size_t rows, u64* total)
+{
+    hipStream_t st = c->stream;
+    const size_t np = rows * q.n_b;
+    GEVC(c->d_ibd_cnt.ensure(np, st));
+    if (q.upper) HIPC(hipMemsetAsync(c->d_ibd_cnt.p, 0, np * sizeof(u32), st));              // (pairs on or below the diagonal are not visited)
+    GEVC(ibd_seg_launch(c, q, row0, rows, false));
+    if (!total) return GEV_OK;
+    GEVC(c->d_ibd_tot.ensure(1, st));
+    HIPC(hipMemsetAsync(c->d_ibd_tot.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_ibd_total, dim3((unsigned)std::min<size_t>(ceil_div(np, 1024), 1024)), dim3(256), 0, st, (const u32*)c->d_ibd_cnt.p, np, c->d_ibd_tot.p);
+    KCHECK();
+    unsigned long long t = 0;
+    HIPC(hipMemcpyAsync(&t, c->d_ibd_tot.p, sizeof t, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    *total = t;
+    return GEV_OK;
+}
+// Two phases.  Every strip is counted and its 64-bit total kept on the host: n_total.  If out holds them, each strip is counted again
+// (a request of one strip still has its counts), scanned and filled into c->d_ibd_seg, which is copied to out at the running offset
+// before the next strip's fill overwrites it.  Strips are whole A rows against all B rows, so row-major order inside a strip is the
+// order of the list and strips concatenate.
+int gev_ibd_segments(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b,
+                     uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total)
+{
+    const char* who = "ibd_segments";
+    GEVC(ibd_seg_args(who, pairs, out, capacity, n_total));
+    GEVC(ibd_begin(c, pop_a, chr, who));
+    if (pop_b != pop_a) GEVC(ibd_begin(c, pop_b, chr, who));
+    PopState &PA = c->pop[pop_a], &PB = c->pop[pop_b];
+    GEVC(check_range(who, "rows (a)", a_begin, n_a, 2 * PA.n_people));
+    GEVC(check_range(who, "rows (b)", b_begin, n_b, 2 * PB.n_people));
+    if (pairs == GEV_IBD_UPPER && pop_a != pop_b) return fail(GEV_EINVAL, "%s: GEV_IBD_UPPER takes one population (%d and %d given)", who, pop_a, pop_b);
+    if (a_begin + n_a > ((size_t)1 << 32) || b_begin + n_b > ((size_t)1 << 32)) return fail(GEV_EUNSUPPORTED, "%s: rows beyond 2^32 - 1 do not fit a record", who);
+    if (!n_a || !n_b) { *n_total = 0; return GEV_OK; }
+    hipStream_t st = c->stream;
+    const IbdSegCall q = {PA.st[chr].poff[PA.cur], PB.st[chr].poff[PB.cur], PA.st[chr].parts[PA.cur], PB.st[chr].parts[PB.cur], a_begin, b_begin, n_b, min_bp, pairs == GEV_IBD_UPPER ? 1u : 0u};
+    const size_t strip_rows = std::min(output_chunk(c, (size_t)1 << 24, n_b), n_a);           // at most 2^24 pairs, at least one row
+    const u64 budget = ((u64)1 << 30) / sizeof(gev_ibd_segment);                               // records of a strip on the device
+    std::vector<IbdStrip> strips;
+    u64 total = 0, largest = 0;
+    for (size_t row0 = 0; row0 < n_a;) {
+        size_t rows = std::min(strip_rows, n_a - row0);
+        u64 t = 0;
+        for (;;) {
+            GEVC(ibd_seg_count(c, q, row0, rows, &t));
+            if (t <= budget || rows == 1) break;
+            rows /= 2;
+        }
+        if (t >> 32) return fail(GEV_EUNSUPPORTED, "%s: row %zu alone shares %llu segments with the %zu rows of side b", who, a_begin + row0, (unsigned long long)t, n_b);
+        strips.push_back({row0, rows, t});
+        total += t; largest = std::max(largest, t);
+        row0 += rows;
+    }
+    *n_total = total;
+    if (!total || total > capacity) return GEV_OK;
+    GEVC(c->d_ibd_seg.ensure((size_t)largest, st));
+    size_t done = 0;
+    for (const IbdStrip& s : strips) {
+        if (!s.total) continue;
+        const size_t np = s.rows * n_b;
+        if (strips.size() > 1) GEVC(ibd_seg_count(c, q, s.row0, s.rows, nullptr));
+        GEVC(c->d_ibd_off.ensure(np + 1, st));
+        GEVC(scan_u32_on(st, c->d_sums, c->d_ibd_cnt.p, np, c->d_ibd_off.p));                 // (s.total < 2^32: no offset wraps)
+        GEVC(ibd_seg_launch(c, q, s.row0, s.rows, true));
+        HIPC(hipMemcpyAsync(out + done, c->d_ibd_seg.p, (size_t)s.total * sizeof(gev_ibd_segment), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        done += (size_t)s.total;
+    }
+    return GEV_OK;
+}
+int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                              uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total)
+{
+    const char* who = "dbg_ibd_segments_host";
+    GEVC(ibd_seg_args(who, pairs, out, capacity, n_total));
+    GEVC(ibd_host_lists(who, parts_a, off_a, n_a, parts_b, off_b, n_b));
+    if (pairs == GEV_IBD_UPPER && (parts_a != parts_b || off_a != off_b)) return fail(GEV_EINVAL, "%s: GEV_IBD_UPPER takes the same lists on both sides", who);
+    if (n_a > 0xffffffffull || n_b > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: rows beyond 2^32 - 1 do not fit a record", who);
+    gev_ibd_segments_fit_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, pairs == GEV_IBD_UPPER, out, capacity, n_total);
     return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------

@@ -1,7 +1,8 @@
 """Identity by descent from the device's walk over the ancestry interval lists (GevContext.ibd_sharing / ancestry_bp): the shared
 length, segment count and longest segment of every pair of haplotypes, realised coancestry and inbreeding of individuals, and admixture
 proportions by root population, summed over chromosomes.  Nothing is downloaded but the integer matrices; every statistic is one
-float64 division of exact integers.  Works on contexts without genotype planes: the lists are all it reads."""
+float64 division of exact integers.  segments() lists the IBD segments themselves (GevContext.ibd_segments): where the tracts two
+haplotypes share lie on each chromosome.  Works on contexts without genotype planes: the lists are all it reads."""
 from collections import namedtuple
 
 import numpy as np
@@ -37,6 +38,44 @@ def sharing(ctx, pop, chr, a=None, b=None, pop_b=None, min_bp=0):
     pop_b = pop if pop_b is None else pop_b
     a0, na = _rows(ctx, pop, a); b0, nb = _rows(ctx, pop_b, b)
     return IBDSharing(ctx._span_bp[(pop, chr)], *ctx.ibd_sharing(chr, pop, a0, na, pop_b, b0, nb, min_bp))
+
+
+def segments_over_chromosomes(chrs, per_chr):
+    """one array with a leading `chr` field (int32) from the segment arrays of several chromosomes (GevContext.ibd_segments, each sorted
+    by (row_a, row_b, st)), the chromosomes in ascending order: sorted by (chr, row_a, row_b, st)"""
+    from .capi import SEGMENT_DTYPE
+    dt = np.dtype([("chr", np.int32)] + [(name, SEGMENT_DTYPE.fields[name][0]) for name in SEGMENT_DTYPE.names])
+    order = sorted(range(len(chrs)), key=lambda k: int(chrs[k]))
+    out = np.zeros(sum(len(s) for s in per_chr), dtype=dt)
+    at = 0
+    for k in order:
+        part = out[at:at + len(per_chr[k])]
+        part["chr"] = int(chrs[k])
+        for name in SEGMENT_DTYPE.names:
+            part[name] = per_chr[k][name]
+        at += len(part)
+    return out
+
+
+def segments(ctx, pop, chrs=None, rows=None, pop_b=None, rows_b=None, min_bp=0, upper=None):
+    """the IBD segments of haplotype rows `rows` of `pop` against rows `rows_b` of pop_b (None: `pop`, and then rows_b None: `rows`
+    again) over the chromosomes `chrs` (None: the active ones): a structured array (chr, st, en, row_a, row_b) sorted by
+    (chr, row_a, row_b, st), [st, en) half-open, rows absolute in their populations.  upper: only pairs with row_a < row_b; None: True
+    when both sides are the same rows of the same population"""
+    same_pop = pop_b is None or pop_b == pop
+    pop_b = pop if pop_b is None else pop_b
+    a0, na = _rows(ctx, pop, rows)
+    b0, nb = (a0, na) if same_pop and rows_b is None else _rows(ctx, pop_b, rows_b)
+    if upper is None:
+        upper = same_pop and (a0, na) == (b0, nb)
+    chrs = _chrs(ctx, chrs)
+    return segments_over_chromosomes(chrs, [ctx.ibd_segments(k, pop, a0, na, pop_b, b0, nb, min_bp, upper) for k in chrs])
+
+
+def segment_individuals(seg):
+    """(ind_a, chromatid_a, ind_b, chromatid_b) of segment records: row = 2 * individual + chromatid"""
+    a, b = np.asarray(seg["row_a"]), np.asarray(seg["row_b"])
+    return a >> 1, a & 1, b >> 1, b & 1
 
 
 def coancestry_from_sums(shared_sum, span_sum):

@@ -708,6 +708,34 @@ int gev_ancestry_bp(gev_ctx*, int pop, int chr, size_t row_begin, size_t n_rows,
  * context.  Outputs as gev_ibd_sharing's. */
 int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
                      uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg);
+/* ---- the IBD segments themselves: where the tracts two haplotypes share lie on the chromosome -------------------------------------
+ * One record per segment of length >= min_bp of the definition above (a maximal interval of the IBD set of two rows: it runs on across
+ * a common change of founder and across adjacent same-label parts of one row; new mutations play no part), [st, en) half-open, for
+ * row a_begin + i of pop_a against row b_begin + k of pop_b.  row_a / row_b are the absolute rows in their populations
+ * (2 * individual + chromatid).  pairs: GEV_IBD_ALL_PAIRS, or GEV_IBD_UPPER for the pairs with row_a < row_b alone, which takes one
+ * population (pop_a == pop_b; GEV_EINVAL otherwise; the ranges may differ).  The records come sorted by (row_a, row_b, st), whatever
+ * the strips, tiles and gev_dbg_output_chunk were: the list is the same bytes on every run.
+ *   *n_total is always set to the number of records of the request (n_total == NULL: GEV_EINVAL).  out is filled if and only if
+ *   *n_total <= capacity; otherwise the call still returns GEV_OK, the caller sees *n_total > capacity and nothing of out is written
+ *   (never a byte at or beyond out[capacity]).  out == NULL with capacity == 0 is the count-only form; a call with the counted capacity
+ *   then fills.  n_a == 0 or n_b == 0 sets *n_total = 0 and touches nothing else.
+ * The pair matrix is walked in strips of whole A rows against all n_b B rows (at most 2^24 pairs, at least one row;
+ * gev_dbg_output_chunk caps a strip's A rows; a strip of more than 1 GiB of records is halved in rows until it fits or is one row): a
+ * count kernel, and when out fits an exclusive scan and a fill kernel that walks again, each lane writing its pair's records from the
+ * pair's offset into a device buffer that is copied to out at the strip's running offset.  So an out that fits costs two walks, three
+ * when the request is more than one strip.  Begins as gev_ibd_sharing, for both populations, and returns its errors; a row index that
+ * does not fit 32 bits, or a single row with 2^32 records or more: GEV_EUNSUPPORTED.  A refused call leaves out and *n_total as they
+ * were.  The device buffers are created by the first call. */
+typedef struct gev_ibd_segment { uint64_t st, en; uint32_t row_a, row_b; } gev_ibd_segment;   /* 24 bytes, [st, en) */
+#define GEV_IBD_ALL_PAIRS 0
+#define GEV_IBD_UPPER     1
+int gev_ibd_segments(gev_ctx*, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b,
+                     uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total);
+/* the same walk compiled for the host on lists in host memory, as gev_dbg_ibd_host takes them and with its refusals: no device, no
+ * context.  row_a / row_b are indices into off_a / off_b; GEV_IBD_UPPER takes the same lists on both sides (parts_a == parts_b and
+ * off_a == off_b; n_a and n_b may differ).  out, capacity and n_total as above. */
+int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
+                              uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */
