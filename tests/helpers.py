@@ -199,6 +199,143 @@ def decode_record(rec, n, Ls, cv_pos, n_pop, rows_travel, active=None):
     return d
 
 
+def write_device(ptr, data):
+    """copy bytes (any contiguous array) from the host to a device pointer"""
+    b = np.ascontiguousarray(data).view(np.uint8).ravel()
+    if len(b):
+        rc = _hip().hipMemcpy(ptr, b.ctypes.data, len(b), 1)   # hipMemcpyHostToDevice
+        assert rc == 0, f"hipMemcpy failed ({rc})"
+
+
+# ---- the same record ENCODED from hand-built individuals, again from the format comment of csrc/gev_migrant_record.h alone.
+# An individual is {"sex": 1 | 2, "chr": [per chromosome: [per chromatid: (parts, muts)]]}; parts: [(st, en, hap_index,
+# root_population)], muts: ascending positions.  The piece form of the library's lists stores no `en` (it is the next part's st, the
+# last map position behind the last part), so only lists that tile the map can be held: everything else is refused here.
+def check_individuals(individuals, span, n_founders, active=None):
+    """the lists the library itself could hold: parts ascending and tiling [span[k][0], span[k][1]) exactly (zero-length parts allowed),
+    root_population in range, hap_index below that population's founder count n_founders[k][rp], mutations strictly ascending"""
+    for i, ind in enumerate(individuals):
+        assert ind["sex"] in (1, 2), f"individual {i}: sex"
+        assert len(ind["chr"]) == len(span), f"individual {i}: one pair of lists per chromosome"
+        for k, pair in enumerate(ind["chr"]):
+            if active is not None and not active[k]:
+                continue
+            assert len(pair) == 2
+            for h, (parts, muts) in enumerate(pair):
+                at = f"individual {i} chromosome {k} chromatid {h}"
+                assert len(parts) >= 1, f"{at}: no part"
+                assert parts[0][0] == span[k][0] and parts[-1][1] == span[k][1], f"{at}: the parts do not begin / end with the map"
+                for q, (st, en, hap, rp) in enumerate(parts):
+                    assert st <= en, f"{at}: part {q} ends in front of its start"
+                    assert q + 1 == len(parts) or en == parts[q + 1][0], f"{at}: part {q + 1} does not start where part {q} ends"
+                    assert 0 <= rp < len(n_founders[k]), f"{at}: root population of part {q}"
+                    assert 0 <= hap < n_founders[k][rp], f"{at}: hap_index of part {q} beyond the founders of population {rp}"
+                m = [int(x) for x in muts]
+                assert all(a < b for a, b in zip(m, m[1:])), f"{at}: mutations not strictly ascending"
+
+
+def _covering(parts, pos):
+    """per position: index of the part with st <= pos < en (-1: none).  Zero-length parts cover nothing."""
+    st = np.array([p[0] for p in parts], dtype=np.uint64); en = np.array([p[1] for p in parts], dtype=np.uint64)
+    pos = np.asarray(pos, dtype=np.uint64)
+    q = np.searchsorted(st, pos, side="right").astype(np.int64) - 1          # the last part that starts at or in front of pos: with
+    ok = (q >= 0) & (en[np.maximum(q, 0)] > pos)                             # ascending tiling parts it is the only candidate
+    return np.where(ok, q, -1)
+
+
+def encode_record(individuals, Ls, cv_pos, n_pop, rows_travel, active=None, founders=None, cv_founders=None, snp_pos=None, span=None,
+                  parts_travel=True, want_mask=False):
+    """the inverse of decode_record.  Ls[k]: loci; cv_pos[p][k]: CV positions in file order; founders[k][rp]: founder bits
+    [n_founder_haps][L] of root population rp; cv_founders[p][k][rp]: CV founder bits [n_founder_haps][C] in file order; snp_pos[k]:
+    SNP positions; span[k]: (first, last) map position.  parts_travel False: a context without interval tracking (part counts zero, no
+    [parts]; the rows are still derived from the parts given).  -> record bytes (uint8); with want_mask also a bool array, False on
+    the padding between sections (asserted: at most 15 bytes behind each)"""
+    nchr, n = len(Ls), len(individuals)
+    active = [True] * nchr if active is None else list(active)
+    check_individuals(individuals, span, [[len(f) for f in founders[k]] for k in range(nchr)], active)
+    out, payload = [], []
+
+    def put(section):                                            # one section; the next one begins at a multiple of 16
+        b = np.ascontiguousarray(section).view(np.uint8).ravel()
+        pad = (-len(b)) % 16
+        assert pad <= 15
+        out.append(b); out.append(np.zeros(pad, dtype=np.uint8))
+        payload.append(np.ones(len(b), dtype=bool)); payload.append(np.zeros(pad, dtype=bool))
+
+    rows_of = lambda k: [individuals[i]["chr"][k][h] for i in range(n) for h in range(2)]
+    counts = np.zeros((n, nchr, 2, 2), dtype=np.uint32)
+    for i, ind in enumerate(individuals):
+        for k in range(nchr):
+            if active[k]:
+                for h in range(2):
+                    parts, muts = ind["chr"][k][h]
+                    counts[i, k, h, 0] = len(muts); counts[i, k, h, 1] = len(parts) if parts_travel else 0
+    put(counts)
+    put(np.array([ind["sex"] for ind in individuals], dtype=np.uint8))
+    for k in range(nchr):                                        # [planes]: the pool row, i.e. the founder mosaic without the row's own mutations
+        if not (active[k] and rows_travel):
+            continue
+        stride = _up(-(-Ls[k] // 8), 128)
+        bits = np.zeros((2 * n, stride * 8), dtype=np.uint8)
+        for r, (parts, _) in enumerate(rows_of(k)):
+            cov = _covering(parts, snp_pos[k])
+            for j in np.flatnonzero(cov >= 0):
+                _, _, hap, rp = parts[cov[j]]
+                bits[r, j] = founders[k][rp][hap][j]
+        put(np.packbits(bits, axis=1, bitorder="little"))
+    rp_bits = (n_pop - 1).bit_length()
+    for p, pos_p in enumerate(cv_pos):                           # [cv]: alleles by position, then one plane per bit of the root population
+        for k in range(nchr):
+            if not active[k]:
+                continue
+            pos = np.asarray(pos_p[k], dtype=np.uint64); C = len(pos)
+            order = np.argsort(pos, kind="stable")               # column -> file index
+            sub = max(-(-C // 32), 1); words = _up(sub * (1 + rp_bits), 4)
+            planes = np.zeros((2 * n, words * 32), dtype=np.uint8)
+            for r, (parts, muts) in enumerate(rows_of(k)):
+                cov = _covering(parts, pos[order]) if C else np.zeros(0, dtype=np.int64)
+                flipped = np.isin(pos[order], np.asarray(muts, dtype=np.uint64))
+                for col in np.flatnonzero(cov >= 0):
+                    _, _, hap, rp = parts[cov[col]]
+                    planes[r, col] = cv_founders[p][k][rp][hap][order[col]] ^ int(flipped[col])
+                    for b in range(rp_bits):
+                        planes[r, (1 + b) * sub * 32 + col] = (rp >> b) & 1
+            put(np.packbits(planes, axis=1, bitorder="little"))
+    for k in range(nchr):
+        if active[k]:
+            put(np.array([m for _, muts in rows_of(k) for m in muts], dtype=np.uint64))
+    for k in range(nchr):
+        if active[k] and parts_travel:
+            from geneevolve_amd.capi import PART_DTYPE
+            flat = [q for parts, _ in rows_of(k) for q in parts]
+            rec = np.zeros(len(flat), dtype=PART_DTYPE)
+            for name, col in zip(("st", "en", "hap_index", "root_population"), range(4)):
+                rec[name] = [q[col] for q in flat]
+            put(rec)
+    rec, mask = np.concatenate(out), np.concatenate(payload)
+    assert len(rec) % 16 == 0
+    return (rec, mask) if want_mask else rec
+
+
+def encode_oracle_record(individuals):
+    """the oracle's private u64 stream (pack_humans of oracle/gev_oracle.cpp): n, then per individual its sex and per chromosome and
+    chromatid the number of parts and per part st, en, hap_index, root_population, its number of mutations and those.  The oracle keeps
+    a mutation with the part that covers it, so every mutation of a row is handed to that part (one that no part covers -- the last
+    map position, where new mutations never land either -- cannot be held and is refused)."""
+    w = [len(individuals)]
+    for ind in individuals:
+        w.append(ind["sex"])
+        for pair in ind["chr"]:
+            for parts, muts in pair:
+                cov = _covering(parts, muts) if len(muts) else np.zeros(0, dtype=np.int64)
+                assert (cov >= 0).all(), "a mutation that no part covers"
+                w.append(len(parts))
+                for q, (st, en, hap, rp) in enumerate(parts):
+                    mine = [int(m) for m, c in zip(muts, cov) if c == q]
+                    w += [st, en, hap, rp, len(mine)] + mine
+    return np.array(w, dtype=np.uint64)
+
+
 def bits_equal(a, b):
     """bit-exact comparison of float64 arrays (NaN-safe, distinguishes -0.0)"""
     return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
