@@ -235,7 +235,8 @@ __global__ void __launch_bounds__(256) k_lp_inherit(const ChrWork* __restrict__ 
     }
 }
 // pass 2, thread per item (persistent grid): the pieces of a range with an event, in two walks over the (short) source pieces --
-// count, one atomic per workgroup and arena, fill
+// count, one atomic per workgroup and arena, fill.  Launched with LITERAL = true only (GEV_LP_LITERAL=1, the cross-check);
+// k_lp_build_plan below took over the closed form, and builds the items over its budget with this kernel's per-thread walks
 template <bool LITERAL>
 __global__ void __launch_bounds__(256) k_lp_build(const ChrWork* __restrict__ Wt, int nchr, int has_mut, SampleDev sd)
 {
@@ -281,7 +282,200 @@ __global__ void __launch_bounds__(256) k_lp_build(const ChrWork* __restrict__ Wt
         __syncthreads();                                  // s_base is written again in the next round
     }
 }
-// pass 2 with EIGHT lanes per item (the default): a piece is short (a few to a few dozen entries), and one lane that bisects it and
+// pass 2, plan per thread and copy per workgroup (GEV_LP_LANES=1 and the default).  A thread walks its item's events ONCE: per
+// interval of the crossover pattern the table lookup and the bisections of lp_interval_fast give run descriptors in LDS instead of
+// entries in the arena -- for the interval piece {first entry of the body run, its length, is the entry in front of it emitted
+// clipped to st = Lc}, for the mutation piece {first entry of the run [lo, hi), its length} and, per new position of the row's
+// side in the range, the number of inherited entries that are not larger (a bisection in the one run the position can lie in) --
+// so np and nm are sums of descriptor fields.  Space is allocated as before (two scans, one atomic per workgroup and arena, the
+// same capacity test); then the WHOLE workgroup copies: the output entries of its 256 items are one index space per arena
+// (the scans' exclusive offsets), thread x, x + 256, ... finds (item, run, entry) by a search in LDS and moves one entry with one
+// independent load and one store.  A mutation entry lands as in lp_build_muts8: an inherited one moves up by the number of new
+// positions in front of it, a new one goes behind every inherited entry that is not larger.
+// The budget per item is LPP_IV intervals (= LPP_IV - 1 boundaries in one range of one gamete) and LPP_NEW new positions: at
+// config 2 (~1 crossover and ~0.5 new mutations per gamete on 31 ranges) one item in several thousand has a third boundary in its
+// range, and LDS is what bounds the kernel's occupancy: 3 + 4 make 116 bytes of descriptors per item = 29 KiB per workgroup,
+// five workgroups per CU (a fourth interval: 33 KiB, four).  An item over either budget
+// is counted and built by its own thread with lp_build_parts / lp_build_muts, in the space the same allocation gave it; an item
+// that does not fit (or is built by its thread) has its copy bit clear and none of its runs is touched by the copy.
+#define LPP_IV 3
+#define LPP_NEW 4
+#define LPP_COPY_P 0x100u
+#define LPP_COPY_M 0x200u
+__device__ __forceinline__ u32 lpp_item_of(const u32* __restrict__ s_off, u32 x)      // last item whose exclusive offset is <= x
+{
+    u32 lo = 0, hi = 256;
+#pragma unroll
+    for (int s = 0; s < 8; s++) { const u32 mid = (lo + hi) >> 1; if (s_off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+__global__ void __launch_bounds__(256) k_lp_build_plan(const ChrWork* __restrict__ Wt, int nchr, int has_mut, SampleDev sd)
+{
+    __shared__ u32 lds[8];
+    __shared__ u32 s_base[2];
+    __shared__ u32 s_offp[256], s_offm[256], s_meta[256];        // exclusive offsets of the items; intervals | new positions << 4 | copy bits
+    __shared__ u32 s_bk[256], s_carry[256];                      // index of the item's boundary j0 in sd.bk; arena index of the carry-in
+    __shared__ u32 s_psrc[LPP_IV][256], s_pcnt[LPP_IV][256];     // interval piece: first body entry, body length | clipped head << 31
+    __shared__ u32 s_msrc[LPP_IV][256], s_mcnt[LPP_IV][256];     // mutation piece: first entry of the run, its length
+    __shared__ u64 s_nv[LPP_NEW][256];                           // new positions of the row's side in the range, ascending
+    __shared__ u32 s_ncnt[LPP_NEW][256];                         // inherited entries that are not larger
+    const ChrWork& w = Wt[blockIdx.y];
+    const LpWork& lp = w.lp;
+    const u32 n_items = *lp.n_items;
+    const u64 bp0 = w.bp0, bp_end = w.bp_end;
+    const u32 tid = threadIdx.x;
+    for (u32 base = blockIdx.x * 256u; base < n_items; base += gridDim.x * 256u) {       // (uniform per workgroup)
+        const u32 q0 = base + tid;
+        const bool live = q0 < n_items;
+        size_t row = 0; u32 t = 0, np = 0, nm = 0, niv = 0, n_new = 0;
+        bool plan_p = false, plan_m = false;
+        LpEvents ev{};
+        if (live) {
+            const u32 it = lp.items[q0];
+            row = it / LP_MAXSEG; t = it % LP_MAXSEG;
+            ev = lp_events(w, row, t, nchr, has_mut, sd);
+            niv = ev.j1 - ev.j0 + 1;
+            if (ev.fresh_m)
+                for (u32 m = ev.in; m < ev.nn; m++) {
+                    const u64 x = sd.nm_pos[m];
+                    if (sd.nm_side[m] == ev.s && x >= bp0 && x < bp_end && lp_seg(x, bp0, lp.lgw, lp.nseg) == t) { if (n_new < LPP_NEW) s_nv[n_new][tid] = x; n_new++; }
+                }
+            plan_p = ev.fresh_p && niv <= LPP_IV;
+            plan_m = ev.fresh_m && niv <= LPP_IV && n_new <= LPP_NEW;
+            if (ev.fresh_p && !plan_p) np = 1 + lp_build_parts<false, false>(lp, ev.parent, ev.start, ev.bk, ev.j0, ev.j1, t, bp0, bp_end, nullptr);
+            if (ev.fresh_m && !plan_m) nm = lp_build_muts<false>(lp, ev.parent, ev.start, ev.bk, ev.j0, ev.j1, t, sd.nm_pos, sd.nm_side, ev.in, ev.nn, ev.s, bp0, bp_end, nullptr);
+            if (plan_p || plan_m) {
+                const bool lastr = t + 1 >= lp.nseg;
+                const u64 en_last = lastr ? bp_end : LP_INF;
+                s_bk[tid] = (u32)(ev.bk - sd.bk) + ev.j0;
+                np = plan_p ? 1u : 0u;
+                for (u32 q = ev.j0; q <= ev.j1; q++) {                 // interval q: behind boundary q-1, in front of boundary q
+                    const u32 qi = q - ev.j0;
+                    const size_t src = ((size_t)2 * ev.parent + ((ev.start ^ q) & 1u)) * lp.nseg + t;
+                    const u64 Lb = q > ev.j0 ? ev.bk[q - 1] : 0ull, Rb = q < ev.j1 ? ev.bk[q] : LP_INF;
+                    if (plan_p) {                                      // lp_interval_fast, its runs named instead of copied
+                        const uint2 pe = lp.ptab_cur[src];
+                        const LpPart* e = lp.parena + pe.x;
+                        const bool head = q > ev.j0 || t == 0;
+                        const u64 Lc = q > ev.j0 ? Lb : bp0, Rc = q < ev.j1 ? Rb : en_last;
+                        if (q == ev.j0) s_carry[tid] = pe.x;
+                        u32 first = 1, hf = 0, cnt = 0;
+                        if (!(head && Lc >= en_last)) {
+                            if (head) { const u32 c0 = lp_count_le(e, pe.y, Lc); if (e[c0].st < Lc) { hf = 1; first = c0 + 1; } else first = c0; }
+                            u32 last = Rc == LP_INF ? pe.y : lp_count_le(e, pe.y, Rc);
+                            if (last >= 1 && e[last].st == Rc) last--;
+                            if (first >= 1 && first <= last) cnt = last - first + 1;
+                        }
+                        s_psrc[qi][tid] = pe.x + first; s_pcnt[qi][tid] = cnt | hf << 31;
+                        np += cnt + hf;
+                    }
+                    if (plan_m) {
+                        const uint2 me = lp.mtab_cur[src];
+                        const u64* a = lp.marena + me.x;
+                        u32 lo = 0, hi = me.y;
+                        if (q > ev.j0) { u32 l = 0, r = me.y; while (l < r) { const u32 m = (l + r) >> 1; if (a[m] < Lb) l = m + 1; else r = m; } lo = l; }
+                        if (q < ev.j1) { u32 l = lo, r = me.y; while (l < r) { const u32 m = (l + r) >> 1; if (a[m] < Rb) l = m + 1; else r = m; } hi = l; }
+                        s_msrc[qi][tid] = me.x + lo; s_mcnt[qi][tid] = hi - lo;
+                        nm += hi - lo;
+                    }
+                }
+                if (plan_m) {
+                    for (u32 i = 0; i < n_new; i++) {                  // run q holds the inherited entries in [boundary q-1, boundary q)
+                        const u64 x = s_nv[i][tid];
+                        u32 c = 0;
+                        for (u32 qi = 0; qi < niv; qi++) {
+                            const u32 cnt = s_mcnt[qi][tid];
+                            if (qi + 1 < niv && x >= ev.bk[ev.j0 + qi]) { c += cnt; continue; }
+                            if (qi > 0 && x < ev.bk[ev.j0 + qi - 1]) break;
+                            const u64* a = lp.marena + s_msrc[qi][tid];
+                            u32 l = 0, r = cnt; while (l < r) { const u32 m = (l + r) >> 1; if (a[m] <= x) l = m + 1; else r = m; }
+                            c += l;
+                        }
+                        s_ncnt[i][tid] = c;
+                    }
+                    nm += n_new;
+                }
+            }
+        }
+        u32 tot_p, tot_m;
+        const u32 ex_p = block_exclusive_scan_256(np, lds, tot_p);
+        const u32 ex_m = block_exclusive_scan_256(nm, lds, tot_m);
+        s_offp[tid] = ex_p; s_offm[tid] = ex_m;
+        if (tid == 0) {
+            s_base[0] = tot_p ? atomicAdd(&sd.status[ST_TOTALS + ST_PER_CHR * w.chr + 1], tot_p) : 0u;
+            s_base[1] = tot_m ? atomicAdd(&sd.status[ST_TOTALS + ST_PER_CHR * w.chr + 0], tot_m) : 0u;
+        }
+        __syncthreads();
+        u32 meta = (niv <= LPP_IV ? niv : 0u) | (n_new <= LPP_NEW ? n_new : 0u) << 4;
+        if (live) {
+            const size_t dst = row * lp.nseg + t;
+            if (ev.fresh_p) {
+                const u64 off = (u64)lp.pbase + s_base[0] + ex_p;
+                if (off + np > lp.pcap) { atomicOr(&sd.status[ST_FLAGS], (u32)FLAG_PARTS_CAP); lp.ptab_alt[dst] = make_uint2(0u, 0u); }
+                else {
+                    if (plan_p) meta |= LPP_COPY_P;
+                    else lp_build_parts<true, false>(lp, ev.parent, ev.start, ev.bk, ev.j0, ev.j1, t, bp0, bp_end, lp.parena + off);
+                    lp.ptab_alt[dst] = make_uint2((u32)off, np - 1u);
+                }
+            }
+            if (ev.fresh_m) {
+                const u64 off = (u64)lp.mbase + s_base[1] + ex_m;
+                if (off + nm > lp.mcap) { atomicOr(&sd.status[ST_FLAGS], (u32)FLAG_MUT_CAP); lp.mtab_alt[dst] = make_uint2(0u, 0u); }
+                else {
+                    if (plan_m) meta |= LPP_COPY_M;
+                    else lp_build_muts<true>(lp, ev.parent, ev.start, ev.bk, ev.j0, ev.j1, t, sd.nm_pos, sd.nm_side, ev.in, ev.nn, ev.s, bp0, bp_end, lp.marena + off);
+                    lp.mtab_alt[dst] = make_uint2((u32)off, nm);
+                }
+            }
+        }
+        s_meta[tid] = meta;
+        __syncthreads();
+        // copy: entry x of the workgroup's interval pieces, then of its mutation pieces
+        for (u32 x = tid; x < tot_p; x += 256) {
+            const u32 i = lpp_item_of(s_offp, x), mi = s_meta[i];
+            if (!(mi & LPP_COPY_P)) continue;
+            const u32 at = x - s_offp[i];
+            LpPart p; bool found = false;
+            if (at == 0) { p = lp.parena[s_carry[i]]; found = true; }
+            else {
+                u32 k = at - 1;
+                for (u32 qi = 0; qi < (mi & 15u); qi++) {
+                    const u32 c = s_pcnt[qi][i], hf = c >> 31, cnt = c & 0x7fffffffu;
+                    if (k < cnt + hf) {
+                        const u32 src = s_psrc[qi][i];
+                        if (hf && k == 0) { p = lp.parena[src - 1]; p.st = qi ? sd.bk[s_bk[i] + qi - 1] : bp0; }     // the clipped head: st = Lc
+                        else p = lp.parena[src + k - hf];
+                        found = true; break;
+                    }
+                    k -= cnt + hf;
+                }
+            }
+            if (found) lp.parena[(size_t)lp.pbase + s_base[0] + x] = p;
+        }
+        for (u32 x = tid; x < tot_m; x += 256) {
+            const u32 i = lpp_item_of(s_offm, x), mi = s_meta[i];
+            if (!(mi & LPP_COPY_M)) continue;
+            const u32 n_new_i = (mi >> 4) & 15u;
+            u64* out = lp.marena + ((size_t)lp.mbase + s_base[1] + s_offm[i]);
+            u32 k = x - s_offm[i];
+            bool inherited = false;
+            for (u32 qi = 0; qi < (mi & 15u); qi++) {
+                const u32 cnt = s_mcnt[qi][i];
+                if (k < cnt) {
+                    const u64 v = lp.marena[s_msrc[qi][i] + k];
+                    u32 shift = 0;
+                    for (u32 j = 0; j < n_new_i; j++) shift += s_nv[j][i] < v;
+                    out[x - s_offm[i] + shift] = v;
+                    inherited = true; break;
+                }
+                k -= cnt;
+            }
+            if (!inherited && k < n_new_i) out[k + s_ncnt[k][i]] = s_nv[k][i];       // k is now the index among the new positions
+        }
+        __syncthreads();                                  // the descriptors and s_base are written again in the next round
+    }
+}
+// pass 2 with EIGHT lanes per item: a piece is short (a few to a few dozen entries), and one lane that bisects it and
 // copies it entry by entry spends its time in chains of dependent loads.  The eight lanes of a group load the piece's entries
 // strided, all at once; c(Lc) and c(Rc) are the group's sums of two comparisons per entry (the entries are sorted: the number
 // of entries <= x is all the closed form needs); the runs are copied eight entries (128 bytes) per step.  The mutation piece is

@@ -113,7 +113,7 @@ const char* gev_version(void);
  *   GEV_AD_RP_FAST=0            several root populations with their own CV effects: per-haplotype a/d lookup in global memory (k_ad_accumulate) even
  *                               when the CV files are in position order (default then: k_ad_accumulate_rp, the piece's values in LDS)
  *   GEV_LP_LITERAL=1            list pieces built by recombine's statements one by one instead of their closed form (cross-check)
- *   GEV_LP_LANES=1|8            lanes per new list piece (default: 1 below 20 interval entries per piece, else 8)
+ *   GEV_LP_LANES=1|8            new list pieces planned per thread and copied per workgroup (1, the default) or built by eight lanes each (8)
  *   GEV_TRACE_HOST=1            stderr: host time per phase of a generation, the main stream's time by phase, allocations, deferred frees */
 int  gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen);
 void gev_destroy(gev_ctx* ctx);
