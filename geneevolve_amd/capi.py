@@ -34,6 +34,14 @@ class gev_ibd_segment(C.Structure):
     _fields_ = [("st", C.c_uint64), ("en", C.c_uint64), ("row_a", C.c_uint32), ("row_b", C.c_uint32)]
 
 
+class gev_roh_params(C.Structure):
+    _fields_ = [("min_snps", C.c_uint32), ("reserved", C.c_uint32), ("min_bp", C.c_uint64), ("max_gap_bp", C.c_uint64)]
+
+
+class gev_roh_segment(C.Structure):
+    _fields_ = [("st", C.c_uint64), ("en", C.c_uint64), ("ind", C.c_uint32), ("snp_first", C.c_uint32), ("n_snps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class gev_move(C.Structure):
     _fields_ = [("src_pop", C.c_int32), ("dst_pop", C.c_int32), ("src_pos", C.c_uint64)]
 
@@ -87,6 +95,8 @@ PART_DTYPE = np.dtype(gev_part)
 MOVE_DTYPE = np.dtype(gev_move)
 SEGMENT_DTYPE = np.dtype(gev_ibd_segment)       # 24 bytes: st, en (uint64, [st, en)), row_a, row_b (uint32)
 IBD_ALL_PAIRS, IBD_UPPER = 0, 1
+ROH_PARAMS_DTYPE = np.dtype(gev_roh_params)      # 24 bytes: min_snps, reserved (uint32), min_bp, max_gap_bp (uint64); 0 = no limit, each
+ROH_SEGMENT_DTYPE = np.dtype(gev_roh_segment)    # 32 bytes: st, en (uint64, both inclusive), ind, snp_first, n_snps, reserved (uint32)
 
 # Every function include/geneevolve_amd.h declares, in its order, as "return: parameters" (tests hold the table equal to the header
 # and check that the library exports every name).  By value: int, size (size_t), u32, u64, f64.  `ctx*` is the context handle.  A
@@ -182,6 +192,9 @@ ABI = {
     "dbg_ibd_host": "int: part* u64* size part* u64* size u64 u64* u32* u64*",
     "ibd_segments": "int: ctx* int int size size int size size u64 int ibd_segment* size u64*",
     "dbg_ibd_segments_host": "int: part* u64* size part* u64* size u64 int ibd_segment* size u64*",
+    "roh_summary": "int: ctx* int int size size size size roh_params* u32* u64* u32* u64* u32*",
+    "roh_segments": "int: ctx* int int size size size size roh_params* roh_segment* size u64*",
+    "dbg_roh_host": "int: u64* size size size u64* size size size size roh_params* u32* u64* u32* u64* u32* roh_segment* size u64*",
     "rank_f64": "int: ctx* f64* size ull*",
     "download_plink_matrix": "int: ctx* int int size size u64* size",
     "format_ped_text": "int: ctx* int int size size u8* u8* u8* size",
@@ -341,6 +354,28 @@ def _ibd_segment_list(call, upper):
     out = np.zeros(n.value, dtype=SEGMENT_DTYPE)
     if n.value:
         call(pairs, out, n.value, C.byref(n))
+        assert n.value == len(out), "the list changed between the count and the fill"
+    return out
+
+
+def _roh_params(min_snps=0, min_bp=0, max_gap_bp=0):
+    return gev_roh_params(int(min_snps), 0, int(min_bp), int(max_gap_bp))
+
+
+def _roh_outs(n_ind, n_snps, want_cover=True):
+    """the five vectors of the ROH summary (cover None where not wanted)"""
+    n_ind, n_snps = max(n_ind, 0), max(n_snps, 0)
+    return (np.empty(n_ind, dtype=np.uint32), np.empty(n_ind, dtype=np.uint64), np.empty(n_ind, dtype=np.uint32), np.empty(n_ind, dtype=np.uint64),
+            np.empty(n_snps, dtype=np.uint32) if want_cover else None)
+
+
+def _roh_segment_list(call):
+    """the two calls of the run list: call(out, capacity, n_total) counts with (None, 0), then fills an exactly sized array"""
+    n = C.c_uint64()
+    call(None, 0, C.byref(n))
+    out = np.zeros(n.value, dtype=ROH_SEGMENT_DTYPE)
+    if n.value:
+        call(out, n.value, C.byref(n))
         assert n.value == len(out), "the list changed between the count and the fill"
     return out
 
@@ -519,6 +554,25 @@ class GevLibrary:
         f = self._f("dbg_ibd_segments_host")
         return _ibd_segment_list(lambda pairs, out, cap, n: self.check(f(parts_a, off_a, len(off_a) - 1, parts_b, off_b, len(off_b) - 1, int(min_bp), pairs, out, cap, n)), upper)
 
+    def dbg_roh_host(self, bits, L, pos, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0, want_cover=True, want_list=True):
+        """the library's run-of-homozygosity word logic compiled for the host (no device needed) -> (n_roh, roh_bp, roh_snps, max_bp, cover,
+        segments) as GevContext.roh_summary and roh_segments give them (cover / segments None where not wanted).  bits: uint64
+        [2 * n_people][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them; pos: the L SNP positions"""
+        bits = _arr(bits, np.uint64); pos = _arr(pos, np.uint64)
+        assert bits.ndim == 2 and bits.shape[0] % 2 == 0 and pos.shape == (L,)
+        n_people = bits.shape[0] // 2
+        n_snps = L - snp_begin if n_snps is None else n_snps
+        n_ind = n_people - ind_begin if n_ind is None else n_ind
+        q = _roh_params(min_snps, min_bp, max_gap_bp)
+        outs = _roh_outs(n_ind, n_snps, want_cover)
+        f = self._f("dbg_roh_host")
+        head = (bits, bits.shape[1], n_people, L, pos, snp_begin, n_snps, ind_begin, n_ind, C.byref(q))
+        if not want_list:
+            self.check(f(*head, *outs, None, 0, None))
+            return (*outs, None)
+        seg = _roh_segment_list(lambda out, cap, n: self.check(f(*head, *outs, out, cap, n)))
+        return (*outs, seg)
+
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
         """the .int text of individuals [ind_begin, +n_ind) by the library's line formatter compiled for the host (no device needed).
         parts / hap_offsets: as download_intervals returns them; ids: Human::ID of every individual; names: one list of founder
@@ -557,6 +611,7 @@ class GevContext:
         self.h = h
         self._nsnp = {}
         self._span_bp = {}
+        self._snp_span_bp = {}
         self._ncv = {}
         self._chr_off = set()
         self._ph_seeds = 0
@@ -587,6 +642,7 @@ class GevContext:
     def set_snps(self, pop, chr, pos):
         pos = _arr(pos, np.uint64)
         self._nsnp[(pop, chr)] = len(pos)
+        self._snp_span_bp[(pop, chr)] = int(pos[-1]) - int(pos[0]) if len(pos) else 0    # (pos[L-1] - pos[0]: the denominator of roh.f_roh)
         self._call("set_snps", pop, chr, pos, len(pos))
 
     def set_cvs(self, pop, phen, chr, bp, a, d, vd):
@@ -1146,6 +1202,29 @@ class GevContext:
         n_a = 2 * self.pop_size(pop_a) - a_begin if n_a is None else n_a
         n_b = 2 * self.pop_size(pop_b) - b_begin if n_b is None else n_b
         return _ibd_segment_list(lambda pairs, out, cap, n: self._call("ibd_segments", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), pairs, out, cap, n), upper)
+
+    def roh_summary(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0, want_cover=True):
+        """-> (n_roh, roh_bp, roh_snps, max_bp, cover): per individual of [ind_begin, +n_ind) over its qualifying runs of homozygosity among
+        the SNPs [snp_begin, +n_snps) (runs are cut at the range's ends), uint32 / uint64 / uint32 / uint64 [n_ind]: their number, their
+        summed length pos[j1] - pos[j0], their summed SNPs and the longest (0 without one); cover uint32 [n_snps] (None unless wanted): the
+        individuals with the SNP inside a qualifying run.  A run: consecutive SNPs at which the two haplotypes agree (mutations applied),
+        broken where neighbouring SNPs lie more than max_gap_bp apart; it qualifies with >= min_snps SNPs and >= min_bp base pairs (0 =
+        no limit, each).  Scanned on the device from the current generation's rows"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        q = _roh_params(min_snps, min_bp, max_gap_bp)
+        outs = _roh_outs(n_ind, n_snps, want_cover)
+        self._call("roh_summary", pop, chr, snp_begin, n_snps, ind_begin, n_ind, C.byref(q), *outs)
+        return outs
+
+    def roh_segments(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0):
+        """-> ROH_SEGMENT_DTYPE records (st, en, ind, snp_first, n_snps, reserved), sorted by (ind, snp_first): the qualifying runs of
+        roh_summary themselves, st = pos[snp_first] and en = pos[snp_first + n_snps - 1] both inclusive, ind and snp_first absolute.  A
+        count call, then a fill call"""
+        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
+        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        q = _roh_params(min_snps, min_bp, max_gap_bp)
+        return _roh_segment_list(lambda out, cap, n: self._call("roh_segments", pop, chr, snp_begin, n_snps, ind_begin, n_ind, C.byref(q), out, cap, n))
 
     def ancestry_bp(self, pop, chr, row_begin=0, n_rows=None):
         """-> (bp uint64 [n_rows][n_pop], n_parts uint32 [n_rows]): the base pairs of every haplotype row covered by parts of each root

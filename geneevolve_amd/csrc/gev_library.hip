@@ -28,6 +28,7 @@
 #include "gev_ldcount.h"
 #include "gev_traitsum.h"
 #include "gev_ibd.h"
+#include "gev_roh.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
 #include "gev_phenotypes.h"
@@ -344,6 +345,7 @@ struct gev_ctx {
     Dev<int32_t> d_ts_trait, d_ts_acc; Dev<uint4> d_ts_b; Dev<long long> d_ts_out; // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
     DevBytes d_ibd_out; Dev<u32> d_ibd_flag; // gev_ibd_sharing / gev_ancestry_bp (gev_ibd.h): a sub-block's results, the flag of a bad root population; created by the first call
     Dev<u32> d_ibd_cnt, d_ibd_off; Dev<gev_ibd_segment> d_ibd_seg; Dev<unsigned long long> d_ibd_tot; // gev_ibd_segments: a strip's counts per pair, their exclusive scan, its records, its 64-bit record count; created by the first call
+    Dev<u64> d_roh_brk; DevBytes d_roh_out; Dev<u32> d_roh_diff, d_roh_cov, d_roh_cnt, d_roh_off; Dev<gev_roh_segment> d_roh_seg; // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's counts, their exclusive scan and its records; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     Dev<uint8_t> d_mflag; Dev<u32> d_mblk, d_posm, d_posf, d_pickblk, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat; Dev<gev_couple> d_couples; Dev<double> d_svf; // gev_random_mate / gev_glob_seeds scratch
     Dev<double> d_gef_io; DevBytes d_gef_stat; // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
@@ -4553,6 +4555,180 @@ int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, si
     if (pairs == GEV_IBD_UPPER && (parts_a != parts_b || off_a != off_b)) return fail(GEV_EINVAL, "%s: GEV_IBD_UPPER takes the same lists on both sides", who);
     if (n_a > 0xffffffffull || n_b > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: rows beyond 2^32 - 1 do not fit a record", who);
     gev_ibd_segments_fit_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, pairs == GEV_IBD_UPPER, out, capacity, n_total);
+    return GEV_OK;
+}
+// ---- runs of homozygosity (gev_roh.h) -------------------------------------------------------------
+// what the device calls and the host form refuse of a request (params, the ranges, indices that do not fit a record's 32 bits)
+static int roh_args(const char* who, const gev_roh_params* q, size_t snp_begin, size_t n_snps, size_t L, size_t ind_begin, size_t n_ind, size_t n_people)
+{
+    if (!q) return fail(GEV_EINVAL, "%s: params is null", who);
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
+    if (L >= 0xffffffffull || n_people > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: SNP or individual indices beyond 2^32 - 1 do not fit a record", who);
+    return GEV_OK;
+}
+static int roh_seg_args(const char* who, const gev_roh_segment* out, size_t capacity, const uint64_t* n_total)
+{
+    if (!n_total) return fail(GEV_EINVAL, "%s: n_total is null", who);
+    if (!out && capacity) return fail(GEV_EINVAL, "%s: a null output of capacity %zu", who, capacity);
+    return GEV_OK;
+}
+static int roh_begin(gev_ctx* c, int pop, int chr, const char* who, const gev_roh_params* q, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind)
+{
+    GEVC(output_begin(c, pop, chr, who, true));
+    GEVC(ensure_csr(c, pop));
+    return roh_args(who, q, snp_begin, n_snps, c->pop[pop].cs[chr].L, ind_begin, n_ind, c->pop[pop].n_people);
+}
+// the break bit plane of the chromosome into c->d_roh_brk (brk: null for max_gap_bp == 0, which has no breaks)
+static int roh_breaks(gev_ctx* c, ChrStatic& S, u64 max_gap_bp, const uint4*& brk)
+{
+    brk = nullptr;
+    if (!max_gap_bp) return GEV_OK;
+    const size_t n_words = 2 * ceil_div(S.L, 128);
+    GEVC(c->d_roh_brk.ensure(n_words, c->stream));
+    hipLaunchKernelGGL(k_roh_breaks, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, c->stream, (const u64*)S.d_pos, (u64)S.L, max_gap_bp, (u32)n_words, c->d_roh_brk.p);
+    KCHECK();
+    brk = (const uint4*)c->d_roh_brk.p;
+    return GEV_OK;
+}
+// one request's constants, and a scan of the n individuals staged from individual ind0 on
+struct RohCall { const u64* pos; const uint4* brk; u32 chunks, snp_begin, n_snps; gev_roh_params q; };
+static int roh_launch(gev_ctx* c, const RohCall& r, int mode, size_t ind0, size_t n, u32* n_roh, u64* roh_bp, u32* roh_snps, u64* max_bp, u32* diff, u32* cnt, gev_roh_segment* out)
+{
+    const auto kernel = mode == ROH_SUMMARY ? k_roh_scan<ROH_SUMMARY> : mode == ROH_COUNT ? k_roh_scan<ROH_COUNT> : k_roh_scan<ROH_FILL>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ceil_div(n, ROH_WAVES)), dim3(ROH_WAVES * 64), 0, c->stream, (const uint4*)c->d_stage.as<uint4>(), r.chunks, (u32)n, (u32)ind0,
+                       r.pos, r.brk, r.snp_begin, r.n_snps, r.q, n_roh, roh_bp, roh_snps, max_bp, diff, cnt, out);
+    KCHECK();
+    return GEV_OK;
+}
+// The individuals are staged in passes (ind_major_chunks); every pass's wave per individual writes entry i of the call's four vectors,
+// the cover's difference array is the whole call's, scanned once behind the last pass.
+int gev_roh_summary(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, const gev_roh_params* q,
+                    uint32_t* n_roh, uint64_t* roh_bp, uint32_t* roh_snps, uint64_t* max_bp, uint32_t* cover)
+{
+    const char* who = "roh_summary";
+    GEVC(roh_begin(c, pop, chr, who, q, snp_begin, n_snps, ind_begin, n_ind));
+    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr];
+    if (!n_ind) { if (cover && n_snps) memset(cover, 0, n_snps * sizeof(u32)); return GEV_OK; }
+    if (!n_snps) {
+        if (n_roh) memset(n_roh, 0, n_ind * sizeof(u32));
+        if (roh_bp) memset(roh_bp, 0, n_ind * sizeof(u64));
+        if (roh_snps) memset(roh_snps, 0, n_ind * sizeof(u32));
+        if (max_bp) memset(max_bp, 0, n_ind * sizeof(u64));
+        return GEV_OK;
+    }
+    if (!n_roh && !roh_bp && !roh_snps && !max_bp && !cover) return GEV_OK;
+    hipStream_t st = c->stream;
+    // the 8-byte vectors first: every part of the buffer begins on a multiple of its element
+    GEVC(c->d_roh_out.ensure(n_ind * 24, st));
+    u64* d_bp = c->d_roh_out.as<u64>(); u64* d_mx = d_bp + n_ind; u32* d_n = (u32*)(d_mx + n_ind); u32* d_sn = d_n + n_ind;
+    u32* d_diff = nullptr;
+    if (cover) {
+        GEVC(c->d_roh_diff.ensure(n_snps + 1, st));
+        GEVC(c->d_roh_cov.ensure(n_snps + 1, st));
+        d_diff = c->d_roh_diff.p;
+        HIPC(hipMemsetAsync(d_diff, 0, (n_snps + 1) * sizeof(u32), st));
+    }
+    RohCall r = {S.d_pos, nullptr, (u32)(S.stride / 16), (u32)snp_begin, (u32)n_snps, *q};
+    GEVC(roh_breaks(c, S, q->max_gap_bp, r.brk));
+    GEVC(ind_major_chunks(c, pop, chr, ind_begin, n_ind, 2 * S.stride, [&](size_t i, size_t n) -> int {
+        return roh_launch(c, r, ROH_SUMMARY, ind_begin + i, n, d_n + i, d_bp + i, d_sn + i, d_mx + i, d_diff, nullptr, nullptr);
+    }));
+    if (cover) {
+        GEVC(scan_u32_on(st, c->d_sums, d_diff, n_snps, c->d_roh_cov.p));      // entry j + 1 = the inclusive sum up to j (mod 2^32, as the -1 entries are)
+        HIPC(hipMemcpyAsync(cover, c->d_roh_cov.p + 1, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
+    }
+    if (n_roh) HIPC(hipMemcpyAsync(n_roh, d_n, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
+    if (roh_bp) HIPC(hipMemcpyAsync(roh_bp, d_bp, n_ind * sizeof(u64), hipMemcpyDeviceToHost, st));
+    if (roh_snps) HIPC(hipMemcpyAsync(roh_snps, d_sn, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
+    if (max_bp) HIPC(hipMemcpyAsync(max_bp, d_mx, n_ind * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the counts of the staged pass into c->d_roh_cnt and their 64-bit sum into *total (in host memory when this returns)
+static int roh_count_pass(gev_ctx* c, const RohCall& r, size_t ind0, size_t n, u64* total)
+{
+    hipStream_t st = c->stream;
+    GEVC(roh_launch(c, r, ROH_COUNT, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_roh_cnt.p, nullptr));
+    GEVC(c->d_ibd_tot.ensure(1, st));
+    HIPC(hipMemsetAsync(c->d_ibd_tot.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_ibd_total, dim3((unsigned)std::min<size_t>(ceil_div(n, 1024), 1024)), dim3(256), 0, st, (const u32*)c->d_roh_cnt.p, n, c->d_ibd_tot.p);
+    KCHECK();
+    unsigned long long t = 0;
+    HIPC(hipMemcpyAsync(&t, c->d_ibd_tot.p, sizeof t, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    *total = t;
+    return GEV_OK;
+}
+// the `total` records of the staged and counted pass into out (host): scan, fill into c->d_roh_seg, copy
+static int roh_fill_pass(gev_ctx* c, const RohCall& r, size_t ind0, size_t n, u64 total, gev_roh_segment* out)
+{
+    hipStream_t st = c->stream;
+    if (total >> 32) return fail(GEV_EUNSUPPORTED, "roh_segments: %llu records in one pass", (unsigned long long)total);
+    GEVC(c->d_roh_seg.ensure((size_t)total, st));
+    GEVC(scan_u32_on(st, c->d_sums, c->d_roh_cnt.p, n, c->d_roh_off.p));
+    GEVC(roh_launch(c, r, ROH_FILL, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_roh_off.p, c->d_roh_seg.p));
+    HIPC(hipMemcpyAsync(out, c->d_roh_seg.p, (size_t)total * sizeof(gev_roh_segment), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// A request of one pass counts, scans and fills on the same staged rows.  A request of several passes counts them all (n_total), and if
+// out holds the records stages each again, counts it (the offsets of its fill) and fills: passes are runs of whole individuals in order,
+// so their records concatenate.
+int gev_roh_segments(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, const gev_roh_params* q,
+                     gev_roh_segment* out, size_t capacity, uint64_t* n_total)
+{
+    const char* who = "roh_segments";
+    GEVC(roh_seg_args(who, out, capacity, n_total));
+    GEVC(roh_begin(c, pop, chr, who, q, snp_begin, n_snps, ind_begin, n_ind));
+    PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr];
+    if (!n_ind || !n_snps) { *n_total = 0; return GEV_OK; }
+    hipStream_t st = c->stream;
+    const size_t per_pass = std::min(output_chunk(c, 256u << 20, 2 * S.stride), n_ind);      // (what ind_major_chunks takes)
+    const bool one_pass = per_pass == n_ind;
+    GEVC(c->d_roh_cnt.ensure(per_pass, st));
+    GEVC(c->d_roh_off.ensure(per_pass + 1, st));
+    RohCall r = {S.d_pos, nullptr, (u32)(S.stride / 16), (u32)snp_begin, (u32)n_snps, *q};
+    GEVC(roh_breaks(c, S, q->max_gap_bp, r.brk));
+    u64 total = 0;
+    GEVC(ind_major_chunks(c, pop, chr, ind_begin, n_ind, 2 * S.stride, [&](size_t i, size_t n) -> int {
+        u64 t = 0;
+        GEVC(roh_count_pass(c, r, ind_begin + i, n, &t));
+        total += t;
+        if (one_pass && t && t <= capacity) GEVC(roh_fill_pass(c, r, ind_begin + i, n, t, out));
+        return GEV_OK;
+    }));
+    *n_total = total;
+    if (one_pass || !total || total > capacity) return GEV_OK;
+    size_t done = 0;
+    return ind_major_chunks(c, pop, chr, ind_begin, n_ind, 2 * S.stride, [&](size_t i, size_t n) -> int {
+        u64 t = 0;
+        GEVC(roh_count_pass(c, r, ind_begin + i, n, &t));
+        if (t) GEVC(roh_fill_pass(c, r, ind_begin + i, n, t, out + done));
+        done += (size_t)t;
+        return GEV_OK;
+    });
+}
+// the walk of gev_roh.h compiled for the host on rows and positions in host memory: no device, no context
+int gev_dbg_roh_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, const uint64_t* pos,
+                     size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, const gev_roh_params* q,
+                     uint32_t* n_roh, uint64_t* roh_bp, uint32_t* roh_snps, uint64_t* max_bp, uint32_t* cover,
+                     gev_roh_segment* out, size_t capacity, uint64_t* n_total)
+{
+    const char* who = "dbg_roh_host";
+    if (n_total) GEVC(roh_seg_args(who, out, capacity, n_total));
+    else if (out || capacity) return fail(GEV_EINVAL, "%s: an output list without n_total", who);
+    GEVC(roh_args(who, q, snp_begin, n_snps, L, ind_begin, n_ind, n_people));
+    if (n_snps && n_ind && (!bits || !pos || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: null rows or positions, or rows of %zu words (%zu needed)", who, row_stride_words, ceil_div(L, 64));
+    if (!n_ind) {
+        if (cover && n_snps) memset(cover, 0, n_snps * sizeof(u32));
+        if (n_total) *n_total = 0;
+        return GEV_OK;
+    }
+    std::vector<u32> diff(cover ? n_snps + 1 : 0, 0);
+    gev_roh_rows_host(bits, row_stride_words, pos, L, snp_begin, n_snps, ind_begin, n_ind, *q, n_roh, roh_bp, roh_snps, max_bp, cover ? diff.data() : nullptr, nullptr);
+    if (cover) gev_roh_cover_host(diff.data(), n_snps, cover);
+    if (n_total) gev_roh_segments_fit_host(bits, row_stride_words, pos, L, snp_begin, n_snps, ind_begin, n_ind, *q, out, capacity, n_total);
     return GEV_OK;
 }
 // ---- PLINK individual-major outputs ---------------------------------------------------------

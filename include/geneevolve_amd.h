@@ -736,6 +736,53 @@ int gev_ibd_segments(gev_ctx*, int chr, int pop_a, size_t a_begin, size_t n_a, i
  * off_a == off_b; n_a and n_b may differ).  out, capacity and n_total as above. */
 int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
                               uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total);
+/* ---- runs of homozygosity: F_ROH, islands and the run list without a dump (csrc/gev_roh.h) -----------------------------------------
+ * The observed side of what gev_ibd_sharing gives from the ancestry: for individual i of (pop, chr) and the SNPs [snp_begin, +n_snps),
+ * hom(j) is true when haplotype rows 2i and 2i+1 carry the same allele at SNP j of the current generation (new mutations applied as
+ * gev_download_haps applies them: !founder at every SNP column whose position is in the row's mutation list, idempotent).  A RUN is a
+ * maximal set of consecutive SNPs j0..j1 INSIDE THE RANGE with hom true throughout and, for max_gap_bp != 0, pos[j] - pos[j-1] <=
+ * max_gap_bp for every j0 < j <= j1.  SNPs outside the range do not exist for the call: runs are cut at the range's ends, so results
+ * are NOT additive over SNP ranges.  A run has n = j1 - j0 + 1 SNPs, st = pos[j0] and en = pos[j1], both inclusive (PLINK's POS1 and
+ * POS2), and en - st base pairs (a one-SNP run has length 0); SNP columns that share a position are consecutive SNPs with gap 0.  A run
+ * QUALIFIES when n >= max(min_snps, 1) and en - st >= min_bp.  No heterozygous or missing call is allowed inside a run (simulated
+ * genotypes have neither): PLINK's --homozyg with --homozyg-window-het 0, without its sliding window.  Each limit: 0 = none.
+ *
+ * gev_roh_summary, per individual ind_begin + i over its qualifying runs, each output may be NULL:
+ *   n_roh    (uint32 [n_ind])  their number                      roh_bp (uint64 [n_ind])  their summed en - st
+ *   roh_snps (uint32 [n_ind])  their summed n                    max_bp (uint64 [n_ind])  the longest en - st, 0 without a run
+ *   cover    (uint32 [n_snps]) entry j: the individuals of the range with SNP snp_begin + j inside a qualifying run (ROH islands)
+ * n_ind == 0 writes zeros into cover and touches nothing else; n_snps == 0 writes zeros into the per-individual vectors.
+ *
+ * gev_roh_segments: one record per qualifying run, ind the absolute individual, snp_first = j0 the absolute SNP index, sorted by
+ * (ind, snp_first): the same bytes on every run, whatever the passes were.  out, capacity and n_total follow gev_ibd_segments' rule:
+ *   *n_total is always set to the number of records of the request (n_total == NULL: GEV_EINVAL).  out is filled if and only if
+ *   *n_total <= capacity; otherwise the call still returns GEV_OK, the caller sees *n_total > capacity and nothing of out is written
+ *   (never a byte at or beyond out[capacity]).  out == NULL with capacity == 0 is the count-only form; a call with the counted capacity
+ *   then fills.  n_ind == 0 or n_snps == 0 sets *n_total = 0 and touches nothing else.  A refused call leaves both as they were.
+ *
+ * Both begin like the other genotype output calls (a pending order is materialised, the planes are waited for, the CSR lists derived)
+ * and return when the results are in the caller's memory.  The rows are staged, mutations applied, in passes of individuals (about
+ * 256 MB of rows; gev_dbg_output_chunk caps a pass's individuals): one extra write and read of the rows, because a sparse mutation can
+ * split or join a run and no after-the-fact correction exists.  One wave scans one individual, 8192 SNPs a step.  gev_roh_segments on
+ * a request of one pass counts, scans and fills on the same staged rows; a request of several passes counts them all, then -- when out
+ * holds the records -- stages every pass again to count and fill it: twice the staging and three scans instead of two.  A pass's
+ * records are held on the device until they are copied out.  GEV_ESTATE, the message naming what is missing: no resident genotype
+ * planes, an inactive chromosome, a population without a current generation, a generation pending; GEV_EINVAL for a range beyond L or
+ * n_people and for params == NULL.  The device buffers are created by the first call. */
+typedef struct gev_roh_params  { uint32_t min_snps, reserved; uint64_t min_bp, max_gap_bp; } gev_roh_params;   /* 0 = no limit, each */
+typedef struct gev_roh_segment { uint64_t st, en; uint32_t ind, snp_first, n_snps, reserved; } gev_roh_segment; /* 32 bytes; reserved = 0 */
+int gev_roh_summary(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, const gev_roh_params*,
+                    uint32_t* n_roh /*[n_ind]*/, uint64_t* roh_bp /*[n_ind]*/, uint32_t* roh_snps /*[n_ind]*/, uint64_t* max_bp /*[n_ind]*/,
+                    uint32_t* cover /*[n_snps]*/);
+int gev_roh_segments(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, const gev_roh_params*,
+                     gev_roh_segment* out, size_t capacity, uint64_t* n_total);
+/* the same word logic (csrc/gev_roh.h) compiled for the host on haplotype-major rows as gev_download_haps returns them (row r = bits +
+ * r * row_stride_words, rows 2i and 2i+1 = individual i of n_people) and the chromosome's L positions: no device, no context, the same
+ * range checks.  The summary outputs as gev_roh_summary's; the list as gev_roh_segments', n_total == NULL: no list wanted. */
+int gev_dbg_roh_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, const uint64_t* pos,
+                     size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, const gev_roh_params*,
+                     uint32_t* n_roh, uint64_t* roh_bp, uint32_t* roh_snps, uint64_t* max_bp, uint32_t* cover,
+                     gev_roh_segment* out, size_t capacity, uint64_t* n_total);
 /* ---- mating support [SURVEY 8(f) row 2] ------------------------------------------------------
  * == CommFunc::ras_rank (src/CommFunc.cpp:152-161), the O(n^2) zero-based rank assort_mate applies to its bivariate-normal
  * template (src/Simulation.cpp:2278-2279): rank[k] = #{x[j] < x[k]} + #{j < k : x[j] == x[k]}.  Host buffers. */

@@ -1,0 +1,438 @@
+"""gev_roh_summary / gev_roh_segments: runs of homozygosity scanned on the device from the staged haplotype rows (one wave per
+individual, geneevolve_amd/csrc/gev_roh.h), against the per-SNP truth of tests/roh_inputs.py on the rows gev_download_haps returns and
+against the same header built for the host: hand-built rows with hets at word, chunk and tile edges on gapped positions, a bred inbred
+population with runs across the tile edges, the mutation overlay, a population behind a migration, the capacity rule with a guard, the
+empty forms and the refusals (pytest -m gpu).  The requirement throughout is device == truth == host build, by equality of the bytes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from geneevolve_amd import capi, roh
+from geneevolve_amd.capi import ROH_SEGMENT_DTYPE
+from geneevolve_amd.host import Simulation, SyntheticConfig
+from tests import helpers
+from tests import roh_inputs as R
+from tests.synth import synth_packed
+
+pytestmark = pytest.mark.gpu
+
+
+def unpacked(ctx, pop, chr):
+    words = ctx.download_haps(pop, chr)
+    return capi.unpack_rows(words, ctx._nsnp[(pop, chr)]), words
+
+
+def device(ctx, pop, chr, s0=0, ns=None, i0=0, ni=None, **lim):
+    """the six results of tests/roh_inputs.truth from the two device calls"""
+    return (*ctx.roh_summary(pop, chr, s0, ns, i0, ni, **lim), ctx.roh_segments(pop, chr, s0, ns, i0, ni, **lim))
+
+
+class Rows:
+    """a context's current rows of (pop, chr) with their truth, computed once per request and left unchanged"""
+
+    def __init__(self, lib, ctx, pos, pop=0, chr=0):
+        self.lib, self.ctx, self.pos, self.pop, self.chr = lib, ctx, np.asarray(pos, dtype=np.uint64), pop, chr
+        self.bits01, self.words = unpacked(ctx, pop, chr)
+        self.L, self.n = self.bits01.shape[1], self.bits01.shape[0] // 2
+        self._truth = {}
+
+    def truth(self, s0=0, ns=None, i0=0, ni=None, **lim):
+        key = (s0, ns, i0, ni, tuple(sorted(lim.items())))
+        if key not in self._truth:
+            self._truth[key] = R.truth(self.bits01, self.pos, s0, ns, i0, ni, **lim)
+            for v in self._truth[key]:
+                v.setflags(write=False)
+        return self._truth[key]
+
+    def check(self, what, s0=0, ns=None, i0=0, ni=None, host=True, **lim):
+        want = self.truth(s0, ns, i0, ni, **lim)
+        label = f"{what}: SNPs [{s0},+{ns}) individuals [{i0},+{ni}) {lim}"
+        got = device(self.ctx, self.pop, self.chr, s0, ns, i0, ni, **lim)
+        R.same(got, want, "device against the truth, " + label)
+        if host:
+            R.same(self.lib.dbg_roh_host(self.words, self.L, self.pos, s0, ns, i0, ni, **lim), want, "host build against the truth, " + label)
+        return got
+
+
+# ---- 1. hand-built rows ----------------------------------------------------------------------------------------------------------------
+def build_hand_built(lib):
+    """the constructed individuals of tests/roh_inputs.py as founders: individual i of generation 0 is founder haplotypes 2i, 2i+1"""
+    patterns = R.het_patterns()
+    words = capi.pack_rows(R.rows_from_patterns(patterns))
+    n = len(patterns)
+    cfg = SyntheticConfig(n, R.L, chrom_bp=3_000_000, map_step=20_000, rec_per_row=1e-3, n_cv=8, seed=3, with_mutation=False)
+    cfg.snp_pos = R.positions()
+    ctx = lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    ctx.upload_founders(0, 0, words, R.L); ctx.upload_cv_founders(0, 0, 0, synth_packed(32, 2 * n, 8), 8)
+    ctx.init_gen0(0, n, 77)
+    assert np.array_equal(ctx.download_haps(0, 0), words), "generation 0 is the founders, row for row"
+    return Rows(lib, ctx, cfg.snp_pos)
+
+
+@pytest.fixture(scope="module")
+def hand_built(gpu_lib):
+    fx = build_hand_built(gpu_lib)
+    yield fx
+    fx.ctx.close()
+
+
+IND_RANGES = ((0, 1), (39, 1), (1, 38), (5, 15))
+
+
+def hand_built_cases(fx, what, host):
+    sets = R.parameter_sets(fx.truth()[5])
+    for lim in sets:
+        for s0, ns in R.SNP_RANGES:
+            R.consistent(fx.check(what, s0, ns, host=host, **lim))
+    for i0, ni in IND_RANGES:
+        for s0, ns in ((0, R.L), (37, 8192 + 100)):
+            fx.check(what, s0, ns, i0, ni, host=host, **sets[7])
+
+
+@pytest.mark.parametrize("chunk", [0, 7, 1])
+def test_hand_built_rows(hand_built, chunk):
+    """40 individuals x 3 * 8192 + 77 SNPs (three tiles of a wave's walk and a last word of 13 loci), every parameter set and SNP range
+    of the CPU test over everybody and individual sub-ranges on one set.  chunk 7: passes of 7 individuals (the last of 5); chunk 1:
+    one individual a pass.  A repeated call gives the same bytes"""
+    fx = hand_built
+    assert fx.n == 40
+    fx.ctx.dbg_output_chunk(chunk)
+    try:
+        hand_built_cases(fx, f"chunk {chunk}", host=chunk == 0)
+        lim = R.parameter_sets(fx.truth()[5])[7]
+        first, again = device(fx.ctx, 0, 0, **lim), device(fx.ctx, 0, 0, **lim)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(first, again)), "the call repeated"
+    finally:
+        fx.ctx.dbg_output_chunk(0)
+
+
+def test_hand_built_rows_in_small_segments(gpu_lib, monkeypatch):
+    """GEV_SEG_CHUNKS=4: rows of 64-byte segments, so the staged copy gathers every row from 49 units"""
+    monkeypatch.setenv("GEV_SEG_CHUNKS", "4")
+    fx = build_hand_built(gpu_lib)
+    try:
+        assert fx.ctx.plane_ptr(0, 0)[1] == 64, "64-byte segments"
+        sets = R.parameter_sets(fx.truth()[5])
+        for chunk in (0, 7):
+            fx.ctx.dbg_output_chunk(chunk)
+            for lim in (sets[0], sets[7]):
+                for s0, ns in ((0, R.L), (37, 8192 + 100), (8191, 2)):
+                    fx.check(f"small segments, chunk {chunk}", s0, ns, host=False, **lim)
+    finally:
+        fx.ctx.close()
+
+
+# ---- 2. a bred inbred population -------------------------------------------------------------------------------------------------------
+N, L, GENS, MIN_SNPS = 48, 20_000, 12, 100
+
+
+def build_bred(lib, with_mutation=True, upload=False):
+    """48 individuals x 20 000 SNPs 100 bp apart on 2 Mbp, map rows every 20 kbp with 0.02 crossovers each, 12 generations of random
+    mating (upload: founders from the host, for a library without the device generator)"""
+    cfg = SyntheticConfig(N, L, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.02, mut_per_row=2e-3, n_cv=8, seed=5, with_mutation=with_mutation)
+    ctx = lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    if upload:
+        ctx.upload_founders(0, 0, synth_packed(31, 2 * N, L), L); ctx.upload_cv_founders(0, 0, 0, synth_packed(32, 2 * N, 8), 8)
+    else:
+        ctx.synth_founders(0, 0, 2 * N, 31); ctx.synth_cv_founders(0, 0, 0, 2 * N, 32)
+    sim = Simulation(ctx, 4247, 1, with_mutation)
+    sim.ras_initial_human_gen0(0, N)
+    for _ in range(GENS):
+        sim.next_generation_rm(0, N)
+    return ctx, cfg
+
+
+def bred_conditions(res):
+    """what the cases below need of the population at min_snps = 100, asserted from the truth -> the figures"""
+    n_roh, rec = res[0], res[5]
+    first = rec["snp_first"].astype(np.int64); last = first + rec["n_snps"] - 1
+    fig = {"runs": len(rec), "cross_4096": int((first // 4096 != last // 4096).sum()), "cross_8192": int((first // 8192 != last // 8192).sum()),
+           "without": int((n_roh == 0).sum()), "three_or_more": int((n_roh >= 3).sum()), "longest": int(rec["n_snps"].max())}
+    assert fig["cross_4096"] >= 1 and fig["cross_8192"] >= 1 and fig["without"] >= 1 and fig["three_or_more"] >= 1, fig
+    return fig
+
+
+@pytest.fixture(scope="module")
+def bred(gpu_lib):
+    """Seed and rates were chosen with the CPU oracle under the same driver, where min_snps = 100 gives 84 qualifying runs, 16 crossing a
+    multiple of 4096 and 13 a multiple of 8192, 10 individuals without a run, 14 with three or more, and a longest run of 8003 SNPs"""
+    ctx, cfg = build_bred(gpu_lib)
+    fx = Rows(gpu_lib, ctx, cfg.snp_pos)
+    fx.figures = bred_conditions(fx.truth(min_snps=MIN_SNPS))
+    print("bred:", fx.figures)
+    yield fx
+    ctx.close()
+
+
+@pytest.mark.parametrize("chunk", [0, 7])
+def test_bred_population(bred, chunk):
+    """the summary, the cover and the list at min_snps = 100 alone, with a length limit, under a gap limit that is every gap (no split)
+    and one below it (every SNP its own run), and without limits on a SNP range across two tile edges"""
+    fx = bred
+    fx.ctx.dbg_output_chunk(chunk)
+    try:
+        got = fx.check(f"chunk {chunk}", min_snps=MIN_SNPS)
+        R.consistent(got)
+        assert len(got[5]) == fx.figures["runs"] and int(got[4].sum()) == int(got[2].sum()), "cover.sum() == roh_snps.sum()"
+        for i in range(N):
+            mine = got[5][got[5]["ind"] == i]
+            bp = mine["en"] - mine["st"]
+            assert (len(mine), int(bp.sum()), int(mine["n_snps"].sum()), int(bp.max()) if len(mine) else 0) == (got[0][i], got[1][i], got[2][i], got[3][i]), f"individual {i}"
+        R.consistent(fx.check(f"chunk {chunk}", min_snps=MIN_SNPS, min_bp=50_000))
+        R.consistent(fx.check(f"chunk {chunk}", min_snps=MIN_SNPS, max_gap_bp=100))
+        R.consistent(fx.check(f"chunk {chunk}", 4000, 12_500, max_gap_bp=99))
+        R.consistent(fx.check(f"chunk {chunk}", 4000, 12_500))
+        fx.check(f"chunk {chunk}", 8191, 8193, 5, 30, min_snps=MIN_SNPS)
+    finally:
+        fx.ctx.dbg_output_chunk(0)
+
+
+def test_roh_module_on_the_bred_population(bred):
+    fx = bred
+    want = fx.truth(min_snps=MIN_SNPS)
+    span = int(fx.pos[-1] - fx.pos[0])
+    s = roh.summary(fx.ctx, 0, min_snps=MIN_SNPS)
+    assert s.span_bp == span and all(np.array_equal(g, w.astype(np.uint64)) for g, w in zip(s[1:], want[:4]))
+    f = roh.f_roh(fx.ctx, 0, min_snps=MIN_SNPS)
+    assert np.array_equal(f, want[1].astype(np.float64) / np.float64(span)) and 0 < f.max() <= 1 and f.min() == 0
+    sub = fx.truth(0, None, 5, 30, min_snps=MIN_SNPS, min_bp=50_000)
+    assert np.array_equal(roh.f_roh(fx.ctx, 0, ind=(5, 30), min_snps=MIN_SNPS, min_kb=50), sub[1].astype(np.float64) / np.float64(span))
+    seg = roh.segments(fx.ctx, 0, min_snps=MIN_SNPS)
+    assert seg.dtype.names == ("chr",) + ROH_SEGMENT_DTYPE.names and (seg["chr"] == 0).all()
+    assert all(np.array_equal(seg[name], want[5][name]) for name in ROH_SEGMENT_DTYPE.names)
+    assert np.array_equal(roh.islands(fx.ctx, 0, 0, min_snps=MIN_SNPS), want[4].astype(np.float64) / np.float64(N))
+    part = fx.truth(4000, 12_500, 5, 30, min_snps=MIN_SNPS)
+    assert np.array_equal(roh.islands(fx.ctx, 0, 0, ind=(5, 30), snp_begin=4000, n_snps=12_500, min_snps=MIN_SNPS), part[4].astype(np.float64) / 30.0)
+
+
+def self_ibd_inside_runs(ctx, pos):
+    """the number of self-IBD segments (rows 2i, 2i+1 descend from one founder haplotype) that hold a SNP; each one's SNPs must lie
+    inside one run of individual i"""
+    seg = ctx.ibd_segments(0, 0, upper=True)
+    seg = seg[(seg["row_a"] % 2 == 0) & (seg["row_b"] == seg["row_a"] + 1)]
+    runs = ctx.roh_segments(0, 0)
+    first = runs["snp_first"].astype(np.int64); last = first + runs["n_snps"] - 1
+    checked = 0
+    for st, en, row_a, _ in seg.tolist():
+        j0, j1 = int(np.searchsorted(pos, st, "left")), int(np.searchsorted(pos, en, "left")) - 1      # the SNPs with st <= pos < en
+        if j1 < j0:
+            continue
+        mine = runs["ind"] == row_a // 2
+        assert ((first[mine] <= j0) & (last[mine] >= j1)).sum() == 1, f"individual {row_a // 2}: SNPs [{j0},{j1}] of an IBD segment are not inside one run"
+        checked += 1
+    return checked
+
+
+def test_self_ibd_segments_lie_inside_runs(gpu_lib):
+    """the same population bred without a mutation map: where an individual's two haplotypes descend from one founder haplotype they
+    carry the same alleles, so the SNPs of every self-IBD segment lie inside one run (no limits, max_gap_bp = 0)"""
+    ctx, cfg = build_bred(gpu_lib, with_mutation=False)
+    try:
+        assert self_ibd_inside_runs(ctx, cfg.snp_pos) >= 10
+    finally:
+        ctx.close()
+
+
+# ---- 3. the mutation overlay -----------------------------------------------------------------------------------------------------------
+def build_overlay(lib, upload=False):
+    """the population of test_gpu_snp_counts.test_counts_under_the_mutation_overlay: 150 individuals, 700 SNPs two base pairs apart,
+    0.2 mutations per 100 bp row and gamete, eight generations; SNP columns 10-12, 300-301 and 650-651 share a position"""
+    n, n_snps = 150, 700
+    cfg = SyntheticConfig(n, n_snps, chrom_bp=1400, map_step=100, rec_per_row=0.05, mut_per_row=0.2, n_cv=8, seed=4)
+    for k in (10, 11, 300, 650):
+        cfg.snp_pos[k + 1] = cfg.snp_pos[k]
+    ctx = lib.create(1, 1, 1)
+    cfg.apply_static(ctx)
+    if upload:
+        ctx.upload_founders(0, 0, synth_packed(7, 2 * n, n_snps), n_snps); ctx.upload_cv_founders(0, 0, 0, synth_packed(8, 2 * n, 8), 8)
+    else:
+        ctx.synth_founders(0, 0, 2 * n, 7); ctx.synth_cv_founders(0, 0, 0, 2 * n, 8)
+    sim = Simulation(ctx, 4, 1, True)
+    sim.ras_initial_human_gen0(0, n)
+    for _ in range(8):
+        sim.next_generation_rm(0, n)
+    return ctx, cfg
+
+
+def mutation_effects(ctx, pos):
+    """from the downloaded mutation lists and rows -> (splits, joins): SNPs with homozygous neighbours on both sides, now and by the
+    founder bits alone, that the founder bits make homozygous and a mutation heterozygous (it splits the run the founder bits would
+    join), or the other way round (it joins two).  The founder bit of a column is the row's bit, flipped where its position is in the
+    row's mutation list"""
+    muts, off = ctx.download_mutations(0, 0)
+    bits, _ = unpacked(ctx, 0, 0)
+    founder = bits.copy()
+    for r in range(bits.shape[0]):
+        founder[r] ^= np.isin(pos, muts[int(off[r]):int(off[r + 1])]).astype(np.uint8)
+    now, was = bits[0::2] == bits[1::2], founder[0::2] == founder[1::2]
+    around = now[:, :-2] & now[:, 2:] & was[:, :-2] & was[:, 2:]
+    return int((was[:, 1:-1] & ~now[:, 1:-1] & around).sum()), int((~was[:, 1:-1] & now[:, 1:-1] & around).sum())
+
+
+def test_runs_under_the_mutation_overlay(gpu_lib):
+    """Seed and rates are those of the SNP-count test, chosen with the CPU oracle under the same driver, where mutations split 349 runs
+    that the founder bits alone would join and join 249 pairs of runs; both must occur here, and every result must equal the truth on
+    the downloaded rows, which have the mutations applied"""
+    ctx, cfg = build_overlay(gpu_lib)
+    try:
+        splits, joins = mutation_effects(ctx, cfg.snp_pos)
+        print(f"mutations split {splits} runs and join {joins} pairs of runs")
+        assert splits >= 1 and joins >= 1
+        fx = Rows(gpu_lib, ctx, cfg.snp_pos)
+        for chunk in (0, 7):
+            ctx.dbg_output_chunk(chunk)
+            for lim in (dict(), dict(min_snps=3), dict(min_snps=2, min_bp=4, max_gap_bp=1), dict(max_gap_bp=2)):
+                for s0, ns in ((0, 700), (10, 3), (11, 1), (301, 350), (129, 571)):
+                    R.consistent(fx.check(f"overlay, chunk {chunk}", s0, ns, host=chunk == 0, **lim))
+            fx.check(f"overlay, chunk {chunk}", 0, 700, 17, 116, min_snps=3)
+    finally:
+        ctx.close()
+
+
+# ---- 4. state and refusals -------------------------------------------------------------------------------------------------------------
+def test_first_call_behind_a_migration(gpu_lib, oracle_lib):
+    """the mig2 fixture replayed (recorded couples, seeds and moves); its last step is a migration, so the logical row order differs
+    from the physical one and the ROH call is the first to ask for it"""
+    fx = helpers.load_fixture("mig2")
+    n_pop, nchr, nphen, ngen = int(fx["n_pop"]), int(fx["nchr"]), int(fx["nphen"]), int(fx["n_gen"])
+    ctx = gpu_lib.create(n_pop, nchr, nphen)
+    try:
+        helpers.setup_static(ctx, fx)
+        for ip, seed in enumerate(helpers.find_gen0_seeds(fx, oracle_lib)):
+            ctx.init_gen0(ip, len(fx[f"g0_pop{ip}_sex"]), seed)
+        for g in range(1, ngen + 1):
+            for ip in range(n_pop):
+                pre = f"g{g}_pop{ip}_"
+                ms = fx[pre + "mut_seeds"]
+                ctx.reproduce(ip, fx[pre + "couples"], int(fx[pre + "seed_reproduce"]), ms if len(ms) else None)
+                ctx.compute_ad(ip)
+            if f"g{g}_moves" in fx:
+                ctx.migrate(helpers.derive_moves(fx, g))
+        assert f"g{ngen}_moves" in fx
+        for ip in range(n_pop):
+            first = device(ctx, ip, 0)                                    # before anything else has asked for the population's rows
+            for ic in range(nchr):
+                rows = Rows(gpu_lib, ctx, fx[f"pop{ip}_chr{ic}_snp_pos"], ip, ic)
+                if ic == 0:
+                    R.same(first, rows.truth(), f"population {ip}, the first call")
+                n = rows.n
+                rows.check(f"mig2 population {ip} chromosome {ic}")
+                rows.check(f"mig2 population {ip} chromosome {ic}", 1, rows.L - 2, 1, n - 2, min_snps=2)
+    finally:
+        ctx.close()
+
+
+def test_capacity_rule(hand_built):
+    """count-only, exact, one short and two to spare through the raw call, on one pass and across passes: nothing at or beyond
+    out[capacity] is ever written"""
+    fx = hand_built
+    ctx = fx.ctx
+    f = ctx.L._f("roh_segments")
+    for chunk in (0, 7):
+        ctx.dbg_output_chunk(chunk)
+        try:
+            for (s0, ns, i0, ni), lim in (((0, R.L, 0, 40), {}), ((37, 8292, 3, 30), dict(min_snps=60, max_gap_bp=R.GAP))):
+                q = R.params(**lim)
+                R.capacity_cases(lambda out, cap, n: f(ctx.h, 0, 0, s0, ns, i0, ni, C.byref(q), out, cap, n), fx.truth(s0, ns, i0, ni, **lim)[5])
+            q = R.params(min_snps=R.L + 1)
+            rc, n, buf = R.raw(lambda out, cap, n: f(ctx.h, 0, 0, 0, R.L, 0, 40, C.byref(q), out, cap, n), 4)
+            assert rc == 0 and n == 0 and (buf == R.SENTINEL).all(), "a threshold beyond every run"
+        finally:
+            ctx.dbg_output_chunk(0)
+
+
+def test_empty_forms(hand_built):
+    fx = hand_built
+    ctx = fx.ctx
+    got = device(ctx, 0, 0, 5, 100, 7, 0)
+    assert len(got[4]) == 100 and not got[4].any() and len(got[0]) == 0 and len(got[5]) == 0, "n_ind == 0: zeros into cover"
+    got = device(ctx, 0, 0, R.L, 0, 3, 9)
+    assert all(len(v) == 9 and not v.any() for v in got[:4]) and len(got[4]) == 0 and len(got[5]) == 0, "n_snps == 0: zeros per individual"
+    f, q = ctx.L._f("roh_summary"), R.params()
+    guard = np.full(9, 7, dtype=np.uint32)
+    assert f(ctx.h, 0, 0, 5, 100, 7, 0, C.byref(q), guard, None, guard, None, None) == 0 and (guard == 7).all(), "n_ind == 0 touches nothing else"
+    assert f(ctx.h, 0, 0, 5, 100, 7, 9, C.byref(q), None, None, None, None, None) == 0, "every output may be NULL"
+    g = ctx.L._f("roh_segments")
+    for s, i in (((5, 0), (3, 9)), ((5, 100), (7, 0)), ((R.L, 0), (40, 0))):
+        rc, n, buf = R.raw(lambda out, cap, n: g(ctx.h, 0, 0, s[0], s[1], i[0], i[1], C.byref(q), out, cap, n), 4)
+        assert rc == 0 and n == 0 and (buf == R.SENTINEL).all()
+    # each output alone
+    want = fx.truth(37, 8292, 3, 30, min_snps=60)
+    for k in range(5):
+        outs = [None] * 5
+        outs[k] = np.empty_like(want[k])
+        qq = R.params(min_snps=60)
+        assert f(ctx.h, 0, 0, 37, 8292, 3, 30, C.byref(qq), *outs) == 0 and np.array_equal(outs[k], want[k]), R.NAMES[k]
+
+
+def test_refusals(gpu_lib):
+    """each gives the documented code and leaves the outputs and n_total untouched"""
+    n, n_snps = 50, 300
+    cfg = SyntheticConfig(n, n_snps, nchr=2, chrom_bp=2_000_000, map_step=20_000, rec_per_row=1e-3, n_cv=10, seed=2, with_mutation=False)
+    out = np.full(8 * ROH_SEGMENT_DTYPE.itemsize, R.SENTINEL, dtype=np.uint8)
+    vec = np.full(n, 7, dtype=np.uint32)
+    q = R.params()
+
+    def refused(ctx, code, word, chr=0, s=(0, n_snps), i=(0, n), params=True):
+        """both calls"""
+        p = C.byref(q) if params else None
+        rc = ctx.L._f("roh_summary")(ctx.h, 0, chr, s[0], s[1], i[0], i[1], p, vec, None, vec, None, None)
+        assert rc == code and word in ctx.L.last_error(), f"roh_summary: {rc} {ctx.L.last_error()}"
+        assert (vec == 7).all()
+        total = C.c_uint64(12345)
+        rc = ctx.L._f("roh_segments")(ctx.h, 0, chr, s[0], s[1], i[0], i[1], p, capi._p(out), 8, C.byref(total))
+        assert rc == code and word in ctx.L.last_error(), f"roh_segments: {rc} {ctx.L.last_error()}"
+        assert (out == R.SENTINEL).all() and total.value == 12345
+
+    def context(dense=True, mine=(0, 1), gen0=True):
+        ctx = gpu_lib.create(1, 2, 1)
+        if not dense:
+            ctx.set_dense_state(False)
+        for c in range(2):
+            ctx.set_rmap(0, c, cfg.rmap_bp, cfg.rmap_prob, cfg.bp_dist)
+        for c in mine:
+            ctx.set_snps(0, c, cfg.snp_pos)
+            bp, a, d = cfg.cv[0][c]
+            ctx.set_cvs(0, 0, c, bp, a, d, cfg.vd)
+        for c in range(2):
+            ctx.set_chr_active(c, c in mine)
+        for c in mine:
+            if dense:
+                ctx.synth_founders(0, c, 2 * n, 50 + c)
+            ctx.synth_cv_founders(0, 0, c, 2 * n, 60 + c)
+        if gen0:
+            ctx.init_gen0(0, n, 77)
+        return ctx
+
+    ctx = context(dense=False)
+    refused(ctx, -2, "no resident genotype planes")
+    ctx.close()
+    ctx = context(mine=(0,))
+    refused(ctx, -2, "not active", chr=1)
+    ctx.close()
+    ctx = context(gen0=False)
+    try:
+        refused(ctx, -2, "no current generation")
+        ctx.init_gen0(0, n, 77)
+        refused(ctx, -1, "SNPs", s=(n_snps - 1, 2))
+        refused(ctx, -1, "SNPs", s=(n_snps + 1, 0))
+        refused(ctx, -1, "individuals", i=(n - 1, 2))
+        refused(ctx, -1, "individuals", i=(n + 1, 0))
+        refused(ctx, -1, "params", params=False)
+        total = C.c_uint64(12345)
+        f = ctx.L._f("roh_segments")
+        assert f(ctx.h, 0, 0, 0, n_snps, 0, n, C.byref(q), capi._p(out), 8, None) == -1 and "n_total" in ctx.L.last_error()
+        assert f(ctx.h, 0, 0, 0, n_snps, 0, n, C.byref(q), None, 3, C.byref(total)) == -1 and "null output" in ctx.L.last_error()
+        assert (out == R.SENTINEL).all() and total.value == 12345
+        ctx.generation_begin(0, 12345, n)
+        try:
+            refused(ctx, -2, "pending")
+        finally:
+            ctx.generation_end()
+        for ic in range(2):
+            Rows(gpu_lib, ctx, cfg.snp_pos, 0, ic).check(f"after generation_end, chromosome {ic}", min_snps=2)
+    finally:
+        ctx.close()
