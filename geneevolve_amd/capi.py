@@ -219,6 +219,8 @@ ABI = {
     "list_stats": "int: ctx* int int ull*",
     "set_track_intervals": "int: ctx* int",
     "set_stitch_mode": "int: ctx* int",
+    "set_cv_stitch_form": "int: ctx* int",
+    "dbg_cv_stitch_launches": "int: ctx* ull*",
     "dbg_verify_planes": "int: ctx* int int u64* ull* ull*",
     "dbg_prefilter_sweep": "int: ctx* u32 u32 ull*",
     "dbg_output_chunk": "int: ctx* size",
@@ -1434,6 +1436,16 @@ class GevContext:
 
     def set_stitch_mode(self, mode):
         self._call("set_stitch_mode", mode)
+
+    def set_cv_stitch_form(self, form):
+        """CV-plane stitch kernel: 0 automatic (default), 1 always k_stitch_small, 2 k_stitch_small8 where it is legal"""
+        self._call("set_cv_stitch_form", form)
+
+    def dbg_cv_stitch_launches(self):
+        """(launches of k_stitch_small, launches of k_stitch_small8) since the context was created"""
+        out = (C.c_ulonglong * 2)()
+        self._call("dbg_cv_stitch_launches", out)
+        return int(out[0]), int(out[1])
 
     def set_track_intervals(self, on):
         self._call("set_track_intervals", 1 if on else 0)

@@ -1019,6 +1019,186 @@ __global__ void __launch_bounds__(SMALL_THREADS) k_stitch_small(const CvWork* __
         for (u32 col = threadIdx.x; col < 1024; col += SMALL_THREADS) out[col] = (uint16_t)s_cnt[(col & 31u) * 32u + (col >> 5)];   // (<= 256 rows per block)
     }
 }
+// The same stitch with EIGHT lanes per output row, for planes whose sub-rows are whole 16-byte chunks (sub_w32 <= 32 and a multiple
+// of 4, stride a multiple of 4, base 16-byte aligned: enqueue_cv_planes decides per launch).  Lane (r, q) = (lane >> 3, lane & 7) of a
+// wave owns words 4q .. 4q+3 of every sub-row of the wave's row r: one 16-byte load and one 16-byte store per sub-row.  A wave
+// therefore has 8 rows in flight where k_stitch_small has 2, a workgroup of 512 threads covers 64 rows per round and its 256 rows
+// are FOUR rounds instead of 16.  A lane whose four mask words are all 0 or all ~0 loads one parental row only (with about one
+// crossover per gamete that is nearly every lane).  Same grid, same LDS copy of the position grid, same records read, same rows
+// and the same partial counts written as k_stitch_small.
+//   SMALL8_BATCH rounds are started together: their descriptor loads are issued first, then their breakpoint loads, then their
+// searches run as one loop (one independent LDS read per round and bisection step), then the row loads.  The library is built with
+// 1: at 64 VGPRs all workgroups of config 2's grid are resident at once (4 per CU), and that is worth more than the overlapped
+// chains -- alone the kernel takes the same 36 us with 1 round (64 VGPRs) as with 4 (128 VGPRs, half the workgroups resident),
+// beside the generation's other streams the small footprint is in front.
+//   Column counts: a lane counts its four allele words over the four rounds bit-sliced (3 planes: <= 4), the eight row groups of a
+// wave are added up bit-sliced over shuffles (6 planes: <= 32), every wave leaves its planes in LDS and one thread per two columns
+// adds the eight waves up: no LDS atomics.
+#define SMALL8_THREADS 512
+#define SMALL8_ROUNDS (SMALL_ROWS_PER_BLOCK / (SMALL8_THREADS / 8))
+#ifndef SMALL8_BATCH
+#define SMALL8_BATCH 1                  // rounds whose chains are started together (1, 2 or 4)
+#endif
+static_assert(SMALL8_ROUNDS == 4 && SMALL8_THREADS == 512 && SMALL8_ROUNDS % SMALL8_BATCH == 0, "k_stitch_small8: 3 count planes per lane and one thread per two columns assume 4 rounds of 64 rows");
+// #{a[i] < v[j]} for a batch of values at once: the same trip count for every lane and value (it depends on n only), so the
+// batch's chains of dependent reads run side by side
+template <typename P>
+__device__ __forceinline__ void lower_bound_batch_u64(P a, u32 n, const u64 (&v)[SMALL8_BATCH], u32 (&out)[SMALL8_BATCH])
+{
+    u32 base[SMALL8_BATCH];
+#pragma unroll
+    for (int j = 0; j < SMALL8_BATCH; j++) base[j] = 0;
+    u32 len = n;
+    while (len > 1) {
+        const u32 half = len >> 1;
+#pragma unroll
+        for (int j = 0; j < SMALL8_BATCH; j++) base[j] += a[base[j] + half - 1] < v[j] ? half : 0u;
+        len -= half;
+    }
+#pragma unroll
+    for (int j = 0; j < SMALL8_BATCH; j++) out[j] = base[j] + ((len == 1 && a[base[j]] < v[j]) ? 1u : 0u);
+}
+// p[0 .. N-1] (bit-sliced counters) += those of the lane `lane ^ xm`: N + 1 planes afterwards, the same in both lanes
+template <int N>
+__device__ __forceinline__ void bitsliced_add_xor(u32 (&p)[6], int xm)
+{
+    u32 carry = 0;
+#pragma unroll
+    for (int b = 0; b < N; b++) {
+        const u32 mine = p[b], other = (u32)__shfl_xor((int)mine, xm), s = mine ^ other;
+        p[b] = s ^ carry;
+        carry = (mine & other) | (carry & s);
+    }
+    p[N] = carry;
+}
+__global__ void __launch_bounds__(SMALL8_THREADS, 8) k_stitch_small8(const CvWork* __restrict__ Vt, u32 nsub, size_t n_rows_out, int nchr, SampleDev sd, u32 pos_lds, int count_cols)
+{
+    extern __shared__ u64 s_pos[];                                        // min(largest CV grid of the launch, SMALL_POS_LDS) entries
+    __shared__ uint4 s_planes[32][SMALL8_THREADS / 64][2];                // [word][wave]: the wave's six count planes of the word (two unused)
+    const CvWork& v = Vt[blockIdx.y];
+    u32* __restrict__ dst = v.cvp_alt; const u32* __restrict__ src = v.cvp_cur;
+    const u32 stride_w32 = v.stride_w32, sub_w32 = v.sub_w32, Cn = v.C;
+    const int chr = v.chr;
+    const bool in_lds = Cn <= pos_lds;
+    if (in_lds) for (u32 e = threadIdx.x; e < Cn; e += SMALL8_THREADS) s_pos[e] = v.pos_sorted[e];
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, q = lane & 7u, g0 = lane & 56u;     // g0: first lane of the row's group
+    const u32 w0 = 4u * q;                                                // first owned word of a sub-row
+    const bool owns = w0 < sub_w32;                                       // (sub_w32 % 4 == 0: all four words or none)
+    const size_t row0 = (size_t)blockIdx.x * SMALL_ROWS_PER_BLOCK + wave * 8u + (lane >> 3);
+    u32 cnt[4][3];                                                        // bit-sliced counters (<= 4 rounds) of the lane's allele words
+#pragma unroll
+    for (int e = 0; e < 4; e++) cnt[e][0] = cnt[e][1] = cnt[e][2] = 0;
+#pragma unroll 1
+    for (u32 r0 = 0; r0 < SMALL8_ROUNDS; r0 += SMALL8_BATCH) {
+    if (r0 && (size_t)blockIdx.x * SMALL_ROWS_PER_BLOCK + (size_t)r0 * (SMALL8_THREADS / 8) >= n_rows_out) break;      // block-uniform
+    // 1. the descriptors of the batch's rounds (dead rows read those of row 0 and take k = 0: their lanes take part in the shuffles)
+    bool live[SMALL8_BATCH]; u32 par[SMALL8_BATCH], st[SMALL8_BATCH], kk[SMALL8_BATCH], off[SMALL8_BATCH];
+#pragma unroll
+    for (int j = 0; j < SMALL8_BATCH; j++) {
+        const size_t row = row0 + (size_t)(r0 + j) * (SMALL8_THREADS / 8);
+        live[j] = row < n_rows_out;
+        const u32 i = live[j] ? (u32)(row >> 1) : 0u, s = (u32)(row & 1);
+        const size_t G = 2 * ((size_t)i * nchr + chr) + s;
+        par[j] = s ? sd.mother[i] : sd.father[i];
+        st[j] = sd.start[G];
+        kk[j] = sd.k[G];
+        off[j] = sd.bk_off[G];
+    }
+    // 2. breakpoint q of the row of every round of the batch
+    u64 bv[SMALL8_BATCH]; u32 kmax[SMALL8_BATCH];
+#pragma unroll
+    for (int j = 0; j < SMALL8_BATCH; j++) {
+        if (!live[j]) kk[j] = 0;
+        bv[j] = 0;
+        if (q < kk[j]) bv[j] = sd.bk[(size_t)off[j] + q];
+        u32 km = kk[j];                                                   // wave-uniform trip count: the largest k of the wave's rows
+        km = max(km, (u32)__shfl_xor((int)km, 8)); km = max(km, (u32)__shfl_xor((int)km, 16)); km = max(km, (u32)__shfl_xor((int)km, 32));
+        kmax[j] = (u32)__builtin_amdgcn_readfirstlane((int)km);
+    }
+    if (r0 == 0) __syncthreads();                                         // s_pos is staged
+    // 3. breakpoints -> column indices, then the toggle masks of the four owned words
+    u32 id[SMALL8_BATCH];
+    if (in_lds) lower_bound_batch_u64((const u64*)s_pos, Cn, bv, id); else lower_bound_batch_u64(v.pos_sorted, Cn, bv, id);
+    u32 mask[SMALL8_BATCH][4];
+#pragma unroll
+    for (int j = 0; j < SMALL8_BATCH; j++) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) mask[j][e] = 0;
+        u32 idq = q < kk[j] ? id[j] : 0xffffffffu;                        // "never": contributes nothing below
+        for (u32 m0 = 0; m0 < kmax[j]; m0 += 8) {
+            if (m0) {                                                     // k > 8: breakpoints q + 8, q + 16, ... (rare)
+                idq = 0xffffffffu;
+                if (m0 + q < kk[j]) {
+                    const u64 b = sd.bk[(size_t)off[j] + m0 + q];
+                    idq = in_lds ? lower_bound_u64((const u64*)s_pos, Cn, b) : lower_bound_u64(v.pos_sorted, Cn, b);
+                }
+            }
+            const u32 nm = min(8u, kmax[j] - m0);
+            for (u32 m = 0; m < nm; m++) {
+                const u32 x = (u32)__shfl((int)idq, (int)(g0 + m));
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const u32 bit0 = (w0 + e) * 32u;
+                    u32 tt = 0;
+                    if (x <= bit0) tt = 0xffffffffu; else if (x < bit0 + 32u) tt = 0xffffffffu << (x - bit0);
+                    mask[j][e] ^= tt;
+                }
+            }
+        }
+    }
+    // 4. the rows: one parental row where the lane's masks agree, both where they are mixed
+    for (u32 sub = 0; sub < nsub; sub++) {
+        const u32 wq = sub * sub_w32 + w0;
+        uint4 a[SMALL8_BATCH], b[SMALL8_BATCH];
+#pragma unroll
+        for (int j = 0; j < SMALL8_BATCH; j++) {
+            const bool all_b = (mask[j][0] & mask[j][1] & mask[j][2] & mask[j][3]) == 0xffffffffu;
+            const bool mixed = !all_b && (mask[j][0] | mask[j][1] | mask[j][2] | mask[j][3]) != 0u;
+            const u32* __restrict__ A = src + (size_t)(2 * par[j] + st[j]) * stride_w32;
+            const u32* __restrict__ B = src + (size_t)(2 * par[j] + (st[j] ^ 1u)) * stride_w32;
+            a[j] = make_uint4(0, 0, 0, 0);
+            if (live[j] && owns) a[j] = *(const uint4*)((all_b ? B : A) + wq);
+            b[j] = a[j];
+            if (live[j] && owns && mixed) b[j] = *(const uint4*)(B + wq);
+        }
+#pragma unroll
+        for (int j = 0; j < SMALL8_BATCH; j++) {
+            uint4 o;
+            o.x = (a[j].x & ~mask[j][0]) | (b[j].x & mask[j][0]); o.y = (a[j].y & ~mask[j][1]) | (b[j].y & mask[j][1]);
+            o.z = (a[j].z & ~mask[j][2]) | (b[j].z & mask[j][2]); o.w = (a[j].w & ~mask[j][3]) | (b[j].w & mask[j][3]);
+            if (live[j] && owns) {
+                const size_t row = row0 + (size_t)(r0 + j) * (SMALL8_THREADS / 8);
+                *(uint4*)(dst + row * stride_w32 + wq) = o;
+            }
+            if (count_cols && sub == 0) {                                 // cnt += o, bit-sliced (o == 0 in lanes that own nothing)
+                const u32 ow[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+                for (int e = 0; e < 4; e++) { u32 c = ow[e], t1; t1 = cnt[e][0] & c; cnt[e][0] ^= c; c = t1; t1 = cnt[e][1] & c; cnt[e][1] ^= c; c = t1; cnt[e][2] ^= c; }
+            }
+        }
+    }
+    }
+    if (count_cols) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            u32 p[6] = {cnt[e][0], cnt[e][1], cnt[e][2], 0, 0, 0};
+            bitsliced_add_xor<3>(p, 8); bitsliced_add_xor<4>(p, 16); bitsliced_add_xor<5>(p, 32);      // the wave's 8 row groups: <= 32
+            if (lane < 8u) { s_planes[w0 + e][wave][0] = make_uint4(p[0], p[1], p[2], p[3]); s_planes[w0 + e][wave][1] = make_uint4(p[4], p[5], 0, 0); }
+        }
+        __syncthreads();
+        const u32 word = threadIdx.x >> 4, b0 = (threadIdx.x & 15u) * 2u;     // columns 2 * threadIdx.x and + 1: bits b0, b0 + 1 of `word`
+        u32 n0 = 0, n1 = 0;
+#pragma unroll
+        for (int wv = 0; wv < SMALL8_THREADS / 64; wv++) {
+            const uint4 lo = s_planes[word][wv][0], hi = s_planes[word][wv][1];
+            const u32 pl[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
+#pragma unroll
+            for (int b = 0; b < 6; b++) { n0 += ((pl[b] >> b0) & 1u) << b; n1 += ((pl[b] >> (b0 + 1u)) & 1u) << b; }
+        }
+        u32* __restrict__ out = (u32*)(v.partial + (size_t)blockIdx.x * 1024);
+        out[threadIdx.x] = n0 | (n1 << 16);                               // (<= 256 rows per block: each count fits the u16)
+    }
+}
 // The generation's NEW mutations (ras_add_mutation, :2497-2552) that fall on a CV position, applied to the offspring plane behind
 // k_stitch_small: ras_find_cv reads !founder where the position is in the covering part's mutation_pos (:2770-2775), so the
 // resolved allele flips -- unless the position already was in that set (a set: a second hit changes nothing).  "Already" means:

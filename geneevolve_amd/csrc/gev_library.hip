@@ -275,6 +275,7 @@ struct gev_ctx {
         size_t nseg_max = 1, cv_used_max = 0; u32 cv_max = 0;    // launch shapes of the generation (enqueue_tables)
         bool pool_rebuild = false;                                                            // this attempt rebuilds the free list of the segment pool
         bool cv_count_fused = false;                                                          // k_stitch_small also counts the alleles per CV column (every grid <= 1024 columns)
+        bool cv_lanes8 = false;                                                               // every CV plane of the launch has the shape k_stitch_small8 takes (enqueue_tables)
         hipEvent_t ev_fork = nullptr, ev_aux = nullptr, ev_lists = nullptr, ev_forked = nullptr;   // joins of the attempt's side streams
         hipEvent_t ev_recs = nullptr, ev_pool = nullptr;                                        // sampling records complete on S (for X); unit table, work list and their counters complete on X
         hipEvent_t ev_small_done = nullptr, ev_stitch_done = nullptr, t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_status = nullptr, ev_sampled = nullptr;   // the generation's status block (and A/D results) have arrived on the host
@@ -316,6 +317,8 @@ struct gev_ctx {
     int ad_host_set_pop = -1;                                // population whose raw A/D totals on the device were supplied by gev_set_ad (locus-split: all-reduced)
     bool eager_ad = true;                                    // compute A/D inside gev_reproduce (same enqueue, same sync)
     int stitch_mode = 0;           // 0 = work-list form (production, k_stitch_segments), 1 = gamete-major (k_stitch_rows)
+    int cv_stitch_form = 0;        // CV-plane stitch (gev_set_cv_stitch_form): 0 = by the planes' shape, 1 = always k_stitch_small, 2 = k_stitch_small8 where it is legal
+    unsigned long long cv_stitch_launches[2] = {0, 0};      // launches of k_stitch_small / k_stitch_small8 (gev_dbg_cv_stitch_launches)
     bool sample_batched = true;               // K1-K3 as eight tasks per wave (gev_sample8.h); GEV_SAMPLE_BATCHED=0: one task per wave
     bool chain_wg = true;                     // no mutation map: a workgroup per link of the gamete chain (k_rec_chain_wg); GEV_CHAIN_WG=0: the one-wave form (k_rec_chain)
     int ad_path = 0;                          // the A/D kernel launched last (gev_dbg_ad_path): AD_PATH_*, + AD_PATH_FROM_COUNTS when it built its terms from the column counts itself
@@ -1520,6 +1523,10 @@ static int enqueue_tables(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
     const u32 nsub = 1 + c->rp_bits;
     sc.cv_count_fused = true;
     for (const CvWork& v : vw) { sc.cv_used_max = std::max<size_t>(sc.cv_used_max, (size_t)v.sub_w32 * nsub); sc.cv_count_fused &= v.sub_w32 <= 32; if (v.C <= SMALL_POS_LDS) sc.cv_max = std::max(sc.cv_max, v.C); }   // LDS copy of the CV grid: sized for the launch, not for the worst case (occupancy)
+    // eight lanes per row (k_stitch_small8): every sub-row of every plane is made of whole, aligned 16-byte chunks and at most 32 words long
+    sc.cv_lanes8 = !vw.empty();
+    for (const CvWork& v : vw)
+        sc.cv_lanes8 &= v.sub_w32 <= 32 && v.sub_w32 % 4 == 0 && v.stride_w32 % 4 == 0 && (uintptr_t)v.cvp_alt % 16 == 0 && (uintptr_t)v.cvp_cur % 16 == 0;
     if (sc.n_chrwork) {
         GEVC(upload_table_cached(c, sc.chrwork, sc.chrwork_shadow, cw.data(), cw.size(), st));
         GEVC(upload_table_cached(c, sc.cvwork, sc.cvwork_shadow, vw.data(), vw.size(), st));
@@ -1598,7 +1605,11 @@ static int enqueue_cv_planes(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, 
     SampleDev sd = make_sd(c, sc, T);
     const CvWork* Vt = sc.cvwork;
     const dim3 grid((unsigned)ceil_div(rows, SMALL_ROWS_PER_BLOCK), sc.n_cvwork); const size_t lds = (size_t)sc.cv_max * sizeof(u64); const u32 nsub = 1u + c->rp_bits;
-    hipLaunchKernelGGL((k_stitch_small<512>), grid, dim3(512), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
+    // two forms of one launch contract: eight lanes per row where every plane of the launch has the shape for it, else a half-wave per row
+    const bool lanes8 = sc.cv_lanes8 && c->cv_stitch_form != 1;
+    if (lanes8) hipLaunchKernelGGL(k_stitch_small8, grid, dim3(SMALL8_THREADS), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
+    else hipLaunchKernelGGL((k_stitch_small<512>), grid, dim3(512), lds, st, Vt, nsub, rows, nchr, sd, sc.cv_max, (int)count_cols);
+    c->cv_stitch_launches[lanes8 ? 1 : 0]++;
     if (count_cols && sum_counts) {
         GEVC(c->d_flag.ensure(16, st));                              // (the launch resets the NaN flag of the A/D kernel behind it)
         const unsigned nblk = (unsigned)grid.x, slices = std::min((nblk + 7u) / 8u, 128u);      // eight partial blocks per thread, as k_cv_finish
@@ -5515,6 +5526,8 @@ int gev_set_overlap(gev_ctx* c, int on)
     c->serialize = on == 0;
     return GEV_OK;
 }
+int gev_set_cv_stitch_form(gev_ctx* c, int form) { if (c && c->pend.active) return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first"); if (!c || form < 0 || form > 2) return fail(GEV_EINVAL, "CV stitch form must be 0 (automatic), 1 (a half-wave per row) or 2 (eight lanes per row where the planes allow it)"); c->cv_stitch_form = form; return GEV_OK; }
+int gev_dbg_cv_stitch_launches(gev_ctx* c, unsigned long long launches[2]) { if (!c || !launches) return fail(GEV_EINVAL, "null argument"); launches[0] = c->cv_stitch_launches[0]; launches[1] = c->cv_stitch_launches[1]; return GEV_OK; }
 int gev_set_stitch_mode(gev_ctx* c, int mode) { if (c && c->pend.active) return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first"); if (!c || mode < 0 || mode > 1) return fail(GEV_EINVAL, "stitch mode must be 0 (work list of the segments to write) or 1 (gamete-major)"); c->stitch_mode = mode; return GEV_OK; }
 
 // ---- diagnostics (tests only; no simulation state involved) --------------------------------

@@ -885,6 +885,14 @@ int gev_set_track_intervals(gev_ctx*, int on);
 /* dense-stitch kernel: 0 = k_stitch_segments (default: one workgroup per entry of the list of segments to write), 1 = gamete-major
  * k_stitch_rows (every output row finds its own segments and sources).  Same results; kept for parity cross-checks. */
 int gev_set_stitch_mode(gev_ctx*, int mode);
+/* CV-plane stitch kernel of the following generations: 0 = automatic (default: k_stitch_small8, eight lanes per offspring row, when
+ * every CV plane of the launch has sub-rows of at most 32 words that are a multiple of 4 words, a row stride that is a multiple of 4
+ * words and a 16-byte aligned base; k_stitch_small, a half-wave per row, otherwise), 1 = always k_stitch_small, 2 = k_stitch_small8
+ * where it is legal (today the same choice as 0).  Same rows and column counts either way; kept for parity cross-checks.  Refused
+ * while a generation is pending.  gev_dbg_cv_stitch_launches: launches[0] / [1] = launches of k_stitch_small / k_stitch_small8 since
+ * the context was created, so that a test can assert which form it ran. */
+int gev_set_cv_stitch_form(gev_ctx*, int form);
+int gev_dbg_cv_stitch_launches(gev_ctx*, unsigned long long launches[2]);
 
 /* ---- diagnostics: RNG building blocks exposed for the parity tests (no simulation state) ----
  * gev_dbg_tables / gev_dbg_threshold / gev_dbg_canonical run on the host (table and threshold
