@@ -348,14 +348,14 @@ def _ibd_outs(n_a, n_b, want=(True, True, True)):
     return tuple(np.empty(shape, dtype=dt) if w else None for dt, w in zip((np.uint64, np.uint32, np.uint64), want))
 
 
-def _ibd_segment_list(call, upper):
-    """the two calls of the segment lists: call(pairs, out, capacity, n_total) counts with (None, 0), then fills an exactly sized array"""
-    pairs = IBD_UPPER if upper else IBD_ALL_PAIRS
+def _record_list(call, dtype):
+    """the two calls of a record list (IBD segments, runs of homozygosity): call(out, capacity, n_total) counts with (None, 0), then
+    fills an exactly sized array of dtype"""
     n = C.c_uint64()
-    call(pairs, None, 0, C.byref(n))
-    out = np.zeros(n.value, dtype=SEGMENT_DTYPE)
+    call(None, 0, C.byref(n))
+    out = np.zeros(n.value, dtype=dtype)
     if n.value:
-        call(pairs, out, n.value, C.byref(n))
+        call(out, n.value, C.byref(n))
         assert n.value == len(out), "the list changed between the count and the fill"
     return out
 
@@ -369,17 +369,6 @@ def _roh_outs(n_ind, n_snps, want_cover=True):
     n_ind, n_snps = max(n_ind, 0), max(n_snps, 0)
     return (np.empty(n_ind, dtype=np.uint32), np.empty(n_ind, dtype=np.uint64), np.empty(n_ind, dtype=np.uint32), np.empty(n_ind, dtype=np.uint64),
             np.empty(n_snps, dtype=np.uint32) if want_cover else None)
-
-
-def _roh_segment_list(call):
-    """the two calls of the run list: call(out, capacity, n_total) counts with (None, 0), then fills an exactly sized array"""
-    n = C.c_uint64()
-    call(None, 0, C.byref(n))
-    out = np.zeros(n.value, dtype=ROH_SEGMENT_DTYPE)
-    if n.value:
-        call(out, n.value, C.byref(n))
-        assert n.value == len(out), "the list changed between the count and the fill"
-    return out
 
 
 def pack_names(names):
@@ -553,8 +542,8 @@ class GevLibrary:
         with row_a < row_b) needs"""
         parts_a = _arr(parts_a, PART_DTYPE); off_a = _arr(off_a, np.uint64)
         parts_b = parts_a if parts_b is None else _arr(parts_b, PART_DTYPE); off_b = off_a if off_b is None else _arr(off_b, np.uint64)
-        f = self._f("dbg_ibd_segments_host")
-        return _ibd_segment_list(lambda pairs, out, cap, n: self.check(f(parts_a, off_a, len(off_a) - 1, parts_b, off_b, len(off_b) - 1, int(min_bp), pairs, out, cap, n)), upper)
+        f, pairs = self._f("dbg_ibd_segments_host"), IBD_UPPER if upper else IBD_ALL_PAIRS
+        return _record_list(lambda out, cap, n: self.check(f(parts_a, off_a, len(off_a) - 1, parts_b, off_b, len(off_b) - 1, int(min_bp), pairs, out, cap, n)), SEGMENT_DTYPE)
 
     def dbg_roh_host(self, bits, L, pos, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0, want_cover=True, want_list=True):
         """the library's run-of-homozygosity word logic compiled for the host (no device needed) -> (n_roh, roh_bp, roh_snps, max_bp, cover,
@@ -572,7 +561,7 @@ class GevLibrary:
         if not want_list:
             self.check(f(*head, *outs, None, 0, None))
             return (*outs, None)
-        seg = _roh_segment_list(lambda out, cap, n: self.check(f(*head, *outs, out, cap, n)))
+        seg = _record_list(lambda out, cap, n: self.check(f(*head, *outs, out, cap, n)), ROH_SEGMENT_DTYPE)
         return (*outs, seg)
 
     def dbg_format_interval_text_host(self, parts, hap_offsets, ids, chr_label, names, header=True, ind_begin=0, n_ind=None, out_bytes=None):
@@ -1080,6 +1069,13 @@ class GevContext:
         self._call("pop_size", pop, C.byref(n))
         return n.value
 
+    # a count given as None: the rest of the SNPs of (pop, chr) / of the individuals (per_individual 2: haplotype rows) of pop from `begin` on
+    def _rest_snps(self, pop, chr, begin, n):
+        return self._nsnp[(pop, chr)] - begin if n is None else n
+
+    def _rest_ind(self, pop, begin, n, per_individual=1):
+        return per_individual * self.pop_size(pop) - begin if n is None else n
+
     def dbg_output_chunk(self, max_units=0):
         """test hook: the following output calls stage at most max_units rows / individuals / SNPs (SNPs in 64s) per pass; 0 = byte budgets"""
         self._call("dbg_output_chunk", max_units)
@@ -1109,23 +1105,23 @@ class GevContext:
     def snp_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
         """-> (n_het, n_hom_alt), uint32 [n_snps]: per SNP of the range, the individuals of [ind_begin, +n_ind) that are heterozygous /
         carry allele 1 twice, counted on the device from the resident rows (mutations applied)"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         het = np.empty(max(n_snps, 0), dtype=np.uint32); hom = np.empty(max(n_snps, 0), dtype=np.uint32)
         self._call("snp_genotype_counts", pop, chr, snp_begin, n_snps, ind_begin, n_ind, het, hom)
         return het, hom
 
     def allele_freq(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None):
         """-> float64 [n_snps]: frequency of allele 1 among the 2 * n_ind haplotypes of the individuals of the range"""
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         het, hom = self.snp_genotype_counts(pop, chr, snp_begin, n_snps, ind_begin, n_ind)
         return (het.astype(np.float64) + 2.0 * hom) / (2.0 * n_ind)
 
     def ind_genotype_counts(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, weight=None):
         """-> (n_het, n_hom_alt) uint32 [n_ind], or with weight (n_snps uint32) (n_het, n_hom_alt, wsum), wsum uint64 [n_ind] =
         sum_j weight[j] * g_ij: per individual of the range over the SNPs of the range, counted on the device (mutations applied)"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         het = np.empty(max(n_ind, 0), dtype=np.uint32); hom = np.empty(max(n_ind, 0), dtype=np.uint32)
         ws = None
         if weight is not None:
@@ -1139,9 +1135,9 @@ class GevContext:
         """-> (n_hethet, n_opphom, dot), uint32 [n_a][n_b]: for every pair (a_begin + i, b_begin + k) of the population over the SNPs of the
         range, the loci where both are heterozygous, the loci where one is 0/0 and the other 1/1, and sum_j g_ij g_kj; exact integer
         products on the device's matrix cores from the resident rows (mutations applied)"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_a = self.pop_size(pop) - a_begin if n_a is None else n_a
-        n_b = self.pop_size(pop) - b_begin if n_b is None else n_b
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_a = self._rest_ind(pop, a_begin, n_a)
+        n_b = self._rest_ind(pop, b_begin, n_b)
         mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(3)]
         self._call("pair_genotype_counts", pop, chr, snp_begin, n_snps, a_begin, n_a, b_begin, n_b, *mats)
         return tuple(mats)
@@ -1152,9 +1148,9 @@ class GevContext:
         per SNP of each side, uint32: allele-1 count, heterozygous and homozygous-alt individuals.  Exact integer products on the device's
         matrix cores from the current generation (mutations applied)"""
         chr_b = chr_a if chr_b is None else chr_b
-        n_a = self._nsnp[(pop, chr_a)] - a_begin if n_a is None else n_a
-        n_b = self._nsnp[(pop, chr_b)] - b_begin if n_b is None else n_b
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_a = self._rest_snps(pop, chr_a, a_begin, n_a)
+        n_b = self._rest_snps(pop, chr_b, b_begin, n_b)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         mats = [np.empty((max(n_a, 0), max(n_b, 0)), dtype=np.uint32) for _ in range(2)]
         vecs = [np.empty(max(n, 0), dtype=np.uint32) for n in (n_a, n_a, n_a, n_b, n_b, n_b)]
         self._call("ld_counts", pop, chr_a, a_begin, n_a, chr_b, b_begin, n_b, ind_begin, n_ind, *mats, *vecs)
@@ -1164,8 +1160,8 @@ class GevContext:
         """-> (score_q40 uint64 [n_snps], n_terms uint32 [n_snps]): for SNP snp_begin + t the sum over SNPs [win_lo[t], win_hi[t]) of the
         chromosome of the r^2 quantum llrint(r^2 * 2^40) (haplotype r^2, or genotype r^2) over individuals [ind_begin, +n_ind), and the
         window's SNPs that are polymorphic among them; the band is walked and reduced on the device"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         lo = _arr(win_lo, np.uint32); hi = _arr(win_hi, np.uint32)
         assert lo.shape == hi.shape == (max(n_snps, 0),), "one window per SNP of the range"
         score = np.empty(max(n_snps, 0), dtype=np.uint64); terms = np.empty(max(n_snps, 0), dtype=np.uint32)
@@ -1177,8 +1173,8 @@ class GevContext:
         [n_traits][n_snps]: gsum = sum_i g_ij q[t][i], hetsum = the sum of q[t][i] over the heterozygous individuals; uint32 [n_snps]: the
         heterozygous and homozygous-alt individuals.  trait: int32 [n_traits][n_ind] quanta, |q| <= 2^30 (or [n_ind] for one trait), entry
         i = individual ind_begin + i.  Exact integer products on the device's matrix cores from the current generation (mutations applied)"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         trait = _traits(trait, n_ind)
         outs = _trait_sum_outs(trait.shape[0], n_snps)
         self._call("snp_trait_sums", pop, chr, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs)
@@ -1190,8 +1186,8 @@ class GevContext:
         their summed length, their number and the longest.  Walked on the device from the ancestry interval lists (works without genotype
         planes).  want: an output that is not wanted goes in as NULL and comes back as None"""
         pop_b = pop_a if pop_b is None else pop_b
-        n_a = 2 * self.pop_size(pop_a) - a_begin if n_a is None else n_a
-        n_b = 2 * self.pop_size(pop_b) - b_begin if n_b is None else n_b
+        n_a = self._rest_ind(pop_a, a_begin, n_a, 2)
+        n_b = self._rest_ind(pop_b, b_begin, n_b, 2)
         outs = _ibd_outs(n_a, n_b, want)
         self._call("ibd_sharing", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), *outs)
         return outs
@@ -1201,9 +1197,10 @@ class GevContext:
         which row a_begin + i of pop_a and row b_begin + k of pop_b (None: pop_a) descend from the same founder haplotype, [st, en), the
         rows absolute in their populations.  upper: only pairs with row_a < row_b (one population).  A count call, then a fill call"""
         pop_b = pop_a if pop_b is None else pop_b
-        n_a = 2 * self.pop_size(pop_a) - a_begin if n_a is None else n_a
-        n_b = 2 * self.pop_size(pop_b) - b_begin if n_b is None else n_b
-        return _ibd_segment_list(lambda pairs, out, cap, n: self._call("ibd_segments", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), pairs, out, cap, n), upper)
+        n_a = self._rest_ind(pop_a, a_begin, n_a, 2)
+        n_b = self._rest_ind(pop_b, b_begin, n_b, 2)
+        pairs = IBD_UPPER if upper else IBD_ALL_PAIRS
+        return _record_list(lambda out, cap, n: self._call("ibd_segments", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), pairs, out, cap, n), SEGMENT_DTYPE)
 
     def roh_summary(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0, want_cover=True):
         """-> (n_roh, roh_bp, roh_snps, max_bp, cover): per individual of [ind_begin, +n_ind) over its qualifying runs of homozygosity among
@@ -1212,8 +1209,8 @@ class GevContext:
         individuals with the SNP inside a qualifying run.  A run: consecutive SNPs at which the two haplotypes agree (mutations applied),
         broken where neighbouring SNPs lie more than max_gap_bp apart; it qualifies with >= min_snps SNPs and >= min_bp base pairs (0 =
         no limit, each).  Scanned on the device from the current generation's rows"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         q = _roh_params(min_snps, min_bp, max_gap_bp)
         outs = _roh_outs(n_ind, n_snps, want_cover)
         self._call("roh_summary", pop, chr, snp_begin, n_snps, ind_begin, n_ind, C.byref(q), *outs)
@@ -1223,15 +1220,15 @@ class GevContext:
         """-> ROH_SEGMENT_DTYPE records (st, en, ind, snp_first, n_snps, reserved), sorted by (ind, snp_first): the qualifying runs of
         roh_summary themselves, st = pos[snp_first] and en = pos[snp_first + n_snps - 1] both inclusive, ind and snp_first absolute.  A
         count call, then a fill call"""
-        n_snps = self._nsnp[(pop, chr)] - snp_begin if n_snps is None else n_snps
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         q = _roh_params(min_snps, min_bp, max_gap_bp)
-        return _roh_segment_list(lambda out, cap, n: self._call("roh_segments", pop, chr, snp_begin, n_snps, ind_begin, n_ind, C.byref(q), out, cap, n))
+        return _record_list(lambda out, cap, n: self._call("roh_segments", pop, chr, snp_begin, n_snps, ind_begin, n_ind, C.byref(q), out, cap, n), ROH_SEGMENT_DTYPE)
 
     def ancestry_bp(self, pop, chr, row_begin=0, n_rows=None):
         """-> (bp uint64 [n_rows][n_pop], n_parts uint32 [n_rows]): the base pairs of every haplotype row covered by parts of each root
         population, and the length of the row's interval list"""
-        n_rows = 2 * self.pop_size(pop) - row_begin if n_rows is None else n_rows
+        n_rows = self._rest_ind(pop, row_begin, n_rows, 2)
         bp = np.empty((max(n_rows, 0), self.n_pop), dtype=np.uint64); n_parts = np.empty(max(n_rows, 0), dtype=np.uint32)
         self._call("ancestry_bp", pop, chr, row_begin, n_rows, bp, n_parts)
         return bp, n_parts
@@ -1272,7 +1269,7 @@ class GevContext:
     def download_plink_matrix(self, pop, chr, ind_begin=0, n_ind=None, stride_words=None):
         """matrix_plink_ped rows (bit 2*snp + hap) of ras_convert_interval_to_format_plink"""
         L = self._nsnp[(pop, chr)]
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         out = _rows_out(n_ind, words_for(2 * L), stride_words)
         self._call("download_plink_matrix", pop, chr, ind_begin, n_ind, out, out.shape[1])
         return out
@@ -1280,7 +1277,7 @@ class GevContext:
     def format_ped_text(self, pop, chr, al0=None, al1=None, ind_begin=0, n_ind=None):
         """genotype columns of the reference's .ped lines (format_plink::write_ped_map; write_ped01_map when al0 is None)"""
         L = self._nsnp[(pop, chr)]
-        n_ind = self.pop_size(pop) - ind_begin if n_ind is None else n_ind
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
         if al0 is not None:
             al0 = _arr(al0, np.uint8); al1 = _arr(al1, np.uint8)
             if len(al0) != L or len(al1) != L:
@@ -1362,7 +1359,7 @@ class GevContext:
         """genotype tile from the interval state; founder_tile: uint64 [n_founder_haps][words] holding SNPs [snp_begin, +n_snps)"""
         L = self._nsnp[(pop, chr)]
         n_snps = L - snp_begin if n_snps is None else n_snps
-        n_rows = 2 * self.pop_size(pop) - row_begin if n_rows is None else n_rows
+        n_rows = self._rest_ind(pop, row_begin, n_rows, 2)
         ft = np.ascontiguousarray(founder_tile, dtype=np.uint64)
         out = _rows_out(n_rows, words_for(n_snps), stride_words)
         self._call("materialize", pop, chr, row_begin, n_rows, snp_begin, n_snps, ft, ft.shape[1], ft.shape[0], out, out.shape[1])
@@ -1372,7 +1369,7 @@ class GevContext:
         """as materialize(), with one founder tile per root population (list of uint64 [n_founder_haps][words])"""
         L = self._nsnp[(pop, chr)]
         n_snps = L - snp_begin if n_snps is None else n_snps
-        n_rows = 2 * self.pop_size(pop) - row_begin if n_rows is None else n_rows
+        n_rows = self._rest_ind(pop, row_begin, n_rows, 2)
         tiles = [np.ascontiguousarray(t, dtype=np.uint64) for t in founder_tiles]
         w = words_for(n_snps)
         ptrs = (C.c_void_p * len(tiles))(*[t.ctypes.data for t in tiles])

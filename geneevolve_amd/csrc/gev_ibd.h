@@ -214,18 +214,6 @@ __global__ void __launch_bounds__(256) k_ibd_segments(const u32* __restrict__ po
         cnt[o] = k.n;
     }
 }
-// *total += the sum of cnt[0 .. n) in 64 bits (the host zeroes it): a strip's record count, which a 32-bit scan's last entry would wrap
-__global__ void __launch_bounds__(256) k_ibd_total(const u32* __restrict__ cnt, size_t n, unsigned long long* __restrict__ total)
-{
-    __shared__ unsigned long long lds[4];
-    unsigned long long s = 0;
-    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) s += cnt[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(total, lds[0] + lds[1] + lds[2] + lds[3]);
-}
 // one thread per row of [row0, +n_rows): bp[r][n_pop] and n_parts[r]; a root population outside [0, n_pop) raises *flag (the host then
 // hands nothing out)
 __global__ void __launch_bounds__(256) k_ancestry_bp(const u32* __restrict__ poff, const gev_part* __restrict__ parts, u64 row0, u32 n_rows, int n_pop,

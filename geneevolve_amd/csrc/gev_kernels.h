@@ -232,6 +232,19 @@ __global__ void __launch_bounds__(256) k_scan_final(const u32* __restrict__ in, 
 #pragma unroll
     for (int j = 0; j < 4; j++) { if (base + j <= n) out[base + j] = ex; ex += v[j]; }
 }
+// *total += the sum of cnt[0 .. n) in 64 bits (the host zeroes it): the record count of a list's strip or pass (count_total), which a
+// 32-bit scan's last entry would wrap
+__global__ void __launch_bounds__(256) k_total_u32(const u32* __restrict__ cnt, size_t n, unsigned long long* __restrict__ total)
+{
+    __shared__ unsigned long long lds[4];
+    unsigned long long s = 0;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) s += cnt[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
+    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(total, lds[0] + lds[1] + lds[2] + lds[3]);
+}
 
 // ------------------------------------------------------------------------------------------
 // synthetic founders (tests/synth.py is the specification) and gen-0 masking

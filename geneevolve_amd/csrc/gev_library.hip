@@ -347,8 +347,9 @@ struct gev_ctx {
     Dev<u32> d_pair_w, d_ld_win; DevBytes d_ld_score; // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
     Dev<int32_t> d_ts_trait, d_ts_acc; Dev<uint4> d_ts_b; Dev<long long> d_ts_out; // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
     DevBytes d_ibd_out; Dev<u32> d_ibd_flag; // gev_ibd_sharing / gev_ancestry_bp (gev_ibd.h): a sub-block's results, the flag of a bad root population; created by the first call
-    Dev<u32> d_ibd_cnt, d_ibd_off; Dev<gev_ibd_segment> d_ibd_seg; Dev<unsigned long long> d_ibd_tot; // gev_ibd_segments: a strip's counts per pair, their exclusive scan, its records, its 64-bit record count; created by the first call
-    Dev<u64> d_roh_brk; DevBytes d_roh_out; Dev<u32> d_roh_diff, d_roh_cov, d_roh_cnt, d_roh_off; Dev<gev_roh_segment> d_roh_seg; // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's counts, their exclusive scan and its records; created by the first call
+    Dev<u32> d_list_cnt, d_list_off; Dev<unsigned long long> d_list_tot; // the record lists (gev_ibd_segments / gev_roh_segments; every call ends with a stream sync, so one set serves both): a strip's or pass's counts per item, their exclusive scan, their 64-bit sum; created by the first call
+    Dev<gev_ibd_segment> d_ibd_seg; // gev_ibd_segments: a strip's records; created by the first call
+    Dev<u64> d_roh_brk; DevBytes d_roh_out; Dev<u32> d_roh_diff, d_roh_cov; Dev<gev_roh_segment> d_roh_seg; // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
     Dev<uint8_t> d_mflag; Dev<u32> d_mblk, d_posm, d_posf, d_pickblk, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat; Dev<gev_couple> d_couples; Dev<double> d_svf; // gev_random_mate / gev_glob_seeds scratch
     Dev<double> d_gef_io; DevBytes d_gef_stat; // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
@@ -3721,6 +3722,12 @@ static int check_out(const char* who, const void* out, size_t n, size_t have, si
     if (n && (!out || have < need)) return fail(GEV_EINVAL, "%s: output buffer of %zu %s, %zu needed", who, have, unit, need);
     return GEV_OK;
 }
+// the haplotype-major rows of L SNPs in host memory that a gev_dbg_*_host form reads (needed: the request reads any)
+static int check_host_rows(const char* who, const uint64_t* bits, size_t row_stride_words, size_t L, bool needed)
+{
+    if (needed && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    return GEV_OK;
+}
 // n_rows device rows of row_bytes bytes (pitch d_pitch) into the caller's rows of row_stride_words words, the pad behind each row
 // zeroed; returns when they have arrived
 static int copy_out_rows(gev_ctx* c, const void* d_rows, size_t d_pitch, size_t row_bytes, size_t n_rows, u64* bits, size_t row_stride_words)
@@ -3837,6 +3844,65 @@ static int download_list(gev_ctx* c, int pop, const char* who, const Dev<u32>& d
     }
     return GEV_OK;
 }
+// The record lists (gev_ibd_segments, gev_roh_segments) in three steps over c->d_list_cnt / d_list_off / d_list_tot.  What the device
+// and the host forms refuse of a list's own arguments:
+static int list_args(const char* who, const void* out, size_t capacity, const uint64_t* n_total)
+{
+    if (!n_total) return fail(GEV_EINVAL, "%s: n_total is null", who);
+    if (!out && capacity) return fail(GEV_EINVAL, "%s: a null output of capacity %zu", who, capacity);
+    return GEV_OK;
+}
+// the sum of the n counts at d_cnt in 64 bits, in host memory when this returns
+static int count_total(gev_ctx* c, const u32* d_cnt, size_t n, u64* total)
+{
+    hipStream_t st = c->stream;
+    GEVC(c->d_list_tot.ensure(1, st));
+    HIPC(hipMemsetAsync(c->d_list_tot.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_total_u32, dim3((unsigned)std::min<size_t>(ceil_div(n, 1024), 1024)), dim3(256), 0, st, d_cnt, n, c->d_list_tot.p);
+    KCHECK();
+    unsigned long long t = 0;
+    HIPC(hipMemcpyAsync(&t, c->d_list_tot.p, sizeof t, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    *total = t;
+    return GEV_OK;
+}
+// the `total` records (< 2^32: no offset wraps) of the n items counted in c->d_list_cnt into out (host): the counts are scanned into
+// c->d_list_off, launch() enqueues the kernel that fills d_rec (already large enough) from those offsets; returns when they have arrived
+template <class T, class Launch>
+static int fill_list(gev_ctx* c, size_t n, u64 total, const Dev<T>& d_rec, T* out, Launch launch)
+{
+    hipStream_t st = c->stream;
+    GEVC(c->d_list_off.ensure(n + 1, st));
+    GEVC(scan_u32_on(st, c->d_sums, c->d_list_cnt.p, n, c->d_list_off.p));
+    GEVC(launch());
+    HIPC(hipMemcpyAsync(out, d_rec.p, (size_t)total * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// An optional result vector of a call: `count` elements of `el` bytes, wanted where host is not null, made at dev (the calls pack theirs
+// into one device buffer, 8-byte elements first: every part begins on a multiple of its element)
+struct OptOut { void* host; size_t el, count; const void* dev = nullptr; };
+template <size_t N>
+static void zero_outs(const OptOut (&outs)[N])
+{
+    for (const OptOut& o : outs) if (o.host) memset(o.host, 0, o.count * o.el);
+}
+// the wanted ones to the host, in the table's order; returns when they have arrived
+template <size_t N>
+static int copy_back_outs(gev_ctx* c, const OptOut (&outs)[N])
+{
+    for (const OptOut& o : outs) if (o.host) HIPC(hipMemcpyAsync(o.host, o.dev, o.count * o.el, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return GEV_OK;
+}
+// a sub-block's results dev ([na][nb] elements of el bytes) into the caller's matrix host (rows of n_b) at (ia, ib), behind the stream's work
+static int copy_out_block(gev_ctx* c, void* host, size_t el, size_t n_b, size_t ia, size_t ib, size_t na, size_t nb, const void* dev)
+{
+    char* dst = (char*)host + (ia * n_b + ib) * el;
+    if (nb == n_b) HIPC(hipMemcpyAsync(dst, dev, na * nb * el, hipMemcpyDeviceToHost, c->stream));      // whole rows of the caller's matrix
+    else HIPC(hipMemcpy2DAsync(dst, n_b * el, dev, nb * el, nb * el, na, hipMemcpyDeviceToHost, c->stream));
+    return GEV_OK;
+}
 }
 int gev_download_haps(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, u64* bits, size_t row_stride_words)
 {
@@ -3906,11 +3972,13 @@ int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
     if (n_snps && (!n_het || !n_hom_alt)) return fail(GEV_EINVAL, "%s: null output vector (n_het and n_hom_alt take %zu counts each)", who, n_snps);
     if (!n_snps) return GEV_OK;
-    if (!n_ind) { memset(n_het, 0, n_snps * sizeof(u32)); memset(n_hom_alt, 0, n_snps * sizeof(u32)); return GEV_OK; }
+    OptOut outs[2] = {{n_het, sizeof(u32), n_snps}, {n_hom_alt, sizeof(u32), n_snps}};
+    if (!n_ind) { zero_outs(outs); return GEV_OK; }
     GEVC(ensure_csr(c, pop));                                           // the overlay reads whole lists
     hipStream_t st = c->stream;
     GEVC(c->d_snpcnt.ensure(2 * n_snps, st));
     u32* d_het = c->d_snpcnt; u32* d_hom = d_het + n_snps;
+    outs[0].dev = d_het; outs[1].dev = d_hom;
     HIPC(hipMemsetAsync(d_het, 0, 2 * n_snps * sizeof(u32), st));
     const size_t q_first = snp_begin / SNPC_LOCI, n_q = (snp_begin + n_snps - 1) / SNPC_LOCI - q_first + 1;     // the chunks that hold a SNP of the range
     const size_t col_blocks = (q_first + n_q - 1) / SNPC_COLS - q_first / SNPC_COLS + 1;                        // the 64-chunk pieces of a row they lie in
@@ -3928,10 +3996,7 @@ int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     hipLaunchKernelGGL(k_snp_counts_apply_mut, dim3((unsigned)ceil_div(n_ind, 256)), dim3(256), 0, st, row_map(P, chr), ind_begin, n_ind,
                        cs.moff[P.cur], cs.mpos[P.cur], S.d_pos, (u32)snp_begin, (u32)n_snps, d_het, d_hom);
     KCHECK();
-    HIPC(hipMemcpyAsync(n_het, d_het, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIPC(hipMemcpyAsync(n_hom_alt, d_hom, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    return copy_back_outs(c, outs);
 }
 // the counter of gev_snpcount.h compiled for the host on haplotype-major rows in host memory: no device, no context
 int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_t n_ind, size_t L, size_t snp_begin, size_t n_snps,
@@ -3940,7 +4005,7 @@ int gev_dbg_snp_counts_host(const uint64_t* bits, size_t row_stride_words, size_
     const char* who = "dbg_snp_counts_host";
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
     if (n_snps && (!n_het || !n_hom_alt)) return fail(GEV_EINVAL, "%s: null output vector", who);
-    if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    GEVC(check_host_rows(who, bits, row_stride_words, L, n_snps && n_ind));
     gev_snpc_count_rows_host(bits, row_stride_words, n_ind, snp_begin, n_snps, n_het, n_hom_alt);
     return GEV_OK;
 }
@@ -3973,11 +4038,11 @@ static constexpr decltype(&k_ld_product<2, false, false>) ld_kernels[2][2][2] = 
 // each may be null) and the stream is waited for, sub-block by sub-block.  With no matrix wanted only the sides are prepared: every
 // block row of A and, where b_alone says that something of side B is wanted for itself, every block of B once
 template <int NOUT, class Prep, class Products>
-static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, uint32_t* const (&outs)[NOUT], bool b_alone, Prep prep, Products products)
+static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, const OptOut (&outs)[NOUT], bool b_alone, Prep prep, Products products)
 {
     hipStream_t st = c->stream;
     bool want_mat = false;
-    for (uint32_t* o : outs) want_mat = want_mat || o;
+    for (const OptOut& o : outs) want_mat = want_mat || o.host;
     GEVC(c->d_bp_out.ensure(NOUT * std::min(blk, n_a) * std::min(blk, n_b), st));
     for (size_t ia = 0; ia < n_a; ia += blk) {
         const size_t na = std::min(blk, n_a - ia);
@@ -3988,13 +4053,9 @@ static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, uint32_t
             GEVC(prep(true, ib, nb, ia == 0));
             if (want_mat) {
                 u32* d_out[NOUT];
-                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o] ? c->d_bp_out + (size_t)o * na * nb : nullptr;
+                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o].host ? c->d_bp_out + (size_t)o * na * nb : nullptr;
                 GEVC(products(na, nb, d_out));
-                for (int o = 0; o < NOUT; o++) {
-                    if (!outs[o]) continue;
-                    if (nb == n_b) HIPC(hipMemcpyAsync(outs[o] + ia * n_b, d_out[o], na * nb * sizeof(u32), hipMemcpyDeviceToHost, st));     // whole rows of the caller's matrix
-                    else HIPC(hipMemcpy2DAsync(outs[o] + ia * n_b + ib, n_b * sizeof(u32), d_out[o], nb * sizeof(u32), nb * sizeof(u32), na, hipMemcpyDeviceToHost, st));
-                }
+                for (int o = 0; o < NOUT; o++) if (outs[o].host) GEVC(copy_out_block(c, outs[o].host, outs[o].el, n_b, ia, ib, na, nb, d_out[o]));
             }
             HIPC(hipStreamSynchronize(st));
         }
@@ -4055,12 +4116,8 @@ int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
     if (!weight != !wsum) return fail(GEV_EINVAL, "%s: weights and wsum come together or not at all", who);
     if (!n_ind) return GEV_OK;
-    if (!n_snps) {
-        if (n_het) memset(n_het, 0, n_ind * sizeof(u32));
-        if (n_hom_alt) memset(n_hom_alt, 0, n_ind * sizeof(u32));
-        if (wsum) memset(wsum, 0, n_ind * sizeof(u64));
-        return GEV_OK;
-    }
+    OptOut outs[3] = {{n_het, sizeof(u32), n_ind}, {n_hom_alt, sizeof(u32), n_ind}, {wsum, sizeof(u64), n_ind}};
+    if (!n_snps) { zero_outs(outs); return GEV_OK; }
     GEVC(ensure_csr(c, pop));
     hipStream_t st = c->stream;
     const u32* d_weight = nullptr;
@@ -4071,12 +4128,9 @@ int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     }
     GEVC(c->d_bp_cnt.ensure(n_ind * 16, st));
     u64* d_ws = c->d_bp_cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
+    outs[0].dev = d_het; outs[1].dev = d_hom; outs[2].dev = d_ws;
     GEVC(pair_prep_side(c, P, chr, ind_begin, n_ind, snp_begin, n_snps, nullptr, d_weight, d_het, d_hom, wsum ? d_ws : nullptr));
-    if (n_het) HIPC(hipMemcpyAsync(n_het, d_het, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
-    if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt, d_hom, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
-    if (wsum) HIPC(hipMemcpyAsync(wsum, d_ws, n_ind * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    return copy_back_outs(c, outs);
 }
 // The pair matrix is walked in sub-blocks of at most pair_block() individuals a side (bitprod_walk; gev_dbg_output_chunk caps them, and the
 // rows of a staging pass), each side staged and prepared through c->d_stage.
@@ -4089,8 +4143,8 @@ int gev_pair_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, siz
     GEVC(check_range(who, "individuals (a)", a_begin, n_a, P.n_people));
     GEVC(check_range(who, "individuals (b)", b_begin, n_b, P.n_people));
     if (!n_a || !n_b) return GEV_OK;
-    uint32_t* const outs[3] = {n_hethet, n_opphom, dot};
-    if (!n_snps) { for (uint32_t* o : outs) if (o) memset(o, 0, n_a * n_b * sizeof(u32)); return GEV_OK; }
+    const OptOut outs[3] = {{n_hethet, sizeof(u32), n_a * n_b}, {n_opphom, sizeof(u32), n_a * n_b}, {dot, sizeof(u32), n_a * n_b}};
+    if (!n_snps) { zero_outs(outs); return GEV_OK; }
     if (!n_hethet && !n_opphom && !dot) return GEV_OK;
     GEVC(ensure_csr(c, pop));
     hipStream_t st = c->stream;
@@ -4118,7 +4172,7 @@ int gev_dbg_pair_counts_host(const uint64_t* bits, size_t row_stride_words, size
     if (n_snps > GEV_PC_MAX_SNPS) return fail(GEV_EUNSUPPORTED, "%s: %zu SNPs in one call, at most %zu (a pair's dot product is a uint32)", who, n_snps, (size_t)GEV_PC_MAX_SNPS);
     GEVC(check_range(who, "individuals (a)", a_begin, n_a, n_ind));
     GEVC(check_range(who, "individuals (b)", b_begin, n_b, n_ind));
-    if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    GEVC(check_host_rows(who, bits, row_stride_words, L, n_snps && n_ind));
     const bool pairs = n_a && n_b;
     gev_pc_counts_host(bits, row_stride_words, n_ind, snp_begin, n_snps, a_begin, pairs ? n_a : 0, b_begin, pairs ? n_b : 0, n_het, n_hom_alt,
                        pairs ? n_hethet : nullptr, pairs ? n_opphom : nullptr, pairs ? dot : nullptr);
@@ -4161,9 +4215,10 @@ int gev_ld_counts(gev_ctx* c, int pop, int chr_a, size_t a_begin, size_t n_a, in
     GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
     if (n_ind > GEV_LD_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a pair's genotype product is a uint32)", who, n_ind, (size_t)GEV_LD_MAX_IND);
     if (!n_a || !n_b) return GEV_OK;
-    uint32_t* const vec_a[3] = {c_a, het_a, hom_a}; uint32_t* const vec_b[3] = {c_b, het_b, hom_b}; uint32_t* const mats[2] = {n11, gg};
+    uint32_t* const vec_a[3] = {c_a, het_a, hom_a}; uint32_t* const vec_b[3] = {c_b, het_b, hom_b};
+    const OptOut mats[2] = {{n11, sizeof(u32), n_a * n_b}, {gg, sizeof(u32), n_a * n_b}};
     if (!n_ind) {
-        for (uint32_t* o : mats) if (o) memset(o, 0, n_a * n_b * sizeof(u32));
+        zero_outs(mats);
         for (uint32_t* o : vec_a) if (o) memset(o, 0, n_a * sizeof(u32));
         for (uint32_t* o : vec_b) if (o) memset(o, 0, n_b * sizeof(u32));
         return GEV_OK;
@@ -4186,7 +4241,7 @@ int gev_ld_counts(gev_ctx* c, int pop, int chr_a, size_t a_begin, size_t n_a, in
             return GEV_OK;
         },
         [&](size_t na, size_t nb, u32* const* d_out) -> int {
-            for (int o = 0; o < 2; o++) if (mats[o]) GEVC(bitprod_launch(c, ld_kernels[0][o], na, nb, (A.n_pad / BP_TILE) * (B.n_pad / BP_TILE), A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, d_out[o], LdScoreArgs{}));
+            for (int o = 0; o < 2; o++) if (mats[o].host) GEVC(bitprod_launch(c, ld_kernels[0][o], na, nb, (A.n_pad / BP_TILE) * (B.n_pad / BP_TILE), A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, d_out[o], LdScoreArgs{}));
             return GEV_OK;
         });
 }
@@ -4215,11 +4270,8 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     if (n_ind > GEV_LD_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a pair's genotype product is a uint32)", who, n_ind, (size_t)GEV_LD_MAX_IND);
     GEVC(ld_check_windows(who, snp_begin, n_snps, win_lo, win_hi, P.cs[chr].L));
     if (!n_snps || (!score_q40 && !n_terms)) return GEV_OK;
-    if (!n_ind) {
-        if (score_q40) memset(score_q40, 0, n_snps * sizeof(u64));
-        if (n_terms) memset(n_terms, 0, n_snps * sizeof(u32));
-        return GEV_OK;
-    }
+    OptOut outs[2] = {{score_q40, sizeof(u64), n_snps}, {n_terms, sizeof(u32), n_snps}};
+    if (!n_ind) { zero_outs(outs); return GEV_OK; }
     hipStream_t st = c->stream;
     const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_snps), bb = std::min<size_t>(blk, P.cs[chr].L);
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind);
@@ -4229,6 +4281,7 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     u32* d_cnt_a = c->d_bp_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
     u32* d_lo = c->d_ld_win; u32* d_hi = d_lo + n_snps;
     u64* d_score = c->d_ld_score.as<u64>(); u32* d_terms = (u32*)(d_score + n_snps);
+    outs[0].dev = d_score; outs[1].dev = d_terms;
     HIPC(hipMemcpyAsync(d_lo, win_lo, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
     HIPC(hipMemcpyAsync(d_hi, win_hi, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
     HIPC(hipMemsetAsync(d_score, 0, n_snps * (sizeof(u64) + sizeof(u32)), st));
@@ -4250,10 +4303,7 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
             GEVC(bitprod_launch(c, ld_kernels[1][genotype != 0], na, nb, band_tiles / LD_SCORE_TILES_PER_CU, A.plane, (u32)A.n_pad, B.plane, (u32)B.n_pad, (u32)n_w4, (u32)na, (u32)nb, (u32*)nullptr, sa));
         }
     }
-    if (score_q40) HIPC(hipMemcpyAsync(score_q40, d_score, n_snps * sizeof(u64), hipMemcpyDeviceToHost, st));
-    if (n_terms) HIPC(hipMemcpyAsync(n_terms, d_terms, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    return copy_back_outs(c, outs);
 }
 // the arithmetic of gev_ldcount.h compiled for the host on haplotype-major rows in host memory: no device, no context.  The block form
 // (SNPs [a_begin, +n_a) of rows_a against [b_begin, +n_b) of rows_b) and, with windows, the score form over side A's rows
@@ -4294,10 +4344,8 @@ static int ts_check_traits(const char* who, const int32_t* trait, size_t n_trait
 }
 static void ts_zero(size_t n_snps, size_t n_traits, int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
 {
-    if (gsum) memset(gsum, 0, n_traits * n_snps * sizeof(int64_t));
-    if (hetsum) memset(hetsum, 0, n_traits * n_snps * sizeof(int64_t));
-    if (n_het) memset(n_het, 0, n_snps * sizeof(u32));
-    if (n_hom_alt) memset(n_hom_alt, 0, n_snps * sizeof(u32));
+    const OptOut outs[4] = {{gsum, sizeof(int64_t), n_traits * n_snps}, {hetsum, sizeof(int64_t), n_traits * n_snps}, {n_het, sizeof(u32), n_snps}, {n_hom_alt, sizeof(u32), n_snps}};
+    zero_outs(outs);
 }
 // The SNPs are walked in blocks of at most ld_block() (gev_dbg_output_chunk caps them): a block is one snp_major_device pass and one
 // k_ld_prep into c->d_bp_a; the traits' operand bytes are made once per call and serve every block; a block's sums are copied out before the
@@ -4360,7 +4408,7 @@ int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
     GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
     GEVC(ts_check_traits(who, trait, n_traits, n_ind));
-    if (n_snps && n_ind && (!bits || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: rows of %zu words, %zu needed", who, row_stride_words, ceil_div(L, 64));
+    GEVC(check_host_rows(who, bits, row_stride_words, L, n_snps && n_ind));
     if (!n_snps) return GEV_OK;
     if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
     gev_trait_sums_host(bits, row_stride_words, snp_begin, n_snps, ind_begin, n_ind, trait, n_traits, gsum, hetsum, n_het, n_hom_alt);
@@ -4402,13 +4450,8 @@ int gev_ibd_sharing(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, 
             hipLaunchKernelGGL(k_ibd_tiles, dim3((unsigned)ceil_div(nb, GEV_IBD_TILE), (unsigned)ceil_div(na, GEV_IBD_TILE)), dim3(256), 0, st,
                                poff_a, parts_a, (u64)(a_begin + ia), (u32)na, poff_b, parts_b, (u64)(b_begin + ib), (u32)nb, (u64)min_bp, d_sh, d_ns, d_mx);
             KCHECK();
-            const struct { void* host; const void* dev; size_t el; } outs[3] = {{shared_bp, d_sh, 8}, {max_seg, d_mx, 8}, {n_seg, d_ns, 4}};
-            for (const auto& o : outs) {
-                if (!o.host) continue;
-                char* dst = (char*)o.host + (ia * n_b + ib) * o.el;
-                if (nb == n_b) HIPC(hipMemcpyAsync(dst, o.dev, na * nb * o.el, hipMemcpyDeviceToHost, st));                       // whole rows of the caller's matrix
-                else HIPC(hipMemcpy2DAsync(dst, n_b * o.el, o.dev, nb * o.el, nb * o.el, na, hipMemcpyDeviceToHost, st));
-            }
+            const OptOut outs[3] = {{shared_bp, 8, na * nb, d_sh}, {max_seg, 8, na * nb, d_mx}, {n_seg, 4, na * nb, d_ns}};
+            for (const OptOut& o : outs) if (o.host) GEVC(copy_out_block(c, o.host, o.el, n_b, ia, ib, na, nb, o.dev));
             HIPC(hipStreamSynchronize(st));
         }
     return GEV_OK;
@@ -4434,10 +4477,8 @@ int gev_ancestry_bp(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_row
     HIPC(hipMemcpyAsync(&flag, c->d_ibd_flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     if (flag) return fail(GEV_EINVAL, "%s: a part of population %d names a root population outside [0, %d)", who, pop, c->n_pop);
-    if (bp) HIPC(hipMemcpyAsync(bp, d_bp, n_rows * npop * sizeof(u64), hipMemcpyDeviceToHost, st));
-    if (n_parts) HIPC(hipMemcpyAsync(n_parts, d_np, n_rows * sizeof(u32), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    const OptOut outs[2] = {{bp, sizeof(u64), n_rows * npop, d_bp}, {n_parts, sizeof(u32), n_rows, d_np}};
+    return copy_back_outs(c, outs);
 }
 // what the host forms refuse of two sets of lists in host memory
 static int ibd_host_lists(const char* who, const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b)
@@ -4462,13 +4503,11 @@ int gev_dbg_ibd_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a,
     return GEV_OK;
 }
 // ---- the IBD segments themselves (gev_ibd.h: k_ibd_segments) ----
-// what the device and the host form refuse of the list's own arguments
+// what the device and the host form refuse of the list's own arguments (pairs behind a null n_total, which list_args reports)
 static int ibd_seg_args(const char* who, int pairs, const gev_ibd_segment* out, size_t capacity, const uint64_t* n_total)
 {
-    if (!n_total) return fail(GEV_EINVAL, "%s: n_total is null", who);
-    if (pairs != GEV_IBD_ALL_PAIRS && pairs != GEV_IBD_UPPER) return fail(GEV_EINVAL, "%s: pairs is %d (GEV_IBD_ALL_PAIRS or GEV_IBD_UPPER)", who, pairs);
-    if (!out && capacity) return fail(GEV_EINVAL, "%s: a null output of capacity %zu", who, capacity);
-    return GEV_OK;
+    if (n_total && pairs != GEV_IBD_ALL_PAIRS && pairs != GEV_IBD_UPPER) return fail(GEV_EINVAL, "%s: pairs is %d (GEV_IBD_ALL_PAIRS or GEV_IBD_UPPER)", who, pairs);
+    return list_args(who, out, capacity, n_total);
 }
 // one request's constants, and a strip of whole A rows [row0, +rows) of it against all its B rows
 struct IbdSegCall { const u32 *poff_a, *poff_b; const gev_part *parts_a, *parts_b; size_t a_begin, b_begin, n_b; u64 min_bp; u32 upper; };
@@ -4481,28 +4520,19 @@ static int ibd_seg_launch(gev_ctx* c, const IbdSegCall& q, size_t row0, size_t r
     const auto kernel = fill ? k_ibd_segments<true> : k_ibd_segments<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, q.poff_a, q.parts_a, (u64)(q.a_begin + row0), (u32)rows,
                        q.poff_b, q.parts_b, (u64)q.b_begin, (u32)q.n_b, q.min_bp, q.upper, ta_log2, (u32)tiles_b,
-                       fill ? c->d_ibd_off.p : c->d_ibd_cnt.p, c->d_ibd_seg.p);
+                       fill ? c->d_list_off.p : c->d_list_cnt.p, c->d_ibd_seg.p);
     KCHECK();
     return GEV_OK;
 }
-// the strip's counts per pair into c->d_ibd_cnt; total: their sum in 64 bits, in host memory when this returns (null: not wanted)
+// the strip's counts per pair into c->d_list_cnt; total: their sum in 64 bits, in host memory when this returns (null: not wanted)
 static int ibd_seg_count(gev_ctx* c, const IbdSegCall& q, size_t row0, size_t rows, u64* total)
 {
     hipStream_t st = c->stream;
     const size_t np = rows * q.n_b;
-    GEVC(c->d_ibd_cnt.ensure(np, st));
-    if (q.upper) HIPC(hipMemsetAsync(c->d_ibd_cnt.p, 0, np * sizeof(u32), st));              // (pairs on or below the diagonal are not visited)
+    GEVC(c->d_list_cnt.ensure(np, st));
+    if (q.upper) HIPC(hipMemsetAsync(c->d_list_cnt.p, 0, np * sizeof(u32), st));             // (pairs on or below the diagonal are not visited)
     GEVC(ibd_seg_launch(c, q, row0, rows, false));
-    if (!total) return GEV_OK;
-    GEVC(c->d_ibd_tot.ensure(1, st));
-    HIPC(hipMemsetAsync(c->d_ibd_tot.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_ibd_total, dim3((unsigned)std::min<size_t>(ceil_div(np, 1024), 1024)), dim3(256), 0, st, (const u32*)c->d_ibd_cnt.p, np, c->d_ibd_tot.p);
-    KCHECK();
-    unsigned long long t = 0;
-    HIPC(hipMemcpyAsync(&t, c->d_ibd_tot.p, sizeof t, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    *total = t;
-    return GEV_OK;
+    return total ? count_total(c, c->d_list_cnt.p, np, total) : GEV_OK;
 }
 // Two phases.  Every strip is counted and its 64-bit total kept on the host: n_total.  If out holds them, each strip is counted again
 // (a request of one strip still has its counts), scanned and filled into c->d_ibd_seg, which is copied to out at the running offset
@@ -4546,13 +4576,8 @@ int gev_ibd_segments(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a,
     size_t done = 0;
     for (const IbdStrip& s : strips) {
         if (!s.total) continue;
-        const size_t np = s.rows * n_b;
         if (strips.size() > 1) GEVC(ibd_seg_count(c, q, s.row0, s.rows, nullptr));
-        GEVC(c->d_ibd_off.ensure(np + 1, st));
-        GEVC(scan_u32_on(st, c->d_sums, c->d_ibd_cnt.p, np, c->d_ibd_off.p));                 // (s.total < 2^32: no offset wraps)
-        GEVC(ibd_seg_launch(c, q, s.row0, s.rows, true));
-        HIPC(hipMemcpyAsync(out + done, c->d_ibd_seg.p, (size_t)s.total * sizeof(gev_ibd_segment), hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
+        GEVC(fill_list(c, s.rows * n_b, s.total, c->d_ibd_seg, out + done, [&] { return ibd_seg_launch(c, q, s.row0, s.rows, true); }));
         done += (size_t)s.total;
     }
     return GEV_OK;
@@ -4576,12 +4601,6 @@ static int roh_args(const char* who, const gev_roh_params* q, size_t snp_begin, 
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
     GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
     if (L >= 0xffffffffull || n_people > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: SNP or individual indices beyond 2^32 - 1 do not fit a record", who);
-    return GEV_OK;
-}
-static int roh_seg_args(const char* who, const gev_roh_segment* out, size_t capacity, const uint64_t* n_total)
-{
-    if (!n_total) return fail(GEV_EINVAL, "%s: n_total is null", who);
-    if (!out && capacity) return fail(GEV_EINVAL, "%s: a null output of capacity %zu", who, capacity);
     return GEV_OK;
 }
 static int roh_begin(gev_ctx* c, int pop, int chr, const char* who, const gev_roh_params* q, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind)
@@ -4621,18 +4640,14 @@ int gev_roh_summary(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snp
     GEVC(roh_begin(c, pop, chr, who, q, snp_begin, n_snps, ind_begin, n_ind));
     PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr];
     if (!n_ind) { if (cover && n_snps) memset(cover, 0, n_snps * sizeof(u32)); return GEV_OK; }
-    if (!n_snps) {
-        if (n_roh) memset(n_roh, 0, n_ind * sizeof(u32));
-        if (roh_bp) memset(roh_bp, 0, n_ind * sizeof(u64));
-        if (roh_snps) memset(roh_snps, 0, n_ind * sizeof(u32));
-        if (max_bp) memset(max_bp, 0, n_ind * sizeof(u64));
-        return GEV_OK;
-    }
+    OptOut outs[4] = {{n_roh, sizeof(u32), n_ind}, {roh_bp, sizeof(u64), n_ind}, {roh_snps, sizeof(u32), n_ind}, {max_bp, sizeof(u64), n_ind}};
+    if (!n_snps) { zero_outs(outs); return GEV_OK; }
     if (!n_roh && !roh_bp && !roh_snps && !max_bp && !cover) return GEV_OK;
     hipStream_t st = c->stream;
     // the 8-byte vectors first: every part of the buffer begins on a multiple of its element
     GEVC(c->d_roh_out.ensure(n_ind * 24, st));
     u64* d_bp = c->d_roh_out.as<u64>(); u64* d_mx = d_bp + n_ind; u32* d_n = (u32*)(d_mx + n_ind); u32* d_sn = d_n + n_ind;
+    outs[0].dev = d_n; outs[1].dev = d_bp; outs[2].dev = d_sn; outs[3].dev = d_mx;
     u32* d_diff = nullptr;
     if (cover) {
         GEVC(c->d_roh_diff.ensure(n_snps + 1, st));
@@ -4649,39 +4664,20 @@ int gev_roh_summary(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snp
         GEVC(scan_u32_on(st, c->d_sums, d_diff, n_snps, c->d_roh_cov.p));      // entry j + 1 = the inclusive sum up to j (mod 2^32, as the -1 entries are)
         HIPC(hipMemcpyAsync(cover, c->d_roh_cov.p + 1, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
     }
-    if (n_roh) HIPC(hipMemcpyAsync(n_roh, d_n, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
-    if (roh_bp) HIPC(hipMemcpyAsync(roh_bp, d_bp, n_ind * sizeof(u64), hipMemcpyDeviceToHost, st));
-    if (roh_snps) HIPC(hipMemcpyAsync(roh_snps, d_sn, n_ind * sizeof(u32), hipMemcpyDeviceToHost, st));
-    if (max_bp) HIPC(hipMemcpyAsync(max_bp, d_mx, n_ind * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    return copy_back_outs(c, outs);
 }
-// the counts of the staged pass into c->d_roh_cnt and their 64-bit sum into *total (in host memory when this returns)
+// the counts of the staged pass into c->d_list_cnt (already large enough) and their 64-bit sum into *total (in host memory when this returns)
 static int roh_count_pass(gev_ctx* c, const RohCall& r, size_t ind0, size_t n, u64* total)
 {
-    hipStream_t st = c->stream;
-    GEVC(roh_launch(c, r, ROH_COUNT, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_roh_cnt.p, nullptr));
-    GEVC(c->d_ibd_tot.ensure(1, st));
-    HIPC(hipMemsetAsync(c->d_ibd_tot.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_ibd_total, dim3((unsigned)std::min<size_t>(ceil_div(n, 1024), 1024)), dim3(256), 0, st, (const u32*)c->d_roh_cnt.p, n, c->d_ibd_tot.p);
-    KCHECK();
-    unsigned long long t = 0;
-    HIPC(hipMemcpyAsync(&t, c->d_ibd_tot.p, sizeof t, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    *total = t;
-    return GEV_OK;
+    GEVC(roh_launch(c, r, ROH_COUNT, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_list_cnt.p, nullptr));
+    return count_total(c, c->d_list_cnt.p, n, total);
 }
-// the `total` records of the staged and counted pass into out (host): scan, fill into c->d_roh_seg, copy
+// the `total` records of the staged and counted pass into out (host) through c->d_roh_seg
 static int roh_fill_pass(gev_ctx* c, const RohCall& r, size_t ind0, size_t n, u64 total, gev_roh_segment* out)
 {
-    hipStream_t st = c->stream;
     if (total >> 32) return fail(GEV_EUNSUPPORTED, "roh_segments: %llu records in one pass", (unsigned long long)total);
-    GEVC(c->d_roh_seg.ensure((size_t)total, st));
-    GEVC(scan_u32_on(st, c->d_sums, c->d_roh_cnt.p, n, c->d_roh_off.p));
-    GEVC(roh_launch(c, r, ROH_FILL, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_roh_off.p, c->d_roh_seg.p));
-    HIPC(hipMemcpyAsync(out, c->d_roh_seg.p, (size_t)total * sizeof(gev_roh_segment), hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    GEVC(c->d_roh_seg.ensure((size_t)total, c->stream));
+    return fill_list(c, n, total, c->d_roh_seg, out, [&] { return roh_launch(c, r, ROH_FILL, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_list_off.p, c->d_roh_seg.p); });
 }
 // A request of one pass counts, scans and fills on the same staged rows.  A request of several passes counts them all (n_total), and if
 // out holds the records stages each again, counts it (the offsets of its fill) and fills: passes are runs of whole individuals in order,
@@ -4690,15 +4686,13 @@ int gev_roh_segments(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_sn
                      gev_roh_segment* out, size_t capacity, uint64_t* n_total)
 {
     const char* who = "roh_segments";
-    GEVC(roh_seg_args(who, out, capacity, n_total));
+    GEVC(list_args(who, out, capacity, n_total));
     GEVC(roh_begin(c, pop, chr, who, q, snp_begin, n_snps, ind_begin, n_ind));
     PopState& P = c->pop[pop]; ChrStatic& S = P.cs[chr];
     if (!n_ind || !n_snps) { *n_total = 0; return GEV_OK; }
-    hipStream_t st = c->stream;
     const size_t per_pass = std::min(output_chunk(c, 256u << 20, 2 * S.stride), n_ind);      // (what ind_major_chunks takes)
     const bool one_pass = per_pass == n_ind;
-    GEVC(c->d_roh_cnt.ensure(per_pass, st));
-    GEVC(c->d_roh_off.ensure(per_pass + 1, st));
+    GEVC(c->d_list_cnt.ensure(per_pass, c->stream));
     RohCall r = {S.d_pos, nullptr, (u32)(S.stride / 16), (u32)snp_begin, (u32)n_snps, *q};
     GEVC(roh_breaks(c, S, q->max_gap_bp, r.brk));
     u64 total = 0;
@@ -4727,7 +4721,7 @@ int gev_dbg_roh_host(const uint64_t* bits, size_t row_stride_words, size_t n_peo
                      gev_roh_segment* out, size_t capacity, uint64_t* n_total)
 {
     const char* who = "dbg_roh_host";
-    if (n_total) GEVC(roh_seg_args(who, out, capacity, n_total));
+    if (n_total) GEVC(list_args(who, out, capacity, n_total));
     else if (out || capacity) return fail(GEV_EINVAL, "%s: an output list without n_total", who);
     GEVC(roh_args(who, q, snp_begin, n_snps, L, ind_begin, n_ind, n_people));
     if (n_snps && n_ind && (!bits || !pos || row_stride_words < ceil_div(L, 64))) return fail(GEV_EINVAL, "%s: null rows or positions, or rows of %zu words (%zu needed)", who, row_stride_words, ceil_div(L, 64));

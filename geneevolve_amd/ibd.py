@@ -7,30 +7,13 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _ranges
+from ._ranges import chrs as _chrs, individuals as _individuals, rows as _rows
+
 IBDSharing = namedtuple("IBDSharing", "span_bp shared_bp n_seg max_seg")
 IBDSharing.__doc__ = """span_bp: the chromosome's length (last minus first position of its recombination map); shared_bp / n_seg / max_seg:
 uint64 / uint32 / uint64 [n_a][n_b] per pair of haplotype rows (row = 2 * individual + chromatid): the summed length, the number and the
 longest of the segments of at least min_bp base pairs along which both rows descend from the same founder haplotype"""
-
-
-def _rows(ctx, pop, r):
-    """(begin, n) of a range of haplotype rows given as None (all of them), (begin, n) or a range / slice-like with .start and .stop"""
-    if r is None:
-        return 0, 2 * ctx.pop_size(pop)
-    if hasattr(r, "start"):
-        return int(r.start or 0), int(r.stop) - int(r.start or 0)
-    return int(r[0]), int(r[1])
-
-
-def _individuals(ctx, pop, ind):
-    """(begin, n) of a range of individuals, given as _rows takes a range of rows"""
-    if ind is None:
-        return 0, ctx.pop_size(pop)
-    return _rows(ctx, pop, ind)
-
-
-def _chrs(ctx, chrs):
-    return list(ctx.active_chrs()) if chrs is None else [int(k) for k in chrs]
 
 
 def sharing(ctx, pop, chr, a=None, b=None, pop_b=None, min_bp=0):
@@ -44,17 +27,7 @@ def segments_over_chromosomes(chrs, per_chr):
     """one array with a leading `chr` field (int32) from the segment arrays of several chromosomes (GevContext.ibd_segments, each sorted
     by (row_a, row_b, st)), the chromosomes in ascending order: sorted by (chr, row_a, row_b, st)"""
     from .capi import SEGMENT_DTYPE
-    dt = np.dtype([("chr", np.int32)] + [(name, SEGMENT_DTYPE.fields[name][0]) for name in SEGMENT_DTYPE.names])
-    order = sorted(range(len(chrs)), key=lambda k: int(chrs[k]))
-    out = np.zeros(sum(len(s) for s in per_chr), dtype=dt)
-    at = 0
-    for k in order:
-        part = out[at:at + len(per_chr[k])]
-        part["chr"] = int(chrs[k])
-        for name in SEGMENT_DTYPE.names:
-            part[name] = per_chr[k][name]
-        at += len(part)
-    return out
+    return _ranges.segments_over_chromosomes(chrs, per_chr, SEGMENT_DTYPE)
 
 
 def segments(ctx, pop, chrs=None, rows=None, pop_b=None, rows_b=None, min_bp=0, upper=None):

@@ -5,18 +5,11 @@ from collections import namedtuple
 
 import numpy as np
 
+from ._ranges import individuals as _range
+
 PairCounts = namedtuple("PairCounts", "n_snps het_a hom_a het_b hom_b n_hethet n_opphom dot")
 PairCounts.__doc__ = """n_snps: loci counted; het_* / hom_*: int64 [n_a] / [n_b] heterozygous loci and loci with allele 1 twice of each individual;
 n_hethet / n_opphom / dot: int64 [n_a][n_b] per pair (i of a, k of b)"""
-
-
-def _range(ctx, pop, r):
-    """(begin, n) of a range given as None (everybody), (begin, n) or a range / slice-like with .start and .stop"""
-    if r is None:
-        return 0, ctx.pop_size(pop)
-    if hasattr(r, "start"):
-        return int(r.start or 0), int(r.stop) - int(r.start or 0)
-    return int(r[0]), int(r[1])
 
 
 def pair_counts(ctx, pop, a=None, b=None):

@@ -8,23 +8,13 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _ranges
+from ._ranges import chrs as _chrs, individuals as _individuals
+
 ROHSummary = namedtuple("ROHSummary", "span_bp n_roh roh_bp roh_snps max_bp")
 ROHSummary.__doc__ = """span_bp: the summed pos[L-1] - pos[0] of the chromosomes; n_roh / roh_bp / roh_snps / max_bp: uint64 [n_ind] per
 individual over its qualifying runs on those chromosomes: their number, their summed length in base pairs (last minus first SNP position
 of each run), their summed SNPs, and the longest in base pairs (0 without a run)"""
-
-
-def _individuals(ctx, pop, ind):
-    """(begin, n) of a range of individuals given as None (everybody), (begin, n) or a range / slice-like with .start and .stop"""
-    if ind is None:
-        return 0, ctx.pop_size(pop)
-    if hasattr(ind, "start"):
-        return int(ind.start or 0), int(ind.stop) - int(ind.start or 0)
-    return int(ind[0]), int(ind[1])
-
-
-def _chrs(ctx, chrs):
-    return list(ctx.active_chrs()) if chrs is None else [int(k) for k in chrs]
 
 
 def _limits(min_snps, min_kb, max_gap_kb):
@@ -60,17 +50,7 @@ def segments_over_chromosomes(chrs, per_chr):
     """one array with a leading `chr` field (int32) from the run arrays of several chromosomes (GevContext.roh_segments, each sorted by
     (ind, snp_first)), the chromosomes in ascending order: sorted by (chr, ind, snp_first)"""
     from .capi import ROH_SEGMENT_DTYPE
-    dt = np.dtype([("chr", np.int32)] + [(name, ROH_SEGMENT_DTYPE.fields[name][0]) for name in ROH_SEGMENT_DTYPE.names])
-    order = sorted(range(len(chrs)), key=lambda k: int(chrs[k]))
-    out = np.zeros(sum(len(s) for s in per_chr), dtype=dt)
-    at = 0
-    for k in order:
-        part = out[at:at + len(per_chr[k])]
-        part["chr"] = int(chrs[k])
-        for name in ROH_SEGMENT_DTYPE.names:
-            part[name] = per_chr[k][name]
-        at += len(part)
-    return out
+    return _ranges.segments_over_chromosomes(chrs, per_chr, ROH_SEGMENT_DTYPE)
 
 
 def summary(ctx, pop, chrs=None, ind=None, min_snps=0, min_kb=0, max_gap_kb=0):

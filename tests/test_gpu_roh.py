@@ -236,6 +236,51 @@ def test_self_ibd_segments_lie_inside_runs(gpu_lib):
         ctx.close()
 
 
+def test_both_record_lists_on_one_context_in_turn(gpu_lib):
+    """gev_ibd_segments and gev_roh_segments count, scan and total in one set of buffers of the context.  80 individuals x 400 SNPs bred
+    for six generations, the two calls in turn, every list against its host build record for record.  Under passes of 3 (strips of 3 rows
+    x 8 pairs, passes of 3 individuals) the run list counts into the vector the segment list sized and left its counts in, and the other
+    way round.  Without a cap the run list of 80 individuals makes the buffers grow behind the segment list (a device buffer holds 64
+    counts at the least), 16 x 16 rows make them grow again, and the smaller requests behind them reuse buffers larger than they need"""
+    n, n_snps = 80, 400
+    cfg = SyntheticConfig(n, n_snps, chrom_bp=2_000_000, map_step=20_000, rec_per_row=0.02, n_cv=8, seed=5, with_mutation=False)
+    ctx = gpu_lib.create(1, 1, 1)
+    try:
+        cfg.apply_static(ctx)
+        ctx.synth_founders(0, 0, 2 * n, 31); ctx.synth_cv_founders(0, 0, 0, 2 * n, 32)
+        sim = Simulation(ctx, 4247, 1, False)
+        sim.ras_initial_human_gen0(0, n)
+        for _ in range(6):
+            sim.next_generation_rm(0, n)
+        parts, off = ctx.download_intervals(0, 0)
+        words, pos = ctx.download_haps(0, 0), np.asarray(cfg.snp_pos, dtype=np.uint64)
+
+        def ibd_pair(a, b):
+            """(device, host build) of rows a x rows b, all pairs"""
+            want = gpu_lib.dbg_ibd_segments_host(parts, off[a[0]:a[0] + a[1] + 1], parts, off[b[0]:b[0] + b[1] + 1])
+            want["row_a"] += a[0]; want["row_b"] += b[0]
+            return ctx.ibd_segments(0, 0, a[0], a[1], 0, b[0], b[1]), want
+
+        def roh_pair(i0, ni, **lim):
+            return ctx.roh_segments(0, 0, 0, None, i0, ni, **lim), gpu_lib.dbg_roh_host(words, n_snps, pos, 0, None, i0, ni, want_cover=False, **lim)[5]
+
+        def same(pair, what):
+            got, want = pair
+            assert len(want) > 0 and got.dtype == want.dtype and got.tobytes() == want.tobytes(), what
+            return got
+
+        for chunk, a, b, many, few in ((3, (4, 8), (10, 8), (0, 40), (33, 5)), (0, (4, 8), (10, 8), (0, 80), (71, 2)), (0, (100, 16), (20, 16), (3, 70), (5, 1))):
+            ctx.dbg_output_chunk(chunk)
+            what = f"chunk {chunk}, rows {a} x {b}"
+            first = same(ibd_pair(a, b), what + ": the segment list")
+            same(roh_pair(*many), what + f": the run list of individuals {many} behind it")
+            again = same(ibd_pair(a, b), what + ": the segment list again")
+            assert again.tobytes() == first.tobytes()
+            same(roh_pair(*few, min_snps=2), what + f": the run list of individuals {few}")
+    finally:
+        ctx.close()
+
+
 # ---- 3. the mutation overlay -----------------------------------------------------------------------------------------------------------
 def build_overlay(lib, upload=False):
     """the population of test_gpu_snp_counts.test_counts_under_the_mutation_overlay: 150 individuals, 700 SNPs two base pairs apart,

@@ -135,3 +135,43 @@ def test_roh_module_helpers_on_arrays(built):
     assert seg.dtype.names == ("chr",) + ROH_SEGMENT_DTYPE.names and seg["chr"].tolist() == [0] * len(half[5]) + [2] * len(full[5])
     assert all(np.array_equal(seg[name][:len(half[5])], half[5][name]) and np.array_equal(seg[name][len(half[5]):], full[5][name]) for name in ROH_SEGMENT_DTYPE.names)
     assert roh._limits(100, 1.5, 0.25) == dict(min_snps=100, min_bp=1500, max_gap_bp=250)
+
+
+class _FixedSize:
+    """what the range helpers ask of a context"""
+    def pop_size(self, pop):
+        return 30 + pop
+
+    def active_chrs(self):
+        return [0, 2]
+
+
+def test_range_helpers_and_chromosome_order_for_both_record_types():
+    from geneevolve_amd import _ranges, ibd, relatedness
+    from geneevolve_amd.capi import SEGMENT_DTYPE
+    ctx = _FixedSize()
+    # the default extent: individuals, or two haplotype rows each
+    for helper, per in ((_ranges.individuals, 1), (_ranges.rows, 2)):
+        assert helper(ctx, 0, None) == (0, 30 * per) and helper(ctx, 3, None) == (0, 33 * per)
+        assert helper(ctx, 0, (4, 7)) == (4, 7) and helper(ctx, 0, np.array([4, 7])) == (4, 7)
+        assert helper(ctx, 0, range(5, 12)) == (5, 7) and helper(ctx, 0, slice(None, 9)) == (0, 9) and helper(ctx, 0, slice(3, 9)) == (3, 6)
+        assert all(type(v) is int for v in helper(ctx, 0, np.array([4, 7])))
+    # the modules' own names are these helpers
+    assert ibd._rows is _ranges.rows and ibd._individuals is _ranges.individuals and roh._individuals is _ranges.individuals
+    assert relatedness._range is _ranges.individuals
+    assert ibd._chrs(ctx, None) == [0, 2] and roh._chrs(ctx, (np.int64(3), 1)) == [3, 1]
+    # chromosomes handed over out of order, for both record types
+    for module, dtype in ((ibd, SEGMENT_DTYPE), (roh, ROH_SEGMENT_DTYPE)):
+        per_chr = []
+        for k, n in enumerate((3, 0, 5)):
+            a = np.zeros(n, dtype=dtype)
+            for j, name in enumerate(dtype.names):
+                a[name] = 100 * k + 10 * j + np.arange(n)
+            per_chr.append(a)
+        got = module.segments_over_chromosomes([7, 4, 1], per_chr)
+        assert got.dtype.names == ("chr",) + dtype.names and got["chr"].dtype == np.int32
+        assert all(got.dtype.fields[name][0] == dtype.fields[name][0] for name in dtype.names)
+        assert got["chr"].tolist() == [1] * 5 + [7] * 3
+        assert all(np.array_equal(got[name][:5], per_chr[2][name]) and np.array_equal(got[name][5:], per_chr[0][name]) for name in dtype.names)
+        assert np.array_equal(got, _ranges.segments_over_chromosomes([7, 4, 1], per_chr, dtype))
+        assert len(module.segments_over_chromosomes([], [])) == 0 and module.segments_over_chromosomes([], []).dtype == got.dtype
