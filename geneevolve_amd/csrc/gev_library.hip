@@ -109,13 +109,13 @@ static int dev_grow(void*& p, size_t& bytes, size_t need, hipStream_t st, bool k
 //   d_snpmajor        SNP-major bit rows: u64 words, unsigned long long for the transpose's atomics, u32 halves in k_materialize_tile
 //   d_stage, d_tmp, d_text, d_map   scratch of whichever call uses them (rows, ranks, text, maps with their offsets)
 //   d_flag            flag words of several calls: u32 flags, or one 64-bit counter
-//   d_bp_cnt          per-row counts of a bit-plane product: u64[n] then u32[n] twice (pair counts), u32 triples (LD, trait sums)
-//   d_ld_score        u64[n] sums, then u32[n] counts
-//   d_gef_stat        GEF_WORDS u32 status words, then {mean, var} as doubles
+//   bp.cnt            per-row counts of a bit-plane product: u64[n] then u32[n] twice (pair counts), u32 triples (LD, trait sums)
+//   bp.ld_score       u64[n] sums, then u32[n] counts
+//   gef.stat          GEF_WORDS u32 status words, then {mean, var} as doubles
 //   ph.res            u32 result words, then {mean, var} pairs as doubles
-//   d_lpc_tmp         an arena compaction's copy of the entries in use: LpPart or u64 (lp_compact_arena)
+//   lpc.tmp           an arena compaction's copy of the entries in use: LpPart or u64 (lp_compact_arena)
 //   am.sort_tmp       scratch of gev_sort_pairs, which gives its size in bytes
-// A buffer of several arrays of one type is typed and its parts are buf + offset (d_snpcnt, d_ld_win, d_sel, d_cnt).
+// A buffer of several arrays of one type is typed and its parts are buf + offset (snp.cnt, bp.ld_win, d_sel, d_cnt).
 template <class T> struct Dev {
     T* p = nullptr;
     ~Dev() { if (p) (void)hipFree(p); }
@@ -157,6 +157,16 @@ struct PinnedBuf {
         return GEV_OK;
     }
 };
+// A stream and an event that their holder owns: null until create(), destroyed with the holder, and converting to the raw handle that
+// every launch, record and wait takes.  Neither is copied or moved: gev_ctx, its scratch sets and PhenoState stay where they were made
+template <class H, hipError_t (*Destroy)(H)> struct Handle {
+    H h = nullptr;
+    Handle() = default; Handle(const Handle&) = delete; Handle& operator=(const Handle&) = delete;
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> { int create(int priority) { HIPC(hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority)); return GEV_OK; } };
+struct Event : Handle<hipEvent_t, hipEventDestroy> { int create(unsigned flags) { HIPC(hipEventCreateWithFlags(&h, flags)); return GEV_OK; } };
 
 struct ChrStatic {                       // one population x one chromosome
     std::vector<u64> rbp; std::vector<double> rprob; u64 bp_dist = 0;
@@ -253,12 +263,24 @@ struct PopState {
     std::vector<double> ad0;
 };
 
+// gev_ctx::Scratch::ev, the events of a scratch set that only order device work against device work.  FORK .. FORKED: joins of the attempt's side streams; RECS: sampling records complete on S (for X); POOL: unit table, work list and their counters complete on X
+enum DevEvent { EV_FORK, EV_AUX, EV_LISTS, EV_FORKED, EV_RECS, EV_POOL, EV_SMALL_DONE, EV_STITCH_DONE, EV_SAMPLED, EV_CHAIN, EV_TAB, N_DEV_EVENTS };
 struct gev_ctx {
+    // The context owns every HIP handle it uses (Stream, Event, Dev, PinnedBuf).  ~gev_ctx waits for the streams and drains the graveyard;
+    // the members then go in reverse declaration order.  The streams are declared FIRST, so they are destroyed LAST: after every Dev has
+    // been freed and every event destroyed.  They are named once as a set, in creation order (gev_create), for ~gev_ctx and gev_sync
+    Stream streams[5];
+    Stream &stream = streams[0], &stream_samp = streams[1], &stream_aux = streams[2], &stream_list = streams[3], &stream_big = streams[4];
+    ~gev_ctx()                              // also of a context gev_create gave up on (null handles); work may be in flight: a pending generation, a head start
+    {
+        (void)hipSetDevice(device);
+        for (Stream& s : streams) if (s) (void)hipStreamSynchronize(s);
+        if (g_graveyard.bytes) g_graveyard.drain(device, false);
+    }
     int device = 0, n_pop = 0, nchr = 0, nphen = 0;
     u32 rp_bits = 0;
     bool ad_effects_shared = false;         // every root population has the same CV effects bit for bit (check_multipop): A/D uses the one-population term table
     bool multipop_ready = false;            // check_multipop has run for the current static inputs (ad_effects_shared, d_aptr / d_dptr are valid); setters clear it
-    hipStream_t stream = nullptr, stream_samp = nullptr, stream_aux = nullptr, stream_list = nullptr;
     float last_ms[4] = {0, 0, 0, 0};
     bool track_intervals = true;
     bool track_pedigree = false;            // gev_set_track_pedigree
@@ -276,11 +298,10 @@ struct gev_ctx {
         bool pool_rebuild = false;                                                            // this attempt rebuilds the free list of the segment pool
         bool cv_count_fused = false;                                                          // k_stitch_small also counts the alleles per CV column (every grid <= 1024 columns)
         bool cv_lanes8 = false;                                                               // every CV plane of the launch has the shape k_stitch_small8 takes (enqueue_tables)
-        hipEvent_t ev_fork = nullptr, ev_aux = nullptr, ev_lists = nullptr, ev_forked = nullptr;   // joins of the attempt's side streams
-        hipEvent_t ev_recs = nullptr, ev_pool = nullptr;                                        // sampling records complete on S (for X); unit table, work list and their counters complete on X
-        hipEvent_t ev_small_done = nullptr, ev_stitch_done = nullptr, t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_status = nullptr, ev_sampled = nullptr;   // the generation's status block (and A/D results) have arrived on the host
+        Event ev[N_DEV_EVENTS], t[6];                    // device-only events, by DevEvent; kernel timings (harvest_timing)
+        Event ev_status;                                 // the generation's status block (and A/D results) have arrived on the host
         bool timing_pending = false, stitch_pending = false;
-        hipEvent_t tc[3] = {nullptr, nullptr, nullptr};   // GEV_TRACE_HOST: start of the attempt's main stream, A/D done, lists joined
+        Event tc[3];                                     // GEV_TRACE_HOST alone: start of the attempt's main stream, A/D done, lists joined
         double th_enq = 0;
         // A head start: the sampling of this set's NEXT generation, enqueued on the head-start stream before its begin call -- by
         // gev_presample for exactly these inputs, or by gev_set_generation_chain's generation in flight (seeds drawn from the predicted
@@ -290,7 +311,6 @@ struct gev_ctx {
         // gev_random_mate: father / mother of this set hold the couples of the next gev_reproduce (couples == NULL) of mate_pop
         bool mated = false, mate_assort = false; int mate_pop = -1; size_t mate_n = 0; unsigned long long mate_epoch = 0;
         Dev<u32> cidx;              // gev_set_track_pedigree: the couple index of every child of a couples list the host passed
-        hipEvent_t ev_chain = nullptr, ev_tab = nullptr;
     } sc[2];
     unsigned gen_counter = 0;
     std::vector<uint8_t> chr_active;        // 0: chromosome held by another context (gev_set_chr_active); sampling chain only
@@ -298,9 +318,8 @@ struct gev_ctx {
     bool migrant_rows = true;               // false (gev_set_migrant_rows): gev_export_rows packs no genotype rows, gev_import_rows rebuilds them from the founder panels
     Dev<u32> d_poff; Dev<uint2> d_prange;                  // rebuild of immigrants' rows: PanelRef per root population, offsets of the rows' parts in the payload
     bool dense = true;                      // false: no resident genotype planes (gev_set_dense_state); lists + CV planes only, output by gev_materialize
-    hipStream_t stream_big = nullptr;
     bool planes_pending = false;            // a stitch may still be writing the current planes (stream_big)
-    hipEvent_t ev_planes = nullptr;         // recorded after the most recent stitch
+    Event ev_planes;                        // recorded after the most recent stitch
     double ms_sum[4] = {0, 0, 0, 0}; unsigned long long ms_count = 0;
     size_t bk_ovf_cap = 1 << 16, nm_ovf_cap = 1 << 16;       // overflow regions of the breakpoint / new-mutation records (GEV_OVF_CAP: initial size, tests force redos with a tiny one)
     int chain_draws = -1;                                    // gev_set_generation_chain: ras_glob_seed() draws the host makes between two generations (-1: unknown, no head start)
@@ -339,20 +358,25 @@ struct gev_ctx {
                           bool assort = false; /* gev_generation_begin_assort: couples made by gev_assort_mate, seeds of reproduce drawn from glob_state */ u32 assort_seed0 = 0; size_t am_nm = 0, am_nf = 0, am_couples = 0;
                           int cidx_mode = 0; /* the children's couple index: 0 = one child per couple, 1 = listed by the host (sc.cidx), 2 = from gev_assort_mate's offspring offsets */ size_t n_couples = 0; } pend;
     DevBytes d_snpmajor, d_text;
-    Dev<u32> d_snpcnt;             // gev_snp_genotype_counts: the two count vectors of a call, created by the first call
-    int n_cu = 0;                  // compute units of the device (bitprod_launch: the tile size), asked for by the first call
-    int dbg_bp_tiles = 0;          // gev_dbg_bitprod_tiles: 0 = the tile size by compute units, 1 = always 64 x 64, 2 = always 128 x 128
-    unsigned long long bp_launches[2] = {0, 0};   // product launches on small / large tiles over the context's life (bitprod_launch)
-    Dev<u64> d_bp_a, d_bp_b; DevBytes d_bp_cnt; Dev<u32> d_bp_out; // the matrix-core products over bit planes (gev_pair_genotype_counts / gev_ind_genotype_counts, gev_ld_counts / gev_ld_scores; every call ends with a stream sync, so one set serves all): the planes of the two sides, the per-row counts, a sub-block's results; created by the first call
-    Dev<u32> d_pair_w, d_ld_win; DevBytes d_ld_score; // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
-    Dev<int32_t> d_ts_trait, d_ts_acc; Dev<uint4> d_ts_b; Dev<long long> d_ts_out; // gev_snp_trait_sums: the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs; created by the first call
-    DevBytes d_ibd_out; Dev<u32> d_ibd_flag; // gev_ibd_sharing / gev_ancestry_bp (gev_ibd.h): a sub-block's results, the flag of a bad root population; created by the first call
-    Dev<u32> d_list_cnt, d_list_off; Dev<unsigned long long> d_list_tot; // the record lists (gev_ibd_segments / gev_roh_segments; every call ends with a stream sync, so one set serves both): a strip's or pass's counts per item, their exclusive scan, their 64-bit sum; created by the first call
-    Dev<gev_ibd_segment> d_ibd_seg; // gev_ibd_segments: a strip's records; created by the first call
-    Dev<u64> d_roh_brk; DevBytes d_roh_out; Dev<u32> d_roh_diff, d_roh_cov; Dev<gev_roh_segment> d_roh_seg; // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records; created by the first call
     size_t dbg_output_chunk = 0;   // gev_dbg_output_chunk: test cap on the units one staging pass of an output call takes (0: the byte budgets)
-    Dev<uint8_t> d_mflag; Dev<u32> d_mblk, d_posm, d_posf, d_pickblk, d_logical, d_globblk /* gev_glob_seeds alone */, d_mstat; Dev<gev_couple> d_couples; Dev<double> d_svf; // gev_random_mate / gev_glob_seeds scratch
-    Dev<double> d_gef_io; DevBytes d_gef_stat; // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
+    Dev<u32> d_logical; Dev<gev_couple> d_couples;           // shared by the mating calls (and gev_download_pedigree): a population's logical -> physical map, the Couples_Info records made last
+    // Scratch of one feature's calls, a sub-state each.  ONE rule serves them all: every call of a feature ends with a sync of its stream,
+    // so one set of buffers serves all its calls; a buffer is created by the first call that needs it, nothing before it.
+    struct BitProdState {   // the matrix-core products over bit planes (gev_bitprod.h) under gev_pair_genotype_counts / gev_ind_genotype_counts (gev_paircount.h), gev_ld_counts / gev_ld_scores (gev_ldcount.h) and the plane side of gev_snp_trait_sums
+        Dev<u64> a, b; DevBytes cnt; Dev<u32> out;         // the planes of the two sides, the per-row counts, a sub-block's results
+        Dev<u32> pair_w, ld_win; DevBytes ld_score;        // gev_ind_genotype_counts: the weights; gev_ld_scores: the windows, the scores
+        int n_cu = 0;                                      // compute units of the device (bitprod_launch: the tile size), asked for by the first call
+        int dbg_tiles = 0;                                 // gev_dbg_bitprod_tiles: 0 = the tile size by compute units, 1 = always 64 x 64, 2 = always 128 x 128
+        unsigned long long launches[2] = {0, 0};           // product launches on small / large tiles over the context's life (bitprod_launch)
+    } bp;
+    struct TraitSumState { Dev<int32_t> trait, acc; Dev<uint4> b; Dev<long long> out; } ts;   // gev_snp_trait_sums (gev_traitsum.h): the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs
+    struct SnpCountState { Dev<u32> cnt; } snp;                                               // gev_snp_genotype_counts (gev_snpcount.h): the two count vectors of a call
+    struct IbdState { DevBytes out; Dev<u32> flag; Dev<gev_ibd_segment> seg; } ibd;           // gev_ibd_sharing / gev_ancestry_bp / gev_ibd_segments (gev_ibd.h): a sub-block's results, the flag of a bad root population, a strip's records
+    struct RohState { Dev<u64> brk; DevBytes out; Dev<u32> diff, cov; Dev<gev_roh_segment> seg; } roh;   // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records
+    struct ListState { Dev<u32> cnt, off; Dev<unsigned long long> tot; } list;                // the record lists of gev_ibd_segments / gev_roh_segments (count_total, fill_list): a strip's or pass's counts per item, their exclusive scan, their 64-bit sum
+    struct MateState { Dev<uint8_t> flag; Dev<u32> blk, posm, posf, pickblk, globblk, stat; Dev<double> svf; } mate;   // gev_random_mate and a fused generation's mating (gev_mate.h, enqueue_mate: on the attempt's streams, which the generation's end waits for); globblk is gev_glob_seeds' alone
+    struct GefState { Dev<double> io; DevBytes stat; } gef;                                   // gev_scale_ad_compute_gef: its vectors; its status words (GEF_*) and {mean, var} of e
+    struct LpcState { Dev<u32> bits, cnt, wpre, len, old_off, new_off; DevBytes tmp; } lpc;   // an arena compaction of the list pieces (lp_compact_arena), which waits for its own scans
     // gev_assort_mate (gev_assort.h): scratch, the last call's result and couple arrays, test knobs
     struct AssortState {
         Dev<u32> wlo, ww, ends, start, cm, cf, om, of, males, females, rnd, scnt, soff, sfill, stgt, ssrc, kept, sorted_m, sorted_f,
@@ -381,7 +405,7 @@ struct gev_ctx {
     struct PhenoState {
         DevBytes res /* result words, then {mean, var} pairs: e, the components, raw A and D */; Dev<u32> starts, blk, globblk; Dev<double> partial, eraw, cval, shift; Dev<NrmStream> streams; Dev<PhTask> tasks;
         PinnedBuf h_res;
-        hipEvent_t ev = nullptr;
+        Event ev;                                          // the result block has arrived in h_res; created by the first call
         bool pending = false; int pop = -1; unsigned long long epoch = 0;
         std::vector<gev_pheno_scheme> scheme; int gen_num = 0, vt_type = 1; u32 glob_state = 0;
         size_t n = 0, words = 0, n_seeds = 0;
@@ -394,7 +418,6 @@ struct gev_ctx {
     // copied to the device on the stream that uses them
     PinnedBuf h_ring; size_t h_ring_off = 0;
     Dev<AdWork> d_adwork2[2]; std::vector<uint8_t> adwork_shadow[2];
-    Dev<u32> d_lpc_bits, d_lpc_cnt, d_lpc_wpre, d_lpc_len, d_lpc_old, d_lpc_new; DevBytes d_lpc_tmp;   // scratch of an arena compaction (lp_compact)
     Dev<u32> d_lp_nitems;                            // [nchr] length of each chromosome's work list of list pieces to build
     std::map<double, GevThr> thr_cache;
 };
@@ -518,27 +541,18 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
     // decides which two streams share a queue.
     int prio_least = 0, prio_greatest = 0;
     HIPC(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    HIPC(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest));
-    HIPC(hipStreamCreateWithPriority(&c->stream_samp, hipStreamNonBlocking, prio_greatest));
-    HIPC(hipStreamCreateWithPriority(&c->stream_aux, hipStreamNonBlocking, prio_greatest));
-    HIPC(hipStreamCreateWithPriority(&c->stream_list, hipStreamNonBlocking, prio_greatest));
-    HIPC(hipStreamCreateWithPriority(&c->stream_big, hipStreamNonBlocking, prio_greatest));
+    for (Stream& s : c->streams) GEVC(s.create(prio_greatest));     // stream, stream_samp, stream_aux, stream_list, stream_big
     // Events that only order DEVICE work against device work carry no system-scope fence (by default recording an event makes the
     // preceding kernel write the dirty L2 lines back to memory: tens of microseconds behind a kernel that wrote 50 MB, paid by
     // whatever small kernel comes next).  Only the event the host waits on before it reads the results (ev_status) keeps it.
     const unsigned dev_only = hipEventDisableTiming | hipEventDisableSystemFence, timed = hipEventDisableSystemFence;
-    HIPC(hipEventCreateWithFlags(&c->ev_planes, dev_only));
+    GEVC(c->ev_planes.create(dev_only));
     c->chr_active.assign(nchr, 1);
     for (auto& sc : c->sc) {
-        HIPC(hipEventCreateWithFlags(&sc.ev_small_done, dev_only));
-        HIPC(hipEventCreateWithFlags(&sc.ev_stitch_done, dev_only));
-        HIPC(hipEventCreateWithFlags(&sc.ev_status, hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&sc.ev_sampled, dev_only));
-        HIPC(hipEventCreateWithFlags(&sc.ev_fork, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_aux, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_lists, dev_only));
-        HIPC(hipEventCreateWithFlags(&sc.ev_forked, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_chain, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_tab, dev_only));
-        HIPC(hipEventCreateWithFlags(&sc.ev_recs, dev_only)); HIPC(hipEventCreateWithFlags(&sc.ev_pool, dev_only));
-        for (auto& e : sc.t) HIPC(hipEventCreateWithFlags(&e, timed));
-        if (g_trace_host) for (auto& e : sc.tc) HIPC(hipEventCreateWithFlags(&e, timed));
+        for (Event& e : sc.ev) GEVC(e.create(dev_only));
+        GEVC(sc.ev_status.create(hipEventDisableTiming));
+        for (Event& e : sc.t) GEVC(e.create(timed));
+        if (g_trace_host) for (Event& e : sc.tc) GEVC(e.create(timed));
     }
     c->pop.resize(n_pop);
     for (auto& P : c->pop) {
@@ -563,23 +577,7 @@ int gev_create(gev_ctx** out, int device, int n_pop, int nchr, int nphen)
     *out = c.release();
     return GEV_OK;
 }
-void gev_destroy(gev_ctx* c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); }
-    if (c->stream_big) { (void)hipStreamSynchronize(c->stream_big); (void)hipStreamDestroy(c->stream_big); }
-    if (c->stream_samp) { (void)hipStreamSynchronize(c->stream_samp); (void)hipStreamDestroy(c->stream_samp); }
-    if (c->stream_aux) { (void)hipStreamSynchronize(c->stream_aux); (void)hipStreamDestroy(c->stream_aux); }
-    if (c->stream_list) { (void)hipStreamSynchronize(c->stream_list); (void)hipStreamDestroy(c->stream_list); }
-    if (g_graveyard.bytes) g_graveyard.drain(c->device, false);
-    if (c->ev_planes) (void)hipEventDestroy(c->ev_planes);
-    for (auto& sc : c->sc) { if (sc.ev_small_done) (void)hipEventDestroy(sc.ev_small_done); if (sc.ev_stitch_done) (void)hipEventDestroy(sc.ev_stitch_done); if (sc.ev_status) (void)hipEventDestroy(sc.ev_status); if (sc.ev_sampled) (void)hipEventDestroy(sc.ev_sampled); if (sc.ev_fork) (void)hipEventDestroy(sc.ev_fork); if (sc.ev_aux) (void)hipEventDestroy(sc.ev_aux); if (sc.ev_lists) (void)hipEventDestroy(sc.ev_lists); if (sc.ev_forked) (void)hipEventDestroy(sc.ev_forked); if (sc.ev_chain) (void)hipEventDestroy(sc.ev_chain); if (sc.ev_tab) (void)hipEventDestroy(sc.ev_tab); if (sc.ev_recs) (void)hipEventDestroy(sc.ev_recs); if (sc.ev_pool) (void)hipEventDestroy(sc.ev_pool); for (auto& e : sc.t) if (e) (void)hipEventDestroy(e); for (auto& e : sc.tc) if (e) (void)hipEventDestroy(e); }
-    hipStream_t s = c->stream;
-    if (c->ph.ev) (void)hipEventDestroy(c->ph.ev);
-    delete c;
-    if (s) (void)hipStreamDestroy(s);
-}
+void gev_destroy(gev_ctx* c) { if (c) delete c; }     // ~gev_ctx: waits for the streams, then releases everything in the order the struct sets
 
 // ---- static inputs -----------------------------------------------------------------------
 // a setter changed what check_multipop compared or tabulated (grids, map ranges, CV positions and effects, the a / d device arrays):
@@ -1229,7 +1227,7 @@ static int ensure_scratch(gev_ctx* c, gev_ctx::Scratch& sc, size_t n_people, boo
 static int claim_scratch(gev_ctx* c, gev_ctx::Scratch& sc, hipStream_t st, bool host_may_block, size_t n_people, bool has_mut)
 {
     if (host_may_block) GEVC(harvest_timing(c, sc)); else GEVC(harvest_sampling_time(sc));
-    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev_stitch_done, 0)); if (host_may_block) sc.stitch_pending = false; }
+    if (sc.stitch_pending) { HIPC(hipStreamWaitEvent(st, sc.ev[EV_STITCH_DONE], 0)); if (host_may_block) sc.stitch_pending = false; }
     if (n_people) GEVC(ensure_scratch(c, sc, n_people, has_mut));
     return GEV_OK;
 }
@@ -1246,7 +1244,7 @@ static int take_head_start(gev_ctx* c, gev_ctx::Scratch& sc, HeadStart::Kind kin
     if (taken && kind == HeadStart::CHAIN) taken = c->chain_valid && c->chain_state == key;
     if (h.kind != HeadStart::NONE && !taken) HIPC(hipStreamSynchronize(c->stream_samp));
     sc.hs = HeadStart(); sc.mated = false; c->chain_valid = false;
-    if (taken) HIPC(hipStreamWaitEvent(c->stream, sc.ev_sampled, 0));     // the head start ran on its own stream
+    if (taken) HIPC(hipStreamWaitEvent(c->stream, sc.ev[EV_SAMPLED], 0));     // the head start ran on its own stream
     return GEV_OK;
 }
 // K1-K3: crossover / mutation sampling and the rand() seed chain; depends on the seeds and n_people only, not on the couples
@@ -1367,25 +1365,25 @@ extern "C++" template <class E> static int lp_compact_arena(gev_ctx* c, uint2* t
 {
     const size_t elem_bytes = sizeof(E);            // k_lpc_copy moves entries of either kind as 64-bit words
     const size_t n_words = ceil_div(std::max<size_t>(*used, 1), 32);
-    GEVC(c->d_lpc_bits.ensure(n_words, st)); GEVC(c->d_lpc_cnt.ensure((n_words + 1), st)); GEVC(c->d_lpc_wpre.ensure((n_words + 1), st));
-    HIPC(hipMemsetAsync(c->d_lpc_bits.p, 0, n_words * sizeof(u32), st));
+    GEVC(c->lpc.bits.ensure(n_words, st)); GEVC(c->lpc.cnt.ensure((n_words + 1), st)); GEVC(c->lpc.wpre.ensure((n_words + 1), st));
+    HIPC(hipMemsetAsync(c->lpc.bits.p, 0, n_words * sizeof(u32), st));
     const unsigned eb = (unsigned)ceil_div(std::max<size_t>(n_entries, 1), 256);
-    hipLaunchKernelGGL(k_lpc_mark, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->d_lpc_bits);
-    hipLaunchKernelGGL(k_lpc_popc, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, st, c->d_lpc_bits, n_words, c->d_lpc_cnt);
+    hipLaunchKernelGGL(k_lpc_mark, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->lpc.bits);
+    hipLaunchKernelGGL(k_lpc_popc, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, st, c->lpc.bits, n_words, c->lpc.cnt);
     KCHECK();
     u32 n_pieces = 0, total = 0;
-    GEVC(scan_u32(c, c->d_lpc_cnt, n_words, c->d_lpc_wpre, &n_pieces));
-    GEVC(c->d_lpc_len.ensure(((size_t)n_pieces + 1), st)); GEVC(c->d_lpc_old.ensure(((size_t)n_pieces + 1), st)); GEVC(c->d_lpc_new.ensure(((size_t)n_pieces + 2), st));
-    hipLaunchKernelGGL(k_lpc_collect, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->d_lpc_bits, c->d_lpc_wpre, c->d_lpc_len, c->d_lpc_old);
+    GEVC(scan_u32(c, c->lpc.cnt, n_words, c->lpc.wpre, &n_pieces));
+    GEVC(c->lpc.len.ensure(((size_t)n_pieces + 1), st)); GEVC(c->lpc.old_off.ensure(((size_t)n_pieces + 1), st)); GEVC(c->lpc.new_off.ensure(((size_t)n_pieces + 2), st));
+    hipLaunchKernelGGL(k_lpc_collect, dim3(eb), dim3(256), 0, st, (const uint2*)tab, n_entries, extra, c->lpc.bits, c->lpc.wpre, c->lpc.len, c->lpc.old_off);
     KCHECK();
-    GEVC(scan_u32(c, c->d_lpc_len, n_pieces, c->d_lpc_new, &total));
+    GEVC(scan_u32(c, c->lpc.len, n_pieces, c->lpc.new_off, &total));
     if (n_pieces) {
-        GEVC(c->d_lpc_tmp.ensure(std::max<size_t>(total, 1) * elem_bytes, st));
-        hipLaunchKernelGGL(k_lpc_copy, dim3((unsigned)ceil_div(n_pieces, 256)), dim3(256), 0, st, (const u64*)arena.p, c->d_lpc_tmp.as<u64>(), c->d_lpc_len, c->d_lpc_old, c->d_lpc_new, (size_t)n_pieces, (u32)(elem_bytes / 8));
+        GEVC(c->lpc.tmp.ensure(std::max<size_t>(total, 1) * elem_bytes, st));
+        hipLaunchKernelGGL(k_lpc_copy, dim3((unsigned)ceil_div(n_pieces, 256)), dim3(256), 0, st, (const u64*)arena.p, c->lpc.tmp.as<u64>(), c->lpc.len, c->lpc.old_off, c->lpc.new_off, (size_t)n_pieces, (u32)(elem_bytes / 8));
         KCHECK();
-        HIPC(hipMemcpyAsync(arena.p, c->d_lpc_tmp.p, (size_t)total * elem_bytes, hipMemcpyDeviceToDevice, st));
+        HIPC(hipMemcpyAsync(arena.p, c->lpc.tmp.p, (size_t)total * elem_bytes, hipMemcpyDeviceToDevice, st));
     }
-    hipLaunchKernelGGL(k_lpc_rewrite, dim3(eb), dim3(256), 0, st, tab, n_entries, extra, c->d_lpc_bits, c->d_lpc_wpre, c->d_lpc_new);
+    hipLaunchKernelGGL(k_lpc_rewrite, dim3(eb), dim3(256), 0, st, tab, n_entries, extra, c->lpc.bits, c->lpc.wpre, c->lpc.new_off);
     KCHECK();
     *used = total;
     return GEV_OK;
@@ -1628,7 +1626,7 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
     const size_t T = n_people * (size_t)nchr, rows = 2 * n_people;
     hipStream_t sb = c->stream_big;
     SampleDev sd = make_sd(c, sc, T);
-    HIPC(hipStreamWaitEvent(sb, sc.ev_small_done, 0));        // recorded once the unit-table and list streams are joined: unit table, work list, sampling results and couples are complete
+    HIPC(hipStreamWaitEvent(sb, sc.ev[EV_SMALL_DONE], 0));        // recorded once the unit-table and list streams are joined: unit table, work list, sampling results and couples are complete
     HIPC(hipEventRecord(sc.t[4], sb));
     if (c->dense && sc.n_chrwork) {
         if (rows > 0x7fffffffull) return fail(GEV_EINVAL, "reproduce: stitch grid too large");
@@ -1647,7 +1645,7 @@ static int enqueue_stitch(gev_ctx* c, gev_ctx::Scratch& sc, int pop, size_t n_pe
         KCHECK();
     }
     HIPC(hipEventRecord(sc.t[3], sb));
-    HIPC(hipEventRecord(sc.ev_stitch_done, sb));
+    HIPC(hipEventRecord(sc.ev[EV_STITCH_DONE], sb));
     HIPC(hipEventRecord(c->ev_planes, sb));
     sc.timing_pending = true; sc.stitch_pending = true; c->planes_pending = true;
     if (c->serialize) {                                  // no overlap: timings are final right away
@@ -1684,17 +1682,17 @@ static int enqueue_mate(gev_ctx* c, hipStream_t st, PopState& P, u32 seed_val, c
         logical = c->d_logical;
     }
     const unsigned nb = (unsigned)ceil_div(n_h, MATE_CHUNK);
-    GEVC(c->d_mflag.ensure(n_h, st)); GEVC(c->d_mblk.ensure(nb, st));
-    GEVC(c->d_posm.ensure(n_h, st)); GEVC(c->d_posf.ensure(n_h, st));
-    hipLaunchKernelGGL(k_mate_flags, dim3(nb), dim3(256), 0, st, P.d_sex[P.cur], logical, d_svf, n_h, seed_val, seed_ptr, c->d_mflag, c->d_mblk);
-    hipLaunchKernelGGL(k_mate_compact, dim3(nb), dim3(256), 0, st, c->d_mflag, n_h, c->d_mblk, nb, c->d_posm, c->d_posf, meta, flags);
+    GEVC(c->mate.flag.ensure(n_h, st)); GEVC(c->mate.blk.ensure(nb, st));
+    GEVC(c->mate.posm.ensure(n_h, st)); GEVC(c->mate.posf.ensure(n_h, st));
+    hipLaunchKernelGGL(k_mate_flags, dim3(nb), dim3(256), 0, st, P.d_sex[P.cur], logical, d_svf, n_h, seed_val, seed_ptr, c->mate.flag, c->mate.blk);
+    hipLaunchKernelGGL(k_mate_compact, dim3(nb), dim3(256), 0, st, c->mate.flag, n_h, c->mate.blk, nb, c->mate.posm, c->mate.posf, meta, flags);
     // candidates of the two pick streams: a draw is rejected with probability < n_h / 2^31
     const u64 n_cand = (u64)pop_size + (u64)(2.0 * (double)pop_size * (double)n_h / 2147483648.0) + 1024;
     const unsigned nbp = (unsigned)ceil_div((size_t)n_cand, REJ_CHUNK);
-    GEVC(c->d_pickblk.ensure(2 * (size_t)nbp, st));
-    hipLaunchKernelGGL(k_pick_count, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, n_cand, c->d_pickblk);
-    hipLaunchKernelGGL(k_pick_emit, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, (u64)pop_size, n_cand, c->d_pickblk,
-                       c->d_posm, c->d_posf, logical, father, mother, d_couples, flags);
+    GEVC(c->mate.pickblk.ensure(2 * (size_t)nbp, st));
+    hipLaunchKernelGGL(k_pick_count, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, n_cand, c->mate.pickblk);
+    hipLaunchKernelGGL(k_pick_emit, dim3(nbp, 2), dim3(256), 0, st, seed_val, seed_ptr, (const u32*)meta, (u64)pop_size, n_cand, c->mate.pickblk,
+                       c->mate.posm, c->mate.posf, logical, father, mother, d_couples, flags);
     KCHECK();
     return GEV_OK;
 }
@@ -1717,7 +1715,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     // the free list of the segment pool; once the sampling records are complete it builds the unit table and the stitch's work list
     // (k_pool_inherit, k_pool_fresh, k_pool_publish), which only the dense stitch and the status block read, next to the CV planes
     // and A/D.  L builds the mutation / interval lists, which nothing else of the generation reads, there too.  The dense stitch has
-    // its own stream as before.  X and L are joined into S before ev_small_done and the status block.  Serialised mode (kernel
+    // its own stream as before.  X and L are joined into S before EV_SMALL_DONE and the status block.  Serialised mode (kernel
     // timings without interference): everything on S, in the order CV planes, A/D, unit table, lists.
     hipStream_t S = c->stream, X = c->serialize ? S : c->stream_aux, L = c->serialize ? S : c->stream_list;
     const size_t T = q.n_people * (size_t)c->nchr;
@@ -1736,7 +1734,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
         } else GEVC(enqueue_glob(sc.globblk, S, q.glob_state, nullptr, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     }
     // (the mating stream starts here: it needs the seeds, not the state behind them)
-    GEVC(hand_over(S, X, sc.ev_fork));
+    GEVC(hand_over(S, X, sc.ev[EV_FORK]));
     if (q.fused && !q.assort) {
         GEVC(enqueue_mate(c, X, P, 0u, gv, q.has_svf ? q.d_svf : nullptr, q.n_people, sc.father, sc.mother,
                           c->d_couples, status + ST_NM_MATE, status + ST_FLAGS));
@@ -1744,28 +1742,28 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (q.fused && !q.assort && c->chain_draws >= 0) {       // where glob_generator will stand when the host comes back for the next generation
         hipLaunchKernelGGL(k_glob_skip, dim3(1), dim3(64), 0, S, (const u32*)(status + ST_GLOB_STATE), (u32)c->chain_draws, status + ST_NEXT_STATE);
         KCHECK();
-        HIPC(hipEventRecord(sc.ev_chain, S));
+        HIPC(hipEventRecord(sc.ev[EV_CHAIN], S));
     }
     GEVC(enqueue_tables(c, sc, q.pop, q.n_people, S));        // (uploaded on S while X mates)
-    GEVC(hand_over(S, X, sc.ev_tab));
+    GEVC(hand_over(S, X, sc.ev[EV_TAB]));
     GEVC(enqueue_pool_free(c, sc, q.pop, X));
-    GEVC(hand_record(X, S, sc.ev_aux));
+    GEVC(hand_record(X, S, sc.ev[EV_AUX]));
     if (q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, 0u, S, gv + 1, gv + 2, /*clear_status=*/false));
     else if (!q.fused && !sampled) GEVC(enqueue_sampling(c, sc, q.pop, q.n_people, q.has_mut, q.seed, S));
-    // (a head start's records were complete before ev_fork, which X has waited for; records sampled here are complete behind ev_recs)
-    if (!sampled) GEVC(hand_record(S, X, sc.ev_recs));
+    // (a head start's records were complete before EV_FORK, which X has waited for; records sampled here are complete behind EV_RECS)
+    if (!sampled) GEVC(hand_record(S, X, sc.ev[EV_RECS]));
     q.th1 = host_ms();
-    GEVC(hand_wait(X, S, sc.ev_aux));
+    GEVC(hand_wait(X, S, sc.ev[EV_AUX]));
     HIPC(hipEventRecord(sc.t[5], S));
-    GEVC(hand_record(S, L, sc.ev_forked));                  // couples and sampling records are complete: what the lists need
+    GEVC(hand_record(S, L, sc.ev[EV_FORKED]));                  // couples and sampling records are complete: what the lists need
     // The unit table, the stitch's work list and their counters: behind the free list in X's own order, next to the CV planes and
     // A/D (nothing on S reads or writes what the pool kernels write).  A repeated attempt's rebuild of the free list is in front of
     // them by the same stream order.  The host enqueues slower than the device runs the first kernels of a generation: the table
     // goes in front of S's CV planes and A/D, because X is idle once it has mated and S waits for the table in the end (both orders
     // measured: DESIGN.md, section 10); the list kernels, which nothing of the generation reads, go last.
-    if (!sampled) GEVC(hand_wait(S, X, sc.ev_recs));
+    if (!sampled) GEVC(hand_wait(S, X, sc.ev[EV_RECS]));
     if (X != S) GEVC(enqueue_pool_assign(c, sc, q.n_people, X));   // (the one difference of serialised mode: there it goes behind A/D, below)
-    GEVC(hand_record(X, S, sc.ev_pool));
+    GEVC(hand_record(X, S, sc.ev[EV_POOL]));
     // the column counters are filled while the planes are written only if the A/D kernels that consume (and clear) them follow in this attempt
     const bool ad_now = c->eager_ad && c->multipop_ready;
     const bool count_cols = ad_now && sc.cv_count_fused && sc.n_cvwork && sc.cv_used_max;
@@ -1781,7 +1779,7 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     if (ad_now) GEVC(enqueue_ad(c, q.pop, c->pop[q.pop].cur ^ 1, q.n_people, sum_counts ? AD_COUNTS_DONE : count_cols ? AD_COUNTS_PARTIAL : AD_COUNTS_NONE, (int)(c->gen_counter & 1)));   // Simulation::ras_compute_AD always follows (src/Simulation.cpp:1935)
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[1], S));
     if (X == S) GEVC(enqueue_pool_assign(c, sc, q.n_people, S));   // serialised: behind A/D, in front of the lists
-    GEVC(hand_wait(S, L, sc.ev_forked));
+    GEVC(hand_wait(S, L, sc.ev[EV_FORKED]));
     // Human::sex of the new generation (:2472) for the next gev_random_mate; a fused generation also sends them to the host with the status block
     HIPC(hipMemcpyAsync(P.d_sex[P.cur ^ 1].p, sc.sex.p, q.n_people, hipMemcpyDeviceToDevice, L));
     if (P.ids_ok) {                                          // the offspring's pedigree ids (:2473-2479) from the parents' rows, into the other buffer
@@ -1796,14 +1794,14 @@ static int enqueue_attempt(gev_ctx* c, int attempt)
     }
     if (q.fused) { HIPC(hipMemcpyAsync(q.hsex, sc.sex.p, q.n_people, hipMemcpyDeviceToHost, L)); HIPC(hipMemcpyAsync(q.hseeds2, gv, 2 * sizeof(u32), hipMemcpyDeviceToHost, L)); }   // (copies nothing on the device waits for: off the main stream)
     GEVC(enqueue_lists(c, sc, q.n_people, q.has_mut, L));
-    GEVC(hand_over(L, S, sc.ev_lists));
-    GEVC(hand_wait(X, S, sc.ev_pool));                        // unit table, work list and the status block's segment totals
+    GEVC(hand_over(L, S, sc.ev[EV_LISTS]));
+    GEVC(hand_wait(X, S, sc.ev[EV_POOL]));                        // unit table, work list and the status block's segment totals
     if (g_trace_host) HIPC(hipEventRecord(sc.tc[2], S));
     // The dense stitch needs the sampling results, the couples and the unit table only, but it saturates HBM, and every
     // latency-bound kernel that runs next to it takes 2-5 times as long (and slows it down in turn).  Behind the whole small work,
     // at the small kernels' priority, it runs alone for 0.16 ms next to the host's turn-around; the NEXT generation's ALU-bound
     // sampling (head start) is what shares the GPU with it (streams).
-    HIPC(hipEventRecord(sc.ev_small_done, S)); GEVC(enqueue_stitch(c, sc, q.pop, q.n_people));
+    HIPC(hipEventRecord(sc.ev[EV_SMALL_DONE], S)); GEVC(enqueue_stitch(c, sc, q.pop, q.n_people));
     HIPC(hipMemcpyAsync(q.hstatus, sc.status.p, q.n_status * sizeof(u32), hipMemcpyDeviceToHost, S));
     HIPC(hipEventRecord(sc.ev_status, S));                  // gev_reproduce_end waits for THIS, not for whatever a head start queued behind it
     sc.th_enq = host_ms();
@@ -1914,13 +1912,13 @@ static int enqueue_chain_head_start(gev_ctx* c)
     // the stitch that last read the other scratch set (the previous generation's) may still be running: the sampling stream waits for
     // it, the host does not (its kernel time is collected when the set's next generation is enqueued)
     GEVC(claim_scratch(c, nx, SS, false, q.n_people, q.has_mut));   // (sizes the buffers in front of the wait below: allocations only, no stream work)
-    HIPC(hipStreamWaitEvent(SS, sc.ev_chain, 0));
+    HIPC(hipStreamWaitEvent(SS, sc.ev[EV_CHAIN], 0));
     GEVC(nx.globvals.ensure((2 + T), SS));
     u32* gv = nx.globvals; u32* status = nx.status;
     HIPC(hipMemsetAsync(nx.status.p, 0, q.n_status * sizeof(u32), SS));
     GEVC(enqueue_glob(nx.globblk, SS, 0u, sc.status + ST_NEXT_STATE, 2 + (q.has_mut ? T : 0), gv, status + ST_GLOB_STATE, status + ST_FLAGS));
     GEVC(enqueue_sampling(c, nx, q.pop, q.n_people, q.has_mut, 0u, SS, gv + 1, gv + 2, /*clear_status=*/false));
-    HIPC(hipEventRecord(nx.ev_sampled, SS));
+    HIPC(hipEventRecord(nx.ev[EV_SAMPLED], SS));
     nx.hs.kind = HeadStart::CHAIN; nx.hs.dropped = false; nx.hs.pop = q.pop; nx.hs.n_people = q.n_people; nx.hs.has_mut = q.has_mut;
     return GEV_OK;
 }
@@ -1980,11 +1978,11 @@ static int generation_begin(gev_ctx* c, int pop, uint32_t glob_state, size_t pop
     }
     GEVC(c->d_couples.ensure(n_people, st));
     if (selection_value_func) {
-        GEVC(c->d_svf.ensure(P.n_people, st));
-        HIPC(hipMemcpyAsync(c->d_svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
+        GEVC(c->mate.svf.ensure(P.n_people, st));
+        HIPC(hipMemcpyAsync(c->mate.svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
         HIPC(hipStreamSynchronize(st));                          // the caller's array is pageable memory of unknown lifetime
     }
-    const double* d_svf = selection_value_func ? c->d_svf : nullptr;
+    const double* d_svf = selection_value_func ? c->mate.svf : nullptr;
     if (dev_sel) d_svf = P.d_sel[P.sbuf] + 2 * P.n_people;     // (enqueued on this stream behind gev_compute_selection: no wait)
     q.has_svf = d_svf != nullptr; q.d_svf = d_svf; q.glob_state = glob_state;
     GEVC(enqueue_attempt(c, 0));
@@ -2150,16 +2148,16 @@ static int random_mate(gev_ctx* c, int pop, uint32_t seed, const double* selecti
     GEVC(claim_scratch(c, sc, st, true, 0, false));
     GEVC(sc.father.ensure(pop_size, st)); GEVC(sc.mother.ensure(pop_size, st));
     GEVC(c->d_couples.ensure(pop_size, st));
-    GEVC(c->d_mstat.ensure(4, st));
-    HIPC(hipMemsetAsync(c->d_mstat.p, 0, 4 * sizeof(u32), st));
+    GEVC(c->mate.stat.ensure(4, st));
+    HIPC(hipMemsetAsync(c->mate.stat.p, 0, 4 * sizeof(u32), st));
     const double* d_svf = nullptr;
     if (selection_value_func) {
-        GEVC(c->d_svf.ensure(P.n_people, st));
-        HIPC(hipMemcpyAsync(c->d_svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
-        d_svf = c->d_svf;
+        GEVC(c->mate.svf.ensure(P.n_people, st));
+        HIPC(hipMemcpyAsync(c->mate.svf.p, selection_value_func, P.n_people * sizeof(double), hipMemcpyHostToDevice, st));
+        d_svf = c->mate.svf;
     }
     if (dev_sel) d_svf = P.d_sel[P.sbuf] + 2 * P.n_people;
-    u32* ms = c->d_mstat;                             // {num_males_mate, num_females_mate, flags}
+    u32* ms = c->mate.stat;                             // {num_males_mate, num_females_mate, flags}
     GEVC(enqueue_mate(c, st, P, (u32)seed, nullptr, d_svf, pop_size, sc.father, sc.mother, couples_out ? c->d_couples : nullptr, ms, ms + 2));
     u32 h[4] = {0, 0, 0, 0};
     HIPC(hipMemcpyAsync(h, ms, sizeof h, hipMemcpyDeviceToHost, st));
@@ -2560,7 +2558,7 @@ int gev_glob_seeds(gev_ctx* c, uint32_t* engine_state, size_t n, uint32_t* out)
     GEVC(c->d_tmp.ensure((n + 4) * sizeof(u32), st));
     u32* vals = c->d_tmp.as<u32>() + 4; u32* stat = c->d_tmp.as<u32>();       // stat = {state, flags}
     HIPC(hipMemsetAsync(stat, 0, 16, st));
-    GEVC(enqueue_glob(c->d_globblk, st, *engine_state, nullptr, n, vals, stat, stat + 1));
+    GEVC(enqueue_glob(c->mate.globblk, st, *engine_state, nullptr, n, vals, stat, stat + 1));
     u32 h[2] = {0, 0};
     HIPC(hipMemcpyAsync(h, stat, sizeof h, hipMemcpyDeviceToHost, st));
     if (out) HIPC(hipMemcpyAsync(out, vals, n * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -2615,18 +2613,17 @@ int gev_presample(gev_ctx* c, int pop, uint32_t seed_reproduce, const uint32_t* 
     GEVC(claim_scratch(c, sc, st, !c->pend.active, n_people, has_mut));
     if (has_mut) HIPC(hipMemcpyAsync(sc.mutseeds.p, c->h_seeds.p, T * sizeof(u32), hipMemcpyHostToDevice, st));
     GEVC(enqueue_sampling(c, sc, pop, n_people, has_mut, seed_reproduce, st));
-    HIPC(hipEventRecord(sc.ev_sampled, st));
+    HIPC(hipEventRecord(sc.ev[EV_SAMPLED], st));
     sc.hs.kind = HeadStart::PRESAMPLE; sc.hs.dropped = false; sc.hs.pop = pop; sc.hs.n_people = n_people; sc.hs.has_mut = has_mut; sc.hs.seed = seed_reproduce;
     return GEV_OK;
 }
-// wait for all device work of the context (both streams) and collect pending kernel timings
+// wait for all device work of the context (every stream) and collect pending kernel timings
 int gev_sync(gev_ctx* c)
 {
     if (!c) return fail(GEV_EINVAL, "null context");
     if (c->pend.active) return fail(GEV_ESTATE, "a gev_reproduce_begin is pending: call gev_reproduce_end first");
     HIPC(hipSetDevice(c->device));
-    HIPC(hipStreamSynchronize(c->stream)); HIPC(hipStreamSynchronize(c->stream_big)); HIPC(hipStreamSynchronize(c->stream_samp));
-    HIPC(hipStreamSynchronize(c->stream_aux)); HIPC(hipStreamSynchronize(c->stream_list));
+    for (Stream& s : c->streams) HIPC(hipStreamSynchronize(s));
     for (auto& sc : c->sc) { GEVC(harvest_timing(c, sc)); sc.stitch_pending = false; }
     c->planes_pending = false;
     if (g_graveyard.bytes) g_graveyard.drain(c->device, false);
@@ -2907,7 +2904,7 @@ static int ph_streams(gev_ctx* c, std::vector<NrmStream>& v, const u32* seeds, u
     KCHECK();
     return GEV_OK;
 }
-enum { GEF_FLAG = 0, GEF_STARTS = 1, GEF_WORDS = 4 };       // d_gef_stat: the short flag, the stream offsets (unused: no stream continues another), then {mean, var} of e
+enum { GEF_FLAG = 0, GEF_STARTS = 1, GEF_WORDS = 4 };       // gef.stat: the short flag, the stream offsets (unused: no stream continues another), then {mean, var} of e
 int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params* par, uint32_t seed,
                              const double* common_sibling, const double* f_father, const double* f_mother,
                              double* additive, double* dominance, double* bv, double* e_noise, double* parental_effect, double* phen_out)
@@ -2922,11 +2919,11 @@ int gev_scale_ad_compute_gef(gev_ctx* c, int pop, int phen, const gev_gef_params
     if (c->ad_cached_pop != pop && c->ad_host_set_pop != pop) GEVC(gev_compute_ad(c, pop, nullptr, nullptr, nullptr, nullptr));      // raw A/D of this generation on the device
     hipStream_t st = c->stream;
     const size_t n = P.n_people;
-    GEVC(c->d_gef_io.ensure(10 * n, st));
-    double* io = c->d_gef_io;
+    GEVC(c->gef.io.ensure(10 * n, st));
+    double* io = c->gef.io;
     double *d_e = io, *d_par = io + n, *d_cs = io + 2 * n, *d_ff = io + 3 * n, *d_out = io + 4 * n;     // d_out: 6 vectors
-    GEVC(c->d_gef_stat.ensure(GEF_WORDS * sizeof(u32) + 2 * sizeof(double), st));
-    u32* stat = c->d_gef_stat.as<u32>(); double* e_stats = (double*)(stat + GEF_WORDS);
+    GEVC(c->gef.stat.ensure(GEF_WORDS * sizeof(u32) + 2 * sizeof(double), st));
+    u32* stat = c->gef.stat.as<u32>(); double* e_stats = (double*)(stat + GEF_WORDS);
     const bool need_par = par->vf > 0;
     if (par->gen_num != 0 && need_par) {
         double* d_fm = d_out;                                                                             // staging before d_out is written
@@ -3844,7 +3841,7 @@ static int download_list(gev_ctx* c, int pop, const char* who, const Dev<u32>& d
     }
     return GEV_OK;
 }
-// The record lists (gev_ibd_segments, gev_roh_segments) in three steps over c->d_list_cnt / d_list_off / d_list_tot.  What the device
+// The record lists (gev_ibd_segments, gev_roh_segments) in three steps over c->list (cnt, off, tot).  What the device
 // and the host forms refuse of a list's own arguments:
 static int list_args(const char* who, const void* out, size_t capacity, const uint64_t* n_total)
 {
@@ -3856,24 +3853,24 @@ static int list_args(const char* who, const void* out, size_t capacity, const ui
 static int count_total(gev_ctx* c, const u32* d_cnt, size_t n, u64* total)
 {
     hipStream_t st = c->stream;
-    GEVC(c->d_list_tot.ensure(1, st));
-    HIPC(hipMemsetAsync(c->d_list_tot.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_total_u32, dim3((unsigned)std::min<size_t>(ceil_div(n, 1024), 1024)), dim3(256), 0, st, d_cnt, n, c->d_list_tot.p);
+    GEVC(c->list.tot.ensure(1, st));
+    HIPC(hipMemsetAsync(c->list.tot.p, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_total_u32, dim3((unsigned)std::min<size_t>(ceil_div(n, 1024), 1024)), dim3(256), 0, st, d_cnt, n, c->list.tot.p);
     KCHECK();
     unsigned long long t = 0;
-    HIPC(hipMemcpyAsync(&t, c->d_list_tot.p, sizeof t, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&t, c->list.tot.p, sizeof t, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     *total = t;
     return GEV_OK;
 }
-// the `total` records (< 2^32: no offset wraps) of the n items counted in c->d_list_cnt into out (host): the counts are scanned into
-// c->d_list_off, launch() enqueues the kernel that fills d_rec (already large enough) from those offsets; returns when they have arrived
+// the `total` records (< 2^32: no offset wraps) of the n items counted in c->list.cnt into out (host): the counts are scanned into
+// c->list.off, launch() enqueues the kernel that fills d_rec (already large enough) from those offsets; returns when they have arrived
 template <class T, class Launch>
 static int fill_list(gev_ctx* c, size_t n, u64 total, const Dev<T>& d_rec, T* out, Launch launch)
 {
     hipStream_t st = c->stream;
-    GEVC(c->d_list_off.ensure(n + 1, st));
-    GEVC(scan_u32_on(st, c->d_sums, c->d_list_cnt.p, n, c->d_list_off.p));
+    GEVC(c->list.off.ensure(n + 1, st));
+    GEVC(scan_u32_on(st, c->d_sums, c->list.cnt.p, n, c->list.off.p));
     GEVC(launch());
     HIPC(hipMemcpyAsync(out, d_rec.p, (size_t)total * sizeof(T), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
@@ -3962,7 +3959,7 @@ int gev_format_bed(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps
 }
 // ---- genotype counts per SNP (gev_snpcount.h) -------------------------------------------------
 // n_het / n_hom_alt of SNPs [snp_begin, +n_snps) over individuals [ind_begin, +n_ind): the plane pass reads the rows in place, the
-// mutation overlay corrects the counts, both add into c->d_snpcnt.  Nothing is staged, so gev_dbg_output_chunk has nothing to cap.
+// mutation overlay corrects the counts, both add into c->snp.cnt.  Nothing is staged, so gev_dbg_output_chunk has nothing to cap.
 int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind, uint32_t* n_het, uint32_t* n_hom_alt)
 {
     const char* who = "snp_genotype_counts";
@@ -3976,8 +3973,8 @@ int gev_snp_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     if (!n_ind) { zero_outs(outs); return GEV_OK; }
     GEVC(ensure_csr(c, pop));                                           // the overlay reads whole lists
     hipStream_t st = c->stream;
-    GEVC(c->d_snpcnt.ensure(2 * n_snps, st));
-    u32* d_het = c->d_snpcnt; u32* d_hom = d_het + n_snps;
+    GEVC(c->snp.cnt.ensure(2 * n_snps, st));
+    u32* d_het = c->snp.cnt; u32* d_hom = d_het + n_snps;
     outs[0].dev = d_het; outs[1].dev = d_hom;
     HIPC(hipMemsetAsync(d_het, 0, 2 * n_snps * sizeof(u32), st));
     const size_t q_first = snp_begin / SNPC_LOCI, n_q = (snp_begin + n_snps - 1) / SNPC_LOCI - q_first + 1;     // the chunks that hold a SNP of the range
@@ -4017,12 +4014,12 @@ extern "C++" {      // (templates cannot have the C linkage of the block this fi
 template <class K, class... Args>
 static int bitprod_launch(gev_ctx* c, K* const (&k)[2], size_t na, size_t nb, size_t tiles, Args... args)
 {
-    if (!c->n_cu) HIPC(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-    const bool large = c->dbg_bp_tiles ? c->dbg_bp_tiles == 2 : tiles >= (size_t)c->n_cu;
+    if (!c->bp.n_cu) HIPC(hipDeviceGetAttribute(&c->bp.n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const bool large = c->bp.dbg_tiles ? c->bp.dbg_tiles == 2 : tiles >= (size_t)c->bp.n_cu;
     const unsigned tile = large ? BP_TILE : BP_TILE / 2;
     hipLaunchKernelGGL(k[large], dim3((unsigned)ceil_div(nb, tile), (unsigned)ceil_div(na, tile)), dim3(256), 0, c->stream, args...);
     KCHECK();
-    c->bp_launches[large]++;
+    c->bp.launches[large]++;
     return GEV_OK;
 }
 // the ten instantiations: [large]; [score][genotype][large]
@@ -4034,7 +4031,7 @@ static constexpr decltype(&k_ld_product<2, false, false>) ld_kernels[2][2][2] = 
 // is prepared once, side B once per sub-block -- O(rows) against the product's O(rows^2); the planes, not the staged rows, are what
 // the product reads, so one staging buffer serves both sides.  prep(side_b, off, n, first) prepares rows [off, +n) of a side into its
 // planes (first: these rows have not been prepared before in this call); products(na, nb, d_out) launches what fills the sub-block's
-// results d_out[o] ([na][nb] in c->d_bp_out, null where outs[o] is).  They are copied into the caller's matrices outs[o] ([n_a][n_b],
+// results d_out[o] ([na][nb] in c->bp.out, null where outs[o] is).  They are copied into the caller's matrices outs[o] ([n_a][n_b],
 // each may be null) and the stream is waited for, sub-block by sub-block.  With no matrix wanted only the sides are prepared: every
 // block row of A and, where b_alone says that something of side B is wanted for itself, every block of B once
 template <int NOUT, class Prep, class Products>
@@ -4043,7 +4040,7 @@ static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, const Op
     hipStream_t st = c->stream;
     bool want_mat = false;
     for (const OptOut& o : outs) want_mat = want_mat || o.host;
-    GEVC(c->d_bp_out.ensure(NOUT * std::min(blk, n_a) * std::min(blk, n_b), st));
+    GEVC(c->bp.out.ensure(NOUT * std::min(blk, n_a) * std::min(blk, n_b), st));
     for (size_t ia = 0; ia < n_a; ia += blk) {
         const size_t na = std::min(blk, n_a - ia);
         GEVC(prep(false, ia, na, true));
@@ -4053,7 +4050,7 @@ static int bitprod_walk(gev_ctx* c, size_t n_a, size_t n_b, size_t blk, const Op
             GEVC(prep(true, ib, nb, ia == 0));
             if (want_mat) {
                 u32* d_out[NOUT];
-                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o].host ? c->d_bp_out + (size_t)o * na * nb : nullptr;
+                for (int o = 0; o < NOUT; o++) d_out[o] = outs[o].host ? c->bp.out + (size_t)o * na * nb : nullptr;
                 GEVC(products(na, nb, d_out));
                 for (int o = 0; o < NOUT; o++) if (outs[o].host) GEVC(copy_out_block(c, outs[o].host, outs[o].el, n_b, ia, ib, na, nb, d_out[o]));
             }
@@ -4069,8 +4066,8 @@ int gev_dbg_bitprod_tiles(gev_ctx* c, int mode, unsigned long long launches[2])
 {
     GEVC(check_not_pending(c));
     if (mode < -1 || mode > 2) return fail(GEV_EINVAL, "dbg_bitprod_tiles: mode %d (0: by compute units, 1: tiles of 64 x 64, 2: tiles of 128 x 128, -1: unchanged)", mode);
-    if (mode >= 0) c->dbg_bp_tiles = mode;
-    if (launches) { launches[0] = c->bp_launches[0]; launches[1] = c->bp_launches[1]; }
+    if (mode >= 0) c->bp.dbg_tiles = mode;
+    if (launches) { launches[0] = c->bp.launches[0]; launches[1] = c->bp.launches[1]; }
     return GEV_OK;
 }
 // ---- genotype counts per individual and per pair of individuals (gev_paircount.h) ---------------
@@ -4122,12 +4119,12 @@ int gev_ind_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, size
     hipStream_t st = c->stream;
     const u32* d_weight = nullptr;
     if (weight) {
-        GEVC(c->d_pair_w.ensure(n_snps, st));
-        HIPC(hipMemcpyAsync(c->d_pair_w.p, weight, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
-        d_weight = c->d_pair_w;
+        GEVC(c->bp.pair_w.ensure(n_snps, st));
+        HIPC(hipMemcpyAsync(c->bp.pair_w.p, weight, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
+        d_weight = c->bp.pair_w;
     }
-    GEVC(c->d_bp_cnt.ensure(n_ind * 16, st));
-    u64* d_ws = c->d_bp_cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
+    GEVC(c->bp.cnt.ensure(n_ind * 16, st));
+    u64* d_ws = c->bp.cnt.as<u64>(); u32* d_het = (u32*)(d_ws + n_ind); u32* d_hom = d_het + n_ind;
     outs[0].dev = d_het; outs[1].dev = d_hom; outs[2].dev = d_ws;
     GEVC(pair_prep_side(c, P, chr, ind_begin, n_ind, snp_begin, n_snps, nullptr, d_weight, d_het, d_hom, wsum ? d_ws : nullptr));
     return copy_back_outs(c, outs);
@@ -4149,15 +4146,15 @@ int gev_pair_genotype_counts(gev_ctx* c, int pop, int chr, size_t snp_begin, siz
     GEVC(ensure_csr(c, pop));
     hipStream_t st = c->stream;
     const size_t blk = pair_block(c, snp_begin, n_snps), ba = std::min(blk, n_a), n_w4 = gev_bp_words4(snp_begin, n_snps);
-    GEVC(c->d_bp_cnt.ensure((ba + std::min(blk, n_b)) * sizeof(u32), st));
-    u32* d_hom_a = c->d_bp_cnt.as<u32>(); u32* d_hom_b = d_hom_a + ba;
+    GEVC(c->bp.cnt.ensure((ba + std::min(blk, n_b)) * sizeof(u32), st));
+    u32* d_hom_a = c->bp.cnt.as<u32>(); u32* d_hom_b = d_hom_a + ba;
     return bitprod_walk(c, n_a, n_b, blk, outs, false,
         [&](bool side_b, size_t off, size_t n, bool) -> int {
-            return pair_prep_side(c, P, chr, (side_b ? b_begin : a_begin) + off, n, snp_begin, n_snps, side_b ? &c->d_bp_b : &c->d_bp_a, nullptr, nullptr, side_b ? d_hom_b : d_hom_a, nullptr);
+            return pair_prep_side(c, P, chr, (side_b ? b_begin : a_begin) + off, n, snp_begin, n_snps, side_b ? &c->bp.b : &c->bp.a, nullptr, nullptr, side_b ? d_hom_b : d_hom_a, nullptr);
         },
         [&](size_t na, size_t nb, u32* const* d_out) -> int {
             const size_t pad_a = round_up(na, BP_TILE), pad_b = round_up(nb, BP_TILE);
-            const u64 *xa = c->d_bp_a, *xb = c->d_bp_b;
+            const u64 *xa = c->bp.a, *xb = c->bp.b;
             return bitprod_launch(c, pair_kernels, na, nb, (pad_a / BP_TILE) * (pad_b / BP_TILE), xa, xa + n_w4 * pad_a, (u32)pad_a, xb, xb + n_w4 * pad_b, (u32)pad_b, (u32)n_w4,
                                   (const u32*)d_hom_a, (const u32*)d_hom_b, (u32)na, (u32)nb, d_out[0], d_out[1], d_out[2]);
         });
@@ -4228,14 +4225,14 @@ int gev_ld_counts(gev_ctx* c, int pop, int chr_a, size_t a_begin, size_t n_a, in
     hipStream_t st = c->stream;
     const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind);
-    GEVC(c->d_bp_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
-    u32* d_cnt_a = c->d_bp_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
+    GEVC(c->bp.cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
+    u32* d_cnt_a = c->bp.cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
     LdSide A, B;
     return bitprod_walk(c, n_a, n_b, blk, mats, want_b,
         [&](bool side_b, size_t off, size_t n, bool first) -> int {                           // a side's vectors come back the first time its SNPs are prepared
             LdSide& S = side_b ? B : A; uint32_t* const* vec = side_b ? vec_b : vec_a;
-            if (side_b) GEVC(ld_prep_side(c, pop, chr_b, b_begin + off, n, ind_begin, n_ind, c->d_bp_b, d_cnt_b, bb, S));
-            else GEVC(ld_prep_side(c, pop, chr_a, a_begin + off, n, ind_begin, n_ind, c->d_bp_a, d_cnt_a, ba, S));
+            if (side_b) GEVC(ld_prep_side(c, pop, chr_b, b_begin + off, n, ind_begin, n_ind, c->bp.b, d_cnt_b, bb, S));
+            else GEVC(ld_prep_side(c, pop, chr_a, a_begin + off, n, ind_begin, n_ind, c->bp.a, d_cnt_a, ba, S));
             u32* const d_vec[3] = {S.c, S.het, S.hom};
             for (int o = 0; o < 3 && first; o++) if (vec[o]) HIPC(hipMemcpyAsync(vec[o] + off, d_vec[o], n * sizeof(u32), hipMemcpyDeviceToHost, st));
             return GEV_OK;
@@ -4275,12 +4272,12 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     hipStream_t st = c->stream;
     const size_t blk = ld_block(c, P.n_people, ind_begin, n_ind), ba = std::min(blk, n_snps), bb = std::min<size_t>(blk, P.cs[chr].L);
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind);
-    GEVC(c->d_bp_cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
-    GEVC(c->d_ld_win.ensure(2 * n_snps, st));
-    GEVC(c->d_ld_score.ensure(n_snps * (sizeof(u64) + sizeof(u32)), st));
-    u32* d_cnt_a = c->d_bp_cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
-    u32* d_lo = c->d_ld_win; u32* d_hi = d_lo + n_snps;
-    u64* d_score = c->d_ld_score.as<u64>(); u32* d_terms = (u32*)(d_score + n_snps);
+    GEVC(c->bp.cnt.ensure(3 * (ba + bb) * sizeof(u32), st));
+    GEVC(c->bp.ld_win.ensure(2 * n_snps, st));
+    GEVC(c->bp.ld_score.ensure(n_snps * (sizeof(u64) + sizeof(u32)), st));
+    u32* d_cnt_a = c->bp.cnt.as<u32>(); u32* d_cnt_b = d_cnt_a + 3 * ba;
+    u32* d_lo = c->bp.ld_win; u32* d_hi = d_lo + n_snps;
+    u64* d_score = c->bp.ld_score.as<u64>(); u32* d_terms = (u32*)(d_score + n_snps);
     outs[0].dev = d_score; outs[1].dev = d_terms;
     HIPC(hipMemcpyAsync(d_lo, win_lo, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
     HIPC(hipMemcpyAsync(d_hi, win_hi, n_snps * sizeof(u32), hipMemcpyHostToDevice, st));
@@ -4288,11 +4285,11 @@ int gev_ld_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps,
     for (size_t ia = 0; ia < n_snps; ia += blk) {
         const size_t na = std::min(blk, n_snps - ia);
         LdSide A, B;
-        GEVC(ld_prep_side(c, pop, chr, snp_begin + ia, na, ind_begin, n_ind, c->d_bp_a, d_cnt_a, ba, A));
+        GEVC(ld_prep_side(c, pop, chr, snp_begin + ia, na, ind_begin, n_ind, c->bp.a, d_cnt_a, ba, A));
         const size_t u0 = win_lo[ia], u1 = win_hi[ia + na - 1];
         for (size_t ib = u0; ib < u1; ib += blk) {
             const size_t nb = std::min(blk, u1 - ib);
-            GEVC(ld_prep_side(c, pop, chr, ib, nb, ind_begin, n_ind, c->d_bp_b, d_cnt_b, bb, B));
+            GEVC(ld_prep_side(c, pop, chr, ib, nb, ind_begin, n_ind, c->bp.b, d_cnt_b, bb, B));
             const LdScoreArgs sa{A.c, A.het, A.hom, B.c, B.het, B.hom, d_lo + ia, d_hi + ia, d_score + ia, d_terms + ia, (u64)n_ind, (u32)ib};
             size_t band_tiles = 0;                                                             // the large tiles of the sub-block that the band touches
             for (size_t r0 = 0; r0 < na; r0 += BP_TILE) {
@@ -4348,7 +4345,7 @@ static void ts_zero(size_t n_snps, size_t n_traits, int64_t* gsum, int64_t* hets
     zero_outs(outs);
 }
 // The SNPs are walked in blocks of at most ld_block() (gev_dbg_output_chunk caps them): a block is one snp_major_device pass and one
-// k_ld_prep into c->d_bp_a; the traits' operand bytes are made once per call and serve every block; a block's sums are copied out before the
+// k_ld_prep into c->bp.a; the traits' operand bytes are made once per call and serve every block; a block's sums are copied out before the
 // next block's kernels run (stream order), and the call returns when the last ones have arrived.
 int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
                        const int32_t* trait, size_t n_traits, int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
@@ -4366,34 +4363,34 @@ int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_
     hipStream_t st = c->stream;
     const size_t blk = std::min(ld_block(c, P.n_people, ind_begin, n_ind), n_snps), pad = round_up(blk, BP_TILE);
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind), n_cg = ceil_div(n_traits, 4), slices = ceil_div(n_w4, GEV_TS_SLICE_W);
-    GEVC(c->d_bp_cnt.ensure(3 * blk * sizeof(u32), st));
+    GEVC(c->bp.cnt.ensure(3 * blk * sizeof(u32), st));
     if (want_sums) {
-        GEVC(c->d_ts_trait.ensure(n_traits * n_ind, st));
-        GEVC(c->d_ts_b.ensure(n_cg * n_w4 * 32, st));                                        // 32 individuals x 16 columns a word: 512 bytes
-        GEVC(c->d_ts_acc.ensure(2 * n_cg * pad * 16, st));
-        GEVC(c->d_ts_out.ensure(2 * n_traits * blk, st));
-        HIPC(hipMemcpyAsync(c->d_ts_trait.p, trait, n_traits * n_ind * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)ceil_div(n_cg * (n_w4 / 4) * 128, 256)), dim3(256), 0, st, c->d_ts_trait, (u32)n_traits,
-                           (u64)ind_begin, (u64)n_ind, (u32)n_w4, (u32)n_cg, c->d_ts_b);
+        GEVC(c->ts.trait.ensure(n_traits * n_ind, st));
+        GEVC(c->ts.b.ensure(n_cg * n_w4 * 32, st));                                        // 32 individuals x 16 columns a word: 512 bytes
+        GEVC(c->ts.acc.ensure(2 * n_cg * pad * 16, st));
+        GEVC(c->ts.out.ensure(2 * n_traits * blk, st));
+        HIPC(hipMemcpyAsync(c->ts.trait.p, trait, n_traits * n_ind * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)ceil_div(n_cg * (n_w4 / 4) * 128, 256)), dim3(256), 0, st, c->ts.trait, (u32)n_traits,
+                           (u64)ind_begin, (u64)n_ind, (u32)n_w4, (u32)n_cg, c->ts.b);
         KCHECK();
     }
     for (size_t off = 0; off < n_snps; off += blk) {
         const size_t n = std::min(blk, n_snps - off);
         LdSide A;
-        GEVC(ld_prep_side(c, pop, chr, snp_begin + off, n, ind_begin, n_ind, c->d_bp_a, c->d_bp_cnt.as<u32>(), blk, A));
+        GEVC(ld_prep_side(c, pop, chr, snp_begin + off, n, ind_begin, n_ind, c->bp.a, c->bp.cnt.as<u32>(), blk, A));
         if (n_het) HIPC(hipMemcpyAsync(n_het + off, A.het, n * sizeof(u32), hipMemcpyDeviceToHost, st));
         if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt + off, A.hom, n * sizeof(u32), hipMemcpyDeviceToHost, st));
         if (!want_sums) continue;
-        HIPC(hipMemsetAsync(c->d_ts_acc.p, 0, 2 * n_cg * A.n_pad * 16 * sizeof(int), st));
+        HIPC(hipMemsetAsync(c->ts.acc.p, 0, 2 * n_cg * A.n_pad * 16 * sizeof(int), st));
         for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535)                                        // (a grid's z)
             hipLaunchKernelGGL(k_ts_product, dim3((unsigned)(A.n_pad / BP_TILE), (unsigned)slices, (unsigned)std::min<size_t>(n_cg - cg0, 65535)), dim3(256), 0, st,
-                               A.plane, (u32)A.n_pad, (u32)n_w4, c->d_ts_b, (u32)n_cg, (u32)cg0, c->d_ts_acc);
-        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_traits * n, 256)), dim3(256), 0, st, c->d_ts_acc, (u32)A.n_pad, (u32)n_cg,
-                           (u32)n_traits, (u32)n, (u32)blk, c->d_ts_out);
+                               A.plane, (u32)A.n_pad, (u32)n_w4, c->ts.b, (u32)n_cg, (u32)cg0, c->ts.acc);
+        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_traits * n, 256)), dim3(256), 0, st, c->ts.acc, (u32)A.n_pad, (u32)n_cg,
+                           (u32)n_traits, (u32)n, (u32)blk, c->ts.out);
         KCHECK();
         int64_t* const outs[2] = {gsum, hetsum};
         for (int o = 0; o < 2; o++)
-            if (outs[o]) HIPC(hipMemcpy2DAsync(outs[o] + off, n_snps * sizeof(int64_t), c->d_ts_out + (size_t)o * n_traits * blk, blk * sizeof(int64_t),
+            if (outs[o]) HIPC(hipMemcpy2DAsync(outs[o] + off, n_snps * sizeof(int64_t), c->ts.out + (size_t)o * n_traits * blk, blk * sizeof(int64_t),
                                                n * sizeof(int64_t), n_traits, hipMemcpyDeviceToHost, st));
     }
     HIPC(hipStreamSynchronize(st));
@@ -4423,7 +4420,7 @@ static int ibd_begin(gev_ctx* c, int pop, int chr, const char* who)
     return ensure_csr(c, pop);
 }
 // The pair matrix is walked in sub-blocks of at most 4096 rows a side (gev_dbg_output_chunk caps them): a sub-block is one launch of
-// k_ibd_tiles into c->d_ibd_out, copied into the caller's matrices before the next one's kernel runs.
+// k_ibd_tiles into c->ibd.out, copied into the caller's matrices before the next one's kernel runs.
 int gev_ibd_sharing(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b,
                     uint64_t min_bp, uint64_t* shared_bp, uint32_t* n_seg, uint64_t* max_seg)
 {
@@ -4439,11 +4436,11 @@ int gev_ibd_sharing(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, 
     const u32* poff_b = PB.st[chr].poff[PB.cur]; const gev_part* parts_b = PB.st[chr].parts[PB.cur];
     const size_t blk = std::min<size_t>(output_chunk(c, (size_t)1 << 30, 1), 4096), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
     const size_t per_pair = (shared_bp ? 8 : 0) + (max_seg ? 8 : 0) + (n_seg ? 4 : 0);
-    GEVC(c->d_ibd_out.ensure(ba * bb * per_pair, st));
+    GEVC(c->ibd.out.ensure(ba * bb * per_pair, st));
     // the 8-byte matrices first: every part of the buffer begins on a multiple of its element
-    u64* d_sh = shared_bp ? c->d_ibd_out.as<u64>() : nullptr;
-    u64* d_mx = max_seg ? c->d_ibd_out.as<u64>() + (shared_bp ? ba * bb : 0) : nullptr;
-    u32* d_ns = n_seg ? (u32*)(c->d_ibd_out.as<u64>() + ((shared_bp ? 1 : 0) + (max_seg ? 1 : 0)) * ba * bb) : nullptr;
+    u64* d_sh = shared_bp ? c->ibd.out.as<u64>() : nullptr;
+    u64* d_mx = max_seg ? c->ibd.out.as<u64>() + (shared_bp ? ba * bb : 0) : nullptr;
+    u32* d_ns = n_seg ? (u32*)(c->ibd.out.as<u64>() + ((shared_bp ? 1 : 0) + (max_seg ? 1 : 0)) * ba * bb) : nullptr;
     for (size_t ia = 0; ia < n_a; ia += blk)
         for (size_t ib = 0; ib < n_b; ib += blk) {
             const size_t na = std::min(blk, n_a - ia), nb = std::min(blk, n_b - ib);
@@ -4466,15 +4463,15 @@ int gev_ancestry_bp(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_row
     if (n_rows > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: %zu rows in one call", who, n_rows);
     hipStream_t st = c->stream;
     const size_t npop = (size_t)c->n_pop;
-    GEVC(c->d_ibd_out.ensure(n_rows * (8 * npop + 4), st));
-    GEVC(c->d_ibd_flag.ensure(1, st));
-    HIPC(hipMemsetAsync(c->d_ibd_flag.p, 0, sizeof(u32), st));
-    u64* d_bp = c->d_ibd_out.as<u64>(); u32* d_np = (u32*)(d_bp + n_rows * npop);
+    GEVC(c->ibd.out.ensure(n_rows * (8 * npop + 4), st));
+    GEVC(c->ibd.flag.ensure(1, st));
+    HIPC(hipMemsetAsync(c->ibd.flag.p, 0, sizeof(u32), st));
+    u64* d_bp = c->ibd.out.as<u64>(); u32* d_np = (u32*)(d_bp + n_rows * npop);
     hipLaunchKernelGGL(k_ancestry_bp, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, st, (const u32*)P.st[chr].poff[P.cur], (const gev_part*)P.st[chr].parts[P.cur],
-                       (u64)row_begin, (u32)n_rows, c->n_pop, d_bp, d_np, c->d_ibd_flag.p);
+                       (u64)row_begin, (u32)n_rows, c->n_pop, d_bp, d_np, c->ibd.flag.p);
     KCHECK();
     u32 flag = 0;
-    HIPC(hipMemcpyAsync(&flag, c->d_ibd_flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&flag, c->ibd.flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     if (flag) return fail(GEV_EINVAL, "%s: a part of population %d names a root population outside [0, %d)", who, pop, c->n_pop);
     const OptOut outs[2] = {{bp, sizeof(u64), n_rows * npop, d_bp}, {n_parts, sizeof(u32), n_rows, d_np}};
@@ -4520,22 +4517,22 @@ static int ibd_seg_launch(gev_ctx* c, const IbdSegCall& q, size_t row0, size_t r
     const auto kernel = fill ? k_ibd_segments<true> : k_ibd_segments<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, q.poff_a, q.parts_a, (u64)(q.a_begin + row0), (u32)rows,
                        q.poff_b, q.parts_b, (u64)q.b_begin, (u32)q.n_b, q.min_bp, q.upper, ta_log2, (u32)tiles_b,
-                       fill ? c->d_list_off.p : c->d_list_cnt.p, c->d_ibd_seg.p);
+                       fill ? c->list.off.p : c->list.cnt.p, c->ibd.seg.p);
     KCHECK();
     return GEV_OK;
 }
-// the strip's counts per pair into c->d_list_cnt; total: their sum in 64 bits, in host memory when this returns (null: not wanted)
+// the strip's counts per pair into c->list.cnt; total: their sum in 64 bits, in host memory when this returns (null: not wanted)
 static int ibd_seg_count(gev_ctx* c, const IbdSegCall& q, size_t row0, size_t rows, u64* total)
 {
     hipStream_t st = c->stream;
     const size_t np = rows * q.n_b;
-    GEVC(c->d_list_cnt.ensure(np, st));
-    if (q.upper) HIPC(hipMemsetAsync(c->d_list_cnt.p, 0, np * sizeof(u32), st));             // (pairs on or below the diagonal are not visited)
+    GEVC(c->list.cnt.ensure(np, st));
+    if (q.upper) HIPC(hipMemsetAsync(c->list.cnt.p, 0, np * sizeof(u32), st));             // (pairs on or below the diagonal are not visited)
     GEVC(ibd_seg_launch(c, q, row0, rows, false));
-    return total ? count_total(c, c->d_list_cnt.p, np, total) : GEV_OK;
+    return total ? count_total(c, c->list.cnt.p, np, total) : GEV_OK;
 }
 // Two phases.  Every strip is counted and its 64-bit total kept on the host: n_total.  If out holds them, each strip is counted again
-// (a request of one strip still has its counts), scanned and filled into c->d_ibd_seg, which is copied to out at the running offset
+// (a request of one strip still has its counts), scanned and filled into c->ibd.seg, which is copied to out at the running offset
 // before the next strip's fill overwrites it.  Strips are whole A rows against all B rows, so row-major order inside a strip is the
 // order of the list and strips concatenate.
 int gev_ibd_segments(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b,
@@ -4572,12 +4569,12 @@ int gev_ibd_segments(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a,
     }
     *n_total = total;
     if (!total || total > capacity) return GEV_OK;
-    GEVC(c->d_ibd_seg.ensure((size_t)largest, st));
+    GEVC(c->ibd.seg.ensure((size_t)largest, st));
     size_t done = 0;
     for (const IbdStrip& s : strips) {
         if (!s.total) continue;
         if (strips.size() > 1) GEVC(ibd_seg_count(c, q, s.row0, s.rows, nullptr));
-        GEVC(fill_list(c, s.rows * n_b, s.total, c->d_ibd_seg, out + done, [&] { return ibd_seg_launch(c, q, s.row0, s.rows, true); }));
+        GEVC(fill_list(c, s.rows * n_b, s.total, c->ibd.seg, out + done, [&] { return ibd_seg_launch(c, q, s.row0, s.rows, true); }));
         done += (size_t)s.total;
     }
     return GEV_OK;
@@ -4609,16 +4606,16 @@ static int roh_begin(gev_ctx* c, int pop, int chr, const char* who, const gev_ro
     GEVC(ensure_csr(c, pop));
     return roh_args(who, q, snp_begin, n_snps, c->pop[pop].cs[chr].L, ind_begin, n_ind, c->pop[pop].n_people);
 }
-// the break bit plane of the chromosome into c->d_roh_brk (brk: null for max_gap_bp == 0, which has no breaks)
+// the break bit plane of the chromosome into c->roh.brk (brk: null for max_gap_bp == 0, which has no breaks)
 static int roh_breaks(gev_ctx* c, ChrStatic& S, u64 max_gap_bp, const uint4*& brk)
 {
     brk = nullptr;
     if (!max_gap_bp) return GEV_OK;
     const size_t n_words = 2 * ceil_div(S.L, 128);
-    GEVC(c->d_roh_brk.ensure(n_words, c->stream));
-    hipLaunchKernelGGL(k_roh_breaks, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, c->stream, (const u64*)S.d_pos, (u64)S.L, max_gap_bp, (u32)n_words, c->d_roh_brk.p);
+    GEVC(c->roh.brk.ensure(n_words, c->stream));
+    hipLaunchKernelGGL(k_roh_breaks, dim3((unsigned)ceil_div(n_words, 256)), dim3(256), 0, c->stream, (const u64*)S.d_pos, (u64)S.L, max_gap_bp, (u32)n_words, c->roh.brk.p);
     KCHECK();
-    brk = (const uint4*)c->d_roh_brk.p;
+    brk = (const uint4*)c->roh.brk.p;
     return GEV_OK;
 }
 // one request's constants, and a scan of the n individuals staged from individual ind0 on
@@ -4645,14 +4642,14 @@ int gev_roh_summary(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snp
     if (!n_roh && !roh_bp && !roh_snps && !max_bp && !cover) return GEV_OK;
     hipStream_t st = c->stream;
     // the 8-byte vectors first: every part of the buffer begins on a multiple of its element
-    GEVC(c->d_roh_out.ensure(n_ind * 24, st));
-    u64* d_bp = c->d_roh_out.as<u64>(); u64* d_mx = d_bp + n_ind; u32* d_n = (u32*)(d_mx + n_ind); u32* d_sn = d_n + n_ind;
+    GEVC(c->roh.out.ensure(n_ind * 24, st));
+    u64* d_bp = c->roh.out.as<u64>(); u64* d_mx = d_bp + n_ind; u32* d_n = (u32*)(d_mx + n_ind); u32* d_sn = d_n + n_ind;
     outs[0].dev = d_n; outs[1].dev = d_bp; outs[2].dev = d_sn; outs[3].dev = d_mx;
     u32* d_diff = nullptr;
     if (cover) {
-        GEVC(c->d_roh_diff.ensure(n_snps + 1, st));
-        GEVC(c->d_roh_cov.ensure(n_snps + 1, st));
-        d_diff = c->d_roh_diff.p;
+        GEVC(c->roh.diff.ensure(n_snps + 1, st));
+        GEVC(c->roh.cov.ensure(n_snps + 1, st));
+        d_diff = c->roh.diff.p;
         HIPC(hipMemsetAsync(d_diff, 0, (n_snps + 1) * sizeof(u32), st));
     }
     RohCall r = {S.d_pos, nullptr, (u32)(S.stride / 16), (u32)snp_begin, (u32)n_snps, *q};
@@ -4661,23 +4658,23 @@ int gev_roh_summary(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snp
         return roh_launch(c, r, ROH_SUMMARY, ind_begin + i, n, d_n + i, d_bp + i, d_sn + i, d_mx + i, d_diff, nullptr, nullptr);
     }));
     if (cover) {
-        GEVC(scan_u32_on(st, c->d_sums, d_diff, n_snps, c->d_roh_cov.p));      // entry j + 1 = the inclusive sum up to j (mod 2^32, as the -1 entries are)
-        HIPC(hipMemcpyAsync(cover, c->d_roh_cov.p + 1, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
+        GEVC(scan_u32_on(st, c->d_sums, d_diff, n_snps, c->roh.cov.p));      // entry j + 1 = the inclusive sum up to j (mod 2^32, as the -1 entries are)
+        HIPC(hipMemcpyAsync(cover, c->roh.cov.p + 1, n_snps * sizeof(u32), hipMemcpyDeviceToHost, st));
     }
     return copy_back_outs(c, outs);
 }
-// the counts of the staged pass into c->d_list_cnt (already large enough) and their 64-bit sum into *total (in host memory when this returns)
+// the counts of the staged pass into c->list.cnt (already large enough) and their 64-bit sum into *total (in host memory when this returns)
 static int roh_count_pass(gev_ctx* c, const RohCall& r, size_t ind0, size_t n, u64* total)
 {
-    GEVC(roh_launch(c, r, ROH_COUNT, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_list_cnt.p, nullptr));
-    return count_total(c, c->d_list_cnt.p, n, total);
+    GEVC(roh_launch(c, r, ROH_COUNT, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->list.cnt.p, nullptr));
+    return count_total(c, c->list.cnt.p, n, total);
 }
-// the `total` records of the staged and counted pass into out (host) through c->d_roh_seg
+// the `total` records of the staged and counted pass into out (host) through c->roh.seg
 static int roh_fill_pass(gev_ctx* c, const RohCall& r, size_t ind0, size_t n, u64 total, gev_roh_segment* out)
 {
     if (total >> 32) return fail(GEV_EUNSUPPORTED, "roh_segments: %llu records in one pass", (unsigned long long)total);
-    GEVC(c->d_roh_seg.ensure((size_t)total, c->stream));
-    return fill_list(c, n, total, c->d_roh_seg, out, [&] { return roh_launch(c, r, ROH_FILL, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->d_list_off.p, c->d_roh_seg.p); });
+    GEVC(c->roh.seg.ensure((size_t)total, c->stream));
+    return fill_list(c, n, total, c->roh.seg, out, [&] { return roh_launch(c, r, ROH_FILL, ind0, n, nullptr, nullptr, nullptr, nullptr, nullptr, c->list.off.p, c->roh.seg.p); });
 }
 // A request of one pass counts, scans and fills on the same staged rows.  A request of several passes counts them all (n_total), and if
 // out holds the records stages each again, counts it (the offsets of its fill) and fills: passes are runs of whole individuals in order,
@@ -4692,7 +4689,7 @@ int gev_roh_segments(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_sn
     if (!n_ind || !n_snps) { *n_total = 0; return GEV_OK; }
     const size_t per_pass = std::min(output_chunk(c, 256u << 20, 2 * S.stride), n_ind);      // (what ind_major_chunks takes)
     const bool one_pass = per_pass == n_ind;
-    GEVC(c->d_list_cnt.ensure(per_pass, c->stream));
+    GEVC(c->list.cnt.ensure(per_pass, c->stream));
     RohCall r = {S.d_pos, nullptr, (u32)(S.stride / 16), (u32)snp_begin, (u32)n_snps, *q};
     GEVC(roh_breaks(c, S, q->max_gap_bp, r.brk));
     u64 total = 0;
@@ -5035,7 +5032,7 @@ static int ph_enqueue(gev_ctx* c)
     GEVC(ph_var(c, comp, n, 1, n, (unsigned)nphen * PH_COMP, comp_stats));           // CommFunc::var of A D G C E F P (:2023-2037)
     GEVC(H.h_res.ensure(res_bytes, res_bytes * 2 + 256, st));
     HIPC(hipMemcpyAsync(H.h_res.p, H.res.p, res_bytes, hipMemcpyDeviceToHost, st));
-    if (!H.ev) HIPC(hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
+    if (!H.ev) GEVC(H.ev.create(hipEventDisableTiming));
     HIPC(hipEventRecord(H.ev, st));
     return GEV_OK;
 }
