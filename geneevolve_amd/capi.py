@@ -187,6 +187,8 @@ ABI = {
     "dbg_ld_r2_q40_host": "int: i64* u64* u64* size u64*",
     "snp_trait_sums": "int: ctx* int int size size size size i32* size i64* i64* u32* u32*",
     "dbg_trait_sums_host": "int: u64* size size size size size size size i32* size i64* i64* u32* u32*",
+    "ind_scores": "int: ctx* int int size size size size i32* size i64* i64*",
+    "dbg_ind_scores_host": "int: u64* size size size size size size size i32* size i64* i64*",
     "ibd_sharing": "int: ctx* int int size size int size size u64 u64* u32* u64*",
     "ancestry_bp": "int: ctx* int int size size u64* u32*",
     "dbg_ibd_host": "int: part* u64* size part* u64* size u64 u64* u32* u64*",
@@ -340,6 +342,20 @@ def _trait_sum_outs(n_traits, n_snps):
     n_snps = max(n_snps, 0)
     return (np.empty((n_traits, n_snps), dtype=np.int64), np.empty((n_traits, n_snps), dtype=np.int64),
             np.empty(n_snps, dtype=np.uint32), np.empty(n_snps, dtype=np.uint32))
+
+
+def _weights(weight, n_snps):
+    """weight columns as the score calls take them: int32 [n_scores][n_snps], a single vector as one column"""
+    weight = _arr(weight, np.int32)
+    if weight.ndim == 1:
+        weight = weight.reshape(1, -1)
+    assert weight.ndim == 2 and weight.shape[1] == max(n_snps, 0), "one weight per column and SNP of the range"
+    return weight
+
+
+def _score_outs(n_scores, n_ind, want=(True, True)):
+    """the two matrices of the score calls (None where not wanted)"""
+    return tuple(np.empty((n_scores, max(n_ind, 0)), dtype=np.int64) if w else None for w in want)
 
 
 def _ibd_outs(n_a, n_b, want=(True, True, True)):
@@ -523,6 +539,20 @@ class GevLibrary:
         trait = _traits(trait, n_ind)
         outs = _trait_sum_outs(trait.shape[0], n_snps)
         self.check(self._f("dbg_trait_sums_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs))
+        return outs
+
+    def dbg_ind_scores_host(self, bits, L, weight, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, want=(True, True)):
+        """the library's score arithmetic compiled for the host (no device needed) -> (gscore, hetscore) as GevContext.ind_scores.  bits:
+        uint64 [2 * n_people][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them; weight: int32
+        [n_scores][n_snps] (or [n_snps] for one column), entry j = SNP snp_begin + j"""
+        bits = _arr(bits, np.uint64)
+        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
+        n_people = bits.shape[0] // 2
+        n_snps = L - snp_begin if n_snps is None else n_snps
+        n_ind = n_people - ind_begin if n_ind is None else n_ind
+        weight = _weights(weight, n_snps)
+        outs = _score_outs(weight.shape[0], n_ind, want)
+        self.check(self._f("dbg_ind_scores_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, ind_begin, n_ind, weight, weight.shape[0], *outs))
         return outs
 
     def dbg_ibd_host(self, parts_a, off_a, parts_b=None, off_b=None, min_bp=0, want=(True, True, True)):
@@ -1178,6 +1208,19 @@ class GevContext:
         trait = _traits(trait, n_ind)
         outs = _trait_sum_outs(trait.shape[0], n_snps)
         self._call("snp_trait_sums", pop, chr, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs)
+        return outs
+
+    def ind_scores(self, pop, chr, weight, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, want=(True, True)):
+        """-> (gscore, hetscore), int64 [n_scores][n_ind]: for individual i of [ind_begin, +n_ind) and column s over SNPs [snp_begin,
+        +n_snps), gscore = sum_j w[s][j] g_ij, hetscore = the sum of w[s][j] over the SNPs at which i is heterozygous.  weight: int32
+        [n_scores][n_snps], |w| <= 2^30 (or [n_snps] for one column), entry j = SNP snp_begin + j; at most 2^22 SNPs a call (the sums
+        are additive: scores.sums splits).  Exact integer products on the device's matrix cores from the current generation (mutations
+        applied).  want: an output that is not wanted goes in as NULL and comes back as None"""
+        n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
+        n_ind = self._rest_ind(pop, ind_begin, n_ind)
+        weight = _weights(weight, n_snps)
+        outs = _score_outs(weight.shape[0], n_ind, want)
+        self._call("ind_scores", pop, chr, snp_begin, n_snps, ind_begin, n_ind, weight, weight.shape[0], *outs)
         return outs
 
     def ibd_sharing(self, chr, pop_a, a_begin=0, n_a=None, pop_b=None, b_begin=0, n_b=None, min_bp=0, want=(True, True, True)):

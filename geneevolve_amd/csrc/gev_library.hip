@@ -27,6 +27,7 @@
 #include "gev_migrant_record.h"
 #include "gev_ldcount.h"
 #include "gev_traitsum.h"
+#include "gev_indscore.h"
 #include "gev_ibd.h"
 #include "gev_roh.h"
 #include "gev_select.h"
@@ -370,6 +371,7 @@ struct gev_ctx {
         unsigned long long launches[2] = {0, 0};           // product launches on small / large tiles over the context's life (bitprod_launch)
     } bp;
     struct TraitSumState { Dev<int32_t> trait, acc; Dev<uint4> b; Dev<long long> out; } ts;   // gev_snp_trait_sums (gev_traitsum.h): the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs
+    struct IndScoreState { Dev<int32_t> w, acc; Dev<uint4> b; Dev<long long> out; } is;      // gev_ind_scores (gev_indscore.h): the weights, their operand bytes, the i32 partials and the 64-bit sums of a block of individuals
     struct SnpCountState { Dev<u32> cnt; } snp;                                               // gev_snp_genotype_counts (gev_snpcount.h): the two count vectors of a call
     struct IbdState { DevBytes out; Dev<u32> flag; Dev<gev_ibd_segment> seg; } ibd;           // gev_ibd_sharing / gev_ancestry_bp / gev_ibd_segments (gev_ibd.h): a sub-block's results, the flag of a bad root population, a strip's records
     struct RohState { Dev<u64> brk; DevBytes out; Dev<u32> diff, cov; Dev<gev_roh_segment> seg; } roh;   // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records
@@ -4409,6 +4411,81 @@ int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_
     if (!n_snps) return GEV_OK;
     if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
     gev_trait_sums_host(bits, row_stride_words, snp_begin, n_snps, ind_begin, n_ind, trait, n_traits, gsum, hetsum, n_het, n_hom_alt);
+    return GEV_OK;
+}
+// ---- scores per individual (gev_indscore.h) ----------------------------------------------------
+static int is_check_weights(const char* who, const int32_t* weight, size_t n_scores, size_t n_snps)
+{
+    if (n_snps > GEV_IS_MAX_SNPS) return fail(GEV_EUNSUPPORTED, "%s: %zu SNPs in one call, at most %zu (a digit's sum is an int32)", who, n_snps, (size_t)GEV_IS_MAX_SNPS);
+    if (!n_scores || !n_snps) return GEV_OK;
+    if (!weight) return fail(GEV_EINVAL, "%s: null weight array (%zu columns of %zu weights each)", who, n_scores, n_snps);
+    for (size_t i = 0; i < n_scores * n_snps; i++)
+        if (weight[i] > GEV_IS_MAX_W || weight[i] < -GEV_IS_MAX_W) return fail(GEV_EINVAL, "%s: weight %d of column %zu, SNP %zu beyond +-2^30", who, weight[i], i / n_snps, i % n_snps);
+    return GEV_OK;
+}
+// individuals of a block: their words of the two planes within ~1 GB as pair_block() has it, at most 65536 (2 KB of partials each at 64 columns)
+static size_t is_block(const gev_ctx* c, size_t snp_begin, size_t n_snps)
+{
+    return std::min<size_t>(output_chunk(c, (size_t)1 << 30, 2 * gev_bp_words4(snp_begin, n_snps) * 8), 65536);
+}
+// The individuals are walked in blocks of at most is_block() (gev_dbg_output_chunk caps them, and the rows of a staging pass): a block is
+// one pair_prep_side into c->bp.a; the weights' operand bytes are made once per call and serve every block; a block's scores are copied out
+// before the next block's kernels run (stream order), and the call returns when the last ones have arrived.
+int gev_ind_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                   const int32_t* weight, size_t n_scores, int64_t* gscore, int64_t* hetscore)
+{
+    const char* who = "ind_scores";
+    GEVC(output_begin(c, pop, chr, who, true));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, P.cs[chr].L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
+    GEVC(is_check_weights(who, weight, n_scores, n_snps));
+    if (!n_ind) return GEV_OK;
+    const OptOut outs[2] = {{gscore, sizeof(int64_t), n_scores * n_ind}, {hetscore, sizeof(int64_t), n_scores * n_ind}};
+    if (!n_snps || !n_scores) { zero_outs(outs); return GEV_OK; }
+    if (!gscore && !hetscore) return GEV_OK;
+    GEVC(ensure_csr(c, pop));
+    hipStream_t st = c->stream;
+    const size_t blk = std::min(is_block(c, snp_begin, n_snps), n_ind), pad = round_up(blk, BP_TILE);
+    const size_t n_w4 = gev_bp_words4(snp_begin, n_snps), n_cg = ceil_div(n_scores, 4), slices = ceil_div(n_w4, GEV_IS_SLICE_W);
+    GEVC(c->is.w.ensure(n_scores * n_snps, st));
+    GEVC(c->is.b.ensure(n_cg * n_w4 * 64, st));                                            // 64 SNPs x 16 columns a word: 1 KiB
+    GEVC(c->is.acc.ensure(2 * n_cg * pad * 16, st));
+    GEVC(c->is.out.ensure(2 * n_scores * blk, st));
+    HIPC(hipMemcpyAsync(c->is.w.p, weight, n_scores * n_snps * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_is_prep, dim3((unsigned)(n_cg * (n_w4 / 4))), dim3(256), 0, st, c->is.w, (u32)n_scores, (u64)snp_begin, (u64)n_snps, (u32)n_w4, (u32)n_cg, c->is.b);
+    KCHECK();
+    for (size_t off = 0; off < n_ind; off += blk) {
+        const size_t n = std::min(blk, n_ind - off), n_pad = round_up(n, BP_TILE);
+        GEVC(pair_prep_side(c, P, chr, ind_begin + off, n, snp_begin, n_snps, &c->bp.a, nullptr, nullptr, nullptr, nullptr));
+        const u64* px = c->bp.a;
+        HIPC(hipMemsetAsync(c->is.acc.p, 0, 2 * n_cg * n_pad * 16 * sizeof(int), st));
+        for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535)                                        // (a grid's z)
+            hipLaunchKernelGGL(k_is_product, dim3((unsigned)(n_pad / BP_TILE), (unsigned)slices, (unsigned)std::min<size_t>(n_cg - cg0, 65535)), dim3(256), 0, st,
+                               px, px + n_w4 * n_pad, (u32)n_pad, (u32)n_w4, c->is.b, (u32)n_cg, (u32)cg0, c->is.acc);
+        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_scores * n, 256)), dim3(256), 0, st, c->is.acc, (u32)n_pad, (u32)n_cg,
+                           (u32)n_scores, (u32)n, (u32)blk, c->is.out);
+        KCHECK();
+        for (int o = 0; o < 2; o++)
+            if (outs[o].host) HIPC(hipMemcpy2DAsync((int64_t*)outs[o].host + off, n_ind * sizeof(int64_t), c->is.out + (size_t)o * n_scores * blk, blk * sizeof(int64_t),
+                                                    n * sizeof(int64_t), n_scores, hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// the arithmetic of gev_indscore.h compiled for the host on haplotype-major rows in host memory: no device, no context
+int gev_dbg_ind_scores_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
+                            size_t ind_begin, size_t n_ind, const int32_t* weight, size_t n_scores, int64_t* gscore, int64_t* hetscore)
+{
+    const char* who = "dbg_ind_scores_host";
+    GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
+    GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
+    GEVC(is_check_weights(who, weight, n_scores, n_snps));
+    GEVC(check_host_rows(who, bits, row_stride_words, L, n_snps && n_ind));
+    if (!n_ind) return GEV_OK;
+    const OptOut outs[2] = {{gscore, sizeof(int64_t), n_scores * n_ind}, {hetscore, sizeof(int64_t), n_scores * n_ind}};
+    if (!n_snps || !n_scores) { zero_outs(outs); return GEV_OK; }
+    gev_ind_scores_host(bits, row_stride_words, snp_begin, n_snps, ind_begin, n_ind, weight, n_scores, gscore, hetscore);
     return GEV_OK;
 }
 // ---- identity by descent per pair of haplotype rows, base pairs by root population (gev_ibd.h) ----------------

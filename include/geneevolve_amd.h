@@ -675,6 +675,32 @@ int gev_snp_trait_sums(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_sn
 int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
                             size_t ind_begin, size_t n_ind, const int32_t* trait, size_t n_traits,
                             int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt);
+/* ---- scores per individual: polygenic scores with signed weight columns without a dump ----------------------------------------------
+ * Counted on the device from the resident rows of the current generation, new mutations applied (csrc/gev_indscore.h).  A score column
+ * is a host vector of int32 weights w[s][j], |w| <= 2^30, entry j = SNP snp_begin + j (floating-point effect sizes are quantised by the
+ * caller: geneevolve_amd/scores.py), so every sum is an exact integer sum, the same on every run and in every order, and additive over
+ * SNP ranges and chromosomes: one call serves one (pop, chr).  For individual i of [ind_begin,+n_ind) and column s over SNPs
+ * [snp_begin,+n_snps), each output may be NULL:
+ *   gscore[s][i]   (int64, [n_scores][n_ind]) = sum_j w[s][j] g_ij, g = 0/1/2 copies of allele 1; |gscore| <= 2^53
+ *   hetscore[s][i] (int64, [n_scores][n_ind]) = sum of w[s][j] over the SNPs at which i is heterozygous
+ * The genotype-class sums are S1 = hetscore and S2 = (gscore - hetscore) / 2.  The individuals go through the staging pass and the
+ * planes x = a ^ b, y = a & b of gev_pair_genotype_counts; the weights are split into four balanced base-256 digits, and the sums are
+ * integer matrix products on the matrix cores (v_mfma_i32_16x16x64_i8) with the SNPs split over workgroups.  The call begins like the
+ * other output calls and returns when the results are in the caller's memory.  GEV_ESTATE on a context without genotype planes, for
+ * an inactive chromosome and for a population without a current generation; GEV_EINVAL for a range beyond L / n_people, for a NULL
+ * weight with n_scores > 0 and n_snps > 0 and for a weight beyond +-2^30 (checked before anything is enqueued); GEV_EUNSUPPORTED for
+ * n_snps > 2^22 (a digit's sum is an int32; the caller splits the range and adds).  n_ind == 0 touches nothing, n_snps == 0 or
+ * n_scores == 0 writes zeros.  The device buffers are created by the first call; gev_dbg_output_chunk caps the individuals of one
+ * staging pass and of one block. */
+int gev_ind_scores(gev_ctx*, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
+                   const int32_t* weight /*[n_scores][n_snps], host*/, size_t n_scores,
+                   int64_t* gscore /*[n_scores][n_ind]*/, int64_t* hetscore /*[n_scores][n_ind]*/);
+/* the same arithmetic (masking, digit split, byte order of both operands, recombination) compiled for the host on rows in host memory
+ * as gev_download_haps returns them (2 n_people rows, stride >= ceil(L/64) words), a plain integer loop in place of the matrix
+ * instruction: no device, no context.  Only the rows of the individuals of the range are read, and of those the words that hold a SNP
+ * of the range. */
+int gev_dbg_ind_scores_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
+                            size_t ind_begin, size_t n_ind, const int32_t* weight, size_t n_scores, int64_t* gscore, int64_t* hetscore);
 /* ---- identity by descent per pair of haplotypes, from the ancestry intervals: realised coancestry and inbreeding without a dump ------
  * The one analysis call on the interval lists (csrc/gev_ibd.h).  For haplotype row r (row = 2 * individual + chromatid) of (pop, chr)
  * let f_r(x) = (root_population, hap_index) of the part of r's list with st <= x < en (half-open, as part::check_interval, reference
