@@ -7,7 +7,8 @@ from collections import namedtuple
 
 import numpy as np
 
-from .relatedness import _range
+from ._ranges import individuals as _range
+from .scores import quantise_weights
 
 TraitSums = namedtuple("TraitSums", "n_ind gsum hetsum n_het n_hom_alt sum_q sum_q2 scale mean")
 TraitSums.__doc__ = """n_ind: individuals summed over (N); gsum / hetsum: int64 [n_traits][n_snps], sum_i g_ij q[t][i] and the sum of q[t][i] over the
@@ -28,17 +29,13 @@ or df2 < 1 or the trait is constant"""
 
 def quantise(y, bits=30):
     """float phenotypes [n_traits][n_ind] (or [n_ind]) -> (q int32, scale float64 [n_traits], mean float64 [n_traits]): centred on the mean over the
-    individuals given, scaled so that max |y - mean| maps to 2^bits and rounded to nearest, so |q * scale + mean - y| <= scale / 2"""
+    individuals given, then scaled and rounded as scores.quantise_weights does, so |q * scale + mean - y| <= scale / 2"""
     assert 1 <= bits <= 30
     y = np.atleast_2d(np.asarray(y, dtype=np.float64))
     if y.shape[1] == 0:
         return np.zeros(y.shape, dtype=np.int32), np.ones(y.shape[0]), np.zeros(y.shape[0])
     mean = y.mean(axis=1)
-    dev = y - mean[:, None]
-    top = np.abs(dev).max(axis=1)
-    scale = np.where(top > 0, top / float(1 << bits), 1.0)
-    q = np.clip(np.rint(dev / scale[:, None]), -(1 << bits), 1 << bits).astype(np.int32)
-    return q, scale, mean
+    return (*quantise_weights(y - mean[:, None], bits), mean)
 
 
 def _exact_moments(q):

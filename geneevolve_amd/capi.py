@@ -329,33 +329,33 @@ def unpack_rows(words, L):
     return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little")[:, :L]
 
 
-def _traits(trait, n_ind):
-    """quanta as the trait-sum calls take them: int32 [n_traits][n_ind], a single vector as one trait"""
-    trait = _arr(trait, np.int32)
-    if trait.ndim == 1:
-        trait = trait.reshape(1, -1)
-    assert trait.ndim == 2 and trait.shape[1] == max(n_ind, 0), "one quantum per trait and individual of the range"
-    return trait
-
-
-def _trait_sum_outs(n_traits, n_snps):
-    n_snps = max(n_snps, 0)
-    return (np.empty((n_traits, n_snps), dtype=np.int64), np.empty((n_traits, n_snps), dtype=np.int64),
-            np.empty(n_snps, dtype=np.uint32), np.empty(n_snps, dtype=np.uint32))
-
-
-def _weights(weight, n_snps):
-    """weight columns as the score calls take them: int32 [n_scores][n_snps], a single vector as one column"""
-    weight = _arr(weight, np.int32)
-    if weight.ndim == 1:
-        weight = weight.reshape(1, -1)
-    assert weight.ndim == 2 and weight.shape[1] == max(n_snps, 0), "one weight per column and SNP of the range"
-    return weight
+def _columns(val, n, per):
+    """columns as the trait-sum and score calls take them (quanta, weights): int32 [n_cols][n], a single vector as one column.  per: what a
+    column holds one value of, for the refusal"""
+    val = _arr(val, np.int32)
+    if val.ndim == 1:
+        val = val.reshape(1, -1)
+    assert val.ndim == 2 and val.shape[1] == max(n, 0), f"one {per} of the range"
+    return val
 
 
 def _score_outs(n_scores, n_ind, want=(True, True)):
     """the two matrices of the score calls (None where not wanted)"""
     return tuple(np.empty((n_scores, max(n_ind, 0)), dtype=np.int64) if w else None for w in want)
+
+
+def _trait_sum_outs(n_traits, n_snps):
+    """the two matrices of the trait-sum calls, as the score calls' with SNPs for individuals, and the two count vectors"""
+    return (*_score_outs(n_traits, n_snps), np.empty(max(n_snps, 0), dtype=np.uint32), np.empty(max(n_snps, 0), dtype=np.uint32))
+
+
+def _hap_rows(bits, L, snp_begin, n_snps, ind_begin=0, n_ind=None):
+    """what the dbg_*_host calls over haplotype-major rows begin with -> (bits as uint64 [2 * n_people][stride_words], n_people, n_snps,
+    n_ind), a range that is None running to the end"""
+    bits = _arr(bits, np.uint64)
+    assert bits.ndim == 2 and bits.shape[0] % 2 == 0
+    n_people = bits.shape[0] // 2
+    return bits, n_people, L - snp_begin if n_snps is None else n_snps, n_people - ind_begin if n_ind is None else n_ind
 
 
 def _ibd_outs(n_a, n_b, want=(True, True, True)):
@@ -467,21 +467,16 @@ class GevLibrary:
     def dbg_snp_counts_host(self, bits, L, snp_begin=0, n_snps=None):
         """(n_het, n_hom_alt) of SNPs [snp_begin, +n_snps) by the library's genotype counter compiled for the host (no device needed).
         bits: uint64 [2 * n_ind][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them"""
-        bits = _arr(bits, np.uint64)
-        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
-        n_snps = L - snp_begin if n_snps is None else n_snps
+        bits, n_people, n_snps, _ = _hap_rows(bits, L, snp_begin, n_snps)
         het = np.empty(n_snps, dtype=np.uint32); hom = np.empty(n_snps, dtype=np.uint32)
-        self.check(self._f("dbg_snp_counts_host")(bits, bits.shape[1], bits.shape[0] // 2, L, snp_begin, n_snps, het, hom))
+        self.check(self._f("dbg_snp_counts_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, het, hom))
         return het, hom
 
     def dbg_pair_counts_host(self, bits, L, snp_begin=0, n_snps=None, a_begin=0, n_a=None, b_begin=0, n_b=None):
         """(n_het, n_hom_alt, n_hethet, n_opphom, dot) by the library's pair counter compiled for the host (no device needed): the first two
         uint32 [n_ind] over SNPs [snp_begin, +n_snps), the others uint32 [n_a][n_b] for the pairs (a_begin + i, b_begin + k).
         bits: uint64 [2 * n_ind][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them"""
-        bits = _arr(bits, np.uint64)
-        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
-        n_ind = bits.shape[0] // 2
-        n_snps = L - snp_begin if n_snps is None else n_snps
+        bits, n_ind, n_snps, _ = _hap_rows(bits, L, snp_begin, n_snps)
         n_a = n_ind - a_begin if n_a is None else n_a
         n_b = n_ind - b_begin if n_b is None else n_b
         het = np.empty(n_ind, dtype=np.uint32); hom = np.empty(n_ind, dtype=np.uint32)
@@ -531,12 +526,8 @@ class GevLibrary:
         """the library's trait-sum arithmetic compiled for the host (no device needed) -> (gsum, hetsum, n_het, n_hom_alt) as
         GevContext.snp_trait_sums.  bits: uint64 [2 * n_people][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns
         them; trait: int32 [n_traits][n_ind] quanta (or [n_ind] for one trait), entry i = individual ind_begin + i"""
-        bits = _arr(bits, np.uint64)
-        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
-        n_people = bits.shape[0] // 2
-        n_snps = L - snp_begin if n_snps is None else n_snps
-        n_ind = n_people - ind_begin if n_ind is None else n_ind
-        trait = _traits(trait, n_ind)
+        bits, n_people, n_snps, n_ind = _hap_rows(bits, L, snp_begin, n_snps, ind_begin, n_ind)
+        trait = _columns(trait, n_ind, "quantum per trait and individual")
         outs = _trait_sum_outs(trait.shape[0], n_snps)
         self.check(self._f("dbg_trait_sums_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs))
         return outs
@@ -545,12 +536,8 @@ class GevLibrary:
         """the library's score arithmetic compiled for the host (no device needed) -> (gscore, hetscore) as GevContext.ind_scores.  bits:
         uint64 [2 * n_people][stride_words >= ceil(L / 64)] haplotype-major rows as download_haps returns them; weight: int32
         [n_scores][n_snps] (or [n_snps] for one column), entry j = SNP snp_begin + j"""
-        bits = _arr(bits, np.uint64)
-        assert bits.ndim == 2 and bits.shape[0] % 2 == 0
-        n_people = bits.shape[0] // 2
-        n_snps = L - snp_begin if n_snps is None else n_snps
-        n_ind = n_people - ind_begin if n_ind is None else n_ind
-        weight = _weights(weight, n_snps)
+        bits, n_people, n_snps, n_ind = _hap_rows(bits, L, snp_begin, n_snps, ind_begin, n_ind)
+        weight = _columns(weight, n_snps, "weight per column and SNP")
         outs = _score_outs(weight.shape[0], n_ind, want)
         self.check(self._f("dbg_ind_scores_host")(bits, bits.shape[1], n_people, L, snp_begin, n_snps, ind_begin, n_ind, weight, weight.shape[0], *outs))
         return outs
@@ -1205,7 +1192,7 @@ class GevContext:
         i = individual ind_begin + i.  Exact integer products on the device's matrix cores from the current generation (mutations applied)"""
         n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
         n_ind = self._rest_ind(pop, ind_begin, n_ind)
-        trait = _traits(trait, n_ind)
+        trait = _columns(trait, n_ind, "quantum per trait and individual")
         outs = _trait_sum_outs(trait.shape[0], n_snps)
         self._call("snp_trait_sums", pop, chr, snp_begin, n_snps, ind_begin, n_ind, trait, trait.shape[0], *outs)
         return outs
@@ -1218,7 +1205,7 @@ class GevContext:
         applied).  want: an output that is not wanted goes in as NULL and comes back as None"""
         n_snps = self._rest_snps(pop, chr, snp_begin, n_snps)
         n_ind = self._rest_ind(pop, ind_begin, n_ind)
-        weight = _weights(weight, n_snps)
+        weight = _columns(weight, n_snps, "weight per column and SNP")
         outs = _score_outs(weight.shape[0], n_ind, want)
         self._call("ind_scores", pop, chr, snp_begin, n_snps, ind_begin, n_ind, weight, weight.shape[0], *outs)
         return outs

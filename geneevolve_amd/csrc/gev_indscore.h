@@ -12,17 +12,13 @@
 // Both are products of individuals x SNPs against SNPs x columns on bytes.
 // Side A is the pair side unchanged (gev_paircount.h): the range-masked individual-major planes x = a ^ b and y = a & b, and per
 // matrix step of a 64-locus word gev_pc_expand_step gives the genotype bytes (x + 2y) and the heterozygote bytes (x).
-// Side B are the weights, split as the quanta of gev_traitsum.h are: four balanced base-256 digits in [-128, 127] (gev_ts_digit),
-// 4 columns x 4 digits = the 16 columns of one fragment (column = 4 (s & 3) + k of column group s >> 2).  The accumulators are i32:
-// |digit| <= 128, g <= 2, so n_snps <= 2^22 keeps them in range; sum_k acc_k 256^k is formed in 64 bits (gev_ts_recombine), and
-// |gscore| <= 2 * 2^30 * 2^22 = 2^53.
-//
-// As in gev_traitsum.h side B is made elsewhere than side A, so its bytes are laid out in exactly the order the expansion gives side
-// A's.  In the step of words 4 W .. 4 W + 3 (counted from the first word of the SNP range) lane group q carries word 4 W + q; of that
-// word matrix step s (0..3) takes the loci of half s >> 1 and parity s & 1 (gev_pc_pack2: field f = locus 2 f + parity of the half),
-// and position 4 j + b of the 16 bytes (register j, byte b) holds field j + 4 b (gev_pc_expand), that is SNP
+// Side B are the weights: the digit-column product of gev_digitprod.h with the individuals as rows and the SNPs summed (n_snps <=
+// GEV_IS_MAX_SNPS), the score columns its columns.  Its bytes in side A's order: in the step of words 4 W .. 4 W + 3 (counted from the
+// first word of the SNP range) lane group q carries word 4 W + q; of that word matrix step s (0..3) takes the loci of half s >> 1 and
+// parity s & 1 (gev_pc_pack2: field f = locus 2 f + parity of the half), and position 4 j + b of the 16 bytes (register j, byte b) holds
+// field j + 4 b (gev_pc_expand), that is SNP
 //     64 (w_first + 4 W + q) + 32 (s >> 1) + 2 (j + 4 b) + (s & 1)
-// of the chromosome.  gev_is_operand_word is that rule, for the device and the host from one source.
+// of the chromosome.  gev_is_operand_word is that rule.
 //
 // The first part of this file is plain C++ (gev_dbg_ind_scores_host and any host program that includes this file alone run the same
 // masking, digit split, byte order of both operands and recombination with a plain integer loop in place of the matrix instruction);
@@ -31,11 +27,11 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
-#include "gev_paircount.h"                         // gev_pc_planes, gev_pc_expand_step; gev_bitprod.h: the range mask, the words of a range, the byte store and dot
-#include "gev_traitsum.h"                          // gev_ts_digit, gev_ts_recombine; k_ts_finish
+#include "gev_paircount.h"                         // gev_pc_planes, gev_pc_expand_step; gev_bitprod.h: the range mask, the words of a range, the byte store
+#include "gev_digitprod.h"                         // the digit split, the operand packing, the host product of a row; the epilogue and the finish
 
-#define GEV_IS_MAX_SNPS ((size_t)1 << 22)         // 128 * 2 * 2^22 = 2^30: an accumulator stays an int32
-#define GEV_IS_MAX_W ((int32_t)1 << 30)           // |weight|
+#define GEV_IS_MAX_SNPS GEV_DP_MAX_N              // SNPs summed
+#define GEV_IS_MAX_W GEV_DP_MAX_VAL               // |weight|
 #define GEV_IS_SLICE_W 64u                        // words of an individual's planes one workgroup sums: 4096 SNPs (a multiple of the 4 words of a step)
 
 // Side B: register j of the 16 operand bytes of column `col` of column group `cg` for matrix step s (0..3) of word `word` of the
@@ -43,14 +39,7 @@
 // for a column beyond n_scores.  weight: [n_scores][n_snps], entry j = SNP snp_begin + j
 GEV_PC_HD inline uint32_t gev_is_operand_word(const int32_t* weight, size_t n_scores, size_t snp_begin, size_t n_snps, size_t word, int s, size_t cg, int col, int j)
 {
-    const size_t t = 4 * cg + (size_t)(col >> 2);
-    if (t >= n_scores) return 0;
-    uint32_t r = 0;
-    for (int b = 0; b < 4; b++) {
-        const size_t snp = 64 * word + 32 * (size_t)(s >> 1) + 2 * (size_t)(j + 4 * b) + (size_t)(s & 1);
-        if (snp >= snp_begin && snp - snp_begin < n_snps) r |= (uint32_t)(uint8_t)gev_ts_digit(weight[t * n_snps + (snp - snp_begin)], col & 3) << (8 * b);
-    }
-    return r;
+    return gev_dp_operand_word(weight, n_scores, snp_begin, n_snps, cg, col, [=](int b) { return 64 * word + 32 * (size_t)(s >> 1) + 2 * (size_t)(j + 4 * b) + (size_t)(s & 1); });
 }
 // The host form on haplotype-major rows (row r = bits + r * stride words, SNP j = bit j & 63 of word j >> 6, rows 2i and 2i+1 =
 // individual i): the planes of individuals [ind_begin, +n_ind) masked and expanded as the device does; the weights laid out as the
@@ -63,15 +52,7 @@ inline void gev_ind_scores_host(const uint64_t* bits, size_t stride, size_t snp_
     const size_t n_w = n_snps ? ((snp_end - 1) >> 6) - w_first + 1 : 0, n_w4 = gev_bp_words4(snp_begin, n_snps);
     const size_t nb = n_w4 * 64, n_cg = (n_scores + 3) / 4;
     if ((!gscore && !hetscore) || !n_scores) return;
-    std::vector<int8_t> tb(n_cg * 16 * nb);                         // [column group][column][the bytes of an individual]
-    for (size_t cg = 0; cg < n_cg; cg++)
-        for (int col = 0; col < 16; col++)
-            for (size_t w = 0; w < n_w4; w++)
-                for (int s = 0; s < 4; s++) {
-                    uint32_t e[4];
-                    for (int j = 0; j < 4; j++) e[j] = gev_is_operand_word(weight, n_scores, snp_begin, n_snps, w_first + w, s, cg, col, j);
-                    gev_bp_store16(e, &tb[(cg * 16 + (size_t)col) * nb + w * 64 + 16 * (size_t)s]);
-                }
+    const std::vector<int8_t> tb = gev_dp_table_host(n_cg, nb, [=](size_t cg, int col, size_t p, int j) { return gev_is_operand_word(weight, n_scores, snp_begin, n_snps, w_first + (p >> 2), (int)(p & 3), cg, col, j); });
     std::vector<int8_t> gb(nb), hb(nb);
     for (size_t i = 0; i < n_ind; i++) {
         const uint64_t* ra = bits + 2 * (ind_begin + i) * stride; const uint64_t* rb = ra + stride;
@@ -84,15 +65,7 @@ inline void gev_ind_scores_host(const uint64_t* bits, size_t stride, size_t snp_
                 gev_bp_store16(ge, &gb[w * 64 + 16 * (size_t)s]); gev_bp_store16(xe, &hb[w * 64 + 16 * (size_t)s]);
             }
         }
-        for (size_t t = 0; t < n_scores; t++) {
-            int32_t ag[4], ah[4];
-            for (int k = 0; k < 4; k++) {
-                const int8_t* b = &tb[((t >> 2) * 16 + 4 * (t & 3) + (size_t)k) * nb];
-                ag[k] = (int32_t)gev_bp_dot_i8(gb.data(), b, nb); ah[k] = (int32_t)gev_bp_dot_i8(hb.data(), b, nb);
-            }
-            if (gscore) gscore[t * n_ind + i] = gev_ts_recombine(ag);
-            if (hetscore) hetscore[t * n_ind + i] = gev_ts_recombine(ah);
-        }
+        gev_dp_row_host(tb, nb, gb.data(), hb.data(), n_scores, n_ind, i, gscore, hetscore);
     }
 }
 
@@ -106,12 +79,10 @@ inline void gev_ind_scores_host(const uint64_t* bits, size_t stride, size_t snp_
 // k_is_product: v_mfma_i32_16x16x64_i8, A = 16 individuals (row = lane & 15), B = the 16 columns of a column group (column =
 //   lane & 15), two accumulator sets (genotype bytes, heterozygote bytes).  The SNPs are split so that a block of individuals against
 //   16 columns fills the device: blockIdx.x = 128 individuals (four waves of IS_FR fragments), blockIdx.y = a slice of
-//   GEV_IS_SLICE_W words, blockIdx.z = the column group; the i32 partials are added with vector atomics (integer adds commute;
-//   two's-complement wrap is harmless while the total is in range).  The planes are padded with zero individuals to BP_TILE and to 4
-//   words, tb is whole steps, so no load needs a bound; a zero partial is not added.  The next step's words and fragments are loaded
-//   before this step's products are issued.  acc: [2 sets][n_cg][n_pad individuals][16 columns].
-// The finish is k_ts_finish (gev_traitsum.h) as it is: the accumulators have its layout with individuals where it has SNPs.
-// Every store and atomic is a vector one.
+//   GEV_IS_SLICE_W words, blockIdx.z = the column group; the partials go to acc through dp_add_partials.  The planes are padded with
+//   zero individuals to BP_TILE and to 4 words, tb is whole steps, so no load needs a bound.  The next step's words and fragments are
+//   loaded before this step's products are issued.  acc: [2 sets][n_cg][n_pad individuals][16 columns].
+// The finish is k_dp_finish (gev_digitprod.h).  Every store is a vector one.
 // ------------------------------------------------------------------------------------------
 #define IS_FR 2                                   // fragments of 16 individuals a wave: 4 waves x 32 = the BP_TILE individuals of a workgroup
 
@@ -123,12 +94,7 @@ __global__ void __launch_bounds__(256) k_is_prep(const int32_t* __restrict__ wei
     const u32 lane = (u32)id & 63u, s = ((u32)(id >> 6)) & 3u, col = lane & 15u, q = lane >> 4;
     const size_t step = (id >> 8) % steps, cg = (id >> 8) / steps;
     const size_t word = (size_t)(snp_begin >> 6) + 4 * step + q;
-    uint4 v;
-    v.x = gev_is_operand_word(weight, n_scores, (size_t)snp_begin, (size_t)n_snps, word, (int)s, cg, (int)col, 0);
-    v.y = gev_is_operand_word(weight, n_scores, (size_t)snp_begin, (size_t)n_snps, word, (int)s, cg, (int)col, 1);
-    v.z = gev_is_operand_word(weight, n_scores, (size_t)snp_begin, (size_t)n_snps, word, (int)s, cg, (int)col, 2);
-    v.w = gev_is_operand_word(weight, n_scores, (size_t)snp_begin, (size_t)n_snps, word, (int)s, cg, (int)col, 3);
-    tb[id] = v;
+    tb[id] = dp_operand16([&](int j) { return gev_is_operand_word(weight, n_scores, (size_t)snp_begin, (size_t)n_snps, word, (int)s, cg, (int)col, j); });
 }
 
 // plane_x / plane_y: n_w4 words x n_pad individuals each (k_pair_prep's); cg0: the column group of blockIdx.z = 0
@@ -156,7 +122,7 @@ __global__ void __launch_bounds__(256) k_is_product(const u64* __restrict__ plan
         if (W + 4u < W1) { px += (size_t)4 * n_pad; py += (size_t)4 * n_pad; pb += 256; load_next(); }
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            const pc_v4i fb = pc_v4i{(int)cur.b[s].x, (int)cur.b[s].y, (int)cur.b[s].z, (int)cur.b[s].w};
+            const pc_v4i fb = dp_frag_b(cur.b[s]);
 #pragma unroll
             for (int m = 0; m < IS_FR; m++) {
                 u32 g[4], e[4];
@@ -166,15 +132,6 @@ __global__ void __launch_bounds__(256) k_is_product(const u64* __restrict__ plan
             }
         }
     }
-    int* const og = acc + ((size_t)cg * n_pad + a0) * 16u + r;       // C/D: column = lane & 15, row = 4 (lane >> 4) + register
-    int* const oh = og + (size_t)n_cg * n_pad * 16u;
-#pragma unroll
-    for (int m = 0; m < IS_FR; m++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const size_t o = (size_t)(16 * m + 4 * (int)q + v) * 16u;
-            if (ag[m][v]) atomicAdd(og + o, ag[m][v]);
-            if (ah[m][v]) atomicAdd(oh + o, ah[m][v]);
-        }
+    dp_add_partials<IS_FR>(ag, ah, acc, n_cg, n_pad, cg, a0, r, q);
 }
 #endif

@@ -370,8 +370,7 @@ struct gev_ctx {
         int dbg_tiles = 0;                                 // gev_dbg_bitprod_tiles: 0 = the tile size by compute units, 1 = always 64 x 64, 2 = always 128 x 128
         unsigned long long launches[2] = {0, 0};           // product launches on small / large tiles over the context's life (bitprod_launch)
     } bp;
-    struct TraitSumState { Dev<int32_t> trait, acc; Dev<uint4> b; Dev<long long> out; } ts;   // gev_snp_trait_sums (gev_traitsum.h): the quanta, their operand bytes, the i32 partials and the 64-bit sums of a block of SNPs
-    struct IndScoreState { Dev<int32_t> w, acc; Dev<uint4> b; Dev<long long> out; } is;      // gev_ind_scores (gev_indscore.h): the weights, their operand bytes, the i32 partials and the 64-bit sums of a block of individuals
+    struct DigitProdState { Dev<int32_t> val, acc; Dev<uint4> b; Dev<long long> out; } dp;   // gev_snp_trait_sums and gev_ind_scores (gev_digitprod.h), one set for both under the rule above: the columns (quanta, weights), their operand bytes, the i32 partials and the 64-bit sums of a block of rows
     struct SnpCountState { Dev<u32> cnt; } snp;                                               // gev_snp_genotype_counts (gev_snpcount.h): the two count vectors of a call
     struct IbdState { DevBytes out; Dev<u32> flag; Dev<gev_ibd_segment> seg; } ibd;           // gev_ibd_sharing / gev_ancestry_bp / gev_ibd_segments (gev_ibd.h): a sub-block's results, the flag of a bad root population, a strip's records
     struct RohState { Dev<u64> brk; DevBytes out; Dev<u32> diff, cov; Dev<gev_roh_segment> seg; } roh;   // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records
@@ -4331,24 +4330,64 @@ int gev_dbg_ld_r2_q40_host(const int64_t* num, const uint64_t* den_j, const uint
     for (size_t i = 0; i < n; i++) q40[i] = gev_ld_r2_q40(num[i], den_j[i], den_k[i]);
     return GEV_OK;
 }
-// ---- trait sums per SNP (gev_traitsum.h) -------------------------------------------------------
-static int ts_check_traits(const char* who, const int32_t* trait, size_t n_traits, size_t n_ind)
+// ---- the signed digit-column product under trait sums and scores (gev_digitprod.h) ---------------
+struct DpNouns { const char *array, *column, *columns, *value, *values, *entry, *entries; };   // what a feature's refusals call its columns
+static const DpNouns TS_NOUNS = {"trait", "trait", "traits", "quantum", "quanta", "individual", "individuals"};
+static const DpNouns IS_NOUNS = {"weight", "column", "columns", "weight", "weights", "SNP", "SNPs"};
+// val: [n_cols][n], n the summed entries of a row
+static int dp_check_columns(const char* who, const DpNouns& nn, const int32_t* val, size_t n_cols, size_t n)
 {
-    if (n_ind > GEV_TS_MAX_IND) return fail(GEV_EUNSUPPORTED, "%s: %zu individuals in one call, at most %zu (a digit's sum is an int32)", who, n_ind, (size_t)GEV_TS_MAX_IND);
-    if (!n_traits || !n_ind) return GEV_OK;
-    if (!trait) return fail(GEV_EINVAL, "%s: null trait array (%zu traits of %zu quanta each)", who, n_traits, n_ind);
-    for (size_t i = 0; i < n_traits * n_ind; i++)
-        if (trait[i] > GEV_TS_MAX_Q || trait[i] < -GEV_TS_MAX_Q) return fail(GEV_EINVAL, "%s: quantum %d of trait %zu, individual %zu beyond +-2^30", who, trait[i], i / n_ind, i % n_ind);
+    if (n > GEV_DP_MAX_N) return fail(GEV_EUNSUPPORTED, "%s: %zu %s in one call, at most %zu (a digit's sum is an int32)", who, n, nn.entries, (size_t)GEV_DP_MAX_N);
+    if (!n_cols || !n) return GEV_OK;
+    if (!val) return fail(GEV_EINVAL, "%s: null %s array (%zu %s of %zu %s each)", who, nn.array, n_cols, nn.columns, n, nn.values);
+    for (size_t i = 0; i < n_cols * n; i++)
+        if (val[i] > GEV_DP_MAX_VAL || val[i] < -GEV_DP_MAX_VAL) return fail(GEV_EINVAL, "%s: %s %d of %s %zu, %s %zu beyond +-2^30", who, nn.value, val[i], nn.column, i / n, nn.entry, i % n);
     return GEV_OK;
 }
-static void ts_zero(size_t n_snps, size_t n_traits, int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
+// Side B of a call: the columns uploaded and turned by the feature's preparation kernel (k_ts_prep, k_is_prep: a thread per 16-byte fragment,
+// `frags` of them per word of the n_w4 summed) into the operand bytes that serve every block; the partials and sums of a block of at most blk rows
+static int dp_operand(gev_ctx* c, void (*k_prep)(const int32_t*, u32, u64, u64, u32, u32, uint4*), const int32_t* val, size_t n_cols, size_t begin, size_t n,
+                      size_t n_w4, size_t frags, size_t blk)
 {
-    const OptOut outs[4] = {{gsum, sizeof(int64_t), n_traits * n_snps}, {hetsum, sizeof(int64_t), n_traits * n_snps}, {n_het, sizeof(u32), n_snps}, {n_hom_alt, sizeof(u32), n_snps}};
-    zero_outs(outs);
+    hipStream_t st = c->stream;
+    const size_t n_cg = ceil_div(n_cols, 4);
+    GEVC(c->dp.val.ensure(n_cols * n, st));
+    GEVC(c->dp.b.ensure(n_cg * n_w4 * frags, st));
+    GEVC(c->dp.acc.ensure(2 * n_cg * round_up(blk, BP_TILE) * 16, st));
+    GEVC(c->dp.out.ensure(2 * n_cols * blk, st));
+    HIPC(hipMemcpyAsync(c->dp.val.p, val, n_cols * n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_prep, dim3((unsigned)ceil_div(n_cg * n_w4 * frags, 256)), dim3(256), 0, st, c->dp.val, (u32)n_cols, (u64)begin, (u64)n, (u32)n_w4, (u32)n_cg, c->dp.b);
+    KCHECK();
+    return GEV_OK;
 }
+// The n_rows rows of the product in blocks of blk: prep(off, n) prepares side A of rows [off, +n), padded to BP_TILE rows as ld_prep_side and
+// pair_prep_side pad them; product(n_pad, cg0, n_z) launches the feature's product kernel for column groups [cg0, +n_z) (a grid's z).  Where a
+// matrix of mats ([n_cols][n_rows] int64 on the host) is wanted a block's sums are finished and copied out before the next block's kernels run
+// (stream order); the call returns when the last ones have arrived
+extern "C++" template <class Prep, class Product>
+static int dp_walk(gev_ctx* c, size_t n_rows, size_t blk, size_t n_cols, const OptOut* mats, Prep prep, Product product)
+{
+    hipStream_t st = c->stream;
+    const size_t n_cg = ceil_div(n_cols, 4);
+    for (size_t off = 0; off < n_rows; off += blk) {
+        const size_t n = std::min(blk, n_rows - off), n_pad = round_up(n, BP_TILE);
+        GEVC(prep(off, n));
+        if (!n_cols || (!mats[0].host && !mats[1].host)) continue;
+        HIPC(hipMemsetAsync(c->dp.acc.p, 0, 2 * n_cg * n_pad * 16 * sizeof(int), st));
+        for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535) product(n_pad, cg0, std::min<size_t>(n_cg - cg0, 65535));
+        hipLaunchKernelGGL(k_dp_finish, dim3((unsigned)ceil_div(2 * n_cols * n, 256)), dim3(256), 0, st, c->dp.acc, (u32)n_pad, (u32)n_cg,
+                           (u32)n_cols, (u32)n, (u32)blk, c->dp.out);
+        KCHECK();
+        for (int o = 0; o < 2; o++)
+            if (mats[o].host) HIPC(hipMemcpy2DAsync((int64_t*)mats[o].host + off, n_rows * sizeof(int64_t), c->dp.out + (size_t)o * n_cols * blk, blk * sizeof(int64_t),
+                                                    n * sizeof(int64_t), n_cols, hipMemcpyDeviceToHost, st));
+    }
+    HIPC(hipStreamSynchronize(st));
+    return GEV_OK;
+}
+// ---- trait sums per SNP (gev_traitsum.h) -------------------------------------------------------
 // The SNPs are walked in blocks of at most ld_block() (gev_dbg_output_chunk caps them): a block is one snp_major_device pass and one
-// k_ld_prep into c->bp.a; the traits' operand bytes are made once per call and serve every block; a block's sums are copied out before the
-// next block's kernels run (stream order), and the call returns when the last ones have arrived.
+// k_ld_prep into c->bp.a, its counts copied out behind it; the traits' operand bytes are made once per call
 int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
                        const int32_t* trait, size_t n_traits, int64_t* gsum, int64_t* hetsum, uint32_t* n_het, uint32_t* n_hom_alt)
 {
@@ -4357,46 +4396,29 @@ int gev_snp_trait_sums(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_
     PopState& P = c->pop[pop];
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, P.cs[chr].L));
     GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
-    GEVC(ts_check_traits(who, trait, n_traits, n_ind));
+    GEVC(dp_check_columns(who, TS_NOUNS, trait, n_traits, n_ind));
     if (!n_snps) return GEV_OK;
-    if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
+    const OptOut outs[4] = {{gsum, sizeof(int64_t), n_traits * n_snps}, {hetsum, sizeof(int64_t), n_traits * n_snps}, {n_het, sizeof(u32), n_snps}, {n_hom_alt, sizeof(u32), n_snps}};
+    if (!n_ind) { zero_outs(outs); return GEV_OK; }
     const bool want_sums = (gsum || hetsum) && n_traits;
     if (!want_sums && !n_het && !n_hom_alt) return GEV_OK;
     hipStream_t st = c->stream;
-    const size_t blk = std::min(ld_block(c, P.n_people, ind_begin, n_ind), n_snps), pad = round_up(blk, BP_TILE);
+    const size_t blk = std::min(ld_block(c, P.n_people, ind_begin, n_ind), n_snps);
     const size_t n_w4 = gev_bp_words4(2 * ind_begin, 2 * n_ind), n_cg = ceil_div(n_traits, 4), slices = ceil_div(n_w4, GEV_TS_SLICE_W);
     GEVC(c->bp.cnt.ensure(3 * blk * sizeof(u32), st));
-    if (want_sums) {
-        GEVC(c->ts.trait.ensure(n_traits * n_ind, st));
-        GEVC(c->ts.b.ensure(n_cg * n_w4 * 32, st));                                        // 32 individuals x 16 columns a word: 512 bytes
-        GEVC(c->ts.acc.ensure(2 * n_cg * pad * 16, st));
-        GEVC(c->ts.out.ensure(2 * n_traits * blk, st));
-        HIPC(hipMemcpyAsync(c->ts.trait.p, trait, n_traits * n_ind * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)ceil_div(n_cg * (n_w4 / 4) * 128, 256)), dim3(256), 0, st, c->ts.trait, (u32)n_traits,
-                           (u64)ind_begin, (u64)n_ind, (u32)n_w4, (u32)n_cg, c->ts.b);
-        KCHECK();
-    }
-    for (size_t off = 0; off < n_snps; off += blk) {
-        const size_t n = std::min(blk, n_snps - off);
-        LdSide A;
-        GEVC(ld_prep_side(c, pop, chr, snp_begin + off, n, ind_begin, n_ind, c->bp.a, c->bp.cnt.as<u32>(), blk, A));
-        if (n_het) HIPC(hipMemcpyAsync(n_het + off, A.het, n * sizeof(u32), hipMemcpyDeviceToHost, st));
-        if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt + off, A.hom, n * sizeof(u32), hipMemcpyDeviceToHost, st));
-        if (!want_sums) continue;
-        HIPC(hipMemsetAsync(c->ts.acc.p, 0, 2 * n_cg * A.n_pad * 16 * sizeof(int), st));
-        for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535)                                        // (a grid's z)
-            hipLaunchKernelGGL(k_ts_product, dim3((unsigned)(A.n_pad / BP_TILE), (unsigned)slices, (unsigned)std::min<size_t>(n_cg - cg0, 65535)), dim3(256), 0, st,
-                               A.plane, (u32)A.n_pad, (u32)n_w4, c->ts.b, (u32)n_cg, (u32)cg0, c->ts.acc);
-        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_traits * n, 256)), dim3(256), 0, st, c->ts.acc, (u32)A.n_pad, (u32)n_cg,
-                           (u32)n_traits, (u32)n, (u32)blk, c->ts.out);
-        KCHECK();
-        int64_t* const outs[2] = {gsum, hetsum};
-        for (int o = 0; o < 2; o++)
-            if (outs[o]) HIPC(hipMemcpy2DAsync(outs[o] + off, n_snps * sizeof(int64_t), c->ts.out + (size_t)o * n_traits * blk, blk * sizeof(int64_t),
-                                               n * sizeof(int64_t), n_traits, hipMemcpyDeviceToHost, st));
-    }
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    if (want_sums) GEVC(dp_operand(c, k_ts_prep, trait, n_traits, ind_begin, n_ind, n_w4, 32, blk));   // 32 individuals x 16 columns a word: 512 bytes
+    LdSide A;
+    return dp_walk(c, n_snps, blk, n_traits, outs,
+        [&](size_t off, size_t n) -> int {
+            GEVC(ld_prep_side(c, pop, chr, snp_begin + off, n, ind_begin, n_ind, c->bp.a, c->bp.cnt.as<u32>(), blk, A));
+            if (n_het) HIPC(hipMemcpyAsync(n_het + off, A.het, n * sizeof(u32), hipMemcpyDeviceToHost, st));
+            if (n_hom_alt) HIPC(hipMemcpyAsync(n_hom_alt + off, A.hom, n * sizeof(u32), hipMemcpyDeviceToHost, st));
+            return GEV_OK;
+        },
+        [&](size_t n_pad, size_t cg0, size_t n_z) {
+            hipLaunchKernelGGL(k_ts_product, dim3((unsigned)(n_pad / BP_TILE), (unsigned)slices, (unsigned)n_z), dim3(256), 0, st,
+                               A.plane, (u32)n_pad, (u32)n_w4, c->dp.b, (u32)n_cg, (u32)cg0, c->dp.acc);
+        });
 }
 // the arithmetic of gev_traitsum.h compiled for the host on haplotype-major rows in host memory: no device, no context
 int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
@@ -4406,31 +4428,18 @@ int gev_dbg_trait_sums_host(const uint64_t* bits, size_t row_stride_words, size_
     const char* who = "dbg_trait_sums_host";
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
     GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
-    GEVC(ts_check_traits(who, trait, n_traits, n_ind));
+    GEVC(dp_check_columns(who, TS_NOUNS, trait, n_traits, n_ind));
     GEVC(check_host_rows(who, bits, row_stride_words, L, n_snps && n_ind));
     if (!n_snps) return GEV_OK;
-    if (!n_ind) { ts_zero(n_snps, n_traits, gsum, hetsum, n_het, n_hom_alt); return GEV_OK; }
+    const OptOut outs[4] = {{gsum, sizeof(int64_t), n_traits * n_snps}, {hetsum, sizeof(int64_t), n_traits * n_snps}, {n_het, sizeof(u32), n_snps}, {n_hom_alt, sizeof(u32), n_snps}};
+    if (!n_ind) { zero_outs(outs); return GEV_OK; }
     gev_trait_sums_host(bits, row_stride_words, snp_begin, n_snps, ind_begin, n_ind, trait, n_traits, gsum, hetsum, n_het, n_hom_alt);
     return GEV_OK;
 }
 // ---- scores per individual (gev_indscore.h) ----------------------------------------------------
-static int is_check_weights(const char* who, const int32_t* weight, size_t n_scores, size_t n_snps)
-{
-    if (n_snps > GEV_IS_MAX_SNPS) return fail(GEV_EUNSUPPORTED, "%s: %zu SNPs in one call, at most %zu (a digit's sum is an int32)", who, n_snps, (size_t)GEV_IS_MAX_SNPS);
-    if (!n_scores || !n_snps) return GEV_OK;
-    if (!weight) return fail(GEV_EINVAL, "%s: null weight array (%zu columns of %zu weights each)", who, n_scores, n_snps);
-    for (size_t i = 0; i < n_scores * n_snps; i++)
-        if (weight[i] > GEV_IS_MAX_W || weight[i] < -GEV_IS_MAX_W) return fail(GEV_EINVAL, "%s: weight %d of column %zu, SNP %zu beyond +-2^30", who, weight[i], i / n_snps, i % n_snps);
-    return GEV_OK;
-}
-// individuals of a block: their words of the two planes within ~1 GB as pair_block() has it, at most 65536 (2 KB of partials each at 64 columns)
-static size_t is_block(const gev_ctx* c, size_t snp_begin, size_t n_snps)
-{
-    return std::min<size_t>(output_chunk(c, (size_t)1 << 30, 2 * gev_bp_words4(snp_begin, n_snps) * 8), 65536);
-}
-// The individuals are walked in blocks of at most is_block() (gev_dbg_output_chunk caps them, and the rows of a staging pass): a block is
-// one pair_prep_side into c->bp.a; the weights' operand bytes are made once per call and serve every block; a block's scores are copied out
-// before the next block's kernels run (stream order), and the call returns when the last ones have arrived.
+// The individuals are walked in blocks (gev_dbg_output_chunk caps them, and the rows of a staging pass): their words of the two planes within
+// ~1 GB as pair_block() has it, at most 65536 (2 KB of partials each at 64 columns); a block is one pair_prep_side into c->bp.a; the weights'
+// operand bytes are made once per call
 int gev_ind_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps, size_t ind_begin, size_t n_ind,
                    const int32_t* weight, size_t n_scores, int64_t* gscore, int64_t* hetscore)
 {
@@ -4439,39 +4448,22 @@ int gev_ind_scores(gev_ctx* c, int pop, int chr, size_t snp_begin, size_t n_snps
     PopState& P = c->pop[pop];
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, P.cs[chr].L));
     GEVC(check_range(who, "individuals", ind_begin, n_ind, P.n_people));
-    GEVC(is_check_weights(who, weight, n_scores, n_snps));
+    GEVC(dp_check_columns(who, IS_NOUNS, weight, n_scores, n_snps));
     if (!n_ind) return GEV_OK;
     const OptOut outs[2] = {{gscore, sizeof(int64_t), n_scores * n_ind}, {hetscore, sizeof(int64_t), n_scores * n_ind}};
     if (!n_snps || !n_scores) { zero_outs(outs); return GEV_OK; }
     if (!gscore && !hetscore) return GEV_OK;
     GEVC(ensure_csr(c, pop));
     hipStream_t st = c->stream;
-    const size_t blk = std::min(is_block(c, snp_begin, n_snps), n_ind), pad = round_up(blk, BP_TILE);
-    const size_t n_w4 = gev_bp_words4(snp_begin, n_snps), n_cg = ceil_div(n_scores, 4), slices = ceil_div(n_w4, GEV_IS_SLICE_W);
-    GEVC(c->is.w.ensure(n_scores * n_snps, st));
-    GEVC(c->is.b.ensure(n_cg * n_w4 * 64, st));                                            // 64 SNPs x 16 columns a word: 1 KiB
-    GEVC(c->is.acc.ensure(2 * n_cg * pad * 16, st));
-    GEVC(c->is.out.ensure(2 * n_scores * blk, st));
-    HIPC(hipMemcpyAsync(c->is.w.p, weight, n_scores * n_snps * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_is_prep, dim3((unsigned)(n_cg * (n_w4 / 4))), dim3(256), 0, st, c->is.w, (u32)n_scores, (u64)snp_begin, (u64)n_snps, (u32)n_w4, (u32)n_cg, c->is.b);
-    KCHECK();
-    for (size_t off = 0; off < n_ind; off += blk) {
-        const size_t n = std::min(blk, n_ind - off), n_pad = round_up(n, BP_TILE);
-        GEVC(pair_prep_side(c, P, chr, ind_begin + off, n, snp_begin, n_snps, &c->bp.a, nullptr, nullptr, nullptr, nullptr));
-        const u64* px = c->bp.a;
-        HIPC(hipMemsetAsync(c->is.acc.p, 0, 2 * n_cg * n_pad * 16 * sizeof(int), st));
-        for (size_t cg0 = 0; cg0 < n_cg; cg0 += 65535)                                        // (a grid's z)
-            hipLaunchKernelGGL(k_is_product, dim3((unsigned)(n_pad / BP_TILE), (unsigned)slices, (unsigned)std::min<size_t>(n_cg - cg0, 65535)), dim3(256), 0, st,
-                               px, px + n_w4 * n_pad, (u32)n_pad, (u32)n_w4, c->is.b, (u32)n_cg, (u32)cg0, c->is.acc);
-        hipLaunchKernelGGL(k_ts_finish, dim3((unsigned)ceil_div(2 * n_scores * n, 256)), dim3(256), 0, st, c->is.acc, (u32)n_pad, (u32)n_cg,
-                           (u32)n_scores, (u32)n, (u32)blk, c->is.out);
-        KCHECK();
-        for (int o = 0; o < 2; o++)
-            if (outs[o].host) HIPC(hipMemcpy2DAsync((int64_t*)outs[o].host + off, n_ind * sizeof(int64_t), c->is.out + (size_t)o * n_scores * blk, blk * sizeof(int64_t),
-                                                    n * sizeof(int64_t), n_scores, hipMemcpyDeviceToHost, st));
-    }
-    HIPC(hipStreamSynchronize(st));
-    return GEV_OK;
+    const size_t n_w4 = gev_bp_words4(snp_begin, n_snps), blk = std::min(std::min<size_t>(output_chunk(c, (size_t)1 << 30, 2 * n_w4 * 8), 65536), n_ind), n_cg = ceil_div(n_scores, 4), slices = ceil_div(n_w4, GEV_IS_SLICE_W);
+    GEVC(dp_operand(c, k_is_prep, weight, n_scores, snp_begin, n_snps, n_w4, 64, blk));                // 64 SNPs x 16 columns a word: 1 KiB
+    return dp_walk(c, n_ind, blk, n_scores, outs,
+        [&](size_t off, size_t n) { return pair_prep_side(c, P, chr, ind_begin + off, n, snp_begin, n_snps, &c->bp.a, nullptr, nullptr, nullptr, nullptr); },
+        [&](size_t n_pad, size_t cg0, size_t n_z) {
+            const u64* px = c->bp.a;
+            hipLaunchKernelGGL(k_is_product, dim3((unsigned)(n_pad / BP_TILE), (unsigned)slices, (unsigned)n_z), dim3(256), 0, st,
+                               px, px + n_w4 * n_pad, (u32)n_pad, (u32)n_w4, c->dp.b, (u32)n_cg, (u32)cg0, c->dp.acc);
+        });
 }
 // the arithmetic of gev_indscore.h compiled for the host on haplotype-major rows in host memory: no device, no context
 int gev_dbg_ind_scores_host(const uint64_t* bits, size_t row_stride_words, size_t n_people, size_t L, size_t snp_begin, size_t n_snps,
@@ -4480,7 +4472,7 @@ int gev_dbg_ind_scores_host(const uint64_t* bits, size_t row_stride_words, size_
     const char* who = "dbg_ind_scores_host";
     GEVC(check_range(who, "SNPs", snp_begin, n_snps, L));
     GEVC(check_range(who, "individuals", ind_begin, n_ind, n_people));
-    GEVC(is_check_weights(who, weight, n_scores, n_snps));
+    GEVC(dp_check_columns(who, IS_NOUNS, weight, n_scores, n_snps));
     GEVC(check_host_rows(who, bits, row_stride_words, L, n_snps && n_ind));
     if (!n_ind) return GEV_OK;
     const OptOut outs[2] = {{gscore, sizeof(int64_t), n_scores * n_ind}, {hetscore, sizeof(int64_t), n_scores * n_ind}};

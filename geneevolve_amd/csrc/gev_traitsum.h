@@ -7,20 +7,15 @@
 //     hetsum[t][j] = sum_{i heterozygous at j} q[t][i]                                                 (int64)
 // and the n_het / n_hom_alt of gev_ld_word_counts.  The genotype-class sums follow: S1 = hetsum, S2 = (gsum - hetsum) / 2.
 //
-// Both are products of SNPs x individuals against individuals x traits on bytes.
+// Both are products of SNPs x individuals against individuals x traits on bytes: the digit-column product of gev_digitprod.h with the
+// SNPs as rows and the individuals summed (n_ind <= GEV_TS_MAX_IND), the traits its columns.
 // Side A is the LD side unchanged (gev_ldcount.h): one plane of masked SNP-major words per block of SNPs; per 32-bit half word
 //     genotype bytes      gev_ld_expand_gen                                      byte b of word j = individual 4 b + j, value 0/1/2
 //     heterozygote bytes  x = (w ^ w >> 1) & 0x55555555, (x >> 2 j) & 0x01010101   the same order, value 0/1
-// Side B are the traits: a quantum is split into four balanced base-256 digits in [-128, 127] (q = sum_k d_k 256^k; the last one is
-// what is left, |d_3| <= 65), 4 traits x 4 digits = the 16 columns of one fragment (column = 4 (t & 3) + k of column group t >> 2).
-// The accumulators are i32: |digit| <= 128, g <= 2, so n_ind <= 2^22 keeps them in range; sum_k acc_k 256^k is formed in 64 bits.
-//
-// The one thing that differs from the products of gev_bitprod.h: there the permutation of the summation index inside a matrix step
-// cancels because both operands come from the same function of (lane, step).  Here side B is made elsewhere, so its bytes are laid
-// out in exactly the order the expansion gives side A's: in the step of words 4 W .. 4 W + 3 (counted from the first word of the
-// haplotype range) lane group q carries word 4 W + q, matrix step s its half s, and position 4 j + b of the 16 bytes (register j,
-// byte b) holds individual 32 (w_first + 4 W + q) + 16 s + 4 b + j -- an individual of the population, not of the range, which need
-// not begin at individual 0 or on a word.  gev_ts_operand_word is that rule, for the device and the host from one source.
+// Side B in that order: in the step of words 4 W .. 4 W + 3 (counted from the first word of the haplotype range) lane group q carries
+// word 4 W + q, matrix step s its half s, and position 4 j + b of the 16 bytes (register j, byte b) holds individual
+// 32 (w_first + 4 W + q) + 16 s + 4 b + j -- an individual of the population, not of the range, which need not begin at individual 0
+// or on a word.  gev_ts_operand_word is that rule.
 //
 // The first part of this file is plain C++ (gev_dbg_trait_sums_host and any host program that includes this file alone run the same
 // masking, digit split, byte order of both operands and recombination with a plain integer loop in place of the matrix instruction);
@@ -29,24 +24,13 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
-#include "gev_ldcount.h"                           // gev_ld_word_counts, gev_ld_expand_gen; gev_bitprod.h: the range mask, the words of a range, the byte store and dot
+#include "gev_ldcount.h"                           // gev_ld_word_counts, gev_ld_expand_gen; gev_bitprod.h: the range mask, the words of a range, the byte store
+#include "gev_digitprod.h"                         // the digit split, the operand packing, the host product of a row; the epilogue and the finish
 
-#define GEV_TS_MAX_IND ((size_t)1 << 22)          // 128 * 2 * 2^22 = 2^30: an accumulator stays an int32
-#define GEV_TS_MAX_Q ((int32_t)1 << 30)           // |quantum|
+#define GEV_TS_MAX_IND GEV_DP_MAX_N               // individuals summed
+#define GEV_TS_MAX_Q GEV_DP_MAX_VAL               // |quantum|
 #define GEV_TS_SLICE_W 64u                        // words of a SNP's row one workgroup sums: 2048 individuals (a multiple of the 4 words of a step)
 
-// balanced base-256 digit k (0..3) of a quantum: q = d0 + 256 d1 + 256^2 d2 + 256^3 d3, d0..d2 in [-128, 127]
-GEV_PC_HD inline int32_t gev_ts_digit(int32_t q, int k)
-{
-    int32_t d = 0;
-    for (int i = 0; i <= k; i++) { d = ((q + 128) & 255) - 128; q = (q - d) / 256; }
-    return d;
-}
-// sum_k acc[k] 256^k
-GEV_PC_HD inline int64_t gev_ts_recombine(const int32_t acc[4])
-{
-    return (int64_t)acc[0] + (int64_t)acc[1] * 256 + (int64_t)acc[2] * 65536 + (int64_t)acc[3] * 16777216;
-}
 // heterozygote bytes of a 32-bit half word (16 individuals), in the order of gev_ld_expand_gen
 GEV_PC_HD inline void gev_ts_expand_het(uint32_t w, uint32_t e[4])
 {
@@ -61,14 +45,7 @@ GEV_PC_HD inline void gev_ts_expand_het(uint32_t w, uint32_t e[4])
 // beyond n_traits.  trait: [n_traits][n_ind], entry i = individual ind_begin + i
 GEV_PC_HD inline uint32_t gev_ts_operand_word(const int32_t* trait, size_t n_traits, size_t ind_begin, size_t n_ind, size_t i_half, size_t cg, int col, int j)
 {
-    const size_t t = 4 * cg + (size_t)(col >> 2);
-    if (t >= n_traits) return 0;
-    uint32_t r = 0;
-    for (int b = 0; b < 4; b++) {
-        const size_t i = i_half + 4 * (size_t)b + (size_t)j;
-        if (i >= ind_begin && i - ind_begin < n_ind) r |= (uint32_t)(uint8_t)gev_ts_digit(trait[t * n_ind + (i - ind_begin)], col & 3) << (8 * b);
-    }
-    return r;
+    return gev_dp_operand_word(trait, n_traits, ind_begin, n_ind, cg, col, [=](int b) { return i_half + 4 * (size_t)b + (size_t)j; });
 }
 // The host form on haplotype-major rows (row r = bits + r * stride words, SNP j = bit j & 63 of word j >> 6): SNPs [snp_begin, +n_snps)
 // turned SNP-major over haplotypes [2 ind_begin, +2 n_ind), masked, counted and expanded as the device does; the traits laid out as
@@ -80,15 +57,8 @@ inline void gev_trait_sums_host(const uint64_t* bits, size_t stride, size_t snp_
     const size_t h0 = 2 * ind_begin, nh = 2 * n_ind, w_first = h0 >> 6;
     const size_t n_w4 = gev_bp_words4(h0, nh), nb = n_w4 * 32, n_cg = (n_traits + 3) / 4;
     const bool want_sums = (gsum || hetsum) && n_traits;
-    std::vector<int8_t> tb(want_sums ? n_cg * 16 * nb : 0);         // [column group][column][the bytes of a row]
-    for (size_t cg = 0; cg < n_cg && want_sums; cg++)
-        for (int col = 0; col < 16; col++)
-            for (size_t w = 0; w < n_w4; w++)
-                for (int half = 0; half < 2; half++) {
-                    uint32_t e[4];
-                    for (int j = 0; j < 4; j++) e[j] = gev_ts_operand_word(trait, n_traits, ind_begin, n_ind, (w_first + w) * 32 + 16 * (size_t)half, cg, col, j);
-                    gev_bp_store16(e, &tb[(cg * 16 + (size_t)col) * nb + w * 32 + 16 * (size_t)half]);
-                }
+    std::vector<int8_t> tb;
+    if (want_sums) tb = gev_dp_table_host(n_cg, nb, [=](size_t cg, int col, size_t p, int j) { return gev_ts_operand_word(trait, n_traits, ind_begin, n_ind, w_first * 32 + 16 * p, cg, col, j); });
     std::vector<uint64_t> row(n_w4);
     std::vector<int8_t> gb(nb), hb(nb);
     for (size_t s = 0; s < n_snps; s++) {
@@ -108,15 +78,7 @@ inline void gev_trait_sums_host(const uint64_t* bits, size_t stride, size_t snp_
         }
         if (n_het) n_het[s] = het;
         if (n_hom_alt) n_hom_alt[s] = hom;
-        for (size_t t = 0; t < n_traits && want_sums; t++) {
-            int32_t ag[4], ah[4];
-            for (int k = 0; k < 4; k++) {
-                const int8_t* b = &tb[((t >> 2) * 16 + 4 * (t & 3) + (size_t)k) * nb];
-                ag[k] = (int32_t)gev_bp_dot_i8(gb.data(), b, nb); ah[k] = (int32_t)gev_bp_dot_i8(hb.data(), b, nb);
-            }
-            if (gsum) gsum[t * n_snps + s] = gev_ts_recombine(ag);
-            if (hetsum) hetsum[t * n_snps + s] = gev_ts_recombine(ah);
-        }
+        if (want_sums) gev_dp_row_host(tb, nb, gb.data(), hb.data(), n_traits, n_snps, s, gsum, hetsum);
     }
 }
 
@@ -130,11 +92,9 @@ inline void gev_trait_sums_host(const uint64_t* bits, size_t stride, size_t snp_
 // k_ts_product: v_mfma_i32_16x16x64_i8, A = 16 SNPs (row = lane & 15), B = the 16 columns of a column group (column = lane & 15),
 //   two accumulator sets (genotype bytes, heterozygote bytes).  A block of SNPs against 16 columns is far too few waves, so the
 //   individuals are split: blockIdx.x = 128 SNPs (four waves of TS_FR fragments), blockIdx.y = a slice of GEV_TS_SLICE_W words,
-//   blockIdx.z = the column group; the i32 partials are added with vector atomics (integer adds commute; two's-complement wrap is
-//   harmless while the total is in range).  The plane is padded with zero rows to BP_TILE SNPs and to 4 words, tb is whole steps, so
-//   no load needs a bound; a zero partial is not added.  acc: [2 sets][n_cg][n_pad SNPs][16 columns].
-// k_ts_finish: sum_k acc_k 256^k per (trait, SNP) in 64 bits, out: [2 sets][n_traits][out_stride SNPs].
-// Every store and atomic is a vector one.
+//   blockIdx.z = the column group; the partials go to acc through dp_add_partials.  The plane is padded with zero rows to BP_TILE SNPs
+//   and to 4 words, tb is whole steps, so no load needs a bound.  acc: [2 sets][n_cg][n_pad SNPs][16 columns].
+// The finish is k_dp_finish (gev_digitprod.h).  Every store is a vector one.
 // ------------------------------------------------------------------------------------------
 #define TS_FR 2                                   // fragments of 16 SNPs a wave: 4 waves x 32 = the BP_TILE SNPs of a workgroup
 
@@ -146,12 +106,7 @@ __global__ void __launch_bounds__(256) k_ts_prep(const int32_t* __restrict__ tra
     const u32 lane = (u32)id & 63u, s = ((u32)(id >> 6)) & 1u, col = lane & 15u, q = lane >> 4;
     const size_t step = (id >> 7) % steps, cg = (id >> 7) / steps;
     const size_t i_half = ((size_t)((2 * ind_begin) >> 6) + 4 * step + q) * 32 + 16 * s;
-    uint4 v;
-    v.x = gev_ts_operand_word(trait, n_traits, (size_t)ind_begin, (size_t)n_ind, i_half, cg, (int)col, 0);
-    v.y = gev_ts_operand_word(trait, n_traits, (size_t)ind_begin, (size_t)n_ind, i_half, cg, (int)col, 1);
-    v.z = gev_ts_operand_word(trait, n_traits, (size_t)ind_begin, (size_t)n_ind, i_half, cg, (int)col, 2);
-    v.w = gev_ts_operand_word(trait, n_traits, (size_t)ind_begin, (size_t)n_ind, i_half, cg, (int)col, 3);
-    tb[id] = v;
+    tb[id] = dp_operand16([&](int j) { return gev_ts_operand_word(trait, n_traits, (size_t)ind_begin, (size_t)n_ind, i_half, cg, (int)col, j); });
 }
 
 // plane: n_w4 words x n_pad SNPs (k_ld_prep's); cg0: the column group of blockIdx.z = 0
@@ -171,7 +126,7 @@ __global__ void __launch_bounds__(256) k_ts_product(const u64* __restrict__ plan
         const uint4 b[2] = {pb[0], pb[64]};
 #pragma unroll
         for (int s = 0; s < 2; s++) {
-            const pc_v4i fb = pc_v4i{(int)b[s].x, (int)b[s].y, (int)b[s].z, (int)b[s].w};
+            const pc_v4i fb = dp_frag_b(b[s]);
 #pragma unroll
             for (int m = 0; m < TS_FR; m++) {
                 const u32 w32 = (u32)(a[m] >> (32 * s));
@@ -181,25 +136,6 @@ __global__ void __launch_bounds__(256) k_ts_product(const u64* __restrict__ plan
             }
         }
     }
-    int* const og = acc + ((size_t)cg * n_pad + a0) * 16u + r;       // C/D: column = lane & 15, row = 4 (lane >> 4) + register
-    int* const oh = og + (size_t)n_cg * n_pad * 16u;
-#pragma unroll
-    for (int m = 0; m < TS_FR; m++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const size_t o = (size_t)(16 * m + 4 * (int)q + v) * 16u;
-            if (ag[m][v]) atomicAdd(og + o, ag[m][v]);
-            if (ah[m][v]) atomicAdd(oh + o, ah[m][v]);
-        }
-}
-
-__global__ void __launch_bounds__(256) k_ts_finish(const int* __restrict__ acc, u32 n_pad, u32 n_cg, u32 n_traits, u32 n, u32 out_stride, long long* __restrict__ out)
-{
-    const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (id >= (size_t)2 * n_traits * n) return;
-    const u32 j = (u32)(id % n), t = (u32)((id / n) % n_traits), set = (u32)(id / ((size_t)n * n_traits));
-    const int4 a = *(const int4*)(acc + (((size_t)set * n_cg + (t >> 2)) * n_pad + j) * 16u + 4u * (t & 3u));
-    const int32_t d[4] = {a.x, a.y, a.z, a.w};
-    out[((size_t)set * n_traits + t) * out_stride + j] = gev_ts_recombine(d);
+    dp_add_partials<TS_FR>(ag, ah, acc, n_cg, n_pad, cg, a0, r, q);
 }
 #endif

@@ -5,7 +5,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .relatedness import _range
+from ._ranges import individuals as _range
 
 Q40 = float(1 << 40)
 

@@ -14,6 +14,7 @@ from tests import helpers
 from tests.ind_scores_inputs import L, N_PEOPLE, NAMES, STEP, W_MAX, genotypes, numpy_scores, one_hot_value, one_hot_weights, population_rows, random_weights
 from tests.test_gpu_snp_counts import overlay_situations, unpacked
 from tests.test_gpu_trait_sums import founder_plane
+from tests.trait_sums_inputs import NAMES as TS_NAMES, numpy_trait_sums, random_quanta
 
 pytestmark = pytest.mark.gpu
 
@@ -150,6 +151,35 @@ def test_each_output_may_be_null_and_empty_requests(founders):
     assert f(ctx.h, 0, 0, 70, 200, 5, 20, w, 3, None, None) == 0
     got = ctx.ind_scores(0, 0, np.zeros((0, 200), dtype=np.int32), 70, 200, 5, 20)
     assert got[0].shape == got[1].shape == (0, 20)
+
+
+@pytest.mark.parametrize("chunk", [0, 7], ids=["byte budgets", "output chunk 7"])
+def test_scores_and_trait_sums_take_turns_on_one_context(founders, chunk):
+    """the two calls share one set of scratch buffers (gev_digitprod.h): scores and trait sums alternate on one context, so that the set
+    is grown and reused across the two layouts -- 17 columns on everything, one on a few, then the other way round, a trait-sum call
+    that wants the counts alone and so touches none of it, and the first call again.  Every result equals its host build and numpy"""
+    ctx, geno, rows = founders
+    bits = capi.unpack_rows(rows, L)
+    rs = np.random.RandomState(70 + chunk)
+
+    def trait_sums(q, s0, ns, i0, ni):
+        got = ctx.snp_trait_sums(0, 0, q, s0, ns, i0, ni)
+        host = ctx.L.dbg_trait_sums_host(rows, L, q, s0, ns, i0, ni)
+        for name, g, h, x in zip(TS_NAMES, got, host, numpy_trait_sums(bits, s0, ns, i0, ni, q)):
+            assert g.shape == x.shape and np.array_equal(g, x) and np.array_equal(g, h), f"chunk {chunk}: {name} of {q.shape[0]} traits, SNPs [{s0},+{ns}) individuals [{i0},+{ni})"
+
+    ctx.dbg_output_chunk(chunk)
+    try:
+        w17 = random_weights(rs, 17, L)
+        first = check(ctx, 0, 0, geno, w17, 0, L, 0, N_PEOPLE, f"chunk {chunk}, first", rows)
+        trait_sums(random_quanta(rs, 1, 129), 63, 130, 5, 129)
+        check(ctx, 0, 0, geno, random_weights(rs, 1, 15), 56, 15, 100, 1, f"chunk {chunk}, one column", rows)
+        trait_sums(random_quanta(rs, 17, N_PEOPLE), 0, L, 0, N_PEOPLE)
+        trait_sums(np.zeros((0, N_PEOPLE), dtype=np.int32), 0, L, 0, N_PEOPLE)
+        again = check(ctx, 0, 0, geno, w17, 0, L, 0, N_PEOPLE, f"chunk {chunk}, again", rows)
+        assert all(np.array_equal(a, b) for a, b in zip(first, again)), "the first call again gives the same integers"
+    finally:
+        ctx.dbg_output_chunk(0)
 
 
 # ---- the mutation overlay and fixture replays ------------------------------------------------------------------------------------------

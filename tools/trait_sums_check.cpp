@@ -98,9 +98,9 @@ int main()
             const int64_t v = (int64_t)e + d;
             if (v > (1 << 30) || v < -(1 << 30)) continue;
             int32_t dg[4];
-            for (int j = 0; j < 4; j++) dg[j] = gev_ts_digit((int32_t)v, j);
+            for (int j = 0; j < 4; j++) dg[j] = gev_dp_digit((int32_t)v, j);
             n_checked++;
-            if (gev_ts_recombine(dg) != v || dg[0] < -128 || dg[0] > 127 || dg[1] < -128 || dg[1] > 127 || dg[2] < -128 || dg[2] > 127 || dg[3] < -65 || dg[3] > 65) { n_bad++; printf("MISMATCH: digits of %lld\n", (long long)v); }
+            if (gev_dp_recombine(dg) != v || dg[0] < -128 || dg[0] > 127 || dg[1] < -128 || dg[1] > 127 || dg[2] < -128 || dg[2] > 127 || dg[3] < -65 || dg[3] > 65) { n_bad++; printf("MISMATCH: digits of %lld\n", (long long)v); }
         }
     printf("%llu shapes checked, %llu mismatches\n", n_checked, n_bad);
     return n_bad ? 1 : 0;
