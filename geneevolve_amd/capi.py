@@ -34,6 +34,10 @@ class gev_ibd_segment(C.Structure):
     _fields_ = [("st", C.c_uint64), ("en", C.c_uint64), ("row_a", C.c_uint32), ("row_b", C.c_uint32)]
 
 
+class gev_lineage_site(C.Structure):
+    _fields_ = [("sum_sq", C.c_uint64), ("n_covered", C.c_uint32), ("n_lineages", C.c_uint32), ("top_count", C.c_uint32), ("top_founder", C.c_uint32)]
+
+
 class gev_roh_params(C.Structure):
     _fields_ = [("min_snps", C.c_uint32), ("reserved", C.c_uint32), ("min_bp", C.c_uint64), ("max_gap_bp", C.c_uint64)]
 
@@ -95,13 +99,15 @@ PART_DTYPE = np.dtype(gev_part)
 MOVE_DTYPE = np.dtype(gev_move)
 SEGMENT_DTYPE = np.dtype(gev_ibd_segment)       # 24 bytes: st, en (uint64, [st, en)), row_a, row_b (uint32)
 IBD_ALL_PAIRS, IBD_UPPER = 0, 1
+LINEAGE_SITE_DTYPE = np.dtype(gev_lineage_site)  # 24 bytes: sum_sq (uint64), n_covered, n_lineages, top_count, top_founder (uint32)
+NO_FOUNDER = 0xFFFFFFFF                          # GEV_NO_FOUNDER: the founder id of a position no part covers
 ROH_PARAMS_DTYPE = np.dtype(gev_roh_params)      # 24 bytes: min_snps, reserved (uint32), min_bp, max_gap_bp (uint64); 0 = no limit, each
 ROH_SEGMENT_DTYPE = np.dtype(gev_roh_segment)    # 32 bytes: st, en (uint64, both inclusive), ind, snp_first, n_snps, reserved (uint32)
 
 # Every function include/geneevolve_amd.h declares, in its order, as "return: parameters" (tests hold the table equal to the header
 # and check that the library exports every name).  By value: int, size (size_t), u32, u64, f64.  `ctx*` is the context handle.  A
 # pointer is its element and a star: int i32 u32 i64 u64 ull (unsigned long long) size f32 f64, u8 (char and uint8_t alike), void, or a
-# gev_* struct by its name without the prefix; two stars: a pointer to pointers.  Returns: int, void, f64, str (const char*).
+# gev_* struct by its name without the prefix; two stars: a pointer to pointers.  Returns: int, u32, void, f64, str (const char*).
 ABI = {
     "last_error": "str:",
     "version": "str:",
@@ -194,6 +200,10 @@ ABI = {
     "dbg_ibd_host": "int: part* u64* size part* u64* size u64 u64* u32* u64*",
     "ibd_segments": "int: ctx* int int size size int size size u64 int ibd_segment* size u64*",
     "dbg_ibd_segments_host": "int: part* u64* size part* u64* size u64 int ibd_segment* size u64*",
+    "founder_at": "int: ctx* int int size size u64* size u64* u32*",
+    "founder_counts": "int: ctx* int int size size u64* size u64* u32* lineage_site* u32*",
+    "dbg_lineage_host": "int: part* u64* size u64* size u64* int u32* u32* lineage_site* u32*",
+    "dbg_lineage_tile": "u32:",
     "roh_summary": "int: ctx* int int size size size size roh_params* u32* u64* u32* u64* u32*",
     "roh_segments": "int: ctx* int int size size size size roh_params* roh_segment* size u64*",
     "dbg_roh_host": "int: u64* size size size u64* size size size size roh_params* u32* u64* u32* u64* u32* roh_segment* size u64*",
@@ -238,7 +248,7 @@ ABI = {
 }
 ABI_SYMBOLS = list(ABI)
 
-_RETURNS = {"int": C.c_int, "void": None, "f64": C.c_double, "str": C.c_char_p}
+_RETURNS = {"int": C.c_int, "u32": C.c_uint32, "void": None, "f64": C.c_double, "str": C.c_char_p}
 _BY_VALUE = {"int": C.c_int, "size": C.c_size_t, "u32": C.c_uint32, "u64": C.c_uint64, "f64": C.c_double, "ctx*": C.c_void_p}
 # numpy kinds and item size of a pointer's elements (char* takes bytes and either signedness)
 _ELEMENTS = {"int": ("i", C.sizeof(C.c_int)), "i32": ("i", 4), "u32": ("u", 4), "i64": ("i", 8), "u64": ("u", 8),
@@ -362,6 +372,22 @@ def _ibd_outs(n_a, n_b, want=(True, True, True)):
     """the three matrices of the IBD calls (None where not wanted)"""
     shape = (max(n_a, 0), max(n_b, 0))
     return tuple(np.empty(shape, dtype=dt) if w else None for dt, w in zip((np.uint64, np.uint32, np.uint64), want))
+
+
+def _founder_haps(n_founder_haps, n_pop):
+    """the founder haplotypes per root population as the lineage calls take them: uint64 [n_pop]"""
+    nfh = _arr(n_founder_haps, np.uint64)
+    assert nfh.shape == (n_pop,), f"one founder count per root population ({n_pop}), {nfh.shape} given"
+    return nfh
+
+
+def _lineage_outs(n_pos, n_rows, n_founders, n_pop, want):
+    """(fid, counts, site, pop_counts) of the lineage calls for want = the names wanted (None where not wanted)"""
+    n_pos, n_rows = max(n_pos, 0), max(n_rows, 0)
+    shapes = {"fid": ((n_pos, n_rows), np.uint32), "counts": ((n_pos, n_founders), np.uint32), "site": ((n_pos,), LINEAGE_SITE_DTYPE),
+              "pop_counts": ((n_pos, n_pop), np.uint32)}
+    assert set(want) <= set(shapes), want
+    return tuple(np.empty(*shapes[k]) if k in want else None for k in ("fid", "counts", "site", "pop_counts"))
 
 
 def _record_list(call, dtype):
@@ -562,6 +588,22 @@ class GevLibrary:
         f, pairs = self._f("dbg_ibd_segments_host"), IBD_UPPER if upper else IBD_ALL_PAIRS
         return _record_list(lambda out, cap, n: self.check(f(parts_a, off_a, len(off_a) - 1, parts_b, off_b, len(off_b) - 1, int(min_bp), pairs, out, cap, n)), SEGMENT_DTYPE)
 
+    def dbg_lineage_host(self, parts, off, pos, n_founder_haps, want=("fid", "counts", "site", "pop_counts")):
+        """(fid, counts, site, pop_counts) as GevContext.founder_at and founder_counts give them, by the library's walk and reductions
+        compiled for the host (no device needed).  parts / off: as download_intervals returns them (off: rows + 1 entries); pos: uint64
+        positions in non-decreasing order; n_founder_haps: the founder haplotypes of every root population (its length is n_pop); want:
+        an output that is not named goes in as NULL and comes back as None"""
+        parts = _arr(parts, PART_DTYPE); off = _arr(off, np.uint64); pos = _arr(pos, np.uint64).ravel()
+        nfh = _arr(n_founder_haps, np.uint64).ravel()
+        n_rows = len(off) - 1
+        outs = _lineage_outs(len(pos), n_rows, int(sum(int(x) for x in nfh)) if set(want) & {"counts"} else 0, len(nfh), want)
+        self.check(self._f("dbg_lineage_host")(parts, off, n_rows, pos, len(pos), nfh, len(nfh), *outs))
+        return outs
+
+    def dbg_lineage_tile(self):
+        """founder bins a workgroup of the lineage count kernel histograms at once"""
+        return int(self._f("dbg_lineage_tile")())
+
     def dbg_roh_host(self, bits, L, pos, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0, want_cover=True, want_list=True):
         """the library's run-of-homozygosity word logic compiled for the host (no device needed) -> (n_roh, roh_bp, roh_snps, max_bp, cover,
         segments) as GevContext.roh_summary and roh_segments give them (cover / segments None where not wanted).  bits: uint64
@@ -620,6 +662,7 @@ class GevContext:
         self._nsnp = {}
         self._span_bp = {}
         self._snp_span_bp = {}
+        self._founder_haps = {}
         self._ncv = {}
         self._chr_off = set()
         self._ph_seeds = 0
@@ -661,21 +704,26 @@ class GevContext:
     def upload_founders(self, pop, chr, words, L):
         words = _arr(words, np.uint64)
         self._call("upload_founders", pop, chr, words, words.shape[1], words.shape[0], L)
+        self._saw_founders(pop, words.shape[0])
 
     def upload_cv_founders(self, pop, phen, chr, words, ncv):
         words = _arr(words, np.uint64)
         self._call("upload_cv_founders", pop, phen, chr, words, words.shape[1], words.shape[0], ncv)
+        self._saw_founders(pop, words.shape[0])
 
     def synth_founders(self, pop, chr, nhap, seed):
         self._call("synth_founders", pop, chr, nhap, seed)
+        self._saw_founders(pop, nhap)
 
     def upload_founder_panel(self, pop, chr, words, L):
         words = _arr(words, np.uint64)
         self._call("upload_founder_panel", pop, chr, words, words.shape[1], words.shape[0], L)
+        self._saw_founders(pop, words.shape[0])
 
     def synth_founder_panel(self, pop, chr, nhap, seed):
         """read-only founder panel of ROOT population `pop` (immigrants' rows are rebuilt from it, set_migrant_rows(False))"""
         self._call("synth_founder_panel", pop, chr, nhap, seed)
+        self._saw_founders(pop, nhap)
 
     def set_migrant_rows(self, on):
         """False: export_rows packs no genotype rows, import_rows rebuilds them from the founder panels"""
@@ -683,6 +731,20 @@ class GevContext:
 
     def synth_cv_founders(self, pop, phen, chr, nhap, seed):
         self._call("synth_cv_founders", pop, phen, chr, nhap, seed)
+        self._saw_founders(pop, nhap)
+
+    def _saw_founders(self, pop, nhap):
+        """the founder haplotypes of root population `pop`, as its uploads and syntheses gave them (the largest: lineage.py's founder ids)"""
+        self._founder_haps[pop] = max(self._founder_haps.get(pop, 0), int(nhap))
+
+    def founder_haps(self, n_founder_haps=None):
+        """uint64 [n_pop] as the lineage calls take it: the argument, or what the founder uploads and syntheses of this context said"""
+        if n_founder_haps is not None:
+            return _founder_haps(n_founder_haps, self.n_pop)
+        if len(self._founder_haps) < self.n_pop:
+            missing = [p for p in range(self.n_pop) if p not in self._founder_haps]
+            raise ValueError(f"n_founder_haps: no founders were uploaded or synthesised for root population(s) {missing}; pass the counts")
+        return np.array([self._founder_haps[p] for p in range(self.n_pop)], dtype=np.uint64)
 
     # ---- generation steps
     def init_gen0(self, pop, n_people, seed_gen0, want_sex=True):
@@ -1231,6 +1293,27 @@ class GevContext:
         n_b = self._rest_ind(pop_b, b_begin, n_b, 2)
         pairs = IBD_UPPER if upper else IBD_ALL_PAIRS
         return _record_list(lambda out, cap, n: self._call("ibd_segments", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), pairs, out, cap, n), SEGMENT_DTYPE)
+
+    def founder_at(self, pop, chr, pos, row_begin=0, n_rows=None, n_founder_haps=None):
+        """-> fid uint32 [n_pos][n_rows]: the founder id of haplotype row row_begin + i at pos[p] (uint64, non-decreasing): base[root
+        population] + hap_index of the part that covers the position, base the exclusive prefix sum of n_founder_haps (None: what the
+        founder uploads and syntheses said); NO_FOUNDER where no part covers it.  Walked on the device from the ancestry interval lists"""
+        n_rows = self._rest_ind(pop, row_begin, n_rows, 2)
+        pos = _arr(pos, np.uint64).ravel(); nfh = self.founder_haps(n_founder_haps)
+        fid = _lineage_outs(len(pos), n_rows, 0, self.n_pop, ("fid",))[0]
+        self._call("founder_at", pop, chr, row_begin, n_rows, pos, len(pos), nfh, fid)
+        return fid
+
+    def founder_counts(self, pop, chr, pos, row_begin=0, n_rows=None, n_founder_haps=None, want=("counts", "site", "pop_counts")):
+        """-> (counts uint32 [n_pos][F], site LINEAGE_SITE_DTYPE [n_pos], pop_counts uint32 [n_pos][n_pop]) per position over the haplotype
+        rows [row_begin, +n_rows): the rows by founder id, their summary (sum_sq, n_covered, n_lineages, top_count, top_founder = the
+        lowest founder id with the largest count) and the rows by root population of the covering part.  want: an output that is not
+        named goes in as NULL and comes back as None (counts is the large one)"""
+        n_rows = self._rest_ind(pop, row_begin, n_rows, 2)
+        pos = _arr(pos, np.uint64).ravel(); nfh = self.founder_haps(n_founder_haps)
+        outs = _lineage_outs(len(pos), n_rows, int(sum(int(x) for x in nfh)) if "counts" in want else 0, self.n_pop, set(want) - {"fid"})[1:]
+        self._call("founder_counts", pop, chr, row_begin, n_rows, pos, len(pos), nfh, *outs)
+        return outs
 
     def roh_summary(self, pop, chr, snp_begin=0, n_snps=None, ind_begin=0, n_ind=None, min_snps=0, min_bp=0, max_gap_bp=0, want_cover=True):
         """-> (n_roh, roh_bp, roh_snps, max_bp, cover): per individual of [ind_begin, +n_ind) over its qualifying runs of homozygosity among

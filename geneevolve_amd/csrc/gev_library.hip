@@ -29,6 +29,7 @@
 #include "gev_traitsum.h"
 #include "gev_indscore.h"
 #include "gev_ibd.h"
+#include "gev_lineage.h"
 #include "gev_roh.h"
 #include "gev_select.h"
 #include "gev_pedigree.h"
@@ -373,6 +374,7 @@ struct gev_ctx {
     struct DigitProdState { Dev<int32_t> val, acc; Dev<uint4> b; Dev<long long> out; } dp;   // gev_snp_trait_sums and gev_ind_scores (gev_digitprod.h), one set for both under the rule above: the columns (quanta, weights), their operand bytes, the i32 partials and the 64-bit sums of a block of rows
     struct SnpCountState { Dev<u32> cnt; } snp;                                               // gev_snp_genotype_counts (gev_snpcount.h): the two count vectors of a call
     struct IbdState { DevBytes out; Dev<u32> flag; Dev<gev_ibd_segment> seg; } ibd;           // gev_ibd_sharing / gev_ancestry_bp / gev_ibd_segments (gev_ibd.h): a sub-block's results, the flag of a bad root population, a strip's records
+    struct LineageState { Dev<u64> pos, tab; Dev<u32> flag, lab, counts, pop, ppop; Dev<gev_lineage_site> site, psite; } lin;   // gev_founder_at / gev_founder_counts (gev_lineage.h): the call's positions, the founder counts and their prefix sums, the flag of a bad label, a batch's labels, counts, per-population sums and site records, and the per-tile partials of the last two
     struct RohState { Dev<u64> brk; DevBytes out; Dev<u32> diff, cov; Dev<gev_roh_segment> seg; } roh;   // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records
     struct ListState { Dev<u32> cnt, off; Dev<unsigned long long> tot; } list;                // the record lists of gev_ibd_segments / gev_roh_segments (count_total, fill_list): a strip's or pass's counts per item, their exclusive scan, their 64-bit sum
     struct MateState { Dev<uint8_t> flag; Dev<u32> blk, posm, posf, pickblk, globblk, stat; Dev<double> svf; } mate;   // gev_random_mate and a fused generation's mating (gev_mate.h, enqueue_mate: on the attempt's streams, which the generation's end waits for); globblk is gev_glob_seeds' alone
@@ -4659,6 +4661,130 @@ int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, si
     gev_ibd_segments_fit_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, pairs == GEV_IBD_UPPER, out, capacity, n_total);
     return GEV_OK;
 }
+// ---- founder lineages along the genome (gev_lineage.h) --------------------------------------------
+// what the device calls and the host form refuse of the founder counts and the positions; tab: n_founder_haps[n_pop], then base[n_pop + 1]
+static int lineage_args(const char* who, const uint64_t* pos, size_t n_pos, const uint64_t* n_founder_haps, int n_pop, std::vector<u64>& tab)
+{
+    if (!n_founder_haps) return fail(GEV_EINVAL, "%s: n_founder_haps is null", who);
+    tab.assign(2 * (size_t)n_pop + 1, 0);
+    u64 sum = 0;
+    for (int q = 0; q < n_pop; q++) {
+        if (n_founder_haps[q] > GEV_LINEAGE_MAX_F - sum) return fail(GEV_EUNSUPPORTED, "%s: more than 2^32 - 2 founder haplotypes in all", who);
+        tab[q] = n_founder_haps[q]; tab[n_pop + q] = sum;
+        sum += n_founder_haps[q];
+    }
+    tab[2 * (size_t)n_pop] = sum;
+    if (n_pos && !pos) return fail(GEV_EINVAL, "%s: null positions", who);
+    for (size_t i = 1; i < n_pos; i++)
+        if (pos[i] < pos[i - 1]) return fail(GEV_EINVAL, "%s: the positions decrease at index %zu (%llu behind %llu)", who, i, (unsigned long long)pos[i], (unsigned long long)pos[i - 1]);
+    return GEV_OK;
+}
+// what gev_lineage_check_row found
+static int lineage_labels(const char* who, u32 bad, int n_pop)
+{
+    if (bad & GEV_LINEAGE_BAD_POP) return fail(GEV_EINVAL, "%s: a part names a root population outside [0, %d)", who, n_pop);
+    if (bad & GEV_LINEAGE_BAD_HAP) return fail(GEV_EINVAL, "%s: a part's hap_index is at or beyond the founder haplotypes given for its root population", who);
+    return GEV_OK;
+}
+// n_rows == 0: the per-position outputs of gev_founder_counts
+static void lineage_no_rows(size_t n_pos, size_t F, int n_pop, uint32_t* counts, gev_lineage_site* site, uint32_t* pop_counts)
+{
+    if (counts) memset(counts, 0, n_pos * F * sizeof(u32));
+    if (site) for (size_t p = 0; p < n_pos; p++) site[p] = gev_lineage_empty();
+    if (pop_counts) memset(pop_counts, 0, n_pos * (size_t)n_pop * sizeof(u32));
+}
+// Both calls: at = gev_founder_at (fid alone).  The labels of all rows of the range are checked before anything leaves, so a call of
+// several batches still writes nothing when it is refused.  A batch is the label kernel into c->lin.lab -- which is fid's own layout and
+// leaves through copy_out_block -- or, for the counts, k_lineage_sites over it (and k_lineage_finish over its partials with several tiles).
+static int lineage_run(gev_ctx* c, const char* who, bool at, int pop, int chr, size_t row_begin, size_t n_rows, const uint64_t* pos, size_t n_pos,
+                       const uint64_t* n_founder_haps, uint32_t* fid, uint32_t* counts, gev_lineage_site* site, uint32_t* pop_counts)
+{
+    GEVC(ibd_begin(c, pop, chr, who));
+    PopState& P = c->pop[pop];
+    GEVC(check_range(who, "rows", row_begin, n_rows, 2 * P.n_people));
+    std::vector<u64> tab;
+    const int n_pop = c->n_pop;
+    GEVC(lineage_args(who, pos, n_pos, n_founder_haps, n_pop, tab));
+    const size_t F = (size_t)tab[2 * (size_t)n_pop];
+    if (at && !fid && n_pos && n_rows) return fail(GEV_EINVAL, "%s: fid is null", who);
+    if (n_rows > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: %zu rows in one call", who, n_rows);
+    if (!n_pos) return GEV_OK;
+    if (!n_rows) { if (!at) lineage_no_rows(n_pos, F, n_pop, counts, site, pop_counts); return GEV_OK; }
+    hipStream_t st = c->stream;
+    auto& S = c->lin;
+    const u32* poff = P.st[chr].poff[P.cur]; const gev_part* parts = P.st[chr].parts[P.cur];
+    GEVC(h2d(c, S.tab, tab.data(), tab.size()));
+    GEVC(S.flag.ensure(1, st));
+    HIPC(hipMemsetAsync(S.flag.p, 0, sizeof(u32), st));
+    hipLaunchKernelGGL(k_lineage_check, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, st, poff, parts, (u64)row_begin, (u32)n_rows, (const u64*)S.tab.p, n_pop, S.flag.p);
+    KCHECK();
+    u32 flag = 0;
+    HIPC(hipMemcpyAsync(&flag, S.flag.p, sizeof flag, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    GEVC(lineage_labels(who, flag, n_pop));
+    if (!at && !counts && !site && !pop_counts) return GEV_OK;
+    GEVC(h2d(c, S.pos, pos, n_pos));
+    const u64* d_base = S.tab.p + n_pop;
+    const size_t n_tiles = std::max<size_t>(ceil_div(F, GEV_LINEAGE_TILE), 1);
+    // a batch's positions: about 256 MB of labels and counts, and a grid of k_lineage_sites that fits 31 bits
+    const size_t batch = std::min(std::min(output_chunk(c, 256u << 20, (n_rows + (counts ? F : 0)) * sizeof(u32)), n_pos), (size_t)0x7fffffff / n_tiles);
+    GEVC(S.lab.ensure(batch * n_rows, st));
+    if (!at) {
+        GEVC(S.site.ensure(batch, st));
+        GEVC(S.pop.ensure(batch * n_pop, st));
+        if (counts) GEVC(S.counts.ensure(std::max<size_t>(batch * F, 1), st));
+        if (n_tiles > 1) { GEVC(S.psite.ensure(batch * n_tiles, st)); GEVC(S.ppop.ensure(batch * n_tiles * n_pop, st)); }
+    }
+    for (size_t p0 = 0; p0 < n_pos; p0 += batch) {
+        const size_t nb = std::min(batch, n_pos - p0);
+        hipLaunchKernelGGL(k_lineage_labels, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, st, poff, parts, (u64)row_begin, (u32)n_rows,
+                           (const u64*)S.pos.p + p0, (u32)nb, d_base, S.lab.p);
+        KCHECK();
+        if (at) {
+            GEVC(copy_out_block(c, fid, sizeof(u32), n_rows, p0, 0, nb, n_rows, S.lab.p));
+            HIPC(hipStreamSynchronize(st));
+            continue;
+        }
+        const bool one = n_tiles == 1;
+        hipLaunchKernelGGL(k_lineage_sites, dim3((unsigned)(nb * n_tiles)), dim3(256), 0, st, (const u32*)S.lab.p, (u32)n_rows, d_base, n_pop, (u32)F, (u32)n_tiles,
+                           counts ? S.counts.p : nullptr, one ? S.site.p : S.psite.p, one ? S.pop.p : S.ppop.p);
+        if (!one) hipLaunchKernelGGL(k_lineage_finish, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, st, (const gev_lineage_site*)S.psite.p, (const u32*)S.ppop.p,
+                                     (u32)nb, (u32)n_tiles, n_pop, S.site.p, S.pop.p);
+        KCHECK();
+        const OptOut outs[3] = {{site ? site + p0 : nullptr, sizeof(gev_lineage_site), nb, S.site.p}, {counts && F ? counts + p0 * F : nullptr, sizeof(u32), nb * F, S.counts.p},
+                                {pop_counts ? pop_counts + p0 * n_pop : nullptr, sizeof(u32), nb * n_pop, S.pop.p}};
+        GEVC(copy_back_outs(c, outs));
+    }
+    return GEV_OK;
+}
+int gev_founder_at(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, const uint64_t* pos, size_t n_pos, const uint64_t* n_founder_haps, uint32_t* fid)
+{
+    return lineage_run(c, "founder_at", true, pop, chr, row_begin, n_rows, pos, n_pos, n_founder_haps, fid, nullptr, nullptr, nullptr);
+}
+int gev_founder_counts(gev_ctx* c, int pop, int chr, size_t row_begin, size_t n_rows, const uint64_t* pos, size_t n_pos, const uint64_t* n_founder_haps,
+                       uint32_t* counts, gev_lineage_site* site, uint32_t* pop_counts)
+{
+    return lineage_run(c, "founder_counts", false, pop, chr, row_begin, n_rows, pos, n_pos, n_founder_haps, nullptr, counts, site, pop_counts);
+}
+// the walk and the reductions of gev_lineage.h compiled for the host on lists in host memory: no device, no context
+int gev_dbg_lineage_host(const gev_part* parts, const uint64_t* off, size_t n_rows, const uint64_t* pos, size_t n_pos, const uint64_t* n_founder_haps, int n_pop,
+                         uint32_t* fid, uint32_t* counts, gev_lineage_site* site, uint32_t* pop_counts)
+{
+    const char* who = "dbg_lineage_host";
+    if (n_pop < 1) return fail(GEV_EINVAL, "%s: n_pop is %d", who, n_pop);
+    GEVC(ibd_host_lists(who, parts, off, n_rows, nullptr, nullptr, 0));
+    std::vector<u64> tab;
+    GEVC(lineage_args(who, pos, n_pos, n_founder_haps, n_pop, tab));
+    if (!n_pos) return GEV_OK;
+    const size_t F = (size_t)tab[2 * (size_t)n_pop];
+    if (!n_rows) { lineage_no_rows(n_pos, F, n_pop, counts, site, pop_counts); return GEV_OK; }
+    u32 bad = 0;
+    for (size_t r = 0; r < n_rows; r++) bad |= gev_lineage_check_row(parts + off[r], (uint32_t)(off[r + 1] - off[r]), tab.data(), n_pop);
+    GEVC(lineage_labels(who, bad, n_pop));
+    gev_lineage_host(parts, off, n_rows, pos, n_pos, tab.data() + n_pop, n_pop, fid, counts, site, pop_counts);
+    return GEV_OK;
+}
+unsigned gev_dbg_lineage_tile(void) { return GEV_LINEAGE_TILE; }
 // ---- runs of homozygosity (gev_roh.h) -------------------------------------------------------------
 // what the device calls and the host form refuse of a request (params, the ranges, indices that do not fit a record's 32 bits)
 static int roh_args(const char* who, const gev_roh_params* q, size_t snp_begin, size_t n_snps, size_t L, size_t ind_begin, size_t n_ind, size_t n_people)

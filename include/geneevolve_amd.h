@@ -762,6 +762,52 @@ int gev_ibd_segments(gev_ctx*, int chr, int pop_a, size_t a_begin, size_t n_a, i
  * off_a == off_b; n_a and n_b may differ).  out, capacity and n_total as above. */
 int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
                               uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total);
+/* ---- founder lineages along the genome: local ancestry and lineage counts per position, without a dump (csrc/gev_lineage.h) ---------
+ * The per-position reading of the interval lists.  f_r(x) is taken as in gev_ibd_sharing: the (root_population, hap_index) of the part
+ * of row r with st <= x < en, undefined where no part covers x (parts with st >= en, gaps, rows without parts, positions before the
+ * first part or at or behind the last en cover nothing).  New mutations play no part.  The caller gives n_founder_haps[n_pop] (n_pop
+ * of gev_create): the founder haplotypes of each root population in its own numbering; any count at or above the largest hap_index + 1
+ * is legal.  base[p] is the exclusive prefix sum and F the total; the FOUNDER ID of a covered position is fid = base[root_population] +
+ * hap_index (uint32), GEV_NO_FOUNDER marks an uncovered one; F > 2^32 - 2 is GEV_EUNSUPPORTED.  pos[n_pos] are arbitrary positions in
+ * non-decreasing order (duplicates allowed; an unsorted array is GEV_EINVAL).  GEV_EINVAL with nothing written, raised from a device
+ * flag as gev_ancestry_bp raises its own, when any part of the rows of the range -- covering a position or not -- has a
+ * root_population outside [0, n_pop) or a hap_index >= n_founder_haps[root_population].
+ *
+ * gev_founder_at: fid[p][i] (uint32 [n_pos][n_rows], position-major) = the founder id of row row_begin + i at pos[p].
+ * gev_founder_counts, per position over the rows of the range, each output may be NULL:
+ *   counts[p][f]     (uint32 [n_pos][F])      the rows with founder id f
+ *   site[p]          (gev_lineage_site)       n_covered = the sum of counts, n_lineages = the founders with a non-zero count, sum_sq = the
+ *                                             sum of counts^2, top_count = the largest count, top_founder = the LOWEST fid that has it
+ *                                             (GEV_NO_FOUNDER when n_covered == 0)
+ *   pop_counts[p][q] (uint32 [n_pos][n_pop])  the rows whose covering part has root population q
+ * Plain integers: exact and the same bytes on every run.  n_covered^2 / sum_sq is the founder-genome equivalents at the position and
+ * (sum_sq - n) / (n (n - 1)), n = n_covered, the probability that two distinct covered rows are identical by descent there.
+ * n_rows == 0 writes zeros (a zeroed site with top_founder = GEV_NO_FOUNDER) into the per-position outputs of gev_founder_counts and
+ * touches nothing else; n_pos == 0 touches nothing.
+ *
+ * Store and sum, no adds into global memory: a label kernel (one thread per row, the lanes of a wave stepping through the sorted
+ * positions together, each with its own part cursor placed by bisection) stores fid[p][row]; a second kernel, one workgroup per
+ * (position, tile of gev_dbg_lineage_tile() founders), counts the position's labels in on-chip bins and reduces them; with several
+ * tiles a small third kernel folds the tiles' partial records in tile order.  The positions go in batches of about 256 MB of labels
+ * (gev_dbg_output_chunk caps a batch's positions); the labels, and the counts when asked for, live in scratch the context owns,
+ * created by the first call.  Both calls begin as gev_ibd_sharing (a pending order is materialised, the CSR lists are derived if need
+ * be), so they work after gev_migrate, after an import and on contexts without genotype planes, return its GEV_ESTATE refusals with
+ * the same messages (interval tracking off, an inactive chromosome, a population without a current generation, a generation pending)
+ * and return only when the results are in the caller's memory.  GEV_EINVAL for a range beyond 2 * n_people, a NULL n_founder_haps, a
+ * NULL pos with n_pos > 0, a NULL fid with something to write. */
+#define GEV_NO_FOUNDER 0xffffffffu
+typedef struct gev_lineage_site { uint64_t sum_sq; uint32_t n_covered, n_lineages, top_count, top_founder; } gev_lineage_site; /* 24 bytes */
+int gev_founder_at(gev_ctx*, int pop, int chr, size_t row_begin, size_t n_rows, const uint64_t* pos, size_t n_pos,
+                   const uint64_t* n_founder_haps /*[n_pop]*/, uint32_t* fid /* [n_pos][n_rows], position-major */);
+int gev_founder_counts(gev_ctx*, int pop, int chr, size_t row_begin, size_t n_rows, const uint64_t* pos, size_t n_pos,
+                       const uint64_t* n_founder_haps, uint32_t* counts /*[n_pos][F]*/, gev_lineage_site* site /*[n_pos]*/,
+                       uint32_t* pop_counts /*[n_pos][n_pop]*/);
+/* the same walk and reductions (csrc/gev_lineage.h) compiled for the host on lists in host memory as gev_download_intervals returns them
+ * (off: n_rows + 1 entries; along a row neither st nor en decreases), with the same refusals of the positions, the founder counts and
+ * the labels: no device, no context.  fid as gev_founder_at's, the others as gev_founder_counts'; each may be NULL. */
+int gev_dbg_lineage_host(const gev_part* parts, const uint64_t* off, size_t n_rows, const uint64_t* pos, size_t n_pos,
+                         const uint64_t* n_founder_haps, int n_pop, uint32_t* fid, uint32_t* counts, gev_lineage_site* site, uint32_t* pop_counts);
+unsigned gev_dbg_lineage_tile(void);   /* founder bins a workgroup histograms at once (tests place a population across that edge) */
 /* ---- runs of homozygosity: F_ROH, islands and the run list without a dump (csrc/gev_roh.h) -----------------------------------------
  * The observed side of what gev_ibd_sharing gives from the ancestry: for individual i of (pop, chr) and the SNPs [snp_begin, +n_snps),
  * hom(j) is true when haplotype rows 2i and 2i+1 carry the same allele at SNP j of the current generation (new mutations applied as
