@@ -200,6 +200,8 @@ ABI = {
     "dbg_ibd_host": "int: part* u64* size part* u64* size u64 u64* u32* u64*",
     "ibd_segments": "int: ctx* int int size size int size size u64 int ibd_segment* size u64*",
     "dbg_ibd_segments_host": "int: part* u64* size part* u64* size u64 int ibd_segment* size u64*",
+    "identity_states": "int: ctx* int int size size int size size u64*",
+    "dbg_identity_host": "int: part* u64* size part* u64* size u64*",
     "founder_at": "int: ctx* int int size size u64* size u64* u32*",
     "founder_counts": "int: ctx* int int size size u64* size u64* u32* lineage_site* u32*",
     "dbg_lineage_host": "int: part* u64* size u64* size u64* int u32* u32* lineage_site* u32*",
@@ -587,6 +589,18 @@ class GevLibrary:
         parts_b = parts_a if parts_b is None else _arr(parts_b, PART_DTYPE); off_b = off_a if off_b is None else _arr(off_b, np.uint64)
         f, pairs = self._f("dbg_ibd_segments_host"), IBD_UPPER if upper else IBD_ALL_PAIRS
         return _record_list(lambda out, cap, n: self.check(f(parts_a, off_a, len(off_a) - 1, parts_b, off_b, len(off_b) - 1, int(min_bp), pairs, out, cap, n)), SEGMENT_DTYPE)
+
+    def dbg_identity_host(self, parts_a, off_a, parts_b=None, off_b=None):
+        """uint64 [9][n_a][n_b]: the base pairs in each of Jacquard's nine identity states of every pair of individuals of two sets of
+        interval lists, by the library's four-cursor walk compiled for the host (no device needed).  parts_* / off_*: as
+        download_intervals returns them (off: 2 * individuals + 1 entries, rows 2i and 2i+1 are individual i; side b None: side a again)"""
+        parts_a = _arr(parts_a, PART_DTYPE); off_a = _arr(off_a, np.uint64)
+        parts_b = parts_a if parts_b is None else _arr(parts_b, PART_DTYPE); off_b = off_a if off_b is None else _arr(off_b, np.uint64)
+        assert len(off_a) % 2 == 1 and len(off_b) % 2 == 1, "two rows per individual: an odd number of offsets"
+        n_a, n_b = (len(off_a) - 1) // 2, (len(off_b) - 1) // 2
+        bp = np.empty((9, n_a, n_b), dtype=np.uint64)
+        self.check(self._f("dbg_identity_host")(parts_a, off_a, n_a, parts_b, off_b, n_b, bp))
+        return bp
 
     def dbg_lineage_host(self, parts, off, pos, n_founder_haps, want=("fid", "counts", "site", "pop_counts")):
         """(fid, counts, site, pop_counts) as GevContext.founder_at and founder_counts give them, by the library's walk and reductions
@@ -1293,6 +1307,19 @@ class GevContext:
         n_b = self._rest_ind(pop_b, b_begin, n_b, 2)
         pairs = IBD_UPPER if upper else IBD_ALL_PAIRS
         return _record_list(lambda out, cap, n: self._call("ibd_segments", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, int(min_bp), pairs, out, cap, n), SEGMENT_DTYPE)
+
+    def identity_states(self, chr, pop_a, a_begin=0, n_a=None, pop_b=None, b_begin=0, n_b=None):
+        """-> uint64 [9][n_a][n_b]: for individual a_begin + i of pop_a against individual b_begin + k of pop_b (None: pop_a), plane s - 1 =
+        the base pairs of the chromosome at which the four haplotypes are in Jacquard's condensed identity state s (all four covered):
+        1 all four IBD, 2 each autozygous, 3 / 4 a autozygous with / without sharing, 5 / 6 b likewise, 7 both pairs across, 8 one
+        pair across, 9 nothing shared.  Walked on the device from the ancestry interval lists (works without genotype planes);
+        identity.py has the statistics"""
+        pop_b = pop_a if pop_b is None else pop_b
+        n_a = self._rest_ind(pop_a, a_begin, n_a)
+        n_b = self._rest_ind(pop_b, b_begin, n_b)
+        bp = np.empty((9, max(n_a, 0), max(n_b, 0)), dtype=np.uint64)
+        self._call("identity_states", chr, pop_a, a_begin, n_a, pop_b, b_begin, n_b, bp)
+        return bp
 
     def founder_at(self, pop, chr, pos, row_begin=0, n_rows=None, n_founder_haps=None):
         """-> fid uint32 [n_pos][n_rows]: the founder id of haplotype row row_begin + i at pos[p] (uint64, non-decreasing): base[root

@@ -29,6 +29,7 @@
 #include "gev_traitsum.h"
 #include "gev_indscore.h"
 #include "gev_ibd.h"
+#include "gev_identity.h"
 #include "gev_lineage.h"
 #include "gev_roh.h"
 #include "gev_select.h"
@@ -373,7 +374,7 @@ struct gev_ctx {
     } bp;
     struct DigitProdState { Dev<int32_t> val, acc; Dev<uint4> b; Dev<long long> out; } dp;   // gev_snp_trait_sums and gev_ind_scores (gev_digitprod.h), one set for both under the rule above: the columns (quanta, weights), their operand bytes, the i32 partials and the 64-bit sums of a block of rows
     struct SnpCountState { Dev<u32> cnt; } snp;                                               // gev_snp_genotype_counts (gev_snpcount.h): the two count vectors of a call
-    struct IbdState { DevBytes out; Dev<u32> flag; Dev<gev_ibd_segment> seg; } ibd;           // gev_ibd_sharing / gev_ancestry_bp / gev_ibd_segments (gev_ibd.h): a sub-block's results, the flag of a bad root population, a strip's records
+    struct IbdState { DevBytes out; Dev<u32> flag; Dev<gev_ibd_segment> seg; Dev<u64> planes; } ibd;   // gev_ibd_sharing / gev_ancestry_bp / gev_ibd_segments (gev_ibd.h): a sub-block's results, the flag of a bad root population, a strip's records; gev_identity_states (gev_identity.h): a sub-block's nine planes
     struct LineageState { Dev<u64> pos, tab; Dev<u32> flag, lab, counts, pop, ppop; Dev<gev_lineage_site> site, psite; } lin;   // gev_founder_at / gev_founder_counts (gev_lineage.h): the call's positions, the founder counts and their prefix sums, the flag of a bad label, a batch's labels, counts, per-population sums and site records, and the per-tile partials of the last two
     struct RohState { Dev<u64> brk; DevBytes out; Dev<u32> diff, cov; Dev<gev_roh_segment> seg; } roh;   // gev_roh_summary / gev_roh_segments (gev_roh.h): the break bit plane, the per-individual results, the cover's difference array and its scan, a pass's records
     struct ListState { Dev<u32> cnt, off; Dev<unsigned long long> tot; } list;                // the record lists of gev_ibd_segments / gev_roh_segments (count_total, fill_list): a strip's or pass's counts per item, their exclusive scan, their 64-bit sum
@@ -4659,6 +4660,46 @@ int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, si
     if (pairs == GEV_IBD_UPPER && (parts_a != parts_b || off_a != off_b)) return fail(GEV_EINVAL, "%s: GEV_IBD_UPPER takes the same lists on both sides", who);
     if (n_a > 0xffffffffull || n_b > 0xffffffffull) return fail(GEV_EUNSUPPORTED, "%s: rows beyond 2^32 - 1 do not fit a record", who);
     gev_ibd_segments_fit_host(parts_a, off_a, n_a, parts_b, off_b, n_b, min_bp, pairs == GEV_IBD_UPPER, out, capacity, n_total);
+    return GEV_OK;
+}
+// ---- identity states per pair of individuals (gev_identity.h) -------------------------------------
+// The pair matrix is walked in sub-blocks of at most 2048 individuals a side (gev_dbg_output_chunk caps them): a sub-block is one launch
+// of k_identity_tiles into the nine planes of c->ibd.planes, each copied into its plane of the caller's before the next one's kernel runs.
+int gev_identity_states(gev_ctx* c, int chr, int pop_a, size_t a_begin, size_t n_a, int pop_b, size_t b_begin, size_t n_b, uint64_t* bp)
+{
+    const char* who = "identity_states";
+    GEVC(ibd_begin(c, pop_a, chr, who));
+    if (pop_b != pop_a) GEVC(ibd_begin(c, pop_b, chr, who));
+    PopState &PA = c->pop[pop_a], &PB = c->pop[pop_b];
+    GEVC(check_range(who, "individuals (a)", a_begin, n_a, PA.n_people));
+    GEVC(check_range(who, "individuals (b)", b_begin, n_b, PB.n_people));
+    if (!n_a || !n_b) return GEV_OK;
+    if (!bp) return fail(GEV_EINVAL, "%s: bp is null", who);
+    hipStream_t st = c->stream;
+    const u32* poff_a = PA.st[chr].poff[PA.cur]; const gev_part* parts_a = PA.st[chr].parts[PA.cur];
+    const u32* poff_b = PB.st[chr].poff[PB.cur]; const gev_part* parts_b = PB.st[chr].parts[PB.cur];
+    const size_t blk = std::min<size_t>(output_chunk(c, (size_t)1 << 30, 1), 2048), ba = std::min(blk, n_a), bb = std::min(blk, n_b);
+    GEVC(c->ibd.planes.ensure(GEV_IDN_STATES * ba * bb, st));
+    for (size_t ia = 0; ia < n_a; ia += blk)
+        for (size_t ib = 0; ib < n_b; ib += blk) {
+            const size_t na = std::min(blk, n_a - ia), nb = std::min(blk, n_b - ib);
+            hipLaunchKernelGGL(k_identity_tiles, dim3((unsigned)ceil_div(nb, GEV_IDN_TILE), (unsigned)ceil_div(na, GEV_IDN_TILE)), dim3(256), 0, st,
+                               poff_a, parts_a, (u64)(a_begin + ia), (u32)na, poff_b, parts_b, (u64)(b_begin + ib), (u32)nb, c->ibd.planes.p);
+            KCHECK();
+            for (size_t q = 0; q < GEV_IDN_STATES; q++) GEVC(copy_out_block(c, bp + q * n_a * n_b, sizeof(u64), n_b, ia, ib, na, nb, c->ibd.planes.p + q * na * nb));
+            HIPC(hipStreamSynchronize(st));
+        }
+    return GEV_OK;
+}
+// the walk of gev_identity.h compiled for the host on lists in host memory: no device, no context
+int gev_dbg_identity_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b, uint64_t* bp)
+{
+    const char* who = "dbg_identity_host";
+    if (n_a > SIZE_MAX / 2 || n_b > SIZE_MAX / 2) return fail(GEV_EINVAL, "%s: %zu x %zu individuals", who, n_a, n_b);
+    GEVC(ibd_host_lists(who, parts_a, off_a, 2 * n_a, parts_b, off_b, 2 * n_b));
+    if (!n_a || !n_b) return GEV_OK;
+    if (!bp) return fail(GEV_EINVAL, "%s: bp is null", who);
+    gev_identity_host(parts_a, off_a, n_a, parts_b, off_b, n_b, bp);
     return GEV_OK;
 }
 // ---- founder lineages along the genome (gev_lineage.h) --------------------------------------------

@@ -762,6 +762,40 @@ int gev_ibd_segments(gev_ctx*, int chr, int pop_a, size_t a_begin, size_t n_a, i
  * off_a == off_b; n_a and n_b may differ).  out, capacity and n_total as above. */
 int gev_dbg_ibd_segments_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a, const gev_part* parts_b, const uint64_t* off_b, size_t n_b,
                               uint64_t min_bp, int pairs, gev_ibd_segment* out, size_t capacity, uint64_t* n_total);
+/* ---- identity states per pair of individuals: Jacquard's nine, IBD0 / IBD1 / IBD2 and fraternity without a dump (csrc/gev_identity.h) --
+ * The per-pair reading of the interval lists at the level of individuals.  f_r(x) is taken as in gev_ibd_sharing: the (root_population,
+ * hap_index) of the part of row r with st <= x < en, labels compared whole, undefined where nothing covers x.  New mutations play no
+ * part.  For individual a_begin + i of pop_a (rows 2i, 2i+1 = a0, a1) against individual b_begin + k of pop_b (rows 2k, 2k+1 = b0, b1)
+ * a position counts only where all four rows are covered.  There the equalities among the four labels are a partition of
+ * {a0, a1, b0, b1}, one of 15; as restricted-growth strings in the order a0 a1 b0 b1 they are Jacquard's condensed identity states
+ *   D1 0000                  all four IBD
+ *   D2 0011                  each autozygous, different founders
+ *   D3 0001 0010             a autozygous, shared with one haplotype of b
+ *   D4 0012                  a autozygous, b's two distinct, nothing shared
+ *   D5 0100 0111             b autozygous, shared with one haplotype of a
+ *   D6 0122                  b autozygous, nothing shared
+ *   D7 0101 0110             both of a's haplotypes IBD with b's, pairwise
+ *   D8 0102 0120 0112 0121   exactly one pair across
+ *   D9 0123                  nothing shared
+ * bp[s][i][k] (uint64, plane-major [9][n_a][n_b], plane s - 1 for Ds) = the base pairs of the chromosome in state Ds.  Plain 64-bit
+ * integers: exact and the same bytes on every run.  The nine planes sum to the length along which all four rows are covered.  The
+ * ranges may overlap, coincide or lie in different populations; an individual against itself is D1 where it is autozygous and D7
+ * elsewhere; swapping the sides swaps D3 with D5 and D4 with D6.  Kinship is (4 D1 + 2 (D3 + D5 + D7) + D8) / (4 sum), IBD2 = D1 + D7,
+ * IBD1 = D3 + D5 + D8, IBD0 = D2 + D4 + D6 + D9 (geneevolve_amd/identity.py).
+ * a_begin, n_a, b_begin, n_b count INDIVIDUALS.  One workgroup takes a tile of 16 x 16 pairs of individuals, one pair per lane, each
+ * lane walking its four lists with four cursors where they lie; nothing bounds a row's length.  Begins as gev_ibd_sharing, for both
+ * populations (a pending order is materialised, the CSR lists are derived if need be), so it works after gev_migrate, after an import
+ * and on contexts without genotype planes, returns its GEV_ESTATE refusals with the same messages and returns only when the results
+ * are in the caller's memory.  GEV_EINVAL for a range beyond n_people and for a NULL bp with something to write; n_a == 0 or
+ * n_b == 0 touches nothing.  The results leave in sub-blocks of at most 2048 individuals a side (gev_dbg_output_chunk caps them), nine
+ * planes in scratch the context owns, created by the first call. */
+int gev_identity_states(gev_ctx*, int chr, int pop_a, size_t a_begin, size_t n_a,
+                        int pop_b, size_t b_begin, size_t n_b, uint64_t* bp /* [9][n_a][n_b] */);
+/* the same walk (csrc/gev_identity.h) compiled for the host on lists in host memory as gev_download_intervals returns them, with the
+ * refusals of gev_dbg_ibd_host: no device, no context.  n_a, n_b count individuals: off_* has 2 n_* + 1 entries, rows 2i and 2i+1 are
+ * individual i; along a row neither st nor en decreases.  bp as above. */
+int gev_dbg_identity_host(const gev_part* parts_a, const uint64_t* off_a, size_t n_a,
+                          const gev_part* parts_b, const uint64_t* off_b, size_t n_b, uint64_t* bp);
 /* ---- founder lineages along the genome: local ancestry and lineage counts per position, without a dump (csrc/gev_lineage.h) ---------
  * The per-position reading of the interval lists.  f_r(x) is taken as in gev_ibd_sharing: the (root_population, hap_index) of the part
  * of row r with st <= x < en, undefined where no part covers x (parts with st >= en, gaps, rows without parts, positions before the
